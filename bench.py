@@ -8,7 +8,11 @@ Metric (BASELINE.json): QPS at recall@10 >= 0.95 on SIFT1M — config C2: N=1e6,
 A "step" = one pass of the search hot path (coarse quantizer -> list ranking -> exact top-k) over one batch of NQ
 queries that are already resident in HBM.  value = queries/s over the timed steps at BASELINE's nprobe (32).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up (data, index build, load), runs W untimed + K timed steps and prints the result line; with
+--dump-outputs DIR it also writes what the last timed step returned (DIR/distances.npy f32, DIR/ids.npy f64, nq x k;
+above 64 MB in all, a fixed seeded sample of the query rows, whose row numbers go to DIR/rows.npy).
 
 N > 1 (launched by torch.distributed.run, one rank per GPU): the same index is partitioned over the ranks (stripes:
 block b of every list on rank b % N; or --placement shards: whole shard files, greedy by bytes), the coarse step is
@@ -16,10 +20,11 @@ split over the ranks by query (one all-gather of the probe lists), every rank ra
 owns, the per-rank top-k are exchanged with ONE all-gather over RCCL and merged with the reference's stable candidate
 order.  Total work is fixed => "scaling": "strong".
 
-Prints ONE JSON line (rank 0).  Besides the contract's fields it carries: roofline (dominant kernel, measured live with
-HIP events on the library's stream), cpu_baseline (the oracle on the host cores, bounded sample), and `extras`: the
-smallest nprobe reaching recall 0.95, the host-pointer entry, small-batch latencies, real-valued data (bf16 x 3 ranking),
-config C1 on the CPU path and on the GPU, the k-means lines (C3 exact assign, update pass, reference-compat train).
+Prints ONE JSON line (rank 0).  With --full it also carries: the recall of every nprobe of the sweep against exact
+ground truth, roofline (dominant kernel, measured live with HIP events on the library's stream), cpu_baseline (the oracle
+on the host cores, bounded sample), and `extras`: the smallest nprobe reaching recall 0.95, the host-pointer entry,
+small-batch latencies, real-valued data (bf16 x 3 ranking), config C1 on the CPU path and on the GPU, the k-means lines
+(C3 exact assign, update pass, reference-compat train).  The --no-* options trim a --full run.
 """
 import argparse
 import json
@@ -102,6 +107,27 @@ def recalls(I, gt):
     return r1, inter
 
 
+DUMP_CAP_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """the (nq, k) result tensors of one step as <out_dir>/<name>.npy: float32 stays float32, integers become float64
+    (exact: ids < 2^53).  Above DUMP_CAP_BYTES in all, every array keeps the same fixed, seeded sample of query rows,
+    whose row numbers go to rows.npy."""
+    host = {name: t.cpu().numpy() for name, t in arrays.items()}
+    host = {name: a if a.dtype == np.float32 else a.astype(np.float64) for name, a in host.items()}
+    nq = next(iter(host.values())).shape[0]
+    row_bytes = sum(a[:1].nbytes for a in host.values())
+    os.makedirs(out_dir, exist_ok=True)
+    if nq * row_bytes > DUMP_CAP_BYTES:
+        keep = (DUMP_CAP_BYTES - 4096) // (row_bytes + 8)  # 4 KB left for the .npy headers
+        rows = np.sort(np.random.default_rng(0).choice(nq, keep, replace=False))
+        host = {name: a[rows] for name, a in host.items()}
+        np.save(os.path.join(out_dir, "rows.npy"), rows.astype(np.float64))
+    for name, a in host.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+
+
 def time_steps(fn, steps, warmup, barrier, world, device):
     """W untimed + exactly K timed steps, bracketed by barrier + synchronize; MAX over the ranks"""
     import torch
@@ -173,7 +199,13 @@ def main():
     ap.add_argument("--no-extras", action="store_true")
     ap.add_argument("--assign-n", type=int, default=10_000_000)
     ap.add_argument("--work-dir", default=None)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the results of the last timed step as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also the recall sweep, roofline, extras, k-means lines and CPU baselines")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     import torch
     import torch.distributed as dist
@@ -291,65 +323,76 @@ def main():
         return Im
 
     # ---- recall at every operating point of the sweep (scripts/run_faiss_bench.sh:55) -----------------
-    if gt is None:
-        gt = ground_truth(xb, xq, k)
     sweep = {}
     min_ok = None
-    for p in sorted({1, 2, 4, 8, 16, 32, 64, args.nprobe}):
-        r1, ri = recalls(step(p), gt)
-        sweep[p] = {"recall_1nn_at_k": round(r1, 4), "recall_at_k": round(ri, 4)}
-        if min_ok is None and ri >= 0.95:
-            min_ok = p
+    if args.full:
+        if gt is None:
+            gt = ground_truth(xb, xq, k)
+        for p in sorted({1, 2, 4, 8, 16, 32, 64, args.nprobe}):
+            r1, ri = recalls(step(p), gt)
+            sweep[p] = {"recall_1nn_at_k": round(r1, 4), "recall_at_k": round(ri, 4)}
+            if min_ok is None and ri >= 0.95:
+                min_ok = p
     head = args.nprobe
 
     # ---- timed region: the headline operating point ---------------------------------------------------
-    # Inside the timed region the library records HIP events around the dominant kernel only (the list rank: what the
-    # roofline is priced on); an event at every phase boundary is five barrier packets per step, 0.01 ms of 0.5.  The
-    # phase breakdown comes from a few more steps right after, outside the timed region.
+    # With --full, the library records HIP events around the dominant kernel only inside the timed region (the list rank:
+    # what the roofline is priced on); an event at every phase boundary is five barrier packets per step, 0.01 ms of 0.5.
+    # The phase breakdown comes from a few more steps right after, outside the timed region.  A plain run records none.
     scan_ms, coarse_ms, group_ms, sel_ms, tot_ms = [], [], [], [], []
-    index.enable_timing(2)
+    if args.full:
+        index.enable_timing(2)
 
-    def timed_step():
-        step(head)
-        scan_ms.append(index.last_stat("ms_scan"))
+        def timed_step():
+            step(head)
+            scan_ms.append(index.last_stat("ms_scan"))
+    else:
+        index.enable_timing(False)
+
+        def timed_step():
+            step(head)
     elapsed = time_steps(timed_step, args.steps, args.warmup, barrier, world, device)
-    scan_ms = scan_ms[args.warmup:]
-    st = index.last_stats()
     ms_per_step = elapsed * 1000.0 / args.steps
     qps = nq * args.steps / elapsed
-    index.enable_timing(True)
-    for i in range(2 + max(3, args.steps // 2)):
-        step(head)
-        sp = index.last_stats()
-        if i >= 2:
-            coarse_ms.append(sp["ms_coarse"]); group_ms.append(sp["ms_group"]); sel_ms.append(sp["ms_merge"]); tot_ms.append(sp["ms_total"])
-    roofline = roofline_of(st, float(np.mean(scan_ms)), d)
-    roofline["pipeline_ms"] = {"coarse": round(float(np.mean(coarse_ms)), 4), "grouping": round(float(np.mean(group_ms)), 4),
-                               "list_rank": round(float(np.mean(scan_ms)), 4), "select": round(float(np.mean(sel_ms)), 4),
-                               "total": round(float(np.mean(tot_ms)), 4),
-                               "note": "list_rank: HIP events inside the timed region; the other phases from steps run right after it "
-                                       "with an event at every phase boundary"}
-    # algorithmic bytes of one launch: the resident image streamed once + the queries + the records written
-    image_bytes = index.num_vectors * d * (2 if int(st["rank_mode"]) == 3 else (4 if int(st["rank_mode"]) == 2 else 4))
-    algo_bytes = image_bytes + nq * d * 4 + st["filter_tile_blocks"] * 8 * 2 * (int(st["group_queries"]) or 128)
-    scan_s = float(np.mean(scan_ms)) / 1000.0
-    roofline["algorithmic_bytes_per_launch"] = int(algo_bytes)
-    roofline["frac_hbm_algorithmic"] = round(algo_bytes / scan_s / 1e9 / HBM_PEAK_GBS, 4) if scan_s > 0 else None
-    # HBM-side traffic of that kernel from the committed PMC passes (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE of this same
-    # command; gfx950 correction as MI355X_MICROARCH.md prescribes), when they were taken on this workload and kernel
-    try:
-        tr = json.load(open(TRAFFIC_FILE))
-        if tr["workload"] == [args.n, d, args.nlist, head, nq, k] and world == 1 and tr.get("rank_mode") == int(st["rank_mode"]):
-            roofline["traffic"] = tr["hbm_bytes_per_launch"]
-            roofline["traffic_source"] = tr["source"]
-            roofline["frac_hbm_traffic"] = round(tr["hbm_bytes_per_launch"] / scan_s / 1e9 / HBM_PEAK_GBS, 4)
-            roofline["traffic_over_algorithmic"] = round(tr["hbm_bytes_per_launch"] / algo_bytes, 2)
-    except Exception:
-        pass
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"distances": D if world == 1 else Dm, "ids": I if world == 1 else Im})
+    roofline = None
+    if args.full:
+        scan_ms = scan_ms[args.warmup:]
+        st = index.last_stats()
+        index.enable_timing(True)
+        for i in range(2 + max(3, args.steps // 2)):
+            step(head)
+            sp = index.last_stats()
+            if i >= 2:
+                coarse_ms.append(sp["ms_coarse"]); group_ms.append(sp["ms_group"]); sel_ms.append(sp["ms_merge"]); tot_ms.append(sp["ms_total"])
+        roofline = roofline_of(st, float(np.mean(scan_ms)), d)
+        roofline["pipeline_ms"] = {"coarse": round(float(np.mean(coarse_ms)), 4), "grouping": round(float(np.mean(group_ms)), 4),
+                                   "list_rank": round(float(np.mean(scan_ms)), 4), "select": round(float(np.mean(sel_ms)), 4),
+                                   "total": round(float(np.mean(tot_ms)), 4),
+                                   "note": "list_rank: HIP events inside the timed region; the other phases from steps run right after it "
+                                           "with an event at every phase boundary"}
+        # algorithmic bytes of one launch: the resident image streamed once + the queries + the records written
+        image_bytes = index.num_vectors * d * (2 if int(st["rank_mode"]) == 3 else (4 if int(st["rank_mode"]) == 2 else 4))
+        algo_bytes = image_bytes + nq * d * 4 + st["filter_tile_blocks"] * 8 * 2 * (int(st["group_queries"]) or 128)
+        scan_s = float(np.mean(scan_ms)) / 1000.0
+        roofline["algorithmic_bytes_per_launch"] = int(algo_bytes)
+        roofline["frac_hbm_algorithmic"] = round(algo_bytes / scan_s / 1e9 / HBM_PEAK_GBS, 4) if scan_s > 0 else None
+        # HBM-side traffic of that kernel from the committed PMC passes (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE of this same
+        # command, with the gfx950 FETCH_SIZE correction), when they were taken on this workload and kernel
+        try:
+            tr = json.load(open(TRAFFIC_FILE))
+            if tr["workload"] == [args.n, d, args.nlist, head, nq, k] and world == 1 and tr.get("rank_mode") == int(st["rank_mode"]):
+                roofline["traffic"] = tr["hbm_bytes_per_launch"]
+                roofline["traffic_source"] = tr["source"]
+                roofline["frac_hbm_traffic"] = round(tr["hbm_bytes_per_launch"] / scan_s / 1e9 / HBM_PEAK_GBS, 4)
+                roofline["traffic_over_algorithmic"] = round(tr["hbm_bytes_per_launch"] / algo_bytes, 2)
+        except Exception:
+            pass
 
     extras = {}
     # ---- multi-GPU: how the scan work splits under the two placements (share of the busiest rank) ----
-    if world > 1:
+    if args.full and world > 1:
         sv = torch.tensor([float(st["scanned_vectors"])], dtype=torch.float64, device=device)
         allsv = [torch.zeros_like(sv) for _ in range(world)]
         dist.all_gather(allsv, sv)
@@ -372,7 +415,7 @@ def main():
         extras["scan_share_of_busiest_rank"][other] = round(max(float(x.item()) for x in allsv2) / max(tot2, 1.0), 4)
         del alt
 
-    if rank == 0 and world == 1 and not args.no_extras:
+    if args.full and rank == 0 and world == 1 and not args.no_extras:
         # (a) the smallest nprobe of the sweep reaching recall@10 >= 0.95, timed the same way
         if min_ok is not None and min_ok != head:
             e = time_steps(lambda: step(min_ok), args.steps, args.warmup, barrier, world, device)
@@ -476,7 +519,7 @@ def main():
 
     # ---- second BASELINE metric: k-means on the matrix cores (config C3) ---------------------------
     kmeans = None
-    if rank == 0 and world == 1 and not args.no_kmeans:
+    if args.full and rank == 0 and world == 1 and not args.no_kmeans:
         del xb
         torch.cuda.empty_cache()
         n3, d3, k3 = args.assign_n, 128, 16384
@@ -580,7 +623,7 @@ def main():
     # ---- CPU baseline: the oracle (C restatement of the reference's CPU path) on the host cores -------
     cpu = None
     c1 = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         import oracle_lib as O
         orc = O.OracleIndex.load(os.path.join(work, "index"), os.path.join(work, "shards"))
         threads = min(O.lib().orc_max_threads(), O.usable_cpus())
@@ -639,11 +682,12 @@ def main():
                "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
                "scaling": "strong" if world > 1 else "weak", "vs_baseline": None, "dtype": "f32", "data": data,
                "config": {"workload": f"IVF search N={args.n} D={d} nlist={args.nlist} nprobe={head} k={k} nq/step={nq} "
-                                      "(BASELINE configs[1])", "nprobe": head, "recall": sweep[head], "nprobe_sweep": sweep,
+                                      "(BASELINE configs[1])", "nprobe": head,
+                          **({"recall": sweep[head], "nprobe_sweep": sweep} if args.full else {}),
                           "index_centroids": index.num_centroids, "build": build,
                           "parallelism": (f"{args.placement} over {world} GPUs, coarse table replicated, coarse step split by query, "
                                           "RCCL all-gather of probe lists and of per-rank top-k") if world > 1 else "1 GPU"},
-               "roofline": roofline, "cpu_baseline": cpu, "kmeans_assign": kmeans, "extras": extras}
+               **({"roofline": roofline, "cpu_baseline": cpu, "kmeans_assign": kmeans, "extras": extras} if args.full else {})}
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.destroy_process_group()
