@@ -322,6 +322,7 @@ typedef struct vi_search_stats {
                                   5 / 6 = 2 / 4 with the images taken about the mean of the stored vectors (real-valued
                                   lists far from the origin: the margins scale with the spread, not the offset) */
   uint64_t group_queries;      /* MFMA path: queries per rank work item (128, or 32 when lists are probed by few) */
+  uint64_t rank_int8;          /* 1: the list rank multiplied int8 images (8-bit descriptors, integer queries in 0..254; rank_mode 3) */
 } vi_search_stats;
 /* phases of the most recent build on this handle (wall-clock ms): the points are uploaded once; k-means, the grouping of
  * ids by list, the shard export and the resident index all work from that device copy */

@@ -63,6 +63,6 @@ print(json.dumps({"workload": [a.n, a.d, a.nlist, a.nprobe, a.nq, a.k], "steps":
                   "ms_per_step_wall": round(wall * 1e3, 4), "queries_per_s": round(a.nq / wall, 1),
                   "pipeline_ms": {"total": round(float(m[0]), 4), "coarse": round(float(m[1]), 4), "grouping": round(float(m[2]), 4),
                                   "list_rank": round(float(m[3]), 4), "select": round(float(m[4]), 4)},
-                  "rank_mode": int(st["rank_mode"]), "scanned_vectors": int(st["scanned_vectors"]),
+                  "rank_mode": int(st["rank_mode"]), "rank_int8": int(st["rank_int8"]), "scanned_vectors": int(st["scanned_vectors"]),
                   "search_launches_in_trace": a.warmup + a.steps}), flush=True)
 shutil.rmtree(work, ignore_errors=True)

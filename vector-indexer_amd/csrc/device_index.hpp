@@ -74,6 +74,7 @@ struct SearchWorkspace {
   DevBuf<float> gval;                       // group records: 4 smallest sub-block minima per (query, probe, segment, lane half)
   DevBuf<uint32_t> gpos;                    // ... and where each record belongs (probe rank | segment | lane half)
   DevBuf<uint32_t> qimg;                    // wide vectors: query-major bf16 hi/lo image of the batch
+  DevBuf<uint32_t> qimg8;                   // int8 image of the batch (q - 127), when the lists have one (split_queries_kernel)
   DevBuf<float> brec;                       // pair records: the 4 sub-block minima of two blocks per (record tile, lane half, query of the group)
   struct GqHint { uint64_t nq; uint32_t P, gq; };
   std::vector<GqHint> gq_hint;              // queries per rank work item measured to suit a batch shape (filter_search.hip)
@@ -103,6 +104,12 @@ struct DeviceIndex {
   DevBuf<uint32_t> lists_bf16, cent_bf16;  // bf16 hi/lo images of the blocks for the MFMA ranking (filter_search.hip)
   DevBuf<uint32_t> lists_u8_nat;           // 8-bit descriptors (integers 0..255): one byte per dimension, same order (exact re-evaluation)
   DevBuf<uint32_t> lists_hi_nat;           // bf16-exact lists: their hi plane in the blocks' own vector order (exact re-evaluation)
+  // 8-bit descriptors, D <= 128: int8 image 127 - v of the lists (block and column order of the bf16 image), h(v) =
+  // ceil(|v - 127|^2 / 2) in image-column order, the frame's centre (dim x 127.0f) and max |v - 127|^2 (rank_stream_i8_kernel)
+  DevBuf<uint32_t> lists_i8;
+  DevBuf<int> i8_norm_img;
+  DevBuf<float> i8_centre;
+  float i8_xmax2 = 0.0f;
   bool lists_lo_zero = false, cent_lo_zero = false;  // every stored value is bf16-exact (lo planes all zero)
   // sampled means over the stored vectors: ||v - centroid of its list||^2 and ||v||^2 (what the ranking arithmetic of
   // real-valued lists is chosen by: filter_search.hip, rank_approx_mode)

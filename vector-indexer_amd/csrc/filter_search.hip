@@ -58,7 +58,7 @@ vi_status stage_coarse(const DeviceIndex &ix, const float *Qd, uint64_t nq, uint
 vi_status adopt_probes(const DeviceIndex &ix, uint64_t nq, uint32_t P, const uint32_t *probes_in, const uint32_t *order_in,
                        bool histogram, hipStream_t st);
 vi_status launch_grouping(const DeviceIndex &ix, const uint32_t *probes, uint64_t nq, uint32_t P, int qg, uint32_t segb0,
-                          uint64_t hstats[14], hipStream_t st, bool histogram_done, const uint32_t *qtot = nullptr,
+                          uint64_t hstats[15], hipStream_t st, bool histogram_done, const uint32_t *qtot = nullptr,
                           uint32_t *qoff = nullptr, const uint32_t *pair_rank = nullptr);
 bool grouping_fuses_query_offsets(const DeviceIndex &ix);
 
@@ -283,6 +283,47 @@ __global__ void u8_natural_kernel(const float4 *blocks, uint32_t dq, uint64_t nb
   out[t] = make_uint4(w[0], w[1], w[2], w[3]);
 }
 
+// 8-bit descriptors ranked with int8 products (rank_stream_i8_kernel), in the frame shifted by 127: the A operand is
+// 127 - v (fits in int8 for v in 0..255), 0 on the dimensions past dim.  Same block and column order as the bf16 image
+// (image_column): per block nc32 chunks of 32 dimensions x [half of 16 dimensions] x 64 columns x 16 B.
+__global__ void i8_image_kernel(const float4 *blocks, uint32_t dq, uint32_t dim, uint32_t nc32, uint64_t nblocks, uint4 *out) {
+  const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;  // (block, chunk, half, vector)
+  if (t >= nblocks * nc32 * 2 * 64) return;
+  const uint32_t v = (uint32_t)(t & 63), h = (uint32_t)((t >> 6) & 1);
+  const uint64_t bc = t >> 7;
+  const uint32_t c = (uint32_t)(bc % nc32);
+  const uint64_t b = bc / nc32;
+  uint32_t w[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const uint32_t qd = 8u * c + 4u * h + (uint32_t)i;  // quad of dimensions 4 qd .. 4 qd + 3 (dim is a multiple of 4)
+    w[i] = 0u;
+    if (4u * qd < dim) {
+      const float4 x = blocks[(b * dq + qd) * 64 + v];
+      w[i] = ((127u - (uint32_t)x.x) & 0xFFu) | (((127u - (uint32_t)x.y) & 0xFFu) << 8) | (((127u - (uint32_t)x.z) & 0xFFu) << 16) |
+             ((127u - (uint32_t)x.w) << 24);
+    }
+  }
+  out[((b * nc32 + c) * 2 + h) * 64 + image_column(v)] = make_uint4(w[0], w[1], w[2], w[3]);
+}
+// ... and the accumulator's start h(v) = ceil(|v - 127|^2 / 2) in image-column order (pad slots, marked kBig in xnorm:
+// kI8PadNorm); *xmax2 = max |v - 127|^2
+__global__ void i8_norms_kernel(const float4 *blocks, uint32_t dq, uint32_t dim, uint64_t nslots, const float *xnorm, int *out,
+                                uint32_t *xmax2) {
+  const uint64_t s = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= nslots) return;
+  const float4 *p = blocks + (s / kWave) * dq * kWave + (s % kWave);
+  int n = 0;
+  for (uint32_t qd = 0; 4u * qd < dim; ++qd) {
+    const float4 x = p[(size_t)qd * kWave];
+    const int a = (int)x.x - 127, b = (int)x.y - 127, c = (int)x.z - 127, d = (int)x.w - 127;
+    n += a * a + b * b + c * c + d * d;
+  }
+  const bool pad = !(xnorm[s] < kBig);
+  if (!pad) atomicMax(xmax2, (uint32_t)n);
+  out[(s & ~63ull) + image_column((uint32_t)(s & 63u))] = pad ? kI8PadNorm : (n + 1) >> 1;
+}
+
 // any nonzero lo half in an image? (pieces of 64 uint4: plane = (piece >> 1) & 1)
 __global__ void lo_plane_any_kernel(const uint4 *img, uint64_t npieces, uint32_t *any) {
   const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -395,14 +436,15 @@ __global__ void item_desc_kernel(const uint32_t *item_start, const uint32_t *seg
 // workgroup finds everything about an item at addresses it can compute from the item's index alone (no chain
 // descriptor -> pairs -> query offsets at the head of every item) — and the place word of the pair's two group records
 // (probe rank | segment << 6 | lane half << 13; every (pair, segment) sits in exactly one item).  One workgroup per
-// item; workgroup 0 also resets the rank kernel's work counter and the "a query has a lo plane" flag of the next batch.
+// item; workgroup 0 also resets the rank kernel's work counter and the "a query has a lo plane" and "a query is no int8
+// image" flags of the next batch.
 __global__ void item_cols_kernel(const uint4 *items, const uint32_t *pairs, const uint32_t *qoff, const uint32_t *rel, uint32_t P,
                                  uint32_t gq, uint32_t *qcol, uint32_t *grec, uint4 *sdesc, uint32_t *gmeta, uint64_t *stats) {
   const uint32_t w = blockIdx.x;
   const uint4 d0 = items[2 * (size_t)w], d1 = items[2 * (size_t)w + 1];
   if (threadIdx.x == 0) {
     sdesc[w] = make_uint4(d0.y, d0.z + d0.w, 2u * (d1.x - d0.w), d1.z);  // queries, first block, tiles, first record tile
-    if (w == 0) stats[13] = 0;
+    if (w == 0) { stats[13] = 0; stats[14] = 0; }
   }
   if (w == 0 && threadIdx.x < 8) stats[16 + 16 * threadIdx.x] = 0;  // the rank kernel's work counters (one per XCD queue, 128 bytes apart)
   for (uint32_t col = threadIdx.x; col < gq; col += blockDim.x) {
@@ -486,7 +528,7 @@ __device__ __forceinline__ void tile_dma_rank(float *tile, const float4 *src, co
 }
 
 __global__ void split_queries_kernel(const float *Q, uint32_t nq, uint32_t dim, uint32_t nc, uint4 *out, unsigned long long *any_lo,
-                                     uint32_t *zero, uint32_t zero_words, const float *mu);
+                                     uint32_t *zero, uint32_t zero_words, const float *mu, uint2 *out8, unsigned long long *not_i8);
 
 // s_waitcnt vmcnt(n) for a wave-uniform run-time n (the instruction takes an immediate)
 __device__ __forceinline__ void wait_vmcnt(uint32_t n) {
@@ -823,8 +865,11 @@ struct WideArgs {
 // *any_lo is raised when some query has a non-zero lo plane (a batch of bf16-exact queries is ranked without them)
 // (`zero`: a buffer the next kernels count into — the coarse step's per-list histogram — cleared here instead of by a memset launch)
 // mu (or null): the centre of the ranking images (DeviceIndex::centre) — the image is then that of -2 fl(q - mu)
+// out8 (or null: the lists have no int8 image): the int8 image of the batch for rank_stream_i8_kernel, q - 127 (0 past
+// dim), 32 ceil(dim / 32) bytes per query in dimension order; *not_i8 is raised when some value is not an integer in
+// 0..254 (the batch is then ranked with bf16)
 __global__ void split_queries_kernel(const float *Q, uint32_t nq, uint32_t dim, uint32_t nc, uint4 *out, unsigned long long *any_lo,
-                                     uint32_t *zero, uint32_t zero_words, const float *mu) {
+                                     uint32_t *zero, uint32_t zero_words, const float *mu, uint2 *out8, unsigned long long *not_i8) {
   const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;  // (query, chunk, half)
   for (uint64_t i = t; i < zero_words; i += (uint64_t)gridDim.x * blockDim.x) zero[i] = 0u;
   if (t >= (uint64_t)nq * nc * 2) return;
@@ -837,6 +882,23 @@ __global__ void split_queries_kernel(const float *Q, uint32_t nq, uint32_t dim, 
   float4 v0 = make_float4(0.f, 0.f, 0.f, 0.f), v1 = v0;
   if (e < dim) v0 = *reinterpret_cast<const float4 *>(row + e);        // dim % 4 == 0
   if (e + 4 < dim) v1 = *reinterpret_cast<const float4 *>(row + e + 4);
+  if (out8) {
+    const float x[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
+    uint32_t w[2] = {0u, 0u};
+    bool ok = true;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      if (e + (uint32_t)i < dim) {
+        ok = ok && x[i] >= 0.0f && x[i] <= 254.0f && x[i] == floorf(x[i]);
+        w[i >> 2] |= (((uint32_t)(int)x[i] - 127u) & 0xFFu) << (8 * (i & 3));
+      }
+    }
+    if (!ok) w[0] = w[1] = 0u;
+    const uint64_t row8 = q * (uint64_t)(nc + (nc & 1u)) * 2u;  // uint2 words per query: 32 ceil(dim / 32) bytes
+    out8[row8 + e / 8] = make_uint2(w[0], w[1]);
+    if ((nc & 1u) && c == nc - 1) out8[row8 + e / 8 + 2] = make_uint2(0u, 0u);  // the zero half of the last 32-dimension chunk
+    if (__ballot(!ok) != 0ull && (threadIdx.x & 63u) == 0u) atomicOr(not_i8, 1ull);
+  }
   if (mu) {
     if (e < dim) { const float4 m = *reinterpret_cast<const float4 *>(mu + e); v0.x -= m.x; v0.y -= m.y; v0.z -= m.z; v0.w -= m.w; }
     if (e + 4 < dim) { const float4 m = *reinterpret_cast<const float4 *>(mu + e + 4); v1.x -= m.x; v1.y -= m.y; v1.z -= m.z; v1.w -= m.w; }
@@ -991,6 +1053,7 @@ struct SelectCommon {
   const uint32_t *gmeta;
   const float4 *brec;
   float gamma, e_scale, xmax2;
+  float e_abs;  // absolute rank error added to the margin (int8 ranking: 1), else 0
   uint32_t gq;  // queries per rank work item (a record tile holds 2 * gq pair records)
   unsigned long long *dbg;  // [6] exact re-evaluations, [7] groups whose pair records were read, [8..] see select_body
   uint32_t image_order;     // the rank kernel multiplied the permuted bf16 image (subblock_vector)
@@ -1368,7 +1431,7 @@ __device__ __forceinline__ void select_body(const SelectCommon &c, uint32_t q, s
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) qn_int += (uint32_t)__shfl_xor((int)qn_int, o);
   }
-  float E = c.e_scale * (qn * (1.0f + c.gamma) + 2.0f * c.xmax2);
+  float E = c.e_scale * (qn * (1.0f + c.gamma) + 2.0f * c.xmax2) + c.e_abs;
   // hi planes of real-valued lists: the image (-2q) . v is ranked as (-2q) . hi(v) [trunc 1] or hi(-2q) . hi(v) [trunc 2];
   // |(-2q) . (v - hi v)| <= 2 |q| rho_max, and |(-2q - hi(-2q)) . v| <= |query residual| max|v|  (|hi(-2q)| <= 2 |q| (1 + 2^-8))
   if (c.trunc) E += 1.02f * (2.0f * sqrtf(qn) * c.rho_max * (1.0f + 0.00391f) + (c.trunc == 2u ? sqrtf(qres) * c.vmax : 0.0f));
@@ -2122,6 +2185,7 @@ SelectCommon select_common(const DeviceIndex &ix, const float *Qd, const float4 
   // within 2^-24 (|q'| + |v'|) of the true one, its distance within 4 * 2^-24 (|q'|^2 + |v'|^2) of the true distance
   const bool centred = ix.centered && rank_bf16();
   c.e_scale = (float)(acc + (centred ? 6.0 * u : 0.0));
+  c.e_abs = 0.0f;
   c.trunc = (uint32_t)trunc;
   c.rho_max = (float)(std::sqrt((double)ix.rho2_max) * 1.0001);
   c.vmax = (float)(std::sqrt((double)xmax2) * 1.0001);
@@ -2354,6 +2418,25 @@ vi_status compute_slot_norms(DeviceIndex *ix) {
         hipLaunchKernelGGL(u8_natural_kernel, dim3((uint32_t)((nt8 + 255) / 256)), dim3(256), 0, ix->stream,
                            (const float4 *)ix->lists.blocks.p, ix->dq, ix->lists.nblocks, (uint4 *)ix->lists_u8_nat.p);
         VI_HIP(hipGetLastError());
+        // the int8 image and norms of the streaming rank kernel's int8 form (rank_stream_i8_kernel), and the frame's centre
+        // (127 on every dimension) for the select's margins
+        const uint32_t nc32 = (ix->dim + 31) / 32;
+        const uint64_t nti = ix->lists.nblocks * nc32 * 128;
+        VI_TRY(ix->lists_i8.reserve(nti * 4));
+        VI_TRY(ix->i8_norm_img.reserve(nslots));
+        VI_TRY(ix->i8_centre.reserve(ix->dim));
+        VI_HIP(hipMemsetAsync(mx.p, 0, 4, ix->stream));
+        hipLaunchKernelGGL(i8_image_kernel, dim3((uint32_t)((nti + 255) / 256)), dim3(256), 0, ix->stream,
+                           (const float4 *)ix->lists.blocks.p, ix->dq, ix->dim, nc32, ix->lists.nblocks, (uint4 *)ix->lists_i8.p);
+        hipLaunchKernelGGL(i8_norms_kernel, dim3((uint32_t)((nslots + 255) / 256)), dim3(256), 0, ix->stream,
+                           (const float4 *)ix->lists.blocks.p, ix->dq, ix->dim, nslots, ix->xnorm.p, ix->i8_norm_img.p, mx.p);
+        VI_HIP(hipGetLastError());
+        const std::vector<float> c127(ix->dim, 127.0f);
+        VI_HIP(hipMemcpyAsync(ix->i8_centre.p, c127.data(), ix->dim * sizeof(float), hipMemcpyHostToDevice, ix->stream));
+        uint32_t n2 = 0;
+        VI_HIP(hipMemcpyAsync(&n2, mx.p, 4, hipMemcpyDeviceToHost, ix->stream));
+        VI_HIP(hipStreamSynchronize(ix->stream));  // (c127 and n2 live on this frame)
+        ix->i8_xmax2 = (float)n2;
       }
     }
     if (ix->lists_lo_zero && ix->dim <= kNarrowDim && !ix->lists_u8_nat.p) {  // exact re-evaluation from bf16 (select_kernel), VI_EXACT_BF16=0: from f32
@@ -2469,15 +2552,18 @@ static vi_status build_query_image(const DeviceIndex &ix, const float *Qd, uint6
   SearchWorkspace &ws = ix.cur().ws;
   const uint32_t nc = ix.dq / 4;
   VI_TRY(ws.qimg.reserve((uint64_t)nq * nc * 4 * 4));  // uint32 words: 4 pieces of 16 B per (query, chunk)
-  if (!ws.stats_zeroed) {  // [13]: some query has a lo plane (read back with the grouping's counts); [14]: the rank kernel's
-    VI_TRY(ws.stats.reserve(160));  // work counter — both reset by item_cols_kernel after their use
+  const bool i8 = ix.lists_i8.p != nullptr;  // the lists have an int8 image: the batch's too (rank_stream_i8_kernel)
+  if (i8) VI_TRY(ws.qimg8.reserve(std::max<uint64_t>(1, (uint64_t)nq * ((ix.dim + 31) / 32) * 8)));  // uint32 words: 32 B per (query, chunk of 32)
+  if (!ws.stats_zeroed) {  // [13]: some query has a lo plane, [14]: some query is no int8 image (both read back with the
+    VI_TRY(ws.stats.reserve(160));  // grouping's counts) — reset by item_cols_kernel after their use
     VI_HIP(hipMemsetAsync(ws.stats.p, 0, 160 * sizeof(uint64_t), st));
     ws.stats_zeroed = true;
   }
   const uint64_t nt = (uint64_t)nq * nc * 2;
   hipLaunchKernelGGL(split_queries_kernel, dim3((uint32_t)((nt + 255) / 256)), dim3(256), 0, st, Qd, (uint32_t)nq, ix.dim, nc,
                      (uint4 *)ws.qimg.p, (unsigned long long *)(ws.stats.p + 13), zero, (uint32_t)zero_words,
-                     ix.centered ? (const float *)ix.centre.p : nullptr);
+                     ix.centered ? (const float *)ix.centre.p : nullptr, i8 ? (uint2 *)ws.qimg8.p : nullptr,
+                     (unsigned long long *)(ws.stats.p + 14));
   VI_HIP(hipGetLastError());
   return VI_OK;
 }
@@ -2540,7 +2626,7 @@ vi_status search_filter_pipeline(const DeviceIndex &ix, const float *Qd, uint64_
   }
   if (timing) VI_HIP(hipEventRecord(ix.cur().ev[1], st));
   // ---- 2. group all (query, probe) pairs by list ----
-  uint64_t hstats[14];
+  uint64_t hstats[15];
   // queries per rank work item: 128 when lists are shared by many queries of the batch, 32 when a list is probed by a
   // handful (large balanced indexes): a 128-query group would keep three of its four waves idle
   // The choice needs the batch's histogram, which only the grouping produces: the first batch of a shape (nq, P) goes by
@@ -2570,6 +2656,10 @@ vi_status search_filter_pipeline(const DeviceIndex &ix, const float *Qd, uint64_
     const char *e = getenv("VI_STREAM_GQ");
     gq = e && atoi(e) == 256 && ws.queries_hi_only ? 256u : 128u;
   }
+  // 8-bit descriptors against a batch of integers in 0..254 (hstats[14] == 0, known after the grouping): the streaming
+  // kernel's int8 form (rank_stream_i8_kernel), exact ranks in the frame shifted by 127.  VI_RANK_I8=0: bf16.
+  const char *ie = getenv("VI_RANK_I8");
+  const bool i8_lists = stream && ix.lists_i8.p && !(ie && *ie == '0');
   const bool fuse_q = grouping_fuses_query_offsets(ix);
   VI_TRY(launch_grouping(ix, ws.probes.p, nq, P, (int)gq, segb0, hstats, st, true, fuse_q ? ws.qtot.p : nullptr, fuse_q ? ws.qoff.p : nullptr,
                          ws.pair_rank_valid ? ws.pair_rank.p : nullptr));
@@ -2585,6 +2675,8 @@ vi_status search_filter_pipeline(const DeviceIndex &ix, const float *Qd, uint64_
     }
   }
   ws.queries_hi_only = hstats[13] == 0;
+  const bool rank_i8 = i8_lists && hstats[14] == 0;
+  stt.rank_int8 = rank_i8 ? 1u : 0u;
   stt.scanned_vectors = hstats[0];
   stt.scan_items = hstats[1];
   stt.filter_tile_blocks = hstats[3];
@@ -2644,46 +2736,53 @@ vi_status search_filter_pipeline(const DeviceIndex &ix, const float *Qd, uint64_
                            ws.pair_rel.p, P, gq, ws.item_qcol.p, ws.item_grec.p, (uint4 *)ws.item_sdesc.p, ws.gpos.p, ws.stats.p);
         VI_HIP(hipGetLastError());
       }
-      RankStreamArgs a{(const uint4 *)ix.lists_bf16.p, ix.xnorm_img.p, (const uint4 *)ws.qimg.p, (const uint4 *)ws.item_sdesc.p, nitems,
-                       ws.item_qcol.p, ws.item_grec.p, (uint32_t *)(ws.stats.p + 16), (float4 *)ws.gval.p,
-                       (float4 *)ws.brec.p, nullptr, env_xmode()};
-      const bool qlo = (hstats[13] != 0 || !hi_only_ok()) && approx != 2;
-      const bool prof = getenv("VI_STREAM_PROF") != nullptr;
-      if (prof) {
-        VI_TRY(ws.prof.reserve(32 + 4 * 1024));
-        VI_HIP(hipMemsetAsync(ws.prof.p, 0, (32 + 4 * 1024) * sizeof(uint64_t), st));
-        VI_HIP(hipMemsetAsync(ws.prof.p + 16, 0xFF, sizeof(uint64_t), st));
-        a.prof = (unsigned long long *)ws.prof.p;
-      }
-      VI_TRY(start_rank_clock());
-      VI_TRY(launch_rank_stream(a, dq / 4, nitems, rank_mode, qlo || rank_mode == 1, gq, st));
-      if (prof) {
-        uint64_t h[24];
-        VI_HIP(hipMemcpyAsync(h, ws.prof.p, sizeof(h), hipMemcpyDeviceToHost, st));
-        VI_HIP(hipStreamSynchronize(st));
-        fprintf(stderr, "rank_stream wave-0 ticks (100 MHz) summed over workgroups: multiply %llu (of which waiting for tiles %llu) "
-                "end-of-item wait %llu gather %llu merge %llu | items %llu steps %llu | loop total %llu\n",
-                (unsigned long long)h[0], (unsigned long long)h[6], (unsigned long long)h[1], (unsigned long long)h[2],
-                (unsigned long long)h[3], (unsigned long long)h[4], (unsigned long long)h[5], (unsigned long long)h[7]);
-        if (const char *dump = getenv("VI_STREAM_PROF_DUMP")) {
-          std::vector<uint64_t> w(4 * 1024);
-          VI_HIP(hipMemcpy(w.data(), ws.prof.p + 32, w.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
-          if (FILE *f = fopen(dump, "w")) {
-            uint64_t base = ~0ull;
-            for (int i = 0; i < 1024; ++i) if (w[4 * i + 1]) base = std::min(base, w[4 * i]);
-            for (int i = 0; i < 1024; ++i)  // workgroup, start, end (10 ns ticks after the first start), items
-              if (w[4 * i + 1]) fprintf(f, "%d %llu %llu %llu\n", i, (unsigned long long)(w[4 * i] - base), (unsigned long long)(w[4 * i + 1] - base),
-                                        (unsigned long long)w[4 * i + 2]);
-            fclose(f);
-          }
+      if (rank_i8) {
+        RankStreamI8Args a{(const uint4 *)ix.lists_i8.p, ix.i8_norm_img.p, (const uint4 *)ws.qimg8.p, (const uint4 *)ws.item_sdesc.p, nitems,
+                           ws.item_qcol.p, ws.item_grec.p, (uint32_t *)(ws.stats.p + 16), (float4 *)ws.gval.p, (float4 *)ws.brec.p};
+        VI_TRY(start_rank_clock());
+        VI_TRY(launch_rank_stream_i8(a, (ix.dim + 31) / 32, nitems, gq, st));
+      } else {
+        RankStreamArgs a{(const uint4 *)ix.lists_bf16.p, ix.xnorm_img.p, (const uint4 *)ws.qimg.p, (const uint4 *)ws.item_sdesc.p, nitems,
+                         ws.item_qcol.p, ws.item_grec.p, (uint32_t *)(ws.stats.p + 16), (float4 *)ws.gval.p,
+                         (float4 *)ws.brec.p, nullptr, env_xmode()};
+        const bool qlo = (hstats[13] != 0 || !hi_only_ok()) && approx != 2;
+        const bool prof = getenv("VI_STREAM_PROF") != nullptr;
+        if (prof) {
+          VI_TRY(ws.prof.reserve(32 + 4 * 1024));
+          VI_HIP(hipMemsetAsync(ws.prof.p, 0, (32 + 4 * 1024) * sizeof(uint64_t), st));
+          VI_HIP(hipMemsetAsync(ws.prof.p + 16, 0xFF, sizeof(uint64_t), st));
+          a.prof = (unsigned long long *)ws.prof.p;
         }
-        fprintf(stderr, "   loops entered over %llu ticks, last exit %llu ticks after the first entry\n", (unsigned long long)(h[17] - h[16]),
-                (unsigned long long)(h[18] - h[16]));
-        fprintf(stderr, "   longest workgroup loop %llu ticks, workgroups with items %llu, most items in one %llu\n", (unsigned long long)h[13],
-                (unsigned long long)h[14], (unsigned long long)h[15]);
-        fprintf(stderr, "   after B1: T+idx %llu, DMA issue %llu, vmcnt(0) %llu, B2 %llu | after B2: merge+stores %llu, idx read %llu, load_item %llu\n",
-                (unsigned long long)h[8], (unsigned long long)h[9], (unsigned long long)h[10], (unsigned long long)h[2],
-                (unsigned long long)h[11], (unsigned long long)h[12], (unsigned long long)h[3]);
+        VI_TRY(start_rank_clock());
+        VI_TRY(launch_rank_stream(a, dq / 4, nitems, rank_mode, qlo || rank_mode == 1, gq, st));
+        if (prof) {
+          uint64_t h[24];
+          VI_HIP(hipMemcpyAsync(h, ws.prof.p, sizeof(h), hipMemcpyDeviceToHost, st));
+          VI_HIP(hipStreamSynchronize(st));
+          fprintf(stderr, "rank_stream wave-0 ticks (100 MHz) summed over workgroups: multiply %llu (of which waiting for tiles %llu) "
+                  "end-of-item wait %llu gather %llu merge %llu | items %llu steps %llu | loop total %llu\n",
+                  (unsigned long long)h[0], (unsigned long long)h[6], (unsigned long long)h[1], (unsigned long long)h[2],
+                  (unsigned long long)h[3], (unsigned long long)h[4], (unsigned long long)h[5], (unsigned long long)h[7]);
+          if (const char *dump = getenv("VI_STREAM_PROF_DUMP")) {
+            std::vector<uint64_t> w(4 * 1024);
+            VI_HIP(hipMemcpy(w.data(), ws.prof.p + 32, w.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
+            if (FILE *f = fopen(dump, "w")) {
+              uint64_t base = ~0ull;
+              for (int i = 0; i < 1024; ++i) if (w[4 * i + 1]) base = std::min(base, w[4 * i]);
+              for (int i = 0; i < 1024; ++i)  // workgroup, start, end (10 ns ticks after the first start), items
+                if (w[4 * i + 1]) fprintf(f, "%d %llu %llu %llu\n", i, (unsigned long long)(w[4 * i] - base), (unsigned long long)(w[4 * i + 1] - base),
+                                          (unsigned long long)w[4 * i + 2]);
+              fclose(f);
+            }
+          }
+          fprintf(stderr, "   loops entered over %llu ticks, last exit %llu ticks after the first entry\n", (unsigned long long)(h[17] - h[16]),
+                  (unsigned long long)(h[18] - h[16]));
+          fprintf(stderr, "   longest workgroup loop %llu ticks, workgroups with items %llu, most items in one %llu\n", (unsigned long long)h[13],
+                  (unsigned long long)h[14], (unsigned long long)h[15]);
+          fprintf(stderr, "   after B1: T+idx %llu, DMA issue %llu, vmcnt(0) %llu, B2 %llu | after B2: merge+stores %llu, idx read %llu, load_item %llu\n",
+                  (unsigned long long)h[8], (unsigned long long)h[9], (unsigned long long)h[10], (unsigned long long)h[2],
+                  (unsigned long long)h[11], (unsigned long long)h[12], (unsigned long long)h[3]);
+        }
       }
     } else {
       FilterArgs a{};
@@ -2712,6 +2811,13 @@ vi_status search_filter_pipeline(const DeviceIndex &ix, const float *Qd, uint64_
     { const char *e = getenv("VI_FILTER_STATS"); if (e && *e == '2') a.c.dbg = nullptr; }
     { const char *e = getenv("VI_EXACT_BF16"); if (ix.lists_hi_nat.p && !(e && *e == '0')) a.c.hi_nat = (const uint4 *)ix.lists_hi_nat.p; }
     { const char *e = getenv("VI_EXACT_U8"); if (ix.lists_u8_nat.p && !(e && *e == '0')) a.c.u8_nat = (const uint4 *)ix.lists_u8_nat.p; }
+    if (rank_i8) {  // rank values 2 r within [m', m' + 1] of m' = |q - v|^2 - |q - 127|^2: the margins of that frame, an absolute error of 1
+      a.c.mu = ix.i8_centre.p;
+      a.c.e_scale = 0.0f;
+      a.c.e_abs = 1.0f;
+      a.c.xmax2 = ix.i8_xmax2;
+      a.c.vmax = (float)(std::sqrt((double)ix.i8_xmax2) * 1.0001);
+    }
     const size_t qsm = 4ull * ix.dim * sizeof(float);
     if (k <= 64) hipLaunchKernelGGL(select_kernel<FastTopK>, dim3((uint32_t)((nq + 3) / 4)), dim3(256), qsm, st, a);
     else hipLaunchKernelGGL(select_kernel<FastTop128>, dim3((uint32_t)((nq + 3) / 4)), dim3(256), qsm, st, a);

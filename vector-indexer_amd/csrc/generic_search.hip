@@ -229,7 +229,7 @@ vi_status sort_rows_u64(uint64_t *keys, uint64_t nrows, uint32_t logL, hipStream
 
 // declared in search_kernels.hip
 vi_status launch_grouping(const DeviceIndex &ix, const uint32_t *probes, uint64_t nq, uint32_t P, int qg, uint32_t segb0,
-                          uint64_t hstats[14], hipStream_t st, bool histogram_done, const uint32_t *qtot = nullptr,
+                          uint64_t hstats[15], hipStream_t st, bool histogram_done, const uint32_t *qtot = nullptr,
                           uint32_t *qoff = nullptr, const uint32_t *pair_rank = nullptr);
 bool grouping_fuses_query_offsets(const DeviceIndex &ix);
 
@@ -358,7 +358,7 @@ vi_status device_index_search_generic(const DeviceIndex &ix, const float *Qd, ui
     VI_HIP(hipMemsetAsync(ws.sort_keys.p, 0xFF, m * L * sizeof(uint64_t), st));
     const double avg_q_per_list = (double)m * P / (double)std::max<uint64_t>(1, nlists);
     const int qg = pick_qg(dq, avg_q_per_list, ix.order);
-    uint64_t hstats[14];
+    uint64_t hstats[15];
     VI_TRY(launch_grouping(ix, ws.probes.p + q0 * P, m, P, qg, segb0, hstats, st, false));
     stt.scan_items += hstats[1];
     ScanArgs a{};

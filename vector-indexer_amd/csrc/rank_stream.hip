@@ -504,6 +504,292 @@ vi_status launch_nc(const RankStreamArgs &a, uint32_t nitems, int rank_mode, boo
   return launch_one<NC, 2, true, 4>(a, nitems, st);
 }
 
+
+// ---------------------------------------------------------------------------------------------------------------------
+// rank_stream_i8_kernel: rank_stream_kernel's item machinery (per-XCD queues, items addressable from their index, the
+// next item requested under the last step, counted waits) with exact int8 products: v_mfma_i32_32x32x32_i8 does twice
+// the K of the bf16 form in the same cycles, so a 32x32 tile of D = 128 is 4 MFMAs instead of 8, a tile is 4 KB instead
+// of 8 KB (4 loads per lane) and a query row in LDS 128 B instead of 256 B.  The accumulator starts at h(v) and ends at
+// r = h(v) - q'.v' (rank_stream.hpp); the tile minimum is taken on i32 with compiler-visible v_min (mfma_bf16.hpp:
+// tile_min explains why no asm may read an accumulator) and stored as the float 2 r.
+// ---------------------------------------------------------------------------------------------------------------------
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+typedef int i32x16 __attribute__((ext_vector_type(16)));
+
+template <int NC>
+struct TileRegsI8 {
+  uint4 a[NC];  // chunk c: 16 dimensions 32 c + 16 h .. of this lane's vector
+  int4 n[4];    // h(v) of the 16 accumulator rows
+};
+
+template <int NC>
+__device__ __forceinline__ void load_tile_i8(TileRegsI8<NC> &t, const uint4 *img, const int *hnorm, uint32_t blk, uint32_t half, int il,
+                                             int h) {
+  const uint4 *ap = img + ((size_t)blk * (NC * 2) + h) * kWave + 32u * half + il;
+#pragma unroll
+  for (int c = 0; c < NC; ++c) t.a[c] = ap[c * 2 * kWave];
+  const int *np = hnorm + (size_t)blk * kWave + 32u * half + 4 * h;
+#pragma unroll
+  for (int q4 = 0; q4 < 4; ++q4) t.n[q4] = *reinterpret_cast<const int4 *>(np + 8 * q4);
+}
+
+template <int NC>
+__device__ __forceinline__ void tile_landed_i8(const TileRegsI8<NC> &t) {
+#pragma unroll
+  for (int i = 0; i < NC; ++i) asm volatile("" ::"v"(t.a[i].x), "v"(t.a[i].y), "v"(t.a[i].z), "v"(t.a[i].w));
+#pragma unroll
+  for (int q4 = 0; q4 < 4; ++q4) asm volatile("" ::"v"(t.n[q4].x), "v"(t.n[q4].y), "v"(t.n[q4].z), "v"(t.n[q4].w));
+  __builtin_amdgcn_sched_barrier(0);
+}
+
+__device__ __forceinline__ int tile_min_i32(const i32x16 &a) {
+  int m[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) m[i] = min(a[2 * i], a[2 * i + 1]);
+  return min(min(min(m[0], m[1]), min(m[2], m[3])), min(min(m[4], m[5]), min(m[6], m[7])));
+}
+
+// NC: chunks of 32 dimensions; NU: 32-query tiles per work item (4: groups of 128; 8: groups of 256)
+template <int NC, int NU>
+__global__ void __launch_bounds__(256, 2) rank_stream_i8_kernel(RankStreamI8Args a) {
+  constexpr int GQ = 32 * NU;
+  constexpr int NR = NU / 4;
+  using L = StreamLayout<2 * NC>;        // a query row: 2 NC pieces of 16 B ([chunk][half]), swizzled as in rank_stream_kernel
+  constexpr int RP = L::RP;
+  constexpr int RPI = 64 / RP;
+  constexpr int IPW = GQ * RP / 256;
+  constexpr int IMG = GQ * RP * 16;
+  constexpr bool DB = stream_double_buffered(IMG);
+  extern __shared__ __attribute__((aligned(16))) float s_mem[];
+  float *s_T = s_mem + (DB ? 2 : 1) * (IMG / 4);
+  uint32_t *s_idx = reinterpret_cast<uint32_t *>(s_T + 2 * 4 * NU * kWave);
+  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
+  const int j = lane & 31, h = lane >> 5;
+  const unsigned lds_q = (unsigned)(size_t)(lds_ptr_t)s_mem;
+
+  auto request_item = [&](uint32_t it, ItemRaw &r) {
+    r.d = make_uint4(0u, 0u, 0u, 0u); r.qid = ~0u; r.rec[0] = ~0u; r.rec[1] = ~0u;
+    if (it >= a.nitems) return;
+    r.d = a.sdesc[it];
+    if ((uint32_t)lane < (uint32_t)(GQ / 4)) r.qid = a.qcol[(size_t)it * GQ + (uint32_t)wave * (GQ / 4) + (uint32_t)lane];
+#pragma unroll
+    for (int k = 0; k < NR; ++k) r.rec[k] = a.grec[(size_t)it * GQ + 32u * ((uint32_t)wave + 4u * k) + (uint32_t)j];
+  };
+  auto decode_item = [&](const ItemRaw &r) {
+    ItemRegs o;
+    o.nqi = (uint32_t)__builtin_amdgcn_readfirstlane((int)r.d.x);
+    o.blk00 = (uint32_t)__builtin_amdgcn_readfirstlane((int)r.d.y);
+    o.ntiles = (uint32_t)__builtin_amdgcn_readfirstlane((int)r.d.z);
+    o.rec0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)r.d.w);
+    return o;
+  };
+  auto gather = [&](uint32_t buf, uint32_t nq_item, uint32_t my_qid) {
+    uint32_t lo = (uint32_t)lane;
+    asm volatile("" : "+v"(lo));
+    uint32_t qids[IPW];
+#pragma unroll
+    for (int i = 0; i < IPW; ++i) qids[i] = (uint32_t)__shfl((int)my_qid, (int)(RPI * i + lo / RP));
+#pragma unroll
+    for (int i = 0; i < IPW; ++i) {
+      const uint32_t row0 = (uint32_t)wave * (GQ / 4) + (uint32_t)(RPI * i);
+      if (row0 < nq_item) {
+        const uint32_t pc = L::swz(lo % RP, row0 + lo / RP);
+        if (qids[i] != ~0u && pc < 2u * NC) glds16_at(a.qimg + (size_t)qids[i] * (NC * 2) + pc, lds_q + buf * (uint32_t)IMG + row0 * RP * 16u);
+      }
+    }
+  };
+
+  constexpr uint32_t kQueues = 8;
+  auto queue_range = [&](uint32_t q, uint32_t &lo, uint32_t &hi) {
+    lo = (uint32_t)(((uint64_t)a.nitems * q) / kQueues);
+    hi = (uint32_t)(((uint64_t)a.nitems * (q + 1)) / kQueues);
+  };
+  uint32_t my_queue = blockIdx.x % kQueues;
+  auto resolve = [&](uint32_t popped) {
+    for (uint32_t tries = 0; tries < kQueues; ++tries) {
+      uint32_t lo, hi;
+      queue_range(my_queue, lo, hi);
+      if (popped < hi - lo) return lo + popped;
+      my_queue = (my_queue + 1) % kQueues;
+      if (tries + 1 < kQueues) popped = atomicAdd(a.queue + 32 * my_queue, 1u);
+    }
+    return a.nitems;
+  };
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (uint32_t k = 0; k < 2; ++k) s_idx[k] = resolve(atomicAdd(a.queue + 32 * my_queue, 1u));
+  }
+  __syncthreads();
+  uint32_t cur = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_idx[0]), nxt = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_idx[1]);
+  ItemRaw rc, rn;
+  request_item(cur, rc);
+  request_item(nxt, rn);
+  ItemRegs ic = decode_item(rc);
+  TileRegsI8<NC> ta, tb;
+  if ((uint32_t)wave < ic.ntiles) load_tile_i8<NC>(ta, a.img, a.hnorm, ic.blk00 + ((uint32_t)wave >> 1), (uint32_t)wave & 1u, j, h);
+  gather(0u, ic.nqi, rc.qid);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  tile_landed_i8<NC>(ta);
+
+  uint32_t buf = 0, par = 0;
+  const uint32_t lane_row = ((uint32_t)j * RP + L::swz(0u, (uint32_t)j)) * 16u;
+  while (cur < a.nitems) {
+    uint32_t after = ~0u;
+    ItemRegs in{0u, 0u, 0u, 0u};
+    auto last_step = [&](TileRegsI8<NC> &spare) {
+      in = decode_item(rn);
+      if ((uint32_t)wave < in.ntiles) load_tile_i8<NC>(spare, a.img, a.hnorm, in.blk00 + ((uint32_t)wave >> 1), (uint32_t)wave & 1u, j, h);
+      if (threadIdx.x == 0) after = queue_pop_asm(a.queue + 32 * my_queue);
+      if (DB) gather(buf ^ 1u, in.nqi, rn.qid);
+    };
+    const uint32_t nqi = ic.nqi, nu = (ic.nqi + 31u) >> 5, ntiles = ic.ntiles, blk00 = ic.blk00;
+    const char *img_at = reinterpret_cast<const char *>(s_mem) + (DB ? buf * (uint32_t)IMG : 0u);
+    auto frag = [&](int c, int u) {
+      const uint32_t pc = (uint32_t)(2 * c) + (uint32_t)h;
+      return __builtin_bit_cast(i32x4, *reinterpret_cast<const int4 *>(img_at + ((lane_row ^ (pc << 4)) + (uint32_t)(32 * u * RP * 16))));
+    };
+
+    float T[NU];
+    float4 pend[NU];
+#pragma unroll
+    for (int u = 0; u < NU; ++u) {
+      T[u] = INFINITY;
+      pend[u] = make_float4(INFINITY, INFINITY, INFINITY, INFINITY);
+    }
+    const uint32_t bi = ic.rec0 * (2u * GQ) + (uint32_t)GQ * (uint32_t)h + (uint32_t)j;
+
+    constexpr int kPF = 4;
+    auto step = [&](const TileRegsI8<NC> &t, uint32_t i, bool last) {
+      i32x16 nrm;
+#pragma unroll
+      for (int q4 = 0; q4 < 4; ++q4) {
+        nrm[4 * q4 + 0] = t.n[q4].x; nrm[4 * q4 + 1] = t.n[q4].y; nrm[4 * q4 + 2] = t.n[q4].z; nrm[4 * q4 + 3] = t.n[q4].w;
+      }
+      i32x4 ring[kPF];
+      auto fetch = [&](int s) {
+        const int u = (s / NC) < NU - 1 ? (s / NC) : NU - 1, c = s % NC;
+        ring[s % kPF] = frag(c, u);
+      };
+#pragma unroll
+      for (int s0 = 0; s0 < kPF; ++s0) fetch(s0);
+      const uint32_t ci = i & 3u;
+#pragma unroll
+      for (int u = 0; u < NU; ++u) {
+        if ((uint32_t)u < nu) {  // wave-uniform
+          i32x16 acc = nrm;
+#pragma unroll
+          for (int c = 0; c < NC; ++c) {
+            const int sp = u * NC + c;
+            __builtin_amdgcn_sched_barrier(0);
+            acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(__builtin_bit_cast(i32x4, t.a[c]), ring[sp % kPF], acc, 0, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);
+            fetch(sp + kPF);
+          }
+          const float m = (float)(2 * tile_min_i32(acc));
+          T[u] = min3_raw(T[u], m, m);
+          pend[u].x = ci == 0u ? m : pend[u].x;
+          pend[u].y = ci == 1u ? m : pend[u].y;
+          pend[u].z = ci == 2u ? m : pend[u].z;
+          pend[u].w = ci == 3u ? m : pend[u].w;
+        }
+      }
+      if (ci == 3u || last) {
+        const uint32_t rt = (i >> 2) * 4u + (uint32_t)wave;
+#pragma unroll
+        for (int u = 0; u < NU; ++u) {
+          if ((uint32_t)u < nu) {
+            if (32u * u + (uint32_t)j < nqi) a.brec[(size_t)bi + 32u * u + (2u * GQ) * rt] = pend[u];
+            pend[u] = make_float4(INFINITY, INFINITY, INFINITY, INFINITY);
+          }
+        }
+      }
+    };
+
+    bool prepared = false, next_in_tb = false;
+    for (uint32_t i = 0;; i += 2) {
+      const uint32_t t0 = 4u * i + (uint32_t)wave;
+      if (t0 >= ntiles) break;
+      const uint32_t t1 = t0 + 4u, t2 = t0 + 8u;
+      tile_landed_i8<NC>(ta);
+      item_landed(rn);
+      if (t1 < ntiles) load_tile_i8<NC>(tb, a.img, a.hnorm, blk00 + (t1 >> 1), t1 & 1u, j, h);
+      else { last_step(tb); prepared = true; next_in_tb = true; }
+      step(ta, i, t1 >= ntiles);
+      if (t1 >= ntiles) break;
+      tile_landed_i8<NC>(tb);
+      item_landed(rn);
+      if (t2 < ntiles) load_tile_i8<NC>(ta, a.img, a.hnorm, blk00 + (t2 >> 1), t2 & 1u, j, h);
+      else { last_step(ta); prepared = true; }
+      step(tb, i + 1u, t2 >= ntiles);
+    }
+    if (!prepared) last_step(ta);
+    const uint32_t young_stores = ntiles > (uint32_t)wave ? nu : 0u;
+
+    if (!DB) __syncthreads();
+    float *s_Tk = s_T + par * (4 * NU * kWave);
+#pragma unroll
+    for (int u = 0; u < NU; ++u)
+      if ((uint32_t)u < nu) s_Tk[(wave * NU + u) * kWave + lane] = T[u];
+    if (!DB) gather(0u, in.nqi, rn.qid);
+    if (DB) wait_vmcnt(young_stores);
+    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if (threadIdx.x == 0) s_idx[par] = resolve(after);
+    __syncthreads();
+    if (next_in_tb) ta = tb;
+    asm volatile("" ::"v"(rc.rec[0]), "v"(rc.rec[1]));
+    tile_landed_i8<NC>(ta);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int r = 0; r < NR; ++r) {
+      const uint32_t u = (uint32_t)wave + 4u * r;
+      if (u < nu) {
+        float v0 = s_Tk[(0 * NU + u) * kWave + lane], v1 = s_Tk[(1 * NU + u) * kWave + lane];
+        float v2 = s_Tk[(2 * NU + u) * kWave + lane], v3 = s_Tk[(3 * NU + u) * kWave + lane];
+        auto cx = [](float &x, float &y) { const float lo = fminf(x, y), hi = fmaxf(x, y); x = lo; y = hi; };
+        cx(v0, v1); cx(v2, v3); cx(v0, v2); cx(v1, v3); cx(v1, v2);
+        if (rc.rec[r] != ~0u) a.gval[rc.rec[r] + (uint32_t)h] = make_float4(v0, v1, v2, v3);
+      }
+    }
+    cur = nxt;
+    nxt = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_idx[par]);
+    par ^= 1u;
+    ic = in;
+    rc = rn;
+    buf ^= 1u;
+    request_item(nxt, rn);
+  }
+}
+
+template <int NC, int NU>
+vi_status launch_one_i8(const RankStreamI8Args &a, uint32_t nitems, hipStream_t st) {
+  const size_t img = (size_t)StreamLayout<2 * NC>::RP * (32 * NU) * 16;
+  const size_t lds = img * (stream_double_buffered((int)img) ? 2 : 1) + 2 * (size_t)NU * 1024 + 16;
+  constexpr int kMaxDev = 64;
+  static uint32_t cus_of[kMaxDev];
+  int dev = 0;
+  VI_HIP(hipGetDevice(&dev));
+  if (dev < 0 || dev >= kMaxDev) return fail(VI_ERR_DEVICE, "device ordinal %d out of range", dev);
+  uint32_t cus = __atomic_load_n(&cus_of[dev], __ATOMIC_ACQUIRE);
+  if (cus == 0) {
+    if (hipFuncSetAttribute((const void *)rank_stream_i8_kernel<NC, NU>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+      return fail(VI_ERR_DEVICE, "cannot reserve %zu bytes of LDS for the int8 rank kernel", lds);
+    int n = 0;
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
+    cus = (uint32_t)n;
+    __atomic_store_n(&cus_of[dev], cus, __ATOMIC_RELEASE);
+  }
+  uint32_t per_cu = lds > 80 * 1024 ? 1u : 2u;
+  if (const char *e = getenv("VI_STREAM_WGS_PER_CU")) per_cu = (uint32_t)std::max(1, atoi(e));  // (experiment)
+  hipLaunchKernelGGL((rank_stream_i8_kernel<NC, NU>), dim3(std::min(nitems, per_cu * cus)), dim3(256), lds, st, a);
+  VI_HIP(hipGetLastError());
+  return VI_OK;
+}
+
+template <int NC>
+vi_status launch_nc_i8(const RankStreamI8Args &a, uint32_t nitems, uint32_t gq, hipStream_t st) {
+  return gq == 256 ? launch_one_i8<NC, 8>(a, nitems, st) : launch_one_i8<NC, 4>(a, nitems, st);
+}
 }  // namespace
 
 vi_status launch_rank_stream(const RankStreamArgs &a, uint32_t nc, uint32_t nitems, int rank_mode, bool qlo, uint32_t gq, hipStream_t st) {
@@ -518,6 +804,17 @@ vi_status launch_rank_stream(const RankStreamArgs &a, uint32_t nc, uint32_t nite
     case 7: return launch_nc<7>(a, nitems, rank_mode, qlo, gq, st);
     case 8: return launch_nc<8>(a, nitems, rank_mode, qlo, gq, st);
     default: return fail(VI_ERR_OTHER, "unsupported dimension for the streaming rank kernel");
+  }
+}
+
+vi_status launch_rank_stream_i8(const RankStreamI8Args &a, uint32_t nc32, uint32_t nitems, uint32_t gq, hipStream_t st) {
+  if (nitems == 0) return VI_OK;
+  switch (nc32) {
+    case 1: return launch_nc_i8<1>(a, nitems, gq, st);
+    case 2: return launch_nc_i8<2>(a, nitems, gq, st);
+    case 3: return launch_nc_i8<3>(a, nitems, gq, st);
+    case 4: return launch_nc_i8<4>(a, nitems, gq, st);
+    default: return fail(VI_ERR_OTHER, "unsupported dimension for the int8 rank kernel");
   }
 }
 

@@ -27,4 +27,25 @@ struct RankStreamArgs {
 // gq: queries per work item the grouping formed, 128 or 256
 vi_status launch_rank_stream(const RankStreamArgs &a, uint32_t nc, uint32_t nitems, int rank_mode, bool qlo, uint32_t gq, hipStream_t st);
 
+// 8-bit descriptors (every stored value an integer in 0..255) against queries of integers in 0..254: the same work items
+// ranked with exact int8 products, in the frame shifted by 127 (filter_search.hip: i8_image_kernel, split_queries_kernel).
+// Rank value of (q, v): 2 r with r = h(v) - q'.v', q' = q - 127, v' = v - 127, h(v) = ceil(|v'|^2 / 2) — an integer with
+// |v'|^2 - 2 q'.v' <= 2 r <= |v'|^2 - 2 q'.v' + 1, stored as a float (exact below 2^24).
+struct RankStreamI8Args {
+  const uint4 *img;      // A = 127 - v as int8 (0 on padded dimensions): per block nc32 chunks x [half] x 64 columns x 16 B
+  const int *hnorm;      // h(v) in image-column order (pad slots: kI8PadNorm)
+  const uint4 *qimg;     // B = q - 127 as int8 (0 on padded dimensions): per query nc32 x [half] x 16 B (split_queries_kernel)
+  const uint4 *sdesc;    // as RankStreamArgs
+  uint32_t nitems;
+  const uint32_t *qcol;
+  const uint32_t *grec;
+  uint32_t *queue;
+  float4 *gval;
+  float4 *brec;
+};
+constexpr int kI8PadNorm = 1 << 28;  // above every h(v) (< 2^21 for D <= 128); 2 r stays below 2^31
+
+// nc32: chunks of 32 dimensions (1..4)
+vi_status launch_rank_stream_i8(const RankStreamI8Args &a, uint32_t nc32, uint32_t nitems, uint32_t gq, hipStream_t st);
+
 }  // namespace vi

@@ -1471,7 +1471,7 @@ vi_status device_index_search(const DeviceIndex &ix, const SearchIO &io) {
 bool grouping_fuses_query_offsets(const DeviceIndex &) { return true; }
 
 vi_status launch_grouping(const DeviceIndex &ix, const uint32_t *probes, uint64_t nq, uint32_t P, int qg, uint32_t segb0,
-                          uint64_t hstats[14], hipStream_t st, bool histogram_done, const uint32_t *qtot, uint32_t *qoff,
+                          uint64_t hstats[15], hipStream_t st, bool histogram_done, const uint32_t *qtot, uint32_t *qoff,
                           const uint32_t *pair_rank) {
   SearchWorkspace &ws = ix.cur().ws;
   const uint64_t nlists = ix.nlists;
@@ -1495,7 +1495,7 @@ vi_status launch_grouping(const DeviceIndex &ix, const uint32_t *probes, uint64_
   // (into page-locked memory: a copy to the caller's stack array is staged by the runtime and costs a few microseconds
   // more on the one synchronisation point of the pipeline)
   if (!ws.hstats_pinned) VI_HIP(hipHostMalloc((void **)&ws.hstats_pinned, 16 * sizeof(uint64_t)));
-  VI_HIP(hipMemcpyAsync(ws.hstats_pinned, ws.stats.p, 14 * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+  VI_HIP(hipMemcpyAsync(ws.hstats_pinned, ws.stats.p, 15 * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
   VI_HIP(hipEventRecord(ix.cur().ev[5], st));
   if (pair_rank && histogram_done)
     hipLaunchKernelGGL(group_scatter_ranked_kernel, dim3((total + 255) / 256), dim3(256), 0, st, probes, ix.list_len.p,
@@ -1505,7 +1505,7 @@ vi_status launch_grouping(const DeviceIndex &ix, const uint32_t *probes, uint64_
                        (uint32_t)nlists, P, ws.cnt.p + subbin_words(nlists), ws.pairs.p, total, ws.seg_start.p, ws.pair_pos.p);
   VI_HIP(hipGetLastError());
   VI_HIP(hipEventSynchronize(ix.cur().ev[5]));
-  std::memcpy(hstats, ws.hstats_pinned, 14 * sizeof(uint64_t));
+  std::memcpy(hstats, ws.hstats_pinned, 15 * sizeof(uint64_t));
   return VI_OK;
 }
 
