@@ -91,12 +91,19 @@ def test_rank_kernels_do_not_spill_and_keep_one_store_per_block(asm):
 
 
 # ---------------------------------------------------------------------------------------------------------------
-# streaming rank kernel (rank_stream.hip): the default instantiations (groups of 128 queries) must not spill, and a
-# step of the tile loop must multiply WITHOUT waiting for the tile it has just requested: the compiler once placed
-# `s_waitcnt vmcnt(0)` in front of the first MFMA of every step (after the prefetch of the next tile), which the
-# explicit tile_landed() touch moved in front of the prefetch.
+# streaming rank kernel (rank_stream.hip), both arithmetic forms of its one item skeleton: rank_stream_kernel (bf16) and
+# rank_stream_i8_kernel (exact int8 products).  The default instantiations (groups of 128 queries) and every int8 one
+# must not spill, the int8 form multiplies with v_mfma_i32_32x32x32_i8 only, and a step of the tile loop must multiply
+# WITHOUT waiting for the tile it has just requested: the compiler once placed `s_waitcnt vmcnt(0)` in front of the first
+# MFMA of every step (after the prefetch of the next tile), which the explicit tile_landed() touch moved in front of the
+# prefetch.
 # ---------------------------------------------------------------------------------------------------------------
 STREAM_SRC = os.path.join(ROOT, "vector-indexer_amd", "csrc", "rank_stream.hip")
+STREAM_FORMS = {   # form -> (mangled name: chunks, [RANK, QLO,] 32-query tiles per item;  its MFMA)
+    "bf16": (r"18rank_stream_kernelILi(?P<nc>\d+)ELi(?P<rank>\d)ELb(?P<qlo>[01])ELi(?P<nu>\d)EEEvNS_14RankStreamArgsE",
+             "v_mfma_f32_32x32x16_bf16"),
+    "int8": (r"21rank_stream_i8_kernelILi(?P<nc>\d+)ELi(?P<nu>\d+)EEEvNS_16RankStreamI8ArgsE", "v_mfma_i32_32x32x32_i8"),
+}
 
 
 @pytest.fixture(scope="module")
@@ -109,55 +116,85 @@ def stream_asm(tmp_path_factory):
     return open(out).read()
 
 
-def stream_kernels(asm_text):
+def stream_kernels(asm_text, form):
+    pattern, mfma = STREAM_FORMS[form]
     out = {}
-    for m in re.finditer(r"^(_ZN2vi12_GLOBAL__N_118rank_stream_kernelILi(\d+)ELi(\d)ELb([01])ELi(\d)EEEvNS_14RankStreamArgsE):[^\n]*\n(.*?)\n\.Lfunc_end",
-                         asm_text, re.S | re.M):
-        name, nc, rank, qlo, nu, body = m.groups()
+    for m in re.finditer(r"^(_ZN2vi12_GLOBAL__N_1" + pattern + r"):[^\n]*\n(?P<body>.*?)\n\.Lfunc_end", asm_text, re.S | re.M):
+        name = m.group(1)
         meta = re.search(r"\.amdhsa_kernel " + re.escape(name) + r"\n(.*?)\.end_amdhsa_kernel", asm_text, re.S).group(1)
-        out[name] = dict(body=body, meta=meta, nc=int(nc), rank=int(rank), qlo=qlo == "1", nu=int(nu))
+        g = m.groupdict()
+        out[name] = dict(body=g["body"], meta=meta, nc=int(g["nc"]), nu=int(g["nu"]), qlo=g.get("qlo") == "1", mfma=mfma)
     return out
 
 
+def assert_no_scratch(name, k):
+    scratch = int(re.search(r"\.amdhsa_private_segment_fixed_size (\d+)", k["meta"]).group(1))
+    assert scratch == 0, f"{name}: {scratch} bytes of scratch per lane"
+    assert not re.search(r"\bscratch_(load|store)|buffer_(load|store)", k["body"]), name
+
+
+def steps_overlapping_the_next_tile(name, k):
+    """every run of tile loads that is followed by a step's MFMAs: no vmcnt(0) drain between its last load and the step's
+    last MFMA; returns the number of such steps"""
+    lines = k["body"].split("\n")
+    tile_loads = [i for i, l in enumerate(lines) if "global_load_dwordx4" in l]
+    mfmas = [i for i, l in enumerate(lines) if k["mfma"] in l]
+    steps = 0
+    for i in tile_loads:
+        nxt = [m for m in mfmas if m > i]
+        if not nxt or any(i < t < nxt[0] for t in tile_loads):
+            continue   # not the last load of its run
+        chain = [m for m in nxt if m < i + 600][: k["nc"] * (2 if k["qlo"] else 1) * 4]
+        if len(chain) < k["nc"]:
+            continue
+        between = "\n".join(lines[i + 1:chain[-1]])
+        if "s_barrier" in between:
+            continue   # (the run in front of the item loop)
+        # (counted waits of the conditional last-step block in between — the next item's first tile goes into registers
+        # whose previous loads the compiler cannot prove complete — are harmless; a full drain is the bug)
+        assert not re.search(r"s_waitcnt[^\n]*vmcnt\(0\)", between), f"{name}: a step drains vector memory after its prefetch"
+        steps += 1
+    return steps
+
+
 def test_streaming_rank_kernels_do_not_spill(stream_asm):
-    ks = stream_kernels(stream_asm)
+    ks = stream_kernels(stream_asm, "bf16")
     assert len(ks) == 32   # NC 1..8 x {queries hi-only, hi + lo} x {groups of 128, 256}
     for name, k in ks.items():
         if k["nu"] != 4:
             continue   # groups of 256 are an experiment knob (VI_STREAM_GQ=256); its hi + lo fallback does spill
-        scratch = int(re.search(r"\.amdhsa_private_segment_fixed_size (\d+)", k["meta"]).group(1))
-        assert scratch == 0, f"{name}: {scratch} bytes of scratch per lane"
-        assert not re.search(r"\bscratch_(load|store)|buffer_(load|store)", k["body"]), name
+        assert_no_scratch(name, k)
 
 
 def test_streaming_rank_kernel_multiplies_while_the_next_tile_loads(stream_asm):
-    ks = stream_kernels(stream_asm)
+    ks = stream_kernels(stream_asm, "bf16")
     checked = 0
     for name, k in ks.items():
         if k["nu"] != 4 or k["nc"] < 4:
             continue
-        lines = k["body"].split("\n")
-        tile_loads = [i for i, l in enumerate(lines) if "global_load_dwordx4" in l]
-        mfmas = [i for i, l in enumerate(lines) if "v_mfma_f32_32x32x16_bf16" in l]
-        # every run of tile loads that is followed by a step's MFMAs: no vmcnt wait between its last load and the step's last MFMA
-        steps = 0
-        for i in tile_loads:
-            nxt = [m for m in mfmas if m > i]
-            if not nxt or any(i < t < nxt[0] for t in tile_loads):
-                continue   # not the last load of its run
-            chain = [m for m in nxt if m < i + 600][: k["nc"] * (2 if k["qlo"] else 1) * 4]
-            if len(chain) < k["nc"]:
-                continue
-            between = "\n".join(lines[i + 1:chain[-1]])
-            if "s_barrier" in between:
-                continue   # (the run in front of the item loop)
-            # (counted waits of the conditional last-step block in between — the next item's first tile goes into registers
-            # whose previous loads the compiler cannot prove complete — are harmless; a full drain is the bug)
-            assert not re.search(r"s_waitcnt[^\n]*vmcnt\(0\)", between), f"{name}: a step drains vector memory after its prefetch"
-            steps += 1
-        assert steps >= 2, name   # the two halves of the unrolled tile loop
+        assert steps_overlapping_the_next_tile(name, k) >= 2, name   # the two halves of the unrolled tile loop
         checked += 1
     assert checked >= 8
+
+
+def test_int8_rank_kernels_use_the_int8_matrix_op_and_do_not_spill(stream_asm):
+    ks = stream_kernels(stream_asm, "int8")
+    assert len(ks) == 8   # 1..4 chunks of 32 dimensions x {groups of 128, 256}
+    for name, k in ks.items():
+        assert_no_scratch(name, k)
+        mfmas = re.findall(r"v_mfma_\w+", k["body"])
+        assert mfmas and set(mfmas) == {"v_mfma_i32_32x32x32_i8"}, f"{name}: {sorted(set(mfmas))}"
+
+
+def test_int8_rank_kernel_multiplies_while_the_next_tile_loads(stream_asm):
+    ks = stream_kernels(stream_asm, "int8")
+    checked = 0
+    for name, k in ks.items():
+        if k["nu"] != 4:
+            continue
+        assert steps_overlapping_the_next_tile(name, k) >= 2, name   # the two halves of the unrolled tile loop
+        checked += 1
+    assert checked == 4
 
 
 # ---------------------------------------------------------------------------------------------------------------

@@ -140,3 +140,19 @@ def test_int8_rank_on_ranks_merges_to_the_single_gpu_result(placement, tmp_path)
             assert (bits(hip.download(Dm, (nq, k), np.float32)) == bits(Do)).all(), (k, n_probe)
     finally:
         hip.close()
+
+
+@pytest.mark.parametrize("d,n", [(128, 16000), (48, 12000)])
+def test_int8_rank_in_groups_of_256(d, n, tmp_path, monkeypatch):
+    """VI_STREAM_GQ=256: rank_stream_i8_kernel<NC, 8>.  Groups of 256 are formed once the handle has seen that its batches'
+    queries are bf16-exact, so the first batch of a shape still runs groups of 128 and the later ones run groups of 256"""
+    monkeypatch.setenv("VI_STREAM_GQ", "256")
+    rng = np.random.default_rng(256 + d)
+    X = descriptors(rng, n, d)
+    orc, gpu = build(tmp_path, X)
+    Q = queries(rng, X, 1800)   # 220-254 lists: over 200 queries per list at n_probe 32, groups past 128 queries
+    for batch, (k, n_probe) in enumerate([(10, 32), (10, 32), (100, 32), (1, 64)]):
+        check(orc, gpu, Q, k, n_probe, 1)
+        if batch:
+            st = gpu.last_stats()
+            assert st["rank_int8"] == 1 and st["group_queries"] == 256, (batch, st)
