@@ -273,7 +273,10 @@ vi_status vi_indexer_search_device(const vi_indexer *ix, const float *queries_de
  *                                    visiting order, ivf_index.rs:223-262) — what the tie keys are built from;
  *   (all-gather of probes / order over the ranks)
  *   vi_indexer_search_probed_device  ivf_index.rs:223-274 for the whole batch against this rank's stripes with the
- *                                    given probe lists; outputs as vi_indexer_search_device.
+ *                                    given probe lists; outputs as vi_indexer_search_device.  Each row must hold its
+ *                                    found real probes (list ids < #centroids) first, then only empty markers
+ *                                    0xFFFFFFFF (whose order is not read), and the orders of the real probes must be
+ *                                    a permutation of 0 .. found-1; anything else is VI_ERR_INVALID_INPUT.
  * Both return with their outputs complete; all pointers are device pointers.  Any k and n_probe the single-GPU entry
  * accepts (k > 128 or n_probe > 64 take the sort-everything path there and here). */
 vi_status vi_indexer_probe_device(const vi_indexer *ix, const float *queries_dev, uint64_t nq, uint64_t n_probe,

@@ -289,3 +289,13 @@ def test_exact_evaluation_pieces_keep_their_address_spaces_and_counted_waits(asm
         assert re.search(r"s_waitcnt vmcnt\(4\)", body) and re.search(r"s_waitcnt vmcnt\(0\)", body), name
         assert len(re.findall(r"v_pk_add_f32", body)) >= 8 and len(re.findall(r"v_pk_mul_f32", body)) >= 8, name
         assert not re.search(r"v_(fma|fmac|mad)_f32", body), f"{name}: a fused multiply-add in the reference's unfused chain"
+
+
+def test_direct_coarse_select_keeps_its_flags_in_registers(asm):
+    """coarse_select_direct_kernel keeps two flag words per lane for up to 2 * kPer = 32 sub-blocks (a class in cls, the
+    row of the minimum in rows_lo / rows_hi) and the 16 records of the lane in rb1 / rb2: all indexed at compile time.
+    A runtime index into one of those register arrays would move it to scratch memory."""
+    ks = _kernel_bodies(asm, r"_ZN2vi12_GLOBAL__N_127coarse_select_direct_kernelENS0_16CoarseSelectArgsE")
+    assert len(ks) == 1
+    for name, (body, meta) in ks.items():
+        assert_no_scratch(name, dict(body=body, meta=meta))

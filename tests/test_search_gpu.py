@@ -448,15 +448,53 @@ def test_out_of_range_probe_lists_are_rejected(tmp_path):
             with pytest.raises(N.ViError) as e:
                 gpu.search_probed_device(xq, nq, k, P, hip.upload(bp), hip.upload(bo), Dg, Ig, Tg)
             assert e.value.kind == "InvalidInput", what
-        # trailing empty markers are legal (a rank whose coarse step found fewer lists)
-        bp = good_p.copy(); bo = good_o.copy()
-        bp[7, P - 1] = 0xFFFFFFFF; bo[7, P - 1] = 0xFFFFFFFF
+        # trailing empty markers are legal (a rank whose coarse step found fewer lists); the ranks of the real probes
+        # that remain are renumbered to 0 .. found-1 (the marker's rank is dropped)
+        bp, bo = with_trailing_marker(good_p, good_o, 7)
         gpu.search_probed_device(xq, nq, k, P, hip.upload(bp), hip.upload(bo), Dg, Ig, Tg)
         # and the handle is still healthy
         gpu.search_probed_device(xq, nq, k, P, probes, order, Dg, Ig, Tg)
         assert (hip.download(Ig, (nq, k), np.int64) == Io).all()
+        # the real ranks of a row must be a permutation of 0 .. found-1, checked on every engine; a second handle with
+        # n_probe 64 and k = 100 (within the MFMA select's limits: the filter path, where the default engine applies)
+        gpu2 = vip.load(str(tmp_path / "index"), str(tmp_path / "shards"), X.shape[1])
+        k2 = 100
+        P2 = min(64, nl)
+        probes2, order2 = hip.alloc(nq * P2 * 4), hip.alloc(nq * P2 * 4)
+        assert gpu2.probe_device(xq, nq, 64, probes2, order2) == P2
+        D2, I2, T2 = hip.alloc(nq * k2 * 4), hip.alloc(nq * k2 * 8), hip.alloc(nq * k2 * 8)
+        gpu2.search_probed_device(xq, nq, k2, P2, probes2, order2, D2, I2, T2)
+        rc, Do2, Io2 = orc.search_batch(Q, k2, P2)
+        assert rc == O.ORC_OK and (hip.download(I2, (nq, k2), np.int64) == Io2).all()
+        good_p2, good_o2 = hip.download(probes2, (nq, P2), np.uint32), hip.download(order2, (nq, P2), np.uint32)
+        for h, kk, PP, gp, go, dd, ii, tt in ((gpu, k, P, good_p, good_o, Dg, Ig, Tg), (gpu2, k2, P2, good_p2, good_o2, D2, I2, T2)):
+            assert (np.sort(go, axis=1) == np.arange(PP, dtype=np.uint32)).all()   # the product's own orders are permutations
+            bp, bo = gp.copy(), go.copy()
+            bo[3, 1] = bo[3, 0]
+            cases = {"duplicated rank": (bp, bo)}
+            bp, bo = with_trailing_marker(gp, go, 11)
+            j = int(np.nonzero(bo[11, :PP - 1] == PP - 2)[0][0])
+            bo[11, j] = PP - 1                                           # distinct, but >= found = PP - 1
+            cases["rank >= found before a trailing marker"] = (bp, bo)
+            for what, (bp, bo) in cases.items():
+                with pytest.raises(N.ViError) as e:
+                    h.search_probed_device(xq, nq, kk, PP, hip.upload(bp), hip.upload(bo), dd, ii, tt)
+                assert e.value.kind == "InvalidInput", (what, PP, kk)
+        gpu2.search_probed_device(xq, nq, k2, P2, probes2, order2, D2, I2, T2)
+        assert (hip.download(I2, (nq, k2), np.int64) == Io2).all()
     finally:
         hip.close()
+
+
+def with_trailing_marker(good_p, good_o, row):
+    """row `row` with its last probe replaced by the empty marker and its remaining ranks renumbered to 0 .. P-2"""
+    bp, bo = good_p.copy(), good_o.copy()
+    P = bp.shape[1]
+    dropped = int(bo[row, P - 1])
+    bp[row, P - 1] = 0xFFFFFFFF
+    bo[row, P - 1] = 0xFFFFFFFF
+    bo[row, :P - 1] -= (bo[row, :P - 1] > dropped).astype(np.uint32)
+    return bp, bo
 
 
 def test_striped_ranks_beyond_the_wave_select_limits(tmp_path):

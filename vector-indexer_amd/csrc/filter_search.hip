@@ -1960,34 +1960,46 @@ __global__ void __launch_bounds__(256) coarse_select_direct_kernel(CoarseSelectA
   // everything): the ballot loop below, which drains the list as it fills.
   bool listed = false;
   if (!(c.xmode & 16u)) {
-    uint32_t cls = 0, rowbits = 0, mine = 0;  // 2 bits per sub-block: 0 none, 1 the row of the minimum, 2 all eight; 3 bits: that row
+    // 2 bits per sub-block in cls: 0 none, 1 the row of the minimum, 2 all eight; 4 bits per sub-block for that row,
+    // sub-blocks 0-15 in rows_lo and 16-31 in rows_hi (the word is chosen at compile time in the flag loop: a runtime
+    // index into a register array would put it in scratch)
+    constexpr uint32_t kSub = 2u * kPer, kSubPerWord = 16u;  // sub-blocks per lane; per rows word
+    static_assert(2u * kSub <= 64u, "cls holds 2 bits for each of a lane's sub-blocks");
+    static_assert(kSub <= 2u * kSubPerWord && 4u * kSubPerWord <= 64u, "rows_lo / rows_hi hold 4 bits for each sub-block");
+    uint64_t cls = 0, rows_lo = 0, rows_hi = 0;
+    uint32_t mine = 0;
 #pragma unroll
     for (uint32_t i = 0; i < kPer; ++i)
       if (i * kWave < nrec) {
         const uint32_t rec = i * kWave + lane;
 #pragma unroll
         for (uint32_t s2 = 0; s2 < 2; ++s2) {
+          const uint32_t sb = 2u * i + s2;
           const bool cand = rec < nrec && !(rb1[i][s2] > thr);
           const bool all8 = cand && (!(rb2[i][s2] > thr) || distrust);
-          const uint32_t k = all8 ? 2u : (cand ? 1u : 0u);
-          cls |= k << (2u * (2u * i + s2));
-          rowbits |= (__float_as_uint(rb1[i][s2]) & 7u) << (3u * (2u * i + s2));
+          const uint64_t k = all8 ? 2u : (cand ? 1u : 0u);
+          cls |= k << (2u * sb);
+          const uint64_t row = __float_as_uint(rb1[i][s2]) & 7u;
+          if (sb < kSubPerWord) rows_lo |= row << (4u * sb);
+          else rows_hi |= row << (4u * (sb - kSubPerWord));
           mine += all8 ? 8u : (cand ? 1u : 0u);
         }
       }
     const uint32_t incl = wave_incl_scan_u32(mine);
     const uint32_t total = readlane_u(incl, 63);
     if (total <= kPickCap) {
-      uint32_t at = incl - mine, left = cls;
+      uint32_t at = incl - mine;
+      uint64_t left = cls;
       // (a lane flags 0.7 of its 8 sub-blocks on average: as many rounds as the busiest lane has flags — three or four —
       //  each lane taking its next flagged sub-block, instead of eight rounds of mostly idle lanes)
       while (__ballot(left != 0u)) {
         if (left != 0u) {
-          const uint32_t sb = (uint32_t)__builtin_ctz(left) >> 1;
-          const uint32_t k = (left >> (2u * sb)) & 3u, rec = (sb >> 1) * kWave + (uint32_t)lane;
-          left &= ~(3u << (2u * sb));
+          const uint32_t sb = (uint32_t)__builtin_ctzll(left) >> 1;
+          const uint32_t k = (uint32_t)(left >> (2u * sb)) & 3u, rec = (sb >> 1) * kWave + (uint32_t)lane;
+          left &= ~(3ull << (2u * sb));
           if (k == 1u) {
-            pick[at] = sub_row(rec, sb & 1u, (rowbits >> (3u * sb)) & 7u);
+            const uint64_t rows = sb < kSubPerWord ? rows_lo : rows_hi;
+            pick[at] = sub_row(rec, sb & 1u, (uint32_t)(rows >> (4u * (sb % kSubPerWord))) & 7u);
             at += 1u;
           } else {
 #pragma unroll

@@ -577,15 +577,31 @@ __global__ void group_scatter_ranked_kernel(const uint32_t *probes, const uint32
   if (pair_pos) pair_pos[i] = pos - seg_start[l];
 }
 
-// caller-supplied probe lists (multi-GPU: another rank's coarse step): every probe must name a list of this index or be the
-// empty marker, the real probes of a row must come first, and the candidate-order ranks must be a rank < P or the marker
-__global__ void validate_probes_kernel(const uint32_t *probes, const uint32_t *order, uint32_t total, uint32_t P,
-                                       uint32_t nlists, uint32_t *bad) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= total) return;
-  const uint32_t l = probes[i], g = order[i];
-  bool ok = (l < nlists && g < P) || (l == kNoPos);
-  if (ok && l != kNoPos && (i % P) != 0 && probes[i - 1] == kNoPos) ok = false;
+// caller-supplied probe lists (multi-GPU: another rank's coarse step), one wave per row: every probe must name a list of
+// this index or be the empty marker, the real probes of a row must come first, and their candidate-order ranks must be
+// distinct and below the row's number of real probes (a permutation of 0 .. found-1: the MFMA select inverts it with one
+// ds_permute).  The ranks of the markers are not read.  A bitmap of the ranks seen in LDS, (P + 31) / 32 words.
+__global__ void __launch_bounds__(64) validate_probes_kernel(const uint32_t *probes, const uint32_t *order, uint32_t P,
+                                                             uint32_t nlists, uint32_t *bad) {
+  extern __shared__ uint32_t seen[];
+  const uint32_t q = blockIdx.x, lane = threadIdx.x, words = (P + 31u) / 32u;
+  const uint32_t *row = probes + (size_t)q * P, *ord = order + (size_t)q * P;
+  for (uint32_t w = lane; w < words; w += 64u) seen[w] = 0u;
+  bool ok = true;
+  uint32_t found = 0;
+  for (uint32_t r0 = 0; r0 < P; r0 += 64u) {
+    const uint32_t r = r0 + lane;
+    const uint32_t l = r < P ? row[r] : kNoPos;
+    const bool real = l != kNoPos;
+    if (real && (l >= nlists || (r > 0 && row[r - 1] == kNoPos))) ok = false;
+    found += (uint32_t)__popcll(__ballot(real));
+  }
+  __syncthreads();
+  for (uint32_t r = lane; r < P; r += 64u) {
+    if (row[r] == kNoPos) continue;
+    const uint32_t g = ord[r];
+    if (g >= found || (atomicOr(&seen[g >> 5], 1u << (g & 31u)) >> (g & 31u)) & 1u) ok = false;
+  }
   if (!ok) atomicOr(bad, 1u);
 }
 
@@ -1243,7 +1259,7 @@ vi_status adopt_probes(const DeviceIndex &ix, uint64_t nq, uint32_t P, const uin
   VI_TRY(ws.probe_flag.reserve(1));
   const uint32_t total = (uint32_t)(nq * P);
   VI_HIP(hipMemsetAsync(ws.probe_flag.p, 0, 4, st));
-  hipLaunchKernelGGL(validate_probes_kernel, dim3((total + 255) / 256), dim3(256), 0, st, probes_in, order_in, total, P,
+  hipLaunchKernelGGL(validate_probes_kernel, dim3((uint32_t)nq), dim3(64), ((P + 31u) / 32u) * 4u, st, probes_in, order_in, P,
                      (uint32_t)nlists, ws.probe_flag.p);
   VI_HIP(hipGetLastError());
   uint32_t bad = 0;
@@ -1253,7 +1269,8 @@ vi_status adopt_probes(const DeviceIndex &ix, uint64_t nq, uint32_t P, const uin
   VI_HIP(hipStreamSynchronize(st));
   if (bad)
     return fail(VI_ERR_INVALID_INPUT, "probe lists out of range: every probe must be < %llu (or the empty marker 0xFFFFFFFF "
-                "after the last real probe of a row) and every order < n_probe_eff", (unsigned long long)nlists);
+                "after the last real probe of a row), and the orders of a row's real probes must be distinct and below "
+                "its number of real probes", (unsigned long long)nlists);
   if (histogram) {
     VI_TRY(ws.cnt.reserve(2 * subbin_words(nlists)));
     VI_HIP(hipMemsetAsync(ws.cnt.p, 0, subbin_words(nlists) * sizeof(uint32_t), st));
