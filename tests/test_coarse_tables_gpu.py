@@ -3,7 +3,8 @@ direct select (coarse_select_direct_kernel, up to 256 blocks of 64 centroids) ru
 
 A lane of the direct select owns 16 records, i.e. up to 32 sub-blocks of 8 centroids; the list counts below sit on the
 boundaries of its per-lane flag words (sub-block 10 from 5 121 lists, sub-block 16 from 8 193 lists) and of the direct
-table itself (256 blocks).  Every check is exact:
+table itself (256 blocks).  The 1 027-list table at D = 256 takes the VALU coarse step, in search and probe export
+alike.  Every check is exact:
 
   probe lists   vi_indexer_probe_device against the oracle's (distance, centroid index) order, and each order row a
                 permutation of 0 .. found-1 — the coarse kernel alone, before the list scan can mask a wrong probe;
@@ -41,13 +42,11 @@ TABLES = {
     "16383": (16384, 20, "gauss", 513, 16777),    # 256 blocks at D = 20
     "16384": (16385, 128, "gauss", 513, 17126),   # the last direct table: 256 full blocks
     "16388": (16385, 128, "gauss", 256, 17110),   # 257 blocks: the non-direct select
+    "1027": (1040, 256, "gauss", 256, 1070),      # D = 256: the VALU coarse step (filter_kernel keeps D <= 128)
 }
 
 KNOBS = {
     "f32 MFMA coarse": {"VI_FILTER_BF16": "0"},
-    "unstaged rows": {"VI_COARSE_STAGED": "0"},
-    "records by block": {"VI_COARSE_QMAJOR": "0"},
-    "rows from the block image": {"VI_COARSE_ROWS": "0"},
     "non-direct select": {"VI_COARSE_DIRECT": "0"},
 }
 # (VI_SELECT_XMODE_COARSE=16 is an ablation with wrong results: it skips the row listing altogether, the ballot loop too)

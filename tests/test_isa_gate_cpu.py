@@ -64,7 +64,7 @@ def block_loop(body):
     return "\n".join(with_barrier[0])
 
 
-def test_rank_kernels_do_not_spill_and_keep_one_store_per_block(asm):
+def test_rank_kernels_do_not_spill_and_keep_their_record_stores_per_block(asm):
     ks = kernels(asm)
     assert len(ks) >= 16
     dbl = {n: k for n, k in ks.items() if k["nbuf"] >= 2}
@@ -77,16 +77,14 @@ def test_rank_kernels_do_not_spill_and_keep_one_store_per_block(asm):
         loop = block_loop(k["body"])
         stores = re.findall(r"^\s*global_store_\w+", loop, re.M)
         # one pair-record store per block; the coarse-table instantiations also hold the two stores of the direct records
-        # in their two layouts (by block / query-major) — three exclusive paths, waited for with vmcnt(1) / vmcnt(2)
-        want = 5 if k["table"] else 1
+        # (query-major) — two exclusive paths, waited for with vmcnt(1) / vmcnt(2)
+        want = 3 if k["table"] else 1
         assert stores == ["\tglobal_store_dwordx4"] * want, f"{name}: stores in the block loop: {stores}"
         loads = re.findall(r"^\s*global_load_(?!lds)\w+", loop, re.M)
         assert not loads, f"{name}: plain global loads inside the block loop: {loads}"
         assert re.search(r"global_load_lds_dwordx4", loop), name
         waits = re.findall(r"s_waitcnt vmcnt\((\d+)\)", loop)
         allowed = {"0", "1", "2"} if k["table"] else {"0", "1"}
-        if k["nbuf"] == 3:  # ring of three: the wait also leaves this iteration's LDS-DMA (<= 5 per wave) in flight
-            allowed = {str(i) for i in range(8)}
         assert "1" in waits and set(waits) <= allowed, f"{name}: vmcnt waits {waits}"
 
 

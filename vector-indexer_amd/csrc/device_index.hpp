@@ -170,6 +170,38 @@ struct SearchIO {
   uint32_t *probes_out = nullptr, *order_out = nullptr;      // coarse step only: probe lists + candidate-order ranks
 };
 vi_status device_index_search(const DeviceIndex &ix, const SearchIO &io);
+
+// The search engines' environment options (filter_search.hip, search_kernels.hip), read once per device_index_search
+// call by read_engine_knobs.  A '0' as the first character turns an on-by-default option off.
+struct EngineKnobs {
+  bool force_generic;       // VI_FORCE_GENERIC (non-zero): the generic engine
+  uint32_t force_qg;        // VI_FORCE_QG: queries per group of the VALU list scan (0: chosen)
+  uint32_t seg_blocks;      // VI_SEG_BLOCKS: blocks per list segment of the VALU list scan
+  bool filter;              // VI_FILTER=0: the VALU engine instead of the MFMA engine
+  bool rank_bf16;           // VI_FILTER_BF16=0: rank with f32 MFMAs instead of bf16 x 3
+  bool hi_only;             // VI_FILTER_HI_ONLY=0: never rank from the hi planes alone
+  int rank_approx;          // VI_RANK_APPROX: hi-plane ranking of real-valued lists, 0..2 (-1: chosen per index)
+  bool debug_approx;        // VI_DEBUG_APPROX: print what rank_approx_mode chose by
+  bool coarse_filter;       // VI_COARSE_FILTER=0: never run the coarse step on the matrix cores
+  bool coarse_direct;       // VI_COARSE_DIRECT=0: the coarse select with group records on tables of <= 256 blocks too
+  uint32_t segb0;           // VI_FILTER_SEGB: blocks per list segment of the MFMA list phase
+  uint32_t gq;              // VI_FILTER_GQ: queries per rank work item, 32 or 128 (0: chosen)
+  bool stream_off;          // VI_RANK_STREAM=0: the block-synchronous rank kernel
+  bool stream_force;        // VI_RANK_STREAM=1: the streaming rank kernel for any D <= 128
+  bool stream_gq256;        // VI_STREAM_GQ=256: streaming groups of 256 bf16-exact queries
+  bool rank_i8;             // VI_RANK_I8=0: rank 8-bit descriptors with bf16
+  uint32_t item_run;        // VI_ITEM_RUN: work items of one tile stream dealt to one XCD in a row
+  bool stream_prof;         // VI_STREAM_PROF: clock the streaming rank kernel
+  const char *stream_prof_dump;  // VI_STREAM_PROF_DUMP: file for its per-workgroup clocks, or null
+  uint32_t filter_xmode;    // VI_FILTER_XMODE: rank kernel ablations
+  uint32_t select_xmode;    // VI_SELECT_XMODE: list select ablations (wrong results)
+  uint32_t coarse_xmode;    // VI_SELECT_XMODE_COARSE: coarse select ablations (wrong results)
+  // VI_FILTER_STATS (set): the selects' counters; '2': the coarse select's instead, and its clocks; '3' / '4': print
+  // the list select's clocks and counters; '4': count every 64th query only
+  bool stats, stats_coarse, stats_print;
+  uint32_t stats_mask;
+};
+EngineKnobs read_engine_knobs();
 // squared norms of the stored vectors (filter_search.hip); called at the end of every index upload
 vi_status compute_slot_norms(DeviceIndex *ix);
 

@@ -479,12 +479,11 @@ struct FilterArgs {
   const uint32_t *qoff, *rel;  // group-record offsets (lists) ...
   uint32_t rec_stride;         // ... or a fixed number of records per slot when qoff is null (coarse table)
   const uint32_t *tile_start;  // pair records: first record tile (2 * GQ records) of each list
-  const uint32_t *item_list;   // list of each work item (null: binary search over item_start)
   const uint4 *items;          // list phase: the work items' descriptors (item_desc_kernel), or null: derived here
   float4 *gval;                // group records: the four smallest sub-block minima of a (pair, segment, lane half)
   uint32_t *gmeta;             // ... and where the record belongs: probe rank | segment << 6 | lane half << 13
   float4 *brec;                // pair records: the sub-block minima of two blocks
-  const uint4 *qimg;  // -2 q of the batch split hi / lo once per search (split_queries_kernel), or null: split here
+  const uint4 *qimg;  // bf16 ranking: -2 q of the batch split hi / lo once per search (split_queries_kernel)
   uint32_t direct;  // coarse table only: records = the minima of the 8-row sub-blocks of every block, no group records
   uint32_t xmode;  // experiment knob (VI_FILTER_XMODE): 1 = do not restage tiles, 2 = no ranking epilogue
 };
@@ -530,21 +529,6 @@ __device__ __forceinline__ void tile_dma_rank(float *tile, const float4 *src, co
 __global__ void split_queries_kernel(const float *Q, uint32_t nq, uint32_t dim, uint32_t nc, uint4 *out, unsigned long long *any_lo,
                                      uint32_t *zero, uint32_t zero_words, const float *mu, uint2 *out8, unsigned long long *not_i8);
 
-// s_waitcnt vmcnt(n) for a wave-uniform run-time n (the instruction takes an immediate)
-__device__ __forceinline__ void wait_vmcnt(uint32_t n) {
-  switch (n) {
-    case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-    case 1: asm volatile("s_waitcnt vmcnt(1)" ::: "memory"); break;
-    case 2: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
-    case 3: asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); break;
-    case 4: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
-    case 5: asm volatile("s_waitcnt vmcnt(5)" ::: "memory"); break;
-    case 6: asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); break;
-    case 7: asm volatile("s_waitcnt vmcnt(7)" ::: "memory"); break;
-    default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;  // (never asked for more than 7; a stricter wait is always safe)
-  }
-}
-
 // NG = dq/2 exactly: a block holds 2*NG quads (dims padded to 16); dim % 4 == 0.  TABLE only names the instance
 // that ranks the centroid table (coarse step), so that profiles tell it from the list scan.
 // RANK 0: f32 MFMA (eight per 16 dims).  RANK 1: three bf16 MFMAs per 16 dims (hi.hi + hi.lo + lo.hi).
@@ -572,15 +556,10 @@ __global__ void __launch_bounds__(GQ * 2, GQ == 32 ? (RANK == 2 ? 2 : 1) : ((NBU
     b1 = (uint32_t)__builtin_amdgcn_readfirstlane((int)d1.x); seg = (uint32_t)__builtin_amdgcn_readfirstlane((int)d1.y);
     rec0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)d1.z);
   } else {
-    uint32_t lo = 0;
-    if (a.item_list) {
-      lo = a.item_list[item];
-    } else {
-      uint32_t hi = a.nlists;
-      while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (a.item_start[mid] <= item) lo = mid; else hi = mid;
-      }
+    uint32_t lo = 0, hi = a.nlists;
+    while (hi - lo > 1) {
+      const uint32_t mid = (lo + hi) >> 1;
+      if (a.item_start[mid] <= item) lo = mid; else hi = mid;
     }
     const uint32_t l = (uint32_t)__builtin_amdgcn_readfirstlane((int)lo);
     const uint32_t s0 = a.seg_start[l], cnt = a.seg_start[l + 1] - s0;
@@ -624,25 +603,13 @@ __global__ void __launch_bounds__(GQ * 2, GQ == 32 ? (RANK == 2 ? 2 : 1) : ((NBU
       if (qlive && e < a.dim) v = *reinterpret_cast<const float4 *>(qrow + e);
       qf[g] = make_float4(-2.f * v.x, -2.f * v.y, -2.f * v.z, -2.f * v.w);
     }
-  } else if (a.qimg) {
+  } else {
     // the batch's queries were split once (every query sits in n_probe work items): 16-byte pieces, no arithmetic here
     const uint4 *qi = a.qimg + (size_t)qid * (NG / 2) * 4 + h;  // [plane][chunk][half]
 #pragma unroll
     for (int c = 0; c < NG / 2; ++c) {
       uint4 hi = make_uint4(0u, 0u, 0u, 0u), lo = hi;
       if (qlive) { hi = qi[c * 2]; lo = qi[NG + c * 2]; }
-      qf[2 * c] = __builtin_bit_cast(float4, hi);
-      qf[2 * c + 1] = __builtin_bit_cast(float4, lo);
-    }
-  } else {
-#pragma unroll
-    for (int c = 0; c < NG / 2; ++c) {
-      const uint32_t e = 16 * c + 8 * h;
-      float4 v0 = make_float4(0.f, 0.f, 0.f, 0.f), v1 = v0;
-      if (qlive && e < a.dim) v0 = *reinterpret_cast<const float4 *>(qrow + e);
-      if (qlive && e + 4 < a.dim) v1 = *reinterpret_cast<const float4 *>(qrow + e + 4);
-      uint4 hi, lo;
-      split8(v0, v1, -2.0f, hi, lo);
       qf[2 * c] = __builtin_bit_cast(float4, hi);
       qf[2 * c + 1] = __builtin_bit_cast(float4, lo);
     }
@@ -664,32 +631,17 @@ __global__ void __launch_bounds__(GQ * 2, GQ == 32 ? (RANK == 2 ? 2 : 1) : ((NBU
   const uint32_t bi = rec0 * (2u * GQ) + (uint32_t)GQ * (uint32_t)h + jq_grp;
 
   // LDS-DMA instructions this wave issues per tile (RANK 2: its share of the NG hi pieces; wave 0 also the norms)
-  const uint32_t dma_ops = (RANK == 2 ? ((uint32_t)wave < (uint32_t)NG ? ((uint32_t)NG - (uint32_t)wave + WAVES - 1) / WAVES : 0u)
-                                      : (uint32_t)(2 * NG / WAVES)) + (wave == 0 ? 1u : 0u);
-  if (NBUF == 3 && b0 + 1 < b1 && !(a.xmode & 1u)) {  // ring of three: two tiles ahead
-    tile_dma_rank<NG, RANK, NBUF, WAVES>(s_tiles[1], a.blocks + ((size_t)(fb + b0 + 1) * a.dq) * kWave, a.xnorm + (size_t)(fb + b0 + 1) * kWave, wave, lane);
-    wait_vmcnt(dma_ops);  // the first tile has landed, the second may still be on its way
-  } else {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's pieces have landed ...
-  }
-  __syncthreads();                     // ... and so have everyone else's
-  uint32_t ring = 0;                   // buffer of the current block (NBUF == 3)
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's pieces have landed ...
+  __syncthreads();                                   // ... and so have everyone else's
   for (uint32_t blk = b0; blk < b1; ++blk) {
     const bool more = (blk + 1 < b1) && !(a.xmode & 1u);
     uint32_t nstores = 0;  // record stores this lane issued in this iteration
-    const float *s_tile = s_tiles[NBUF == 3 ? ring : (NBUF == 2 ? ((blk - b0) & 1u) : 0)];
+    const float *s_tile = s_tiles[NBUF == 2 ? ((blk - b0) & 1u) : 0];
     // next block: lands in the other buffer during this block's MFMAs (every wave left that buffer at the
-    // barrier that ended the previous iteration); with three buffers the block after the next is requested here, so
-    // that two tiles per workgroup are in flight (an experiment, VI_FILTER_NBUF=3: it measured equal)
-    uint32_t issued = 0;  // LDS-DMA instructions of this iteration (younger than the tile the block's end waits for)
+    // barrier that ended the previous iteration)
     if (NBUF == 2 && more)
       tile_dma_rank<NG, RANK, NBUF, WAVES>(s_tiles[((blk - b0) & 1u) ^ 1u], a.blocks + ((size_t)(fb + blk + 1) * a.dq) * kWave,
                    a.xnorm + (size_t)(fb + blk + 1) * kWave, wave, lane);
-    if (NBUF == 3 && blk + 2 < b1 && !(a.xmode & 1u)) {
-      tile_dma_rank<NG, RANK, NBUF, WAVES>(s_tiles[ring >= 1 ? ring - 1 : 2], a.blocks + ((size_t)(fb + blk + 2) * a.dq) * kWave,
-                   a.xnorm + (size_t)(fb + blk + 2) * kWave, wave, lane);
-      issued = dma_ops;
-    }
     if (wave_live) {
       // both row tiles (vectors 0..31 and 32..63) advance together: two independent accumulator chains
       f32x16 acc0, acc1;
@@ -778,16 +730,10 @@ __global__ void __launch_bounds__(GQ * 2, GQ == 32 ? (RANK == 2 ? 2 : 1) : ((NBU
         nstores = qlive ? 2u : 0u;
         if (qlive) {
           const float2 s00 = tile_min8_idx(acc0, 0), s01 = tile_min8_idx(acc0, 8), s10 = tile_min8_idx(acc1, 0), s11 = tile_min8_idx(acc1, 8);
-          if (a.direct == 2u) {
-            // query-major: the select reads a query's records as 1 KB runs (these stores pay for it: 32 queries x 32 bytes each)
-            float4 *dst = a.brec + ((size_t)chunk * GQ + jq_grp) * (4u * nblk) + 4u * blk + (uint32_t)h;
-            dst[0] = make_float4(s00.x, s00.y, s01.x, s01.y);
-            dst[2] = make_float4(s10.x, s10.y, s11.x, s11.y);
-          } else {
-            float4 *dst = a.brec + ((size_t)chunk * nblk + blk) * (4u * GQ) + (uint32_t)GQ * (uint32_t)h + jq_grp;
-            dst[0] = make_float4(s00.x, s00.y, s01.x, s01.y);
-            dst[2u * GQ] = make_float4(s10.x, s10.y, s11.x, s11.y);
-          }
+          // query-major: the select reads a query's records as 1 KB runs (these stores pay for it: 32 queries x 32 bytes each)
+          float4 *dst = a.brec + ((size_t)chunk * GQ + jq_grp) * (4u * nblk) + 4u * blk + (uint32_t)h;
+          dst[0] = make_float4(s00.x, s00.y, s01.x, s01.y);
+          dst[2] = make_float4(s10.x, s10.y, s11.x, s11.y);
         }
       } else if (!(a.xmode & 2u)) {
         // all that is kept of the two 16-row sub-blocks: their minima
@@ -815,10 +761,7 @@ __global__ void __launch_bounds__(GQ * 2, GQ == 32 ? (RANK == 2 ? 2 : 1) : ((NBU
       // insert vmcnt(0), hence the raw barrier (LDS reads of this tile are complete: lgkmcnt(0)).
       // (a store instruction is issued iff some lane of the wave stores: the ballots are the wave-uniform form of that)
       const uint32_t st_ops = __ballot(nstores == 2u) != 0ull ? 2u : (__ballot(nstores == 1u) != 0ull ? 1u : 0u);
-      if (NBUF == 3) {
-        wait_vmcnt(issued + st_ops);  // everything but this iteration's DMA and stores: the NEXT block's tile has landed
-        ring = ring == 2 ? 0 : ring + 1;
-      } else if (st_ops == 2u) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+      if (st_ops == 2u) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
       else if (st_ops == 1u) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
       else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -1790,12 +1733,11 @@ struct CoarseSelectArgs {
   uint32_t nq, P, nlists, segb, recs;  // recs = group records per query
   const uint32_t *list_shard, *list_len;
   uint32_t *probes, *gorder, *cnt;
-  uint32_t query_major;  // direct records laid out [query][record] (filter_kernel: a.direct == 2)
-  const float4 *cent_rows;  // the table row-major (rows_from_blocks_kernel) for single-row re-evaluation, or null
+  const float4 *cent_rows;  // the table row-major (rows_from_blocks_kernel) for single-row re-evaluation
   // record counts of the list phase (what pair_groups_kernel computes otherwise)
   uint32_t list_segb0;
   uint32_t *rel, *qtot;
-  uint32_t staged;  // single rows fetched by the whole wave through LDS (exact_batch_rows_staged_fn); VI_COARSE_STAGED=0: a row per lane
+  uint32_t staged;  // single rows fetched by the whole wave through LDS (exact_batch_rows_staged_fn, D % 16 == 0), else a row per lane
   uint32_t *pair_rank;  // where the pair stands among the pairs of its (list, sub-bin) — the value its histogram
                         // increment returns — so that the grouping's scatter needs no atomics of its own; or null
 };
@@ -1886,15 +1828,12 @@ __global__ void __launch_bounds__(256) coarse_select_direct_kernel(CoarseSelectA
   const float E = c.e_scale * (qn * (1.0f + c.gamma) + 2.0f * c.xmax2);
   const bool distrust = !(qn < 1.0e30f);  // see select_body
   const uint32_t K = a.P, nblk = (a.nlists + kWave - 1) / kWave, nrec = 4u * nblk;  // records: (block, tile, lane half)
-  const size_t base = (size_t)(q / c.gq) * nblk * (4u * c.gq) + (q % c.gq);
   constexpr uint32_t kPer = kDirectBlocks * 4 / kWave;  // records per lane
   // (min of sub-block 0 with its row, its second min, the same of sub-block 1)
   auto record = [&](uint32_t i) {
     const uint32_t rec = i * kWave + lane;  // block rec >> 2, tile (rec >> 1) & 1, lane half rec & 1
     float4 r = make_float4(INFINITY, INFINITY, INFINITY, INFINITY);
-    if (rec < nrec)
-      r = a.query_major ? c.brec[(size_t)q * nrec + rec]
-                        : c.brec[base + (size_t)(rec >> 2) * (4u * c.gq) + (size_t)((rec >> 1) & 1u) * (2u * c.gq) + c.gq * (rec & 1u)];
+    if (rec < nrec) r = c.brec[(size_t)q * nrec + rec];
     return r;
   };
   // bound of the K-th distance: every lane's smallest minimum belongs to a different centroid, so K centroids are at
@@ -1926,11 +1865,6 @@ __global__ void __launch_bounds__(256) coarse_select_direct_kernel(CoarseSelectA
   FastTopK sel;
   sel.init();
   uint32_t npick = 0;
-  auto exact_rows = [&](bool live, uint32_t pos) {
-    live = live && pos < a.nlists && !(c.xmode & 1u);
-    sel = exact_batch_fn(sel, qlds, c.blocks + ((size_t)((live ? pos : 0u) / kWave) * c.dq) * kWave + (pos % kWave), c.dim, live, pos,
-                         (int)K);
-  };
   // sub-block s (0/1) of record rec: its first row is register 8s of tile t of lane half h
   auto sub_row = [&](uint32_t rec, uint32_t s, uint32_t e) {
     return (rec >> 2) * kWave + subblock_vector(8u * s + e, (rec >> 1) & 1u, rec & 1u, c.image_order != 0u);
@@ -1943,13 +1877,11 @@ __global__ void __launch_bounds__(256) coarse_select_direct_kernel(CoarseSelectA
       n_single += cnt;
       bool live = (uint32_t)lane < cnt;
       const uint32_t pos = live ? pick[npick + lane] : 0u;
-      if (a.cent_rows && a.staged) {  // one centroid per lane, the rows fetched by the whole wave
+      if (a.staged) {  // one centroid per lane, the rows fetched by the whole wave
         if (!(c.xmode & 1u)) sel = exact_batch_rows_staged_fn(sel, qlds, a.cent_rows, a.nlists, c.dim, cnt, pos, (int)K, s_stage[wave]);
-      } else if (a.cent_rows) {  // one centroid per lane, each its own whole cache lines
+      } else {  // one centroid per lane, each its own whole cache lines
         live = live && pos < a.nlists && !(c.xmode & 1u);
         sel = exact_batch_row_fn(sel, qlds, a.cent_rows + (size_t)(live ? pos : 0u) * (c.dim / 4), c.dim, live, pos, (int)K);
-      } else {
-        exact_rows(live, pos);
       }
     }
   };
@@ -2024,7 +1956,7 @@ __global__ void __launch_bounds__(256) coarse_select_direct_kernel(CoarseSelectA
       const uint32_t rec = i * kWave + lane;
       const float4 Ri = record(i);
       const float b1[2] = {Ri.x, Ri.z}, b2[2] = {Ri.y, Ri.w};
-#pragma unroll
+#pragma nounroll  // (a cold path: unrolled, its inlined exact rounds would double the kernel's code)
       for (uint32_t s2 = 0; s2 < 2; ++s2) {
         const bool cand = rec < nrec && !(b1[s2] > thr);
         const bool all8 = cand && (!(b2[s2] > thr) || distrust);
@@ -2090,13 +2022,6 @@ __global__ void __launch_bounds__(256) coarse_select_direct_kernel(CoarseSelectA
   }
 }
 
-// a ring of three tile buffers (two tiles in flight per workgroup) for the hi-planes-only list ranking: measured equal to
-// two buffers on the bench workload (0.303 ms both: the launch is not waiting on the fabric), so off unless VI_FILTER_NBUF=3
-inline bool nbuf3_ok() {
-  const char *e = getenv("VI_FILTER_NBUF");
-  return e && *e == '3';
-}
-
 template <int NG>
 vi_status launch_filter_t(const FilterArgs &a, uint32_t nitems, int rank_mode, uint32_t gq, hipStream_t st) {
   if (nitems == 0) return VI_OK;
@@ -2111,7 +2036,6 @@ vi_status launch_filter_t(const FilterArgs &a, uint32_t nitems, int rank_mode, u
     const dim3 block(256);
     if (rank_mode == 2) {  // half-size tiles: two buffers fit where one full image did, the next tile loads during the MFMAs
       if (table) hipLaunchKernelGGL((filter_kernel<NG, 2, true, 2, 128>), grid, block, 0, st, a);
-      else if (nbuf3_ok()) hipLaunchKernelGGL((filter_kernel<NG, 3, false, 2, 128>), grid, block, 0, st, a);
       else hipLaunchKernelGGL((filter_kernel<NG, 2, false, 2, 128>), grid, block, 0, st, a);
     } else if (rank_mode == 1) {  // full images: one buffer, three workgroups per CU (two buffers cost the third: measured slower)
       if (table) hipLaunchKernelGGL((filter_kernel<NG, 1, true, 1, 128>), grid, block, 0, st, a);
@@ -2139,34 +2063,19 @@ vi_status launch_filter(const FilterArgs &a, uint32_t dq, uint32_t nitems, int r
   }
 }
 
-// rank arithmetic: bf16 x 3 unless VI_FILTER_BF16=0 (f32 MFMA)
-bool rank_bf16() {
-  const char *e = getenv("VI_FILTER_BF16");
-  return !(e && *e == '0');
-}
-
-// RANK 2 (hi planes only when the stored values are bf16-exact) unless VI_FILTER_HI_ONLY=0
-bool hi_only_ok() {
-  const char *e = getenv("VI_FILTER_HI_ONLY");
-  return !(e && *e == '0');
-}
-
 // Real-valued lists (not bf16-exact) ranked from their hi planes alone instead of hi + lo (bf16 x 3): a third (queries'
 // hi + lo planes: mode 1) or a sixth (queries' hi plane only: mode 2) of the matrix work, paid for with a wider margin
 // (select_body: 2 |q| max|v - hi(v)|, plus |query residual| max|v| in mode 2 — the residual norms are measured, not
 // bounded by 2^-8 |v|: rounding to nearest leaves about a third of that), which the select turns into more sub-blocks
 // re-evaluated exactly; no result depends on a rank value (file header).  Chosen per index from its sampled spread;
 // VI_RANK_APPROX=0 / 1 / 2 forces bf16 x 3 / queries hi + lo / queries' hi plane only.
-int rank_approx_mode(const DeviceIndex &ix) {
-  if (const char *e = getenv("VI_RANK_APPROX")) {
-    const int v = atoi(e);
-    return v < 0 || v > 2 ? 1 : v;
-  }
+int rank_approx_mode(const DeviceIndex &ix, const EngineKnobs &kn) {
+  if (kn.rank_approx >= 0) return kn.rank_approx;
   // a typical query is as long as a typical stored vector, and its image's residual about twice that of a stored vector's
   const double qlen = std::sqrt((double)(ix.centered ? ix.mean_norm2_c : ix.mean_norm2));
   const double vmax = std::sqrt((double)(ix.centered ? ix.xmax2_c : ix.xmax2)), rho = std::sqrt((double)ix.rho2_max);
   const double unit1 = 2.0 * qlen * rho, unit2 = unit1 + 2.0 * rho * vmax;
-  if (getenv("VI_DEBUG_APPROX"))
+  if (kn.debug_approx)
     fprintf(stderr, "[vi] approx: centred %d qlen %.4g vmax %.4g rho %.4g spread %.4g unit1/spread %.4g unit2/spread %.4g\n", (int)ix.centered,
             qlen, vmax, rho, (double)ix.mean_spread, unit1 / (double)ix.mean_spread, unit2 / (double)ix.mean_spread);
   // The margin grows by `unit`; what it admits grows with unit / (distance of a vector to its neighbours), for which the
@@ -2177,8 +2086,8 @@ int rank_approx_mode(const DeviceIndex &ix) {
   return 0;
 }
 
-SelectCommon select_common(const DeviceIndex &ix, const float *Qd, const float4 *blocks, float xmax2, uint32_t gq, bool wave_order = false,
-                           int trunc = 0) {
+SelectCommon select_common(const DeviceIndex &ix, const EngineKnobs &kn, const float *Qd, const float4 *blocks, float xmax2, uint32_t gq,
+                           bool wave_order = false, int trunc = 0) {
   const double u = 1.01 * std::ldexp(1.0, -24);
   SelectCommon c{};
   c.Q = Qd; c.dim = ix.dim; c.dq = ix.dq; c.blocks = blocks;
@@ -2191,11 +2100,11 @@ SelectCommon select_common(const DeviceIndex &ix, const float *Qd, const float4 
   //              |x - hi| <= 2^-8 |x|, |x - hi - lo| <= 2^-17 |x|; 2 (|ql.vl| + |qr.v| + |q.vr|) <= 2 (2^-16 + 2 * 2^-17)
   //              |q||v| <= 2^-15 (|q|^2 + |v|^2) — round 2 budgeted 3 * 2^-18 here, 2.7 times too little), and
   //              (3D+2) * 2u' for the f32 accumulation of 3D exact bf16 products (2u': also covers an accumulator that truncates)
-  const double acc = rank_bf16() ? (3.0 * ix.dim + 2.0) * 2.0 * u + 1.01 * std::ldexp(1.0, -15) : (ix.dim + 2.0) * u;
+  const double acc = kn.rank_bf16 ? (3.0 * ix.dim + 2.0) * 2.0 * u + 1.01 * std::ldexp(1.0, -15) : (ix.dim + 2.0) * u;
   //   (real-valued lists ranked from their bf16 hi planes alone: SelectCommon::trunc, added per query in select_body)
   // centred images (DeviceIndex::centered): v - mu and q - mu are rounded before they are split — the ranked pair sits
   // within 2^-24 (|q'| + |v'|) of the true one, its distance within 4 * 2^-24 (|q'|^2 + |v'|^2) of the true distance
-  const bool centred = ix.centered && rank_bf16();
+  const bool centred = ix.centered && kn.rank_bf16;
   c.e_scale = (float)(acc + (centred ? 6.0 * u : 0.0));
   c.e_abs = 0.0f;
   c.trunc = (uint32_t)trunc;
@@ -2204,28 +2113,16 @@ SelectCommon select_common(const DeviceIndex &ix, const float *Qd, const float4 
   c.xmax2 = xmax2;
   c.mu = centred ? ix.centre.p : nullptr;
   c.gq = gq;
-  c.image_order = rank_bf16() ? 1u : 0u;
+  c.image_order = kn.rank_bf16 ? 1u : 0u;
   c.wave_order = wave_order ? 1u : 0u;
   c.hi_nat = nullptr;
   c.u8_nat = nullptr;
   // per-wave counters go to two addresses: 2 same-address atomics per query cost more than the whole select, so
   // they are a diagnostic (VI_FILTER_STATS=1), not part of the normal path
-  c.dbg = getenv("VI_FILTER_STATS") ? (unsigned long long *)ix.cur().ws.stats.p : nullptr;
-  { const char *e = getenv("VI_FILTER_STATS"); c.dbg_mask = e && *e == '4' ? 63u : 0u; }
-  { const char *xm = getenv("VI_SELECT_XMODE"); c.xmode = xm ? (uint32_t)atoi(xm) : 0u; }
+  c.dbg = kn.stats ? (unsigned long long *)ix.cur().ws.stats.p : nullptr;
+  c.dbg_mask = kn.stats_mask;
+  c.xmode = kn.select_xmode;
   return c;
-}
-
-uint32_t env_xmode() {
-  const char *xm = getenv("VI_FILTER_XMODE");
-  return xm ? (uint32_t)atoi(xm) : 0u;
-}
-
-// items of one tile stream dealt to the same XCD in a row (item_desc_kernel); VI_ITEM_RUN=1: plain round-robin
-uint32_t item_run() {
-  const char *e = getenv("VI_ITEM_RUN");
-  const int v = e ? atoi(e) : 8;
-  return (uint32_t)std::min(std::max(v, 1), 256);
 }
 
 }  // namespace
@@ -2451,7 +2348,7 @@ vi_status compute_slot_norms(DeviceIndex *ix) {
         ix->i8_xmax2 = (float)n2;
       }
     }
-    if (ix->lists_lo_zero && ix->dim <= kNarrowDim && !ix->lists_u8_nat.p) {  // exact re-evaluation from bf16 (select_kernel), VI_EXACT_BF16=0: from f32
+    if (ix->lists_lo_zero && ix->dim <= kNarrowDim && !ix->lists_u8_nat.p) {  // exact re-evaluation from bf16 (select_kernel)
       VI_TRY(ix->lists_hi_nat.reserve(ix->lists.nblocks * per_block / 2));
       hipLaunchKernelGGL(hi_natural_kernel, dim3((uint32_t)((nt_l + 255) / 256)), dim3(256), 0, ix->stream,
                          (const uint4 *)ix->lists_bf16.p, ix->dq / 4, ix->lists.nblocks, (uint4 *)ix->lists_hi_nat.p);
@@ -2468,8 +2365,8 @@ vi_status compute_slot_norms(DeviceIndex *ix) {
 
 // coarse quantizer on the matrix cores: the centroid table is one "list" probed by every query.
 // Leaves probes / gorder and the per-list histogram (ws.cnt) behind, like stage_coarse.
-vi_status stage_coarse_filter(const DeviceIndex &ix, const float *Qd, uint64_t nq, uint32_t P, uint32_t list_segb0,
-                              hipStream_t st, bool histogram_cleared = false) {
+vi_status stage_coarse_filter(const DeviceIndex &ix, const EngineKnobs &kn, const float *Qd, uint64_t nq, uint32_t P, hipStream_t st,
+                              bool histogram_cleared = false) {
   SearchWorkspace &ws = ix.cur().ws;
   const uint32_t dim = ix.dim, dq = ix.dq;
   const uint64_t nlists = ix.nlists;
@@ -2489,8 +2386,8 @@ vi_status stage_coarse_filter(const DeviceIndex &ix, const float *Qd, uint64_t n
   VI_TRY(ws.c_pairs.reserve(nq));
   VI_TRY(ws.gval.reserve(nq * recs * 4));
   VI_TRY(ws.gpos.reserve(nq * recs));
-  const char *de = getenv("VI_COARSE_DIRECT");
-  const bool direct = ix.centroids.nblocks <= kDirectBlocks && !(de && *de == '0');
+  const bool direct = ix.centroids.nblocks <= kDirectBlocks && kn.coarse_direct;
+  if (direct && !ix.cent_rows.p) return fail(VI_ERR_OTHER, "coarse table without its row-major copy");  // (compute_slot_norms: D <= 128)
   VI_TRY(ws.brec.reserve((uint64_t)ngroups * (direct ? 2 * ix.centroids.nblocks : (uint64_t)nseg * seg_records(segb)) * 256 * 4));
   VI_TRY(ws.stats.reserve(160));
   if (ws.c_nq != nq) {  // the table's one-list grouping depends on the batch size only
@@ -2501,34 +2398,29 @@ vi_status stage_coarse_filter(const DeviceIndex &ix, const float *Qd, uint64_t n
     VI_HIP(hipStreamSynchronize(st));  // h_seg / h_item live on this stack frame
     ws.c_nq = nq;
   }
-  bool qmajor = false;
   {
     FilterArgs a{};
-    a.blocks = rank_bf16() ? (const float4 *)ix.cent_bf16.p : (const float4 *)ix.centroids.blocks.p;
-    a.xnorm = rank_bf16() ? ix.cent_xnorm_img.p : ix.cent_xnorm.p; a.dq = dq; a.dim = dim; a.Q = Qd;
+    a.blocks = kn.rank_bf16 ? (const float4 *)ix.cent_bf16.p : (const float4 *)ix.centroids.blocks.p;
+    a.xnorm = kn.rank_bf16 ? ix.cent_xnorm_img.p : ix.cent_xnorm.p; a.dq = dq; a.dim = dim; a.Q = Qd;
     a.first_block = ix.c_first.p; a.list_len = ix.c_len.p; a.item_start = ws.c_item.p; a.seg_start = ws.c_seg.p;
     a.pairs = ws.c_pairs.p; a.nlists = 1; a.P = 1; a.segb0 = segb0;
     a.qoff = nullptr; a.rel = nullptr; a.rec_stride = recs;
     a.tile_start = ix.c_first.p;  // one list: its tiles start at 0 (c_first holds a single 0)
     a.gval = (float4 *)ws.gval.p; a.gmeta = ws.gpos.p; a.brec = (float4 *)ws.brec.p;
-    { const char *e = getenv("VI_COARSE_QMAJOR"); qmajor = direct && !(e && *e == '0'); }
-    a.direct = direct ? (qmajor ? 2u : 1u) : 0u;
-    a.qimg = rank_bf16() ? (const uint4 *)ws.qimg.p : nullptr;
-    VI_TRY(launch_filter(a, dq, ngroups * nseg, rank_bf16() ? (ix.cent_lo_zero && hi_only_ok() ? 2 : 1) : 0, kGroupQ, st));
+    a.direct = direct ? 1u : 0u;
+    a.qimg = kn.rank_bf16 ? (const uint4 *)ws.qimg.p : nullptr;
+    VI_TRY(launch_filter(a, dq, ngroups * nseg, kn.rank_bf16 ? (ix.cent_lo_zero && kn.hi_only ? 2 : 1) : 0, kGroupQ, st));
   }
   {
-    CoarseSelectArgs a{select_common(ix, Qd, (const float4 *)ix.centroids.blocks.p, rank_bf16() && ix.centered ? ix.cent_xmax2_c : ix.cent_xmax2, kGroupQ), (uint32_t)nq, P,
-                       (uint32_t)nlists, segb, recs, ix.list_shard.p, ix.list_len.p, ws.probes.p, ws.gorder.p,
-                       ws.cnt.p, qmajor ? 1u : 0u, nullptr, list_segb0, ws.pair_rel.p, ws.qtot.p};
-    { const char *e = getenv("VI_COARSE_ROWS"); if (ix.cent_rows.p && !(e && *e == '0')) a.cent_rows = (const float4 *)ix.cent_rows.p; }
-    { const char *e = getenv("VI_COARSE_STAGED"); a.staged = (e && *e == '0') || (ix.dim & 15u) ? 0u : 1u; }
-    {
-      const char *e = getenv("VI_SCATTER_RANKED");
-      ws.pair_rank_valid = !(e && *e == '0');  // (both coarse selects keep what their histogram increment returns)
-      if (ws.pair_rank_valid) { VI_TRY(ws.pair_rank.reserve(nq * P)); a.pair_rank = ws.pair_rank.p; }
-    }
-    { const char *e = getenv("VI_FILTER_STATS"); if (!(e && *e == '2')) a.c.dbg = nullptr; }  // '2': count the coarse step
-    { const char *e = getenv("VI_SELECT_XMODE_COARSE"); a.c.xmode = e ? (uint32_t)atoi(e) : 0u; }
+    // (both coarse selects keep what their histogram increment returns: the grouping's scatter ranks the pairs with it)
+    VI_TRY(ws.pair_rank.reserve(nq * P));
+    ws.pair_rank_valid = true;
+    CoarseSelectArgs a{select_common(ix, kn, Qd, (const float4 *)ix.centroids.blocks.p, kn.rank_bf16 && ix.centered ? ix.cent_xmax2_c : ix.cent_xmax2,
+                                     kGroupQ), (uint32_t)nq, P, (uint32_t)nlists, segb, recs, ix.list_shard.p, ix.list_len.p, ws.probes.p,
+                       ws.gorder.p, ws.cnt.p, (const float4 *)ix.cent_rows.p, kn.segb0, ws.pair_rel.p, ws.qtot.p,
+                       (ix.dim & 15u) ? 0u : 1u, ws.pair_rank.p};
+    if (!kn.stats_coarse) a.c.dbg = nullptr;  // '2': count the coarse step
+    a.c.xmode = kn.coarse_xmode;
     if (direct) a.c.e_scale += (float)(1.01 * std::ldexp(1.0, -20));  // the row index rides in 3 mantissa bits of the minima
     if (direct) hipLaunchKernelGGL(coarse_select_direct_kernel, dim3((uint32_t)((nq + 3) / 4)), dim3(256), 0, st, a);
     else hipLaunchKernelGGL(coarse_select_kernel, dim3((uint32_t)((nq + 3) / 4)), dim3(256), 0, st, a);
@@ -2537,30 +2429,28 @@ vi_status stage_coarse_filter(const DeviceIndex &ix, const float *Qd, uint64_t n
   return VI_OK;
 }
 
-bool filter_path_applicable(const DeviceIndex &ix, uint64_t nq, uint64_t k, uint32_t P) {
-  const char *force = getenv("VI_FILTER");
-  if (force && *force == '0') return false;
+bool filter_path_applicable(const DeviceIndex &ix, const EngineKnobs &kn, uint64_t k, uint32_t P) {
+  if (!kn.filter) return false;
   if (ix.order != VI_ORDER_SCALAR || ix.dim > kMaxFilterDim || (ix.dim & 3) || ix.dim < 4) return false;
-  if (ix.dim > kNarrowDim && !rank_bf16()) return false;  // the wide kernel ranks with bf16 x 3 only
+  if (ix.dim > kNarrowDim && !kn.rank_bf16) return false;  // the wide kernel ranks with bf16 x 3 only
   if (k > 2 * kMaxSelect || P > kMaxSelect || P < 1) return false;  // k <= 128 (WaveTop128), n_probe <= 64
   if (ix.lists.nblocks * 64ull >= (1ull << kPosBits)) return false;  // record position < 2^26, block < 2^20
   if (!(ix.xmax2 < 1.0e30f) || !(ix.cent_xmax2 < 1.0e30f)) return false;  // norms must stay far below kBig
-  (void)nq;
   // measured on the bench index from nq = 1 (0.19 ms vs 0.83 ms) to nq = 10 000 (0.93 ms vs 6 ms): the MFMA engine
   // also wins on tiny batches, because it cuts long lists into segments that run in parallel
   return true;
 }
 
-// the list-phase segment size (VI_FILTER_SEGB)
-static uint32_t list_segb0() {
-  const char *sb = getenv("VI_FILTER_SEGB");
-  return sb ? (uint32_t)std::max(1, atoi(sb)) : 32u;  // <= 2048 vectors per work item
+// the coarse step on the matrix cores (stage_coarse_filter) rather than the VALU one (stage_coarse): batches of >= 256
+// queries against tables of >= 1024 lists, D <= 128 (filter_kernel keeps a query in registers)
+bool coarse_on_matrix_cores(const DeviceIndex &ix, const EngineKnobs &kn, uint64_t nq, uint32_t P) {
+  return filter_path_applicable(ix, kn, 1, P) && kn.coarse_filter && nq >= 256 && ix.nlists >= 1024 && ix.dim <= kNarrowDim;
 }
 
 // the batch's queries as MFMA operands: -2 q split into bf16 hi / lo once (a query sits in n_probe work items)
-static vi_status build_query_image(const DeviceIndex &ix, const float *Qd, uint64_t nq, hipStream_t st, uint32_t *zero = nullptr,
-                                   uint64_t zero_words = 0) {
-  if (!rank_bf16()) return VI_OK;
+static vi_status build_query_image(const DeviceIndex &ix, const EngineKnobs &kn, const float *Qd, uint64_t nq, hipStream_t st,
+                                   uint32_t *zero = nullptr, uint64_t zero_words = 0) {
+  if (!kn.rank_bf16) return VI_OK;
   SearchWorkspace &ws = ix.cur().ws;
   const uint32_t nc = ix.dq / 4;
   VI_TRY(ws.qimg.reserve((uint64_t)nq * nc * 4 * 4));  // uint32 words: 4 pieces of 16 B per (query, chunk)
@@ -2581,15 +2471,15 @@ static vi_status build_query_image(const DeviceIndex &ix, const float *Qd, uint6
 }
 
 // coarse step alone on the matrix cores (probe export for other ranks): fills ws.probes / ws.gorder
-vi_status coarse_only_filter(const DeviceIndex &ix, const float *Qd, uint64_t nq, uint32_t P, hipStream_t st) {
+vi_status coarse_only_filter(const DeviceIndex &ix, const EngineKnobs &kn, const float *Qd, uint64_t nq, uint32_t P, hipStream_t st) {
   SearchWorkspace &ws = ix.cur().ws;
-  VI_TRY(build_query_image(ix, Qd, nq, st));
+  VI_TRY(build_query_image(ix, kn, Qd, nq, st));
   VI_TRY(ws.pair_rel.reserve(nq * P));
   VI_TRY(ws.qtot.reserve(nq));
-  return stage_coarse_filter(ix, Qd, nq, P, list_segb0(), st);
+  return stage_coarse_filter(ix, kn, Qd, nq, P, st);
 }
 
-vi_status search_filter_pipeline(const DeviceIndex &ix, const float *Qd, uint64_t nq, uint64_t k, uint32_t P, uint32_t K,
+vi_status search_filter_pipeline(const DeviceIndex &ix, const EngineKnobs &kn, const float *Qd, uint64_t nq, uint64_t k, uint32_t P,
                                  float *Dd, int64_t *Id, uint64_t *Td, uint64_t *slots, uint32_t *counts, hipStream_t st,
                                  int timing_level, const uint32_t *probes_in, const uint32_t *order_in) {
   SearchWorkspace &ws = ix.cur().ws;
@@ -2599,33 +2489,30 @@ vi_status search_filter_pipeline(const DeviceIndex &ix, const float *Qd, uint64_
   const bool timing = timing_level == 1, rank_timing = timing_level != 0;
   const uint32_t dq = ix.dq;
   const uint64_t nlists = ix.nlists;
-  (void)K;
-  const uint32_t segb0 = list_segb0();
+  const uint32_t segb0 = kn.segb0;
   VI_TRY(ws.pair_rel.reserve(nq * P));
   VI_TRY(ws.qtot.reserve(nq));
   VI_TRY(ws.qoff.reserve(nq + 1));
   VI_TRY(ws.stats.reserve(160));
-  if (getenv("VI_FILTER_STATS")) {
+  if (kn.stats) {
     VI_HIP(hipMemsetAsync(ws.stats.p + 6, 0, 6 * sizeof(uint64_t), st));
     VI_HIP(hipMemsetAsync(ws.stats.p + 150, 0, 8 * sizeof(uint64_t), st));
   }
   ws.pair_rank_valid = false;  // (set by the direct coarse select of THIS search)
   if (timing) VI_HIP(hipEventRecord(ix.cur().ev[0], st));
   // the batch's queries as MFMA operands: -2 q split into bf16 hi / lo once (a query sits in n_probe work items)
-  const char *cf = getenv("VI_COARSE_FILTER");
-  const bool coarse_mfma = !probes_in && !(cf && *cf == '0') && nq >= 256 && nlists >= 1024 && ix.dim <= kNarrowDim && rank_bf16();
-  if (coarse_mfma) {  // (its per-list histogram is cleared by the kernel that splits the queries)
+  const bool coarse_mfma = !probes_in && coarse_on_matrix_cores(ix, kn, nq, P);
+  const bool histogram_cleared = coarse_mfma && kn.rank_bf16;
+  if (histogram_cleared) {  // (the coarse step's per-list histogram is cleared by the kernel that splits the queries)
     VI_TRY(ws.cnt.reserve(2 * subbin_words(nlists)));
-    VI_TRY(build_query_image(ix, Qd, nq, st, ws.cnt.p, subbin_words(nlists)));
+    VI_TRY(build_query_image(ix, kn, Qd, nq, st, ws.cnt.p, subbin_words(nlists)));
   } else {
-    VI_TRY(build_query_image(ix, Qd, nq, st));
+    VI_TRY(build_query_image(ix, kn, Qd, nq, st));
   }
   // ---- 1. coarse quantizer: probes, shard visiting order, per-list histogram, record offsets ----
   {
     if (coarse_mfma) {
-      VI_TRY(stage_coarse_filter(ix, Qd, nq, P, segb0, st, true));
-    } else if (!probes_in && !(cf && *cf == '0') && nq >= 256 && nlists >= 1024 && ix.dim <= kNarrowDim) {
-      VI_TRY(stage_coarse_filter(ix, Qd, nq, P, segb0, st));
+      VI_TRY(stage_coarse_filter(ix, kn, Qd, nq, P, st, histogram_cleared));
     } else {
       if (probes_in) VI_TRY(adopt_probes(ix, nq, P, probes_in, order_in, true, st));
       else VI_TRY(stage_coarse(ix, Qd, nq, P, st));
@@ -2646,11 +2533,10 @@ vi_status search_filter_pipeline(const DeviceIndex &ix, const float *Qd, uint64_
   // 128-query grouping has (pairs per tile slot; the grouping counts its tiles whichever size runs).  The mean alone is
   // wrong on skewed indexes: the reference's k-means on unclustered data leaves a few enormous lists that every query
   // probes (C5-shaped run: 4.9 queries per list on average, yet 128-query groups are three quarters full).
-  const char *gqe = getenv("VI_FILTER_GQ");
   uint32_t gq = (double)nq * P / (double)std::max<uint64_t>(1, nlists) >= 24.0 ? 128u : 32u;
   for (const auto &h : ws.gq_hint)
     if (h.nq == nq && h.P == P) gq = h.gq;
-  if (gqe) gq = atoi(gqe) == 32 ? 32u : 128u;
+  if (kn.gq) gq = kn.gq;
   if (ix.dim > kNarrowDim) gq = 128u;  // the wide kernel's C tile holds 128 queries
   // D <= 128, stored values bf16-exact (hi planes only): the streaming kernel (rank_stream.hip).  A work item holds up to
   // 128 queries and costs MFMAs for its live 32-query tiles only, so there is no group size to choose (VI_STREAM_GQ=256:
@@ -2658,20 +2544,15 @@ vi_status search_filter_pipeline(const DeviceIndex &ix, const float *Qd, uint64_
   // (bf16 x 3 keeps the block-synchronous kernel: two tiles of hi + lo planes do not fit in the streaming kernel's registers)
   // (measured at D = 32 / 64 / 96 / 128: its helper kernels and item skeleton pay off from 7 chunks of 16 dimensions on;
   // VI_RANK_STREAM=1 forces it for any D <= 128)
-  const char *se = getenv("VI_RANK_STREAM");
   // real-valued lists: hi planes only + a wider margin (rank_approx_mode) — the streaming kernel serves them too
-  const int approx = (rank_bf16() && !ix.lists_lo_zero && hi_only_ok() && ix.dim <= kNarrowDim) ? rank_approx_mode(ix) : 0;
-  const bool hi_lists = (ix.lists_lo_zero && hi_only_ok()) || approx != 0;
-  const bool stream = ix.dim <= kNarrowDim && rank_bf16() && hi_lists && !(se && *se == '0') &&
-                      (dq / 4 >= 7 || (se && *se == '1') || (approx != 0 && dq / 4 >= 5));
-  if (stream) {
-    const char *e = getenv("VI_STREAM_GQ");
-    gq = e && atoi(e) == 256 && ws.queries_hi_only ? 256u : 128u;
-  }
+  const int approx = (kn.rank_bf16 && !ix.lists_lo_zero && kn.hi_only && ix.dim <= kNarrowDim) ? rank_approx_mode(ix, kn) : 0;
+  const bool hi_lists = (ix.lists_lo_zero && kn.hi_only) || approx != 0;
+  const bool stream = ix.dim <= kNarrowDim && kn.rank_bf16 && hi_lists && !kn.stream_off &&
+                      (dq / 4 >= 7 || kn.stream_force || (approx != 0 && dq / 4 >= 5));
+  if (stream) gq = kn.stream_gq256 && ws.queries_hi_only ? 256u : 128u;
   // 8-bit descriptors against a batch of integers in 0..254 (hstats[14] == 0, known after the grouping): the streaming
   // kernel's int8 form (rank_stream_i8_kernel), exact ranks in the frame shifted by 127.  VI_RANK_I8=0: bf16.
-  const char *ie = getenv("VI_RANK_I8");
-  const bool i8_lists = stream && ix.lists_i8.p && !(ie && *ie == '0');
+  const bool i8_lists = stream && ix.lists_i8.p && kn.rank_i8;
   const bool fuse_q = grouping_fuses_query_offsets(ix);
   VI_TRY(launch_grouping(ix, ws.probes.p, nq, P, (int)gq, segb0, hstats, st, true, fuse_q ? ws.qtot.p : nullptr, fuse_q ? ws.qoff.p : nullptr,
                          ws.pair_rank_valid ? ws.pair_rank.p : nullptr));
@@ -2731,12 +2612,12 @@ vi_status search_filter_pipeline(const DeviceIndex &ix, const float *Qd, uint64_
     if (nitems) {
       hipLaunchKernelGGL(item_desc_kernel, dim3((nitems + 255) / 256), dim3(256), 0, st, ws.item_start.p, ws.seg_start.p,
                          ix.list_len.p, ix.list_first_block.p, ws.tile_start.p, (uint32_t)nlists, nitems, segb0, gq,
-                         item_run(), (uint4 *)ws.items.p);
+                         kn.item_run, (uint4 *)ws.items.p);
       VI_HIP(hipGetLastError());
     }
-    const int rank_mode = rank_bf16() ? (hi_lists ? 2 : 1) : 0;
+    const int rank_mode = kn.rank_bf16 ? (hi_lists ? 2 : 1) : 0;
     stt.rank_mode = approx ? 4u : (uint64_t)rank_mode + 1;
-    if (rank_bf16() && ix.centered && (stt.rank_mode == 2 || stt.rank_mode == 4)) stt.rank_mode = stt.rank_mode == 2 ? 5 : 6;  // the same about the mean
+    if (kn.rank_bf16 && ix.centered && (stt.rank_mode == 2 || stt.rank_mode == 4)) stt.rank_mode = stt.rank_mode == 2 ? 5 : 6;  // the same about the mean
     stt.group_queries = gq;
     if (stream) {
       // queries in LDS, vectors through registers, no barrier in the block loop, persistent workgroups (rank_stream.hip)
@@ -2756,9 +2637,9 @@ vi_status search_filter_pipeline(const DeviceIndex &ix, const float *Qd, uint64_
       } else {
         RankStreamArgs a{(const uint4 *)ix.lists_bf16.p, ix.xnorm_img.p, (const uint4 *)ws.qimg.p, (const uint4 *)ws.item_sdesc.p, nitems,
                          ws.item_qcol.p, ws.item_grec.p, (uint32_t *)(ws.stats.p + 16), (float4 *)ws.gval.p,
-                         (float4 *)ws.brec.p, nullptr, env_xmode()};
-        const bool qlo = (hstats[13] != 0 || !hi_only_ok()) && approx != 2;
-        const bool prof = getenv("VI_STREAM_PROF") != nullptr;
+                         (float4 *)ws.brec.p, nullptr, kn.filter_xmode};
+        const bool qlo = (hstats[13] != 0 || !kn.hi_only) && approx != 2;
+        const bool prof = kn.stream_prof;
         if (prof) {
           VI_TRY(ws.prof.reserve(32 + 4 * 1024));
           VI_HIP(hipMemsetAsync(ws.prof.p, 0, (32 + 4 * 1024) * sizeof(uint64_t), st));
@@ -2775,7 +2656,7 @@ vi_status search_filter_pipeline(const DeviceIndex &ix, const float *Qd, uint64_
                   "end-of-item wait %llu gather %llu merge %llu | items %llu steps %llu | loop total %llu\n",
                   (unsigned long long)h[0], (unsigned long long)h[6], (unsigned long long)h[1], (unsigned long long)h[2],
                   (unsigned long long)h[3], (unsigned long long)h[4], (unsigned long long)h[5], (unsigned long long)h[7]);
-          if (const char *dump = getenv("VI_STREAM_PROF_DUMP")) {
+          if (const char *dump = kn.stream_prof_dump) {
             std::vector<uint64_t> w(4 * 1024);
             VI_HIP(hipMemcpy(w.data(), ws.prof.p + 32, w.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
             if (FILE *f = fopen(dump, "w")) {
@@ -2798,17 +2679,16 @@ vi_status search_filter_pipeline(const DeviceIndex &ix, const float *Qd, uint64_
       }
     } else {
       FilterArgs a{};
-      a.blocks = rank_bf16() ? (const float4 *)ix.lists_bf16.p : (const float4 *)ix.lists.blocks.p;
-      a.xnorm = rank_bf16() ? ix.xnorm_img.p : ix.xnorm.p; a.dq = dq; a.dim = ix.dim; a.Q = Qd;
+      a.blocks = kn.rank_bf16 ? (const float4 *)ix.lists_bf16.p : (const float4 *)ix.lists.blocks.p;
+      a.xnorm = kn.rank_bf16 ? ix.xnorm_img.p : ix.xnorm.p; a.dq = dq; a.dim = ix.dim; a.Q = Qd;
       a.first_block = ix.list_first_block.p; a.list_len = ix.list_len.p; a.item_start = ws.item_start.p;
       a.seg_start = ws.seg_start.p; a.pairs = ws.pairs.p; a.nlists = (uint32_t)nlists; a.P = P; a.segb0 = segb0;
       a.qoff = ws.qoff.p; a.rel = ws.pair_rel.p; a.rec_stride = 0;
       a.tile_start = ws.tile_start.p;
-      a.item_list = nullptr;
       a.items = (const uint4 *)ws.items.p;
       a.gval = (float4 *)ws.gval.p; a.gmeta = ws.gpos.p; a.brec = (float4 *)ws.brec.p;
-      a.xmode = env_xmode();
-      a.qimg = rank_bf16() ? (const uint4 *)ws.qimg.p : nullptr;
+      a.xmode = kn.filter_xmode;
+      a.qimg = kn.rank_bf16 ? (const uint4 *)ws.qimg.p : nullptr;
       VI_TRY(start_rank_clock());
       VI_TRY(launch_filter(a, dq, nitems, rank_mode, gq, st));
     }
@@ -2817,12 +2697,12 @@ vi_status search_filter_pipeline(const DeviceIndex &ix, const float *Qd, uint64_
   if (rank_timing) VI_HIP(hipEventRecord(ix.cur().ev[3], st));
   // ---- 4. select ----
   {
-    SelectArgs a{select_common(ix, Qd, (const float4 *)ix.lists.blocks.p, rank_bf16() && ix.centered ? ix.xmax2_c : ix.xmax2, gq, stream, approx), (uint32_t)nq, P, (uint32_t)k, segb0,
+    SelectArgs a{select_common(ix, kn, Qd, (const float4 *)ix.lists.blocks.p, kn.rank_bf16 && ix.centered ? ix.xmax2_c : ix.xmax2, gq, stream, approx), (uint32_t)nq, P, (uint32_t)k, segb0,
                  ws.qoff.p, ws.qtot.p, ws.pair_rel.p, ws.pair_pos.p, ws.tile_start.p, ws.probes.p, ws.gorder.p, ix.list_first_block.p, ix.list_len.p,
                  ix.ext_ids.p, Dd, Id, Td, slots, counts};
-    { const char *e = getenv("VI_FILTER_STATS"); if (e && *e == '2') a.c.dbg = nullptr; }
-    { const char *e = getenv("VI_EXACT_BF16"); if (ix.lists_hi_nat.p && !(e && *e == '0')) a.c.hi_nat = (const uint4 *)ix.lists_hi_nat.p; }
-    { const char *e = getenv("VI_EXACT_U8"); if (ix.lists_u8_nat.p && !(e && *e == '0')) a.c.u8_nat = (const uint4 *)ix.lists_u8_nat.p; }
+    if (kn.stats_coarse) a.c.dbg = nullptr;
+    a.c.hi_nat = (const uint4 *)ix.lists_hi_nat.p;
+    a.c.u8_nat = (const uint4 *)ix.lists_u8_nat.p;
     if (rank_i8) {  // rank values 2 r within [m', m' + 1] of m' = |q - v|^2 - |q - 127|^2: the margins of that frame, an absolute error of 1
       a.c.mu = ix.i8_centre.p;
       a.c.e_scale = 0.0f;
@@ -2836,21 +2716,21 @@ vi_status search_filter_pipeline(const DeviceIndex &ix, const float *Qd, uint64_
     VI_HIP(hipGetLastError());
   }
   if (timing) VI_HIP(hipEventRecord(ix.cur().ev[4], st));
-  if (timing && getenv("VI_FILTER_STATS")) {
+  if (timing && kn.stats) {
     uint64_t dbg[12], tks[8];
     VI_HIP(hipMemcpyAsync(dbg, ws.stats.p, sizeof(dbg), hipMemcpyDeviceToHost, st));
     VI_HIP(hipMemcpyAsync(tks, ws.stats.p + 150, sizeof(tks), hipMemcpyDeviceToHost, st));
     VI_HIP(hipStreamSynchronize(st));
-    if (const char *e = getenv("VI_FILTER_STATS"); e && *e == '2')
+    if (kn.stats_coarse)
       fprintf(stderr, "coarse select ticks (every 64th query): query row %llu, records + bound %llu, flags (+ rounds a full list forces) %llu, exact rounds %llu, tail %llu; rows %llu "
               "of which in whole sub-blocks %llu\n", (unsigned long long)tks[0], (unsigned long long)tks[1], (unsigned long long)tks[2],
               (unsigned long long)tks[3], (unsigned long long)tks[4], (unsigned long long)dbg[6], 8ull * (unsigned long long)dbg[7]);
-    if (const char *e = getenv("VI_FILTER_STATS"); e && (*e == '3' || *e == '4'))
+    if (kn.stats_print)
       fprintf(stderr, "select ticks: records -> LDS %llu, threshold %llu, refinement %llu, scan of pair records (+ exact rounds it triggers) %llu, "
               "last exact rounds %llu\n", (unsigned long long)tks[0], (unsigned long long)tks[1], (unsigned long long)tks[2],
               (unsigned long long)tks[3], (unsigned long long)tks[4]);
     stt.filter_rechecked = dbg[6]; stt.filter_accepted = dbg[7];
-    if (const char *e = getenv("VI_FILTER_STATS"); e && (*e == '3' || *e == '4'))
+    if (kn.stats_print)
       fprintf(stderr, "select stats: exact %llu groups_scanned %llu queries_with_full_group %llu full_groups %llu sub_blocks %llu\n",
               (unsigned long long)dbg[6], (unsigned long long)dbg[7], (unsigned long long)dbg[8], (unsigned long long)dbg[9],
               (unsigned long long)dbg[10]);

@@ -46,12 +46,6 @@ constexpr int kBlockThreads = kWave * kWavesPerBlock;
 // gains in load balance, so only extreme lists (> 64k vectors) are cut (seg 256 measured +9 %).
 constexpr uint32_t kSegBlocksDefault = 1024;
 
-// tuning knobs for experiments (scripts/gpu_scan_bench.py); unset => defaults
-inline uint32_t env_u32(const char *name, uint32_t dflt) {
-  const char *v = getenv(name);
-  return (v && *v) ? (uint32_t)strtoul(v, nullptr, 10) : dflt;
-}
-
 // ------------------------------------------------------------------------------------------
 // Exact-order accumulators.  SCALAR: src/utils.rs:28-30.  LANES: src/kmeans.rs:377-419
 // (8-lane chunks, then one 4-lane chunk, then a scalar tail; reduce order see oracle header).
@@ -1183,11 +1177,12 @@ vi_status device_index_from_rows(int device, int order, uint32_t dim, const floa
   return compute_slot_norms(ix);
 }
 
-vi_status search_filter_pipeline(const DeviceIndex &ix, const float *Qd, uint64_t nq, uint64_t k, uint32_t P, uint32_t K,
+vi_status search_filter_pipeline(const DeviceIndex &ix, const EngineKnobs &kn, const float *Qd, uint64_t nq, uint64_t k, uint32_t P,
                                  float *Dd, int64_t *Id, uint64_t *Td, uint64_t *slots, uint32_t *counts, hipStream_t st,
                                  int timing_level, const uint32_t *probes_in, const uint32_t *order_in);
-vi_status coarse_only_filter(const DeviceIndex &ix, const float *Qd, uint64_t nq, uint32_t P, hipStream_t st);
-bool filter_path_applicable(const DeviceIndex &ix, uint64_t nq, uint64_t k, uint32_t P);
+vi_status coarse_only_filter(const DeviceIndex &ix, const EngineKnobs &kn, const float *Qd, uint64_t nq, uint32_t P, hipStream_t st);
+bool filter_path_applicable(const DeviceIndex &ix, const EngineKnobs &kn, uint64_t k, uint32_t P);
+bool coarse_on_matrix_cores(const DeviceIndex &ix, const EngineKnobs &kn, uint64_t nq, uint32_t P);
 
 vi_status device_index_search_generic(const DeviceIndex &ix, const float *Qd, uint64_t nq, uint64_t k, uint32_t P,
                                       float *Dd, int64_t *Id, uint64_t *Td, uint64_t *slots, uint32_t *counts,
@@ -1281,8 +1276,8 @@ vi_status adopt_probes(const DeviceIndex &ix, uint64_t nq, uint32_t P, const uin
   return VI_OK;
 }
 
-vi_status search_valu_pipeline(const DeviceIndex &ix, const float *Qd, uint64_t nq, uint64_t k, uint32_t P, uint32_t K,
-                               float *Dd, int64_t *Id, uint64_t *Td, uint64_t *slots, uint32_t *counts, hipStream_t st,
+vi_status search_valu_pipeline(const DeviceIndex &ix, const EngineKnobs &kn, const float *Qd, uint64_t nq, uint64_t k, uint32_t P,
+                               uint32_t K, float *Dd, int64_t *Id, uint64_t *Td, uint64_t *slots, uint32_t *counts, hipStream_t st,
                                int timing_level, const uint32_t *probes_in, const uint32_t *order_in) {
   const bool timing = timing_level == 1, rank_timing = timing_level != 0;
   SearchWorkspace &ws = ix.cur().ws;
@@ -1302,10 +1297,10 @@ vi_status search_valu_pipeline(const DeviceIndex &ix, const float *Qd, uint64_t 
   const double avg_q_per_list = (double)nq * P / (double)std::max<uint64_t>(1, nlists);
   int qg_l = pick_qg(dq, avg_q_per_list, ix.order);
   {
-    const uint32_t f = env_u32("VI_FORCE_QG", 0);
+    const uint32_t f = kn.force_qg;
     if (f == 1 || f == 2 || f == 4 || (f == 8 && ix.order == VI_ORDER_SCALAR)) qg_l = (int)f;
   }
-  const uint32_t kSegBlocks = std::max<uint32_t>(1, env_u32("VI_SEG_BLOCKS", kSegBlocksDefault));
+  const uint32_t kSegBlocks = kn.seg_blocks;
   VI_TRY(ws.seg_start.reserve(nlists + 1));
   VI_TRY(ws.item_start.reserve(nlists + 1));
   VI_TRY(ws.pairs.reserve(nq * P));
@@ -1377,6 +1372,46 @@ __global__ void stripe_tie_kernel(uint64_t *tie, uint64_t n, uint32_t rank, uint
   tie[i] = (t & 0xFFFFFFFF00000000ull) | (uint64_t)(((p >> 6) * world + rank) * 64u + (p & 63u));
 }
 
+EngineKnobs read_engine_knobs() {
+  auto on = [](const char *name) { const char *e = getenv(name); return !(e && *e == '0'); };
+  auto num = [](const char *name, int dflt) { const char *e = getenv(name); return e ? atoi(e) : dflt; };
+  auto u32 = [](const char *name, uint32_t dflt) {  // (unset or empty: the default)
+    const char *e = getenv(name);
+    return (e && *e) ? (uint32_t)strtoul(e, nullptr, 10) : dflt;
+  };
+  const char *stats = getenv("VI_FILTER_STATS"), *approx = getenv("VI_RANK_APPROX"), *gq = getenv("VI_FILTER_GQ");
+  const char *stream = getenv("VI_RANK_STREAM");
+  EngineKnobs kn{};
+  kn.force_generic = u32("VI_FORCE_GENERIC", 0) != 0;
+  kn.force_qg = u32("VI_FORCE_QG", 0);
+  kn.seg_blocks = std::max<uint32_t>(1, u32("VI_SEG_BLOCKS", kSegBlocksDefault));
+  kn.filter = on("VI_FILTER");
+  kn.rank_bf16 = on("VI_FILTER_BF16");
+  kn.hi_only = on("VI_FILTER_HI_ONLY");
+  kn.rank_approx = -1;
+  if (approx) { const int v = atoi(approx); kn.rank_approx = v < 0 || v > 2 ? 1 : v; }
+  kn.debug_approx = getenv("VI_DEBUG_APPROX") != nullptr;
+  kn.coarse_filter = on("VI_COARSE_FILTER");
+  kn.coarse_direct = on("VI_COARSE_DIRECT");
+  kn.segb0 = (uint32_t)std::max(1, num("VI_FILTER_SEGB", 32));  // <= 2048 vectors per work item
+  kn.gq = gq ? (atoi(gq) == 32 ? 32u : 128u) : 0u;
+  kn.stream_off = stream && *stream == '0';
+  kn.stream_force = stream && *stream == '1';
+  kn.stream_gq256 = num("VI_STREAM_GQ", 0) == 256;
+  kn.rank_i8 = on("VI_RANK_I8");
+  kn.item_run = (uint32_t)std::min(std::max(num("VI_ITEM_RUN", 8), 1), 256);
+  kn.stream_prof = getenv("VI_STREAM_PROF") != nullptr;
+  kn.stream_prof_dump = getenv("VI_STREAM_PROF_DUMP");
+  kn.filter_xmode = (uint32_t)num("VI_FILTER_XMODE", 0);
+  kn.select_xmode = (uint32_t)num("VI_SELECT_XMODE", 0);
+  kn.coarse_xmode = (uint32_t)num("VI_SELECT_XMODE_COARSE", 0);
+  kn.stats = stats != nullptr;
+  kn.stats_coarse = stats && *stats == '2';
+  kn.stats_print = stats && (*stats == '3' || *stats == '4');
+  kn.stats_mask = stats && *stats == '4' ? 63u : 0u;
+  return kn;
+}
+
 vi_status device_index_search(const DeviceIndex &ix, const SearchIO &io) {
   VI_HIP(hipSetDevice(ix.device));
   ContextLease lease(ix);
@@ -1391,8 +1426,9 @@ vi_status device_index_search(const DeviceIndex &ix, const SearchIO &io) {
   const uint32_t P = (uint32_t)std::min<uint64_t>(io.n_probe, nlists);  // take(n_probe) (ivf_index.rs:216-220)
   const uint32_t K = (uint32_t)std::min<uint64_t>(k, kMaxSelect);
   // k in (64, 128]: the MFMA engine's select keeps two entries per lane; the VALU engine's wave top-k stops at 64
-  const bool generic = P > kMaxSelect || k > 2 * kMaxSelect || (k > kMaxSelect && !filter_path_applicable(ix, nq, k, P)) ||
-                       env_u32("VI_FORCE_GENERIC", 0) != 0;
+  const EngineKnobs kn = read_engine_knobs();
+  const bool generic = P > kMaxSelect || k > 2 * kMaxSelect || (k > kMaxSelect && !filter_path_applicable(ix, kn, k, P)) ||
+                       kn.force_generic;
 
   // ---- outputs / queries on device ----
   const float *Qd = io.queries;
@@ -1430,11 +1466,11 @@ vi_status device_index_search(const DeviceIndex &ix, const SearchIO &io) {
     return VI_OK;
   }
 
-  const bool use_filter = !generic && filter_path_applicable(ix, nq, k, P);
+  const bool use_filter = !generic && filter_path_applicable(ix, kn, k, P);
   const int timing = generic ? 0 : ix.timing;
   if (io.probes_out) {  // coarse step only (multi-GPU: this rank's slice of the queries)
     if (P > kMaxSelect) VI_TRY(generic_probe_export(ix, Qd, nq, P, st));  // any n_probe: every coarse distance, sorted
-    else if (filter_path_applicable(ix, nq, 1, P) && nq >= 256 && nlists >= 1024) VI_TRY(coarse_only_filter(ix, Qd, nq, P, st));
+    else if (coarse_on_matrix_cores(ix, kn, nq, P)) VI_TRY(coarse_only_filter(ix, kn, Qd, nq, P, st));
     else VI_TRY(stage_coarse(ix, Qd, nq, P, st));
     VI_HIP(hipMemcpyAsync(io.probes_out, ws.probes.p, nq * P * 4, hipMemcpyDeviceToDevice, st));
     VI_HIP(hipMemcpyAsync(io.order_out, ws.gorder.p, nq * P * 4, hipMemcpyDeviceToDevice, st));
@@ -1444,9 +1480,9 @@ vi_status device_index_search(const DeviceIndex &ix, const SearchIO &io) {
   if (generic) {  // (k > 128 or n_probe > 64, with the caller's probe lists too)
     VI_TRY(device_index_search_generic(ix, Qd, nq, k, P, Dd, Id, Td, slots, ws.counts.p, st, io.probes_in, io.order_in));
   } else if (use_filter) {
-    VI_TRY(search_filter_pipeline(ix, Qd, nq, k, P, K, Dd, Id, Td, slots, ws.counts.p, st, timing, io.probes_in, io.order_in));
+    VI_TRY(search_filter_pipeline(ix, kn, Qd, nq, k, P, Dd, Id, Td, slots, ws.counts.p, st, timing, io.probes_in, io.order_in));
   } else {
-    VI_TRY(search_valu_pipeline(ix, Qd, nq, k, P, K, Dd, Id, Td, slots, ws.counts.p, st, timing, io.probes_in, io.order_in));
+    VI_TRY(search_valu_pipeline(ix, kn, Qd, nq, k, P, K, Dd, Id, Td, slots, ws.counts.p, st, timing, io.probes_in, io.order_in));
   }
 
   if (ix.stripe_world > 1 && Td) {
