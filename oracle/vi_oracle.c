@@ -475,19 +475,31 @@ static float centroid_delta(const float *cur, const float *prev, size_t k, size_
   return sqrtf(dsq / (float)(k * d));
 }
 
-/* src/kmeans.rs:674-719 */
-void orc_update_centroids(const float *X, size_t n, size_t d, const uint64_t *labels, size_t k,
-                          float *C_new, uint64_t *counts) {
-  memset(C_new, 0, sizeof(float) * k * d);
+/* src/kmeans.rs:674-698, the accumulation alone: every cluster's members added in ascending id, one sequential f32
+ * chain per column starting from +0.0 */
+void orc_cluster_sums(const float *X, size_t n, size_t d, const uint64_t *labels, size_t k,
+                      float *sums, uint64_t *counts) {
+  memset(sums, 0, sizeof(float) * k * d);
   memset(counts, 0, sizeof(uint64_t) * k);
   for (size_t i = 0; i < n; ++i) {
     uint64_t c = labels[i];
     counts[c] += 1;
-    for (size_t j = 0; j < d; ++j) C_new[c * d + j] += X[i * d + j];
+    for (size_t j = 0; j < d; ++j) sums[c * d + j] += X[i * d + j];
   }
+}
+
+/* src/kmeans.rs:699-712: sum / count in place, an empty cluster keeps its row of zeros */
+static void divide_by_counts(float *sums, const uint64_t *counts, size_t k, size_t d) {
   for (size_t c = 0; c < k; ++c)
     if (counts[c] > 0)
-      for (size_t j = 0; j < d; ++j) C_new[c * d + j] /= (float)counts[c];
+      for (size_t j = 0; j < d; ++j) sums[c * d + j] /= (float)counts[c];
+}
+
+/* src/kmeans.rs:674-719 */
+void orc_update_centroids(const float *X, size_t n, size_t d, const uint64_t *labels, size_t k,
+                          float *C_new, uint64_t *counts) {
+  orc_cluster_sums(X, n, d, labels, k, C_new, counts);
+  divide_by_counts(C_new, counts, k, d);
 }
 
 /* src/kmeans.rs:15-60 */

@@ -95,7 +95,11 @@ void orc_build_centroid_hierarchy(const float *C, size_t k, size_t d, size_t met
 /* kmeans_plus_plus_init :154-310 */
 void orc_kmeans_pp_init(const float *X, size_t n, size_t d, size_t k, uint64_t seed,
                         float *C);
-/* update_centroids_parallel :674-719 */
+/* the accumulation of update_centroids_parallel (:674-698) without its division: sums (k x d) = every cluster's
+ * members added in ascending id, one sequential f32 chain per column from +0.0; counts (k) */
+void orc_cluster_sums(const float *X, size_t n, size_t d, const uint64_t *labels, size_t k,
+                      float *sums, uint64_t *counts);
+/* update_centroids_parallel :674-719 (orc_cluster_sums, then sum / count; zeros for an empty cluster) */
 void orc_update_centroids(const float *X, size_t n, size_t d, const uint64_t *labels,
                           size_t k, float *C_new, uint64_t *counts);
 /* run_kmeans_mini_batch :64-150.  thr < 0 => None => 1e-4.

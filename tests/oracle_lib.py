@@ -79,6 +79,7 @@ def lib():
         "orc_assign": (None, [vp, C.c_size_t, C.c_size_t, vp, C.c_size_t, u64, vp]),
         "orc_build_centroid_hierarchy": (None, [vp, C.c_size_t, C.c_size_t, C.c_size_t, u64, vp, vp]),
         "orc_kmeans_pp_init": (None, [vp, C.c_size_t, C.c_size_t, C.c_size_t, u64, vp]),
+        "orc_cluster_sums": (None, [vp, C.c_size_t, C.c_size_t, vp, C.c_size_t, vp, vp]),
         "orc_update_centroids": (None, [vp, C.c_size_t, C.c_size_t, vp, C.c_size_t, vp, vp]),
         "orc_kmeans_mini_batch": (C.c_int, [vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, f32, u64, C.c_int, vp, vp, P(u64)]),
         "orc_kmeans_parallel": (C.c_int, [vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, f32, u64, C.c_int, vp, vp, P(u64)]),
@@ -154,6 +155,17 @@ def kmeans_pp_init(X, k, seed):
     Cn = np.zeros((k, d), dtype=np.float32)
     lib().orc_kmeans_pp_init(_p(X), n, d, k, seed, _p(Cn))
     return Cn
+
+
+def cluster_sums(X, labels, k):
+    """(sums k x d f32, counts k u64): members added in ascending id, one sequential f32 chain per column from +0.0"""
+    X = f32c(X)
+    n, d = X.shape
+    labels = np.ascontiguousarray(labels, dtype=np.uint64)
+    sums = np.zeros((k, d), dtype=np.float32)
+    counts = np.zeros(k, dtype=np.uint64)
+    lib().orc_cluster_sums(_p(X), n, d, _p(labels), k, _p(sums), _p(counts))
+    return sums, counts
 
 
 def update_centroids(X, labels, k):

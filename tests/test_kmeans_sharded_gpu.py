@@ -180,6 +180,55 @@ def test_sharded_lloyd_all_reduce(world):
             hip.close()
 
 
+class RecordingEngine(VD.GpuKMeansEngine):
+    """keeps what every vi_kmeans_partial_sums_device call of this rank read and wrote (before the all-reduce)"""
+
+    def __init__(self, hip, device=0):
+        super().__init__(device)
+        self.hip, self.calls = hip, []
+
+    def partial_sums(self, X_ptr, n_local, d, labels_ptr, k, sums_ptr, counts_ptr):
+        super().partial_sums(X_ptr, n_local, d, labels_ptr, k, sums_ptr, counts_ptr)
+        self.calls.append((self.hip.download(labels_ptr, (n_local,), np.uint32), self.hip.download(sums_ptr, (k, d), np.float32),
+                           self.hip.download(counts_ptr, (k,), np.uint32)))
+
+
+@pytest.mark.parametrize("world", [2, 8])
+def test_sharded_lloyd_with_big_local_clusters(world):
+    """100 000 points in 4 clusters: every rank's local clusters exceed 2048 members (segment_big_kernel sums them).
+    What is exact under the all-reduce: a rank's partial sums are the oracle's sequential sums of that rank's slice, bit
+    for bit, and the counts add up to the single-GPU counts.  The reduced centroids agree to rounding as before."""
+    n, d, k = 100000, 16, 4
+    X = clustered(n, d, 4, 77)
+    Cs, ls, its = vip.kmeans_parallel(X, k, 1, seed=5, mode=vip.VI_ASSIGN_EXACT)
+    rec = [None] * world
+
+    def fn(engine, comm, pts, hip):
+        engine = rec[comm.rank] = RecordingEngine(hip)
+        Cb, Lb, it = VD.kmeans_parallel_sharded(engine, comm, pts, k, 1, seed=5, mode=vip.VI_ASSIGN_EXACT)
+        return hip.download(Cb.ptr, (k, d), np.float32), hip.download(Lb.ptr, (pts.n_local,), np.uint32), it, pts.row_begin
+    res, hip = run_ranks(world, X, fn)
+    try:
+        total = np.zeros(k, dtype=np.uint64)
+        for r in range(world):
+            Cr, lab_r, it, b = res[r]
+            assert len(rec[r].calls) == 1 and it == 1
+            lab_call, sums, counts = rec[r].calls[0]
+            assert (lab_call == lab_r).all()
+            So, co = O.cluster_sums(X[b:b + lab_r.size], lab_r, k)
+            assert co.max() > 2048, co
+            assert (counts == co).all()
+            assert (sums.view(np.uint32) == So.view(np.uint32)).all(), r
+            total += counts
+            assert (Cr.view(np.uint32) == res[0][0].view(np.uint32)).all()   # every rank holds the same table
+        lab = np.concatenate([r[1] for r in res])
+        assert (lab == ls).all()                                 # same initial centroids => same first assignment
+        assert (total == np.bincount(ls.astype(np.int64), minlength=k).astype(np.uint64)).all()
+        assert np.allclose(res[0][0], Cs, rtol=1e-5, atol=1e-6)
+    finally:
+        hip.close()
+
+
 def test_sharded_lloyd_with_ranks_that_own_no_points():
     """n = 9 points over 8 ranks (two per rank: ranks 5..7 are empty): an empty rank contributes zero sums and counts to
     the all-reduce instead of failing the loop (vi_kmeans_partial_sums_device with n_local = 0)"""

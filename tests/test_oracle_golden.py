@@ -158,3 +158,38 @@ def test_bench_dataset_checksum():
     rng = np.random.default_rng(42)
     xb = rng.standard_normal((50000, 64)).astype(np.float32)
     assert hashlib.sha256(xb.tobytes()).hexdigest() == sha["c1_xb_50000x64_seed42"]
+
+
+def test_cluster_sums_is_the_sequential_f32_chain():
+    """orc_cluster_sums against a plain Python loop of np.float32 adds: members in ascending id, every column one chain
+    from +0.0; orc_update_centroids = the same sums divided by the counts (zeros for an empty cluster)"""
+    rng = np.random.default_rng(5)
+    n, d, k = 400, 7, 6
+    X = (rng.standard_normal((n, d)) * 10.0 ** rng.uniform(-3, 3, size=(n, 1))).astype(np.float32)
+    labels = rng.integers(0, k - 1, n).astype(np.uint64)           # cluster k - 1 stays empty
+    X[labels == 2, 0] = np.float32(-0.0)                           # a column of -0.0 only: +0.0 + -0.0 = +0.0
+    X[np.flatnonzero(labels == 1)[3], 1] = np.float32(np.inf)      # a column holding inf
+    X[np.flatnonzero(labels == 3)[2], 2] = np.float32(-np.inf)
+    tiny = np.array([1, 2, 0x7FFFFF, 0x80000003, 0x00400000], dtype=np.uint32).view(np.float32)
+    sub = np.flatnonzero(labels == 0)
+    X[sub, 3] = tiny[np.arange(sub.size) % tiny.size]              # a column of subnormal values
+    X[sub[:5], 4] = tiny                                           # ... and subnormals among ordinary values
+    exp = np.zeros((k, d), dtype=np.float32)
+    cnt = np.zeros(k, dtype=np.uint64)
+    for i in range(n):
+        c = int(labels[i])
+        cnt[c] += 1
+        for j in range(d):
+            exp[c, j] = np.float32(exp[c, j]) + np.float32(X[i, j])
+    S, counts = O.cluster_sums(X, labels, k)
+    assert (counts == cnt).all() and counts[k - 1] == 0 and counts.dtype == np.uint64
+    assert (S.view(np.uint32) == exp.view(np.uint32)).all()
+    assert (S[2, 0:1].view(np.uint32) == 0).all() and (S[k - 1].view(np.uint32) == 0).all()
+    assert S[1, 1] == np.inf and S[3, 2] == -np.inf
+    assert 0 < abs(float(S[0, 3])) and np.isfinite(S).sum() == S.size - 2
+    Cn, counts2 = O.update_centroids(X, labels, k)
+    mean = exp.copy()
+    for c in range(k):
+        if cnt[c]:
+            mean[c] = exp[c] / np.float32(cnt[c])
+    assert (counts2 == cnt).all() and (Cn.view(np.uint32) == mean.view(np.uint32)).all()
