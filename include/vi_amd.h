@@ -236,7 +236,8 @@ vi_status vi_indexer_load(const vi_config *cfg, vi_indexer **out);
  * Device memory: the build keeps the uploaded points (4 n D bytes, + 16 n for ids and timestamps when given) resident
  * until the searchable index built from them (another 4 n D for the blocks + 4 n D of bf16 images, + 1 n D for 8-bit data)
  * is complete: its peak is about twice what vi_indexer_load of the same index needs; the grouping sort adds 16 n bytes
- * and the largest shard's staging image transiently.  A data set that fills more than ~40 % of HBM should be built in
+ * and the largest shard's staging image transiently.  The resident index keeps 16 bytes per stored vector beside its
+ * images: the external id and the timestamp (vi_indexer_filter_timestamps); a built or a loaded index alike.  A data set that fills more than ~40 % of HBM should be built in
  * parts or loaded from shard files written elsewhere. */
 vi_status vi_indexer_build_from_records(vi_indexer *ix, const uint64_t *ext_ids, const float *values,
                                         const uint64_t *timestamps, const uint32_t *dims, uint64_t n);
@@ -285,6 +286,37 @@ vi_status vi_indexer_search_probed_device(const vi_indexer *ix, const float *que
                                           uint64_t n_probe_eff, const uint32_t *probes_dev,
                                           const uint32_t *order_dev, float *D_dev, int64_t *I_dev,
                                           uint64_t *tie_dev);
+
+/* ---- timestamp-window filtered search (extension: the reference stores VectorMeta.timestamp, shards.rs:45-51, but never
+ * filters on it) ----
+ * The filtered result of a query is what the reference's search would return if the candidates whose STORED timestamp
+ * (the value in the shard file: a record built with timestamp 0 carries the build's `now`) lies outside
+ * [ts_min, ts_max] — both inclusive — were deleted from its candidate sequence before the stable sort.  The coarse step
+ * does not look at the filter (the probed lists are those of the unfiltered search), so a query may find fewer than k
+ * results: padded +inf / -1 / zero vectors and reported in counts, as always.  Distances and tie keys are the unfiltered
+ * ones, so per-rank partial results merge exactly through vi_merge_partials*_device when every rank filters by the same
+ * window.  A window that admits everything returns bit for bit what the unfiltered entry returns; one that admits
+ * nothing returns VI_OK with zero results; ts_min > ts_max is VI_ERR_INVALID_INPUT.
+ * A vi_filter belongs to the resident index of ONE handle (another handle's, or one made before the handle was rebuilt,
+ * is VI_ERR_INVALID_INPUT), is immutable, and may be shared by the concurrent searches a handle allows.  It holds 12 bytes
+ * of device memory per resident slot (16 for 8-bit descriptor data) and must be freed before its indexer.
+ * f == NULL: the unfiltered entry. */
+typedef struct vi_filter vi_filter;
+vi_status vi_indexer_filter_timestamps(const vi_indexer *ix, uint64_t ts_min, uint64_t ts_max, vi_filter **out);
+uint64_t vi_filter_num_allowed(const vi_filter *f); /* resident vectors inside the window */
+void vi_filter_free(vi_filter *f);                  /* NULL ok */
+/* vi_indexer_search / _search_device / _search_probed_device with a filter: the same arguments after it, the same
+ * clamping and validation of k / n_probe / query_dim */
+vi_status vi_indexer_search_filtered(const vi_indexer *ix, const vi_filter *f, const float *queries, uint64_t nq,
+                                     uint32_t query_dim, uint64_t k, uint64_t n_probe, float *D, int64_t *I, float *V,
+                                     uint64_t *counts, uint64_t *k_out);
+vi_status vi_indexer_search_filtered_device(const vi_indexer *ix, const vi_filter *f, const float *queries_dev,
+                                            uint64_t nq, uint64_t k, uint64_t n_probe, float *D_dev, int64_t *I_dev,
+                                            uint64_t *tie_dev);
+vi_status vi_indexer_search_probed_filtered_device(const vi_indexer *ix, const vi_filter *f, const float *queries_dev,
+                                                   uint64_t nq, uint64_t k, uint64_t n_probe_eff,
+                                                   const uint32_t *probes_dev, const uint32_t *order_dev, float *D_dev,
+                                                   int64_t *I_dev, uint64_t *tie_dev);
 
 /* Merge `parts` per-rank partial results (each nq x k, device pointers laid out
  * [part][nq][k]) into the global top-k with the reference's stable order. */

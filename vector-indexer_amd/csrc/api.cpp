@@ -13,6 +13,7 @@
 #include "kmeans.hpp"
 #include "rng.hpp"
 #include "shards.hpp"
+#include "slot_filter.hpp"
 
 namespace vi {
 
@@ -178,7 +179,7 @@ static vi_status fit_and_save(Indexer *ix, const float *X, const uint64_t *ext_i
   } else {
     auto dev = std::make_unique<DeviceIndex>();
     rc = device_index_from_order(ix->cfg.device, dim, ix->meta.centroids.data(), kk, Xd.p, order.p, src_off, len, lshard,
-                                 ext_ids ? ext_dev.p : nullptr, dev.get());
+                                 ext_ids ? ext_dev.p : nullptr, timestamps ? ts_dev.p : nullptr, now, dev.get());
     if (rc == VI_OK) ix->dev = std::move(dev);
   }
   const double t6 = now_ms();
@@ -196,6 +197,10 @@ using vi::Indexer;
 
 struct vi_indexer {
   Indexer impl;
+};
+
+struct vi_filter {
+  vi::SlotFilter impl;
 };
 
 extern "C" {
@@ -450,10 +455,23 @@ static vi_status search_common(const vi_indexer *ix, uint64_t *k, uint64_t *n_pr
   return VI_OK;
 }
 
-vi_status vi_indexer_search(const vi_indexer *ix, const float *queries, uint64_t nq, uint32_t query_dim, uint64_t k,
-                            uint64_t n_probe, float *D, int64_t *I, float *V, uint64_t *counts, uint64_t *k_out) {
+// the filter of a search entry: null (unfiltered), or one made from this handle's resident index
+static vi_status filter_common(const vi_indexer *ix, const vi_filter *f, const vi::SlotFilter **out) {
+  *out = nullptr;
+  if (!f) return VI_OK;
+  if (!ix->impl.dev || f->impl.owner_serial != ix->impl.dev->serial)
+    return fail(VI_ERR_INVALID_INPUT, "the filter was made from another indexer (or before this one was rebuilt)");
+  *out = &f->impl;
+  return VI_OK;
+}
+
+vi_status vi_indexer_search_filtered(const vi_indexer *ix, const vi_filter *f, const float *queries, uint64_t nq,
+                                     uint32_t query_dim, uint64_t k, uint64_t n_probe, float *D, int64_t *I, float *V,
+                                     uint64_t *counts, uint64_t *k_out) {
   return vi::guarded([&]() -> vi_status {
   VI_TRY(search_common(ix, &k, &n_probe));
+  const vi::SlotFilter *flt = nullptr;
+  VI_TRY(filter_common(ix, f, &flt));
   if (k_out) *k_out = k;
   if (query_dim != ix->impl.cfg.dimension)  // api.rs:192-201
     return fail(VI_ERR_INVALID_INPUT, "query dimension mismatch: expected %u, got %u", ix->impl.cfg.dimension,
@@ -470,14 +488,22 @@ vi_status vi_indexer_search(const vi_indexer *ix, const float *queries, uint64_t
   vi::SearchIO io;
   io.queries = queries; io.nq = nq; io.k = k; io.n_probe = n_probe;
   io.D = D; io.I = I; io.V = V; io.counts = counts;
+  io.filter = flt;
   return vi::device_index_search(*ix->impl.dev, io);
   });
 }
 
-vi_status vi_indexer_search_device(const vi_indexer *ix, const float *queries_dev, uint64_t nq, uint64_t k,
-                                   uint64_t n_probe, float *D_dev, int64_t *I_dev, uint64_t *tie_dev) {
+vi_status vi_indexer_search(const vi_indexer *ix, const float *queries, uint64_t nq, uint32_t query_dim, uint64_t k,
+                            uint64_t n_probe, float *D, int64_t *I, float *V, uint64_t *counts, uint64_t *k_out) {
+  return vi_indexer_search_filtered(ix, nullptr, queries, nq, query_dim, k, n_probe, D, I, V, counts, k_out);
+}
+
+vi_status vi_indexer_search_filtered_device(const vi_indexer *ix, const vi_filter *f, const float *queries_dev, uint64_t nq,
+                                            uint64_t k, uint64_t n_probe, float *D_dev, int64_t *I_dev, uint64_t *tie_dev) {
   return vi::guarded([&]() -> vi_status {
   VI_TRY(search_common(ix, &k, &n_probe));
+  const vi::SlotFilter *flt = nullptr;
+  VI_TRY(filter_common(ix, f, &flt));
   if (k == 0 || n_probe == 0) return fail(VI_ERR_INVALID_INPUT, "k and n_probe must be greater than 0");
   if (nq == 0) return VI_OK;
   if (!queries_dev || !D_dev || !I_dev) return fail(VI_ERR_INVALID_INPUT, "null pointer");
@@ -485,8 +511,14 @@ vi_status vi_indexer_search_device(const vi_indexer *ix, const float *queries_de
   vi::SearchIO io;
   io.queries = queries_dev; io.on_device = true; io.nq = nq; io.k = k; io.n_probe = n_probe;
   io.D = D_dev; io.I = I_dev; io.tie = tie_dev;
+  io.filter = flt;
   return vi::device_index_search(*ix->impl.dev, io);
   });
+}
+
+vi_status vi_indexer_search_device(const vi_indexer *ix, const float *queries_dev, uint64_t nq, uint64_t k,
+                                   uint64_t n_probe, float *D_dev, int64_t *I_dev, uint64_t *tie_dev) {
+  return vi_indexer_search_filtered_device(ix, nullptr, queries_dev, nq, k, n_probe, D_dev, I_dev, tie_dev);
 }
 
 vi_status vi_indexer_probe_device(const vi_indexer *ix, const float *queries_dev, uint64_t nq, uint64_t n_probe,
@@ -507,13 +539,15 @@ vi_status vi_indexer_probe_device(const vi_indexer *ix, const float *queries_dev
   });
 }
 
-vi_status vi_indexer_search_probed_device(const vi_indexer *ix, const float *queries_dev, uint64_t nq, uint64_t k,
-                                          uint64_t n_probe_eff, const uint32_t *probes_dev,
-                                          const uint32_t *order_dev, float *D_dev, int64_t *I_dev,
-                                          uint64_t *tie_dev) {
+vi_status vi_indexer_search_probed_filtered_device(const vi_indexer *ix, const vi_filter *f, const float *queries_dev,
+                                                   uint64_t nq, uint64_t k, uint64_t n_probe_eff, const uint32_t *probes_dev,
+                                                   const uint32_t *order_dev, float *D_dev, int64_t *I_dev,
+                                                   uint64_t *tie_dev) {
   return vi::guarded([&]() -> vi_status {
   uint64_t n_probe = n_probe_eff;
   VI_TRY(search_common(ix, &k, &n_probe));
+  const vi::SlotFilter *flt = nullptr;
+  VI_TRY(filter_common(ix, f, &flt));
   if (k == 0 || n_probe == 0) return fail(VI_ERR_INVALID_INPUT, "k and n_probe must be greater than 0");
   if (nq == 0) return VI_OK;
   if (!queries_dev || !D_dev || !I_dev || !probes_dev || !order_dev) return fail(VI_ERR_INVALID_INPUT, "null pointer");
@@ -524,9 +558,34 @@ vi_status vi_indexer_search_probed_device(const vi_indexer *ix, const float *que
   io.queries = queries_dev; io.on_device = true; io.nq = nq; io.k = k; io.n_probe = n_probe;
   io.D = D_dev; io.I = I_dev; io.tie = tie_dev;
   io.probes_in = probes_dev; io.order_in = order_dev;
+  io.filter = flt;
   return vi::device_index_search(*ix->impl.dev, io);
   });
 }
+
+vi_status vi_indexer_search_probed_device(const vi_indexer *ix, const float *queries_dev, uint64_t nq, uint64_t k,
+                                          uint64_t n_probe_eff, const uint32_t *probes_dev,
+                                          const uint32_t *order_dev, float *D_dev, int64_t *I_dev,
+                                          uint64_t *tie_dev) {
+  return vi_indexer_search_probed_filtered_device(ix, nullptr, queries_dev, nq, k, n_probe_eff, probes_dev, order_dev, D_dev,
+                                                  I_dev, tie_dev);
+}
+
+vi_status vi_indexer_filter_timestamps(const vi_indexer *ix, uint64_t ts_min, uint64_t ts_max, vi_filter **out) {
+  return vi::guarded([&]() -> vi_status {
+  if (!ix || !out) return fail(VI_ERR_INVALID_INPUT, "null pointer");
+  if (ts_min > ts_max) return fail(VI_ERR_INVALID_INPUT, "timestamp window: ts_min > ts_max");
+  if (!ix->impl.dev) return fail(VI_ERR_DEVICE, "index is not resident on a GPU (build or load it first)");
+  auto f = std::make_unique<vi_filter>();
+  VI_TRY(vi::slot_filter_timestamps(*ix->impl.dev, ts_min, ts_max, &f->impl));
+  *out = f.release();
+  return VI_OK;
+  });
+}
+
+uint64_t vi_filter_num_allowed(const vi_filter *f) { return f ? f->impl.num_allowed : 0; }
+
+void vi_filter_free(vi_filter *f) { delete f; }
 
 vi_status vi_merge_partials_device(int32_t device, uint64_t nq, uint64_t k, uint32_t parts, const float *D_parts,
                                    const int64_t *I_parts, const uint64_t *tie_parts, float *D_out, int64_t *I_out) {

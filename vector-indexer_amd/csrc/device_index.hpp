@@ -15,6 +15,7 @@
 // indexed by slot = 64*block + lane.  The AoS record layout of the shard files
 // (24 B meta + 4·D B + pad, shards.rs:106-114) is kept only on disk.
 #pragma once
+#include <atomic>
 #include <cstdint>
 #include <condition_variable>
 #include <memory>
@@ -26,6 +27,8 @@
 #include "shards.hpp"
 
 namespace vi {
+
+struct SlotFilter;  // slot_filter.hpp
 
 constexpr uint32_t kNoPos = 0xFFFFFFFFu;   // empty slot marker in a sorted run
 constexpr uint32_t kMaxSelect = 64;        // wave-resident top-k width of the fast path
@@ -82,10 +85,17 @@ struct SearchWorkspace {
   bool stats_zeroed = false;                // stats[13], [14] start at zero (filter_search.hip)
   bool queries_hi_only = false;             // the previous batch's -2 q were all bf16-exact (no lo plane)
   DevBuf<uint64_t> sort_keys, order_keys, total;
+  DevBuf<uint64_t> total_allowed;           // generic engine with a filter: candidates per query that received a key
   DevBuf<uint32_t> gprobe, off_by_g, off_by_rank;
 };
 
+inline uint64_t next_index_serial() {
+  static std::atomic<uint64_t> n{0};
+  return ++n;
+}
+
 struct DeviceIndex {
+  const uint64_t serial = next_index_serial();  // never reused in a process: what a SlotFilter names its index by
   int device = 0;
   int order = VI_ORDER_SCALAR;  // summation order of every distance this index computes
   uint32_t dim = 0, dq = 0;
@@ -98,6 +108,8 @@ struct DeviceIndex {
   DevBuf<uint32_t> list_len;          // [nlists]  (0 => not resident here / empty)
   DevBuf<uint32_t> list_shard;        // [nlists]
   DevBuf<uint64_t> ext_ids;           // [lists.nblocks*64]
+  DevBuf<uint64_t> timestamps;        // [lists.nblocks*64] stored timestamp per slot (pad slots 0, never read); null on the
+                                      // k-means hierarchy's indexes (device_index_from_rows)
   uint32_t stripe_rank = 0, stripe_world = 1;  // multi-GPU: block b of a list lives on rank b % world
   DevBuf<float> xnorm;                // [lists.nblocks*64] squared norm per slot (3e38 on pad slots)
   DevBuf<float> xnorm_img, cent_xnorm_img;  // the same in the column order of the bf16 images (filter_search.hip: image_column)
@@ -168,6 +180,7 @@ struct SearchIO {
   // multi-GPU: the coarse step of a query slice can run on another rank (device pointers, [nq][n_probe_eff])
   const uint32_t *probes_in = nullptr, *order_in = nullptr;  // skip the coarse step, use these probe lists
   uint32_t *probes_out = nullptr, *order_out = nullptr;      // coarse step only: probe lists + candidate-order ranks
+  const SlotFilter *filter = nullptr;  // restrict the candidates to the filter's slots (the coarse step never sees it)
 };
 vi_status device_index_search(const DeviceIndex &ix, const SearchIO &io);
 
@@ -223,11 +236,12 @@ vi_status device_index_from_rows(int device, int order, uint32_t dim, const floa
 vi_status group_ids_by_label_device(const uint32_t *labels_dev, uint64_t n, uint64_t k, DevBuf<uint32_t> &order,
                                     DevBuf<uint32_t> &seg, std::vector<uint64_t> *off_host, hipStream_t st,
                                     DevBuf<uint32_t> *scratch_keep = nullptr);
-// resident index straight from device data: list l = rows order[src_off[l] .. + len[l]) of X_dev
+// resident index straight from device data: list l = rows order[src_off[l] .. + len[l]) of X_dev; ts_dev (optional) =
+// timestamp per row, 0 or no array => now (what shard_export_device writes)
 vi_status device_index_from_order(int device, uint32_t dim, const float *table_host, uint64_t nlists, const float *X_dev,
                                   const uint32_t *order_dev, const std::vector<uint64_t> &src_off,
                                   const std::vector<uint32_t> &len, const std::vector<uint32_t> &list_shard,
-                                  const uint64_t *ids_dev, DeviceIndex *out);
+                                  const uint64_t *ids_dev, const uint64_t *ts_dev, uint64_t now, DeviceIndex *out);
 struct ShardExportWs {  // staging of shard_export_device, reused from shard to shard
   DevBuf<uint8_t> image;
   DevBuf<uint64_t> d_src, d_dst;

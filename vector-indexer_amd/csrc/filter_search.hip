@@ -48,6 +48,7 @@
 #include "mfma_bf16.hpp"
 #include "rank_stream.hpp"
 #include "scan.hpp"
+#include "slot_filter.hpp"
 #include "wave_select.hpp"
 #include "wave_sort.hpp"
 
@@ -70,7 +71,6 @@ constexpr int kGroupQ = 128;       // queries per work item: 4 waves x one MFMA 
 constexpr uint32_t kPosBits = 26;  // candidate key = (probe rank << 26) | position in list
 constexpr uint32_t kPosMask = (1u << kPosBits) - 1u;
 constexpr double kApproxRatio = 0.04;  // rank_approx_mode: margin unit / list spread up to which the hi planes alone rank
-constexpr float kBig = 3.0e38f;            // norm of pad slots inside the kernel (finite: low bits are reused)
 
 // mu (or null): the centre the ranking images are taken about (mean_kernel) — the norm of fl(v - mu) then
 __global__ void slot_norms_kernel(const float4 *blocks, uint32_t dq, uint64_t nslots, float *xnorm, uint32_t *xmax_bits,
@@ -191,14 +191,7 @@ __global__ void list_spread_kernel(const float4 *blocks, uint32_t dq, const floa
 // f32 blocks [quad][64] float4 -> bf16 blocks [chunk of 16 dims][plane hi/lo][half of 8 dims][64] x 16 B: the
 // image a 32x32x16 MFMA wants (lane (j,h) reads the 8 consecutive dims 16c+8h.. of vector j as one ds_read_b128),
 // same bytes per block as the f32 form
-// Column of vector v (0..63 of its block) in the bf16 image.  A lane of lane half h ends an MFMA holding rows
-// (e&3) + 8(e>>2) + 4h (e = 0..15) of each 32-row tile: a SUB-BLOCK, the unit the select re-evaluates exactly.  The image
-// places vectors so that sub-block (tile t, half h) is the 16 CONSECUTIVE vectors 32t + 16h .. + 15 of the block: their
-// f32 quads are 256 contiguous bytes, two whole cache lines, where the identity placement touched half of four.
-__host__ __device__ inline uint32_t image_column(uint32_t v) {
-  const uint32_t t = v >> 5, h = (v >> 4) & 1u, e = v & 15u;
-  return 32u * t + (e & 3u) + 8u * (e >> 2) + 4u * h;
-}
+// (the column of vector v of a block in the image: image_column, slot_filter.hpp)
 
 __global__ void split_bf16_kernel(const float4 *blocks, uint32_t dq, uint64_t nblocks, uint4 *out, const float4 *mu = nullptr) {
   const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;  // (block, chunk, half, vector)
@@ -1009,6 +1002,7 @@ struct SelectCommon {
   const float *mu;          // centre of the ranking images (rank values are those of q - mu against v - mu), or null
   uint32_t trunc;           // real-valued lists ranked from their hi planes: 1 queries hi + lo, 2 queries' hi plane only; 0 otherwise
   float rho_max, vmax;      // ... max |v - hi(v)| and max |v| over the lists (rounded up)
+  const uint64_t *allow;    // filtered search (select_kernel<Top, true> only): one allow word per block (slot_filter.hpp)
 };
 
 // the query's probes, one per lane r < P
@@ -1333,7 +1327,9 @@ constexpr uint32_t kCacheG = 256;      // group records (values + probe/segment/
 // One wave: top-K of query q under (exact distance, (g << 26) | position) from its G group records at gbase.
 // Leaves the result in `sel` (entry e of lane i = result 64e + i, key kNoPos when there are fewer than K).
 // Top = FastTopK (K <= 64) or FastTop128 (K <= 128: the Faiss-style harness asks for 100 neighbours), wave_sort.hpp.
-template <class Top>
+// FILT: a vector is offered only if its allow bit is set — the rank kernels saw the excluded slots with the pad norm, so
+// they sit in no bound; a sub-block queued for its allowed members is re-evaluated without the others.
+template <class Top, bool FILT = false>
 __device__ __forceinline__ void select_body(const SelectCommon &c, uint32_t q, size_t gbase, uint32_t G, uint32_t P,
                                             const ProbeRegs &pr, uint32_t K, int lane, uint32_t *pick, float4 *tcache,
                                             uint32_t *lcache, float *qlds, Top &sel, uint32_t *qbytes = nullptr) {
@@ -1396,6 +1392,10 @@ __device__ __forceinline__ void select_body(const SelectCommon &c, uint32_t q, s
     const uint32_t g = (uint32_t)__shfl((int)pr.g, (int)r);
     const uint32_t len = (uint32_t)__shfl((int)pr.len, (int)r);
     live = live && pos < len && !(c.xmode & 1u);
+    if constexpr (FILT) {  // slot = (fb + pos / 64) * 64 + pos % 64: the word is shared by the 16 lanes of a sub-block
+      const uint32_t p = live ? pos : 0u;
+      live = live && ((c.allow[fb + p / kWave] >> (p % kWave)) & 1ull) != 0ull;
+    }
     n_exact += (uint32_t)__popcll(__ballot(live));
     if (c.u8_nat && q_bytes)
       sel = exact_batch_u8_int_fn(sel, qbytes, qn_int, c.u8_nat + ((size_t)(fb + (live ? pos : 0u) / kWave) * (c.dq / 4)) * kWave + (pos % kWave),
@@ -1667,7 +1667,7 @@ struct SelectArgs {
 };
 
 // one wave per query: top-k over its probed lists in the reference's stable order (ivf_index.rs:264-274)
-template <class Top>
+template <class Top, bool FILT = false>
 __global__ void __launch_bounds__(256, 4) select_kernel(SelectArgs a) {
   __shared__ uint32_t s_pick[4][kPickCap], s_lcache[4][kCacheG];
   __shared__ float4 s_tcache[4][kCacheG];
@@ -1693,7 +1693,7 @@ __global__ void __launch_bounds__(256, 4) select_kernel(SelectArgs a) {
     }
   }
   Top sel;
-  select_body<Top>(a.c, q, a.qoff[q], a.qtot[q], a.P, pr, a.k, lane, s_pick[wave], s_tcache[wave],
+  select_body<Top, FILT>(a.c, q, a.qoff[q], a.qtot[q], a.P, pr, a.k, lane, s_pick[wave], s_tcache[wave],
                    s_lcache[wave], s_qrows + (size_t)wave * a.c.dim, sel, s_qbytes[wave]);
   // entry e of lane i holds result 64e + i: map the candidate-order rank g back to the probe rank r
   uint32_t found = 0;
@@ -2117,6 +2117,7 @@ SelectCommon select_common(const DeviceIndex &ix, const EngineKnobs &kn, const f
   c.wave_order = wave_order ? 1u : 0u;
   c.hi_nat = nullptr;
   c.u8_nat = nullptr;
+  c.allow = nullptr;
   // per-wave counters go to two addresses: 2 same-address atomics per query cost more than the whole select, so
   // they are a diagnostic (VI_FILTER_STATS=1), not part of the normal path
   c.dbg = kn.stats ? (unsigned long long *)ix.cur().ws.stats.p : nullptr;
@@ -2481,9 +2482,13 @@ vi_status coarse_only_filter(const DeviceIndex &ix, const EngineKnobs &kn, const
 
 vi_status search_filter_pipeline(const DeviceIndex &ix, const EngineKnobs &kn, const float *Qd, uint64_t nq, uint64_t k, uint32_t P,
                                  float *Dd, int64_t *Id, uint64_t *Td, uint64_t *slots, uint32_t *counts, hipStream_t st,
-                                 int timing_level, const uint32_t *probes_in, const uint32_t *order_in) {
+                                 int timing_level, const uint32_t *probes_in, const uint32_t *order_in, const SlotFilter *flt) {
   SearchWorkspace &ws = ix.cur().ws;
   vi_search_stats &stt = ix.cur().stats;
+  // a filter swaps the norms the LIST phase ranks with for its masked copies (excluded slots rank as pad slots do); the
+  // coarse phase keeps the table's own
+  const float *l_xnorm = flt ? flt->xnorm.p : ix.xnorm.p, *l_xnorm_img = flt ? flt->xnorm_img.p : ix.xnorm_img.p;
+  const int *l_i8_norm_img = flt ? flt->i8_norm_img.p : ix.i8_norm_img.p;
   // 1: an event at every phase boundary; 2: around the rank kernel only (every record is a barrier packet the next
   // kernel's dispatch waits behind: five of them cost 0.01 ms of a 0.5 ms step)
   const bool timing = timing_level == 1, rank_timing = timing_level != 0;
@@ -2593,7 +2598,7 @@ vi_status search_filter_pipeline(const DeviceIndex &ix, const EngineKnobs &kn, c
     if (nitems) {
       hipLaunchKernelGGL(item_list_kernel, dim3((nitems + 255) / 256), dim3(256), 0, st, ws.item_start.p, (uint32_t)nlists, nitems,
                          ws.item_list.p);
-      WideArgs a{(const uint4 *)ix.lists_bf16.p, ix.xnorm_img.p, (const uint4 *)ws.qimg.p, nc, ix.list_first_block.p, ix.list_len.p,
+      WideArgs a{(const uint4 *)ix.lists_bf16.p, l_xnorm_img, (const uint4 *)ws.qimg.p, nc, ix.list_first_block.p, ix.list_len.p,
                  ws.item_start.p, ws.seg_start.p, ws.pairs.p, ws.item_list.p, P, segb0, ws.qoff.p, ws.pair_rel.p, ws.tile_start.p,
                  (float4 *)ws.gval.p, ws.gpos.p, (float4 *)ws.brec.p};
       // (set on the device that launches, every time: a process may hold indexes on several GPUs)
@@ -2630,12 +2635,12 @@ vi_status search_filter_pipeline(const DeviceIndex &ix, const EngineKnobs &kn, c
         VI_HIP(hipGetLastError());
       }
       if (rank_i8) {
-        RankStreamI8Args a{(const uint4 *)ix.lists_i8.p, ix.i8_norm_img.p, (const uint4 *)ws.qimg8.p, (const uint4 *)ws.item_sdesc.p, nitems,
+        RankStreamI8Args a{(const uint4 *)ix.lists_i8.p, l_i8_norm_img, (const uint4 *)ws.qimg8.p, (const uint4 *)ws.item_sdesc.p, nitems,
                            ws.item_qcol.p, ws.item_grec.p, (uint32_t *)(ws.stats.p + 16), (float4 *)ws.gval.p, (float4 *)ws.brec.p};
         VI_TRY(start_rank_clock());
         VI_TRY(launch_rank_stream_i8(a, (ix.dim + 31) / 32, nitems, gq, st));
       } else {
-        RankStreamArgs a{(const uint4 *)ix.lists_bf16.p, ix.xnorm_img.p, (const uint4 *)ws.qimg.p, (const uint4 *)ws.item_sdesc.p, nitems,
+        RankStreamArgs a{(const uint4 *)ix.lists_bf16.p, l_xnorm_img, (const uint4 *)ws.qimg.p, (const uint4 *)ws.item_sdesc.p, nitems,
                          ws.item_qcol.p, ws.item_grec.p, (uint32_t *)(ws.stats.p + 16), (float4 *)ws.gval.p,
                          (float4 *)ws.brec.p, nullptr, kn.filter_xmode};
         const bool qlo = (hstats[13] != 0 || !kn.hi_only) && approx != 2;
@@ -2680,7 +2685,7 @@ vi_status search_filter_pipeline(const DeviceIndex &ix, const EngineKnobs &kn, c
     } else {
       FilterArgs a{};
       a.blocks = kn.rank_bf16 ? (const float4 *)ix.lists_bf16.p : (const float4 *)ix.lists.blocks.p;
-      a.xnorm = kn.rank_bf16 ? ix.xnorm_img.p : ix.xnorm.p; a.dq = dq; a.dim = ix.dim; a.Q = Qd;
+      a.xnorm = kn.rank_bf16 ? l_xnorm_img : l_xnorm; a.dq = dq; a.dim = ix.dim; a.Q = Qd;
       a.first_block = ix.list_first_block.p; a.list_len = ix.list_len.p; a.item_start = ws.item_start.p;
       a.seg_start = ws.seg_start.p; a.pairs = ws.pairs.p; a.nlists = (uint32_t)nlists; a.P = P; a.segb0 = segb0;
       a.qoff = ws.qoff.p; a.rel = ws.pair_rel.p; a.rec_stride = 0;
@@ -2711,8 +2716,16 @@ vi_status search_filter_pipeline(const DeviceIndex &ix, const EngineKnobs &kn, c
       a.c.vmax = (float)(std::sqrt((double)ix.i8_xmax2) * 1.0001);
     }
     const size_t qsm = 4ull * ix.dim * sizeof(float);
-    if (k <= 64) hipLaunchKernelGGL(select_kernel<FastTopK>, dim3((uint32_t)((nq + 3) / 4)), dim3(256), qsm, st, a);
-    else hipLaunchKernelGGL(select_kernel<FastTop128>, dim3((uint32_t)((nq + 3) / 4)), dim3(256), qsm, st, a);
+    const dim3 grid((uint32_t)((nq + 3) / 4));
+    if (flt) {  // an instantiation of its own: the unfiltered one keeps its registers and its four workgroups per CU
+      a.c.allow = flt->allow.p;
+      if (k <= 64) hipLaunchKernelGGL((select_kernel<FastTopK, true>), grid, dim3(256), qsm, st, a);
+      else hipLaunchKernelGGL((select_kernel<FastTop128, true>), grid, dim3(256), qsm, st, a);
+    } else if (k <= 64) {
+      hipLaunchKernelGGL(select_kernel<FastTopK>, grid, dim3(256), qsm, st, a);
+    } else {
+      hipLaunchKernelGGL(select_kernel<FastTop128>, grid, dim3(256), qsm, st, a);
+    }
     VI_HIP(hipGetLastError());
   }
   if (timing) VI_HIP(hipEventRecord(ix.cur().ev[4], st));

@@ -21,6 +21,7 @@
 
 #include "device_index.hpp"
 #include "scan.hpp"
+#include "slot_filter.hpp"
 
 namespace vi {
 namespace {
@@ -222,6 +223,18 @@ __global__ void generic_output_kernel(OutArgs a) {
   if (a.slots) a.slots[t] = gslot;
 }
 
+// filtered search: the excluded candidates received no key (their places kept the 0xFF fill, which sorts last), so the
+// real keys among the first k of a sorted row are the query's results
+__global__ void count_keys_kernel(const uint64_t *keys, uint32_t logL, uint32_t nq, uint32_t k, uint64_t *total) {
+  const uint32_t q = blockIdx.x, lane = threadIdx.x;
+  if (q >= nq) return;
+  uint32_t n = 0;
+  for (uint32_t i = lane; i < k; i += 64u) n += keys[((size_t)q << logL) + i] != ~0ull ? 1u : 0u;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) n += (uint32_t)__shfl_xor((int)n, o);
+  if (lane == 0) total[q] = n;
+}
+
 }  // namespace
 
 // device-wide sort of rows of 2^logL u64 keys (list_build.hip groups the point ids by list with it)
@@ -319,7 +332,7 @@ vi_status generic_probe_export(const DeviceIndex &ix, const float *Qd, uint64_t 
 
 vi_status device_index_search_generic(const DeviceIndex &ix, const float *Qd, uint64_t nq, uint64_t k, uint32_t P,
                                       float *Dd, int64_t *Id, uint64_t *Td, uint64_t *slots, uint32_t *counts,
-                                      hipStream_t st, const uint32_t *probes_in, const uint32_t *order_in) {
+                                      hipStream_t st, const uint32_t *probes_in, const uint32_t *order_in, const SlotFilter *flt) {
   SearchWorkspace &ws = ix.cur().ws;
   const uint32_t dim = ix.dim, dq = ix.dq;
   const uint64_t nlists = ix.nlists;
@@ -339,6 +352,7 @@ vi_status device_index_search_generic(const DeviceIndex &ix, const float *Qd, ui
     if (h_total[q] > 0xFFFFFFFFull) return fail(VI_ERR_OTHER, "more than 2^32 candidates for one query");
     stt.scanned_vectors += h_total[q];
   }
+  if (flt) VI_TRY(ws.total_allowed.reserve(nq));
 
   // ---- C/D. per chunk of queries: dump candidate keys, sort rows, emit the first k ----
   const uint32_t segb0 = 256;
@@ -368,10 +382,17 @@ vi_status device_index_search_generic(const DeviceIndex &ix, const float *Qd, ui
     a.seg_start = ws.seg_start.p; a.pairs = ws.pairs.p; a.nlists = (uint32_t)nlists; a.P = P;
     a.segb0 = segb0; a.segrun_start = ws.segrun_start.p;
     a.dump_keys = ws.sort_keys.p; a.dump_row = L; a.dump_off = ws.off_by_rank.p + q0 * P;
+    // a filter only drops keys: the candidate indices — and with them the recovery of (g, pos) — stay the unfiltered ones
+    a.allow = flt ? flt->allow.p : nullptr;
     VI_TRY(launch_scan(a, qg, ix.order, false, (uint32_t)hstats[1], st));
     VI_TRY(sort_rows(ws.sort_keys.p, m, logL, st));
+    if (flt) {
+      hipLaunchKernelGGL(count_keys_kernel, dim3((uint32_t)m), dim3(64), 0, st, ws.sort_keys.p, logL, (uint32_t)m, (uint32_t)k,
+                         ws.total_allowed.p + q0);
+      VI_HIP(hipGetLastError());
+    }
     OutArgs o{ws.sort_keys.p, logL, (uint32_t)m, P, (uint32_t)k, ws.probes.p + q0 * P, ws.gprobe.p + q0 * P,
-              ws.off_by_g.p + q0 * P, ix.list_first_block.p, ws.total.p + q0, ix.ext_ids.p, Dd + q0 * k, Id + q0 * k,
+              ws.off_by_g.p + q0 * P, ix.list_first_block.p, (flt ? ws.total_allowed.p : ws.total.p) + q0, ix.ext_ids.p, Dd + q0 * k, Id + q0 * k,
               Td ? Td + q0 * k : nullptr, slots ? slots + q0 * k : nullptr, counts ? counts + q0 : nullptr};
     hipLaunchKernelGGL(generic_output_kernel, dim3((uint32_t)((m * k + 255) / 256)), dim3(256), 0, st, o);
     VI_HIP(hipGetLastError());

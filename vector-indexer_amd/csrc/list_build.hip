@@ -165,6 +165,20 @@ __global__ void slot_rows_kernel(const uint32_t *order, const uint64_t *src_off,
   for (uint32_t j = threadIdx.x; j < padded; j += blockDim.x) dst[j] = j < len ? order[so + j] : kNoPos;
 }
 
+// the timestamp every slot's record carries in the shard files (export_records_kernel: 0 or no array => now); pad slots 0
+__global__ void slot_timestamps_kernel(const uint32_t *row_of_slot, const uint64_t *timestamps, uint64_t now, uint64_t nslots,
+                                       uint64_t *out) {
+  const uint64_t s = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= nslots) return;
+  const uint32_t row = row_of_slot[s];
+  uint64_t ts = 0ull;
+  if (row != kNoPos) {
+    ts = timestamps ? timestamps[row] : 0ull;
+    if (ts == 0) ts = now;
+  }
+  out[s] = ts;
+}
+
 // records of one shard in file order.  One wave per record: 32-bit words of {id, external_id, timestamp, D x f32, pad}
 struct ExportArgs {
   const float *X;
@@ -275,7 +289,7 @@ vi_status group_ids_by_label_device(const uint32_t *labels_dev, uint64_t n, uint
 vi_status device_index_from_order(int device, uint32_t dim, const float *table_host, uint64_t nlists, const float *X_dev,
                                   const uint32_t *order_dev, const std::vector<uint64_t> &src_off,
                                   const std::vector<uint32_t> &len, const std::vector<uint32_t> &list_shard,
-                                  const uint64_t *ids_dev, DeviceIndex *ix) {
+                                  const uint64_t *ids_dev, const uint64_t *ts_dev, uint64_t now, DeviceIndex *ix) {
   VI_TRY(init_device_index_pub(ix, device, dim, nlists));
   ix->order = VI_ORDER_SCALAR;
   const uint32_t dq = ix->dq;
@@ -309,6 +323,7 @@ vi_status device_index_from_order(int device, uint32_t dim, const float *table_h
   ix->lists.nblocks = total_blocks;
   VI_TRY(ix->lists.blocks.reserve(std::max<uint64_t>(1, total_blocks) * dq * kWave * 4));
   VI_TRY(ix->ext_ids.reserve(std::max<uint64_t>(1, total_blocks) * kWave));
+  VI_TRY(ix->timestamps.reserve(std::max<uint64_t>(1, total_blocks) * kWave));
   VI_TRY(ix->list_first_block.reserve(std::max<uint64_t>(1, nlists)));
   VI_TRY(ix->list_len.reserve(std::max<uint64_t>(1, nlists)));
   VI_TRY(ix->list_shard.reserve(std::max<uint64_t>(1, nlists)));
@@ -324,6 +339,11 @@ vi_status device_index_from_order(int device, uint32_t dim, const float *table_h
                        ix->list_len.p, (uint32_t)nlists, dros.p);
     VI_HIP(hipGetLastError());
     VI_TRY(launch_repack_rows(X_dev, dim, dq, dros.p, total_blocks * kWave, ids_dev, ix->lists.blocks.p, ix->ext_ids.p, st));
+    if (total_blocks) {
+      hipLaunchKernelGGL(slot_timestamps_kernel, dim3((uint32_t)((total_blocks * kWave + 255) / 256)), dim3(256), 0, st, dros.p,
+                         ts_dev, now, total_blocks * kWave, ix->timestamps.p);
+      VI_HIP(hipGetLastError());
+    }
     VI_HIP(hipStreamSynchronize(st));
   }
   return compute_slot_norms(ix);

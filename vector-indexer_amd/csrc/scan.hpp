@@ -50,6 +50,8 @@ struct ScanArgs {
   const uint32_t *segrun_start;
   float *seg_run_dist;
   uint32_t *seg_run_pos;
+  // LISTS, optional: one allow word per block (slot_filter.hpp); a vector whose bit is 0 is no candidate
+  const uint64_t *allow;
 };
 
 // segmentation rule shared by the grouping, scan and segment-merge kernels

@@ -31,6 +31,7 @@
 #include "device_index.hpp"
 #include "device_math.hpp"
 #include "scan.hpp"
+#include "slot_filter.hpp"
 #include "wave_select.hpp"
 #include "wave_sort.hpp"
 
@@ -113,7 +114,9 @@ struct Acc<VI_ORDER_LANES, QG> {
 // ------------------------------------------------------------------------------------------
 // scan kernel
 // ------------------------------------------------------------------------------------------
-template <int QG, int ORDER, bool COARSE, bool DUMP>
+// FILT (lists only): a vector is a candidate only if its bit of the block's allow word is set (slot_filter.hpp) — an
+// instantiation of its own, so that the unfiltered kernels keep their registers
+template <int QG, int ORDER, bool COARSE, bool DUMP, bool FILT = false>
 __global__ void __launch_bounds__(kBlockThreads) scan_kernel(ScanArgs a) {
   extern __shared__ float4 smem[];
   const int lane = threadIdx.x & (kWave - 1);
@@ -222,7 +225,8 @@ __global__ void __launch_bounds__(kBlockThreads) scan_kernel(ScanArgs a) {
     for (int j = 0; j < QG; ++j) acc.template add<3>(j, qi + 3, n8x2, has4, lq[j * a.dq + qi + 3], x3);
     if (++gq == gpb) {
       const uint32_t pos = blk * kWave + lane;
-      const bool valid = pos < len;
+      bool valid = pos < len;
+      if constexpr (FILT) valid = valid && ((a.allow[fb + blk] >> lane) & 1ull) != 0ull;  // (one word per block: a scalar load)
       const uint32_t p = valid ? pos : kNoPos;
 #pragma unroll
       for (int j = 0; j < QG; ++j)
@@ -713,6 +717,8 @@ struct RepackArgs {
   int32_t id_off;               // byte offset of the u64 external id, or -1
   float *blocks;
   uint64_t *ext_ids;            // may be null
+  int32_t ts_off;               // byte offset of the u64 timestamp, or -1
+  uint64_t *timestamps;         // may be null
 };
 
 __global__ void __launch_bounds__(kBlockThreads) repack_kernel(RepackArgs a) {
@@ -739,6 +745,11 @@ __global__ void __launch_bounds__(kBlockThreads) repack_kernel(RepackArgs a) {
     uint64_t id = ~0ull;
     if (valid && a.id_off >= 0) id = *reinterpret_cast<const uint64_t *>(rec + a.id_off);
     a.ext_ids[(size_t)dst * kWave + lane] = id;
+  }
+  if (a.timestamps) {
+    uint64_t ts = 0ull;
+    if (valid && a.ts_off >= 0) ts = *reinterpret_cast<const uint64_t *>(rec + a.ts_off);
+    a.timestamps[(size_t)dst * kWave + lane] = ts;
   }
 }
 
@@ -794,17 +805,29 @@ __global__ void l2sq_pairs_kernel(const float *a, const float *b, uint64_t n, ui
 // ------------------------------------------------------------------------------------------
 // launch helpers
 // ------------------------------------------------------------------------------------------
-template <int QG, int ORDER, bool COARSE, bool DUMP>
+template <int QG, int ORDER, bool COARSE, bool DUMP, bool FILT = false>
 vi_status launch_scan_t(const ScanArgs &a, uint32_t nitems_upper, hipStream_t st) {
   if (nitems_upper == 0) return VI_OK;
   const uint32_t grid = (nitems_upper + kWavesPerBlock - 1) / kWavesPerBlock;
   const size_t smem = (size_t)kWavesPerBlock * QG * a.dq * sizeof(float4);
   if (smem > 64 * 1024)
-    VI_HIP(hipFuncSetAttribute((const void *)scan_kernel<QG, ORDER, COARSE, DUMP>,
+    VI_HIP(hipFuncSetAttribute((const void *)scan_kernel<QG, ORDER, COARSE, DUMP, FILT>,
                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-  hipLaunchKernelGGL((scan_kernel<QG, ORDER, COARSE, DUMP>), dim3(grid), dim3(kBlockThreads), smem, st, a);
+  hipLaunchKernelGGL((scan_kernel<QG, ORDER, COARSE, DUMP, FILT>), dim3(grid), dim3(kBlockThreads), smem, st, a);
   VI_HIP(hipGetLastError());
   return VI_OK;
+}
+
+// mode (table / lists), output (runs / one key per candidate) and, on lists, with or without allow bits
+template <int QG, int ORDER>
+vi_status launch_scan_q(const ScanArgs &a, bool coarse, uint32_t nitems_upper, hipStream_t st) {
+  const bool dump = a.dump_keys != nullptr;
+  if (coarse)
+    return dump ? launch_scan_t<QG, ORDER, true, true>(a, nitems_upper, st) : launch_scan_t<QG, ORDER, true, false>(a, nitems_upper, st);
+  if (a.allow)
+    return dump ? launch_scan_t<QG, ORDER, false, true, true>(a, nitems_upper, st)
+                : launch_scan_t<QG, ORDER, false, false, true>(a, nitems_upper, st);
+  return dump ? launch_scan_t<QG, ORDER, false, true>(a, nitems_upper, st) : launch_scan_t<QG, ORDER, false, false>(a, nitems_upper, st);
 }
 
 }  // namespace
@@ -826,18 +849,8 @@ vi_status launch_scan(const ScanArgs &a, int qg, int order, bool coarse, uint32_
 #define VI_SCAN_CASE(QGV)                                                                                  \
   if (qg == QGV) {                                                                                         \
     constexpr int QL = QGV > 4 ? 4 : QGV; /* LANES order keeps 8 accumulators per pair: cap the group */   \
-    if (a.dump_keys) {                                                                                     \
-      if (order == VI_ORDER_SCALAR)                                                                        \
-        return coarse ? launch_scan_t<QGV, VI_ORDER_SCALAR, true, true>(a, nitems_upper, st)               \
-                      : launch_scan_t<QGV, VI_ORDER_SCALAR, false, true>(a, nitems_upper, st);             \
-      return coarse ? launch_scan_t<QL, VI_ORDER_LANES, true, true>(a, nitems_upper, st)                   \
-                    : launch_scan_t<QL, VI_ORDER_LANES, false, true>(a, nitems_upper, st);                 \
-    }                                                                                                      \
-    if (order == VI_ORDER_SCALAR)                                                                          \
-      return coarse ? launch_scan_t<QGV, VI_ORDER_SCALAR, true, false>(a, nitems_upper, st)                \
-                    : launch_scan_t<QGV, VI_ORDER_SCALAR, false, false>(a, nitems_upper, st);              \
-    return coarse ? launch_scan_t<QL, VI_ORDER_LANES, true, false>(a, nitems_upper, st)                    \
-                  : launch_scan_t<QL, VI_ORDER_LANES, false, false>(a, nitems_upper, st);                  \
+    if (order == VI_ORDER_SCALAR) return launch_scan_q<QGV, VI_ORDER_SCALAR>(a, coarse, nitems_upper, st); \
+    return launch_scan_q<QL, VI_ORDER_LANES>(a, coarse, nitems_upper, st);                                 \
   }
   VI_SCAN_CASE(1)
   VI_SCAN_CASE(2)
@@ -925,7 +938,7 @@ struct ContextLease {
 static vi_status repack_upload(const uint8_t *host_src, size_t src_bytes, const std::vector<uint64_t> &blk_src,
                                const std::vector<uint32_t> &blk_nv, const std::vector<uint32_t> &blk_dst,
                                uint32_t dim, uint32_t dq, uint32_t stride, uint32_t vec_off, int32_t id_off,
-                               float *blocks, uint64_t *ext_ids, hipStream_t st) {
+                               float *blocks, uint64_t *ext_ids, int32_t ts_off, uint64_t *timestamps, hipStream_t st) {
   const uint32_t nb = (uint32_t)blk_src.size();
   if (nb == 0) return VI_OK;
   DevBuf<uint8_t> img;
@@ -939,7 +952,7 @@ static vi_status repack_upload(const uint8_t *host_src, size_t src_bytes, const 
   VI_HIP(hipMemcpyAsync(dsrc.p, blk_src.data(), nb * sizeof(uint64_t), hipMemcpyHostToDevice, st));
   VI_HIP(hipMemcpyAsync(dnv.p, blk_nv.data(), nb * sizeof(uint32_t), hipMemcpyHostToDevice, st));
   VI_HIP(hipMemcpyAsync(ddst.p, blk_dst.data(), nb * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-  RepackArgs a{img.p, dsrc.p, dnv.p, ddst.p, nb, dim, dq, stride, vec_off, id_off, blocks, ext_ids};
+  RepackArgs a{img.p, dsrc.p, dnv.p, ddst.p, nb, dim, dq, stride, vec_off, id_off, blocks, ext_ids, ts_off, timestamps};
   hipLaunchKernelGGL(repack_kernel, dim3((nb + kWavesPerBlock - 1) / kWavesPerBlock), dim3(kBlockThreads), 0, st, a);
   VI_HIP(hipGetLastError());
   VI_HIP(hipStreamSynchronize(st));  // img is freed on return
@@ -984,7 +997,7 @@ vi_status device_index_load(const IndexMeta &meta, const std::string &shards_dir
       dst[b] = (uint32_t)b;
     }
     VI_TRY(repack_upload((const uint8_t *)meta.centroids.data(), meta.centroids.size() * 4, src, nv, dst, dim, dq,
-                         dim * 4, 0, -1, ix->centroids.blocks.p, nullptr, ix->stream));
+                         dim * 4, 0, -1, ix->centroids.blocks.p, nullptr, -1, nullptr, ix->stream));
   }
 
   // ---- lists: every rank maps all shard files and keeps a STRIPE of every list resident: block b (64 vectors)
@@ -1054,6 +1067,7 @@ vi_status device_index_load(const IndexMeta &meta, const std::string &shards_dir
   ix->lists.nblocks = total_blocks;
   VI_TRY(ix->lists.blocks.reserve(std::max<uint64_t>(1, total_blocks) * dq * kWave * 4));
   VI_TRY(ix->ext_ids.reserve(std::max<uint64_t>(1, total_blocks) * kWave));
+  VI_TRY(ix->timestamps.reserve(std::max<uint64_t>(1, total_blocks) * kWave));
   const uint32_t stride = (uint32_t)record_stride(dim);
   for (uint64_t s = 0; s < nshards; ++s) {
     if (!files[s]) continue;
@@ -1082,8 +1096,9 @@ vi_status device_index_load(const IndexMeta &meta, const std::string &shards_dir
         if (dst.back() >= total_blocks) return fail(VI_ERR_INVALID_DATA, "shard_%llu.bin: list blocks exceed the index layout", (unsigned long long)s);
       }
     }
+    // VectorMeta {id, external_id, timestamp} (shards.rs:45-51): the timestamp stays resident for vi_indexer_filter_timestamps
     VI_TRY(repack_upload(lo, (size_t)(hi - lo), src, nv, dst, dim, dq, stride, (uint32_t)kVectorMetaBytes, 8,
-                         ix->lists.blocks.p, ix->ext_ids.p, ix->stream));
+                         ix->lists.blocks.p, ix->ext_ids.p, 16, ix->timestamps.p, ix->stream));
   }
   VI_TRY(ix->list_first_block.reserve(std::max<uint64_t>(1, k)));
   VI_TRY(ix->list_len.reserve(std::max<uint64_t>(1, k)));
@@ -1179,14 +1194,14 @@ vi_status device_index_from_rows(int device, int order, uint32_t dim, const floa
 
 vi_status search_filter_pipeline(const DeviceIndex &ix, const EngineKnobs &kn, const float *Qd, uint64_t nq, uint64_t k, uint32_t P,
                                  float *Dd, int64_t *Id, uint64_t *Td, uint64_t *slots, uint32_t *counts, hipStream_t st,
-                                 int timing_level, const uint32_t *probes_in, const uint32_t *order_in);
+                                 int timing_level, const uint32_t *probes_in, const uint32_t *order_in, const SlotFilter *flt);
 vi_status coarse_only_filter(const DeviceIndex &ix, const EngineKnobs &kn, const float *Qd, uint64_t nq, uint32_t P, hipStream_t st);
 bool filter_path_applicable(const DeviceIndex &ix, const EngineKnobs &kn, uint64_t k, uint32_t P);
 bool coarse_on_matrix_cores(const DeviceIndex &ix, const EngineKnobs &kn, uint64_t nq, uint32_t P);
 
 vi_status device_index_search_generic(const DeviceIndex &ix, const float *Qd, uint64_t nq, uint64_t k, uint32_t P,
                                       float *Dd, int64_t *Id, uint64_t *Td, uint64_t *slots, uint32_t *counts,
-                                      hipStream_t st, const uint32_t *probes_in, const uint32_t *order_in);
+                                      hipStream_t st, const uint32_t *probes_in, const uint32_t *order_in, const SlotFilter *flt);
 vi_status generic_probe_export(const DeviceIndex &ix, const float *Qd, uint64_t nq, uint32_t P, hipStream_t st);
 
 // ------------------------------------------------------------------------------------------
@@ -1278,7 +1293,7 @@ vi_status adopt_probes(const DeviceIndex &ix, uint64_t nq, uint32_t P, const uin
 
 vi_status search_valu_pipeline(const DeviceIndex &ix, const EngineKnobs &kn, const float *Qd, uint64_t nq, uint64_t k, uint32_t P,
                                uint32_t K, float *Dd, int64_t *Id, uint64_t *Td, uint64_t *slots, uint32_t *counts, hipStream_t st,
-                               int timing_level, const uint32_t *probes_in, const uint32_t *order_in) {
+                               int timing_level, const uint32_t *probes_in, const uint32_t *order_in, const SlotFilter *flt) {
   const bool timing = timing_level == 1, rank_timing = timing_level != 0;
   SearchWorkspace &ws = ix.cur().ws;
   vi_search_stats &stt = ix.cur().stats;
@@ -1335,6 +1350,7 @@ vi_status search_valu_pipeline(const DeviceIndex &ix, const EngineKnobs &kn, con
     a.seg_start = ws.seg_start.p; a.pairs = ws.pairs.p; a.nlists = (uint32_t)nlists; a.P = P;
     a.segb0 = kSegBlocks; a.segrun_start = ws.segrun_start.p;
     a.seg_run_dist = ws.seg_run_dist.p; a.seg_run_pos = ws.seg_run_pos.p;
+    a.allow = flt ? flt->allow.p : nullptr;  // excluded vectors never enter a run: the merges below see none of them
     VI_TRY(launch_scan(a, qg_l, ix.order, false, (uint32_t)hstats[1], st));
     if (nsegruns) {
       SegMergeArgs m{ws.seg_start.p, ws.segrun_start.p, ix.list_len.p, ws.pairs.p, (uint32_t)nlists, kSegBlocks, K,
@@ -1422,6 +1438,8 @@ vi_status device_index_search(const DeviceIndex &ix, const SearchIO &io) {
   const uint32_t dim = ix.dim, dq = ix.dq;
   const uint64_t nlists = ix.nlists;
   if (nq == 0) return VI_OK;
+  const SlotFilter *flt = io.filter;
+  if (flt && flt->owner_serial != ix.serial) return fail(VI_ERR_INVALID_INPUT, "the filter was made for another index");
   if (nq * std::max<uint64_t>(k, 64) > 0x7FFFFFFFull) return fail(VI_ERR_INVALID_INPUT, "batch too large: split nq");
   const uint32_t P = (uint32_t)std::min<uint64_t>(io.n_probe, nlists);  // take(n_probe) (ivf_index.rs:216-220)
   const uint32_t K = (uint32_t)std::min<uint64_t>(k, kMaxSelect);
@@ -1478,11 +1496,11 @@ vi_status device_index_search(const DeviceIndex &ix, const SearchIO &io) {
     return VI_OK;
   }
   if (generic) {  // (k > 128 or n_probe > 64, with the caller's probe lists too)
-    VI_TRY(device_index_search_generic(ix, Qd, nq, k, P, Dd, Id, Td, slots, ws.counts.p, st, io.probes_in, io.order_in));
+    VI_TRY(device_index_search_generic(ix, Qd, nq, k, P, Dd, Id, Td, slots, ws.counts.p, st, io.probes_in, io.order_in, flt));
   } else if (use_filter) {
-    VI_TRY(search_filter_pipeline(ix, kn, Qd, nq, k, P, Dd, Id, Td, slots, ws.counts.p, st, timing, io.probes_in, io.order_in));
+    VI_TRY(search_filter_pipeline(ix, kn, Qd, nq, k, P, Dd, Id, Td, slots, ws.counts.p, st, timing, io.probes_in, io.order_in, flt));
   } else {
-    VI_TRY(search_valu_pipeline(ix, kn, Qd, nq, k, P, K, Dd, Id, Td, slots, ws.counts.p, st, timing, io.probes_in, io.order_in));
+    VI_TRY(search_valu_pipeline(ix, kn, Qd, nq, k, P, K, Dd, Id, Td, slots, ws.counts.p, st, timing, io.probes_in, io.order_in, flt));
   }
 
   if (ix.stripe_world > 1 && Td) {

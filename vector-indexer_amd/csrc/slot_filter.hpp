@@ -1,0 +1,42 @@
+// slot_filter.hpp — a subset of an index's resident vectors that a search may be restricted to (slot_filter.hip).
+//
+// The search engines already ignore some slots: the pad lanes at the tail of every list.  The matrix-core ranking never
+// ranks them because their squared norm is kBig (kI8PadNorm in the int8 frame), the exact evaluations mask them by
+// `pos < len`.  A filter makes the excluded slots look the same way: a copy of the norm arrays in which they hold the pad
+// value, and one allow bit per slot for the places where exact distances are offered.  The coarse step, the grouping, the
+// work items, the records and the tie keys of a filtered search are those of the unfiltered one.
+#pragma once
+#include <cstdint>
+
+#include "common.hpp"
+
+namespace vi {
+
+struct DeviceIndex;
+
+constexpr float kBig = 3.0e38f;  // norm of pad slots inside the rank kernels (finite: low bits are reused)
+
+// Column of vector v (0..63 of its block) in the bf16 / int8 images.  A lane of lane half h ends an MFMA holding rows
+// (e&3) + 8(e>>2) + 4h (e = 0..15) of each 32-row tile: a SUB-BLOCK, the unit the select re-evaluates exactly.  The image
+// places vectors so that sub-block (tile t, half h) is the 16 CONSECUTIVE vectors 32t + 16h .. + 15 of the block: their
+// f32 quads are 256 contiguous bytes, two whole cache lines, where the identity placement touched half of four.
+__host__ __device__ inline uint32_t image_column(uint32_t v) {
+  const uint32_t t = v >> 5, h = (v >> 4) & 1u, e = v & 15u;
+  return 32u * t + (e & 3u) + 8u * (e >> 2) + 4u * h;
+}
+
+// Immutable once built: any number of concurrent searches of its index may share it.  12 bytes per resident slot
+// (16 with an int8 image) + 1 bit.
+struct SlotFilter {
+  uint64_t owner_serial = 0;      // DeviceIndex::serial of the index whose slots it describes
+  DevBuf<uint64_t> allow;         // [lists.nblocks] bit = lane of the block; pad slots 0
+  DevBuf<float> xnorm;            // the index's xnorm / xnorm_img / i8_norm_img with kBig / kI8PadNorm on every slot
+  DevBuf<float> xnorm_img;        //   whose allow bit is 0
+  DevBuf<int> i8_norm_img;        // (only when the index has an int8 image)
+  uint64_t num_allowed = 0;       // resident vectors with allow bit 1
+};
+
+// allow = stored timestamp within [ts_min, ts_max] (both inclusive)
+vi_status slot_filter_timestamps(const DeviceIndex &ix, uint64_t ts_min, uint64_t ts_max, SlotFilter *out);
+
+}  // namespace vi

@@ -24,13 +24,40 @@ import numpy as np
 from . import _native
 from ._native import (ViError, lib, VI_ASSIGN_EXACT, VI_ASSIGN_REFERENCE, VI_ORDER_LANES, VI_ORDER_SCALAR)
 
-__all__ = ["build", "load", "suggest_nlist", "VectorIndex", "ViError", "kmeans_mini_batch", "kmeans_parallel",
+__all__ = ["build", "load", "suggest_nlist", "VectorIndex", "TimestampFilter", "ViError", "kmeans_mini_batch", "kmeans_parallel",
            "assign", "l2sq_pairs", "VI_ASSIGN_EXACT", "VI_ASSIGN_REFERENCE", "VI_ORDER_LANES", "VI_ORDER_SCALAR"]
 
 
 def suggest_nlist(n: int) -> int:
     """lib.rs:308-315 (mirrors src/utils.rs:9-16)."""
     return int(lib().vi_calculate_num_clusters(int(n)))
+
+
+class TimestampFilter:
+    """The vectors of one VectorIndex whose stored timestamp lies in [ts_min, ts_max] (VectorIndex.filter_timestamps).
+    Immutable; pass it as `filter=` to that index's searches.  Keeps its index alive and frees itself."""
+
+    def __init__(self, index, handle, ts_min, ts_max):
+        self._index = index  # (the native filter must be freed before its indexer)
+        self._h = handle
+        self.ts_min, self.ts_max = int(ts_min), int(ts_max)
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h and lib is not None:
+            try:
+                lib().vi_filter_free(h)
+            except Exception:
+                pass
+
+    @property
+    def num_allowed(self) -> int:
+        """resident vectors inside the window"""
+        return int(lib().vi_filter_num_allowed(self._h))
+
+
+def _filter_handle(f):
+    return f._h if f is not None else None
 
 
 class VectorIndex:
@@ -73,7 +100,13 @@ class VectorIndex:
         return cent, c2s
 
     # PyVectorIndex.search_blocking (lib.rs:123-203)
-    def search_sync(self, xq, k: int, n_probe: int, include_vectors: bool = False):
+    def filter_timestamps(self, ts_min: int, ts_max: int) -> TimestampFilter:
+        """extension: the searches of this index restricted to stored timestamps in [ts_min, ts_max], both inclusive"""
+        h = C.c_void_p()
+        _native.check(lib().vi_indexer_filter_timestamps(self._h, int(ts_min), int(ts_max), C.byref(h)))
+        return TimestampFilter(self, h, ts_min, ts_max)
+
+    def search_sync(self, xq, k: int, n_probe: int, include_vectors: bool = False, filter: Optional[TimestampFilter] = None):
         xq = np.asarray(xq)
         if xq.ndim != 2:
             raise RuntimeError("Query array must be 2-dimensional")
@@ -86,9 +119,9 @@ class VectorIndex:
         I = np.full((nq, max(k, 0)), -1, dtype=np.int64)
         V = np.zeros((nq, k, self._dimension), dtype=np.float32) if include_vectors else None
         kout = C.c_uint64(0)
-        _native.check(lib().vi_indexer_search(self._h, _native.ptr(xq), nq, xq.shape[1], k, int(n_probe),
-                                              _native.ptr(D), _native.ptr(I), _native.ptr(V), None,
-                                              C.byref(kout)))
+        _native.check(lib().vi_indexer_search_filtered(self._h, _filter_handle(filter), _native.ptr(xq), nq, xq.shape[1], k,
+                                                       int(n_probe), _native.ptr(D), _native.ptr(I), _native.ptr(V), None,
+                                                       C.byref(kout)))
         if kout.value != k:  # k was clamped to max_k (api.rs:189): results occupy the first kout columns
             kk = kout.value
             D2 = np.full((nq, k), np.inf, dtype=np.float32)
@@ -125,9 +158,11 @@ class VectorIndex:
         return {f: getattr(st, f) for f, _ in st._fields_}
 
     # device-pointer search used by the multi-GPU path (torch tensors on this GPU)
-    def search_device(self, xq_ptr: int, nq: int, k: int, n_probe: int, D_ptr: int, I_ptr: int, tie_ptr: int = 0):
-        _native.check(lib().vi_indexer_search_device(self._h, C.c_void_p(xq_ptr), nq, k, n_probe, C.c_void_p(D_ptr),
-                                                     C.c_void_p(I_ptr), C.c_void_p(tie_ptr) if tie_ptr else None))
+    def search_device(self, xq_ptr: int, nq: int, k: int, n_probe: int, D_ptr: int, I_ptr: int, tie_ptr: int = 0,
+                      filter: Optional[TimestampFilter] = None):
+        _native.check(lib().vi_indexer_search_filtered_device(self._h, _filter_handle(filter), C.c_void_p(xq_ptr), nq, k,
+                                                              n_probe, C.c_void_p(D_ptr), C.c_void_p(I_ptr),
+                                                              C.c_void_p(tie_ptr) if tie_ptr else None))
 
 
     def probe_device(self, xq_ptr: int, nq: int, n_probe: int, probes_ptr: int, order_ptr: int) -> int:
@@ -138,12 +173,13 @@ class VectorIndex:
         return int(p_eff.value)
 
     def search_probed_device(self, xq_ptr: int, nq: int, k: int, n_probe_eff: int, probes_ptr: int, order_ptr: int,
-                             D_ptr: int, I_ptr: int, tie_ptr: int = 0):
+                             D_ptr: int, I_ptr: int, tie_ptr: int = 0, filter: Optional[TimestampFilter] = None):
         """list scan + top-k (ivf_index.rs:223-274) with probe lists computed elsewhere"""
-        _native.check(lib().vi_indexer_search_probed_device(self._h, C.c_void_p(xq_ptr), nq, k, n_probe_eff,
-                                                            C.c_void_p(probes_ptr), C.c_void_p(order_ptr),
-                                                            C.c_void_p(D_ptr), C.c_void_p(I_ptr),
-                                                            C.c_void_p(tie_ptr) if tie_ptr else None))
+        _native.check(lib().vi_indexer_search_probed_filtered_device(self._h, _filter_handle(filter), C.c_void_p(xq_ptr), nq,
+                                                                     k, n_probe_eff, C.c_void_p(probes_ptr),
+                                                                     C.c_void_p(order_ptr), C.c_void_p(D_ptr),
+                                                                     C.c_void_p(I_ptr),
+                                                                     C.c_void_p(tie_ptr) if tie_ptr else None))
 
 
 def _config(dimension, index_dir, shards_dir, **ext):

@@ -92,6 +92,12 @@ SIGNATURES = {
     "vi_indexer_search_device": (C.c_int, [vp, vp, u64, u64, u64, vp, vp, vp]),
     "vi_indexer_probe_device": (C.c_int, [vp, vp, u64, u64, vp, vp, C.POINTER(u64)]),
     "vi_indexer_search_probed_device": (C.c_int, [vp, vp, u64, u64, u64, vp, vp, vp, vp, vp]),
+    "vi_indexer_filter_timestamps": (C.c_int, [vp, u64, u64, C.POINTER(vp)]),
+    "vi_filter_num_allowed": (u64, [vp]),
+    "vi_filter_free": (None, [vp]),
+    "vi_indexer_search_filtered": (C.c_int, [vp, vp, vp, u64, u32, u64, u64, vp, vp, vp, vp, C.POINTER(u64)]),
+    "vi_indexer_search_filtered_device": (C.c_int, [vp, vp, vp, u64, u64, u64, vp, vp, vp]),
+    "vi_indexer_search_probed_filtered_device": (C.c_int, [vp, vp, vp, u64, u64, u64, vp, vp, vp, vp, vp]),
     "vi_merge_partials_device": (C.c_int, [i32, u64, u64, u32, vp, vp, vp, vp, vp]),
     "vi_packed_result_bytes": (u64, [u64, u64]),
     "vi_merge_partials_packed_device": (C.c_int, [i32, u64, u64, u32, vp, vp, vp]),

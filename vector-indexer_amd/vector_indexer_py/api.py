@@ -11,7 +11,7 @@ Errors are ViError (a RuntimeError) whose .kind is the io::ErrorKind name the re
 """
 import ctypes as C
 from dataclasses import dataclass, field, replace
-from typing import List, Optional
+from typing import List, Optional, Tuple
 
 import numpy as np
 
@@ -61,6 +61,8 @@ class SearchRequest:
     include_vectors: bool = False
     k: int = 10
     n_probe: int = 20
+    # extension: only records whose stored timestamp lies in [lo, hi], both inclusive (None: all, the reference's search)
+    timestamp_range: Optional[Tuple[int, int]] = None
 
     def with_k(self, k):
         return replace(self, k=k)
@@ -70,6 +72,9 @@ class SearchRequest:
 
     def with_include_vectors(self, include_vectors):
         return replace(self, include_vectors=include_vectors)
+
+    def with_timestamp_range(self, lo, hi):
+        return replace(self, timestamp_range=(int(lo), int(hi)))
 
 
 @dataclass
@@ -83,11 +88,31 @@ class VectorIndexer:
     def __init__(self, cfg: VectorIndexerConfig, handle):
         self._cfg = cfg
         self._h = handle
+        self._filters = {}  # (lo, hi) -> native filter of the resident index
+
+    def _drop_filters(self):
+        filters, self._filters = getattr(self, "_filters", {}), {}
+        for f in filters.values():
+            lib().vi_filter_free(f)
 
     def __del__(self):
+        self._drop_filters()  # (before their indexer)
         h, self._h = getattr(self, "_h", None), None
         if h:
             lib().vi_indexer_free(h)
+
+    def _filter(self, rng):
+        if rng is None:
+            return None
+        key = (int(rng[0]), int(rng[1]))
+        f = self._filters.get(key)
+        if f is None:
+            f = C.c_void_p()
+            _native.check(lib().vi_indexer_filter_timestamps(self._h, key[0], key[1], C.byref(f)))
+            if len(self._filters) >= 16:  # (a filter holds device memory in proportion to the index)
+                self._drop_filters()
+            self._filters[key] = f
+        return f
 
     @staticmethod
     def _native_cfg(cfg: VectorIndexerConfig):
@@ -115,6 +140,7 @@ class VectorIndexer:
         return VectorIndexer(cfg, h)
 
     def build_from_records(self, records: List[VectorRecord]) -> "VectorIndexer":
+        self._drop_filters()  # (they describe the index this build replaces)
         n = len(records)
         dim = self._cfg.dimension
         dims = np.array([len(r.values) for r in records], dtype=np.uint32)
@@ -129,6 +155,7 @@ class VectorIndexer:
         return self
 
     def build_from_vector_file(self, path) -> "VectorIndexer":
+        self._drop_filters()
         _native.check(lib().vi_indexer_build_from_vector_file(self._h, str(path).encode()))
         return self
 
@@ -141,9 +168,9 @@ class VectorIndexer:
         V = np.zeros((1, max(kcap, 1), self._cfg.dimension), dtype=np.float32) if req.include_vectors else None
         cnt = np.zeros(1, dtype=np.uint64)
         kout = C.c_uint64(0)
-        _native.check(lib().vi_indexer_search(self._h, _native.ptr(q), 1, q.shape[1], k, int(req.n_probe),
-                                              _native.ptr(D), _native.ptr(I), _native.ptr(V), _native.ptr(cnt),
-                                              C.byref(kout)))
+        _native.check(lib().vi_indexer_search_filtered(self._h, self._filter(req.timestamp_range), _native.ptr(q), 1,
+                                                       q.shape[1], k, int(req.n_probe), _native.ptr(D), _native.ptr(I),
+                                                       _native.ptr(V), _native.ptr(cnt), C.byref(kout)))
         return [SearchResult(int(I[0, j]), float(D[0, j]), V[0, j].tolist() if V is not None else None)
                 for j in range(int(cnt[0]))]
 
