@@ -61,7 +61,7 @@ struct SearchWorkspace {
   DevBuf<uint64_t> tie;
   DevBuf<uint64_t> slots;       // [nq][k] global slot of each result (include_vectors gather)
   DevBuf<uint32_t> counts;      // [nq]
-  DevBuf<uint64_t> stats;       // device-side counters
+  DevBuf<uint64_t> stats;       // device-side counters (layout: StatWord, search_internal.hpp)
   DevBuf<float> V;
   // MFMA filter path (filter_search.hip)
   DevBuf<uint32_t> c_seg, c_item, c_pairs;  // the coarse table grouped as one list ...
@@ -81,8 +81,8 @@ struct SearchWorkspace {
   DevBuf<float> brec;                       // pair records: the 4 sub-block minima of two blocks per (record tile, lane half, query of the group)
   struct GqHint { uint64_t nq; uint32_t P, gq; };
   std::vector<GqHint> gq_hint;              // queries per rank work item measured to suit a batch shape (filter_search.hip)
-  uint64_t *hstats_pinned = nullptr;        // page-locked landing buffer of the grouping's counts (16 words)
-  bool stats_zeroed = false;                // stats[13], [14] start at zero (filter_search.hip)
+  uint64_t *hstats_pinned = nullptr;        // page-locked landing buffer of the grouping's counts (kStatGroupingLanding words)
+  bool stats_zeroed = false;                // the batch flags of ws.stats start at zero (StatWord, search_internal.hpp)
   bool queries_hi_only = false;             // the previous batch's -2 q were all bf16-exact (no lo plane)
   DevBuf<uint64_t> sort_keys, order_keys, total;
   DevBuf<uint64_t> total_allowed;           // generic engine with a filter: candidates per query that received a key
@@ -112,8 +112,8 @@ struct DeviceIndex {
                                       // k-means hierarchy's indexes (device_index_from_rows)
   uint32_t stripe_rank = 0, stripe_world = 1;  // multi-GPU: block b of a list lives on rank b % world
   DevBuf<float> xnorm;                // [lists.nblocks*64] squared norm per slot (3e38 on pad slots)
-  DevBuf<float> xnorm_img, cent_xnorm_img;  // the same in the column order of the bf16 images (filter_search.hip: image_column)
-  DevBuf<uint32_t> lists_bf16, cent_bf16;  // bf16 hi/lo images of the blocks for the MFMA ranking (filter_search.hip)
+  DevBuf<float> xnorm_img, cent_xnorm_img;  // the same in the column order of the bf16 images (slot_filter.hpp: image_column)
+  DevBuf<uint32_t> lists_bf16, cent_bf16;  // bf16 hi/lo images of the blocks for the MFMA ranking (rank_images.hip)
   DevBuf<uint32_t> lists_u8_nat;           // 8-bit descriptors (integers 0..255): one byte per dimension, same order (exact re-evaluation)
   DevBuf<uint32_t> lists_hi_nat;           // bf16-exact lists: their hi plane in the blocks' own vector order (exact re-evaluation)
   // 8-bit descriptors, D <= 128: int8 image 127 - v of the lists (block and column order of the bf16 image), h(v) =
@@ -215,8 +215,6 @@ struct EngineKnobs {
   uint32_t stats_mask;
 };
 EngineKnobs read_engine_knobs();
-// squared norms of the stored vectors (filter_search.hip); called at the end of every index upload
-vi_status compute_slot_norms(DeviceIndex *ix);
 
 // Build a device index from device-resident arrays (used by the k-means path, where the
 // "index" is the two-level centroid hierarchy of assign_points_hierarchical, kmeans.rs:474-581,

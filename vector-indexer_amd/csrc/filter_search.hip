@@ -48,284 +48,19 @@
 #include "mfma_bf16.hpp"
 #include "rank_stream.hpp"
 #include "scan.hpp"
+#include "search_internal.hpp"
 #include "slot_filter.hpp"
 #include "wave_select.hpp"
 #include "wave_sort.hpp"
 
 namespace vi {
-
-// provided by search_kernels.hip
-vi_status stage_coarse(const DeviceIndex &ix, const float *Qd, uint64_t nq, uint32_t P, hipStream_t st);
-vi_status adopt_probes(const DeviceIndex &ix, uint64_t nq, uint32_t P, const uint32_t *probes_in, const uint32_t *order_in,
-                       bool histogram, hipStream_t st);
-vi_status launch_grouping(const DeviceIndex &ix, const uint32_t *probes, uint64_t nq, uint32_t P, int qg, uint32_t segb0,
-                          uint64_t hstats[15], hipStream_t st, bool histogram_done, const uint32_t *qtot = nullptr,
-                          uint32_t *qoff = nullptr, const uint32_t *pair_rank = nullptr);
-bool grouping_fuses_query_offsets(const DeviceIndex &ix);
-
 namespace {
 
 constexpr int kWave = 64;
-constexpr uint32_t kMaxFilterDim = 1536;  // the MFMA engine's dimension limit (rank_wide_kernel above 128)
-constexpr int kGroupQ = 128;       // queries per work item: 4 waves x one MFMA column tile of 32
+constexpr int kGroupQ = 128;      // queries per work item: 4 waves x one MFMA column tile of 32
 constexpr uint32_t kPosBits = 26;  // candidate key = (probe rank << 26) | position in list
 constexpr uint32_t kPosMask = (1u << kPosBits) - 1u;
 constexpr double kApproxRatio = 0.04;  // rank_approx_mode: margin unit / list spread up to which the hi planes alone rank
-
-// mu (or null): the centre the ranking images are taken about (mean_kernel) — the norm of fl(v - mu) then
-__global__ void slot_norms_kernel(const float4 *blocks, uint32_t dq, uint64_t nslots, float *xnorm, uint32_t *xmax_bits,
-                                  const float4 *mu = nullptr) {
-  const uint64_t s = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (s >= nslots) return;
-  double acc = 0.0;  // (pad slots hold zeros: they are marked by pad_norms_kernel from the list layout afterwards)
-  const float4 *p = blocks + (s / kWave) * dq * kWave + (s % kWave);
-  for (uint32_t qd = 0; qd < dq; ++qd) {
-    float4 v = p[(size_t)qd * kWave];
-    if (mu) { const float4 m = mu[qd]; v.x -= m.x; v.y -= m.y; v.z -= m.z; v.w -= m.w; }
-    acc += (double)v.x * v.x + (double)v.y * v.y + (double)v.z * v.z + (double)v.w * v.w;
-  }
-  float out = (float)acc;
-  if (out < kBig) atomicMax(xmax_bits, __float_as_uint(out));
-  xnorm[s] = fminf(out, kBig);
-}
-
-// pad slots (positions len .. 64*ceil(len/64) of every list) never rank: the mask comes from the layout, not from the
-// stored ids — the reference accepts ANY u64 as external_id (api.rs:57-62), 2^64-1 included
-__global__ void pad_norms_kernel(const uint32_t *first_block, const uint32_t *list_len, uint32_t nlists, float *xnorm) {
-  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-  const uint32_t l = t >> 6, j = t & 63u;
-  if (l >= nlists) return;
-  const uint32_t len = list_len[l], p = len + j;
-  if (p < ((len + 63u) & ~63u)) xnorm[(size_t)first_block[l] * kWave + p] = kBig;  // (finite: the kernel reuses the low mantissa bits)
-}
-
-// component sums of all stored vectors (pad slots hold zeros): WG (quad, g) walks blocks g, g + G, ..., a lane per vector;
-// one atomic per component and work-group.  sums: dq * 4 doubles.
-__global__ void mean_kernel(const float4 *blocks, uint32_t dq, uint64_t nblocks, double *sums) {
-  const uint32_t qd = blockIdx.x, lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
-  for (uint64_t b = (uint64_t)blockIdx.y * 4 + wave; b < nblocks; b += (uint64_t)gridDim.y * 4) {
-    const float4 v = blocks[(b * dq + qd) * 64 + lane];
-    a0 += v.x; a1 += v.y; a2 += v.z; a3 += v.w;
-  }
-  for (int o = 32; o > 0; o >>= 1) {
-    a0 += __shfl_xor(a0, o); a1 += __shfl_xor(a1, o); a2 += __shfl_xor(a2, o); a3 += __shfl_xor(a3, o);
-  }
-  if (lane == 0) {
-    atomicAdd(sums + 4 * qd + 0, a0); atomicAdd(sums + 4 * qd + 1, a1);
-    atomicAdd(sums + 4 * qd + 2, a2); atomicAdd(sums + 4 * qd + 3, a3);
-  }
-}
-__global__ void sum_f32_kernel(const float *x, uint64_t n, double *out) {  // finite entries only (pad slots hold kBig)
-  double a = 0.0;
-  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
-    const float v = x[i];
-    if (v < 1.0e37f) a += v;
-  }
-  for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o);
-  if ((threadIdx.x & 63u) == 0u) atomicAdd(out, a);
-}
-__global__ void max_finite_kernel(const float *x, uint64_t n, uint32_t *bits) {  // non-negative entries; pad slots (kBig) skipped
-  float m = 0.0f;
-  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
-    const float v = x[i];
-    if (v < 1.0e37f) m = fmaxf(m, v);
-  }
-  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-  if ((threadIdx.x & 63u) == 0u) atomicMax(bits, __float_as_uint(m));
-}
-// max over the stored vectors of |x - hi(x)|^2, x = v - mu and hi = its bf16 image: what ranking from the hi planes alone
-// leaves out of q.v is at most |q| times the root of this (pad slots — norm kBig in `norms` — do not count)
-__global__ void trunc_residual_kernel(const float4 *blocks, uint32_t dq, uint64_t nslots, const float *norms, const float4 *mu,
-                                      uint32_t *max_bits) {
-  const uint64_t s = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  float out = 0.0f;
-  if (s < nslots && norms[s] < 1.0e37f) {
-    double acc = 0.0;
-    const float4 *p = blocks + (s / kWave) * dq * kWave + (s % kWave);
-    for (uint32_t qd = 0; qd < dq; ++qd) {
-      float4 v = p[(size_t)qd * kWave];
-      if (mu) { const float4 m = mu[qd]; v.x -= m.x; v.y -= m.y; v.z -= m.z; v.w -= m.w; }
-      const float r0 = v.x - __uint_as_float(bf16_rn(v.x) << 16), r1 = v.y - __uint_as_float(bf16_rn(v.y) << 16);
-      const float r2 = v.z - __uint_as_float(bf16_rn(v.z) << 16), r3 = v.w - __uint_as_float(bf16_rn(v.w) << 16);
-      acc += (double)r0 * r0 + (double)r1 * r1 + (double)r2 * r2 + (double)r3 * r3;
-    }
-    out = (float)(acc * 1.000001);
-  }
-  for (int o = 32; o > 0; o >>= 1) out = fmaxf(out, __shfl_xor(out, o));
-  if ((threadIdx.x & 63u) == 0u && out > 0.0f) atomicMax(max_bits, __float_as_uint(out));
-}
-__global__ void mean_finish_kernel(const double *sums, uint32_t dim, uint32_t dim_pad, double n, float *mu) {
-  const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
-  if (e < dim_pad) mu[e] = e < dim ? (float)(sums[e] / n) : 0.0f;
-}
-
-// sampled spread of the lists: sums of ||v - c(list)||^2 and ||v||^2 over the first blocks of every list (one wave per list)
-__global__ void list_spread_kernel(const float4 *blocks, uint32_t dq, const float4 *cent_rows, uint32_t dim, const uint32_t *first_block,
-                                   const uint32_t *list_len, uint32_t nlists, uint32_t max_blocks, double *out) {
-  const uint32_t l = blockIdx.x, lane = threadIdx.x;
-  if (l >= nlists) return;
-  const uint32_t len = list_len[l], nb = min((len + 63u) / 64u, max_blocks);
-  double s_spread = 0.0, s_norm = 0.0, cnt = 0.0;
-  for (uint32_t b = 0; b < nb; ++b) {
-    if (b * 64u + lane >= len) continue;
-    const float4 *p = blocks + ((size_t)(first_block[l] + b) * dq) * 64 + lane;
-    float sp = 0.0f, nn = 0.0f;
-    for (uint32_t qd = 0; qd < dim / 4; ++qd) {
-      const float4 v = p[(size_t)qd * 64], c = cent_rows[(size_t)l * (dim / 4) + qd];
-      sp += (v.x - c.x) * (v.x - c.x) + (v.y - c.y) * (v.y - c.y) + (v.z - c.z) * (v.z - c.z) + (v.w - c.w) * (v.w - c.w);
-      nn += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
-    }
-    s_spread += sp; s_norm += nn; cnt += 1.0;
-  }
-  for (int o = 32; o > 0; o >>= 1) {
-    s_spread += __shfl_xor(s_spread, o); s_norm += __shfl_xor(s_norm, o); cnt += __shfl_xor(cnt, o);
-  }
-  if (lane == 0 && cnt > 0.0) { atomicAdd(out, s_spread); atomicAdd(out + 1, s_norm); atomicAdd(out + 2, cnt); }
-}
-
-// ------------------------------------------------------------------------------------------
-// bf16 x 3 ranking: every stored value x is split as hi + lo with hi = bf16(x), lo = bf16(x - hi)
-// (|x - hi| <= 2^-8 |x|, |x - hi - lo| <= 2^-17 |x|); q.v ~ hi.hi + hi.lo + lo.hi on the bf16 matrix pipe (16x the f32 rate)
-// ------------------------------------------------------------------------------------------
-// f32 blocks [quad][64] float4 -> bf16 blocks [chunk of 16 dims][plane hi/lo][half of 8 dims][64] x 16 B: the
-// image a 32x32x16 MFMA wants (lane (j,h) reads the 8 consecutive dims 16c+8h.. of vector j as one ds_read_b128),
-// same bytes per block as the f32 form
-// (the column of vector v of a block in the image: image_column, slot_filter.hpp)
-
-__global__ void split_bf16_kernel(const float4 *blocks, uint32_t dq, uint64_t nblocks, uint4 *out, const float4 *mu = nullptr) {
-  const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;  // (block, chunk, half, vector)
-  const uint32_t nc = dq / 4;
-  if (t >= nblocks * nc * 2 * 64) return;
-  const uint32_t v = (uint32_t)(t & 63), h = (uint32_t)((t >> 6) & 1);
-  const uint64_t bc = t >> 7;
-  const uint32_t c = (uint32_t)(bc % nc);
-  const uint64_t b = bc / nc;
-  const float4 *src = blocks + (b * dq + 4 * c + 2 * h) * 64 + v;
-  uint4 hi, lo;
-  float4 v0 = src[0], v1 = src[64];
-  if (mu) {  // the image of fl(v - mu)
-    const float4 m0 = mu[4 * c + 2 * h], m1 = mu[4 * c + 2 * h + 1];
-    v0.x -= m0.x; v0.y -= m0.y; v0.z -= m0.z; v0.w -= m0.w;
-    v1.x -= m1.x; v1.y -= m1.y; v1.z -= m1.z; v1.w -= m1.w;
-  }
-  split8(v0, v1, 1.0f, hi, lo);
-  uint4 *dst = out + ((b * nc + c) * 4) * 64;
-  const uint32_t col = image_column(v);
-  dst[(0 * 2 + h) * 64 + col] = hi;
-  dst[(1 * 2 + h) * 64 + col] = lo;
-}
-
-// the squared norms in image order (the accumulator of MFMA row i starts at the norm of the vector in column i)
-__global__ void image_norms_kernel(const float *xnorm, uint64_t nslots, float *out) {
-  const uint64_t s = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (s < nslots) out[(s & ~63ull) + image_column((uint32_t)(s & 63u))] = xnorm[s];
-}
-
-// bf16-exact stored values: the hi plane IS the value.  A second copy of it in the blocks' own vector order — piece
-// (chunk c, half h) of vector v at (block * 2 nc + 2c + h) * 64 + v — lets the select re-evaluate a 16-vector sub-block
-// from 256 contiguous bytes per 8 dimensions: half the cache lines of the f32 quads (the MFMA image's column order
-// interleaves the two sub-blocks of a tile within every line).
-__global__ void hi_natural_kernel(const uint4 *img, uint32_t nc, uint64_t nblocks, uint4 *out) {
-  const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;  // (block, chunk, half, vector)
-  if (t >= nblocks * nc * 2 * 64) return;
-  const uint32_t v = (uint32_t)(t & 63), h = (uint32_t)((t >> 6) & 1);
-  const uint64_t bc = t >> 7;
-  const uint32_t c = (uint32_t)(bc % nc);
-  const uint64_t b = bc / nc;
-  out[((b * nc + c) * 2 + h) * 64 + v] = img[(((b * nc + c) * 4) + h) * 64 + image_column(v)];
-}
-
-// The coarse table once more, row-major (centroid c = dim consecutive floats): the coarse select re-evaluates ONE
-// centroid per candidate sub-block, and a lone row of a lane-interleaved block is 16 bytes in each of dim / 4 cache
-// lines; from this copy it is dim / 32 whole lines.  (k' x dim floats; the lists stay lane-interleaved only.)
-__global__ void rows_from_blocks_kernel(const float4 *blocks, uint32_t dq, uint32_t nrows, uint32_t nquad, float4 *out) {
-  const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= (uint64_t)nrows * nquad) return;
-  const uint32_t row = (uint32_t)(t / nquad), qd = (uint32_t)(t % nquad);
-  out[t] = blocks[((size_t)(row / 64) * dq + qd) * 64 + (row % 64)];
-}
-
-// 8-bit descriptors (every stored value an integer in 0..255, as SIFT's): one byte per dimension, 16 dimensions of vector
-// v at (block * ceil(dq / 4) + p) * 64 + v — a 16-vector sub-block is re-evaluated from 256 contiguous bytes per 16
-// dimensions, half of the bf16 copy again.  `not_u8` is raised if some value does not fit.
-__global__ void u8_check_kernel(const float4 *blocks, uint64_t nquads, uint32_t *not_u8) {
-  const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  bool bad = false;
-  if (t < nquads) {
-    const float4 v = blocks[t];
-    auto ok = [](float x) { return x >= 0.0f && x <= 255.0f && x == floorf(x); };
-    bad = !(ok(v.x) && ok(v.y) && ok(v.z) && ok(v.w));
-  }
-  if (__ballot(bad) != 0ull && (threadIdx.x & 63u) == 0u) atomicOr(not_u8, 1u);
-}
-__global__ void u8_natural_kernel(const float4 *blocks, uint32_t dq, uint64_t nblocks, uint4 *out) {
-  const uint32_t np = (dq + 3) / 4;  // pieces of 16 dimensions (dq is a multiple of 4)
-  const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;  // (block, piece, vector)
-  if (t >= nblocks * np * 64) return;
-  const uint32_t v = (uint32_t)(t & 63);
-  const uint64_t bp = t >> 6;
-  const uint32_t p = (uint32_t)(bp % np);
-  const uint64_t b = bp / np;
-  uint32_t w[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const float4 x = blocks[(b * dq + 4 * p + i) * 64 + v];
-    w[i] = (uint32_t)x.x | ((uint32_t)x.y << 8) | ((uint32_t)x.z << 16) | ((uint32_t)x.w << 24);
-  }
-  out[t] = make_uint4(w[0], w[1], w[2], w[3]);
-}
-
-// 8-bit descriptors ranked with int8 products (rank_stream_i8_kernel), in the frame shifted by 127: the A operand is
-// 127 - v (fits in int8 for v in 0..255), 0 on the dimensions past dim.  Same block and column order as the bf16 image
-// (image_column): per block nc32 chunks of 32 dimensions x [half of 16 dimensions] x 64 columns x 16 B.
-__global__ void i8_image_kernel(const float4 *blocks, uint32_t dq, uint32_t dim, uint32_t nc32, uint64_t nblocks, uint4 *out) {
-  const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;  // (block, chunk, half, vector)
-  if (t >= nblocks * nc32 * 2 * 64) return;
-  const uint32_t v = (uint32_t)(t & 63), h = (uint32_t)((t >> 6) & 1);
-  const uint64_t bc = t >> 7;
-  const uint32_t c = (uint32_t)(bc % nc32);
-  const uint64_t b = bc / nc32;
-  uint32_t w[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const uint32_t qd = 8u * c + 4u * h + (uint32_t)i;  // quad of dimensions 4 qd .. 4 qd + 3 (dim is a multiple of 4)
-    w[i] = 0u;
-    if (4u * qd < dim) {
-      const float4 x = blocks[(b * dq + qd) * 64 + v];
-      w[i] = ((127u - (uint32_t)x.x) & 0xFFu) | (((127u - (uint32_t)x.y) & 0xFFu) << 8) | (((127u - (uint32_t)x.z) & 0xFFu) << 16) |
-             ((127u - (uint32_t)x.w) << 24);
-    }
-  }
-  out[((b * nc32 + c) * 2 + h) * 64 + image_column(v)] = make_uint4(w[0], w[1], w[2], w[3]);
-}
-// ... and the accumulator's start h(v) = ceil(|v - 127|^2 / 2) in image-column order (pad slots, marked kBig in xnorm:
-// kI8PadNorm); *xmax2 = max |v - 127|^2
-__global__ void i8_norms_kernel(const float4 *blocks, uint32_t dq, uint32_t dim, uint64_t nslots, const float *xnorm, int *out,
-                                uint32_t *xmax2) {
-  const uint64_t s = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (s >= nslots) return;
-  const float4 *p = blocks + (s / kWave) * dq * kWave + (s % kWave);
-  int n = 0;
-  for (uint32_t qd = 0; 4u * qd < dim; ++qd) {
-    const float4 x = p[(size_t)qd * kWave];
-    const int a = (int)x.x - 127, b = (int)x.y - 127, c = (int)x.z - 127, d = (int)x.w - 127;
-    n += a * a + b * b + c * c + d * d;
-  }
-  const bool pad = !(xnorm[s] < kBig);
-  if (!pad) atomicMax(xmax2, (uint32_t)n);
-  out[(s & ~63ull) + image_column((uint32_t)(s & 63u))] = pad ? kI8PadNorm : (n + 1) >> 1;
-}
-
-// any nonzero lo half in an image? (pieces of 64 uint4: plane = (piece >> 1) & 1)
-__global__ void lo_plane_any_kernel(const uint4 *img, uint64_t npieces, uint32_t *any) {
-  const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= npieces * 64) return;
-  const uint64_t piece = t >> 6;
-  if (((piece >> 1) & 1) == 0) return;
-  const uint4 v = img[t];
-  if (((v.x | v.y | v.z | v.w) & 0x7FFF7FFFu) != 0u) atomicOr(any, 1u);
-}
 
 // ------------------------------------------------------------------------------------------
 // record bookkeeping: where the records of (query, probe) start
@@ -345,33 +80,6 @@ __global__ void pair_groups_kernel(const uint32_t *probes, const uint32_t *list_
     }
   }
   qtot[q] = run;
-}
-
-// qoff = exclusive scan of qtot over the queries (one workgroup), qoff[nq] = total
-__global__ void __launch_bounds__(1024) query_offsets_kernel(const uint32_t *qtot, uint32_t nq, uint32_t *qoff) {
-  __shared__ uint32_t s[16];
-  const uint32_t t = threadIdx.x;
-  const int lane = t & 63, wave = t >> 6;
-  const uint32_t per = (nq + 1023) / 1024;
-  const uint32_t beg = min(nq, t * per), end = min(nq, beg + per);
-  uint32_t sum = 0;
-  for (uint32_t i = beg; i < end; ++i) sum += qtot[i];
-  uint32_t inc = sum;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t x = (uint32_t)__shfl_up((int)inc, o);
-    if (lane >= o) inc += x;
-  }
-  if (lane == 63) s[wave] = inc;
-  __syncthreads();
-  uint32_t w = 0, tot = 0;
-  for (int i = 0; i < 16; ++i) {
-    if (i < wave) w += s[i];
-    tot += s[i];
-  }
-  uint32_t run = w + inc - sum;
-  for (uint32_t i = beg; i < end; ++i) { qoff[i] = run; run += qtot[i]; }
-  if (t == 0) qoff[nq] = tot;
 }
 
 // list of every work item: keeps a 12-step dependent binary search out of each rank workgroup's prologue
@@ -437,9 +145,9 @@ __global__ void item_cols_kernel(const uint4 *items, const uint32_t *pairs, cons
   const uint4 d0 = items[2 * (size_t)w], d1 = items[2 * (size_t)w + 1];
   if (threadIdx.x == 0) {
     sdesc[w] = make_uint4(d0.y, d0.z + d0.w, 2u * (d1.x - d0.w), d1.z);  // queries, first block, tiles, first record tile
-    if (w == 0) { stats[13] = 0; stats[14] = 0; }
+    if (w == 0) { stats[kStatQueryLo] = 0; stats[kStatQueryNotI8] = 0; }
   }
-  if (w == 0 && threadIdx.x < 8) stats[16 + 16 * threadIdx.x] = 0;  // the rank kernel's work counters (one per XCD queue, 128 bytes apart)
+  if (w == 0 && threadIdx.x < kStatRankWorkCount) stats[kStatRankWork + kStatRankWorkStride * threadIdx.x] = 0;  // the rank kernel's work counters (one per XCD queue, 128 bytes apart)
   for (uint32_t col = threadIdx.x; col < gq; col += blockDim.x) {
     uint32_t q = ~0u, g = ~0u;
     if (col < d0.y) {
@@ -1319,7 +1027,6 @@ __device__ __forceinline__ uint32_t subblock_vector(uint32_t e, uint32_t t, uint
   return image_order ? 32u * t + 16u * hh + e : 32u * t + (e & 3u) + 8u * (e >> 2) + 4u * hh;
 }
 
-constexpr uint32_t kNarrowDim = 128;     // up to here the queries of a work item stay in registers (filter_kernel)
 constexpr uint32_t kPickCap = 256;     // sub-blocks waiting for their 16 exact distances (per wave)
 constexpr uint32_t kSubBits = 21;      // request key = (probe rank << 22) | (sub-block of the list << 1) | lane half
 constexpr uint32_t kCacheG = 256;      // group records (values + probe/segment/half) kept in LDS per wave
@@ -1481,7 +1188,7 @@ __device__ __forceinline__ void select_body(const SelectCommon &c, uint32_t q, s
     }
   };
 
-  // (diagnostic, VI_FILTER_STATS: s_memtime ticks per stage, summed over the queries into dbg[150..155])
+  // (diagnostic, VI_FILTER_STATS: s_memtime ticks per stage, summed over the queries into the stage clocks of ws.stats, kStatClocks)
   unsigned long long tk = c.dbg ? __builtin_amdgcn_s_memtime() : 0ull, tks[6] = {0, 0, 0, 0, 0, 0};
   auto lap = [&](int i) {
     if (c.dbg) {
@@ -1645,12 +1352,12 @@ __device__ __forceinline__ void select_body(const SelectCommon &c, uint32_t q, s
   lap(4);
   if (c.dbg && lane == 0 && (q & c.dbg_mask) == 0u) {
 #pragma unroll
-    for (int i = 0; i < 5; ++i) atomicAdd(&c.dbg[150 + i], tks[i]);
-    atomicAdd(&c.dbg[6], (unsigned long long)n_exact);
-    atomicAdd(&c.dbg[7], (unsigned long long)n_scanned);
-    atomicAdd(&c.dbg[8], (unsigned long long)(any_full ? 1u : 0u));
-    atomicAdd(&c.dbg[9], (unsigned long long)n_full);
-    atomicAdd(&c.dbg[10], (unsigned long long)n_sub);
+    for (int i = 0; i < 5; ++i) atomicAdd(&c.dbg[kStatClocks + i], tks[i]);
+    atomicAdd(&c.dbg[kStatSelExact], (unsigned long long)n_exact);
+    atomicAdd(&c.dbg[kStatSelScanned], (unsigned long long)n_scanned);
+    atomicAdd(&c.dbg[kStatSelQueriesFull], (unsigned long long)(any_full ? 1u : 0u));
+    atomicAdd(&c.dbg[kStatSelFullGroups], (unsigned long long)n_full);
+    atomicAdd(&c.dbg[kStatSelSubBlocks], (unsigned long long)n_sub);
   }
 }
 
@@ -1770,7 +1477,7 @@ __global__ void __launch_bounds__(256, 4) coarse_select_kernel(CoarseSelectArgs 
       if (a.pair_rank) a.pair_rank[(size_t)q * a.P + lane] = before;
     }
   }
-  // group records of the list phase: 2 per (probe, segment); query_offsets_kernel turns the per-query totals
+  // group records of the list phase: 2 per (probe, segment); group_prepare_kernel turns the per-query totals
   // into offsets
   uint32_t ng = 0;
   if (mylist != kNoPos) {
@@ -1805,7 +1512,7 @@ __global__ void __launch_bounds__(256) coarse_select_direct_kernel(CoarseSelectA
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
   };
-  // (diagnostic, VI_FILTER_STATS=2: s_memtime ticks per stage, summed over the queries into dbg[150..155])
+  // (diagnostic, VI_FILTER_STATS=2: s_memtime ticks per stage, summed over the queries into the stage clocks of ws.stats, kStatClocks)
   unsigned long long tk = c.dbg ? __builtin_amdgcn_s_memtime() : 0ull, tks[6] = {0, 0, 0, 0, 0, 0};
   auto lap = [&](int i) {
     if (c.dbg) {
@@ -2016,9 +1723,9 @@ __global__ void __launch_bounds__(256) coarse_select_direct_kernel(CoarseSelectA
   if (lane == 63) a.qtot[q] = ig;
   lap(4);
   if (c.dbg && lane == 0 && (q & 63u) == 0u) {  // (every 64th query: 70 000 same-address atomics would be most of the kernel)
-    for (int i = 0; i < 5; ++i) atomicAdd(&c.dbg[150 + i], tks[i]);
-    atomicAdd(c.dbg + 6, (unsigned long long)n_single);
-    atomicAdd(c.dbg + 7, (unsigned long long)n_whole);
+    for (int i = 0; i < 5; ++i) atomicAdd(&c.dbg[kStatClocks + i], tks[i]);
+    atomicAdd(c.dbg + kStatSelExact, (unsigned long long)n_single);
+    atomicAdd(c.dbg + kStatSelScanned, (unsigned long long)n_whole);
   }
 }
 
@@ -2128,242 +1835,6 @@ SelectCommon select_common(const DeviceIndex &ix, const EngineKnobs &kn, const f
 
 }  // namespace
 
-// norms of the stored vectors (MFMA accumulator init) — called once after the blocks are built
-vi_status compute_slot_norms(DeviceIndex *ix) {
-  const uint64_t nslots = ix->lists.nblocks * kWave;
-  VI_TRY(ix->xnorm.reserve(std::max<uint64_t>(1, nslots)));
-  DevBuf<uint32_t> mx;
-  VI_TRY(mx.reserve(1));
-  VI_HIP(hipMemsetAsync(mx.p, 0, 4, ix->stream));
-  if (nslots) {
-    hipLaunchKernelGGL(slot_norms_kernel, dim3((uint32_t)((nslots + 255) / 256)), dim3(256), 0, ix->stream,
-                       (const float4 *)ix->lists.blocks.p, ix->dq, nslots, ix->xnorm.p, mx.p);
-    if (ix->nlists)
-      hipLaunchKernelGGL(pad_norms_kernel, dim3((uint32_t)((ix->nlists * 64 + 255) / 256)), dim3(256), 0, ix->stream,
-                         ix->list_first_block.p, ix->list_len.p, (uint32_t)ix->nlists, ix->xnorm.p);
-    VI_HIP(hipGetLastError());
-  }
-  uint32_t bits = 0;
-  VI_HIP(hipMemcpyAsync(&bits, mx.p, 4, hipMemcpyDeviceToHost, ix->stream));
-  VI_HIP(hipStreamSynchronize(ix->stream));
-  float f;
-  std::memcpy(&f, &bits, 4);
-  ix->xmax2 = f;
-  // the coarse table: pad slots (>= nlists) must never rank
-  const uint64_t cslots = ix->centroids.nblocks * kWave;
-  VI_TRY(ix->cent_xnorm.reserve(std::max<uint64_t>(1, cslots)));
-  VI_HIP(hipMemsetAsync(mx.p, 0, 4, ix->stream));
-  if (cslots) {
-    hipLaunchKernelGGL(slot_norms_kernel, dim3((uint32_t)((cslots + 255) / 256)), dim3(256), 0, ix->stream,
-                       (const float4 *)ix->centroids.blocks.p, ix->dq, cslots, ix->cent_xnorm.p, mx.p);
-    VI_HIP(hipGetLastError());
-    const uint64_t npad = cslots - ix->nlists;
-    if (npad) {
-      std::vector<float> inf(npad, kBig);
-      VI_HIP(hipMemcpyAsync(ix->cent_xnorm.p + ix->nlists, inf.data(), npad * 4, hipMemcpyHostToDevice, ix->stream));
-    }
-  }
-  VI_HIP(hipMemcpyAsync(&bits, mx.p, 4, hipMemcpyDeviceToHost, ix->stream));
-  VI_HIP(hipStreamSynchronize(ix->stream));
-  std::memcpy(&f, &bits, 4);
-  ix->cent_xmax2 = f;
-  VI_TRY(ix->xnorm_img.reserve(std::max<uint64_t>(1, nslots)));
-  VI_TRY(ix->cent_xnorm_img.reserve(std::max<uint64_t>(1, cslots)));
-  if (nslots)
-    hipLaunchKernelGGL(image_norms_kernel, dim3((uint32_t)((nslots + 255) / 256)), dim3(256), 0, ix->stream, ix->xnorm.p,
-                       nslots, ix->xnorm_img.p);
-  if (cslots)
-    hipLaunchKernelGGL(image_norms_kernel, dim3((uint32_t)((cslots + 255) / 256)), dim3(256), 0, ix->stream,
-                       ix->cent_xnorm.p, cslots, ix->cent_xnorm_img.p);
-  VI_HIP(hipGetLastError());
-  // bf16 hi/lo images of the lists and of the centroid table (same size as the f32 blocks)
-  if ((ix->dim & 3) == 0 && ix->dim <= kMaxFilterDim) {
-    const uint64_t per_block = (uint64_t)ix->dq * kWave * 4;  // uint32 words per block
-    VI_TRY(ix->lists_bf16.reserve(std::max<uint64_t>(1, ix->lists.nblocks * per_block)));
-    VI_TRY(ix->cent_bf16.reserve(std::max<uint64_t>(1, ix->centroids.nblocks * per_block)));
-    const uint64_t nt_l = ix->lists.nblocks * (ix->dq / 4) * 128, nt_c = ix->centroids.nblocks * (ix->dq / 4) * 128;
-    if (nt_l)
-      hipLaunchKernelGGL(split_bf16_kernel, dim3((uint32_t)((nt_l + 255) / 256)), dim3(256), 0, ix->stream,
-                         (const float4 *)ix->lists.blocks.p, ix->dq, ix->lists.nblocks, (uint4 *)ix->lists_bf16.p);
-    if (nt_c)
-      hipLaunchKernelGGL(split_bf16_kernel, dim3((uint32_t)((nt_c + 255) / 256)), dim3(256), 0, ix->stream,
-                         (const float4 *)ix->centroids.blocks.p, ix->dq, ix->centroids.nblocks, (uint4 *)ix->cent_bf16.p);
-    VI_HIP(hipGetLastError());
-    // bf16-exact stored values (8-bit descriptors): the lo planes are all zero and need not be streamed
-    uint32_t h_any[2] = {0u, 0u};
-    VI_HIP(hipMemsetAsync(mx.p, 0, 4, ix->stream));
-    const uint64_t np_l = ix->lists.nblocks * ix->dq, np_c = ix->centroids.nblocks * ix->dq;
-    if (np_l)
-      hipLaunchKernelGGL(lo_plane_any_kernel, dim3((uint32_t)((np_l * 64 + 255) / 256)), dim3(256), 0, ix->stream,
-                         (const uint4 *)ix->lists_bf16.p, np_l, mx.p);
-    VI_HIP(hipMemcpyAsync(&h_any[0], mx.p, 4, hipMemcpyDeviceToHost, ix->stream));
-    VI_HIP(hipStreamSynchronize(ix->stream));
-    VI_HIP(hipMemsetAsync(mx.p, 0, 4, ix->stream));
-    if (np_c)
-      hipLaunchKernelGGL(lo_plane_any_kernel, dim3((uint32_t)((np_c * 64 + 255) / 256)), dim3(256), 0, ix->stream,
-                         (const uint4 *)ix->cent_bf16.p, np_c, mx.p);
-    VI_HIP(hipMemcpyAsync(&h_any[1], mx.p, 4, hipMemcpyDeviceToHost, ix->stream));
-    VI_HIP(hipStreamSynchronize(ix->stream));
-    ix->lists_lo_zero = np_l > 0 && h_any[0] == 0;
-    ix->cent_lo_zero = np_c > 0 && h_any[1] == 0;
-    ix->centered = false;
-    const char *ce = getenv("VI_CENTER");
-    if (!ix->lists_lo_zero && ix->dim <= kNarrowDim && ix->nlists && ix->nvec_resident && !(ce && *ce == '0')) {
-      // real-valued lists: images about the mean of the stored vectors when that at least halves the norms the margins
-      // scale with (VI_CENTER=1: always, =0: never)
-      DevBuf<double> sums;
-      DevBuf<float> cn, ccn;
-      DevBuf<double> nsum;
-      VI_TRY(sums.reserve((uint64_t)ix->dq * 4));
-      VI_TRY(ix->centre.reserve((uint64_t)ix->dq * 4));
-      VI_TRY(cn.reserve(nslots));
-      VI_TRY(ccn.reserve(cslots));
-      VI_HIP(hipMemsetAsync(sums.p, 0, (uint64_t)ix->dq * 4 * sizeof(double), ix->stream));
-      hipLaunchKernelGGL(mean_kernel, dim3(ix->dq, 64), dim3(256), 0, ix->stream, (const float4 *)ix->lists.blocks.p, ix->dq,
-                         ix->lists.nblocks, sums.p);
-      hipLaunchKernelGGL(mean_finish_kernel, dim3((ix->dq * 4 + 255) / 256), dim3(256), 0, ix->stream, sums.p, ix->dim, ix->dq * 4,
-                         (double)ix->nvec_resident, ix->centre.p);
-      uint32_t mxb[2] = {0u, 0u};
-      DevBuf<uint32_t> mx2;
-      VI_TRY(mx2.reserve(2));
-      VI_HIP(hipMemsetAsync(mx2.p, 0, 8, ix->stream));
-      hipLaunchKernelGGL(slot_norms_kernel, dim3((uint32_t)((nslots + 255) / 256)), dim3(256), 0, ix->stream,
-                         (const float4 *)ix->lists.blocks.p, ix->dq, nslots, cn.p, mx2.p, (const float4 *)ix->centre.p);
-      hipLaunchKernelGGL(slot_norms_kernel, dim3((uint32_t)((cslots + 255) / 256)), dim3(256), 0, ix->stream,
-                         (const float4 *)ix->centroids.blocks.p, ix->dq, (uint64_t)ix->nlists, ccn.p, mx2.p + 1, (const float4 *)ix->centre.p);
-      hipLaunchKernelGGL(pad_norms_kernel, dim3((uint32_t)((ix->nlists * 64 + 255) / 256)), dim3(256), 0, ix->stream,
-                         ix->list_first_block.p, ix->list_len.p, (uint32_t)ix->nlists, cn.p);
-      VI_HIP(hipMemsetAsync(mx2.p, 0, 8, ix->stream));  // (the pad slots' zero vectors entered the kernel's own maximum)
-      hipLaunchKernelGGL(max_finite_kernel, dim3(256), dim3(256), 0, ix->stream, cn.p, nslots, mx2.p);
-      hipLaunchKernelGGL(max_finite_kernel, dim3(64), dim3(256), 0, ix->stream, ccn.p, (uint64_t)ix->nlists, mx2.p + 1);
-      VI_HIP(hipGetLastError());
-      VI_HIP(hipMemcpyAsync(mxb, mx2.p, 8, hipMemcpyDeviceToHost, ix->stream));
-      std::vector<double> hs((size_t)ix->dq * 4);
-      VI_HIP(hipMemcpyAsync(hs.data(), sums.p, hs.size() * sizeof(double), hipMemcpyDeviceToHost, ix->stream));
-      VI_HIP(hipStreamSynchronize(ix->stream));
-      float xc, cc;
-      std::memcpy(&xc, &mxb[0], 4);
-      std::memcpy(&cc, &mxb[1], 4);
-      double mu2 = 0.0;  // |mu|^2; the mean of |v - mu|^2 is the mean of |v|^2 less this
-      for (uint32_t e = 0; e < ix->dim; ++e) { const double m = hs[e] / (double)ix->nvec_resident; mu2 += m * m; }
-      double mean_raw = 0.0;
-      {  // the mean squared norm of ALL stored vectors (list_spread_kernel below only samples)
-        DevBuf<double> acc;
-        VI_TRY(acc.reserve(1));
-        VI_HIP(hipMemsetAsync(acc.p, 0, sizeof(double), ix->stream));
-        hipLaunchKernelGGL(sum_f32_kernel, dim3(256), dim3(256), 0, ix->stream, ix->xnorm.p, nslots, acc.p);
-        VI_HIP(hipGetLastError());
-        VI_HIP(hipMemcpyAsync(&mean_raw, acc.p, sizeof(double), hipMemcpyDeviceToHost, ix->stream));
-        VI_HIP(hipStreamSynchronize(ix->stream));
-        mean_raw /= (double)ix->nvec_resident;
-      }
-      const double mean_c = std::max(0.0, mean_raw - mu2);
-      const bool gain = mean_c + 2.0 * (double)xc < 0.5 * (mean_raw + 2.0 * (double)ix->xmax2);
-      if ((ce && *ce == '1') || gain) {
-        ix->centered = true;
-        ix->mean_norm2_c = (float)mean_c;
-        ix->xmax2_c = xc;
-        ix->cent_xmax2_c = cc;
-        const uint64_t npad = cslots - ix->nlists;
-        if (npad) {
-          std::vector<float> inf(npad, kBig);
-          VI_HIP(hipMemcpyAsync(ccn.p + ix->nlists, inf.data(), npad * 4, hipMemcpyHostToDevice, ix->stream));
-          VI_HIP(hipStreamSynchronize(ix->stream));  // (inf lives on this frame)
-        }
-        hipLaunchKernelGGL(image_norms_kernel, dim3((uint32_t)((nslots + 255) / 256)), dim3(256), 0, ix->stream, cn.p, nslots,
-                           ix->xnorm_img.p);
-        hipLaunchKernelGGL(image_norms_kernel, dim3((uint32_t)((cslots + 255) / 256)), dim3(256), 0, ix->stream, ccn.p, cslots,
-                           ix->cent_xnorm_img.p);
-        hipLaunchKernelGGL(split_bf16_kernel, dim3((uint32_t)((nt_l + 255) / 256)), dim3(256), 0, ix->stream,
-                           (const float4 *)ix->lists.blocks.p, ix->dq, ix->lists.nblocks, (uint4 *)ix->lists_bf16.p, (const float4 *)ix->centre.p);
-        hipLaunchKernelGGL(split_bf16_kernel, dim3((uint32_t)((nt_c + 255) / 256)), dim3(256), 0, ix->stream,
-                           (const float4 *)ix->centroids.blocks.p, ix->dq, ix->centroids.nblocks, (uint4 *)ix->cent_bf16.p, (const float4 *)ix->centre.p);
-        VI_HIP(hipGetLastError());
-        VI_HIP(hipStreamSynchronize(ix->stream));
-        ix->cent_lo_zero = false;
-      }
-    }
-    ix->rho2_max = 0.0f;
-    if (!ix->lists_lo_zero && ix->dim <= kNarrowDim && nslots) {  // real-valued lists: what their hi planes leave out (rank_approx_mode)
-      VI_HIP(hipMemsetAsync(mx.p, 0, 4, ix->stream));
-      hipLaunchKernelGGL(trunc_residual_kernel, dim3((uint32_t)((nslots + 255) / 256)), dim3(256), 0, ix->stream,
-                         (const float4 *)ix->lists.blocks.p, ix->dq, nslots, ix->xnorm.p, ix->centered ? (const float4 *)ix->centre.p : nullptr, mx.p);
-      VI_HIP(hipGetLastError());
-      VI_HIP(hipMemcpyAsync(&bits, mx.p, 4, hipMemcpyDeviceToHost, ix->stream));
-      VI_HIP(hipStreamSynchronize(ix->stream));
-      std::memcpy(&ix->rho2_max, &bits, 4);
-    }
-    if (ix->nlists && ix->dim <= kNarrowDim) {  // single-row exact re-evaluation of the coarse select
-      const uint32_t nquad = ix->dim / 4;
-      VI_TRY(ix->cent_rows.reserve((uint64_t)ix->nlists * ix->dim));
-      const uint64_t nt = (uint64_t)ix->nlists * nquad;
-      hipLaunchKernelGGL(rows_from_blocks_kernel, dim3((uint32_t)((nt + 255) / 256)), dim3(256), 0, ix->stream,
-                         (const float4 *)ix->centroids.blocks.p, ix->dq, (uint32_t)ix->nlists, nquad, (float4 *)ix->cent_rows.p);
-      VI_HIP(hipGetLastError());
-    }
-    if (ix->nlists && ix->dim <= kNarrowDim && ix->lists.nblocks && !ix->lists_lo_zero) {
-      // real-valued lists: how far the vectors sit from their centroids, against how large they are (rank_approx_mode)
-      DevBuf<double> sums;
-      VI_TRY(sums.reserve(3));
-      VI_HIP(hipMemsetAsync(sums.p, 0, 3 * sizeof(double), ix->stream));
-      hipLaunchKernelGGL(list_spread_kernel, dim3((uint32_t)ix->nlists), dim3(64), 0, ix->stream, (const float4 *)ix->lists.blocks.p, ix->dq,
-                         (const float4 *)ix->cent_rows.p, ix->dim, ix->list_first_block.p, ix->list_len.p, (uint32_t)ix->nlists, 8u, sums.p);
-      VI_HIP(hipGetLastError());
-      double h[3] = {0, 0, 0};
-      VI_HIP(hipMemcpyAsync(h, sums.p, sizeof(h), hipMemcpyDeviceToHost, ix->stream));
-      VI_HIP(hipStreamSynchronize(ix->stream));
-      if (h[2] > 0) { ix->mean_spread = (float)(h[0] / h[2]); ix->mean_norm2 = (float)(h[1] / h[2]); }
-    }
-    if (ix->lists_lo_zero && ix->dim <= kNarrowDim && ix->lists.nblocks) {  // 8-bit descriptors?  (bf16-exact is necessary)
-      VI_HIP(hipMemsetAsync(mx.p, 0, 4, ix->stream));
-      const uint64_t nquads = ix->lists.nblocks * ix->dq * 64;
-      hipLaunchKernelGGL(u8_check_kernel, dim3((uint32_t)((nquads + 255) / 256)), dim3(256), 0, ix->stream,
-                         (const float4 *)ix->lists.blocks.p, nquads, mx.p);
-      uint32_t not_u8 = 1;
-      VI_HIP(hipMemcpyAsync(&not_u8, mx.p, 4, hipMemcpyDeviceToHost, ix->stream));
-      VI_HIP(hipStreamSynchronize(ix->stream));
-      if (!not_u8) {
-        const uint64_t nt8 = ix->lists.nblocks * (ix->dq / 4) * 64;
-        VI_TRY(ix->lists_u8_nat.reserve(nt8 * 4));
-        hipLaunchKernelGGL(u8_natural_kernel, dim3((uint32_t)((nt8 + 255) / 256)), dim3(256), 0, ix->stream,
-                           (const float4 *)ix->lists.blocks.p, ix->dq, ix->lists.nblocks, (uint4 *)ix->lists_u8_nat.p);
-        VI_HIP(hipGetLastError());
-        // the int8 image and norms of the streaming rank kernel's int8 form (rank_stream_i8_kernel), and the frame's centre
-        // (127 on every dimension) for the select's margins
-        const uint32_t nc32 = (ix->dim + 31) / 32;
-        const uint64_t nti = ix->lists.nblocks * nc32 * 128;
-        VI_TRY(ix->lists_i8.reserve(nti * 4));
-        VI_TRY(ix->i8_norm_img.reserve(nslots));
-        VI_TRY(ix->i8_centre.reserve(ix->dim));
-        VI_HIP(hipMemsetAsync(mx.p, 0, 4, ix->stream));
-        hipLaunchKernelGGL(i8_image_kernel, dim3((uint32_t)((nti + 255) / 256)), dim3(256), 0, ix->stream,
-                           (const float4 *)ix->lists.blocks.p, ix->dq, ix->dim, nc32, ix->lists.nblocks, (uint4 *)ix->lists_i8.p);
-        hipLaunchKernelGGL(i8_norms_kernel, dim3((uint32_t)((nslots + 255) / 256)), dim3(256), 0, ix->stream,
-                           (const float4 *)ix->lists.blocks.p, ix->dq, ix->dim, nslots, ix->xnorm.p, ix->i8_norm_img.p, mx.p);
-        VI_HIP(hipGetLastError());
-        const std::vector<float> c127(ix->dim, 127.0f);
-        VI_HIP(hipMemcpyAsync(ix->i8_centre.p, c127.data(), ix->dim * sizeof(float), hipMemcpyHostToDevice, ix->stream));
-        uint32_t n2 = 0;
-        VI_HIP(hipMemcpyAsync(&n2, mx.p, 4, hipMemcpyDeviceToHost, ix->stream));
-        VI_HIP(hipStreamSynchronize(ix->stream));  // (c127 and n2 live on this frame)
-        ix->i8_xmax2 = (float)n2;
-      }
-    }
-    if (ix->lists_lo_zero && ix->dim <= kNarrowDim && !ix->lists_u8_nat.p) {  // exact re-evaluation from bf16 (select_kernel)
-      VI_TRY(ix->lists_hi_nat.reserve(ix->lists.nblocks * per_block / 2));
-      hipLaunchKernelGGL(hi_natural_kernel, dim3((uint32_t)((nt_l + 255) / 256)), dim3(256), 0, ix->stream,
-                         (const uint4 *)ix->lists_bf16.p, ix->dq / 4, ix->lists.nblocks, (uint4 *)ix->lists_hi_nat.p);
-      VI_HIP(hipGetLastError());
-    }
-  }
-  const uint32_t one_first[1] = {0u}, one_len[1] = {(uint32_t)ix->nlists};
-  VI_TRY(ix->c_first.reserve(1));
-  VI_TRY(ix->c_len.reserve(1));
-  VI_HIP(hipMemcpy(ix->c_first.p, one_first, 4, hipMemcpyHostToDevice));
-  VI_HIP(hipMemcpy(ix->c_len.p, one_len, 4, hipMemcpyHostToDevice));
-  return VI_OK;
-}
-
 // coarse quantizer on the matrix cores: the centroid table is one "list" probed by every query.
 // Leaves probes / gorder and the per-list histogram (ws.cnt) behind, like stage_coarse.
 vi_status stage_coarse_filter(const DeviceIndex &ix, const EngineKnobs &kn, const float *Qd, uint64_t nq, uint32_t P, hipStream_t st,
@@ -2388,9 +1859,9 @@ vi_status stage_coarse_filter(const DeviceIndex &ix, const EngineKnobs &kn, cons
   VI_TRY(ws.gval.reserve(nq * recs * 4));
   VI_TRY(ws.gpos.reserve(nq * recs));
   const bool direct = ix.centroids.nblocks <= kDirectBlocks && kn.coarse_direct;
-  if (direct && !ix.cent_rows.p) return fail(VI_ERR_OTHER, "coarse table without its row-major copy");  // (compute_slot_norms: D <= 128)
+  if (direct && !ix.cent_rows.p) return fail(VI_ERR_OTHER, "coarse table without its row-major copy");  // (prepare_rank_images: D <= 128)
   VI_TRY(ws.brec.reserve((uint64_t)ngroups * (direct ? 2 * ix.centroids.nblocks : (uint64_t)nseg * seg_records(segb)) * 256 * 4));
-  VI_TRY(ws.stats.reserve(160));
+  VI_TRY(ws.stats.reserve(kStatWords));
   if (ws.c_nq != nq) {  // the table's one-list grouping depends on the batch size only
     VI_HIP(hipMemcpyAsync(ws.c_seg.p, h_seg, 8, hipMemcpyHostToDevice, st));
     VI_HIP(hipMemcpyAsync(ws.c_item.p, h_item, 8, hipMemcpyHostToDevice, st));
@@ -2457,16 +1928,16 @@ static vi_status build_query_image(const DeviceIndex &ix, const EngineKnobs &kn,
   VI_TRY(ws.qimg.reserve((uint64_t)nq * nc * 4 * 4));  // uint32 words: 4 pieces of 16 B per (query, chunk)
   const bool i8 = ix.lists_i8.p != nullptr;  // the lists have an int8 image: the batch's too (rank_stream_i8_kernel)
   if (i8) VI_TRY(ws.qimg8.reserve(std::max<uint64_t>(1, (uint64_t)nq * ((ix.dim + 31) / 32) * 8)));  // uint32 words: 32 B per (query, chunk of 32)
-  if (!ws.stats_zeroed) {  // [13]: some query has a lo plane, [14]: some query is no int8 image (both read back with the
-    VI_TRY(ws.stats.reserve(160));  // grouping's counts) — reset by item_cols_kernel after their use
-    VI_HIP(hipMemsetAsync(ws.stats.p, 0, 160 * sizeof(uint64_t), st));
+  if (!ws.stats_zeroed) {  // kStatQueryLo, kStatQueryNotI8 start at zero (both are read back with the
+    VI_TRY(ws.stats.reserve(kStatWords));  // grouping's counts) — reset by item_cols_kernel after their use
+    VI_HIP(hipMemsetAsync(ws.stats.p, 0, kStatWords * sizeof(uint64_t), st));
     ws.stats_zeroed = true;
   }
   const uint64_t nt = (uint64_t)nq * nc * 2;
   hipLaunchKernelGGL(split_queries_kernel, dim3((uint32_t)((nt + 255) / 256)), dim3(256), 0, st, Qd, (uint32_t)nq, ix.dim, nc,
-                     (uint4 *)ws.qimg.p, (unsigned long long *)(ws.stats.p + 13), zero, (uint32_t)zero_words,
+                     (uint4 *)ws.qimg.p, (unsigned long long *)(ws.stats.p + kStatQueryLo), zero, (uint32_t)zero_words,
                      ix.centered ? (const float *)ix.centre.p : nullptr, i8 ? (uint2 *)ws.qimg8.p : nullptr,
-                     (unsigned long long *)(ws.stats.p + 14));
+                     (unsigned long long *)(ws.stats.p + kStatQueryNotI8));
   VI_HIP(hipGetLastError());
   return VI_OK;
 }
@@ -2498,10 +1969,10 @@ vi_status search_filter_pipeline(const DeviceIndex &ix, const EngineKnobs &kn, c
   VI_TRY(ws.pair_rel.reserve(nq * P));
   VI_TRY(ws.qtot.reserve(nq));
   VI_TRY(ws.qoff.reserve(nq + 1));
-  VI_TRY(ws.stats.reserve(160));
+  VI_TRY(ws.stats.reserve(kStatWords));
   if (kn.stats) {
-    VI_HIP(hipMemsetAsync(ws.stats.p + 6, 0, 6 * sizeof(uint64_t), st));
-    VI_HIP(hipMemsetAsync(ws.stats.p + 150, 0, 8 * sizeof(uint64_t), st));
+    VI_HIP(hipMemsetAsync(ws.stats.p + kStatSelExact, 0, (kStatSelectEnd - kStatSelExact) * sizeof(uint64_t), st));
+    VI_HIP(hipMemsetAsync(ws.stats.p + kStatClocks, 0, kStatClockCount * sizeof(uint64_t), st));
   }
   ws.pair_rank_valid = false;  // (set by the direct coarse select of THIS search)
   if (timing) VI_HIP(hipEventRecord(ix.cur().ev[0], st));
@@ -2525,12 +1996,11 @@ vi_status search_filter_pipeline(const DeviceIndex &ix, const EngineKnobs &kn, c
                          ix.list_len.p, (uint32_t)nq, P, segb0, ws.pair_rel.p, ws.qtot.p);
     }
     // (the grouping's scan kernel scans the record offsets too, as a second workgroup)
-    if (!grouping_fuses_query_offsets(ix)) hipLaunchKernelGGL(query_offsets_kernel, dim3(1), dim3(1024), 0, st, ws.qtot.p, (uint32_t)nq, ws.qoff.p);
     VI_HIP(hipGetLastError());
   }
   if (timing) VI_HIP(hipEventRecord(ix.cur().ev[1], st));
   // ---- 2. group all (query, probe) pairs by list ----
-  uint64_t hstats[15];
+  GroupingCounts hstats;
   // queries per rank work item: 128 when lists are shared by many queries of the batch, 32 when a list is probed by a
   // handful (large balanced indexes): a 128-query group would keep three of its four waves idle
   // The choice needs the batch's histogram, which only the grouping produces: the first batch of a shape (nq, P) goes by
@@ -2555,14 +2025,13 @@ vi_status search_filter_pipeline(const DeviceIndex &ix, const EngineKnobs &kn, c
   const bool stream = ix.dim <= kNarrowDim && kn.rank_bf16 && hi_lists && !kn.stream_off &&
                       (dq / 4 >= 7 || kn.stream_force || (approx != 0 && dq / 4 >= 5));
   if (stream) gq = kn.stream_gq256 && ws.queries_hi_only ? 256u : 128u;
-  // 8-bit descriptors against a batch of integers in 0..254 (hstats[14] == 0, known after the grouping): the streaming
+  // 8-bit descriptors against a batch of integers in 0..254 (no kStatQueryNotI8 flag, known after the grouping): the streaming
   // kernel's int8 form (rank_stream_i8_kernel), exact ranks in the frame shifted by 127.  VI_RANK_I8=0: bf16.
   const bool i8_lists = stream && ix.lists_i8.p && kn.rank_i8;
-  const bool fuse_q = grouping_fuses_query_offsets(ix);
-  VI_TRY(launch_grouping(ix, ws.probes.p, nq, P, (int)gq, segb0, hstats, st, true, fuse_q ? ws.qtot.p : nullptr, fuse_q ? ws.qoff.p : nullptr,
+  VI_TRY(launch_grouping(ix, ws.probes.p, nq, P, (int)gq, segb0, hstats, st, true, ws.qtot.p, ws.qoff.p,
                          ws.pair_rank_valid ? ws.pair_rank.p : nullptr));
   {
-    const double fill128 = hstats[12] ? (double)hstats[0] / ((double)hstats[12] * 128.0 * 64.0) : 0.0;
+    const double fill128 = hstats[kStatTiles128] ? (double)hstats[kStatScannedVectors] / ((double)hstats[kStatTiles128] * 128.0 * 64.0) : 0.0;
     const uint32_t next = fill128 >= 0.3 ? 128u : 32u;
     bool seen = false;
     for (auto &h : ws.gq_hint)
@@ -2572,13 +2041,13 @@ vi_status search_filter_pipeline(const DeviceIndex &ix, const EngineKnobs &kn, c
       ws.gq_hint.push_back({nq, P, next});
     }
   }
-  ws.queries_hi_only = hstats[13] == 0;
-  const bool rank_i8 = i8_lists && hstats[14] == 0;
+  ws.queries_hi_only = hstats[kStatQueryLo] == 0;
+  const bool rank_i8 = i8_lists && hstats[kStatQueryNotI8] == 0;
   stt.rank_int8 = rank_i8 ? 1u : 0u;
-  stt.scanned_vectors = hstats[0];
-  stt.scan_items = hstats[1];
-  stt.filter_tile_blocks = hstats[3];
-  const uint64_t nrec = hstats[4], nbrec = hstats[5] * 2 * gq;  // pair records: 2 x gq per (query group, segment, 2 blocks)
+  stt.scanned_vectors = hstats[kStatScannedVectors];
+  stt.scan_items = hstats[kStatItems];
+  stt.filter_tile_blocks = hstats[kStatTileBlocks];
+  const uint64_t nrec = hstats[kStatGroupRecords], nbrec = hstats[kStatRecordTiles] * 2 * gq;  // pair records: 2 x gq per (query group, segment, 2 blocks)
   if (nrec >= (1ull << 31) || nbrec >= (1ull << 32)) return fail(VI_ERR_INVALID_INPUT, "batch too large: split nq");
   VI_TRY(ws.gval.reserve(std::max<uint64_t>(1, nrec) * 4));
   VI_TRY(ws.gpos.reserve(std::max<uint64_t>(1, nrec)));
@@ -2593,7 +2062,7 @@ vi_status search_filter_pipeline(const DeviceIndex &ix, const EngineKnobs &kn, c
   // ---- 3. rank on the matrix cores ----
   if (ix.dim > kNarrowDim) {
     const uint32_t nc = dq / 4;
-    const uint32_t nitems = (uint32_t)hstats[1];
+    const uint32_t nitems = (uint32_t)hstats[kStatItems];
     VI_TRY(ws.item_list.reserve(std::max<uint32_t>(1, nitems)));
     if (nitems) {
       hipLaunchKernelGGL(item_list_kernel, dim3((nitems + 255) / 256), dim3(256), 0, st, ws.item_start.p, (uint32_t)nlists, nitems,
@@ -2612,7 +2081,7 @@ vi_status search_filter_pipeline(const DeviceIndex &ix, const EngineKnobs &kn, c
     stt.rank_mode = 2;
     stt.group_queries = gq;
   } else {
-    const uint32_t nitems = (uint32_t)hstats[1];
+    const uint32_t nitems = (uint32_t)hstats[kStatItems];
     VI_TRY(ws.items.reserve(std::max<uint32_t>(1, nitems) * 8ull));
     if (nitems) {
       hipLaunchKernelGGL(item_desc_kernel, dim3((nitems + 255) / 256), dim3(256), 0, st, ws.item_start.p, ws.seg_start.p,
@@ -2636,14 +2105,14 @@ vi_status search_filter_pipeline(const DeviceIndex &ix, const EngineKnobs &kn, c
       }
       if (rank_i8) {
         RankStreamI8Args a{(const uint4 *)ix.lists_i8.p, l_i8_norm_img, (const uint4 *)ws.qimg8.p, (const uint4 *)ws.item_sdesc.p, nitems,
-                           ws.item_qcol.p, ws.item_grec.p, (uint32_t *)(ws.stats.p + 16), (float4 *)ws.gval.p, (float4 *)ws.brec.p};
+                           ws.item_qcol.p, ws.item_grec.p, (uint32_t *)(ws.stats.p + kStatRankWork), (float4 *)ws.gval.p, (float4 *)ws.brec.p};
         VI_TRY(start_rank_clock());
         VI_TRY(launch_rank_stream_i8(a, (ix.dim + 31) / 32, nitems, gq, st));
       } else {
         RankStreamArgs a{(const uint4 *)ix.lists_bf16.p, l_xnorm_img, (const uint4 *)ws.qimg.p, (const uint4 *)ws.item_sdesc.p, nitems,
-                         ws.item_qcol.p, ws.item_grec.p, (uint32_t *)(ws.stats.p + 16), (float4 *)ws.gval.p,
+                         ws.item_qcol.p, ws.item_grec.p, (uint32_t *)(ws.stats.p + kStatRankWork), (float4 *)ws.gval.p,
                          (float4 *)ws.brec.p, nullptr, kn.filter_xmode};
-        const bool qlo = (hstats[13] != 0 || !kn.hi_only) && approx != 2;
+        const bool qlo = (hstats[kStatQueryLo] != 0 || !kn.hi_only) && approx != 2;
         const bool prof = kn.stream_prof;
         if (prof) {
           VI_TRY(ws.prof.reserve(32 + 4 * 1024));
@@ -2730,23 +2199,23 @@ vi_status search_filter_pipeline(const DeviceIndex &ix, const EngineKnobs &kn, c
   }
   if (timing) VI_HIP(hipEventRecord(ix.cur().ev[4], st));
   if (timing && kn.stats) {
-    uint64_t dbg[12], tks[8];
+    uint64_t dbg[kStatSelectEnd], tks[kStatClockCount];
     VI_HIP(hipMemcpyAsync(dbg, ws.stats.p, sizeof(dbg), hipMemcpyDeviceToHost, st));
-    VI_HIP(hipMemcpyAsync(tks, ws.stats.p + 150, sizeof(tks), hipMemcpyDeviceToHost, st));
+    VI_HIP(hipMemcpyAsync(tks, ws.stats.p + kStatClocks, sizeof(tks), hipMemcpyDeviceToHost, st));
     VI_HIP(hipStreamSynchronize(st));
     if (kn.stats_coarse)
       fprintf(stderr, "coarse select ticks (every 64th query): query row %llu, records + bound %llu, flags (+ rounds a full list forces) %llu, exact rounds %llu, tail %llu; rows %llu "
               "of which in whole sub-blocks %llu\n", (unsigned long long)tks[0], (unsigned long long)tks[1], (unsigned long long)tks[2],
-              (unsigned long long)tks[3], (unsigned long long)tks[4], (unsigned long long)dbg[6], 8ull * (unsigned long long)dbg[7]);
+              (unsigned long long)tks[3], (unsigned long long)tks[4], (unsigned long long)dbg[kStatSelExact], 8ull * (unsigned long long)dbg[kStatSelScanned]);
     if (kn.stats_print)
       fprintf(stderr, "select ticks: records -> LDS %llu, threshold %llu, refinement %llu, scan of pair records (+ exact rounds it triggers) %llu, "
               "last exact rounds %llu\n", (unsigned long long)tks[0], (unsigned long long)tks[1], (unsigned long long)tks[2],
               (unsigned long long)tks[3], (unsigned long long)tks[4]);
-    stt.filter_rechecked = dbg[6]; stt.filter_accepted = dbg[7];
+    stt.filter_rechecked = dbg[kStatSelExact]; stt.filter_accepted = dbg[kStatSelScanned];
     if (kn.stats_print)
       fprintf(stderr, "select stats: exact %llu groups_scanned %llu queries_with_full_group %llu full_groups %llu sub_blocks %llu\n",
-              (unsigned long long)dbg[6], (unsigned long long)dbg[7], (unsigned long long)dbg[8], (unsigned long long)dbg[9],
-              (unsigned long long)dbg[10]);
+              (unsigned long long)dbg[kStatSelExact], (unsigned long long)dbg[kStatSelScanned], (unsigned long long)dbg[kStatSelQueriesFull],
+              (unsigned long long)dbg[kStatSelFullGroups], (unsigned long long)dbg[kStatSelSubBlocks]);
   }
   return VI_OK;
 }

@@ -21,6 +21,7 @@
 
 #include "device_index.hpp"
 #include "scan.hpp"
+#include "search_internal.hpp"
 #include "slot_filter.hpp"
 
 namespace vi {
@@ -240,16 +241,6 @@ __global__ void count_keys_kernel(const uint64_t *keys, uint32_t logL, uint32_t 
 // device-wide sort of rows of 2^logL u64 keys (list_build.hip groups the point ids by list with it)
 vi_status sort_rows_u64(uint64_t *keys, uint64_t nrows, uint32_t logL, hipStream_t st) { return sort_rows(keys, nrows, logL, st); }
 
-// declared in search_kernels.hip
-vi_status launch_grouping(const DeviceIndex &ix, const uint32_t *probes, uint64_t nq, uint32_t P, int qg, uint32_t segb0,
-                          uint64_t hstats[15], hipStream_t st, bool histogram_done, const uint32_t *qtot = nullptr,
-                          uint32_t *qoff = nullptr, const uint32_t *pair_rank = nullptr);
-bool grouping_fuses_query_offsets(const DeviceIndex &ix);
-
-// declared in search_kernels.hip
-vi_status adopt_probes(const DeviceIndex &ix, uint64_t nq, uint32_t P, const uint32_t *probes_in, const uint32_t *order_in,
-                       bool histogram, hipStream_t st);
-
 namespace {
 
 // A. probes: dump all coarse distances, sort each row, take the first P -> ws.probes
@@ -372,9 +363,9 @@ vi_status device_index_search_generic(const DeviceIndex &ix, const float *Qd, ui
     VI_HIP(hipMemsetAsync(ws.sort_keys.p, 0xFF, m * L * sizeof(uint64_t), st));
     const double avg_q_per_list = (double)m * P / (double)std::max<uint64_t>(1, nlists);
     const int qg = pick_qg(dq, avg_q_per_list, ix.order);
-    uint64_t hstats[15];
+    GroupingCounts hstats;
     VI_TRY(launch_grouping(ix, ws.probes.p + q0 * P, m, P, qg, segb0, hstats, st, false));
-    stt.scan_items += hstats[1];
+    stt.scan_items += hstats[kStatItems];
     ScanArgs a{};
     a.blocks = (const float4 *)ix.lists.blocks.p; a.dq = dq; a.dim = dim; a.Q = Qd + q0 * dim; a.nq = (uint32_t)m;
     a.K = 1;
@@ -384,7 +375,7 @@ vi_status device_index_search_generic(const DeviceIndex &ix, const float *Qd, ui
     a.dump_keys = ws.sort_keys.p; a.dump_row = L; a.dump_off = ws.off_by_rank.p + q0 * P;
     // a filter only drops keys: the candidate indices — and with them the recovery of (g, pos) — stay the unfiltered ones
     a.allow = flt ? flt->allow.p : nullptr;
-    VI_TRY(launch_scan(a, qg, ix.order, false, (uint32_t)hstats[1], st));
+    VI_TRY(launch_scan(a, qg, ix.order, false, (uint32_t)hstats[kStatItems], st));
     VI_TRY(sort_rows(ws.sort_keys.p, m, logL, st));
     if (flt) {
       hipLaunchKernelGGL(count_keys_kernel, dim3((uint32_t)m), dim3(64), 0, st, ws.sort_keys.p, logL, (uint32_t)m, (uint32_t)k,

@@ -21,13 +21,10 @@
 
 #include "device_index.hpp"
 #include "scan.hpp"
+#include "search_internal.hpp"
 #include "shards.hpp"
 
 namespace vi {
-
-// search_kernels.hip
-vi_status init_device_index_pub(DeviceIndex *ix, int device, uint32_t dim, uint64_t nlists);
-
 namespace {
 
 constexpr int kWave = 64;
@@ -290,7 +287,7 @@ vi_status device_index_from_order(int device, uint32_t dim, const float *table_h
                                   const uint32_t *order_dev, const std::vector<uint64_t> &src_off,
                                   const std::vector<uint32_t> &len, const std::vector<uint32_t> &list_shard,
                                   const uint64_t *ids_dev, const uint64_t *ts_dev, uint64_t now, DeviceIndex *ix) {
-  VI_TRY(init_device_index_pub(ix, device, dim, nlists));
+  VI_TRY(init_device_index(ix, device, dim, nlists));
   ix->order = VI_ORDER_SCALAR;
   const uint32_t dq = ix->dq;
   hipStream_t st = ix->stream;
@@ -346,7 +343,7 @@ vi_status device_index_from_order(int device, uint32_t dim, const float *table_h
     }
     VI_HIP(hipStreamSynchronize(st));
   }
-  return compute_slot_norms(ix);
+  return prepare_rank_images(ix);
 }
 
 // One shard file from device-resident points (byte-identical to shard_save_to, shards.cpp): lists = the shard's lists in

@@ -28,7 +28,7 @@ struct RankStreamArgs {
 vi_status launch_rank_stream(const RankStreamArgs &a, uint32_t nc, uint32_t nitems, int rank_mode, bool qlo, uint32_t gq, hipStream_t st);
 
 // 8-bit descriptors (every stored value an integer in 0..255) against queries of integers in 0..254: the same work items
-// ranked with exact int8 products, in the frame shifted by 127 (filter_search.hip: i8_image_kernel, split_queries_kernel).
+// ranked with exact int8 products, in the frame shifted by 127 (rank_images.hip: i8_image_kernel; filter_search.hip: split_queries_kernel).
 // Rank value of (q, v): 2 r with r = h(v) - q'.v', q' = q - 127, v' = v - 127, h(v) = ceil(|v'|^2 / 2) — an integer with
 // |v'|^2 - 2 q'.v' <= 2 r <= |v'|^2 - 2 q'.v' + 1, stored as a float (exact below 2^24).
 struct RankStreamI8Args {

@@ -1,0 +1,77 @@
+// search_internal.hpp — what the search engines' translation units (search_kernels.hip, generic_search.hip,
+// filter_search.hip, rank_images.hip, list_build.hip) call in each other and share: declared once, here.
+#pragma once
+#include <array>
+#include <cstdint>
+
+#include "device_index.hpp"
+
+namespace vi {
+
+constexpr uint32_t kMaxFilterDim = 1536;  // the MFMA engine's dimension limit (rank_wide_kernel above 128)
+constexpr uint32_t kNarrowDim = 128;     // up to here the queries of a work item stay in registers (filter_kernel)
+
+// ---- SearchWorkspace::stats: the engines' block of 64-bit device counters, by word ----
+enum StatWord {
+  // the grouping's counts: reset by list_totals_kernel, written by group_scan_kernel / group_prepare_kernel, read back by
+  // launch_grouping (the first three by search_valu_pipeline)
+  kStatScannedVectors = 0,  // sum over the lists of (queries probing it) x (its length)
+  kStatItems = 1,           // scan / rank work items
+  kStatSegRuns = 2,         // segment runs awaiting seg_merge_kernel (VALU engine)
+  kStatTileBlocks = 3,      // (query group, block) tiles of the MFMA list phase
+  kStatGroupRecords = 4,    // group records
+  kStatRecordTiles = 5,     // record tiles (pair records: 2 x gq each)
+  kStatListCounts = 6,      // ... words [0, 6): what the VALU engine clears itself
+  // the selects' counters (VI_FILTER_STATS): cleared by search_filter_pipeline as [6, 12)
+  kStatSelExact = 6,        // list select: vectors evaluated exactly; coarse select: single rows
+  kStatSelScanned = 7,      // list select: groups scanned; coarse select: whole sub-blocks
+  kStatSelQueriesFull = 8,  // queries with a full group
+  kStatSelFullGroups = 9,
+  kStatSelSubBlocks = 10,
+  kStatSelectEnd = 12,
+  kStatTiles128 = 12,       // the grouping again: tiles a grouping by 128 queries would have (the fill behind gq_hint)
+  // batch flags: raised by split_queries_kernel, read back with the grouping's counts, reset by item_cols_kernel
+  kStatQueryLo = 13,        // some query has a lo plane
+  kStatQueryNotI8 = 14,     // some query is no int8 image
+  kStatGroupingWords = 15,  // words [0, 15): what the host reads back after the grouping ...
+  kStatGroupingLanding = 16,  // ... into a pinned buffer of this many
+  // the streaming rank kernel's work counters: one per XCD queue, 128 bytes apart, reset by item_cols_kernel
+  kStatRankWork = 16, kStatRankWorkStride = 16, kStatRankWorkCount = 8,
+  // the selects' stage clocks (VI_FILTER_STATS)
+  kStatClocks = 150, kStatClockCount = 8,
+  kStatWords = 160          // size of the block
+};
+static_assert(kStatGroupingWords <= kStatGroupingLanding, "the landing buffer holds the grouping's counts");
+static_assert(kStatRankWork + kStatRankWorkStride * kStatRankWorkCount <= kStatClocks && kStatClocks + kStatClockCount <= kStatWords,
+              "the ranges of the counter block do not overlap");
+using GroupingCounts = std::array<uint64_t, kStatGroupingWords>;  // host copy of words [0, kStatGroupingWords)
+
+// ---- search_kernels.hip ----
+vi_status init_device_index(DeviceIndex *ix, int device, uint32_t dim, uint64_t nlists);
+vi_status stage_coarse(const DeviceIndex &ix, const float *Qd, uint64_t nq, uint32_t P, hipStream_t st);
+vi_status adopt_probes(const DeviceIndex &ix, uint64_t nq, uint32_t P, const uint32_t *probes_in, const uint32_t *order_in,
+                       bool histogram, hipStream_t st);
+vi_status launch_grouping(const DeviceIndex &ix, const uint32_t *probes, uint64_t nq, uint32_t P, int qg, uint32_t segb0,
+                          GroupingCounts &hstats, hipStream_t st, bool histogram_done, const uint32_t *qtot = nullptr,
+                          uint32_t *qoff = nullptr, const uint32_t *pair_rank = nullptr);
+
+// ---- filter_search.hip ----
+vi_status search_filter_pipeline(const DeviceIndex &ix, const EngineKnobs &kn, const float *Qd, uint64_t nq, uint64_t k, uint32_t P,
+                                 float *Dd, int64_t *Id, uint64_t *Td, uint64_t *slots, uint32_t *counts, hipStream_t st,
+                                 int timing_level, const uint32_t *probes_in, const uint32_t *order_in, const SlotFilter *flt);
+vi_status coarse_only_filter(const DeviceIndex &ix, const EngineKnobs &kn, const float *Qd, uint64_t nq, uint32_t P, hipStream_t st);
+bool filter_path_applicable(const DeviceIndex &ix, const EngineKnobs &kn, uint64_t k, uint32_t P);
+bool coarse_on_matrix_cores(const DeviceIndex &ix, const EngineKnobs &kn, uint64_t nq, uint32_t P);
+
+// ---- generic_search.hip ----
+vi_status device_index_search_generic(const DeviceIndex &ix, const float *Qd, uint64_t nq, uint64_t k, uint32_t P,
+                                      float *Dd, int64_t *Id, uint64_t *Td, uint64_t *slots, uint32_t *counts,
+                                      hipStream_t st, const uint32_t *probes_in, const uint32_t *order_in, const SlotFilter *flt);
+vi_status generic_probe_export(const DeviceIndex &ix, const float *Qd, uint64_t nq, uint32_t P, hipStream_t st);
+
+// ---- rank_images.hip ----
+// everything the MFMA engine ranks an index from, derived from its f32 blocks: norms, bf16 / int8 images, the centre, the
+// margins' constants (the DeviceIndex fields from xnorm to c_len); called at the end of every index upload
+vi_status prepare_rank_images(DeviceIndex *ix);
+
+}  // namespace vi

@@ -31,6 +31,7 @@
 #include "device_index.hpp"
 #include "device_math.hpp"
 #include "scan.hpp"
+#include "search_internal.hpp"
 #include "slot_filter.hpp"
 #include "wave_select.hpp"
 #include "wave_sort.hpp"
@@ -367,13 +368,13 @@ __global__ void __launch_bounds__(kBlockThreads) coarse_merge_kernel(CoarseMerge
 //   seg_start    Σ cnt                      (pairs grouped by list)
 //   item_start   Σ ceil(cnt/QG) * nseg      (scan work items)
 //   segrun_start Σ cnt * nseg [nseg > 1]    (segment runs awaiting seg_merge_kernel)
-// stats[0] = Σ cnt*len, stats[1] = items, stats[2] = segment runs
+// and the grouping's counts of ws.stats (StatWord, search_internal.hpp): Σ cnt*len, items, segment runs, ...
 // queries probing every list: the sum of its sub-bin counters (one thread per list: coalesced along each sub-bin row)
-// (also resets the counters group_scan_kernel adds to — stats[0..5] and [12] — when `stats` is given: two memset
+// (also resets the counters group_scan_kernel adds to — the grouping's counts — when `stats` is given: two memset
 // launches less on a path made of 5-microsecond kernels)
 __global__ void list_totals_kernel(const uint32_t *cnt, uint32_t nlists, uint32_t *tot, uint64_t *stats) {
   const uint32_t l = blockIdx.x * blockDim.x + threadIdx.x;
-  if (stats && l < 7) stats[l < 6 ? l : 12] = 0;
+  if (stats && l < kStatListCounts + 1) stats[l < kStatListCounts ? l : kStatTiles128] = 0;
   if (l >= nlists) return;
   const uint32_t st = subbin_stride(nlists);
   uint32_t c = 0;
@@ -448,10 +449,10 @@ __device__ __forceinline__ void group_scan_lists(const uint32_t *cnt, const uint
   }
   if (lane == 0) {
     s_seg[wave] = seg; s_item[wave] = item; s_run[wave] = run; s_tile[wave] = tile;
-    atomicAdd((unsigned long long *)&stats[0], v4[0]);
-    atomicAdd((unsigned long long *)&stats[4], v4[1]);
-    atomicAdd((unsigned long long *)&stats[3], v4[2]);
-    atomicAdd((unsigned long long *)&stats[12], v4[3]);
+    atomicAdd((unsigned long long *)&stats[kStatScannedVectors], v4[0]);
+    atomicAdd((unsigned long long *)&stats[kStatGroupRecords], v4[1]);
+    atomicAdd((unsigned long long *)&stats[kStatTileBlocks], v4[2]);
+    atomicAdd((unsigned long long *)&stats[kStatTiles128], v4[3]);
   }
   __syncthreads();
   uint32_t rs = 0, ri = 0, rr = 0, rt = 0, tseg = 0, titem = 0, trun = 0, ttile = 0;
@@ -486,9 +487,9 @@ __device__ __forceinline__ void group_scan_lists(const uint32_t *cnt, const uint
     seg_start[nlists] = tseg;
     item_start[nlists] = titem;
     segrun_start[nlists] = trun;
-    stats[1] = titem;
-    stats[2] = trun;
-    stats[5] = ttile;
+    stats[kStatItems] = titem;
+    stats[kStatSegRuns] = trun;
+    stats[kStatRecordTiles] = ttile;
   }
 }
 
@@ -959,8 +960,6 @@ static vi_status repack_upload(const uint8_t *host_src, size_t src_bytes, const 
   return VI_OK;
 }
 
-static vi_status init_device_index(DeviceIndex *ix, int device, uint32_t dim, uint64_t nlists);
-
 std::vector<uint32_t> shard_owners(const std::vector<uint64_t> &shard_bytes, uint32_t world) {
   const size_t ns = shard_bytes.size();
   std::vector<uint32_t> order(ns), owner(ns, 0);
@@ -1108,10 +1107,10 @@ vi_status device_index_load(const IndexMeta &meta, const std::string &shards_dir
     VI_HIP(hipMemcpy(ix->list_len.p, h_len.data(), k * 4, hipMemcpyHostToDevice));
     VI_HIP(hipMemcpy(ix->list_shard.p, h_shard.data(), k * 4, hipMemcpyHostToDevice));
   }
-  return compute_slot_norms(ix);
+  return prepare_rank_images(ix);
 }
 
-static vi_status init_device_index(DeviceIndex *ix, int device, uint32_t dim, uint64_t nlists) {
+vi_status init_device_index(DeviceIndex *ix, int device, uint32_t dim, uint64_t nlists) {
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
     return fail(VI_ERR_DEVICE, "no HIP device visible: libvi_amd never falls back to the CPU");
@@ -1123,10 +1122,6 @@ static vi_status init_device_index(DeviceIndex *ix, int device, uint32_t dim, ui
   ix->nlists = nlists;
   if (!ix->stream) VI_HIP(hipStreamCreateWithFlags(&ix->stream, hipStreamDefault));
   return VI_OK;
-}
-
-vi_status init_device_index_pub(DeviceIndex *ix, int device, uint32_t dim, uint64_t nlists) {
-  return init_device_index(ix, device, dim, nlists);
 }
 
 vi_status device_index_from_rows(int device, int order, uint32_t dim, const float *table_dev, uint64_t ntable,
@@ -1189,20 +1184,8 @@ vi_status device_index_from_rows(int device, int order, uint32_t dim, const floa
     VI_HIP(hipMemcpy(ix->list_len.p, h_len.data(), nlists * 4, hipMemcpyHostToDevice));
     VI_HIP(hipMemcpy(ix->list_shard.p, h_shard.data(), nlists * 4, hipMemcpyHostToDevice));
   }
-  return compute_slot_norms(ix);
+  return prepare_rank_images(ix);
 }
-
-vi_status search_filter_pipeline(const DeviceIndex &ix, const EngineKnobs &kn, const float *Qd, uint64_t nq, uint64_t k, uint32_t P,
-                                 float *Dd, int64_t *Id, uint64_t *Td, uint64_t *slots, uint32_t *counts, hipStream_t st,
-                                 int timing_level, const uint32_t *probes_in, const uint32_t *order_in, const SlotFilter *flt);
-vi_status coarse_only_filter(const DeviceIndex &ix, const EngineKnobs &kn, const float *Qd, uint64_t nq, uint32_t P, hipStream_t st);
-bool filter_path_applicable(const DeviceIndex &ix, const EngineKnobs &kn, uint64_t k, uint32_t P);
-bool coarse_on_matrix_cores(const DeviceIndex &ix, const EngineKnobs &kn, uint64_t nq, uint32_t P);
-
-vi_status device_index_search_generic(const DeviceIndex &ix, const float *Qd, uint64_t nq, uint64_t k, uint32_t P,
-                                      float *Dd, int64_t *Id, uint64_t *Td, uint64_t *slots, uint32_t *counts,
-                                      hipStream_t st, const uint32_t *probes_in, const uint32_t *order_in, const SlotFilter *flt);
-vi_status generic_probe_export(const DeviceIndex &ix, const float *Qd, uint64_t nq, uint32_t P, hipStream_t st);
 
 // ------------------------------------------------------------------------------------------
 // pipeline stages
@@ -1320,11 +1303,11 @@ vi_status search_valu_pipeline(const DeviceIndex &ix, const EngineKnobs &kn, con
   VI_TRY(ws.item_start.reserve(nlists + 1));
   VI_TRY(ws.pairs.reserve(nq * P));
   VI_TRY(ws.segrun_start.reserve(nlists + 1));
-  VI_HIP(hipMemsetAsync(ws.stats.p, 0, 6 * sizeof(uint64_t), st));  // [6] .. [11] belong to the MFMA path's select
+  VI_HIP(hipMemsetAsync(ws.stats.p, 0, kStatListCounts * sizeof(uint64_t), st));  // (the selects' counters behind them belong to the MFMA engine)
   VI_TRY(launch_group_scan(ix, (uint32_t)qg_l, kSegBlocks, nullptr, st));
   // exact work-item / segment-run counts size the scan grid and its scratch; the host waits for them while the
   // scatter runs
-  uint64_t hstats[3] = {0, 0, 0};
+  uint64_t hstats[kStatSegRuns + 1] = {};
   VI_HIP(hipMemcpyAsync(hstats, ws.stats.p, sizeof(hstats), hipMemcpyDeviceToHost, st));
   VI_HIP(hipEventRecord(ix.cur().ev[5], st));
   {
@@ -1335,9 +1318,9 @@ vi_status search_valu_pipeline(const DeviceIndex &ix, const EngineKnobs &kn, con
     VI_HIP(hipGetLastError());
   }
   VI_HIP(hipEventSynchronize(ix.cur().ev[5]));
-  stt.scanned_vectors = hstats[0];
-  stt.scan_items = hstats[1];
-  const uint64_t nsegruns = hstats[2];
+  stt.scanned_vectors = hstats[kStatScannedVectors];
+  stt.scan_items = hstats[kStatItems];
+  const uint64_t nsegruns = hstats[kStatSegRuns];
   VI_TRY(ws.seg_run_dist.reserve(nsegruns * K));
   VI_TRY(ws.seg_run_pos.reserve(nsegruns * K));
   if (rank_timing) VI_HIP(hipEventRecord(ix.cur().ev[2], st));
@@ -1351,7 +1334,7 @@ vi_status search_valu_pipeline(const DeviceIndex &ix, const EngineKnobs &kn, con
     a.segb0 = kSegBlocks; a.segrun_start = ws.segrun_start.p;
     a.seg_run_dist = ws.seg_run_dist.p; a.seg_run_pos = ws.seg_run_pos.p;
     a.allow = flt ? flt->allow.p : nullptr;  // excluded vectors never enter a run: the merges below see none of them
-    VI_TRY(launch_scan(a, qg_l, ix.order, false, (uint32_t)hstats[1], st));
+    VI_TRY(launch_scan(a, qg_l, ix.order, false, (uint32_t)hstats[kStatItems], st));
     if (nsegruns) {
       SegMergeArgs m{ws.seg_start.p, ws.segrun_start.p, ix.list_len.p, ws.pairs.p, (uint32_t)nlists, kSegBlocks, K,
                      ws.seg_run_dist.p, ws.seg_run_pos.p, ws.run_dist.p, ws.run_pos.p};
@@ -1461,7 +1444,7 @@ vi_status device_index_search(const DeviceIndex &ix, const SearchIO &io) {
     Qd = ws.q.p; Dd = ws.D.p; Id = ws.I.p; Td = nullptr;
   }
   VI_TRY(ws.counts.reserve(nq));
-  VI_TRY(ws.stats.reserve(160));
+  VI_TRY(ws.stats.reserve(kStatWords));
   uint64_t *slots = nullptr;
   if (io.V) { VI_TRY(ws.slots.reserve(nq * k)); slots = ws.slots.p; }
 
@@ -1539,10 +1522,8 @@ vi_status device_index_search(const DeviceIndex &ix, const SearchIO &io) {
 
 // Counting sort of nq*P (query, probe) pairs by list for the generic path (the fast path folds
 // the histogram into coarse_merge_kernel).  Fills ws.{cnt,seg_start,item_start,segrun_start,pairs}.
-bool grouping_fuses_query_offsets(const DeviceIndex &) { return true; }
-
 vi_status launch_grouping(const DeviceIndex &ix, const uint32_t *probes, uint64_t nq, uint32_t P, int qg, uint32_t segb0,
-                          uint64_t hstats[15], hipStream_t st, bool histogram_done, const uint32_t *qtot, uint32_t *qoff,
+                          GroupingCounts &hstats, hipStream_t st, bool histogram_done, const uint32_t *qtot, uint32_t *qoff,
                           const uint32_t *pair_rank) {
   SearchWorkspace &ws = ix.cur().ws;
   const uint64_t nlists = ix.nlists;
@@ -1554,8 +1535,8 @@ vi_status launch_grouping(const DeviceIndex &ix, const uint32_t *probes, uint64_
   VI_TRY(ws.pairs.reserve(total));
   VI_TRY(ws.pair_pos.reserve(total));
   VI_TRY(ws.tile_start.reserve(nlists + 1));
-  VI_TRY(ws.stats.reserve(160));
-  // (stats[0..5] and [12] are reset by list_totals_kernel; [6] .. [11] belong to the MFMA path's select)
+  VI_TRY(ws.stats.reserve(kStatWords));
+  // (the layout of ws.stats: StatWord, search_internal.hpp — the grouping's counts are reset by list_totals_kernel)
   if (!histogram_done) {  // the coarse step of the fast paths leaves the histogram behind
     VI_HIP(hipMemsetAsync(ws.cnt.p, 0, subbin_words(nlists) * sizeof(uint32_t), st));
     hipLaunchKernelGGL(histogram_kernel, dim3((total + 255) / 256), dim3(256), 0, st, probes, ix.list_len.p,
@@ -1565,8 +1546,8 @@ vi_status launch_grouping(const DeviceIndex &ix, const uint32_t *probes, uint64_
   // the host waits for the counts (grid size, scratch) while the scatter runs
   // (into page-locked memory: a copy to the caller's stack array is staged by the runtime and costs a few microseconds
   // more on the one synchronisation point of the pipeline)
-  if (!ws.hstats_pinned) VI_HIP(hipHostMalloc((void **)&ws.hstats_pinned, 16 * sizeof(uint64_t)));
-  VI_HIP(hipMemcpyAsync(ws.hstats_pinned, ws.stats.p, 15 * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+  if (!ws.hstats_pinned) VI_HIP(hipHostMalloc((void **)&ws.hstats_pinned, kStatGroupingLanding * sizeof(uint64_t)));
+  VI_HIP(hipMemcpyAsync(ws.hstats_pinned, ws.stats.p, sizeof(GroupingCounts), hipMemcpyDeviceToHost, st));
   VI_HIP(hipEventRecord(ix.cur().ev[5], st));
   if (pair_rank && histogram_done)
     hipLaunchKernelGGL(group_scatter_ranked_kernel, dim3((total + 255) / 256), dim3(256), 0, st, probes, ix.list_len.p,
@@ -1576,7 +1557,7 @@ vi_status launch_grouping(const DeviceIndex &ix, const uint32_t *probes, uint64_
                        (uint32_t)nlists, P, ws.cnt.p + subbin_words(nlists), ws.pairs.p, total, ws.seg_start.p, ws.pair_pos.p);
   VI_HIP(hipGetLastError());
   VI_HIP(hipEventSynchronize(ix.cur().ev[5]));
-  std::memcpy(hstats, ws.hstats_pinned, 15 * sizeof(uint64_t));
+  std::memcpy(hstats.data(), ws.hstats_pinned, sizeof(GroupingCounts));
   return VI_OK;
 }
 
