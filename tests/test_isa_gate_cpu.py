@@ -259,8 +259,13 @@ def test_big_cluster_sums_stay_in_registers(tmp_path_factory):
         assert len(re.findall(r"global_load_dwordx4", body)) >= 8, name   # 16-byte row pieces
 
 
-def test_select_top_k_sorts_without_the_lds_crossbar(asm):
-    ks = _kernel_bodies(asm, r"_ZN2vi12_GLOBAL__N_113offer_bulk_fnINS_(8FastTopK|10FastTop128)EEET_S\d_fji")
+@pytest.fixture(scope="module")
+def select_asm(tmp_path_factory):
+    return _compile(tmp_path_factory, os.path.join(ROOT, "vector-indexer_amd", "csrc", "select.hip"))
+
+
+def test_select_top_k_sorts_without_the_lds_crossbar(select_asm):
+    ks = _kernel_bodies(select_asm, r"_ZN2vi12_GLOBAL__N_113offer_bulk_fnINS_(8FastTopK|10FastTop128)EEET_S\d_fji")
     assert len(ks) == 2
     for name, (body, _) in ks.items():
         assert "ds_bpermute" not in body, f"{name}: the sorting network goes through the LDS crossbar again"
@@ -268,12 +273,12 @@ def test_select_top_k_sorts_without_the_lds_crossbar(asm):
         assert len(re.findall(r"v_cmp_\w+_u64", body)) >= 27, name   # one 64-bit compare per compare-exchange step
 
 
-def test_exact_evaluation_pieces_keep_their_address_spaces_and_counted_waits(asm):
+def test_exact_evaluation_pieces_keep_their_address_spaces_and_counted_waits(select_asm):
     """The exact-evaluation pieces of the select kernels are real (noinline) functions: their pointer arguments are
     generic, and without the address-space casts every access — the query row in LDS included — is a flat_load through
     the vector-memory address pipe.  The staged row evaluation of the coarse select also counts its LDS-DMA copies by
     hand (vmcnt(4) / vmcnt(0)): correct only while those copies are the function's ONLY vector-memory operations."""
-    fns = _kernel_bodies(asm, r"_ZN2vi12_GLOBAL__N_1\d+exact_batch_\w*fnINS_(8FastTopK|10FastTop128)EEET_\w+")
+    fns = _kernel_bodies(select_asm, r"_ZN2vi12_GLOBAL__N_1\d+exact_batch_\w*fnINS_(8FastTopK|10FastTop128)EEET_\w+")
     assert len(fns) >= 8, sorted(fns)
     for name, (body, _) in fns.items():
         assert not re.search(r"^\s*flat_(load|store)", body, re.M), f"{name}: generic-pointer access"
@@ -289,11 +294,11 @@ def test_exact_evaluation_pieces_keep_their_address_spaces_and_counted_waits(asm
         assert not re.search(r"v_(fma|fmac|mad)_f32", body), f"{name}: a fused multiply-add in the reference's unfused chain"
 
 
-def test_direct_coarse_select_keeps_its_flags_in_registers(asm):
+def test_direct_coarse_select_keeps_its_flags_in_registers(select_asm):
     """coarse_select_direct_kernel keeps two flag words per lane for up to 2 * kPer = 32 sub-blocks (a class in cls, the
     row of the minimum in rows_lo / rows_hi) and the 16 records of the lane in rb1 / rb2: all indexed at compile time.
     A runtime index into one of those register arrays would move it to scratch memory."""
-    ks = _kernel_bodies(asm, r"_ZN2vi12_GLOBAL__N_127coarse_select_direct_kernelENS0_16CoarseSelectArgsE")
+    ks = _kernel_bodies(select_asm, r"_ZN2vi12_GLOBAL__N_127coarse_select_direct_kernelENS0_16CoarseSelectArgsE")
     assert len(ks) == 1
     for name, (body, meta) in ks.items():
         assert_no_scratch(name, dict(body=body, meta=meta))

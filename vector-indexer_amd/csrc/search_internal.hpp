@@ -1,5 +1,6 @@
 // search_internal.hpp — what the search engines' translation units (search_kernels.hip, generic_search.hip,
-// filter_search.hip, rank_images.hip, list_build.hip) call in each other and share: declared once, here.
+// filter_search.hip, select.hip, rank_images.hip, list_build.hip) call in each other and share: declared once, here.
+// (filter_search.hip launches its rank and select phases through headers of their own: rank_stream.hpp, select.hpp)
 #pragma once
 #include <array>
 #include <cstdint>
