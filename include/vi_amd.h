@@ -318,6 +318,37 @@ vi_status vi_indexer_search_probed_filtered_device(const vi_indexer *ix, const v
                                                    const uint32_t *probes_dev, const uint32_t *order_dev, float *D_dev,
                                                    int64_t *I_dev, uint64_t *tie_dev);
 
+/* ---- extension: radius (range) search -----------------------------------------------------------------------------
+ * Every candidate of the probed lists whose squared distance is at most radius2.  The result of a query is the
+ * reference's candidate sequence (probed lists in shard visiting order, then probe rank, then list position) after the
+ * reference's stable sort by distance, cut at the first candidate with d > radius2: take_while(d <= radius2) where a
+ * search has take(k).  d is the reference's f32 scalar-order sum and the comparison is made in f32, so d == radius2 is
+ * inside.  Ids, distance bits, order and per-query counts are exact on every engine.
+ *   - the coarse step is the unfiltered, unradiused one: the result covers the n_probe probed lists only; n_probe is
+ *     clamped to max_n_probe; n_probe == 0 or a query_dim mismatch is VI_ERR_INVALID_INPUT
+ *   - radius2 NaN: VI_ERR_INVALID_INPUT; negative: VI_OK with zero results; +inf: everything probed, sorted
+ *   - a NaN / Inf query value: VI_ERR_PANIC (host entry), as for a search
+ *   - f: candidates outside the filter's window are deleted from the sequence first (NULL: no filter)
+ *   - on a partitioned handle (world_size > 1) the result covers the resident part, with the tie keys
+ *     vi_indexer_search_device gives (stripe correction included): per-rank results merge by (distance, tie)
+ *   - a batch is all or nothing: when scratch or result memory cannot be had the call fails (VI_ERR_DEVICE, or
+ *     VI_ERR_INVALID_INPUT "split nq") and *out stays NULL
+ * The result is an opaque object in CSR layout, as Faiss's RangeSearchResult: query q owns entries [lims[q], lims[q+1])
+ * of D / I / tie.  It owns its device buffers, stays valid through later searches of the handle, and must be freed
+ * before its indexer.  vi_indexer_last_stats after a radius search reads as after a search, with k = 0. */
+typedef struct vi_range_result vi_range_result;
+vi_status vi_indexer_range_search(const vi_indexer *ix, const vi_filter *f, const float *queries, uint64_t nq,
+                                  uint32_t query_dim, float radius2, uint64_t n_probe, vi_range_result **out);
+vi_status vi_indexer_range_search_device(const vi_indexer *ix, const vi_filter *f, const float *queries_dev, uint64_t nq,
+                                         float radius2, uint64_t n_probe, vi_range_result **out);
+uint64_t vi_range_result_total(const vi_range_result *r); /* lims[nq]; NULL: 0 */
+/* host buffers: lims nq + 1, D and I `total` each, V (optional) total x dim: the stored vectors of the hits */
+vi_status vi_range_result_copy(const vi_range_result *r, uint64_t *lims, float *D, int64_t *I, float *V);
+/* the result's own device buffers (any of the four may be NULL); tie = (candidate-order rank << 32) | list position */
+vi_status vi_range_result_device(const vi_range_result *r, const uint64_t **lims_dev, const float **D_dev,
+                                 const int64_t **I_dev, const uint64_t **tie_dev);
+void vi_range_result_free(vi_range_result *r); /* NULL ok */
+
 /* Merge `parts` per-rank partial results (each nq x k, device pointers laid out
  * [part][nq][k]) into the global top-k with the reference's stable order. */
 vi_status vi_merge_partials_device(int32_t device, uint64_t nq, uint64_t k, uint32_t parts,

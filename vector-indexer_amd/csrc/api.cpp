@@ -203,6 +203,10 @@ struct vi_filter {
   vi::SlotFilter impl;
 };
 
+struct vi_range_result {
+  vi::RangeResult impl;
+};
+
 extern "C" {
 
 const char *vi_last_error(void) { return vi::last_error_ref().c_str(); }
@@ -586,6 +590,78 @@ vi_status vi_indexer_filter_timestamps(const vi_indexer *ix, uint64_t ts_min, ui
 uint64_t vi_filter_num_allowed(const vi_filter *f) { return f ? f->impl.num_allowed : 0; }
 
 void vi_filter_free(vi_filter *f) { delete f; }
+
+// the checks the radius entries share; *done: nothing to search (an empty result was made)
+static vi_status range_common(const vi_indexer *ix, const vi_filter *f, const float *queries, uint64_t nq, float radius2,
+                              uint64_t *n_probe, vi_range_result **out, const vi::SlotFilter **flt) {
+  uint64_t k = 1;
+  VI_TRY(search_common(ix, &k, n_probe));
+  if (!out) return fail(VI_ERR_INVALID_INPUT, "null pointer");
+  *out = nullptr;
+  VI_TRY(filter_common(ix, f, flt));
+  if (*n_probe == 0) return fail(VI_ERR_INVALID_INPUT, "n_probe must be greater than 0");
+  if (std::isnan(radius2)) return fail(VI_ERR_INVALID_INPUT, "radius2 is NaN");
+  if (nq && !queries) return fail(VI_ERR_INVALID_INPUT, "null pointer");
+  if (!ix->impl.dev) return fail(VI_ERR_DEVICE, "index is not resident on a GPU (build or load it first)");
+  return VI_OK;
+}
+
+static vi_status range_run(const vi_indexer *ix, const vi::RangeIO &io, vi_range_result **out) {
+  auto r = std::make_unique<vi_range_result>();
+  VI_TRY(vi::device_index_range_search(*ix->impl.dev, io, &r->impl));  // (all or nothing: a failed search leaves no result)
+  *out = r.release();
+  return VI_OK;
+}
+
+vi_status vi_indexer_range_search(const vi_indexer *ix, const vi_filter *f, const float *queries, uint64_t nq, uint32_t query_dim,
+                                  float radius2, uint64_t n_probe, vi_range_result **out) {
+  return vi::guarded([&]() -> vi_status {
+  const vi::SlotFilter *flt = nullptr;
+  VI_TRY(range_common(ix, f, queries, nq, radius2, &n_probe, out, &flt));
+  if (query_dim != ix->impl.cfg.dimension)
+    return fail(VI_ERR_INVALID_INPUT, "query dimension mismatch: expected %u, got %u", ix->impl.cfg.dimension, query_dim);
+  // NaN/Inf in a query makes partial_cmp().unwrap() panic in the reference (ivf_index.rs:215)
+  for (uint64_t i = 0; i < nq * (uint64_t)query_dim; ++i)
+    if (!std::isfinite(queries[i])) return fail(VI_ERR_PANIC, "non-finite query value at flat index %llu", (unsigned long long)i);
+  vi::RangeIO io;
+  io.queries = queries; io.nq = nq; io.n_probe = n_probe; io.radius2 = radius2; io.filter = flt;
+  return range_run(ix, io, out);
+  });
+}
+
+vi_status vi_indexer_range_search_device(const vi_indexer *ix, const vi_filter *f, const float *queries_dev, uint64_t nq,
+                                         float radius2, uint64_t n_probe, vi_range_result **out) {
+  return vi::guarded([&]() -> vi_status {
+  const vi::SlotFilter *flt = nullptr;
+  VI_TRY(range_common(ix, f, queries_dev, nq, radius2, &n_probe, out, &flt));
+  vi::RangeIO io;
+  io.queries = queries_dev; io.on_device = true; io.nq = nq; io.n_probe = n_probe; io.radius2 = radius2; io.filter = flt;
+  return range_run(ix, io, out);
+  });
+}
+
+uint64_t vi_range_result_total(const vi_range_result *r) { return r ? r->impl.total : 0; }
+
+vi_status vi_range_result_copy(const vi_range_result *r, uint64_t *lims, float *D, int64_t *I, float *V) {
+  return vi::guarded([&]() -> vi_status {
+  if (!r) return fail(VI_ERR_INVALID_INPUT, "null range result");
+  return vi::range_result_copy(r->impl, lims, D, I, V);
+  });
+}
+
+vi_status vi_range_result_device(const vi_range_result *r, const uint64_t **lims_dev, const float **D_dev, const int64_t **I_dev,
+                                 const uint64_t **tie_dev) {
+  return vi::guarded([&]() -> vi_status {
+  if (!r) return fail(VI_ERR_INVALID_INPUT, "null range result");
+  if (lims_dev) *lims_dev = r->impl.lims.p;
+  if (D_dev) *D_dev = r->impl.D.p;
+  if (I_dev) *I_dev = r->impl.I.p;
+  if (tie_dev) *tie_dev = r->impl.tie.p;
+  return VI_OK;
+  });
+}
+
+void vi_range_result_free(vi_range_result *r) { delete r; }
 
 vi_status vi_merge_partials_device(int32_t device, uint64_t nq, uint64_t k, uint32_t parts, const float *D_parts,
                                    const int64_t *I_parts, const uint64_t *tie_parts, float *D_out, int64_t *I_out) {

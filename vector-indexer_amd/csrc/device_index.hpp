@@ -87,6 +87,7 @@ struct SearchWorkspace {
   DevBuf<uint64_t> sort_keys, order_keys, total;
   DevBuf<uint64_t> total_allowed;           // generic engine with a filter: candidates per query that received a key
   DevBuf<uint32_t> gprobe, off_by_g, off_by_rank;
+  DevBuf<uint32_t> range_bound;             // radius search: per query an upper bound of its hits (+ one flag word)
 };
 
 inline uint64_t next_index_serial() {
@@ -183,6 +184,31 @@ struct SearchIO {
   const SlotFilter *filter = nullptr;  // restrict the candidates to the filter's slots (the coarse step never sees it)
 };
 vi_status device_index_search(const DeviceIndex &ix, const SearchIO &io);
+
+// Result of a radius search (device_index_range_search): CSR like Faiss's RangeSearchResult — query q owns entries
+// [lims[q], lims[q + 1]) of D / I / tie / slots, sorted as the reference's stable candidate sort leaves them.  Owns its
+// device buffers; outlives later searches of its index, not the index.
+struct RangeResult {
+  const DeviceIndex *ix = nullptr;  // the index searched (vi_range_result_copy gathers stored vectors from it)
+  uint64_t nq = 0, total = 0;
+  std::vector<uint64_t> h_lims;     // host copy of lims: nq + 1
+  DevBuf<uint64_t> lims;            // nq + 1
+  DevBuf<float> D;                  // `total` entries each, in buffers of `cap`
+  DevBuf<int64_t> I;
+  DevBuf<uint64_t> tie, slots;      // tie key (candidate-order rank << 32 | list position); global slot of the stored vector
+  uint64_t cap = 0;
+};
+struct RangeIO {
+  const float *queries = nullptr;  // host or device (on_device)
+  bool on_device = false;
+  uint64_t nq = 0, n_probe = 0;
+  float radius2 = 0.0f;            // squared L2 radius, inclusive; not NaN
+  const SlotFilter *filter = nullptr;
+};
+// every probed candidate with reference distance <= radius2, per query in the reference's stable order: all or nothing
+vi_status device_index_range_search(const DeviceIndex &ix, const RangeIO &io, RangeResult *out);
+// host copies of a result: lims (nq + 1), D, I (total each), V (optional, total x dim: the stored vectors)
+vi_status range_result_copy(const RangeResult &r, uint64_t *lims, float *D, int64_t *I, float *V);
 
 // The search engines' environment options (filter_search.hip, search_kernels.hip), read once per device_index_search
 // call by read_engine_knobs.  A '0' as the first character turns an on-by-default option off.

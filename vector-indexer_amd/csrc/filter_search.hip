@@ -1177,15 +1177,16 @@ vi_status report_select_stats(const Batch &b) {
 
 }  // namespace
 
-vi_status search_filter_pipeline(const DeviceIndex &ix, const EngineKnobs &kn, const float *Qd, uint64_t nq, uint64_t k, uint32_t P,
-                                 float *Dd, int64_t *Id, uint64_t *Td, uint64_t *slots, uint32_t *counts, hipStream_t st,
-                                 int timing_level, const uint32_t *probes_in, const uint32_t *order_in, const SlotFilter *flt) {
+// ---- 1 to 3 on the search stream: what both list selects (top-k, radius) start from.  Leaves the plan the lists were
+//      ranked by; timing_level 1: an event at every phase boundary; 2: around the rank kernel only (every record is a
+//      barrier packet the next kernel's dispatch waits behind: five of them cost 0.01 ms of a 0.5 ms step) ----
+static vi_status rank_lists(Batch &b, int timing_level, const uint32_t *probes_in, const uint32_t *order_in, RankPlan &plan) {
+  const DeviceIndex &ix = b.ix;
+  const EngineKnobs &kn = b.kn;
+  hipStream_t st = b.st;
   SearchWorkspace &ws = ix.cur().ws;
   vi_search_stats &stt = ix.cur().stats;
-  // 1: an event at every phase boundary; 2: around the rank kernel only (every record is a barrier packet the next
-  // kernel's dispatch waits behind: five of them cost 0.01 ms of a 0.5 ms step)
   const bool timing = timing_level == 1;
-  Batch b{ix, kn, Qd, nq, P, flt, st, timing_level != 0};
   VI_TRY(ws.stats.reserve(kStatWords));
   if (kn.stats) {  // the selects' counters and stage clocks
     VI_HIP(hipMemsetAsync(ws.stats.p + kStatSelExact, 0, (kStatSelectEnd - kStatSelExact) * sizeof(uint64_t), st));
@@ -1196,7 +1197,7 @@ vi_status search_filter_pipeline(const DeviceIndex &ix, const EngineKnobs &kn, c
   VI_TRY(coarse_phase(b, probes_in, order_in));
   if (timing) VI_HIP(hipEventRecord(ix.cur().ev[1], st));
 
-  RankPlan plan = plan_rank(ix, kn, nq, P, gq_hint_for(ws, nq, P), ws.queries_hi_only);
+  plan = plan_rank(ix, kn, b.nq, b.P, gq_hint_for(ws, b.nq, b.P), ws.queries_hi_only);
   GroupingCounts hstats;
   VI_TRY(group_pairs(b, plan, hstats));
   stt.rank_mode = rank_mode_code(ix, plan);
@@ -1211,9 +1212,32 @@ vi_status search_filter_pipeline(const DeviceIndex &ix, const EngineKnobs &kn, c
   }
   VI_TRY(b.start_rank_clock());  // (nothing to rank)
   if (b.rank_timing) VI_HIP(hipEventRecord(ix.cur().ev[3], st));
+  return VI_OK;
+}
 
+vi_status search_filter_pipeline(const DeviceIndex &ix, const EngineKnobs &kn, const float *Qd, uint64_t nq, uint64_t k, uint32_t P,
+                                 float *Dd, int64_t *Id, uint64_t *Td, uint64_t *slots, uint32_t *counts, hipStream_t st,
+                                 int timing_level, const uint32_t *probes_in, const uint32_t *order_in, const SlotFilter *flt) {
+  const bool timing = timing_level == 1;
+  Batch b{ix, kn, Qd, nq, P, flt, st, timing_level != 0};
+  RankPlan plan;
+  VI_TRY(rank_lists(b, timing_level, probes_in, order_in, plan));
   VI_TRY(launch_list_select(ix, kn, Qd, nq, P, k, SelectFrame{plan.gq, plan.kernel == RankKernel::Stream, plan.approx, plan.rank_i8},
                             SelectOutputs{Dd, Id, Td, slots, counts}, flt, st));
+  if (timing) VI_HIP(hipEventRecord(ix.cur().ev[4], st));
+  if (timing && kn.stats) VI_TRY(report_select_stats(b));
+  return VI_OK;
+}
+
+// the radius search: the same records, read by the radius select (range_select.hip) instead of the top-k select
+vi_status range_filter_pipeline(const DeviceIndex &ix, const EngineKnobs &kn, const float *Qd, uint64_t nq, float radius2, uint32_t P,
+                                RangeResult *res, hipStream_t st, int timing_level, const SlotFilter *flt) {
+  const bool timing = timing_level == 1;
+  Batch b{ix, kn, Qd, nq, P, flt, st, timing_level != 0};
+  RankPlan plan;
+  VI_TRY(rank_lists(b, timing_level, nullptr, nullptr, plan));
+  VI_TRY(launch_range_select(ix, kn, Qd, nq, P, radius2, SelectFrame{plan.gq, plan.kernel == RankKernel::Stream, plan.approx, plan.rank_i8},
+                             flt, res, st));
   if (timing) VI_HIP(hipEventRecord(ix.cur().ev[4], st));
   if (timing && kn.stats) VI_TRY(report_select_stats(b));
   return VI_OK;

@@ -321,12 +321,12 @@ vi_status generic_probe_export(const DeviceIndex &ix, const float *Qd, uint64_t 
   return generic_candidate_order(ix, nq, P, false, st);
 }
 
-vi_status device_index_search_generic(const DeviceIndex &ix, const float *Qd, uint64_t nq, uint64_t k, uint32_t P,
-                                      float *Dd, int64_t *Id, uint64_t *Td, uint64_t *slots, uint32_t *counts,
-                                      hipStream_t st, const uint32_t *probes_in, const uint32_t *order_in, const SlotFilter *flt) {
+namespace {
+
+// A + B for a batch, and the candidates per query on the host (added to the search's scanned_vectors)
+vi_status generic_prepare(const DeviceIndex &ix, const float *Qd, uint64_t nq, uint32_t P, hipStream_t st, const uint32_t *probes_in,
+                          const uint32_t *order_in, std::vector<uint64_t> &h_total) {
   SearchWorkspace &ws = ix.cur().ws;
-  const uint32_t dim = ix.dim, dq = ix.dq;
-  const uint64_t nlists = ix.nlists;
   if (ix.nshards > 24576) return fail(VI_ERR_OTHER, "generic path supports at most 24576 shards");
   vi_search_stats &stt = ix.cur().stats;
   if (probes_in) {  // probe lists computed elsewhere: validated, then placed by the given order
@@ -336,47 +336,129 @@ vi_status device_index_search_generic(const DeviceIndex &ix, const float *Qd, ui
     VI_TRY(generic_coarse(ix, Qd, nq, P, st));
     VI_TRY(generic_candidate_order(ix, nq, P, false, st));
   }
-  std::vector<uint64_t> h_total(nq);
+  h_total.resize(nq);
   VI_HIP(hipMemcpyAsync(h_total.data(), ws.total.p, nq * 8, hipMemcpyDeviceToHost, st));
   VI_HIP(hipStreamSynchronize(st));
   for (uint64_t q = 0; q < nq; ++q) {
     if (h_total[q] > 0xFFFFFFFFull) return fail(VI_ERR_OTHER, "more than 2^32 candidates for one query");
     stt.scanned_vectors += h_total[q];
   }
+  return VI_OK;
+}
+
+// how many queries from q0 on share a chunk — rows x row-length within the key budget — and the row length exponent
+// that holds the longest candidate sequence among them (and `least` keys)
+uint64_t chunk_queries(const std::vector<uint64_t> &h_total, uint64_t q0, uint64_t least, uint32_t *logL) {
+  const uint64_t nq = h_total.size();
+  uint64_t mx = std::max<uint64_t>(h_total[q0], 1);
+  uint64_t m = 1;
+  while (q0 + m < nq) {  // grow the chunk while rows x row-length stays within the key budget
+    const uint64_t mx2 = std::max(mx, h_total[q0 + m]);
+    if ((m + 1) << log2_ceil_rows(mx2) > kMaxKeys) break;
+    mx = mx2;
+    ++m;
+  }
+  *logL = log2_ceil_rows(std::max<uint64_t>(mx, least));
+  return m;
+}
+
+// C. queries [q0, q0 + m): every candidate's key into the query's row of 2^logL keys (the rest stays ~0), rows sorted
+vi_status generic_sorted_rows(const DeviceIndex &ix, const float *Qd, uint64_t q0, uint64_t m, uint32_t P, uint32_t logL,
+                              const SlotFilter *flt, hipStream_t st) {
+  SearchWorkspace &ws = ix.cur().ws;
+  vi_search_stats &stt = ix.cur().stats;
+  const uint32_t dim = ix.dim, dq = ix.dq;
+  const uint64_t nlists = ix.nlists;
+  const uint32_t segb0 = 256;
+  const uint64_t L = 1ull << logL;
+  VI_TRY(ws.sort_keys.reserve(m * L));
+  VI_HIP(hipMemsetAsync(ws.sort_keys.p, 0xFF, m * L * sizeof(uint64_t), st));
+  const double avg_q_per_list = (double)m * P / (double)std::max<uint64_t>(1, nlists);
+  const int qg = pick_qg(dq, avg_q_per_list, ix.order);
+  GroupingCounts hstats;
+  VI_TRY(launch_grouping(ix, ws.probes.p + q0 * P, m, P, qg, segb0, hstats, st, false));
+  stt.scan_items += hstats[kStatItems];
+  ScanArgs a{};
+  a.blocks = (const float4 *)ix.lists.blocks.p; a.dq = dq; a.dim = dim; a.Q = Qd + q0 * dim; a.nq = (uint32_t)m;
+  a.K = 1;
+  a.first_block = ix.list_first_block.p; a.list_len = ix.list_len.p; a.item_start = ws.item_start.p;
+  a.seg_start = ws.seg_start.p; a.pairs = ws.pairs.p; a.nlists = (uint32_t)nlists; a.P = P;
+  a.segb0 = segb0; a.segrun_start = ws.segrun_start.p;
+  a.dump_keys = ws.sort_keys.p; a.dump_row = L; a.dump_off = ws.off_by_rank.p + q0 * P;
+  // a filter only drops keys: the candidate indices — and with them the recovery of (g, pos) — stay the unfiltered ones
+  a.allow = flt ? flt->allow.p : nullptr;
+  VI_TRY(launch_scan(a, qg, ix.order, false, (uint32_t)hstats[kStatItems], st));
+  return sort_rows(ws.sort_keys.p, m, logL, st);
+}
+
+// radius search: a sorted row's results are its prefix of keys with distance <= radius2 (the ~0 fill is a NaN: outside)
+__global__ void count_radius_kernel(const uint64_t *keys, uint32_t logL, uint32_t nq, float radius2, uint32_t *counts) {
+  const uint32_t q = blockIdx.x;
+  if (q >= nq) return;
+  __shared__ uint32_t s_n;
+  if (threadIdx.x == 0) s_n = 0u;
+  __syncthreads();
+  uint32_t n = 0;
+  for (uint64_t i = threadIdx.x; i < (1ull << logL); i += blockDim.x)
+    n += __uint_as_float((uint32_t)(keys[((size_t)q << logL) + i] >> 32)) <= radius2 ? 1u : 0u;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) n += (uint32_t)__shfl_xor((int)n, o);
+  if ((threadIdx.x & 63u) == 0u && n) atomicAdd(&s_n, n);
+  __syncthreads();
+  if (threadIdx.x == 0) counts[q] = s_n;
+}
+
+struct RangeOutArgs {
+  const uint64_t *keys;
+  uint32_t logL, nq, P;
+  const uint32_t *counts, *probes, *gprobe, *off_by_g, *first_block;
+  const uint64_t *lims, *ext_ids;
+  float *D;
+  int64_t *I;
+  uint64_t *tie, *slots;
+};
+
+// ... and go out at lims[q] + i (generic_output_kernel's recovery of (g, pos) from the candidate index)
+__global__ void __launch_bounds__(256) generic_range_output_kernel(RangeOutArgs a) {
+  const uint32_t q = blockIdx.x;
+  if (q >= a.nq) return;
+  const uint32_t *off = a.off_by_g + (size_t)q * a.P;
+  const uint64_t at = a.lims[q];
+  for (uint32_t i = threadIdx.x; i < a.counts[q]; i += blockDim.x) {
+    const uint64_t key = a.keys[((size_t)q << a.logL) + i];
+    const uint32_t ci = (uint32_t)key;
+    uint32_t lo = 0, hi = a.P;  // largest g with off[g] <= ci; empty lists share an offset with their successor
+    while (hi - lo > 1) {
+      const uint32_t mid = (lo + hi) >> 1;
+      if (off[mid] <= ci) lo = mid; else hi = mid;
+    }
+    const uint32_t g = lo, pos = ci - off[g];
+    const uint32_t gr = a.gprobe[(size_t)q * a.P + g];
+    const uint32_t l = a.probes[(size_t)q * a.P + (gr < a.P ? gr : 0u)];
+    const uint64_t gslot = (uint64_t)a.first_block[l] * 64 + pos;
+    a.D[at + i] = __uint_as_float((uint32_t)(key >> 32));
+    a.I[at + i] = (int64_t)a.ext_ids[gslot];
+    a.tie[at + i] = ((uint64_t)g << 32) | pos;
+    a.slots[at + i] = gslot;
+  }
+}
+
+}  // namespace
+
+vi_status device_index_search_generic(const DeviceIndex &ix, const float *Qd, uint64_t nq, uint64_t k, uint32_t P,
+                                      float *Dd, int64_t *Id, uint64_t *Td, uint64_t *slots, uint32_t *counts,
+                                      hipStream_t st, const uint32_t *probes_in, const uint32_t *order_in, const SlotFilter *flt) {
+  SearchWorkspace &ws = ix.cur().ws;
+  std::vector<uint64_t> h_total;
+  VI_TRY(generic_prepare(ix, Qd, nq, P, st, probes_in, order_in, h_total));
   if (flt) VI_TRY(ws.total_allowed.reserve(nq));
 
   // ---- C/D. per chunk of queries: dump candidate keys, sort rows, emit the first k ----
-  const uint32_t segb0 = 256;
   uint64_t q0 = 0;
   while (q0 < nq) {
-    uint64_t mx = std::max<uint64_t>(h_total[q0], 1);
-    uint64_t m = 1;
-    while (q0 + m < nq) {  // grow the chunk while rows x row-length stays within the key budget
-      const uint64_t mx2 = std::max(mx, h_total[q0 + m]);
-      if ((m + 1) << log2_ceil_rows(mx2) > kMaxKeys) break;
-      mx = mx2;
-      ++m;
-    }
-    const uint32_t logL = log2_ceil_rows(std::max<uint64_t>(mx, k));
-    const uint64_t L = 1ull << logL;
-    VI_TRY(ws.sort_keys.reserve(m * L));
-    VI_HIP(hipMemsetAsync(ws.sort_keys.p, 0xFF, m * L * sizeof(uint64_t), st));
-    const double avg_q_per_list = (double)m * P / (double)std::max<uint64_t>(1, nlists);
-    const int qg = pick_qg(dq, avg_q_per_list, ix.order);
-    GroupingCounts hstats;
-    VI_TRY(launch_grouping(ix, ws.probes.p + q0 * P, m, P, qg, segb0, hstats, st, false));
-    stt.scan_items += hstats[kStatItems];
-    ScanArgs a{};
-    a.blocks = (const float4 *)ix.lists.blocks.p; a.dq = dq; a.dim = dim; a.Q = Qd + q0 * dim; a.nq = (uint32_t)m;
-    a.K = 1;
-    a.first_block = ix.list_first_block.p; a.list_len = ix.list_len.p; a.item_start = ws.item_start.p;
-    a.seg_start = ws.seg_start.p; a.pairs = ws.pairs.p; a.nlists = (uint32_t)nlists; a.P = P;
-    a.segb0 = segb0; a.segrun_start = ws.segrun_start.p;
-    a.dump_keys = ws.sort_keys.p; a.dump_row = L; a.dump_off = ws.off_by_rank.p + q0 * P;
-    // a filter only drops keys: the candidate indices — and with them the recovery of (g, pos) — stay the unfiltered ones
-    a.allow = flt ? flt->allow.p : nullptr;
-    VI_TRY(launch_scan(a, qg, ix.order, false, (uint32_t)hstats[kStatItems], st));
-    VI_TRY(sort_rows(ws.sort_keys.p, m, logL, st));
+    uint32_t logL;
+    const uint64_t m = chunk_queries(h_total, q0, k, &logL);
+    VI_TRY(generic_sorted_rows(ix, Qd, q0, m, P, logL, flt, st));
     if (flt) {
       hipLaunchKernelGGL(count_keys_kernel, dim3((uint32_t)m), dim3(64), 0, st, ws.sort_keys.p, logL, (uint32_t)m, (uint32_t)k,
                          ws.total_allowed.p + q0);
@@ -386,6 +468,33 @@ vi_status device_index_search_generic(const DeviceIndex &ix, const float *Qd, ui
               ws.off_by_g.p + q0 * P, ix.list_first_block.p, (flt ? ws.total_allowed.p : ws.total.p) + q0, ix.ext_ids.p, Dd + q0 * k, Id + q0 * k,
               Td ? Td + q0 * k : nullptr, slots ? slots + q0 * k : nullptr, counts ? counts + q0 : nullptr};
     hipLaunchKernelGGL(generic_output_kernel, dim3((uint32_t)((m * k + 255) / 256)), dim3(256), 0, st, o);
+    VI_HIP(hipGetLastError());
+    VI_HIP(hipStreamSynchronize(st));
+    q0 += m;
+  }
+  return VI_OK;
+}
+
+// the radius form: the same sorted rows; a row's result is its prefix within radius2, appended to res chunk by chunk
+vi_status device_index_range_generic(const DeviceIndex &ix, const float *Qd, uint64_t nq, float radius2, uint32_t P, RangeResult *res,
+                                     hipStream_t st, const SlotFilter *flt) {
+  SearchWorkspace &ws = ix.cur().ws;
+  std::vector<uint64_t> h_total;
+  VI_TRY(generic_prepare(ix, Qd, nq, P, st, nullptr, nullptr, h_total));
+  VI_TRY(ws.counts.reserve(nq));
+  uint64_t q0 = 0;
+  while (q0 < nq) {
+    uint32_t logL;
+    const uint64_t m = chunk_queries(h_total, q0, 1, &logL);
+    VI_TRY(generic_sorted_rows(ix, Qd, q0, m, P, logL, flt, st));
+    hipLaunchKernelGGL(count_radius_kernel, dim3((uint32_t)m), dim3(256), 0, st, ws.sort_keys.p, logL, (uint32_t)m, radius2,
+                       ws.counts.p + q0);
+    VI_HIP(hipGetLastError());
+    VI_TRY(range_result_place(res, q0, m, ws.counts.p + q0, st));
+    RangeOutArgs o{ws.sort_keys.p, logL, (uint32_t)m, P, ws.counts.p + q0, ws.probes.p + q0 * P, ws.gprobe.p + q0 * P,
+                   ws.off_by_g.p + q0 * P, ix.list_first_block.p, res->lims.p + q0, ix.ext_ids.p, res->D.p, res->I.p, res->tie.p,
+                   res->slots.p};
+    hipLaunchKernelGGL(generic_range_output_kernel, dim3((uint32_t)m), dim3(256), 0, st, o);
     VI_HIP(hipGetLastError());
     VI_HIP(hipStreamSynchronize(st));
     q0 += m;

@@ -1,0 +1,421 @@
+// range_select.hip — the radius form of the MFMA engine's list select: from the records the rank kernels leave to every
+// probed vector whose reference distance is at or below radius2, in the reference's stable order.
+//
+// The top-k select (select.hip) spends its first stages finding a threshold from the K-th smallest rank value.  Here the
+// threshold is known before anything is read: a vector with reference distance d <= radius2 has, in the frame its records
+// live in (||q||^2 = qn there), a rank value
+//     m <= thr = (radius2 - qn) + w + 2E + 3 gamma (radius2 + E),      w = (D/64 + 9) u' (|radius2| + qn)
+// E and gamma as in select.hip (*); w covers the f32 rounding of the subtraction and of qn's own sum.  So one pass over
+// the records is enough: the groups whose smallest minimum is at or below thr, their pair records, and of those every
+// sub-block whose minimum is at or below thr — re-evaluated as a whole in the reference's exact order, as the top-k
+// select does it, four sub-blocks per wave instruction.  What comes out depends on exact distances only.
+//
+// Sizing, with nothing evaluated twice: the same pass WITHOUT the evaluations (range_select_kernel<false>) counts the
+// sub-blocks per query; 16 x that bounds the query's hits and sizes its row of the key scratch.  The pass with the
+// evaluations writes (distance, (candidate-order rank << 26) | position) keys into the row and leaves the true count;
+// the rows are sorted by key — the reference's stable order — and range_output_kernel turns them into D / I / tie / slot
+// at lims[q].  Queries go through this in chunks whose rows fit the key budget.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <vector>
+
+#include "select.hpp"
+#include "select_device.hpp"
+
+namespace vi {
+
+vi_status sort_rows_u64(uint64_t *keys, uint64_t nrows, uint32_t logL, hipStream_t st);  // generic_search.hip
+
+namespace {
+
+constexpr uint64_t kMaxRangeKeys = 1ull << 27;  // keys in flight per chunk of queries (1 GiB): the generic engine's budget
+constexpr uint32_t kMinRowLog = 11;             // rows of at least 2048 keys (sort_rows_u64)
+
+struct RangeArgs {
+  SelectCommon c;
+  uint32_t q0, m, P, segb0;  // queries [q0, q0 + m) of the batch
+  float radius2;
+  const uint32_t *qoff, *qtot, *rel, *pair_pos, *tile_start;
+  const uint32_t *probes, *gorder, *first_block, *list_len;
+  uint32_t *bound;    // EMIT false: [nq] 16 x (sub-blocks at or below the threshold)
+  uint64_t *keys;     // EMIT true: row (q - q0) of 2^logL keys, preset to ~0
+  uint32_t logL;
+  uint32_t *counts;   // EMIT true: [nq] hits
+  uint32_t *overflow; // EMIT true: raised if a row would not hold its hits (the two passes disagree: never)
+};
+
+// exact reference distance of one (query, stored vector) pair per live lane, in the form exact_offer (select.hip) takes
+// for the same index and query: 0 the f32 blocks, 1 the natural-order hi plane of bf16-exact lists, 2 one byte per
+// dimension, 3 bytes against an integer-valued query.  A real function: its four loops inlined at every place the queue
+// drains would be most of the kernel's code.
+__device__ __attribute__((noinline)) float exact_dist_fn(uint32_t form, const float *qrow, const uint32_t *qbytes, uint32_t qn_int,
+                                                         const uint4 *x, uint32_t dim, bool live) {
+  float d = INFINITY;
+  if (live) {
+    if (form == 3u) d = exact_pair_u8_int(qbytes, qn_int, x, dim);
+    else if (form == 2u) d = exact_pair_u8(qrow, x, dim);
+    else if (form == 1u) d = exact_pair_bf16(qrow, x, dim);
+    else d = exact_pair<kWave>(qrow, (const float4 *)x, dim);
+  }
+  return d;
+}
+
+// One wave per query.  EMIT false: count; EMIT true: evaluate and write keys.  FILT: only vectors whose allow bit is set
+// are evaluated (the rank kernels saw the others with the pad norm, so they sit in no record minimum).
+template <bool EMIT, bool FILT>
+__global__ void __launch_bounds__(256, 4) range_select_kernel(RangeArgs a) {
+  __shared__ uint32_t s_pick[4][kPickCap], s_lcache[4][kCacheG];
+  __shared__ float4 s_tcache[4][kCacheG];
+  __shared__ __attribute__((aligned(16))) uint32_t s_qbytes[4][64];  // the 4 queries as bytes (8-bit lists, D <= 256)
+  extern __shared__ __attribute__((aligned(16))) float s_qrows[];    // the 4 query rows of the workgroup: 4 x dim floats
+  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
+  if (blockIdx.x * 4 + wave >= a.m) return;
+  const uint32_t q = a.q0 + blockIdx.x * 4 + wave;
+  const SelectCommon &c = a.c;
+  uint32_t *pick = s_pick[wave], *lcache = s_lcache[wave], *qbytes = s_qbytes[wave];
+  float4 *tcache = s_tcache[wave];
+  float *qlds = s_qrows + (size_t)wave * c.dim;
+  ProbeRegs pr{0u, 0u, 0u, 0u, 0u, 1u, kNoPos};
+  if ((uint32_t)lane < a.P) {
+    const size_t s = (size_t)q * a.P + lane;
+    const uint32_t mylist = a.probes[s];
+    pr.g = a.gorder[s];
+    pr.rel = a.rel[s];
+    if (mylist != kNoPos) {
+      pr.len = a.list_len[mylist];
+      pr.fb = a.first_block[mylist];
+      const uint32_t pp = a.pair_pos[s];  // where the pair sits among the pairs of its list
+      const uint32_t nseg = list_segments(pr.len, a.segb0, &pr.segb);
+      pr.ng = 2u * nseg;
+      pr.boff = (a.tile_start[mylist] + (pp / c.gq) * nseg * seg_records(pr.segb)) * (2u * c.gq) + (pp % c.gq);
+    }
+  }
+  const size_t gbase = a.qoff[q];
+  const uint32_t G = a.qtot[q];
+  const uint64_t below = (1ull << lane) - 1ull;
+  auto lds_sync = [&]() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  };
+  // ---- the query row, its norm in the records' frame and the margin E: as select_body forms them ----
+  float qn = 0.0f, qres = 0.0f;
+  bool q_bytes = c.u8_nat != nullptr && c.dim <= 256u;  // -> the query is integer-valued in 0..255
+  for (uint32_t e = lane; e < c.dim; e += kWave) {
+    const float v = c.Q[(size_t)q * c.dim + e];
+    if (EMIT) qlds[e] = v;
+    const float vc = c.mu ? v - c.mu[e] : v;
+    qn += vc * vc;
+    const float im = -2.0f * vc, ir = im - __uint_as_float(bf16_rn(im) << 16);
+    qres += ir * ir;
+    q_bytes = q_bytes && v >= 0.0f && v <= 255.0f && v == floorf(v);
+  }
+  q_bytes = __ballot(!q_bytes) == 0ull;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) { qn += __shfl_xor(qn, o); qres += __shfl_xor(qres, o); }
+  uint32_t qn_int = 0u;
+  if (EMIT && q_bytes) {  // the query as bytes, zero padded to whole 16-byte pieces (exact_pair_u8_int), and |q|^2 as an integer
+    const uint32_t nw = ((c.dim + 15u) >> 4) * 4u;
+    for (uint32_t w = lane; w < nw; w += kWave) {
+      uint32_t word = 0u;
+#pragma unroll
+      for (uint32_t b = 0; b < 4; ++b) {
+        const uint32_t e = 4u * w + b;
+        const uint32_t v = e < c.dim ? (uint32_t)c.Q[(size_t)q * c.dim + e] : 0u;
+        word |= v << (8u * b);
+        qn_int += v * v;
+      }
+      qbytes[w] = word;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) qn_int += (uint32_t)__shfl_xor((int)qn_int, o);
+  }
+  float E = c.e_scale * (qn * (1.0f + c.gamma) + 2.0f * c.xmax2) + c.e_abs;
+  if (c.trunc) E += 1.02f * (2.0f * sqrtf(qn) * c.rho_max * (1.0f + 0.00391f) + (c.trunc == 2u ? sqrtf(qres) * c.vmax : 0.0f));
+  // ---- the threshold: known before any record is read.  A query norm the rank arithmetic may have overflowed on, or a
+  //      radius beyond the point where the bound means anything: no bound, everything probed is re-evaluated ----
+  float thr = INFINITY;
+  if (qn < 1.0e30f && a.radius2 < 1.0e37f) {
+    const float w = ((float)(c.dim >> 6) + 9.0f) * 6.1e-8f * (fabsf(a.radius2) + qn);  // 6.1e-8 > u' = 1.01 * 2^-24
+    const float mk = (a.radius2 - qn) + w;
+    const float scale = fmaxf(mk + qn, 0.0f) + E;
+    thr = mk + (2.0f * E + 3.0f * c.gamma * scale) * 1.001f + 1e-30f;
+  }
+  const uint32_t form = c.u8_nat ? (q_bytes ? 3u : 2u) : (c.hi_nat ? 1u : 0u);
+  const uint4 *xbase = c.u8_nat ? c.u8_nat : (c.hi_nat ? c.hi_nat : (const uint4 *)c.blocks);
+  const uint32_t xmult = c.u8_nat ? c.dq / 4u : (c.hi_nat ? c.dq / 2u : c.dq);  // 16-byte pieces per vector
+  uint64_t *row = EMIT ? a.keys + ((size_t)(q - a.q0) << a.logL) : nullptr;
+  const uint32_t cap = EMIT ? 1u << a.logL : 0u;
+  uint32_t npick = 0, n_exact = 0, n_scanned = 0, n_sub = 0, cursor = 0;
+  // one (probe rank, position) per lane: exact distance, and a key at the query's cursor if it is within the radius
+  auto exact_emit = [&](bool live, uint32_t r, uint32_t pos) {
+    const uint32_t fb = (uint32_t)__shfl((int)pr.fb, (int)r);
+    const uint32_t g = (uint32_t)__shfl((int)pr.g, (int)r);
+    const uint32_t len = (uint32_t)__shfl((int)pr.len, (int)r);
+    live = live && pos < len;
+    const uint32_t p = live ? pos : 0u;
+    if constexpr (FILT) live = live && ((c.allow[fb + p / kWave] >> (p % kWave)) & 1ull) != 0ull;
+    n_exact += (uint32_t)__popcll(__ballot(live));
+    const float d = exact_dist_fn(form, qlds, qbytes, qn_int, xbase + ((size_t)(fb + p / kWave) * xmult) * kWave + (p % kWave), c.dim, live);
+    const bool hit = live && d <= a.radius2;
+    const uint64_t m = __ballot(hit);
+    if (hit) {
+      const uint32_t at = cursor + (uint32_t)__popcll(m & below);
+      if (at < cap) row[at] = pack_key(d, (g << kPosBits) | pos);
+    }
+    cursor += (uint32_t)__popcll(m);
+  };
+  // sub-blocks waiting in `pick`: four per round, 16 lanes (= the 16 rows of the sub-block) each
+  auto drain_pick = [&]() {
+    while (npick > 0) {
+      const uint32_t cnt = npick >= 4u ? 4u : npick;
+      npick -= cnt;
+      const uint32_t rq = (uint32_t)lane >> 4;
+      const bool live = rq < cnt;
+      const uint32_t ck = live ? pick[npick + rq] : 0u;
+      const uint32_t r = ck >> (kSubBits + 1), sub = (ck >> 1) & ((1u << kSubBits) - 1u), hh = ck & 1u;
+      exact_emit(live, r, (sub >> 1) * kWave + subblock_vector((uint32_t)lane & 15u, sub & 1u, hh, c.image_order != 0u));
+    }
+  };
+  auto push_sub = [&](bool want, uint32_t r, uint32_t sub, uint32_t hh) {  // every lane calls
+    const uint64_t m = __ballot(want);
+    if (!m) return;
+    const uint32_t cnt = (uint32_t)__popcll(m);
+    n_sub += cnt;
+    if constexpr (EMIT) {
+      if (npick + cnt > kPickCap) drain_pick();
+      if (want) pick[npick + (uint32_t)__popcll(m & below)] = (r << (kSubBits + 1)) | (sub << 1) | hh;
+      npick += cnt;
+      lds_sync();
+    }
+  };
+  // The pair records of the groups flagged `want`, four groups per round (16 lanes x one pair record = the 64 sub-block
+  // minima of a 32-block segment half): every sub-block whose minimum is at or below thr is queued (select_body's
+  // scan_groups in its mode 1)
+  auto scan_groups = [&](bool want, uint32_t r, uint32_t seg, uint32_t hh) {
+    uint64_t m = __ballot(want);
+    const uint32_t slot = (uint32_t)lane >> 4, pi = (uint32_t)lane & 15u;
+    while (m) {
+      int src = 0;
+      uint32_t taken = 0;
+#pragma unroll
+      for (uint32_t i = 0; i < 4; ++i)
+        if (m) {
+          const int b = __builtin_ctzll(m);
+          m &= m - 1ull;
+          if (slot == i) src = b;
+          ++taken;
+        }
+      const bool mine = slot < taken;
+      n_scanned += taken;
+      const uint32_t rr = (uint32_t)__shfl((int)r, src), sg = (uint32_t)__shfl((int)seg, src);
+      const uint32_t h2 = (uint32_t)__shfl((int)hh, src);
+      const uint32_t segb = (uint32_t)__shfl((int)pr.segb, (int)rr), ln = (uint32_t)__shfl((int)pr.len, (int)rr);
+      const uint32_t boff = (uint32_t)__shfl((int)pr.boff, (int)rr);
+      const uint32_t nblk = (ln + kWave - 1) / kWave;
+      const uint32_t bs = sg * segb, be = min(nblk, bs + segb);
+      const uint32_t ntile = be > bs ? 2u * (be - bs) : 0u;
+      const uint32_t npairs = !mine ? 0u : (c.wave_order ? 4u * ((ntile + 15u) / 16u) : (ntile + 3u) / 4u);
+      uint32_t mx = npairs;  // wave maximum: segments of very long lists hold more than 16 records
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) mx = max(mx, (uint32_t)__shfl_xor((int)mx, o));
+      for (uint32_t p0 = 0; p0 < mx; p0 += 16u) {
+        const uint32_t p = p0 + pi;
+        const bool live = p < npairs;
+        float4 B = make_float4(INFINITY, INFINITY, INFINITY, INFINITY);
+        if (live) B = c.brec[(size_t)boff + 2u * c.gq * (sg * seg_records(segb) + p) + c.gq * h2];
+        const float bv[4] = {B.x, B.y, B.z, B.w};
+#pragma unroll
+        for (uint32_t j = 0; j < 4; ++j) {
+          const uint32_t tl = c.wave_order ? 16u * (p >> 2) + 4u * j + (p & 3u) : 4u * p + j;  // tile of the segment
+          const bool ok = live && tl < ntile;  // (a record's unused components, and records no wave wrote, are not read as values)
+          push_sub(ok && !(bv[j] > thr), rr, 2u * bs + tl, h2);  // (!(v > thr): a NaN minimum is expanded, never skipped)
+        }
+      }
+    }
+  };
+  // ---- the first 256 group records go to LDS in one round of loads (select_body's stage 0) ----
+  {
+    float4 t4[kCacheG / kWave];
+    uint32_t l4[kCacheG / kWave];
+#pragma unroll
+    for (uint32_t ch = 0; ch < kCacheG / kWave; ++ch) {
+      const uint32_t gidx = ch * kWave + lane;
+      t4[ch] = make_float4(INFINITY, INFINITY, INFINITY, INFINITY);
+      l4[ch] = 0u;
+      if (gidx < G) {
+        t4[ch] = c.gval[gbase + gidx];
+        l4[ch] = c.gmeta[gbase + gidx];  // probe rank | segment << 6 | lane half << 13
+      }
+    }
+#pragma unroll
+    for (uint32_t ch = 0; ch < kCacheG / kWave; ++ch) {
+      const uint32_t gidx = ch * kWave + lane;
+      if (ch * kWave < G) {
+        tcache[gidx] = t4[ch];
+        lcache[gidx] = l4[ch];
+      }
+    }
+    lds_sync();
+  }
+  // ---- every sub-block whose minimum is at or below thr sits in a group whose smallest minimum is (select_body's stage 2) ----
+  for (uint32_t gb = 0; gb < G; gb += kWave) {
+    const uint32_t gidx = gb + lane;
+    const bool live = gidx < G;
+    float4 T = make_float4(INFINITY, INFINITY, INFINITY, INFINITY);
+    uint32_t L = 0u;
+    if (live) {
+      T = gidx < kCacheG ? tcache[gidx] : c.gval[gbase + gidx];
+      L = gidx < kCacheG ? lcache[gidx] : c.gmeta[gbase + gidx];
+    }
+    scan_groups(live && !(T.x > thr), L & 63u, (L >> 6) & 127u, L >> 13);
+  }
+  if constexpr (EMIT) {
+    drain_pick();
+    if (lane == 0) {
+      a.counts[q] = min(cursor, cap);
+      if (cursor > cap) atomicOr(a.overflow, 1u);
+    }
+    if (c.dbg && lane == 0 && (q & c.dbg_mask) == 0u) {
+      atomicAdd(&c.dbg[kStatSelExact], (unsigned long long)n_exact);
+      atomicAdd(&c.dbg[kStatSelScanned], (unsigned long long)n_scanned);
+      atomicAdd(&c.dbg[kStatSelSubBlocks], (unsigned long long)n_sub);
+    }
+  } else {
+    if (lane == 0) a.bound[q] = 16u * n_sub;
+  }
+}
+
+struct RangeOutArgs {
+  const uint64_t *keys;  // sorted rows of 2^logL keys, row (q - q0)
+  uint32_t logL, q0, m, P;
+  const uint32_t *counts, *probes, *gorder, *first_block;
+  const uint64_t *lims, *ext_ids;
+  float *D;
+  int64_t *I;
+  uint64_t *tie, *slots;
+};
+
+// one wave per query: the first counts[q] keys of its sorted row to D / I / tie / slot at lims[q]; the candidate-order
+// rank g of a key goes back to its probe as in select_kernel's epilogue
+__global__ void __launch_bounds__(256) range_output_kernel(RangeOutArgs a) {
+  __shared__ uint32_t s_fb[4][kWave];
+  const uint32_t lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
+  if (blockIdx.x * 4 + wave >= a.m) return;
+  const uint32_t q = a.q0 + blockIdx.x * 4 + wave;
+  if (lane < a.P) {  // first block of the probe with candidate-order rank g, at s_fb[g] (the ranks of a query's probes are distinct)
+    const uint32_t l = a.probes[(size_t)q * a.P + lane], g = a.gorder[(size_t)q * a.P + lane];
+    if (l != kNoPos && g < kWave) s_fb[wave][g] = a.first_block[l];
+  }
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  const uint64_t *row = a.keys + ((size_t)(q - a.q0) << a.logL);
+  const uint64_t at = a.lims[q];
+  const uint32_t n = a.counts[q];
+  for (uint32_t i = lane; i < n; i += kWave) {
+    const uint64_t key = row[i];
+    const uint32_t t = (uint32_t)key, g = t >> kPosBits, pos = t & kPosMask;
+    const uint64_t gslot = (uint64_t)s_fb[wave][g & 63u] * kWave + pos;
+    a.D[at + i] = sortable_f32((uint32_t)(key >> 32));
+    a.I[at + i] = (int64_t)a.ext_ids[gslot];
+    a.tie[at + i] = ((uint64_t)g << 32) | pos;
+    a.slots[at + i] = gslot;
+  }
+}
+
+}  // namespace
+
+vi_status launch_range_select(const DeviceIndex &ix, const EngineKnobs &kn, const float *Qd, uint64_t nq, uint32_t P, float radius2,
+                              const SelectFrame &f, const SlotFilter *flt, RangeResult *res, hipStream_t st) {
+  SearchWorkspace &ws = ix.cur().ws;
+  VI_TRY(ws.range_bound.reserve(nq + 1));  // (the last word: the overflow flag)
+  VI_TRY(ws.counts.reserve(nq));
+  RangeArgs a{list_select_common(ix, kn, Qd, f), 0u, (uint32_t)nq, P, kn.segb0, radius2, ws.qoff.p, ws.qtot.p, ws.pair_rel.p, ws.pair_pos.p,
+              ws.tile_start.p, ws.probes.p, ws.gorder.p, ix.list_first_block.p, ix.list_len.p, ws.range_bound.p, nullptr, 0u, ws.counts.p,
+              ws.range_bound.p + nq};
+  if (flt) a.c.allow = flt->allow.p;
+  unsigned long long *dbg = a.c.dbg;
+  const size_t qsm = 4ull * ix.dim * sizeof(float);
+  // (VI_FILTER_STATS=3 / 4) the steps' own clocks, printed like the select's: events of this call's, each read after a
+  // synchronisation the step makes anyway
+  hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  struct EventGuard { hipEvent_t *e; ~EventGuard() { for (int i = 0; i < 5; ++i) if (e[i]) (void)hipEventDestroy(e[i]); } } guard{ev};
+  float ms_step[4] = {0.0f, 0.0f, 0.0f, 0.0f};  // bound pass, evaluation, sort, placing + output
+  auto mark = [&](int i) -> vi_status {
+    if (!kn.stats_print) return VI_OK;
+    if (!ev[i]) VI_HIP(hipEventCreate(&ev[i]));
+    VI_HIP(hipEventRecord(ev[i], st));
+    return VI_OK;
+  };
+  auto lap = [&](int step, int from, int to) {
+    float ms = 0.0f;
+    if (kn.stats_print && hipEventElapsedTime(&ms, ev[from], ev[to]) == hipSuccess) ms_step[step] += ms;
+  };
+  // ---- 1. the bound pass: 16 x (sub-blocks at or below the threshold) per query ----
+  a.c.dbg = nullptr;
+  VI_HIP(hipMemsetAsync(ws.range_bound.p + nq, 0, sizeof(uint32_t), st));
+  VI_TRY(mark(0));
+  hipLaunchKernelGGL((range_select_kernel<false, false>), dim3((uint32_t)((nq + 3) / 4)), dim3(256), qsm, st, a);
+  VI_HIP(hipGetLastError());
+  VI_TRY(mark(1));
+  std::vector<uint32_t> h_bound(nq);
+  VI_HIP(hipMemcpyAsync(h_bound.data(), ws.range_bound.p, nq * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  VI_HIP(hipStreamSynchronize(st));
+  lap(0, 0, 1);
+  a.c.dbg = dbg;
+  // ---- 2. per chunk of queries whose rows fit the key budget: evaluate, sort, place, write ----
+  uint64_t q0 = 0;
+  while (q0 < nq) {
+    uint32_t logL = kMinRowLog;
+    while ((1ull << logL) < h_bound[q0]) ++logL;
+    if ((1ull << logL) > kMaxRangeKeys) return fail(VI_ERR_INVALID_INPUT, "a query's radius admits more candidates than the key scratch holds");
+    uint64_t m = 1;
+    while (q0 + m < nq) {  // grow the chunk while rows x row-length stays within the key budget
+      uint32_t lg = logL;
+      while ((1ull << lg) < h_bound[q0 + m]) ++lg;
+      if ((m + 1) << lg > kMaxRangeKeys) break;
+      logL = lg;
+      ++m;
+    }
+    const uint64_t L = 1ull << logL;
+    VI_TRY(ws.sort_keys.reserve(m * L));
+    VI_TRY(mark(0));
+    VI_HIP(hipMemsetAsync(ws.sort_keys.p, 0xFF, m * L * sizeof(uint64_t), st));
+    a.q0 = (uint32_t)q0; a.m = (uint32_t)m; a.keys = ws.sort_keys.p; a.logL = logL;
+    const dim3 grid((uint32_t)((m + 3) / 4));
+    if (flt) hipLaunchKernelGGL((range_select_kernel<true, true>), grid, dim3(256), qsm, st, a);
+    else hipLaunchKernelGGL((range_select_kernel<true, false>), grid, dim3(256), qsm, st, a);
+    VI_HIP(hipGetLastError());
+    VI_TRY(mark(1));
+    VI_TRY(sort_rows_u64(ws.sort_keys.p, m, logL, st));
+    VI_TRY(mark(2));
+    VI_TRY(range_result_place(res, q0, m, ws.counts.p + q0, st));
+    RangeOutArgs o{ws.sort_keys.p, logL, (uint32_t)q0, (uint32_t)m, P, ws.counts.p, ws.probes.p, ws.gorder.p, ix.list_first_block.p,
+                   res->lims.p, ix.ext_ids.p, res->D.p, res->I.p, res->tie.p, res->slots.p};
+    hipLaunchKernelGGL(range_output_kernel, grid, dim3(256), 0, st, o);
+    VI_HIP(hipGetLastError());
+    VI_TRY(mark(3));
+    if (kn.stats_print) {
+      VI_HIP(hipStreamSynchronize(st));
+      lap(1, 0, 1); lap(2, 1, 2); lap(3, 2, 3);
+    }
+    q0 += m;
+  }
+  uint32_t overflow = 0;
+  VI_HIP(hipMemcpyAsync(&overflow, ws.range_bound.p + nq, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  VI_HIP(hipStreamSynchronize(st));
+  if (kn.stats_print) {
+    uint64_t bound_total = 0;
+    for (uint32_t b : h_bound) bound_total += b;
+    fprintf(stderr, "range select ms: bound pass %.4f, evaluation %.4f, sort %.4f, placing + output %.4f; hits %llu of a bound of %llu\n",
+            ms_step[0], ms_step[1], ms_step[2], ms_step[3], (unsigned long long)res->total, (unsigned long long)bound_total);
+  }
+  if (overflow) return fail(VI_ERR_OTHER, "radius select: a query found more hits than its bound pass counted");
+  return VI_OK;
+}
+
+}  // namespace vi

@@ -1,5 +1,5 @@
 // search_internal.hpp — what the search engines' translation units (search_kernels.hip, generic_search.hip,
-// filter_search.hip, select.hip, rank_images.hip, list_build.hip) call in each other and share: declared once, here.
+// filter_search.hip, select.hip, range_select.hip, rank_images.hip, list_build.hip) call in each other and share: declared once, here.
 // (filter_search.hip launches its rank and select phases through headers of their own: rank_stream.hpp, select.hpp)
 #pragma once
 #include <array>
@@ -56,7 +56,15 @@ vi_status launch_grouping(const DeviceIndex &ix, const uint32_t *probes, uint64_
                           GroupingCounts &hstats, hipStream_t st, bool histogram_done, const uint32_t *qtot = nullptr,
                           uint32_t *qoff = nullptr, const uint32_t *pair_rank = nullptr);
 
+// a radius search's result as the engines fill it, chunk of queries after chunk: range_result_begin sizes lims;
+// range_result_place reads the hit counts of queries [q0, q0 + m) back (it synchronises), extends lims by them on the
+// host and the device and grows D / I / tie / slots to hold them, keeping what earlier chunks wrote
+vi_status range_result_begin(const DeviceIndex &ix, uint64_t nq, RangeResult *res);
+vi_status range_result_place(RangeResult *res, uint64_t q0, uint64_t m, const uint32_t *counts_dev, hipStream_t st);
+
 // ---- filter_search.hip ----
+vi_status range_filter_pipeline(const DeviceIndex &ix, const EngineKnobs &kn, const float *Qd, uint64_t nq, float radius2, uint32_t P,
+                                RangeResult *res, hipStream_t st, int timing_level, const SlotFilter *flt);
 vi_status search_filter_pipeline(const DeviceIndex &ix, const EngineKnobs &kn, const float *Qd, uint64_t nq, uint64_t k, uint32_t P,
                                  float *Dd, int64_t *Id, uint64_t *Td, uint64_t *slots, uint32_t *counts, hipStream_t st,
                                  int timing_level, const uint32_t *probes_in, const uint32_t *order_in, const SlotFilter *flt);
@@ -68,6 +76,8 @@ bool coarse_on_matrix_cores(const DeviceIndex &ix, const EngineKnobs &kn, uint64
 vi_status device_index_search_generic(const DeviceIndex &ix, const float *Qd, uint64_t nq, uint64_t k, uint32_t P,
                                       float *Dd, int64_t *Id, uint64_t *Td, uint64_t *slots, uint32_t *counts,
                                       hipStream_t st, const uint32_t *probes_in, const uint32_t *order_in, const SlotFilter *flt);
+vi_status device_index_range_generic(const DeviceIndex &ix, const float *Qd, uint64_t nq, float radius2, uint32_t P, RangeResult *res,
+                                     hipStream_t st, const SlotFilter *flt);
 vi_status generic_probe_export(const DeviceIndex &ix, const float *Qd, uint64_t nq, uint32_t P, hipStream_t st);
 
 // ---- rank_images.hip ----

@@ -1520,6 +1520,122 @@ vi_status device_index_search(const DeviceIndex &ix, const SearchIO &io) {
   return VI_OK;
 }
 
+// ------------------------------------------------------------------------------------------
+// radius search
+// ------------------------------------------------------------------------------------------
+vi_status range_result_begin(const DeviceIndex &ix, uint64_t nq, RangeResult *res) {
+  res->ix = &ix;
+  res->nq = nq;
+  res->total = 0;
+  res->h_lims.assign(nq + 1, 0);
+  return res->lims.reserve(nq + 1);  // (written by range_result_place: every call fills it from its first query on)
+}
+
+namespace {
+// a result buffer grown to `cap` entries with its first `used` kept
+template <typename T>
+vi_status grow_keeping(DevBuf<T> &b, uint64_t used, uint64_t cap, hipStream_t st) {
+  DevBuf<T> bigger;
+  VI_TRY(bigger.reserve(cap));
+  if (used) VI_HIP(hipMemcpyAsync(bigger.p, b.p, used * sizeof(T), hipMemcpyDeviceToDevice, st));
+  VI_HIP(hipStreamSynchronize(st));
+  std::swap(b.p, bigger.p);
+  std::swap(b.n, bigger.n);
+  return VI_OK;
+}
+}  // namespace
+
+vi_status range_result_place(RangeResult *res, uint64_t q0, uint64_t m, const uint32_t *counts_dev, hipStream_t st) {
+  std::vector<uint32_t> h(m);
+  if (m) {
+    VI_HIP(hipMemcpyAsync(h.data(), counts_dev, m * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    VI_HIP(hipStreamSynchronize(st));
+  }
+  for (uint64_t i = 0; i < m; ++i) res->h_lims[q0 + i + 1] = res->h_lims[q0 + i] + h[i];
+  const uint64_t total = res->h_lims[q0 + m];
+  for (uint64_t q = q0 + m; q < res->nq; ++q) res->h_lims[q + 1] = total;  // (queries still to come: empty so far)
+  if (total > res->cap || !res->D.p) {
+    // (one chunk — the rule — allocates exactly; a further chunk at least doubles)
+    const uint64_t cap = std::max<uint64_t>(1, res->cap ? std::max(total, 2 * res->cap) : total);
+    VI_TRY(grow_keeping(res->D, res->total, cap, st));
+    VI_TRY(grow_keeping(res->I, res->total, cap, st));
+    VI_TRY(grow_keeping(res->tie, res->total, cap, st));
+    VI_TRY(grow_keeping(res->slots, res->total, cap, st));
+    res->cap = cap;
+  }
+  res->total = total;
+  VI_HIP(hipMemcpyAsync(res->lims.p + q0, res->h_lims.data() + q0, (res->nq + 1 - q0) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+  return VI_OK;
+}
+
+vi_status device_index_range_search(const DeviceIndex &ix, const RangeIO &io, RangeResult *out) {
+  VI_HIP(hipSetDevice(ix.device));
+  ContextLease lease(ix);
+  VI_TRY(lease.acquire());
+  hipStream_t st = ix.cur().stream;
+  SearchWorkspace &ws = ix.cur().ws;
+  const uint64_t nq = io.nq, nlists = ix.nlists;
+  const SlotFilter *flt = io.filter;
+  if (flt && flt->owner_serial != ix.serial) return fail(VI_ERR_INVALID_INPUT, "the filter was made for another index");
+  if (nq * 64 > 0x7FFFFFFFull) return fail(VI_ERR_INVALID_INPUT, "batch too large: split nq");
+  VI_TRY(range_result_begin(ix, nq, out));
+  const uint32_t P = (uint32_t)std::min<uint64_t>(io.n_probe, nlists);  // take(n_probe) (ivf_index.rs:216-220)
+  vi_search_stats &stt = ix.cur().stats;
+  stt = vi_search_stats{};
+  stt.nq = nq; stt.k = 0; stt.n_probe_eff = P; stt.coarse_candidates = nq * nlists;
+  // nothing to find: no query, an empty index, or a radius no squared distance is within
+  if (nq == 0 || P == 0 || nlists == 0 || io.radius2 < 0.0f) return range_result_place(out, 0, 0, nullptr, st);
+  const EngineKnobs kn = read_engine_knobs();
+  const float *Qd = io.queries;
+  if (!io.on_device) {
+    VI_TRY(ws.q.reserve(nq * ix.dim));
+    VI_HIP(hipMemcpyAsync(ws.q.p, io.queries, nq * ix.dim * sizeof(float), hipMemcpyHostToDevice, st));
+    Qd = ws.q.p;
+  }
+  VI_TRY(ws.stats.reserve(kStatWords));
+  // the MFMA engine has no k to limit it; everything else (D % 4 != 0, D > 1536, n_probe > 64, VI_FILTER=0) sorts every candidate
+  const bool mfma = !kn.force_generic && filter_path_applicable(ix, kn, 1, P);
+  const int timing = mfma ? ix.timing : 0;
+  if (mfma) VI_TRY(range_filter_pipeline(ix, kn, Qd, nq, io.radius2, P, out, st, timing, flt));
+  else VI_TRY(device_index_range_generic(ix, Qd, nq, io.radius2, P, out, st, flt));
+  if (ix.stripe_world > 1 && out->total) {
+    hipLaunchKernelGGL(stripe_tie_kernel, dim3((uint32_t)((out->total + 255) / 256)), dim3(256), 0, st, out->tie.p, out->total,
+                       ix.stripe_rank, ix.stripe_world);
+    VI_HIP(hipGetLastError());
+  }
+  VI_HIP(hipStreamSynchronize(st));
+  if (timing) (void)hipEventElapsedTime(&stt.ms_scan, ix.cur().ev[2], ix.cur().ev[3]);
+  if (timing == 1) {
+    (void)hipEventElapsedTime(&stt.ms_coarse, ix.cur().ev[0], ix.cur().ev[1]);
+    (void)hipEventElapsedTime(&stt.ms_group, ix.cur().ev[1], ix.cur().ev[2]);
+    (void)hipEventElapsedTime(&stt.ms_merge, ix.cur().ev[3], ix.cur().ev[4]);
+    (void)hipEventElapsedTime(&stt.ms_total, ix.cur().ev[0], ix.cur().ev[4]);
+  }
+  return VI_OK;
+}
+
+vi_status range_result_copy(const RangeResult &r, uint64_t *lims, float *D, int64_t *I, float *V) {
+  if (lims) std::memcpy(lims, r.h_lims.data(), (r.nq + 1) * sizeof(uint64_t));
+  if (r.total == 0) return VI_OK;
+  VI_HIP(hipSetDevice(r.ix->device));
+  if (D) VI_HIP(hipMemcpy(D, r.D.p, r.total * sizeof(float), hipMemcpyDeviceToHost));
+  if (I) VI_HIP(hipMemcpy(I, r.I.p, r.total * sizeof(int64_t), hipMemcpyDeviceToHost));
+  if (V) {
+    const uint32_t dim = r.ix->dim;
+    DevBuf<float> Vd;
+    const uint64_t step = std::max<uint64_t>(1, std::min<uint64_t>(r.total, (1ull << 28) / dim));  // <= 1 GiB of rows at a time
+    VI_TRY(Vd.reserve(step * dim));
+    for (uint64_t at = 0; at < r.total; at += step) {
+      const uint64_t n = std::min(step, r.total - at);
+      hipLaunchKernelGGL(gather_vectors_kernel, dim3((uint32_t)n), dim3(64), 0, nullptr, r.ix->lists.blocks.p, r.ix->dq, dim,
+                         r.slots.p + at, n, Vd.p);
+      VI_HIP(hipGetLastError());
+      VI_HIP(hipMemcpy(V + at * dim, Vd.p, n * dim * sizeof(float), hipMemcpyDeviceToHost));
+    }
+  }
+  return VI_OK;
+}
+
 // Counting sort of nq*P (query, probe) pairs by list for the generic path (the fast path folds
 // the histogram into coarse_merge_kernel).  Fills ws.{cnt,seg_start,item_start,segrun_start,pairs}.
 vi_status launch_grouping(const DeviceIndex &ix, const uint32_t *probes, uint64_t nq, uint32_t P, int qg, uint32_t segb0,

@@ -1,4 +1,4 @@
-// select.hpp — the select phase of the MFMA engine (select.hip) as filter_search.hip's pipeline launches it, and the
+// select.hpp — the select phase of the MFMA engine (select.hip, range_select.hip) as filter_search.hip's pipelines launch it, and the
 // constants both sides must agree on.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -34,6 +34,11 @@ struct SelectOutputs {
 // four select_kernel instantiations (k <= 64 or <= 128; with or without the allow words of flt).
 vi_status launch_list_select(const DeviceIndex &ix, const EngineKnobs &kn, const float *Qd, uint64_t nq, uint32_t P, uint64_t k,
                              const SelectFrame &f, const SelectOutputs &out, const SlotFilter *flt, hipStream_t st);
+
+// radius select (range_select.hip): one wave per query, every probed vector whose reference distance is <= radius2, in
+// the reference's stable order, appended to res query chunk by query chunk (search_internal.hpp: range_result_place)
+vi_status launch_range_select(const DeviceIndex &ix, const EngineKnobs &kn, const float *Qd, uint64_t nq, uint32_t P, float radius2,
+                              const SelectFrame &f, const SlotFilter *flt, RangeResult *res, hipStream_t st);
 
 // coarse select: from the table's records (segments of segb blocks, recs group records per query; direct: the direct
 // records of a table of <= kDirectBlocks blocks) to ws.probes / gorder, the per-list histogram with ws.pair_rank, and

@@ -24,7 +24,7 @@ import numpy as np
 from . import _native
 from ._native import (ViError, lib, VI_ASSIGN_EXACT, VI_ASSIGN_REFERENCE, VI_ORDER_LANES, VI_ORDER_SCALAR)
 
-__all__ = ["build", "load", "suggest_nlist", "VectorIndex", "TimestampFilter", "ViError", "kmeans_mini_batch", "kmeans_parallel",
+__all__ = ["build", "load", "suggest_nlist", "VectorIndex", "TimestampFilter", "RangeResult", "ViError", "kmeans_mini_batch", "kmeans_parallel",
            "assign", "l2sq_pairs", "VI_ASSIGN_EXACT", "VI_ASSIGN_REFERENCE", "VI_ORDER_LANES", "VI_ORDER_SCALAR"]
 
 
@@ -54,6 +54,41 @@ class TimestampFilter:
     def num_allowed(self) -> int:
         """resident vectors inside the window"""
         return int(lib().vi_filter_num_allowed(self._h))
+
+
+class RangeResult:
+    """A radius search's result left on the device (VectorIndex.range_search_device), CSR like Faiss's RangeSearchResult:
+    query q owns entries [lims[q], lims[q + 1]) of D / I / tie.  The four pointers are device addresses of buffers this
+    object owns; they stay valid through later searches of the index, until free() (or the object's end).  Keeps its
+    index alive."""
+
+    def __init__(self, index, handle, nq):
+        self._index = index  # (the native result must be freed before its indexer)
+        self._h = handle
+        self.nq = int(nq)
+        self.total = int(lib().vi_range_result_total(handle))
+        p = [C.c_void_p() for _ in range(4)]
+        _native.check(lib().vi_range_result_device(handle, *[C.byref(x) for x in p]))
+        self.lims_ptr, self.D_ptr, self.I_ptr, self.tie_ptr = [x.value or 0 for x in p]
+
+    def copy(self, include_vectors=False):
+        """(lims u64[nq + 1], D f32[total], I i64[total][, V f32[total, dim]]) on the host"""
+        lims = np.zeros(self.nq + 1, dtype=np.uint64)
+        D, I = np.zeros(self.total, dtype=np.float32), np.zeros(self.total, dtype=np.int64)
+        V = np.zeros((self.total, self._index.dimension), dtype=np.float32) if include_vectors else None
+        _native.check(lib().vi_range_result_copy(self._h, _native.ptr(lims), _native.ptr(D), _native.ptr(I), _native.ptr(V)))
+        return (lims, D, I, V) if include_vectors else (lims, D, I)
+
+    def free(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h and lib is not None:
+            try:
+                lib().vi_range_result_free(h)
+            except Exception:
+                pass
+        self.lims_ptr = self.D_ptr = self.I_ptr = self.tie_ptr = 0
+
+    __del__ = free
 
 
 def _filter_handle(f):
@@ -130,6 +165,31 @@ class VectorIndex:
             I2[:, :kk] = I.reshape(-1)[: nq * kk].reshape(nq, kk)
             D, I = D2, I2
         return (D, I, V) if include_vectors else (D, I)
+
+    def range_search_sync(self, xq, radius2: float, n_probe: int, include_vectors: bool = False,
+                          filter: Optional[TimestampFilter] = None):
+        """extension: every probed candidate with squared distance <= radius2, per query in the reference's stable order ->
+        (lims u64[nq + 1], D f32[total], I i64[total][, V f32[total, dim]]); query q owns [lims[q], lims[q + 1])"""
+        xq = np.asarray(xq)
+        if xq.ndim != 2:
+            raise RuntimeError("Query array must be 2-dimensional")
+        xq = np.ascontiguousarray(xq, dtype=np.float32)
+        h = C.c_void_p()
+        _native.check(lib().vi_indexer_range_search(self._h, _filter_handle(filter), _native.ptr(xq), xq.shape[0], xq.shape[1],
+                                                    float(radius2), int(n_probe), C.byref(h)))
+        res = RangeResult(self, h, xq.shape[0])
+        try:
+            return res.copy(include_vectors)
+        finally:
+            res.free()
+
+    def range_search_device(self, xq_ptr: int, nq: int, radius2: float, n_probe: int,
+                            filter: Optional[TimestampFilter] = None) -> RangeResult:
+        """... for nq queries in device memory; the result stays there (RangeResult)"""
+        h = C.c_void_p()
+        _native.check(lib().vi_indexer_range_search_device(self._h, _filter_handle(filter), C.c_void_p(xq_ptr), int(nq),
+                                                           float(radius2), int(n_probe), C.byref(h)))
+        return RangeResult(self, h, nq)
 
     async def search(self, xq, k: int, n_probe: int) -> Tuple[np.ndarray, np.ndarray]:
         loop = asyncio.get_event_loop()

@@ -98,6 +98,12 @@ SIGNATURES = {
     "vi_indexer_search_filtered": (C.c_int, [vp, vp, vp, u64, u32, u64, u64, vp, vp, vp, vp, C.POINTER(u64)]),
     "vi_indexer_search_filtered_device": (C.c_int, [vp, vp, vp, u64, u64, u64, vp, vp, vp]),
     "vi_indexer_search_probed_filtered_device": (C.c_int, [vp, vp, vp, u64, u64, u64, vp, vp, vp, vp, vp]),
+    "vi_indexer_range_search": (C.c_int, [vp, vp, vp, u64, u32, f32, u64, C.POINTER(vp)]),
+    "vi_indexer_range_search_device": (C.c_int, [vp, vp, vp, u64, f32, u64, C.POINTER(vp)]),
+    "vi_range_result_total": (u64, [vp]),
+    "vi_range_result_copy": (C.c_int, [vp, vp, vp, vp, vp]),
+    "vi_range_result_device": (C.c_int, [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]),
+    "vi_range_result_free": (None, [vp]),
     "vi_merge_partials_device": (C.c_int, [i32, u64, u64, u32, vp, vp, vp, vp, vp]),
     "vi_packed_result_bytes": (u64, [u64, u64]),
     "vi_merge_partials_packed_device": (C.c_int, [i32, u64, u64, u32, vp, vp, vp]),

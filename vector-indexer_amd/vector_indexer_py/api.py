@@ -6,6 +6,7 @@
     SearchResult(external_id, distance, vector)                                    api.rs:89-94
     VectorIndexer.new(cfg) / .load(cfg) / .build_from_records / .build_from_vector_file /
     .search(req) / .search_request(query) / .config()                             api.rs:101-237
+    .range_search(query, radius2, ...)                                            extension: everything within a radius
 
 Errors are ViError (a RuntimeError) whose .kind is the io::ErrorKind name the reference returns.
 """
@@ -173,6 +174,25 @@ class VectorIndexer:
                                                        _native.ptr(V), _native.ptr(cnt), C.byref(kout)))
         return [SearchResult(int(I[0, j]), float(D[0, j]), V[0, j].tolist() if V is not None else None)
                 for j in range(int(cnt[0]))]
+
+    def range_search(self, query, radius2: float, n_probe: Optional[int] = None, include_vectors: bool = False,
+                     timestamp_range: Optional[Tuple[int, int]] = None) -> List[SearchResult]:
+        """extension: every record of the probed lists within squared distance radius2 of the query, nearest first (the
+        reference's stable order); n_probe None: the config's default_n_probe"""
+        q = np.ascontiguousarray(np.asarray(query, dtype=np.float32).reshape(1, -1))
+        p = self._cfg.default_n_probe if n_probe is None else int(n_probe)
+        h = C.c_void_p()
+        _native.check(lib().vi_indexer_range_search(self._h, self._filter(timestamp_range), _native.ptr(q), 1, q.shape[1],
+                                                    float(radius2), p, C.byref(h)))
+        try:
+            n = int(lib().vi_range_result_total(h))
+            lims = np.zeros(2, dtype=np.uint64)
+            D, I = np.zeros(n, dtype=np.float32), np.zeros(n, dtype=np.int64)
+            V = np.zeros((n, self._cfg.dimension), dtype=np.float32) if include_vectors else None
+            _native.check(lib().vi_range_result_copy(h, _native.ptr(lims), _native.ptr(D), _native.ptr(I), _native.ptr(V)))
+        finally:
+            lib().vi_range_result_free(h)
+        return [SearchResult(int(I[j]), float(D[j]), V[j].tolist() if V is not None else None) for j in range(n)]
 
     def search_request(self, query) -> SearchRequest:
         return SearchRequest(list(query), False, self._cfg.default_k, self._cfg.default_n_probe)

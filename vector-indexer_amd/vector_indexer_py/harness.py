@@ -118,7 +118,7 @@ def synthetic_dataset(n: int, d: int, nq: int, k: int, seed: int = 42) -> Tuple[
 
 # ---- the adapter + eval loop --------------------------------------------------------------------------------------
 class FaissStyleAdapter:
-    """the Faiss-looking face of an index: .d, .nprobe (settable), .search(xq, k) -> (D, I)
+    """the Faiss-looking face of an index: .d, .nprobe (settable), .search(xq, k) -> (D, I), .range_search(x, thresh)
     (vector_indexer_adapter.py:75-140; the reference hops through an asyncio thread, the search here is synchronous)"""
 
     def __init__(self, vector_index, k: int = 100):
@@ -138,6 +138,11 @@ class FaissStyleAdapter:
 
     def search(self, xq: np.ndarray, k: int):
         return self._idx.search_sync(np.ascontiguousarray(xq, dtype=np.float32), k, self._nprobe)
+
+    def range_search(self, x: np.ndarray, thresh: float):
+        """Faiss's Index.range_search: (lims, D, I) — query i owns D / I[lims[i]:lims[i + 1]], squared L2 <= thresh, among
+        the nprobe probed lists"""
+        return self._idx.range_search_sync(np.ascontiguousarray(x, dtype=np.float32), float(thresh), self._nprobe)
 
     def __repr__(self):
         return f"FaissStyleAdapter(d={self.d}, nprobe={self.nprobe})"
