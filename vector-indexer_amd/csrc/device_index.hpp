@@ -72,7 +72,7 @@ struct SearchWorkspace {
   DevBuf<uint32_t> item_list;               // list of each rank work item
   DevBuf<uint32_t> items;                   // ... or its whole descriptor (8 words), item_desc_kernel
   DevBuf<uint64_t> prof;                    // diagnostic counters (VI_STREAM_PROF)
-  DevBuf<uint32_t> item_qcol, item_grec, item_sdesc;    // streaming rank kernel: per (item, column) the query / its group record (item_cols_kernel)
+  DevBuf<uint32_t> item_qcol, item_grec, item_sdesc;    // streaming rank kernel: per (item, column) the query / its group record (item_cols_kernel, item_push_kernel)
   DevBuf<uint32_t> tile_start, pair_pos;    // pair records: first record tile of each list; position of a (query, probe) pair in its list
   DevBuf<float> gval;                       // group records: 4 smallest sub-block minima per (query, probe, segment, lane half)
   DevBuf<uint32_t> gpos;                    // ... and where each record belongs (probe rank | segment | lane half)
@@ -230,6 +230,7 @@ struct EngineKnobs {
   bool stream_gq256;        // VI_STREAM_GQ=256: streaming groups of 256 bf16-exact queries
   bool rank_i8;             // VI_RANK_I8=0: rank 8-bit descriptors with bf16
   uint32_t item_run;        // VI_ITEM_RUN: work items of one tile stream dealt to one XCD in a row
+  bool item_push;           // VI_ITEM_PUSH=0: the work items' columns by kernels of their own behind the scatter
   bool stream_prof;         // VI_STREAM_PROF: clock the streaming rank kernel
   const char *stream_prof_dump;  // VI_STREAM_PROF_DUMP: file for its per-workgroup clocks, or null
   uint32_t filter_xmode;    // VI_FILTER_XMODE: rank kernel ablations

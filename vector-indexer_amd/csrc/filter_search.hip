@@ -148,6 +148,99 @@ __global__ void item_cols_kernel(const uint4 *items, const uint32_t *pairs, cons
   }
 }
 
+// The scatter and both kernels above in one launch, for the streaming rank kernel (VI_ITEM_PUSH=0: the chain above).
+// Every (query, probe) pair knows its list, and with the list its work items: the thread that places the pair among the
+// pairs of its list writes the pair's column of every item it sits in itself, instead of leaving `pairs` behind for
+// item_desc_kernel (a 12-step binary search per item for the list) and item_cols_kernel (items -> pairs -> qoff / rel,
+// three dependent loads) to find it again.  What a list owns rather than a pair — the items' descriptors, and the dead
+// columns behind the last query group of every segment, which the rank kernel reads as ~0 — is written by a wave per
+// probed list: the workgroups behind the pairs' (a giant list's dead columns are no work for one pair's thread).
+// subprefix: a sub-bin's start within the pairs of its list (list_totals_kernel).  The item and record buffers are sized
+// by counts the host reads back while this kernel runs: it is given their capacities as they are and leaves everything
+// but the resets alone when the batch needs more (group_pairs grows them and launches it again).
+struct ItemPushArgs {
+  const uint32_t *probes, *pair_rank, *subprefix, *list_len, *first_block, *seg_start, *item_start, *tile_start, *qoff, *rel;
+  uint32_t total, P, nlists, gq, segb0, run;
+  uint32_t pair_groups;      // workgroups [0, pair_groups): a thread per pair; behind them: a wave per list
+  uint64_t cap_items, cap_records;  // work items the column / descriptor buffers hold, group records gmeta holds
+  uint32_t *pair_pos, *qcol, *grec, *gmeta;
+  uint4 *sdesc;
+  uint64_t *stats;
+};
+
+// workgroup of the rank kernel that takes `item`: the inverse of item_desc_kernel's dealing in runs to the XCDs
+__device__ __forceinline__ uint32_t item_workgroup(uint32_t item, uint32_t run, uint32_t nitems) {
+  if (run <= 1u) return item;
+  const uint32_t span = 8u * run, pow2 = (run & (run - 1u)) == 0u, sh = (uint32_t)__builtin_ctz(run);
+  const uint32_t cycle = pow2 ? item >> (sh + 3u) : item / span;
+  if ((cycle + 1u) * span > nitems) return item;  // (the last, partial cycle keeps its order)
+  const uint32_t in = item - cycle * span, x = pow2 ? in >> sh : in / run;
+  return cycle * span + (in - x * run) * 8u + x;
+}
+
+__global__ void __launch_bounds__(256) item_push_kernel(ItemPushArgs a) {
+  // the rank kernel's work counters and the batch flags of the next batch (their D2H copy is ahead of this kernel)
+  if (blockIdx.x == 0) {
+    if (threadIdx.x < kStatRankWorkCount) a.stats[kStatRankWork + kStatRankWorkStride * threadIdx.x] = 0;
+    if (threadIdx.x == 0) { a.stats[kStatQueryLo] = 0; a.stats[kStatQueryNotI8] = 0; }
+  }
+  // (the pair's own words are asked for ahead of the counts the test below waits for)
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  const bool pair = blockIdx.x < a.pair_groups && i < a.total;
+  const uint32_t l_pair = pair ? a.probes[i] : kNoPos, rank = pair ? a.pair_rank[i] : 0u, rel = pair ? a.rel[i] : 0u;
+  const uint64_t nitems64 = a.stats[kStatItems];
+  if (nitems64 > a.cap_items || a.stats[kStatGroupRecords] > a.cap_records) return;
+  const uint32_t nitems = (uint32_t)nitems64, gq = a.gq;
+  if (blockIdx.x < a.pair_groups) {  // ---- a thread per pair: its place, and its column in the items of its list ----
+    const uint32_t l = l_pair;
+    if (l >= a.nlists) return;
+    const uint32_t len = a.list_len[l];
+    if (len == 0) return;
+    const uint32_t q = div_probes(i, a.P);
+    const uint32_t s0 = a.seg_start[l], cnt = a.seg_start[l + 1] - s0;
+    const uint32_t pp = a.subprefix[subbin_index(l, q & (kSubBins - 1), a.nlists)] + rank;
+    if (pp >= cnt) return;  // (never: the ranks are the histogram's own increments)
+    a.pair_pos[i] = pp;
+    uint32_t segb;
+    const uint32_t nseg = list_segments(len, a.segb0, &segb);
+    // (chunk = pp / gq, by group_chunks' shift for the group widths in use)
+    const uint32_t nchunk = group_chunks(cnt, gq), chunk = group_chunks(pp + 1u, gq) - 1u, col = pp - chunk * gq;
+    const uint32_t g0 = a.qoff[q] + rel, r = i - q * a.P;
+    uint32_t item = a.item_start[l] + chunk;  // segment-major: segment s, chunk c = item_start + s * nchunk + c
+    for (uint32_t s = 0; s < nseg; ++s, item += nchunk) {
+      const size_t o = (size_t)item_workgroup(item, a.run, nitems) * gq + col;
+      const uint32_t g = g0 + 2u * s, place = r | (s << 6);
+      a.qcol[o] = q;
+      a.grec[o] = g;
+      *reinterpret_cast<uint2 *>(a.gmeta + g) = make_uint2(place, place | (1u << 13));  // (g is even: 8-byte aligned)
+    }
+    return;
+  }
+  // ---- a wave per probed list: its items' descriptors, the dead columns of every segment's last query group ----
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t l = (blockIdx.x - a.pair_groups) * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  if (l >= a.nlists) return;
+  const uint32_t s0 = a.seg_start[l], cnt = a.seg_start[l + 1] - s0;
+  if (cnt == 0) return;
+  const uint32_t len = a.list_len[l], fb = a.first_block[l], it0 = a.item_start[l], t0 = a.tile_start[l];
+  uint32_t segb;
+  const uint32_t nseg = list_segments(len, a.segb0, &segb);
+  const uint32_t nchunk = group_chunks(cnt, gq), nblk = (len + 63u) / 64u, srec = seg_records(segb);
+  for (uint32_t k = lane; k < nchunk * nseg; k += 64u) {
+    const uint32_t seg = k / nchunk, chunk = k - seg * nchunk;
+    const uint32_t b0 = seg * segb, b1 = min(nblk, b0 + segb);
+    // queries, first block, tiles, first record tile
+    a.sdesc[item_workgroup(it0 + k, a.run, nitems)] =
+        make_uint4(min(gq, cnt - chunk * gq), fb + b0, 2u * (b1 - b0), t0 + (chunk * nseg + seg) * srec);
+  }
+  const uint32_t last = nchunk - 1u, live = cnt - last * gq;
+  if (live == gq) return;
+  for (uint32_t seg = 0; seg < nseg; ++seg) {
+    const size_t o = (size_t)item_workgroup(it0 + seg * nchunk + last, a.run, nitems) * gq;
+    for (uint32_t col = live + lane; col < gq; col += 64u) { a.qcol[o + col] = ~0u; a.grec[o + col] = ~0u; }
+  }
+}
+
 __global__ void iota_kernel(uint32_t *p, uint32_t n) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) p[i] = i;
@@ -933,6 +1026,30 @@ vi_status coarse_only_filter(const DeviceIndex &ix, const EngineKnobs &kn, const
   return stage_coarse_filter(ix, kn, Qd, nq, P, st);
 }
 
+// the grouping's scatter for the streaming rank kernel (item_push_kernel), with the item and record buffers as they stand
+vi_status launch_item_push(const DeviceIndex &ix, const uint32_t *probes, uint64_t nq, uint32_t P, uint32_t gq, uint32_t segb0,
+                           uint32_t run, const uint32_t *pair_rank, hipStream_t st) {
+  SearchWorkspace &ws = ix.cur().ws;
+  const uint32_t nlists = (uint32_t)ix.nlists, total = (uint32_t)(nq * P);
+  VI_TRY(ws.item_qcol.reserve(1));  // (no null pointers; a first batch finds no room and is pushed again)
+  VI_TRY(ws.item_grec.reserve(1));
+  VI_TRY(ws.item_sdesc.reserve(4));
+  VI_TRY(ws.gpos.reserve(1));
+  ItemPushArgs a{};
+  a.probes = probes; a.pair_rank = pair_rank; a.subprefix = ws.cnt.p + subbin_words(nlists);
+  a.list_len = ix.list_len.p; a.first_block = ix.list_first_block.p; a.seg_start = ws.seg_start.p; a.item_start = ws.item_start.p;
+  a.tile_start = ws.tile_start.p; a.qoff = ws.qoff.p; a.rel = ws.pair_rel.p;
+  a.total = total; a.P = P; a.nlists = nlists; a.gq = gq; a.segb0 = segb0; a.run = run;
+  a.pair_groups = (total + 255u) / 256u;
+  a.cap_items = std::min<uint64_t>(std::min(ws.item_qcol.n, ws.item_grec.n) / gq, ws.item_sdesc.n / 4);
+  a.cap_records = ws.gpos.n;
+  a.pair_pos = ws.pair_pos.p; a.qcol = ws.item_qcol.p; a.grec = ws.item_grec.p; a.gmeta = ws.gpos.p;
+  a.sdesc = (uint4 *)ws.item_sdesc.p; a.stats = ws.stats.p;
+  hipLaunchKernelGGL(item_push_kernel, dim3(std::max(1u, a.pair_groups + (nlists + 3u) / 4u)), dim3(256), 0, st, a);
+  VI_HIP(hipGetLastError());
+  return VI_OK;
+}
+
 // ------------------------------------------------------------------------------------------
 // the steps of search_filter_pipeline, in the order they run on the search stream
 // ------------------------------------------------------------------------------------------
@@ -950,6 +1067,7 @@ struct Batch {
   hipStream_t st;
   bool rank_timing;  // the rank kernel is timed: an event in front of it and one behind
   bool rank_clock_started = false;
+  bool items_pushed = false;  // the grouping's scatter left the streaming rank kernel's work items behind (item_push_kernel)
   SearchWorkspace &ws() const { return ix.cur().ws; }
   // (the phase clock of the rank kernel starts right in front of it: the work-item helper kernels count as grouping)
   vi_status start_rank_clock() {
@@ -1003,12 +1121,14 @@ void note_group_fill(SearchWorkspace &ws, uint64_t nq, uint32_t P, const Groupin
 
 // ---- 2. group all (query, probe) pairs by list; the counts come back (the pipeline's one synchronisation) and with them
 //      the two flags that complete the plan; the record buffers are sized by them ----
-vi_status group_pairs(const Batch &b, RankPlan &plan, GroupingCounts &hstats) {
+vi_status group_pairs(Batch &b, RankPlan &plan, GroupingCounts &hstats) {
   SearchWorkspace &ws = b.ws();
   vi_search_stats &stt = b.ix.cur().stats;
   VI_TRY(ws.qoff.reserve(b.nq + 1));
+  // the streaming kernel's work items come out of the scatter itself when the coarse select left every pair's rank
+  b.items_pushed = b.kn.item_push && plan.kernel == RankKernel::Stream && ws.pair_rank_valid;
   VI_TRY(launch_grouping(b.ix, ws.probes.p, b.nq, b.P, (int)plan.gq, b.kn.segb0, hstats, b.st, true, ws.qtot.p, ws.qoff.p,
-                         ws.pair_rank_valid ? ws.pair_rank.p : nullptr));
+                         ws.pair_rank_valid ? ws.pair_rank.p : nullptr, b.items_pushed ? b.kn.item_run : 0u));
   note_group_fill(ws, b.nq, b.P, hstats);
   ws.queries_hi_only = hstats[kStatQueryLo] == 0;
   complete_rank_plan(plan, b.kn, hstats);
@@ -1018,9 +1138,19 @@ vi_status group_pairs(const Batch &b, RankPlan &plan, GroupingCounts &hstats) {
   const uint64_t nrec = hstats[kStatGroupRecords], nbrec = hstats[kStatRecordTiles] * 2 * plan.gq;  // pair records: 2 x gq per (query group, segment, 2 blocks)
   if (nrec >= (1ull << 31) || nbrec >= (1ull << 32)) return fail(VI_ERR_INVALID_INPUT, "batch too large: split nq");
   VI_TRY(ws.gval.reserve(std::max<uint64_t>(1, nrec) * 4));
-  VI_TRY(ws.gpos.reserve(std::max<uint64_t>(1, nrec)));
   VI_TRY(ws.brec.reserve(std::max<uint64_t>(1, nbrec) * 4));
-  return VI_OK;
+  if (!b.items_pushed) return ws.gpos.reserve(std::max<uint64_t>(1, nrec));
+  // The scatter compared the same counts with the buffers it was given: where they did not fit it wrote nothing — grow
+  // them, by a quarter more than asked so that a slightly larger batch fits, and push again.  (A batch shape's first
+  // search; batches of a steady size never come here.)
+  const uint64_t ncol = hstats[kStatItems] * plan.gq, ndesc = hstats[kStatItems] * 4;
+  if (ncol <= ws.item_qcol.n && ncol <= ws.item_grec.n && ndesc <= ws.item_sdesc.n && nrec <= ws.gpos.n) return VI_OK;
+  auto grow = [](DevBuf<uint32_t> &buf, uint64_t need) { return need <= buf.n ? VI_OK : buf.reserve(need + need / 4); };
+  VI_TRY(grow(ws.item_qcol, ncol));
+  VI_TRY(grow(ws.item_grec, ncol));
+  VI_TRY(grow(ws.item_sdesc, ndesc));
+  VI_TRY(grow(ws.gpos, nrec));
+  return launch_item_push(b.ix, ws.probes.p, b.nq, b.P, plan.gq, b.kn.segb0, b.kn.item_run, ws.pair_rank.p, b.st);
 }
 
 // ---- 3. rank on the matrix cores: one of the three below ----
@@ -1097,11 +1227,11 @@ vi_status rank_stream(Batch &b, const RankPlan &plan, uint32_t nitems) {
   SearchWorkspace &ws = b.ws();
   const DeviceIndex &ix = b.ix;
   const uint32_t gq = plan.gq;
-  VI_TRY(describe_items(b, gq, nitems));
-  VI_TRY(ws.item_qcol.reserve(std::max<uint64_t>(1, (uint64_t)nitems * gq)));
+  if (!b.items_pushed) VI_TRY(describe_items(b, gq, nitems));
+  VI_TRY(ws.item_qcol.reserve(std::max<uint64_t>(1, (uint64_t)nitems * gq)));  // (pushed: sized by group_pairs)
   VI_TRY(ws.item_grec.reserve(std::max<uint64_t>(1, (uint64_t)nitems * gq)));
   VI_TRY(ws.item_sdesc.reserve(std::max<uint64_t>(1, (uint64_t)nitems * 4)));
-  if (nitems) {
+  if (nitems && !b.items_pushed) {
     hipLaunchKernelGGL(item_cols_kernel, dim3(nitems), dim3(128), 0, b.st, (const uint4 *)ws.items.p, ws.pairs.p, ws.qoff.p,
                        ws.pair_rel.p, b.P, gq, ws.item_qcol.p, ws.item_grec.p, (uint4 *)ws.item_sdesc.p, ws.gpos.p, ws.stats.p);
     VI_HIP(hipGetLastError());

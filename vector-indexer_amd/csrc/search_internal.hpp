@@ -31,12 +31,12 @@ enum StatWord {
   kStatSelSubBlocks = 10,
   kStatSelectEnd = 12,
   kStatTiles128 = 12,       // the grouping again: tiles a grouping by 128 queries would have (the fill behind gq_hint)
-  // batch flags: raised by split_queries_kernel, read back with the grouping's counts, reset by item_cols_kernel
+  // batch flags: raised by split_queries_kernel, read back with the grouping's counts, reset by item_cols_kernel / item_push_kernel
   kStatQueryLo = 13,        // some query has a lo plane
   kStatQueryNotI8 = 14,     // some query is no int8 image
   kStatGroupingWords = 15,  // words [0, 15): what the host reads back after the grouping ...
   kStatGroupingLanding = 16,  // ... into a pinned buffer of this many
-  // the streaming rank kernel's work counters: one per XCD queue, 128 bytes apart, reset by item_cols_kernel
+  // the streaming rank kernel's work counters: one per XCD queue, 128 bytes apart, reset by item_cols_kernel / item_push_kernel
   kStatRankWork = 16, kStatRankWorkStride = 16, kStatRankWorkCount = 8,
   // the selects' stage clocks (VI_FILTER_STATS)
   kStatClocks = 150, kStatClockCount = 8,
@@ -54,7 +54,7 @@ vi_status adopt_probes(const DeviceIndex &ix, uint64_t nq, uint32_t P, const uin
                        bool histogram, hipStream_t st);
 vi_status launch_grouping(const DeviceIndex &ix, const uint32_t *probes, uint64_t nq, uint32_t P, int qg, uint32_t segb0,
                           GroupingCounts &hstats, hipStream_t st, bool histogram_done, const uint32_t *qtot = nullptr,
-                          uint32_t *qoff = nullptr, const uint32_t *pair_rank = nullptr);
+                          uint32_t *qoff = nullptr, const uint32_t *pair_rank = nullptr, uint32_t push_run = 0);
 
 // a radius search's result as the engines fill it, chunk of queries after chunk: range_result_begin sizes lims;
 // range_result_place reads the hit counts of queries [q0, q0 + m) back (it synchronises), extends lims by them on the
@@ -63,6 +63,11 @@ vi_status range_result_begin(const DeviceIndex &ix, uint64_t nq, RangeResult *re
 vi_status range_result_place(RangeResult *res, uint64_t q0, uint64_t m, const uint32_t *counts_dev, hipStream_t st);
 
 // ---- filter_search.hip ----
+// the scatter of launch_grouping that also builds the streaming rank kernel's work items (item_push_kernel), dealt to the
+// XCDs in runs of `run`: it writes into the workspace's item and record buffers as they are and nothing when the
+// batch's counts exceed them — the caller compares the counts it reads back, grows the buffers and launches it again
+vi_status launch_item_push(const DeviceIndex &ix, const uint32_t *probes, uint64_t nq, uint32_t P, uint32_t gq, uint32_t segb0,
+                           uint32_t run, const uint32_t *pair_rank, hipStream_t st);
 vi_status range_filter_pipeline(const DeviceIndex &ix, const EngineKnobs &kn, const float *Qd, uint64_t nq, float radius2, uint32_t P,
                                 RangeResult *res, hipStream_t st, int timing_level, const SlotFilter *flt);
 vi_status search_filter_pipeline(const DeviceIndex &ix, const EngineKnobs &kn, const float *Qd, uint64_t nq, uint64_t k, uint32_t P,

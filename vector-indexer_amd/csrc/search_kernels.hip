@@ -369,18 +369,46 @@ __global__ void __launch_bounds__(kBlockThreads) coarse_merge_kernel(CoarseMerge
 //   item_start   Σ ceil(cnt/QG) * nseg      (scan work items)
 //   segrun_start Σ cnt * nseg [nseg > 1]    (segment runs awaiting seg_merge_kernel)
 // and the grouping's counts of ws.stats (StatWord, search_internal.hpp): Σ cnt*len, items, segment runs, ...
-// queries probing every list: the sum of its sub-bin counters (one thread per list: coalesced along each sub-bin row)
+// queries probing every list: the sum of its sub-bin counters.  A workgroup takes 64 lists, a lane per list (coalesced
+// along each sub-bin row), each of its four waves a quarter of the sub-bins; the quarters meet in LDS.  (One thread
+// walking all 32 counters of its list left 16 workgroups on the GPU at 4096 lists, each behind 32 loads of its own.)
 // (also resets the counters group_scan_kernel adds to — the grouping's counts — when `stats` is given: two memset
 // launches less on a path made of 5-microsecond kernels)
-__global__ void list_totals_kernel(const uint32_t *cnt, uint32_t nlists, uint32_t *tot, uint64_t *stats) {
-  const uint32_t l = blockIdx.x * blockDim.x + threadIdx.x;
-  if (stats && l < kStatListCounts + 1) stats[l < kStatListCounts ? l : kStatTiles128] = 0;
-  if (l >= nlists) return;
+// `prefix` (optional): where each sub-bin's pairs start within the pairs of their list, in the layout of the counters —
+// every count is in hand here, and the scatter that builds the work items (item_push_kernel) adds seg_start itself,
+// so no cursor_kernel reads the 32 counters of every list a second time
+constexpr uint32_t kTotalsLists = 64, kTotalsWaves = 4, kTotalsBins = kSubBins / kTotalsWaves;  // per workgroup / per wave
+static_assert(kTotalsBins * kTotalsWaves == kSubBins, "the waves of list_totals_kernel share the sub-bins evenly");
+__global__ void __launch_bounds__(kTotalsLists * kTotalsWaves) list_totals_kernel(const uint32_t *cnt, uint32_t nlists, uint32_t *tot,
+                                                                                  uint64_t *stats, uint32_t *prefix) {
+  __shared__ uint32_t s_part[kTotalsWaves][kTotalsLists];
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  const uint32_t l = blockIdx.x * kTotalsLists + lane;
+  if (stats && blockIdx.x == 0 && threadIdx.x < kStatListCounts + 1) stats[threadIdx.x < kStatListCounts ? threadIdx.x : kStatTiles128] = 0;
   const uint32_t st = subbin_stride(nlists);
-  uint32_t c = 0;
+  uint32_t c[kTotalsBins], sum = 0;
 #pragma unroll
-  for (uint32_t s = 0; s < kSubBins; ++s) c += cnt[s * st + l];
-  tot[l] = c;
+  for (uint32_t u = 0; u < kTotalsBins; ++u) {
+    c[u] = l < nlists ? cnt[(wave * kTotalsBins + u) * st + l] : 0u;
+    sum += c[u];
+  }
+  s_part[wave][lane] = sum;
+  __syncthreads();
+  if (l >= nlists) return;
+  uint32_t run = 0, total = 0;  // the list's pairs in the sub-bins of the waves before this one, in all
+#pragma unroll
+  for (uint32_t w = 0; w < kTotalsWaves; ++w) {
+    const uint32_t v = s_part[w][lane];
+    if (w < wave) run += v;
+    total += v;
+  }
+  if (wave == 0) tot[l] = total;
+  if (!prefix) return;
+#pragma unroll
+  for (uint32_t u = 0; u < kTotalsBins; ++u) {
+    prefix[(wave * kTotalsBins + u) * st + l] = run;
+    run += c[u];
+  }
 }
 
 // where each sub-bin of a list scatters to: its own slice of the list's segment of `pairs`
@@ -1191,20 +1219,24 @@ vi_status device_index_from_rows(int device, int order, uint32_t dim, const floa
 // pipeline stages
 // ------------------------------------------------------------------------------------------
 // histogram (ws.cnt) -> totals -> offsets of the lists in pairs / items / records -> scatter cursors
+// (relative_cursors: each sub-bin's start within its list instead, left by list_totals_kernel — one launch less)
 static vi_status launch_group_scan(const DeviceIndex &ix, uint32_t qg, uint32_t segb0, uint32_t *tile_start, hipStream_t st,
-                                   bool reset_stats = false, const uint32_t *qtot = nullptr, uint32_t nq = 0, uint32_t *qoff = nullptr) {
+                                   bool reset_stats = false, const uint32_t *qtot = nullptr, uint32_t nq = 0, uint32_t *qoff = nullptr,
+                                   bool relative_cursors = false) {
   SearchWorkspace &ws = ix.cur().ws;
   const uint32_t nlists = (uint32_t)ix.nlists;
   VI_TRY(ws.list_tot.reserve(std::max<uint32_t>(1, nlists)));
   const dim3 grid((nlists + 255) / 256), block(256);
-  hipLaunchKernelGGL(list_totals_kernel, grid, block, 0, st, ws.cnt.p, nlists, ws.list_tot.p, reset_stats ? ws.stats.p : nullptr);
+  uint32_t *cursor = ws.cnt.p + subbin_words(nlists);
+  hipLaunchKernelGGL(list_totals_kernel, dim3((nlists + kTotalsLists - 1) / kTotalsLists), dim3(kTotalsLists * kTotalsWaves), 0, st, ws.cnt.p, nlists, ws.list_tot.p, reset_stats ? ws.stats.p : nullptr,
+                     relative_cursors ? cursor : nullptr);
   if (qtot)  // (+ the queries' record offsets: a second workgroup of the same launch)
     hipLaunchKernelGGL(group_prepare_kernel, dim3(2), dim3(1024), 0, st, ws.list_tot.p, ix.list_len.p, nlists, qg, segb0,
                        ws.seg_start.p, ws.item_start.p, ws.segrun_start.p, ws.stats.p, tile_start, qtot, nq, qoff);
   else
     hipLaunchKernelGGL(group_scan_kernel, dim3(1), dim3(1024), 0, st, ws.list_tot.p, ix.list_len.p, nlists, qg, segb0,
                        ws.seg_start.p, ws.item_start.p, ws.segrun_start.p, ws.stats.p, tile_start);
-  hipLaunchKernelGGL(cursor_kernel, grid, block, 0, st, ws.cnt.p, ws.seg_start.p, nlists, ws.cnt.p + subbin_words(nlists));
+  if (!relative_cursors) hipLaunchKernelGGL(cursor_kernel, grid, block, 0, st, ws.cnt.p, ws.seg_start.p, nlists, cursor);
   VI_HIP(hipGetLastError());
   return VI_OK;
 }
@@ -1399,6 +1431,7 @@ EngineKnobs read_engine_knobs() {
   kn.stream_gq256 = num("VI_STREAM_GQ", 0) == 256;
   kn.rank_i8 = on("VI_RANK_I8");
   kn.item_run = (uint32_t)std::min(std::max(num("VI_ITEM_RUN", 8), 1), 256);
+  kn.item_push = on("VI_ITEM_PUSH");
   kn.stream_prof = getenv("VI_STREAM_PROF") != nullptr;
   kn.stream_prof_dump = getenv("VI_STREAM_PROF_DUMP");
   kn.filter_xmode = (uint32_t)num("VI_FILTER_XMODE", 0);
@@ -1640,7 +1673,7 @@ vi_status range_result_copy(const RangeResult &r, uint64_t *lims, float *D, int6
 // the histogram into coarse_merge_kernel).  Fills ws.{cnt,seg_start,item_start,segrun_start,pairs}.
 vi_status launch_grouping(const DeviceIndex &ix, const uint32_t *probes, uint64_t nq, uint32_t P, int qg, uint32_t segb0,
                           GroupingCounts &hstats, hipStream_t st, bool histogram_done, const uint32_t *qtot, uint32_t *qoff,
-                          const uint32_t *pair_rank) {
+                          const uint32_t *pair_rank, uint32_t push_run) {
   SearchWorkspace &ws = ix.cur().ws;
   const uint64_t nlists = ix.nlists;
   const uint32_t total = (uint32_t)(nq * P);
@@ -1658,14 +1691,19 @@ vi_status launch_grouping(const DeviceIndex &ix, const uint32_t *probes, uint64_
     hipLaunchKernelGGL(histogram_kernel, dim3((total + 255) / 256), dim3(256), 0, st, probes, ix.list_len.p,
                        (uint32_t)nlists, total, P, ws.cnt.p);
   }
-  VI_TRY(launch_group_scan(ix, (uint32_t)qg, segb0, ws.tile_start.p, st, true, qtot, (uint32_t)nq, qoff));
+  // (push_run: the scatter builds the streaming rank kernel's work items as well, item_push_kernel — the caller has
+  //  checked what that needs: the pairs' ranks, the histogram, the record offsets)
+  const bool push = push_run != 0 && pair_rank && histogram_done && qtot;
+  VI_TRY(launch_group_scan(ix, (uint32_t)qg, segb0, ws.tile_start.p, st, true, qtot, (uint32_t)nq, qoff, push));
   // the host waits for the counts (grid size, scratch) while the scatter runs
   // (into page-locked memory: a copy to the caller's stack array is staged by the runtime and costs a few microseconds
   // more on the one synchronisation point of the pipeline)
   if (!ws.hstats_pinned) VI_HIP(hipHostMalloc((void **)&ws.hstats_pinned, kStatGroupingLanding * sizeof(uint64_t)));
   VI_HIP(hipMemcpyAsync(ws.hstats_pinned, ws.stats.p, sizeof(GroupingCounts), hipMemcpyDeviceToHost, st));
   VI_HIP(hipEventRecord(ix.cur().ev[5], st));
-  if (pair_rank && histogram_done)
+  if (push)
+    VI_TRY(launch_item_push(ix, probes, nq, P, (uint32_t)qg, segb0, push_run, pair_rank, st));
+  else if (pair_rank && histogram_done)
     hipLaunchKernelGGL(group_scatter_ranked_kernel, dim3((total + 255) / 256), dim3(256), 0, st, probes, ix.list_len.p,
                        (uint32_t)nlists, P, ws.cnt.p + subbin_words(nlists), pair_rank, ws.pairs.p, total, ws.seg_start.p, ws.pair_pos.p);
   else
