@@ -318,6 +318,31 @@ vi_status vi_indexer_search_probed_filtered_device(const vi_indexer *ix, const v
                                                    const uint32_t *probes_dev, const uint32_t *order_dev, float *D_dev,
                                                    int64_t *I_dev, uint64_t *tie_dev);
 
+/* ---- filters by external id: allow and deny sets, and the intersection of two filters (extension; what Faiss calls
+ * IDSelectorBatch / IDSelectorNot) ----
+ * The filtered result of a query is the reference's candidate sequence with some candidates deleted before the stable
+ * sort: VI_IDS_ALLOW deletes the candidates whose external id is NOT in the set, VI_IDS_DENY those whose external id IS
+ * in it (a deny set is how records are "deleted" from an immutable index).  The coarse step, distances, tie keys,
+ * padding and counts are exactly as for the timestamp filter above, so per-rank partial results merge exactly when every
+ * rank filters by the same set.
+ *   - the set needs no order; duplicates are allowed; ids that no resident vector carries are ignored
+ *   - any u64 is a legal id, 0 and UINT64_MAX included
+ *   - n == 0 (ids may be NULL): ALLOW admits nothing (VI_OK, zero results); DENY admits everything and returns bit for
+ *     bit what the unfiltered entry returns
+ *   - a null ix or out, ids == NULL with n > 0, or a mode other than 0 / 1: VI_ERR_INVALID_INPUT, before any device work
+ *   - _device: the n ids are read in place from device memory; the host entry uploads them once
+ *   - on a partitioned handle (world_size > 1) the filter covers the resident slots
+ * vi_filter_intersect: the vectors both a and b admit (for example "this tenant's ids" and "last week").  A null filter,
+ * or a filter of another handle or of a replaced index, is VI_ERR_INVALID_INPUT; a and b stay valid and independent.
+ * The resulting vi_filter is a vi_filter like any other: the three *_filtered* search entries and both radius entries
+ * take it, vi_filter_num_allowed and vi_filter_free apply, and it holds the same device memory as a timestamp filter (the
+ * id set itself is not kept). */
+typedef enum vi_id_mode { VI_IDS_ALLOW = 0, VI_IDS_DENY = 1 } vi_id_mode;
+vi_status vi_indexer_filter_ids(const vi_indexer *ix, const uint64_t *ids, uint64_t n, vi_id_mode mode, vi_filter **out);
+vi_status vi_indexer_filter_ids_device(const vi_indexer *ix, const uint64_t *ids_dev, uint64_t n, vi_id_mode mode,
+                                       vi_filter **out);
+vi_status vi_filter_intersect(const vi_indexer *ix, const vi_filter *a, const vi_filter *b, vi_filter **out);
+
 /* ---- extension: radius (range) search -----------------------------------------------------------------------------
  * Every candidate of the probed lists whose squared distance is at most radius2.  The result of a query is the
  * reference's candidate sequence (probed lists in shard visiting order, then probe rank, then list position) after the

@@ -587,6 +587,43 @@ vi_status vi_indexer_filter_timestamps(const vi_indexer *ix, uint64_t ts_min, ui
   });
 }
 
+static vi_status filter_ids_common(const vi_indexer *ix, const uint64_t *ids, uint64_t n, vi_id_mode mode, bool on_device,
+                                   vi_filter **out) {
+  return vi::guarded([&]() -> vi_status {
+  if (!ix || !out) return fail(VI_ERR_INVALID_INPUT, "null pointer");
+  if (n && !ids) return fail(VI_ERR_INVALID_INPUT, "null id set with n = %llu", (unsigned long long)n);
+  if ((int)mode != VI_IDS_ALLOW && (int)mode != VI_IDS_DENY)
+    return fail(VI_ERR_INVALID_INPUT, "id filter mode %d (VI_IDS_ALLOW = 0 or VI_IDS_DENY = 1)", (int)mode);
+  if (!ix->impl.dev) return fail(VI_ERR_DEVICE, "index is not resident on a GPU (build or load it first)");
+  auto f = std::make_unique<vi_filter>();
+  VI_TRY(vi::slot_filter_ids(*ix->impl.dev, ids, n, on_device, (int)mode == VI_IDS_DENY, &f->impl));
+  *out = f.release();
+  return VI_OK;
+  });
+}
+
+vi_status vi_indexer_filter_ids(const vi_indexer *ix, const uint64_t *ids, uint64_t n, vi_id_mode mode, vi_filter **out) {
+  return filter_ids_common(ix, ids, n, mode, false, out);
+}
+
+vi_status vi_indexer_filter_ids_device(const vi_indexer *ix, const uint64_t *ids_dev, uint64_t n, vi_id_mode mode,
+                                       vi_filter **out) {
+  return filter_ids_common(ix, ids_dev, n, mode, true, out);
+}
+
+vi_status vi_filter_intersect(const vi_indexer *ix, const vi_filter *a, const vi_filter *b, vi_filter **out) {
+  return vi::guarded([&]() -> vi_status {
+  if (!ix || !out || !a || !b) return fail(VI_ERR_INVALID_INPUT, "null pointer");
+  const vi::SlotFilter *fa = nullptr, *fb = nullptr;
+  VI_TRY(filter_common(ix, a, &fa));
+  VI_TRY(filter_common(ix, b, &fb));
+  auto f = std::make_unique<vi_filter>();
+  VI_TRY(vi::slot_filter_intersect(*ix->impl.dev, *fa, *fb, &f->impl));
+  *out = f.release();
+  return VI_OK;
+  });
+}
+
 uint64_t vi_filter_num_allowed(const vi_filter *f) { return f ? f->impl.num_allowed : 0; }
 
 void vi_filter_free(vi_filter *f) { delete f; }

@@ -1,4 +1,5 @@
-// slot_filter.hip — builds a SlotFilter (slot_filter.hpp) from the resident timestamps of an index.
+// slot_filter.hip — builds a SlotFilter (slot_filter.hpp): from the resident timestamps of an index, from a set of
+// external ids, or as the intersection of two filters of one index.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -13,11 +14,15 @@ namespace {
 constexpr int kWave = 64;
 constexpr uint32_t kListSplit = 8;  // workgroups sharing the blocks of one list (long lists carry most of an index)
 
-struct FilterBuildArgs {
+// the list layout, taken as pad_norms_kernel takes it (first block and length of every list; lists that are not resident
+// here have length 0)
+struct FilterLists {
   const uint32_t *first_block, *list_len;
   uint32_t nlists;
-  const uint64_t *timestamps;
-  uint64_t ts_min, ts_max;
+};
+
+// what every filter is made of: the index's norm arrays, the filter's masked copies of them, its allow words, its count
+struct FilterOut {
   const float *xnorm, *xnorm_img;
   const int *i8_norm_img;  // or null
   uint64_t *allow;
@@ -26,38 +31,118 @@ struct FilterBuildArgs {
   unsigned long long *count;
 };
 
-// One wave per 64-vector block, the list layout taken as pad_norms_kernel takes it (first block and length of every
-// list; lists that are not resident here have length 0).  Lane = vector of the block: its allow bit is `timestamp in the
-// window` AND `position below the list length`; lane 0 stores the wave's ballot as the block's allow word.  The masked
-// norms: natural order as they are, image order through image_column — the one definition of that permutation.
-__global__ void __launch_bounds__(256) slot_filter_kernel(FilterBuildArgs a) {
-  const uint32_t l = blockIdx.x, lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  if (l >= a.nlists) return;
-  const uint32_t len = a.list_len[l], fb = a.first_block[l], nblk = (len + 63u) / 64u;
+// The one writer of a filter, called by a whole wave for 64-vector block `block` with lane = vector of the block and
+// ok = "this slot is allowed" (false on every pad slot): lane 0 stores the wave's ballot as the block's allow word; the
+// masked norms: natural order as they are, image order through image_column — the one definition of that permutation —
+// with kBig / kI8PadNorm on the slots that are not allowed.  Returns the number of allowed slots of the block.
+__device__ __forceinline__ uint32_t write_filter_block(const FilterOut &o, uint32_t block, uint32_t lane, bool ok) {
+  const size_t base = (size_t)block * kWave;
   const uint32_t col = image_column(lane);
-  uint32_t n = 0;
-  for (uint32_t b = blockIdx.y * 4u + wave; b < nblk; b += gridDim.y * 4u) {  // (wave-uniform)
-    const size_t base = (size_t)(fb + b) * kWave;
-    const uint64_t ts = a.timestamps[base + lane];
-    const bool ok = b * 64u + lane < len && ts >= a.ts_min && ts <= a.ts_max;
-    const uint64_t word = __ballot(ok);
-    if (lane == 0) a.allow[fb + b] = word;
-    a.xnorm_out[base + lane] = ok ? a.xnorm[base + lane] : kBig;
-    a.xnorm_img_out[base + col] = ok ? a.xnorm_img[base + col] : kBig;
-    if (a.i8_norm_img) a.i8_out[base + col] = ok ? a.i8_norm_img[base + col] : kI8PadNorm;
-    n += (uint32_t)__popcll(word);
-  }
-  if (lane == 0 && n) atomicAdd(a.count, (unsigned long long)n);
+  const uint64_t word = __ballot(ok);
+  if (lane == 0) o.allow[block] = word;
+  o.xnorm_out[base + lane] = ok ? o.xnorm[base + lane] : kBig;
+  o.xnorm_img_out[base + col] = ok ? o.xnorm_img[base + col] : kBig;
+  if (o.i8_norm_img) o.i8_out[base + col] = ok ? o.i8_norm_img[base + col] : kI8PadNorm;
+  return (uint32_t)__popcll(word);
 }
 
-}  // namespace
+// allow = stored timestamp within [ts_min, ts_max]
+struct TimestampPred {
+  const uint64_t *timestamps;
+  uint64_t ts_min, ts_max;
+  __device__ bool operator()(uint32_t block, uint32_t lane, bool resident) const {
+    const uint64_t ts = timestamps[(size_t)block * kWave + lane];
+    return resident && ts >= ts_min && ts <= ts_max;
+  }
+};
 
+// ---- a set of u64 ids as an open-addressing table: power-of-two capacity, linear probing, kEmptyKey = free word.  The id
+// that equals kEmptyKey cannot be a key: whether the set holds it is a flag word of its own.
+constexpr uint64_t kEmptyKey = ~0ull;
+
+__device__ __forceinline__ uint64_t mix_id(uint64_t x) {  // splitmix64's finalizer: every id bit reaches every index bit
+  x ^= x >> 30; x *= 0xbf58476d1ce4e5b9ull;
+  x ^= x >> 27; x *= 0x94d049bb133111ebull;
+  return x ^ (x >> 31);
+}
+
+struct IdTable {
+  unsigned long long *words;  // [capacity]
+  uint64_t mask;              // capacity - 1
+  uint32_t *flags;            // [0]: the set holds kEmptyKey   [1]: an insert found no free word (cannot happen: load <= 0.5)
+};
+
+// One thread per id of the set.  A duplicate meets its own key and is done.  The probe loop ends after `capacity` words
+// whatever the table holds.
+__global__ void __launch_bounds__(256) id_table_insert_kernel(IdTable t, const uint64_t *ids, uint64_t n) {
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+    const uint64_t id = ids[i];
+    if (id == kEmptyKey) {
+      t.flags[0] = 1u;
+      continue;
+    }
+    uint64_t h = mix_id(id) & t.mask;
+    bool done = false;
+    for (uint64_t probe = 0; probe <= t.mask && !done; ++probe, h = (h + 1) & t.mask) {
+      const unsigned long long prev = atomicCAS(&t.words[h], (unsigned long long)kEmptyKey, (unsigned long long)id);
+      done = prev == kEmptyKey || prev == id;
+    }
+    if (!done) t.flags[1] = 1u;
+  }
+}
+
+// allow = (external id is in the table) != exclude; the table is complete (the insert kernel ran before on the stream)
+struct IdPred {
+  const uint64_t *ext_ids;
+  IdTable t;
+  bool exclude;
+  __device__ bool operator()(uint32_t block, uint32_t lane, bool resident) const {
+    const uint64_t id = ext_ids[(size_t)block * kWave + lane];
+    bool member = false;
+    if (id == kEmptyKey) {
+      member = t.flags[0] != 0u;
+    } else {
+      uint64_t h = mix_id(id) & t.mask;
+      for (uint64_t probe = 0; probe <= t.mask; ++probe, h = (h + 1) & t.mask) {
+        const uint64_t w = t.words[h];
+        if (w == id) member = true;
+        if (w == id || w == kEmptyKey) break;
+      }
+    }
+    return resident && member != exclude;  // (resident first in both modes: a deny filter never allows a pad slot)
+  }
+};
+
+// allow = a.allow & b.allow
+struct IntersectPred {
+  const uint64_t *a, *b;
+  __device__ bool operator()(uint32_t block, uint32_t lane, bool resident) const {
+    return resident && (((a[block] & b[block]) >> lane) & 1ull) != 0;
+  }
+};
+
+// One wave per 64-vector block, kListSplit workgroups of four waves per list.  Lane = vector of the block: its allow bit
+// is the predicate AND `position below the list length`.
+template <class Pred>
+__global__ void __launch_bounds__(256) slot_filter_kernel(FilterLists L, FilterOut o, Pred pred) {
+  const uint32_t l = blockIdx.x, lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  if (l >= L.nlists) return;
+  const uint32_t len = L.list_len[l], fb = L.first_block[l], nblk = (len + 63u) / 64u;
+  uint32_t n = 0;
+  for (uint32_t b = blockIdx.y * 4u + wave; b < nblk; b += gridDim.y * 4u) {  // (wave-uniform)
+    const bool ok = pred(fb + b, lane, b * 64u + lane < len);
+    n += write_filter_block(o, fb + b, lane, ok);
+  }
+  if (lane == 0 && n) atomicAdd(o.count, (unsigned long long)n);
+}
+
+// The part every filter shares: the buffers of *f, the zeroed count, one launch of the kernel with `pred`, the count.
 // The index's own statistics — xmax2, rho2_max, the centring mu, mean_* — are left as they are and keep setting the rank
 // margins and the rank mode of a filtered search: a filter only removes candidates, it never widens a bound, so the
-// margins of the full index remain valid upper bounds for every subset of it.
-vi_status slot_filter_timestamps(const DeviceIndex &ix, uint64_t ts_min, uint64_t ts_max, SlotFilter *f) {
-  if (!ix.timestamps.p) return fail(VI_ERR_INVALID_INPUT, "this index keeps no timestamps");
-  VI_HIP(hipSetDevice(ix.device));
+// margins of the full index remain valid upper bounds for every subset of it — whatever predicate chose the subset.
+template <class Pred>
+vi_status build_filter(const DeviceIndex &ix, const Pred &pred, SlotFilter *f, const uint32_t *flags_dev = nullptr,
+                       uint32_t *flags_host = nullptr) {
   const uint64_t nb = ix.lists.nblocks, nslots = nb * kWave;
   f->owner_serial = ix.serial;
   VI_TRY(f->allow.reserve(std::max<uint64_t>(1, nb)));
@@ -70,17 +155,66 @@ vi_status slot_filter_timestamps(const DeviceIndex &ix, uint64_t ts_min, uint64_
   VI_HIP(hipMemsetAsync(cnt.p, 0, sizeof(unsigned long long), st));
   VI_HIP(hipMemsetAsync(f->allow.p, 0, std::max<uint64_t>(1, nb) * sizeof(uint64_t), st));
   if (nb && ix.nlists) {
-    FilterBuildArgs a{ix.list_first_block.p, ix.list_len.p, (uint32_t)ix.nlists, ix.timestamps.p, ts_min, ts_max,
-                      ix.xnorm.p, ix.xnorm_img.p, ix.i8_norm_img.p, f->allow.p, f->xnorm.p, f->xnorm_img.p,
-                      f->i8_norm_img.p, cnt.p};
-    hipLaunchKernelGGL(slot_filter_kernel, dim3((uint32_t)ix.nlists, kListSplit), dim3(256), 0, st, a);
+    FilterLists L{ix.list_first_block.p, ix.list_len.p, (uint32_t)ix.nlists};
+    FilterOut o{ix.xnorm.p, ix.xnorm_img.p, ix.i8_norm_img.p, f->allow.p, f->xnorm.p, f->xnorm_img.p, f->i8_norm_img.p, cnt.p};
+    hipLaunchKernelGGL(slot_filter_kernel<Pred>, dim3((uint32_t)ix.nlists, kListSplit), dim3(256), 0, st, L, o, pred);
     VI_HIP(hipGetLastError());
   }
   unsigned long long n = 0;
   VI_HIP(hipMemcpyAsync(&n, cnt.p, sizeof(n), hipMemcpyDeviceToHost, st));
+  if (flags_dev) VI_HIP(hipMemcpyAsync(flags_host, flags_dev, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
   VI_HIP(hipStreamSynchronize(st));
   f->num_allowed = n;
   return VI_OK;
+}
+
+}  // namespace
+
+vi_status slot_filter_timestamps(const DeviceIndex &ix, uint64_t ts_min, uint64_t ts_max, SlotFilter *f) {
+  if (!ix.timestamps.p) return fail(VI_ERR_INVALID_INPUT, "this index keeps no timestamps");
+  VI_HIP(hipSetDevice(ix.device));
+  return build_filter(ix, TimestampPred{ix.timestamps.p, ts_min, ts_max}, f);
+}
+
+vi_status slot_filter_ids(const DeviceIndex &ix, const uint64_t *ids, uint64_t n, bool ids_on_device, bool exclude,
+                          SlotFilter *f) {
+  if (!ix.ext_ids.p) return fail(VI_ERR_INVALID_INPUT, "this index keeps no external ids");
+  if (n > (1ull << 40)) return fail(VI_ERR_INVALID_INPUT, "id set of %llu ids is too large", (unsigned long long)n);
+  VI_HIP(hipSetDevice(ix.device));
+  hipStream_t st = ix.stream;
+  uint64_t capacity = 2;  // power of two >= 2 max(n, 1): load factor <= 0.5
+  while (capacity < 2 * n) capacity <<= 1;
+  // the table, the flags and the uploaded copy of host ids live until this function returns
+  DevBuf<unsigned long long> words;
+  DevBuf<uint32_t> flags;
+  DevBuf<uint64_t> upload;
+  VI_TRY(words.reserve(capacity));
+  VI_TRY(flags.reserve(2));
+  VI_HIP(hipMemsetAsync(words.p, 0xff, capacity * sizeof(unsigned long long), st));  // every word kEmptyKey
+  VI_HIP(hipMemsetAsync(flags.p, 0, 2 * sizeof(uint32_t), st));
+  IdTable t{words.p, capacity - 1, flags.p};
+  if (n) {
+    if (!ids_on_device) {
+      VI_TRY(upload.reserve(n));
+      VI_HIP(hipMemcpyAsync(upload.p, ids, n * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+      ids = upload.p;
+    }
+    const uint32_t grid = (uint32_t)std::min<uint64_t>((n + 255) / 256, 65536);
+    hipLaunchKernelGGL(id_table_insert_kernel, dim3(grid), dim3(256), 0, st, t, ids, n);
+    VI_HIP(hipGetLastError());
+  }
+  uint32_t fl[2] = {0, 0};
+  VI_TRY(build_filter(ix, IdPred{ix.ext_ids.p, t, exclude}, f, flags.p, fl));
+  if (fl[1]) return fail(VI_ERR_DEVICE, "id filter: the id table (capacity %llu for %llu ids) overflowed",
+                         (unsigned long long)capacity, (unsigned long long)n);
+  return VI_OK;
+}
+
+vi_status slot_filter_intersect(const DeviceIndex &ix, const SlotFilter &a, const SlotFilter &b, SlotFilter *f) {
+  if (a.owner_serial != ix.serial || b.owner_serial != ix.serial)
+    return fail(VI_ERR_INVALID_INPUT, "the filter was made from another indexer (or before this one was rebuilt)");
+  VI_HIP(hipSetDevice(ix.device));
+  return build_filter(ix, IntersectPred{a.allow.p, b.allow.p}, f);
 }
 
 }  // namespace vi

@@ -39,4 +39,13 @@ struct SlotFilter {
 // allow = stored timestamp within [ts_min, ts_max] (both inclusive)
 vi_status slot_filter_timestamps(const DeviceIndex &ix, uint64_t ts_min, uint64_t ts_max, SlotFilter *out);
 
+// allow = (external id is one of ids[0..n)) != exclude.  The set needs no order and may repeat ids; any u64 is an id.  It
+// becomes a hash table on the device (host ids are uploaded once, device ids are read in place); the table and the upload
+// are freed before the call returns, so the finished filter costs what a timestamp filter costs.
+vi_status slot_filter_ids(const DeviceIndex &ix, const uint64_t *ids, uint64_t n, bool ids_on_device, bool exclude,
+                          SlotFilter *out);
+
+// allow = a.allow & b.allow; both must be filters of ix (VI_ERR_INVALID_INPUT otherwise)
+vi_status slot_filter_intersect(const DeviceIndex &ix, const SlotFilter &a, const SlotFilter &b, SlotFilter *out);
+
 }  // namespace vi

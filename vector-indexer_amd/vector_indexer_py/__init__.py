@@ -17,14 +17,14 @@ import asyncio
 import ctypes as C
 import os
 import tempfile
-from typing import Optional, Tuple
+from typing import Optional, Tuple, Union
 
 import numpy as np
 
 from . import _native
 from ._native import (ViError, lib, VI_ASSIGN_EXACT, VI_ASSIGN_REFERENCE, VI_ORDER_LANES, VI_ORDER_SCALAR)
 
-__all__ = ["build", "load", "suggest_nlist", "VectorIndex", "TimestampFilter", "RangeResult", "ViError", "kmeans_mini_batch", "kmeans_parallel",
+__all__ = ["build", "load", "suggest_nlist", "VectorIndex", "TimestampFilter", "IdFilter", "FilterIntersection", "AnyFilter", "RangeResult", "ViError", "kmeans_mini_batch", "kmeans_parallel",
            "assign", "l2sq_pairs", "VI_ASSIGN_EXACT", "VI_ASSIGN_REFERENCE", "VI_ORDER_LANES", "VI_ORDER_SCALAR"]
 
 
@@ -33,14 +33,13 @@ def suggest_nlist(n: int) -> int:
     return int(lib().vi_calculate_num_clusters(int(n)))
 
 
-class TimestampFilter:
-    """The vectors of one VectorIndex whose stored timestamp lies in [ts_min, ts_max] (VectorIndex.filter_timestamps).
-    Immutable; pass it as `filter=` to that index's searches.  Keeps its index alive and frees itself."""
+class _Filter:
+    """A subset of the resident vectors of one VectorIndex.  Immutable; pass it as `filter=` to that index's searches.
+    Keeps its index alive and frees itself.  `a & b` of two filters of one index: the vectors both admit."""
 
-    def __init__(self, index, handle, ts_min, ts_max):
+    def __init__(self, index, handle):
         self._index = index  # (the native filter must be freed before its indexer)
         self._h = handle
-        self.ts_min, self.ts_max = int(ts_min), int(ts_max)
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None
@@ -52,8 +51,43 @@ class TimestampFilter:
 
     @property
     def num_allowed(self) -> int:
-        """resident vectors inside the window"""
+        """resident vectors the filter admits"""
         return int(lib().vi_filter_num_allowed(self._h))
+
+    def __and__(self, other):
+        if not isinstance(other, _Filter):
+            return NotImplemented
+        h = C.c_void_p()
+        _native.check(lib().vi_filter_intersect(self._index._h, self._h, other._h, C.byref(h)))
+        return FilterIntersection(self._index, h, (self, other))
+
+
+class TimestampFilter(_Filter):
+    """The vectors of one VectorIndex whose stored timestamp lies in [ts_min, ts_max] (VectorIndex.filter_timestamps)."""
+
+    def __init__(self, index, handle, ts_min, ts_max):
+        super().__init__(index, handle)
+        self.ts_min, self.ts_max = int(ts_min), int(ts_max)
+
+
+class IdFilter(_Filter):
+    """The vectors of one VectorIndex whose external id is in a set (exclude=False), or is not in it (exclude=True)
+    (VectorIndex.filter_ids, .filter_ids_device).  The set itself is not kept."""
+
+    def __init__(self, index, handle, num_ids, exclude):
+        super().__init__(index, handle)
+        self.num_ids, self.exclude = int(num_ids), bool(exclude)
+
+
+class FilterIntersection(_Filter):
+    """`a & b`: a filter of its own (the operands may go away); keeps the index of both operands alive."""
+
+    def __init__(self, index, handle, operands):
+        super().__init__(index, handle)
+        self._indexes = tuple(o._index for o in operands)
+
+
+AnyFilter = Union[TimestampFilter, IdFilter, FilterIntersection]
 
 
 class RangeResult:
@@ -141,7 +175,24 @@ class VectorIndex:
         _native.check(lib().vi_indexer_filter_timestamps(self._h, int(ts_min), int(ts_max), C.byref(h)))
         return TimestampFilter(self, h, ts_min, ts_max)
 
-    def search_sync(self, xq, k: int, n_probe: int, include_vectors: bool = False, filter: Optional[TimestampFilter] = None):
+    def filter_ids(self, ids, exclude: bool = False) -> IdFilter:
+        """extension: the searches of this index restricted to the records whose external id is in `ids` (any integer
+        array-like; no order needed, duplicates allowed), or — exclude=True — to the records whose id is NOT in it"""
+        a = _native.id_array(ids)
+        h = C.c_void_p()
+        _native.check(lib().vi_indexer_filter_ids(self._h, _native.ptr(a) if a.size else None, a.size,
+                                                  _native.VI_IDS_DENY if exclude else _native.VI_IDS_ALLOW, C.byref(h)))
+        return IdFilter(self, h, a.size, exclude)
+
+    def filter_ids_device(self, ids_ptr: int, n: int, exclude: bool = False) -> IdFilter:
+        """... for n u64 ids in device memory, read in place"""
+        h = C.c_void_p()
+        _native.check(lib().vi_indexer_filter_ids_device(self._h, C.c_void_p(ids_ptr) if ids_ptr else None, int(n),
+                                                         _native.VI_IDS_DENY if exclude else _native.VI_IDS_ALLOW,
+                                                         C.byref(h)))
+        return IdFilter(self, h, n, exclude)
+
+    def search_sync(self, xq, k: int, n_probe: int, include_vectors: bool = False, filter: Optional[AnyFilter] = None):
         xq = np.asarray(xq)
         if xq.ndim != 2:
             raise RuntimeError("Query array must be 2-dimensional")
@@ -167,7 +218,7 @@ class VectorIndex:
         return (D, I, V) if include_vectors else (D, I)
 
     def range_search_sync(self, xq, radius2: float, n_probe: int, include_vectors: bool = False,
-                          filter: Optional[TimestampFilter] = None):
+                          filter: Optional[AnyFilter] = None):
         """extension: every probed candidate with squared distance <= radius2, per query in the reference's stable order ->
         (lims u64[nq + 1], D f32[total], I i64[total][, V f32[total, dim]]); query q owns [lims[q], lims[q + 1])"""
         xq = np.asarray(xq)
@@ -184,7 +235,7 @@ class VectorIndex:
             res.free()
 
     def range_search_device(self, xq_ptr: int, nq: int, radius2: float, n_probe: int,
-                            filter: Optional[TimestampFilter] = None) -> RangeResult:
+                            filter: Optional[AnyFilter] = None) -> RangeResult:
         """... for nq queries in device memory; the result stays there (RangeResult)"""
         h = C.c_void_p()
         _native.check(lib().vi_indexer_range_search_device(self._h, _filter_handle(filter), C.c_void_p(xq_ptr), int(nq),
@@ -219,7 +270,7 @@ class VectorIndex:
 
     # device-pointer search used by the multi-GPU path (torch tensors on this GPU)
     def search_device(self, xq_ptr: int, nq: int, k: int, n_probe: int, D_ptr: int, I_ptr: int, tie_ptr: int = 0,
-                      filter: Optional[TimestampFilter] = None):
+                      filter: Optional[AnyFilter] = None):
         _native.check(lib().vi_indexer_search_filtered_device(self._h, _filter_handle(filter), C.c_void_p(xq_ptr), nq, k,
                                                               n_probe, C.c_void_p(D_ptr), C.c_void_p(I_ptr),
                                                               C.c_void_p(tie_ptr) if tie_ptr else None))
@@ -233,7 +284,7 @@ class VectorIndex:
         return int(p_eff.value)
 
     def search_probed_device(self, xq_ptr: int, nq: int, k: int, n_probe_eff: int, probes_ptr: int, order_ptr: int,
-                             D_ptr: int, I_ptr: int, tie_ptr: int = 0, filter: Optional[TimestampFilter] = None):
+                             D_ptr: int, I_ptr: int, tie_ptr: int = 0, filter: Optional[AnyFilter] = None):
         """list scan + top-k (ivf_index.rs:223-274) with probe lists computed elsewhere"""
         _native.check(lib().vi_indexer_search_probed_filtered_device(self._h, _filter_handle(filter), C.c_void_p(xq_ptr), nq,
                                                                      k, n_probe_eff, C.c_void_p(probes_ptr),

@@ -6,6 +6,7 @@ VI_OK, VI_ERR_INVALID_INPUT, VI_ERR_NOT_FOUND, VI_ERR_INVALID_DATA, VI_ERR_OTHER
     VI_ERR_DEVICE = range(8)
 VI_ORDER_SCALAR, VI_ORDER_LANES = 0, 1
 VI_ASSIGN_REFERENCE, VI_ASSIGN_EXACT = 0, 1
+VI_IDS_ALLOW, VI_IDS_DENY = 0, 1
 
 _STATUS_NAME = {1: "InvalidInput", 2: "NotFound", 3: "InvalidData", 4: "Other", 5: "Io", 6: "Panic", 7: "Device"}
 
@@ -93,6 +94,9 @@ SIGNATURES = {
     "vi_indexer_probe_device": (C.c_int, [vp, vp, u64, u64, vp, vp, C.POINTER(u64)]),
     "vi_indexer_search_probed_device": (C.c_int, [vp, vp, u64, u64, u64, vp, vp, vp, vp, vp]),
     "vi_indexer_filter_timestamps": (C.c_int, [vp, u64, u64, C.POINTER(vp)]),
+    "vi_indexer_filter_ids": (C.c_int, [vp, vp, u64, C.c_int, C.POINTER(vp)]),
+    "vi_indexer_filter_ids_device": (C.c_int, [vp, vp, u64, C.c_int, C.POINTER(vp)]),
+    "vi_filter_intersect": (C.c_int, [vp, vp, vp, C.POINTER(vp)]),
     "vi_filter_num_allowed": (u64, [vp]),
     "vi_filter_free": (None, [vp]),
     "vi_indexer_search_filtered": (C.c_int, [vp, vp, vp, u64, u32, u64, u64, vp, vp, vp, vp, C.POINTER(u64)]),
@@ -139,6 +143,23 @@ def lib():
 
 def ptr(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
+
+
+def id_array(ids):
+    """any integer array-like of external ids -> flat contiguous uint64 (every u64 is an id; negatives are an error)"""
+    import numpy as np
+    if not isinstance(ids, np.ndarray):
+        ids = list(ids)
+        if any(isinstance(x, bool) or not isinstance(x, (int, np.integer)) for x in ids):
+            raise TypeError("ids must be integers")
+        if any(x < 0 for x in ids):
+            raise ValueError("ids must be non-negative (external ids are u64)")
+        return np.array(ids, dtype=np.uint64)   # (python ints: the whole u64 range, which no signed dtype holds)
+    if ids.size and ids.dtype.kind not in "iu":
+        raise TypeError("ids must be integers")
+    if ids.dtype.kind == "i" and (ids < 0).any():
+        raise ValueError("ids must be non-negative (external ids are u64)")
+    return np.ascontiguousarray(ids.reshape(-1), dtype=np.uint64)
 
 
 def check(status, prefix=""):

@@ -7,10 +7,12 @@
     VectorIndexer.new(cfg) / .load(cfg) / .build_from_records / .build_from_vector_file /
     .search(req) / .search_request(query) / .config()                             api.rs:101-237
     .range_search(query, radius2, ...)                                            extension: everything within a radius
+    SearchRequest.with_timestamp_range / .with_allowed_ids / .with_excluded_ids   extension: filtered search
 
 Errors are ViError (a RuntimeError) whose .kind is the io::ErrorKind name the reference returns.
 """
 import ctypes as C
+import hashlib
 from dataclasses import dataclass, field, replace
 from typing import List, Optional, Tuple
 
@@ -56,6 +58,25 @@ class VectorRecord:
     timestamp: Optional[int] = None
 
 
+@dataclass(frozen=True, eq=False)
+class IdSelector:
+    """a set of external ids a search is restricted to (exclude=False) or kept away from (exclude=True): the ids sorted,
+    unique, uint64 and read-only; `key` names the set in the indexer's filter cache"""
+    ids: np.ndarray
+    exclude: bool
+    digest: str
+
+    @staticmethod
+    def of(ids, exclude: bool) -> "IdSelector":
+        a = np.unique(_native.id_array(ids))
+        a.setflags(write=False)
+        return IdSelector(a, bool(exclude), hashlib.sha256(a.tobytes()).hexdigest())
+
+    @property
+    def key(self):
+        return ("ids", self.exclude, int(self.ids.size), self.digest)
+
+
 @dataclass
 class SearchRequest:
     query: List[float]
@@ -64,6 +85,8 @@ class SearchRequest:
     n_probe: int = 20
     # extension: only records whose stored timestamp lies in [lo, hi], both inclusive (None: all, the reference's search)
     timestamp_range: Optional[Tuple[int, int]] = None
+    # extension: only records whose external id is in a set / is not in a set (None: all); with timestamp_range: both
+    id_selector: Optional[IdSelector] = None
 
     def with_k(self, k):
         return replace(self, k=k)
@@ -77,6 +100,12 @@ class SearchRequest:
     def with_timestamp_range(self, lo, hi):
         return replace(self, timestamp_range=(int(lo), int(hi)))
 
+    def with_allowed_ids(self, ids):
+        return replace(self, id_selector=IdSelector.of(ids, False))
+
+    def with_excluded_ids(self, ids):
+        return replace(self, id_selector=IdSelector.of(ids, True))
+
 
 @dataclass
 class SearchResult:
@@ -89,7 +118,7 @@ class VectorIndexer:
     def __init__(self, cfg: VectorIndexerConfig, handle):
         self._cfg = cfg
         self._h = handle
-        self._filters = {}  # (lo, hi) -> native filter of the resident index
+        self._filters = {}  # (lo, hi) / IdSelector.key / (both) -> native filter of the resident index
 
     def _drop_filters(self):
         filters, self._filters = getattr(self, "_filters", {}), {}
@@ -102,18 +131,36 @@ class VectorIndexer:
         if h:
             lib().vi_indexer_free(h)
 
-    def _filter(self, rng):
-        if rng is None:
-            return None
-        key = (int(rng[0]), int(rng[1]))
-        f = self._filters.get(key)
-        if f is None:
+    def _filter(self, rng, selector: Optional[IdSelector] = None):
+        """the native filter of a timestamp window, an id selector, or both (their intersection); None: no filter"""
+        tkey = None if rng is None else (int(rng[0]), int(rng[1]))
+        ikey = None if selector is None else selector.key
+        if tkey is None or ikey is None:
+            key = tkey if ikey is None else ikey
+            if key is None:
+                return None
+        else:
+            key = (tkey, ikey)
+        if key in self._filters:
+            return self._filters[key]
+        missing = [k for k in {tkey, ikey, key} if k is not None and k not in self._filters]
+        if len(self._filters) + len(missing) > 16:  # (a filter holds device memory in proportion to the index)
+            self._drop_filters()
+        if tkey is not None and tkey not in self._filters:
             f = C.c_void_p()
-            _native.check(lib().vi_indexer_filter_timestamps(self._h, key[0], key[1], C.byref(f)))
-            if len(self._filters) >= 16:  # (a filter holds device memory in proportion to the index)
-                self._drop_filters()
+            _native.check(lib().vi_indexer_filter_timestamps(self._h, tkey[0], tkey[1], C.byref(f)))
+            self._filters[tkey] = f
+        if ikey is not None and ikey not in self._filters:
+            f, ids = C.c_void_p(), selector.ids
+            _native.check(lib().vi_indexer_filter_ids(self._h, _native.ptr(ids) if ids.size else None, ids.size,
+                                                      _native.VI_IDS_DENY if selector.exclude else _native.VI_IDS_ALLOW,
+                                                      C.byref(f)))
+            self._filters[ikey] = f
+        if key not in self._filters:
+            f = C.c_void_p()
+            _native.check(lib().vi_filter_intersect(self._h, self._filters[tkey], self._filters[ikey], C.byref(f)))
             self._filters[key] = f
-        return f
+        return self._filters[key]
 
     @staticmethod
     def _native_cfg(cfg: VectorIndexerConfig):
@@ -169,20 +216,25 @@ class VectorIndexer:
         V = np.zeros((1, max(kcap, 1), self._cfg.dimension), dtype=np.float32) if req.include_vectors else None
         cnt = np.zeros(1, dtype=np.uint64)
         kout = C.c_uint64(0)
-        _native.check(lib().vi_indexer_search_filtered(self._h, self._filter(req.timestamp_range), _native.ptr(q), 1,
+        _native.check(lib().vi_indexer_search_filtered(self._h, self._filter(req.timestamp_range, req.id_selector), _native.ptr(q), 1,
                                                        q.shape[1], k, int(req.n_probe), _native.ptr(D), _native.ptr(I),
                                                        _native.ptr(V), _native.ptr(cnt), C.byref(kout)))
         return [SearchResult(int(I[0, j]), float(D[0, j]), V[0, j].tolist() if V is not None else None)
                 for j in range(int(cnt[0]))]
 
     def range_search(self, query, radius2: float, n_probe: Optional[int] = None, include_vectors: bool = False,
-                     timestamp_range: Optional[Tuple[int, int]] = None) -> List[SearchResult]:
+                     timestamp_range: Optional[Tuple[int, int]] = None, allowed_ids=None,
+                     excluded_ids=None) -> List[SearchResult]:
         """extension: every record of the probed lists within squared distance radius2 of the query, nearest first (the
         reference's stable order); n_probe None: the config's default_n_probe"""
+        if allowed_ids is not None and excluded_ids is not None:
+            raise ValueError("give allowed_ids or excluded_ids, not both")
+        selector = (IdSelector.of(allowed_ids, False) if allowed_ids is not None
+                    else IdSelector.of(excluded_ids, True) if excluded_ids is not None else None)
         q = np.ascontiguousarray(np.asarray(query, dtype=np.float32).reshape(1, -1))
         p = self._cfg.default_n_probe if n_probe is None else int(n_probe)
         h = C.c_void_p()
-        _native.check(lib().vi_indexer_range_search(self._h, self._filter(timestamp_range), _native.ptr(q), 1, q.shape[1],
+        _native.check(lib().vi_indexer_range_search(self._h, self._filter(timestamp_range, selector), _native.ptr(q), 1, q.shape[1],
                                                     float(radius2), p, C.byref(h)))
         try:
             n = int(lib().vi_range_result_total(h))

@@ -136,13 +136,29 @@ class FaissStyleAdapter:
     def nprobe(self, value: int):
         self._nprobe = int(value)
 
-    def search(self, xq: np.ndarray, k: int):
-        return self._idx.search_sync(np.ascontiguousarray(xq, dtype=np.float32), k, self._nprobe)
+    def _id_filter(self, allowed_ids, excluded_ids):
+        """what Faiss passes as SearchParameters(sel=IDSelectorBatch / IDSelectorNot); None when neither is given"""
+        if allowed_ids is not None and excluded_ids is not None:
+            raise ValueError("give allowed_ids or excluded_ids, not both")
+        if allowed_ids is not None:
+            return self._idx.filter_ids(allowed_ids)
+        if excluded_ids is not None:
+            return self._idx.filter_ids(excluded_ids, exclude=True)
+        return None
 
-    def range_search(self, x: np.ndarray, thresh: float):
+    def search(self, xq: np.ndarray, k: int, allowed_ids=None, excluded_ids=None):
+        flt = self._id_filter(allowed_ids, excluded_ids)
+        if flt is None:
+            return self._idx.search_sync(np.ascontiguousarray(xq, dtype=np.float32), k, self._nprobe)
+        return self._idx.search_sync(np.ascontiguousarray(xq, dtype=np.float32), k, self._nprobe, filter=flt)
+
+    def range_search(self, x: np.ndarray, thresh: float, allowed_ids=None, excluded_ids=None):
         """Faiss's Index.range_search: (lims, D, I) — query i owns D / I[lims[i]:lims[i + 1]], squared L2 <= thresh, among
         the nprobe probed lists"""
-        return self._idx.range_search_sync(np.ascontiguousarray(x, dtype=np.float32), float(thresh), self._nprobe)
+        flt = self._id_filter(allowed_ids, excluded_ids)
+        if flt is None:
+            return self._idx.range_search_sync(np.ascontiguousarray(x, dtype=np.float32), float(thresh), self._nprobe)
+        return self._idx.range_search_sync(np.ascontiguousarray(x, dtype=np.float32), float(thresh), self._nprobe, filter=flt)
 
     def __repr__(self):
         return f"FaissStyleAdapter(d={self.d}, nprobe={self.nprobe})"
