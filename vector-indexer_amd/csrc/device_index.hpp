@@ -51,7 +51,12 @@ struct SearchWorkspace {
   DevBuf<uint32_t> seg_start;   // [nlists+1]
   DevBuf<uint32_t> item_start;  // [nlists+1]
   DevBuf<uint32_t> segrun_start;  // [nlists+1]
-  DevBuf<float> seg_run_dist;   // segment runs of long lists, merged by seg_merge_kernel
+  // the scans inside list_totals_kernel (GroupScanArgs) instead of the three arrays above: per list (pairs; items, segment
+  // runs, record tiles before it within its 64 lists), per 64 lists their sums; item_push_kernel adds the two up
+  DevBuf<uint32_t> list_local, list_block_sums;  // [nlists] x 4, [kGroupScanBlocks] x 4
+  bool lists_scanned_in_totals = false;     // ... by this search's grouping
+  bool group_counts_cleared = false;        // the grouping's counts of ws.stats were cleared by this search's split_queries_kernel
+  DevBuf<float> seg_run_dist;  // segment runs of long lists, merged by seg_merge_kernel
   DevBuf<uint32_t> seg_run_pos;
   DevBuf<uint32_t> pairs;       // [nq*P] slot ids grouped by list
   DevBuf<float> run_dist;       // [nq*P][K]
@@ -231,6 +236,7 @@ struct EngineKnobs {
   bool rank_i8;             // VI_RANK_I8=0: rank 8-bit descriptors with bf16
   uint32_t item_run;        // VI_ITEM_RUN: work items of one tile stream dealt to one XCD in a row
   bool item_push;           // VI_ITEM_PUSH=0: the work items' columns by kernels of their own behind the scatter
+  bool scan_in_totals;      // VI_SCAN_IN_TOTALS=0: the grouping's scans by group_prepare_kernel, a launch of its own, as everywhere without item_push
   bool stream_prof;         // VI_STREAM_PROF: clock the streaming rank kernel
   const char *stream_prof_dump;  // VI_STREAM_PROF_DUMP: file for its per-workgroup clocks, or null
   uint32_t filter_xmode;    // VI_FILTER_XMODE: rank kernel ablations

@@ -41,6 +41,7 @@
 #include "search_internal.hpp"
 #include "select.hpp"
 #include "slot_filter.hpp"
+#include "wave_sort.hpp"
 
 namespace vi {
 namespace {
@@ -163,6 +164,11 @@ struct ItemPushArgs {
   uint32_t total, P, nlists, gq, segb0, run;
   uint32_t pair_groups;      // workgroups [0, pair_groups): a thread per pair; behind them: a wave per list
   uint64_t cap_items, cap_records;  // work items the column / descriptor buffers hold, group records gmeta holds
+  // the lists' offsets as list_totals_kernel leaves them when it scans itself (GroupScanArgs), or null (seg_start,
+  // item_start, tile_start as group_prepare_kernel wrote them): per list, relative to its 64 lists, and the sums of
+  // every 64 lists — scanned here by every workgroup.  tile_out: each list's absolute first record tile, for the selects
+  const uint4 *local, *block_sums;
+  uint32_t *tile_out;
   uint32_t *pair_pos, *qcol, *grec, *gmeta;
   uint4 *sdesc;
   uint64_t *stats;
@@ -179,6 +185,8 @@ __device__ __forceinline__ uint32_t item_workgroup(uint32_t item, uint32_t run, 
 }
 
 __global__ void __launch_bounds__(256) item_push_kernel(ItemPushArgs a) {
+  __shared__ uint2 s_base[kGroupScanBlocks];  // items, record tiles of the 64-list workgroups before each (a.local only)
+  __shared__ uint2 s_wave[4];
   // the rank kernel's work counters and the batch flags of the next batch (their D2H copy is ahead of this kernel)
   if (blockIdx.x == 0) {
     if (threadIdx.x < kStatRankWorkCount) a.stats[kStatRankWork + kStatRankWorkStride * threadIdx.x] = 0;
@@ -188,16 +196,36 @@ __global__ void __launch_bounds__(256) item_push_kernel(ItemPushArgs a) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   const bool pair = blockIdx.x < a.pair_groups && i < a.total;
   const uint32_t l_pair = pair ? a.probes[i] : kNoPos, rank = pair ? a.pair_rank[i] : 0u, rel = pair ? a.rel[i] : 0u;
+  uint4 sums = make_uint4(0u, 0u, 0u, 0u);
+  if (a.local && threadIdx.x < (a.nlists + 63u) / 64u) sums = a.block_sums[threadIdx.x];
   const uint64_t nitems64 = a.stats[kStatItems];
-  if (nitems64 > a.cap_items || a.stats[kStatGroupRecords] > a.cap_records) return;
+  if (nitems64 > a.cap_items || a.stats[kStatGroupRecords] > a.cap_records) return;  // (every thread of the grid alike)
   const uint32_t nitems = (uint32_t)nitems64, gq = a.gq;
+  if (a.local) {  // the exclusive scan of the 64-list sums, a thread per sum
+    const uint32_t wv = threadIdx.x >> 6, ii = wave_incl_scan_u32(sums.y), it = wave_incl_scan_u32(sums.w);
+    if ((threadIdx.x & 63u) == 63u) s_wave[wv] = make_uint2(ii, it);
+    __syncthreads();
+    uint2 base = make_uint2(ii - sums.y, it - sums.w);
+#pragma unroll
+    for (uint32_t w = 0; w < 3; ++w)
+      if (w < wv) { base.x += s_wave[w].x; base.y += s_wave[w].y; }
+    s_base[threadIdx.x] = base;
+    __syncthreads();
+  }
   if (blockIdx.x < a.pair_groups) {  // ---- a thread per pair: its place, and its column in the items of its list ----
     const uint32_t l = l_pair;
     if (l >= a.nlists) return;
     const uint32_t len = a.list_len[l];
     if (len == 0) return;
     const uint32_t q = div_probes(i, a.P);
-    const uint32_t s0 = a.seg_start[l], cnt = a.seg_start[l + 1] - s0;
+    uint32_t cnt, it0;
+    if (a.local) {
+      const uint4 lc = a.local[l];
+      cnt = lc.x; it0 = s_base[l >> 6].x + lc.y;
+    } else {
+      const uint32_t s0 = a.seg_start[l];
+      cnt = a.seg_start[l + 1] - s0; it0 = a.item_start[l];
+    }
     const uint32_t pp = a.subprefix[subbin_index(l, q & (kSubBins - 1), a.nlists)] + rank;
     if (pp >= cnt) return;  // (never: the ranks are the histogram's own increments)
     a.pair_pos[i] = pp;
@@ -206,7 +234,7 @@ __global__ void __launch_bounds__(256) item_push_kernel(ItemPushArgs a) {
     // (chunk = pp / gq, by group_chunks' shift for the group widths in use)
     const uint32_t nchunk = group_chunks(cnt, gq), chunk = group_chunks(pp + 1u, gq) - 1u, col = pp - chunk * gq;
     const uint32_t g0 = a.qoff[q] + rel, r = i - q * a.P;
-    uint32_t item = a.item_start[l] + chunk;  // segment-major: segment s, chunk c = item_start + s * nchunk + c
+    uint32_t item = it0 + chunk;  // segment-major: segment s, chunk c = item_start + s * nchunk + c
     for (uint32_t s = 0; s < nseg; ++s, item += nchunk) {
       const size_t o = (size_t)item_workgroup(item, a.run, nitems) * gq + col;
       const uint32_t g = g0 + 2u * s, place = r | (s << 6);
@@ -220,9 +248,20 @@ __global__ void __launch_bounds__(256) item_push_kernel(ItemPushArgs a) {
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t l = (blockIdx.x - a.pair_groups) * (blockDim.x >> 6) + (threadIdx.x >> 6);
   if (l >= a.nlists) return;
-  const uint32_t s0 = a.seg_start[l], cnt = a.seg_start[l + 1] - s0;
-  if (cnt == 0) return;
-  const uint32_t len = a.list_len[l], fb = a.first_block[l], it0 = a.item_start[l], t0 = a.tile_start[l];
+  uint32_t cnt, it0, t0;
+  if (a.local) {
+    const uint4 lc = a.local[l];
+    const uint2 base = s_base[l >> 6];
+    cnt = lc.x; it0 = base.x + lc.y; t0 = base.y + lc.w;
+    if (lane == 0) a.tile_out[l] = t0;  // (every list, as group_prepare_kernel: the selects read it for every probe)
+    if (cnt == 0) return;
+  } else {
+    const uint32_t s0 = a.seg_start[l];
+    cnt = a.seg_start[l + 1] - s0;
+    if (cnt == 0) return;
+    it0 = a.item_start[l]; t0 = a.tile_start[l];
+  }
+  const uint32_t len = a.list_len[l], fb = a.first_block[l];
   uint32_t segb;
   const uint32_t nseg = list_segments(len, a.segb0, &segb);
   const uint32_t nchunk = group_chunks(cnt, gq), nblk = (len + 63u) / 64u, srec = seg_records(segb);
@@ -307,7 +346,8 @@ __device__ __forceinline__ void tile_dma_rank(float *tile, const float4 *src, co
 }
 
 __global__ void split_queries_kernel(const float *Q, uint32_t nq, uint32_t dim, uint32_t nc, uint4 *out, unsigned long long *any_lo,
-                                     uint32_t *zero, uint32_t zero_words, const float *mu, uint2 *out8, unsigned long long *not_i8);
+                                     uint32_t *zero, uint32_t zero_words, const float *mu, uint2 *out8, unsigned long long *not_i8,
+                                     uint64_t *counts);
 
 // NG = dq/2 exactly: a block holds 2*NG quads (dims padded to 16); dim % 4 == 0.  TABLE only names the instance
 // that ranks the centroid table (coarse step), so that profiles tell it from the list scan.
@@ -591,10 +631,14 @@ struct WideArgs {
 // out8 (or null: the lists have no int8 image): the int8 image of the batch for rank_stream_i8_kernel, q - 127 (0 past
 // dim), 32 ceil(dim / 32) bytes per query in dimension order; *not_i8 is raised when some value is not an integer in
 // 0..254 (the batch is then ranked with bf16)
+// counts: ws.stats — the grouping's counts (words [0, kStatListCounts) and kStatTiles128) are cleared here, for a grouping
+// whose every workgroup adds to them (list_totals_kernel with GroupScanArgs: no kernel of that chain can clear them first)
 __global__ void split_queries_kernel(const float *Q, uint32_t nq, uint32_t dim, uint32_t nc, uint4 *out, unsigned long long *any_lo,
-                                     uint32_t *zero, uint32_t zero_words, const float *mu, uint2 *out8, unsigned long long *not_i8) {
+                                     uint32_t *zero, uint32_t zero_words, const float *mu, uint2 *out8, unsigned long long *not_i8,
+                                     uint64_t *counts) {
   const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;  // (query, chunk, half)
   for (uint64_t i = t; i < zero_words; i += (uint64_t)gridDim.x * blockDim.x) zero[i] = 0u;
+  if (t < kStatListCounts + 1) counts[t < kStatListCounts ? t : kStatTiles128] = 0;
   if (t >= (uint64_t)nq * nc * 2) return;
   const uint32_t h = (uint32_t)(t & 1u);
   const uint64_t qc = t >> 1;
@@ -1003,8 +1047,9 @@ static vi_status build_query_image(const DeviceIndex &ix, const EngineKnobs &kn,
   VI_TRY(ws.qimg.reserve((uint64_t)nq * nc * 4 * 4));  // uint32 words: 4 pieces of 16 B per (query, chunk)
   const bool i8 = ix.lists_i8.p != nullptr;  // the lists have an int8 image: the batch's too (rank_stream_i8_kernel)
   if (i8) VI_TRY(ws.qimg8.reserve(std::max<uint64_t>(1, (uint64_t)nq * ((ix.dim + 31) / 32) * 8)));  // uint32 words: 32 B per (query, chunk of 32)
+  VI_TRY(ws.stats.reserve(kStatWords));
   if (!ws.stats_zeroed) {  // kStatQueryLo, kStatQueryNotI8 start at zero (both are read back with the
-    VI_TRY(ws.stats.reserve(kStatWords));  // grouping's counts) — reset by item_cols_kernel after their use
+                           // grouping's counts) — reset by item_cols_kernel after their use
     VI_HIP(hipMemsetAsync(ws.stats.p, 0, kStatWords * sizeof(uint64_t), st));
     ws.stats_zeroed = true;
   }
@@ -1012,7 +1057,8 @@ static vi_status build_query_image(const DeviceIndex &ix, const EngineKnobs &kn,
   hipLaunchKernelGGL(split_queries_kernel, dim3((uint32_t)((nt + 255) / 256)), dim3(256), 0, st, Qd, (uint32_t)nq, ix.dim, nc,
                      (uint4 *)ws.qimg.p, (unsigned long long *)(ws.stats.p + kStatQueryLo), zero, (uint32_t)zero_words,
                      ix.centered ? (const float *)ix.centre.p : nullptr, i8 ? (uint2 *)ws.qimg8.p : nullptr,
-                     (unsigned long long *)(ws.stats.p + kStatQueryNotI8));
+                     (unsigned long long *)(ws.stats.p + kStatQueryNotI8), ws.stats.p);
+  ws.group_counts_cleared = true;  // (rank_lists lowers it at the head of every search)
   VI_HIP(hipGetLastError());
   return VI_OK;
 }
@@ -1039,6 +1085,10 @@ vi_status launch_item_push(const DeviceIndex &ix, const uint32_t *probes, uint64
   a.probes = probes; a.pair_rank = pair_rank; a.subprefix = ws.cnt.p + subbin_words(nlists);
   a.list_len = ix.list_len.p; a.first_block = ix.list_first_block.p; a.seg_start = ws.seg_start.p; a.item_start = ws.item_start.p;
   a.tile_start = ws.tile_start.p; a.qoff = ws.qoff.p; a.rel = ws.pair_rel.p;
+  if (ws.lists_scanned_in_totals) {  // (launch_grouping: the lists' offsets come in two parts, list_totals_kernel's)
+    a.local = (const uint4 *)ws.list_local.p; a.block_sums = (const uint4 *)ws.list_block_sums.p; a.tile_out = ws.tile_start.p;
+    a.seg_start = a.item_start = a.tile_start = nullptr;  // (not written by this search)
+  }
   a.total = total; a.P = P; a.nlists = nlists; a.gq = gq; a.segb0 = segb0; a.run = run;
   a.pair_groups = (total + 255u) / 256u;
   a.cap_items = std::min<uint64_t>(std::min(ws.item_qcol.n, ws.item_grec.n) / gq, ws.item_sdesc.n / 4);
@@ -1098,7 +1148,7 @@ vi_status coarse_phase(const Batch &b, const uint32_t *probes_in, const uint32_t
     hipLaunchKernelGGL(pair_groups_kernel, dim3((uint32_t)((b.nq + 255) / 256)), dim3(256), 0, b.st, ws.probes.p,
                        b.ix.list_len.p, (uint32_t)b.nq, b.P, b.kn.segb0, ws.pair_rel.p, ws.qtot.p);
   }
-  // (the grouping's scan kernel scans the record offsets too, as a second workgroup)
+  // (the grouping scans the record offsets too: workgroups of list_totals_kernel, or the second of group_prepare_kernel)
   VI_HIP(hipGetLastError());
   return VI_OK;
 }
@@ -1128,7 +1178,8 @@ vi_status group_pairs(Batch &b, RankPlan &plan, GroupingCounts &hstats) {
   // the streaming kernel's work items come out of the scatter itself when the coarse select left every pair's rank
   b.items_pushed = b.kn.item_push && plan.kernel == RankKernel::Stream && ws.pair_rank_valid;
   VI_TRY(launch_grouping(b.ix, ws.probes.p, b.nq, b.P, (int)plan.gq, b.kn.segb0, hstats, b.st, true, ws.qtot.p, ws.qoff.p,
-                         ws.pair_rank_valid ? ws.pair_rank.p : nullptr, b.items_pushed ? b.kn.item_run : 0u));
+                         ws.pair_rank_valid ? ws.pair_rank.p : nullptr, b.items_pushed ? b.kn.item_run : 0u,
+                         b.kn.scan_in_totals && ws.group_counts_cleared));
   note_group_fill(ws, b.nq, b.P, hstats);
   ws.queries_hi_only = hstats[kStatQueryLo] == 0;
   complete_rank_plan(plan, b.kn, hstats);
@@ -1323,6 +1374,7 @@ static vi_status rank_lists(Batch &b, int timing_level, const uint32_t *probes_i
     VI_HIP(hipMemsetAsync(ws.stats.p + kStatClocks, 0, kStatClockCount * sizeof(uint64_t), st));
   }
   ws.pair_rank_valid = false;  // (set by the coarse select of THIS search)
+  ws.group_counts_cleared = false;  // (by the split_queries_kernel of THIS search)
   if (timing) VI_HIP(hipEventRecord(ix.cur().ev[0], st));
   VI_TRY(coarse_phase(b, probes_in, order_in));
   if (timing) VI_HIP(hipEventRecord(ix.cur().ev[1], st));

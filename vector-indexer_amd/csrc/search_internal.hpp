@@ -15,7 +15,8 @@ constexpr uint32_t kNarrowDim = 128;     // up to here the queries of a work ite
 // ---- SearchWorkspace::stats: the engines' block of 64-bit device counters, by word ----
 enum StatWord {
   // the grouping's counts: reset by list_totals_kernel, written by group_scan_kernel / group_prepare_kernel, read back by
-  // launch_grouping (the first three by search_valu_pipeline)
+  // launch_grouping (the first three by search_valu_pipeline).  With the scans inside list_totals_kernel (GroupScanArgs)
+  // its workgroups add to them instead: split_queries_kernel has cleared them, and kStatTiles128, at the head of the search
   kStatScannedVectors = 0,  // sum over the lists of (queries probing it) x (its length)
   kStatItems = 1,           // scan / rank work items
   kStatSegRuns = 2,         // segment runs awaiting seg_merge_kernel (VALU engine)
@@ -54,7 +55,15 @@ vi_status adopt_probes(const DeviceIndex &ix, uint64_t nq, uint32_t P, const uin
                        bool histogram, hipStream_t st);
 vi_status launch_grouping(const DeviceIndex &ix, const uint32_t *probes, uint64_t nq, uint32_t P, int qg, uint32_t segb0,
                           GroupingCounts &hstats, hipStream_t st, bool histogram_done, const uint32_t *qtot = nullptr,
-                          uint32_t *qoff = nullptr, const uint32_t *pair_rank = nullptr, uint32_t push_run = 0);
+                          uint32_t *qoff = nullptr, const uint32_t *pair_rank = nullptr, uint32_t push_run = 0,
+                          bool scan_in_totals = false);
+
+// The grouping's scans inside list_totals_kernel, completed by item_push_kernel (two launches, no group_prepare_kernel):
+// every workgroup of item_push_kernel scans the sums of the 64-list workgroups of list_totals_kernel itself, one per
+// thread — so at most this many of them (16 384 lists: every table the direct coarse select, which item_push_kernel
+// depends on, takes).  launch_grouping falls back to group_prepare_kernel above that.
+constexpr uint32_t kGroupScanBlocks = 256;
+inline bool group_scan_in_totals_applicable(uint64_t nlists) { return (nlists + 63) / 64 <= kGroupScanBlocks; }
 
 // a radius search's result as the engines fill it, chunk of queries after chunk: range_result_begin sizes lims;
 // range_result_place reads the hit counts of queries [q0, q0 + m) back (it synchronises), extends lims by them on the

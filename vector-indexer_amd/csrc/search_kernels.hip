@@ -379,12 +379,136 @@ __global__ void __launch_bounds__(kBlockThreads) coarse_merge_kernel(CoarseMerge
 // so no cursor_kernel reads the 32 counters of every list a second time
 constexpr uint32_t kTotalsLists = 64, kTotalsWaves = 4, kTotalsBins = kSubBins / kTotalsWaves;  // per workgroup / per wave
 static_assert(kTotalsBins * kTotalsWaves == kSubBins, "the waves of list_totals_kernel share the sub-bins evenly");
+
+// what a list probed by c queries adds to the grouping: pairs, work items, segment runs, record tiles — and (v4, optional)
+// to the counts vectors scanned, group records, tile blocks, tile blocks of a grouping by 128 queries
+struct ListGroupCounts { uint32_t seg, item, run, tile; };
+__device__ __forceinline__ ListGroupCounts list_group_counts(uint32_t c, uint32_t len, uint32_t qg, uint32_t segb0, unsigned long long *v4) {
+  uint32_t segb;
+  const uint32_t ns = list_segments(len, segb0, &segb);
+  const uint32_t chunks = group_chunks(c, qg);
+  if (v4) {
+    v4[0] += (unsigned long long)c * len;
+    v4[1] += 2ull * c * ns;
+    v4[2] += (unsigned long long)chunks * ((len + 63) / 64);
+    v4[3] += (unsigned long long)((c + 127) / 128) * ((len + 63) / 64);
+  }
+  return ListGroupCounts{c, chunks * ns, ns > 1 ? c * ns : 0u, chunks * ns * seg_records(segb)};
+}
+
+// The grouping's scans inside list_totals_kernel (GroupScanArgs::local set) instead of a launch of two single workgroups
+// behind it (group_prepare_kernel).  A list workgroup has the totals of its 64 lists in hand: wave 0 derives every
+// list's counts from them, scans them across its lanes and leaves per list (pairs, items / segment runs / record tiles of
+// the workgroup's lists before it), per workgroup the four sums, and adds its share of the grouping's counts to the
+// statistics.  What is then missing for an absolute offset — the sums of the workgroups before — is at most
+// kGroupScanBlocks values per quantity, which every workgroup of item_push_kernel scans for itself.  A few more
+// workgroups, behind the list workgroups, scan the queries' record totals into their offsets (scan_query_offsets).
+struct GroupScanArgs {
+  const uint32_t *list_len;
+  uint32_t qg, segb0;
+  uint4 *local;          // [nlists] pairs of the list; items, segment runs, record tiles before it within its 64 lists
+  uint4 *block_sums;     // [workgroups] pairs, items, segment runs, record tiles of the 64 lists
+  const uint32_t *qtot;  // the queries' record totals -> qoff[0..nq], qoff[nq] = their sum (both 16-byte aligned)
+  uint32_t *qoff;
+  uint32_t nq, q_tiles;  // ... by workgroups of q_tiles tiles each (qoff_tiles_per_block)
+};
+
+// qtot -> qoff by a few workgroups of 256 threads behind the list workgroups, each on its own run of whole tiles of 1024
+// words, [begin, end): a lane on four consecutive words of a tile (16-byte loads and stores, a wave on 1 KB).  What a
+// workgroup needs from the ones before it is one number, the sum of qtot[0, begin): it adds those words up itself — plain
+// coalesced loads in flight together with its own tiles' — so that no workgroup waits for another and the longest
+// dependent chain is one round: a DPP scan per tile and wave, the (tile, wave) sums through LDS, one barrier pair.
+// (At most kQoffBlocks workgroups, so that the words read twice stay below kQoffBlocks / 2 x nq.)
+constexpr uint32_t kQoffTiles = 4, kQoffBlocks = 16, kQoffTile = 4u * kTotalsLists * kTotalsWaves;  // tiles per round; words per tile
+static_assert((kQoffTiles + 1) * kTotalsWaves <= kTotalsWaves * kTotalsLists, "the (tile, wave) sums fit the kernel's LDS words");
+inline uint32_t qoff_tiles_per_block(uint32_t nq) { return ((nq + kQoffTile - 1) / kQoffTile + kQoffBlocks - 1) / kQoffBlocks; }
+__device__ __forceinline__ void scan_query_offsets(const uint32_t *qtot, uint32_t nq, uint32_t *qoff, uint32_t begin, uint32_t end,
+                                                   uint32_t *s_sum) {
+  const uint32_t t = threadIdx.x, lane = t & 63u, wave = t >> 6;
+  uint4 v[kQoffTiles];
+  auto load_round = [&](uint32_t r0) {
+#pragma unroll
+    for (uint32_t k = 0; k < kQoffTiles; ++k) {
+      const uint32_t i = r0 + k * kQoffTile + 4u * t;
+      v[k] = make_uint4(0u, 0u, 0u, 0u);
+      if (i + 4u <= end) v[k] = *reinterpret_cast<const uint4 *>(qtot + i);
+    }
+#pragma unroll
+    for (uint32_t k = 0; k < kQoffTiles; ++k) {  // (the last words of all: never a load past qtot[nq - 1])
+      const uint32_t i = r0 + k * kQoffTile + 4u * t;
+      if (i < end && i + 4u > end) {
+        v[k].x = qtot[i];
+        if (i + 1u < end) v[k].y = qtot[i + 1u];
+        if (i + 2u < end) v[k].z = qtot[i + 2u];
+      }
+    }
+  };
+  load_round(begin);
+  uint32_t head = 0;  // this lane's share of the words in front of the workgroup's (begin is a multiple of the tile)
+#pragma unroll 8
+  for (uint32_t i = 4u * t; i < begin; i += kQoffTile) {
+    const uint4 x = *reinterpret_cast<const uint4 *>(qtot + i);
+    head += x.x + x.y + x.z + x.w;
+  }
+  head = wave_incl_scan_u32(head);
+  if (lane == 63u) s_sum[kQoffTiles * kTotalsWaves + wave] = head;
+  uint32_t carry = 0;  // the sum of everything in front of the round
+  for (uint32_t r0 = begin; r0 < end; r0 += kQoffTiles * kQoffTile) {
+    if (r0 != begin) load_round(r0);
+    uint32_t before[kQoffTiles];  // the words of the tile in front of this lane's four, within its wave
+#pragma unroll
+    for (uint32_t k = 0; k < kQoffTiles; ++k) {
+      const uint32_t s = v[k].x + v[k].y + v[k].z + v[k].w, inc = wave_incl_scan_u32(s);
+      before[k] = inc - s;
+      if (lane == 63u) s_sum[k * kTotalsWaves + wave] = inc;
+    }
+    __syncthreads();
+    if (r0 == begin) {
+#pragma unroll
+      for (uint32_t w = 0; w < kTotalsWaves; ++w) carry += s_sum[kQoffTiles * kTotalsWaves + w];
+    }
+    uint32_t run = carry;
+#pragma unroll
+    for (uint32_t k = 0; k < kQoffTiles; ++k) {
+#pragma unroll
+      for (uint32_t w = 0; w < kTotalsWaves; ++w) {
+        if (w == wave) before[k] += run;
+        run += s_sum[k * kTotalsWaves + w];
+      }
+    }
+    carry = run;
+#pragma unroll
+    for (uint32_t k = 0; k < kQoffTiles; ++k) {
+      const uint32_t i = r0 + k * kQoffTile + 4u * t;
+      const uint4 o = make_uint4(before[k], before[k] + v[k].x, before[k] + v[k].x + v[k].y, before[k] + v[k].x + v[k].y + v[k].z);
+      if (i + 4u <= end) *reinterpret_cast<uint4 *>(qoff + i) = o;
+      else if (i < end) {
+        qoff[i] = o.x;
+        if (i + 1u < end) qoff[i + 1u] = o.y;
+        if (i + 2u < end) qoff[i + 2u] = o.z;
+      }
+    }
+    __syncthreads();  // (the next round writes the sums again)
+  }
+  if (end == nq && t == 0) qoff[nq] = carry;  // (the last workgroup)
+}
+
+// (SCANS: with GroupScanArgs — an instantiation of its own, so that the query scan's registers, a round of tiles, do not
+// lower the occupancy of the plain form on tables of thousands of workgroups)
+template <bool SCANS>
 __global__ void __launch_bounds__(kTotalsLists * kTotalsWaves) list_totals_kernel(const uint32_t *cnt, uint32_t nlists, uint32_t *tot,
-                                                                                  uint64_t *stats, uint32_t *prefix) {
+                                                                                  uint64_t *stats, uint32_t *prefix, GroupScanArgs g) {
   __shared__ uint32_t s_part[kTotalsWaves][kTotalsLists];
   const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  if (SCANS && blockIdx.x * kTotalsLists >= nlists) {  // ---- the workgroups behind the lists: the queries' record offsets ----
+    const uint32_t span = g.q_tiles * kQoffTile, begin = (blockIdx.x - (nlists + kTotalsLists - 1) / kTotalsLists) * span;
+    scan_query_offsets(g.qtot, g.nq, g.qoff, begin, min(g.nq, begin + span), &s_part[0][0]);
+    return;
+  }
   const uint32_t l = blockIdx.x * kTotalsLists + lane;
-  if (stats && blockIdx.x == 0 && threadIdx.x < kStatListCounts + 1) stats[threadIdx.x < kStatListCounts ? threadIdx.x : kStatTiles128] = 0;
+  // (with the scans in this launch every workgroup ADDS to the counts: they were cleared ahead of it, by split_queries_kernel)
+  if (stats && !SCANS && blockIdx.x == 0 && threadIdx.x < kStatListCounts + 1) stats[threadIdx.x < kStatListCounts ? threadIdx.x : kStatTiles128] = 0;
+  const uint32_t len = (SCANS && wave == 0 && l < nlists) ? g.list_len[l] : 0u;  // (asked for with the counters)
   const uint32_t st = subbin_stride(nlists);
   uint32_t c[kTotalsBins], sum = 0;
 #pragma unroll
@@ -394,14 +518,36 @@ __global__ void __launch_bounds__(kTotalsLists * kTotalsWaves) list_totals_kerne
   }
   s_part[wave][lane] = sum;
   __syncthreads();
-  if (l >= nlists) return;
-  uint32_t run = 0, total = 0;  // the list's pairs in the sub-bins of the waves before this one, in all
+  uint32_t run = 0, total = 0;  // the list's pairs in the sub-bins of the waves before this one, in all (0 past the last list)
 #pragma unroll
   for (uint32_t w = 0; w < kTotalsWaves; ++w) {
     const uint32_t v = s_part[w][lane];
     if (w < wave) run += v;
     total += v;
   }
+  if (SCANS && wave == 0) {  // (wave-uniform: all 64 lanes scan, lists past the last as zeros)
+    unsigned long long v4[4] = {0, 0, 0, 0};  // vec, rec, mtile, mtile128
+    const ListGroupCounts p = list_group_counts(total, len, g.qg, g.segb0, v4);
+    const uint32_t is = wave_incl_scan_u32(p.seg), ii = wave_incl_scan_u32(p.item);
+    const uint32_t ir = wave_incl_scan_u32(p.run), it = wave_incl_scan_u32(p.tile);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      v4[0] += __shfl_xor(v4[0], o); v4[1] += __shfl_xor(v4[1], o); v4[2] += __shfl_xor(v4[2], o); v4[3] += __shfl_xor(v4[3], o);
+    }
+    if (l < nlists) g.local[l] = make_uint4(p.seg, ii - p.item, ir - p.run, it - p.tile);
+    if (lane == 63u) g.block_sums[blockIdx.x] = make_uint4(is, ii, ir, it);  // (the inclusive scans end here: the workgroup's sums)
+    // the workgroup's share of the seven counts, a lane per count: one atomic instruction (a workgroup without a probed
+    // list adds nothing)
+    const uint32_t sums[3] = {readlane_u(ii, 63), readlane_u(it, 63), readlane_u(ir, 63)};
+    constexpr uint32_t kWord[7] = {kStatScannedVectors, kStatGroupRecords, kStatTileBlocks, kStatTiles128, kStatItems, kStatRecordTiles, kStatSegRuns};
+    unsigned long long add = 0;
+    uint32_t word = 0;
+#pragma unroll
+    for (uint32_t i = 0; i < 7; ++i)
+      if (lane == i) { add = i < 4 ? v4[i] : (unsigned long long)sums[i - 4]; word = kWord[i]; }
+    if (lane < 7u && add) atomicAdd((unsigned long long *)&stats[word], add);
+  }
+  if (l >= nlists) return;
   if (wave == 0) tot[l] = total;
   if (!prefix) return;
 #pragma unroll
@@ -439,19 +585,8 @@ __device__ __forceinline__ void group_scan_lists(const uint32_t *cnt, const uint
   // DPP scan per row and quantity, the carry from row to row.
   const uint32_t rows = ((nlists + 63u) / 64u + 15u) / 16u;  // rows of 64 lists per wave
   const uint32_t l_base = (uint32_t)wave * rows * 64u;
-  struct PerList { uint32_t seg, item, run, tile; };
-  auto per_list = [&](uint32_t c, uint32_t len, unsigned long long *v4) {
-    uint32_t segb;
-    const uint32_t ns = list_segments(len, segb0, &segb);
-    const uint32_t chunks = group_chunks(c, qg);
-    if (v4) {
-      v4[0] += (unsigned long long)c * len;
-      v4[1] += 2ull * c * ns;
-      v4[2] += (unsigned long long)chunks * ((len + 63) / 64);
-      v4[3] += (unsigned long long)((c + 127) / 128) * ((len + 63) / 64);
-    }
-    return PerList{c, chunks * ns, ns > 1 ? c * ns : 0u, chunks * ns * seg_records(segb)};
-  };
+  using PerList = ListGroupCounts;
+  auto per_list = [&](uint32_t c, uint32_t len, unsigned long long *v4) { return list_group_counts(c, len, qg, segb0, v4); };
   uint32_t seg = 0, item = 0, run = 0, tile = 0;  // this lane's column sums over the wave's rows
   unsigned long long v4[4] = {0, 0, 0, 0};        // vec, rec, mtile, mtile128
   for (uint32_t r0 = 0; r0 < rows; r0 += 8) {
@@ -1222,14 +1357,25 @@ vi_status device_index_from_rows(int device, int order, uint32_t dim, const floa
 // (relative_cursors: each sub-bin's start within its list instead, left by list_totals_kernel — one launch less)
 static vi_status launch_group_scan(const DeviceIndex &ix, uint32_t qg, uint32_t segb0, uint32_t *tile_start, hipStream_t st,
                                    bool reset_stats = false, const uint32_t *qtot = nullptr, uint32_t nq = 0, uint32_t *qoff = nullptr,
-                                   bool relative_cursors = false) {
+                                   bool relative_cursors = false, bool scan_in_totals = false) {
   SearchWorkspace &ws = ix.cur().ws;
   const uint32_t nlists = (uint32_t)ix.nlists;
   VI_TRY(ws.list_tot.reserve(std::max<uint32_t>(1, nlists)));
   const dim3 grid((nlists + 255) / 256), block(256);
   uint32_t *cursor = ws.cnt.p + subbin_words(nlists);
-  hipLaunchKernelGGL(list_totals_kernel, dim3((nlists + kTotalsLists - 1) / kTotalsLists), dim3(kTotalsLists * kTotalsWaves), 0, st, ws.cnt.p, nlists, ws.list_tot.p, reset_stats ? ws.stats.p : nullptr,
-                     relative_cursors ? cursor : nullptr);
+  const uint32_t list_blocks = (nlists + kTotalsLists - 1) / kTotalsLists;
+  if (scan_in_totals) {  // (the caller has checked: at most kGroupScanBlocks workgroups of lists, the counts cleared, qtot given)
+    VI_TRY(ws.list_local.reserve(4ull * std::max<uint32_t>(1, nlists)));
+    VI_TRY(ws.list_block_sums.reserve(4ull * kGroupScanBlocks));
+    const uint32_t q_tiles = std::max(1u, qoff_tiles_per_block(nq)), q_blocks = std::max(1u, (nq + q_tiles * kQoffTile - 1) / (q_tiles * kQoffTile));
+    const GroupScanArgs g{ix.list_len.p, qg, segb0, (uint4 *)ws.list_local.p, (uint4 *)ws.list_block_sums.p, qtot, qoff, nq, q_tiles};
+    hipLaunchKernelGGL(list_totals_kernel<true>, dim3(list_blocks + q_blocks), dim3(kTotalsLists * kTotalsWaves), 0, st, ws.cnt.p, nlists, ws.list_tot.p,
+                       ws.stats.p, cursor, g);
+    VI_HIP(hipGetLastError());
+    return VI_OK;
+  }
+  hipLaunchKernelGGL(list_totals_kernel<false>, dim3(list_blocks), dim3(kTotalsLists * kTotalsWaves), 0, st, ws.cnt.p, nlists, ws.list_tot.p, reset_stats ? ws.stats.p : nullptr,
+                     relative_cursors ? cursor : nullptr, GroupScanArgs{});
   if (qtot)  // (+ the queries' record offsets: a second workgroup of the same launch)
     hipLaunchKernelGGL(group_prepare_kernel, dim3(2), dim3(1024), 0, st, ws.list_tot.p, ix.list_len.p, nlists, qg, segb0,
                        ws.seg_start.p, ws.item_start.p, ws.segrun_start.p, ws.stats.p, tile_start, qtot, nq, qoff);
@@ -1432,6 +1578,7 @@ EngineKnobs read_engine_knobs() {
   kn.rank_i8 = on("VI_RANK_I8");
   kn.item_run = (uint32_t)std::min(std::max(num("VI_ITEM_RUN", 8), 1), 256);
   kn.item_push = on("VI_ITEM_PUSH");
+  kn.scan_in_totals = on("VI_SCAN_IN_TOTALS");
   kn.stream_prof = getenv("VI_STREAM_PROF") != nullptr;
   kn.stream_prof_dump = getenv("VI_STREAM_PROF_DUMP");
   kn.filter_xmode = (uint32_t)num("VI_FILTER_XMODE", 0);
@@ -1673,7 +1820,7 @@ vi_status range_result_copy(const RangeResult &r, uint64_t *lims, float *D, int6
 // the histogram into coarse_merge_kernel).  Fills ws.{cnt,seg_start,item_start,segrun_start,pairs}.
 vi_status launch_grouping(const DeviceIndex &ix, const uint32_t *probes, uint64_t nq, uint32_t P, int qg, uint32_t segb0,
                           GroupingCounts &hstats, hipStream_t st, bool histogram_done, const uint32_t *qtot, uint32_t *qoff,
-                          const uint32_t *pair_rank, uint32_t push_run) {
+                          const uint32_t *pair_rank, uint32_t push_run, bool scan_in_totals) {
   SearchWorkspace &ws = ix.cur().ws;
   const uint64_t nlists = ix.nlists;
   const uint32_t total = (uint32_t)(nq * P);
@@ -1694,7 +1841,11 @@ vi_status launch_grouping(const DeviceIndex &ix, const uint32_t *probes, uint64_
   // (push_run: the scatter builds the streaming rank kernel's work items as well, item_push_kernel — the caller has
   //  checked what that needs: the pairs' ranks, the histogram, the record offsets)
   const bool push = push_run != 0 && pair_rank && histogram_done && qtot;
-  VI_TRY(launch_group_scan(ix, (uint32_t)qg, segb0, ws.tile_start.p, st, true, qtot, (uint32_t)nq, qoff, push));
+  // (scan_in_totals: the scans of the lists and the queries ride in list_totals_kernel, no group_prepare_kernel — where
+  //  item_push_kernel, which completes the lists' offsets, follows, and the caller has had the counts cleared)
+  const bool in_totals = push && scan_in_totals && group_scan_in_totals_applicable(nlists) && (((uintptr_t)qtot | (uintptr_t)qoff) & 15u) == 0;
+  ws.lists_scanned_in_totals = in_totals;  // (launch_item_push, also when group_pairs launches it a second time)
+  VI_TRY(launch_group_scan(ix, (uint32_t)qg, segb0, ws.tile_start.p, st, true, qtot, (uint32_t)nq, qoff, push, in_totals));
   // the host waits for the counts (grid size, scratch) while the scatter runs
   // (into page-locked memory: a copy to the caller's stack array is staged by the runtime and costs a few microseconds
   // more on the one synchronisation point of the pipeline)
