@@ -1,5 +1,5 @@
-"""GPU parity of the grouping in two launches (search_kernels.hip: list_totals_kernel with GroupScanArgs; filter_search.hip:
-item_push_kernel): a workgroup of list_totals_kernel leaves every list's counts relative to its 64 lists and the sums of
+"""GPU parity of the grouping in two launches (grouping.hip: list_totals_kernel with GroupScanArgs, then
+item_push_kernel — GroupingRoute::ScansPush): a workgroup of list_totals_kernel leaves every list's counts relative to its 64 lists and the sums of
 the 64, a few more workgroups scan the queries' record totals (a run of whole tiles each), and every workgroup of
 item_push_kernel scans the sums.  One small index of 1 150 clusters — 18 workgroups of lists, the last a partial one —
 and batches whose probes, taken from the oracle's own coarse step, leave one whole workgroup of 64 (non-empty) lists in
@@ -99,7 +99,7 @@ class Fixture:
         return self._probes[key]
 
     def counts(self, Q, segb):
-        """work items, scanned vectors, tile blocks of the batch (scan.hpp: list_segments; search_kernels.hip: list_group_counts)"""
+        """work items, scanned vectors, tile blocks of the batch (scan.hpp: list_segments; grouping.hip: list_group_counts)"""
         cnt = np.where(self.lens > 0, self.probed_by(Q), 0)
         nblk = (self.lens + 63) // 64
         sb = np.maximum((nblk + 63) // 64, segb)

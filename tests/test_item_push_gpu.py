@@ -1,4 +1,4 @@
-"""GPU parity of the grouping scatter that builds the streaming rank kernel's work items itself (filter_search.hip:
+"""GPU parity of the grouping scatter that builds the streaming rank kernel's work items itself (grouping.hip:
 item_push_kernel, VI_ITEM_PUSH): every pair writes its column of every work item it sits in, a wave per probed list
 writes the items' descriptors and the dead columns.  One small index with the shapes that matter — lists probed by more
 than 128 and more than 256 queries of the batch (several query groups, partial last groups), lists of several

@@ -51,10 +51,9 @@ struct SearchWorkspace {
   DevBuf<uint32_t> seg_start;   // [nlists+1]
   DevBuf<uint32_t> item_start;  // [nlists+1]
   DevBuf<uint32_t> segrun_start;  // [nlists+1]
-  // the scans inside list_totals_kernel (GroupScanArgs) instead of the three arrays above: per list (pairs; items, segment
+  // the scans inside list_totals_kernel (grouping.hip: GroupScanArgs) instead of the three arrays above: per list (pairs; items, segment
   // runs, record tiles before it within its 64 lists), per 64 lists their sums; item_push_kernel adds the two up
   DevBuf<uint32_t> list_local, list_block_sums;  // [nlists] x 4, [kGroupScanBlocks] x 4
-  bool lists_scanned_in_totals = false;     // ... by this search's grouping
   bool group_counts_cleared = false;        // the grouping's counts of ws.stats were cleared by this search's split_queries_kernel
   DevBuf<float> seg_run_dist;  // segment runs of long lists, merged by seg_merge_kernel
   DevBuf<uint32_t> seg_run_pos;
@@ -75,9 +74,9 @@ struct SearchWorkspace {
   DevBuf<uint32_t> pair_rank;               // a pair's place among the pairs of its (list, sub-bin): from the direct coarse select
   bool pair_rank_valid = false;             // ... filled by this search
   DevBuf<uint32_t> item_list;               // list of each rank work item
-  DevBuf<uint32_t> items;                   // ... or its whole descriptor (8 words), item_desc_kernel
+  DevBuf<uint32_t> items;                   // ... or its whole descriptor (8 words), item_desc_kernel (grouping.hip)
   DevBuf<uint64_t> prof;                    // diagnostic counters (VI_STREAM_PROF)
-  DevBuf<uint32_t> item_qcol, item_grec, item_sdesc;    // streaming rank kernel: per (item, column) the query / its group record (item_cols_kernel, item_push_kernel)
+  DevBuf<uint32_t> item_qcol, item_grec, item_sdesc;    // streaming rank kernel: per (item, column) the query / its group record (grouping.hip: item_cols_kernel, item_push_kernel)
   DevBuf<uint32_t> tile_start, pair_pos;    // pair records: first record tile of each list; position of a (query, probe) pair in its list
   DevBuf<float> gval;                       // group records: 4 smallest sub-block minima per (query, probe, segment, lane half)
   DevBuf<uint32_t> gpos;                    // ... and where each record belongs (probe rank | segment | lane half)

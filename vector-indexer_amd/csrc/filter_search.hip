@@ -25,6 +25,7 @@
 // list probed by every query and K = n_probe.
 //
 // Host side: which rank kernel a batch takes is decided first (RankPlan), then search_filter_pipeline runs its steps.
+// The grouping between the coarse step and the rank, and the kernels that build the rank work items, are grouping.hip's.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -35,6 +36,7 @@
 
 #include "device_index.hpp"
 #include "device_math.hpp"
+#include "grouping.hpp"
 #include "mfma_bf16.hpp"
 #include "rank_stream.hpp"
 #include "scan.hpp"
@@ -67,217 +69,6 @@ __global__ void pair_groups_kernel(const uint32_t *probes, const uint32_t *list_
     }
   }
   qtot[q] = run;
-}
-
-// list of every work item: keeps a 12-step dependent binary search out of each rank workgroup's prologue
-__global__ void item_list_kernel(const uint32_t *item_start, uint32_t nlists, uint32_t nitems, uint32_t *item_list) {
-  const uint32_t item = blockIdx.x * blockDim.x + threadIdx.x;
-  if (item >= nitems) return;
-  uint32_t lo = 0, hi = nlists;
-  while (hi - lo > 1) {
-    const uint32_t mid = (lo + hi) >> 1;
-    if (item_start[mid] <= item) lo = mid; else hi = mid;
-  }
-  item_list[item] = lo;
-}
-
-// everything a list-rank work item needs to know about itself, 32 bytes it reads with two wave-uniform loads instead
-// of a chain of five dependent ones (list -> offsets -> length -> ...) at the head of every workgroup:
-// {first pair, queries, first block of the list, b0, b1, segment, first record tile, -}
-// Workgroup -> item: the hardware deals workgroups to the 8 XCDs round-robin (workgroup w runs on XCD w % 8), and each
-// XCD has its own L2.  The query groups of one list segment stream the SAME blocks, so they are numbered next to each
-// other (segment-major) and dealt in runs of `run` items to one XCD: workgroup w = (cycle, r, x) -> item
-// cycle * 8 run + x * run + r.  They start together, the followers hit the L2 lines the first one brought in, and a
-// hit is faster than a miss, which keeps them together.  (run <= 1: workgroup w takes item w.)
-__global__ void item_desc_kernel(const uint32_t *item_start, const uint32_t *seg_start, const uint32_t *list_len,
-                                 const uint32_t *first_block, const uint32_t *tile_start, uint32_t nlists, uint32_t nitems,
-                                 uint32_t segb0, uint32_t gq, uint32_t run, uint4 *items) {
-  const uint32_t w = blockIdx.x * blockDim.x + threadIdx.x;
-  if (w >= nitems) return;
-  uint32_t item = w;
-  if (run > 1u) {
-    const uint32_t span = 8u * run, cycle = w / span;
-    if ((cycle + 1u) * span <= nitems) {  // (the last, partial cycle keeps its order)
-      const uint32_t in = w - cycle * span;
-      item = cycle * span + (in & 7u) * run + (in >> 3);
-    }
-  }
-  uint32_t lo = 0, hi = nlists;
-  while (hi - lo > 1) {
-    const uint32_t mid = (lo + hi) >> 1;
-    if (item_start[mid] <= item) lo = mid; else hi = mid;
-  }
-  const uint32_t l = lo;
-  const uint32_t s0 = seg_start[l], cnt = seg_start[l + 1] - s0, len = list_len[l];
-  uint32_t segb;
-  const uint32_t nseg = list_segments(len, segb0, &segb);
-  const uint32_t local = item - item_start[l];
-  const uint32_t nchunk = (cnt + gq - 1u) / gq;  // query groups of the list: its items are nchunk * nseg
-  const uint32_t seg = local / nchunk, chunk = local - seg * nchunk;
-  const uint32_t j0 = chunk * gq;
-  const uint32_t nblk = (len + 63u) / 64u, b0 = seg * segb, b1 = min(nblk, b0 + segb);
-  items[2 * (size_t)w] = make_uint4(s0 + j0, min(gq, cnt - j0), first_block[l], b0);
-  items[2 * (size_t)w + 1] = make_uint4(b1, seg, tile_start[l] + (chunk * nseg + seg) * seg_records(segb), 0u);
-}
-
-// Per (work item, column of its query group): the query, and where its group record goes — so that the rank
-// workgroup finds everything about an item at addresses it can compute from the item's index alone (no chain
-// descriptor -> pairs -> query offsets at the head of every item) — and the place word of the pair's two group records
-// (probe rank | segment << 6 | lane half << 13; every (pair, segment) sits in exactly one item).  One workgroup per
-// item; workgroup 0 also resets the rank kernel's work counter and the "a query has a lo plane" and "a query is no int8
-// image" flags of the next batch.
-__global__ void item_cols_kernel(const uint4 *items, const uint32_t *pairs, const uint32_t *qoff, const uint32_t *rel, uint32_t P,
-                                 uint32_t gq, uint32_t *qcol, uint32_t *grec, uint4 *sdesc, uint32_t *gmeta, uint64_t *stats) {
-  const uint32_t w = blockIdx.x;
-  const uint4 d0 = items[2 * (size_t)w], d1 = items[2 * (size_t)w + 1];
-  if (threadIdx.x == 0) {
-    sdesc[w] = make_uint4(d0.y, d0.z + d0.w, 2u * (d1.x - d0.w), d1.z);  // queries, first block, tiles, first record tile
-    if (w == 0) { stats[kStatQueryLo] = 0; stats[kStatQueryNotI8] = 0; }
-  }
-  if (w == 0 && threadIdx.x < kStatRankWorkCount) stats[kStatRankWork + kStatRankWorkStride * threadIdx.x] = 0;  // the rank kernel's work counters (one per XCD queue, 128 bytes apart)
-  for (uint32_t col = threadIdx.x; col < gq; col += blockDim.x) {
-    uint32_t q = ~0u, g = ~0u;
-    if (col < d0.y) {
-      const uint32_t slot = pairs[d0.x + col];
-      q = div_probes(slot, P);
-      g = qoff[q] + rel[slot] + 2u * d1.y;
-      const uint32_t place = (slot - q * P) | (d1.y << 6);
-      *reinterpret_cast<uint2 *>(gmeta + g) = make_uint2(place, place | (1u << 13));  // (g is even: 8-byte aligned)
-    }
-    qcol[(size_t)w * gq + col] = q;
-    grec[(size_t)w * gq + col] = g;
-  }
-}
-
-// The scatter and both kernels above in one launch, for the streaming rank kernel (VI_ITEM_PUSH=0: the chain above).
-// Every (query, probe) pair knows its list, and with the list its work items: the thread that places the pair among the
-// pairs of its list writes the pair's column of every item it sits in itself, instead of leaving `pairs` behind for
-// item_desc_kernel (a 12-step binary search per item for the list) and item_cols_kernel (items -> pairs -> qoff / rel,
-// three dependent loads) to find it again.  What a list owns rather than a pair — the items' descriptors, and the dead
-// columns behind the last query group of every segment, which the rank kernel reads as ~0 — is written by a wave per
-// probed list: the workgroups behind the pairs' (a giant list's dead columns are no work for one pair's thread).
-// subprefix: a sub-bin's start within the pairs of its list (list_totals_kernel).  The item and record buffers are sized
-// by counts the host reads back while this kernel runs: it is given their capacities as they are and leaves everything
-// but the resets alone when the batch needs more (group_pairs grows them and launches it again).
-struct ItemPushArgs {
-  const uint32_t *probes, *pair_rank, *subprefix, *list_len, *first_block, *seg_start, *item_start, *tile_start, *qoff, *rel;
-  uint32_t total, P, nlists, gq, segb0, run;
-  uint32_t pair_groups;      // workgroups [0, pair_groups): a thread per pair; behind them: a wave per list
-  uint64_t cap_items, cap_records;  // work items the column / descriptor buffers hold, group records gmeta holds
-  // the lists' offsets as list_totals_kernel leaves them when it scans itself (GroupScanArgs), or null (seg_start,
-  // item_start, tile_start as group_prepare_kernel wrote them): per list, relative to its 64 lists, and the sums of
-  // every 64 lists — scanned here by every workgroup.  tile_out: each list's absolute first record tile, for the selects
-  const uint4 *local, *block_sums;
-  uint32_t *tile_out;
-  uint32_t *pair_pos, *qcol, *grec, *gmeta;
-  uint4 *sdesc;
-  uint64_t *stats;
-};
-
-// workgroup of the rank kernel that takes `item`: the inverse of item_desc_kernel's dealing in runs to the XCDs
-__device__ __forceinline__ uint32_t item_workgroup(uint32_t item, uint32_t run, uint32_t nitems) {
-  if (run <= 1u) return item;
-  const uint32_t span = 8u * run, pow2 = (run & (run - 1u)) == 0u, sh = (uint32_t)__builtin_ctz(run);
-  const uint32_t cycle = pow2 ? item >> (sh + 3u) : item / span;
-  if ((cycle + 1u) * span > nitems) return item;  // (the last, partial cycle keeps its order)
-  const uint32_t in = item - cycle * span, x = pow2 ? in >> sh : in / run;
-  return cycle * span + (in - x * run) * 8u + x;
-}
-
-__global__ void __launch_bounds__(256) item_push_kernel(ItemPushArgs a) {
-  __shared__ uint2 s_base[kGroupScanBlocks];  // items, record tiles of the 64-list workgroups before each (a.local only)
-  __shared__ uint2 s_wave[4];
-  // the rank kernel's work counters and the batch flags of the next batch (their D2H copy is ahead of this kernel)
-  if (blockIdx.x == 0) {
-    if (threadIdx.x < kStatRankWorkCount) a.stats[kStatRankWork + kStatRankWorkStride * threadIdx.x] = 0;
-    if (threadIdx.x == 0) { a.stats[kStatQueryLo] = 0; a.stats[kStatQueryNotI8] = 0; }
-  }
-  // (the pair's own words are asked for ahead of the counts the test below waits for)
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  const bool pair = blockIdx.x < a.pair_groups && i < a.total;
-  const uint32_t l_pair = pair ? a.probes[i] : kNoPos, rank = pair ? a.pair_rank[i] : 0u, rel = pair ? a.rel[i] : 0u;
-  uint4 sums = make_uint4(0u, 0u, 0u, 0u);
-  if (a.local && threadIdx.x < (a.nlists + 63u) / 64u) sums = a.block_sums[threadIdx.x];
-  const uint64_t nitems64 = a.stats[kStatItems];
-  if (nitems64 > a.cap_items || a.stats[kStatGroupRecords] > a.cap_records) return;  // (every thread of the grid alike)
-  const uint32_t nitems = (uint32_t)nitems64, gq = a.gq;
-  if (a.local) {  // the exclusive scan of the 64-list sums, a thread per sum
-    const uint32_t wv = threadIdx.x >> 6, ii = wave_incl_scan_u32(sums.y), it = wave_incl_scan_u32(sums.w);
-    if ((threadIdx.x & 63u) == 63u) s_wave[wv] = make_uint2(ii, it);
-    __syncthreads();
-    uint2 base = make_uint2(ii - sums.y, it - sums.w);
-#pragma unroll
-    for (uint32_t w = 0; w < 3; ++w)
-      if (w < wv) { base.x += s_wave[w].x; base.y += s_wave[w].y; }
-    s_base[threadIdx.x] = base;
-    __syncthreads();
-  }
-  if (blockIdx.x < a.pair_groups) {  // ---- a thread per pair: its place, and its column in the items of its list ----
-    const uint32_t l = l_pair;
-    if (l >= a.nlists) return;
-    const uint32_t len = a.list_len[l];
-    if (len == 0) return;
-    const uint32_t q = div_probes(i, a.P);
-    uint32_t cnt, it0;
-    if (a.local) {
-      const uint4 lc = a.local[l];
-      cnt = lc.x; it0 = s_base[l >> 6].x + lc.y;
-    } else {
-      const uint32_t s0 = a.seg_start[l];
-      cnt = a.seg_start[l + 1] - s0; it0 = a.item_start[l];
-    }
-    const uint32_t pp = a.subprefix[subbin_index(l, q & (kSubBins - 1), a.nlists)] + rank;
-    if (pp >= cnt) return;  // (never: the ranks are the histogram's own increments)
-    a.pair_pos[i] = pp;
-    uint32_t segb;
-    const uint32_t nseg = list_segments(len, a.segb0, &segb);
-    // (chunk = pp / gq, by group_chunks' shift for the group widths in use)
-    const uint32_t nchunk = group_chunks(cnt, gq), chunk = group_chunks(pp + 1u, gq) - 1u, col = pp - chunk * gq;
-    const uint32_t g0 = a.qoff[q] + rel, r = i - q * a.P;
-    uint32_t item = it0 + chunk;  // segment-major: segment s, chunk c = item_start + s * nchunk + c
-    for (uint32_t s = 0; s < nseg; ++s, item += nchunk) {
-      const size_t o = (size_t)item_workgroup(item, a.run, nitems) * gq + col;
-      const uint32_t g = g0 + 2u * s, place = r | (s << 6);
-      a.qcol[o] = q;
-      a.grec[o] = g;
-      *reinterpret_cast<uint2 *>(a.gmeta + g) = make_uint2(place, place | (1u << 13));  // (g is even: 8-byte aligned)
-    }
-    return;
-  }
-  // ---- a wave per probed list: its items' descriptors, the dead columns of every segment's last query group ----
-  const uint32_t lane = threadIdx.x & 63u;
-  const uint32_t l = (blockIdx.x - a.pair_groups) * (blockDim.x >> 6) + (threadIdx.x >> 6);
-  if (l >= a.nlists) return;
-  uint32_t cnt, it0, t0;
-  if (a.local) {
-    const uint4 lc = a.local[l];
-    const uint2 base = s_base[l >> 6];
-    cnt = lc.x; it0 = base.x + lc.y; t0 = base.y + lc.w;
-    if (lane == 0) a.tile_out[l] = t0;  // (every list, as group_prepare_kernel: the selects read it for every probe)
-    if (cnt == 0) return;
-  } else {
-    const uint32_t s0 = a.seg_start[l];
-    cnt = a.seg_start[l + 1] - s0;
-    if (cnt == 0) return;
-    it0 = a.item_start[l]; t0 = a.tile_start[l];
-  }
-  const uint32_t len = a.list_len[l], fb = a.first_block[l];
-  uint32_t segb;
-  const uint32_t nseg = list_segments(len, a.segb0, &segb);
-  const uint32_t nchunk = group_chunks(cnt, gq), nblk = (len + 63u) / 64u, srec = seg_records(segb);
-  for (uint32_t k = lane; k < nchunk * nseg; k += 64u) {
-    const uint32_t seg = k / nchunk, chunk = k - seg * nchunk;
-    const uint32_t b0 = seg * segb, b1 = min(nblk, b0 + segb);
-    // queries, first block, tiles, first record tile
-    a.sdesc[item_workgroup(it0 + k, a.run, nitems)] =
-        make_uint4(min(gq, cnt - chunk * gq), fb + b0, 2u * (b1 - b0), t0 + (chunk * nseg + seg) * srec);
-  }
-  const uint32_t last = nchunk - 1u, live = cnt - last * gq;
-  if (live == gq) return;
-  for (uint32_t seg = 0; seg < nseg; ++seg) {
-    const size_t o = (size_t)item_workgroup(it0 + seg * nchunk + last, a.run, nitems) * gq;
-    for (uint32_t col = live + lane; col < gq; col += 64u) { a.qcol[o + col] = ~0u; a.grec[o + col] = ~0u; }
-  }
 }
 
 __global__ void iota_kernel(uint32_t *p, uint32_t n) {
@@ -1072,34 +863,6 @@ vi_status coarse_only_filter(const DeviceIndex &ix, const EngineKnobs &kn, const
   return stage_coarse_filter(ix, kn, Qd, nq, P, st);
 }
 
-// the grouping's scatter for the streaming rank kernel (item_push_kernel), with the item and record buffers as they stand
-vi_status launch_item_push(const DeviceIndex &ix, const uint32_t *probes, uint64_t nq, uint32_t P, uint32_t gq, uint32_t segb0,
-                           uint32_t run, const uint32_t *pair_rank, hipStream_t st) {
-  SearchWorkspace &ws = ix.cur().ws;
-  const uint32_t nlists = (uint32_t)ix.nlists, total = (uint32_t)(nq * P);
-  VI_TRY(ws.item_qcol.reserve(1));  // (no null pointers; a first batch finds no room and is pushed again)
-  VI_TRY(ws.item_grec.reserve(1));
-  VI_TRY(ws.item_sdesc.reserve(4));
-  VI_TRY(ws.gpos.reserve(1));
-  ItemPushArgs a{};
-  a.probes = probes; a.pair_rank = pair_rank; a.subprefix = ws.cnt.p + subbin_words(nlists);
-  a.list_len = ix.list_len.p; a.first_block = ix.list_first_block.p; a.seg_start = ws.seg_start.p; a.item_start = ws.item_start.p;
-  a.tile_start = ws.tile_start.p; a.qoff = ws.qoff.p; a.rel = ws.pair_rel.p;
-  if (ws.lists_scanned_in_totals) {  // (launch_grouping: the lists' offsets come in two parts, list_totals_kernel's)
-    a.local = (const uint4 *)ws.list_local.p; a.block_sums = (const uint4 *)ws.list_block_sums.p; a.tile_out = ws.tile_start.p;
-    a.seg_start = a.item_start = a.tile_start = nullptr;  // (not written by this search)
-  }
-  a.total = total; a.P = P; a.nlists = nlists; a.gq = gq; a.segb0 = segb0; a.run = run;
-  a.pair_groups = (total + 255u) / 256u;
-  a.cap_items = std::min<uint64_t>(std::min(ws.item_qcol.n, ws.item_grec.n) / gq, ws.item_sdesc.n / 4);
-  a.cap_records = ws.gpos.n;
-  a.pair_pos = ws.pair_pos.p; a.qcol = ws.item_qcol.p; a.grec = ws.item_grec.p; a.gmeta = ws.gpos.p;
-  a.sdesc = (uint4 *)ws.item_sdesc.p; a.stats = ws.stats.p;
-  hipLaunchKernelGGL(item_push_kernel, dim3(std::max(1u, a.pair_groups + (nlists + 3u) / 4u)), dim3(256), 0, st, a);
-  VI_HIP(hipGetLastError());
-  return VI_OK;
-}
-
 // ------------------------------------------------------------------------------------------
 // the steps of search_filter_pipeline, in the order they run on the search stream
 // ------------------------------------------------------------------------------------------
@@ -1177,9 +940,12 @@ vi_status group_pairs(Batch &b, RankPlan &plan, GroupingCounts &hstats) {
   VI_TRY(ws.qoff.reserve(b.nq + 1));
   // the streaming kernel's work items come out of the scatter itself when the coarse select left every pair's rank
   b.items_pushed = b.kn.item_push && plan.kernel == RankKernel::Stream && ws.pair_rank_valid;
-  VI_TRY(launch_grouping(b.ix, ws.probes.p, b.nq, b.P, (int)plan.gq, b.kn.segb0, hstats, b.st, true, ws.qtot.p, ws.qoff.p,
-                         ws.pair_rank_valid ? ws.pair_rank.p : nullptr, b.items_pushed ? b.kn.item_run : 0u,
-                         b.kn.scan_in_totals && ws.group_counts_cleared));
+  GroupingRequest rq;
+  rq.probes = ws.probes.p; rq.nq = b.nq; rq.P = b.P; rq.qg = plan.gq; rq.segb0 = b.kn.segb0; rq.histogram_done = true;
+  rq.qtot = ws.qtot.p; rq.qoff = ws.qoff.p; rq.pair_rank = ws.pair_rank_valid ? ws.pair_rank.p : nullptr;
+  rq.push_run = b.items_pushed ? b.kn.item_run : 0u; rq.counts_cleared = b.kn.scan_in_totals && ws.group_counts_cleared;
+  rq.tile_start = rq.pair_pos = true;  // (the selects read both)
+  VI_TRY(group_probes(b.ix, rq, hstats, b.st));
   note_group_fill(ws, b.nq, b.P, hstats);
   ws.queries_hi_only = hstats[kStatQueryLo] == 0;
   complete_rank_plan(plan, b.kn, hstats);
@@ -1201,7 +967,7 @@ vi_status group_pairs(Batch &b, RankPlan &plan, GroupingCounts &hstats) {
   VI_TRY(grow(ws.item_grec, ncol));
   VI_TRY(grow(ws.item_sdesc, ndesc));
   VI_TRY(grow(ws.gpos, nrec));
-  return launch_item_push(b.ix, ws.probes.p, b.nq, b.P, plan.gq, b.kn.segb0, b.kn.item_run, ws.pair_rank.p, b.st);
+  return repush_items(b.ix, rq, b.st);
 }
 
 // ---- 3. rank on the matrix cores: one of the three below ----
@@ -1209,10 +975,8 @@ vi_status group_pairs(Batch &b, RankPlan &plan, GroupingCounts &hstats) {
 vi_status rank_wide(Batch &b, uint32_t nitems) {
   SearchWorkspace &ws = b.ws();
   const DeviceIndex &ix = b.ix;
-  VI_TRY(ws.item_list.reserve(std::max<uint32_t>(1, nitems)));
+  VI_TRY(launch_item_list(ix, nitems, b.st));
   if (nitems) {
-    hipLaunchKernelGGL(item_list_kernel, dim3((nitems + 255) / 256), dim3(256), 0, b.st, ws.item_start.p, (uint32_t)ix.nlists, nitems,
-                       ws.item_list.p);
     WideArgs a{(const uint4 *)ix.lists_bf16.p, b.flt ? b.flt->xnorm_img.p : ix.xnorm_img.p, (const uint4 *)ws.qimg.p, ix.dq / 4,
                ix.list_first_block.p, ix.list_len.p, ws.item_start.p, ws.seg_start.p, ws.pairs.p, ws.item_list.p, b.P, b.kn.segb0,
                ws.qoff.p, ws.pair_rel.p, ws.tile_start.p, (float4 *)ws.gval.p, ws.gpos.p, (float4 *)ws.brec.p};
@@ -1229,15 +993,7 @@ vi_status rank_wide(Batch &b, uint32_t nitems) {
 
 // the work items' descriptors, for both kernels of D <= 128
 vi_status describe_items(const Batch &b, uint32_t gq, uint32_t nitems) {
-  SearchWorkspace &ws = b.ws();
-  VI_TRY(ws.items.reserve(std::max<uint32_t>(1, nitems) * 8ull));
-  if (nitems) {
-    hipLaunchKernelGGL(item_desc_kernel, dim3((nitems + 255) / 256), dim3(256), 0, b.st, ws.item_start.p, ws.seg_start.p,
-                       b.ix.list_len.p, b.ix.list_first_block.p, ws.tile_start.p, (uint32_t)b.ix.nlists, nitems, b.kn.segb0, gq,
-                       b.kn.item_run, (uint4 *)ws.items.p);
-    VI_HIP(hipGetLastError());
-  }
-  return VI_OK;
+  return launch_item_desc(b.ix, b.kn, gq, nitems, b.st);
 }
 
 // (VI_STREAM_PROF) the streaming kernel's phase clocks, read back behind it: this step synchronises
@@ -1278,14 +1034,9 @@ vi_status rank_stream(Batch &b, const RankPlan &plan, uint32_t nitems) {
   SearchWorkspace &ws = b.ws();
   const DeviceIndex &ix = b.ix;
   const uint32_t gq = plan.gq;
-  if (!b.items_pushed) VI_TRY(describe_items(b, gq, nitems));
-  VI_TRY(ws.item_qcol.reserve(std::max<uint64_t>(1, (uint64_t)nitems * gq)));  // (pushed: sized by group_pairs)
-  VI_TRY(ws.item_grec.reserve(std::max<uint64_t>(1, (uint64_t)nitems * gq)));
-  VI_TRY(ws.item_sdesc.reserve(std::max<uint64_t>(1, (uint64_t)nitems * 4)));
-  if (nitems && !b.items_pushed) {
-    hipLaunchKernelGGL(item_cols_kernel, dim3(nitems), dim3(128), 0, b.st, (const uint4 *)ws.items.p, ws.pairs.p, ws.qoff.p,
-                       ws.pair_rel.p, b.P, gq, ws.item_qcol.p, ws.item_grec.p, (uint4 *)ws.item_sdesc.p, ws.gpos.p, ws.stats.p);
-    VI_HIP(hipGetLastError());
+  if (!b.items_pushed) {  // (pushed: the columns stand, in buffers sized by group_pairs)
+    VI_TRY(describe_items(b, gq, nitems));
+    VI_TRY(launch_item_cols(ix, b.P, gq, nitems, b.st));
   }
   if (plan.rank_i8) {
     RankStreamI8Args a{(const uint4 *)ix.lists_i8.p, b.flt ? b.flt->i8_norm_img.p : ix.i8_norm_img.p, (const uint4 *)ws.qimg8.p,

@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "device_index.hpp"
+#include "grouping.hpp"
 #include "scan.hpp"
 #include "search_internal.hpp"
 #include "slot_filter.hpp"
@@ -376,7 +377,10 @@ vi_status generic_sorted_rows(const DeviceIndex &ix, const float *Qd, uint64_t q
   const double avg_q_per_list = (double)m * P / (double)std::max<uint64_t>(1, nlists);
   const int qg = pick_qg(dq, avg_q_per_list, ix.order);
   GroupingCounts hstats;
-  VI_TRY(launch_grouping(ix, ws.probes.p + q0 * P, m, P, qg, segb0, hstats, st, false));
+  GroupingRequest rq;
+  rq.probes = ws.probes.p + q0 * P; rq.nq = m; rq.P = P; rq.qg = (uint32_t)qg; rq.segb0 = segb0;
+  rq.tile_start = rq.pair_pos = true;
+  VI_TRY(group_probes(ix, rq, hstats, st));
   stt.scan_items += hstats[kStatItems];
   ScanArgs a{};
   a.blocks = (const float4 *)ix.lists.blocks.p; a.dq = dq; a.dim = dim; a.Q = Qd + q0 * dim; a.nq = (uint32_t)m;

@@ -1,6 +1,7 @@
 // search_internal.hpp — what the search engines' translation units (search_kernels.hip, generic_search.hip,
-// filter_search.hip, select.hip, range_select.hip, rank_images.hip, list_build.hip) call in each other and share: declared once, here.
-// (filter_search.hip launches its rank and select phases through headers of their own: rank_stream.hpp, select.hpp)
+// filter_search.hip, grouping.hip, select.hip, range_select.hip, rank_images.hip, list_build.hip) call in each other and share:
+// declared once, here.  (The probe grouping is called through a header of its own, grouping.hpp; filter_search.hip launches
+// its rank and select phases through rank_stream.hpp and select.hpp.)
 #pragma once
 #include <array>
 #include <cstdint>
@@ -14,16 +15,16 @@ constexpr uint32_t kNarrowDim = 128;     // up to here the queries of a work ite
 
 // ---- SearchWorkspace::stats: the engines' block of 64-bit device counters, by word ----
 enum StatWord {
-  // the grouping's counts: reset by list_totals_kernel, written by group_scan_kernel / group_prepare_kernel, read back by
-  // launch_grouping (the first three by search_valu_pipeline).  With the scans inside list_totals_kernel (GroupScanArgs)
-  // its workgroups add to them instead: split_queries_kernel has cleared them, and kStatTiles128, at the head of the search
+  // the grouping's counts (grouping.hip): reset by list_totals_kernel, written by group_prepare_kernel, read back by
+  // group_probes.  With the scans inside list_totals_kernel (GroupScanArgs) its workgroups add to them instead:
+  // split_queries_kernel has cleared them, and kStatTiles128, at the head of the search
   kStatScannedVectors = 0,  // sum over the lists of (queries probing it) x (its length)
   kStatItems = 1,           // scan / rank work items
   kStatSegRuns = 2,         // segment runs awaiting seg_merge_kernel (VALU engine)
   kStatTileBlocks = 3,      // (query group, block) tiles of the MFMA list phase
   kStatGroupRecords = 4,    // group records
   kStatRecordTiles = 5,     // record tiles (pair records: 2 x gq each)
-  kStatListCounts = 6,      // ... words [0, 6): what the VALU engine clears itself
+  kStatListCounts = 6,      // ... words [0, 6): what list_totals_kernel resets (and kStatTiles128)
   // the selects' counters (VI_FILTER_STATS): cleared by search_filter_pipeline as [6, 12)
   kStatSelExact = 6,        // list select: vectors evaluated exactly; coarse select: single rows
   kStatSelScanned = 7,      // list select: groups scanned; coarse select: whole sub-blocks
@@ -53,17 +54,6 @@ vi_status init_device_index(DeviceIndex *ix, int device, uint32_t dim, uint64_t 
 vi_status stage_coarse(const DeviceIndex &ix, const float *Qd, uint64_t nq, uint32_t P, hipStream_t st);
 vi_status adopt_probes(const DeviceIndex &ix, uint64_t nq, uint32_t P, const uint32_t *probes_in, const uint32_t *order_in,
                        bool histogram, hipStream_t st);
-vi_status launch_grouping(const DeviceIndex &ix, const uint32_t *probes, uint64_t nq, uint32_t P, int qg, uint32_t segb0,
-                          GroupingCounts &hstats, hipStream_t st, bool histogram_done, const uint32_t *qtot = nullptr,
-                          uint32_t *qoff = nullptr, const uint32_t *pair_rank = nullptr, uint32_t push_run = 0,
-                          bool scan_in_totals = false);
-
-// The grouping's scans inside list_totals_kernel, completed by item_push_kernel (two launches, no group_prepare_kernel):
-// every workgroup of item_push_kernel scans the sums of the 64-list workgroups of list_totals_kernel itself, one per
-// thread — so at most this many of them (16 384 lists: every table the direct coarse select, which item_push_kernel
-// depends on, takes).  launch_grouping falls back to group_prepare_kernel above that.
-constexpr uint32_t kGroupScanBlocks = 256;
-inline bool group_scan_in_totals_applicable(uint64_t nlists) { return (nlists + 63) / 64 <= kGroupScanBlocks; }
 
 // a radius search's result as the engines fill it, chunk of queries after chunk: range_result_begin sizes lims;
 // range_result_place reads the hit counts of queries [q0, q0 + m) back (it synchronises), extends lims by them on the
@@ -72,11 +62,6 @@ vi_status range_result_begin(const DeviceIndex &ix, uint64_t nq, RangeResult *re
 vi_status range_result_place(RangeResult *res, uint64_t q0, uint64_t m, const uint32_t *counts_dev, hipStream_t st);
 
 // ---- filter_search.hip ----
-// the scatter of launch_grouping that also builds the streaming rank kernel's work items (item_push_kernel), dealt to the
-// XCDs in runs of `run`: it writes into the workspace's item and record buffers as they are and nothing when the
-// batch's counts exceed them — the caller compares the counts it reads back, grows the buffers and launches it again
-vi_status launch_item_push(const DeviceIndex &ix, const uint32_t *probes, uint64_t nq, uint32_t P, uint32_t gq, uint32_t segb0,
-                           uint32_t run, const uint32_t *pair_rank, hipStream_t st);
 vi_status range_filter_pipeline(const DeviceIndex &ix, const EngineKnobs &kn, const float *Qd, uint64_t nq, float radius2, uint32_t P,
                                 RangeResult *res, hipStream_t st, int timing_level, const SlotFilter *flt);
 vi_status search_filter_pipeline(const DeviceIndex &ix, const EngineKnobs &kn, const float *Qd, uint64_t nq, uint64_t k, uint32_t P,

@@ -13,7 +13,7 @@
 //                         sorted top-P list per query (DPP shift insertion)
 //   coarse_merge_kernel   one wave per query: S sorted partial runs -> probe list, shard
 //                         visiting order, histogram of probed lists
-//   group_*_kernel        counting sort of (query,probe) pairs by list  => every list block is
+//   grouping (grouping.hip)  counting sort of (query,probe) pairs by list  => every list block is
 //                         streamed once per group of QG queries that probe it
 //   scan_kernel<LISTS>    one wave = (list) x (group of <= QG queries probing it)
 //   final_merge_kernel    one wave per query: P sorted runs -> top-k, ids, tie keys
@@ -30,6 +30,7 @@
 
 #include "device_index.hpp"
 #include "device_math.hpp"
+#include "grouping.hpp"
 #include "scan.hpp"
 #include "search_internal.hpp"
 #include "slot_filter.hpp"
@@ -359,384 +360,6 @@ __global__ void __launch_bounds__(kBlockThreads) coarse_merge_kernel(CoarseMerge
     a.gorder[(size_t)q * a.P + lane] = live ? g : kNoPos;
     if (live && a.list_len[mylist] > 0) atomicAdd(&a.cnt[subbin_index(mylist, q & (kSubBins - 1), a.nlists)], 1u);
   }
-}
-
-// ------------------------------------------------------------------------------------------
-// grouping (counting sort of (query, probe) pairs by list)
-// ------------------------------------------------------------------------------------------
-// single block (cnt = the per-list totals of list_totals_kernel): exclusive scans over the lists of
-//   seg_start    Σ cnt                      (pairs grouped by list)
-//   item_start   Σ ceil(cnt/QG) * nseg      (scan work items)
-//   segrun_start Σ cnt * nseg [nseg > 1]    (segment runs awaiting seg_merge_kernel)
-// and the grouping's counts of ws.stats (StatWord, search_internal.hpp): Σ cnt*len, items, segment runs, ...
-// queries probing every list: the sum of its sub-bin counters.  A workgroup takes 64 lists, a lane per list (coalesced
-// along each sub-bin row), each of its four waves a quarter of the sub-bins; the quarters meet in LDS.  (One thread
-// walking all 32 counters of its list left 16 workgroups on the GPU at 4096 lists, each behind 32 loads of its own.)
-// (also resets the counters group_scan_kernel adds to — the grouping's counts — when `stats` is given: two memset
-// launches less on a path made of 5-microsecond kernels)
-// `prefix` (optional): where each sub-bin's pairs start within the pairs of their list, in the layout of the counters —
-// every count is in hand here, and the scatter that builds the work items (item_push_kernel) adds seg_start itself,
-// so no cursor_kernel reads the 32 counters of every list a second time
-constexpr uint32_t kTotalsLists = 64, kTotalsWaves = 4, kTotalsBins = kSubBins / kTotalsWaves;  // per workgroup / per wave
-static_assert(kTotalsBins * kTotalsWaves == kSubBins, "the waves of list_totals_kernel share the sub-bins evenly");
-
-// what a list probed by c queries adds to the grouping: pairs, work items, segment runs, record tiles — and (v4, optional)
-// to the counts vectors scanned, group records, tile blocks, tile blocks of a grouping by 128 queries
-struct ListGroupCounts { uint32_t seg, item, run, tile; };
-__device__ __forceinline__ ListGroupCounts list_group_counts(uint32_t c, uint32_t len, uint32_t qg, uint32_t segb0, unsigned long long *v4) {
-  uint32_t segb;
-  const uint32_t ns = list_segments(len, segb0, &segb);
-  const uint32_t chunks = group_chunks(c, qg);
-  if (v4) {
-    v4[0] += (unsigned long long)c * len;
-    v4[1] += 2ull * c * ns;
-    v4[2] += (unsigned long long)chunks * ((len + 63) / 64);
-    v4[3] += (unsigned long long)((c + 127) / 128) * ((len + 63) / 64);
-  }
-  return ListGroupCounts{c, chunks * ns, ns > 1 ? c * ns : 0u, chunks * ns * seg_records(segb)};
-}
-
-// The grouping's scans inside list_totals_kernel (GroupScanArgs::local set) instead of a launch of two single workgroups
-// behind it (group_prepare_kernel).  A list workgroup has the totals of its 64 lists in hand: wave 0 derives every
-// list's counts from them, scans them across its lanes and leaves per list (pairs, items / segment runs / record tiles of
-// the workgroup's lists before it), per workgroup the four sums, and adds its share of the grouping's counts to the
-// statistics.  What is then missing for an absolute offset — the sums of the workgroups before — is at most
-// kGroupScanBlocks values per quantity, which every workgroup of item_push_kernel scans for itself.  A few more
-// workgroups, behind the list workgroups, scan the queries' record totals into their offsets (scan_query_offsets).
-struct GroupScanArgs {
-  const uint32_t *list_len;
-  uint32_t qg, segb0;
-  uint4 *local;          // [nlists] pairs of the list; items, segment runs, record tiles before it within its 64 lists
-  uint4 *block_sums;     // [workgroups] pairs, items, segment runs, record tiles of the 64 lists
-  const uint32_t *qtot;  // the queries' record totals -> qoff[0..nq], qoff[nq] = their sum (both 16-byte aligned)
-  uint32_t *qoff;
-  uint32_t nq, q_tiles;  // ... by workgroups of q_tiles tiles each (qoff_tiles_per_block)
-};
-
-// qtot -> qoff by a few workgroups of 256 threads behind the list workgroups, each on its own run of whole tiles of 1024
-// words, [begin, end): a lane on four consecutive words of a tile (16-byte loads and stores, a wave on 1 KB).  What a
-// workgroup needs from the ones before it is one number, the sum of qtot[0, begin): it adds those words up itself — plain
-// coalesced loads in flight together with its own tiles' — so that no workgroup waits for another and the longest
-// dependent chain is one round: a DPP scan per tile and wave, the (tile, wave) sums through LDS, one barrier pair.
-// (At most kQoffBlocks workgroups, so that the words read twice stay below kQoffBlocks / 2 x nq.)
-constexpr uint32_t kQoffTiles = 4, kQoffBlocks = 16, kQoffTile = 4u * kTotalsLists * kTotalsWaves;  // tiles per round; words per tile
-static_assert((kQoffTiles + 1) * kTotalsWaves <= kTotalsWaves * kTotalsLists, "the (tile, wave) sums fit the kernel's LDS words");
-inline uint32_t qoff_tiles_per_block(uint32_t nq) { return ((nq + kQoffTile - 1) / kQoffTile + kQoffBlocks - 1) / kQoffBlocks; }
-__device__ __forceinline__ void scan_query_offsets(const uint32_t *qtot, uint32_t nq, uint32_t *qoff, uint32_t begin, uint32_t end,
-                                                   uint32_t *s_sum) {
-  const uint32_t t = threadIdx.x, lane = t & 63u, wave = t >> 6;
-  uint4 v[kQoffTiles];
-  auto load_round = [&](uint32_t r0) {
-#pragma unroll
-    for (uint32_t k = 0; k < kQoffTiles; ++k) {
-      const uint32_t i = r0 + k * kQoffTile + 4u * t;
-      v[k] = make_uint4(0u, 0u, 0u, 0u);
-      if (i + 4u <= end) v[k] = *reinterpret_cast<const uint4 *>(qtot + i);
-    }
-#pragma unroll
-    for (uint32_t k = 0; k < kQoffTiles; ++k) {  // (the last words of all: never a load past qtot[nq - 1])
-      const uint32_t i = r0 + k * kQoffTile + 4u * t;
-      if (i < end && i + 4u > end) {
-        v[k].x = qtot[i];
-        if (i + 1u < end) v[k].y = qtot[i + 1u];
-        if (i + 2u < end) v[k].z = qtot[i + 2u];
-      }
-    }
-  };
-  load_round(begin);
-  uint32_t head = 0;  // this lane's share of the words in front of the workgroup's (begin is a multiple of the tile)
-#pragma unroll 8
-  for (uint32_t i = 4u * t; i < begin; i += kQoffTile) {
-    const uint4 x = *reinterpret_cast<const uint4 *>(qtot + i);
-    head += x.x + x.y + x.z + x.w;
-  }
-  head = wave_incl_scan_u32(head);
-  if (lane == 63u) s_sum[kQoffTiles * kTotalsWaves + wave] = head;
-  uint32_t carry = 0;  // the sum of everything in front of the round
-  for (uint32_t r0 = begin; r0 < end; r0 += kQoffTiles * kQoffTile) {
-    if (r0 != begin) load_round(r0);
-    uint32_t before[kQoffTiles];  // the words of the tile in front of this lane's four, within its wave
-#pragma unroll
-    for (uint32_t k = 0; k < kQoffTiles; ++k) {
-      const uint32_t s = v[k].x + v[k].y + v[k].z + v[k].w, inc = wave_incl_scan_u32(s);
-      before[k] = inc - s;
-      if (lane == 63u) s_sum[k * kTotalsWaves + wave] = inc;
-    }
-    __syncthreads();
-    if (r0 == begin) {
-#pragma unroll
-      for (uint32_t w = 0; w < kTotalsWaves; ++w) carry += s_sum[kQoffTiles * kTotalsWaves + w];
-    }
-    uint32_t run = carry;
-#pragma unroll
-    for (uint32_t k = 0; k < kQoffTiles; ++k) {
-#pragma unroll
-      for (uint32_t w = 0; w < kTotalsWaves; ++w) {
-        if (w == wave) before[k] += run;
-        run += s_sum[k * kTotalsWaves + w];
-      }
-    }
-    carry = run;
-#pragma unroll
-    for (uint32_t k = 0; k < kQoffTiles; ++k) {
-      const uint32_t i = r0 + k * kQoffTile + 4u * t;
-      const uint4 o = make_uint4(before[k], before[k] + v[k].x, before[k] + v[k].x + v[k].y, before[k] + v[k].x + v[k].y + v[k].z);
-      if (i + 4u <= end) *reinterpret_cast<uint4 *>(qoff + i) = o;
-      else if (i < end) {
-        qoff[i] = o.x;
-        if (i + 1u < end) qoff[i + 1u] = o.y;
-        if (i + 2u < end) qoff[i + 2u] = o.z;
-      }
-    }
-    __syncthreads();  // (the next round writes the sums again)
-  }
-  if (end == nq && t == 0) qoff[nq] = carry;  // (the last workgroup)
-}
-
-// (SCANS: with GroupScanArgs — an instantiation of its own, so that the query scan's registers, a round of tiles, do not
-// lower the occupancy of the plain form on tables of thousands of workgroups)
-template <bool SCANS>
-__global__ void __launch_bounds__(kTotalsLists * kTotalsWaves) list_totals_kernel(const uint32_t *cnt, uint32_t nlists, uint32_t *tot,
-                                                                                  uint64_t *stats, uint32_t *prefix, GroupScanArgs g) {
-  __shared__ uint32_t s_part[kTotalsWaves][kTotalsLists];
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  if (SCANS && blockIdx.x * kTotalsLists >= nlists) {  // ---- the workgroups behind the lists: the queries' record offsets ----
-    const uint32_t span = g.q_tiles * kQoffTile, begin = (blockIdx.x - (nlists + kTotalsLists - 1) / kTotalsLists) * span;
-    scan_query_offsets(g.qtot, g.nq, g.qoff, begin, min(g.nq, begin + span), &s_part[0][0]);
-    return;
-  }
-  const uint32_t l = blockIdx.x * kTotalsLists + lane;
-  // (with the scans in this launch every workgroup ADDS to the counts: they were cleared ahead of it, by split_queries_kernel)
-  if (stats && !SCANS && blockIdx.x == 0 && threadIdx.x < kStatListCounts + 1) stats[threadIdx.x < kStatListCounts ? threadIdx.x : kStatTiles128] = 0;
-  const uint32_t len = (SCANS && wave == 0 && l < nlists) ? g.list_len[l] : 0u;  // (asked for with the counters)
-  const uint32_t st = subbin_stride(nlists);
-  uint32_t c[kTotalsBins], sum = 0;
-#pragma unroll
-  for (uint32_t u = 0; u < kTotalsBins; ++u) {
-    c[u] = l < nlists ? cnt[(wave * kTotalsBins + u) * st + l] : 0u;
-    sum += c[u];
-  }
-  s_part[wave][lane] = sum;
-  __syncthreads();
-  uint32_t run = 0, total = 0;  // the list's pairs in the sub-bins of the waves before this one, in all (0 past the last list)
-#pragma unroll
-  for (uint32_t w = 0; w < kTotalsWaves; ++w) {
-    const uint32_t v = s_part[w][lane];
-    if (w < wave) run += v;
-    total += v;
-  }
-  if (SCANS && wave == 0) {  // (wave-uniform: all 64 lanes scan, lists past the last as zeros)
-    unsigned long long v4[4] = {0, 0, 0, 0};  // vec, rec, mtile, mtile128
-    const ListGroupCounts p = list_group_counts(total, len, g.qg, g.segb0, v4);
-    const uint32_t is = wave_incl_scan_u32(p.seg), ii = wave_incl_scan_u32(p.item);
-    const uint32_t ir = wave_incl_scan_u32(p.run), it = wave_incl_scan_u32(p.tile);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      v4[0] += __shfl_xor(v4[0], o); v4[1] += __shfl_xor(v4[1], o); v4[2] += __shfl_xor(v4[2], o); v4[3] += __shfl_xor(v4[3], o);
-    }
-    if (l < nlists) g.local[l] = make_uint4(p.seg, ii - p.item, ir - p.run, it - p.tile);
-    if (lane == 63u) g.block_sums[blockIdx.x] = make_uint4(is, ii, ir, it);  // (the inclusive scans end here: the workgroup's sums)
-    // the workgroup's share of the seven counts, a lane per count: one atomic instruction (a workgroup without a probed
-    // list adds nothing)
-    const uint32_t sums[3] = {readlane_u(ii, 63), readlane_u(it, 63), readlane_u(ir, 63)};
-    constexpr uint32_t kWord[7] = {kStatScannedVectors, kStatGroupRecords, kStatTileBlocks, kStatTiles128, kStatItems, kStatRecordTiles, kStatSegRuns};
-    unsigned long long add = 0;
-    uint32_t word = 0;
-#pragma unroll
-    for (uint32_t i = 0; i < 7; ++i)
-      if (lane == i) { add = i < 4 ? v4[i] : (unsigned long long)sums[i - 4]; word = kWord[i]; }
-    if (lane < 7u && add) atomicAdd((unsigned long long *)&stats[word], add);
-  }
-  if (l >= nlists) return;
-  if (wave == 0) tot[l] = total;
-  if (!prefix) return;
-#pragma unroll
-  for (uint32_t u = 0; u < kTotalsBins; ++u) {
-    prefix[(wave * kTotalsBins + u) * st + l] = run;
-    run += c[u];
-  }
-}
-
-// where each sub-bin of a list scatters to: its own slice of the list's segment of `pairs`
-__global__ void cursor_kernel(const uint32_t *cnt, const uint32_t *seg_start, uint32_t nlists, uint32_t *cursor) {
-  const uint32_t l = blockIdx.x * blockDim.x + threadIdx.x;
-  if (l >= nlists) return;
-  const uint32_t st = subbin_stride(nlists);
-  uint32_t run = seg_start[l];
-#pragma unroll
-  for (uint32_t s = 0; s < kSubBins; ++s) {
-    cursor[s * st + l] = run;
-    run += cnt[s * st + l];
-  }
-}
-
-// the scan over the lists shared by group_scan_kernel and group_prepare_kernel (one workgroup of 1024 threads)
-__device__ __forceinline__ void group_scan_lists(const uint32_t *cnt, const uint32_t *list_len, uint32_t nlists, uint32_t qg,
-                                                 uint32_t segb0, uint32_t *seg_start, uint32_t *item_start, uint32_t *segrun_start,
-                                                 uint64_t *stats, uint32_t *tile_start, uint32_t *s_seg, uint32_t *s_item,
-                                                 uint32_t *s_run, uint32_t *s_tile) {
-  const uint32_t t = threadIdx.x;
-  const int lane = t & 63, wave = t >> 6;
-  // ---- lists (cnt = the per-list totals of list_totals_kernel, which also reset the counters added to below) ----
-  // Wave w owns the contiguous lists [w R 64, (w + 1) R 64) as R rows of 64, a lane per list: every load and store is one
-  // coalesced instruction, eight rows' loads in flight together.  (A thread walking its own 64 lists — 65 536 lists — read
-  // and wrote with a stride of 256 bytes between lanes, 64 cache lines per instruction, all from the one CU this scan runs
-  // on: 0.34 ms of a 4.9 ms search.)  Pass 1: the wave's totals; pass 2, behind the workgroup's prefix over the waves: a
-  // DPP scan per row and quantity, the carry from row to row.
-  const uint32_t rows = ((nlists + 63u) / 64u + 15u) / 16u;  // rows of 64 lists per wave
-  const uint32_t l_base = (uint32_t)wave * rows * 64u;
-  using PerList = ListGroupCounts;
-  auto per_list = [&](uint32_t c, uint32_t len, unsigned long long *v4) { return list_group_counts(c, len, qg, segb0, v4); };
-  uint32_t seg = 0, item = 0, run = 0, tile = 0;  // this lane's column sums over the wave's rows
-  unsigned long long v4[4] = {0, 0, 0, 0};        // vec, rec, mtile, mtile128
-  for (uint32_t r0 = 0; r0 < rows; r0 += 8) {
-    uint32_t cs[8], lens[8];
-#pragma unroll
-    for (uint32_t u = 0; u < 8; ++u) {
-      const uint32_t l = l_base + (r0 + u) * 64u + (uint32_t)lane;
-      const bool in = r0 + u < rows && l < nlists;
-      cs[u] = in ? cnt[l] : 0u;
-      lens[u] = in ? list_len[l] : 0u;
-    }
-#pragma unroll
-    for (uint32_t u = 0; u < 8; ++u) {
-      const PerList p = per_list(cs[u], lens[u], v4);  // (rows past the end: zeros)
-      seg += p.seg; item += p.item; run += p.run; tile += p.tile;
-    }
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    seg += (uint32_t)__shfl_xor((int)seg, o); item += (uint32_t)__shfl_xor((int)item, o);
-    run += (uint32_t)__shfl_xor((int)run, o); tile += (uint32_t)__shfl_xor((int)tile, o);
-    v4[0] += __shfl_xor(v4[0], o); v4[1] += __shfl_xor(v4[1], o); v4[2] += __shfl_xor(v4[2], o); v4[3] += __shfl_xor(v4[3], o);
-  }
-  if (lane == 0) {
-    s_seg[wave] = seg; s_item[wave] = item; s_run[wave] = run; s_tile[wave] = tile;
-    atomicAdd((unsigned long long *)&stats[kStatScannedVectors], v4[0]);
-    atomicAdd((unsigned long long *)&stats[kStatGroupRecords], v4[1]);
-    atomicAdd((unsigned long long *)&stats[kStatTileBlocks], v4[2]);
-    atomicAdd((unsigned long long *)&stats[kStatTiles128], v4[3]);
-  }
-  __syncthreads();
-  uint32_t rs = 0, ri = 0, rr = 0, rt = 0, tseg = 0, titem = 0, trun = 0, ttile = 0;
-  for (int w = 0; w < 16; ++w) {
-    if (w < wave) { rs += s_seg[w]; ri += s_item[w]; rr += s_run[w]; rt += s_tile[w]; }
-    tseg += s_seg[w]; titem += s_item[w]; trun += s_run[w]; ttile += s_tile[w];
-  }
-  for (uint32_t r0 = 0; r0 < rows; r0 += 8) {  // (the same values again, from L2 now)
-    uint32_t cs[8], lens[8];
-#pragma unroll
-    for (uint32_t u = 0; u < 8; ++u) {
-      const uint32_t l = l_base + (r0 + u) * 64u + (uint32_t)lane;
-      const bool in = r0 + u < rows && l < nlists;
-      cs[u] = in ? cnt[l] : 0u;
-      lens[u] = in ? list_len[l] : 0u;
-    }
-#pragma unroll
-    for (uint32_t u = 0; u < 8; ++u) {
-      if (r0 + u >= rows) break;  // (wave-uniform)
-      const uint32_t l = l_base + (r0 + u) * 64u + (uint32_t)lane;
-      const PerList p = per_list(cs[u], lens[u], nullptr);
-      const uint32_t is = wave_incl_scan_u32(p.seg), ii = wave_incl_scan_u32(p.item);
-      const uint32_t ir = wave_incl_scan_u32(p.run), it = wave_incl_scan_u32(p.tile);
-      if (l < nlists) {
-        seg_start[l] = rs + is - p.seg; item_start[l] = ri + ii - p.item; segrun_start[l] = rr + ir - p.run;
-        if (tile_start) tile_start[l] = rt + it - p.tile;
-      }
-      rs += readlane_u(is, 63); ri += readlane_u(ii, 63); rr += readlane_u(ir, 63); rt += readlane_u(it, 63);
-    }
-  }
-  if (t == 0) {
-    seg_start[nlists] = tseg;
-    item_start[nlists] = titem;
-    segrun_start[nlists] = trun;
-    stats[kStatItems] = titem;
-    stats[kStatSegRuns] = trun;
-    stats[kStatRecordTiles] = ttile;
-  }
-}
-
-__global__ void __launch_bounds__(1024) group_scan_kernel(const uint32_t *cnt, const uint32_t *list_len,
-                                                          uint32_t nlists, uint32_t qg, uint32_t segb0,
-                                                          uint32_t *seg_start, uint32_t *item_start,
-                                                          uint32_t *segrun_start, uint64_t *stats,
-                                                          uint32_t *tile_start) {
-  __shared__ uint32_t s_seg[16], s_item[16], s_run[16], s_tile[16];
-  group_scan_lists(cnt, list_len, nlists, qg, segb0, seg_start, item_start, segrun_start, stats, tile_start, s_seg, s_item, s_run, s_tile);
-}
-
-// group_scan_kernel (workgroup 0) and the queries' record offsets (workgroup 1: exclusive scan of qtot, qoff[nq] = total)
-// in one launch: both are single-workgroup scans, independent of each other.  (Folding list_totals and cursor in as well —
-// one workgroup reading all 32 sub-bins of every list twice — was measured: the grouping took twice as long.)
-__global__ void __launch_bounds__(1024) group_prepare_kernel(const uint32_t *cnt, const uint32_t *list_len, uint32_t nlists, uint32_t qg,
-                                                             uint32_t segb0, uint32_t *seg_start, uint32_t *item_start,
-                                                             uint32_t *segrun_start, uint64_t *stats, uint32_t *tile_start,
-                                                             const uint32_t *qtot, uint32_t nq, uint32_t *qoff) {
-  __shared__ uint32_t s_seg[16], s_item[16], s_run[16], s_tile[16];
-  const uint32_t t = threadIdx.x;
-  const int lane = t & 63, wave = t >> 6;
-  if (blockIdx.x == 1) {  // ---- query offsets ----
-    if (!qtot) return;
-    const uint32_t per = (nq + 1023) / 1024;
-    const uint32_t beg = min(nq, t * per), end = min(nq, beg + per);
-    uint32_t sum = 0;
-    for (uint32_t i = beg; i < end; ++i) sum += qtot[i];
-    uint32_t inc = sum;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const uint32_t x = (uint32_t)__shfl_up((int)inc, o);
-      if (lane >= o) inc += x;
-    }
-    if (lane == 63) s_seg[wave] = inc;
-    __syncthreads();
-    uint32_t w = 0, tot = 0;
-    for (int i = 0; i < 16; ++i) {
-      if (i < wave) w += s_seg[i];
-      tot += s_seg[i];
-    }
-    uint32_t run = w + inc - sum;
-    for (uint32_t i = beg; i < end; ++i) { qoff[i] = run; run += qtot[i]; }
-    if (t == 0) qoff[nq] = tot;
-    return;
-  }
-  group_scan_lists(cnt, list_len, nlists, qg, segb0, seg_start, item_start, segrun_start, stats, tile_start, s_seg, s_item, s_run, s_tile);
-}
-
-// (list ids are range-checked wherever they index: a caller-supplied probe list, vi_indexer_search_probed_device, is
-// validated up front by validate_probes_kernel, and a stray word can then still not fault the GPU)
-__global__ void histogram_kernel(const uint32_t *probes, const uint32_t *list_len, uint32_t nlists, uint32_t n, uint32_t P,
-                                 uint32_t *cnt) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const uint32_t l = probes[i];
-  if (l < nlists && list_len[l] > 0) atomicAdd(&cnt[subbin_index(l, div_probes(i, P) & (kSubBins - 1), nlists)], 1u);
-}
-
-__global__ void group_scatter_kernel(const uint32_t *probes, const uint32_t *list_len, uint32_t nlists, uint32_t P,
-                                     uint32_t *cursor, uint32_t *pairs, uint32_t total, const uint32_t *seg_start,
-                                     uint32_t *pair_pos) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= total) return;
-  const uint32_t l = probes[i];
-  if (l >= nlists || list_len[l] == 0) return;
-  const uint32_t pos = atomicAdd(&cursor[subbin_index(l, div_probes(i, P) & (kSubBins - 1), nlists)], 1u);
-  pairs[pos] = i;  // slot id = q*P + rank
-  if (pair_pos) pair_pos[i] = pos - seg_start[l];  // MFMA path: where the pair sits among the pairs of its list
-}
-
-// the same without atomics: the pair's place among the pairs of its (list, sub-bin) came back from the histogram
-// increment of the kernel that chose the probe (coarse_select_direct_kernel) — 320 000 returning atomics on counters
-// shared across the XCDs were most of the scatter's 17 us
-__global__ void group_scatter_ranked_kernel(const uint32_t *probes, const uint32_t *list_len, uint32_t nlists, uint32_t P,
-                                            const uint32_t *cursor, const uint32_t *pair_rank, uint32_t *pairs, uint32_t total,
-                                            const uint32_t *seg_start, uint32_t *pair_pos) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= total) return;
-  const uint32_t l = probes[i];
-  if (l >= nlists || list_len[l] == 0) return;
-  const uint32_t pos = cursor[subbin_index(l, div_probes(i, P) & (kSubBins - 1), nlists)] + pair_rank[i];
-  pairs[pos] = i;
-  if (pair_pos) pair_pos[i] = pos - seg_start[l];
 }
 
 // caller-supplied probe lists (multi-GPU: another rank's coarse step), one wave per row: every probe must name a list of
@@ -1353,40 +976,6 @@ vi_status device_index_from_rows(int device, int order, uint32_t dim, const floa
 // ------------------------------------------------------------------------------------------
 // pipeline stages
 // ------------------------------------------------------------------------------------------
-// histogram (ws.cnt) -> totals -> offsets of the lists in pairs / items / records -> scatter cursors
-// (relative_cursors: each sub-bin's start within its list instead, left by list_totals_kernel — one launch less)
-static vi_status launch_group_scan(const DeviceIndex &ix, uint32_t qg, uint32_t segb0, uint32_t *tile_start, hipStream_t st,
-                                   bool reset_stats = false, const uint32_t *qtot = nullptr, uint32_t nq = 0, uint32_t *qoff = nullptr,
-                                   bool relative_cursors = false, bool scan_in_totals = false) {
-  SearchWorkspace &ws = ix.cur().ws;
-  const uint32_t nlists = (uint32_t)ix.nlists;
-  VI_TRY(ws.list_tot.reserve(std::max<uint32_t>(1, nlists)));
-  const dim3 grid((nlists + 255) / 256), block(256);
-  uint32_t *cursor = ws.cnt.p + subbin_words(nlists);
-  const uint32_t list_blocks = (nlists + kTotalsLists - 1) / kTotalsLists;
-  if (scan_in_totals) {  // (the caller has checked: at most kGroupScanBlocks workgroups of lists, the counts cleared, qtot given)
-    VI_TRY(ws.list_local.reserve(4ull * std::max<uint32_t>(1, nlists)));
-    VI_TRY(ws.list_block_sums.reserve(4ull * kGroupScanBlocks));
-    const uint32_t q_tiles = std::max(1u, qoff_tiles_per_block(nq)), q_blocks = std::max(1u, (nq + q_tiles * kQoffTile - 1) / (q_tiles * kQoffTile));
-    const GroupScanArgs g{ix.list_len.p, qg, segb0, (uint4 *)ws.list_local.p, (uint4 *)ws.list_block_sums.p, qtot, qoff, nq, q_tiles};
-    hipLaunchKernelGGL(list_totals_kernel<true>, dim3(list_blocks + q_blocks), dim3(kTotalsLists * kTotalsWaves), 0, st, ws.cnt.p, nlists, ws.list_tot.p,
-                       ws.stats.p, cursor, g);
-    VI_HIP(hipGetLastError());
-    return VI_OK;
-  }
-  hipLaunchKernelGGL(list_totals_kernel<false>, dim3(list_blocks), dim3(kTotalsLists * kTotalsWaves), 0, st, ws.cnt.p, nlists, ws.list_tot.p, reset_stats ? ws.stats.p : nullptr,
-                     relative_cursors ? cursor : nullptr, GroupScanArgs{});
-  if (qtot)  // (+ the queries' record offsets: a second workgroup of the same launch)
-    hipLaunchKernelGGL(group_prepare_kernel, dim3(2), dim3(1024), 0, st, ws.list_tot.p, ix.list_len.p, nlists, qg, segb0,
-                       ws.seg_start.p, ws.item_start.p, ws.segrun_start.p, ws.stats.p, tile_start, qtot, nq, qoff);
-  else
-    hipLaunchKernelGGL(group_scan_kernel, dim3(1), dim3(1024), 0, st, ws.list_tot.p, ix.list_len.p, nlists, qg, segb0,
-                       ws.seg_start.p, ws.item_start.p, ws.segrun_start.p, ws.stats.p, tile_start);
-  if (!relative_cursors) hipLaunchKernelGGL(cursor_kernel, grid, block, 0, st, ws.cnt.p, ws.seg_start.p, nlists, cursor);
-  VI_HIP(hipGetLastError());
-  return VI_OK;
-}
-
 // 1+2: coarse scan over the centroid table, merge -> ws.probes / ws.gorder, histogram in ws.cnt
 vi_status stage_coarse(const DeviceIndex &ix, const float *Qd, uint64_t nq, uint32_t P, hipStream_t st) {
   SearchWorkspace &ws = ix.cur().ws;
@@ -1428,7 +1017,6 @@ vi_status adopt_probes(const DeviceIndex &ix, uint64_t nq, uint32_t P, const uin
   VI_TRY(ws.probes.reserve(nq * P));
   VI_TRY(ws.gorder.reserve(nq * P));
   VI_TRY(ws.probe_flag.reserve(1));
-  const uint32_t total = (uint32_t)(nq * P);
   VI_HIP(hipMemsetAsync(ws.probe_flag.p, 0, 4, st));
   hipLaunchKernelGGL(validate_probes_kernel, dim3((uint32_t)nq), dim3(64), ((P + 31u) / 32u) * 4u, st, probes_in, order_in, P,
                      (uint32_t)nlists, ws.probe_flag.p);
@@ -1442,13 +1030,7 @@ vi_status adopt_probes(const DeviceIndex &ix, uint64_t nq, uint32_t P, const uin
     return fail(VI_ERR_INVALID_INPUT, "probe lists out of range: every probe must be < %llu (or the empty marker 0xFFFFFFFF "
                 "after the last real probe of a row), and the orders of a row's real probes must be distinct and below "
                 "its number of real probes", (unsigned long long)nlists);
-  if (histogram) {
-    VI_TRY(ws.cnt.reserve(2 * subbin_words(nlists)));
-    VI_HIP(hipMemsetAsync(ws.cnt.p, 0, subbin_words(nlists) * sizeof(uint32_t), st));
-    hipLaunchKernelGGL(histogram_kernel, dim3((total + 255) / 256), dim3(256), 0, st, ws.probes.p, ix.list_len.p,
-                       (uint32_t)nlists, total, P, ws.cnt.p);
-    VI_HIP(hipGetLastError());
-  }
+  if (histogram) VI_TRY(launch_probe_histogram(ix, ws.probes.p, (uint32_t)(nq * P), P, st));
   return VI_OK;
 }
 
@@ -1477,25 +1059,11 @@ vi_status search_valu_pipeline(const DeviceIndex &ix, const EngineKnobs &kn, con
     if (f == 1 || f == 2 || f == 4 || (f == 8 && ix.order == VI_ORDER_SCALAR)) qg_l = (int)f;
   }
   const uint32_t kSegBlocks = kn.seg_blocks;
-  VI_TRY(ws.seg_start.reserve(nlists + 1));
-  VI_TRY(ws.item_start.reserve(nlists + 1));
-  VI_TRY(ws.pairs.reserve(nq * P));
-  VI_TRY(ws.segrun_start.reserve(nlists + 1));
-  VI_HIP(hipMemsetAsync(ws.stats.p, 0, kStatListCounts * sizeof(uint64_t), st));  // (the selects' counters behind them belong to the MFMA engine)
-  VI_TRY(launch_group_scan(ix, (uint32_t)qg_l, kSegBlocks, nullptr, st));
-  // exact work-item / segment-run counts size the scan grid and its scratch; the host waits for them while the
-  // scatter runs
-  uint64_t hstats[kStatSegRuns + 1] = {};
-  VI_HIP(hipMemcpyAsync(hstats, ws.stats.p, sizeof(hstats), hipMemcpyDeviceToHost, st));
-  VI_HIP(hipEventRecord(ix.cur().ev[5], st));
-  {
-    const uint32_t total = (uint32_t)(nq * P);
-    hipLaunchKernelGGL(group_scatter_kernel, dim3((total + 255) / 256), dim3(256), 0, st, ws.probes.p,
-                       ix.list_len.p, (uint32_t)nlists, P, ws.cnt.p + subbin_words(nlists), ws.pairs.p, total,
-                       ws.seg_start.p, (uint32_t *)nullptr);
-    VI_HIP(hipGetLastError());
-  }
-  VI_HIP(hipEventSynchronize(ix.cur().ev[5]));
+  // exact work-item / segment-run counts size the scan grid and its scratch (record tiles, pair positions: the MFMA engine's)
+  GroupingRequest rq;
+  rq.probes = ws.probes.p; rq.nq = nq; rq.P = P; rq.qg = (uint32_t)qg_l; rq.segb0 = kSegBlocks; rq.histogram_done = true;
+  GroupingCounts hstats;
+  VI_TRY(group_probes(ix, rq, hstats, st));
   stt.scanned_vectors = hstats[kStatScannedVectors];
   stt.scan_items = hstats[kStatItems];
   const uint64_t nsegruns = hstats[kStatSegRuns];
@@ -1813,56 +1381,6 @@ vi_status range_result_copy(const RangeResult &r, uint64_t *lims, float *D, int6
       VI_HIP(hipMemcpy(V + at * dim, Vd.p, n * dim * sizeof(float), hipMemcpyDeviceToHost));
     }
   }
-  return VI_OK;
-}
-
-// Counting sort of nq*P (query, probe) pairs by list for the generic path (the fast path folds
-// the histogram into coarse_merge_kernel).  Fills ws.{cnt,seg_start,item_start,segrun_start,pairs}.
-vi_status launch_grouping(const DeviceIndex &ix, const uint32_t *probes, uint64_t nq, uint32_t P, int qg, uint32_t segb0,
-                          GroupingCounts &hstats, hipStream_t st, bool histogram_done, const uint32_t *qtot, uint32_t *qoff,
-                          const uint32_t *pair_rank, uint32_t push_run, bool scan_in_totals) {
-  SearchWorkspace &ws = ix.cur().ws;
-  const uint64_t nlists = ix.nlists;
-  const uint32_t total = (uint32_t)(nq * P);
-  VI_TRY(ws.cnt.reserve(2 * subbin_words(nlists)));
-  VI_TRY(ws.seg_start.reserve(nlists + 1));
-  VI_TRY(ws.item_start.reserve(nlists + 1));
-  VI_TRY(ws.segrun_start.reserve(nlists + 1));
-  VI_TRY(ws.pairs.reserve(total));
-  VI_TRY(ws.pair_pos.reserve(total));
-  VI_TRY(ws.tile_start.reserve(nlists + 1));
-  VI_TRY(ws.stats.reserve(kStatWords));
-  // (the layout of ws.stats: StatWord, search_internal.hpp — the grouping's counts are reset by list_totals_kernel)
-  if (!histogram_done) {  // the coarse step of the fast paths leaves the histogram behind
-    VI_HIP(hipMemsetAsync(ws.cnt.p, 0, subbin_words(nlists) * sizeof(uint32_t), st));
-    hipLaunchKernelGGL(histogram_kernel, dim3((total + 255) / 256), dim3(256), 0, st, probes, ix.list_len.p,
-                       (uint32_t)nlists, total, P, ws.cnt.p);
-  }
-  // (push_run: the scatter builds the streaming rank kernel's work items as well, item_push_kernel — the caller has
-  //  checked what that needs: the pairs' ranks, the histogram, the record offsets)
-  const bool push = push_run != 0 && pair_rank && histogram_done && qtot;
-  // (scan_in_totals: the scans of the lists and the queries ride in list_totals_kernel, no group_prepare_kernel — where
-  //  item_push_kernel, which completes the lists' offsets, follows, and the caller has had the counts cleared)
-  const bool in_totals = push && scan_in_totals && group_scan_in_totals_applicable(nlists) && (((uintptr_t)qtot | (uintptr_t)qoff) & 15u) == 0;
-  ws.lists_scanned_in_totals = in_totals;  // (launch_item_push, also when group_pairs launches it a second time)
-  VI_TRY(launch_group_scan(ix, (uint32_t)qg, segb0, ws.tile_start.p, st, true, qtot, (uint32_t)nq, qoff, push, in_totals));
-  // the host waits for the counts (grid size, scratch) while the scatter runs
-  // (into page-locked memory: a copy to the caller's stack array is staged by the runtime and costs a few microseconds
-  // more on the one synchronisation point of the pipeline)
-  if (!ws.hstats_pinned) VI_HIP(hipHostMalloc((void **)&ws.hstats_pinned, kStatGroupingLanding * sizeof(uint64_t)));
-  VI_HIP(hipMemcpyAsync(ws.hstats_pinned, ws.stats.p, sizeof(GroupingCounts), hipMemcpyDeviceToHost, st));
-  VI_HIP(hipEventRecord(ix.cur().ev[5], st));
-  if (push)
-    VI_TRY(launch_item_push(ix, probes, nq, P, (uint32_t)qg, segb0, push_run, pair_rank, st));
-  else if (pair_rank && histogram_done)
-    hipLaunchKernelGGL(group_scatter_ranked_kernel, dim3((total + 255) / 256), dim3(256), 0, st, probes, ix.list_len.p,
-                       (uint32_t)nlists, P, ws.cnt.p + subbin_words(nlists), pair_rank, ws.pairs.p, total, ws.seg_start.p, ws.pair_pos.p);
-  else
-    hipLaunchKernelGGL(group_scatter_kernel, dim3((total + 255) / 256), dim3(256), 0, st, probes, ix.list_len.p,
-                       (uint32_t)nlists, P, ws.cnt.p + subbin_words(nlists), ws.pairs.p, total, ws.seg_start.p, ws.pair_pos.p);
-  VI_HIP(hipGetLastError());
-  VI_HIP(hipEventSynchronize(ix.cur().ev[5]));
-  std::memcpy(hstats.data(), ws.hstats_pinned, sizeof(GroupingCounts));
   return VI_OK;
 }
 
