@@ -192,6 +192,17 @@ vi_status vi_shard_get_centroid_vectors_from(const char *shards_dir, uint64_t sh
                                              uint32_t *dim_out, uint64_t *counts, float *centroid_out,
                                              uint64_t *metas_out, float *vecs_out);
 
+/* extension: append n_add records to lists of an existing shard file (the file half of vi_indexer_add_records on its own;
+ * needs no GPU).  Record i — internal id ids[i], external id ext_ids[i], stored timestamp timestamps[i], vector
+ * vecs[i, 0..dim) with dim read from the file — goes to the list of centroid_ids[i], behind the list's old records and
+ * behind the records of this call named before it.  The result is byte-identical to vi_shard_save_to of the merged lists;
+ * old records are copied verbatim.  The new file is written beside the old one under a temporary name and renamed over it
+ * when complete.  A centroid id the shard does not hold: VI_ERR_NOT_FOUND, and the file is untouched.  A file that cannot
+ * be read: the errors of vi_shard_get_centroid_vectors_from.  n_add == 0 leaves the file as it is. */
+vi_status vi_shard_append_to(const char *shards_dir, uint64_t shard_id, uint64_t n_add, const uint64_t *centroid_ids,
+                             const uint64_t *ids, const uint64_t *ext_ids, const uint64_t *timestamps,
+                             const float *vecs);
+
 /* ---- VectorIndexer (src/api.rs) ---------------------------------------------------- */
 /* mirrors VectorIndexerConfig — src/api.rs:8-54 — plus clearly marked extensions */
 typedef struct vi_config {
@@ -243,6 +254,35 @@ vi_status vi_indexer_build_from_records(vi_indexer *ix, const uint64_t *ext_ids,
                                         const uint64_t *timestamps, const uint32_t *dims, uint64_t n);
 /* VectorIndexer::build_from_vector_file(self, path) — src/api.rs:149-186 */
 vi_status vi_indexer_build_from_vector_file(vi_indexer *ix, const char *vector_file);
+
+/* extension (the reference has no add, api.rs:101-237): append n records to a built or loaded index.  Afterwards the index
+ * is the one the reference would search if each new record had been appended to the inverted list of its nearest kept
+ * centroid: "nearest" is the first probe of the reference's coarse step (ivf_index.rs:205-220: smallest
+ * euclidean_distance_squared in scalar order, ties to the lower centroid index).  The coarse table, index.bin and
+ * centroids_to_shard do not change and nothing is retrained, so the balance of the lists degrades as adds accumulate.
+ *   - order inside a list: old records keep their positions; new records follow in call order (ascending i); a second
+ *     call goes behind the first
+ *   - VectorMeta.id of new record i is N_before + i, N_before = vi_indexer_num_vectors before the call
+ *   - values: n x dimension; ext_ids: n (NULL => N_before + i); timestamps: n (NULL or 0 => cfg.now_secs, else wall clock);
+ *     duplicate external ids are not checked, as in a build
+ *   - files: every touched shard file is rewritten, byte-identical to vi_shard_save_to of the merged lists (old records
+ *     copied verbatim): all new files are written beside the old ones under temporary names, then renamed, and only then
+ *     is the resident index swapped; a failure before the renames leaves files and handle unchanged.  A later
+ *     vi_indexer_load of the directories gives the same index.  Cost: the touched shard files, plus one rebuild of the
+ *     resident images.
+ *   - resident index: rebuilt ON THE GPU from the old resident blocks and the new rows, not re-read from the files.  It
+ *     is a replaced index: every vi_filter made before the call is VI_ERR_INVALID_INPUT afterwards (free it), and
+ *     vi_range_results must be freed or copied before the call.  The call must not overlap searches on the handle, as for
+ *     a rebuild; this is not enforced.
+ *   - errors, all before any file or device change (VI_ERR_INVALID_INPUT): a null ix, values == NULL with n > 0, a
+ *     non-finite value, a handle with no index, a partitioned handle (world_size > 1: ranks reload from the files an
+ *     unpartitioned handle wrote), a total past 2^32 - 2 records or the 32-bit slot limit.  Files that no longer match the
+ *     resident lists: VI_ERR_INVALID_DATA.
+ *   - n == 0: VI_OK, nothing at all changes (old filters stay valid)
+ * Device memory: the old and the new resident index coexist until the swap (about twice what vi_indexer_load of the new
+ * index needs), beside the n uploaded rows (4 n D + 28 n bytes). */
+vi_status vi_indexer_add_records(vi_indexer *ix, const uint64_t *ext_ids, const float *values, const uint64_t *timestamps,
+                                 uint64_t n);
 
 /* VectorIndexer::search(&self, SearchRequest) — src/api.rs:188-222 — batched over nq queries
  * (extension: the reference takes one query per call; bindings/python/src/lib.rs:74-97 loops).
@@ -423,6 +463,20 @@ typedef struct vi_build_stats {
   float ms_total, ms_upload, ms_kmeans, ms_group, ms_super, ms_export, ms_index;
 } vi_build_stats;
 vi_status vi_indexer_last_build_stats(const vi_indexer *ix, vi_build_stats *out);
+/* the most recent vi_indexer_add_records on this handle that added something (wall-clock ms unless said otherwise) */
+typedef struct vi_add_stats {
+  uint64_t n;                /* records added */
+  uint64_t lists_touched;    /* lists that received records */
+  uint64_t shards_rewritten; /* shard files rewritten */
+  uint64_t bytes_written;    /* bytes of those files */
+  float ms_total;
+  float ms_assign;           /* upload, labels (coarse step), grouping by list */
+  float ms_files;            /* new shard files written and renamed */
+  float ms_index;            /* new resident index: append_blocks_kernel + the ranking images */
+  float ms_kernel;           /* HIP-event time of append_blocks_kernel alone (part of ms_index) ... */
+  uint64_t kernel_bytes;     /* ... and the bytes it read and wrote */
+} vi_add_stats;
+vi_status vi_indexer_last_add_stats(const vi_indexer *ix, vi_add_stats *out);
 
 /* stats of the most recent search on this handle (timing collected only if enabled) */
 vi_status vi_indexer_last_stats(const vi_indexer *ix, vi_search_stats *out);

@@ -2,8 +2,11 @@
 // extern "C" boundary declared in include/vi_amd.h.
 #include <sys/time.h>
 
+#include <unistd.h>
+
 #include <cmath>
 #include <cstring>
+#include <map>
 #include <memory>
 #include <new>
 #include <stdexcept>
@@ -29,6 +32,7 @@ struct Indexer {
   IndexMeta meta;                       // IvfIndex{centroids, centroids_to_shard, dimension}
   std::unique_ptr<DeviceIndex> dev;     // HBM-resident lists (null until load/build)
   vi_build_stats build_stats{};         // phases of the last build on this handle
+  vi_add_stats add_stats{};             // ... and of the last vi_indexer_add_records that added something
 };
 
 // No C++ exception may unwind through the C ABI into a Rust / ctypes caller (std::vector growth, std::string, a
@@ -188,6 +192,119 @@ static vi_status fit_and_save(Indexer *ix, const float *X, const uint64_t *ext_i
   bs.lists = kk;
   bs.shards = num_shards;
   return rc;
+}
+
+// vi_indexer_add_records behind its argument checks: labels on the GPU, the touched shard files written under temporary
+// names, the new resident index built from the old blocks, then the renames, then the swap.  Everything before the renames
+// can fail without a trace: the temporary files are removed, the handle keeps its index.
+static vi_status add_records(Indexer *ix, const uint64_t *ext_ids, const float *X, const uint64_t *timestamps, uint64_t n) {
+  const DeviceIndex &old = *ix->dev;
+  const uint32_t dim = ix->cfg.dimension;
+  const uint64_t nlists = old.nlists, n_before = old.nvec_resident;
+  const uint64_t now = ix->cfg.now_secs ? ix->cfg.now_secs : unix_timestamp_secs();
+  vi_add_stats as{};
+  as.n = n;
+  const double t0 = now_ms();
+  VI_HIP(hipSetDevice(old.device));
+  hipStream_t st = nullptr;
+  VI_HIP(hipStreamCreateWithFlags(&st, hipStreamDefault));
+  struct StreamGuard { hipStream_t s; ~StreamGuard() { (void)hipStreamDestroy(s); } } guard{st};
+  // what every new record carries in the files and on the device
+  std::vector<uint64_t> ids(n), ext(n), ts(n);
+  for (uint64_t i = 0; i < n; ++i) {
+    ids[i] = n_before + i;
+    ext[i] = ext_ids ? ext_ids[i] : n_before + i;
+    ts[i] = timestamps && timestamps[i] ? timestamps[i] : now;  // vector_store.rs:36-40
+  }
+  DevBuf<float> Xd;
+  DevBuf<uint64_t> ext_dev, ts_dev;
+  DevBuf<uint32_t> lab, order, seg_dev;
+  VI_TRY(Xd.reserve(n * dim));
+  VI_TRY(ext_dev.reserve(n));
+  VI_TRY(ts_dev.reserve(n));
+  VI_TRY(lab.reserve(n));
+  VI_HIP(hipMemcpyAsync(Xd.p, X, n * dim * sizeof(float), hipMemcpyHostToDevice, st));
+  VI_HIP(hipMemcpyAsync(ext_dev.p, ext.data(), n * 8, hipMemcpyHostToDevice, st));
+  VI_HIP(hipMemcpyAsync(ts_dev.p, ts.data(), n * 8, hipMemcpyHostToDevice, st));
+  VI_HIP(hipStreamSynchronize(st));
+  VI_TRY(device_index_label_rows(old, Xd.p, n, lab.p));
+  std::vector<uint64_t> seg;
+  VI_TRY(group_ids_by_label_device(lab.p, n, nlists, order, seg_dev, &seg, st));
+  std::vector<uint32_t> h_order(n), h_len(nlists);
+  VI_HIP(hipMemcpy(h_order.data(), order.p, n * 4, hipMemcpyDeviceToHost));
+  VI_HIP(hipMemcpy(h_len.data(), old.list_len.p, nlists * 4, hipMemcpyDeviceToHost));
+  if (seg.size() != nlists + 1 || seg[nlists] != n) return fail(VI_ERR_OTHER, "add: a record was assigned to no list");
+  {  // the slot limit of the new layout, before anything is written
+    uint64_t blocks = 0;
+    for (uint64_t l = 0; l < nlists; ++l) blocks += ((uint64_t)h_len[l] + (seg[l + 1] - seg[l]) + 63) / 64;
+    if (blocks >= 0xFFFFFFFFull / 64) return fail(VI_ERR_INVALID_INPUT, "index too large for 32-bit slot ids");
+  }
+  const double t1 = now_ms();
+  as.ms_assign = (float)(t1 - t0);
+
+  // ---- files: every touched shard under a temporary name ----
+  std::map<uint64_t, std::vector<uint32_t>> lists_of_shard;  // touched lists of every touched shard, ascending
+  for (uint64_t l = 0; l < nlists; ++l)
+    if (seg[l + 1] > seg[l]) { lists_of_shard[ix->meta.c2s[l]].push_back((uint32_t)l); ++as.lists_touched; }
+  std::vector<std::pair<std::string, std::string>> renames;  // (temporary, final)
+  auto drop_temporaries = [&] { for (auto &r : renames) ::unlink(r.first.c_str()); };
+  {
+    std::vector<uint64_t> s_cid, s_id, s_ext, s_ts;
+    std::vector<float> s_vec;
+    for (const auto &kv : lists_of_shard) {
+      const uint64_t s = kv.first;
+      ShardFile f;
+      vi_status rc = f.open(ix->shards_dir, s);
+      if (rc == VI_OK && f.dim() != dim) rc = fail(VI_ERR_INVALID_DATA, "shard_%llu.bin holds dimension %u", (unsigned long long)s, f.dim());
+      s_cid.clear(); s_id.clear(); s_ext.clear(); s_ts.clear(); s_vec.clear();
+      for (size_t li = 0; rc == VI_OK && li < kv.second.size(); ++li) {
+        const uint32_t l = kv.second[li];
+        const ShardListView *lv = f.find(l);
+        if (!lv || lv->num_vectors != h_len[l]) {  // (the resident blocks are what the old records are taken to be)
+          rc = fail(VI_ERR_INVALID_DATA, "shard_%llu.bin no longer matches the resident list %u", (unsigned long long)s, l);
+          break;
+        }
+        for (uint64_t e = seg[l]; e < seg[l + 1]; ++e) {
+          const uint32_t r = h_order[e];
+          s_cid.push_back(l); s_id.push_back(ids[r]); s_ext.push_back(ext[r]); s_ts.push_back(ts[r]);
+          s_vec.insert(s_vec.end(), X + (uint64_t)r * dim, X + (uint64_t)r * dim + dim);
+        }
+      }
+      const std::string path = shard_file_path(ix->shards_dir, s), tmp = path + ".tmp";
+      uint64_t bytes = 0;
+      if (rc == VI_OK)
+        rc = shard_append_write(f, s, s_cid.size(), s_cid.data(), s_id.data(), s_ext.data(), s_ts.data(), s_vec.data(), tmp,
+                                &bytes, nullptr);
+      if (rc != VI_OK) { drop_temporaries(); return rc; }
+      renames.emplace_back(tmp, path);
+      as.bytes_written += bytes;
+      ++as.shards_rewritten;
+    }
+  }
+  const double t2 = now_ms();
+
+  // ---- the new resident index, beside the old one ----
+  auto dev = std::make_unique<DeviceIndex>();
+  const vi_status rc = device_index_append(old, Xd.p, n, order.p, seg_dev.p, seg, ext_dev.p, ts_dev.p, dev.get(), &as.ms_kernel,
+                                           &as.kernel_bytes);
+  if (rc != VI_OK) { drop_temporaries(); return rc; }
+  const double t3 = now_ms();
+  as.ms_index = (float)(t3 - t2);
+
+  // ---- renames, then the swap ----
+  for (size_t i = 0; i < renames.size(); ++i)
+    if (::rename(renames[i].first.c_str(), renames[i].second.c_str()) != 0) {
+      const int e = errno;
+      for (size_t j = i; j < renames.size(); ++j) ::unlink(renames[j].first.c_str());
+      return fail(VI_ERR_IO, "rename(%s): %s%s", renames[i].first.c_str(), strerror(e),
+                  i ? " (earlier shard files of this call are already in place: reload the index)" : "");
+    }
+  ix->dev = std::move(dev);
+  const double t4 = now_ms();
+  as.ms_files = (float)((t2 - t1) + (t4 - t3));
+  as.ms_total = (float)(t4 - t0);
+  ix->add_stats = as;
+  return VI_OK;
 }
 
 }  // namespace vi
@@ -376,6 +493,15 @@ vi_status vi_shard_get_centroid_vectors_from(const char *shards_dir, uint64_t sh
   });
 }
 
+vi_status vi_shard_append_to(const char *shards_dir, uint64_t shard_id, uint64_t n_add, const uint64_t *centroid_ids,
+                             const uint64_t *ids, const uint64_t *ext_ids, const uint64_t *timestamps, const float *vecs) {
+  return vi::guarded([&]() -> vi_status {
+  if (!shards_dir) return fail(VI_ERR_INVALID_INPUT, "null pointer");
+  if (n_add && (!centroid_ids || !ids || !ext_ids || !timestamps || !vecs)) return fail(VI_ERR_INVALID_INPUT, "null pointer");
+  return vi::shard_append_to(shards_dir, shard_id, n_add, centroid_ids, ids, ext_ids, timestamps, vecs);
+  });
+}
+
 void vi_config_init(vi_config *cfg, uint32_t dimension) {
   std::memset(cfg, 0, sizeof(*cfg));
   cfg->dimension = dimension;
@@ -448,6 +574,28 @@ vi_status vi_indexer_build_from_vector_file(vi_indexer *ix, const char *vector_f
     ts[i] = recs[i].meta;  // VectorStore::new(vectors): third field is the timestamp (api.rs:181)
   }
   return vi::fit_and_save(&ix->impl, X.data(), eid.data(), ts.data(), recs.size());
+  });
+}
+
+vi_status vi_indexer_add_records(vi_indexer *ix, const uint64_t *ext_ids, const float *values, const uint64_t *timestamps,
+                                 uint64_t n) {
+  return vi::guarded([&]() -> vi_status {
+  if (!ix) return fail(VI_ERR_INVALID_INPUT, "null indexer");
+  if (n == 0) return VI_OK;  // nothing changes: no file, no index, no filter
+  if (!values) return fail(VI_ERR_INVALID_INPUT, "null values");
+  const uint32_t dim = ix->impl.cfg.dimension;
+  if (dim && n > ~0ull / 4 / dim) return fail(VI_ERR_INVALID_INPUT, "more than 2^32 - 2 vectors");
+  // a record is stored as it is and searched for ever: a NaN would poison every distance of its list
+  for (uint64_t i = 0; i < n * (uint64_t)dim; ++i)
+    if (!std::isfinite(values[i]))
+      return fail(VI_ERR_INVALID_INPUT, "non-finite value at flat index %llu", (unsigned long long)i);
+  if (!ix->impl.dev) return fail(VI_ERR_INVALID_INPUT, "the indexer holds no index (build or load it first)");
+  if (ix->impl.cfg.world_size > 1 || ix->impl.dev->stripe_world > 1)
+    return fail(VI_ERR_INVALID_INPUT, "records are added through an unpartitioned handle (world_size <= 1); ranks reload from its files");
+  if (ix->impl.dev->nlists == 0) return fail(VI_ERR_INVALID_INPUT, "the index has no list to add to");
+  if (n > 0xFFFFFFFEull || ix->impl.dev->nvec_resident + n > 0xFFFFFFFEull)
+    return fail(VI_ERR_INVALID_INPUT, "more than 2^32 - 2 vectors");
+  return vi::add_records(&ix->impl, ext_ids, values, timestamps, n);
   });
 }
 
@@ -746,6 +894,14 @@ vi_status vi_indexer_last_build_stats(const vi_indexer *ix, vi_build_stats *out)
   return vi::guarded([&]() -> vi_status {
   if (!ix || !out) return fail(VI_ERR_INVALID_INPUT, "no stats");
   *out = ix->impl.build_stats;
+  return VI_OK;
+  });
+}
+
+vi_status vi_indexer_last_add_stats(const vi_indexer *ix, vi_add_stats *out) {
+  return vi::guarded([&]() -> vi_status {
+  if (!ix || !out) return fail(VI_ERR_INVALID_INPUT, "no stats");
+  *out = ix->impl.add_stats;
   return VI_OK;
   });
 }

@@ -286,6 +286,19 @@ vi_status shard_export_device(const std::string &shards_dir, uint64_t shard_id, 
                               const float *X_dev, const uint32_t *order_dev, const uint64_t *ext_dev, const uint64_t *ts_dev,
                               uint64_t now, ShardExportWs &ws, hipStream_t st);
 
+// ---- appending records to a resident index (list_append.hip) ----
+// labels_dev[i] (device, n u32) = the list the reference's coarse step probes first for row i of rows_dev (device, n x dim):
+// the index's own coarse step with n_probe = 1, in chunks
+vi_status device_index_label_rows(const DeviceIndex &ix, const float *rows_dev, uint64_t n, uint32_t *labels_dev);
+// `out` = a fresh index holding the lists of `old` (unpartitioned; only read) with list l followed by rows
+// order_dev[seg[l] .. seg[l + 1]) of rows_dev (seg on the device and the host: group_ids_by_label_device); row_ext_dev /
+// row_ts_dev: external id and stored timestamp of every row.  Old blocks are copied device to device, nothing comes from
+// the shard files; old and new index coexist until the caller drops the old one.  ms_kernel / kernel_bytes (optional):
+// HIP-event time of append_blocks_kernel and the bytes it moves.
+vi_status device_index_append(const DeviceIndex &old, const float *rows_dev, uint64_t n, const uint32_t *order_dev,
+                              const uint32_t *seg_dev, const std::vector<uint64_t> &seg_host, const uint64_t *row_ext_dev,
+                              const uint64_t *row_ts_dev, DeviceIndex *out, float *ms_kernel, uint64_t *kernel_bytes);
+
 vi_status merge_partials_packed_device(int device, uint64_t nq, uint64_t k, uint32_t parts, const void *packed,
                                        float *D_out, int64_t *I_out);
 vi_status merge_partials_device(int device, uint64_t nq, uint64_t k, uint32_t parts, const float *D_parts,

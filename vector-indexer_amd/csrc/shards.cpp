@@ -10,6 +10,7 @@
 
 #include <cstdio>
 #include <cstring>
+#include <unordered_map>
 
 namespace vi {
 
@@ -143,6 +144,87 @@ vi_status shard_save_to(const std::string &shards_dir, uint64_t shard_id, uint32
   if (!f) return fail(VI_ERR_IO, "File::create(%s): %s", path.c_str(), strerror(errno));
   const bool ok = img.empty() || fwrite(img.data(), 1, img.size(), f) == img.size();
   if (fclose(f) != 0 || !ok) return fail(VI_ERR_IO, "write(%s) failed", path.c_str());
+  return VI_OK;
+}
+
+std::string shard_file_path(const std::string &shards_dir, uint64_t shard_id) { return shard_path(shards_dir, shard_id); }
+
+vi_status shard_append_write(const ShardFile &f, uint64_t shard_id, uint64_t n_add, const uint64_t *centroid_ids,
+                             const uint64_t *ids, const uint64_t *ext_ids, const uint64_t *timestamps, const float *vecs,
+                             const std::string &out_path, uint64_t *bytes_out, uint64_t *lists_out) {
+  const uint32_t dim = f.dim(), nl = f.num_lists();
+  const uint64_t vsz = 4ull * dim, pad = pad8(vsz), stride = record_stride(dim);
+  // the list of every added record: the first entry with its centroid id, as the reader finds it (shards.rs:257-265)
+  std::unordered_map<uint64_t, uint32_t> entry_of;
+  for (uint32_t i = nl; i-- > 0;) entry_of[f.list(i).centroid_id] = i;
+  std::vector<uint32_t> entry(n_add);
+  std::vector<uint64_t> added(nl, 0);
+  for (uint64_t i = 0; i < n_add; ++i) {
+    const auto it = entry_of.find(centroid_ids[i]);
+    if (it == entry_of.end()) return fail(VI_ERR_NOT_FOUND, "Centroid %llu not found", (unsigned long long)centroid_ids[i]);
+    entry[i] = it->second;
+    ++added[it->second];
+  }
+  const uint64_t data_off = kShardHeaderBytes + kIndexEntryBytes * (uint64_t)nl;
+  uint64_t total = data_off, touched = 0;
+  std::vector<uint64_t> next(nl);  // where the next added record of a list goes
+  for (uint32_t i = 0; i < nl; ++i) {
+    const uint64_t nv = (uint64_t)f.list(i).num_vectors + added[i];
+    if (nv > 0xFFFFFFFFull) return fail(VI_ERR_INVALID_INPUT, "list %llu would pass 2^32 - 1 records", (unsigned long long)f.list(i).centroid_id);
+    next[i] = total + vsz + pad + (uint64_t)f.list(i).num_vectors * stride;
+    total += vsz + pad + nv * stride;
+    touched += added[i] != 0;
+  }
+  std::vector<uint8_t> img(total, 0);
+  uint8_t *p = img.data();
+  auto put64 = [&](uint64_t off, uint64_t v) { std::memcpy(p + off, &v, 8); };
+  auto put32 = [&](uint64_t off, uint32_t v) { std::memcpy(p + off, &v, 4); };
+  put64(0, shard_id); put64(8, 1); put32(16, dim); put32(20, nl);
+  put64(24, kShardHeaderBytes); put64(32, data_off);
+  uint64_t cur = data_off;
+  for (uint32_t i = 0; i < nl; ++i) {
+    const ShardListView &lv = f.list(i);
+    const uint64_t nv = (uint64_t)lv.num_vectors + added[i];
+    const uint64_t size = vsz + pad + nv * stride;
+    const uint64_t e = kShardHeaderBytes + (uint64_t)i * kIndexEntryBytes;
+    put64(e, lv.centroid_id); put32(e + 8, (uint32_t)nv); put32(e + 12, 0);
+    put64(e + 16, cur); put64(e + 24, size);
+    std::memcpy(p + cur, lv.centroid, vsz);
+    if (lv.num_vectors) std::memcpy(p + cur + vsz + pad, lv.records, (uint64_t)lv.num_vectors * stride);  // verbatim
+    cur += size;
+  }
+  for (uint64_t i = 0; i < n_add; ++i) {
+    uint64_t &o = next[entry[i]];
+    put64(o, ids[i]); put64(o + 8, ext_ids[i]); put64(o + 16, timestamps[i]);
+    std::memcpy(p + o + kVectorMetaBytes, vecs + i * dim, vsz);
+    o += stride;
+  }
+  FILE *out = fopen(out_path.c_str(), "wb");
+  if (!out) return fail(VI_ERR_IO, "File::create(%s): %s", out_path.c_str(), strerror(errno));
+  const bool ok = img.empty() || fwrite(img.data(), 1, img.size(), out) == img.size();
+  if (fclose(out) != 0 || !ok) {
+    ::unlink(out_path.c_str());
+    return fail(VI_ERR_IO, "write(%s) failed", out_path.c_str());
+  }
+  if (bytes_out) *bytes_out = total;
+  if (lists_out) *lists_out = touched;
+  return VI_OK;
+}
+
+vi_status shard_append_to(const std::string &shards_dir, uint64_t shard_id, uint64_t n_add, const uint64_t *centroid_ids,
+                          const uint64_t *ids, const uint64_t *ext_ids, const uint64_t *timestamps, const float *vecs) {
+  const std::string path = shard_path(shards_dir, shard_id), tmp = path + ".tmp";
+  {
+    ShardFile f;
+    VI_TRY(f.open(shards_dir, shard_id));
+    if (n_add == 0) return VI_OK;
+    VI_TRY(shard_append_write(f, shard_id, n_add, centroid_ids, ids, ext_ids, timestamps, vecs, tmp, nullptr, nullptr));
+  }  // (unmapped before the rename)
+  if (::rename(tmp.c_str(), path.c_str()) != 0) {
+    const int e = errno;
+    ::unlink(tmp.c_str());
+    return fail(VI_ERR_IO, "rename(%s): %s", tmp.c_str(), strerror(e));
+  }
   return VI_OK;
 }
 

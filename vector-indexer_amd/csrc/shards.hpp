@@ -58,6 +58,21 @@ vi_status shard_save_to(const std::string &shards_dir, uint64_t shard_id, uint32
                         const uint64_t *list_off, const uint64_t *ids, const uint64_t *ext_ids,
                         const uint64_t *timestamps, const float *vecs);
 
+// Append records to lists of an open shard file: added record i goes to the FIRST list of the file that carries
+// centroid_ids[i], behind the list's old records and behind the added records named before it.  The merged file is
+// written to out_path — byte-identical to shard_save_to of the merged lists, the old records and centroid vectors copied
+// verbatim — and f's own file is left alone: the caller renames out_path over it when every file of its batch is
+// complete (api.cpp: vi_indexer_add_records).  A centroid id the file does not hold: NotFound, nothing written.
+// bytes_out / lists_out (optional): size of the file written, lists that received records.
+vi_status shard_append_write(const ShardFile &f, uint64_t shard_id, uint64_t n_add, const uint64_t *centroid_ids,
+                             const uint64_t *ids, const uint64_t *ext_ids, const uint64_t *timestamps, const float *vecs,
+                             const std::string &out_path, uint64_t *bytes_out, uint64_t *lists_out);
+// ... for one shard file on its own: open, write beside it under a temporary name, rename.  n_add == 0: the file is
+// opened (the reader's errors) and left as it is.
+vi_status shard_append_to(const std::string &shards_dir, uint64_t shard_id, uint64_t n_add, const uint64_t *centroid_ids,
+                          const uint64_t *ids, const uint64_t *ext_ids, const uint64_t *timestamps, const float *vecs);
+std::string shard_file_path(const std::string &shards_dir, uint64_t shard_id);
+
 // index/index.bin: IvfIndex{centroids, centroids_to_shard, dimension} through bincode 2
 // `config::standard()` + ndarray serde.  PARITY UNPINNED (no cargo here to confirm bytes).
 struct IndexMeta {

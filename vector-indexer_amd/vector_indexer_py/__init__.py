@@ -9,6 +9,7 @@ bindings/python/python/vector_indexer_py/__init__.py):
     VectorIndex.search(xq, k, n_probe)   (coroutine) -> (D f32[nq,k], I i64[nq,k])   +inf / -1 padded
     VectorIndex.search_sync(xq, k, n_probe)
     VectorIndex.dimension
+    VectorIndex.add(xb, ext_ids=None, timestamps=None)      extension: append records to a built or loaded index
 
 Errors surface as RuntimeError, as PyO3's PyRuntimeError does.  There is NO CPU fallback: if
 libvi_amd.so is missing or no MI355X is visible, build/load/search raise.
@@ -263,6 +264,31 @@ class VectorIndex:
         _native.check(lib().vi_indexer_last_stats(self._h, C.byref(st)))
         return getattr(st, field)
 
+    def add(self, xb, ext_ids=None, timestamps=None) -> None:
+        """extension: append the rows of xb to the index, each to the list of its nearest centroid (nothing is retrained),
+        in the shard files and on the GPU.  ext_ids None: num_vectors + i; timestamps None or 0: now.  Unpartitioned
+        indexes only.  Filters made before the call are rejected afterwards; RangeResults must be copied or freed before it;
+        the call must not overlap searches of this index."""
+        xb = np.asarray(xb)
+        if xb.ndim != 2:
+            raise RuntimeError("Array must be 2-dimensional")
+        if xb.shape[1] != self._dimension:
+            raise RuntimeError(f"Vector dimension {xb.shape[1]} doesn't match index dimension {self._dimension}")
+        xb = np.ascontiguousarray(xb, dtype=np.float32)
+        n = xb.shape[0]
+        e = None if ext_ids is None else _native.id_array(ext_ids)
+        t = None if timestamps is None else np.ascontiguousarray(timestamps, dtype=np.uint64).reshape(-1)
+        if (e is not None and e.size != n) or (t is not None and t.size != n):
+            raise RuntimeError("ext_ids and timestamps must have one entry per row")
+        _native.check(lib().vi_indexer_add_records(self._h, _native.ptr(e), _native.ptr(xb), _native.ptr(t), n),
+                      prefix="Failed to add records: ")
+
+    def add_stats(self) -> dict:
+        """phases of the most recent add() that added something"""
+        st = _native.AddStats()
+        _native.check(lib().vi_indexer_last_add_stats(self._h, C.byref(st)))
+        return {f: getattr(st, f) for f, _ in st._fields_}
+
     def build_stats(self) -> dict:
         st = _native.BuildStats()
         _native.check(lib().vi_indexer_last_build_stats(self._h, C.byref(st)))
@@ -335,10 +361,11 @@ def build(xb, work_dir: Optional[str] = None, *, nlist: int = 0, seed: int = 0, 
 
 
 def load(index_dir: str, shards_dir: str, dimension: int, *, device: int = 0, rank: int = 0,
-         world_size: int = 0, placement: int = 0) -> VectorIndex:
-    """load(index_dir, shards_dir, dimension) — lib.rs:291-304."""
+         world_size: int = 0, placement: int = 0, now_secs: int = 0) -> VectorIndex:
+    """load(index_dir, shards_dir, dimension) — lib.rs:291-304.  now_secs: the timestamp add() gives records without one
+    (0: wall clock)."""
     cfg, keep = _config(dimension, index_dir, shards_dir, device=device, rank=rank, world_size=world_size,
-                        placement=placement)
+                        placement=placement, now_secs=now_secs)
     h = C.c_void_p()
     _native.check(lib().vi_indexer_load(C.byref(cfg), C.byref(h)), prefix="Failed to load index: ")
     return VectorIndex(h, dimension, keep)

@@ -47,6 +47,11 @@ class BuildStats(C.Structure):
                 ("ms_index", f32)]
 
 
+class AddStats(C.Structure):
+    _fields_ = [("n", u64), ("lists_touched", u64), ("shards_rewritten", u64), ("bytes_written", u64), ("ms_total", f32),
+                ("ms_assign", f32), ("ms_files", f32), ("ms_index", f32), ("ms_kernel", f32), ("kernel_bytes", u64)]
+
+
 FETCH_ROWS_FN = C.CFUNCTYPE(C.c_int, vp, C.POINTER(u64), u64, vp)
 
 
@@ -84,11 +89,13 @@ SIGNATURES = {
     "vi_rng_free": (None, [vp]),
     "vi_shard_save_to": (C.c_int, [C.c_char_p, u64, u32, u32, vp, vp, vp, vp, vp, vp, vp]),
     "vi_shard_get_centroid_vectors_from": (C.c_int, [C.c_char_p, u64, vp, u64, C.POINTER(u32), vp, vp, vp, vp]),
+    "vi_shard_append_to": (C.c_int, [C.c_char_p, u64, u64, vp, vp, vp, vp, vp]),
     "vi_config_init": (None, [C.POINTER(Config), u32]),
     "vi_indexer_new": (C.c_int, [C.POINTER(Config), C.POINTER(vp)]),
     "vi_indexer_load": (C.c_int, [C.POINTER(Config), C.POINTER(vp)]),
     "vi_indexer_build_from_records": (C.c_int, [vp, vp, vp, vp, vp, u64]),
     "vi_indexer_build_from_vector_file": (C.c_int, [vp, C.c_char_p]),
+    "vi_indexer_add_records": (C.c_int, [vp, vp, vp, vp, u64]),
     "vi_indexer_search": (C.c_int, [vp, vp, u64, u32, u64, u64, vp, vp, vp, vp, C.POINTER(u64)]),
     "vi_indexer_search_device": (C.c_int, [vp, vp, u64, u64, u64, vp, vp, vp]),
     "vi_indexer_probe_device": (C.c_int, [vp, vp, u64, u64, vp, vp, C.POINTER(u64)]),
@@ -120,6 +127,7 @@ SIGNATURES = {
     "vi_indexer_last_stats": (C.c_int, [vp, C.POINTER(SearchStats)]),
     "vi_indexer_enable_timing": (None, [vp, C.c_int]),
     "vi_indexer_last_build_stats": (C.c_int, [vp, C.POINTER(BuildStats)]),
+    "vi_indexer_last_add_stats": (C.c_int, [vp, C.POINTER(AddStats)]),
 }
 
 _lib = None

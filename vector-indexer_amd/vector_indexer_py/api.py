@@ -7,6 +7,7 @@
     VectorIndexer.new(cfg) / .load(cfg) / .build_from_records / .build_from_vector_file /
     .search(req) / .search_request(query) / .config()                             api.rs:101-237
     .range_search(query, radius2, ...)                                            extension: everything within a radius
+    .add_records(records)                                                         extension: append to a built index
     SearchRequest.with_timestamp_range / .with_allowed_ids / .with_excluded_ids   extension: filtered search
 
 Errors are ViError (a RuntimeError) whose .kind is the io::ErrorKind name the reference returns.
@@ -200,6 +201,24 @@ class VectorIndexer:
         ts = np.array([r.timestamp or 0 for r in records], dtype=np.uint64)  # unwrap_or(0), api.rs:138
         _native.check(lib().vi_indexer_build_from_records(self._h, _native.ptr(ext), _native.ptr(vals), _native.ptr(ts),
                                                           _native.ptr(dims), n))
+        return self
+
+    def add_records(self, records: List[VectorRecord]) -> "VectorIndexer":
+        """extension: append records to the built or loaded index, each to the list of its nearest centroid (files and
+        resident index; nothing is retrained).  An empty list changes nothing."""
+        n = len(records)
+        dim = self._cfg.dimension
+        for i, r in enumerate(records):
+            if len(r.values) != dim:  # (the message of build_from_records, api.rs:122-133)
+                raise ViError(_native.VI_ERR_INVALID_INPUT,
+                              f"vector dimension mismatch at index {i}: expected {dim}, got {len(r.values)}")
+        if n == 0:
+            return self
+        vals = np.ascontiguousarray([r.values for r in records], dtype=np.float32).reshape(n, dim)
+        ext = np.array([r.external_id for r in records], dtype=np.uint64)
+        ts = np.array([r.timestamp or 0 for r in records], dtype=np.uint64)
+        self._drop_filters()  # (cached filters describe the index this call replaces)
+        _native.check(lib().vi_indexer_add_records(self._h, _native.ptr(ext), _native.ptr(vals), _native.ptr(ts), n))
         return self
 
     def build_from_vector_file(self, path) -> "VectorIndexer":

@@ -118,7 +118,8 @@ def synthetic_dataset(n: int, d: int, nq: int, k: int, seed: int = 42) -> Tuple[
 
 # ---- the adapter + eval loop --------------------------------------------------------------------------------------
 class FaissStyleAdapter:
-    """the Faiss-looking face of an index: .d, .nprobe (settable), .search(xq, k) -> (D, I), .range_search(x, thresh)
+    """the Faiss-looking face of an index: .d, .nprobe (settable), .search(xq, k) -> (D, I), .range_search(x, thresh),
+    .add(x), .add_with_ids(x, ids)
     (vector_indexer_adapter.py:75-140; the reference hops through an asyncio thread, the search here is synchronous)"""
 
     def __init__(self, vector_index, k: int = 100):
@@ -159,6 +160,14 @@ class FaissStyleAdapter:
         if flt is None:
             return self._idx.range_search_sync(np.ascontiguousarray(x, dtype=np.float32), float(thresh), self._nprobe)
         return self._idx.range_search_sync(np.ascontiguousarray(x, dtype=np.float32), float(thresh), self._nprobe, filter=flt)
+
+    def add(self, x: np.ndarray):
+        """Faiss's Index.add: the rows of x join the index with ids ntotal, ntotal + 1, ..."""
+        self._idx.add(np.ascontiguousarray(x, dtype=np.float32))
+
+    def add_with_ids(self, x: np.ndarray, ids):
+        """Faiss's Index.add_with_ids"""
+        self._idx.add(np.ascontiguousarray(x, dtype=np.float32), ext_ids=ids)
 
     def __repr__(self):
         return f"FaissStyleAdapter(d={self.d}, nprobe={self.nprobe})"
