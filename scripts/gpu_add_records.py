@@ -78,7 +78,11 @@ for s in sizes:
     entry = {"add": {f: spread([a[f] for a in adds]) for f in ("ms_total", "ms_assign", "ms_files", "ms_index", "ms_kernel")},
              "lists_touched": adds[0]["lists_touched"], "shards_rewritten": adds[0]["shards_rewritten"],
              "bytes_written": adds[0]["bytes_written"], "kernel_bytes": adds[0]["kernel_bytes"],
-             "load_of_the_base_ms": spread(loads)}
+             "load_of_the_base_ms": spread(loads),
+             # every run's own figures (what a comparison of two commits takes its medians and maxima from)
+             "runs": {"load_ms": [round(v, 3) for v in loads], "add_ms_index": [round(a["ms_index"], 3) for a in adds],
+                      "add_ms_kernel": [round(a["ms_kernel"], 4) for a in adds],
+                      "rebuild_ms_index": [round(b["ms_index"], 3) for b in rebuilds]}}
     kms = statistics.median(a["ms_kernel"] for a in adds)
     entry["kernel_TBps"] = round(adds[0]["kernel_bytes"] / (kms * 1e-3) / 1e12, 3) if kms > 0 else None
     entry["kernel_share_of_copy_bandwidth"] = round(entry["kernel_TBps"] / COPY_TBPS, 3) if kms > 0 else None

@@ -14,6 +14,7 @@
 
 #include "device_index.hpp"
 #include "kmeans.hpp"
+#include "list_layout.hpp"
 #include "rng.hpp"
 #include "shards.hpp"
 #include "slot_filter.hpp"
@@ -235,9 +236,11 @@ static vi_status add_records(Indexer *ix, const uint64_t *ext_ids, const float *
   VI_HIP(hipMemcpy(h_len.data(), old.list_len.p, nlists * 4, hipMemcpyDeviceToHost));
   if (seg.size() != nlists + 1 || seg[nlists] != n) return fail(VI_ERR_OTHER, "add: a record was assigned to no list");
   {  // the slot limit of the new layout, before anything is written
-    uint64_t blocks = 0;
-    for (uint64_t l = 0; l < nlists; ++l) blocks += ((uint64_t)h_len[l] + (seg[l + 1] - seg[l]) + 63) / 64;
-    if (blocks >= 0xFFFFFFFFull / 64) return fail(VI_ERR_INVALID_INPUT, "index too large for 32-bit slot ids");
+    std::vector<uint64_t> full_len(nlists);
+    for (uint64_t l = 0; l < nlists; ++l) full_len[l] = (uint64_t)h_len[l] + (seg[l + 1] - seg[l]);
+    ListLayout lay;
+    if (plan_list_layout(full_len.data(), nlists, 1, 0, &lay) != LayoutError::none)
+      return fail(VI_ERR_INVALID_INPUT, "index too large for 32-bit slot ids");
   }
   const double t1 = now_ms();
   as.ms_assign = (float)(t1 - t0);

@@ -166,12 +166,46 @@ struct DeviceIndex {
   ~DeviceIndex();
 };
 
+// ---- the four routes to a resident index ----
+// Each lays its lists out by list_layout.hpp, reserves and uploads through alloc_list_storage, builds (or copies) the
+// coarse table and ends with prepare_rank_images (search_internal.hpp, device_index.hip); what differs is where the list
+// blocks come from:
+//   device_index_load        (device_index.hip)  records of the shard files, in stripes or by shard placement: a load, and
+//                                                the build of a rank of a multi-GPU run (api.cpp: attach_device)
+//   device_index_from_rows   (device_index.hip)  rows of a device matrix, grouped on the host: the two-level hierarchy of
+//                                                the k-means assignment (kmeans.hip)
+//   device_index_from_order  (list_build.hip)    rows of a device matrix, grouped on the device: a single-GPU build (api.cpp)
+//   device_index_append      (list_append.hip)   the blocks of an older index and new rows: vi_indexer_add_records (api.cpp)
+//
 // Upload: centroid table + this rank's part of the lists, repacked on the GPU.  placement 0: a stripe of every list
 // (block b on rank b % world); 1: the whole lists of the shard files dealt to this rank (greedy by bytes).
 vi_status device_index_load(const IndexMeta &meta, const std::string &shards_dir, int device, int rank,
                             int world, int placement, DeviceIndex *out);
 // owner rank of every shard under placement 1: shards by descending bytes, each to the least loaded rank so far
 std::vector<uint32_t> shard_owners(const std::vector<uint64_t> &shard_bytes, uint32_t world);
+// Build a device index from device-resident arrays (the k-means path, where the "index" is the two-level centroid
+// hierarchy of assign_points_hierarchical, kmeans.rs:474-581).  table: ntable x dim row-major (device) = coarse table;
+// rows: row-major device matrix the lists draw from; list_off[nlists+1] (host) delimits
+// member_rows (host, row index per list member, list order = scan order); ids (device,
+// optional) = external id per row (null => row index); list_shard (host, optional).  No timestamps are kept.
+vi_status device_index_from_rows(int device, int order, uint32_t dim, const float *table_dev, uint64_t ntable,
+                                 const float *rows_dev, const std::vector<uint64_t> &list_off,
+                                 const std::vector<uint32_t> &member_rows, const uint64_t *ids_dev,
+                                 const std::vector<uint32_t> *list_shard, DeviceIndex *out);
+// resident index straight from device data: list l = rows order[src_off[l] .. + len[l]) of X_dev; ts_dev (optional) =
+// timestamp per row, 0 or no array => now (what shard_export_device writes)
+vi_status device_index_from_order(int device, uint32_t dim, const float *table_host, uint64_t nlists, const float *X_dev,
+                                  const uint32_t *order_dev, const std::vector<uint64_t> &src_off,
+                                  const std::vector<uint32_t> &len, const std::vector<uint32_t> &list_shard,
+                                  const uint64_t *ids_dev, const uint64_t *ts_dev, uint64_t now, DeviceIndex *out);
+// `out` = a fresh index holding the lists of `old` (unpartitioned; only read) with list l followed by rows
+// order_dev[seg[l] .. seg[l + 1]) of rows_dev (seg on the device and the host: group_ids_by_label_device); row_ext_dev /
+// row_ts_dev: external id and stored timestamp of every row.  Old blocks are copied device to device, nothing comes from
+// the shard files; old and new index coexist until the caller drops the old one.  ms_kernel / kernel_bytes (optional):
+// HIP-event time of append_blocks_kernel and the bytes it moves.
+vi_status device_index_append(const DeviceIndex &old, const float *rows_dev, uint64_t n, const uint32_t *order_dev,
+                              const uint32_t *seg_dev, const std::vector<uint64_t> &seg_host, const uint64_t *row_ext_dev,
+                              const uint64_t *row_ts_dev, DeviceIndex *out, float *ms_kernel, uint64_t *kernel_bytes);
 
 struct SearchIO {
   const float *queries = nullptr;  // host or device (queries_on_device)
@@ -248,30 +282,13 @@ struct EngineKnobs {
 };
 EngineKnobs read_engine_knobs();
 
-// Build a device index from device-resident arrays (used by the k-means path, where the
-// "index" is the two-level centroid hierarchy of assign_points_hierarchical, kmeans.rs:474-581,
-// and by the GPU list build).  table: ntable x dim row-major (device) = coarse table;
-// rows: row-major device matrix the lists draw from; list_off[nlists+1] (host) delimits
-// member_rows (host, row index per list member, list order = scan order); ids (device,
-// optional) = external id per row (null => row index); list_shard (host, optional).
-vi_status device_index_from_rows(int device, int order, uint32_t dim, const float *table_dev, uint64_t ntable,
-                                 const float *rows_dev, const std::vector<uint64_t> &list_off,
-                                 const std::vector<uint32_t> &member_rows, const uint64_t *ids_dev,
-                                 const std::vector<uint32_t> *list_shard, DeviceIndex *out);
-
-// ---- GPU list build (list_build.hip) ----
+// ---- GPU list build (list_build.hip; device_index_from_order is declared with the routes above) ----
 // ids 0..n-1 grouped by label, ascending id inside a label (stable radix sort): order (device, n u32), seg (device,
 // k+1 u32 offsets into order) and the offsets on the host if off_host is given.  Complete on return.  scratch_keep
 // (optional): the sort's scratch (3 n + 256 n / 4096 words) in a buffer of the caller's, kept from call to call.
 vi_status group_ids_by_label_device(const uint32_t *labels_dev, uint64_t n, uint64_t k, DevBuf<uint32_t> &order,
                                     DevBuf<uint32_t> &seg, std::vector<uint64_t> *off_host, hipStream_t st,
                                     DevBuf<uint32_t> *scratch_keep = nullptr);
-// resident index straight from device data: list l = rows order[src_off[l] .. + len[l]) of X_dev; ts_dev (optional) =
-// timestamp per row, 0 or no array => now (what shard_export_device writes)
-vi_status device_index_from_order(int device, uint32_t dim, const float *table_host, uint64_t nlists, const float *X_dev,
-                                  const uint32_t *order_dev, const std::vector<uint64_t> &src_off,
-                                  const std::vector<uint32_t> &len, const std::vector<uint32_t> &list_shard,
-                                  const uint64_t *ids_dev, const uint64_t *ts_dev, uint64_t now, DeviceIndex *out);
 struct ShardExportWs {  // staging of shard_export_device, reused from shard to shard
   DevBuf<uint8_t> image;
   DevBuf<uint64_t> d_src, d_dst;
@@ -286,18 +303,10 @@ vi_status shard_export_device(const std::string &shards_dir, uint64_t shard_id, 
                               const float *X_dev, const uint32_t *order_dev, const uint64_t *ext_dev, const uint64_t *ts_dev,
                               uint64_t now, ShardExportWs &ws, hipStream_t st);
 
-// ---- appending records to a resident index (list_append.hip) ----
+// ---- appending records to a resident index (list_append.hip; device_index_append is declared with the routes above) ----
 // labels_dev[i] (device, n u32) = the list the reference's coarse step probes first for row i of rows_dev (device, n x dim):
 // the index's own coarse step with n_probe = 1, in chunks
 vi_status device_index_label_rows(const DeviceIndex &ix, const float *rows_dev, uint64_t n, uint32_t *labels_dev);
-// `out` = a fresh index holding the lists of `old` (unpartitioned; only read) with list l followed by rows
-// order_dev[seg[l] .. seg[l + 1]) of rows_dev (seg on the device and the host: group_ids_by_label_device); row_ext_dev /
-// row_ts_dev: external id and stored timestamp of every row.  Old blocks are copied device to device, nothing comes from
-// the shard files; old and new index coexist until the caller drops the old one.  ms_kernel / kernel_bytes (optional):
-// HIP-event time of append_blocks_kernel and the bytes it moves.
-vi_status device_index_append(const DeviceIndex &old, const float *rows_dev, uint64_t n, const uint32_t *order_dev,
-                              const uint32_t *seg_dev, const std::vector<uint64_t> &seg_host, const uint64_t *row_ext_dev,
-                              const uint64_t *row_ts_dev, DeviceIndex *out, float *ms_kernel, uint64_t *kernel_bytes);
 
 vi_status merge_partials_packed_device(int device, uint64_t nq, uint64_t k, uint32_t parts, const void *packed,
                                        float *D_out, int64_t *I_out);

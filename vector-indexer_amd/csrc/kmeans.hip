@@ -32,6 +32,7 @@
 #include "kmeans.hpp"
 #include "rng.hpp"
 #include "scan.hpp"
+#include "search_internal.hpp"
 
 namespace vi {
 namespace {
@@ -514,13 +515,7 @@ vi_status assign_brute_device(Ctx &cx, const float *Xq, uint64_t n, const float 
   const uint32_t dq = layout_dq(d);
   const uint64_t nb = (k + 63) / 64;
   VI_TRY(ws.cblocks.reserve(std::max<uint64_t>(1, nb) * dq * 64 * 4));
-  {
-    std::vector<uint32_t> ros(nb * 64, kNoPos);
-    for (uint64_t i = 0; i < k; ++i) ros[i] = (uint32_t)i;
-    VI_TRY(to_device(ws.ros, ros.data(), ros.size(), cx.st));
-    VI_TRY(launch_repack_rows(Cd, d, dq, ws.ros.p, ros.size(), nullptr, ws.cblocks.p, nullptr, cx.st));
-    VI_HIP(hipStreamSynchronize(cx.st));  // ros (host vector) must outlive the copy
-  }
+  VI_TRY(repack_table(Cd, k, d, dq, ws.cblocks.p, cx.st, &ws.ros));
   for (uint64_t q0 = 0; q0 < n; q0 += kAssignChunk) {
     const uint64_t nq = std::min<uint64_t>(kAssignChunk, n - q0);
     const int qg = pick_qg(dq, (double)nq, VI_ORDER_LANES);

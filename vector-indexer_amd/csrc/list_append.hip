@@ -92,13 +92,6 @@ __global__ void __launch_bounds__(kAppendWaves * kWave) append_blocks_kernel(App
   a.ts[slot] = is_old ? a.old_ts[old_slot] : is_new ? a.row_ts[row] : 0ull;
 }
 
-template <typename T>
-vi_status upload(DevBuf<T> &buf, const T *host, size_t n, hipStream_t st) {
-  VI_TRY(buf.reserve(std::max<size_t>(n, 1)));
-  if (n) VI_HIP(hipMemcpyAsync(buf.p, host, n * sizeof(T), hipMemcpyHostToDevice, st));
-  return VI_OK;
-}
-
 struct EventPair {
   hipEvent_t a = nullptr, b = nullptr;
   ~EventPair() {
@@ -143,27 +136,25 @@ vi_status device_index_append(const DeviceIndex &old, const float *rows_dev, uin
   ix->timing = old.timing;
   const uint32_t dq = ix->dq;
   hipStream_t st = ix->stream;
-  // the old layout, and the new one: lists back to back in list order, each padded to whole blocks (as a load lays them)
-  std::vector<uint32_t> o_first(nlists), o_len(nlists), n_first(nlists), n_len(nlists);
+  // the new layout from the old lengths: lists back to back in list order, each padded to whole blocks (as a load lays them)
+  std::vector<uint32_t> o_len(nlists);
   if (nlists) {
-    VI_HIP(hipMemcpyAsync(o_first.data(), old.list_first_block.p, nlists * 4, hipMemcpyDeviceToHost, st));
     VI_HIP(hipMemcpyAsync(o_len.data(), old.list_len.p, nlists * 4, hipMemcpyDeviceToHost, st));
     VI_HIP(hipStreamSynchronize(st));
   }
-  uint64_t total_blocks = 0, total_vec = 0;
-  for (uint64_t l = 0; l < nlists; ++l) {
-    const uint64_t len = (uint64_t)o_len[l] + (seg_host[l + 1] - seg_host[l]);
-    if (len > 0xFFFFFFFFull - kWave) return fail(VI_ERR_INVALID_INPUT, "a list would pass the 32-bit position limit");
-    n_first[l] = (uint32_t)total_blocks;
-    n_len[l] = (uint32_t)len;
-    total_blocks += (len + kWave - 1) / kWave;
-    total_vec += len;
-    if (total_blocks >= 0xFFFFFFFFull / kWave) return fail(VI_ERR_INVALID_INPUT, "index too large for 32-bit slot ids");
+  std::vector<uint64_t> full_len(nlists);
+  for (uint64_t l = 0; l < nlists; ++l) full_len[l] = (uint64_t)o_len[l] + (seg_host[l + 1] - seg_host[l]);
+  ListLayout lay;
+  switch (plan_list_layout(full_len.data(), nlists, 1, 0, &lay)) {
+    case LayoutError::list_too_long: return fail(VI_ERR_INVALID_INPUT, "a list would pass the 32-bit position limit");
+    case LayoutError::too_many_slots: return fail(VI_ERR_INVALID_INPUT, "index too large for 32-bit slot ids");
+    case LayoutError::none: break;
   }
+  const uint64_t total_blocks = lay.total_blocks;
   std::vector<uint32_t> block_list(total_blocks);
   for (uint64_t l = 0; l < nlists; ++l) {
-    const uint64_t nb = ((uint64_t)n_len[l] + kWave - 1) / kWave;
-    std::fill(block_list.begin() + n_first[l], block_list.begin() + n_first[l] + nb, (uint32_t)l);
+    const uint64_t nb = ((uint64_t)lay.len[l] + kWave - 1) / kWave;
+    std::fill(block_list.begin() + lay.first[l], block_list.begin() + lay.first[l] + nb, (uint32_t)l);
   }
   // coarse table and shard of every list: unchanged
   ix->centroids.dq = dq;
@@ -173,21 +164,7 @@ vi_status device_index_append(const DeviceIndex &old, const float *rows_dev, uin
   if (old.centroids.nblocks)
     VI_HIP(hipMemcpyAsync(ix->centroids.blocks.p, old.centroids.blocks.p, old.centroids.nblocks * dq * kWave * 4 * sizeof(float),
                           hipMemcpyDeviceToDevice, st));
-  VI_TRY(ix->list_first_block.reserve(std::max<uint64_t>(1, nlists)));
-  VI_TRY(ix->list_len.reserve(std::max<uint64_t>(1, nlists)));
-  VI_TRY(ix->list_shard.reserve(std::max<uint64_t>(1, nlists)));
-  if (nlists) {
-    VI_HIP(hipMemcpyAsync(ix->list_first_block.p, n_first.data(), nlists * 4, hipMemcpyHostToDevice, st));
-    VI_HIP(hipMemcpyAsync(ix->list_len.p, n_len.data(), nlists * 4, hipMemcpyHostToDevice, st));
-    VI_HIP(hipMemcpyAsync(ix->list_shard.p, old.list_shard.p, nlists * 4, hipMemcpyDeviceToDevice, st));
-  }
-  ix->nshards = old.nshards;
-  ix->nvec_resident = total_vec;
-  ix->lists.dq = dq;
-  ix->lists.nblocks = total_blocks;
-  VI_TRY(ix->lists.blocks.reserve(std::max<uint64_t>(1, total_blocks) * dq * kWave * 4));
-  VI_TRY(ix->ext_ids.reserve(std::max<uint64_t>(1, total_blocks) * kWave));
-  VI_TRY(ix->timestamps.reserve(std::max<uint64_t>(1, total_blocks) * kWave));
+  VI_TRY(alloc_list_storage(ix, lay, nullptr, &old, true));  // (queues the new first / len ahead of the kernel below)
   if (ms_kernel) *ms_kernel = 0.0f;
   if (kernel_bytes) *kernel_bytes = 0;
   if (total_blocks) {

@@ -9,7 +9,9 @@
 //        to 65 536 lists) — no atomics decide a position, so the order is the reference's, run after run
 //     -> list offsets by binary search of the sorted labels
 //     -> the lane-interleaved blocks + bf16 images of the resident index straight from X (device_index_from_order):
-//        nothing is re-read from the shard files the build has just written
+//        nothing is re-read from the shard files the build has just written.  Layout, storage and coarse table are the
+//        steps every index route shares (list_layout.hpp, device_index.hip); slot_rows_kernel and
+//        slot_timestamps_kernel are this route's own
 //     -> shard files: one kernel per shard lays the records (24 B meta + D f32 + pad) out in file order in a staging
 //        image, one copy to pinned host memory, one write(2).
 #include <hip/hip_runtime.h>
@@ -221,13 +223,6 @@ __global__ void __launch_bounds__(256) export_records_kernel(ExportArgs a) {
   }
 }
 
-template <typename T>
-vi_status upload(DevBuf<T> &buf, const T *host, size_t n, hipStream_t st) {
-  VI_TRY(buf.reserve(std::max<size_t>(n, 1)));
-  if (n) VI_HIP(hipMemcpyAsync(buf.p, host, n * sizeof(T), hipMemcpyHostToDevice, st));
-  return VI_OK;
-}
-
 }  // namespace
 
 // ids 0..n-1 grouped by label (ascending id inside a label): order (device, n u32), seg (device, k+1 u32: list c is
@@ -292,42 +287,17 @@ vi_status device_index_from_order(int device, uint32_t dim, const float *table_h
   const uint32_t dq = ix->dq;
   hipStream_t st = ix->stream;
   {  // coarse table
-    const uint64_t nb = (nlists + kWave - 1) / kWave;
-    ix->centroids.dq = dq;
-    ix->centroids.nblocks = nb;
-    VI_TRY(ix->centroids.blocks.reserve(std::max<uint64_t>(1, nb) * dq * kWave * 4));
-    std::vector<uint32_t> ros(nb * kWave, kNoPos);
-    for (uint64_t i = 0; i < nlists; ++i) ros[i] = (uint32_t)i;
-    DevBuf<uint32_t> dros;
     DevBuf<float> dtab;
-    VI_TRY(upload(dros, ros.data(), ros.size(), st));
     VI_TRY(upload(dtab, table_host, nlists * dim, st));
-    VI_TRY(launch_repack_rows(dtab.p, dim, dq, dros.p, ros.size(), nullptr, ix->centroids.blocks.p, nullptr, st));
-    VI_HIP(hipStreamSynchronize(st));
+    VI_TRY(coarse_table_from_rows(ix, dtab.p));
   }
-  std::vector<uint32_t> h_first(nlists, 0);
-  uint64_t total_blocks = 0, total_vec = 0, nshards = 0;
-  for (uint64_t l = 0; l < nlists; ++l) {
-    h_first[l] = (uint32_t)total_blocks;
-    total_blocks += (len[l] + kWave - 1) / kWave;
-    total_vec += len[l];
-    nshards = std::max<uint64_t>(nshards, (uint64_t)list_shard[l] + 1);
-  }
-  if (total_blocks >= 0xFFFFFFFFull / kWave) return fail(VI_ERR_OTHER, "index too large for 32-bit slot ids");
-  ix->nvec_resident = total_vec;
-  ix->nshards = nshards;
-  ix->lists.dq = dq;
-  ix->lists.nblocks = total_blocks;
-  VI_TRY(ix->lists.blocks.reserve(std::max<uint64_t>(1, total_blocks) * dq * kWave * 4));
-  VI_TRY(ix->ext_ids.reserve(std::max<uint64_t>(1, total_blocks) * kWave));
-  VI_TRY(ix->timestamps.reserve(std::max<uint64_t>(1, total_blocks) * kWave));
-  VI_TRY(ix->list_first_block.reserve(std::max<uint64_t>(1, nlists)));
-  VI_TRY(ix->list_len.reserve(std::max<uint64_t>(1, nlists)));
-  VI_TRY(ix->list_shard.reserve(std::max<uint64_t>(1, nlists)));
+  const std::vector<uint64_t> full_len(len.begin(), len.end());
+  ListLayout lay;
+  if (plan_list_layout(full_len.data(), nlists, 1, 0, &lay) != LayoutError::none)
+    return fail(VI_ERR_OTHER, "index too large for 32-bit slot ids");
+  VI_TRY(alloc_list_storage(ix, lay, list_shard.data(), nullptr, true));
+  const uint64_t total_blocks = lay.total_blocks;
   if (nlists) {
-    VI_HIP(hipMemcpyAsync(ix->list_first_block.p, h_first.data(), nlists * 4, hipMemcpyHostToDevice, st));
-    VI_HIP(hipMemcpyAsync(ix->list_len.p, len.data(), nlists * 4, hipMemcpyHostToDevice, st));
-    VI_HIP(hipMemcpyAsync(ix->list_shard.p, list_shard.data(), nlists * 4, hipMemcpyHostToDevice, st));
     DevBuf<uint64_t> dsrc;
     DevBuf<uint32_t> dros;
     VI_TRY(upload(dsrc, src_off.data(), nlists, st));

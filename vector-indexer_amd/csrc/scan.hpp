@@ -1,5 +1,6 @@
-// scan.hpp — launchers of the exact-order scan / select / repack kernels shared by the
-// search path (search_kernels.hip) and the k-means path (kmeans.hip).
+// scan.hpp — launchers of the exact-order scan / select kernels (search_kernels.hip) and the row repack kernel
+// (device_index.hip) shared by the search path, the index builders (device_index.hip, list_build.hip) and the
+// k-means path (kmeans.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -1,12 +1,14 @@
-// search_internal.hpp — what the search engines' translation units (search_kernels.hip, generic_search.hip,
-// filter_search.hip, grouping.hip, select.hip, range_select.hip, rank_images.hip, list_build.hip) call in each other and share:
-// declared once, here.  (The probe grouping is called through a header of its own, grouping.hpp; filter_search.hip launches
+// search_internal.hpp — what the search engines' and the index builders' translation units (search_kernels.hip,
+// generic_search.hip, filter_search.hip, grouping.hip, select.hip, range_select.hip, rank_images.hip, device_index.hip,
+// list_build.hip, list_append.hip, kmeans.hip) call in each other and share: declared once, here.  (The probe grouping is called through a header of its own, grouping.hpp; filter_search.hip launches
 // its rank and select phases through rank_stream.hpp and select.hpp.)
 #pragma once
+#include <algorithm>
 #include <array>
 #include <cstdint>
 
 #include "device_index.hpp"
+#include "list_layout.hpp"
 
 namespace vi {
 
@@ -49,8 +51,30 @@ static_assert(kStatRankWork + kStatRankWorkStride * kStatRankWorkCount <= kStatC
               "the ranges of the counter block do not overlap");
 using GroupingCounts = std::array<uint64_t, kStatGroupingWords>;  // host copy of words [0, kStatGroupingWords)
 
-// ---- search_kernels.hip ----
+// ---- device_index.hip: the steps every route that builds a DeviceIndex takes ----
 vi_status init_device_index(DeviceIndex *ix, int device, uint32_t dim, uint64_t nlists);
+// Everything of an initialised index that follows from the layout of its lists, on ix->stream: lists.dq / nblocks,
+// nvec_resident, the blocks and ext_ids (and timestamps, if asked for) reserved, list_first_block and list_len uploaded,
+// list_shard and nshards from a host array (nshards = max + 1) or, if shard_from is given, from that index.  The copies
+// are queued: `lay` and shard_host stay alive until the caller has synchronised ix->stream.
+vi_status alloc_list_storage(DeviceIndex *ix, const ListLayout &lay, const uint32_t *shard_host, const DeviceIndex *shard_from,
+                             bool with_timestamps);
+// rows 0..n-1 of a row-major device matrix -> ceil(n / 64) lane-interleaved blocks, pad lanes zero; complete on return.
+// ros_keep (optional): the row-of-slot scratch in a buffer of the caller's, kept from call to call.
+vi_status repack_table(const float *rows_dev, uint64_t n, uint32_t dim, uint32_t dq, float *blocks, hipStream_t st,
+                       DevBuf<uint32_t> *ros_keep = nullptr);
+// the coarse table of an initialised index (centroids.dq / nblocks / blocks) from its nlists x dim rows on the device
+vi_status coarse_table_from_rows(DeviceIndex *ix, const float *rows_dev);
+
+// host array -> device buffer (grown to hold it), queued on st: `host` stays alive until st is synchronised
+template <typename T>
+vi_status upload(DevBuf<T> &buf, const T *host, size_t n, hipStream_t st) {
+  VI_TRY(buf.reserve(std::max<size_t>(n, 1)));
+  if (n) VI_HIP(hipMemcpyAsync(buf.p, host, n * sizeof(T), hipMemcpyHostToDevice, st));
+  return VI_OK;
+}
+
+// ---- search_kernels.hip ----
 vi_status stage_coarse(const DeviceIndex &ix, const float *Qd, uint64_t nq, uint32_t P, hipStream_t st);
 vi_status adopt_probes(const DeviceIndex &ix, uint64_t nq, uint32_t P, const uint32_t *probes_in, const uint32_t *order_in,
                        bool histogram, hipStream_t st);

@@ -13,7 +13,7 @@ import numpy as np
 
 
 def block_owner(block: int, world: int) -> int:
-    """placement rule shared by vi_indexer_load (csrc/search_kernels.hip) and the oracle's protocol checker: block b
+    """placement rule shared by vi_indexer_load (csrc/device_index.hip, csrc/list_layout.hpp) and the oracle's protocol checker: block b
     (vectors 64b .. 64b+63) of EVERY list lives on rank b % world.  Stripes, not whole lists or shard files: the scan
     work is concentrated in a few huge lists (two lists carry half of it on the bench index), which no placement of
     whole lists can balance."""
