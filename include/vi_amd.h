@@ -362,7 +362,7 @@ vi_status vi_indexer_search_probed_filtered_device(const vi_indexer *ix, const v
  * IDSelectorBatch / IDSelectorNot) ----
  * The filtered result of a query is the reference's candidate sequence with some candidates deleted before the stable
  * sort: VI_IDS_ALLOW deletes the candidates whose external id is NOT in the set, VI_IDS_DENY those whose external id IS
- * in it (a deny set is how records are "deleted" from an immutable index).  The coarse step, distances, tie keys,
+ * in it (a deny set hides records for one search; vi_indexer_remove_ids removes them).  The coarse step, distances, tie keys,
  * padding and counts are exactly as for the timestamp filter above, so per-rank partial results merge exactly when every
  * rank filters by the same set.
  *   - the set needs no order; duplicates are allowed; ids that no resident vector carries are ignored
@@ -382,6 +382,48 @@ vi_status vi_indexer_filter_ids(const vi_indexer *ix, const uint64_t *ids, uint6
 vi_status vi_indexer_filter_ids_device(const vi_indexer *ix, const uint64_t *ids_dev, uint64_t n, vi_id_mode mode,
                                        vi_filter **out);
 vi_status vi_filter_intersect(const vi_indexer *ix, const vi_filter *a, const vi_filter *b, vi_filter **out);
+
+/* ---- extension (the reference has no remove, api.rs:101-237): remove records from a built or loaded index ----
+ * Afterwards the index is the one the reference would search if the removed records had been deleted from their inverted
+ * lists: the remaining records of each list close up in their old order.  The coarse table, index.bin, centroids_to_shard
+ * and the centroid vectors in the shard files do not change and nothing is retrained.  A list that loses every record
+ * stays in its shard file as an entry with num_vectors == 0, stays in the coarse table and is still probed (it yields no
+ * candidate).  Every search afterwards returns, in ids and distance bits, what the same search returned before through a
+ * filter admitting exactly the kept records; tie keys differ, because positions move.
+ *   vi_indexer_retain      keeps exactly the resident records `keep` admits (any vi_filter of this handle's index: a
+ *                          timestamp window, an id set, an intersection)
+ *   vi_indexer_remove_ids  Faiss's remove_ids: removes every record whose external id is in the set, by the rules of a
+ *                          VI_IDS_DENY set (any order, duplicates allowed, unknown ids ignored, any u64 is an id); it is
+ *                          vi_indexer_retain of that deny filter
+ *   *removed_out (optional): records removed (0 on an error)
+ *   - files: only shard files that hold a removed record are rewritten, WHOLE, byte-identical to vi_shard_save_to of the
+ *     remaining lists (lists in file order, centroid vectors and kept records copied verbatim, VectorMeta.id unchanged).
+ *     All new files are written beside the old ones as shard_<id>.bin.tmp, then renamed, and only then is the resident
+ *     index swapped; a failure before the renames removes the temporaries and leaves files and handle unchanged.  A later
+ *     vi_indexer_load of the directories gives the same index.
+ *   - resident index: rebuilt ON THE GPU from the old resident blocks, not re-read from the files.  It is a replaced
+ *     index: every vi_filter made before the call is VI_ERR_INVALID_INPUT afterwards, `keep` included (free them), and
+ *     vi_range_results must be freed or copied before the call.  The call must not overlap searches on the handle; this
+ *     is not enforced.
+ *   - nothing to remove (`keep` admits everything, n == 0, no id matches): VI_OK, *removed_out = 0, no file is touched,
+ *     no index is replaced, old filters stay valid
+ *   - errors, all VI_ERR_INVALID_INPUT before any file or device change: a null ix, a null keep, ext_ids == NULL with
+ *     n > 0, a handle with no index, a filter of another handle or of a replaced index, a partitioned handle
+ *     (world_size > 1: ranks reload from the files an unpartitioned handle wrote), a removal that would leave the index
+ *     with no record at all (an index keeps at least one record; to drop an index, delete its directories).  A shard
+ *     file whose list no longer has its resident length: VI_ERR_INVALID_DATA.
+ *   - vi_indexer_add_records afterwards still numbers VectorMeta.id from vi_indexer_num_vectors, so after a remove a
+ *     later add can repeat an internal id that is still in the files.  Nothing in the search path reads VectorMeta.id:
+ *     results carry external ids.
+ * Device memory: the old and the new resident index coexist until the swap, beside one filter (vi_indexer_remove_ids
+ * makes its own).
+ * vi_shard_remove_from: the file half alone, no GPU: the same removal, by external id, from one shard file (written
+ * beside it under a temporary name, renamed when complete).  A file that cannot be read: the errors of
+ * vi_shard_get_centroid_vectors_from.  No record matches: the file is left as it is. */
+vi_status vi_indexer_retain(vi_indexer *ix, const vi_filter *keep, uint64_t *removed_out);
+vi_status vi_indexer_remove_ids(vi_indexer *ix, const uint64_t *ext_ids, uint64_t n, uint64_t *removed_out);
+vi_status vi_shard_remove_from(const char *shards_dir, uint64_t shard_id, const uint64_t *ext_ids, uint64_t n,
+                               uint64_t *removed_out);
 
 /* ---- extension: radius (range) search -----------------------------------------------------------------------------
  * Every candidate of the probed lists whose squared distance is at most radius2.  The result of a query is the
@@ -477,6 +519,22 @@ typedef struct vi_add_stats {
   uint64_t kernel_bytes;     /* ... and the bytes it read and wrote */
 } vi_add_stats;
 vi_status vi_indexer_last_add_stats(const vi_indexer *ix, vi_add_stats *out);
+/* the most recent vi_indexer_retain / vi_indexer_remove_ids on this handle that removed something (wall-clock ms unless
+ * said otherwise) */
+typedef struct vi_remove_stats {
+  uint64_t n_removed;        /* records removed */
+  uint64_t lists_touched;    /* lists that lost records ... */
+  uint64_t lists_emptied;    /* ... and of them, lists that lost their last */
+  uint64_t shards_rewritten; /* shard files rewritten */
+  uint64_t bytes_written;    /* bytes of those files */
+  float ms_total;
+  float ms_plan;             /* the allow words read back, the touched lists and shards found */
+  float ms_files;            /* new shard files written and renamed */
+  float ms_index;            /* new resident index: kept_count_kernel, compact_blocks_kernel + the ranking images */
+  float ms_kernel;           /* HIP-event time of compact_blocks_kernel alone (part of ms_index) ... */
+  uint64_t kernel_bytes;     /* ... and the bytes it read and wrote */
+} vi_remove_stats;
+vi_status vi_indexer_last_remove_stats(const vi_indexer *ix, vi_remove_stats *out);
 
 /* stats of the most recent search on this handle (timing collected only if enabled) */
 vi_status vi_indexer_last_stats(const vi_indexer *ix, vi_search_stats *out);

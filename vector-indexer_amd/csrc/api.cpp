@@ -34,6 +34,7 @@ struct Indexer {
   std::unique_ptr<DeviceIndex> dev;     // HBM-resident lists (null until load/build)
   vi_build_stats build_stats{};         // phases of the last build on this handle
   vi_add_stats add_stats{};             // ... and of the last vi_indexer_add_records that added something
+  vi_remove_stats remove_stats{};       // ... and of the last vi_indexer_retain / vi_indexer_remove_ids that removed something
 };
 
 // No C++ exception may unwind through the C ABI into a Rust / ctypes caller (std::vector growth, std::string, a
@@ -307,6 +308,94 @@ static vi_status add_records(Indexer *ix, const uint64_t *ext_ids, const float *
   as.ms_files = (float)((t2 - t1) + (t4 - t3));
   as.ms_total = (float)(t4 - t0);
   ix->add_stats = as;
+  return VI_OK;
+}
+
+// vi_indexer_retain / vi_indexer_remove_ids behind their argument checks, in the order of add_records: the plan from the
+// filter's allow words, the touched shard files written under temporary names, the new resident index gathered from the
+// old blocks, then the renames, then the swap.  Everything before the renames can fail without a trace.  `keep` is a
+// filter of ix->dev.
+static vi_status retain_records(Indexer *ix, const SlotFilter &keep, uint64_t *removed_out) {
+  const DeviceIndex &old = *ix->dev;
+  const uint32_t dim = ix->cfg.dimension;
+  const uint64_t nlists = old.nlists;
+  if (removed_out) *removed_out = 0;
+  if (keep.num_allowed > old.nvec_resident) return fail(VI_ERR_OTHER, "retain: the filter admits more records than the index holds");
+  const uint64_t n_removed = old.nvec_resident - keep.num_allowed;
+  if (n_removed == 0) return VI_OK;  // nothing changes: no file, no index, no filter
+  if (keep.num_allowed == 0)
+    return fail(VI_ERR_INVALID_INPUT, "the removal would leave the index without a record (an index keeps at least one; to drop it, delete its directories)");
+  vi_remove_stats rs{};
+  rs.n_removed = n_removed;
+  const double t0 = now_ms();
+  VI_HIP(hipSetDevice(old.device));
+  // ---- plan: which positions of which lists stay (position p of list l: bit p % 64 of word first[l] + p / 64) ----
+  std::vector<uint64_t> h_allow(old.lists.nblocks);
+  std::vector<uint32_t> h_first(nlists), h_len(nlists);
+  if (old.lists.nblocks) VI_HIP(hipMemcpy(h_allow.data(), keep.allow.p, old.lists.nblocks * 8, hipMemcpyDeviceToHost));
+  VI_HIP(hipMemcpy(h_first.data(), old.list_first_block.p, nlists * 4, hipMemcpyDeviceToHost));
+  VI_HIP(hipMemcpy(h_len.data(), old.list_len.p, nlists * 4, hipMemcpyDeviceToHost));
+  std::map<uint64_t, std::vector<uint32_t>> lists_of_shard;  // touched lists of every touched shard, ascending
+  for (uint64_t l = 0; l < nlists; ++l) {
+    uint64_t kept = 0;
+    for (uint32_t b = 0; b < (h_len[l] + 63u) / 64u; ++b) kept += (uint64_t)__builtin_popcountll(h_allow[h_first[l] + b]);
+    if (kept == h_len[l]) continue;
+    lists_of_shard[ix->meta.c2s[l]].push_back((uint32_t)l);
+    ++rs.lists_touched;
+    rs.lists_emptied += kept == 0;
+  }
+  const double t1 = now_ms();
+  rs.ms_plan = (float)(t1 - t0);
+
+  // ---- files: every touched shard under a temporary name ----
+  std::vector<std::pair<std::string, std::string>> renames;  // (temporary, final)
+  auto drop_temporaries = [&] { for (auto &r : renames) ::unlink(r.first.c_str()); };
+  for (const auto &kv : lists_of_shard) {
+    const uint64_t s = kv.first;
+    ShardFile f;
+    vi_status rc = f.open(ix->shards_dir, s);
+    if (rc == VI_OK && f.dim() != dim) rc = fail(VI_ERR_INVALID_DATA, "shard_%llu.bin holds dimension %u", (unsigned long long)s, f.dim());
+    std::vector<const uint64_t *> keep_of(rc == VI_OK ? f.num_lists() : 0, nullptr);
+    for (size_t li = 0; rc == VI_OK && li < kv.second.size(); ++li) {
+      const uint32_t l = kv.second[li];
+      const ShardListView *lv = f.find(l);
+      if (!lv || lv->num_vectors != h_len[l]) {  // (the resident blocks are what the records are taken to be)
+        rc = fail(VI_ERR_INVALID_DATA, "shard_%llu.bin no longer matches the resident list %u", (unsigned long long)s, l);
+        break;
+      }
+      keep_of[lv - &f.list(0)] = h_allow.data() + h_first[l];
+    }
+    const std::string path = shard_file_path(ix->shards_dir, s), tmp = path + ".tmp";
+    uint64_t bytes = 0;
+    if (rc == VI_OK) rc = shard_retain_write(f, s, keep_of, tmp, &bytes, nullptr);
+    if (rc != VI_OK) { drop_temporaries(); return rc; }
+    renames.emplace_back(tmp, path);
+    rs.bytes_written += bytes;
+    ++rs.shards_rewritten;
+  }
+  const double t2 = now_ms();
+
+  // ---- the new resident index, beside the old one ----
+  auto dev = std::make_unique<DeviceIndex>();
+  const vi_status rc = device_index_compact(old, keep, dev.get(), &rs.ms_kernel, &rs.kernel_bytes);
+  if (rc != VI_OK) { drop_temporaries(); return rc; }
+  const double t3 = now_ms();
+  rs.ms_index = (float)(t3 - t2);
+
+  // ---- renames, then the swap ----
+  for (size_t i = 0; i < renames.size(); ++i)
+    if (::rename(renames[i].first.c_str(), renames[i].second.c_str()) != 0) {
+      const int e = errno;
+      for (size_t j = i; j < renames.size(); ++j) ::unlink(renames[j].first.c_str());
+      return fail(VI_ERR_IO, "rename(%s): %s%s", renames[i].first.c_str(), strerror(e),
+                  i ? " (earlier shard files of this call are already in place: reload the index)" : "");
+    }
+  ix->dev = std::move(dev);
+  const double t4 = now_ms();
+  rs.ms_files = (float)((t2 - t1) + (t4 - t3));
+  rs.ms_total = (float)(t4 - t0);
+  ix->remove_stats = rs;
+  if (removed_out) *removed_out = n_removed;
   return VI_OK;
 }
 
@@ -599,6 +688,48 @@ vi_status vi_indexer_add_records(vi_indexer *ix, const uint64_t *ext_ids, const 
   if (n > 0xFFFFFFFEull || ix->impl.dev->nvec_resident + n > 0xFFFFFFFEull)
     return fail(VI_ERR_INVALID_INPUT, "more than 2^32 - 2 vectors");
   return vi::add_records(&ix->impl, ext_ids, values, timestamps, n);
+  });
+}
+
+// the refusals vi_indexer_retain and vi_indexer_remove_ids share, before any file or device change
+static vi_status remove_common(const vi_indexer *ix) {
+  if (!ix) return fail(VI_ERR_INVALID_INPUT, "null indexer");
+  if (!ix->impl.dev) return fail(VI_ERR_INVALID_INPUT, "the indexer holds no index (build or load it first)");
+  if (ix->impl.cfg.world_size > 1 || ix->impl.dev->stripe_world > 1)
+    return fail(VI_ERR_INVALID_INPUT, "records are removed through an unpartitioned handle (world_size <= 1); ranks reload from its files");
+  return VI_OK;
+}
+
+vi_status vi_indexer_retain(vi_indexer *ix, const vi_filter *keep, uint64_t *removed_out) {
+  return vi::guarded([&]() -> vi_status {
+  if (removed_out) *removed_out = 0;
+  VI_TRY(remove_common(ix));
+  if (!keep) return fail(VI_ERR_INVALID_INPUT, "null filter");
+  if (keep->impl.owner_serial != ix->impl.dev->serial)
+    return fail(VI_ERR_INVALID_INPUT, "the filter was made from another indexer (or before this one was rebuilt)");
+  return vi::retain_records(&ix->impl, keep->impl, removed_out);
+  });
+}
+
+vi_status vi_indexer_remove_ids(vi_indexer *ix, const uint64_t *ext_ids, uint64_t n, uint64_t *removed_out) {
+  return vi::guarded([&]() -> vi_status {
+  if (removed_out) *removed_out = 0;
+  VI_TRY(remove_common(ix));
+  if (n && !ext_ids) return fail(VI_ERR_INVALID_INPUT, "null id set with n = %llu", (unsigned long long)n);
+  if (n == 0) return VI_OK;  // nothing changes: no file, no index, no filter
+  vi::SlotFilter keep;       // the records a VI_IDS_DENY filter of the set admits
+  VI_TRY(vi::slot_filter_ids(*ix->impl.dev, ext_ids, n, false, true, &keep));
+  return vi::retain_records(&ix->impl, keep, removed_out);
+  });
+}
+
+vi_status vi_shard_remove_from(const char *shards_dir, uint64_t shard_id, const uint64_t *ext_ids, uint64_t n,
+                               uint64_t *removed_out) {
+  return vi::guarded([&]() -> vi_status {
+  if (removed_out) *removed_out = 0;
+  if (!shards_dir) return fail(VI_ERR_INVALID_INPUT, "null pointer");
+  if (n && !ext_ids) return fail(VI_ERR_INVALID_INPUT, "null id set with n = %llu", (unsigned long long)n);
+  return vi::shard_remove_from(shards_dir, shard_id, ext_ids, n, removed_out);
   });
 }
 
@@ -905,6 +1036,14 @@ vi_status vi_indexer_last_add_stats(const vi_indexer *ix, vi_add_stats *out) {
   return vi::guarded([&]() -> vi_status {
   if (!ix || !out) return fail(VI_ERR_INVALID_INPUT, "no stats");
   *out = ix->impl.add_stats;
+  return VI_OK;
+  });
+}
+
+vi_status vi_indexer_last_remove_stats(const vi_indexer *ix, vi_remove_stats *out) {
+  return vi::guarded([&]() -> vi_status {
+  if (!ix || !out) return fail(VI_ERR_INVALID_INPUT, "no stats");
+  *out = ix->impl.remove_stats;
   return VI_OK;
   });
 }

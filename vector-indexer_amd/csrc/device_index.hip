@@ -1,13 +1,15 @@
 // device_index.hip — where a resident index (DeviceIndex, device_index.hpp) is constructed.
 //
-// Four routes build one (device_index.hpp names them and their callers): device_index_load and device_index_from_rows
-// here, device_index_from_order in list_build.hip, device_index_append in list_append.hip.  The steps they share:
+// Five routes build one (device_index.hpp names them and their callers): device_index_load and device_index_from_rows
+// here, device_index_from_order in list_build.hip, device_index_append in list_append.hip, device_index_compact in
+// list_compact.hip.  The steps they share:
 //   layout        plan_list_layout (list_layout.hpp): first block and local length of every list, the two 32-bit limits
 //   storage       alloc_list_storage: blocks, ids, timestamps and the per-list arrays, sized and uploaded from the layout
 //   coarse table  coarse_table_from_rows / repack_table: rows 0..n-1 into lane-interleaved blocks
+//   (layout, storage and a copied coarse table at once for the two routes that start from an older index: lay_out_from_old)
 //   ending        prepare_rank_images (rank_images.hip)
 // What fills the list blocks is each route's own: repack_kernel (shard records), repack_rows_kernel (rows of a matrix),
-// append_blocks_kernel (an older index).
+// append_blocks_kernel (an older index and new rows), compact_blocks_kernel (the kept records of an older index).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -155,6 +157,36 @@ vi_status alloc_list_storage(DeviceIndex *ix, const ListLayout &lay, const uint3
     for (uint64_t l = 0; l < nlists; ++l) ix->nshards = std::max<uint64_t>(ix->nshards, (uint64_t)shard_host[l] + 1);
     VI_TRY(upload(ix->list_shard, shard_host, nlists, st));
   }
+  return VI_OK;
+}
+
+vi_status lay_out_from_old(DeviceIndex *ix, const DeviceIndex &old, const uint64_t *full_len, DevBuf<uint32_t> *block_list_dev) {
+  const uint64_t nlists = ix->nlists;
+  const uint32_t dq = ix->dq;
+  hipStream_t st = ix->stream;
+  // lists back to back in list order, each padded to whole blocks (as a load lays them)
+  ListLayout lay;
+  switch (plan_list_layout(full_len, nlists, 1, 0, &lay)) {
+    case LayoutError::list_too_long: return fail(VI_ERR_INVALID_INPUT, "a list would pass the 32-bit position limit");
+    case LayoutError::too_many_slots: return fail(VI_ERR_INVALID_INPUT, "index too large for 32-bit slot ids");
+    case LayoutError::none: break;
+  }
+  std::vector<uint32_t> block_list(lay.total_blocks);
+  for (uint64_t l = 0; l < nlists; ++l) {
+    const uint64_t nb = ((uint64_t)lay.len[l] + kWave - 1) / kWave;
+    std::fill(block_list.begin() + lay.first[l], block_list.begin() + lay.first[l] + nb, (uint32_t)l);
+  }
+  // coarse table and shard of every list: unchanged
+  ix->centroids.dq = dq;
+  ix->centroids.nblocks = old.centroids.nblocks;
+  const uint64_t cwords = std::max<uint64_t>(1, old.centroids.nblocks) * dq * kWave * 4;
+  VI_TRY(ix->centroids.blocks.reserve(cwords));
+  if (old.centroids.nblocks)
+    VI_HIP(hipMemcpyAsync(ix->centroids.blocks.p, old.centroids.blocks.p, old.centroids.nblocks * dq * kWave * 4 * sizeof(float),
+                          hipMemcpyDeviceToDevice, st));
+  VI_TRY(alloc_list_storage(ix, lay, nullptr, &old, true));
+  VI_TRY(upload(*block_list_dev, block_list.data(), block_list.size(), st));
+  VI_HIP(hipStreamSynchronize(st));  // (lay and block_list are read by the copies queued above)
   return VI_OK;
 }
 

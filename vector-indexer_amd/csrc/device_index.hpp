@@ -166,7 +166,7 @@ struct DeviceIndex {
   ~DeviceIndex();
 };
 
-// ---- the four routes to a resident index ----
+// ---- the five routes to a resident index ----
 // Each lays its lists out by list_layout.hpp, reserves and uploads through alloc_list_storage, builds (or copies) the
 // coarse table and ends with prepare_rank_images (search_internal.hpp, device_index.hip); what differs is where the list
 // blocks come from:
@@ -176,6 +176,8 @@ struct DeviceIndex {
 //                                                the k-means assignment (kmeans.hip)
 //   device_index_from_order  (list_build.hip)    rows of a device matrix, grouped on the device: a single-GPU build (api.cpp)
 //   device_index_append      (list_append.hip)   the blocks of an older index and new rows: vi_indexer_add_records (api.cpp)
+//   device_index_compact     (list_compact.hip)  the blocks of an older index less the records a filter excludes:
+//                                                vi_indexer_retain / vi_indexer_remove_ids (api.cpp)
 //
 // Upload: centroid table + this rank's part of the lists, repacked on the GPU.  placement 0: a stripe of every list
 // (block b on rank b % world); 1: the whole lists of the shard files dealt to this rank (greedy by bytes).
@@ -206,6 +208,12 @@ vi_status device_index_from_order(int device, uint32_t dim, const float *table_h
 vi_status device_index_append(const DeviceIndex &old, const float *rows_dev, uint64_t n, const uint32_t *order_dev,
                               const uint32_t *seg_dev, const std::vector<uint64_t> &seg_host, const uint64_t *row_ext_dev,
                               const uint64_t *row_ts_dev, DeviceIndex *out, float *ms_kernel, uint64_t *kernel_bytes);
+// `out` = a fresh index holding the records of `old` (unpartitioned; only read) whose allow bit in `keep` (a filter of
+// `old`) is 1: the kept records of every list close up in their old order, a list that keeps none stays as an empty list.
+// Blocks are gathered device to device, nothing comes from the shard files; old and new index coexist until the caller
+// drops the old one.  ms_kernel / kernel_bytes (optional): HIP-event time of compact_blocks_kernel and the bytes it moves.
+vi_status device_index_compact(const DeviceIndex &old, const SlotFilter &keep, DeviceIndex *out, float *ms_kernel,
+                               uint64_t *kernel_bytes);
 
 struct SearchIO {
   const float *queries = nullptr;  // host or device (queries_on_device)

@@ -144,33 +144,13 @@ vi_status device_index_append(const DeviceIndex &old, const float *rows_dev, uin
   }
   std::vector<uint64_t> full_len(nlists);
   for (uint64_t l = 0; l < nlists; ++l) full_len[l] = (uint64_t)o_len[l] + (seg_host[l + 1] - seg_host[l]);
-  ListLayout lay;
-  switch (plan_list_layout(full_len.data(), nlists, 1, 0, &lay)) {
-    case LayoutError::list_too_long: return fail(VI_ERR_INVALID_INPUT, "a list would pass the 32-bit position limit");
-    case LayoutError::too_many_slots: return fail(VI_ERR_INVALID_INPUT, "index too large for 32-bit slot ids");
-    case LayoutError::none: break;
-  }
-  const uint64_t total_blocks = lay.total_blocks;
-  std::vector<uint32_t> block_list(total_blocks);
-  for (uint64_t l = 0; l < nlists; ++l) {
-    const uint64_t nb = ((uint64_t)lay.len[l] + kWave - 1) / kWave;
-    std::fill(block_list.begin() + lay.first[l], block_list.begin() + lay.first[l] + nb, (uint32_t)l);
-  }
-  // coarse table and shard of every list: unchanged
-  ix->centroids.dq = dq;
-  ix->centroids.nblocks = old.centroids.nblocks;
-  const uint64_t cwords = std::max<uint64_t>(1, old.centroids.nblocks) * dq * kWave * 4;
-  VI_TRY(ix->centroids.blocks.reserve(cwords));
-  if (old.centroids.nblocks)
-    VI_HIP(hipMemcpyAsync(ix->centroids.blocks.p, old.centroids.blocks.p, old.centroids.nblocks * dq * kWave * 4 * sizeof(float),
-                          hipMemcpyDeviceToDevice, st));
-  VI_TRY(alloc_list_storage(ix, lay, nullptr, &old, true));  // (queues the new first / len ahead of the kernel below)
+  DevBuf<uint32_t> d_block_list;
+  VI_TRY(lay_out_from_old(ix, old, full_len.data(), &d_block_list));  // (the new first / len are in place for the kernel below)
+  const uint64_t total_blocks = ix->lists.nblocks;
   if (ms_kernel) *ms_kernel = 0.0f;
   if (kernel_bytes) *kernel_bytes = 0;
   if (total_blocks) {
     if (!old.timestamps.p || !old.ext_ids.p) return fail(VI_ERR_INVALID_INPUT, "the index keeps no ids or timestamps");
-    DevBuf<uint32_t> d_block_list;
-    VI_TRY(upload(d_block_list, block_list.data(), block_list.size(), st));
     AppendArgs a{};
     a.old_blocks = (const float4 *)old.lists.blocks.p;
     a.old_ext = old.ext_ids.p; a.old_ts = old.timestamps.p;

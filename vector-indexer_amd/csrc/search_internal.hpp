@@ -1,6 +1,6 @@
 // search_internal.hpp — what the search engines' and the index builders' translation units (search_kernels.hip,
 // generic_search.hip, filter_search.hip, grouping.hip, select.hip, range_select.hip, rank_images.hip, device_index.hip,
-// list_build.hip, list_append.hip, kmeans.hip) call in each other and share: declared once, here.  (The probe grouping is called through a header of its own, grouping.hpp; filter_search.hip launches
+// list_build.hip, list_append.hip, list_compact.hip, kmeans.hip) call in each other and share: declared once, here.  (The probe grouping is called through a header of its own, grouping.hpp; filter_search.hip launches
 // its rank and select phases through rank_stream.hpp and select.hpp.)
 #pragma once
 #include <algorithm>
@@ -59,6 +59,10 @@ vi_status init_device_index(DeviceIndex *ix, int device, uint32_t dim, uint64_t 
 // are queued: `lay` and shard_host stay alive until the caller has synchronised ix->stream.
 vi_status alloc_list_storage(DeviceIndex *ix, const ListLayout &lay, const uint32_t *shard_host, const DeviceIndex *shard_from,
                              bool with_timestamps);
+// An initialised index that keeps the lists of `old` (unpartitioned) at new lengths full_len[l]: the layout planned (its
+// two limits: VI_ERR_INVALID_INPUT), the coarse table and list_shard copied from `old` device to device, the list storage
+// allocated (alloc_list_storage, with timestamps) and block_list_dev = the list of every new block.  Complete on return.
+vi_status lay_out_from_old(DeviceIndex *ix, const DeviceIndex &old, const uint64_t *full_len, DevBuf<uint32_t> *block_list_dev);
 // rows 0..n-1 of a row-major device matrix -> ceil(n / 64) lane-interleaved blocks, pad lanes zero; complete on return.
 // ros_keep (optional): the row-of-slot scratch in a buffer of the caller's, kept from call to call.
 vi_status repack_table(const float *rows_dev, uint64_t n, uint32_t dim, uint32_t dq, float *blocks, hipStream_t st,

@@ -11,6 +11,7 @@
 #include <cstdio>
 #include <cstring>
 #include <unordered_map>
+#include <unordered_set>
 
 namespace vi {
 
@@ -225,6 +226,108 @@ vi_status shard_append_to(const std::string &shards_dir, uint64_t shard_id, uint
     ::unlink(tmp.c_str());
     return fail(VI_ERR_IO, "rename(%s): %s", tmp.c_str(), strerror(e));
   }
+  return VI_OK;
+}
+
+vi_status shard_retain_write(const ShardFile &f, uint64_t shard_id, const std::vector<const uint64_t *> &keep,
+                             const std::string &out_path, uint64_t *bytes_out, uint64_t *removed_out) {
+  const uint32_t dim = f.dim(), nl = f.num_lists();
+  if (keep.size() != nl) return fail(VI_ERR_OTHER, "retain: %zu keep entries for %u lists", keep.size(), nl);
+  const uint64_t vsz = 4ull * dim, pad = pad8(vsz), stride = record_stride(dim);
+  auto stays = [](const uint64_t *w, uint32_t p) { return ((w[p >> 6] >> (p & 63u)) & 1ull) != 0; };
+  std::vector<uint32_t> kept(nl);
+  const uint64_t data_off = kShardHeaderBytes + kIndexEntryBytes * (uint64_t)nl;
+  uint64_t total = data_off, removed = 0;
+  for (uint32_t i = 0; i < nl; ++i) {
+    const uint32_t nv = f.list(i).num_vectors;
+    uint32_t n = nv;
+    if (keep[i]) {
+      n = 0;
+      for (uint32_t p = 0; p < nv; ++p) n += stays(keep[i], p);
+    }
+    kept[i] = n;
+    removed += nv - n;
+    total += vsz + pad + (uint64_t)n * stride;
+  }
+  std::vector<uint8_t> img(total, 0);
+  uint8_t *p = img.data();
+  auto put64 = [&](uint64_t off, uint64_t v) { std::memcpy(p + off, &v, 8); };
+  auto put32 = [&](uint64_t off, uint32_t v) { std::memcpy(p + off, &v, 4); };
+  put64(0, shard_id); put64(8, 1); put32(16, dim); put32(20, nl);
+  put64(24, kShardHeaderBytes); put64(32, data_off);
+  uint64_t cur = data_off;
+  for (uint32_t i = 0; i < nl; ++i) {
+    const ShardListView &lv = f.list(i);
+    const uint64_t size = vsz + pad + (uint64_t)kept[i] * stride;
+    const uint64_t e = kShardHeaderBytes + (uint64_t)i * kIndexEntryBytes;
+    put64(e, lv.centroid_id); put32(e + 8, kept[i]); put32(e + 12, 0);
+    put64(e + 16, cur); put64(e + 24, size);
+    std::memcpy(p + cur, lv.centroid, vsz);
+    uint8_t *o = p + cur + vsz + pad;
+    if (kept[i] == lv.num_vectors) {  // nothing lost: verbatim
+      if (kept[i]) std::memcpy(o, lv.records, (uint64_t)kept[i] * stride);
+    } else {
+      for (uint32_t v = 0; v < lv.num_vectors;) {  // runs of kept records
+        if (!stays(keep[i], v)) { ++v; continue; }
+        uint32_t end = v + 1;
+        while (end < lv.num_vectors && stays(keep[i], end)) ++end;
+        std::memcpy(o, lv.records + (uint64_t)v * stride, (uint64_t)(end - v) * stride);
+        o += (uint64_t)(end - v) * stride;
+        v = end;
+      }
+    }
+    cur += size;
+  }
+  FILE *out = fopen(out_path.c_str(), "wb");
+  if (!out) return fail(VI_ERR_IO, "File::create(%s): %s", out_path.c_str(), strerror(errno));
+  const bool ok = img.empty() || fwrite(img.data(), 1, img.size(), out) == img.size();
+  if (fclose(out) != 0 || !ok) {
+    ::unlink(out_path.c_str());
+    return fail(VI_ERR_IO, "write(%s) failed", out_path.c_str());
+  }
+  if (bytes_out) *bytes_out = total;
+  if (removed_out) *removed_out = removed;
+  return VI_OK;
+}
+
+vi_status shard_remove_from(const std::string &shards_dir, uint64_t shard_id, const uint64_t *ext_ids, uint64_t n,
+                            uint64_t *removed_out) {
+  if (removed_out) *removed_out = 0;
+  const std::string path = shard_path(shards_dir, shard_id), tmp = path + ".tmp";
+  uint64_t removed = 0;
+  {
+    ShardFile f;
+    VI_TRY(f.open(shards_dir, shard_id));
+    if (n == 0) return VI_OK;
+    const std::unordered_set<uint64_t> gone(ext_ids, ext_ids + n);
+    const uint32_t nl = f.num_lists();
+    const uint64_t stride = record_stride(f.dim());
+    std::vector<std::vector<uint64_t>> words(nl);
+    std::vector<const uint64_t *> keep(nl, nullptr);
+    for (uint32_t i = 0; i < nl; ++i) {
+      const ShardListView &lv = f.list(i);
+      if (f.find(lv.centroid_id) != &lv) continue;  // (a later entry of a repeated centroid id: no reader sees it)
+      bool any = false;
+      words[i].assign(((uint64_t)lv.num_vectors + 63) / 64, 0);
+      for (uint32_t v = 0; v < lv.num_vectors; ++v) {
+        uint64_t ext;
+        std::memcpy(&ext, lv.records + (uint64_t)v * stride + 8, 8);  // VectorMeta.external_id
+        if (gone.count(ext)) any = true;
+        else words[i][v >> 6] |= 1ull << (v & 63u);
+      }
+      if (any) keep[i] = words[i].data();
+    }
+    bool any = false;
+    for (const uint64_t *k : keep) any = any || k;
+    if (!any) return VI_OK;
+    VI_TRY(shard_retain_write(f, shard_id, keep, tmp, nullptr, &removed));
+  }  // (unmapped before the rename)
+  if (::rename(tmp.c_str(), path.c_str()) != 0) {
+    const int e = errno;
+    ::unlink(tmp.c_str());
+    return fail(VI_ERR_IO, "rename(%s): %s", tmp.c_str(), strerror(e));
+  }
+  if (removed_out) *removed_out = removed;
   return VI_OK;
 }
 

@@ -73,6 +73,22 @@ vi_status shard_append_to(const std::string &shards_dir, uint64_t shard_id, uint
                           const uint64_t *ids, const uint64_t *ext_ids, const uint64_t *timestamps, const float *vecs);
 std::string shard_file_path(const std::string &shards_dir, uint64_t shard_id);
 
+// Remove records from lists of an open shard file.  keep[i] belongs to list entry i of the file (file order; keep has
+// num_lists() entries): null = every record of the list stays, else record p stays iff bit p % 64 of word p / 64 is set
+// (ceil(num_vectors / 64) words: the allow words of a SlotFilter over the list's blocks).  The file of the remaining lists
+// is written to out_path — byte-identical to shard_save_to of them: lists keep their file order, centroid vectors and
+// kept records are copied verbatim (VectorMeta.id included), a list that keeps nothing stays as an entry with
+// num_vectors == 0 — and f's own file is left alone: the caller renames.  bytes_out / removed_out (optional): size of the
+// file written, records removed.
+vi_status shard_retain_write(const ShardFile &f, uint64_t shard_id, const std::vector<const uint64_t *> &keep,
+                             const std::string &out_path, uint64_t *bytes_out, uint64_t *removed_out);
+// ... for one shard file on its own, by external id: every record whose external id is one of ext_ids[0..n) goes (any
+// order, duplicates allowed, unknown ids ignored; of entries that repeat a centroid id only the first, the one a reader
+// finds, is looked at).  Open, write beside the file under a temporary name, rename; nothing matches: the file is opened
+// (the reader's errors) and left as it is.
+vi_status shard_remove_from(const std::string &shards_dir, uint64_t shard_id, const uint64_t *ext_ids, uint64_t n,
+                            uint64_t *removed_out);
+
 // index/index.bin: IvfIndex{centroids, centroids_to_shard, dimension} through bincode 2
 // `config::standard()` + ndarray serde.  PARITY UNPINNED (no cargo here to confirm bytes).
 struct IndexMeta {

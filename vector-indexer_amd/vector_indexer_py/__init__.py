@@ -10,6 +10,7 @@ bindings/python/python/vector_indexer_py/__init__.py):
     VectorIndex.search_sync(xq, k, n_probe)
     VectorIndex.dimension
     VectorIndex.add(xb, ext_ids=None, timestamps=None)      extension: append records to a built or loaded index
+    VectorIndex.remove_ids(ids) / .retain(filter) -> int    extension: remove records from it (by id / all a filter excludes)
 
 Errors surface as RuntimeError, as PyO3's PyRuntimeError does.  There is NO CPU fallback: if
 libvi_amd.so is missing or no MI355X is visible, build/load/search raise.
@@ -287,6 +288,33 @@ class VectorIndex:
         """phases of the most recent add() that added something"""
         st = _native.AddStats()
         _native.check(lib().vi_indexer_last_add_stats(self._h, C.byref(st)))
+        return {f: getattr(st, f) for f, _ in st._fields_}
+
+    def retain(self, filter: AnyFilter) -> int:
+        """extension: keep exactly the records `filter` (a filter of this index) admits, in the shard files and on the
+        GPU; the kept records of every list close up in their old order, nothing is retrained -> records removed.
+        Unpartitioned indexes only; at least one record must stay.  Unless nothing was removed, filters made before the
+        call — `filter` included — are rejected afterwards; RangeResults must be copied or freed before it; the call must
+        not overlap searches of this index."""
+        if filter is None:
+            raise ViError(_native.VI_ERR_INVALID_INPUT, "null filter")
+        removed = C.c_uint64(0)
+        _native.check(lib().vi_indexer_retain(self._h, filter._h, C.byref(removed)), prefix="Failed to remove records: ")
+        return int(removed.value)
+
+    def remove_ids(self, ids) -> int:
+        """extension: remove every record whose external id is in `ids` (any integer array-like; no order needed,
+        duplicates allowed, unknown ids ignored) -> records removed.  The limits of retain() apply."""
+        a = _native.id_array(ids)
+        removed = C.c_uint64(0)
+        _native.check(lib().vi_indexer_remove_ids(self._h, _native.ptr(a) if a.size else None, a.size, C.byref(removed)),
+                      prefix="Failed to remove records: ")
+        return int(removed.value)
+
+    def remove_stats(self) -> dict:
+        """phases of the most recent retain() / remove_ids() that removed something"""
+        st = _native.RemoveStats()
+        _native.check(lib().vi_indexer_last_remove_stats(self._h, C.byref(st)))
         return {f: getattr(st, f) for f, _ in st._fields_}
 
     def build_stats(self) -> dict:

@@ -52,6 +52,12 @@ class AddStats(C.Structure):
                 ("ms_assign", f32), ("ms_files", f32), ("ms_index", f32), ("ms_kernel", f32), ("kernel_bytes", u64)]
 
 
+class RemoveStats(C.Structure):
+    _fields_ = [("n_removed", u64), ("lists_touched", u64), ("lists_emptied", u64), ("shards_rewritten", u64),
+                ("bytes_written", u64), ("ms_total", f32), ("ms_plan", f32), ("ms_files", f32), ("ms_index", f32),
+                ("ms_kernel", f32), ("kernel_bytes", u64)]
+
+
 FETCH_ROWS_FN = C.CFUNCTYPE(C.c_int, vp, C.POINTER(u64), u64, vp)
 
 
@@ -128,6 +134,10 @@ SIGNATURES = {
     "vi_indexer_enable_timing": (None, [vp, C.c_int]),
     "vi_indexer_last_build_stats": (C.c_int, [vp, C.POINTER(BuildStats)]),
     "vi_indexer_last_add_stats": (C.c_int, [vp, C.POINTER(AddStats)]),
+    "vi_indexer_retain": (C.c_int, [vp, vp, C.POINTER(u64)]),
+    "vi_indexer_remove_ids": (C.c_int, [vp, vp, u64, C.POINTER(u64)]),
+    "vi_shard_remove_from": (C.c_int, [C.c_char_p, u64, vp, u64, C.POINTER(u64)]),
+    "vi_indexer_last_remove_stats": (C.c_int, [vp, C.POINTER(RemoveStats)]),
 }
 
 _lib = None

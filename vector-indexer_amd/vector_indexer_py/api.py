@@ -8,6 +8,7 @@
     .search(req) / .search_request(query) / .config()                             api.rs:101-237
     .range_search(query, radius2, ...)                                            extension: everything within a radius
     .add_records(records)                                                         extension: append to a built index
+    .remove_records(external_ids) -> int                                          extension: remove from a built index
     SearchRequest.with_timestamp_range / .with_allowed_ids / .with_excluded_ids   extension: filtered search
 
 Errors are ViError (a RuntimeError) whose .kind is the io::ErrorKind name the reference returns.
@@ -220,6 +221,15 @@ class VectorIndexer:
         self._drop_filters()  # (cached filters describe the index this call replaces)
         _native.check(lib().vi_indexer_add_records(self._h, _native.ptr(ext), _native.ptr(vals), _native.ptr(ts), n))
         return self
+
+    def remove_records(self, external_ids) -> int:
+        """extension: remove every record whose external id is in external_ids from the built or loaded index (files and
+        resident index; unknown ids are ignored) -> records removed.  An empty set changes nothing."""
+        ids = _native.id_array(external_ids)
+        removed = C.c_uint64(0)
+        self._drop_filters()  # (cached filters describe the index this call replaces)
+        _native.check(lib().vi_indexer_remove_ids(self._h, _native.ptr(ids) if ids.size else None, ids.size, C.byref(removed)))
+        return int(removed.value)
 
     def build_from_vector_file(self, path) -> "VectorIndexer":
         self._drop_filters()

@@ -119,7 +119,7 @@ def synthetic_dataset(n: int, d: int, nq: int, k: int, seed: int = 42) -> Tuple[
 # ---- the adapter + eval loop --------------------------------------------------------------------------------------
 class FaissStyleAdapter:
     """the Faiss-looking face of an index: .d, .nprobe (settable), .search(xq, k) -> (D, I), .range_search(x, thresh),
-    .add(x), .add_with_ids(x, ids)
+    .add(x), .add_with_ids(x, ids), .remove_ids(ids) -> int, .ntotal
     (vector_indexer_adapter.py:75-140; the reference hops through an asyncio thread, the search here is synchronous)"""
 
     def __init__(self, vector_index, k: int = 100):
@@ -168,6 +168,14 @@ class FaissStyleAdapter:
     def add_with_ids(self, x: np.ndarray, ids):
         """Faiss's Index.add_with_ids"""
         self._idx.add(np.ascontiguousarray(x, dtype=np.float32), ext_ids=ids)
+
+    def remove_ids(self, ids) -> int:
+        """Faiss's Index.remove_ids for a batch of ids: the number of records removed"""
+        return self._idx.remove_ids(ids)
+
+    @property
+    def ntotal(self) -> int:
+        return self._idx.num_vectors
 
     def __repr__(self):
         return f"FaissStyleAdapter(d={self.d}, nprobe={self.nprobe})"
