@@ -196,9 +196,28 @@ static vi_status fit_and_save(Indexer *ix, const float *X, const uint64_t *ext_i
   return rc;
 }
 
-// vi_indexer_add_records behind its argument checks: labels on the GPU, the touched shard files written under temporary
-// names, the new resident index built from the old blocks, then the renames, then the swap.  Everything before the renames
-// can fail without a trace: the temporary files are removed, the handle keeps its index.
+// ---- updates of a built index: add_records and retain_records ----
+// Both run: a plan (which lists change), the touched shard files written under temporary names (ShardRewriteSet,
+// shards.hpp), the new resident index built from the old blocks (list_update.hip), then the renames, then the swap.
+// Everything before the renames can fail without a trace: the temporary files are removed, the handle keeps its index.
+
+// the lengths of the resident lists, read back once per call
+static vi_status read_list_lengths(const DeviceIndex &ix, std::vector<uint32_t> *len) {
+  len->resize(ix.nlists);
+  if (ix.nlists) VI_HIP(hipMemcpy(len->data(), ix.list_len.p, ix.nlists * 4, hipMemcpyDeviceToHost));
+  return VI_OK;
+}
+
+// touched lists of every touched shard, ascending; touched(l) is asked once per list, in list order
+template <typename F>
+static std::map<uint64_t, std::vector<uint32_t>> touched_lists_by_shard(const IndexMeta &meta, uint64_t nlists, F touched) {
+  std::map<uint64_t, std::vector<uint32_t>> lists_of_shard;
+  for (uint64_t l = 0; l < nlists; ++l)
+    if (touched(l)) lists_of_shard[meta.c2s[l]].push_back((uint32_t)l);
+  return lists_of_shard;
+}
+
+// vi_indexer_add_records behind its argument checks; the plan is the label of every new record, from the GPU
 static vi_status add_records(Indexer *ix, const uint64_t *ext_ids, const float *X, const uint64_t *timestamps, uint64_t n) {
   const DeviceIndex &old = *ix->dev;
   const uint32_t dim = ix->cfg.dimension;
@@ -232,9 +251,9 @@ static vi_status add_records(Indexer *ix, const uint64_t *ext_ids, const float *
   VI_TRY(device_index_label_rows(old, Xd.p, n, lab.p));
   std::vector<uint64_t> seg;
   VI_TRY(group_ids_by_label_device(lab.p, n, nlists, order, seg_dev, &seg, st));
-  std::vector<uint32_t> h_order(n), h_len(nlists);
+  std::vector<uint32_t> h_order(n), h_len;
   VI_HIP(hipMemcpy(h_order.data(), order.p, n * 4, hipMemcpyDeviceToHost));
-  VI_HIP(hipMemcpy(h_len.data(), old.list_len.p, nlists * 4, hipMemcpyDeviceToHost));
+  VI_TRY(read_list_lengths(old, &h_len));
   if (seg.size() != nlists + 1 || seg[nlists] != n) return fail(VI_ERR_OTHER, "add: a record was assigned to no list");
   {  // the slot limit of the new layout, before anything is written
     std::vector<uint64_t> full_len(nlists);
@@ -247,74 +266,57 @@ static vi_status add_records(Indexer *ix, const uint64_t *ext_ids, const float *
   as.ms_assign = (float)(t1 - t0);
 
   // ---- files: every touched shard under a temporary name ----
-  std::map<uint64_t, std::vector<uint32_t>> lists_of_shard;  // touched lists of every touched shard, ascending
-  for (uint64_t l = 0; l < nlists; ++l)
-    if (seg[l + 1] > seg[l]) { lists_of_shard[ix->meta.c2s[l]].push_back((uint32_t)l); ++as.lists_touched; }
-  std::vector<std::pair<std::string, std::string>> renames;  // (temporary, final)
-  auto drop_temporaries = [&] { for (auto &r : renames) ::unlink(r.first.c_str()); };
+  const auto lists_of_shard = touched_lists_by_shard(ix->meta, nlists, [&](uint64_t l) {
+    as.lists_touched += seg[l + 1] > seg[l];
+    return seg[l + 1] > seg[l];
+  });
+  ShardRewriteSet files(ix->shards_dir);
   {
     std::vector<uint64_t> s_cid, s_id, s_ext, s_ts;
     std::vector<float> s_vec;
     for (const auto &kv : lists_of_shard) {
       const uint64_t s = kv.first;
       ShardFile f;
-      vi_status rc = f.open(ix->shards_dir, s);
-      if (rc == VI_OK && f.dim() != dim) rc = fail(VI_ERR_INVALID_DATA, "shard_%llu.bin holds dimension %u", (unsigned long long)s, f.dim());
+      VI_TRY(files.open(s, dim, &f));
       s_cid.clear(); s_id.clear(); s_ext.clear(); s_ts.clear(); s_vec.clear();
-      for (size_t li = 0; rc == VI_OK && li < kv.second.size(); ++li) {
-        const uint32_t l = kv.second[li];
-        const ShardListView *lv = f.find(l);
-        if (!lv || lv->num_vectors != h_len[l]) {  // (the resident blocks are what the old records are taken to be)
-          rc = fail(VI_ERR_INVALID_DATA, "shard_%llu.bin no longer matches the resident list %u", (unsigned long long)s, l);
-          break;
-        }
+      for (const uint32_t l : kv.second) {
+        const ShardListView *lv;
+        VI_TRY(files.find(f, s, l, h_len[l], &lv));
         for (uint64_t e = seg[l]; e < seg[l + 1]; ++e) {
           const uint32_t r = h_order[e];
           s_cid.push_back(l); s_id.push_back(ids[r]); s_ext.push_back(ext[r]); s_ts.push_back(ts[r]);
           s_vec.insert(s_vec.end(), X + (uint64_t)r * dim, X + (uint64_t)r * dim + dim);
         }
       }
-      const std::string path = shard_file_path(ix->shards_dir, s), tmp = path + ".tmp";
       uint64_t bytes = 0;
-      if (rc == VI_OK)
-        rc = shard_append_write(f, s, s_cid.size(), s_cid.data(), s_id.data(), s_ext.data(), s_ts.data(), s_vec.data(), tmp,
-                                &bytes, nullptr);
-      if (rc != VI_OK) { drop_temporaries(); return rc; }
-      renames.emplace_back(tmp, path);
-      as.bytes_written += bytes;
-      ++as.shards_rewritten;
+      VI_TRY(shard_append_write(f, s, s_cid.size(), s_cid.data(), s_id.data(), s_ext.data(), s_ts.data(), s_vec.data(),
+                                files.temporary(s), &bytes, nullptr));
+      files.add(s, bytes);
     }
   }
   const double t2 = now_ms();
 
   // ---- the new resident index, beside the old one ----
   auto dev = std::make_unique<DeviceIndex>();
-  const vi_status rc = device_index_append(old, Xd.p, n, order.p, seg_dev.p, seg, ext_dev.p, ts_dev.p, dev.get(), &as.ms_kernel,
-                                           &as.kernel_bytes);
-  if (rc != VI_OK) { drop_temporaries(); return rc; }
+  VI_TRY(device_index_append(old, h_len, Xd.p, n, order.p, seg_dev.p, seg, ext_dev.p, ts_dev.p, dev.get(), &as.ms_kernel,
+                             &as.kernel_bytes));
   const double t3 = now_ms();
   as.ms_index = (float)(t3 - t2);
 
   // ---- renames, then the swap ----
-  for (size_t i = 0; i < renames.size(); ++i)
-    if (::rename(renames[i].first.c_str(), renames[i].second.c_str()) != 0) {
-      const int e = errno;
-      for (size_t j = i; j < renames.size(); ++j) ::unlink(renames[j].first.c_str());
-      return fail(VI_ERR_IO, "rename(%s): %s%s", renames[i].first.c_str(), strerror(e),
-                  i ? " (earlier shard files of this call are already in place: reload the index)" : "");
-    }
+  VI_TRY(files.commit());
   ix->dev = std::move(dev);
   const double t4 = now_ms();
+  as.bytes_written = files.bytes();
+  as.shards_rewritten = files.files();
   as.ms_files = (float)((t2 - t1) + (t4 - t3));
   as.ms_total = (float)(t4 - t0);
   ix->add_stats = as;
   return VI_OK;
 }
 
-// vi_indexer_retain / vi_indexer_remove_ids behind their argument checks, in the order of add_records: the plan from the
-// filter's allow words, the touched shard files written under temporary names, the new resident index gathered from the
-// old blocks, then the renames, then the swap.  Everything before the renames can fail without a trace.  `keep` is a
-// filter of ix->dev.
+// vi_indexer_retain / vi_indexer_remove_ids behind their argument checks; the plan comes from the allow words of `keep`, a
+// filter of ix->dev
 static vi_status retain_records(Indexer *ix, const SlotFilter &keep, uint64_t *removed_out) {
   const DeviceIndex &old = *ix->dev;
   const uint32_t dim = ix->cfg.dimension;
@@ -331,67 +333,51 @@ static vi_status retain_records(Indexer *ix, const SlotFilter &keep, uint64_t *r
   VI_HIP(hipSetDevice(old.device));
   // ---- plan: which positions of which lists stay (position p of list l: bit p % 64 of word first[l] + p / 64) ----
   std::vector<uint64_t> h_allow(old.lists.nblocks);
-  std::vector<uint32_t> h_first(nlists), h_len(nlists);
+  std::vector<uint32_t> h_first(nlists), h_len;
   if (old.lists.nblocks) VI_HIP(hipMemcpy(h_allow.data(), keep.allow.p, old.lists.nblocks * 8, hipMemcpyDeviceToHost));
   VI_HIP(hipMemcpy(h_first.data(), old.list_first_block.p, nlists * 4, hipMemcpyDeviceToHost));
-  VI_HIP(hipMemcpy(h_len.data(), old.list_len.p, nlists * 4, hipMemcpyDeviceToHost));
-  std::map<uint64_t, std::vector<uint32_t>> lists_of_shard;  // touched lists of every touched shard, ascending
-  for (uint64_t l = 0; l < nlists; ++l) {
+  VI_TRY(read_list_lengths(old, &h_len));
+  const auto lists_of_shard = touched_lists_by_shard(ix->meta, nlists, [&](uint64_t l) {
     uint64_t kept = 0;
     for (uint32_t b = 0; b < (h_len[l] + 63u) / 64u; ++b) kept += (uint64_t)__builtin_popcountll(h_allow[h_first[l] + b]);
-    if (kept == h_len[l]) continue;
-    lists_of_shard[ix->meta.c2s[l]].push_back((uint32_t)l);
+    if (kept == h_len[l]) return false;
     ++rs.lists_touched;
     rs.lists_emptied += kept == 0;
-  }
+    return true;
+  });
   const double t1 = now_ms();
   rs.ms_plan = (float)(t1 - t0);
 
   // ---- files: every touched shard under a temporary name ----
-  std::vector<std::pair<std::string, std::string>> renames;  // (temporary, final)
-  auto drop_temporaries = [&] { for (auto &r : renames) ::unlink(r.first.c_str()); };
+  ShardRewriteSet files(ix->shards_dir);
   for (const auto &kv : lists_of_shard) {
     const uint64_t s = kv.first;
     ShardFile f;
-    vi_status rc = f.open(ix->shards_dir, s);
-    if (rc == VI_OK && f.dim() != dim) rc = fail(VI_ERR_INVALID_DATA, "shard_%llu.bin holds dimension %u", (unsigned long long)s, f.dim());
-    std::vector<const uint64_t *> keep_of(rc == VI_OK ? f.num_lists() : 0, nullptr);
-    for (size_t li = 0; rc == VI_OK && li < kv.second.size(); ++li) {
-      const uint32_t l = kv.second[li];
-      const ShardListView *lv = f.find(l);
-      if (!lv || lv->num_vectors != h_len[l]) {  // (the resident blocks are what the records are taken to be)
-        rc = fail(VI_ERR_INVALID_DATA, "shard_%llu.bin no longer matches the resident list %u", (unsigned long long)s, l);
-        break;
-      }
+    VI_TRY(files.open(s, dim, &f));
+    std::vector<const uint64_t *> keep_of(f.num_lists(), nullptr);
+    for (const uint32_t l : kv.second) {
+      const ShardListView *lv;
+      VI_TRY(files.find(f, s, l, h_len[l], &lv));
       keep_of[lv - &f.list(0)] = h_allow.data() + h_first[l];
     }
-    const std::string path = shard_file_path(ix->shards_dir, s), tmp = path + ".tmp";
     uint64_t bytes = 0;
-    if (rc == VI_OK) rc = shard_retain_write(f, s, keep_of, tmp, &bytes, nullptr);
-    if (rc != VI_OK) { drop_temporaries(); return rc; }
-    renames.emplace_back(tmp, path);
-    rs.bytes_written += bytes;
-    ++rs.shards_rewritten;
+    VI_TRY(shard_retain_write(f, s, keep_of, files.temporary(s), &bytes, nullptr));
+    files.add(s, bytes);
   }
   const double t2 = now_ms();
 
   // ---- the new resident index, beside the old one ----
   auto dev = std::make_unique<DeviceIndex>();
-  const vi_status rc = device_index_compact(old, keep, dev.get(), &rs.ms_kernel, &rs.kernel_bytes);
-  if (rc != VI_OK) { drop_temporaries(); return rc; }
+  VI_TRY(device_index_compact(old, keep, dev.get(), &rs.ms_kernel, &rs.kernel_bytes));
   const double t3 = now_ms();
   rs.ms_index = (float)(t3 - t2);
 
   // ---- renames, then the swap ----
-  for (size_t i = 0; i < renames.size(); ++i)
-    if (::rename(renames[i].first.c_str(), renames[i].second.c_str()) != 0) {
-      const int e = errno;
-      for (size_t j = i; j < renames.size(); ++j) ::unlink(renames[j].first.c_str());
-      return fail(VI_ERR_IO, "rename(%s): %s%s", renames[i].first.c_str(), strerror(e),
-                  i ? " (earlier shard files of this call are already in place: reload the index)" : "");
-    }
+  VI_TRY(files.commit());
   ix->dev = std::move(dev);
   const double t4 = now_ms();
+  rs.bytes_written = files.bytes();
+  rs.shards_rewritten = files.files();
   rs.ms_files = (float)((t2 - t1) + (t4 - t3));
   rs.ms_total = (float)(t4 - t0);
   ix->remove_stats = rs;

@@ -1,8 +1,8 @@
 // device_index.hip — where a resident index (DeviceIndex, device_index.hpp) is constructed.
 //
 // Five routes build one (device_index.hpp names them and their callers): device_index_load and device_index_from_rows
-// here, device_index_from_order in list_build.hip, device_index_append in list_append.hip, device_index_compact in
-// list_compact.hip.  The steps they share:
+// here, device_index_from_order in list_build.hip, device_index_append and device_index_compact in list_update.hip.  The
+// steps they share:
 //   layout        plan_list_layout (list_layout.hpp): first block and local length of every list, the two 32-bit limits
 //   storage       alloc_list_storage: blocks, ids, timestamps and the per-list arrays, sized and uploaded from the layout
 //   coarse table  coarse_table_from_rows / repack_table: rows 0..n-1 into lane-interleaved blocks

@@ -175,8 +175,8 @@ struct DeviceIndex {
 //   device_index_from_rows   (device_index.hip)  rows of a device matrix, grouped on the host: the two-level hierarchy of
 //                                                the k-means assignment (kmeans.hip)
 //   device_index_from_order  (list_build.hip)    rows of a device matrix, grouped on the device: a single-GPU build (api.cpp)
-//   device_index_append      (list_append.hip)   the blocks of an older index and new rows: vi_indexer_add_records (api.cpp)
-//   device_index_compact     (list_compact.hip)  the blocks of an older index less the records a filter excludes:
+//   device_index_append      (list_update.hip)   the blocks of an older index and new rows: vi_indexer_add_records (api.cpp)
+//   device_index_compact     (list_update.hip)   the blocks of an older index less the records a filter excludes:
 //                                                vi_indexer_retain / vi_indexer_remove_ids (api.cpp)
 //
 // Upload: centroid table + this rank's part of the lists, repacked on the GPU.  placement 0: a stripe of every list
@@ -200,14 +200,15 @@ vi_status device_index_from_order(int device, uint32_t dim, const float *table_h
                                   const uint32_t *order_dev, const std::vector<uint64_t> &src_off,
                                   const std::vector<uint32_t> &len, const std::vector<uint32_t> &list_shard,
                                   const uint64_t *ids_dev, const uint64_t *ts_dev, uint64_t now, DeviceIndex *out);
-// `out` = a fresh index holding the lists of `old` (unpartitioned; only read) with list l followed by rows
-// order_dev[seg[l] .. seg[l + 1]) of rows_dev (seg on the device and the host: group_ids_by_label_device); row_ext_dev /
-// row_ts_dev: external id and stored timestamp of every row.  Old blocks are copied device to device, nothing comes from
-// the shard files; old and new index coexist until the caller drops the old one.  ms_kernel / kernel_bytes (optional):
-// HIP-event time of append_blocks_kernel and the bytes it moves.
-vi_status device_index_append(const DeviceIndex &old, const float *rows_dev, uint64_t n, const uint32_t *order_dev,
-                              const uint32_t *seg_dev, const std::vector<uint64_t> &seg_host, const uint64_t *row_ext_dev,
-                              const uint64_t *row_ts_dev, DeviceIndex *out, float *ms_kernel, uint64_t *kernel_bytes);
+// `out` = a fresh index holding the lists of `old` (unpartitioned; only read; old_len_host = a host copy of its list_len)
+// with list l followed by rows order_dev[seg[l] .. seg[l + 1]) of rows_dev (seg on the device and the host:
+// group_ids_by_label_device); row_ext_dev / row_ts_dev: external id and stored timestamp of every row.  Old blocks are
+// copied device to device, nothing comes from the shard files; old and new index coexist until the caller drops the old
+// one.  ms_kernel / kernel_bytes (optional): HIP-event time of append_blocks_kernel and the bytes it moves.
+vi_status device_index_append(const DeviceIndex &old, const std::vector<uint32_t> &old_len_host, const float *rows_dev, uint64_t n,
+                              const uint32_t *order_dev, const uint32_t *seg_dev, const std::vector<uint64_t> &seg_host,
+                              const uint64_t *row_ext_dev, const uint64_t *row_ts_dev, DeviceIndex *out, float *ms_kernel,
+                              uint64_t *kernel_bytes);
 // `out` = a fresh index holding the records of `old` (unpartitioned; only read) whose allow bit in `keep` (a filter of
 // `old`) is 1: the kept records of every list close up in their old order, a list that keeps none stays as an empty list.
 // Blocks are gathered device to device, nothing comes from the shard files; old and new index coexist until the caller
@@ -311,7 +312,7 @@ vi_status shard_export_device(const std::string &shards_dir, uint64_t shard_id, 
                               const float *X_dev, const uint32_t *order_dev, const uint64_t *ext_dev, const uint64_t *ts_dev,
                               uint64_t now, ShardExportWs &ws, hipStream_t st);
 
-// ---- appending records to a resident index (list_append.hip; device_index_append is declared with the routes above) ----
+// ---- appending records to a resident index (list_update.hip; device_index_append is declared with the routes above) ----
 // labels_dev[i] (device, n u32) = the list the reference's coarse step probes first for row i of rows_dev (device, n x dim):
 // the index's own coarse step with n_probe = 1, in chunks
 vi_status device_index_label_rows(const DeviceIndex &ix, const float *rows_dev, uint64_t n, uint32_t *labels_dev);

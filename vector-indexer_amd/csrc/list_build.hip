@@ -316,29 +316,20 @@ vi_status device_index_from_order(int device, uint32_t dim, const float *table_h
   return prepare_rank_images(ix);
 }
 
-// One shard file from device-resident points (byte-identical to shard_save_to, shards.cpp): lists = the shard's lists in
-// file order, each (centroid id, centroid vector (host), offset into order_dev, length).
+// One shard file from device-resident points, the frame by the routines shard_save_to uses (shards.cpp: byte-identical):
+// lists = the shard's lists in file order, each (centroid id, centroid vector (host), offset into order_dev, length).
 vi_status shard_export_device(const std::string &shards_dir, uint64_t shard_id, uint32_t dim, const std::vector<uint64_t> &cids,
                               const float *cvecs_host, const std::vector<uint64_t> &src_off, const std::vector<uint32_t> &len,
                               const float *X_dev, const uint32_t *order_dev, const uint64_t *ext_dev, const uint64_t *ts_dev,
                               uint64_t now, ShardExportWs &ws, hipStream_t st) {
   VI_TRY(make_dirs(shards_dir));
-  const std::string path = shards_dir + "/shard_" + std::to_string(shard_id) + ".bin";
+  const std::string path = shard_file_path(shards_dir, shard_id);
   ::remove(path.c_str());  // shards.rs:73
   const uint32_t nl = (uint32_t)cids.size();
-  const uint64_t vsz = 4ull * dim, pad = pad8(vsz), stride = record_stride(dim);
-  const uint64_t data_off = kShardHeaderBytes + kIndexEntryBytes * (uint64_t)nl;
-  std::vector<uint64_t> rec_dst(nl), blk_off(nl);
-  std::vector<uint32_t> rec_first(nl);
-  uint64_t cur = data_off, nrec = 0;
-  for (uint32_t i = 0; i < nl; ++i) {
-    blk_off[i] = cur;
-    rec_dst[i] = cur + vsz + pad;
-    rec_first[i] = (uint32_t)nrec;
-    cur += vsz + pad + (uint64_t)len[i] * stride;
-    nrec += len[i];
-  }
-  const uint64_t total = cur;
+  const ShardPlan pl(dim, std::vector<uint64_t>(len.begin(), len.end()));
+  const uint64_t data_off = pl.data_off, total = pl.total;
+  uint64_t nrec = 0;
+  for (uint32_t i = 0; i < nl; ++i) nrec += len[i];
   if (nrec >= 0xFFFFFFFFull) return fail(VI_ERR_OTHER, "shard with more than 2^32 records");
   // staging image on the device (records only; header, index and centroid vectors are patched in on the host)
   VI_TRY(ws.image.reserve(total + 16));
@@ -352,37 +343,26 @@ vi_status shard_export_device(const std::string &shards_dir, uint64_t shard_id, 
   // only lists with records take part in the kernel's search table
   std::vector<uint64_t> k_src, k_dst;
   std::vector<uint32_t> k_len, k_first;
-  for (uint32_t i = 0; i < nl; ++i)
-    if (len[i]) { k_src.push_back(src_off[i]); k_dst.push_back(rec_dst[i]); k_len.push_back(len[i]); k_first.push_back(rec_first[i]); }
+  for (uint32_t i = 0, first = 0; i < nl; ++i) {
+    if (len[i]) { k_src.push_back(src_off[i]); k_dst.push_back(pl.records(i)); k_len.push_back(len[i]); k_first.push_back(first); }
+    first += len[i];
+  }
   if (nrec) {
     VI_TRY(upload(ws.d_src, k_src.data(), k_src.size(), st));
     VI_TRY(upload(ws.d_dst, k_dst.data(), k_dst.size(), st));
     VI_TRY(upload(ws.d_len, k_len.data(), k_len.size(), st));
     VI_TRY(upload(ws.d_first, k_first.data(), k_first.size(), st));
     ExportArgs a{X_dev, order_dev, ext_dev, ts_dev, now, ws.d_src.p, ws.d_dst.p, ws.d_len.p, ws.d_first.p,
-                 (uint32_t)k_src.size(), dim, (uint32_t)stride, nrec, ws.image.p};
+                 (uint32_t)k_src.size(), dim, (uint32_t)pl.stride, nrec, ws.image.p};
     hipLaunchKernelGGL(export_records_kernel, dim3((uint32_t)((nrec + 3) / 4)), dim3(256), 0, st, a);
     VI_HIP(hipGetLastError());
     VI_HIP(hipMemcpyAsync(ws.host + data_off, ws.image.p + data_off, total - data_off, hipMemcpyDeviceToHost, st));
     VI_HIP(hipStreamSynchronize(st));  // (k_* are read by the copies above)
   }
-  uint8_t *p = ws.host;
-  auto put64 = [&](uint64_t off, uint64_t v) { std::memcpy(p + off, &v, 8); };
-  auto put32 = [&](uint64_t off, uint32_t v) { std::memcpy(p + off, &v, 4); };
-  put64(0, shard_id); put64(8, 1); put32(16, dim); put32(20, nl);
-  put64(24, kShardHeaderBytes); put64(32, data_off);
-  for (uint32_t i = 0; i < nl; ++i) {
-    const uint64_t e = kShardHeaderBytes + (uint64_t)i * kIndexEntryBytes;
-    put64(e, cids[i]); put32(e + 8, len[i]); put32(e + 12, 0);
-    put64(e + 16, blk_off[i]); put64(e + 24, vsz + pad + (uint64_t)len[i] * stride);
-    std::memcpy(p + blk_off[i], cvecs_host + (uint64_t)i * dim, vsz);
-    if (pad) std::memset(p + blk_off[i] + vsz, 0, pad);
-  }
-  FILE *f = fopen(path.c_str(), "wb");
-  if (!f) return fail(VI_ERR_IO, "File::create(%s): %s", path.c_str(), strerror(errno));
-  const bool ok = total == 0 || fwrite(p, 1, total, f) == total;
-  if (fclose(f) != 0 || !ok) return fail(VI_ERR_IO, "write(%s) failed", path.c_str());
-  return VI_OK;
+  std::vector<const void *> cvecs(nl);
+  for (uint32_t i = 0; i < nl; ++i) cvecs[i] = cvecs_host + (uint64_t)i * dim;
+  shard_frame_write(ws.host, pl, shard_id, cids.data(), cvecs.data());
+  return shard_image_write(path, ws.host, total, false);
 }
 
 ShardExportWs::~ShardExportWs() {

@@ -1,0 +1,350 @@
+// list_update.hip — the resident half of vi_indexer_add_records and of vi_indexer_retain / vi_indexer_remove_ids: a new
+// DeviceIndex from the blocks of the old one, without re-reading a shard file.  Both routes run
+//
+//   begin_update: the refusals, a fresh index on the old one's device
+//     -> the new length of every list (append: old length + rows received; compact: kept_count_kernel)
+//     -> on the host: the new layout from the new lengths, and the list of every new block (lay_out_from_old)
+//     -> one wave per NEW block, lane = vector (append_blocks_kernel / compact_blocks_kernel).  A block whose 64 positions
+//        are the records of one old block is a straight copy of it (copy_old_block).  Pad lanes get what every index
+//        upload leaves there: zero vectors, external id ~0, timestamp 0.  Every word of the new blocks / ext_ids /
+//        timestamps is written exactly once.
+//     -> finish_update: the launch between two events, then prepare_rank_images: norms, images and the rank mode's
+//        statistics, by the code a load runs.
+//
+// Append.  The new rows (device, row-major, uploaded once) get their label from the coarse step of the old index with
+// n_probe = 1 (device_index_label_rows: device_index_search with probes_out, in chunks) — the first probe of the
+// reference's coarse step (ivf_index.rs:205-220), whatever engine ranks it — and are grouped by label, ascending call
+// index inside a label (group_ids_by_label_device).  Positions inside a list are kept: the one block of a list where old
+// records end takes its old lanes from the old block and the others from the row-major upload (as repack_rows_kernel
+// reads it); blocks behind it are new rows only.
+//
+// Compact.  keep.allow holds one bit per old slot, pad slots 0.  kept_count_kernel, one wave per list: lanes stride over
+// the list's old blocks; the popcount of each block's allow word, scanned across the wave with a carry from stride to
+// stride, is the number of kept records of the list in front of the block (block_prefix) and, at the end, the list's new
+// length.  compact_blocks_kernel is a gather: new position p = 64 j + lane looks its source up, the old block by binary
+// search over the list's block_prefix, the lane inside it as the (p - prefix)-th set bit of the block's allow word.
+// Sources inside a wave ascend and are mostly adjacent; the writes are whole rows.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <vector>
+
+#include "device_index.hpp"
+#include "search_internal.hpp"
+#include "slot_filter.hpp"
+
+namespace vi {
+namespace {
+
+constexpr int kWave = 64;
+constexpr int kUpdateWaves = 4;            // waves per workgroup: new blocks of the two block kernels, lists of kept_count_kernel
+constexpr uint64_t kLabelChunk = 65536;    // rows per coarse step
+
+// The two block kernels' arguments name what they share alike (the old index, the new layout, the new storage: filled in
+// by finish_update); each struct keeps the field order its kernel was compiled and profiled with.
+//
+// A new block that is one old block, vectors, ids and timestamps: four 1 KiB rows in flight.  src / dst: the lane's column
+// of the old / new block, old_slot / slot: its slot there.
+template <typename Args>
+__device__ __forceinline__ void copy_old_block(const Args &a, const float4 *src, float4 *dst, uint64_t old_slot, uint64_t slot) {
+  for (uint32_t qd = 0; qd < a.dq; qd += 4) {  // (dq is a multiple of 4: layout_dq)
+    const float4 t0 = src[(size_t)(qd + 0) * kWave], t1 = src[(size_t)(qd + 1) * kWave];
+    const float4 t2 = src[(size_t)(qd + 2) * kWave], t3 = src[(size_t)(qd + 3) * kWave];
+    dst[(size_t)(qd + 0) * kWave] = t0;
+    dst[(size_t)(qd + 1) * kWave] = t1;
+    dst[(size_t)(qd + 2) * kWave] = t2;
+    dst[(size_t)(qd + 3) * kWave] = t3;
+  }
+  a.ext[slot] = a.old_ext[old_slot];
+  a.ts[slot] = a.old_ts[old_slot];
+}
+
+struct AppendArgs {
+  // the old index
+  const float4 *old_blocks;
+  const uint64_t *old_ext, *old_ts;
+  const uint32_t *old_first, *old_len;     // per list
+  // the new layout
+  const uint32_t *new_first, *new_len;     // per list
+  const uint32_t *block_list;              // per new block: its list
+  uint64_t nblocks;                        // new blocks
+  // the new rows, grouped by list: list l receives rows order[seg[l] .. seg[l + 1]) in that order
+  const float *rows;                       // n x dim
+  const uint64_t *row_ext, *row_ts;        // per row, resolved on the host (never null)
+  const uint32_t *order, *seg;
+  uint32_t dim, dq;
+  float4 *blocks;
+  uint64_t *ext, *ts;
+};
+
+__global__ void __launch_bounds__(kUpdateWaves * kWave) append_blocks_kernel(AppendArgs a) {
+  const int lane = threadIdx.x & (kWave - 1);
+  const uint64_t b = (uint64_t)blockIdx.x * kUpdateWaves + (threadIdx.x >> 6);
+  if (b >= a.nblocks) return;
+  const uint32_t l = a.block_list[b];
+  const uint32_t j = (uint32_t)(b - a.new_first[l]);           // block of the list
+  const uint32_t old_len = a.old_len[l], new_len = a.new_len[l];
+  const uint32_t pos = j * kWave + lane;                       // position inside the list (new_len < 2^32 - 64)
+  const uint32_t dq = a.dq;
+  float4 *dst = a.blocks + (b * dq) * kWave + lane;
+  const uint64_t slot = b * kWave + lane;
+  const float4 *src = a.old_blocks + ((uint64_t)(a.old_first[l] + j) * dq) * kWave + lane;  // (read only where pos < old_len)
+  const uint64_t old_slot = (uint64_t)(a.old_first[l] + j) * kWave + lane;
+  if (j * kWave + (kWave - 1) < old_len) {  // all 64 positions old (wave-uniform)
+    copy_old_block(a, src, dst, old_slot, slot);
+    return;
+  }
+  const bool is_old = pos < old_len, is_new = !is_old && pos < new_len;
+  uint32_t row = 0;
+  if (is_new) row = a.order[a.seg[l] + (pos - old_len)];
+  const float *v = a.rows + (size_t)row * a.dim;
+  for (uint32_t qd = 0; qd < dq; ++qd) {
+    float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
+    const uint32_t e = qd * 4;
+    if (is_old) {
+      x = src[(size_t)qd * kWave];
+    } else if (is_new) {
+      if (e + 0 < a.dim) x.x = v[e + 0];
+      if (e + 1 < a.dim) x.y = v[e + 1];
+      if (e + 2 < a.dim) x.z = v[e + 2];
+      if (e + 3 < a.dim) x.w = v[e + 3];
+    }
+    dst[(size_t)qd * kWave] = x;
+  }
+  a.ext[slot] = is_old ? a.old_ext[old_slot] : is_new ? a.row_ext[row] : ~0ull;
+  a.ts[slot] = is_old ? a.old_ts[old_slot] : is_new ? a.row_ts[row] : 0ull;
+}
+
+struct CountArgs {
+  const uint64_t *allow;                   // per old block
+  const uint32_t *old_first, *old_len;     // per list
+  uint32_t nlists;
+  uint32_t *block_prefix;                  // per old block: kept records of its list in front of it
+  uint32_t *new_len;                       // per list
+};
+
+__global__ void __launch_bounds__(kUpdateWaves * kWave) kept_count_kernel(CountArgs a) {
+  const uint32_t lane = threadIdx.x & (kWave - 1);
+  const uint32_t l = blockIdx.x * kUpdateWaves + (threadIdx.x >> 6);
+  if (l >= a.nlists) return;
+  const uint32_t first = a.old_first[l], nblk = (a.old_len[l] + kWave - 1) / kWave;
+  uint32_t carry = 0;
+  for (uint32_t base = 0; base < nblk; base += kWave) {  // (wave-uniform)
+    const uint32_t b = base + lane;
+    const uint32_t c = b < nblk ? (uint32_t)__popcll(a.allow[first + b]) : 0u;
+    uint32_t incl = c;
+#pragma unroll
+    for (int d = 1; d < kWave; d <<= 1) {
+      const uint32_t up = __shfl_up(incl, d, kWave);
+      if ((int)lane >= d) incl += up;
+    }
+    if (b < nblk) a.block_prefix[first + b] = carry + incl - c;
+    carry += __shfl(incl, kWave - 1, kWave);
+  }
+  if (lane == 0) a.new_len[l] = carry;
+}
+
+struct CompactArgs {
+  // the old index and what is kept of it
+  const float4 *old_blocks;
+  const uint64_t *old_ext, *old_ts;
+  const uint32_t *old_first, *old_len;     // per list
+  const uint64_t *allow;                   // per old block
+  const uint32_t *block_prefix;            // per old block (kept_count_kernel)
+  // the new layout
+  const uint32_t *new_first, *new_len;     // per list
+  const uint32_t *block_list;              // per new block: its list
+  uint64_t nblocks;                        // new blocks
+  uint32_t dq;
+  float4 *blocks;
+  uint64_t *ext, *ts;
+};
+
+// the r-th (from 0) set bit of w, which has more than r set bits: halve the word, step into the half that holds it
+__device__ __forceinline__ uint32_t nth_set_bit(uint64_t w, uint32_t r) {
+  uint32_t pos = 0;
+#pragma unroll
+  for (uint32_t width = 32; width; width >>= 1) {
+    const uint32_t c = (uint32_t)__popcll(w & ((1ull << width) - 1ull));
+    if (r >= c) { r -= c; w >>= width; pos += width; }
+  }
+  return pos;
+}
+
+__global__ void __launch_bounds__(kUpdateWaves * kWave) compact_blocks_kernel(CompactArgs a) {
+  const uint32_t lane = threadIdx.x & (kWave - 1);
+  const uint64_t b = (uint64_t)blockIdx.x * kUpdateWaves + (threadIdx.x >> 6);
+  if (b >= a.nblocks) return;
+  const uint32_t l = a.block_list[b];
+  const uint32_t j = (uint32_t)(b - a.new_first[l]);           // block of the list
+  const uint32_t old_len = a.old_len[l], new_len = a.new_len[l], old_first = a.old_first[l];
+  const uint32_t dq = a.dq;
+  float4 *dst = a.blocks + (b * dq) * kWave + lane;
+  const uint64_t slot = b * kWave + lane;
+  const bool untouched = new_len == old_len;                   // (wave-uniform) positions are the old ones
+  if (untouched && j * kWave + (kWave - 1) < new_len) {        // ... and all 64 are records
+    copy_old_block(a, a.old_blocks + ((uint64_t)(old_first + j) * dq) * kWave + lane, dst, (uint64_t)(old_first + j) * kWave + lane, slot);
+    return;
+  }
+  const uint32_t p = j * kWave + lane;                         // position inside the new list (new_len < 2^32 - 64)
+  const bool valid = p < new_len;
+  uint32_t sb = j, sl = lane;                                  // source block of the old list, lane inside it
+  if (!untouched) {
+    const uint32_t old_nblk = (old_len + kWave - 1) / kWave;   // >= 1: the list has a new block, so it had records
+    const uint32_t ps = valid ? p : 0u;                        // (pad lanes search too, and read nothing afterwards)
+    // the last old block whose prefix is <= ps: it holds kept record ps (blocks with nothing kept share the prefix of
+    // the block behind them, so they are never the last).  The trip count depends on old_nblk alone: wave-uniform.
+    uint32_t lo = 0, hi = old_nblk;
+    while (hi - lo > 1) {
+      const uint32_t mid = lo + (hi - lo) / 2;
+      if (a.block_prefix[old_first + mid] <= ps) lo = mid; else hi = mid;
+    }
+    sb = lo;
+    sl = valid ? nth_set_bit(a.allow[old_first + sb], ps - a.block_prefix[old_first + sb]) : 0u;
+  }
+  const float4 *src = a.old_blocks + ((uint64_t)(old_first + sb) * dq) * kWave + sl;  // (read only where valid)
+  const uint64_t old_slot = (uint64_t)(old_first + sb) * kWave + sl;
+  for (uint32_t qd = 0; qd < dq; qd += 4) {  // four rows in flight here too
+    float4 t0 = make_float4(0.f, 0.f, 0.f, 0.f), t1 = t0, t2 = t0, t3 = t0;
+    if (valid) {
+      t0 = src[(size_t)(qd + 0) * kWave];
+      t1 = src[(size_t)(qd + 1) * kWave];
+      t2 = src[(size_t)(qd + 2) * kWave];
+      t3 = src[(size_t)(qd + 3) * kWave];
+    }
+    dst[(size_t)(qd + 0) * kWave] = t0;
+    dst[(size_t)(qd + 1) * kWave] = t1;
+    dst[(size_t)(qd + 2) * kWave] = t2;
+    dst[(size_t)(qd + 3) * kWave] = t3;
+  }
+  a.ext[slot] = valid ? a.old_ext[old_slot] : ~0ull;
+  a.ts[slot] = valid ? a.old_ts[old_slot] : 0ull;
+}
+
+struct EventPair {
+  hipEvent_t a = nullptr, b = nullptr;
+  ~EventPair() {
+    if (a) (void)hipEventDestroy(a);
+    if (b) (void)hipEventDestroy(b);
+  }
+};
+
+// What both routes begin with: the refusals (`refusal`: the route's own words for a partitioned index), a fresh index on
+// old's device with old's summation order and timing, the two out-values at zero.
+vi_status begin_update(const DeviceIndex &old, const char *refusal, DeviceIndex *ix, float *ms_kernel, uint64_t *kernel_bytes) {
+  if (old.stripe_world > 1) return fail(VI_ERR_INVALID_INPUT, "%s", refusal);
+  if (!old.timestamps.p || !old.ext_ids.p) return fail(VI_ERR_INVALID_INPUT, "the index keeps no ids or timestamps");
+  VI_TRY(init_device_index(ix, old.device, old.dim, old.nlists));
+  ix->order = old.order;
+  ix->timing = old.timing;
+  if (ms_kernel) *ms_kernel = 0.0f;
+  if (kernel_bytes) *kernel_bytes = 0;
+  return VI_OK;
+}
+
+// ... and end with, once lay_out_from_old has run: the fields both kernels share filled in, the block kernel timed between
+// two events (one wave per new block), prepare_rank_images.
+template <typename Args>
+vi_status finish_update(const DeviceIndex &old, DeviceIndex *ix, const DevBuf<uint32_t> &block_list, void (*kernel)(Args), Args a,
+                        float *ms_kernel, uint64_t *kernel_bytes) {
+  hipStream_t st = ix->stream;
+  const uint64_t total_blocks = ix->lists.nblocks;
+  if (total_blocks) {
+    a.old_blocks = (const float4 *)old.lists.blocks.p;
+    a.old_ext = old.ext_ids.p; a.old_ts = old.timestamps.p;
+    a.old_first = old.list_first_block.p; a.old_len = old.list_len.p;
+    a.new_first = ix->list_first_block.p; a.new_len = ix->list_len.p;
+    a.block_list = block_list.p; a.nblocks = total_blocks;
+    a.dq = ix->dq;
+    a.blocks = (float4 *)ix->lists.blocks.p; a.ext = ix->ext_ids.p; a.ts = ix->timestamps.p;
+    EventPair ev;
+    VI_HIP(hipEventCreate(&ev.a));
+    VI_HIP(hipEventCreate(&ev.b));
+    VI_HIP(hipEventRecord(ev.a, st));
+    hipLaunchKernelGGL(kernel, dim3((uint32_t)((total_blocks + kUpdateWaves - 1) / kUpdateWaves)), dim3(kUpdateWaves * kWave), 0, st, a);
+    VI_HIP(hipGetLastError());
+    VI_HIP(hipEventRecord(ev.b, st));
+    VI_HIP(hipStreamSynchronize(st));  // (the block list and the caller's scratch are freed on return)
+    if (ms_kernel) (void)hipEventElapsedTime(ms_kernel, ev.a, ev.b);
+    // read + written: every new block once each way (blocks, ids, timestamps), less what pad and new lanes do not read
+    if (kernel_bytes) *kernel_bytes = 2 * total_blocks * ((uint64_t)ix->dq * kWave * 16 + kWave * 16);
+  }
+  return prepare_rank_images(ix);
+}
+
+}  // namespace
+
+// labels_dev[i] = the list the reference's coarse step probes first for row i: the old index's own coarse step, n_probe 1
+vi_status device_index_label_rows(const DeviceIndex &ix, const float *rows_dev, uint64_t n, uint32_t *labels_dev) {
+  if (n == 0) return VI_OK;
+  if (ix.nlists == 0) return fail(VI_ERR_INVALID_INPUT, "the index has no list to add to");
+  VI_HIP(hipSetDevice(ix.device));
+  DevBuf<uint32_t> order_scratch;  // (the coarse step writes the candidate-order ranks too: all zero at one probe)
+  VI_TRY(order_scratch.reserve(std::min(n, kLabelChunk)));
+  for (uint64_t at = 0; at < n; at += kLabelChunk) {
+    SearchIO io;
+    io.queries = rows_dev + at * ix.dim;
+    io.on_device = true;
+    io.nq = std::min(kLabelChunk, n - at);
+    io.k = 1;
+    io.n_probe = 1;
+    io.probes_out = labels_dev + at;
+    io.order_out = order_scratch.p;
+    VI_TRY(device_index_search(ix, io));
+  }
+  return VI_OK;
+}
+
+// The index `old` with rows appended: list l receives rows order_dev[seg_host[l] .. seg_host[l + 1]) of rows_dev behind its
+// old_len_host[l] old records.  Complete on return; `old` is only read.
+vi_status device_index_append(const DeviceIndex &old, const std::vector<uint32_t> &old_len_host, const float *rows_dev, uint64_t n,
+                              const uint32_t *order_dev, const uint32_t *seg_dev, const std::vector<uint64_t> &seg_host,
+                              const uint64_t *row_ext_dev, const uint64_t *row_ts_dev, DeviceIndex *ix, float *ms_kernel,
+                              uint64_t *kernel_bytes) {
+  const uint64_t nlists = old.nlists;
+  VI_TRY(begin_update(old, "a partitioned index takes no records", ix, ms_kernel, kernel_bytes));
+  if (seg_host.size() != nlists + 1 || seg_host[nlists] != n || old_len_host.size() != nlists)
+    return fail(VI_ERR_OTHER, "append: grouping does not match the index");
+  // the new layout from the old lengths: lists back to back in list order, each padded to whole blocks (as a load lays them)
+  std::vector<uint64_t> full_len(nlists);
+  for (uint64_t l = 0; l < nlists; ++l) full_len[l] = (uint64_t)old_len_host[l] + (seg_host[l + 1] - seg_host[l]);
+  DevBuf<uint32_t> d_block_list;
+  VI_TRY(lay_out_from_old(ix, old, full_len.data(), &d_block_list));  // (the new first / len are in place for the kernel)
+  AppendArgs a{};
+  a.rows = rows_dev; a.row_ext = row_ext_dev; a.row_ts = row_ts_dev;
+  a.order = order_dev; a.seg = seg_dev;
+  a.dim = ix->dim;
+  return finish_update(old, ix, d_block_list, append_blocks_kernel, a, ms_kernel, kernel_bytes);
+}
+
+// The index `old` without the records whose allow bit in `keep` is 0; the others close up in their old order.  Complete
+// on return; `old` and `keep` are only read.
+vi_status device_index_compact(const DeviceIndex &old, const SlotFilter &keep, DeviceIndex *ix, float *ms_kernel,
+                               uint64_t *kernel_bytes) {
+  const uint64_t nlists = old.nlists;
+  VI_TRY(begin_update(old, "a partitioned index gives no records up", ix, ms_kernel, kernel_bytes));
+  if (keep.owner_serial != old.serial) return fail(VI_ERR_INVALID_INPUT, "the filter was made from another index");
+  hipStream_t st = ix->stream;
+  // ---- count pass: the new length of every list, the kept records in front of every old block ----
+  DevBuf<uint32_t> block_prefix, d_new_len;
+  VI_TRY(block_prefix.reserve(std::max<uint64_t>(1, old.lists.nblocks)));
+  VI_TRY(d_new_len.reserve(std::max<uint64_t>(1, nlists)));
+  std::vector<uint32_t> n_len(nlists);
+  if (nlists) {
+    CountArgs c{keep.allow.p, old.list_first_block.p, old.list_len.p, (uint32_t)nlists, block_prefix.p, d_new_len.p};
+    hipLaunchKernelGGL(kept_count_kernel, dim3((uint32_t)((nlists + kUpdateWaves - 1) / kUpdateWaves)),
+                       dim3(kUpdateWaves * kWave), 0, st, c);
+    VI_HIP(hipGetLastError());
+    VI_HIP(hipMemcpyAsync(n_len.data(), d_new_len.p, nlists * 4, hipMemcpyDeviceToHost, st));
+    VI_HIP(hipStreamSynchronize(st));
+  }
+  const std::vector<uint64_t> full_len(n_len.begin(), n_len.end());
+  DevBuf<uint32_t> d_block_list;
+  VI_TRY(lay_out_from_old(ix, old, full_len.data(), &d_block_list));
+  if (ix->nvec_resident != keep.num_allowed) return fail(VI_ERR_OTHER, "compact: the filter's count does not match its allow words");
+  CompactArgs a{};
+  a.allow = keep.allow.p; a.block_prefix = block_prefix.p;
+  return finish_update(old, ix, d_block_list, compact_blocks_kernel, a, ms_kernel, kernel_bytes);
+}
+
+}  // namespace vi

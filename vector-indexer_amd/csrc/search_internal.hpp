@@ -1,6 +1,6 @@
 // search_internal.hpp — what the search engines' and the index builders' translation units (search_kernels.hip,
 // generic_search.hip, filter_search.hip, grouping.hip, select.hip, range_select.hip, rank_images.hip, device_index.hip,
-// list_build.hip, list_append.hip, list_compact.hip, kmeans.hip) call in each other and share: declared once, here.  (The probe grouping is called through a header of its own, grouping.hpp; filter_search.hip launches
+// list_build.hip, list_update.hip, kmeans.hip) call in each other and share: declared once, here.  (The probe grouping is called through a header of its own, grouping.hpp; filter_search.hip launches
 // its rank and select phases through rank_stream.hpp and select.hpp.)
 #pragma once
 #include <algorithm>

@@ -22,10 +22,16 @@ T load_le(const uint8_t *p) {
   std::memcpy(&v, p, sizeof(T));
   return v;
 }
-std::string shard_path(const std::string &dir, uint64_t id) {
-  return dir + "/shard_" + std::to_string(id) + ".bin";
+void put_record(uint8_t *o, uint64_t id, uint64_t ext_id, uint64_t timestamp, const float *vec, uint64_t vsz) {
+  const uint64_t meta[3] = {id, ext_id, timestamp};  // VectorMeta (shards.rs:45-51)
+  std::memcpy(o, meta, kVectorMetaBytes);
+  std::memcpy(o + kVectorMetaBytes, vec, vsz);
 }
 }  // namespace
+
+std::string shard_file_path(const std::string &shards_dir, uint64_t shard_id) {
+  return shards_dir + "/shard_" + std::to_string(shard_id) + ".bin";
+}
 
 vi_status make_dirs(const std::string &path) {
   if (path.empty()) return fail(VI_ERR_IO, "empty directory path");
@@ -47,7 +53,7 @@ ShardFile::~ShardFile() {
 }
 
 vi_status ShardFile::open(const std::string &shards_dir, uint64_t shard_id) {
-  const std::string path = shard_path(shards_dir, shard_id);
+  const std::string path = shard_file_path(shards_dir, shard_id);
   int fd = ::open(path.c_str(), O_RDONLY);
   if (fd < 0)
     return fail(VI_ERR_OTHER, "Failed to open shard_%llu.bin file: %s", (unsigned long long)shard_id,
@@ -107,185 +113,167 @@ const ShardListView *ShardFile::find(uint64_t centroid_id) const {
   return nullptr;
 }
 
+// ---- the frame every writer shares ---------------------------------------------------------
+ShardPlan::ShardPlan(uint32_t dim_, std::vector<uint64_t> counts)
+    : dim(dim_), vsz(4ull * dim_), pad(pad8(vsz)), stride(record_stride(dim_)),
+      data_off(kShardHeaderBytes + kIndexEntryBytes * (uint64_t)counts.size()), total(data_off), count(std::move(counts)) {
+  for (uint64_t nv : count) {
+    off.push_back(total);
+    size.push_back(vsz + pad + nv * stride);
+    total += size.back();
+  }
+}
+
+void shard_frame_write(uint8_t *p, const ShardPlan &pl, uint64_t shard_id, const uint64_t *cids, const void *const *cvecs) {
+  auto put64 = [&](uint64_t off, uint64_t v) { std::memcpy(p + off, &v, 8); };
+  auto put32 = [&](uint64_t off, uint32_t v) { std::memcpy(p + off, &v, 4); };
+  const uint32_t nl = (uint32_t)pl.count.size();
+  put64(0, shard_id); put64(8, 1); put32(16, pl.dim); put32(20, nl);
+  put64(24, kShardHeaderBytes); put64(32, pl.data_off);
+  for (uint32_t i = 0; i < nl; ++i) {
+    const uint64_t e = kShardHeaderBytes + (uint64_t)i * kIndexEntryBytes;
+    put64(e, cids[i]); put32(e + 8, (uint32_t)pl.count[i]); put32(e + 12, 0);
+    put64(e + 16, pl.off[i]); put64(e + 24, pl.size[i]);
+    std::memcpy(p + pl.off[i], cvecs[i], pl.vsz);
+    std::memset(p + pl.off[i] + pl.vsz, 0, pl.pad);
+  }
+}
+
+vi_status shard_image_write(const std::string &path, const uint8_t *p, uint64_t total, bool unlink_on_failure) {
+  FILE *f = fopen(path.c_str(), "wb");
+  if (!f) return fail(VI_ERR_IO, "File::create(%s): %s", path.c_str(), strerror(errno));
+  const bool ok = total == 0 || fwrite(p, 1, total, f) == total;
+  if (fclose(f) != 0 || !ok) {
+    if (unlink_on_failure) ::unlink(path.c_str());
+    return fail(VI_ERR_IO, "write(%s) failed", path.c_str());
+  }
+  return VI_OK;
+}
+
+namespace {
+// the zeroed image of f's lists with other record counts, its frame written: what append and retain start from
+ShardPlan image_of_file(const ShardFile &f, uint64_t shard_id, std::vector<uint64_t> counts, std::vector<uint8_t> *img) {
+  const uint32_t nl = f.num_lists();
+  std::vector<uint64_t> cids(nl);
+  std::vector<const void *> cvecs(nl);
+  for (uint32_t i = 0; i < nl; ++i) { cids[i] = f.list(i).centroid_id; cvecs[i] = f.list(i).centroid; }
+  ShardPlan pl(f.dim(), std::move(counts));
+  img->assign(pl.total, 0);
+  shard_frame_write(img->data(), pl, shard_id, cids.data(), cvecs.data());
+  return pl;
+}
+}  // namespace
+
 vi_status shard_save_to(const std::string &shards_dir, uint64_t shard_id, uint32_t dim,
                         uint32_t num_lists, const uint64_t *centroid_ids, const float *centroid_vecs,
                         const uint64_t *list_off, const uint64_t *ids, const uint64_t *ext_ids,
                         const uint64_t *timestamps, const float *vecs) {
   VI_TRY(make_dirs(shards_dir));
-  const std::string path = shard_path(shards_dir, shard_id);
+  const std::string path = shard_file_path(shards_dir, shard_id);
   ::unlink(path.c_str());  // shards.rs:73
-  const uint64_t vsz = 4ull * dim, pad = pad8(vsz), stride = record_stride(dim);
-  const uint64_t data_off = kShardHeaderBytes + kIndexEntryBytes * (uint64_t)num_lists;
-  uint64_t total = data_off;
-  for (uint32_t i = 0; i < num_lists; ++i) total += vsz + pad + (list_off[i + 1] - list_off[i]) * stride;
-  // Assemble the whole image once and write it with a single call.
-  std::vector<uint8_t> img(total, 0);
-  uint8_t *p = img.data();
-  auto put64 = [&](uint64_t off, uint64_t v) { std::memcpy(p + off, &v, 8); };
-  auto put32 = [&](uint64_t off, uint32_t v) { std::memcpy(p + off, &v, 4); };
-  put64(0, shard_id); put64(8, 1); put32(16, dim); put32(20, num_lists);
-  put64(24, kShardHeaderBytes); put64(32, data_off);
-  uint64_t cur = data_off;
+  std::vector<uint64_t> counts(num_lists);
+  std::vector<const void *> cvecs(num_lists);
+  for (uint32_t i = 0; i < num_lists; ++i) { counts[i] = list_off[i + 1] - list_off[i]; cvecs[i] = centroid_vecs + (uint64_t)i * dim; }
+  const ShardPlan pl(dim, std::move(counts));
+  std::vector<uint8_t> img(pl.total, 0);  // the whole image assembled once, written with a single call
+  shard_frame_write(img.data(), pl, shard_id, centroid_ids, cvecs.data());
   for (uint32_t i = 0; i < num_lists; ++i) {
-    const uint64_t nv = list_off[i + 1] - list_off[i];
-    const uint64_t size = vsz + pad + nv * stride;
-    const uint64_t e = kShardHeaderBytes + (uint64_t)i * kIndexEntryBytes;
-    put64(e, centroid_ids[i]); put32(e + 8, (uint32_t)nv); put32(e + 12, 0);
-    put64(e + 16, cur); put64(e + 24, size);
-    std::memcpy(p + cur, centroid_vecs + (uint64_t)i * dim, vsz);
-    uint64_t o = cur + vsz + pad;
-    for (uint64_t v = list_off[i]; v < list_off[i + 1]; ++v) {
-      put64(o, ids[v]); put64(o + 8, ext_ids[v]); put64(o + 16, timestamps[v]);
-      std::memcpy(p + o + kVectorMetaBytes, vecs + v * dim, vsz);
-      o += stride;
-    }
-    cur += size;
+    uint8_t *o = img.data() + pl.records(i);
+    for (uint64_t v = list_off[i]; v < list_off[i + 1]; ++v, o += pl.stride)
+      put_record(o, ids[v], ext_ids[v], timestamps[v], vecs + v * dim, pl.vsz);
   }
-  FILE *f = fopen(path.c_str(), "wb");
-  if (!f) return fail(VI_ERR_IO, "File::create(%s): %s", path.c_str(), strerror(errno));
-  const bool ok = img.empty() || fwrite(img.data(), 1, img.size(), f) == img.size();
-  if (fclose(f) != 0 || !ok) return fail(VI_ERR_IO, "write(%s) failed", path.c_str());
-  return VI_OK;
+  return shard_image_write(path, img.data(), pl.total, false);
 }
-
-std::string shard_file_path(const std::string &shards_dir, uint64_t shard_id) { return shard_path(shards_dir, shard_id); }
 
 vi_status shard_append_write(const ShardFile &f, uint64_t shard_id, uint64_t n_add, const uint64_t *centroid_ids,
                              const uint64_t *ids, const uint64_t *ext_ids, const uint64_t *timestamps, const float *vecs,
                              const std::string &out_path, uint64_t *bytes_out, uint64_t *lists_out) {
   const uint32_t dim = f.dim(), nl = f.num_lists();
-  const uint64_t vsz = 4ull * dim, pad = pad8(vsz), stride = record_stride(dim);
   // the list of every added record: the first entry with its centroid id, as the reader finds it (shards.rs:257-265)
   std::unordered_map<uint64_t, uint32_t> entry_of;
   for (uint32_t i = nl; i-- > 0;) entry_of[f.list(i).centroid_id] = i;
   std::vector<uint32_t> entry(n_add);
-  std::vector<uint64_t> added(nl, 0);
+  std::vector<uint64_t> counts(nl);
+  for (uint32_t i = 0; i < nl; ++i) counts[i] = f.list(i).num_vectors;
   for (uint64_t i = 0; i < n_add; ++i) {
     const auto it = entry_of.find(centroid_ids[i]);
     if (it == entry_of.end()) return fail(VI_ERR_NOT_FOUND, "Centroid %llu not found", (unsigned long long)centroid_ids[i]);
     entry[i] = it->second;
-    ++added[it->second];
+    ++counts[it->second];
   }
-  const uint64_t data_off = kShardHeaderBytes + kIndexEntryBytes * (uint64_t)nl;
-  uint64_t total = data_off, touched = 0;
+  uint64_t touched = 0;
+  for (uint32_t i = 0; i < nl; ++i) {
+    if (counts[i] > 0xFFFFFFFFull) return fail(VI_ERR_INVALID_INPUT, "list %llu would pass 2^32 - 1 records", (unsigned long long)f.list(i).centroid_id);
+    touched += counts[i] != f.list(i).num_vectors;
+  }
+  std::vector<uint8_t> img;
+  const ShardPlan pl = image_of_file(f, shard_id, std::move(counts), &img);
   std::vector<uint64_t> next(nl);  // where the next added record of a list goes
   for (uint32_t i = 0; i < nl; ++i) {
-    const uint64_t nv = (uint64_t)f.list(i).num_vectors + added[i];
-    if (nv > 0xFFFFFFFFull) return fail(VI_ERR_INVALID_INPUT, "list %llu would pass 2^32 - 1 records", (unsigned long long)f.list(i).centroid_id);
-    next[i] = total + vsz + pad + (uint64_t)f.list(i).num_vectors * stride;
-    total += vsz + pad + nv * stride;
-    touched += added[i] != 0;
-  }
-  std::vector<uint8_t> img(total, 0);
-  uint8_t *p = img.data();
-  auto put64 = [&](uint64_t off, uint64_t v) { std::memcpy(p + off, &v, 8); };
-  auto put32 = [&](uint64_t off, uint32_t v) { std::memcpy(p + off, &v, 4); };
-  put64(0, shard_id); put64(8, 1); put32(16, dim); put32(20, nl);
-  put64(24, kShardHeaderBytes); put64(32, data_off);
-  uint64_t cur = data_off;
-  for (uint32_t i = 0; i < nl; ++i) {
-    const ShardListView &lv = f.list(i);
-    const uint64_t nv = (uint64_t)lv.num_vectors + added[i];
-    const uint64_t size = vsz + pad + nv * stride;
-    const uint64_t e = kShardHeaderBytes + (uint64_t)i * kIndexEntryBytes;
-    put64(e, lv.centroid_id); put32(e + 8, (uint32_t)nv); put32(e + 12, 0);
-    put64(e + 16, cur); put64(e + 24, size);
-    std::memcpy(p + cur, lv.centroid, vsz);
-    if (lv.num_vectors) std::memcpy(p + cur + vsz + pad, lv.records, (uint64_t)lv.num_vectors * stride);  // verbatim
-    cur += size;
+    const uint64_t old_bytes = (uint64_t)f.list(i).num_vectors * pl.stride;
+    if (old_bytes) std::memcpy(img.data() + pl.records(i), f.list(i).records, old_bytes);  // verbatim
+    next[i] = pl.records(i) + old_bytes;
   }
   for (uint64_t i = 0; i < n_add; ++i) {
-    uint64_t &o = next[entry[i]];
-    put64(o, ids[i]); put64(o + 8, ext_ids[i]); put64(o + 16, timestamps[i]);
-    std::memcpy(p + o + kVectorMetaBytes, vecs + i * dim, vsz);
-    o += stride;
+    put_record(img.data() + next[entry[i]], ids[i], ext_ids[i], timestamps[i], vecs + i * dim, pl.vsz);
+    next[entry[i]] += pl.stride;
   }
-  FILE *out = fopen(out_path.c_str(), "wb");
-  if (!out) return fail(VI_ERR_IO, "File::create(%s): %s", out_path.c_str(), strerror(errno));
-  const bool ok = img.empty() || fwrite(img.data(), 1, img.size(), out) == img.size();
-  if (fclose(out) != 0 || !ok) {
-    ::unlink(out_path.c_str());
-    return fail(VI_ERR_IO, "write(%s) failed", out_path.c_str());
-  }
-  if (bytes_out) *bytes_out = total;
+  VI_TRY(shard_image_write(out_path, img.data(), pl.total, true));
+  if (bytes_out) *bytes_out = pl.total;
   if (lists_out) *lists_out = touched;
   return VI_OK;
 }
 
 vi_status shard_append_to(const std::string &shards_dir, uint64_t shard_id, uint64_t n_add, const uint64_t *centroid_ids,
                           const uint64_t *ids, const uint64_t *ext_ids, const uint64_t *timestamps, const float *vecs) {
-  const std::string path = shard_path(shards_dir, shard_id), tmp = path + ".tmp";
+  ShardRewriteSet set(shards_dir);
   {
     ShardFile f;
     VI_TRY(f.open(shards_dir, shard_id));
     if (n_add == 0) return VI_OK;
-    VI_TRY(shard_append_write(f, shard_id, n_add, centroid_ids, ids, ext_ids, timestamps, vecs, tmp, nullptr, nullptr));
+    uint64_t bytes = 0;
+    VI_TRY(shard_append_write(f, shard_id, n_add, centroid_ids, ids, ext_ids, timestamps, vecs, set.temporary(shard_id), &bytes, nullptr));
+    set.add(shard_id, bytes);
   }  // (unmapped before the rename)
-  if (::rename(tmp.c_str(), path.c_str()) != 0) {
-    const int e = errno;
-    ::unlink(tmp.c_str());
-    return fail(VI_ERR_IO, "rename(%s): %s", tmp.c_str(), strerror(e));
-  }
-  return VI_OK;
+  return set.commit();
 }
 
 vi_status shard_retain_write(const ShardFile &f, uint64_t shard_id, const std::vector<const uint64_t *> &keep,
                              const std::string &out_path, uint64_t *bytes_out, uint64_t *removed_out) {
-  const uint32_t dim = f.dim(), nl = f.num_lists();
+  const uint32_t nl = f.num_lists();
   if (keep.size() != nl) return fail(VI_ERR_OTHER, "retain: %zu keep entries for %u lists", keep.size(), nl);
-  const uint64_t vsz = 4ull * dim, pad = pad8(vsz), stride = record_stride(dim);
   auto stays = [](const uint64_t *w, uint32_t p) { return ((w[p >> 6] >> (p & 63u)) & 1ull) != 0; };
-  std::vector<uint32_t> kept(nl);
-  const uint64_t data_off = kShardHeaderBytes + kIndexEntryBytes * (uint64_t)nl;
-  uint64_t total = data_off, removed = 0;
+  std::vector<uint64_t> kept(nl);
+  uint64_t removed = 0;
   for (uint32_t i = 0; i < nl; ++i) {
     const uint32_t nv = f.list(i).num_vectors;
-    uint32_t n = nv;
+    kept[i] = nv;
     if (keep[i]) {
-      n = 0;
-      for (uint32_t p = 0; p < nv; ++p) n += stays(keep[i], p);
+      kept[i] = 0;
+      for (uint32_t p = 0; p < nv; ++p) kept[i] += stays(keep[i], p);
     }
-    kept[i] = n;
-    removed += nv - n;
-    total += vsz + pad + (uint64_t)n * stride;
+    removed += nv - kept[i];
   }
-  std::vector<uint8_t> img(total, 0);
-  uint8_t *p = img.data();
-  auto put64 = [&](uint64_t off, uint64_t v) { std::memcpy(p + off, &v, 8); };
-  auto put32 = [&](uint64_t off, uint32_t v) { std::memcpy(p + off, &v, 4); };
-  put64(0, shard_id); put64(8, 1); put32(16, dim); put32(20, nl);
-  put64(24, kShardHeaderBytes); put64(32, data_off);
-  uint64_t cur = data_off;
+  std::vector<uint8_t> img;
+  const ShardPlan pl = image_of_file(f, shard_id, std::move(kept), &img);
   for (uint32_t i = 0; i < nl; ++i) {
     const ShardListView &lv = f.list(i);
-    const uint64_t size = vsz + pad + (uint64_t)kept[i] * stride;
-    const uint64_t e = kShardHeaderBytes + (uint64_t)i * kIndexEntryBytes;
-    put64(e, lv.centroid_id); put32(e + 8, kept[i]); put32(e + 12, 0);
-    put64(e + 16, cur); put64(e + 24, size);
-    std::memcpy(p + cur, lv.centroid, vsz);
-    uint8_t *o = p + cur + vsz + pad;
-    if (kept[i] == lv.num_vectors) {  // nothing lost: verbatim
-      if (kept[i]) std::memcpy(o, lv.records, (uint64_t)kept[i] * stride);
-    } else {
-      for (uint32_t v = 0; v < lv.num_vectors;) {  // runs of kept records
-        if (!stays(keep[i], v)) { ++v; continue; }
-        uint32_t end = v + 1;
-        while (end < lv.num_vectors && stays(keep[i], end)) ++end;
-        std::memcpy(o, lv.records + (uint64_t)v * stride, (uint64_t)(end - v) * stride);
-        o += (uint64_t)(end - v) * stride;
-        v = end;
-      }
+    uint8_t *o = img.data() + pl.records(i);
+    if (pl.count[i] == lv.num_vectors) {  // nothing lost: verbatim
+      if (lv.num_vectors) std::memcpy(o, lv.records, (uint64_t)lv.num_vectors * pl.stride);
+      continue;
     }
-    cur += size;
+    for (uint32_t v = 0; v < lv.num_vectors;) {  // runs of kept records
+      if (!stays(keep[i], v)) { ++v; continue; }
+      uint32_t end = v + 1;
+      while (end < lv.num_vectors && stays(keep[i], end)) ++end;
+      std::memcpy(o, lv.records + (uint64_t)v * pl.stride, (uint64_t)(end - v) * pl.stride);
+      o += (uint64_t)(end - v) * pl.stride;
+      v = end;
+    }
   }
-  FILE *out = fopen(out_path.c_str(), "wb");
-  if (!out) return fail(VI_ERR_IO, "File::create(%s): %s", out_path.c_str(), strerror(errno));
-  const bool ok = img.empty() || fwrite(img.data(), 1, img.size(), out) == img.size();
-  if (fclose(out) != 0 || !ok) {
-    ::unlink(out_path.c_str());
-    return fail(VI_ERR_IO, "write(%s) failed", out_path.c_str());
-  }
-  if (bytes_out) *bytes_out = total;
+  VI_TRY(shard_image_write(out_path, img.data(), pl.total, true));
+  if (bytes_out) *bytes_out = pl.total;
   if (removed_out) *removed_out = removed;
   return VI_OK;
 }
@@ -293,7 +281,7 @@ vi_status shard_retain_write(const ShardFile &f, uint64_t shard_id, const std::v
 vi_status shard_remove_from(const std::string &shards_dir, uint64_t shard_id, const uint64_t *ext_ids, uint64_t n,
                             uint64_t *removed_out) {
   if (removed_out) *removed_out = 0;
-  const std::string path = shard_path(shards_dir, shard_id), tmp = path + ".tmp";
+  ShardRewriteSet set(shards_dir);
   uint64_t removed = 0;
   {
     ShardFile f;
@@ -304,30 +292,61 @@ vi_status shard_remove_from(const std::string &shards_dir, uint64_t shard_id, co
     const uint64_t stride = record_stride(f.dim());
     std::vector<std::vector<uint64_t>> words(nl);
     std::vector<const uint64_t *> keep(nl, nullptr);
+    bool any = false;
     for (uint32_t i = 0; i < nl; ++i) {
       const ShardListView &lv = f.list(i);
       if (f.find(lv.centroid_id) != &lv) continue;  // (a later entry of a repeated centroid id: no reader sees it)
-      bool any = false;
       words[i].assign(((uint64_t)lv.num_vectors + 63) / 64, 0);
       for (uint32_t v = 0; v < lv.num_vectors; ++v) {
         uint64_t ext;
         std::memcpy(&ext, lv.records + (uint64_t)v * stride + 8, 8);  // VectorMeta.external_id
-        if (gone.count(ext)) any = true;
+        if (gone.count(ext)) keep[i] = words[i].data();
         else words[i][v >> 6] |= 1ull << (v & 63u);
       }
-      if (any) keep[i] = words[i].data();
+      any = any || keep[i];
     }
-    bool any = false;
-    for (const uint64_t *k : keep) any = any || k;
     if (!any) return VI_OK;
-    VI_TRY(shard_retain_write(f, shard_id, keep, tmp, nullptr, &removed));
+    uint64_t bytes = 0;
+    VI_TRY(shard_retain_write(f, shard_id, keep, set.temporary(shard_id), &bytes, &removed));
+    set.add(shard_id, bytes);
   }  // (unmapped before the rename)
-  if (::rename(tmp.c_str(), path.c_str()) != 0) {
-    const int e = errno;
-    ::unlink(tmp.c_str());
-    return fail(VI_ERR_IO, "rename(%s): %s", tmp.c_str(), strerror(e));
-  }
+  VI_TRY(set.commit());
   if (removed_out) *removed_out = removed;
+  return VI_OK;
+}
+
+// ---- the rewrite set ------------------------------------------------------------------------
+vi_status ShardRewriteSet::open(uint64_t s, uint32_t dim, ShardFile *f) const {
+  VI_TRY(f->open(dir_, s));
+  if (f->dim() != dim) return fail(VI_ERR_INVALID_DATA, "shard_%llu.bin holds dimension %u", (unsigned long long)s, f->dim());
+  return VI_OK;
+}
+
+vi_status ShardRewriteSet::find(const ShardFile &f, uint64_t s, uint32_t l, uint32_t len, const ShardListView **out) const {
+  *out = f.find(l);
+  if (!*out || (*out)->num_vectors != len)  // (the resident blocks are what the file's records are taken to be)
+    return fail(VI_ERR_INVALID_DATA, "shard_%llu.bin no longer matches the resident list %u", (unsigned long long)s, l);
+  return VI_OK;
+}
+
+void ShardRewriteSet::add(uint64_t s, uint64_t bytes) {
+  pairs_.emplace_back(temporary(s), shard_file_path(dir_, s));
+  bytes_ += bytes;
+}
+
+void ShardRewriteSet::drop() {
+  for (; done_ < pairs_.size(); ++done_) ::unlink(pairs_[done_].first.c_str());
+}
+
+vi_status ShardRewriteSet::commit() {
+  for (; done_ < pairs_.size(); ++done_)
+    if (::rename(pairs_[done_].first.c_str(), pairs_[done_].second.c_str()) != 0) {
+      const int e = errno;
+      const size_t i = done_;
+      drop();
+      return fail(VI_ERR_IO, "rename(%s): %s%s", pairs_[i].first.c_str(), strerror(e),
+                  i ? " (earlier shard files of this call are already in place: reload the index)" : "");
+    }
   return VI_OK;
 }
 

@@ -7,6 +7,7 @@
 #pragma once
 #include <cstdint>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "common.hpp"
@@ -53,6 +54,22 @@ class ShardFile {
   std::vector<ShardListView> lists_;
 };
 
+// Where everything of a shard image lies, from dim and the record count of every list in file order: header, index
+// entries, then list after list its centroid vector, the pad to 8 bytes and its records (shards.rs:68-177).
+struct ShardPlan {
+  uint32_t dim;
+  uint64_t vsz, pad, stride, data_off, total;  // bytes of a vector, its pad, a record; first block; the whole image
+  std::vector<uint64_t> count, off, size;      // per list: records, byte offset and bytes of its block
+  ShardPlan(uint32_t dim, std::vector<uint64_t> counts);
+  uint64_t records(uint32_t i) const { return off[i] + vsz + pad; }  // byte offset of list i's first record
+};
+// Header, index entries and centroid vectors (pad zeroed) of the image at p, pl.total bytes; the records are the
+// caller's.  cids[i] / cvecs[i]: centroid id and vector (dim f32) of list i.  The one place these bytes are laid down.
+void shard_frame_write(uint8_t *p, const ShardPlan &pl, uint64_t shard_id, const uint64_t *cids, const void *const *cvecs);
+// The image to the file `path` (created or truncated).  unlink_on_failure: a file left short by a failed write is removed.
+vi_status shard_image_write(const std::string &path, const uint8_t *p, uint64_t total, bool unlink_on_failure);
+std::string shard_file_path(const std::string &shards_dir, uint64_t shard_id);  // the one place a shard file is named
+
 vi_status shard_save_to(const std::string &shards_dir, uint64_t shard_id, uint32_t dim,
                         uint32_t num_lists, const uint64_t *centroid_ids, const float *centroid_vecs,
                         const uint64_t *list_off, const uint64_t *ids, const uint64_t *ext_ids,
@@ -71,7 +88,6 @@ vi_status shard_append_write(const ShardFile &f, uint64_t shard_id, uint64_t n_a
 // opened (the reader's errors) and left as it is.
 vi_status shard_append_to(const std::string &shards_dir, uint64_t shard_id, uint64_t n_add, const uint64_t *centroid_ids,
                           const uint64_t *ids, const uint64_t *ext_ids, const uint64_t *timestamps, const float *vecs);
-std::string shard_file_path(const std::string &shards_dir, uint64_t shard_id);
 
 // Remove records from lists of an open shard file.  keep[i] belongs to list entry i of the file (file order; keep has
 // num_lists() entries): null = every record of the list stays, else record p stays iff bit p % 64 of word p / 64 is set
@@ -88,6 +104,36 @@ vi_status shard_retain_write(const ShardFile &f, uint64_t shard_id, const std::v
 // (the reader's errors) and left as it is.
 vi_status shard_remove_from(const std::string &shards_dir, uint64_t shard_id, const uint64_t *ext_ids, uint64_t n,
                             uint64_t *removed_out);
+
+// The shard files one call rewrites: every file is written beside the old one under a temporary name and registered;
+// commit() renames them over the old files in the order registered.  Whatever is registered and not renamed when the set
+// goes away is unlinked: a call can fail anywhere before commit() without a trace.  Host only.
+class ShardRewriteSet {
+ public:
+  explicit ShardRewriteSet(std::string shards_dir) : dir_(std::move(shards_dir)) {}
+  ~ShardRewriteSet() { drop(); }
+  ShardRewriteSet(const ShardRewriteSet &) = delete;
+  ShardRewriteSet &operator=(const ShardRewriteSet &) = delete;
+
+  // shard_<s>.bin of the directory, which must hold vectors of `dim` dimensions (else InvalidData)
+  vi_status open(uint64_t s, uint32_t dim, ShardFile *f) const;
+  // resident list l in f (= shard s), which must hold `len` records there (else InvalidData)
+  vi_status find(const ShardFile &f, uint64_t s, uint32_t l, uint32_t len, const ShardListView **out) const;
+  std::string temporary(uint64_t s) const { return shard_file_path(dir_, s) + ".tmp"; }
+  void add(uint64_t s, uint64_t bytes);  // temporary(s) is written, `bytes` long
+  // Renames in order.  The first failure unlinks the temporaries not yet renamed: VI_ERR_IO (the files renamed before it
+  // stay in place, and the message says so).  Close every ShardFile of the set's files first.
+  vi_status commit();
+  uint64_t files() const { return pairs_.size(); }
+  uint64_t bytes() const { return bytes_; }
+
+ private:
+  void drop();
+  std::string dir_;
+  std::vector<std::pair<std::string, std::string>> pairs_;  // (temporary, final)
+  size_t done_ = 0;                                         // pairs renamed or unlinked
+  uint64_t bytes_ = 0;
+};
 
 // index/index.bin: IvfIndex{centroids, centroids_to_shard, dimension} through bincode 2
 // `config::standard()` + ndarray serde.  PARITY UNPINNED (no cargo here to confirm bytes).
