@@ -425,6 +425,49 @@ vi_status vi_indexer_remove_ids(vi_indexer *ix, const uint64_t *ext_ids, uint64_
 vi_status vi_shard_remove_from(const char *shards_dir, uint64_t shard_id, const uint64_t *ext_ids, uint64_t n,
                                uint64_t *removed_out);
 
+/* ---- extension (the reference has no update, api.rs:101-237): upsert records in a built or loaded index; what Faiss's IVF
+ * calls update_vectors ----
+ * "This id has a new vector."  Afterwards the index is the one these two calls leave, in this order on the same handle:
+ *   vi_indexer_remove_ids(ix, ext_ids, n, &r);  vi_indexer_add_records(ix, ext_ids, values, timestamps, n);
+ * with byte-identical shard files, an untouched index.bin / coarse table / centroids_to_shard, and the same ids, distance
+ * bits, counts, padding and tie keys from every search — but every touched shard file is written ONCE, the resident
+ * index is rebuilt ONCE (one pass of update_blocks_kernel over the new blocks, one set of ranking images) and swapped
+ * ONCE, and the record is never absent from the files or the handle in between.
+ *   - what goes: every stored record whose external id is in ext_ids, by the rules of a VI_IDS_DENY set (any order,
+ *     duplicates allowed, ids nothing carries are ignored, any u64 is an id; an id several stored records carry removes
+ *     them all).  The kept records of a list close up in their old order.
+ *   - where new records go: record i goes behind the kept records of the list of its nearest centroid ("nearest": the
+ *     first probe of the reference's coarse step, ivf_index.rs:205-220, on the old index; the table does not change),
+ *     new records in call order.  An id named twice in one call is added twice, as vi_indexer_add_records does; nothing
+ *     is de-duplicated.
+ *   - VectorMeta.id of new record i is N_before - replaced + i; timestamps: NULL or 0 => cfg.now_secs, else wall clock
+ *   - *replaced_out (optional): records removed (0 on an error)
+ *   - no id matches: a plain add with those ids.  n == 0: VI_OK, nothing at all changes (old filters stay valid).
+ *   - one deliberate difference from the two calls: a call may replace EVERY record of the index (the two-call form stops
+ *     at "an index keeps at least one record"); the result holds n >= 1 records.  Lists that receive nothing become empty
+ *     entries (num_vectors == 0, still in the coarse table, still probed).
+ *   - files: a shard file is rewritten, whole, if a list in it lost or received a record; all new files are written
+ *     beside the old ones as shard_<id>.bin.tmp, then renamed, and only then is the resident index swapped; a failure
+ *     before the renames removes the temporaries and leaves files and handle unchanged
+ *   - resident index: a replaced index, as after an add or a remove: every vi_filter made before the call is
+ *     VI_ERR_INVALID_INPUT afterwards (free it), vi_range_results must be freed or copied before the call, and the call
+ *     must not overlap searches on the handle; this is not enforced
+ *   - errors, all VI_ERR_INVALID_INPUT before any file or device change: a null ix, ext_ids == NULL or values == NULL
+ *     with n > 0, a non-finite value, a handle with no index, a partitioned handle (world_size > 1),
+ *     N_before - replaced + n past 2^32 - 2, the 32-bit slot limit of the planned layout.  A shard file whose list no
+ *     longer has its resident length: VI_ERR_INVALID_DATA.
+ * Device memory: the old and the new resident index coexist until the swap, beside one filter and the n uploaded rows
+ * (4 n D + 28 n bytes).
+ * vi_shard_upsert_to: the file half alone, no GPU: from one shard file every record whose external id is in ext_ids goes
+ * (the rules of vi_shard_remove_from), then record i joins the list of centroid_ids[i] (the arguments and rules of
+ * vi_shard_append_to); one image, one temporary file, one rename.  A centroid id the shard does not hold:
+ * VI_ERR_NOT_FOUND, and the file is untouched.  n == 0 leaves the file as it is.  *removed_out (optional): records removed. */
+vi_status vi_indexer_upsert_records(vi_indexer *ix, const uint64_t *ext_ids, const float *values, const uint64_t *timestamps,
+                                    uint64_t n, uint64_t *replaced_out);
+vi_status vi_shard_upsert_to(const char *shards_dir, uint64_t shard_id, uint64_t n, const uint64_t *centroid_ids,
+                             const uint64_t *ids, const uint64_t *ext_ids, const uint64_t *timestamps, const float *vecs,
+                             uint64_t *removed_out);
+
 /* ---- extension: radius (range) search -----------------------------------------------------------------------------
  * Every candidate of the probed lists whose squared distance is at most radius2.  The result of a query is the
  * reference's candidate sequence (probed lists in shard visiting order, then probe rank, then list position) after the
@@ -535,6 +578,22 @@ typedef struct vi_remove_stats {
   uint64_t kernel_bytes;     /* ... and the bytes it read and wrote */
 } vi_remove_stats;
 vi_status vi_indexer_last_remove_stats(const vi_indexer *ix, vi_remove_stats *out);
+/* the most recent vi_indexer_upsert_records on this handle with n > 0 (wall-clock ms unless said otherwise) */
+typedef struct vi_upsert_stats {
+  uint64_t n;                /* records added */
+  uint64_t n_replaced;       /* records removed */
+  uint64_t lists_touched;    /* lists that lost or received records ... */
+  uint64_t lists_emptied;    /* ... and of them, lists that lost their last and received none */
+  uint64_t shards_rewritten; /* shard files rewritten, each once */
+  uint64_t bytes_written;    /* bytes of those files */
+  float ms_total;
+  float ms_plan;             /* upload, deny filter, labels (coarse step), grouping, allow words read back */
+  float ms_files;            /* new shard files written and renamed */
+  float ms_index;            /* new resident index: kept_count_kernel, update_blocks_kernel + the ranking images */
+  float ms_kernel;           /* HIP-event time of update_blocks_kernel alone (part of ms_index) ... */
+  uint64_t kernel_bytes;     /* ... and the bytes it read and wrote */
+} vi_upsert_stats;
+vi_status vi_indexer_last_upsert_stats(const vi_indexer *ix, vi_upsert_stats *out);
 
 /* stats of the most recent search on this handle (timing collected only if enabled) */
 vi_status vi_indexer_last_stats(const vi_indexer *ix, vi_search_stats *out);

@@ -35,6 +35,7 @@ struct Indexer {
   vi_build_stats build_stats{};         // phases of the last build on this handle
   vi_add_stats add_stats{};             // ... and of the last vi_indexer_add_records that added something
   vi_remove_stats remove_stats{};       // ... and of the last vi_indexer_retain / vi_indexer_remove_ids that removed something
+  vi_upsert_stats upsert_stats{};       // ... and of the last vi_indexer_upsert_records with n > 0
 };
 
 // No C++ exception may unwind through the C ABI into a Rust / ctypes caller (std::vector growth, std::string, a
@@ -385,6 +386,121 @@ static vi_status retain_records(Indexer *ix, const SlotFilter &keep, uint64_t *r
   return VI_OK;
 }
 
+// vi_indexer_upsert_records behind its argument checks: the order of events of the two calls above, once.  The plan is
+// the allow words of a deny filter of ext_ids (what goes) and the label of every new record (where it goes), both from
+// the old index.
+static vi_status upsert_records(Indexer *ix, const uint64_t *ext_ids, const float *X, const uint64_t *timestamps, uint64_t n,
+                                uint64_t *replaced_out) {
+  const DeviceIndex &old = *ix->dev;
+  const uint32_t dim = ix->cfg.dimension;
+  const uint64_t nlists = old.nlists, n_before = old.nvec_resident;
+  const uint64_t now = ix->cfg.now_secs ? ix->cfg.now_secs : unix_timestamp_secs();
+  vi_upsert_stats us{};
+  us.n = n;
+  const double t0 = now_ms();
+  VI_HIP(hipSetDevice(old.device));
+  hipStream_t st = nullptr;
+  VI_HIP(hipStreamCreateWithFlags(&st, hipStreamDefault));
+  struct StreamGuard { hipStream_t s; ~StreamGuard() { (void)hipStreamDestroy(s); } } guard{st};
+  // ---- plan ----
+  DevBuf<float> Xd;
+  DevBuf<uint64_t> ext_dev, ts_dev;
+  DevBuf<uint32_t> lab, order, seg_dev;
+  std::vector<uint64_t> ts(n);
+  for (uint64_t i = 0; i < n; ++i) ts[i] = timestamps && timestamps[i] ? timestamps[i] : now;  // vector_store.rs:36-40
+  VI_TRY(Xd.reserve(n * dim));
+  VI_TRY(ext_dev.reserve(n));
+  VI_TRY(ts_dev.reserve(n));
+  VI_TRY(lab.reserve(n));
+  VI_HIP(hipMemcpyAsync(Xd.p, X, n * dim * sizeof(float), hipMemcpyHostToDevice, st));
+  VI_HIP(hipMemcpyAsync(ext_dev.p, ext_ids, n * 8, hipMemcpyHostToDevice, st));
+  VI_HIP(hipMemcpyAsync(ts_dev.p, ts.data(), n * 8, hipMemcpyHostToDevice, st));
+  VI_HIP(hipStreamSynchronize(st));
+  SlotFilter keep;  // the records a VI_IDS_DENY filter of the set admits (the ids are read from the upload)
+  VI_TRY(slot_filter_ids(old, ext_dev.p, n, true, true, &keep));
+  if (keep.num_allowed > n_before) return fail(VI_ERR_OTHER, "upsert: the filter admits more records than the index holds");
+  const uint64_t n_replaced = n_before - keep.num_allowed;
+  if (keep.num_allowed + n > 0xFFFFFFFEull) return fail(VI_ERR_INVALID_INPUT, "more than 2^32 - 2 vectors");
+  us.n_replaced = n_replaced;
+  VI_TRY(device_index_label_rows(old, Xd.p, n, lab.p));
+  std::vector<uint64_t> seg;
+  VI_TRY(group_ids_by_label_device(lab.p, n, nlists, order, seg_dev, &seg, st));
+  if (seg.size() != nlists + 1 || seg[nlists] != n) return fail(VI_ERR_OTHER, "upsert: a record was assigned to no list");
+  // which positions of which lists stay (position p of list l: bit p % 64 of word first[l] + p / 64), which rows follow
+  std::vector<uint64_t> h_allow(old.lists.nblocks);
+  std::vector<uint32_t> h_first(nlists), h_len, h_order(n);
+  if (old.lists.nblocks) VI_HIP(hipMemcpy(h_allow.data(), keep.allow.p, old.lists.nblocks * 8, hipMemcpyDeviceToHost));
+  VI_HIP(hipMemcpy(h_first.data(), old.list_first_block.p, nlists * 4, hipMemcpyDeviceToHost));
+  VI_HIP(hipMemcpy(h_order.data(), order.p, n * 4, hipMemcpyDeviceToHost));
+  VI_TRY(read_list_lengths(old, &h_len));
+  std::vector<uint64_t> kept(nlists), full_len(nlists);
+  for (uint64_t l = 0; l < nlists; ++l) {
+    for (uint32_t b = 0; b < (h_len[l] + 63u) / 64u; ++b) kept[l] += (uint64_t)__builtin_popcountll(h_allow[h_first[l] + b]);
+    full_len[l] = kept[l] + (seg[l + 1] - seg[l]);
+  }
+  {  // the slot limit of the new layout, before anything is written
+    ListLayout lay;
+    if (plan_list_layout(full_len.data(), nlists, 1, 0, &lay) != LayoutError::none)
+      return fail(VI_ERR_INVALID_INPUT, "index too large for 32-bit slot ids");
+  }
+  const auto lists_of_shard = touched_lists_by_shard(ix->meta, nlists, [&](uint64_t l) {
+    if (kept[l] == h_len[l] && seg[l + 1] == seg[l]) return false;  // lost nothing, received nothing
+    ++us.lists_touched;
+    us.lists_emptied += h_len[l] != 0 && full_len[l] == 0;
+    return true;
+  });
+  const double t1 = now_ms();
+  us.ms_plan = (float)(t1 - t0);
+
+  // ---- files: every touched shard once, under a temporary name ----
+  ShardRewriteSet files(ix->shards_dir);
+  {
+    std::vector<uint64_t> s_cid, s_id, s_ext, s_ts;
+    std::vector<float> s_vec;
+    for (const auto &kv : lists_of_shard) {
+      const uint64_t s = kv.first;
+      ShardFile f;
+      VI_TRY(files.open(s, dim, &f));
+      std::vector<const uint64_t *> keep_of(f.num_lists(), nullptr);
+      s_cid.clear(); s_id.clear(); s_ext.clear(); s_ts.clear(); s_vec.clear();
+      for (const uint32_t l : kv.second) {
+        const ShardListView *lv;
+        VI_TRY(files.find(f, s, l, h_len[l], &lv));
+        if (kept[l] != h_len[l]) keep_of[lv - &f.list(0)] = h_allow.data() + h_first[l];
+        for (uint64_t e = seg[l]; e < seg[l + 1]; ++e) {
+          const uint32_t r = h_order[e];
+          s_cid.push_back(l); s_id.push_back(keep.num_allowed + r); s_ext.push_back(ext_ids[r]); s_ts.push_back(ts[r]);
+          s_vec.insert(s_vec.end(), X + (uint64_t)r * dim, X + (uint64_t)r * dim + dim);
+        }
+      }
+      uint64_t bytes = 0;
+      VI_TRY(shard_update_write(f, s, keep_of, s_cid.size(), s_cid.data(), s_id.data(), s_ext.data(), s_ts.data(), s_vec.data(),
+                                files.temporary(s), &bytes, nullptr, nullptr));
+      files.add(s, bytes);
+    }
+  }
+  const double t2 = now_ms();
+
+  // ---- the new resident index, beside the old one ----
+  auto dev = std::make_unique<DeviceIndex>();
+  VI_TRY(device_index_update(old, keep, Xd.p, n, order.p, seg_dev.p, seg, ext_dev.p, ts_dev.p, dev.get(), &us.ms_kernel,
+                             &us.kernel_bytes));
+  const double t3 = now_ms();
+  us.ms_index = (float)(t3 - t2);
+
+  // ---- renames, then the swap ----
+  VI_TRY(files.commit());
+  ix->dev = std::move(dev);
+  const double t4 = now_ms();
+  us.bytes_written = files.bytes();
+  us.shards_rewritten = files.files();
+  us.ms_files = (float)((t2 - t1) + (t4 - t3));
+  us.ms_total = (float)(t4 - t0);
+  ix->upsert_stats = us;
+  if (replaced_out) *replaced_out = n_replaced;
+  return VI_OK;
+}
+
 }  // namespace vi
 
 using vi::fail;
@@ -719,6 +835,38 @@ vi_status vi_shard_remove_from(const char *shards_dir, uint64_t shard_id, const 
   });
 }
 
+vi_status vi_indexer_upsert_records(vi_indexer *ix, const uint64_t *ext_ids, const float *values, const uint64_t *timestamps,
+                                    uint64_t n, uint64_t *replaced_out) {
+  return vi::guarded([&]() -> vi_status {
+  if (replaced_out) *replaced_out = 0;
+  if (!ix) return fail(VI_ERR_INVALID_INPUT, "null indexer");
+  if (n == 0) return VI_OK;  // nothing changes: no file, no index, no filter
+  if (!ext_ids) return fail(VI_ERR_INVALID_INPUT, "null id set with n = %llu", (unsigned long long)n);
+  if (!values) return fail(VI_ERR_INVALID_INPUT, "null values");
+  const uint32_t dim = ix->impl.cfg.dimension;
+  if (n > 0xFFFFFFFEull || (dim && n > ~0ull / 4 / dim)) return fail(VI_ERR_INVALID_INPUT, "more than 2^32 - 2 vectors");
+  for (uint64_t i = 0; i < n * (uint64_t)dim; ++i)
+    if (!std::isfinite(values[i]))
+      return fail(VI_ERR_INVALID_INPUT, "non-finite value at flat index %llu", (unsigned long long)i);
+  if (!ix->impl.dev) return fail(VI_ERR_INVALID_INPUT, "the indexer holds no index (build or load it first)");
+  if (ix->impl.cfg.world_size > 1 || ix->impl.dev->stripe_world > 1)
+    return fail(VI_ERR_INVALID_INPUT, "records are upserted through an unpartitioned handle (world_size <= 1); ranks reload from its files");
+  if (ix->impl.dev->nlists == 0) return fail(VI_ERR_INVALID_INPUT, "the index has no list to add to");
+  return vi::upsert_records(&ix->impl, ext_ids, values, timestamps, n, replaced_out);
+  });
+}
+
+vi_status vi_shard_upsert_to(const char *shards_dir, uint64_t shard_id, uint64_t n, const uint64_t *centroid_ids,
+                             const uint64_t *ids, const uint64_t *ext_ids, const uint64_t *timestamps, const float *vecs,
+                             uint64_t *removed_out) {
+  return vi::guarded([&]() -> vi_status {
+  if (removed_out) *removed_out = 0;
+  if (!shards_dir) return fail(VI_ERR_INVALID_INPUT, "null pointer");
+  if (n && (!centroid_ids || !ids || !ext_ids || !timestamps || !vecs)) return fail(VI_ERR_INVALID_INPUT, "null pointer");
+  return vi::shard_upsert_to(shards_dir, shard_id, n, centroid_ids, ids, ext_ids, timestamps, vecs, removed_out);
+  });
+}
+
 static vi_status search_common(const vi_indexer *ix, uint64_t *k, uint64_t *n_probe) {
   if (!ix) return fail(VI_ERR_INVALID_INPUT, "null indexer");
   const vi_config &c = ix->impl.cfg;
@@ -1030,6 +1178,14 @@ vi_status vi_indexer_last_remove_stats(const vi_indexer *ix, vi_remove_stats *ou
   return vi::guarded([&]() -> vi_status {
   if (!ix || !out) return fail(VI_ERR_INVALID_INPUT, "no stats");
   *out = ix->impl.remove_stats;
+  return VI_OK;
+  });
+}
+
+vi_status vi_indexer_last_upsert_stats(const vi_indexer *ix, vi_upsert_stats *out) {
+  return vi::guarded([&]() -> vi_status {
+  if (!ix || !out) return fail(VI_ERR_INVALID_INPUT, "no stats");
+  *out = ix->impl.upsert_stats;
   return VI_OK;
   });
 }

@@ -166,7 +166,7 @@ struct DeviceIndex {
   ~DeviceIndex();
 };
 
-// ---- the five routes to a resident index ----
+// ---- the six routes to a resident index ----
 // Each lays its lists out by list_layout.hpp, reserves and uploads through alloc_list_storage, builds (or copies) the
 // coarse table and ends with prepare_rank_images (search_internal.hpp, device_index.hip); what differs is where the list
 // blocks come from:
@@ -178,6 +178,8 @@ struct DeviceIndex {
 //   device_index_append      (list_update.hip)   the blocks of an older index and new rows: vi_indexer_add_records (api.cpp)
 //   device_index_compact     (list_update.hip)   the blocks of an older index less the records a filter excludes:
 //                                                vi_indexer_retain / vi_indexer_remove_ids (api.cpp)
+//   device_index_update      (list_update.hip)   both at once, the kept records of a list followed by its new rows:
+//                                                vi_indexer_upsert_records (api.cpp)
 //
 // Upload: centroid table + this rank's part of the lists, repacked on the GPU.  placement 0: a stripe of every list
 // (block b on rank b % world); 1: the whole lists of the shard files dealt to this rank (greedy by bytes).
@@ -215,6 +217,15 @@ vi_status device_index_append(const DeviceIndex &old, const std::vector<uint32_t
 // drops the old one.  ms_kernel / kernel_bytes (optional): HIP-event time of compact_blocks_kernel and the bytes it moves.
 vi_status device_index_compact(const DeviceIndex &old, const SlotFilter &keep, DeviceIndex *out, float *ms_kernel,
                                uint64_t *kernel_bytes);
+// `out` = a fresh index holding, list by list, the records of `old` (unpartitioned; only read) whose allow bit in `keep` (a
+// filter of `old`) is 1, closed up in their old order, followed by rows order_dev[seg[l] .. seg[l + 1]) of rows_dev (the
+// arguments of device_index_append).  A list may keep nothing and receive rows, or keep nothing and receive none (an
+// empty list).  One pass over the new blocks; old and new index coexist until the caller drops the old one.  ms_kernel /
+// kernel_bytes (optional): HIP-event time of update_blocks_kernel and the bytes it moves.
+vi_status device_index_update(const DeviceIndex &old, const SlotFilter &keep, const float *rows_dev, uint64_t n,
+                              const uint32_t *order_dev, const uint32_t *seg_dev, const std::vector<uint64_t> &seg_host,
+                              const uint64_t *row_ext_dev, const uint64_t *row_ts_dev, DeviceIndex *out, float *ms_kernel,
+                              uint64_t *kernel_bytes);
 
 struct SearchIO {
   const float *queries = nullptr;  // host or device (queries_on_device)

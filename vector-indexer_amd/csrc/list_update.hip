@@ -1,5 +1,5 @@
-// list_update.hip — the resident half of vi_indexer_add_records and of vi_indexer_retain / vi_indexer_remove_ids: a new
-// DeviceIndex from the blocks of the old one, without re-reading a shard file.  Both routes run
+// list_update.hip — the resident half of vi_indexer_add_records, of vi_indexer_retain / vi_indexer_remove_ids and of
+// vi_indexer_upsert_records: a new DeviceIndex from the blocks of the old one, without re-reading a shard file.  All routes run
 //
 //   begin_update: the refusals, a fresh index on the old one's device
 //     -> the new length of every list (append: old length + rows received; compact: kept_count_kernel)
@@ -24,6 +24,12 @@
 // length.  compact_blocks_kernel is a gather: new position p = 64 j + lane looks its source up, the old block by binary
 // search over the list's block_prefix, the lane inside it as the (p - prefix)-th set bit of the block's allow word.
 // Sources inside a wave ascend and are mostly adjacent; the writes are whole rows.
+//
+// Update (vi_indexer_upsert_records).  Both at once: the count pass of compact gives kept[l], the grouping of append
+// gives the rows list l receives, new_len[l] = kept[l] + received[l].  update_blocks_kernel takes position p < kept[l]
+// from the old blocks as compact does and kept[l] <= p < new_len[l] from the upload as append does.  A straight copy
+// needs a list that lost nothing AND a block of old records only: equal lengths do not mean equal positions (one record
+// out, one in).  A list may have no old block at all (an emptied list that receives rows): it never searches block_prefix.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -221,6 +227,101 @@ __global__ void __launch_bounds__(kUpdateWaves * kWave) compact_blocks_kernel(Co
   a.ts[slot] = valid ? a.old_ts[old_slot] : 0ull;
 }
 
+struct UpdateArgs {
+  // the old index and what is kept of it
+  const float4 *old_blocks;
+  const uint64_t *old_ext, *old_ts;
+  const uint32_t *old_first, *old_len;     // per list
+  const uint64_t *allow;                   // per old block
+  const uint32_t *block_prefix;            // per old block (kept_count_kernel)
+  const uint32_t *kept;                    // per list: kept records (kept_count_kernel)
+  // the new layout
+  const uint32_t *new_first, *new_len;     // per list: new_len = kept + rows received
+  const uint32_t *block_list;              // per new block: its list
+  uint64_t nblocks;                        // new blocks
+  // the new rows, grouped by list: list l receives rows order[seg[l] .. seg[l + 1]) in that order, behind its kept records
+  const float *rows;                       // n x dim
+  const uint64_t *row_ext, *row_ts;        // per row, resolved on the host (never null)
+  const uint32_t *order, *seg;
+  uint32_t dim, dq;
+  float4 *blocks;
+  uint64_t *ext, *ts;
+};
+
+// quad qd of a row-major row of `dim` values, zero beyond dim (as append_blocks_kernel reads the upload)
+__device__ __forceinline__ float4 row_quad(const float *v, uint32_t qd, uint32_t dim) {
+  float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
+  const uint32_t e = qd * 4;
+  if (e + 0 < dim) x.x = v[e + 0];
+  if (e + 1 < dim) x.y = v[e + 1];
+  if (e + 2 < dim) x.z = v[e + 2];
+  if (e + 3 < dim) x.w = v[e + 3];
+  return x;
+}
+
+// Compact and append in one pass: new position p = 64 j + lane of list l is kept record p of the old list where
+// p < kept (the gather of compact_blocks_kernel), row order[seg[l] + p - kept] of the upload where kept <= p < new_len
+// (the read of append_blocks_kernel), a pad lane behind that.
+__global__ void __launch_bounds__(kUpdateWaves * kWave) update_blocks_kernel(UpdateArgs a) {
+  const uint32_t lane = threadIdx.x & (kWave - 1);
+  const uint64_t b = (uint64_t)blockIdx.x * kUpdateWaves + (threadIdx.x >> 6);
+  if (b >= a.nblocks) return;
+  const uint32_t l = a.block_list[b];
+  const uint32_t j = (uint32_t)(b - a.new_first[l]);           // block of the list
+  const uint32_t old_len = a.old_len[l], new_len = a.new_len[l], kept = a.kept[l], old_first = a.old_first[l];
+  const uint32_t dq = a.dq;
+  float4 *dst = a.blocks + (b * dq) * kWave + lane;
+  const uint64_t slot = b * kWave + lane;
+  const bool lost_nothing = kept == old_len;                   // (wave-uniform) kept positions are the old ones
+  // a straight copy needs both: a list that loses one record and receives one keeps its length and moves every position
+  if (lost_nothing && j * kWave + (kWave - 1) < old_len) {     // ... and all 64 are old records
+    copy_old_block(a, a.old_blocks + ((uint64_t)(old_first + j) * dq) * kWave + lane, dst, (uint64_t)(old_first + j) * kWave + lane, slot);
+    return;
+  }
+  const uint32_t p = j * kWave + lane;                         // position inside the new list (new_len < 2^32 - 64)
+  const bool is_old = p < kept, is_new = !is_old && p < new_len;
+  uint32_t sb = j, sl = lane;                                  // source block of the old list, lane inside it
+  if (!lost_nothing && j * kWave < kept) {                     // (wave-uniform) the block holds kept records that moved
+    // kept < old_len here, so the list had records: old_nblk >= 1.  A list without old blocks (an emptied list that
+    // receives rows) has kept == old_len == 0 and never searches; a block of new rows only does not either.
+    const uint32_t old_nblk = (old_len + kWave - 1) / kWave;
+    const uint32_t ps = is_old ? p : 0u;                       // (the other lanes search too, and read nothing afterwards)
+    // the last old block whose prefix is <= ps (compact_blocks_kernel); the trip count depends on old_nblk alone
+    uint32_t lo = 0, hi = old_nblk;
+    while (hi - lo > 1) {
+      const uint32_t mid = lo + (hi - lo) / 2;
+      if (a.block_prefix[old_first + mid] <= ps) lo = mid; else hi = mid;
+    }
+    sb = lo;
+    sl = is_old ? nth_set_bit(a.allow[old_first + sb], ps - a.block_prefix[old_first + sb]) : 0u;
+  }
+  const float4 *src = a.old_blocks + ((uint64_t)(old_first + sb) * dq) * kWave + sl;  // (read only where is_old)
+  const uint64_t old_slot = (uint64_t)(old_first + sb) * kWave + sl;
+  uint32_t row = 0;
+  if (is_new) row = a.order[a.seg[l] + (p - kept)];
+  const float *v = a.rows + (size_t)row * a.dim;               // (read only where is_new)
+  for (uint32_t qd = 0; qd < dq; qd += 4) {  // four rows in flight (dq is a multiple of 4: layout_dq)
+    float4 t0 = make_float4(0.f, 0.f, 0.f, 0.f), t1 = t0, t2 = t0, t3 = t0;
+    if (is_old) {
+      t0 = src[(size_t)(qd + 0) * kWave];
+      t1 = src[(size_t)(qd + 1) * kWave];
+      t2 = src[(size_t)(qd + 2) * kWave];
+      t3 = src[(size_t)(qd + 3) * kWave];
+    } else if (is_new) {
+      t0 = row_quad(v, qd + 0, a.dim);
+      t1 = row_quad(v, qd + 1, a.dim);
+      t2 = row_quad(v, qd + 2, a.dim);
+      t3 = row_quad(v, qd + 3, a.dim);
+    }
+    dst[(size_t)(qd + 0) * kWave] = t0;
+    dst[(size_t)(qd + 1) * kWave] = t1;
+    dst[(size_t)(qd + 2) * kWave] = t2;
+    dst[(size_t)(qd + 3) * kWave] = t3;
+  }
+  a.ext[slot] = is_old ? a.old_ext[old_slot] : is_new ? a.row_ext[row] : ~0ull;
+  a.ts[slot] = is_old ? a.old_ts[old_slot] : is_new ? a.row_ts[row] : 0ull;
+}
+
 struct EventPair {
   hipEvent_t a = nullptr, b = nullptr;
   ~EventPair() {
@@ -345,6 +446,44 @@ vi_status device_index_compact(const DeviceIndex &old, const SlotFilter &keep, D
   CompactArgs a{};
   a.allow = keep.allow.p; a.block_prefix = block_prefix.p;
   return finish_update(old, ix, d_block_list, compact_blocks_kernel, a, ms_kernel, kernel_bytes);
+}
+
+// The index `old` without the records whose allow bit in `keep` is 0 and with rows appended: the kept records of list l
+// close up in their old order, rows order_dev[seg_host[l] .. seg_host[l + 1]) of rows_dev follow them.  Complete on
+// return; `old` and `keep` are only read.
+vi_status device_index_update(const DeviceIndex &old, const SlotFilter &keep, const float *rows_dev, uint64_t n,
+                              const uint32_t *order_dev, const uint32_t *seg_dev, const std::vector<uint64_t> &seg_host,
+                              const uint64_t *row_ext_dev, const uint64_t *row_ts_dev, DeviceIndex *ix, float *ms_kernel,
+                              uint64_t *kernel_bytes) {
+  const uint64_t nlists = old.nlists;
+  VI_TRY(begin_update(old, "a partitioned index takes no records and gives none up", ix, ms_kernel, kernel_bytes));
+  if (keep.owner_serial != old.serial) return fail(VI_ERR_INVALID_INPUT, "the filter was made from another index");
+  if (seg_host.size() != nlists + 1 || seg_host[nlists] != n) return fail(VI_ERR_OTHER, "update: grouping does not match the index");
+  hipStream_t st = ix->stream;
+  // ---- count pass: the kept records of every list, and those in front of every old block ----
+  DevBuf<uint32_t> block_prefix, d_kept;
+  VI_TRY(block_prefix.reserve(std::max<uint64_t>(1, old.lists.nblocks)));
+  VI_TRY(d_kept.reserve(std::max<uint64_t>(1, nlists)));
+  std::vector<uint32_t> kept(nlists);
+  if (nlists) {
+    CountArgs c{keep.allow.p, old.list_first_block.p, old.list_len.p, (uint32_t)nlists, block_prefix.p, d_kept.p};
+    hipLaunchKernelGGL(kept_count_kernel, dim3((uint32_t)((nlists + kUpdateWaves - 1) / kUpdateWaves)),
+                       dim3(kUpdateWaves * kWave), 0, st, c);
+    VI_HIP(hipGetLastError());
+    VI_HIP(hipMemcpyAsync(kept.data(), d_kept.p, nlists * 4, hipMemcpyDeviceToHost, st));
+    VI_HIP(hipStreamSynchronize(st));
+  }
+  std::vector<uint64_t> full_len(nlists);
+  for (uint64_t l = 0; l < nlists; ++l) full_len[l] = (uint64_t)kept[l] + (seg_host[l + 1] - seg_host[l]);
+  DevBuf<uint32_t> d_block_list;
+  VI_TRY(lay_out_from_old(ix, old, full_len.data(), &d_block_list));
+  if (ix->nvec_resident != keep.num_allowed + n) return fail(VI_ERR_OTHER, "update: the filter's count does not match its allow words");
+  UpdateArgs a{};
+  a.allow = keep.allow.p; a.block_prefix = block_prefix.p; a.kept = d_kept.p;
+  a.rows = rows_dev; a.row_ext = row_ext_dev; a.row_ts = row_ts_dev;
+  a.order = order_dev; a.seg = seg_dev;
+  a.dim = ix->dim;
+  return finish_update(old, ix, d_block_list, update_blocks_kernel, a, ms_kernel, kernel_bytes);
 }
 
 }  // namespace vi

@@ -105,6 +105,22 @@ vi_status shard_retain_write(const ShardFile &f, uint64_t shard_id, const std::v
 vi_status shard_remove_from(const std::string &shards_dir, uint64_t shard_id, const uint64_t *ext_ids, uint64_t n,
                             uint64_t *removed_out);
 
+// Remove and append in one image: `keep` as for shard_retain_write, the add arguments as for shard_append_write.  The
+// kept records of every list are copied verbatim, in runs, and the added records of the list go behind them in call
+// order.  Written to out_path, byte-identical to shard_retain_write followed by shard_append_write; f's own file is left
+// alone.  A centroid id the file does not hold: NotFound, nothing written.  bytes_out / removed_out / lists_out
+// (optional): size of the file written, records removed, lists that lost or received a record.
+vi_status shard_update_write(const ShardFile &f, uint64_t shard_id, const std::vector<const uint64_t *> &keep, uint64_t n_add,
+                             const uint64_t *centroid_ids, const uint64_t *ids, const uint64_t *ext_ids,
+                             const uint64_t *timestamps, const float *vecs, const std::string &out_path, uint64_t *bytes_out,
+                             uint64_t *removed_out, uint64_t *lists_out);
+// ... for one shard file on its own: every record whose external id is one of ext_ids[0..n) goes (the rules of
+// shard_remove_from), then record i goes to the list of centroid_ids[i] (the rules of shard_append_to).  Open, write
+// beside the file under a temporary name, rename.  n == 0: the file is opened (the reader's errors) and left as it is.
+vi_status shard_upsert_to(const std::string &shards_dir, uint64_t shard_id, uint64_t n, const uint64_t *centroid_ids,
+                          const uint64_t *ids, const uint64_t *ext_ids, const uint64_t *timestamps, const float *vecs,
+                          uint64_t *removed_out);
+
 // The shard files one call rewrites: every file is written beside the old one under a temporary name and registered;
 // commit() renames them over the old files in the order registered.  Whatever is registered and not renamed when the set
 // goes away is unlinked: a call can fail anywhere before commit() without a trace.  Host only.

@@ -11,6 +11,7 @@ bindings/python/python/vector_indexer_py/__init__.py):
     VectorIndex.dimension
     VectorIndex.add(xb, ext_ids=None, timestamps=None)      extension: append records to a built or loaded index
     VectorIndex.remove_ids(ids) / .retain(filter) -> int    extension: remove records from it (by id / all a filter excludes)
+    VectorIndex.upsert(xb, ext_ids, timestamps=None) -> int extension: replace the records that carry ext_ids, in one rewrite
 
 Errors surface as RuntimeError, as PyO3's PyRuntimeError does.  There is NO CPU fallback: if
 libvi_amd.so is missing or no MI355X is visible, build/load/search raise.
@@ -315,6 +316,36 @@ class VectorIndex:
         """phases of the most recent retain() / remove_ids() that removed something"""
         st = _native.RemoveStats()
         _native.check(lib().vi_indexer_last_remove_stats(self._h, C.byref(st)))
+        return {f: getattr(st, f) for f, _ in st._fields_}
+
+    def upsert(self, xb, ext_ids, timestamps=None) -> int:
+        """extension: "these ids have new vectors": every stored record whose external id is in ext_ids goes (the rules
+        of remove_ids()), then row i of xb joins the list of its nearest centroid with id ext_ids[i] (the rules of add())
+        -> records replaced.  The index afterwards is the one remove_ids(ext_ids) followed by add(xb, ext_ids, timestamps)
+        leaves, from one rewrite of every touched shard file and one rebuild of the resident index; unlike that pair, a
+        call may replace every record.  Ids nothing carries are simply added; an id named twice is added twice.
+        Unpartitioned indexes only.  Filters made before the call are rejected afterwards; RangeResults must be copied or
+        freed before it; the call must not overlap searches of this index."""
+        xb = np.asarray(xb)
+        if xb.ndim != 2:
+            raise RuntimeError("Array must be 2-dimensional")
+        if xb.shape[1] != self._dimension:
+            raise RuntimeError(f"Vector dimension {xb.shape[1]} doesn't match index dimension {self._dimension}")
+        xb = np.ascontiguousarray(xb, dtype=np.float32)
+        n = xb.shape[0]
+        e = _native.id_array(ext_ids)
+        t = None if timestamps is None else np.ascontiguousarray(timestamps, dtype=np.uint64).reshape(-1)
+        if e.size != n or (t is not None and t.size != n):
+            raise RuntimeError("ext_ids and timestamps must have one entry per row")
+        replaced = C.c_uint64(0)
+        _native.check(lib().vi_indexer_upsert_records(self._h, _native.ptr(e) if n else None, _native.ptr(xb), _native.ptr(t), n,
+                                                      C.byref(replaced)), prefix="Failed to upsert records: ")
+        return int(replaced.value)
+
+    def upsert_stats(self) -> dict:
+        """phases of the most recent upsert() of at least one row"""
+        st = _native.UpsertStats()
+        _native.check(lib().vi_indexer_last_upsert_stats(self._h, C.byref(st)))
         return {f: getattr(st, f) for f, _ in st._fields_}
 
     def build_stats(self) -> dict:

@@ -58,7 +58,13 @@ class RemoveStats(C.Structure):
                 ("ms_kernel", f32), ("kernel_bytes", u64)]
 
 
-FETCH_ROWS_FN = C.CFUNCTYPE(C.c_int, vp, C.POINTER(u64), u64, vp)
+class UpsertStats(C.Structure):
+    _fields_ = [("n", u64), ("n_replaced", u64), ("lists_touched", u64), ("lists_emptied", u64), ("shards_rewritten", u64),
+                ("bytes_written", u64), ("ms_total", f32), ("ms_plan", f32), ("ms_files", f32), ("ms_index", f32),
+                ("ms_kernel", f32), ("kernel_bytes", u64)]
+
+
+FETCH_ROWS_FN =C.CFUNCTYPE(C.c_int, vp, C.POINTER(u64), u64, vp)
 
 
 class RowSource(C.Structure):
@@ -138,6 +144,9 @@ SIGNATURES = {
     "vi_indexer_remove_ids": (C.c_int, [vp, vp, u64, C.POINTER(u64)]),
     "vi_shard_remove_from": (C.c_int, [C.c_char_p, u64, vp, u64, C.POINTER(u64)]),
     "vi_indexer_last_remove_stats": (C.c_int, [vp, C.POINTER(RemoveStats)]),
+    "vi_indexer_upsert_records": (C.c_int, [vp, vp, vp, vp, u64, C.POINTER(u64)]),
+    "vi_shard_upsert_to": (C.c_int, [C.c_char_p, u64, u64, vp, vp, vp, vp, vp, C.POINTER(u64)]),
+    "vi_indexer_last_upsert_stats": (C.c_int, [vp, C.POINTER(UpsertStats)]),
 }
 
 _lib = None

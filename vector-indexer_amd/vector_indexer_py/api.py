@@ -9,6 +9,7 @@
     .range_search(query, radius2, ...)                                            extension: everything within a radius
     .add_records(records)                                                         extension: append to a built index
     .remove_records(external_ids) -> int                                          extension: remove from a built index
+    .upsert_records(records) -> int                                               extension: replace by external id
     SearchRequest.with_timestamp_range / .with_allowed_ids / .with_excluded_ids   extension: filtered search
 
 Errors are ViError (a RuntimeError) whose .kind is the io::ErrorKind name the reference returns.
@@ -230,6 +231,26 @@ class VectorIndexer:
         self._drop_filters()  # (cached filters describe the index this call replaces)
         _native.check(lib().vi_indexer_remove_ids(self._h, _native.ptr(ids) if ids.size else None, ids.size, C.byref(removed)))
         return int(removed.value)
+
+    def upsert_records(self, records: List[VectorRecord]) -> int:
+        """extension: replace the stored records that carry the records' external ids by the records (files and resident
+        index, one rewrite; ids nothing carries are added) -> records replaced.  An empty list changes nothing."""
+        n = len(records)
+        dim = self._cfg.dimension
+        for i, r in enumerate(records):
+            if len(r.values) != dim:  # (the message of build_from_records, api.rs:122-133)
+                raise ViError(_native.VI_ERR_INVALID_INPUT,
+                              f"vector dimension mismatch at index {i}: expected {dim}, got {len(r.values)}")
+        if n == 0:
+            return 0
+        vals = np.ascontiguousarray([r.values for r in records], dtype=np.float32).reshape(n, dim)
+        ext = np.array([r.external_id for r in records], dtype=np.uint64)
+        ts = np.array([r.timestamp or 0 for r in records], dtype=np.uint64)
+        replaced = C.c_uint64(0)
+        self._drop_filters()  # (cached filters describe the index this call replaces)
+        _native.check(lib().vi_indexer_upsert_records(self._h, _native.ptr(ext), _native.ptr(vals), _native.ptr(ts), n,
+                                                      C.byref(replaced)))
+        return int(replaced.value)
 
     def build_from_vector_file(self, path) -> "VectorIndexer":
         self._drop_filters()

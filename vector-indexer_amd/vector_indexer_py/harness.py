@@ -119,7 +119,7 @@ def synthetic_dataset(n: int, d: int, nq: int, k: int, seed: int = 42) -> Tuple[
 # ---- the adapter + eval loop --------------------------------------------------------------------------------------
 class FaissStyleAdapter:
     """the Faiss-looking face of an index: .d, .nprobe (settable), .search(xq, k) -> (D, I), .range_search(x, thresh),
-    .add(x), .add_with_ids(x, ids), .remove_ids(ids) -> int, .ntotal
+    .add(x), .add_with_ids(x, ids), .remove_ids(ids) -> int, .update_vectors(ids, x) -> int, .ntotal
     (vector_indexer_adapter.py:75-140; the reference hops through an asyncio thread, the search here is synchronous)"""
 
     def __init__(self, vector_index, k: int = 100):
@@ -172,6 +172,11 @@ class FaissStyleAdapter:
     def remove_ids(self, ids) -> int:
         """Faiss's Index.remove_ids for a batch of ids: the number of records removed"""
         return self._idx.remove_ids(ids)
+
+    def update_vectors(self, ids, x: np.ndarray) -> int:
+        """Faiss's IndexIVF.update_vectors(ids, x): the records that carry ids[i] are replaced by row i of x -> records
+        replaced.  Unlike Faiss, an id the index does not hold is added"""
+        return self._idx.upsert(np.ascontiguousarray(x, dtype=np.float32), ids)
 
     @property
     def ntotal(self) -> int:
