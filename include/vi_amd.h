@@ -557,8 +557,8 @@ typedef struct vi_add_stats {
   float ms_total;
   float ms_assign;           /* upload, labels (coarse step), grouping by list */
   float ms_files;            /* new shard files written and renamed */
-  float ms_index;            /* new resident index: append_blocks_kernel + the ranking images */
-  float ms_kernel;           /* HIP-event time of append_blocks_kernel alone (part of ms_index) ... */
+  float ms_index;            /* new resident index: update_blocks_kernel + the ranking images */
+  float ms_kernel;           /* HIP-event time of update_blocks_kernel alone (part of ms_index) ... */
   uint64_t kernel_bytes;     /* ... and the bytes it read and wrote */
 } vi_add_stats;
 vi_status vi_indexer_last_add_stats(const vi_indexer *ix, vi_add_stats *out);
@@ -573,8 +573,8 @@ typedef struct vi_remove_stats {
   float ms_total;
   float ms_plan;             /* the allow words read back, the touched lists and shards found */
   float ms_files;            /* new shard files written and renamed */
-  float ms_index;            /* new resident index: kept_count_kernel, compact_blocks_kernel + the ranking images */
-  float ms_kernel;           /* HIP-event time of compact_blocks_kernel alone (part of ms_index) ... */
+  float ms_index;            /* new resident index: kept_count_kernel, update_blocks_kernel + the ranking images */
+  float ms_kernel;           /* HIP-event time of update_blocks_kernel alone (part of ms_index) ... */
   uint64_t kernel_bytes;     /* ... and the bytes it read and wrote */
 } vi_remove_stats;
 vi_status vi_indexer_last_remove_stats(const vi_indexer *ix, vi_remove_stats *out);

@@ -4,7 +4,7 @@
 
 For 1 000, 10 000 and 100 000 added records, `--repeats` times each: a copy of the base index's files is loaded, the
 records are added (vi_add_stats), and the same final set is built in full (ms_total and ms_index of vi_build_stats).  The
-added records come from the mixture the base was drawn from.  append_blocks_kernel's HIP-event time and the bytes it moved
+added records come from the mixture the base was drawn from.  update_blocks_kernel's HIP-event time and the bytes it moved
 give its achieved bandwidth, beside the float4-copy bandwidth measured on this chip (6.29 TB/s).
 Writes profiles/r09_add_records.json."""
 import argparse

@@ -5,8 +5,8 @@ builds (N = 1e6, D = 128, 4096 lists), against loading the files the removal wro
 For 1 000, 10 000 and 100 000 random external ids (remove_ids) and for a timestamp window that keeps half of the records
 (retain), `--repeats` times each: a copy of the base index's files is loaded, the records are removed (vi_remove_stats),
 the resulting directories are loaded afresh (wall clock around vi_indexer_load), and one record is added to the shrunken
-index (vi_add_stats: append_blocks_kernel's rate on the same index, in the same run).  compact_blocks_kernel's HIP-event
-time and the bytes it moved give its achieved bandwidth, beside the float4-copy bandwidth measured on this chip
+index (vi_add_stats: update_blocks_kernel's rate without a filter on the same index, in the same run).  Its HIP-event
+time with the filter and the bytes it moved give its achieved bandwidth, beside the float4-copy bandwidth measured on this chip
 (6.29 TB/s).  Writes profiles/r11_remove_records.json."""
 import argparse
 import json

@@ -135,8 +135,8 @@ static void check_round_trip(const std::string &work, uint32_t dim) {
   {
     ShardFile f;
     CHECK(f.open(a, 3) == VI_OK, "D %u: %s", dim, last_error_ref().c_str());
-    CHECK(shard_append_write(f, 3, 5, cid.data(), id.data(), ext.data(), ts.data(), vec.data(), shard_file_path(b, 3), &bytes, &lists) == VI_OK,
-          "D %u: %s", dim, last_error_ref().c_str());
+    CHECK(shard_update_write(f, 3, {}, 5, cid.data(), id.data(), ext.data(), ts.data(), vec.data(), shard_file_path(b, 3), &bytes, nullptr,
+                             &lists) == VI_OK, "D %u: %s", dim, last_error_ref().c_str());  // (no keep: nothing goes)
   }
   CHECK(lists == 2 && bytes == first.size() + 5 * record_stride(dim), "D %u: %llu lists, %llu bytes", dim, (unsigned long long)lists,
         (unsigned long long)bytes);
@@ -148,7 +148,8 @@ static void check_round_trip(const std::string &work, uint32_t dim) {
     CHECK(f.num_lists() == 5 && f.list(1).num_vectors == 73 && f.list(2).num_vectors == 2, "D %u: appended counts", dim);
     const uint64_t keep70[2] = {~0ull, (1ull << 6) - 1}, keep_none[1] = {0};  // positions 0..69 of 73; neither of 2
     const std::vector<const uint64_t *> keep{nullptr, keep70, keep_none, nullptr, nullptr};
-    CHECK(shard_retain_write(f, 3, keep, back, &bytes, &removed) == VI_OK, "D %u: %s", dim, last_error_ref().c_str());
+    CHECK(shard_update_write(f, 3, keep, 0, nullptr, nullptr, nullptr, nullptr, nullptr, back, &bytes, &removed, nullptr) == VI_OK,
+          "D %u: %s", dim, last_error_ref().c_str());  // (no rows: nothing joins)
   }
   CHECK(removed == 5 && bytes == first.size(), "D %u: %llu removed, %llu bytes", dim, (unsigned long long)removed, (unsigned long long)bytes);
   CHECK(slurp(back) == first, "D %u: append then retain does not give the first file back", dim);

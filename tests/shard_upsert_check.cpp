@@ -1,5 +1,5 @@
 // shard_upsert_check.cpp — host checks of shard_update_write of csrc/shards.cpp, the writer that drops and appends in one
-// image (compiled together with shards.cpp and run by test_shard_upsert_cpu.py, in the scratch directory given as
+// image, with both halves, with either alone and with "nothing goes" said both ways (compiled together with shards.cpp and run by test_shard_upsert_cpu.py, in the scratch directory given as
 // argv[1]): prints one line per failed check and exits non-zero if there was one.
 #include <sys/stat.h>
 #include <unistd.h>
@@ -101,14 +101,14 @@ static void check_update(const std::string &work, uint32_t dim) {
         last_error_ref().c_str());
   const Bytes first = slurp(shard_file_path(a, 3));
   uint64_t bytes = 0, removed = 0, lists = 0;
-  {  // the two existing writers, one after the other
+  {  // two executions, one after the other: drop only (no rows), then append only (no keep) to the file that left
     ShardFile f, g;
     CHECK(f.open(a, 3) == VI_OK, "D %u: %s", dim, last_error_ref().c_str());
-    CHECK(shard_retain_write(f, 3, c.keep, shard_file_path(mid, 3), nullptr, &removed) == VI_OK && removed == 1 + 1 + 64, "D %u: retain: %s",
-          dim, last_error_ref().c_str());
+    CHECK(shard_update_write(f, 3, c.keep, 0, nullptr, nullptr, nullptr, nullptr, nullptr, shard_file_path(mid, 3), nullptr, &removed,
+                             nullptr) == VI_OK && removed == 1 + 1 + 64, "D %u: retain: %s", dim, last_error_ref().c_str());
     CHECK(g.open(mid, 3) == VI_OK, "D %u: %s", dim, last_error_ref().c_str());
-    CHECK(shard_append_write(g, 3, c.cid.size(), c.cid.data(), c.id.data(), c.ext.data(), c.ts.data(), c.vec.data(), shard_file_path(pair, 3),
-                             nullptr, nullptr) == VI_OK, "D %u: append: %s", dim, last_error_ref().c_str());
+    CHECK(shard_update_write(g, 3, {}, c.cid.size(), c.cid.data(), c.id.data(), c.ext.data(), c.ts.data(), c.vec.data(),
+                             shard_file_path(pair, 3), nullptr, nullptr, nullptr) == VI_OK, "D %u: append: %s", dim, last_error_ref().c_str());
   }
   {  // ... and the one that does both
     ShardFile f;
@@ -144,6 +144,31 @@ static void check_update(const std::string &work, uint32_t dim) {
   // kept run, then the new records
   CHECK(meta_word(f.list(4), dim, 0, 0) == 76 + 64 && meta_word(f.list(4), dim, 65, 0) == 76 + 129 && meta_word(f.list(4), dim, 66, 0) == 301 &&
             meta_word(f.list(4), dim, 67, 0) == 304, "D %u list 24: kept records, then new ones", dim);
+}
+
+// "nothing goes" said both ways: an empty keep, and num_lists() null entries
+static void check_no_keep(const std::string &work, uint32_t dim) {
+  const std::string a = work + "/nokeep_a_" + std::to_string(dim), out = work + "/nokeep_" + std::to_string(dim);
+  const Lists L(dim);
+  const Call c(dim);
+  CHECK(L.save(a, 3) == VI_OK, "D %u: %s", dim, last_error_ref().c_str());
+  const Bytes first = slurp(shard_file_path(a, 3));
+  ShardFile f;
+  CHECK(f.open(a, 3) == VI_OK, "D %u: %s", dim, last_error_ref().c_str());
+  const std::vector<const uint64_t *> empty, nulls(f.num_lists(), nullptr);
+  uint64_t bytes[2] = {0, 0}, removed[2] = {7, 7}, lists[2] = {0, 0};
+  CHECK(shard_update_write(f, 3, empty, c.cid.size(), c.cid.data(), c.id.data(), c.ext.data(), c.ts.data(), c.vec.data(), out + ".empty",
+                           &bytes[0], &removed[0], &lists[0]) == VI_OK, "D %u: empty keep: %s", dim, last_error_ref().c_str());
+  CHECK(shard_update_write(f, 3, nulls, c.cid.size(), c.cid.data(), c.id.data(), c.ext.data(), c.ts.data(), c.vec.data(), out + ".nulls",
+                           &bytes[1], &removed[1], &lists[1]) == VI_OK, "D %u: null keep entries: %s", dim, last_error_ref().c_str());
+  const Bytes got = slurp(out + ".empty");
+  CHECK(got.size() == first.size() + 6 * record_stride(dim) && got == slurp(out + ".nulls"), "D %u: an empty keep and null entries differ", dim);
+  for (int i = 0; i < 2; ++i)
+    CHECK(removed[i] == 0 && lists[i] == 3 && bytes[i] == got.size(), "D %u: %llu removed, %llu lists, %llu bytes", dim,
+          (unsigned long long)removed[i], (unsigned long long)lists[i], (unsigned long long)bytes[i]);
+  // ... and with nothing to join either: the file again
+  CHECK(shard_update_write(f, 3, empty, 0, nullptr, nullptr, nullptr, nullptr, nullptr, out + ".same", nullptr, nullptr, &lists[0]) == VI_OK &&
+            lists[0] == 0 && slurp(out + ".same") == first, "D %u: nothing goes, nothing joins: %s", dim, last_error_ref().c_str());
 }
 
 static void check_failures(const std::string &work) {
@@ -196,6 +221,7 @@ int main(int argc, char **argv) {
   }
   const std::string work = argv[1];
   for (uint32_t dim : {3u, 16u}) check_update(work, dim);
+  for (uint32_t dim : {3u, 16u}) check_no_keep(work, dim);
   check_failures(work);
   if (failures) std::printf("%d checks failed\n", failures);
   return failures ? 1 : 0;

@@ -425,3 +425,39 @@ def test_python_wrappers_equal_the_c_abi_path(small):
     assert all_bytes(roots["faiss"][1]) == want
     assert_same(*fa.search(small["Q"], 10), Da, Ia, "FaissStyleAdapter.update_vectors")
     assert fa.update_vectors(ext, x) == len(ext) and fa.ntotal == N0 + 2      # now every id is known
+
+
+def test_upsert_of_unknown_ids_equals_add(small):
+    """filter present with every bit set against filter absent, through the one block kernel: an upsert whose ids no record
+    carries drops nothing, so it must leave what add leaves — files, ids, distance bits and tie keys"""
+    rng = np.random.default_rng(14)
+    orc = O.OracleIndex.load(small["idx"], small["sh"])
+    lens = np.array([orc.list_len(c) for c in range(len(small["cent"]))], dtype=np.int64)
+    # 66 rows behind a list whose last block is partly filled: that block mixes old and new lanes, the next holds new rows
+    # only; 4 rows that fit into the last block of another list
+    a = int(np.flatnonzero(lens % 64 != 0)[0])
+    b = int(np.flatnonzero((lens % 64 != 0) & (lens % 64 <= 60) & (np.arange(len(lens)) != a))[0])
+    aims = np.array([a] * 66 + [b] * 4, dtype=np.int64)[rng.permutation(70)]
+    x = U.rows_near(small["cent"], aims, rng)
+    assert (U.oracle_labels(orc, x) == aims.astype(np.uint64)).all(), "a row is not nearest to the centroid it was made for"
+    assert 0 < lens[a] % 64 and 0 < lens[b] % 64 <= 60      # (64 - r of the 66 fill a's block, the other 2 + r have their own)
+    ext = np.uint64(U.NEW_EXT0) + np.arange(70, dtype=np.uint64)
+    ts = np.uint64(7000) + np.arange(70, dtype=np.uint64)
+    ts[::7] = 0                                                       # the add's `now` rule
+    roots = {name: copy_dirs(small["idx"], small["sh"], small["root"], name) for name in ("added", "upserted")}
+    added = vip.load(*roots["added"], 16, now_secs=NOW)
+    upserted = vip.load(*roots["upserted"], 16, now_secs=NOW)
+    added.add(x, ext_ids=ext, timestamps=ts)
+    assert upserted.upsert(x, ext, ts) == 0 and upserted.upsert_stats()["n_replaced"] == 0
+    assert added.num_vectors == upserted.num_vectors == N0 + 70
+    want = all_bytes(roots["added"][1])
+    assert want != all_bytes(small["sh"]) and all_bytes(roots["upserted"][1]) == want
+    new = O.OracleIndex.load(*roots["upserted"])
+    assert new.list_len(a) == lens[a] + 66 and new.list_len(b) == lens[b] + 4
+    Q = np.concatenate([x, small["Q"]]).astype(np.float32)
+    for nq, k, p in SHAPES:
+        Da, Ia, Ta = device_search_tie(added, Q[:nq], k, p)
+        Du, Iu, Tu = device_search_tie(upserted, Q[:nq], k, p)
+        assert_same(Du, Iu, Da, Ia, f"upsert against add {(nq, k, p)}")
+        assert np.array_equal(Tu[Iu != -1], Ta[Ia != -1]), (nq, k, p)
+        assert np.isin(Iu[Iu != -1], ext.astype(np.int64)).any(), (nq, k, p)      # (the first queries are new rows themselves)

@@ -197,10 +197,41 @@ static vi_status fit_and_save(Indexer *ix, const float *X, const uint64_t *ext_i
   return rc;
 }
 
-// ---- updates of a built index: add_records and retain_records ----
-// Both run: a plan (which lists change), the touched shard files written under temporary names (ShardRewriteSet,
-// shards.hpp), the new resident index built from the old blocks (list_update.hip), then the renames, then the swap.
-// Everything before the renames can fail without a trace: the temporary files are removed, the handle keeps its index.
+// ---- updates of a built index: add_records, retain_records and upsert_records ----
+// All three run update_records: a plan (which lists change), the touched shard files written under temporary names
+// (ShardRewriteSet, shards.hpp), the new resident index built from the old blocks (list_update.hip), then the renames,
+// then the swap.  Everything before the renames can fail without a trace: the temporary files are removed, the handle
+// keeps its index.  What goes is a keep filter of ix->dev, what joins is a set of uploaded rows; either may be absent.
+
+// the rows an add or an upsert brings: the caller's host arrays, the stored timestamps, the device copies and their stream
+struct NewRows {
+  const float *X = nullptr;
+  const uint64_t *ext = nullptr;
+  uint64_t n = 0;
+  std::vector<uint64_t> ts;
+  hipStream_t st = nullptr;
+  DevBuf<float> Xd;
+  DevBuf<uint64_t> ext_dev, ts_dev;
+  ~NewRows() { if (st) (void)hipStreamDestroy(st); }
+};
+
+static vi_status upload_rows(const Indexer *ix, const uint64_t *ext, const float *X, const uint64_t *timestamps, uint64_t n, NewRows *r) {
+  const uint32_t dim = ix->cfg.dimension;
+  const uint64_t now = ix->cfg.now_secs ? ix->cfg.now_secs : unix_timestamp_secs();
+  r->X = X; r->ext = ext; r->n = n;
+  r->ts.resize(n);
+  for (uint64_t i = 0; i < n; ++i) r->ts[i] = timestamps && timestamps[i] ? timestamps[i] : now;  // vector_store.rs:36-40
+  VI_HIP(hipSetDevice(ix->dev->device));
+  VI_HIP(hipStreamCreateWithFlags(&r->st, hipStreamDefault));
+  VI_TRY(r->Xd.reserve(n * dim));
+  VI_TRY(r->ext_dev.reserve(n));
+  VI_TRY(r->ts_dev.reserve(n));
+  VI_HIP(hipMemcpyAsync(r->Xd.p, X, n * dim * sizeof(float), hipMemcpyHostToDevice, r->st));
+  VI_HIP(hipMemcpyAsync(r->ext_dev.p, ext, n * 8, hipMemcpyHostToDevice, r->st));
+  VI_HIP(hipMemcpyAsync(r->ts_dev.p, r->ts.data(), n * 8, hipMemcpyHostToDevice, r->st));
+  VI_HIP(hipStreamSynchronize(r->st));
+  return VI_OK;
+}
 
 // the lengths of the resident lists, read back once per call
 static vi_status read_list_lengths(const DeviceIndex &ix, std::vector<uint32_t> *len) {
@@ -218,226 +249,45 @@ static std::map<uint64_t, std::vector<uint32_t>> touched_lists_by_shard(const In
   return lists_of_shard;
 }
 
-// vi_indexer_add_records behind its argument checks; the plan is the label of every new record, from the GPU
-static vi_status add_records(Indexer *ix, const uint64_t *ext_ids, const float *X, const uint64_t *timestamps, uint64_t n) {
+struct UpdateStats {
+  uint64_t lists_touched = 0, lists_emptied = 0, shards_rewritten = 0, bytes_written = 0, kernel_bytes = 0;
+  float ms_plan = 0, ms_files = 0, ms_index = 0, ms_kernel = 0, ms_total = 0;
+};
+
+// The order of events, once.  keep (or null: nothing goes): a filter of ix->dev, its allow words say which positions of
+// which lists stay (position p of list l: bit p % 64 of word first[l] + p / 64).  rows (or null: nothing joins): the
+// label of every row, from the old index, says where it goes; row r gets internal id (records kept) + r.  t0: when the
+// call began.  On success the handle holds the new index and *us the figures; on failure nothing has changed.
+static vi_status update_records(Indexer *ix, const SlotFilter *keep, const NewRows *rows, double t0, UpdateStats *us) {
   const DeviceIndex &old = *ix->dev;
   const uint32_t dim = ix->cfg.dimension;
-  const uint64_t nlists = old.nlists, n_before = old.nvec_resident;
-  const uint64_t now = ix->cfg.now_secs ? ix->cfg.now_secs : unix_timestamp_secs();
-  vi_add_stats as{};
-  as.n = n;
-  const double t0 = now_ms();
+  const uint64_t nlists = old.nlists, n = rows ? rows->n : 0, n_kept = keep ? keep->num_allowed : old.nvec_resident;
   VI_HIP(hipSetDevice(old.device));
-  hipStream_t st = nullptr;
-  VI_HIP(hipStreamCreateWithFlags(&st, hipStreamDefault));
-  struct StreamGuard { hipStream_t s; ~StreamGuard() { (void)hipStreamDestroy(s); } } guard{st};
-  // what every new record carries in the files and on the device
-  std::vector<uint64_t> ids(n), ext(n), ts(n);
-  for (uint64_t i = 0; i < n; ++i) {
-    ids[i] = n_before + i;
-    ext[i] = ext_ids ? ext_ids[i] : n_before + i;
-    ts[i] = timestamps && timestamps[i] ? timestamps[i] : now;  // vector_store.rs:36-40
-  }
-  DevBuf<float> Xd;
-  DevBuf<uint64_t> ext_dev, ts_dev;
-  DevBuf<uint32_t> lab, order, seg_dev;
-  VI_TRY(Xd.reserve(n * dim));
-  VI_TRY(ext_dev.reserve(n));
-  VI_TRY(ts_dev.reserve(n));
-  VI_TRY(lab.reserve(n));
-  VI_HIP(hipMemcpyAsync(Xd.p, X, n * dim * sizeof(float), hipMemcpyHostToDevice, st));
-  VI_HIP(hipMemcpyAsync(ext_dev.p, ext.data(), n * 8, hipMemcpyHostToDevice, st));
-  VI_HIP(hipMemcpyAsync(ts_dev.p, ts.data(), n * 8, hipMemcpyHostToDevice, st));
-  VI_HIP(hipStreamSynchronize(st));
-  VI_TRY(device_index_label_rows(old, Xd.p, n, lab.p));
-  std::vector<uint64_t> seg;
-  VI_TRY(group_ids_by_label_device(lab.p, n, nlists, order, seg_dev, &seg, st));
-  std::vector<uint32_t> h_order(n), h_len;
-  VI_HIP(hipMemcpy(h_order.data(), order.p, n * 4, hipMemcpyDeviceToHost));
-  VI_TRY(read_list_lengths(old, &h_len));
-  if (seg.size() != nlists + 1 || seg[nlists] != n) return fail(VI_ERR_OTHER, "add: a record was assigned to no list");
-  {  // the slot limit of the new layout, before anything is written
-    std::vector<uint64_t> full_len(nlists);
-    for (uint64_t l = 0; l < nlists; ++l) full_len[l] = (uint64_t)h_len[l] + (seg[l + 1] - seg[l]);
-    ListLayout lay;
-    if (plan_list_layout(full_len.data(), nlists, 1, 0, &lay) != LayoutError::none)
-      return fail(VI_ERR_INVALID_INPUT, "index too large for 32-bit slot ids");
-  }
-  const double t1 = now_ms();
-  as.ms_assign = (float)(t1 - t0);
-
-  // ---- files: every touched shard under a temporary name ----
-  const auto lists_of_shard = touched_lists_by_shard(ix->meta, nlists, [&](uint64_t l) {
-    as.lists_touched += seg[l + 1] > seg[l];
-    return seg[l + 1] > seg[l];
-  });
-  ShardRewriteSet files(ix->shards_dir);
-  {
-    std::vector<uint64_t> s_cid, s_id, s_ext, s_ts;
-    std::vector<float> s_vec;
-    for (const auto &kv : lists_of_shard) {
-      const uint64_t s = kv.first;
-      ShardFile f;
-      VI_TRY(files.open(s, dim, &f));
-      s_cid.clear(); s_id.clear(); s_ext.clear(); s_ts.clear(); s_vec.clear();
-      for (const uint32_t l : kv.second) {
-        const ShardListView *lv;
-        VI_TRY(files.find(f, s, l, h_len[l], &lv));
-        for (uint64_t e = seg[l]; e < seg[l + 1]; ++e) {
-          const uint32_t r = h_order[e];
-          s_cid.push_back(l); s_id.push_back(ids[r]); s_ext.push_back(ext[r]); s_ts.push_back(ts[r]);
-          s_vec.insert(s_vec.end(), X + (uint64_t)r * dim, X + (uint64_t)r * dim + dim);
-        }
-      }
-      uint64_t bytes = 0;
-      VI_TRY(shard_append_write(f, s, s_cid.size(), s_cid.data(), s_id.data(), s_ext.data(), s_ts.data(), s_vec.data(),
-                                files.temporary(s), &bytes, nullptr));
-      files.add(s, bytes);
-    }
-  }
-  const double t2 = now_ms();
-
-  // ---- the new resident index, beside the old one ----
-  auto dev = std::make_unique<DeviceIndex>();
-  VI_TRY(device_index_append(old, h_len, Xd.p, n, order.p, seg_dev.p, seg, ext_dev.p, ts_dev.p, dev.get(), &as.ms_kernel,
-                             &as.kernel_bytes));
-  const double t3 = now_ms();
-  as.ms_index = (float)(t3 - t2);
-
-  // ---- renames, then the swap ----
-  VI_TRY(files.commit());
-  ix->dev = std::move(dev);
-  const double t4 = now_ms();
-  as.bytes_written = files.bytes();
-  as.shards_rewritten = files.files();
-  as.ms_files = (float)((t2 - t1) + (t4 - t3));
-  as.ms_total = (float)(t4 - t0);
-  ix->add_stats = as;
-  return VI_OK;
-}
-
-// vi_indexer_retain / vi_indexer_remove_ids behind their argument checks; the plan comes from the allow words of `keep`, a
-// filter of ix->dev
-static vi_status retain_records(Indexer *ix, const SlotFilter &keep, uint64_t *removed_out) {
-  const DeviceIndex &old = *ix->dev;
-  const uint32_t dim = ix->cfg.dimension;
-  const uint64_t nlists = old.nlists;
-  if (removed_out) *removed_out = 0;
-  if (keep.num_allowed > old.nvec_resident) return fail(VI_ERR_OTHER, "retain: the filter admits more records than the index holds");
-  const uint64_t n_removed = old.nvec_resident - keep.num_allowed;
-  if (n_removed == 0) return VI_OK;  // nothing changes: no file, no index, no filter
-  if (keep.num_allowed == 0)
-    return fail(VI_ERR_INVALID_INPUT, "the removal would leave the index without a record (an index keeps at least one; to drop it, delete its directories)");
-  vi_remove_stats rs{};
-  rs.n_removed = n_removed;
-  const double t0 = now_ms();
-  VI_HIP(hipSetDevice(old.device));
-  // ---- plan: which positions of which lists stay (position p of list l: bit p % 64 of word first[l] + p / 64) ----
-  std::vector<uint64_t> h_allow(old.lists.nblocks);
-  std::vector<uint32_t> h_first(nlists), h_len;
-  if (old.lists.nblocks) VI_HIP(hipMemcpy(h_allow.data(), keep.allow.p, old.lists.nblocks * 8, hipMemcpyDeviceToHost));
-  VI_HIP(hipMemcpy(h_first.data(), old.list_first_block.p, nlists * 4, hipMemcpyDeviceToHost));
-  VI_TRY(read_list_lengths(old, &h_len));
-  const auto lists_of_shard = touched_lists_by_shard(ix->meta, nlists, [&](uint64_t l) {
-    uint64_t kept = 0;
-    for (uint32_t b = 0; b < (h_len[l] + 63u) / 64u; ++b) kept += (uint64_t)__builtin_popcountll(h_allow[h_first[l] + b]);
-    if (kept == h_len[l]) return false;
-    ++rs.lists_touched;
-    rs.lists_emptied += kept == 0;
-    return true;
-  });
-  const double t1 = now_ms();
-  rs.ms_plan = (float)(t1 - t0);
-
-  // ---- files: every touched shard under a temporary name ----
-  ShardRewriteSet files(ix->shards_dir);
-  for (const auto &kv : lists_of_shard) {
-    const uint64_t s = kv.first;
-    ShardFile f;
-    VI_TRY(files.open(s, dim, &f));
-    std::vector<const uint64_t *> keep_of(f.num_lists(), nullptr);
-    for (const uint32_t l : kv.second) {
-      const ShardListView *lv;
-      VI_TRY(files.find(f, s, l, h_len[l], &lv));
-      keep_of[lv - &f.list(0)] = h_allow.data() + h_first[l];
-    }
-    uint64_t bytes = 0;
-    VI_TRY(shard_retain_write(f, s, keep_of, files.temporary(s), &bytes, nullptr));
-    files.add(s, bytes);
-  }
-  const double t2 = now_ms();
-
-  // ---- the new resident index, beside the old one ----
-  auto dev = std::make_unique<DeviceIndex>();
-  VI_TRY(device_index_compact(old, keep, dev.get(), &rs.ms_kernel, &rs.kernel_bytes));
-  const double t3 = now_ms();
-  rs.ms_index = (float)(t3 - t2);
-
-  // ---- renames, then the swap ----
-  VI_TRY(files.commit());
-  ix->dev = std::move(dev);
-  const double t4 = now_ms();
-  rs.bytes_written = files.bytes();
-  rs.shards_rewritten = files.files();
-  rs.ms_files = (float)((t2 - t1) + (t4 - t3));
-  rs.ms_total = (float)(t4 - t0);
-  ix->remove_stats = rs;
-  if (removed_out) *removed_out = n_removed;
-  return VI_OK;
-}
-
-// vi_indexer_upsert_records behind its argument checks: the order of events of the two calls above, once.  The plan is
-// the allow words of a deny filter of ext_ids (what goes) and the label of every new record (where it goes), both from
-// the old index.
-static vi_status upsert_records(Indexer *ix, const uint64_t *ext_ids, const float *X, const uint64_t *timestamps, uint64_t n,
-                                uint64_t *replaced_out) {
-  const DeviceIndex &old = *ix->dev;
-  const uint32_t dim = ix->cfg.dimension;
-  const uint64_t nlists = old.nlists, n_before = old.nvec_resident;
-  const uint64_t now = ix->cfg.now_secs ? ix->cfg.now_secs : unix_timestamp_secs();
-  vi_upsert_stats us{};
-  us.n = n;
-  const double t0 = now_ms();
-  VI_HIP(hipSetDevice(old.device));
-  hipStream_t st = nullptr;
-  VI_HIP(hipStreamCreateWithFlags(&st, hipStreamDefault));
-  struct StreamGuard { hipStream_t s; ~StreamGuard() { (void)hipStreamDestroy(s); } } guard{st};
   // ---- plan ----
-  DevBuf<float> Xd;
-  DevBuf<uint64_t> ext_dev, ts_dev;
   DevBuf<uint32_t> lab, order, seg_dev;
-  std::vector<uint64_t> ts(n);
-  for (uint64_t i = 0; i < n; ++i) ts[i] = timestamps && timestamps[i] ? timestamps[i] : now;  // vector_store.rs:36-40
-  VI_TRY(Xd.reserve(n * dim));
-  VI_TRY(ext_dev.reserve(n));
-  VI_TRY(ts_dev.reserve(n));
-  VI_TRY(lab.reserve(n));
-  VI_HIP(hipMemcpyAsync(Xd.p, X, n * dim * sizeof(float), hipMemcpyHostToDevice, st));
-  VI_HIP(hipMemcpyAsync(ext_dev.p, ext_ids, n * 8, hipMemcpyHostToDevice, st));
-  VI_HIP(hipMemcpyAsync(ts_dev.p, ts.data(), n * 8, hipMemcpyHostToDevice, st));
-  VI_HIP(hipStreamSynchronize(st));
-  SlotFilter keep;  // the records a VI_IDS_DENY filter of the set admits (the ids are read from the upload)
-  VI_TRY(slot_filter_ids(old, ext_dev.p, n, true, true, &keep));
-  if (keep.num_allowed > n_before) return fail(VI_ERR_OTHER, "upsert: the filter admits more records than the index holds");
-  const uint64_t n_replaced = n_before - keep.num_allowed;
-  if (keep.num_allowed + n > 0xFFFFFFFEull) return fail(VI_ERR_INVALID_INPUT, "more than 2^32 - 2 vectors");
-  us.n_replaced = n_replaced;
-  VI_TRY(device_index_label_rows(old, Xd.p, n, lab.p));
-  std::vector<uint64_t> seg;
-  VI_TRY(group_ids_by_label_device(lab.p, n, nlists, order, seg_dev, &seg, st));
-  if (seg.size() != nlists + 1 || seg[nlists] != n) return fail(VI_ERR_OTHER, "upsert: a record was assigned to no list");
-  // which positions of which lists stay (position p of list l: bit p % 64 of word first[l] + p / 64), which rows follow
-  std::vector<uint64_t> h_allow(old.lists.nblocks);
-  std::vector<uint32_t> h_first(nlists), h_len, h_order(n);
-  if (old.lists.nblocks) VI_HIP(hipMemcpy(h_allow.data(), keep.allow.p, old.lists.nblocks * 8, hipMemcpyDeviceToHost));
-  VI_HIP(hipMemcpy(h_first.data(), old.list_first_block.p, nlists * 4, hipMemcpyDeviceToHost));
-  VI_HIP(hipMemcpy(h_order.data(), order.p, n * 4, hipMemcpyDeviceToHost));
-  VI_TRY(read_list_lengths(old, &h_len));
-  std::vector<uint64_t> kept(nlists), full_len(nlists);
-  for (uint64_t l = 0; l < nlists; ++l) {
-    for (uint32_t b = 0; b < (h_len[l] + 63u) / 64u; ++b) kept[l] += (uint64_t)__builtin_popcountll(h_allow[h_first[l] + b]);
-    full_len[l] = kept[l] + (seg[l + 1] - seg[l]);
+  std::vector<uint64_t> seg(nlists + 1, 0);
+  std::vector<uint32_t> h_order(n), h_first, h_len;
+  std::vector<uint64_t> h_allow;
+  if (rows) {
+    VI_TRY(lab.reserve(n));
+    VI_TRY(device_index_label_rows(old, rows->Xd.p, n, lab.p));
+    VI_TRY(group_ids_by_label_device(lab.p, n, nlists, order, seg_dev, &seg, rows->st));
+    if (seg.size() != nlists + 1 || seg[nlists] != n) return fail(VI_ERR_OTHER, "update: a record was assigned to no list");
+    VI_HIP(hipMemcpy(h_order.data(), order.p, n * 4, hipMemcpyDeviceToHost));
   }
+  VI_TRY(read_list_lengths(old, &h_len));
+  std::vector<uint64_t> kept(h_len.begin(), h_len.end()), full_len(nlists);
+  if (keep) {
+    h_allow.resize(old.lists.nblocks);
+    h_first.resize(nlists);
+    if (old.lists.nblocks) VI_HIP(hipMemcpy(h_allow.data(), keep->allow.p, old.lists.nblocks * 8, hipMemcpyDeviceToHost));
+    VI_HIP(hipMemcpy(h_first.data(), old.list_first_block.p, nlists * 4, hipMemcpyDeviceToHost));
+    for (uint64_t l = 0; l < nlists; ++l) {
+      kept[l] = 0;
+      for (uint32_t b = 0; b < (h_len[l] + 63u) / 64u; ++b) kept[l] += (uint64_t)__builtin_popcountll(h_allow[h_first[l] + b]);
+    }
+  }
+  for (uint64_t l = 0; l < nlists; ++l) full_len[l] = kept[l] + (seg[l + 1] - seg[l]);
   {  // the slot limit of the new layout, before anything is written
     ListLayout lay;
     if (plan_list_layout(full_len.data(), nlists, 1, 0, &lay) != LayoutError::none)
@@ -445,23 +295,24 @@ static vi_status upsert_records(Indexer *ix, const uint64_t *ext_ids, const floa
   }
   const auto lists_of_shard = touched_lists_by_shard(ix->meta, nlists, [&](uint64_t l) {
     if (kept[l] == h_len[l] && seg[l + 1] == seg[l]) return false;  // lost nothing, received nothing
-    ++us.lists_touched;
-    us.lists_emptied += h_len[l] != 0 && full_len[l] == 0;
+    ++us->lists_touched;
+    us->lists_emptied += h_len[l] != 0 && full_len[l] == 0;
     return true;
   });
   const double t1 = now_ms();
-  us.ms_plan = (float)(t1 - t0);
+  us->ms_plan = (float)(t1 - t0);
 
   // ---- files: every touched shard once, under a temporary name ----
   ShardRewriteSet files(ix->shards_dir);
   {
     std::vector<uint64_t> s_cid, s_id, s_ext, s_ts;
     std::vector<float> s_vec;
+    std::vector<const uint64_t *> keep_of;  // (left empty without a filter: nothing goes)
     for (const auto &kv : lists_of_shard) {
       const uint64_t s = kv.first;
       ShardFile f;
       VI_TRY(files.open(s, dim, &f));
-      std::vector<const uint64_t *> keep_of(f.num_lists(), nullptr);
+      if (keep) keep_of.assign(f.num_lists(), nullptr);
       s_cid.clear(); s_id.clear(); s_ext.clear(); s_ts.clear(); s_vec.clear();
       for (const uint32_t l : kv.second) {
         const ShardListView *lv;
@@ -469,8 +320,8 @@ static vi_status upsert_records(Indexer *ix, const uint64_t *ext_ids, const floa
         if (kept[l] != h_len[l]) keep_of[lv - &f.list(0)] = h_allow.data() + h_first[l];
         for (uint64_t e = seg[l]; e < seg[l + 1]; ++e) {
           const uint32_t r = h_order[e];
-          s_cid.push_back(l); s_id.push_back(keep.num_allowed + r); s_ext.push_back(ext_ids[r]); s_ts.push_back(ts[r]);
-          s_vec.insert(s_vec.end(), X + (uint64_t)r * dim, X + (uint64_t)r * dim + dim);
+          s_cid.push_back(l); s_id.push_back(n_kept + r); s_ext.push_back(rows->ext[r]); s_ts.push_back(rows->ts[r]);
+          s_vec.insert(s_vec.end(), rows->X + (uint64_t)r * dim, rows->X + (uint64_t)r * dim + dim);
         }
       }
       uint64_t bytes = 0;
@@ -483,20 +334,89 @@ static vi_status upsert_records(Indexer *ix, const uint64_t *ext_ids, const floa
 
   // ---- the new resident index, beside the old one ----
   auto dev = std::make_unique<DeviceIndex>();
-  VI_TRY(device_index_update(old, keep, Xd.p, n, order.p, seg_dev.p, seg, ext_dev.p, ts_dev.p, dev.get(), &us.ms_kernel,
-                             &us.kernel_bytes));
+  VI_TRY(device_index_update(old, keep, rows ? rows->Xd.p : nullptr, n, order.p, seg_dev.p, seg, rows ? rows->ext_dev.p : nullptr,
+                             rows ? rows->ts_dev.p : nullptr, h_len, dev.get(), &us->ms_kernel, &us->kernel_bytes));
   const double t3 = now_ms();
-  us.ms_index = (float)(t3 - t2);
+  us->ms_index = (float)(t3 - t2);
 
   // ---- renames, then the swap ----
   VI_TRY(files.commit());
   ix->dev = std::move(dev);
   const double t4 = now_ms();
-  us.bytes_written = files.bytes();
-  us.shards_rewritten = files.files();
-  us.ms_files = (float)((t2 - t1) + (t4 - t3));
-  us.ms_total = (float)(t4 - t0);
-  ix->upsert_stats = us;
+  us->bytes_written = files.bytes();
+  us->shards_rewritten = files.files();
+  us->ms_files = (float)((t2 - t1) + (t4 - t3));
+  us->ms_total = (float)(t4 - t0);
+  return VI_OK;
+}
+
+// vi_indexer_add_records behind its argument checks: rows, no filter
+static vi_status add_records(Indexer *ix, const uint64_t *ext_ids, const float *X, const uint64_t *timestamps, uint64_t n) {
+  const double t0 = now_ms();
+  const uint64_t n_before = ix->dev->nvec_resident;
+  std::vector<uint64_t> own_ext;  // no external ids: the internal ones
+  if (!ext_ids) {
+    own_ext.resize(n);
+    for (uint64_t i = 0; i < n; ++i) own_ext[i] = n_before + i;
+    ext_ids = own_ext.data();
+  }
+  NewRows rows;
+  UpdateStats us;
+  VI_TRY(upload_rows(ix, ext_ids, X, timestamps, n, &rows));
+  VI_TRY(update_records(ix, nullptr, &rows, t0, &us));
+  vi_add_stats as{};
+  as.n = n;
+  as.lists_touched = us.lists_touched; as.shards_rewritten = us.shards_rewritten; as.bytes_written = us.bytes_written;
+  as.kernel_bytes = us.kernel_bytes;
+  as.ms_assign = us.ms_plan; as.ms_files = us.ms_files; as.ms_index = us.ms_index; as.ms_kernel = us.ms_kernel; as.ms_total = us.ms_total;
+  ix->add_stats = as;
+  return VI_OK;
+}
+
+// vi_indexer_retain / vi_indexer_remove_ids behind their argument checks: `keep`, a filter of ix->dev, and no rows (so no
+// stream, no upload, no labelling)
+static vi_status retain_records(Indexer *ix, const SlotFilter &keep, uint64_t *removed_out) {
+  const uint64_t n_before = ix->dev->nvec_resident;
+  if (removed_out) *removed_out = 0;
+  if (keep.num_allowed > n_before) return fail(VI_ERR_OTHER, "retain: the filter admits more records than the index holds");
+  const uint64_t n_removed = n_before - keep.num_allowed;
+  if (n_removed == 0) return VI_OK;  // nothing changes: no file, no index, no filter
+  if (keep.num_allowed == 0)
+    return fail(VI_ERR_INVALID_INPUT, "the removal would leave the index without a record (an index keeps at least one; to drop it, delete its directories)");
+  const double t0 = now_ms();
+  UpdateStats us;
+  VI_TRY(update_records(ix, &keep, nullptr, t0, &us));
+  vi_remove_stats rs{};
+  rs.n_removed = n_removed;
+  rs.lists_touched = us.lists_touched; rs.lists_emptied = us.lists_emptied; rs.shards_rewritten = us.shards_rewritten;
+  rs.bytes_written = us.bytes_written; rs.kernel_bytes = us.kernel_bytes;
+  rs.ms_plan = us.ms_plan; rs.ms_files = us.ms_files; rs.ms_index = us.ms_index; rs.ms_kernel = us.ms_kernel; rs.ms_total = us.ms_total;
+  ix->remove_stats = rs;
+  if (removed_out) *removed_out = n_removed;
+  return VI_OK;
+}
+
+// vi_indexer_upsert_records behind its argument checks: rows, and the filter that denies their external ids
+static vi_status upsert_records(Indexer *ix, const uint64_t *ext_ids, const float *X, const uint64_t *timestamps, uint64_t n,
+                                uint64_t *replaced_out) {
+  const double t0 = now_ms();
+  const uint64_t n_before = ix->dev->nvec_resident;
+  NewRows rows;
+  UpdateStats us;
+  VI_TRY(upload_rows(ix, ext_ids, X, timestamps, n, &rows));
+  SlotFilter keep;  // the records a VI_IDS_DENY filter of the set admits (the ids are read from the upload)
+  VI_TRY(slot_filter_ids(*ix->dev, rows.ext_dev.p, n, true, true, &keep));
+  if (keep.num_allowed > n_before) return fail(VI_ERR_OTHER, "upsert: the filter admits more records than the index holds");
+  const uint64_t n_replaced = n_before - keep.num_allowed;
+  if (keep.num_allowed + n > 0xFFFFFFFEull) return fail(VI_ERR_INVALID_INPUT, "more than 2^32 - 2 vectors");
+  VI_TRY(update_records(ix, &keep, &rows, t0, &us));
+  vi_upsert_stats st{};
+  st.n = n;
+  st.n_replaced = n_replaced;
+  st.lists_touched = us.lists_touched; st.lists_emptied = us.lists_emptied; st.shards_rewritten = us.shards_rewritten;
+  st.bytes_written = us.bytes_written; st.kernel_bytes = us.kernel_bytes;
+  st.ms_plan = us.ms_plan; st.ms_files = us.ms_files; st.ms_index = us.ms_index; st.ms_kernel = us.ms_kernel; st.ms_total = us.ms_total;
+  ix->upsert_stats = st;
   if (replaced_out) *replaced_out = n_replaced;
   return VI_OK;
 }

@@ -1,15 +1,14 @@
 // device_index.hip — where a resident index (DeviceIndex, device_index.hpp) is constructed.
 //
-// Five routes build one (device_index.hpp names them and their callers): device_index_load and device_index_from_rows
-// here, device_index_from_order in list_build.hip, device_index_append and device_index_compact in list_update.hip.  The
-// steps they share:
+// Four routes build one (device_index.hpp names them and their callers): device_index_load and device_index_from_rows
+// here, device_index_from_order in list_build.hip, device_index_update in list_update.hip.  The steps they share:
 //   layout        plan_list_layout (list_layout.hpp): first block and local length of every list, the two 32-bit limits
 //   storage       alloc_list_storage: blocks, ids, timestamps and the per-list arrays, sized and uploaded from the layout
 //   coarse table  coarse_table_from_rows / repack_table: rows 0..n-1 into lane-interleaved blocks
-//   (layout, storage and a copied coarse table at once for the two routes that start from an older index: lay_out_from_old)
+//   (layout, storage and a copied coarse table at once for the route that starts from an older index: lay_out_from_old)
 //   ending        prepare_rank_images (rank_images.hip)
 // What fills the list blocks is each route's own: repack_kernel (shard records), repack_rows_kernel (rows of a matrix),
-// append_blocks_kernel (an older index and new rows), compact_blocks_kernel (the kept records of an older index).
+// update_blocks_kernel (the kept records of an older index and new rows).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>

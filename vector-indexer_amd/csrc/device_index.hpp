@@ -166,7 +166,7 @@ struct DeviceIndex {
   ~DeviceIndex();
 };
 
-// ---- the six routes to a resident index ----
+// ---- the four routes to a resident index ----
 // Each lays its lists out by list_layout.hpp, reserves and uploads through alloc_list_storage, builds (or copies) the
 // coarse table and ends with prepare_rank_images (search_internal.hpp, device_index.hip); what differs is where the list
 // blocks come from:
@@ -175,11 +175,9 @@ struct DeviceIndex {
 //   device_index_from_rows   (device_index.hip)  rows of a device matrix, grouped on the host: the two-level hierarchy of
 //                                                the k-means assignment (kmeans.hip)
 //   device_index_from_order  (list_build.hip)    rows of a device matrix, grouped on the device: a single-GPU build (api.cpp)
-//   device_index_append      (list_update.hip)   the blocks of an older index and new rows: vi_indexer_add_records (api.cpp)
-//   device_index_compact     (list_update.hip)   the blocks of an older index less the records a filter excludes:
-//                                                vi_indexer_retain / vi_indexer_remove_ids (api.cpp)
-//   device_index_update      (list_update.hip)   both at once, the kept records of a list followed by its new rows:
-//                                                vi_indexer_upsert_records (api.cpp)
+//   device_index_update      (list_update.hip)   the blocks of an older index, less the records a filter excludes and / or
+//                                                with new rows behind them: vi_indexer_add_records, vi_indexer_retain /
+//                                                vi_indexer_remove_ids, vi_indexer_upsert_records (api.cpp: update_records)
 //
 // Upload: centroid table + this rank's part of the lists, repacked on the GPU.  placement 0: a stripe of every list
 // (block b on rank b % world); 1: the whole lists of the shard files dealt to this rank (greedy by bytes).
@@ -202,30 +200,20 @@ vi_status device_index_from_order(int device, uint32_t dim, const float *table_h
                                   const uint32_t *order_dev, const std::vector<uint64_t> &src_off,
                                   const std::vector<uint32_t> &len, const std::vector<uint32_t> &list_shard,
                                   const uint64_t *ids_dev, const uint64_t *ts_dev, uint64_t now, DeviceIndex *out);
-// `out` = a fresh index holding the lists of `old` (unpartitioned; only read; old_len_host = a host copy of its list_len)
-// with list l followed by rows order_dev[seg[l] .. seg[l + 1]) of rows_dev (seg on the device and the host:
-// group_ids_by_label_device); row_ext_dev / row_ts_dev: external id and stored timestamp of every row.  Old blocks are
-// copied device to device, nothing comes from the shard files; old and new index coexist until the caller drops the old
-// one.  ms_kernel / kernel_bytes (optional): HIP-event time of append_blocks_kernel and the bytes it moves.
-vi_status device_index_append(const DeviceIndex &old, const std::vector<uint32_t> &old_len_host, const float *rows_dev, uint64_t n,
+// `out` = a fresh index holding, list by list, the records of `old` (unpartitioned; only read) that stay, closed up in
+// their old order, followed by the rows the list receives.  Both halves are optional:
+//   keep (a filter of `old`, or null): the records whose allow bit is 1 stay.  Null: all stay, nothing is counted or read
+//     back, and the lengths come from old_len_host (a host copy of old's list_len; not read where keep is given).
+//   n rows (or 0): list l receives rows order_dev[seg[l] .. seg[l + 1]) of rows_dev (seg on the device and the host:
+//     group_ids_by_label_device); row_ext_dev / row_ts_dev: external id and stored timestamp of every row.  n == 0: none
+//     of the six row arguments is read.
+// A list may keep nothing and receive rows, or keep nothing and receive none (it stays as an empty list).  Old blocks are
+// copied or gathered device to device, nothing comes from the shard files; old and new index coexist until the caller
+// drops the old one.  ms_kernel / kernel_bytes (optional): HIP-event time of update_blocks_kernel and the bytes it moves.
+vi_status device_index_update(const DeviceIndex &old, const SlotFilter *keep, const float *rows_dev, uint64_t n,
                               const uint32_t *order_dev, const uint32_t *seg_dev, const std::vector<uint64_t> &seg_host,
-                              const uint64_t *row_ext_dev, const uint64_t *row_ts_dev, DeviceIndex *out, float *ms_kernel,
-                              uint64_t *kernel_bytes);
-// `out` = a fresh index holding the records of `old` (unpartitioned; only read) whose allow bit in `keep` (a filter of
-// `old`) is 1: the kept records of every list close up in their old order, a list that keeps none stays as an empty list.
-// Blocks are gathered device to device, nothing comes from the shard files; old and new index coexist until the caller
-// drops the old one.  ms_kernel / kernel_bytes (optional): HIP-event time of compact_blocks_kernel and the bytes it moves.
-vi_status device_index_compact(const DeviceIndex &old, const SlotFilter &keep, DeviceIndex *out, float *ms_kernel,
-                               uint64_t *kernel_bytes);
-// `out` = a fresh index holding, list by list, the records of `old` (unpartitioned; only read) whose allow bit in `keep` (a
-// filter of `old`) is 1, closed up in their old order, followed by rows order_dev[seg[l] .. seg[l + 1]) of rows_dev (the
-// arguments of device_index_append).  A list may keep nothing and receive rows, or keep nothing and receive none (an
-// empty list).  One pass over the new blocks; old and new index coexist until the caller drops the old one.  ms_kernel /
-// kernel_bytes (optional): HIP-event time of update_blocks_kernel and the bytes it moves.
-vi_status device_index_update(const DeviceIndex &old, const SlotFilter &keep, const float *rows_dev, uint64_t n,
-                              const uint32_t *order_dev, const uint32_t *seg_dev, const std::vector<uint64_t> &seg_host,
-                              const uint64_t *row_ext_dev, const uint64_t *row_ts_dev, DeviceIndex *out, float *ms_kernel,
-                              uint64_t *kernel_bytes);
+                              const uint64_t *row_ext_dev, const uint64_t *row_ts_dev, const std::vector<uint32_t> &old_len_host,
+                              DeviceIndex *out, float *ms_kernel, uint64_t *kernel_bytes);
 
 struct SearchIO {
   const float *queries = nullptr;  // host or device (queries_on_device)
@@ -323,7 +311,7 @@ vi_status shard_export_device(const std::string &shards_dir, uint64_t shard_id, 
                               const float *X_dev, const uint32_t *order_dev, const uint64_t *ext_dev, const uint64_t *ts_dev,
                               uint64_t now, ShardExportWs &ws, hipStream_t st);
 
-// ---- appending records to a resident index (list_update.hip; device_index_append is declared with the routes above) ----
+// ---- appending records to a resident index (list_update.hip; device_index_update is declared with the routes above) ----
 // labels_dev[i] (device, n u32) = the list the reference's coarse step probes first for row i of rows_dev (device, n x dim):
 // the index's own coarse step with n_probe = 1, in chunks
 vi_status device_index_label_rows(const DeviceIndex &ix, const float *rows_dev, uint64_t n, uint32_t *labels_dev);

@@ -1,35 +1,36 @@
 // list_update.hip — the resident half of vi_indexer_add_records, of vi_indexer_retain / vi_indexer_remove_ids and of
-// vi_indexer_upsert_records: a new DeviceIndex from the blocks of the old one, without re-reading a shard file.  All routes run
+// vi_indexer_upsert_records: a new DeviceIndex from the blocks of the old one, without re-reading a shard file.  One
+// route, device_index_update, with two optional halves — what goes (a keep filter) and what joins (rows):
 //
 //   begin_update: the refusals, a fresh index on the old one's device
-//     -> the new length of every list (append: old length + rows received; compact: kept_count_kernel)
-//     -> on the host: the new layout from the new lengths, and the list of every new block (lay_out_from_old)
-//     -> one wave per NEW block, lane = vector (append_blocks_kernel / compact_blocks_kernel).  A block whose 64 positions
-//        are the records of one old block is a straight copy of it (copy_old_block).  Pad lanes get what every index
-//        upload leaves there: zero vectors, external id ~0, timestamp 0.  Every word of the new blocks / ext_ids /
-//        timestamps is written exactly once.
+//     -> the records every list keeps: with a filter, kept_count_kernel and one read-back; without, the old lengths the
+//        caller read (nothing is launched)
+//     -> on the host: new length = kept + rows received, the new layout from the new lengths, and the list of every new
+//        block (lay_out_from_old)
+//     -> one wave per NEW block, lane = vector (update_blocks_kernel).  A block whose 64 positions are the records of one
+//        old block is a straight copy of it (copy_old_block).  Pad lanes get what every index upload leaves there: zero
+//        vectors, external id ~0, timestamp 0.  Every word of the new blocks / ext_ids / timestamps is written exactly once.
 //     -> finish_update: the launch between two events, then prepare_rank_images: norms, images and the rank mode's
 //        statistics, by the code a load runs.
 //
-// Append.  The new rows (device, row-major, uploaded once) get their label from the coarse step of the old index with
+// What goes.  keep.allow holds one bit per old slot, pad slots 0.  kept_count_kernel, one wave per list: lanes stride over
+// the list's old blocks; the popcount of each block's allow word, scanned across the wave with a carry from stride to
+// stride, is the number of kept records of the list in front of the block (block_prefix) and, at the end, kept[l].  New
+// position p < kept[l] is a gather: it looks its source up, the old block by binary search over the list's block_prefix,
+// the lane inside it as the (p - prefix)-th set bit of the block's allow word.  Sources inside a wave ascend and are
+// mostly adjacent; the writes are whole rows.  No filter: kept[l] is the old length, every old record keeps its position,
+// and allow, block_prefix and kept are never read.
+//
+// What joins.  The new rows (device, row-major, uploaded once) get their label from the coarse step of the old index with
 // n_probe = 1 (device_index_label_rows: device_index_search with probes_out, in chunks) — the first probe of the
 // reference's coarse step (ivf_index.rs:205-220), whatever engine ranks it — and are grouped by label, ascending call
-// index inside a label (group_ids_by_label_device).  Positions inside a list are kept: the one block of a list where old
-// records end takes its old lanes from the old block and the others from the row-major upload (as repack_rows_kernel
-// reads it); blocks behind it are new rows only.
+// index inside a label (group_ids_by_label_device).  Position kept[l] <= p < new_len[l] reads its row from the row-major
+// upload (as repack_rows_kernel reads it).  No rows: new_len == kept everywhere, no lane is new, and rows, order, seg,
+// row_ext and row_ts are never read.
 //
-// Compact.  keep.allow holds one bit per old slot, pad slots 0.  kept_count_kernel, one wave per list: lanes stride over
-// the list's old blocks; the popcount of each block's allow word, scanned across the wave with a carry from stride to
-// stride, is the number of kept records of the list in front of the block (block_prefix) and, at the end, the list's new
-// length.  compact_blocks_kernel is a gather: new position p = 64 j + lane looks its source up, the old block by binary
-// search over the list's block_prefix, the lane inside it as the (p - prefix)-th set bit of the block's allow word.
-// Sources inside a wave ascend and are mostly adjacent; the writes are whole rows.
-//
-// Update (vi_indexer_upsert_records).  Both at once: the count pass of compact gives kept[l], the grouping of append
-// gives the rows list l receives, new_len[l] = kept[l] + received[l].  update_blocks_kernel takes position p < kept[l]
-// from the old blocks as compact does and kept[l] <= p < new_len[l] from the upload as append does.  A straight copy
-// needs a list that lost nothing AND a block of old records only: equal lengths do not mean equal positions (one record
-// out, one in).  A list may have no old block at all (an emptied list that receives rows): it never searches block_prefix.
+// A straight copy needs a list that lost nothing AND a block of old records only: equal lengths do not mean equal
+// positions (one record out, one in).  A list may have no old block at all (an emptied list that receives rows): it never
+// searches block_prefix.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -43,90 +44,15 @@ namespace vi {
 namespace {
 
 constexpr int kWave = 64;
-constexpr int kUpdateWaves = 4;            // waves per workgroup: new blocks of the two block kernels, lists of kept_count_kernel
+constexpr int kUpdateWaves = 4;            // waves per workgroup: new blocks of update_blocks_kernel, lists of kept_count_kernel
 constexpr uint64_t kLabelChunk = 65536;    // rows per coarse step
-
-// The two block kernels' arguments name what they share alike (the old index, the new layout, the new storage: filled in
-// by finish_update); each struct keeps the field order its kernel was compiled and profiled with.
-//
-// A new block that is one old block, vectors, ids and timestamps: four 1 KiB rows in flight.  src / dst: the lane's column
-// of the old / new block, old_slot / slot: its slot there.
-template <typename Args>
-__device__ __forceinline__ void copy_old_block(const Args &a, const float4 *src, float4 *dst, uint64_t old_slot, uint64_t slot) {
-  for (uint32_t qd = 0; qd < a.dq; qd += 4) {  // (dq is a multiple of 4: layout_dq)
-    const float4 t0 = src[(size_t)(qd + 0) * kWave], t1 = src[(size_t)(qd + 1) * kWave];
-    const float4 t2 = src[(size_t)(qd + 2) * kWave], t3 = src[(size_t)(qd + 3) * kWave];
-    dst[(size_t)(qd + 0) * kWave] = t0;
-    dst[(size_t)(qd + 1) * kWave] = t1;
-    dst[(size_t)(qd + 2) * kWave] = t2;
-    dst[(size_t)(qd + 3) * kWave] = t3;
-  }
-  a.ext[slot] = a.old_ext[old_slot];
-  a.ts[slot] = a.old_ts[old_slot];
-}
-
-struct AppendArgs {
-  // the old index
-  const float4 *old_blocks;
-  const uint64_t *old_ext, *old_ts;
-  const uint32_t *old_first, *old_len;     // per list
-  // the new layout
-  const uint32_t *new_first, *new_len;     // per list
-  const uint32_t *block_list;              // per new block: its list
-  uint64_t nblocks;                        // new blocks
-  // the new rows, grouped by list: list l receives rows order[seg[l] .. seg[l + 1]) in that order
-  const float *rows;                       // n x dim
-  const uint64_t *row_ext, *row_ts;        // per row, resolved on the host (never null)
-  const uint32_t *order, *seg;
-  uint32_t dim, dq;
-  float4 *blocks;
-  uint64_t *ext, *ts;
-};
-
-__global__ void __launch_bounds__(kUpdateWaves * kWave) append_blocks_kernel(AppendArgs a) {
-  const int lane = threadIdx.x & (kWave - 1);
-  const uint64_t b = (uint64_t)blockIdx.x * kUpdateWaves + (threadIdx.x >> 6);
-  if (b >= a.nblocks) return;
-  const uint32_t l = a.block_list[b];
-  const uint32_t j = (uint32_t)(b - a.new_first[l]);           // block of the list
-  const uint32_t old_len = a.old_len[l], new_len = a.new_len[l];
-  const uint32_t pos = j * kWave + lane;                       // position inside the list (new_len < 2^32 - 64)
-  const uint32_t dq = a.dq;
-  float4 *dst = a.blocks + (b * dq) * kWave + lane;
-  const uint64_t slot = b * kWave + lane;
-  const float4 *src = a.old_blocks + ((uint64_t)(a.old_first[l] + j) * dq) * kWave + lane;  // (read only where pos < old_len)
-  const uint64_t old_slot = (uint64_t)(a.old_first[l] + j) * kWave + lane;
-  if (j * kWave + (kWave - 1) < old_len) {  // all 64 positions old (wave-uniform)
-    copy_old_block(a, src, dst, old_slot, slot);
-    return;
-  }
-  const bool is_old = pos < old_len, is_new = !is_old && pos < new_len;
-  uint32_t row = 0;
-  if (is_new) row = a.order[a.seg[l] + (pos - old_len)];
-  const float *v = a.rows + (size_t)row * a.dim;
-  for (uint32_t qd = 0; qd < dq; ++qd) {
-    float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
-    const uint32_t e = qd * 4;
-    if (is_old) {
-      x = src[(size_t)qd * kWave];
-    } else if (is_new) {
-      if (e + 0 < a.dim) x.x = v[e + 0];
-      if (e + 1 < a.dim) x.y = v[e + 1];
-      if (e + 2 < a.dim) x.z = v[e + 2];
-      if (e + 3 < a.dim) x.w = v[e + 3];
-    }
-    dst[(size_t)qd * kWave] = x;
-  }
-  a.ext[slot] = is_old ? a.old_ext[old_slot] : is_new ? a.row_ext[row] : ~0ull;
-  a.ts[slot] = is_old ? a.old_ts[old_slot] : is_new ? a.row_ts[row] : 0ull;
-}
 
 struct CountArgs {
   const uint64_t *allow;                   // per old block
   const uint32_t *old_first, *old_len;     // per list
   uint32_t nlists;
   uint32_t *block_prefix;                  // per old block: kept records of its list in front of it
-  uint32_t *new_len;                       // per list
+  uint32_t *kept;                          // per list
 };
 
 __global__ void __launch_bounds__(kUpdateWaves * kWave) kept_count_kernel(CountArgs a) {
@@ -147,24 +73,46 @@ __global__ void __launch_bounds__(kUpdateWaves * kWave) kept_count_kernel(CountA
     if (b < nblk) a.block_prefix[first + b] = carry + incl - c;
     carry += __shfl(incl, kWave - 1, kWave);
   }
-  if (lane == 0) a.new_len[l] = carry;
+  if (lane == 0) a.kept[l] = carry;
 }
 
-struct CompactArgs {
-  // the old index and what is kept of it
+struct UpdateArgs {
+  // the old index
   const float4 *old_blocks;
   const uint64_t *old_ext, *old_ts;
   const uint32_t *old_first, *old_len;     // per list
+  // what is kept of it.  allow == nullptr: everything, and none of the three is read
   const uint64_t *allow;                   // per old block
   const uint32_t *block_prefix;            // per old block (kept_count_kernel)
+  const uint32_t *kept;                    // per list: kept records (kept_count_kernel)
   // the new layout
-  const uint32_t *new_first, *new_len;     // per list
+  const uint32_t *new_first, *new_len;     // per list: new_len = kept + rows received
   const uint32_t *block_list;              // per new block: its list
   uint64_t nblocks;                        // new blocks
-  uint32_t dq;
+  // the new rows, grouped by list: list l receives rows order[seg[l] .. seg[l + 1]) in that order, behind its kept records.
+  // No rows: new_len == kept, and none of the five is read
+  const float *rows;                       // n x dim
+  const uint64_t *row_ext, *row_ts;        // per row, resolved on the host
+  const uint32_t *order, *seg;
+  uint32_t dim, dq;
   float4 *blocks;
   uint64_t *ext, *ts;
 };
+
+// A new block that is one old block, vectors, ids and timestamps: four 1 KiB rows in flight.  src / dst: the lane's column
+// of the old / new block, old_slot / slot: its slot there.
+__device__ __forceinline__ void copy_old_block(const UpdateArgs &a, const float4 *src, float4 *dst, uint64_t old_slot, uint64_t slot) {
+  for (uint32_t qd = 0; qd < a.dq; qd += 4) {  // (dq is a multiple of 4: layout_dq)
+    const float4 t0 = src[(size_t)(qd + 0) * kWave], t1 = src[(size_t)(qd + 1) * kWave];
+    const float4 t2 = src[(size_t)(qd + 2) * kWave], t3 = src[(size_t)(qd + 3) * kWave];
+    dst[(size_t)(qd + 0) * kWave] = t0;
+    dst[(size_t)(qd + 1) * kWave] = t1;
+    dst[(size_t)(qd + 2) * kWave] = t2;
+    dst[(size_t)(qd + 3) * kWave] = t3;
+  }
+  a.ext[slot] = a.old_ext[old_slot];
+  a.ts[slot] = a.old_ts[old_slot];
+}
 
 // the r-th (from 0) set bit of w, which has more than r set bits: halve the word, step into the half that holds it
 __device__ __forceinline__ uint32_t nth_set_bit(uint64_t w, uint32_t r) {
@@ -177,78 +125,7 @@ __device__ __forceinline__ uint32_t nth_set_bit(uint64_t w, uint32_t r) {
   return pos;
 }
 
-__global__ void __launch_bounds__(kUpdateWaves * kWave) compact_blocks_kernel(CompactArgs a) {
-  const uint32_t lane = threadIdx.x & (kWave - 1);
-  const uint64_t b = (uint64_t)blockIdx.x * kUpdateWaves + (threadIdx.x >> 6);
-  if (b >= a.nblocks) return;
-  const uint32_t l = a.block_list[b];
-  const uint32_t j = (uint32_t)(b - a.new_first[l]);           // block of the list
-  const uint32_t old_len = a.old_len[l], new_len = a.new_len[l], old_first = a.old_first[l];
-  const uint32_t dq = a.dq;
-  float4 *dst = a.blocks + (b * dq) * kWave + lane;
-  const uint64_t slot = b * kWave + lane;
-  const bool untouched = new_len == old_len;                   // (wave-uniform) positions are the old ones
-  if (untouched && j * kWave + (kWave - 1) < new_len) {        // ... and all 64 are records
-    copy_old_block(a, a.old_blocks + ((uint64_t)(old_first + j) * dq) * kWave + lane, dst, (uint64_t)(old_first + j) * kWave + lane, slot);
-    return;
-  }
-  const uint32_t p = j * kWave + lane;                         // position inside the new list (new_len < 2^32 - 64)
-  const bool valid = p < new_len;
-  uint32_t sb = j, sl = lane;                                  // source block of the old list, lane inside it
-  if (!untouched) {
-    const uint32_t old_nblk = (old_len + kWave - 1) / kWave;   // >= 1: the list has a new block, so it had records
-    const uint32_t ps = valid ? p : 0u;                        // (pad lanes search too, and read nothing afterwards)
-    // the last old block whose prefix is <= ps: it holds kept record ps (blocks with nothing kept share the prefix of
-    // the block behind them, so they are never the last).  The trip count depends on old_nblk alone: wave-uniform.
-    uint32_t lo = 0, hi = old_nblk;
-    while (hi - lo > 1) {
-      const uint32_t mid = lo + (hi - lo) / 2;
-      if (a.block_prefix[old_first + mid] <= ps) lo = mid; else hi = mid;
-    }
-    sb = lo;
-    sl = valid ? nth_set_bit(a.allow[old_first + sb], ps - a.block_prefix[old_first + sb]) : 0u;
-  }
-  const float4 *src = a.old_blocks + ((uint64_t)(old_first + sb) * dq) * kWave + sl;  // (read only where valid)
-  const uint64_t old_slot = (uint64_t)(old_first + sb) * kWave + sl;
-  for (uint32_t qd = 0; qd < dq; qd += 4) {  // four rows in flight here too
-    float4 t0 = make_float4(0.f, 0.f, 0.f, 0.f), t1 = t0, t2 = t0, t3 = t0;
-    if (valid) {
-      t0 = src[(size_t)(qd + 0) * kWave];
-      t1 = src[(size_t)(qd + 1) * kWave];
-      t2 = src[(size_t)(qd + 2) * kWave];
-      t3 = src[(size_t)(qd + 3) * kWave];
-    }
-    dst[(size_t)(qd + 0) * kWave] = t0;
-    dst[(size_t)(qd + 1) * kWave] = t1;
-    dst[(size_t)(qd + 2) * kWave] = t2;
-    dst[(size_t)(qd + 3) * kWave] = t3;
-  }
-  a.ext[slot] = valid ? a.old_ext[old_slot] : ~0ull;
-  a.ts[slot] = valid ? a.old_ts[old_slot] : 0ull;
-}
-
-struct UpdateArgs {
-  // the old index and what is kept of it
-  const float4 *old_blocks;
-  const uint64_t *old_ext, *old_ts;
-  const uint32_t *old_first, *old_len;     // per list
-  const uint64_t *allow;                   // per old block
-  const uint32_t *block_prefix;            // per old block (kept_count_kernel)
-  const uint32_t *kept;                    // per list: kept records (kept_count_kernel)
-  // the new layout
-  const uint32_t *new_first, *new_len;     // per list: new_len = kept + rows received
-  const uint32_t *block_list;              // per new block: its list
-  uint64_t nblocks;                        // new blocks
-  // the new rows, grouped by list: list l receives rows order[seg[l] .. seg[l + 1]) in that order, behind its kept records
-  const float *rows;                       // n x dim
-  const uint64_t *row_ext, *row_ts;        // per row, resolved on the host (never null)
-  const uint32_t *order, *seg;
-  uint32_t dim, dq;
-  float4 *blocks;
-  uint64_t *ext, *ts;
-};
-
-// quad qd of a row-major row of `dim` values, zero beyond dim (as append_blocks_kernel reads the upload)
+// quad qd of a row-major row of `dim` values, zero beyond dim (as repack_rows_kernel reads an upload)
 __device__ __forceinline__ float4 row_quad(const float *v, uint32_t qd, uint32_t dim) {
   float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
   const uint32_t e = qd * 4;
@@ -259,16 +136,20 @@ __device__ __forceinline__ float4 row_quad(const float *v, uint32_t qd, uint32_t
   return x;
 }
 
-// Compact and append in one pass: new position p = 64 j + lane of list l is kept record p of the old list where
-// p < kept (the gather of compact_blocks_kernel), row order[seg[l] + p - kept] of the upload where kept <= p < new_len
-// (the read of append_blocks_kernel), a pad lane behind that.
+// New position p = 64 j + lane of list l is kept record p of the old list where p < kept (a gather where the list lost
+// records, the old position where it lost none), row order[seg[l] + p - kept] of the upload where kept <= p < new_len, a
+// pad lane behind that.  kDrops: there is a filter (else kept == old_len and allow / block_prefix / kept are not read);
+// kRows: there may be rows (else kept == new_len and rows / order / seg / row_ext / row_ts are not read).  One body, the
+// three instantiations finish_update chooses from: the two tests cost the remove route 1 % as kernel arguments (r14).
+template <bool kDrops, bool kRows>
 __global__ void __launch_bounds__(kUpdateWaves * kWave) update_blocks_kernel(UpdateArgs a) {
   const uint32_t lane = threadIdx.x & (kWave - 1);
   const uint64_t b = (uint64_t)blockIdx.x * kUpdateWaves + (threadIdx.x >> 6);
   if (b >= a.nblocks) return;
   const uint32_t l = a.block_list[b];
   const uint32_t j = (uint32_t)(b - a.new_first[l]);           // block of the list
-  const uint32_t old_len = a.old_len[l], new_len = a.new_len[l], kept = a.kept[l], old_first = a.old_first[l];
+  const uint32_t old_len = a.old_len[l], new_len = a.new_len[l], old_first = a.old_first[l];
+  const uint32_t kept = !kDrops ? old_len : !kRows ? new_len : a.kept[l];
   const uint32_t dq = a.dq;
   float4 *dst = a.blocks + (b * dq) * kWave + lane;
   const uint64_t slot = b * kWave + lane;
@@ -279,14 +160,15 @@ __global__ void __launch_bounds__(kUpdateWaves * kWave) update_blocks_kernel(Upd
     return;
   }
   const uint32_t p = j * kWave + lane;                         // position inside the new list (new_len < 2^32 - 64)
-  const bool is_old = p < kept, is_new = !is_old && p < new_len;
+  const bool is_old = p < kept, is_new = kRows && !is_old && p < new_len;
   uint32_t sb = j, sl = lane;                                  // source block of the old list, lane inside it
-  if (!lost_nothing && j * kWave < kept) {                     // (wave-uniform) the block holds kept records that moved
-    // kept < old_len here, so the list had records: old_nblk >= 1.  A list without old blocks (an emptied list that
-    // receives rows) has kept == old_len == 0 and never searches; a block of new rows only does not either.
+  if (kDrops && !lost_nothing && j * kWave < kept) {           // (wave-uniform) the block holds kept records that moved
+    // kept < old_len here, so there is a filter and the list had records: old_nblk >= 1.  A list without old blocks (an
+    // emptied list that receives rows) has kept == old_len == 0 and never searches; a block of new rows only does not either.
     const uint32_t old_nblk = (old_len + kWave - 1) / kWave;
     const uint32_t ps = is_old ? p : 0u;                       // (the other lanes search too, and read nothing afterwards)
-    // the last old block whose prefix is <= ps (compact_blocks_kernel); the trip count depends on old_nblk alone
+    // the last old block whose prefix is <= ps: it holds kept record ps (blocks with nothing kept share the prefix of
+    // the block behind them, so they are never the last).  The trip count depends on old_nblk alone: wave-uniform.
     uint32_t lo = 0, hi = old_nblk;
     while (hi - lo > 1) {
       const uint32_t mid = lo + (hi - lo) / 2;
@@ -330,7 +212,7 @@ struct EventPair {
   }
 };
 
-// What both routes begin with: the refusals (`refusal`: the route's own words for a partitioned index), a fresh index on
+// What an update begins with: the refusals (`refusal`: the call's own words for a partitioned index), a fresh index on
 // old's device with old's summation order and timing, the two out-values at zero.
 vi_status begin_update(const DeviceIndex &old, const char *refusal, DeviceIndex *ix, float *ms_kernel, uint64_t *kernel_bytes) {
   if (old.stripe_world > 1) return fail(VI_ERR_INVALID_INPUT, "%s", refusal);
@@ -343,11 +225,10 @@ vi_status begin_update(const DeviceIndex &old, const char *refusal, DeviceIndex 
   return VI_OK;
 }
 
-// ... and end with, once lay_out_from_old has run: the fields both kernels share filled in, the block kernel timed between
-// two events (one wave per new block), prepare_rank_images.
-template <typename Args>
-vi_status finish_update(const DeviceIndex &old, DeviceIndex *ix, const DevBuf<uint32_t> &block_list, void (*kernel)(Args), Args a,
-                        float *ms_kernel, uint64_t *kernel_bytes) {
+// ... and ends with, once lay_out_from_old has run: the old index, the new layout and the new storage filled in, the block
+// kernel timed between two events (one wave per new block), prepare_rank_images.
+vi_status finish_update(const DeviceIndex &old, DeviceIndex *ix, const DevBuf<uint32_t> &block_list, UpdateArgs a, float *ms_kernel,
+                        uint64_t *kernel_bytes) {
   hipStream_t st = ix->stream;
   const uint64_t total_blocks = ix->lists.nblocks;
   if (total_blocks) {
@@ -356,12 +237,15 @@ vi_status finish_update(const DeviceIndex &old, DeviceIndex *ix, const DevBuf<ui
     a.old_first = old.list_first_block.p; a.old_len = old.list_len.p;
     a.new_first = ix->list_first_block.p; a.new_len = ix->list_len.p;
     a.block_list = block_list.p; a.nblocks = total_blocks;
-    a.dq = ix->dq;
+    a.dim = ix->dim; a.dq = ix->dq;
     a.blocks = (float4 *)ix->lists.blocks.p; a.ext = ix->ext_ids.p; a.ts = ix->timestamps.p;
     EventPair ev;
     VI_HIP(hipEventCreate(&ev.a));
     VI_HIP(hipEventCreate(&ev.b));
     VI_HIP(hipEventRecord(ev.a, st));
+    // (rows without a filter, a filter without rows, both; neither — nothing changes — runs as the first: no lane is new)
+    void (*kernel)(UpdateArgs) = !a.allow ? update_blocks_kernel<false, true> : !a.rows ? update_blocks_kernel<true, false>
+                                                                                         : update_blocks_kernel<true, true>;
     hipLaunchKernelGGL(kernel, dim3((uint32_t)((total_blocks + kUpdateWaves - 1) / kUpdateWaves)), dim3(kUpdateWaves * kWave), 0, st, a);
     VI_HIP(hipGetLastError());
     VI_HIP(hipEventRecord(ev.b, st));
@@ -396,94 +280,50 @@ vi_status device_index_label_rows(const DeviceIndex &ix, const float *rows_dev, 
   return VI_OK;
 }
 
-// The index `old` with rows appended: list l receives rows order_dev[seg_host[l] .. seg_host[l + 1]) of rows_dev behind its
-// old_len_host[l] old records.  Complete on return; `old` is only read.
-vi_status device_index_append(const DeviceIndex &old, const std::vector<uint32_t> &old_len_host, const float *rows_dev, uint64_t n,
+// The index `old` without the records whose allow bit in `keep` is 0 (keep == nullptr: with all of them) and with n rows
+// appended (n == 0: with none): the kept records of list l close up in their old order, rows order_dev[seg_host[l] ..
+// seg_host[l + 1]) of rows_dev follow them.  Complete on return; `old` and `keep` are only read.
+vi_status device_index_update(const DeviceIndex &old, const SlotFilter *keep, const float *rows_dev, uint64_t n,
                               const uint32_t *order_dev, const uint32_t *seg_dev, const std::vector<uint64_t> &seg_host,
-                              const uint64_t *row_ext_dev, const uint64_t *row_ts_dev, DeviceIndex *ix, float *ms_kernel,
-                              uint64_t *kernel_bytes) {
+                              const uint64_t *row_ext_dev, const uint64_t *row_ts_dev, const std::vector<uint32_t> &old_len_host,
+                              DeviceIndex *ix, float *ms_kernel, uint64_t *kernel_bytes) {
   const uint64_t nlists = old.nlists;
-  VI_TRY(begin_update(old, "a partitioned index takes no records", ix, ms_kernel, kernel_bytes));
-  if (seg_host.size() != nlists + 1 || seg_host[nlists] != n || old_len_host.size() != nlists)
-    return fail(VI_ERR_OTHER, "append: grouping does not match the index");
-  // the new layout from the old lengths: lists back to back in list order, each padded to whole blocks (as a load lays them)
+  VI_TRY(begin_update(old, !keep ? "a partitioned index takes no records" : n == 0 ? "a partitioned index gives no records up"
+                                 : "a partitioned index takes no records and gives none up", ix, ms_kernel, kernel_bytes));
+  if (keep && keep->owner_serial != old.serial) return fail(VI_ERR_INVALID_INPUT, "the filter was made from another index");
+  if (n && (seg_host.size() != nlists + 1 || seg_host[nlists] != n)) return fail(VI_ERR_OTHER, "update: grouping does not match the index");
+  if (!keep && old_len_host.size() != nlists) return fail(VI_ERR_OTHER, "update: the list lengths do not match the index");
+  UpdateArgs a{};
+  // ---- the kept records of every list: all of them, or a count pass that also leaves those in front of every old block ----
+  DevBuf<uint32_t> block_prefix, d_kept;
+  std::vector<uint32_t> counted;
+  if (keep) {
+    VI_TRY(block_prefix.reserve(std::max<uint64_t>(1, old.lists.nblocks)));
+    VI_TRY(d_kept.reserve(std::max<uint64_t>(1, nlists)));
+    counted.resize(nlists);
+    if (nlists) {
+      hipStream_t st = ix->stream;
+      CountArgs c{keep->allow.p, old.list_first_block.p, old.list_len.p, (uint32_t)nlists, block_prefix.p, d_kept.p};
+      hipLaunchKernelGGL(kept_count_kernel, dim3((uint32_t)((nlists + kUpdateWaves - 1) / kUpdateWaves)),
+                         dim3(kUpdateWaves * kWave), 0, st, c);
+      VI_HIP(hipGetLastError());
+      VI_HIP(hipMemcpyAsync(counted.data(), d_kept.p, nlists * 4, hipMemcpyDeviceToHost, st));
+      VI_HIP(hipStreamSynchronize(st));
+    }
+    a.allow = keep->allow.p; a.block_prefix = block_prefix.p; a.kept = d_kept.p;
+  }
+  const std::vector<uint32_t> &kept = keep ? counted : old_len_host;
+  // the new layout from the new lengths: lists back to back in list order, each padded to whole blocks (as a load lays them)
   std::vector<uint64_t> full_len(nlists);
-  for (uint64_t l = 0; l < nlists; ++l) full_len[l] = (uint64_t)old_len_host[l] + (seg_host[l + 1] - seg_host[l]);
+  for (uint64_t l = 0; l < nlists; ++l) full_len[l] = (uint64_t)kept[l] + (n ? seg_host[l + 1] - seg_host[l] : 0);
   DevBuf<uint32_t> d_block_list;
   VI_TRY(lay_out_from_old(ix, old, full_len.data(), &d_block_list));  // (the new first / len are in place for the kernel)
-  AppendArgs a{};
-  a.rows = rows_dev; a.row_ext = row_ext_dev; a.row_ts = row_ts_dev;
-  a.order = order_dev; a.seg = seg_dev;
-  a.dim = ix->dim;
-  return finish_update(old, ix, d_block_list, append_blocks_kernel, a, ms_kernel, kernel_bytes);
-}
-
-// The index `old` without the records whose allow bit in `keep` is 0; the others close up in their old order.  Complete
-// on return; `old` and `keep` are only read.
-vi_status device_index_compact(const DeviceIndex &old, const SlotFilter &keep, DeviceIndex *ix, float *ms_kernel,
-                               uint64_t *kernel_bytes) {
-  const uint64_t nlists = old.nlists;
-  VI_TRY(begin_update(old, "a partitioned index gives no records up", ix, ms_kernel, kernel_bytes));
-  if (keep.owner_serial != old.serial) return fail(VI_ERR_INVALID_INPUT, "the filter was made from another index");
-  hipStream_t st = ix->stream;
-  // ---- count pass: the new length of every list, the kept records in front of every old block ----
-  DevBuf<uint32_t> block_prefix, d_new_len;
-  VI_TRY(block_prefix.reserve(std::max<uint64_t>(1, old.lists.nblocks)));
-  VI_TRY(d_new_len.reserve(std::max<uint64_t>(1, nlists)));
-  std::vector<uint32_t> n_len(nlists);
-  if (nlists) {
-    CountArgs c{keep.allow.p, old.list_first_block.p, old.list_len.p, (uint32_t)nlists, block_prefix.p, d_new_len.p};
-    hipLaunchKernelGGL(kept_count_kernel, dim3((uint32_t)((nlists + kUpdateWaves - 1) / kUpdateWaves)),
-                       dim3(kUpdateWaves * kWave), 0, st, c);
-    VI_HIP(hipGetLastError());
-    VI_HIP(hipMemcpyAsync(n_len.data(), d_new_len.p, nlists * 4, hipMemcpyDeviceToHost, st));
-    VI_HIP(hipStreamSynchronize(st));
+  if (keep && ix->nvec_resident != keep->num_allowed + n) return fail(VI_ERR_OTHER, "update: the filter's count does not match its allow words");
+  if (n) {
+    a.rows = rows_dev; a.row_ext = row_ext_dev; a.row_ts = row_ts_dev;
+    a.order = order_dev; a.seg = seg_dev;
   }
-  const std::vector<uint64_t> full_len(n_len.begin(), n_len.end());
-  DevBuf<uint32_t> d_block_list;
-  VI_TRY(lay_out_from_old(ix, old, full_len.data(), &d_block_list));
-  if (ix->nvec_resident != keep.num_allowed) return fail(VI_ERR_OTHER, "compact: the filter's count does not match its allow words");
-  CompactArgs a{};
-  a.allow = keep.allow.p; a.block_prefix = block_prefix.p;
-  return finish_update(old, ix, d_block_list, compact_blocks_kernel, a, ms_kernel, kernel_bytes);
-}
-
-// The index `old` without the records whose allow bit in `keep` is 0 and with rows appended: the kept records of list l
-// close up in their old order, rows order_dev[seg_host[l] .. seg_host[l + 1]) of rows_dev follow them.  Complete on
-// return; `old` and `keep` are only read.
-vi_status device_index_update(const DeviceIndex &old, const SlotFilter &keep, const float *rows_dev, uint64_t n,
-                              const uint32_t *order_dev, const uint32_t *seg_dev, const std::vector<uint64_t> &seg_host,
-                              const uint64_t *row_ext_dev, const uint64_t *row_ts_dev, DeviceIndex *ix, float *ms_kernel,
-                              uint64_t *kernel_bytes) {
-  const uint64_t nlists = old.nlists;
-  VI_TRY(begin_update(old, "a partitioned index takes no records and gives none up", ix, ms_kernel, kernel_bytes));
-  if (keep.owner_serial != old.serial) return fail(VI_ERR_INVALID_INPUT, "the filter was made from another index");
-  if (seg_host.size() != nlists + 1 || seg_host[nlists] != n) return fail(VI_ERR_OTHER, "update: grouping does not match the index");
-  hipStream_t st = ix->stream;
-  // ---- count pass: the kept records of every list, and those in front of every old block ----
-  DevBuf<uint32_t> block_prefix, d_kept;
-  VI_TRY(block_prefix.reserve(std::max<uint64_t>(1, old.lists.nblocks)));
-  VI_TRY(d_kept.reserve(std::max<uint64_t>(1, nlists)));
-  std::vector<uint32_t> kept(nlists);
-  if (nlists) {
-    CountArgs c{keep.allow.p, old.list_first_block.p, old.list_len.p, (uint32_t)nlists, block_prefix.p, d_kept.p};
-    hipLaunchKernelGGL(kept_count_kernel, dim3((uint32_t)((nlists + kUpdateWaves - 1) / kUpdateWaves)),
-                       dim3(kUpdateWaves * kWave), 0, st, c);
-    VI_HIP(hipGetLastError());
-    VI_HIP(hipMemcpyAsync(kept.data(), d_kept.p, nlists * 4, hipMemcpyDeviceToHost, st));
-    VI_HIP(hipStreamSynchronize(st));
-  }
-  std::vector<uint64_t> full_len(nlists);
-  for (uint64_t l = 0; l < nlists; ++l) full_len[l] = (uint64_t)kept[l] + (seg_host[l + 1] - seg_host[l]);
-  DevBuf<uint32_t> d_block_list;
-  VI_TRY(lay_out_from_old(ix, old, full_len.data(), &d_block_list));
-  if (ix->nvec_resident != keep.num_allowed + n) return fail(VI_ERR_OTHER, "update: the filter's count does not match its allow words");
-  UpdateArgs a{};
-  a.allow = keep.allow.p; a.block_prefix = block_prefix.p; a.kept = d_kept.p;
-  a.rows = rows_dev; a.row_ext = row_ext_dev; a.row_ts = row_ts_dev;
-  a.order = order_dev; a.seg = seg_dev;
-  a.dim = ix->dim;
-  return finish_update(old, ix, d_block_list, update_blocks_kernel, a, ms_kernel, kernel_bytes);
+  return finish_update(old, ix, d_block_list, a, ms_kernel, kernel_bytes);
 }
 
 }  // namespace vi

@@ -151,7 +151,7 @@ vi_status shard_image_write(const std::string &path, const uint8_t *p, uint64_t 
 }
 
 namespace {
-// the zeroed image of f's lists with other record counts, its frame written: what append and retain start from
+// the zeroed image of f's lists with other record counts, its frame written: what shard_update_write starts from
 ShardPlan image_of_file(const ShardFile &f, uint64_t shard_id, std::vector<uint64_t> counts, std::vector<uint8_t> *img) {
   const uint32_t nl = f.num_lists();
   std::vector<uint64_t> cids(nl);
@@ -185,34 +185,59 @@ vi_status shard_save_to(const std::string &shards_dir, uint64_t shard_id, uint32
   return shard_image_write(path, img.data(), pl.total, false);
 }
 
-vi_status shard_append_write(const ShardFile &f, uint64_t shard_id, uint64_t n_add, const uint64_t *centroid_ids,
-                             const uint64_t *ids, const uint64_t *ext_ids, const uint64_t *timestamps, const float *vecs,
-                             const std::string &out_path, uint64_t *bytes_out, uint64_t *lists_out) {
+vi_status shard_update_write(const ShardFile &f, uint64_t shard_id, const std::vector<const uint64_t *> &keep, uint64_t n_add,
+                             const uint64_t *centroid_ids, const uint64_t *ids, const uint64_t *ext_ids,
+                             const uint64_t *timestamps, const float *vecs, const std::string &out_path, uint64_t *bytes_out,
+                             uint64_t *removed_out, uint64_t *lists_out) {
   const uint32_t dim = f.dim(), nl = f.num_lists();
+  if (!keep.empty() && keep.size() != nl) return fail(VI_ERR_OTHER, "update: %zu keep entries for %u lists", keep.size(), nl);
+  auto words_of = [&](uint32_t i) { return keep.empty() ? nullptr : keep[i]; };  // (an empty keep: nothing goes)
+  auto stays = [](const uint64_t *w, uint32_t p) { return ((w[p >> 6] >> (p & 63u)) & 1ull) != 0; };
   // the list of every added record: the first entry with its centroid id, as the reader finds it (shards.rs:257-265)
   std::unordered_map<uint64_t, uint32_t> entry_of;
   for (uint32_t i = nl; i-- > 0;) entry_of[f.list(i).centroid_id] = i;
   std::vector<uint32_t> entry(n_add);
-  std::vector<uint64_t> counts(nl);
-  for (uint32_t i = 0; i < nl; ++i) counts[i] = f.list(i).num_vectors;
+  std::vector<uint64_t> kept(nl), received(nl, 0);
   for (uint64_t i = 0; i < n_add; ++i) {
     const auto it = entry_of.find(centroid_ids[i]);
     if (it == entry_of.end()) return fail(VI_ERR_NOT_FOUND, "Centroid %llu not found", (unsigned long long)centroid_ids[i]);
     entry[i] = it->second;
-    ++counts[it->second];
+    ++received[it->second];
   }
-  uint64_t touched = 0;
+  uint64_t removed = 0, touched = 0;
+  std::vector<uint64_t> counts(nl);
   for (uint32_t i = 0; i < nl; ++i) {
+    const uint32_t nv = f.list(i).num_vectors;
+    kept[i] = nv;
+    if (const uint64_t *w = words_of(i)) {
+      kept[i] = 0;
+      for (uint32_t p = 0; p < nv; ++p) kept[i] += stays(w, p);
+    }
+    counts[i] = kept[i] + received[i];
     if (counts[i] > 0xFFFFFFFFull) return fail(VI_ERR_INVALID_INPUT, "list %llu would pass 2^32 - 1 records", (unsigned long long)f.list(i).centroid_id);
-    touched += counts[i] != f.list(i).num_vectors;
+    removed += nv - kept[i];
+    touched += kept[i] != nv || received[i] != 0;
   }
   std::vector<uint8_t> img;
   const ShardPlan pl = image_of_file(f, shard_id, std::move(counts), &img);
-  std::vector<uint64_t> next(nl);  // where the next added record of a list goes
+  std::vector<uint64_t> next(nl);  // where the next added record of a list goes: behind its kept records
   for (uint32_t i = 0; i < nl; ++i) {
-    const uint64_t old_bytes = (uint64_t)f.list(i).num_vectors * pl.stride;
-    if (old_bytes) std::memcpy(img.data() + pl.records(i), f.list(i).records, old_bytes);  // verbatim
-    next[i] = pl.records(i) + old_bytes;
+    const ShardListView &lv = f.list(i);
+    uint8_t *o = img.data() + pl.records(i);
+    next[i] = pl.records(i) + kept[i] * pl.stride;
+    if (kept[i] == lv.num_vectors) {  // nothing lost: verbatim
+      if (lv.num_vectors) std::memcpy(o, lv.records, (uint64_t)lv.num_vectors * pl.stride);
+      continue;
+    }
+    const uint64_t *w = words_of(i);  // (not null: the list lost a record)
+    for (uint32_t v = 0; v < lv.num_vectors;) {  // runs of kept records
+      if (!stays(w, v)) { ++v; continue; }
+      uint32_t end = v + 1;
+      while (end < lv.num_vectors && stays(w, end)) ++end;
+      std::memcpy(o, lv.records + (uint64_t)v * pl.stride, (uint64_t)(end - v) * pl.stride);
+      o += (uint64_t)(end - v) * pl.stride;
+      v = end;
+    }
   }
   for (uint64_t i = 0; i < n_add; ++i) {
     put_record(img.data() + next[entry[i]], ids[i], ext_ids[i], timestamps[i], vecs + i * dim, pl.vsz);
@@ -220,61 +245,8 @@ vi_status shard_append_write(const ShardFile &f, uint64_t shard_id, uint64_t n_a
   }
   VI_TRY(shard_image_write(out_path, img.data(), pl.total, true));
   if (bytes_out) *bytes_out = pl.total;
-  if (lists_out) *lists_out = touched;
-  return VI_OK;
-}
-
-vi_status shard_append_to(const std::string &shards_dir, uint64_t shard_id, uint64_t n_add, const uint64_t *centroid_ids,
-                          const uint64_t *ids, const uint64_t *ext_ids, const uint64_t *timestamps, const float *vecs) {
-  ShardRewriteSet set(shards_dir);
-  {
-    ShardFile f;
-    VI_TRY(f.open(shards_dir, shard_id));
-    if (n_add == 0) return VI_OK;
-    uint64_t bytes = 0;
-    VI_TRY(shard_append_write(f, shard_id, n_add, centroid_ids, ids, ext_ids, timestamps, vecs, set.temporary(shard_id), &bytes, nullptr));
-    set.add(shard_id, bytes);
-  }  // (unmapped before the rename)
-  return set.commit();
-}
-
-vi_status shard_retain_write(const ShardFile &f, uint64_t shard_id, const std::vector<const uint64_t *> &keep,
-                             const std::string &out_path, uint64_t *bytes_out, uint64_t *removed_out) {
-  const uint32_t nl = f.num_lists();
-  if (keep.size() != nl) return fail(VI_ERR_OTHER, "retain: %zu keep entries for %u lists", keep.size(), nl);
-  auto stays = [](const uint64_t *w, uint32_t p) { return ((w[p >> 6] >> (p & 63u)) & 1ull) != 0; };
-  std::vector<uint64_t> kept(nl);
-  uint64_t removed = 0;
-  for (uint32_t i = 0; i < nl; ++i) {
-    const uint32_t nv = f.list(i).num_vectors;
-    kept[i] = nv;
-    if (keep[i]) {
-      kept[i] = 0;
-      for (uint32_t p = 0; p < nv; ++p) kept[i] += stays(keep[i], p);
-    }
-    removed += nv - kept[i];
-  }
-  std::vector<uint8_t> img;
-  const ShardPlan pl = image_of_file(f, shard_id, std::move(kept), &img);
-  for (uint32_t i = 0; i < nl; ++i) {
-    const ShardListView &lv = f.list(i);
-    uint8_t *o = img.data() + pl.records(i);
-    if (pl.count[i] == lv.num_vectors) {  // nothing lost: verbatim
-      if (lv.num_vectors) std::memcpy(o, lv.records, (uint64_t)lv.num_vectors * pl.stride);
-      continue;
-    }
-    for (uint32_t v = 0; v < lv.num_vectors;) {  // runs of kept records
-      if (!stays(keep[i], v)) { ++v; continue; }
-      uint32_t end = v + 1;
-      while (end < lv.num_vectors && stays(keep[i], end)) ++end;
-      std::memcpy(o, lv.records + (uint64_t)v * pl.stride, (uint64_t)(end - v) * pl.stride);
-      o += (uint64_t)(end - v) * pl.stride;
-      v = end;
-    }
-  }
-  VI_TRY(shard_image_write(out_path, img.data(), pl.total, true));
-  if (bytes_out) *bytes_out = pl.total;
   if (removed_out) *removed_out = removed;
+  if (lists_out) *lists_out = touched;
   return VI_OK;
 }
 
@@ -303,113 +275,47 @@ bool deny_words_of_file(const ShardFile &f, const uint64_t *ext_ids, uint64_t n,
   }
   return any;
 }
-}  // namespace
 
-vi_status shard_remove_from(const std::string &shards_dir, uint64_t shard_id, const uint64_t *ext_ids, uint64_t n,
-                            uint64_t *removed_out) {
+// One shard file on its own: the records that carry one of gone_ext[0..n_gone) go, n_add records join; open, write beside
+// the file under a temporary name, rename.  Nothing to go and nothing to join: the file is opened and left as it is.
+vi_status update_one_file(const std::string &shards_dir, uint64_t shard_id, const uint64_t *gone_ext, uint64_t n_gone, uint64_t n_add,
+                          const uint64_t *centroid_ids, const uint64_t *ids, const uint64_t *ext_ids, const uint64_t *timestamps,
+                          const float *vecs, uint64_t *removed_out) {
   if (removed_out) *removed_out = 0;
   ShardRewriteSet set(shards_dir);
   uint64_t removed = 0;
   {
     ShardFile f;
     VI_TRY(f.open(shards_dir, shard_id));
-    if (n == 0) return VI_OK;
     std::vector<std::vector<uint64_t>> words;
-    std::vector<const uint64_t *> keep;
-    if (!deny_words_of_file(f, ext_ids, n, &words, &keep)) return VI_OK;
+    std::vector<const uint64_t *> keep;  // (stays empty where no id is given: nothing goes)
+    const bool any_goes = n_gone && deny_words_of_file(f, gone_ext, n_gone, &words, &keep);
+    if (!any_goes && n_add == 0) return VI_OK;
     uint64_t bytes = 0;
-    VI_TRY(shard_retain_write(f, shard_id, keep, set.temporary(shard_id), &bytes, &removed));
-    set.add(shard_id, bytes);
-  }  // (unmapped before the rename)
-  VI_TRY(set.commit());
-  if (removed_out) *removed_out = removed;
-  return VI_OK;
-}
-
-vi_status shard_update_write(const ShardFile &f, uint64_t shard_id, const std::vector<const uint64_t *> &keep, uint64_t n_add,
-                             const uint64_t *centroid_ids, const uint64_t *ids, const uint64_t *ext_ids,
-                             const uint64_t *timestamps, const float *vecs, const std::string &out_path, uint64_t *bytes_out,
-                             uint64_t *removed_out, uint64_t *lists_out) {
-  const uint32_t dim = f.dim(), nl = f.num_lists();
-  if (keep.size() != nl) return fail(VI_ERR_OTHER, "update: %zu keep entries for %u lists", keep.size(), nl);
-  auto stays = [](const uint64_t *w, uint32_t p) { return ((w[p >> 6] >> (p & 63u)) & 1ull) != 0; };
-  // the list of every added record: the first entry with its centroid id, as the reader finds it (shards.rs:257-265)
-  std::unordered_map<uint64_t, uint32_t> entry_of;
-  for (uint32_t i = nl; i-- > 0;) entry_of[f.list(i).centroid_id] = i;
-  std::vector<uint32_t> entry(n_add);
-  std::vector<uint64_t> kept(nl), received(nl, 0);
-  for (uint64_t i = 0; i < n_add; ++i) {
-    const auto it = entry_of.find(centroid_ids[i]);
-    if (it == entry_of.end()) return fail(VI_ERR_NOT_FOUND, "Centroid %llu not found", (unsigned long long)centroid_ids[i]);
-    entry[i] = it->second;
-    ++received[it->second];
-  }
-  uint64_t removed = 0, touched = 0;
-  std::vector<uint64_t> counts(nl);
-  for (uint32_t i = 0; i < nl; ++i) {
-    const uint32_t nv = f.list(i).num_vectors;
-    kept[i] = nv;
-    if (keep[i]) {
-      kept[i] = 0;
-      for (uint32_t p = 0; p < nv; ++p) kept[i] += stays(keep[i], p);
-    }
-    counts[i] = kept[i] + received[i];
-    if (counts[i] > 0xFFFFFFFFull) return fail(VI_ERR_INVALID_INPUT, "list %llu would pass 2^32 - 1 records", (unsigned long long)f.list(i).centroid_id);
-    removed += nv - kept[i];
-    touched += kept[i] != nv || received[i] != 0;
-  }
-  std::vector<uint8_t> img;
-  const ShardPlan pl = image_of_file(f, shard_id, std::move(counts), &img);
-  std::vector<uint64_t> next(nl);  // where the next added record of a list goes: behind its kept records
-  for (uint32_t i = 0; i < nl; ++i) {
-    const ShardListView &lv = f.list(i);
-    uint8_t *o = img.data() + pl.records(i);
-    next[i] = pl.records(i) + kept[i] * pl.stride;
-    if (kept[i] == lv.num_vectors) {  // nothing lost: verbatim
-      if (lv.num_vectors) std::memcpy(o, lv.records, (uint64_t)lv.num_vectors * pl.stride);
-      continue;
-    }
-    for (uint32_t v = 0; v < lv.num_vectors;) {  // runs of kept records
-      if (!stays(keep[i], v)) { ++v; continue; }
-      uint32_t end = v + 1;
-      while (end < lv.num_vectors && stays(keep[i], end)) ++end;
-      std::memcpy(o, lv.records + (uint64_t)v * pl.stride, (uint64_t)(end - v) * pl.stride);
-      o += (uint64_t)(end - v) * pl.stride;
-      v = end;
-    }
-  }
-  for (uint64_t i = 0; i < n_add; ++i) {
-    put_record(img.data() + next[entry[i]], ids[i], ext_ids[i], timestamps[i], vecs + i * dim, pl.vsz);
-    next[entry[i]] += pl.stride;
-  }
-  VI_TRY(shard_image_write(out_path, img.data(), pl.total, true));
-  if (bytes_out) *bytes_out = pl.total;
-  if (removed_out) *removed_out = removed;
-  if (lists_out) *lists_out = touched;
-  return VI_OK;
-}
-
-vi_status shard_upsert_to(const std::string &shards_dir, uint64_t shard_id, uint64_t n, const uint64_t *centroid_ids,
-                          const uint64_t *ids, const uint64_t *ext_ids, const uint64_t *timestamps, const float *vecs,
-                          uint64_t *removed_out) {
-  if (removed_out) *removed_out = 0;
-  ShardRewriteSet set(shards_dir);
-  uint64_t removed = 0;
-  {
-    ShardFile f;
-    VI_TRY(f.open(shards_dir, shard_id));
-    if (n == 0) return VI_OK;
-    std::vector<std::vector<uint64_t>> words;
-    std::vector<const uint64_t *> keep;
-    (void)deny_words_of_file(f, ext_ids, n, &words, &keep);  // (nothing goes: the append alone)
-    uint64_t bytes = 0;
-    VI_TRY(shard_update_write(f, shard_id, keep, n, centroid_ids, ids, ext_ids, timestamps, vecs, set.temporary(shard_id), &bytes,
+    VI_TRY(shard_update_write(f, shard_id, keep, n_add, centroid_ids, ids, ext_ids, timestamps, vecs, set.temporary(shard_id), &bytes,
                               &removed, nullptr));
     set.add(shard_id, bytes);
   }  // (unmapped before the rename)
   VI_TRY(set.commit());
   if (removed_out) *removed_out = removed;
   return VI_OK;
+}
+}  // namespace
+
+vi_status shard_append_to(const std::string &shards_dir, uint64_t shard_id, uint64_t n_add, const uint64_t *centroid_ids,
+                          const uint64_t *ids, const uint64_t *ext_ids, const uint64_t *timestamps, const float *vecs) {
+  return update_one_file(shards_dir, shard_id, nullptr, 0, n_add, centroid_ids, ids, ext_ids, timestamps, vecs, nullptr);
+}
+
+vi_status shard_remove_from(const std::string &shards_dir, uint64_t shard_id, const uint64_t *ext_ids, uint64_t n,
+                            uint64_t *removed_out) {
+  return update_one_file(shards_dir, shard_id, ext_ids, n, 0, nullptr, nullptr, nullptr, nullptr, nullptr, removed_out);
+}
+
+vi_status shard_upsert_to(const std::string &shards_dir, uint64_t shard_id, uint64_t n, const uint64_t *centroid_ids,
+                          const uint64_t *ids, const uint64_t *ext_ids, const uint64_t *timestamps, const float *vecs,
+                          uint64_t *removed_out) {
+  return update_one_file(shards_dir, shard_id, ext_ids, n, n, centroid_ids, ids, ext_ids, timestamps, vecs, removed_out);
 }
 
 // ---- the rewrite set ------------------------------------------------------------------------

@@ -75,48 +75,32 @@ vi_status shard_save_to(const std::string &shards_dir, uint64_t shard_id, uint32
                         const uint64_t *list_off, const uint64_t *ids, const uint64_t *ext_ids,
                         const uint64_t *timestamps, const float *vecs);
 
-// Append records to lists of an open shard file: added record i goes to the FIRST list of the file that carries
-// centroid_ids[i], behind the list's old records and behind the added records named before it.  The merged file is
-// written to out_path — byte-identical to shard_save_to of the merged lists, the old records and centroid vectors copied
-// verbatim — and f's own file is left alone: the caller renames out_path over it when every file of its batch is
-// complete (api.cpp: vi_indexer_add_records).  A centroid id the file does not hold: NotFound, nothing written.
-// bytes_out / lists_out (optional): size of the file written, lists that received records.
-vi_status shard_append_write(const ShardFile &f, uint64_t shard_id, uint64_t n_add, const uint64_t *centroid_ids,
-                             const uint64_t *ids, const uint64_t *ext_ids, const uint64_t *timestamps, const float *vecs,
-                             const std::string &out_path, uint64_t *bytes_out, uint64_t *lists_out);
-// ... for one shard file on its own: open, write beside it under a temporary name, rename.  n_add == 0: the file is
-// opened (the reader's errors) and left as it is.
-vi_status shard_append_to(const std::string &shards_dir, uint64_t shard_id, uint64_t n_add, const uint64_t *centroid_ids,
-                          const uint64_t *ids, const uint64_t *ext_ids, const uint64_t *timestamps, const float *vecs);
-
-// Remove records from lists of an open shard file.  keep[i] belongs to list entry i of the file (file order; keep has
-// num_lists() entries): null = every record of the list stays, else record p stays iff bit p % 64 of word p / 64 is set
-// (ceil(num_vectors / 64) words: the allow words of a SlotFilter over the list's blocks).  The file of the remaining lists
-// is written to out_path — byte-identical to shard_save_to of them: lists keep their file order, centroid vectors and
-// kept records are copied verbatim (VectorMeta.id included), a list that keeps nothing stays as an entry with
-// num_vectors == 0 — and f's own file is left alone: the caller renames.  bytes_out / removed_out (optional): size of the
-// file written, records removed.
-vi_status shard_retain_write(const ShardFile &f, uint64_t shard_id, const std::vector<const uint64_t *> &keep,
-                             const std::string &out_path, uint64_t *bytes_out, uint64_t *removed_out);
-// ... for one shard file on its own, by external id: every record whose external id is one of ext_ids[0..n) goes (any
-// order, duplicates allowed, unknown ids ignored; of entries that repeat a centroid id only the first, the one a reader
-// finds, is looked at).  Open, write beside the file under a temporary name, rename; nothing matches: the file is opened
-// (the reader's errors) and left as it is.
-vi_status shard_remove_from(const std::string &shards_dir, uint64_t shard_id, const uint64_t *ext_ids, uint64_t n,
-                            uint64_t *removed_out);
-
-// Remove and append in one image: `keep` as for shard_retain_write, the add arguments as for shard_append_write.  The
-// kept records of every list are copied verbatim, in runs, and the added records of the list go behind them in call
-// order.  Written to out_path, byte-identical to shard_retain_write followed by shard_append_write; f's own file is left
-// alone.  A centroid id the file does not hold: NotFound, nothing written.  bytes_out / removed_out / lists_out
+// Remove records from lists of an open shard file and append records to them, in one image.
+//   keep: what goes.  Either empty — nothing goes, the same as num_lists() null entries — or one entry per list entry of
+//     the file, in file order: null = every record of the list stays, else record p stays iff bit p % 64 of word p / 64
+//     is set (ceil(num_vectors / 64) words: the allow words of a SlotFilter over the list's blocks).
+//   n_add records: what joins; 0 = nothing is appended and none of the five arrays is read.  Added record i goes to the FIRST
+//     list of the file that carries centroid_ids[i], behind the list's kept records and behind the added records named
+//     before it.  A centroid id the file does not hold: NotFound, nothing written.
+// The file is written to out_path — byte-identical to shard_save_to of the resulting lists: lists keep their file order,
+// centroid vectors and kept records are copied verbatim, in runs (VectorMeta.id included), a list that keeps nothing and
+// receives nothing stays as an entry with num_vectors == 0 — and f's own file is left alone: the caller renames out_path
+// over it when every file of its batch is complete (api.cpp: update_records).  bytes_out / removed_out / lists_out
 // (optional): size of the file written, records removed, lists that lost or received a record.
 vi_status shard_update_write(const ShardFile &f, uint64_t shard_id, const std::vector<const uint64_t *> &keep, uint64_t n_add,
                              const uint64_t *centroid_ids, const uint64_t *ids, const uint64_t *ext_ids,
                              const uint64_t *timestamps, const float *vecs, const std::string &out_path, uint64_t *bytes_out,
                              uint64_t *removed_out, uint64_t *lists_out);
-// ... for one shard file on its own: every record whose external id is one of ext_ids[0..n) goes (the rules of
-// shard_remove_from), then record i goes to the list of centroid_ids[i] (the rules of shard_append_to).  Open, write
-// beside the file under a temporary name, rename.  n == 0: the file is opened (the reader's errors) and left as it is.
+// The same for one shard file on its own: open, write beside it under a temporary name, rename.
+// shard_append_to: nothing goes.  n_add == 0: the file is opened (the reader's errors) and left as it is.
+vi_status shard_append_to(const std::string &shards_dir, uint64_t shard_id, uint64_t n_add, const uint64_t *centroid_ids,
+                          const uint64_t *ids, const uint64_t *ext_ids, const uint64_t *timestamps, const float *vecs);
+// shard_remove_from: nothing joins; every record whose external id is one of ext_ids[0..n) goes (any order, duplicates
+// allowed, unknown ids ignored; of entries that repeat a centroid id only the first, the one a reader finds, is looked
+// at).  Nothing matches: the file is opened and left as it is.
+vi_status shard_remove_from(const std::string &shards_dir, uint64_t shard_id, const uint64_t *ext_ids, uint64_t n,
+                            uint64_t *removed_out);
+// shard_upsert_to: both, the ids that go being those of the records that join.  n == 0: the file is opened and left as it is.
 vi_status shard_upsert_to(const std::string &shards_dir, uint64_t shard_id, uint64_t n, const uint64_t *centroid_ids,
                           const uint64_t *ids, const uint64_t *ext_ids, const uint64_t *timestamps, const float *vecs,
                           uint64_t *removed_out);
