@@ -468,6 +468,43 @@ vi_status vi_shard_upsert_to(const char *shards_dir, uint64_t shard_id, uint64_t
                              const uint64_t *ids, const uint64_t *ext_ids, const uint64_t *timestamps, const float *vecs,
                              uint64_t *removed_out);
 
+/* ---- extension (the reference reads a stored vector only through include_vectors, api.rs:213-217): read records back from
+ * a built or loaded index: by external id, or a range of all of them in list order ----
+ * LIST ORDER: the resident records ordered by list index ascending (the row of vi_indexer_centroids = the centroid_id of
+ * the shard files), then by position in the list ascending (the record's place in its list in the shard file, which is
+ * the reference's candidate order inside a list).  where = (list index << 32) | position in the FULL list.
+ * vi_indexer_get_records, per requested id i:
+ *   - count_out[i]: the resident records whose external id equals ext_ids[i]; 0: absent
+ *   - values_out[i, 0..dim) (the stored f32 bits), timestamps_out[i], where_out[i]: the FIRST such record in list order
+ *   - an absent id: a zero-filled row, timestamp 0, where VI_WHERE_NONE, and the call still returns VI_OK
+ *   - the request needs no order and may repeat ids; every row is filled, a repeated id's included; any u64 is an id
+ *   - any of the four outputs may be NULL, which skips that work: with values_out == NULL nothing is gathered and the call
+ *     is "contains / how many"
+ *   - n == 0: VI_OK, nothing is read or written
+ * vi_indexer_export_records: records [first, first + count) of the list order; row j of every output is record first + j.
+ *   first + count > vi_indexer_num_vectors: VI_ERR_INVALID_INPUT; count == 0: VI_OK; outputs may be NULL, as above.
+ * The _device forms take and fill device pointers (ids, counts u32, values f32 row-major n x dim, timestamps, where).
+ *   - on a partitioned handle (world_size > 1, both placements) both calls cover the resident records of this rank in
+ *     its local list order; where still carries the position in the full list (a stripe's local position p is
+ *     ((p / 64) * world + rank) * 64 + p % 64 there), so per-rank answers combine by the lowest where and the sum of counts
+ *   - VectorMeta.id (the internal id) is not resident and is not returned
+ *   - the result is the caller's memory: it stays valid across later updates of the handle
+ *   - threads: the contract of a search: const on the handle, any number of gets, exports and searches at once (each
+ *     holds a stream of its own), none of them overlapping an update (add / remove / upsert / build)
+ *   - cost: there is no persistent id -> slot map: every get reads the 8-byte external id of every resident slot once
+ *     (a hash table of the REQUESTED ids is probed with them), then gathers n rows; an export reads each block once
+ *   - errors, all VI_ERR_INVALID_INPUT before any device work: a null ix, ext_ids == NULL with n > 0, a handle with no
+ *     index, n past 2^40.  Any other failure is VI_ERR_DEVICE, the outputs unspecified. */
+#define VI_WHERE_NONE UINT64_MAX
+vi_status vi_indexer_get_records(const vi_indexer *ix, const uint64_t *ext_ids, uint64_t n, uint32_t *count_out,
+                                 float *values_out, uint64_t *timestamps_out, uint64_t *where_out);
+vi_status vi_indexer_get_records_device(const vi_indexer *ix, const uint64_t *ext_ids_dev, uint64_t n, uint32_t *count_dev,
+                                        float *values_dev, uint64_t *timestamps_dev, uint64_t *where_dev);
+vi_status vi_indexer_export_records(const vi_indexer *ix, uint64_t first, uint64_t count, uint64_t *ext_ids_out,
+                                    float *values_out, uint64_t *timestamps_out, uint64_t *where_out);
+vi_status vi_indexer_export_records_device(const vi_indexer *ix, uint64_t first, uint64_t count, uint64_t *ext_ids_dev,
+                                           float *values_dev, uint64_t *timestamps_dev, uint64_t *where_dev);
+
 /* ---- extension: radius (range) search -----------------------------------------------------------------------------
  * Every candidate of the probed lists whose squared distance is at most radius2.  The result of a query is the
  * reference's candidate sequence (probed lists in shard visiting order, then probe rank, then list position) after the
@@ -594,6 +631,19 @@ typedef struct vi_upsert_stats {
   uint64_t kernel_bytes;     /* ... and the bytes it read and wrote */
 } vi_upsert_stats;
 vi_status vi_indexer_last_upsert_stats(const vi_indexer *ix, vi_upsert_stats *out);
+/* the most recent vi_indexer_get_records* / vi_indexer_export_records* on this handle (n > 0 / count > 0).  The ms_* are
+ * HIP-event times on the call's stream, non-zero only under vi_indexer_enable_timing; an export has no table and no match */
+typedef struct vi_fetch_stats {
+  uint64_t n;             /* ids requested / records exported */
+  uint64_t n_found;       /* requested ids (repeats counted) that a resident record carries / records exported */
+  uint64_t slots_scanned; /* get: resident records whose external id was probed; export: slots of the blocks read */
+  uint64_t bytes_moved;   /* device bytes the kernels read and wrote (the request, the scan, the rows in and out) */
+  float ms_total;
+  float ms_table;         /* get: clearing the id table and inserting the request */
+  float ms_match;         /* get: fetch_match_kernel, the scan of the resident external ids */
+  float ms_gather;        /* get: fetch_resolve_gather_kernel; export: export_blocks_kernel */
+} vi_fetch_stats;
+vi_status vi_indexer_last_fetch_stats(const vi_indexer *ix, vi_fetch_stats *out);
 
 /* stats of the most recent search on this handle (timing collected only if enabled) */
 vi_status vi_indexer_last_stats(const vi_indexer *ix, vi_search_stats *out);

@@ -15,6 +15,7 @@
 #include "device_index.hpp"
 #include "kmeans.hpp"
 #include "list_layout.hpp"
+#include "record_fetch.hpp"
 #include "rng.hpp"
 #include "shards.hpp"
 #include "slot_filter.hpp"
@@ -784,6 +785,62 @@ vi_status vi_shard_upsert_to(const char *shards_dir, uint64_t shard_id, uint64_t
   if (!shards_dir) return fail(VI_ERR_INVALID_INPUT, "null pointer");
   if (n && (!centroid_ids || !ids || !ext_ids || !timestamps || !vecs)) return fail(VI_ERR_INVALID_INPUT, "null pointer");
   return vi::shard_upsert_to(shards_dir, shard_id, n, centroid_ids, ids, ext_ids, timestamps, vecs, removed_out);
+  });
+}
+
+// ---- reading records back (record_fetch.hip) ----
+static vi_status get_records_common(const vi_indexer *ix, const uint64_t *ids, uint64_t n, bool on_device, uint32_t *count,
+                                    float *values, uint64_t *timestamps, uint64_t *where) {
+  return vi::guarded([&]() -> vi_status {
+  if (!ix) return fail(VI_ERR_INVALID_INPUT, "null indexer");
+  if (n && !ids) return fail(VI_ERR_INVALID_INPUT, "null id set with n = %llu", (unsigned long long)n);
+  if (!ix->impl.dev) return fail(VI_ERR_INVALID_INPUT, "the indexer holds no index (build or load it first)");
+  if (n > (1ull << 40)) return fail(VI_ERR_INVALID_INPUT, "id set of %llu ids is too large", (unsigned long long)n);
+  if (n == 0) return VI_OK;  // nothing is read or written
+  return vi::fetch_records_by_id(*ix->impl.dev, ids, n, on_device, count, values, timestamps, where);
+  });
+}
+
+vi_status vi_indexer_get_records(const vi_indexer *ix, const uint64_t *ext_ids, uint64_t n, uint32_t *count_out,
+                                 float *values_out, uint64_t *timestamps_out, uint64_t *where_out) {
+  return get_records_common(ix, ext_ids, n, false, count_out, values_out, timestamps_out, where_out);
+}
+
+vi_status vi_indexer_get_records_device(const vi_indexer *ix, const uint64_t *ext_ids_dev, uint64_t n, uint32_t *count_dev,
+                                        float *values_dev, uint64_t *timestamps_dev, uint64_t *where_dev) {
+  return get_records_common(ix, ext_ids_dev, n, true, count_dev, values_dev, timestamps_dev, where_dev);
+}
+
+static vi_status export_records_common(const vi_indexer *ix, uint64_t first, uint64_t count, bool on_device, uint64_t *ext_ids,
+                                       float *values, uint64_t *timestamps, uint64_t *where) {
+  return vi::guarded([&]() -> vi_status {
+  if (!ix) return fail(VI_ERR_INVALID_INPUT, "null indexer");
+  if (!ix->impl.dev) return fail(VI_ERR_INVALID_INPUT, "the indexer holds no index (build or load it first)");
+  const uint64_t nvec = ix->impl.dev->nvec_resident;
+  if (first > nvec || count > nvec - first)
+    return fail(VI_ERR_INVALID_INPUT, "records [%llu, %llu + %llu) of %llu resident records", (unsigned long long)first,
+                (unsigned long long)first, (unsigned long long)count, (unsigned long long)nvec);
+  if (count == 0) return VI_OK;
+  return vi::export_records(*ix->impl.dev, first, count, on_device, ext_ids, values, timestamps, where);
+  });
+}
+
+vi_status vi_indexer_export_records(const vi_indexer *ix, uint64_t first, uint64_t count, uint64_t *ext_ids_out,
+                                    float *values_out, uint64_t *timestamps_out, uint64_t *where_out) {
+  return export_records_common(ix, first, count, false, ext_ids_out, values_out, timestamps_out, where_out);
+}
+
+vi_status vi_indexer_export_records_device(const vi_indexer *ix, uint64_t first, uint64_t count, uint64_t *ext_ids_dev,
+                                           float *values_dev, uint64_t *timestamps_dev, uint64_t *where_dev) {
+  return export_records_common(ix, first, count, true, ext_ids_dev, values_dev, timestamps_dev, where_dev);
+}
+
+vi_status vi_indexer_last_fetch_stats(const vi_indexer *ix, vi_fetch_stats *out) {
+  return vi::guarded([&]() -> vi_status {
+  if (!ix || !out || !ix->impl.dev) return fail(VI_ERR_INVALID_INPUT, "no stats");
+  std::lock_guard<std::mutex> lock(ix->impl.dev->fetch.mu);
+  *out = ix->impl.dev->fetch.last;
+  return VI_OK;
   });
 }
 

@@ -94,6 +94,41 @@ struct SearchWorkspace {
   DevBuf<uint32_t> range_bound;             // radius search: per query an upper bound of its hits (+ one flag word)
 };
 
+// ---- reading records back (record_fetch.hip) ----
+// A get or an export holds one FetchContext for the duration of the call, as a search holds a SearchContext: its own
+// stream and events, the id table of a get and the staging of host outputs, all grow-only.  Up to kFetchContexts calls
+// run at once on one handle, further callers wait for a free one.
+struct FetchContext {
+  hipStream_t stream = nullptr;
+  hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  DevBuf<unsigned long long> words;    // id table: [capacity] keys ...
+  DevBuf<uint32_t> first_slot, count;  // ... and [capacity + 1] values: lowest slot that carries the key, records that do
+  DevBuf<uint32_t> flags;              // IdTable::flags, then [2..3] one u64: requests that found a record
+  DevBuf<uint64_t> upload;             // host ids on the device
+  DevBuf<uint32_t> out_count;          // host outputs are produced here and copied back
+  DevBuf<float> out_values;
+  DevBuf<uint64_t> out_ids, out_ts, out_where;
+  ~FetchContext() {
+    for (auto &e : ev)
+      if (e) (void)hipEventDestroy(e);
+    if (stream) (void)hipStreamDestroy(stream);
+  }
+};
+struct FetchState {
+  static constexpr int kFetchContexts = 4;
+  std::mutex mu;  // guards everything below
+  std::condition_variable cv;
+  std::vector<std::unique_ptr<FetchContext>> contexts;  // created on demand
+  std::vector<FetchContext *> free_contexts;
+  vi_fetch_stats last{};  // of the most recent get or export that finished on this handle
+  // the layout of the (immutable) index, read back by the first export: first block, length and the exclusive prefix
+  // of the lengths (= list-order ordinal of a list's first record), on the host and the prefix on the device too
+  bool layout_ready = false;
+  std::vector<uint32_t> h_first, h_len;
+  std::vector<uint64_t> h_prefix;  // [nlists + 1]
+  DevBuf<uint64_t> prefix;         // [nlists]
+};
+
 inline uint64_t next_index_serial() {
   static std::atomic<uint64_t> n{0};
   return ++n;
@@ -162,6 +197,7 @@ struct DeviceIndex {
   mutable vi_search_stats last_stats{};  // of the most recent search that finished on this handle
   SearchContext &cur() const;         // the context the calling thread holds (device_index_search acquired it)
   int timing = 0;  // 0 off, 1 HIP events at every phase boundary, 2 around the list-rank kernel only
+  mutable FetchState fetch;  // gets and exports: const on the index, like searches
 
   ~DeviceIndex();
 };

@@ -1,0 +1,66 @@
+// id_table.hpp — a set of u64 ids as an open-addressing table on the device: power-of-two capacity, linear probing,
+// kEmptyKey = free word.  The id that equals kEmptyKey cannot be a key: whether the set holds it is a flag word of its
+// own, and its entry number is `capacity`, one past the words.  Used by the id filters (slot_filter.hip) and by the
+// record fetch (record_fetch.hip), which keeps value arrays of capacity + 1 entries beside the words.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+namespace vi {
+
+constexpr uint64_t kEmptyKey = ~0ull;
+constexpr uint64_t kNoEntry = ~0ull;  // id_table_find: the set does not hold the id
+
+__device__ __forceinline__ uint64_t mix_id(uint64_t x) {  // splitmix64's finalizer: every id bit reaches every index bit
+  x ^= x >> 30; x *= 0xbf58476d1ce4e5b9ull;
+  x ^= x >> 27; x *= 0x94d049bb133111ebull;
+  return x ^ (x >> 31);
+}
+
+struct IdTable {
+  unsigned long long *words;  // [capacity]
+  uint64_t mask;              // capacity - 1
+  uint32_t *flags;            // [0]: the set holds kEmptyKey   [1]: an insert found no free word (cannot happen: load <= 0.5)
+};
+
+// power of two >= 2 max(n, 1): load factor <= 0.5
+inline uint64_t id_table_capacity(uint64_t n) {
+  uint64_t capacity = 2;
+  while (capacity < 2 * n) capacity <<= 1;
+  return capacity;
+}
+
+// One thread per id of the set.  A duplicate meets its own key and is done.  The probe loop ends after `capacity` words
+// whatever the table holds.
+static __global__ void __launch_bounds__(256) id_table_insert_kernel(IdTable t, const uint64_t *ids, uint64_t n) {
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+    const uint64_t id = ids[i];
+    if (id == kEmptyKey) {
+      t.flags[0] = 1u;
+      continue;
+    }
+    uint64_t h = mix_id(id) & t.mask;
+    bool done = false;
+    for (uint64_t probe = 0; probe <= t.mask && !done; ++probe, h = (h + 1) & t.mask) {
+      const unsigned long long prev = atomicCAS(&t.words[h], (unsigned long long)kEmptyKey, (unsigned long long)id);
+      done = prev == kEmptyKey || prev == id;
+    }
+    if (!done) t.flags[1] = 1u;
+  }
+}
+
+// the entry of `id` in a complete table (the insert kernel ran before on the stream): its word's index, `capacity` for
+// kEmptyKey, kNoEntry when the set does not hold it
+__device__ __forceinline__ uint64_t id_table_find(const IdTable &t, uint64_t id) {
+  if (id == kEmptyKey) return t.flags[0] != 0u ? t.mask + 1 : kNoEntry;
+  uint64_t h = mix_id(id) & t.mask;
+  for (uint64_t probe = 0; probe <= t.mask; ++probe, h = (h + 1) & t.mask) {
+    const uint64_t w = t.words[h];
+    if (w == id) return h;
+    if (w == kEmptyKey) break;
+  }
+  return kNoEntry;
+}
+
+}  // namespace vi

@@ -26,6 +26,29 @@ inline uint64_t local_len(uint64_t n, uint32_t world, uint32_t rank) {
   return (lb - 1) * kListBlock + (last == nb - 1 ? n - last * kListBlock : kListBlock);
 }
 
+// ---- reading a layout back (record_fetch.hip and tests/record_order_check.cpp share these two) ----
+#if defined(__HIP__) || defined(__HIPCC__)
+#define VI_LAYOUT_HD __host__ __device__
+#else
+#define VI_LAYOUT_HD
+#endif
+
+// the list position of local position p on rank `rank` of `world` (1, 0: the identity).  Monotone in p: a rank's local
+// order of a list is its order in the full list.
+VI_LAYOUT_HD inline uint64_t full_position(uint64_t p, uint32_t world, uint32_t rank) {
+  return ((p / kListBlock) * world + rank) * kListBlock + p % kListBlock;
+}
+// the list that owns resident block `block` (block < total_blocks, nlists >= 1): a list without blocks here shares its
+// `first` with the next list, so the owner is the LAST list with first[l] <= block
+VI_LAYOUT_HD inline uint32_t list_of_block(const uint32_t *first, uint32_t nlists, uint32_t block) {
+  uint32_t lo = 0, hi = nlists;  // first[lo] <= block < first[hi], with first[nlists] read as +infinity
+  while (hi - lo > 1) {
+    const uint32_t mid = lo + (hi - lo) / 2;
+    if (first[mid] <= block) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+
 struct ListLayout {
   std::vector<uint32_t> first, len;  // per list: its first block, its local length
   uint64_t total_blocks = 0, total_vec = 0;

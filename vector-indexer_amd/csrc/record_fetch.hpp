@@ -1,0 +1,24 @@
+// record_fetch.hpp — reading records back from a resident index (record_fetch.hip): by external id, or a range of all of
+// them in list order.  The contract is vi_indexer_get_records / vi_indexer_export_records in include/vi_amd.h.
+//
+// List order is the order the slots already lie in: lists back to back in list order, positions ascending inside a list,
+// pad slots skipped.  So "the first record in list order" is the lowest slot, on a striped rank too (full_position,
+// list_layout.hpp, is monotone in the local position).
+#pragma once
+#include <cstdint>
+
+#include "common.hpp"
+
+namespace vi {
+
+struct DeviceIndex;
+
+// Both are const on the index: they hold a FetchContext of it (device_index.hpp), never ix.stream.  on_device: the ids
+// and every output are device pointers; otherwise host pointers, staged through the context.  Any output may be null.
+// Arguments are checked by the caller (api.cpp); n > 0 / count > 0.
+vi_status fetch_records_by_id(const DeviceIndex &ix, const uint64_t *ids, uint64_t n, bool on_device, uint32_t *count,
+                              float *values, uint64_t *timestamps, uint64_t *where);
+vi_status export_records(const DeviceIndex &ix, uint64_t first, uint64_t count, bool on_device, uint64_t *ext_ids,
+                         float *values, uint64_t *timestamps, uint64_t *where);
+
+}  // namespace vi

@@ -5,6 +5,7 @@
 #include <algorithm>
 
 #include "device_index.hpp"
+#include "id_table.hpp"
 #include "rank_stream.hpp"
 #include "slot_filter.hpp"
 
@@ -56,59 +57,13 @@ struct TimestampPred {
   }
 };
 
-// ---- a set of u64 ids as an open-addressing table: power-of-two capacity, linear probing, kEmptyKey = free word.  The id
-// that equals kEmptyKey cannot be a key: whether the set holds it is a flag word of its own.
-constexpr uint64_t kEmptyKey = ~0ull;
-
-__device__ __forceinline__ uint64_t mix_id(uint64_t x) {  // splitmix64's finalizer: every id bit reaches every index bit
-  x ^= x >> 30; x *= 0xbf58476d1ce4e5b9ull;
-  x ^= x >> 27; x *= 0x94d049bb133111ebull;
-  return x ^ (x >> 31);
-}
-
-struct IdTable {
-  unsigned long long *words;  // [capacity]
-  uint64_t mask;              // capacity - 1
-  uint32_t *flags;            // [0]: the set holds kEmptyKey   [1]: an insert found no free word (cannot happen: load <= 0.5)
-};
-
-// One thread per id of the set.  A duplicate meets its own key and is done.  The probe loop ends after `capacity` words
-// whatever the table holds.
-__global__ void __launch_bounds__(256) id_table_insert_kernel(IdTable t, const uint64_t *ids, uint64_t n) {
-  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
-    const uint64_t id = ids[i];
-    if (id == kEmptyKey) {
-      t.flags[0] = 1u;
-      continue;
-    }
-    uint64_t h = mix_id(id) & t.mask;
-    bool done = false;
-    for (uint64_t probe = 0; probe <= t.mask && !done; ++probe, h = (h + 1) & t.mask) {
-      const unsigned long long prev = atomicCAS(&t.words[h], (unsigned long long)kEmptyKey, (unsigned long long)id);
-      done = prev == kEmptyKey || prev == id;
-    }
-    if (!done) t.flags[1] = 1u;
-  }
-}
-
-// allow = (external id is in the table) != exclude; the table is complete (the insert kernel ran before on the stream)
+// allow = (external id is in the table, id_table.hpp) != exclude; the table is complete (the insert kernel ran before on the stream)
 struct IdPred {
   const uint64_t *ext_ids;
   IdTable t;
   bool exclude;
   __device__ bool operator()(uint32_t block, uint32_t lane, bool resident) const {
-    const uint64_t id = ext_ids[(size_t)block * kWave + lane];
-    bool member = false;
-    if (id == kEmptyKey) {
-      member = t.flags[0] != 0u;
-    } else {
-      uint64_t h = mix_id(id) & t.mask;
-      for (uint64_t probe = 0; probe <= t.mask; ++probe, h = (h + 1) & t.mask) {
-        const uint64_t w = t.words[h];
-        if (w == id) member = true;
-        if (w == id || w == kEmptyKey) break;
-      }
-    }
+    const bool member = id_table_find(t, ext_ids[(size_t)block * kWave + lane]) != kNoEntry;
     return resident && member != exclude;  // (resident first in both modes: a deny filter never allows a pad slot)
   }
 };
@@ -182,8 +137,7 @@ vi_status slot_filter_ids(const DeviceIndex &ix, const uint64_t *ids, uint64_t n
   if (n > (1ull << 40)) return fail(VI_ERR_INVALID_INPUT, "id set of %llu ids is too large", (unsigned long long)n);
   VI_HIP(hipSetDevice(ix.device));
   hipStream_t st = ix.stream;
-  uint64_t capacity = 2;  // power of two >= 2 max(n, 1): load factor <= 0.5
-  while (capacity < 2 * n) capacity <<= 1;
+  const uint64_t capacity = id_table_capacity(n);
   // the table, the flags and the uploaded copy of host ids live until this function returns
   DevBuf<unsigned long long> words;
   DevBuf<uint32_t> flags;

@@ -12,6 +12,7 @@ bindings/python/python/vector_indexer_py/__init__.py):
     VectorIndex.add(xb, ext_ids=None, timestamps=None)      extension: append records to a built or loaded index
     VectorIndex.remove_ids(ids) / .retain(filter) -> int    extension: remove records from it (by id / all a filter excludes)
     VectorIndex.upsert(xb, ext_ids, timestamps=None) -> int extension: replace the records that carry ext_ids, in one rewrite
+    VectorIndex.get(ids) / .export(first, count)            extension: read records back, by id / a range in list order
 
 Errors surface as RuntimeError, as PyO3's PyRuntimeError does.  There is NO CPU fallback: if
 libvi_amd.so is missing or no MI355X is visible, build/load/search raise.
@@ -346,6 +347,55 @@ class VectorIndex:
         """phases of the most recent upsert() of at least one row"""
         st = _native.UpsertStats()
         _native.check(lib().vi_indexer_last_upsert_stats(self._h, C.byref(st)))
+        return {f: getattr(st, f) for f, _ in st._fields_}
+
+    def get(self, ids, *, vectors: bool = True):
+        """extension: read records back by external id (any integer array-like; no order needed, ids may repeat) ->
+        (counts u32[n], X f32[n, dim] or None, timestamps u64[n], where u64[n]).  counts[i]: resident records that carry
+        ids[i] (0: absent — a zero row, timestamp 0, where 2^64 - 1); the rest describes the first of them in list order:
+        the stored f32 bits, the stored timestamp, where = (list << 32) | position in the full list.  vectors=False:
+        nothing is gathered ("contains / how many").  May run beside searches, not beside an update."""
+        a = _native.id_array(ids)
+        n = a.size
+        counts, ts = np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint64)
+        where = np.full(n, _native.WHERE_NONE, dtype=np.uint64)
+        X = np.zeros((n, self._dimension), dtype=np.float32) if vectors else None
+        _native.check(lib().vi_indexer_get_records(self._h, _native.ptr(a) if n else None, n, _native.ptr(counts), _native.ptr(X),
+                                                   _native.ptr(ts), _native.ptr(where)), prefix="Failed to get records: ")
+        return counts, X, ts, where
+
+    def get_device(self, ids_ptr: int, n: int, count_ptr: int = 0, values_ptr: int = 0, ts_ptr: int = 0, where_ptr: int = 0):
+        """... for n u64 ids in device memory, into device memory: counts u32[n], values f32[n, dim], timestamps and where
+        u64[n]; a pointer of 0 skips that output"""
+        _native.check(lib().vi_indexer_get_records_device(self._h, C.c_void_p(ids_ptr) if ids_ptr else None, int(n),
+                                                          *[C.c_void_p(p) if p else None
+                                                            for p in (count_ptr, values_ptr, ts_ptr, where_ptr)]),
+                      prefix="Failed to get records: ")
+
+    def export(self, first: int = 0, count: Optional[int] = None):
+        """extension: records [first, first + count) of the list order (lists ascending, positions ascending; count None:
+        to the end) -> (ext_ids u64[count], X f32[count, dim], timestamps u64[count], where u64[count]).  On a rank of a
+        partitioned index: the rank's resident records, where carrying full-list positions."""
+        first = int(first)
+        count = max(self.num_vectors - first, 0) if count is None else int(count)
+        ext, ts, where = (np.zeros(count, dtype=np.uint64) for _ in range(3))
+        X = np.zeros((count, self._dimension), dtype=np.float32)
+        _native.check(lib().vi_indexer_export_records(self._h, first, count, _native.ptr(ext), _native.ptr(X), _native.ptr(ts),
+                                                      _native.ptr(where)), prefix="Failed to export records: ")
+        return ext, X, ts, where
+
+    def export_device(self, first: int, count: int, ids_ptr: int = 0, values_ptr: int = 0, ts_ptr: int = 0, where_ptr: int = 0):
+        """... into device memory: ext_ids u64[count], values f32[count, dim] row-major, timestamps and where u64[count];
+        a pointer of 0 skips that output"""
+        _native.check(lib().vi_indexer_export_records_device(self._h, int(first), int(count),
+                                                             *[C.c_void_p(p) if p else None
+                                                               for p in (ids_ptr, values_ptr, ts_ptr, where_ptr)]),
+                      prefix="Failed to export records: ")
+
+    def fetch_stats(self) -> dict:
+        """figures of the most recent get() / export() (either form); the ms_* only under enable_timing()"""
+        st = _native.FetchStats()
+        _native.check(lib().vi_indexer_last_fetch_stats(self._h, C.byref(st)))
         return {f: getattr(st, f) for f, _ in st._fields_}
 
     def build_stats(self) -> dict:

@@ -64,6 +64,14 @@ class UpsertStats(C.Structure):
                 ("ms_kernel", f32), ("kernel_bytes", u64)]
 
 
+class FetchStats(C.Structure):
+    _fields_ = [("n", u64), ("n_found", u64), ("slots_scanned", u64), ("bytes_moved", u64), ("ms_total", f32),
+                ("ms_table", f32), ("ms_match", f32), ("ms_gather", f32)]
+
+
+WHERE_NONE = (1 << 64) - 1   # VI_WHERE_NONE
+
+
 FETCH_ROWS_FN =C.CFUNCTYPE(C.c_int, vp, C.POINTER(u64), u64, vp)
 
 
@@ -147,6 +155,11 @@ SIGNATURES = {
     "vi_indexer_upsert_records": (C.c_int, [vp, vp, vp, vp, u64, C.POINTER(u64)]),
     "vi_shard_upsert_to": (C.c_int, [C.c_char_p, u64, u64, vp, vp, vp, vp, vp, C.POINTER(u64)]),
     "vi_indexer_last_upsert_stats": (C.c_int, [vp, C.POINTER(UpsertStats)]),
+    "vi_indexer_get_records": (C.c_int, [vp, vp, u64, vp, vp, vp, vp]),
+    "vi_indexer_get_records_device": (C.c_int, [vp, vp, u64, vp, vp, vp, vp]),
+    "vi_indexer_export_records": (C.c_int, [vp, u64, u64, vp, vp, vp, vp]),
+    "vi_indexer_export_records_device": (C.c_int, [vp, u64, u64, vp, vp, vp, vp]),
+    "vi_indexer_last_fetch_stats": (C.c_int, [vp, C.POINTER(FetchStats)]),
 }
 
 _lib = None

@@ -10,6 +10,7 @@
     .add_records(records)                                                         extension: append to a built index
     .remove_records(external_ids) -> int                                          extension: remove from a built index
     .upsert_records(records) -> int                                               extension: replace by external id
+    .get_records(external_ids) -> [VectorRecord or None]                          extension: read back by external id
     SearchRequest.with_timestamp_range / .with_allowed_ids / .with_excluded_ids   extension: filtered search
 
 Errors are ViError (a RuntimeError) whose .kind is the io::ErrorKind name the reference returns.
@@ -251,6 +252,17 @@ class VectorIndexer:
         _native.check(lib().vi_indexer_upsert_records(self._h, _native.ptr(ext), _native.ptr(vals), _native.ptr(ts), n,
                                                       C.byref(replaced)))
         return int(replaced.value)
+
+    def get_records(self, external_ids) -> List[Optional[VectorRecord]]:
+        """extension: the stored record of every id, in request order: its vector and timestamp as they are stored (of the
+        first record in list order where several carry the id); None for an id nothing carries"""
+        ids = _native.id_array(external_ids)
+        n, dim = ids.size, self._cfg.dimension
+        cnt, ts = np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint64)
+        vals = np.zeros((n, dim), dtype=np.float32)
+        _native.check(lib().vi_indexer_get_records(self._h, _native.ptr(ids) if n else None, n, _native.ptr(cnt),
+                                                   _native.ptr(vals), _native.ptr(ts), None))
+        return [VectorRecord(int(ids[i]), vals[i].tolist(), int(ts[i])) if cnt[i] else None for i in range(n)]
 
     def build_from_vector_file(self, path) -> "VectorIndexer":
         self._drop_filters()

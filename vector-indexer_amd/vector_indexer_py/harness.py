@@ -119,7 +119,8 @@ def synthetic_dataset(n: int, d: int, nq: int, k: int, seed: int = 42) -> Tuple[
 # ---- the adapter + eval loop --------------------------------------------------------------------------------------
 class FaissStyleAdapter:
     """the Faiss-looking face of an index: .d, .nprobe (settable), .search(xq, k) -> (D, I), .range_search(x, thresh),
-    .add(x), .add_with_ids(x, ids), .remove_ids(ids) -> int, .update_vectors(ids, x) -> int, .ntotal
+    .add(x), .add_with_ids(x, ids), .remove_ids(ids) -> int, .update_vectors(ids, x) -> int, .reconstruct(id),
+    .reconstruct_batch(ids), .ntotal
     (vector_indexer_adapter.py:75-140; the reference hops through an asyncio thread, the search here is synchronous)"""
 
     def __init__(self, vector_index, k: int = 100):
@@ -177,6 +178,21 @@ class FaissStyleAdapter:
         """Faiss's IndexIVF.update_vectors(ids, x): the records that carry ids[i] are replaced by row i of x -> records
         replaced.  Unlike Faiss, an id the index does not hold is added"""
         return self._idx.upsert(np.ascontiguousarray(x, dtype=np.float32), ids)
+
+    def reconstruct_batch(self, ids) -> np.ndarray:
+        """Faiss's Index.reconstruct_batch: the stored vectors of ids, one row each; an id the index does not hold raises
+        KeyError naming it"""
+        from ._native import id_array
+        ids = id_array(ids)
+        counts, X, _, _ = self._idx.get(ids)
+        absent = np.flatnonzero(counts == 0)
+        if absent.size:
+            raise KeyError(int(ids[absent[0]]))
+        return X
+
+    def reconstruct(self, id: int) -> np.ndarray:
+        """Faiss's Index.reconstruct: the stored vector of one id (KeyError if the index does not hold it)"""
+        return self.reconstruct_batch([int(id)])[0]
 
     @property
     def ntotal(self) -> int:
