@@ -23,8 +23,8 @@ for line in out.splitlines():
         rows[cur][m.group(1).strip()] = int(m.group(2))
 for k, v in rows.items():
     if pat in k:
-        print("%-80s vgpr %3s agpr %3s spill %3s scratch %4s occ %s" % (k[-80:], v.get("VGPRs"), v.get("AGPRs"), v.get("VGPRs Spill"),
-                                                                        v.get("ScratchSize"), v.get("Occupancy")))
+        print("%-80s vgpr %3s agpr %3s sgpr %3s spill %3s scratch %4s occ %s" % (k[-80:], v.get("VGPRs"), v.get("AGPRs"), v.get("TotalSGPRs"),
+                                                                                 v.get("VGPRs Spill"), v.get("ScratchSize"), v.get("Occupancy")))
 try:
     os.remove("/tmp/kr_%d.o" % os.getpid())
 except OSError:

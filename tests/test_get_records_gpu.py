@@ -145,38 +145,42 @@ def built(request, tmp_path_factory):
 DUP3, DUP64 = 777_000_000_777, 888_000_000_888
 
 
-@pytest.fixture(scope="module")
-def hand(tmp_path_factory):
-    """nine lists of 1, 63, 64, 65, 0, 0, 200, 0, 129 records: the oracle writes an index of nine lists, then every shard
-    file is rewritten through the oracle's writer with lists of exactly these lengths (an empty list last in its file).
-    DUP3 is carried by one record of lists 1, 3 and 8 and by two of list 6; DUP64 by every record of list 2."""
-    d = 20
+def hand_made(root, lens, d, duplicates):
+    """nine lists of exactly `lens` records: the oracle writes an index of nine lists, then every shard file is rewritten
+    through the oracle's writer with lists of these lengths (an empty list last in its file)"""
     rng = np.random.default_rng(77)
     centres = 8.0 * rng.standard_normal((9, d))
     X0 = (centres[np.arange(900) % 9] + 0.1 * rng.standard_normal((900, d))).astype(np.float32)
-    root = tmp_path_factory.mktemp("hand")
     idx, sh = str(root / "index"), str(root / "shards")
     orc = O.OracleIndex.build(X0, idx, sh, nlist=9, now=NOW)
     cent, c2s = orc.centroids()
-    assert len(c2s) == len(HAND_LENS)
-    total = sum(HAND_LENS)
+    assert len(c2s) == len(lens)
+    total = sum(lens)
     X = special_values(rng.standard_normal((total, d)))
     ext = ext_ids_for(total) + np.uint64(1)
     ext[0], ext[400] = 0, U64_MAX
     ts = timestamps_for(total)
-    off = np.concatenate([[0], np.cumsum(HAND_LENS)])
-    ext[off[2]:off[3]] = DUP64
-    for l, p in ((1, 40), (3, 64), (8, 128), (6, 70), (6, 199)):
-        ext[off[l] + p] = DUP3
+    off = np.concatenate([[0], np.cumsum(lens)])
+    if duplicates:
+        ext[off[2]:off[3]] = DUP64
+        for l, p in ((1, 40), (3, 64), (8, 128), (6, 70), (6, 199)):
+            ext[off[l] + p] = DUP3
     for s in sorted(set(int(x) for x in c2s)):
         mine = [l for l in range(9) if int(c2s[l]) == s]
-        mine.sort(key=lambda l: (HAND_LENS[l] == 0, l))
+        mine.sort(key=lambda l: (lens[l] == 0, l))
         lists = [(np.arange(off[l], off[l + 1], dtype=np.uint64), ext[off[l]:off[l + 1]], ts[off[l]:off[l + 1]],
                   X[off[l]:off[l + 1]]) for l in mine]
         assert O.shard_save(sh, s, d, mine, cent[mine], lists) == O.ORC_OK
     fx = Fx(root, idx, sh, d, seed=7)
-    assert fx.want.lens == HAND_LENS and fx.n == total
+    assert fx.want.lens == lens and fx.n == total
     return fx
+
+
+@pytest.fixture(scope="module")
+def hand(tmp_path_factory):
+    """nine lists of 1, 63, 64, 65, 0, 0, 200, 0, 129 records.  DUP3 is carried by one record of lists 1, 3 and 8 and by
+    two of list 6; DUP64 by every record of list 2."""
+    return hand_made(tmp_path_factory.mktemp("hand"), HAND_LENS, 20, duplicates=True)
 
 
 def raw_get(ix, ids, outputs="cvtw", dim=None):
@@ -358,6 +362,34 @@ def test_stored_duplicates(hand):
     assert hand.gpu.fetch_stats()["n_found"] == 3
 
 
+# ---- every case of the walk over the resident slots (csrc/list_layout.hpp), by a get and by an id filter ----
+WALK_LENS = [0, 1, 63, 64, 65, 2113, 0, 0, 0]   # 2113 = 32 blocks + 65: a workgroup column of the walk takes a second pass
+
+
+def test_the_slot_walk_of_a_get_and_of_an_id_filter(tmp_path_factory):
+    fx = hand_made(tmp_path_factory.mktemp("walk"), WALK_LENS, 8, duplicates=False)
+    assert np.unique(fx.want.ext).size == fx.n
+    for name in ("all", "n65", "mostly_absent", "odd"):
+        same_get(fx.gpu.get(fx.sets[name]), fx.want.get(fx.sets[name]), name)
+    counts, _, _, where = fx.gpu.get(fx.want.ext)
+    assert (counts == 1).all() and np.array_equal(where, fx.want.where)     # every resident slot, first to last
+    # the filters of a third of the records, and the oracle's whole candidate sequence (k = N, every list probed) less
+    # what a filter removes
+    rng = np.random.default_rng(5)
+    ids = fx.want.ext[rng.random(fx.n) < 1 / 3]
+    Q = np.concatenate([fx.want.X[[0, 1, 64, 65, 129, 193, 194, 2305]], rng.standard_normal((8, 8)).astype(np.float32)])
+    rc, D, I = O.OracleIndex.load(fx.idx, fx.sh).search_batch(Q, fx.n, 9)
+    assert rc == O.ORC_OK and I.shape == (len(Q), fx.n)
+    member = np.isin(np.ascontiguousarray(I).view(np.uint64), ids)    # (the id 2^64 - 1 reads as -1 here and on the GPU)
+    for exclude in (False, True):
+        flt = fx.gpu.filter_ids(ids, exclude=exclude)
+        assert flt.num_allowed == (fx.n - ids.size if exclude else ids.size)
+        Dg, Ig = fx.gpu.search_sync(Q, 10, 9, filter=flt)
+        for q in range(len(Q)):
+            keep = np.flatnonzero(member[q] != exclude)[:10]
+            assert np.array_equal(Ig[q], I[q][keep]) and np.array_equal(bits(Dg[q]), bits(D[q][keep])), (exclude, q)
+
+
 # ---- after updates ----
 def writable(fx, name):
     root = fx.root / name
@@ -495,6 +527,29 @@ def test_four_threads_get_while_a_fifth_searches(built):
     stop.set()
     s.join()
     assert not errors, errors
+
+
+def test_the_first_export_of_a_handle_beside_three_gets(built):
+    """a fresh handle: the export that reads the list layout back runs while three threads get, and all four answer as
+    they do alone"""
+    gpu = vip.load(built.idx, built.sh, built.dim)
+    reqs = [built.sets["all"], built.sets["mostly_absent"], built.sets["n65"]]
+    want = [built.want.get(r) for r in reqs]
+    errors = []
+
+    def run(check):
+        try:
+            check()
+        except Exception as e:  # noqa: BLE001
+            errors.append(e)
+
+    checks = [lambda: same_export(gpu.export(), built.want, 0, built.n, "export")]
+    checks += [lambda t=t: same_get(gpu.get(reqs[t]), want[t], f"get {t}") for t in range(3)]
+    threads = [threading.Thread(target=run, args=(c,)) for c in checks]
+    [t.start() for t in threads]
+    [t.join() for t in threads]
+    assert not errors, errors
+    same_export(gpu.export(7, 100), built.want, 7, 107, "a later export")
 
 
 # ---- adapters ----

@@ -838,8 +838,7 @@ vi_status vi_indexer_export_records_device(const vi_indexer *ix, uint64_t first,
 vi_status vi_indexer_last_fetch_stats(const vi_indexer *ix, vi_fetch_stats *out) {
   return vi::guarded([&]() -> vi_status {
   if (!ix || !out || !ix->impl.dev) return fail(VI_ERR_INVALID_INPUT, "no stats");
-  std::lock_guard<std::mutex> lock(ix->impl.dev->fetch.mu);
-  *out = ix->impl.dev->fetch.last;
+  ix->impl.dev->fetch.pool.locked([&] { *out = ix->impl.dev->fetch.last; });
   return VI_OK;
   });
 }
@@ -1129,8 +1128,7 @@ void vi_indexer_free(vi_indexer *ix) { delete ix; }
 vi_status vi_indexer_last_stats(const vi_indexer *ix, vi_search_stats *out) {
   return vi::guarded([&]() -> vi_status {
   if (!ix || !out || !ix->impl.dev) return fail(VI_ERR_INVALID_INPUT, "no stats");
-  std::lock_guard<std::mutex> lock(ix->impl.dev->mu);
-  *out = ix->impl.dev->last_stats;
+  ix->impl.dev->search_contexts.locked([&] { *out = ix->impl.dev->last_stats; });
   return VI_OK;
   });
 }

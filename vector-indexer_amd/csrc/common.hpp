@@ -5,6 +5,7 @@
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -68,6 +69,43 @@ struct DevBuf {
     return VI_OK;
   }
 };
+
+// The keys, the flag words and the uploaded host ids of an id set (id_table.hpp: id_set_build).  Here, not there: a
+// FetchContext (device_index.hpp) keeps one, and every file that includes id_table.hpp compiles its kernel.
+struct IdSetBuffers { DevBuf<unsigned long long> words; DevBuf<uint32_t> flags; DevBuf<uint64_t> upload; };
+
+// the stream and the K events of a context (context_pool.hpp)
+template <int K>
+struct StreamEvents {
+  hipStream_t stream = nullptr;
+  hipEvent_t ev[K] = {};
+  vi_status create() {
+    if (hipStreamCreateWithFlags(&stream, hipStreamDefault) != hipSuccess)
+      return fail(VI_ERR_DEVICE, "hipStreamCreate failed: %s", hipGetErrorString(hipGetLastError()));
+    for (auto &e : ev)
+      if (hipEventCreate(&e) != hipSuccess) return fail(VI_ERR_DEVICE, "hipEventCreate failed");
+    return VI_OK;
+  }
+  ~StreamEvents() {
+    for (auto &e : ev)
+      if (e) (void)hipEventDestroy(e);
+    if (stream) (void)hipStreamDestroy(stream);
+  }
+};
+
+// what a ContextPool makes its contexts with: null (and create's message) on failure
+template <class Ctx>
+std::unique_ptr<Ctx> make_context() {
+  auto c = std::make_unique<Ctx>();
+  if (c->create() != VI_OK) c.reset();
+  return c;
+}
+
+inline float elapsed_ms(hipEvent_t a, hipEvent_t b) {
+  float ms = 0.0f;
+  (void)hipEventElapsedTime(&ms, a, b);
+  return ms;
+}
 
 inline uint32_t ceil_div_u32(uint64_t a, uint64_t b) { return (uint32_t)((a + b - 1) / b); }
 

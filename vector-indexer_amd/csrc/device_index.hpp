@@ -17,13 +17,12 @@
 #pragma once
 #include <atomic>
 #include <cstdint>
-#include <condition_variable>
-#include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
 
 #include "common.hpp"
+#include "context_pool.hpp"
 #include "shards.hpp"
 
 namespace vi {
@@ -95,34 +94,21 @@ struct SearchWorkspace {
 };
 
 // ---- reading records back (record_fetch.hip) ----
-// A get or an export holds one FetchContext for the duration of the call, as a search holds a SearchContext: its own
-// stream and events, the id table of a get and the staging of host outputs, all grow-only.  Up to kFetchContexts calls
-// run at once on one handle, further callers wait for a free one.
-struct FetchContext {
-  hipStream_t stream = nullptr;
-  hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  DevBuf<unsigned long long> words;    // id table: [capacity] keys ...
-  DevBuf<uint32_t> first_slot, count;  // ... and [capacity + 1] values: lowest slot that carries the key, records that do
-  DevBuf<uint32_t> flags;              // IdTable::flags, then [2..3] one u64: requests that found a record
-  DevBuf<uint64_t> upload;             // host ids on the device
+// A get or an export holds one FetchContext of the handle's pool (context_pool.hpp) for the duration of the call: its
+// stream and events, the id table of a get and the staging of host outputs, all grow-only.
+struct FetchContext : StreamEvents<5> {
+  IdSetBuffers ids;                    // the requested ids; its flags carry two more words, one u64: requests that found a record
+  DevBuf<uint32_t> first_slot, count;  // [capacity + 1] values beside the keys: lowest slot that carries the key, records that do
   DevBuf<uint32_t> out_count;          // host outputs are produced here and copied back
   DevBuf<float> out_values;
   DevBuf<uint64_t> out_ids, out_ts, out_where;
-  ~FetchContext() {
-    for (auto &e : ev)
-      if (e) (void)hipEventDestroy(e);
-    if (stream) (void)hipStreamDestroy(stream);
-  }
 };
 struct FetchState {
-  static constexpr int kFetchContexts = 4;
-  std::mutex mu;  // guards everything below
-  std::condition_variable cv;
-  std::vector<std::unique_ptr<FetchContext>> contexts;  // created on demand
-  std::vector<FetchContext *> free_contexts;
-  vi_fetch_stats last{};  // of the most recent get or export that finished on this handle
+  ContextPool<FetchContext, 4> pool;
+  vi_fetch_stats last{};  // of the most recent get or export that succeeded on this handle (under the pool's lock)
   // the layout of the (immutable) index, read back by the first export: first block, length and the exclusive prefix
   // of the lengths (= list-order ordinal of a list's first record), on the host and the prefix on the device too
+  std::mutex layout_mu;  // guards the making of the five below; they are read freely once layout_ready was seen under it
   bool layout_ready = false;
   std::vector<uint32_t> h_first, h_len;
   std::vector<uint64_t> h_prefix;  // [nlists + 1]
@@ -180,21 +166,15 @@ struct DeviceIndex {
   DevBuf<uint32_t> c_first, c_len;    // the coarse table described as one list
   hipStream_t stream = nullptr;       // uploads and index construction
   // Searches: the reference's search is &self and runs concurrently from several OS threads
-  // (tests/ivf_index_tests.rs:768-807).  A search holds one SearchContext — its own stream, events, workspace — for
-  // the duration of the call; up to kSearchContexts calls run at once on one handle, further callers wait for a free one.
-  struct SearchContext {
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  // (tests/ivf_index_tests.rs:768-807).  A search holds one SearchContext of the pool (context_pool.hpp) — its own
+  // stream, events, workspace — for the duration of the call: up to four calls run at once on one handle.
+  struct SearchContext : StreamEvents<6> {
     SearchWorkspace ws;
     vi_search_stats stats{};
-    ~SearchContext();
+    ~SearchContext() { if (ws.hstats_pinned) (void)hipHostFree(ws.hstats_pinned); }
   };
-  static constexpr int kSearchContexts = 4;
-  mutable std::mutex mu;              // guards the context pool and last_stats
-  mutable std::condition_variable cv;
-  mutable std::vector<std::unique_ptr<SearchContext>> contexts;  // created on demand
-  mutable std::vector<SearchContext *> free_contexts;
-  mutable vi_search_stats last_stats{};  // of the most recent search that finished on this handle
+  mutable ContextPool<SearchContext, 4> search_contexts;
+  mutable vi_search_stats last_stats{};  // of the most recent search that finished on this handle (under the pool's lock)
   SearchContext &cur() const;         // the context the calling thread holds (device_index_search acquired it)
   int timing = 0;  // 0 off, 1 HIP events at every phase boundary, 2 around the list-rank kernel only
   mutable FetchState fetch;  // gets and exports: const on the index, like searches

@@ -5,7 +5,10 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
+
+#include "common.hpp"
 
 namespace vi {
 
@@ -61,6 +64,37 @@ __device__ __forceinline__ uint64_t id_table_find(const IdTable &t, uint64_t id)
     if (w == kEmptyKey) break;
   }
   return kNoEntry;
+}
+
+// The set of ids[0 .. n) (host memory unless on_device; n == 0: none is read) as *out, complete on stream st: 2 +
+// extra_flag_words cleared flag words, host ids in b.upload.  `uploaded` (or null) is recorded behind the upload.
+inline vi_status id_set_build(IdSetBuffers &b, const uint64_t *ids, uint64_t n, bool on_device, uint32_t extra_flag_words,
+                              hipStream_t st, IdTable *out, hipEvent_t uploaded = nullptr) {
+  const uint64_t capacity = id_table_capacity(n);
+  VI_TRY(b.words.reserve(capacity));
+  VI_TRY(b.flags.reserve(2 + extra_flag_words));
+  if (n && !on_device) {
+    VI_TRY(b.upload.reserve(n));
+    VI_HIP(hipMemcpyAsync(b.upload.p, ids, n * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    ids = b.upload.p;
+  }
+  if (uploaded) VI_HIP(hipEventRecord(uploaded, st));
+  VI_HIP(hipMemsetAsync(b.words.p, 0xff, capacity * sizeof(unsigned long long), st));  // every word kEmptyKey
+  VI_HIP(hipMemsetAsync(b.flags.p, 0, (2 + extra_flag_words) * sizeof(uint32_t), st));
+  *out = IdTable{b.words.p, capacity - 1, b.flags.p};
+  if (n) {
+    const uint32_t grid = (uint32_t)std::min<uint64_t>((n + 255) / 256, 65536);
+    hipLaunchKernelGGL(id_table_insert_kernel, dim3(grid), dim3(256), 0, st, *out, ids, n);
+    VI_HIP(hipGetLastError());
+  }
+  return VI_OK;
+}
+
+// the refusal of a table whose flag words, read back, report an insert that found no free word
+inline vi_status id_set_check(const uint32_t *flags_host, const IdTable &t, uint64_t n, const char *what) {
+  if (flags_host[1]) return fail(VI_ERR_DEVICE, "%s: the id table (capacity %llu for %llu ids) overflowed", what,
+                                 (unsigned long long)(t.mask + 1), (unsigned long long)n);
+  return VI_OK;
 }
 
 }  // namespace vi

@@ -17,35 +17,29 @@
 namespace vi {
 namespace {
 
-constexpr uint32_t kListSplit = 8;      // workgroups sharing the blocks of one list, as in slot_filter.hip
 constexpr uint32_t kNoSlot = 0xFFFFFFFFu;
 constexpr uint32_t kResolveBlocks = 2048;  // workgroups of the answer kernel: 8 per CU fill the chip, each loops over its rows
 constexpr uint64_t kWhereNone = ~0ull;  // VI_WHERE_NONE
 
 // ---- get: the scan ----
 struct MatchArgs {
-  const uint32_t *first_block, *list_len;
-  uint32_t nlists;
+  ResidentLists lists;
   const uint64_t *ext_ids;
   IdTable t;
   uint32_t *first_slot, *count;  // [capacity + 1], kNoSlot / 0 before the launch
 };
 
-// One wave per 64-vector block, kListSplit workgroups of four waves per list, lane = vector of the block, masked by the
-// list length (a pad slot's id word is never read).  A slot whose id is requested leaves the lowest slot number and one
-// count on the id's entry; lists lie back to back in list order, so the lowest slot is the first record in list order.
+// The walk of list_layout.hpp, masked by the list length (a pad slot's id word is never read).  A requested id's slot leaves
+// the lowest slot number and one count on its entry; lists lie in list order, so that is the first record in list order.
 __global__ void __launch_bounds__(256) fetch_match_kernel(MatchArgs a) {
-  const uint32_t l = blockIdx.x, lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  if (l >= a.nlists) return;
-  const uint32_t len = a.list_len[l], fb = a.first_block[l], nblk = (len + 63u) / 64u;
-  for (uint32_t b = blockIdx.y * 4u + wave; b < nblk; b += gridDim.y * 4u) {  // (wave-uniform)
-    if (b * 64u + lane >= len) continue;
-    const uint32_t slot = (fb + b) * 64u + lane;
+  for_each_resident_block(a.lists, [&](uint32_t block, uint32_t lane, bool resident) {
+    if (!resident) return;
+    const uint32_t slot = block * 64u + lane;
     const uint64_t e = id_table_find(a.t, a.ext_ids[slot]);
-    if (e == kNoEntry) continue;
+    if (e == kNoEntry) return;
     atomicMin(&a.first_slot[e], slot);
     atomicAdd(&a.count[e], 1u);
-  }
+  });
 }
 
 // ---- get: the answers ----
@@ -212,68 +206,30 @@ __global__ void __launch_bounds__(64) export_blocks_kernel(ExportArgs a) {
   }
 }
 
-// ---- the context a call holds ----
-struct FetchLease {
-  const DeviceIndex &ix;
-  FetchContext *mine = nullptr;
-  vi_fetch_stats stats{};
-  bool done = false;  // the call succeeded: its stats become the handle's
-  explicit FetchLease(const DeviceIndex &i) : ix(i) {}
-  vi_status acquire() {
-    FetchState &f = ix.fetch;
-    std::unique_lock<std::mutex> lock(f.mu);
-    for (;;) {
-      if (!f.free_contexts.empty()) { mine = f.free_contexts.back(); f.free_contexts.pop_back(); return VI_OK; }
-      if ((int)f.contexts.size() < FetchState::kFetchContexts) {
-        auto c = std::make_unique<FetchContext>();
-        if (hipStreamCreateWithFlags(&c->stream, hipStreamDefault) != hipSuccess)
-          return fail(VI_ERR_DEVICE, "hipStreamCreate failed: %s", hipGetErrorString(hipGetLastError()));
-        for (auto &e : c->ev)
-          if (hipEventCreate(&e) != hipSuccess) return fail(VI_ERR_DEVICE, "hipEventCreate failed");
-        mine = c.get();
-        f.contexts.push_back(std::move(c));
-        return VI_OK;
-      }
-      f.cv.wait(lock);
-    }
+// The wanted outputs of a host caller: stage() points p, the caller's pointer, at the context's staging for the kernels to
+// write; copy_back brings them home.  A device caller's pointers and an output not wanted stay as they are.
+struct Staged {
+  const bool on_device;
+  struct { void *user; const void *dev; size_t bytes; } o[4];
+  int n = 0;
+  template <typename T>
+  vi_status stage(T *&p, DevBuf<T> &buf, uint64_t count) {
+    if (on_device || !p) return VI_OK;
+    VI_TRY(buf.reserve(count));
+    o[n++] = {p, buf.p, count * sizeof(T)};
+    p = buf.p;
+    return VI_OK;
   }
-  ~FetchLease() {
-    if (!mine) return;
-    {
-      std::lock_guard<std::mutex> lock(ix.fetch.mu);
-      if (done) ix.fetch.last = stats;
-      ix.fetch.free_contexts.push_back(mine);
-    }
-    ix.fetch.cv.notify_one();
+  vi_status copy_back(hipStream_t st) const {
+    for (int i = 0; i < n; ++i) VI_HIP(hipMemcpyAsync(o[i].user, o[i].dev, o[i].bytes, hipMemcpyDeviceToHost, st));
+    return VI_OK;
   }
 };
 
-float elapsed(hipEvent_t a, hipEvent_t b) {
-  float ms = 0.0f;
-  (void)hipEventElapsedTime(&ms, a, b);
-  return ms;
-}
-
-// where the kernels write an output: the caller's device memory, or (host callers, output wanted) the context's staging
-template <typename T>
-vi_status stage(bool on_device, T *user, DevBuf<T> &buf, uint64_t count, T **dev) {
-  *dev = user;
-  if (on_device || !user) return VI_OK;
-  VI_TRY(buf.reserve(count));
-  *dev = buf.p;
-  return VI_OK;
-}
-template <typename T>
-vi_status unstage(bool on_device, T *user, const T *dev, uint64_t count, hipStream_t st) {
-  if (on_device || !user) return VI_OK;
-  VI_HIP(hipMemcpyAsync(user, dev, count * sizeof(T), hipMemcpyDeviceToHost, st));
-  return VI_OK;
-}
-
-// the host copy of the layout and the prefix of the lengths, made by the first export of an index (it never changes)
+// the host copy of the layout and the prefix of the lengths, made by the first export of an index under a lock of its own
 vi_status ensure_layout(const DeviceIndex &ix, hipStream_t st) {
   FetchState &f = ix.fetch;
-  std::lock_guard<std::mutex> lock(f.mu);
+  std::lock_guard<std::mutex> lock(f.layout_mu);
   if (f.layout_ready) return VI_OK;
   const uint64_t nl = ix.nlists;
   f.h_first.resize(nl);
@@ -302,46 +258,33 @@ vi_status fetch_records_by_id(const DeviceIndex &ix, const uint64_t *ids, uint64
                               float *values, uint64_t *timestamps, uint64_t *where) {
   if (!ix.ext_ids.p) return fail(VI_ERR_INVALID_INPUT, "this index keeps no external ids");
   VI_HIP(hipSetDevice(ix.device));
-  FetchLease lease(ix);
-  VI_TRY(lease.acquire());
-  FetchContext &c = *lease.mine;
+  vi_fetch_stats s{};
+  bool done = false;  // the call succeeded: its stats become the handle's
+  ContextLease lease(ix.fetch.pool, make_context<FetchContext>, [&] { if (done) ix.fetch.last = s; });
+  if (!lease.ctx) return VI_ERR_DEVICE;  // (the message is make_context's)
+  FetchContext &c = *lease.ctx;
   hipStream_t st = c.stream;
   const bool timing = ix.timing != 0;
   const uint32_t dim = ix.dim;
   const uint64_t capacity = id_table_capacity(n);
-  VI_TRY(c.words.reserve(capacity));
   VI_TRY(c.first_slot.reserve(capacity + 1));
   VI_TRY(c.count.reserve(capacity + 1));
-  VI_TRY(c.flags.reserve(4));
-  uint32_t *d_count;
-  float *d_values;
-  uint64_t *d_ts, *d_where;
-  VI_TRY(stage(on_device, count, c.out_count, n, &d_count));
-  VI_TRY(stage(on_device, values, c.out_values, n * dim, &d_values));
-  VI_TRY(stage(on_device, timestamps, c.out_ts, n, &d_ts));
-  VI_TRY(stage(on_device, where, c.out_where, n, &d_where));
-  if (!on_device) {
-    VI_TRY(c.upload.reserve(n));
-    VI_HIP(hipMemcpyAsync(c.upload.p, ids, n * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-    ids = c.upload.p;
-  }
-  // ---- the table of the requested ids ----
-  if (timing) VI_HIP(hipEventRecord(c.ev[0], st));
-  VI_HIP(hipMemsetAsync(c.words.p, 0xff, capacity * sizeof(unsigned long long), st));  // every word kEmptyKey
+  Staged out{on_device};
+  VI_TRY(out.stage(count, c.out_count, n));
+  VI_TRY(out.stage(values, c.out_values, n * dim));
+  VI_TRY(out.stage(timestamps, c.out_ts, n));
+  VI_TRY(out.stage(where, c.out_where, n));
+  // ---- the table of the requested ids (two more flag words: `found`), timed from behind the upload of host ids ----
+  IdTable t;
+  VI_TRY(id_set_build(c.ids, ids, n, on_device, 2, st, &t, timing ? c.ev[0] : nullptr));
+  if (!on_device) ids = c.ids.upload.p;
   VI_HIP(hipMemsetAsync(c.first_slot.p, 0xff, (capacity + 1) * sizeof(uint32_t), st));  // kNoSlot
   VI_HIP(hipMemsetAsync(c.count.p, 0, (capacity + 1) * sizeof(uint32_t), st));
-  VI_HIP(hipMemsetAsync(c.flags.p, 0, 4 * sizeof(uint32_t), st));
-  IdTable t{c.words.p, capacity - 1, c.flags.p};
-  {
-    const uint32_t grid = (uint32_t)std::min<uint64_t>((n + 255) / 256, 65536);
-    hipLaunchKernelGGL(id_table_insert_kernel, dim3(grid), dim3(256), 0, st, t, ids, n);
-    VI_HIP(hipGetLastError());
-  }
   if (timing) VI_HIP(hipEventRecord(c.ev[1], st));
   // ---- the scan of the resident ids ----
   if (ix.lists.nblocks && ix.nlists) {
-    MatchArgs m{ix.list_first_block.p, ix.list_len.p, (uint32_t)ix.nlists, ix.ext_ids.p, t, c.first_slot.p, c.count.p};
-    hipLaunchKernelGGL(fetch_match_kernel, dim3((uint32_t)ix.nlists, kListSplit), dim3(256), 0, st, m);
+    MatchArgs m{{ix.list_first_block.p, ix.list_len.p, (uint32_t)ix.nlists}, ix.ext_ids.p, t, c.first_slot.p, c.count.p};
+    hipLaunchKernelGGL(fetch_match_kernel, slot_walk_grid((uint32_t)ix.nlists), dim3(256), 0, st, m);
     VI_HIP(hipGetLastError());
   }
   if (timing) VI_HIP(hipEventRecord(c.ev[2], st));
@@ -351,10 +294,10 @@ vi_status fetch_records_by_id(const DeviceIndex &ix, const uint64_t *ids, uint64
   r.blocks = reinterpret_cast<const float4 *>(ix.lists.blocks.p); r.dq = ix.dq; r.dim = dim;
   r.first_block = ix.list_first_block.p; r.nlists = (uint32_t)ix.nlists; r.timestamps = ix.timestamps.p;
   r.world = ix.stripe_world; r.rank = ix.stripe_rank;
-  r.out_count = d_count; r.out_values = d_values; r.out_ts = d_ts; r.out_where = d_where;
-  r.found = reinterpret_cast<unsigned long long *>(c.flags.p + 2);
-  r.vec_store = dim % 4 == 0 && aligned16(d_values);
-  if (d_values) {
+  r.out_count = count; r.out_values = values; r.out_ts = timestamps; r.out_where = where;
+  r.found = reinterpret_cast<unsigned long long *>(c.ids.flags.p + 2);
+  r.vec_store = dim % 4 == 0 && aligned16(values);
+  if (values) {
     const uint32_t grid = (uint32_t)std::min<uint64_t>((n + 3) / 4, kResolveBlocks);
     hipLaunchKernelGGL(fetch_resolve_gather_kernel<true>, dim3(grid), dim3(256), 0, st, r);
   } else {
@@ -364,28 +307,23 @@ vi_status fetch_records_by_id(const DeviceIndex &ix, const uint64_t *ids, uint64
   VI_HIP(hipGetLastError());
   if (timing) VI_HIP(hipEventRecord(c.ev[3], st));
   uint32_t fl[4] = {0, 0, 0, 0};
-  VI_HIP(hipMemcpyAsync(fl, c.flags.p, sizeof(fl), hipMemcpyDeviceToHost, st));
-  VI_TRY(unstage(on_device, count, d_count, n, st));
-  VI_TRY(unstage(on_device, values, d_values, n * dim, st));
-  VI_TRY(unstage(on_device, timestamps, d_ts, n, st));
-  VI_TRY(unstage(on_device, where, d_where, n, st));
+  VI_HIP(hipMemcpyAsync(fl, c.ids.flags.p, sizeof(fl), hipMemcpyDeviceToHost, st));
+  VI_TRY(out.copy_back(st));
   if (timing) VI_HIP(hipEventRecord(c.ev[4], st));
   VI_HIP(hipStreamSynchronize(st));
-  if (fl[1]) return fail(VI_ERR_DEVICE, "get: the id table (capacity %llu for %llu ids) overflowed",
-                         (unsigned long long)capacity, (unsigned long long)n);
-  vi_fetch_stats &s = lease.stats;
+  VI_TRY(id_set_check(fl, t, n, "get"));
   s.n = n;
   s.n_found = (uint64_t)fl[2] | ((uint64_t)fl[3] << 32);
   s.slots_scanned = ix.nvec_resident;
-  s.bytes_moved = 16 * n + 8 * ix.nvec_resident + (d_count ? 4 * n : 0) + (d_ts ? 8 * n + 8 * s.n_found : 0) +
-                  (d_where ? 8 * n : 0) + (d_values ? 4ull * dim * (n + s.n_found) : 0);
+  s.bytes_moved = 16 * n + 8 * ix.nvec_resident + (count ? 4 * n : 0) + (timestamps ? 8 * n + 8 * s.n_found : 0) +
+                  (where ? 8 * n : 0) + (values ? 4ull * dim * (n + s.n_found) : 0);
   if (timing) {
-    s.ms_table = elapsed(c.ev[0], c.ev[1]);
-    s.ms_match = elapsed(c.ev[1], c.ev[2]);
-    s.ms_gather = elapsed(c.ev[2], c.ev[3]);
-    s.ms_total = elapsed(c.ev[0], c.ev[4]);
+    s.ms_table = elapsed_ms(c.ev[0], c.ev[1]);
+    s.ms_match = elapsed_ms(c.ev[1], c.ev[2]);
+    s.ms_gather = elapsed_ms(c.ev[2], c.ev[3]);
+    s.ms_total = elapsed_ms(c.ev[0], c.ev[4]);
   }
-  lease.done = true;
+  done = true;
   return VI_OK;
 }
 
@@ -393,9 +331,11 @@ vi_status export_records(const DeviceIndex &ix, uint64_t first, uint64_t count, 
                          float *values, uint64_t *timestamps, uint64_t *where) {
   if (!ix.ext_ids.p) return fail(VI_ERR_INVALID_INPUT, "this index keeps no external ids");
   VI_HIP(hipSetDevice(ix.device));
-  FetchLease lease(ix);
-  VI_TRY(lease.acquire());
-  FetchContext &c = *lease.mine;
+  vi_fetch_stats s{};
+  bool done = false;  // the call succeeded: its stats become the handle's
+  ContextLease lease(ix.fetch.pool, make_context<FetchContext>, [&] { if (done) ix.fetch.last = s; });
+  if (!lease.ctx) return VI_ERR_DEVICE;  // (the message is make_context's)
+  FetchContext &c = *lease.ctx;
   hipStream_t st = c.stream;
   const bool timing = ix.timing != 0;
   const uint32_t dim = ix.dim;
@@ -409,42 +349,37 @@ vi_status export_records(const DeviceIndex &ix, uint64_t first, uint64_t count, 
   const uint64_t block_lo = block_of(first), block_hi = block_of(first + count - 1);
   if (block_hi < block_lo || block_hi >= ix.lists.nblocks) return fail(VI_ERR_OTHER, "export: the list layout is inconsistent");
   const uint64_t nblk = block_hi - block_lo + 1;
-  uint64_t *d_ids, *d_ts, *d_where;
-  float *d_values;
-  VI_TRY(stage(on_device, ext_ids, c.out_ids, count, &d_ids));
-  VI_TRY(stage(on_device, values, c.out_values, count * dim, &d_values));
-  VI_TRY(stage(on_device, timestamps, c.out_ts, count, &d_ts));
-  VI_TRY(stage(on_device, where, c.out_where, count, &d_where));
+  Staged out{on_device};
+  VI_TRY(out.stage(ext_ids, c.out_ids, count));
+  VI_TRY(out.stage(values, c.out_values, count * dim));
+  VI_TRY(out.stage(timestamps, c.out_ts, count));
+  VI_TRY(out.stage(where, c.out_where, count));
   ExportArgs a{};
   a.blocks = reinterpret_cast<const float4 *>(ix.lists.blocks.p); a.dq = ix.dq; a.dim = dim;
   a.first_block = ix.list_first_block.p; a.list_len = ix.list_len.p; a.prefix = f.prefix.p; a.nlists = (uint32_t)ix.nlists;
   a.ext_ids = ix.ext_ids.p; a.timestamps = ix.timestamps.p;
   a.block_lo = (uint32_t)block_lo; a.first = first; a.count = count;
   a.world = ix.stripe_world; a.rank = ix.stripe_rank;
-  a.out_ids = d_ids; a.out_values = d_values; a.out_ts = d_ts; a.out_where = d_where;
+  a.out_ids = ext_ids; a.out_values = values; a.out_ts = timestamps; a.out_where = where;
   if (timing) VI_HIP(hipEventRecord(c.ev[0], st));
-  if (dim % 4 == 0 && aligned16(d_values))
+  if (dim % 4 == 0 && aligned16(values))
     hipLaunchKernelGGL(export_blocks_kernel<true>, dim3((uint32_t)nblk), dim3(64), 0, st, a);
   else
     hipLaunchKernelGGL(export_blocks_kernel<false>, dim3((uint32_t)nblk), dim3(64), 0, st, a);
   VI_HIP(hipGetLastError());
   if (timing) VI_HIP(hipEventRecord(c.ev[3], st));
-  VI_TRY(unstage(on_device, ext_ids, d_ids, count, st));
-  VI_TRY(unstage(on_device, values, d_values, count * dim, st));
-  VI_TRY(unstage(on_device, timestamps, d_ts, count, st));
-  VI_TRY(unstage(on_device, where, d_where, count, st));
+  VI_TRY(out.copy_back(st));
   if (timing) VI_HIP(hipEventRecord(c.ev[4], st));
   VI_HIP(hipStreamSynchronize(st));
-  vi_fetch_stats &s = lease.stats;
   s.n = s.n_found = count;
   s.slots_scanned = nblk * 64;
-  s.bytes_moved = (d_ids ? 16 * count : 0) + (d_ts ? 16 * count : 0) + (d_where ? 8 * count : 0) +
-                  (d_values ? nblk * 64 * 16ull * ((dim + 3) / 4) + 4ull * dim * count : 0);
+  s.bytes_moved = (ext_ids ? 16 * count : 0) + (timestamps ? 16 * count : 0) + (where ? 8 * count : 0) +
+                  (values ? nblk * 64 * 16ull * ((dim + 3) / 4) + 4ull * dim * count : 0);
   if (timing) {
-    s.ms_gather = elapsed(c.ev[0], c.ev[3]);
-    s.ms_total = elapsed(c.ev[0], c.ev[4]);
+    s.ms_gather = elapsed_ms(c.ev[0], c.ev[3]);
+    s.ms_total = elapsed_ms(c.ev[0], c.ev[4]);
   }
-  lease.done = true;
+  done = true;
   return VI_OK;
 }
 

@@ -579,13 +579,6 @@ uint32_t coarse_splits(uint64_t nq, int qg, uint32_t nblk, uint32_t *bps) {
   return std::max<uint32_t>(1, (nblk + *bps - 1) / *bps);
 }
 
-DeviceIndex::SearchContext::~SearchContext() {
-  if (ws.hstats_pinned) (void)hipHostFree(ws.hstats_pinned);
-  for (auto &e : ev)
-    if (e) (void)hipEventDestroy(e);
-  if (stream) (void)hipStreamDestroy(stream);
-}
-
 // the context held by the calling thread: set for the duration of device_index_search (a search of ANOTHER index from
 // inside a search — the hierarchical k-means assignment does that — saves and restores it)
 static thread_local DeviceIndex::SearchContext *t_ctx = nullptr;
@@ -593,41 +586,21 @@ static thread_local DeviceIndex::SearchContext *t_ctx = nullptr;
 DeviceIndex::SearchContext &DeviceIndex::cur() const { return *t_ctx; }
 
 namespace {
-struct ContextLease {
-  const DeviceIndex &ix;
-  DeviceIndex::SearchContext *mine = nullptr, *prev = nullptr;
-  explicit ContextLease(const DeviceIndex &i) : ix(i) {}
-  vi_status acquire() {
-    std::unique_lock<std::mutex> lock(ix.mu);
-    for (;;) {
-      if (!ix.free_contexts.empty()) { mine = ix.free_contexts.back(); ix.free_contexts.pop_back(); break; }
-      if ((int)ix.contexts.size() < DeviceIndex::kSearchContexts) {
-        auto c = std::make_unique<DeviceIndex::SearchContext>();
-        if (hipStreamCreateWithFlags(&c->stream, hipStreamDefault) != hipSuccess)
-          return fail(VI_ERR_DEVICE, "hipStreamCreate failed: %s", hipGetErrorString(hipGetLastError()));
-        for (auto &e : c->ev)
-          if (hipEventCreate(&e) != hipSuccess) return fail(VI_ERR_DEVICE, "hipEventCreate failed");
-        mine = c.get();
-        ix.contexts.push_back(std::move(c));
-        break;
-      }
-      ix.cv.wait(lock);
-    }
-    prev = t_ctx;
-    t_ctx = mine;
-    return VI_OK;
-  }
-  ~ContextLease() {
-    if (!mine) return;
-    t_ctx = prev;
-    {
-      std::lock_guard<std::mutex> lock(ix.mu);
-      ix.last_stats = mine->stats;
-      ix.free_contexts.push_back(mine);
-    }
-    ix.cv.notify_one();
-  }
-};
+// A context of the index's pool, to be made t_ctx by the caller; every release publishes its stats as the handle's and
+// puts the thread's earlier context back.
+auto lease_search_context(const DeviceIndex &ix) {
+  auto give_back = [&ix, prev = t_ctx] { ix.last_stats = t_ctx->stats; t_ctx = prev; };
+  return ContextLease(ix.search_contexts, make_context<DeviceIndex::SearchContext>, give_back);
+}
+
+void fill_phase_times(vi_search_stats &s, const hipEvent_t *ev, int level) {
+  if (level) (void)hipEventElapsedTime(&s.ms_scan, ev[2], ev[3]);
+  if (level != 1) return;
+  (void)hipEventElapsedTime(&s.ms_coarse, ev[0], ev[1]);
+  (void)hipEventElapsedTime(&s.ms_group, ev[1], ev[2]);
+  (void)hipEventElapsedTime(&s.ms_merge, ev[3], ev[4]);
+  (void)hipEventElapsedTime(&s.ms_total, ev[0], ev[4]);
+}
 }  // namespace
 
 // ------------------------------------------------------------------------------------------
@@ -818,8 +791,9 @@ EngineKnobs read_engine_knobs() {
 
 vi_status device_index_search(const DeviceIndex &ix, const SearchIO &io) {
   VI_HIP(hipSetDevice(ix.device));
-  ContextLease lease(ix);
-  VI_TRY(lease.acquire());
+  auto lease = lease_search_context(ix);
+  if (!lease.ctx) return VI_ERR_DEVICE;  // (the message is make_context's)
+  t_ctx = lease.ctx;
   hipStream_t st = ix.cur().stream;
   SearchWorkspace &ws = ix.cur().ws;
   const uint64_t nq = io.nq, k = io.k;
@@ -915,13 +889,7 @@ vi_status device_index_search(const DeviceIndex &ix, const SearchIO &io) {
     }
   }
   VI_HIP(hipStreamSynchronize(st));
-  if (timing) (void)hipEventElapsedTime(&stt.ms_scan, ix.cur().ev[2], ix.cur().ev[3]);
-  if (timing == 1) {
-    (void)hipEventElapsedTime(&stt.ms_coarse, ix.cur().ev[0], ix.cur().ev[1]);
-    (void)hipEventElapsedTime(&stt.ms_group, ix.cur().ev[1], ix.cur().ev[2]);
-    (void)hipEventElapsedTime(&stt.ms_merge, ix.cur().ev[3], ix.cur().ev[4]);
-    (void)hipEventElapsedTime(&stt.ms_total, ix.cur().ev[0], ix.cur().ev[4]);
-  }
+  fill_phase_times(stt, ix.cur().ev, timing);
   return VI_OK;
 }
 
@@ -975,8 +943,9 @@ vi_status range_result_place(RangeResult *res, uint64_t q0, uint64_t m, const ui
 
 vi_status device_index_range_search(const DeviceIndex &ix, const RangeIO &io, RangeResult *out) {
   VI_HIP(hipSetDevice(ix.device));
-  ContextLease lease(ix);
-  VI_TRY(lease.acquire());
+  auto lease = lease_search_context(ix);
+  if (!lease.ctx) return VI_ERR_DEVICE;  // (the message is make_context's)
+  t_ctx = lease.ctx;
   hipStream_t st = ix.cur().stream;
   SearchWorkspace &ws = ix.cur().ws;
   const uint64_t nq = io.nq, nlists = ix.nlists;
@@ -1009,13 +978,7 @@ vi_status device_index_range_search(const DeviceIndex &ix, const RangeIO &io, Ra
     VI_HIP(hipGetLastError());
   }
   VI_HIP(hipStreamSynchronize(st));
-  if (timing) (void)hipEventElapsedTime(&stt.ms_scan, ix.cur().ev[2], ix.cur().ev[3]);
-  if (timing == 1) {
-    (void)hipEventElapsedTime(&stt.ms_coarse, ix.cur().ev[0], ix.cur().ev[1]);
-    (void)hipEventElapsedTime(&stt.ms_group, ix.cur().ev[1], ix.cur().ev[2]);
-    (void)hipEventElapsedTime(&stt.ms_merge, ix.cur().ev[3], ix.cur().ev[4]);
-    (void)hipEventElapsedTime(&stt.ms_total, ix.cur().ev[0], ix.cur().ev[4]);
-  }
+  fill_phase_times(stt, ix.cur().ev, timing);
   return VI_OK;
 }
 

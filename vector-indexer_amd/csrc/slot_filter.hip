@@ -6,6 +6,7 @@
 
 #include "device_index.hpp"
 #include "id_table.hpp"
+#include "list_layout.hpp"
 #include "rank_stream.hpp"
 #include "slot_filter.hpp"
 
@@ -13,14 +14,6 @@ namespace vi {
 namespace {
 
 constexpr int kWave = 64;
-constexpr uint32_t kListSplit = 8;  // workgroups sharing the blocks of one list (long lists carry most of an index)
-
-// the list layout, taken as pad_norms_kernel takes it (first block and length of every list; lists that are not resident
-// here have length 0)
-struct FilterLists {
-  const uint32_t *first_block, *list_len;
-  uint32_t nlists;
-};
 
 // what every filter is made of: the index's norm arrays, the filter's masked copies of them, its allow words, its count
 struct FilterOut {
@@ -76,19 +69,14 @@ struct IntersectPred {
   }
 };
 
-// One wave per 64-vector block, kListSplit workgroups of four waves per list.  Lane = vector of the block: its allow bit
-// is the predicate AND `position below the list length`.
+// The walk of list_layout.hpp: a slot's allow bit is the predicate AND `position below the list length`.
 template <class Pred>
-__global__ void __launch_bounds__(256) slot_filter_kernel(FilterLists L, FilterOut o, Pred pred) {
-  const uint32_t l = blockIdx.x, lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  if (l >= L.nlists) return;
-  const uint32_t len = L.list_len[l], fb = L.first_block[l], nblk = (len + 63u) / 64u;
+__global__ void __launch_bounds__(256) slot_filter_kernel(ResidentLists L, FilterOut o, Pred pred) {
   uint32_t n = 0;
-  for (uint32_t b = blockIdx.y * 4u + wave; b < nblk; b += gridDim.y * 4u) {  // (wave-uniform)
-    const bool ok = pred(fb + b, lane, b * 64u + lane < len);
-    n += write_filter_block(o, fb + b, lane, ok);
-  }
-  if (lane == 0 && n) atomicAdd(o.count, (unsigned long long)n);
+  for_each_resident_block(L, [&](uint32_t block, uint32_t lane, bool resident) {
+    n += write_filter_block(o, block, lane, pred(block, lane, resident));
+  });
+  if ((threadIdx.x & 63u) == 0 && n) atomicAdd(o.count, (unsigned long long)n);
 }
 
 // The part every filter shares: the buffers of *f, the zeroed count, one launch of the kernel with `pred`, the count.
@@ -110,9 +98,9 @@ vi_status build_filter(const DeviceIndex &ix, const Pred &pred, SlotFilter *f, c
   VI_HIP(hipMemsetAsync(cnt.p, 0, sizeof(unsigned long long), st));
   VI_HIP(hipMemsetAsync(f->allow.p, 0, std::max<uint64_t>(1, nb) * sizeof(uint64_t), st));
   if (nb && ix.nlists) {
-    FilterLists L{ix.list_first_block.p, ix.list_len.p, (uint32_t)ix.nlists};
+    ResidentLists L{ix.list_first_block.p, ix.list_len.p, (uint32_t)ix.nlists};
     FilterOut o{ix.xnorm.p, ix.xnorm_img.p, ix.i8_norm_img.p, f->allow.p, f->xnorm.p, f->xnorm_img.p, f->i8_norm_img.p, cnt.p};
-    hipLaunchKernelGGL(slot_filter_kernel<Pred>, dim3((uint32_t)ix.nlists, kListSplit), dim3(256), 0, st, L, o, pred);
+    hipLaunchKernelGGL(slot_filter_kernel<Pred>, slot_walk_grid((uint32_t)ix.nlists), dim3(256), 0, st, L, o, pred);
     VI_HIP(hipGetLastError());
   }
   unsigned long long n = 0;
@@ -136,32 +124,12 @@ vi_status slot_filter_ids(const DeviceIndex &ix, const uint64_t *ids, uint64_t n
   if (!ix.ext_ids.p) return fail(VI_ERR_INVALID_INPUT, "this index keeps no external ids");
   if (n > (1ull << 40)) return fail(VI_ERR_INVALID_INPUT, "id set of %llu ids is too large", (unsigned long long)n);
   VI_HIP(hipSetDevice(ix.device));
-  hipStream_t st = ix.stream;
-  const uint64_t capacity = id_table_capacity(n);
-  // the table, the flags and the uploaded copy of host ids live until this function returns
-  DevBuf<unsigned long long> words;
-  DevBuf<uint32_t> flags;
-  DevBuf<uint64_t> upload;
-  VI_TRY(words.reserve(capacity));
-  VI_TRY(flags.reserve(2));
-  VI_HIP(hipMemsetAsync(words.p, 0xff, capacity * sizeof(unsigned long long), st));  // every word kEmptyKey
-  VI_HIP(hipMemsetAsync(flags.p, 0, 2 * sizeof(uint32_t), st));
-  IdTable t{words.p, capacity - 1, flags.p};
-  if (n) {
-    if (!ids_on_device) {
-      VI_TRY(upload.reserve(n));
-      VI_HIP(hipMemcpyAsync(upload.p, ids, n * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-      ids = upload.p;
-    }
-    const uint32_t grid = (uint32_t)std::min<uint64_t>((n + 255) / 256, 65536);
-    hipLaunchKernelGGL(id_table_insert_kernel, dim3(grid), dim3(256), 0, st, t, ids, n);
-    VI_HIP(hipGetLastError());
-  }
+  IdSetBuffers set;  // lives until this function returns
+  IdTable t;
+  VI_TRY(id_set_build(set, ids, n, ids_on_device, 0, ix.stream, &t));
   uint32_t fl[2] = {0, 0};
-  VI_TRY(build_filter(ix, IdPred{ix.ext_ids.p, t, exclude}, f, flags.p, fl));
-  if (fl[1]) return fail(VI_ERR_DEVICE, "id filter: the id table (capacity %llu for %llu ids) overflowed",
-                         (unsigned long long)capacity, (unsigned long long)n);
-  return VI_OK;
+  VI_TRY(build_filter(ix, IdPred{ix.ext_ids.p, t, exclude}, f, set.flags.p, fl));
+  return id_set_check(fl, t, n, "id filter");
 }
 
 vi_status slot_filter_intersect(const DeviceIndex &ix, const SlotFilter &a, const SlotFilter &b, SlotFilter *f) {
