@@ -267,3 +267,59 @@ def test_concurrent_batches_of_different_shapes_on_one_handle(tmp_path):
     [t.join() for t in ts]
     assert not errors, errors[0]
     assert idx.last_stats()["nq"] in {s[0] for s in shapes}
+
+
+@pytest.mark.parametrize("engine_env", [{}, {"VI_FILTER": "0"}, {"VI_FORCE_GENERIC": "1"}], ids=["mfma", "valu", "generic"])
+def test_two_handles_interleaved_and_concurrent(tmp_path, monkeypatch, engine_env):
+    """two indexes in one process, searched in turn from one thread and at once from two: every result is bitwise the
+    one its handle gives alone, and each handle's last_stats() is of its own last search — per engine (default: MFMA;
+    VI_FILTER=0: exact-order VALU; VI_FORCE_GENERIC=1: generic).  The shapes are the smallest with several lists, a
+    second probe and a partly filled last block."""
+    for name, value in engine_env.items():
+        monkeypatch.setenv(name, value)
+    rng = np.random.default_rng(29)
+    XA = rng.integers(0, 41, size=(300, 8)).astype(np.float32)
+    XB = rng.standard_normal((500, 16)).astype(np.float32)
+    QA = rng.integers(0, 41, size=(5, 8)).astype(np.float32)
+    QB = (XB[:7] + 0.05 * rng.standard_normal((7, 16))).astype(np.float32)
+    a = vip.build(XA, str(tmp_path / "a"), nlist=6)
+    b = vip.build(XB, str(tmp_path / "b"), nlist=9)
+    calls = {"a": (a, QA, 3, 2), "b": (b, QB, 4, 3)}  # handle, queries, k, n_probe
+
+    def same(got, want):
+        return (got[1] == want[1]).all() and (got[0].view(np.uint32) == want[0].view(np.uint32)).all()
+
+    solo, solo_stats = {}, {}
+    for name, (idx, Q, k, p) in calls.items():
+        solo[name] = idx.search_sync(Q, k, p)
+        solo_stats[name] = idx.last_stats()
+        assert solo_stats[name]["nq"] == len(Q) and solo_stats[name]["n_probe_eff"] == p
+    # a radius around each query of B that holds its own near copy and a few more: 1 to 20 hits per query
+    radius2 = float(np.median(solo["b"][0][:, 1]))
+    solo_range = b.range_search_sync(QB, radius2, 3)
+    hits = np.diff(solo_range[0].astype(np.int64))
+    assert hits.min() >= 1 and hits.max() <= 20, hits
+
+    for name in ("a", "b", "a", "b"):  # interleaved on one thread
+        idx, Q, k, p = calls[name]
+        assert same(idx.search_sync(Q, k, p), solo[name]), name
+        st = idx.last_stats()
+        assert st["nq"] == len(Q) and st["n_probe_eff"] == p and st["k"] == k, (name, st)
+
+    errors = []
+
+    def worker(name):
+        try:
+            idx, Q, k, p = calls[name]
+            for _ in range(6):
+                assert same(idx.search_sync(Q, k, p), solo[name]), name
+                if name == "b":
+                    lims, D, I = idx.range_search_sync(Q, radius2, p)
+                    assert (lims == solo_range[0]).all() and (I == solo_range[2]).all(), name
+                    assert (D.view(np.uint32) == solo_range[1].view(np.uint32)).all(), name
+        except BaseException as e:  # noqa: BLE001
+            errors.append(e)
+    ts = [threading.Thread(target=worker, args=(name,)) for name in calls]
+    [t.start() for t in ts]
+    [t.join() for t in ts]
+    assert not errors, errors[0]

@@ -53,7 +53,6 @@ struct SearchWorkspace {
   // the scans inside list_totals_kernel (grouping.hip: GroupScanArgs) instead of the three arrays above: per list (pairs; items, segment
   // runs, record tiles before it within its 64 lists), per 64 lists their sums; item_push_kernel adds the two up
   DevBuf<uint32_t> list_local, list_block_sums;  // [nlists] x 4, [kGroupScanBlocks] x 4
-  bool group_counts_cleared = false;        // the grouping's counts of ws.stats were cleared by this search's split_queries_kernel
   DevBuf<float> seg_run_dist;  // segment runs of long lists, merged by seg_merge_kernel
   DevBuf<uint32_t> seg_run_pos;
   DevBuf<uint32_t> pairs;       // [nq*P] slot ids grouped by list
@@ -66,12 +65,11 @@ struct SearchWorkspace {
   DevBuf<uint32_t> counts;      // [nq]
   DevBuf<uint64_t> stats;       // device-side counters (layout: StatWord, search_internal.hpp)
   DevBuf<float> V;
-  // MFMA filter path (filter_search.hip)
+  // MFMA engine (filter_search.hip)
   DevBuf<uint32_t> c_seg, c_item, c_pairs;  // the coarse table grouped as one list ...
   uint64_t c_nq = 0;                        // ... for this batch size
   DevBuf<uint32_t> pair_rel, qtot, qoff;    // group-record offsets: per (query, probe), per query, scan over queries
   DevBuf<uint32_t> pair_rank;               // a pair's place among the pairs of its (list, sub-bin): from the direct coarse select
-  bool pair_rank_valid = false;             // ... filled by this search
   DevBuf<uint32_t> item_list;               // list of each rank work item
   DevBuf<uint32_t> items;                   // ... or its whole descriptor (8 words), item_desc_kernel (grouping.hip)
   DevBuf<uint64_t> prof;                    // diagnostic counters (VI_STREAM_PROF)
@@ -159,7 +157,7 @@ struct DeviceIndex {
   bool centered = false;
   DevBuf<float> centre;  // mu: dq * 4 floats (zero beyond dim)
   float mean_norm2_c = 0.0f, xmax2_c = 0.0f, cent_xmax2_c = 0.0f;  // ... and the norms about mu
-  float xmax2 = 0.0f;                 // max squared norm of a stored vector (MFMA filter margin)
+  float xmax2 = 0.0f;                 // max squared norm of a stored vector (MFMA engine's rank margin)
   DevBuf<float> cent_xnorm;           // same for the coarse table
   DevBuf<float> cent_rows;            // the coarse table row-major (coarse select: single-row exact re-evaluation)
   float cent_xmax2 = 0.0f;
@@ -167,7 +165,8 @@ struct DeviceIndex {
   hipStream_t stream = nullptr;       // uploads and index construction
   // Searches: the reference's search is &self and runs concurrently from several OS threads
   // (tests/ivf_index_tests.rs:768-807).  A search holds one SearchContext of the pool (context_pool.hpp) — its own
-  // stream, events, workspace — for the duration of the call: up to four calls run at once on one handle.
+  // stream, events, workspace — for the duration of the call: up to four calls run at once on one handle.  The call's
+  // SearchBatch (search_internal.hpp) carries it to every stage; what is in it outlives the search (grow-only buffers, gq_hint, ...).
   struct SearchContext : StreamEvents<6> {
     SearchWorkspace ws;
     vi_search_stats stats{};
@@ -175,7 +174,6 @@ struct DeviceIndex {
   };
   mutable ContextPool<SearchContext, 4> search_contexts;
   mutable vi_search_stats last_stats{};  // of the most recent search that finished on this handle (under the pool's lock)
-  SearchContext &cur() const;         // the context the calling thread holds (device_index_search acquired it)
   int timing = 0;  // 0 off, 1 HIP events at every phase boundary, 2 around the list-rank kernel only
   mutable FetchState fetch;  // gets and exports: const on the index, like searches
 
@@ -272,18 +270,18 @@ vi_status device_index_range_search(const DeviceIndex &ix, const RangeIO &io, Ra
 // host copies of a result: lims (nq + 1), D, I (total each), V (optional, total x dim: the stored vectors)
 vi_status range_result_copy(const RangeResult &r, uint64_t *lims, float *D, int64_t *I, float *V);
 
-// The search engines' environment options (filter_search.hip, search_kernels.hip), read once per device_index_search
-// call by read_engine_knobs.  A '0' as the first character turns an on-by-default option off.
+// The search engines' environment options, read once per search by read_engine_knobs (search.hip) into the call's SearchBatch.
+// A '0' as the first character turns an on-by-default option off.  (The MFMA engine's variables keep its first name, VI_FILTER.)
 struct EngineKnobs {
   bool force_generic;       // VI_FORCE_GENERIC (non-zero): the generic engine
   uint32_t force_qg;        // VI_FORCE_QG: queries per group of the VALU list scan (0: chosen)
   uint32_t seg_blocks;      // VI_SEG_BLOCKS: blocks per list segment of the VALU list scan
-  bool filter;              // VI_FILTER=0: the VALU engine instead of the MFMA engine
+  bool mfma;                // VI_FILTER=0: the VALU engine instead of the MFMA engine
   bool rank_bf16;           // VI_FILTER_BF16=0: rank with f32 MFMAs instead of bf16 x 3
   bool hi_only;             // VI_FILTER_HI_ONLY=0: never rank from the hi planes alone
   int rank_approx;          // VI_RANK_APPROX: hi-plane ranking of real-valued lists, 0..2 (-1: chosen per index)
   bool debug_approx;        // VI_DEBUG_APPROX: print what rank_approx_mode chose by
-  bool coarse_filter;       // VI_COARSE_FILTER=0: never run the coarse step on the matrix cores
+  bool coarse_mfma;         // VI_COARSE_FILTER=0: never run the coarse step on the matrix cores
   bool coarse_direct;       // VI_COARSE_DIRECT=0: the coarse select with group records on tables of <= 256 blocks too
   uint32_t segb0;           // VI_FILTER_SEGB: blocks per list segment of the MFMA list phase
   uint32_t gq;              // VI_FILTER_GQ: queries per rank work item, 32 or 128 (0: chosen)
@@ -296,7 +294,7 @@ struct EngineKnobs {
   bool scan_in_totals;      // VI_SCAN_IN_TOTALS=0: the grouping's scans by group_prepare_kernel, a launch of its own, as everywhere without item_push
   bool stream_prof;         // VI_STREAM_PROF: clock the streaming rank kernel
   const char *stream_prof_dump;  // VI_STREAM_PROF_DUMP: file for its per-workgroup clocks, or null
-  uint32_t filter_xmode;    // VI_FILTER_XMODE: rank kernel ablations
+  uint32_t rank_xmode;      // VI_FILTER_XMODE: rank kernel ablations
   uint32_t select_xmode;    // VI_SELECT_XMODE: list select ablations (wrong results)
   uint32_t coarse_xmode;    // VI_SELECT_XMODE_COARSE: coarse select ablations (wrong results)
   // VI_FILTER_STATS (set): the selects' counters; '2': the coarse select's instead, and its clocks; '3' / '4': print

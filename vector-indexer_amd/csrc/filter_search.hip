@@ -24,7 +24,8 @@
 // The coarse quantizer (ivf_index.rs:205-220) is the same computation with the centroid table as one
 // list probed by every query and K = n_probe.
 //
-// Host side: which rank kernel a batch takes is decided first (RankPlan), then search_filter_pipeline runs its steps.
+// Host side: the dispatcher (search.hip) hands the pipelines their SearchBatch; which rank kernel it takes is decided first (RankPlan).
+// ("filter" in this file's name, its kernels and the VI_FILTER variables is the engine's first name; in host code it means a SlotFilter.)
 // The grouping between the coarse step and the rank, and the kernels that build the rank work items, are grouping.hip's.
 #include <hip/hip_runtime.h>
 
@@ -602,7 +603,7 @@ __global__ void __launch_bounds__(256, 1) rank_wide_kernel(WideArgs a) {
 
 
 template <int NG>
-vi_status launch_filter_t(const FilterArgs &a, uint32_t nitems, int rank_mode, uint32_t gq, hipStream_t st) {
+vi_status launch_mfma_rank_t(const FilterArgs &a, uint32_t nitems, int rank_mode, uint32_t gq, hipStream_t st) {
   if (nitems == 0) return VI_OK;
   const bool table = a.qoff == nullptr;
   const dim3 grid(nitems);
@@ -628,17 +629,17 @@ vi_status launch_filter_t(const FilterArgs &a, uint32_t nitems, int rank_mode, u
   return VI_OK;
 }
 
-vi_status launch_filter(const FilterArgs &a, uint32_t dq, uint32_t nitems, int rank_mode, uint32_t gq, hipStream_t st) {
+vi_status launch_mfma_rank(const FilterArgs &a, uint32_t dq, uint32_t nitems, int rank_mode, uint32_t gq, hipStream_t st) {
   switch (dq / 2) {  // dq is a multiple of 4
-    case 2: return launch_filter_t<2>(a, nitems, rank_mode, gq, st);
-    case 4: return launch_filter_t<4>(a, nitems, rank_mode, gq, st);
-    case 6: return launch_filter_t<6>(a, nitems, rank_mode, gq, st);
-    case 8: return launch_filter_t<8>(a, nitems, rank_mode, gq, st);
-    case 10: return launch_filter_t<10>(a, nitems, rank_mode, gq, st);
-    case 12: return launch_filter_t<12>(a, nitems, rank_mode, gq, st);
-    case 14: return launch_filter_t<14>(a, nitems, rank_mode, gq, st);
-    case 16: return launch_filter_t<16>(a, nitems, rank_mode, gq, st);
-    default: return fail(VI_ERR_OTHER, "unsupported dimension for the MFMA filter");
+    case 2: return launch_mfma_rank_t<2>(a, nitems, rank_mode, gq, st);
+    case 4: return launch_mfma_rank_t<4>(a, nitems, rank_mode, gq, st);
+    case 6: return launch_mfma_rank_t<6>(a, nitems, rank_mode, gq, st);
+    case 8: return launch_mfma_rank_t<8>(a, nitems, rank_mode, gq, st);
+    case 10: return launch_mfma_rank_t<10>(a, nitems, rank_mode, gq, st);
+    case 12: return launch_mfma_rank_t<12>(a, nitems, rank_mode, gq, st);
+    case 14: return launch_mfma_rank_t<14>(a, nitems, rank_mode, gq, st);
+    case 16: return launch_mfma_rank_t<16>(a, nitems, rank_mode, gq, st);
+    default: return fail(VI_ERR_OTHER, "unsupported dimension for the MFMA engine");
   }
 }
 
@@ -701,7 +702,7 @@ RankPlan plan_rank(const DeviceIndex &ix, const EngineKnobs &kn, uint64_t nq, ui
   const bool stream = !wide && kn.rank_bf16 && p.hi_lists && !kn.stream_off &&
                       (dq / 4 >= 7 || kn.stream_force || (p.approx != 0 && dq / 4 >= 5));
   p.kernel = wide ? RankKernel::Wide : stream ? RankKernel::Stream : RankKernel::Block;
-  // (the wide kernel multiplies bf16 x 3 whatever the lists hold: filter_path_applicable)
+  // (the wide kernel multiplies bf16 x 3 whatever the lists hold: mfma_path_applicable)
   p.math = !kn.rank_bf16 ? RankMath::F32 : (p.hi_lists && !wide) ? RankMath::HiPlanes : RankMath::Bf16x3;
   switch (p.kernel) {
     case RankKernel::Wide:  // the wide kernel's C tile holds 128 queries
@@ -764,11 +765,13 @@ uint64_t rank_mode_code(const DeviceIndex &ix, const RankPlan &p) {
 // ------------------------------------------------------------------------------------------
 // The centroid table is one "list" probed by every query.
 // Leaves probes / gorder and the per-list histogram (ws.cnt) behind, like stage_coarse.
-vi_status stage_coarse_filter(const DeviceIndex &ix, const EngineKnobs &kn, const float *Qd, uint64_t nq, uint32_t P, hipStream_t st,
-                              bool histogram_cleared = false) {
-  SearchWorkspace &ws = ix.cur().ws;
-  const uint32_t dim = ix.dim, dq = ix.dq;
-  const uint64_t nlists = ix.nlists;
+static vi_status stage_coarse_mfma(SearchBatch &b, bool histogram_cleared = false) {
+  const DeviceIndex &ix = b.ix;
+  const EngineKnobs &kn = b.kn;
+  SearchWorkspace &ws = b.ws();
+  hipStream_t st = b.st();
+  const uint32_t P = b.P, dim = ix.dim, dq = ix.dq;
+  const uint64_t nq = b.nq, nlists = ix.nlists;
   VI_TRY(ws.cnt.reserve(2 * subbin_words(nlists)));
   if (!histogram_cleared) VI_HIP(hipMemsetAsync(ws.cnt.p, 0, subbin_words(nlists) * sizeof(uint32_t), st));
   VI_TRY(ws.probes.reserve(nq * P));
@@ -799,7 +802,7 @@ vi_status stage_coarse_filter(const DeviceIndex &ix, const EngineKnobs &kn, cons
   }
   FilterArgs a{};
   a.blocks = kn.rank_bf16 ? (const float4 *)ix.cent_bf16.p : (const float4 *)ix.centroids.blocks.p;
-  a.xnorm = kn.rank_bf16 ? ix.cent_xnorm_img.p : ix.cent_xnorm.p; a.dq = dq; a.dim = dim; a.Q = Qd;
+  a.xnorm = kn.rank_bf16 ? ix.cent_xnorm_img.p : ix.cent_xnorm.p; a.dq = dq; a.dim = dim; a.Q = b.Qd;
   a.first_block = ix.c_first.p; a.list_len = ix.c_len.p; a.item_start = ws.c_item.p; a.seg_start = ws.c_seg.p;
   a.pairs = ws.c_pairs.p; a.nlists = 1; a.P = 1; a.segb0 = segb0;
   a.qoff = nullptr; a.rel = nullptr; a.rec_stride = recs;
@@ -807,12 +810,12 @@ vi_status stage_coarse_filter(const DeviceIndex &ix, const EngineKnobs &kn, cons
   a.gval = (float4 *)ws.gval.p; a.gmeta = ws.gpos.p; a.brec = (float4 *)ws.brec.p;
   a.direct = direct ? 1u : 0u;
   a.qimg = kn.rank_bf16 ? (const uint4 *)ws.qimg.p : nullptr;
-  VI_TRY(launch_filter(a, dq, ngroups * nseg, kn.rank_bf16 ? (ix.cent_lo_zero && kn.hi_only ? 2 : 1) : 0, kGroupQ, st));
-  return launch_coarse_select(ix, kn, Qd, nq, P, segb, recs, direct, st);
+  VI_TRY(launch_mfma_rank(a, dq, ngroups * nseg, kn.rank_bf16 ? (ix.cent_lo_zero && kn.hi_only ? 2 : 1) : 0, kGroupQ, st));
+  return launch_coarse_select(b, segb, recs, direct);
 }
 
-bool filter_path_applicable(const DeviceIndex &ix, const EngineKnobs &kn, uint64_t k, uint32_t P) {
-  if (!kn.filter) return false;
+bool mfma_path_applicable(const DeviceIndex &ix, const EngineKnobs &kn, uint64_t k, uint32_t P) {
+  if (!kn.mfma) return false;
   if (ix.order != VI_ORDER_SCALAR || ix.dim > kMaxFilterDim || (ix.dim & 3) || ix.dim < 4) return false;
   if (ix.dim > kNarrowDim && !kn.rank_bf16) return false;  // the wide kernel ranks with bf16 x 3 only
   if (k > 2 * kMaxSelect || P > kMaxSelect || P < 1) return false;  // k <= 128 (WaveTop128), n_probe <= 64
@@ -823,17 +826,19 @@ bool filter_path_applicable(const DeviceIndex &ix, const EngineKnobs &kn, uint64
   return true;
 }
 
-// the coarse step on the matrix cores (stage_coarse_filter) rather than the VALU one (stage_coarse): batches of >= 256
+// the coarse step on the matrix cores (stage_coarse_mfma) rather than the VALU one (stage_coarse): batches of >= 256
 // queries against tables of >= 1024 lists, D <= 128 (filter_kernel keeps a query in registers)
 bool coarse_on_matrix_cores(const DeviceIndex &ix, const EngineKnobs &kn, uint64_t nq, uint32_t P) {
-  return filter_path_applicable(ix, kn, 1, P) && kn.coarse_filter && nq >= 256 && ix.nlists >= 1024 && ix.dim <= kNarrowDim;
+  return mfma_path_applicable(ix, kn, 1, P) && kn.coarse_mfma && nq >= 256 && ix.nlists >= 1024 && ix.dim <= kNarrowDim;
 }
 
 // the batch's queries as MFMA operands: -2 q split into bf16 hi / lo once (a query sits in n_probe work items)
-static vi_status build_query_image(const DeviceIndex &ix, const EngineKnobs &kn, const float *Qd, uint64_t nq, hipStream_t st,
-                                   uint32_t *zero = nullptr, uint64_t zero_words = 0) {
-  if (!kn.rank_bf16) return VI_OK;
-  SearchWorkspace &ws = ix.cur().ws;
+static vi_status build_query_image(SearchBatch &b, uint32_t *zero = nullptr, uint64_t zero_words = 0) {
+  if (!b.kn.rank_bf16) return VI_OK;
+  const DeviceIndex &ix = b.ix;
+  SearchWorkspace &ws = b.ws();
+  const uint64_t nq = b.nq;
+  hipStream_t st = b.st();
   const uint32_t nc = ix.dq / 4;
   VI_TRY(ws.qimg.reserve((uint64_t)nq * nc * 4 * 4));  // uint32 words: 4 pieces of 16 B per (query, chunk)
   const bool i8 = ix.lists_i8.p != nullptr;  // the lists have an int8 image: the batch's too (rank_stream_i8_kernel)
@@ -845,70 +850,55 @@ static vi_status build_query_image(const DeviceIndex &ix, const EngineKnobs &kn,
     ws.stats_zeroed = true;
   }
   const uint64_t nt = (uint64_t)nq * nc * 2;
-  hipLaunchKernelGGL(split_queries_kernel, dim3((uint32_t)((nt + 255) / 256)), dim3(256), 0, st, Qd, (uint32_t)nq, ix.dim, nc,
+  hipLaunchKernelGGL(split_queries_kernel, dim3((uint32_t)((nt + 255) / 256)), dim3(256), 0, st, b.Qd, (uint32_t)nq, ix.dim, nc,
                      (uint4 *)ws.qimg.p, (unsigned long long *)(ws.stats.p + kStatQueryLo), zero, (uint32_t)zero_words,
                      ix.centered ? (const float *)ix.centre.p : nullptr, i8 ? (uint2 *)ws.qimg8.p : nullptr,
                      (unsigned long long *)(ws.stats.p + kStatQueryNotI8), ws.stats.p);
-  ws.group_counts_cleared = true;  // (rank_lists lowers it at the head of every search)
+  b.group_counts_cleared = true;
   VI_HIP(hipGetLastError());
   return VI_OK;
 }
 
 // coarse step alone on the matrix cores (probe export for other ranks): fills ws.probes / ws.gorder
-vi_status coarse_only_filter(const DeviceIndex &ix, const EngineKnobs &kn, const float *Qd, uint64_t nq, uint32_t P, hipStream_t st) {
-  SearchWorkspace &ws = ix.cur().ws;
-  VI_TRY(build_query_image(ix, kn, Qd, nq, st));
-  VI_TRY(ws.pair_rel.reserve(nq * P));
-  VI_TRY(ws.qtot.reserve(nq));
-  return stage_coarse_filter(ix, kn, Qd, nq, P, st);
+vi_status coarse_only_mfma(SearchBatch &b) {
+  VI_TRY(build_query_image(b));
+  VI_TRY(b.ws().pair_rel.reserve(b.nq * b.P));
+  VI_TRY(b.ws().qtot.reserve(b.nq));
+  return stage_coarse_mfma(b);
 }
 
 // ------------------------------------------------------------------------------------------
-// the steps of search_filter_pipeline, in the order they run on the search stream
+// the steps of the two pipelines, in the order they run on the search stream, each on the SearchBatch.  (b.flt swaps the norms
+// the LIST phase ranks with for its masked copies — excluded slots rank as pad slots do; the coarse phase keeps the table's.)
 // ------------------------------------------------------------------------------------------
 namespace {
 
-// what every step works from
-struct Batch {
-  const DeviceIndex &ix;
-  const EngineKnobs &kn;
-  const float *Qd;
-  uint64_t nq;
-  uint32_t P;
-  const SlotFilter *flt;  // a filter swaps the norms the LIST phase ranks with for its masked copies (excluded slots rank as
-                          // pad slots do); the coarse phase keeps the table's own
-  hipStream_t st;
-  bool rank_timing;  // the rank kernel is timed: an event in front of it and one behind
-  bool rank_clock_started = false;
-  bool items_pushed = false;  // the grouping's scatter left the streaming rank kernel's work items behind (item_push_kernel)
-  SearchWorkspace &ws() const { return ix.cur().ws; }
-  // (the phase clock of the rank kernel starts right in front of it: the work-item helper kernels count as grouping)
-  vi_status start_rank_clock() {
-    if (rank_timing && !rank_clock_started) VI_HIP(hipEventRecord(ix.cur().ev[2], st));
-    rank_clock_started = true;
-    return VI_OK;
-  }
-};
+// (the phase clock of the rank kernel starts right in front of it: the work-item helper kernels count as grouping)
+vi_status start_rank_clock(SearchBatch &b) {
+  if (b.timing && !b.rank_clock_started) VI_HIP(hipEventRecord(b.ctx.ev[2], b.st()));
+  b.rank_clock_started = true;
+  return VI_OK;
+}
 
 // ---- 1. coarse quantizer: the queries' image, then probes, shard visiting order, per-list histogram, record offsets ----
-vi_status coarse_phase(const Batch &b, const uint32_t *probes_in, const uint32_t *order_in) {
+vi_status coarse_phase(SearchBatch &b) {
   SearchWorkspace &ws = b.ws();
   VI_TRY(ws.pair_rel.reserve(b.nq * b.P));
   VI_TRY(ws.qtot.reserve(b.nq));
-  const bool coarse_mfma = !probes_in && coarse_on_matrix_cores(b.ix, b.kn, b.nq, b.P);
+  const bool coarse_mfma = !b.probes_in && coarse_on_matrix_cores(b.ix, b.kn, b.nq, b.P);
   const bool histogram_cleared = coarse_mfma && b.kn.rank_bf16;
   if (histogram_cleared) {  // (the coarse step's per-list histogram is cleared by the kernel that splits the queries)
     VI_TRY(ws.cnt.reserve(2 * subbin_words(b.ix.nlists)));
-    VI_TRY(build_query_image(b.ix, b.kn, b.Qd, b.nq, b.st, ws.cnt.p, subbin_words(b.ix.nlists)));
+    VI_TRY(build_query_image(b, ws.cnt.p, subbin_words(b.ix.nlists)));
   } else {
-    VI_TRY(build_query_image(b.ix, b.kn, b.Qd, b.nq, b.st));
+    VI_TRY(build_query_image(b));
   }
   if (coarse_mfma) {
-    VI_TRY(stage_coarse_filter(b.ix, b.kn, b.Qd, b.nq, b.P, b.st, histogram_cleared));
+    VI_TRY(stage_coarse_mfma(b, histogram_cleared));
   } else {
-    if (probes_in) VI_TRY(adopt_probes(b.ix, b.nq, b.P, probes_in, order_in, true, b.st));
-    else VI_TRY(stage_coarse(b.ix, b.Qd, b.nq, b.P, b.st));
-    hipLaunchKernelGGL(pair_groups_kernel, dim3((uint32_t)((b.nq + 255) / 256)), dim3(256), 0, b.st, ws.probes.p,
+    if (b.probes_in) VI_TRY(adopt_probes(b, true));
+    else VI_TRY(stage_coarse(b));
+    hipLaunchKernelGGL(pair_groups_kernel, dim3((uint32_t)((b.nq + 255) / 256)), dim3(256), 0, b.st(), ws.probes.p,
                        b.ix.list_len.p, (uint32_t)b.nq, b.P, b.kn.segb0, ws.pair_rel.p, ws.qtot.p);
   }
   // (the grouping scans the record offsets too: workgroups of list_totals_kernel, or the second of group_prepare_kernel)
@@ -934,18 +924,18 @@ void note_group_fill(SearchWorkspace &ws, uint64_t nq, uint32_t P, const Groupin
 
 // ---- 2. group all (query, probe) pairs by list; the counts come back (the pipeline's one synchronisation) and with them
 //      the two flags that complete the plan; the record buffers are sized by them ----
-vi_status group_pairs(Batch &b, RankPlan &plan, GroupingCounts &hstats) {
+vi_status group_pairs(SearchBatch &b, RankPlan &plan, GroupingCounts &hstats) {
   SearchWorkspace &ws = b.ws();
-  vi_search_stats &stt = b.ix.cur().stats;
+  vi_search_stats &stt = b.ctx.stats;
   VI_TRY(ws.qoff.reserve(b.nq + 1));
   // the streaming kernel's work items come out of the scatter itself when the coarse select left every pair's rank
-  b.items_pushed = b.kn.item_push && plan.kernel == RankKernel::Stream && ws.pair_rank_valid;
+  b.items_pushed = b.kn.item_push && plan.kernel == RankKernel::Stream && b.pair_rank_valid;
   GroupingRequest rq;
   rq.probes = ws.probes.p; rq.nq = b.nq; rq.P = b.P; rq.qg = plan.gq; rq.segb0 = b.kn.segb0; rq.histogram_done = true;
-  rq.qtot = ws.qtot.p; rq.qoff = ws.qoff.p; rq.pair_rank = ws.pair_rank_valid ? ws.pair_rank.p : nullptr;
-  rq.push_run = b.items_pushed ? b.kn.item_run : 0u; rq.counts_cleared = b.kn.scan_in_totals && ws.group_counts_cleared;
+  rq.qtot = ws.qtot.p; rq.qoff = ws.qoff.p; rq.pair_rank = b.pair_rank_valid ? ws.pair_rank.p : nullptr;
+  rq.push_run = b.items_pushed ? b.kn.item_run : 0u; rq.counts_cleared = b.kn.scan_in_totals && b.group_counts_cleared;
   rq.tile_start = rq.pair_pos = true;  // (the selects read both)
-  VI_TRY(group_probes(b.ix, rq, hstats, b.st));
+  VI_TRY(group_probes(b.ix, b.ctx, rq, hstats));
   note_group_fill(ws, b.nq, b.P, hstats);
   ws.queries_hi_only = hstats[kStatQueryLo] == 0;
   complete_rank_plan(plan, b.kn, hstats);
@@ -967,15 +957,15 @@ vi_status group_pairs(Batch &b, RankPlan &plan, GroupingCounts &hstats) {
   VI_TRY(grow(ws.item_grec, ncol));
   VI_TRY(grow(ws.item_sdesc, ndesc));
   VI_TRY(grow(ws.gpos, nrec));
-  return repush_items(b.ix, rq, b.st);
+  return repush_items(b.ix, ws, rq, b.st());
 }
 
 // ---- 3. rank on the matrix cores: one of the three below ----
 // D > 128: the GEMM-shaped kernel
-vi_status rank_wide(Batch &b, uint32_t nitems) {
+vi_status rank_wide(SearchBatch &b, uint32_t nitems) {
   SearchWorkspace &ws = b.ws();
   const DeviceIndex &ix = b.ix;
-  VI_TRY(launch_item_list(ix, nitems, b.st));
+  VI_TRY(launch_item_list(ix, ws, nitems, b.st()));
   if (nitems) {
     WideArgs a{(const uint4 *)ix.lists_bf16.p, b.flt ? b.flt->xnorm_img.p : ix.xnorm_img.p, (const uint4 *)ws.qimg.p, ix.dq / 4,
                ix.list_first_block.p, ix.list_len.p, ws.item_start.p, ws.seg_start.p, ws.pairs.p, ws.item_list.p, b.P, b.kn.segb0,
@@ -984,24 +974,19 @@ vi_status rank_wide(Batch &b, uint32_t nitems) {
     if (hipFuncSetAttribute((const void *)rank_wide_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                             kWideLdsFloats * (int)sizeof(float)) != hipSuccess)
       return fail(VI_ERR_DEVICE, "cannot reserve %d bytes of LDS for the wide rank kernel", kWideLdsFloats * 4);
-    VI_TRY(b.start_rank_clock());
-    hipLaunchKernelGGL(rank_wide_kernel, dim3(nitems), dim3(256), kWideLdsFloats * sizeof(float), b.st, a);
+    VI_TRY(start_rank_clock(b));
+    hipLaunchKernelGGL(rank_wide_kernel, dim3(nitems), dim3(256), kWideLdsFloats * sizeof(float), b.st(), a);
   }
   VI_HIP(hipGetLastError());
   return VI_OK;
 }
 
-// the work items' descriptors, for both kernels of D <= 128
-vi_status describe_items(const Batch &b, uint32_t gq, uint32_t nitems) {
-  return launch_item_desc(b.ix, b.kn, gq, nitems, b.st);
-}
-
 // (VI_STREAM_PROF) the streaming kernel's phase clocks, read back behind it: this step synchronises
-vi_status print_stream_profile(const Batch &b) {
+vi_status print_stream_profile(SearchBatch &b) {
   SearchWorkspace &ws = b.ws();
   uint64_t h[24];
-  VI_HIP(hipMemcpyAsync(h, ws.prof.p, sizeof(h), hipMemcpyDeviceToHost, b.st));
-  VI_HIP(hipStreamSynchronize(b.st));
+  VI_HIP(hipMemcpyAsync(h, ws.prof.p, sizeof(h), hipMemcpyDeviceToHost, b.st()));
+  VI_HIP(hipStreamSynchronize(b.st()));
   fprintf(stderr, "rank_stream wave-0 ticks (100 MHz) summed over workgroups: multiply %llu (of which waiting for tiles %llu) "
           "end-of-item wait %llu gather %llu merge %llu | items %llu steps %llu | loop total %llu\n",
           (unsigned long long)h[0], (unsigned long long)h[6], (unsigned long long)h[1], (unsigned long long)h[2],
@@ -1030,43 +1015,43 @@ vi_status print_stream_profile(const Batch &b) {
 
 // D <= 128, hi planes only: queries in LDS, vectors through registers, no barrier in the block loop, persistent workgroups
 // (rank_stream.hip), with int8 products when the plan says so
-vi_status rank_stream(Batch &b, const RankPlan &plan, uint32_t nitems) {
+vi_status rank_stream(SearchBatch &b, const RankPlan &plan, uint32_t nitems) {
   SearchWorkspace &ws = b.ws();
   const DeviceIndex &ix = b.ix;
   const uint32_t gq = plan.gq;
   if (!b.items_pushed) {  // (pushed: the columns stand, in buffers sized by group_pairs)
-    VI_TRY(describe_items(b, gq, nitems));
-    VI_TRY(launch_item_cols(ix, b.P, gq, nitems, b.st));
+    VI_TRY(launch_item_desc(ix, ws, b.kn, gq, nitems, b.st()));
+    VI_TRY(launch_item_cols(ws, b.P, gq, nitems, b.st()));
   }
   if (plan.rank_i8) {
     RankStreamI8Args a{(const uint4 *)ix.lists_i8.p, b.flt ? b.flt->i8_norm_img.p : ix.i8_norm_img.p, (const uint4 *)ws.qimg8.p,
                        (const uint4 *)ws.item_sdesc.p, nitems, ws.item_qcol.p, ws.item_grec.p,
                        (uint32_t *)(ws.stats.p + kStatRankWork), (float4 *)ws.gval.p, (float4 *)ws.brec.p};
-    VI_TRY(b.start_rank_clock());
-    return launch_rank_stream_i8(a, (ix.dim + 31) / 32, nitems, gq, b.st);
+    VI_TRY(start_rank_clock(b));
+    return launch_rank_stream_i8(a, (ix.dim + 31) / 32, nitems, gq, b.st());
   }
   RankStreamArgs a{(const uint4 *)ix.lists_bf16.p, b.flt ? b.flt->xnorm_img.p : ix.xnorm_img.p, (const uint4 *)ws.qimg.p,
                    (const uint4 *)ws.item_sdesc.p, nitems, ws.item_qcol.p, ws.item_grec.p, (uint32_t *)(ws.stats.p + kStatRankWork),
-                   (float4 *)ws.gval.p, (float4 *)ws.brec.p, nullptr, b.kn.filter_xmode};
+                   (float4 *)ws.gval.p, (float4 *)ws.brec.p, nullptr, b.kn.rank_xmode};
   if (b.kn.stream_prof) {
     VI_TRY(ws.prof.reserve(32 + 4 * 1024));
-    VI_HIP(hipMemsetAsync(ws.prof.p, 0, (32 + 4 * 1024) * sizeof(uint64_t), b.st));
-    VI_HIP(hipMemsetAsync(ws.prof.p + 16, 0xFF, sizeof(uint64_t), b.st));
+    VI_HIP(hipMemsetAsync(ws.prof.p, 0, (32 + 4 * 1024) * sizeof(uint64_t), b.st()));
+    VI_HIP(hipMemsetAsync(ws.prof.p + 16, 0xFF, sizeof(uint64_t), b.st()));
     a.prof = (unsigned long long *)ws.prof.p;
   }
-  VI_TRY(b.start_rank_clock());
+  VI_TRY(start_rank_clock(b));
   // (this kernel ranks hi planes only: plan.math is HiPlanes here)
-  VI_TRY(launch_rank_stream(a, ix.dq / 4, nitems, (int)plan.math, plan.qlo, gq, b.st));
+  VI_TRY(launch_rank_stream(a, ix.dq / 4, nitems, (int)plan.math, plan.qlo, gq, b.st()));
   if (b.kn.stream_prof) VI_TRY(print_stream_profile(b));
   return VI_OK;
 }
 
 // D <= 128, everything else: the block-synchronous kernel, in the plan's arithmetic
-vi_status rank_block(Batch &b, const RankPlan &plan, uint32_t nitems) {
+vi_status rank_block(SearchBatch &b, const RankPlan &plan, uint32_t nitems) {
   SearchWorkspace &ws = b.ws();
   const DeviceIndex &ix = b.ix;
   const bool bf16 = b.kn.rank_bf16;
-  VI_TRY(describe_items(b, plan.gq, nitems));
+  VI_TRY(launch_item_desc(ix, ws, b.kn, plan.gq, nitems, b.st()));
   FilterArgs a{};
   a.blocks = bf16 ? (const float4 *)ix.lists_bf16.p : (const float4 *)ix.lists.blocks.p;
   a.xnorm = bf16 ? (b.flt ? b.flt->xnorm_img.p : ix.xnorm_img.p) : (b.flt ? b.flt->xnorm.p : ix.xnorm.p);
@@ -1077,20 +1062,20 @@ vi_status rank_block(Batch &b, const RankPlan &plan, uint32_t nitems) {
   a.tile_start = ws.tile_start.p;
   a.items = (const uint4 *)ws.items.p;
   a.gval = (float4 *)ws.gval.p; a.gmeta = ws.gpos.p; a.brec = (float4 *)ws.brec.p;
-  a.xmode = b.kn.filter_xmode;
+  a.xmode = b.kn.rank_xmode;
   a.qimg = bf16 ? (const uint4 *)ws.qimg.p : nullptr;
-  VI_TRY(b.start_rank_clock());
-  return launch_filter(a, ix.dq, nitems, (int)plan.math, plan.gq, b.st);
+  VI_TRY(start_rank_clock(b));
+  return launch_mfma_rank(a, ix.dq, nitems, (int)plan.math, plan.gq, b.st());
 }
 
 // (VI_FILTER_STATS with timing level 1) the selects' counters and stage clocks, read back behind the select: synchronises
-vi_status report_select_stats(const Batch &b) {
+vi_status report_select_stats(SearchBatch &b) {
   const EngineKnobs &kn = b.kn;
-  vi_search_stats &stt = b.ix.cur().stats;
+  vi_search_stats &stt = b.ctx.stats;
   uint64_t dbg[kStatSelectEnd], tks[kStatClockCount];
-  VI_HIP(hipMemcpyAsync(dbg, b.ws().stats.p, sizeof(dbg), hipMemcpyDeviceToHost, b.st));
-  VI_HIP(hipMemcpyAsync(tks, b.ws().stats.p + kStatClocks, sizeof(tks), hipMemcpyDeviceToHost, b.st));
-  VI_HIP(hipStreamSynchronize(b.st));
+  VI_HIP(hipMemcpyAsync(dbg, b.ws().stats.p, sizeof(dbg), hipMemcpyDeviceToHost, b.st()));
+  VI_HIP(hipMemcpyAsync(tks, b.ws().stats.p + kStatClocks, sizeof(tks), hipMemcpyDeviceToHost, b.st()));
+  VI_HIP(hipStreamSynchronize(b.st()));
   if (kn.stats_coarse)
     fprintf(stderr, "coarse select ticks (every 64th query): query row %llu, records + bound %llu, flags (+ rounds a full list forces) %llu, exact rounds %llu, tail %llu; rows %llu "
             "of which in whole sub-blocks %llu\n", (unsigned long long)tks[0], (unsigned long long)tks[1], (unsigned long long)tks[2],
@@ -1109,28 +1094,26 @@ vi_status report_select_stats(const Batch &b) {
 
 }  // namespace
 
-// ---- 1 to 3 on the search stream: what both list selects (top-k, radius) start from.  Leaves the plan the lists were
-//      ranked by; timing_level 1: an event at every phase boundary; 2: around the rank kernel only (every record is a
+// ---- 1 to 3 on the search stream: what both list selects (top-k, radius) start from.  Leaves the frame the lists were
+//      ranked by; b.timing 1: an event at every phase boundary; 2: around the rank kernel only (every record is a
 //      barrier packet the next kernel's dispatch waits behind: five of them cost 0.01 ms of a 0.5 ms step) ----
-static vi_status rank_lists(Batch &b, int timing_level, const uint32_t *probes_in, const uint32_t *order_in, RankPlan &plan) {
+static vi_status rank_lists(SearchBatch &b, SelectFrame &ranked) {
   const DeviceIndex &ix = b.ix;
   const EngineKnobs &kn = b.kn;
-  hipStream_t st = b.st;
-  SearchWorkspace &ws = ix.cur().ws;
-  vi_search_stats &stt = ix.cur().stats;
-  const bool timing = timing_level == 1;
+  hipStream_t st = b.st();
+  SearchWorkspace &ws = b.ws();
+  vi_search_stats &stt = b.ctx.stats;
+  const bool timing = b.timing == 1;
   VI_TRY(ws.stats.reserve(kStatWords));
   if (kn.stats) {  // the selects' counters and stage clocks
     VI_HIP(hipMemsetAsync(ws.stats.p + kStatSelExact, 0, (kStatSelectEnd - kStatSelExact) * sizeof(uint64_t), st));
     VI_HIP(hipMemsetAsync(ws.stats.p + kStatClocks, 0, kStatClockCount * sizeof(uint64_t), st));
   }
-  ws.pair_rank_valid = false;  // (set by the coarse select of THIS search)
-  ws.group_counts_cleared = false;  // (by the split_queries_kernel of THIS search)
-  if (timing) VI_HIP(hipEventRecord(ix.cur().ev[0], st));
-  VI_TRY(coarse_phase(b, probes_in, order_in));
-  if (timing) VI_HIP(hipEventRecord(ix.cur().ev[1], st));
+  if (timing) VI_HIP(hipEventRecord(b.ctx.ev[0], st));
+  VI_TRY(coarse_phase(b));
+  if (timing) VI_HIP(hipEventRecord(b.ctx.ev[1], st));
 
-  plan = plan_rank(ix, kn, b.nq, b.P, gq_hint_for(ws, b.nq, b.P), ws.queries_hi_only);
+  RankPlan plan = plan_rank(ix, kn, b.nq, b.P, gq_hint_for(ws, b.nq, b.P), ws.queries_hi_only);
   GroupingCounts hstats;
   VI_TRY(group_pairs(b, plan, hstats));
   stt.rank_mode = rank_mode_code(ix, plan);
@@ -1143,37 +1126,28 @@ static vi_status rank_lists(Batch &b, int timing_level, const uint32_t *probes_i
     case RankKernel::Stream: VI_TRY(rank_stream(b, plan, nitems)); break;
     case RankKernel::Block: VI_TRY(rank_block(b, plan, nitems)); break;
   }
-  VI_TRY(b.start_rank_clock());  // (nothing to rank)
-  if (b.rank_timing) VI_HIP(hipEventRecord(ix.cur().ev[3], st));
+  VI_TRY(start_rank_clock(b));  // (nothing to rank)
+  if (b.timing) VI_HIP(hipEventRecord(b.ctx.ev[3], st));
+  ranked = SelectFrame{plan.gq, plan.kernel == RankKernel::Stream, plan.approx, plan.rank_i8};
   return VI_OK;
 }
 
-vi_status search_filter_pipeline(const DeviceIndex &ix, const EngineKnobs &kn, const float *Qd, uint64_t nq, uint64_t k, uint32_t P,
-                                 float *Dd, int64_t *Id, uint64_t *Td, uint64_t *slots, uint32_t *counts, hipStream_t st,
-                                 int timing_level, const uint32_t *probes_in, const uint32_t *order_in, const SlotFilter *flt) {
-  const bool timing = timing_level == 1;
-  Batch b{ix, kn, Qd, nq, P, flt, st, timing_level != 0};
-  RankPlan plan;
-  VI_TRY(rank_lists(b, timing_level, probes_in, order_in, plan));
-  VI_TRY(launch_list_select(ix, kn, Qd, nq, P, k, SelectFrame{plan.gq, plan.kernel == RankKernel::Stream, plan.approx, plan.rank_i8},
-                            SelectOutputs{Dd, Id, Td, slots, counts}, flt, st));
-  if (timing) VI_HIP(hipEventRecord(ix.cur().ev[4], st));
-  if (timing && kn.stats) VI_TRY(report_select_stats(b));
-  return VI_OK;
+
+vi_status search_mfma_pipeline(SearchBatch &b, uint64_t k, const SelectOutputs &out) {
+  SelectFrame ranked;
+  VI_TRY(rank_lists(b, ranked));
+  VI_TRY(launch_list_select(b, k, ranked, out));
+  if (b.timing == 1) VI_HIP(hipEventRecord(b.ctx.ev[4], b.st()));
+  return b.timing == 1 && b.kn.stats ? report_select_stats(b) : VI_OK;
 }
 
 // the radius search: the same records, read by the radius select (range_select.hip) instead of the top-k select
-vi_status range_filter_pipeline(const DeviceIndex &ix, const EngineKnobs &kn, const float *Qd, uint64_t nq, float radius2, uint32_t P,
-                                RangeResult *res, hipStream_t st, int timing_level, const SlotFilter *flt) {
-  const bool timing = timing_level == 1;
-  Batch b{ix, kn, Qd, nq, P, flt, st, timing_level != 0};
-  RankPlan plan;
-  VI_TRY(rank_lists(b, timing_level, nullptr, nullptr, plan));
-  VI_TRY(launch_range_select(ix, kn, Qd, nq, P, radius2, SelectFrame{plan.gq, plan.kernel == RankKernel::Stream, plan.approx, plan.rank_i8},
-                             flt, res, st));
-  if (timing) VI_HIP(hipEventRecord(ix.cur().ev[4], st));
-  if (timing && kn.stats) VI_TRY(report_select_stats(b));
-  return VI_OK;
+vi_status range_mfma_pipeline(SearchBatch &b, float radius2, RangeResult *res) {
+  SelectFrame ranked;
+  VI_TRY(rank_lists(b, ranked));
+  VI_TRY(launch_range_select(b, radius2, ranked, res));
+  if (b.timing == 1) VI_HIP(hipEventRecord(b.ctx.ev[4], b.st()));
+  return b.timing == 1 && b.kn.stats ? report_select_stats(b) : VI_OK;
 }
 
 }  // namespace vi

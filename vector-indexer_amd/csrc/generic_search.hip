@@ -195,6 +195,22 @@ struct OutArgs {
   uint32_t *counts;
 };
 
+// where candidate ci of a query went in: candidate-order rank g (the largest with off_by_g[g] <= ci; empty lists share an
+// offset with their successor), position in that list, and the global slot of the vector
+struct CandidatePlace { uint32_t g, pos; uint64_t gslot; };
+__device__ __forceinline__ CandidatePlace candidate_place(uint32_t ci, uint32_t P, const uint32_t *off, const uint32_t *gprobe,
+                                                          const uint32_t *probes, const uint32_t *first_block) {
+  uint32_t lo = 0, hi = P;
+  while (hi - lo > 1) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (off[mid] <= ci) lo = mid; else hi = mid;
+  }
+  const uint32_t g = lo, pos = ci - off[g];
+  const uint32_t gr = gprobe[g];
+  const uint32_t l = probes[gr < P ? gr : 0u];
+  return {g, pos, (uint64_t)first_block[l] * 64 + pos};
+}
+
 __global__ void generic_output_kernel(OutArgs a) {
   const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= (uint64_t)a.nq * a.k) return;
@@ -208,21 +224,12 @@ __global__ void generic_output_kernel(OutArgs a) {
     return;
   }
   const uint64_t key = a.keys[((size_t)q << a.logL) + i];
-  const uint32_t ci = (uint32_t)key;
-  const uint32_t *off = a.off_by_g + (size_t)q * a.P;
-  uint32_t lo = 0, hi = a.P;  // largest g with off[g] <= ci; empty lists share an offset with their successor
-  while (hi - lo > 1) {
-    const uint32_t mid = (lo + hi) >> 1;
-    if (off[mid] <= ci) lo = mid; else hi = mid;
-  }
-  const uint32_t g = lo, pos = ci - off[g];
-  const uint32_t gr = a.gprobe[(size_t)q * a.P + g];
-  const uint32_t l = a.probes[(size_t)q * a.P + (gr < a.P ? gr : 0u)];
-  const uint64_t gslot = (uint64_t)a.first_block[l] * 64 + pos;
+  const size_t row = (size_t)q * a.P;
+  const CandidatePlace c = candidate_place((uint32_t)key, a.P, a.off_by_g + row, a.gprobe + row, a.probes + row, a.first_block);
   a.D[t] = __uint_as_float((uint32_t)(key >> 32));
-  a.I[t] = (int64_t)a.ext_ids[gslot];
-  if (a.tie) a.tie[t] = ((uint64_t)g << 32) | pos;
-  if (a.slots) a.slots[t] = gslot;
+  a.I[t] = (int64_t)a.ext_ids[c.gslot];
+  if (a.tie) a.tie[t] = ((uint64_t)c.g << 32) | c.pos;
+  if (a.slots) a.slots[t] = c.gslot;
 }
 
 // filtered search: the excluded candidates received no key (their places kept the 0xFF fill, which sorts last), so the
@@ -245,10 +252,13 @@ vi_status sort_rows_u64(uint64_t *keys, uint64_t nrows, uint32_t logL, hipStream
 namespace {
 
 // A. probes: dump all coarse distances, sort each row, take the first P -> ws.probes
-vi_status generic_coarse(const DeviceIndex &ix, const float *Qd, uint64_t nq, uint32_t P, hipStream_t st) {
-  SearchWorkspace &ws = ix.cur().ws;
-  const uint32_t dim = ix.dim, dq = ix.dq;
-  const uint64_t nlists = ix.nlists;
+vi_status generic_coarse(SearchBatch &b) {
+  const DeviceIndex &ix = b.ix;
+  SearchWorkspace &ws = b.ws();
+  const float *Qd = b.Qd;
+  hipStream_t st = b.st();
+  const uint32_t P = b.P, dim = ix.dim, dq = ix.dq;
+  const uint64_t nq = b.nq, nlists = ix.nlists;
   VI_TRY(ws.probes.reserve(nq * P));
   VI_TRY(ws.gorder.reserve(nq * P));
   const uint32_t logLc = log2_ceil_rows(nlists);
@@ -277,8 +287,12 @@ vi_status generic_coarse(const DeviceIndex &ix, const float *Qd, uint64_t nq, ui
 
 // B. shard visiting order -> candidate order of the probes (ws.gorder and the offset arrays), from ws.probes; or, with
 // `given`, from the order the caller supplied (already in ws.gorder)
-vi_status generic_candidate_order(const DeviceIndex &ix, uint64_t nq, uint32_t P, bool given, hipStream_t st) {
-  SearchWorkspace &ws = ix.cur().ws;
+vi_status generic_candidate_order(SearchBatch &b, bool given) {
+  const DeviceIndex &ix = b.ix;
+  SearchWorkspace &ws = b.ws();
+  hipStream_t st = b.st();
+  const uint64_t nq = b.nq;
+  const uint32_t P = b.P;
   VI_TRY(ws.gprobe.reserve(nq * P));
   VI_TRY(ws.off_by_g.reserve(nq * P));
   VI_TRY(ws.off_by_rank.reserve(nq * P));
@@ -316,33 +330,32 @@ vi_status generic_candidate_order(const DeviceIndex &ix, uint64_t nq, uint32_t P
 }  // namespace
 
 // the coarse step alone for any n_probe (probe export of the multi-GPU protocol): ws.probes / ws.gorder
-vi_status generic_probe_export(const DeviceIndex &ix, const float *Qd, uint64_t nq, uint32_t P, hipStream_t st) {
-  if (ix.nshards > 24576) return fail(VI_ERR_OTHER, "generic path supports at most 24576 shards");
-  VI_TRY(generic_coarse(ix, Qd, nq, P, st));
-  return generic_candidate_order(ix, nq, P, false, st);
+vi_status generic_probe_export(SearchBatch &b) {
+  if (b.ix.nshards > 24576) return fail(VI_ERR_OTHER, "generic path supports at most 24576 shards");
+  VI_TRY(generic_coarse(b));
+  return generic_candidate_order(b, false);
 }
 
 namespace {
 
 // A + B for a batch, and the candidates per query on the host (added to the search's scanned_vectors)
-vi_status generic_prepare(const DeviceIndex &ix, const float *Qd, uint64_t nq, uint32_t P, hipStream_t st, const uint32_t *probes_in,
-                          const uint32_t *order_in, std::vector<uint64_t> &h_total) {
-  SearchWorkspace &ws = ix.cur().ws;
-  if (ix.nshards > 24576) return fail(VI_ERR_OTHER, "generic path supports at most 24576 shards");
-  vi_search_stats &stt = ix.cur().stats;
-  if (probes_in) {  // probe lists computed elsewhere: validated, then placed by the given order
-    VI_TRY(adopt_probes(ix, nq, P, probes_in, order_in, false, st));
-    VI_TRY(generic_candidate_order(ix, nq, P, true, st));
+vi_status generic_prepare(SearchBatch &b, std::vector<uint64_t> &h_total) {
+  SearchWorkspace &ws = b.ws();
+  if (b.ix.nshards > 24576) return fail(VI_ERR_OTHER, "generic path supports at most 24576 shards");
+  const uint64_t nq = b.nq;
+  if (b.probes_in) {  // probe lists computed elsewhere: validated, then placed by the given order
+    VI_TRY(adopt_probes(b, false));
+    VI_TRY(generic_candidate_order(b, true));
   } else {
-    VI_TRY(generic_coarse(ix, Qd, nq, P, st));
-    VI_TRY(generic_candidate_order(ix, nq, P, false, st));
+    VI_TRY(generic_coarse(b));
+    VI_TRY(generic_candidate_order(b, false));
   }
   h_total.resize(nq);
-  VI_HIP(hipMemcpyAsync(h_total.data(), ws.total.p, nq * 8, hipMemcpyDeviceToHost, st));
-  VI_HIP(hipStreamSynchronize(st));
+  VI_HIP(hipMemcpyAsync(h_total.data(), ws.total.p, nq * 8, hipMemcpyDeviceToHost, b.st()));
+  VI_HIP(hipStreamSynchronize(b.st()));
   for (uint64_t q = 0; q < nq; ++q) {
     if (h_total[q] > 0xFFFFFFFFull) return fail(VI_ERR_OTHER, "more than 2^32 candidates for one query");
-    stt.scanned_vectors += h_total[q];
+    b.ctx.stats.scanned_vectors += h_total[q];
   }
   return VI_OK;
 }
@@ -364,10 +377,11 @@ uint64_t chunk_queries(const std::vector<uint64_t> &h_total, uint64_t q0, uint64
 }
 
 // C. queries [q0, q0 + m): every candidate's key into the query's row of 2^logL keys (the rest stays ~0), rows sorted
-vi_status generic_sorted_rows(const DeviceIndex &ix, const float *Qd, uint64_t q0, uint64_t m, uint32_t P, uint32_t logL,
-                              const SlotFilter *flt, hipStream_t st) {
-  SearchWorkspace &ws = ix.cur().ws;
-  vi_search_stats &stt = ix.cur().stats;
+vi_status generic_sorted_rows(const DeviceIndex &ix, SearchContext &ctx, const float *Qd, uint64_t q0, uint64_t m, uint32_t P,
+                              uint32_t logL, const SlotFilter *flt) {
+  SearchWorkspace &ws = ctx.ws;
+  vi_search_stats &stt = ctx.stats;
+  hipStream_t st = ctx.stream;
   const uint32_t dim = ix.dim, dq = ix.dq;
   const uint64_t nlists = ix.nlists;
   const uint32_t segb0 = 256;
@@ -380,7 +394,7 @@ vi_status generic_sorted_rows(const DeviceIndex &ix, const float *Qd, uint64_t q
   GroupingRequest rq;
   rq.probes = ws.probes.p + q0 * P; rq.nq = m; rq.P = P; rq.qg = (uint32_t)qg; rq.segb0 = segb0;
   rq.tile_start = rq.pair_pos = true;
-  VI_TRY(group_probes(ix, rq, hstats, st));
+  VI_TRY(group_probes(ix, ctx, rq, hstats));
   stt.scan_items += hstats[kStatItems];
   ScanArgs a{};
   a.blocks = (const float4 *)ix.lists.blocks.p; a.dq = dq; a.dim = dim; a.Q = Qd + q0 * dim; a.nq = (uint32_t)m;
@@ -422,75 +436,69 @@ struct RangeOutArgs {
   uint64_t *tie, *slots;
 };
 
-// ... and go out at lims[q] + i (generic_output_kernel's recovery of (g, pos) from the candidate index)
+// ... and go out at lims[q] + i
 __global__ void __launch_bounds__(256) generic_range_output_kernel(RangeOutArgs a) {
   const uint32_t q = blockIdx.x;
   if (q >= a.nq) return;
-  const uint32_t *off = a.off_by_g + (size_t)q * a.P;
+  const size_t row = (size_t)q * a.P;
   const uint64_t at = a.lims[q];
   for (uint32_t i = threadIdx.x; i < a.counts[q]; i += blockDim.x) {
     const uint64_t key = a.keys[((size_t)q << a.logL) + i];
-    const uint32_t ci = (uint32_t)key;
-    uint32_t lo = 0, hi = a.P;  // largest g with off[g] <= ci; empty lists share an offset with their successor
-    while (hi - lo > 1) {
-      const uint32_t mid = (lo + hi) >> 1;
-      if (off[mid] <= ci) lo = mid; else hi = mid;
-    }
-    const uint32_t g = lo, pos = ci - off[g];
-    const uint32_t gr = a.gprobe[(size_t)q * a.P + g];
-    const uint32_t l = a.probes[(size_t)q * a.P + (gr < a.P ? gr : 0u)];
-    const uint64_t gslot = (uint64_t)a.first_block[l] * 64 + pos;
+    const CandidatePlace c = candidate_place((uint32_t)key, a.P, a.off_by_g + row, a.gprobe + row, a.probes + row, a.first_block);
     a.D[at + i] = __uint_as_float((uint32_t)(key >> 32));
-    a.I[at + i] = (int64_t)a.ext_ids[gslot];
-    a.tie[at + i] = ((uint64_t)g << 32) | pos;
-    a.slots[at + i] = gslot;
+    a.I[at + i] = (int64_t)a.ext_ids[c.gslot];
+    a.tie[at + i] = ((uint64_t)c.g << 32) | c.pos;
+    a.slots[at + i] = c.gslot;
   }
 }
 
 }  // namespace
 
-vi_status device_index_search_generic(const DeviceIndex &ix, const float *Qd, uint64_t nq, uint64_t k, uint32_t P,
-                                      float *Dd, int64_t *Id, uint64_t *Td, uint64_t *slots, uint32_t *counts,
-                                      hipStream_t st, const uint32_t *probes_in, const uint32_t *order_in, const SlotFilter *flt) {
-  SearchWorkspace &ws = ix.cur().ws;
+vi_status device_index_search_generic(SearchBatch &b, uint64_t k, const SelectOutputs &out) {
+  const DeviceIndex &ix = b.ix;
+  SearchWorkspace &ws = b.ws();
+  const SlotFilter *flt = b.flt;
+  hipStream_t st = b.st();
+  const uint64_t nq = b.nq;
+  const uint32_t P = b.P;
   std::vector<uint64_t> h_total;
-  VI_TRY(generic_prepare(ix, Qd, nq, P, st, probes_in, order_in, h_total));
+  VI_TRY(generic_prepare(b, h_total));
   if (flt) VI_TRY(ws.total_allowed.reserve(nq));
 
   // ---- C/D. per chunk of queries: dump candidate keys, sort rows, emit the first k ----
-  uint64_t q0 = 0;
-  while (q0 < nq) {
+  for (uint64_t q0 = 0, m; q0 < nq; q0 += m) {
     uint32_t logL;
-    const uint64_t m = chunk_queries(h_total, q0, k, &logL);
-    VI_TRY(generic_sorted_rows(ix, Qd, q0, m, P, logL, flt, st));
+    m = chunk_queries(h_total, q0, k, &logL);
+    VI_TRY(generic_sorted_rows(ix, b.ctx, b.Qd, q0, m, P, logL, flt));
     if (flt) {
       hipLaunchKernelGGL(count_keys_kernel, dim3((uint32_t)m), dim3(64), 0, st, ws.sort_keys.p, logL, (uint32_t)m, (uint32_t)k,
                          ws.total_allowed.p + q0);
       VI_HIP(hipGetLastError());
     }
     OutArgs o{ws.sort_keys.p, logL, (uint32_t)m, P, (uint32_t)k, ws.probes.p + q0 * P, ws.gprobe.p + q0 * P,
-              ws.off_by_g.p + q0 * P, ix.list_first_block.p, (flt ? ws.total_allowed.p : ws.total.p) + q0, ix.ext_ids.p, Dd + q0 * k, Id + q0 * k,
-              Td ? Td + q0 * k : nullptr, slots ? slots + q0 * k : nullptr, counts ? counts + q0 : nullptr};
+              ws.off_by_g.p + q0 * P, ix.list_first_block.p, (flt ? ws.total_allowed.p : ws.total.p) + q0, ix.ext_ids.p, out.D + q0 * k, out.I + q0 * k,
+              out.tie ? out.tie + q0 * k : nullptr, out.slots ? out.slots + q0 * k : nullptr, out.counts ? out.counts + q0 : nullptr};
     hipLaunchKernelGGL(generic_output_kernel, dim3((uint32_t)((m * k + 255) / 256)), dim3(256), 0, st, o);
     VI_HIP(hipGetLastError());
     VI_HIP(hipStreamSynchronize(st));
-    q0 += m;
   }
   return VI_OK;
 }
 
 // the radius form: the same sorted rows; a row's result is its prefix within radius2, appended to res chunk by chunk
-vi_status device_index_range_generic(const DeviceIndex &ix, const float *Qd, uint64_t nq, float radius2, uint32_t P, RangeResult *res,
-                                     hipStream_t st, const SlotFilter *flt) {
-  SearchWorkspace &ws = ix.cur().ws;
+vi_status device_index_range_generic(SearchBatch &b, float radius2, RangeResult *res) {
+  const DeviceIndex &ix = b.ix;
+  SearchWorkspace &ws = b.ws();
+  hipStream_t st = b.st();
+  const uint64_t nq = b.nq;
+  const uint32_t P = b.P;
   std::vector<uint64_t> h_total;
-  VI_TRY(generic_prepare(ix, Qd, nq, P, st, nullptr, nullptr, h_total));
+  VI_TRY(generic_prepare(b, h_total));
   VI_TRY(ws.counts.reserve(nq));
-  uint64_t q0 = 0;
-  while (q0 < nq) {
+  for (uint64_t q0 = 0, m; q0 < nq; q0 += m) {
     uint32_t logL;
-    const uint64_t m = chunk_queries(h_total, q0, 1, &logL);
-    VI_TRY(generic_sorted_rows(ix, Qd, q0, m, P, logL, flt, st));
+    m = chunk_queries(h_total, q0, 1, &logL);
+    VI_TRY(generic_sorted_rows(ix, b.ctx, b.Qd, q0, m, P, logL, b.flt));
     hipLaunchKernelGGL(count_radius_kernel, dim3((uint32_t)m), dim3(256), 0, st, ws.sort_keys.p, logL, (uint32_t)m, radius2,
                        ws.counts.p + q0);
     VI_HIP(hipGetLastError());
@@ -501,7 +509,6 @@ vi_status device_index_range_generic(const DeviceIndex &ix, const float *Qd, uin
     hipLaunchKernelGGL(generic_range_output_kernel, dim3((uint32_t)m), dim3(256), 0, st, o);
     VI_HIP(hipGetLastError());
     VI_HIP(hipStreamSynchronize(st));
-    q0 += m;
   }
   return VI_OK;
 }

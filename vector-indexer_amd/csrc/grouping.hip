@@ -602,8 +602,7 @@ bool pushes_items(GroupingRoute route) { return route == GroupingRoute::PrepareP
 
 // histogram (ws.cnt) -> totals -> offsets of the lists in pairs / items / records -> what the route's scatter starts
 // from: absolute cursors, or each sub-bin's start within its list (left by list_totals_kernel — one launch less)
-vi_status launch_group_scans(const DeviceIndex &ix, const GroupingRequest &rq, GroupingRoute route, hipStream_t st) {
-  SearchWorkspace &ws = ix.cur().ws;
+vi_status launch_group_scans(const DeviceIndex &ix, SearchWorkspace &ws, const GroupingRequest &rq, GroupingRoute route, hipStream_t st) {
   const uint32_t nlists = (uint32_t)ix.nlists, nq = (uint32_t)rq.nq;
   const bool push = pushes_items(route);
   VI_TRY(ws.list_tot.reserve(std::max<uint32_t>(1, nlists)));
@@ -631,8 +630,7 @@ vi_status launch_group_scans(const DeviceIndex &ix, const GroupingRequest &rq, G
 }
 
 // the grouping's scatter for the streaming rank kernel (item_push_kernel), with the item and record buffers as they stand
-vi_status launch_item_push(const DeviceIndex &ix, const GroupingRequest &rq, GroupingRoute route, hipStream_t st) {
-  SearchWorkspace &ws = ix.cur().ws;
+vi_status launch_item_push(const DeviceIndex &ix, SearchWorkspace &ws, const GroupingRequest &rq, GroupingRoute route, hipStream_t st) {
   const uint32_t nlists = (uint32_t)ix.nlists, total = (uint32_t)(rq.nq * rq.P);
   VI_TRY(ws.item_qcol.reserve(1));  // (no null pointers; a first batch finds no room and is pushed again)
   VI_TRY(ws.item_grec.reserve(1));
@@ -669,8 +667,7 @@ GroupingRoute grouping_route(const GroupingRequest &rq, uint64_t nlists) {
   return in_totals ? GroupingRoute::ScansPush : GroupingRoute::PreparePush;
 }
 
-vi_status launch_probe_histogram(const DeviceIndex &ix, const uint32_t *probes, uint32_t total, uint32_t P, hipStream_t st) {
-  SearchWorkspace &ws = ix.cur().ws;
+vi_status launch_probe_histogram(const DeviceIndex &ix, SearchWorkspace &ws, const uint32_t *probes, uint32_t total, uint32_t P, hipStream_t st) {
   const uint64_t nlists = ix.nlists;
   VI_TRY(ws.cnt.reserve(2 * subbin_words(nlists)));
   VI_HIP(hipMemsetAsync(ws.cnt.p, 0, subbin_words(nlists) * sizeof(uint32_t), st));
@@ -679,8 +676,9 @@ vi_status launch_probe_histogram(const DeviceIndex &ix, const uint32_t *probes, 
   return VI_OK;
 }
 
-vi_status group_probes(const DeviceIndex &ix, const GroupingRequest &rq, GroupingCounts &counts, hipStream_t st) {
-  SearchWorkspace &ws = ix.cur().ws;
+vi_status group_probes(const DeviceIndex &ix, SearchContext &ctx, const GroupingRequest &rq, GroupingCounts &counts) {
+  SearchWorkspace &ws = ctx.ws;
+  hipStream_t st = ctx.stream;
   const uint64_t nlists = ix.nlists;
   const uint32_t total = (uint32_t)(rq.nq * rq.P);
   const GroupingRoute route = grouping_route(rq, nlists);
@@ -694,14 +692,14 @@ vi_status group_probes(const DeviceIndex &ix, const GroupingRequest &rq, Groupin
   if (tile_start) VI_TRY(ws.tile_start.reserve(nlists + 1));
   VI_TRY(ws.stats.reserve(kStatWords));
   // (the layout of ws.stats: StatWord, search_internal.hpp — the grouping's counts are reset by list_totals_kernel)
-  if (!rq.histogram_done) VI_TRY(launch_probe_histogram(ix, rq.probes, total, rq.P, st));
-  VI_TRY(launch_group_scans(ix, rq, route, st));
+  if (!rq.histogram_done) VI_TRY(launch_probe_histogram(ix, ws, rq.probes, total, rq.P, st));
+  VI_TRY(launch_group_scans(ix, ws, rq, route, st));
   // the host waits for the counts (grid size, scratch) while the scatter runs
   // (into page-locked memory: a copy to the caller's stack array is staged by the runtime and costs a few microseconds
   // more on the one synchronisation point of the pipeline)
   if (!ws.hstats_pinned) VI_HIP(hipHostMalloc((void **)&ws.hstats_pinned, kStatGroupingLanding * sizeof(uint64_t)));
   VI_HIP(hipMemcpyAsync(ws.hstats_pinned, ws.stats.p, sizeof(GroupingCounts), hipMemcpyDeviceToHost, st));
-  VI_HIP(hipEventRecord(ix.cur().ev[5], st));
+  VI_HIP(hipEventRecord(ctx.ev[5], st));
   const dim3 grid((total + 255) / 256), block(256);
   uint32_t *cursor = ws.cnt.p + subbin_words(nlists), *pos_out = pair_pos ? ws.pair_pos.p : nullptr;
   switch (route) {
@@ -715,21 +713,20 @@ vi_status group_probes(const DeviceIndex &ix, const GroupingRequest &rq, Groupin
       break;
     case GroupingRoute::PreparePush:
     case GroupingRoute::ScansPush:
-      VI_TRY(launch_item_push(ix, rq, route, st));
+      VI_TRY(launch_item_push(ix, ws, rq, route, st));
       break;
   }
   VI_HIP(hipGetLastError());
-  VI_HIP(hipEventSynchronize(ix.cur().ev[5]));
+  VI_HIP(hipEventSynchronize(ctx.ev[5]));
   std::memcpy(counts.data(), ws.hstats_pinned, sizeof(GroupingCounts));
   return VI_OK;
 }
 
-vi_status repush_items(const DeviceIndex &ix, const GroupingRequest &rq, hipStream_t st) {
-  return launch_item_push(ix, rq, grouping_route(rq, ix.nlists), st);
+vi_status repush_items(const DeviceIndex &ix, SearchWorkspace &ws, const GroupingRequest &rq, hipStream_t st) {
+  return launch_item_push(ix, ws, rq, grouping_route(rq, ix.nlists), st);
 }
 
-vi_status launch_item_list(const DeviceIndex &ix, uint32_t nitems, hipStream_t st) {
-  SearchWorkspace &ws = ix.cur().ws;
+vi_status launch_item_list(const DeviceIndex &ix, SearchWorkspace &ws, uint32_t nitems, hipStream_t st) {
   VI_TRY(ws.item_list.reserve(std::max<uint32_t>(1, nitems)));
   if (!nitems) return VI_OK;
   hipLaunchKernelGGL(item_list_kernel, dim3((nitems + 255) / 256), dim3(256), 0, st, ws.item_start.p, (uint32_t)ix.nlists, nitems, ws.item_list.p);
@@ -737,8 +734,7 @@ vi_status launch_item_list(const DeviceIndex &ix, uint32_t nitems, hipStream_t s
   return VI_OK;
 }
 
-vi_status launch_item_desc(const DeviceIndex &ix, const EngineKnobs &kn, uint32_t gq, uint32_t nitems, hipStream_t st) {
-  SearchWorkspace &ws = ix.cur().ws;
+vi_status launch_item_desc(const DeviceIndex &ix, SearchWorkspace &ws, const EngineKnobs &kn, uint32_t gq, uint32_t nitems, hipStream_t st) {
   VI_TRY(ws.items.reserve(std::max<uint32_t>(1, nitems) * 8ull));
   if (!nitems) return VI_OK;
   hipLaunchKernelGGL(item_desc_kernel, dim3((nitems + 255) / 256), dim3(256), 0, st, ws.item_start.p, ws.seg_start.p, ix.list_len.p,
@@ -747,8 +743,7 @@ vi_status launch_item_desc(const DeviceIndex &ix, const EngineKnobs &kn, uint32_
   return VI_OK;
 }
 
-vi_status launch_item_cols(const DeviceIndex &ix, uint32_t P, uint32_t gq, uint32_t nitems, hipStream_t st) {
-  SearchWorkspace &ws = ix.cur().ws;
+vi_status launch_item_cols(SearchWorkspace &ws, uint32_t P, uint32_t gq, uint32_t nitems, hipStream_t st) {
   VI_TRY(ws.item_qcol.reserve(std::max<uint64_t>(1, (uint64_t)nitems * gq)));
   VI_TRY(ws.item_grec.reserve(std::max<uint64_t>(1, (uint64_t)nitems * gq)));
   VI_TRY(ws.item_sdesc.reserve(std::max<uint64_t>(1, (uint64_t)nitems * 4)));

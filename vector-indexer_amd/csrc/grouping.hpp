@@ -1,7 +1,8 @@
 // grouping.hpp — the probe grouping (grouping.hip): the counting sort of a batch's nq x n_probe (query, probe) pairs by
 // list, the scans over the lists built from it (where each list's pairs, work items, segment runs and record tiles start)
 // and the MFMA engine's rank work items.  One request, one entry; which chain of launches serves a request is a value
-// (GroupingRoute) computed from the request alone.
+// (GroupingRoute) computed from the request alone.  It takes no SearchBatch (the generic engine groups chunks of one): the index,
+// the workspace it fills and the stream (group_probes: the context, whose event it waits on).
 #pragma once
 #include <cstdint>
 
@@ -49,21 +50,21 @@ enum class GroupingRoute {
 };
 GroupingRoute grouping_route(const GroupingRequest &rq, uint64_t nlists);
 
-// Groups the pairs; `counts` is the host copy of the grouping's counts, read back while the scatter runs (the pipeline's
-// one synchronisation point).
-vi_status group_probes(const DeviceIndex &ix, const GroupingRequest &rq, GroupingCounts &counts, hipStream_t st);
+// Groups the pairs on ctx.stream; `counts` is the host copy of the grouping's counts, read back behind ctx.ev[5] while
+// the scatter runs (the pipeline's one synchronisation point).
+vi_status group_probes(const DeviceIndex &ix, SearchContext &ctx, const GroupingRequest &rq, GroupingCounts &counts);
 // the item push of a request once more, into item and record buffers the caller has grown since group_probes
-vi_status repush_items(const DeviceIndex &ix, const GroupingRequest &rq, hipStream_t st);
+vi_status repush_items(const DeviceIndex &ix, SearchWorkspace &ws, const GroupingRequest &rq, hipStream_t st);
 
 // clears the sub-bin counters (ws.cnt) and counts `total` = nq x P probes into them
-vi_status launch_probe_histogram(const DeviceIndex &ix, const uint32_t *probes, uint32_t total, uint32_t P, hipStream_t st);
+vi_status launch_probe_histogram(const DeviceIndex &ix, SearchWorkspace &ws, const uint32_t *probes, uint32_t total, uint32_t P, hipStream_t st);
 
 // ---- the rank work items where the scatter did not push them: kernels of their own behind it ----
 // ws.item_list: the list of every work item
-vi_status launch_item_list(const DeviceIndex &ix, uint32_t nitems, hipStream_t st);
+vi_status launch_item_list(const DeviceIndex &ix, SearchWorkspace &ws, uint32_t nitems, hipStream_t st);
 // ws.items: every work item's descriptor, dealt to the XCDs in runs of kn.item_run
-vi_status launch_item_desc(const DeviceIndex &ix, const EngineKnobs &kn, uint32_t gq, uint32_t nitems, hipStream_t st);
+vi_status launch_item_desc(const DeviceIndex &ix, SearchWorkspace &ws, const EngineKnobs &kn, uint32_t gq, uint32_t nitems, hipStream_t st);
 // ws.item_{qcol, grec, sdesc}, ws.gpos: the streaming rank kernel's columns, from ws.items
-vi_status launch_item_cols(const DeviceIndex &ix, uint32_t P, uint32_t gq, uint32_t nitems, hipStream_t st);
+vi_status launch_item_cols(SearchWorkspace &ws, uint32_t P, uint32_t gq, uint32_t nitems, hipStream_t st);
 
 }  // namespace vi

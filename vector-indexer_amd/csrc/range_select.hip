@@ -329,15 +329,18 @@ __global__ void __launch_bounds__(256) range_output_kernel(RangeOutArgs a) {
 
 }  // namespace
 
-vi_status launch_range_select(const DeviceIndex &ix, const EngineKnobs &kn, const float *Qd, uint64_t nq, uint32_t P, float radius2,
-                              const SelectFrame &f, const SlotFilter *flt, RangeResult *res, hipStream_t st) {
-  SearchWorkspace &ws = ix.cur().ws;
+vi_status launch_range_select(SearchBatch &b, float radius2, const SelectFrame &f, RangeResult *res) {
+  const DeviceIndex &ix = b.ix;
+  const EngineKnobs &kn = b.kn;
+  SearchWorkspace &ws = b.ws();
+  const uint64_t nq = b.nq;
+  hipStream_t st = b.st();
   VI_TRY(ws.range_bound.reserve(nq + 1));  // (the last word: the overflow flag)
   VI_TRY(ws.counts.reserve(nq));
-  RangeArgs a{list_select_common(ix, kn, Qd, f), 0u, (uint32_t)nq, P, kn.segb0, radius2, ws.qoff.p, ws.qtot.p, ws.pair_rel.p, ws.pair_pos.p,
+  RangeArgs a{list_select_common(b, f), 0u, (uint32_t)nq, b.P, kn.segb0, radius2, ws.qoff.p, ws.qtot.p, ws.pair_rel.p, ws.pair_pos.p,
               ws.tile_start.p, ws.probes.p, ws.gorder.p, ix.list_first_block.p, ix.list_len.p, ws.range_bound.p, nullptr, 0u, ws.counts.p,
               ws.range_bound.p + nq};
-  if (flt) a.c.allow = flt->allow.p;
+  if (b.flt) a.c.allow = b.flt->allow.p;
   unsigned long long *dbg = a.c.dbg;
   const size_t qsm = 4ull * ix.dim * sizeof(float);
   // (VI_FILTER_STATS=3 / 4) the steps' own clocks, printed like the select's: events of this call's, each read after a
@@ -387,14 +390,14 @@ vi_status launch_range_select(const DeviceIndex &ix, const EngineKnobs &kn, cons
     VI_HIP(hipMemsetAsync(ws.sort_keys.p, 0xFF, m * L * sizeof(uint64_t), st));
     a.q0 = (uint32_t)q0; a.m = (uint32_t)m; a.keys = ws.sort_keys.p; a.logL = logL;
     const dim3 grid((uint32_t)((m + 3) / 4));
-    if (flt) hipLaunchKernelGGL((range_select_kernel<true, true>), grid, dim3(256), qsm, st, a);
+    if (b.flt) hipLaunchKernelGGL((range_select_kernel<true, true>), grid, dim3(256), qsm, st, a);
     else hipLaunchKernelGGL((range_select_kernel<true, false>), grid, dim3(256), qsm, st, a);
     VI_HIP(hipGetLastError());
     VI_TRY(mark(1));
     VI_TRY(sort_rows_u64(ws.sort_keys.p, m, logL, st));
     VI_TRY(mark(2));
     VI_TRY(range_result_place(res, q0, m, ws.counts.p + q0, st));
-    RangeOutArgs o{ws.sort_keys.p, logL, (uint32_t)q0, (uint32_t)m, P, ws.counts.p, ws.probes.p, ws.gorder.p, ix.list_first_block.p,
+    RangeOutArgs o{ws.sort_keys.p, logL, (uint32_t)q0, (uint32_t)m, b.P, ws.counts.p, ws.probes.p, ws.gorder.p, ix.list_first_block.p,
                    res->lims.p, ix.ext_ids.p, res->D.p, res->I.p, res->tie.p, res->slots.p};
     hipLaunchKernelGGL(range_output_kernel, grid, dim3(256), 0, st, o);
     VI_HIP(hipGetLastError());

@@ -1,7 +1,9 @@
-// search_internal.hpp — what the search engines' and the index builders' translation units (search_kernels.hip,
+// search_internal.hpp — what the search engines' and the index builders' translation units (search.hip, search_kernels.hip,
 // generic_search.hip, filter_search.hip, grouping.hip, select.hip, range_select.hip, rank_images.hip, device_index.hip,
-// list_build.hip, list_update.hip, kmeans.hip) call in each other and share: declared once, here.  (The probe grouping is called through a header of its own, grouping.hpp; filter_search.hip launches
-// its rank and select phases through rank_stream.hpp and select.hpp.)
+// list_build.hip, list_update.hip, kmeans.hip) call in each other and share: declared once, here.  A search is one
+// SearchBatch, built by the dispatcher (search.hip) and handed to the engine it chose; the engines hand it on to their
+// stages.  (The probe grouping is called through a header of its own, grouping.hpp; filter_search.hip launches its rank
+// and select phases through rank_stream.hpp and select.hpp.)
 #pragma once
 #include <algorithm>
 #include <array>
@@ -27,7 +29,7 @@ enum StatWord {
   kStatGroupRecords = 4,    // group records
   kStatRecordTiles = 5,     // record tiles (pair records: 2 x gq each)
   kStatListCounts = 6,      // ... words [0, 6): what list_totals_kernel resets (and kStatTiles128)
-  // the selects' counters (VI_FILTER_STATS): cleared by search_filter_pipeline as [6, 12)
+  // the selects' counters (VI_FILTER_STATS): cleared by the MFMA pipelines as [6, 12)
   kStatSelExact = 6,        // list select: vectors evaluated exactly; coarse select: single rows
   kStatSelScanned = 7,      // list select: groups scanned; coarse select: whole sub-blocks
   kStatSelQueriesFull = 8,  // queries with a full group
@@ -78,34 +80,50 @@ vi_status upload(DevBuf<T> &buf, const T *host, size_t n, hipStream_t st) {
   return VI_OK;
 }
 
-// ---- search_kernels.hip ----
-vi_status stage_coarse(const DeviceIndex &ix, const float *Qd, uint64_t nq, uint32_t P, hipStream_t st);
-vi_status adopt_probes(const DeviceIndex &ix, uint64_t nq, uint32_t P, const uint32_t *probes_in, const uint32_t *order_in,
-                       bool histogram, hipStream_t st);
+// ---- one search: what every stage of it works from ----
+using SearchContext = DeviceIndex::SearchContext;
+struct SearchBatch {
+  const DeviceIndex &ix;
+  SearchContext &ctx;      // leased for this call: workspace, stats, events and THE stream of this search
+  const SlotFilter *flt;   // restricts the candidates of the list phase (the coarse step never sees it), or null
+  const uint32_t *probes_in, *order_in;  // the caller's probe lists instead of a coarse step, or null
+  EngineKnobs kn{};
+  const float *Qd = nullptr;  // nq x dim on the device
+  uint64_t nq = 0;
+  uint32_t P = 0;          // n_probe clamped to the lists
+  int timing = 0;          // DeviceIndex::timing for the engine chosen: 1 events at every phase boundary, 2 around the rank only
+  // what this search has done so far: the coarse select filled ws.pair_rank; split_queries_kernel cleared the grouping's
+  // counts of ws.stats; (MFMA engine) the event in front of the rank kernel is recorded; the grouping's scatter left the
+  // streaming rank kernel's work items behind (item_push_kernel)
+  bool pair_rank_valid = false, group_counts_cleared = false, rank_clock_started = false, items_pushed = false;
+  SearchWorkspace &ws() const { return ctx.ws; }
+  hipStream_t st() const { return ctx.stream; }
+};
+// device buffers of a top-k search's results: nq x k each; tie, slots and counts (nq) may be null
+struct SelectOutputs { float *D; int64_t *I; uint64_t *tie, *slots; uint32_t *counts; };
 
-// a radius search's result as the engines fill it, chunk of queries after chunk: range_result_begin sizes lims;
-// range_result_place reads the hit counts of queries [q0, q0 + m) back (it synchronises), extends lims by them on the
-// host and the device and grows D / I / tie / slots to hold them, keeping what earlier chunks wrote
+// ---- search.hip: a radius search's result as the engines fill it, chunk of queries after chunk ----
+// range_result_begin sizes lims; range_result_place reads the hit counts of queries [q0, q0 + m) back (it synchronises),
+// extends lims by them on the host and the device and grows D / I / tie / slots to hold them, keeping what earlier chunks wrote
 vi_status range_result_begin(const DeviceIndex &ix, uint64_t nq, RangeResult *res);
 vi_status range_result_place(RangeResult *res, uint64_t q0, uint64_t m, const uint32_t *counts_dev, hipStream_t st);
 
-// ---- filter_search.hip ----
-vi_status range_filter_pipeline(const DeviceIndex &ix, const EngineKnobs &kn, const float *Qd, uint64_t nq, float radius2, uint32_t P,
-                                RangeResult *res, hipStream_t st, int timing_level, const SlotFilter *flt);
-vi_status search_filter_pipeline(const DeviceIndex &ix, const EngineKnobs &kn, const float *Qd, uint64_t nq, uint64_t k, uint32_t P,
-                                 float *Dd, int64_t *Id, uint64_t *Td, uint64_t *slots, uint32_t *counts, hipStream_t st,
-                                 int timing_level, const uint32_t *probes_in, const uint32_t *order_in, const SlotFilter *flt);
-vi_status coarse_only_filter(const DeviceIndex &ix, const EngineKnobs &kn, const float *Qd, uint64_t nq, uint32_t P, hipStream_t st);
-bool filter_path_applicable(const DeviceIndex &ix, const EngineKnobs &kn, uint64_t k, uint32_t P);
+// ---- search_kernels.hip: the exact-order VALU engine ----
+vi_status stage_coarse(SearchBatch &b);                   // ws.probes / gorder and the per-list histogram (ws.cnt)
+vi_status adopt_probes(SearchBatch &b, bool histogram);   // ... from b.probes_in / order_in, validated
+vi_status search_valu_pipeline(SearchBatch &b, uint64_t k, const SelectOutputs &out);
+
+// ---- filter_search.hip: the MFMA engine ----
+vi_status search_mfma_pipeline(SearchBatch &b, uint64_t k, const SelectOutputs &out);
+vi_status range_mfma_pipeline(SearchBatch &b, float radius2, RangeResult *res);
+vi_status coarse_only_mfma(SearchBatch &b);
+bool mfma_path_applicable(const DeviceIndex &ix, const EngineKnobs &kn, uint64_t k, uint32_t P);
 bool coarse_on_matrix_cores(const DeviceIndex &ix, const EngineKnobs &kn, uint64_t nq, uint32_t P);
 
-// ---- generic_search.hip ----
-vi_status device_index_search_generic(const DeviceIndex &ix, const float *Qd, uint64_t nq, uint64_t k, uint32_t P,
-                                      float *Dd, int64_t *Id, uint64_t *Td, uint64_t *slots, uint32_t *counts,
-                                      hipStream_t st, const uint32_t *probes_in, const uint32_t *order_in, const SlotFilter *flt);
-vi_status device_index_range_generic(const DeviceIndex &ix, const float *Qd, uint64_t nq, float radius2, uint32_t P, RangeResult *res,
-                                     hipStream_t st, const SlotFilter *flt);
-vi_status generic_probe_export(const DeviceIndex &ix, const float *Qd, uint64_t nq, uint32_t P, hipStream_t st);
+// ---- generic_search.hip: every candidate sorted ----
+vi_status device_index_search_generic(SearchBatch &b, uint64_t k, const SelectOutputs &out);
+vi_status device_index_range_generic(SearchBatch &b, float radius2, RangeResult *res);
+vi_status generic_probe_export(SearchBatch &b);
 
 // ---- rank_images.hip ----
 // everything the MFMA engine ranks an index from, derived from its f32 blocks: norms, bf16 / int8 images, the centre, the

@@ -1,4 +1,5 @@
-// search_kernels.hip — gfx950 kernels of the IVF search path and their host-side pipeline.
+// search_kernels.hip — the exact-order VALU engine: its gfx950 kernels and the pipeline that runs a SearchBatch through them
+// (the dispatcher is search.hip), and the two small utilities built on its kernels (merge_partials*, l2sq_pairs_device).
 //
 // Reference path being replaced: IvfIndex::search_with_paths (src/ivf_index.rs:190-267):
 //   coarse  : euclidean_distance_squared(q, c_i) for all centroids, stable sort, take n_probe
@@ -43,11 +44,6 @@ namespace {
 constexpr int kWave = 64;
 constexpr int kWavesPerBlock = 4;
 constexpr int kBlockThreads = kWave * kWavesPerBlock;
-
-// Minimum blocks (x64 vectors) per list segment.  Measured on the C2 workload (profiles/
-// r01_experiments.md): cutting lists finer than this costs more in repeated top-k warm-up than it
-// gains in load balance, so only extreme lists (> 64k vectors) are cut (seg 256 measured +9 %).
-constexpr uint32_t kSegBlocksDefault = 1024;
 
 // ------------------------------------------------------------------------------------------
 // Exact-order accumulators.  SCALAR: src/utils.rs:28-30.  LANES: src/kmeans.rs:377-419
@@ -490,22 +486,6 @@ __global__ void __launch_bounds__(kBlockThreads) merge_partials_kernel(uint64_t 
   for (uint32_t i = found + lane; i < k; i += kWave) { D[q * k + i] = INFINITY; I[q * k + i] = -1; }
 }
 
-// gather result vectors (include_vectors, api.rs:213-217) back to row-major
-__global__ void gather_vectors_kernel(const float *blocks, uint32_t dq, uint32_t dim, const uint64_t *slots,
-                                      uint64_t nres, float *V) {
-  const uint64_t r = blockIdx.x;
-  if (r >= nres) return;
-  const uint64_t s = slots[r];
-  for (uint32_t e = threadIdx.x; e < dim; e += blockDim.x) {
-    float val = 0.0f;
-    if (s != ~0ull) {
-      const uint64_t blk = s / kWave, ln = s % kWave;
-      val = blocks[((blk * dq + e / 4) * kWave + ln) * 4 + (e & 3)];
-    }
-    V[r * dim + e] = val;
-  }
-}
-
 // plain pairwise distances in either order (vi_l2sq_pairs)
 __global__ void l2sq_pairs_kernel(const float *a, const float *b, uint64_t n, uint32_t d, int order, float *out) {
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -579,38 +559,16 @@ uint32_t coarse_splits(uint64_t nq, int qg, uint32_t nblk, uint32_t *bps) {
   return std::max<uint32_t>(1, (nblk + *bps - 1) / *bps);
 }
 
-// the context held by the calling thread: set for the duration of device_index_search (a search of ANOTHER index from
-// inside a search — the hierarchical k-means assignment does that — saves and restores it)
-static thread_local DeviceIndex::SearchContext *t_ctx = nullptr;
-
-DeviceIndex::SearchContext &DeviceIndex::cur() const { return *t_ctx; }
-
-namespace {
-// A context of the index's pool, to be made t_ctx by the caller; every release publishes its stats as the handle's and
-// puts the thread's earlier context back.
-auto lease_search_context(const DeviceIndex &ix) {
-  auto give_back = [&ix, prev = t_ctx] { ix.last_stats = t_ctx->stats; t_ctx = prev; };
-  return ContextLease(ix.search_contexts, make_context<DeviceIndex::SearchContext>, give_back);
-}
-
-void fill_phase_times(vi_search_stats &s, const hipEvent_t *ev, int level) {
-  if (level) (void)hipEventElapsedTime(&s.ms_scan, ev[2], ev[3]);
-  if (level != 1) return;
-  (void)hipEventElapsedTime(&s.ms_coarse, ev[0], ev[1]);
-  (void)hipEventElapsedTime(&s.ms_group, ev[1], ev[2]);
-  (void)hipEventElapsedTime(&s.ms_merge, ev[3], ev[4]);
-  (void)hipEventElapsedTime(&s.ms_total, ev[0], ev[4]);
-}
-}  // namespace
-
 // ------------------------------------------------------------------------------------------
 // pipeline stages
 // ------------------------------------------------------------------------------------------
 // 1+2: coarse scan over the centroid table, merge -> ws.probes / ws.gorder, histogram in ws.cnt
-vi_status stage_coarse(const DeviceIndex &ix, const float *Qd, uint64_t nq, uint32_t P, hipStream_t st) {
-  SearchWorkspace &ws = ix.cur().ws;
-  const uint32_t dim = ix.dim, dq = ix.dq;
-  const uint64_t nlists = ix.nlists;
+vi_status stage_coarse(SearchBatch &b) {
+  const DeviceIndex &ix = b.ix;
+  SearchWorkspace &ws = b.ws();
+  hipStream_t st = b.st();
+  const uint32_t P = b.P, dim = ix.dim, dq = ix.dq;
+  const uint64_t nq = b.nq, nlists = ix.nlists;
   VI_TRY(ws.cnt.reserve(2 * subbin_words(nlists)));
   VI_HIP(hipMemsetAsync(ws.cnt.p, 0, subbin_words(nlists) * sizeof(uint32_t), st));
   const uint32_t nblk_c = (uint32_t)ix.centroids.nblocks;
@@ -622,7 +580,7 @@ vi_status stage_coarse(const DeviceIndex &ix, const float *Qd, uint64_t nq, uint
   VI_TRY(ws.crun_pos.reserve(nq * S * P));
   {
     ScanArgs a{};
-    a.blocks = (const float4 *)ix.centroids.blocks.p; a.dq = dq; a.dim = dim; a.Q = Qd; a.nq = (uint32_t)nq;
+    a.blocks = (const float4 *)ix.centroids.blocks.p; a.dq = dq; a.dim = dim; a.Q = b.Qd; a.nq = (uint32_t)nq;
     a.K = P; a.run_dist = ws.crun_dist.p; a.run_pos = ws.crun_pos.p;
     a.nvec = (uint32_t)nlists; a.S = S; a.bps = bps;
     VI_TRY(launch_scan(a, qg_c, ix.order, true, nqg * S, st));
@@ -637,13 +595,14 @@ vi_status stage_coarse(const DeviceIndex &ix, const float *Qd, uint64_t nq, uint
   return VI_OK;
 }
 
-// exact-order VALU pipeline: coarse -> group -> list scan -> final merge
 // probes given by the caller (multi-GPU: coarse step done elsewhere): probe lists + candidate-order ranks into
 // the workspace, and the per-list histogram the grouping scan starts from
-vi_status adopt_probes(const DeviceIndex &ix, uint64_t nq, uint32_t P, const uint32_t *probes_in, const uint32_t *order_in,
-                       bool histogram, hipStream_t st) {
-  SearchWorkspace &ws = ix.cur().ws;
-  const uint64_t nlists = ix.nlists;
+vi_status adopt_probes(SearchBatch &b, bool histogram) {
+  const DeviceIndex &ix = b.ix;
+  SearchWorkspace &ws = b.ws();
+  const uint64_t nq = b.nq, nlists = ix.nlists;
+  const uint32_t P = b.P, *probes_in = b.probes_in, *order_in = b.order_in;
+  hipStream_t st = b.st();
   VI_TRY(ws.probes.reserve(nq * P));
   VI_TRY(ws.gorder.reserve(nq * P));
   VI_TRY(ws.probe_flag.reserve(1));
@@ -660,27 +619,30 @@ vi_status adopt_probes(const DeviceIndex &ix, uint64_t nq, uint32_t P, const uin
     return fail(VI_ERR_INVALID_INPUT, "probe lists out of range: every probe must be < %llu (or the empty marker 0xFFFFFFFF "
                 "after the last real probe of a row), and the orders of a row's real probes must be distinct and below "
                 "its number of real probes", (unsigned long long)nlists);
-  if (histogram) VI_TRY(launch_probe_histogram(ix, ws.probes.p, (uint32_t)(nq * P), P, st));
+  if (histogram) VI_TRY(launch_probe_histogram(ix, ws, ws.probes.p, (uint32_t)(nq * P), P, st));
   return VI_OK;
 }
 
-vi_status search_valu_pipeline(const DeviceIndex &ix, const EngineKnobs &kn, const float *Qd, uint64_t nq, uint64_t k, uint32_t P,
-                               uint32_t K, float *Dd, int64_t *Id, uint64_t *Td, uint64_t *slots, uint32_t *counts, hipStream_t st,
-                               int timing_level, const uint32_t *probes_in, const uint32_t *order_in, const SlotFilter *flt) {
-  const bool timing = timing_level == 1, rank_timing = timing_level != 0;
-  SearchWorkspace &ws = ix.cur().ws;
-  vi_search_stats &stt = ix.cur().stats;
-  const uint32_t dim = ix.dim, dq = ix.dq;
-  const uint64_t nlists = ix.nlists;
+// exact-order VALU pipeline: coarse -> group -> list scan -> final merge (k <= 64: the wave-resident top-k)
+vi_status search_valu_pipeline(SearchBatch &b, uint64_t k, const SelectOutputs &out) {
+  const DeviceIndex &ix = b.ix;
+  const EngineKnobs &kn = b.kn;
+  SearchContext &ctx = b.ctx;
+  SearchWorkspace &ws = ctx.ws;
+  vi_search_stats &stt = ctx.stats;
+  hipStream_t st = ctx.stream;
+  const uint64_t nq = b.nq, nlists = ix.nlists;
+  const uint32_t P = b.P, K = (uint32_t)std::min<uint64_t>(k, kMaxSelect), dim = ix.dim, dq = ix.dq;
+  const bool timing = b.timing == 1, rank_timing = b.timing != 0;
   VI_TRY(ws.run_dist.reserve(nq * P * K));
   VI_TRY(ws.run_pos.reserve(nq * P * K));
   // runs of lists that are not resident here (other rank / unreadable shard) stay empty
   VI_HIP(hipMemsetAsync(ws.run_pos.p, 0xFF, nq * P * K * sizeof(uint32_t), st));
 
-  if (timing) VI_HIP(hipEventRecord(ix.cur().ev[0], st));
-  if (probes_in) VI_TRY(adopt_probes(ix, nq, P, probes_in, order_in, true, st));
-  else VI_TRY(stage_coarse(ix, Qd, nq, P, st));
-  if (timing) VI_HIP(hipEventRecord(ix.cur().ev[1], st));
+  if (timing) VI_HIP(hipEventRecord(ctx.ev[0], st));
+  if (b.probes_in) VI_TRY(adopt_probes(b, true));
+  else VI_TRY(stage_coarse(b));
+  if (timing) VI_HIP(hipEventRecord(ctx.ev[1], st));
   // ---- 3. group (query,probe) pairs by list ----
   const double avg_q_per_list = (double)nq * P / (double)std::max<uint64_t>(1, nlists);
   int qg_l = pick_qg(dq, avg_q_per_list, ix.order);
@@ -693,23 +655,23 @@ vi_status search_valu_pipeline(const DeviceIndex &ix, const EngineKnobs &kn, con
   GroupingRequest rq;
   rq.probes = ws.probes.p; rq.nq = nq; rq.P = P; rq.qg = (uint32_t)qg_l; rq.segb0 = kSegBlocks; rq.histogram_done = true;
   GroupingCounts hstats;
-  VI_TRY(group_probes(ix, rq, hstats, st));
+  VI_TRY(group_probes(ix, ctx, rq, hstats));
   stt.scanned_vectors = hstats[kStatScannedVectors];
   stt.scan_items = hstats[kStatItems];
   const uint64_t nsegruns = hstats[kStatSegRuns];
   VI_TRY(ws.seg_run_dist.reserve(nsegruns * K));
   VI_TRY(ws.seg_run_pos.reserve(nsegruns * K));
-  if (rank_timing) VI_HIP(hipEventRecord(ix.cur().ev[2], st));
+  if (rank_timing) VI_HIP(hipEventRecord(ctx.ev[2], st));
   // ---- 4. list scan ----
   {
     ScanArgs a{};
-    a.blocks = (const float4 *)ix.lists.blocks.p; a.dq = dq; a.dim = dim; a.Q = Qd; a.nq = (uint32_t)nq;
+    a.blocks = (const float4 *)ix.lists.blocks.p; a.dq = dq; a.dim = dim; a.Q = b.Qd; a.nq = (uint32_t)nq;
     a.K = K; a.run_dist = ws.run_dist.p; a.run_pos = ws.run_pos.p;
     a.first_block = ix.list_first_block.p; a.list_len = ix.list_len.p; a.item_start = ws.item_start.p;
     a.seg_start = ws.seg_start.p; a.pairs = ws.pairs.p; a.nlists = (uint32_t)nlists; a.P = P;
     a.segb0 = kSegBlocks; a.segrun_start = ws.segrun_start.p;
     a.seg_run_dist = ws.seg_run_dist.p; a.seg_run_pos = ws.seg_run_pos.p;
-    a.allow = flt ? flt->allow.p : nullptr;  // excluded vectors never enter a run: the merges below see none of them
+    a.allow = b.flt ? b.flt->allow.p : nullptr;  // excluded vectors never enter a run: the merges below see none of them
     VI_TRY(launch_scan(a, qg_l, ix.order, false, (uint32_t)hstats[kStatItems], st));
     if (nsegruns) {
       SegMergeArgs m{ws.seg_start.p, ws.segrun_start.p, ix.list_len.p, ws.pairs.p, (uint32_t)nlists, kSegBlocks, K,
@@ -720,287 +682,16 @@ vi_status search_valu_pipeline(const DeviceIndex &ix, const EngineKnobs &kn, con
       VI_HIP(hipGetLastError());
     }
   }
-  if (rank_timing) VI_HIP(hipEventRecord(ix.cur().ev[3], st));
+  if (rank_timing) VI_HIP(hipEventRecord(ctx.ev[3], st));
   // ---- 5. final merge ----
   {
     FinalMergeArgs a{ws.run_dist.p, ws.run_pos.p, (uint32_t)nq, P, K, (uint32_t)k, ws.probes.p, ws.gorder.p,
-                     ix.list_first_block.p, ix.ext_ids.p, Dd, Id, Td, slots, counts};
+                     ix.list_first_block.p, ix.ext_ids.p, out.D, out.I, out.tie, out.slots, out.counts};
     hipLaunchKernelGGL(final_merge_kernel, dim3((uint32_t)((nq + kWavesPerBlock - 1) / kWavesPerBlock)),
                        dim3(kBlockThreads), 0, st, a);
     VI_HIP(hipGetLastError());
   }
-  if (timing) VI_HIP(hipEventRecord(ix.cur().ev[4], st));
-  return VI_OK;
-}
-
-// ------------------------------------------------------------------------------------------
-// search pipeline (fast path: n_probe_eff <= 64 and k <= 64)
-// ------------------------------------------------------------------------------------------
-// striped lists: local position -> position in the whole list, so that the merge over ranks sees the
-// reference's candidate order
-__global__ void stripe_tie_kernel(uint64_t *tie, uint64_t n, uint32_t rank, uint32_t world) {
-  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const uint64_t t = tie[i];
-  if (t == ~0ull) return;
-  const uint32_t p = (uint32_t)t;
-  tie[i] = (t & 0xFFFFFFFF00000000ull) | (uint64_t)(((p >> 6) * world + rank) * 64u + (p & 63u));
-}
-
-EngineKnobs read_engine_knobs() {
-  auto on = [](const char *name) { const char *e = getenv(name); return !(e && *e == '0'); };
-  auto num = [](const char *name, int dflt) { const char *e = getenv(name); return e ? atoi(e) : dflt; };
-  auto u32 = [](const char *name, uint32_t dflt) {  // (unset or empty: the default)
-    const char *e = getenv(name);
-    return (e && *e) ? (uint32_t)strtoul(e, nullptr, 10) : dflt;
-  };
-  const char *stats = getenv("VI_FILTER_STATS"), *approx = getenv("VI_RANK_APPROX"), *gq = getenv("VI_FILTER_GQ");
-  const char *stream = getenv("VI_RANK_STREAM");
-  EngineKnobs kn{};
-  kn.force_generic = u32("VI_FORCE_GENERIC", 0) != 0;
-  kn.force_qg = u32("VI_FORCE_QG", 0);
-  kn.seg_blocks = std::max<uint32_t>(1, u32("VI_SEG_BLOCKS", kSegBlocksDefault));
-  kn.filter = on("VI_FILTER");
-  kn.rank_bf16 = on("VI_FILTER_BF16");
-  kn.hi_only = on("VI_FILTER_HI_ONLY");
-  kn.rank_approx = -1;
-  if (approx) { const int v = atoi(approx); kn.rank_approx = v < 0 || v > 2 ? 1 : v; }
-  kn.debug_approx = getenv("VI_DEBUG_APPROX") != nullptr;
-  kn.coarse_filter = on("VI_COARSE_FILTER");
-  kn.coarse_direct = on("VI_COARSE_DIRECT");
-  kn.segb0 = (uint32_t)std::max(1, num("VI_FILTER_SEGB", 32));  // <= 2048 vectors per work item
-  kn.gq = gq ? (atoi(gq) == 32 ? 32u : 128u) : 0u;
-  kn.stream_off = stream && *stream == '0';
-  kn.stream_force = stream && *stream == '1';
-  kn.stream_gq256 = num("VI_STREAM_GQ", 0) == 256;
-  kn.rank_i8 = on("VI_RANK_I8");
-  kn.item_run = (uint32_t)std::min(std::max(num("VI_ITEM_RUN", 8), 1), 256);
-  kn.item_push = on("VI_ITEM_PUSH");
-  kn.scan_in_totals = on("VI_SCAN_IN_TOTALS");
-  kn.stream_prof = getenv("VI_STREAM_PROF") != nullptr;
-  kn.stream_prof_dump = getenv("VI_STREAM_PROF_DUMP");
-  kn.filter_xmode = (uint32_t)num("VI_FILTER_XMODE", 0);
-  kn.select_xmode = (uint32_t)num("VI_SELECT_XMODE", 0);
-  kn.coarse_xmode = (uint32_t)num("VI_SELECT_XMODE_COARSE", 0);
-  kn.stats = stats != nullptr;
-  kn.stats_coarse = stats && *stats == '2';
-  kn.stats_print = stats && (*stats == '3' || *stats == '4');
-  kn.stats_mask = stats && *stats == '4' ? 63u : 0u;
-  return kn;
-}
-
-vi_status device_index_search(const DeviceIndex &ix, const SearchIO &io) {
-  VI_HIP(hipSetDevice(ix.device));
-  auto lease = lease_search_context(ix);
-  if (!lease.ctx) return VI_ERR_DEVICE;  // (the message is make_context's)
-  t_ctx = lease.ctx;
-  hipStream_t st = ix.cur().stream;
-  SearchWorkspace &ws = ix.cur().ws;
-  const uint64_t nq = io.nq, k = io.k;
-  const uint32_t dim = ix.dim, dq = ix.dq;
-  const uint64_t nlists = ix.nlists;
-  if (nq == 0) return VI_OK;
-  const SlotFilter *flt = io.filter;
-  if (flt && flt->owner_serial != ix.serial) return fail(VI_ERR_INVALID_INPUT, "the filter was made for another index");
-  if (nq * std::max<uint64_t>(k, 64) > 0x7FFFFFFFull) return fail(VI_ERR_INVALID_INPUT, "batch too large: split nq");
-  const uint32_t P = (uint32_t)std::min<uint64_t>(io.n_probe, nlists);  // take(n_probe) (ivf_index.rs:216-220)
-  const uint32_t K = (uint32_t)std::min<uint64_t>(k, kMaxSelect);
-  // k in (64, 128]: the MFMA engine's select keeps two entries per lane; the VALU engine's wave top-k stops at 64
-  const EngineKnobs kn = read_engine_knobs();
-  const bool generic = P > kMaxSelect || k > 2 * kMaxSelect || (k > kMaxSelect && !filter_path_applicable(ix, kn, k, P)) ||
-                       kn.force_generic;
-
-  // ---- outputs / queries on device ----
-  const float *Qd = io.queries;
-  float *Dd = io.D;
-  int64_t *Id = io.I;
-  uint64_t *Td = io.tie;
-  if (!io.on_device) {
-    VI_TRY(ws.q.reserve(nq * dim));
-    VI_TRY(ws.D.reserve(nq * k));
-    VI_TRY(ws.I.reserve(nq * k));
-    VI_HIP(hipMemcpyAsync(ws.q.p, io.queries, nq * dim * sizeof(float), hipMemcpyHostToDevice, st));
-    Qd = ws.q.p; Dd = ws.D.p; Id = ws.I.p; Td = nullptr;
-  }
-  VI_TRY(ws.counts.reserve(nq));
-  VI_TRY(ws.stats.reserve(kStatWords));
-  uint64_t *slots = nullptr;
-  if (io.V) { VI_TRY(ws.slots.reserve(nq * k)); slots = ws.slots.p; }
-
-  vi_search_stats &stt = ix.cur().stats;
-  stt = vi_search_stats{};
-  stt.nq = nq; stt.k = k; stt.n_probe_eff = P; stt.coarse_candidates = nq * nlists;
-
-  if (P == 0 || nlists == 0) {  // empty index: every query has zero results
-    std::vector<float> hD(nq * k, INFINITY);
-    std::vector<int64_t> hI(nq * k, -1);
-    if (io.on_device) {
-      VI_HIP(hipMemcpy(io.D, hD.data(), hD.size() * 4, hipMemcpyHostToDevice));
-      VI_HIP(hipMemcpy(io.I, hI.data(), hI.size() * 8, hipMemcpyHostToDevice));
-    } else {
-      std::memcpy(io.D, hD.data(), hD.size() * 4);
-      std::memcpy(io.I, hI.data(), hI.size() * 8);
-      if (io.counts) std::memset(io.counts, 0, nq * 8);
-      if (io.V) std::memset(io.V, 0, nq * k * dim * 4);
-    }
-    return VI_OK;
-  }
-
-  const bool use_filter = !generic && filter_path_applicable(ix, kn, k, P);
-  const int timing = generic ? 0 : ix.timing;
-  if (io.probes_out) {  // coarse step only (multi-GPU: this rank's slice of the queries)
-    if (P > kMaxSelect) VI_TRY(generic_probe_export(ix, Qd, nq, P, st));  // any n_probe: every coarse distance, sorted
-    else if (coarse_on_matrix_cores(ix, kn, nq, P)) VI_TRY(coarse_only_filter(ix, kn, Qd, nq, P, st));
-    else VI_TRY(stage_coarse(ix, Qd, nq, P, st));
-    VI_HIP(hipMemcpyAsync(io.probes_out, ws.probes.p, nq * P * 4, hipMemcpyDeviceToDevice, st));
-    VI_HIP(hipMemcpyAsync(io.order_out, ws.gorder.p, nq * P * 4, hipMemcpyDeviceToDevice, st));
-    VI_HIP(hipStreamSynchronize(st));
-    return VI_OK;
-  }
-  if (generic) {  // (k > 128 or n_probe > 64, with the caller's probe lists too)
-    VI_TRY(device_index_search_generic(ix, Qd, nq, k, P, Dd, Id, Td, slots, ws.counts.p, st, io.probes_in, io.order_in, flt));
-  } else if (use_filter) {
-    VI_TRY(search_filter_pipeline(ix, kn, Qd, nq, k, P, Dd, Id, Td, slots, ws.counts.p, st, timing, io.probes_in, io.order_in, flt));
-  } else {
-    VI_TRY(search_valu_pipeline(ix, kn, Qd, nq, k, P, K, Dd, Id, Td, slots, ws.counts.p, st, timing, io.probes_in, io.order_in, flt));
-  }
-
-  if (ix.stripe_world > 1 && Td) {
-    hipLaunchKernelGGL(stripe_tie_kernel, dim3((uint32_t)((nq * k + 255) / 256)), dim3(256), 0, st, Td, nq * k,
-                       ix.stripe_rank, ix.stripe_world);
-    VI_HIP(hipGetLastError());
-  }
-  // ---- results ----
-  if (!io.on_device) {
-    VI_HIP(hipMemcpyAsync(io.D, Dd, nq * k * sizeof(float), hipMemcpyDeviceToHost, st));
-    VI_HIP(hipMemcpyAsync(io.I, Id, nq * k * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    if (io.V) {
-      VI_TRY(ws.V.reserve(nq * k * dim));
-      hipLaunchKernelGGL(gather_vectors_kernel, dim3((uint32_t)(nq * k)), dim3(64), 0, st, ix.lists.blocks.p, dq, dim,
-                         slots, nq * k, ws.V.p);
-      VI_HIP(hipGetLastError());
-      VI_HIP(hipMemcpyAsync(io.V, ws.V.p, nq * k * dim * sizeof(float), hipMemcpyDeviceToHost, st));
-    }
-    if (io.counts) {
-      std::vector<uint32_t> c32(nq);
-      VI_HIP(hipMemcpyAsync(c32.data(), ws.counts.p, nq * 4, hipMemcpyDeviceToHost, st));
-      VI_HIP(hipStreamSynchronize(st));
-      for (uint64_t i = 0; i < nq; ++i) io.counts[i] = c32[i];
-    }
-  }
-  VI_HIP(hipStreamSynchronize(st));
-  fill_phase_times(stt, ix.cur().ev, timing);
-  return VI_OK;
-}
-
-// ------------------------------------------------------------------------------------------
-// radius search
-// ------------------------------------------------------------------------------------------
-vi_status range_result_begin(const DeviceIndex &ix, uint64_t nq, RangeResult *res) {
-  res->ix = &ix;
-  res->nq = nq;
-  res->total = 0;
-  res->h_lims.assign(nq + 1, 0);
-  return res->lims.reserve(nq + 1);  // (written by range_result_place: every call fills it from its first query on)
-}
-
-namespace {
-// a result buffer grown to `cap` entries with its first `used` kept
-template <typename T>
-vi_status grow_keeping(DevBuf<T> &b, uint64_t used, uint64_t cap, hipStream_t st) {
-  DevBuf<T> bigger;
-  VI_TRY(bigger.reserve(cap));
-  if (used) VI_HIP(hipMemcpyAsync(bigger.p, b.p, used * sizeof(T), hipMemcpyDeviceToDevice, st));
-  VI_HIP(hipStreamSynchronize(st));
-  std::swap(b.p, bigger.p);
-  std::swap(b.n, bigger.n);
-  return VI_OK;
-}
-}  // namespace
-
-vi_status range_result_place(RangeResult *res, uint64_t q0, uint64_t m, const uint32_t *counts_dev, hipStream_t st) {
-  std::vector<uint32_t> h(m);
-  if (m) {
-    VI_HIP(hipMemcpyAsync(h.data(), counts_dev, m * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    VI_HIP(hipStreamSynchronize(st));
-  }
-  for (uint64_t i = 0; i < m; ++i) res->h_lims[q0 + i + 1] = res->h_lims[q0 + i] + h[i];
-  const uint64_t total = res->h_lims[q0 + m];
-  for (uint64_t q = q0 + m; q < res->nq; ++q) res->h_lims[q + 1] = total;  // (queries still to come: empty so far)
-  if (total > res->cap || !res->D.p) {
-    // (one chunk — the rule — allocates exactly; a further chunk at least doubles)
-    const uint64_t cap = std::max<uint64_t>(1, res->cap ? std::max(total, 2 * res->cap) : total);
-    VI_TRY(grow_keeping(res->D, res->total, cap, st));
-    VI_TRY(grow_keeping(res->I, res->total, cap, st));
-    VI_TRY(grow_keeping(res->tie, res->total, cap, st));
-    VI_TRY(grow_keeping(res->slots, res->total, cap, st));
-    res->cap = cap;
-  }
-  res->total = total;
-  VI_HIP(hipMemcpyAsync(res->lims.p + q0, res->h_lims.data() + q0, (res->nq + 1 - q0) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-  return VI_OK;
-}
-
-vi_status device_index_range_search(const DeviceIndex &ix, const RangeIO &io, RangeResult *out) {
-  VI_HIP(hipSetDevice(ix.device));
-  auto lease = lease_search_context(ix);
-  if (!lease.ctx) return VI_ERR_DEVICE;  // (the message is make_context's)
-  t_ctx = lease.ctx;
-  hipStream_t st = ix.cur().stream;
-  SearchWorkspace &ws = ix.cur().ws;
-  const uint64_t nq = io.nq, nlists = ix.nlists;
-  const SlotFilter *flt = io.filter;
-  if (flt && flt->owner_serial != ix.serial) return fail(VI_ERR_INVALID_INPUT, "the filter was made for another index");
-  if (nq * 64 > 0x7FFFFFFFull) return fail(VI_ERR_INVALID_INPUT, "batch too large: split nq");
-  VI_TRY(range_result_begin(ix, nq, out));
-  const uint32_t P = (uint32_t)std::min<uint64_t>(io.n_probe, nlists);  // take(n_probe) (ivf_index.rs:216-220)
-  vi_search_stats &stt = ix.cur().stats;
-  stt = vi_search_stats{};
-  stt.nq = nq; stt.k = 0; stt.n_probe_eff = P; stt.coarse_candidates = nq * nlists;
-  // nothing to find: no query, an empty index, or a radius no squared distance is within
-  if (nq == 0 || P == 0 || nlists == 0 || io.radius2 < 0.0f) return range_result_place(out, 0, 0, nullptr, st);
-  const EngineKnobs kn = read_engine_knobs();
-  const float *Qd = io.queries;
-  if (!io.on_device) {
-    VI_TRY(ws.q.reserve(nq * ix.dim));
-    VI_HIP(hipMemcpyAsync(ws.q.p, io.queries, nq * ix.dim * sizeof(float), hipMemcpyHostToDevice, st));
-    Qd = ws.q.p;
-  }
-  VI_TRY(ws.stats.reserve(kStatWords));
-  // the MFMA engine has no k to limit it; everything else (D % 4 != 0, D > 1536, n_probe > 64, VI_FILTER=0) sorts every candidate
-  const bool mfma = !kn.force_generic && filter_path_applicable(ix, kn, 1, P);
-  const int timing = mfma ? ix.timing : 0;
-  if (mfma) VI_TRY(range_filter_pipeline(ix, kn, Qd, nq, io.radius2, P, out, st, timing, flt));
-  else VI_TRY(device_index_range_generic(ix, Qd, nq, io.radius2, P, out, st, flt));
-  if (ix.stripe_world > 1 && out->total) {
-    hipLaunchKernelGGL(stripe_tie_kernel, dim3((uint32_t)((out->total + 255) / 256)), dim3(256), 0, st, out->tie.p, out->total,
-                       ix.stripe_rank, ix.stripe_world);
-    VI_HIP(hipGetLastError());
-  }
-  VI_HIP(hipStreamSynchronize(st));
-  fill_phase_times(stt, ix.cur().ev, timing);
-  return VI_OK;
-}
-
-vi_status range_result_copy(const RangeResult &r, uint64_t *lims, float *D, int64_t *I, float *V) {
-  if (lims) std::memcpy(lims, r.h_lims.data(), (r.nq + 1) * sizeof(uint64_t));
-  if (r.total == 0) return VI_OK;
-  VI_HIP(hipSetDevice(r.ix->device));
-  if (D) VI_HIP(hipMemcpy(D, r.D.p, r.total * sizeof(float), hipMemcpyDeviceToHost));
-  if (I) VI_HIP(hipMemcpy(I, r.I.p, r.total * sizeof(int64_t), hipMemcpyDeviceToHost));
-  if (V) {
-    const uint32_t dim = r.ix->dim;
-    DevBuf<float> Vd;
-    const uint64_t step = std::max<uint64_t>(1, std::min<uint64_t>(r.total, (1ull << 28) / dim));  // <= 1 GiB of rows at a time
-    VI_TRY(Vd.reserve(step * dim));
-    for (uint64_t at = 0; at < r.total; at += step) {
-      const uint64_t n = std::min(step, r.total - at);
-      hipLaunchKernelGGL(gather_vectors_kernel, dim3((uint32_t)n), dim3(64), 0, nullptr, r.ix->lists.blocks.p, r.ix->dq, dim,
-                         r.slots.p + at, n, Vd.p);
-      VI_HIP(hipGetLastError());
-      VI_HIP(hipMemcpy(V + at * dim, Vd.p, n * dim * sizeof(float), hipMemcpyDeviceToHost));
-    }
-  }
+  if (timing) VI_HIP(hipEventRecord(ctx.ev[4], st));
   return VI_OK;
 }
 

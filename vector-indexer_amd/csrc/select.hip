@@ -840,16 +840,17 @@ __global__ void __launch_bounds__(256) coarse_select_direct_kernel(CoarseSelectA
 
 }  // namespace
 
-vi_status launch_list_select(const DeviceIndex &ix, const EngineKnobs &kn, const float *Qd, uint64_t nq, uint32_t P, uint64_t k,
-                             const SelectFrame &f, const SelectOutputs &out, const SlotFilter *flt, hipStream_t st) {
-  SearchWorkspace &ws = ix.cur().ws;
-  SelectArgs a{list_select_common(ix, kn, Qd, f),
-               (uint32_t)nq, P, (uint32_t)k, kn.segb0, ws.qoff.p, ws.qtot.p, ws.pair_rel.p, ws.pair_pos.p, ws.tile_start.p, ws.probes.p,
+vi_status launch_list_select(SearchBatch &b, uint64_t k, const SelectFrame &f, const SelectOutputs &out) {
+  const DeviceIndex &ix = b.ix;
+  SearchWorkspace &ws = b.ws();
+  hipStream_t st = b.st();
+  SelectArgs a{list_select_common(b, f),
+               (uint32_t)b.nq, b.P, (uint32_t)k, b.kn.segb0, ws.qoff.p, ws.qtot.p, ws.pair_rel.p, ws.pair_pos.p, ws.tile_start.p, ws.probes.p,
                ws.gorder.p, ix.list_first_block.p, ix.list_len.p, ix.ext_ids.p, out.D, out.I, out.tie, out.slots, out.counts};
   const size_t qsm = 4ull * ix.dim * sizeof(float);
-  const dim3 grid((uint32_t)((nq + 3) / 4));
-  if (flt) {  // an instantiation of its own: the unfiltered one keeps its registers and its four workgroups per CU
-    a.c.allow = flt->allow.p;
+  const dim3 grid((uint32_t)((b.nq + 3) / 4));
+  if (b.flt) {  // an instantiation of its own: the unfiltered one keeps its registers and its four workgroups per CU
+    a.c.allow = b.flt->allow.p;
     if (k <= 64) hipLaunchKernelGGL((select_kernel<FastTopK, true>), grid, dim3(256), qsm, st, a);
     else hipLaunchKernelGGL((select_kernel<FastTop128, true>), grid, dim3(256), qsm, st, a);
   } else if (k <= 64) {
@@ -861,13 +862,16 @@ vi_status launch_list_select(const DeviceIndex &ix, const EngineKnobs &kn, const
   return VI_OK;
 }
 
-vi_status launch_coarse_select(const DeviceIndex &ix, const EngineKnobs &kn, const float *Qd, uint64_t nq, uint32_t P, uint32_t segb,
-                               uint32_t recs, bool direct, hipStream_t st) {
-  SearchWorkspace &ws = ix.cur().ws;
+vi_status launch_coarse_select(SearchBatch &b, uint32_t segb, uint32_t recs, bool direct) {
+  const DeviceIndex &ix = b.ix;
+  const EngineKnobs &kn = b.kn;
+  SearchWorkspace &ws = b.ws();
+  const uint32_t nq = (uint32_t)b.nq, P = b.P;
+  hipStream_t st = b.st();
   // (both coarse selects keep what their histogram increment returns: the grouping's scatter ranks the pairs with it)
-  VI_TRY(ws.pair_rank.reserve(nq * P));
-  ws.pair_rank_valid = true;
-  CoarseSelectArgs a{select_common(ix, kn, Qd, (const float4 *)ix.centroids.blocks.p, kn.rank_bf16 && ix.centered ? ix.cent_xmax2_c : ix.cent_xmax2,
+  VI_TRY(ws.pair_rank.reserve(b.nq * P));
+  b.pair_rank_valid = true;
+  CoarseSelectArgs a{select_common(b, (const float4 *)ix.centroids.blocks.p, kn.rank_bf16 && ix.centered ? ix.cent_xmax2_c : ix.cent_xmax2,
                                    kGroupQ), (uint32_t)nq, P, (uint32_t)ix.nlists, segb, recs, ix.list_shard.p, ix.list_len.p, ws.probes.p,
                      ws.gorder.p, ws.cnt.p, (const float4 *)ix.cent_rows.p, kn.segb0, ws.pair_rel.p, ws.qtot.p,
                      (ix.dim & 15u) ? 0u : 1u, ws.pair_rank.p};

@@ -227,14 +227,15 @@ constexpr uint32_t kPickCap = 256;     // sub-blocks waiting for their 16 exact 
 constexpr uint32_t kSubBits = 21;      // request key = (probe rank << 22) | (sub-block of the list << 1) | lane half
 constexpr uint32_t kCacheG = 256;      // group records (values + probe/segment/half) kept in LDS per wave
 
-// the frame of a list or table ranked with the engine's current arithmetic (kn); the launchers adjust it per phase
-inline SelectCommon select_common(const DeviceIndex &ix, const EngineKnobs &kn, const float *Qd, const float4 *blocks, float xmax2, uint32_t gq,
-                                  bool wave_order = false, int trunc = 0) {
+// the frame of a list or table ranked with the batch's arithmetic (b.kn), records in b's workspace; the launchers adjust it per phase
+inline SelectCommon select_common(const SearchBatch &b, const float4 *blocks, float xmax2, uint32_t gq, bool wave_order = false, int trunc = 0) {
+  const DeviceIndex &ix = b.ix;
+  const EngineKnobs &kn = b.kn;
   const double u = 1.01 * std::ldexp(1.0, -24);
   SelectCommon c{};
-  c.Q = Qd; c.dim = ix.dim; c.dq = ix.dq; c.blocks = blocks;
-  c.gval = (const float4 *)ix.cur().ws.gval.p; c.gmeta = (const uint32_t *)ix.cur().ws.gpos.p;
-  c.brec = (const float4 *)ix.cur().ws.brec.p;
+  c.Q = b.Qd; c.dim = ix.dim; c.dq = ix.dq; c.blocks = blocks;
+  c.gval = (const float4 *)b.ws().gval.p; c.gmeta = (const uint32_t *)b.ws().gpos.p;
+  c.brec = (const float4 *)b.ws().brec.p;
   c.gamma = (float)((ix.dim + 2.0) * u);
   // |ranked value - (||v||^2 - 2 q.v)| <= e_scale (||q||^2 + 2 max||v||^2):
   //   f32 MFMA : (D+2) u'  accumulation of D products + the norm
@@ -262,17 +263,18 @@ inline SelectCommon select_common(const DeviceIndex &ix, const EngineKnobs &kn, 
   c.allow = nullptr;
   // per-wave counters go to two addresses: 2 same-address atomics per query cost more than the whole select, so
   // they are a diagnostic (VI_FILTER_STATS=1), not part of the normal path
-  c.dbg = kn.stats ? (unsigned long long *)ix.cur().ws.stats.p : nullptr;
+  c.dbg = kn.stats ? (unsigned long long *)b.ws().stats.p : nullptr;
   c.dbg_mask = kn.stats_mask;
   c.xmode = kn.select_xmode;
   return c;
 }
 
 // ... of the list phase as ranked per SelectFrame: what both list selects (top-k, radius) start from
-inline SelectCommon list_select_common(const DeviceIndex &ix, const EngineKnobs &kn, const float *Qd, const SelectFrame &f) {
-  SelectCommon c = select_common(ix, kn, Qd, (const float4 *)ix.lists.blocks.p, kn.rank_bf16 && ix.centered ? ix.xmax2_c : ix.xmax2, f.gq,
+inline SelectCommon list_select_common(const SearchBatch &b, const SelectFrame &f) {
+  const DeviceIndex &ix = b.ix;
+  SelectCommon c = select_common(b, (const float4 *)ix.lists.blocks.p, b.kn.rank_bf16 && ix.centered ? ix.xmax2_c : ix.xmax2, f.gq,
                                  f.wave_order, f.approx);
-  if (kn.stats_coarse) c.dbg = nullptr;
+  if (b.kn.stats_coarse) c.dbg = nullptr;
   c.hi_nat = (const uint4 *)ix.lists_hi_nat.p;
   c.u8_nat = (const uint4 *)ix.lists_u8_nat.p;
   if (f.rank_i8) {  // rank values 2 r within [m', m' + 1] of m' = |q - v|^2 - |q - 127|^2: the margins of that frame, an absolute error of 1
