@@ -517,7 +517,7 @@ vi_status vi_indexer_export_records_device(const vi_indexer *ix, uint64_t first,
  *   - a NaN / Inf query value: VI_ERR_PANIC (host entry), as for a search
  *   - f: candidates outside the filter's window are deleted from the sequence first (NULL: no filter)
  *   - on a partitioned handle (world_size > 1) the result covers the resident part, with the tie keys
- *     vi_indexer_search_device gives (stripe correction included): per-rank results merge by (distance, tie)
+ *     vi_indexer_search_device gives (stripe correction included): per-rank results merge by (distance, tie) — vi_range_merge_device
  *   - a batch is all or nothing: when scratch or result memory cannot be had the call fails (VI_ERR_DEVICE, or
  *     VI_ERR_INVALID_INPUT "split nq") and *out stays NULL
  * The result is an opaque object in CSR layout, as Faiss's RangeSearchResult: query q owns entries [lims[q], lims[q+1])
@@ -534,6 +534,10 @@ vi_status vi_range_result_copy(const vi_range_result *r, uint64_t *lims, float *
 /* the result's own device buffers (any of the four may be NULL); tie = (candidate-order rank << 32) | list position */
 vi_status vi_range_result_device(const vi_range_result *r, const uint64_t **lims_dev, const float **D_dev,
                                  const int64_t **I_dev, const uint64_t **tie_dev);
+/* the same four arrays copied into DEVICE buffers of the caller on the result's GPU (lims nq + 1, the rest `total` each;
+ * any may be NULL), e.g. tensors of a framework that is to own them; complete on return */
+vi_status vi_range_result_copy_device(const vi_range_result *r, uint64_t *lims_dev, float *D_dev, int64_t *I_dev,
+                                      uint64_t *tie_dev);
 void vi_range_result_free(vi_range_result *r); /* NULL ok */
 
 /* Merge `parts` per-rank partial results (each nq x k, device pointers laid out
@@ -548,6 +552,36 @@ vi_status vi_merge_partials_device(int32_t device, uint64_t nq, uint64_t k, uint
 uint64_t vi_packed_result_bytes(uint64_t nq, uint64_t k);
 vi_status vi_merge_partials_packed_device(int32_t device, uint64_t nq, uint64_t k, uint32_t parts,
                                           const void *packed_dev, float *D_out, int64_t *I_out);
+
+/* ---- extension: merging per-rank radius results ---------------------------------------------------------------------
+ * The radius results of the ranks of a partitioned index, for the same nq queries, merged into the result the
+ * unpartitioned index gives: ids, distance bits, tie keys, order and per-query counts.  Every part is CSR (lims nq + 1;
+ * D / I / tie of lims[nq] entries) with each row sorted by (distance bits, tie), which is how
+ * vi_indexer_range_search_device leaves it; the output row of query q is the parts' rows q merged on that key and
+ * lims[q] is the sum of the parts' lims[q].
+ *   - the pointer arrays serve both uses: in-process ranks pass what vi_range_result_device returned; after an
+ *     all-gather into one buffer the pointers are base + r * stride
+ *   - the result is an ordinary vi_range_result that belongs to no index: _total, _device (tie included), _free and
+ *     _copy with V == NULL work as for any result; _copy with V != NULL is VI_ERR_INVALID_INPUT (the stored vectors
+ *     live on the ranks).  It owns its buffers and stays valid after the parts and their indexers are freed
+ *   - parts == 1 is a copy; a part or a row without entries is legal; no entry at all is VI_OK with lims all zero;
+ *     nq == 0 is VI_OK with the one lims entry 0, as a radius search of no query
+ *   - sortedness is NOT checked: parts whose rows are not sorted give an unspecified order inside each row, never an
+ *     access outside the buffers (lims must be non-decreasing CSR offsets).  Equal keys in two parts (the same rank
+ *     passed twice) come out lower part first
+ *   - errors, all VI_ERR_INVALID_INPUT before any device work: out == NULL, a NULL array, parts == 0 or > 64, a NULL
+ *     lims pointer, a NULL D / I / tie pointer of a part.  Then: no device, or an ordinal out of range, is
+ *     VI_ERR_DEVICE; there is no CPU fallback.  All or nothing: on any failure *out stays NULL
+ *   - one stream, one host synchronisation before the output is allocated (the total sizes it), complete on return
+ * lims_dev / D_dev / I_dev / tie_dev: HOST arrays of `parts` DEVICE pointers (part p: lims nq+1, the rest lims_p[nq] each). */
+vi_status vi_range_merge_device(int32_t device, uint64_t nq, uint32_t parts,
+                                const uint64_t *const *lims_dev, const float *const *D_dev,
+                                const int64_t *const *I_dev, const uint64_t *const *tie_dev,
+                                vi_range_result **out);
+/* HIP-event times of the calling thread's last vi_range_merge_device, taken only while the environment variable
+ * VI_RANGE_MERGE_TIMING is set (and not "0"); zeros otherwise.  ms_alloc: between the two kernels — the read-back of
+ * lims, the synchronisation, the allocations.  Any pointer may be NULL. */
+vi_status vi_range_merge_last_times(float *ms_lims, float *ms_alloc, float *ms_place);
 
 /* accessors */
 uint32_t vi_indexer_dimension(const vi_indexer *ix);

@@ -1090,7 +1090,51 @@ vi_status vi_range_result_device(const vi_range_result *r, const uint64_t **lims
   });
 }
 
+vi_status vi_range_result_copy_device(const vi_range_result *r, uint64_t *lims_dev, float *D_dev, int64_t *I_dev,
+                                      uint64_t *tie_dev) {
+  return vi::guarded([&]() -> vi_status {
+  if (!r) return fail(VI_ERR_INVALID_INPUT, "null range result");
+  const vi::RangeResult &x = r->impl;
+  VI_HIP(hipSetDevice(x.device));
+  if (lims_dev) VI_HIP(hipMemcpyAsync(lims_dev, x.lims.p, (x.nq + 1) * sizeof(uint64_t), hipMemcpyDeviceToDevice, nullptr));
+  if (D_dev && x.total) VI_HIP(hipMemcpyAsync(D_dev, x.D.p, x.total * sizeof(float), hipMemcpyDeviceToDevice, nullptr));
+  if (I_dev && x.total) VI_HIP(hipMemcpyAsync(I_dev, x.I.p, x.total * sizeof(int64_t), hipMemcpyDeviceToDevice, nullptr));
+  if (tie_dev && x.total) VI_HIP(hipMemcpyAsync(tie_dev, x.tie.p, x.total * sizeof(uint64_t), hipMemcpyDeviceToDevice, nullptr));
+  VI_HIP(hipStreamSynchronize(nullptr));
+  return VI_OK;
+  });
+}
+
 void vi_range_result_free(vi_range_result *r) { delete r; }
+
+vi_status vi_range_merge_device(int32_t device, uint64_t nq, uint32_t parts, const uint64_t *const *lims_dev, const float *const *D_dev,
+                                const int64_t *const *I_dev, const uint64_t *const *tie_dev, vi_range_result **out) {
+  return vi::guarded([&]() -> vi_status {
+  if (!out) return fail(VI_ERR_INVALID_INPUT, "null pointer");
+  *out = nullptr;
+  if (!lims_dev || !D_dev || !I_dev || !tie_dev) return fail(VI_ERR_INVALID_INPUT, "null pointer array");
+  if (parts == 0 || parts > vi::kRangeMergeMaxParts) return fail(VI_ERR_INVALID_INPUT, "parts must be 1..64, got %u", parts);
+  for (uint32_t p = 0; p < parts; ++p) {
+    if (!lims_dev[p]) return fail(VI_ERR_INVALID_INPUT, "part %u: null lims pointer", p);
+    // (a part without entries still has buffers: every vi_range_result does)
+    if (!D_dev[p] || !I_dev[p] || !tie_dev[p]) return fail(VI_ERR_INVALID_INPUT, "part %u: null D / I / tie pointer", p);
+  }
+  auto r = std::make_unique<vi_range_result>();
+  VI_TRY(vi::range_merge_device(device, nq, parts, lims_dev, D_dev, I_dev, tie_dev, &r->impl));  // (all or nothing)
+  *out = r.release();
+  return VI_OK;
+  });
+}
+
+vi_status vi_range_merge_last_times(float *ms_lims, float *ms_alloc, float *ms_place) {
+  return vi::guarded([&]() -> vi_status {
+  const vi::RangeMergeTimes t = vi::range_merge_last_times();
+  if (ms_lims) *ms_lims = t.ms_lims;
+  if (ms_alloc) *ms_alloc = t.ms_alloc;
+  if (ms_place) *ms_place = t.ms_place;
+  return VI_OK;
+  });
+}
 
 vi_status vi_merge_partials_device(int32_t device, uint64_t nq, uint64_t k, uint32_t parts, const float *D_parts,
                                    const int64_t *I_parts, const uint64_t *tie_parts, float *D_out, int64_t *I_out) {

@@ -249,7 +249,9 @@ vi_status device_index_search(const DeviceIndex &ix, const SearchIO &io);
 // [lims[q], lims[q + 1]) of D / I / tie / slots, sorted as the reference's stable candidate sort leaves them.  Owns its
 // device buffers; outlives later searches of its index, not the index.
 struct RangeResult {
-  const DeviceIndex *ix = nullptr;  // the index searched (vi_range_result_copy gathers stored vectors from it)
+  const DeviceIndex *ix = nullptr;  // the index searched (vi_range_result_copy gathers stored vectors from it); null: a
+                                    // merged result (range_merge_device), which belongs to no index and has no slots
+  int device = 0;                   // where the buffers live
   uint64_t nq = 0, total = 0;
   std::vector<uint64_t> h_lims;     // host copy of lims: nq + 1
   DevBuf<uint64_t> lims;            // nq + 1
@@ -335,6 +337,18 @@ vi_status merge_partials_packed_device(int device, uint64_t nq, uint64_t k, uint
 vi_status merge_partials_device(int device, uint64_t nq, uint64_t k, uint32_t parts, const float *D_parts,
                                 const int64_t *I_parts, const uint64_t *tie_parts, float *D_out,
                                 int64_t *I_out);
+
+// ---- merging per-rank radius results (range_merge.hip) ----
+// `parts` (1..kRangeMergeMaxParts) CSR radius results of the same nq queries, every row sorted by (bits(D), tie) -> one
+// result in that order on `device`, owned by *out (ix == nullptr).  The four arrays are HOST arrays of device pointers.
+// One stream, one synchronisation before the output is allocated, synchronised on return.  Sortedness is not checked:
+// unsorted rows give an unspecified order, never an access outside the buffers.
+constexpr uint32_t kRangeMergeMaxParts = 64;
+vi_status range_merge_device(int device, uint64_t nq, uint32_t parts, const uint64_t *const *lims_dev, const float *const *D_dev,
+                             const int64_t *const *I_dev, const uint64_t *const *tie_dev, RangeResult *out);
+// HIP-event times of this thread's last range_merge_device under VI_RANGE_MERGE_TIMING (set, not '0'); zeros otherwise
+struct RangeMergeTimes { float ms_lims = 0, ms_alloc = 0, ms_place = 0; };  // ms_alloc: lims read-back, the sync, the allocations
+RangeMergeTimes range_merge_last_times();
 
 vi_status l2sq_pairs_device(const float *a, const float *b, uint64_t n, uint32_t d, int order, float *out);
 

@@ -263,6 +263,7 @@ vi_status device_index_range_search(const DeviceIndex &ix, const RangeIO &io, Ra
 
 vi_status range_result_begin(const DeviceIndex &ix, uint64_t nq, RangeResult *res) {
   res->ix = &ix;
+  res->device = ix.device;
   res->nq = nq;
   res->total = 0;
   res->h_lims.assign(nq + 1, 0);
@@ -293,9 +294,10 @@ vi_status range_result_place(RangeResult *res, uint64_t q0, uint64_t m, const ui
 }
 
 vi_status range_result_copy(const RangeResult &r, uint64_t *lims, float *D, int64_t *I, float *V) {
+  if (V && !r.ix) return fail(VI_ERR_INVALID_INPUT, "a merged result has no stored vectors: they live on the ranks");
   if (lims) std::memcpy(lims, r.h_lims.data(), (r.nq + 1) * sizeof(uint64_t));
   if (r.total == 0) return VI_OK;
-  VI_HIP(hipSetDevice(r.ix->device));
+  VI_HIP(hipSetDevice(r.device));
   if (D) VI_HIP(hipMemcpy(D, r.D.p, r.total * sizeof(float), hipMemcpyDeviceToHost));
   if (I) VI_HIP(hipMemcpy(I, r.I.p, r.total * sizeof(int64_t), hipMemcpyDeviceToHost));
   if (V) {

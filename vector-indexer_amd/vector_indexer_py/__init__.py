@@ -13,6 +13,8 @@ bindings/python/python/vector_indexer_py/__init__.py):
     VectorIndex.remove_ids(ids) / .retain(filter) -> int    extension: remove records from it (by id / all a filter excludes)
     VectorIndex.upsert(xb, ext_ids, timestamps=None) -> int extension: replace the records that carry ext_ids, in one rewrite
     VectorIndex.get(ids) / .export(first, count)            extension: read records back, by id / a range in list order
+    merge_range_results(device, parts) -> RangeResult       extension: the radius results of the ranks of a partitioned
+                                                            index merged on the device into the unpartitioned result
 
 Errors surface as RuntimeError, as PyO3's PyRuntimeError does.  There is NO CPU fallback: if
 libvi_amd.so is missing or no MI355X is visible, build/load/search raise.
@@ -28,7 +30,7 @@ import numpy as np
 from . import _native
 from ._native import (ViError, lib, VI_ASSIGN_EXACT, VI_ASSIGN_REFERENCE, VI_ORDER_LANES, VI_ORDER_SCALAR)
 
-__all__ = ["build", "load", "suggest_nlist", "VectorIndex", "TimestampFilter", "IdFilter", "FilterIntersection", "AnyFilter", "RangeResult", "ViError", "kmeans_mini_batch", "kmeans_parallel",
+__all__ = ["build", "load", "suggest_nlist", "VectorIndex", "TimestampFilter", "IdFilter", "FilterIntersection", "AnyFilter", "RangeResult", "merge_range_results", "merge_range_results_device", "ViError", "kmeans_mini_batch", "kmeans_parallel",
            "assign", "l2sq_pairs", "VI_ASSIGN_EXACT", "VI_ASSIGN_REFERENCE", "VI_ORDER_LANES", "VI_ORDER_SCALAR"]
 
 
@@ -98,10 +100,11 @@ class RangeResult:
     """A radius search's result left on the device (VectorIndex.range_search_device), CSR like Faiss's RangeSearchResult:
     query q owns entries [lims[q], lims[q + 1]) of D / I / tie.  The four pointers are device addresses of buffers this
     object owns; they stay valid through later searches of the index, until free() (or the object's end).  Keeps its
-    index alive."""
+    index alive.  index None: a merged result (merge_range_results), which belongs to no index — it outlives its parts,
+    and the stored vectors of its hits stay on the ranks."""
 
     def __init__(self, index, handle, nq):
-        self._index = index  # (the native result must be freed before its indexer)
+        self._index = index  # (the native result must be freed before its indexer; None: a merged result)
         self._h = handle
         self.nq = int(nq)
         self.total = int(lib().vi_range_result_total(handle))
@@ -111,11 +114,19 @@ class RangeResult:
 
     def copy(self, include_vectors=False):
         """(lims u64[nq + 1], D f32[total], I i64[total][, V f32[total, dim]]) on the host"""
+        if include_vectors and self._index is None:
+            raise ViError(_native.VI_ERR_INVALID_INPUT, "a merged result has no stored vectors: they live on the ranks")
         lims = np.zeros(self.nq + 1, dtype=np.uint64)
         D, I = np.zeros(self.total, dtype=np.float32), np.zeros(self.total, dtype=np.int64)
         V = np.zeros((self.total, self._index.dimension), dtype=np.float32) if include_vectors else None
         _native.check(lib().vi_range_result_copy(self._h, _native.ptr(lims), _native.ptr(D), _native.ptr(I), _native.ptr(V)))
         return (lims, D, I, V) if include_vectors else (lims, D, I)
+
+    def copy_device(self, lims_ptr: int = 0, D_ptr: int = 0, I_ptr: int = 0, tie_ptr: int = 0):
+        """the same arrays (tie included) copied into device buffers of the caller's on the result's GPU — lims nq + 1,
+        the rest `total` entries each; a pointer of 0 skips that array.  Complete on return."""
+        _native.check(lib().vi_range_result_copy_device(self._h, *[C.c_void_p(p) if p else None
+                                                                   for p in (lims_ptr, D_ptr, I_ptr, tie_ptr)]))
 
     def free(self):
         h, self._h = getattr(self, "_h", None), None
@@ -127,6 +138,32 @@ class RangeResult:
         self.lims_ptr = self.D_ptr = self.I_ptr = self.tie_ptr = 0
 
     __del__ = free
+
+
+def merge_range_results_device(device: int, nq: int, lims_ptrs, D_ptrs, I_ptrs, tie_ptrs) -> RangeResult:
+    """extension: the radius results of the ranks of a partitioned index, for the same nq queries, merged on `device` into
+    the unpartitioned result (vi_range_merge_device).  Part p is CSR in device memory: lims_ptrs[p] -> u64[nq + 1],
+    D / I / tie_ptrs[p] -> f32 / i64 / u64 of lims[nq] entries, every row sorted by (distance bits, tie) as
+    range_search_device leaves it.  Complete on return; the parts may go afterwards."""
+    cols = [list(map(int, c)) for c in (lims_ptrs, D_ptrs, I_ptrs, tie_ptrs)]
+    parts = len(cols[0])
+    if any(len(c) != parts for c in cols):
+        raise ViError(_native.VI_ERR_INVALID_INPUT, "one lims, D, I and tie pointer per part")
+    arrays = [(C.c_void_p * max(parts, 1))(*c) for c in cols]
+    h = C.c_void_p()
+    _native.check(lib().vi_range_merge_device(int(device), int(nq), parts, *arrays, C.byref(h)))
+    return RangeResult(None, h, nq)
+
+
+def merge_range_results(device: int, parts) -> RangeResult:
+    """... for RangeResults that live on `device` (in-process ranks)"""
+    parts = list(parts)
+    if not parts:
+        raise ViError(_native.VI_ERR_INVALID_INPUT, "parts must be 1..64")
+    if any(p.nq != parts[0].nq for p in parts):
+        raise ViError(_native.VI_ERR_INVALID_INPUT, "the parts answer different numbers of queries")
+    return merge_range_results_device(device, parts[0].nq, [p.lims_ptr for p in parts], [p.D_ptr for p in parts],
+                                      [p.I_ptr for p in parts], [p.tie_ptr for p in parts])
 
 
 def _filter_handle(f):

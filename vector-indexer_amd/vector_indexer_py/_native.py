@@ -134,7 +134,10 @@ SIGNATURES = {
     "vi_range_result_total": (u64, [vp]),
     "vi_range_result_copy": (C.c_int, [vp, vp, vp, vp, vp]),
     "vi_range_result_device": (C.c_int, [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]),
+    "vi_range_result_copy_device": (C.c_int, [vp, vp, vp, vp, vp]),
     "vi_range_result_free": (None, [vp]),
+    "vi_range_merge_device": (C.c_int, [i32, u64, u32, vp, vp, vp, vp, C.POINTER(vp)]),
+    "vi_range_merge_last_times": (C.c_int, [C.POINTER(f32), C.POINTER(f32), C.POINTER(f32)]),
     "vi_merge_partials_device": (C.c_int, [i32, u64, u64, u32, vp, vp, vp, vp, vp]),
     "vi_packed_result_bytes": (u64, [u64, u64]),
     "vi_merge_partials_packed_device": (C.c_int, [i32, u64, u64, u32, vp, vp, vp]),

@@ -6,6 +6,11 @@ keys.  Per query each rank returns its local top-k (D, I, tie); the three arrays
 torch.distributed.all_gather (backend "nccl" == RCCL over xGMI on the GPU box, "gloo" in the CPU
 protocol tests) and merged on (dist, tie), which reproduces the single-GPU stable order exactly.
 
+A radius search returns ragged rows, so its exchange is two all-gathers: every rank's lims (nq + 1 u64: fixed size, and
+they tell every rank every total), then one byte buffer per rank padded to the largest total (range_part_layout).  The
+merge by the same key runs on the device, parallel over entries (vi_range_merge_device).  A filter belongs to one handle:
+every rank makes its own from the same predicate and passes it as `filter=`.
+
 The reference has no distributed mode (its "two-level sharding" only groups files,
 src/ivf_index.rs:104-164); this is the MI355X-native extension BASELINE.json's north_star asks for.
 """
@@ -20,21 +25,93 @@ def block_owner(block: int, world: int) -> int:
     return int(block) % max(int(world), 1)
 
 
-class ShardedSearcher:
-    """local_search(xq, k, n_probe) -> (D, I, tie) tensors on this rank's device;
-    merge(D_all, I_all, T_all) -> (D, I) with *_all shaped [world, nq, k]."""
+def range_part_layout(cap: int):
+    """one rank's radius result padded to `cap` entries, as the second all-gather of ShardedSearcher.range_search carries
+    it: [D f32 cap | pad to 8 B | I i64 cap | tie u64 cap] (the layout idea of vi_packed_result_bytes) ->
+    (byte offset of I, byte offset of tie, bytes in all).  Every block starts 8-byte aligned."""
+    cap = int(cap)
+    off_I = (cap * 4 + 7) // 8 * 8
+    off_tie = off_I + cap * 8
+    return off_I, off_tie, off_tie + cap * 8
 
-    def __init__(self, local_search, merge, group=None):
+
+def pack_range_part(cap: int, D, I, tie):
+    """(D f32[n], I i64[n], tie i64[n] — the u64 bit pattern) tensors, n <= cap -> a uint8 tensor of
+    range_part_layout(cap) bytes on their device; the padding is zero"""
+    import torch
+    off_I, off_tie, nbytes = range_part_layout(cap)
+    n = int(D.shape[0])
+    if n > cap or I.shape[0] != n or tie.shape[0] != n:
+        raise ValueError("a part holds n entries of D, I and tie each, n <= cap")
+    buf = torch.zeros(nbytes, dtype=torch.uint8, device=D.device)
+    if n:
+        buf[:4 * n].view(torch.float32).copy_(D)
+        buf[off_I:off_I + 8 * n].view(torch.int64).copy_(I)
+        buf[off_tie:off_tie + 8 * n].view(torch.int64).copy_(tie)
+    return buf
+
+
+def unpack_range_part(buf, cap: int, n: int):
+    """the first n entries of a packed part -> (D, I, tie) views of buf"""
+    import torch
+    off_I, off_tie, nbytes = range_part_layout(cap)
+    if buf.numel() != nbytes or n > cap:
+        raise ValueError("not a part packed for this cap")
+    n = int(n)
+    return (buf[:4 * n].view(torch.float32), buf[off_I:off_I + 8 * n].view(torch.int64),
+            buf[off_tie:off_tie + 8 * n].view(torch.int64))
+
+
+class ShardedSearcher:
+    """local_search(xq, k, n_probe[, filter=]) -> (D, I, tie) tensors on this rank's device;
+    merge(D_all, I_all, T_all) -> (D, I) with *_all shaped [world, nq, k].
+
+    Radius search (both optional; range_search needs them):
+    local_range_search(xq, radius2, n_probe[, filter=]) -> (lims i64[nq + 1], D f32[n], I i64[n], tie i64[n]) tensors on
+    this rank's device, CSR, n = lims[nq], every row sorted by (distance bits, tie) (lims and tie: u64 bit patterns);
+    merge_range(lims_all i64[world, nq + 1], packed u8[world, range_part_layout(cap)[2]], cap) -> the merged
+    (lims, D, I, tie), rank r's part being unpack_range_part(packed[r], cap, lims_all[r, nq])."""
+
+    def __init__(self, local_search, merge, group=None, local_range_search=None, merge_range=None):
         import torch.distributed as dist
         self._dist = dist
         self._local_search = local_search
         self._merge = merge
         self._group = group
+        self.local_range_search = local_range_search
+        self.merge_range = merge_range
         self.world = dist.get_world_size(group) if dist.is_initialized() else 1
 
-    def search(self, xq, k, n_probe):
+    def range_search(self, xq, radius2, n_probe, filter=None):
+        """every probed candidate within radius2 over all ranks -> (lims, D, I, tie) as local_range_search gives them,
+        equal to the unpartitioned index's result; world 1: the local result.  filter: this rank's own filter object
+        (every rank makes its own from the same predicate).  Two all-gathers: the ranks' lims (which tell every rank
+        every total), then one byte buffer per rank padded to the largest total (range_part_layout); the second and the
+        merge are skipped when no rank found anything."""
         import torch
-        D, I, T = self._local_search(xq, k, n_probe)
+        if self.local_range_search is None or self.merge_range is None:
+            raise RuntimeError("this ShardedSearcher was made without local_range_search / merge_range")
+        kw = {} if filter is None else {"filter": filter}
+        lims, D, I, T = self.local_range_search(xq, radius2, n_probe, **kw)
+        if self.world == 1:
+            return lims, D, I, T
+        n1 = lims.shape[0]
+        lims_all = torch.empty((self.world * n1,), dtype=lims.dtype, device=lims.device)
+        self._dist.all_gather_into_tensor(lims_all, lims.contiguous(), group=self._group)
+        lims_all = lims_all.view(self.world, n1)
+        cap = int(lims_all[:, -1].max().item())
+        if cap == 0:
+            return lims, D, I, T       # (every rank's result is the empty one)
+        mine = pack_range_part(cap, D, I, T)
+        packed = torch.empty((self.world * mine.numel(),), dtype=torch.uint8, device=mine.device)
+        self._dist.all_gather_into_tensor(packed, mine, group=self._group)
+        return self.merge_range(lims_all, packed.view(self.world, mine.numel()), cap)
+
+    def search(self, xq, k, n_probe, filter=None):
+        """filter: this rank's own filter object (every rank makes its own from the same predicate); it reaches
+        local_search as the keyword `filter`, and only when given"""
+        import torch
+        D, I, T = self._local_search(xq, k, n_probe) if filter is None else self._local_search(xq, k, n_probe, filter=filter)
         if self.world == 1:
             return D, I
         nq, k = D.shape
@@ -56,13 +133,37 @@ def gpu_searcher(index, device_index: int, group=None) -> ShardedSearcher:
 
     dev = torch.device("cuda", device_index)
 
-    def local_search(xq, k, n_probe):
+    def local_search(xq, k, n_probe, filter=None):
         nq = xq.shape[0]
         D = torch.empty((nq, k), dtype=torch.float32, device=dev)
         I = torch.empty((nq, k), dtype=torch.int64, device=dev)
         T = torch.empty((nq, k), dtype=torch.int64, device=dev)  # u64 bit pattern
-        index.search_device(xq.data_ptr(), nq, k, n_probe, D.data_ptr(), I.data_ptr(), T.data_ptr())
+        index.search_device(xq.data_ptr(), nq, k, n_probe, D.data_ptr(), I.data_ptr(), T.data_ptr(), filter=filter)
         return D, I, T
+
+    def to_tensors(res):
+        """a native RangeResult's arrays copied into torch tensors (the exchange works on tensors), the result freed"""
+        n, nq = res.total, res.nq
+        out = (torch.empty(nq + 1, dtype=torch.int64, device=dev), torch.empty(n, dtype=torch.float32, device=dev),
+               torch.empty(n, dtype=torch.int64, device=dev), torch.empty(n, dtype=torch.int64, device=dev))
+        torch.cuda.synchronize(dev)
+        res.copy_device(*[t.data_ptr() if t.numel() else 0 for t in out])
+        res.free()
+        return out
+
+    def local_range_search(xq, radius2, n_probe, filter=None):
+        torch.cuda.synchronize(dev)  # (xq may come from torch's stream)
+        return to_tensors(index.range_search_device(xq.data_ptr(), xq.shape[0], radius2, n_probe, filter=filter))
+
+    def merge_range(lims_all, packed, cap):
+        from . import merge_range_results_device
+        world, n1 = lims_all.shape
+        off_I, off_tie, stride = range_part_layout(cap)
+        lims_all, packed = lims_all.contiguous(), packed.contiguous()
+        torch.cuda.synchronize(dev)  # (the all-gathers ran on torch's stream)
+        base = [packed.data_ptr() + r * stride for r in range(world)]
+        return to_tensors(merge_range_results_device(device_index, n1 - 1, [lims_all.data_ptr() + r * n1 * 8 for r in range(world)],
+                                                     base, [b + off_I for b in base], [b + off_tie for b in base]))
 
     def merge(Dg, Ig, Tg):
         world, nq, k = Dg.shape
@@ -73,7 +174,28 @@ def gpu_searcher(index, device_index: int, group=None) -> ShardedSearcher:
                                                              Tg.data_ptr(), D.data_ptr(), I.data_ptr()))
         return D, I
 
-    return ShardedSearcher(local_search, merge, group)
+    return ShardedSearcher(local_search, merge, group, local_range_search, merge_range)
+
+
+def merge_range_reference(parts):
+    """numpy statement of the radius merge rule (used by the CPU protocol tests): parts = [(lims, D, I, tie), ...], CSR
+    results of the same queries -> (lims u64, D, I, tie u64): per query the union of the parts' rows ordered by
+    (distance bits, tie) — distances are >= +0 — and, for equal keys, by part"""
+    parts = [(np.asarray(l).astype(np.uint64), np.asarray(d, dtype=np.float32), np.asarray(i, dtype=np.int64),
+              np.asarray(t).view(np.uint64) if np.asarray(t).dtype == np.int64 else np.asarray(t, dtype=np.uint64))
+             for l, d, i, t in parts]
+    nq = parts[0][0].size - 1
+    lims = np.zeros(nq + 1, dtype=np.uint64)
+    for l, _, _, _ in parts:
+        lims += l
+    D, I, T = np.zeros(int(lims[-1]), np.float32), np.zeros(int(lims[-1]), np.int64), np.zeros(int(lims[-1]), np.uint64)
+    for q in range(nq):
+        rows = [(d[int(l[q]):int(l[q + 1])], i[int(l[q]):int(l[q + 1])], t[int(l[q]):int(l[q + 1])]) for l, d, i, t in parts]
+        d, i, t = (np.concatenate([r[c] for r in rows]) for c in range(3))
+        order = np.lexsort((t, d.view(np.uint32)))  # (stable: equal keys stay in part order)
+        a, b = int(lims[q]), int(lims[q + 1])
+        D[a:b], I[a:b], T[a:b] = d[order], i[order], t[order]
+    return lims, D, I, T
 
 
 def merge_partials_reference(Dg, Ig, Tg):
