@@ -338,7 +338,8 @@ vi_status vi_indexer_search_probed_device(const vi_indexer *ix, const float *que
  * window.  A window that admits everything returns bit for bit what the unfiltered entry returns; one that admits
  * nothing returns VI_OK with zero results; ts_min > ts_max is VI_ERR_INVALID_INPUT.
  * A vi_filter belongs to the resident index of ONE handle (another handle's, or one made before the handle was rebuilt,
- * is VI_ERR_INVALID_INPUT), is immutable, and may be shared by the concurrent searches a handle allows.  It holds 12 bytes
+ * is VI_ERR_INVALID_INPUT), is immutable (the one exception: `reuse` of vi_indexer_filter_compose, below), and may be
+ * shared by the concurrent searches a handle allows.  It holds 12 bytes
  * of device memory per resident slot (16 for 8-bit descriptor data) and must be freed before its indexer.
  * f == NULL: the unfiltered entry. */
 typedef struct vi_filter vi_filter;
@@ -382,6 +383,59 @@ vi_status vi_indexer_filter_ids(const vi_indexer *ix, const uint64_t *ids, uint6
 vi_status vi_indexer_filter_ids_device(const vi_indexer *ix, const uint64_t *ids_dev, uint64_t n, vi_id_mode mode,
                                        vi_filter **out);
 vi_status vi_filter_intersect(const vi_indexer *ix, const vi_filter *a, const vi_filter *b, vi_filter **out);
+
+/* ---- compound filters: union, complement, id ranges, masks, and one call for a whole expression (extension; Faiss's
+ * IDSelectorRange / IDSelectorOr / IDSelectorNot / IDSelectorBitmap) ----
+ * vi_indexer_filter_compose makes ONE filter from the AND (VI_JOIN_AND) or the OR (VI_JOIN_OR) of n_terms = 1 ..
+ * VI_FILTER_MAX_TERMS terms, in one kernel launch with one synchronisation.  A resident record is admitted when the join
+ * of the terms holds; `negate` = 1 flips a term before the join.  Negation is relative to the resident records: no
+ * expression admits a pad slot, as with a deny set.  Deeper expressions nest through VI_TERM_FILTER.  The result is a
+ * vi_filter like any other (searches, radius searches, vi_indexer_retain, the per-rank merges), and the filtered result
+ * of a query is, as above, the reference's candidate sequence less the candidates the filter does not admit.
+ * Fields a kind does not use are ignored.  Per kind:
+ *   VI_TERM_TIMESTAMPS   lo <= stored timestamp <= hi   } both inclusive; any u64 is a legal bound, (0, UINT64_MAX) holds
+ *   VI_TERM_ID_RANGE     lo <= external id <= hi        } everywhere; lo > hi is VI_ERR_INVALID_INPUT
+ *   VI_TERM_IDS          the external id is one of data[0 .. n) (u64, host memory): the rules of vi_indexer_filter_ids —
+ *   VI_TERM_IDS_DEVICE     no order, duplicates allowed, absent ids ignored, UINT64_MAX legal; n == 0 (data may be NULL)
+ *                          holds nowhere.  _DEVICE: the ids are read in place from device memory.  Every id term of a
+ *                          call gets a table of its own; all are freed before the call returns.
+ *   VI_TERM_MASK         data[i] != 0 (n bytes, host memory; _DEVICE: device memory, read in place), i = the record's
+ *   VI_TERM_MASK_DEVICE    ordinal in LIST ORDER: byte i belongs to the record vi_indexer_export_records returns as row i
+ *                          — an attribute the caller keeps beside an export.  n must equal vi_indexer_num_vectors(ix).  On
+ *                          a partitioned handle this is the rank's own list order, as for an export: a mask is per rank.
+ *   VI_TERM_FILTER       `filter` admits the record: a filter of this handle's index (another handle's, or one made
+ *                          before an update: VI_ERR_INVALID_INPUT)
+ * reuse (or NULL): a filter of this handle's index that the call OVERWRITES in place; *out is then `reuse`, and no filter
+ * buffer is allocated.  This is the one exception to "a vi_filter is immutable": THE CALLER GUARANTEES THAT NO SEARCH IS
+ * USING `reuse` DURING THE CALL.  `reuse` passes the same validity check as an operand (one made before an update is
+ * rejected) and must not be one of the call's own VI_TERM_FILTER operands (the writer clears the allow words first):
+ * VI_ERR_INVALID_INPUT before any device work, `reuse` untouched.  On an error after validation the content of `reuse`
+ * is unspecified; it stays freeable.
+ * Errors, all VI_ERR_INVALID_INPUT before any device work (*out untouched): a null ix, terms or out; n_terms outside
+ * 1 .. 8; an unknown kind or join; negate other than 0 / 1; data == NULL with n > 0; a null `filter` of a FILTER term; a
+ * handle with no index; a timestamp term on an index that keeps no timestamps; an id or id-range term on an index that
+ * keeps no external ids; an id set of more than 2^40 ids; a mask of the wrong length.
+ * The five entries below it are thin calls into it: a | b, the complement of a within the resident records, one id range,
+ * one mask. */
+#define VI_FILTER_MAX_TERMS 8
+typedef enum vi_term_kind { VI_TERM_TIMESTAMPS = 0, VI_TERM_ID_RANGE = 1, VI_TERM_IDS = 2, VI_TERM_IDS_DEVICE = 3,
+                            VI_TERM_MASK = 4, VI_TERM_MASK_DEVICE = 5, VI_TERM_FILTER = 6 } vi_term_kind;
+typedef enum vi_filter_join { VI_JOIN_AND = 0, VI_JOIN_OR = 1 } vi_filter_join;
+typedef struct vi_filter_term {
+  uint32_t kind;            /* vi_term_kind */
+  uint32_t negate;          /* 0 / 1 */
+  uint64_t lo, hi;          /* TIMESTAMPS, ID_RANGE: both inclusive */
+  const void *data;         /* IDS*: n u64 ids;  MASK*: n bytes, non-zero admits */
+  uint64_t n;
+  const vi_filter *filter;  /* FILTER */
+} vi_filter_term;
+vi_status vi_indexer_filter_compose(const vi_indexer *ix, vi_filter_join join, const vi_filter_term *terms,
+                                    uint32_t n_terms, vi_filter *reuse, vi_filter **out);
+vi_status vi_filter_union(const vi_indexer *ix, const vi_filter *a, const vi_filter *b, vi_filter **out);
+vi_status vi_filter_complement(const vi_indexer *ix, const vi_filter *a, vi_filter **out);
+vi_status vi_indexer_filter_id_range(const vi_indexer *ix, uint64_t id_min, uint64_t id_max, vi_filter **out);
+vi_status vi_indexer_filter_mask(const vi_indexer *ix, const uint8_t *mask, uint64_t n, vi_filter **out);
+vi_status vi_indexer_filter_mask_device(const vi_indexer *ix, const uint8_t *mask_dev, uint64_t n, vi_filter **out);
 
 /* ---- extension (the reference has no remove, api.rs:101-237): remove records from a built or loaded index ----
  * Afterwards the index is the one the reference would search if the removed records had been deleted from their inverted

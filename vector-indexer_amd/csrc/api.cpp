@@ -1016,6 +1016,90 @@ vi_status vi_filter_intersect(const vi_indexer *ix, const vi_filter *a, const vi
   });
 }
 
+// Every check of a composed filter that does not need the resident arrays (those are slot_filter_compose's, which still
+// come before any device work); then one launch.  With `reuse` the filter is written in place and *out = reuse.
+vi_status vi_indexer_filter_compose(const vi_indexer *ix, vi_filter_join join, const vi_filter_term *terms, uint32_t n_terms,
+                                    vi_filter *reuse, vi_filter **out) {
+  return vi::guarded([&]() -> vi_status {
+  if (!ix || !terms || !out) return fail(VI_ERR_INVALID_INPUT, "null pointer");
+  if ((int)join != VI_JOIN_AND && (int)join != VI_JOIN_OR)
+    return fail(VI_ERR_INVALID_INPUT, "filter join %d (VI_JOIN_AND = 0 or VI_JOIN_OR = 1)", (int)join);
+  if (n_terms < 1 || n_terms > VI_FILTER_MAX_TERMS)
+    return fail(VI_ERR_INVALID_INPUT, "%u terms (1 to %d)", n_terms, VI_FILTER_MAX_TERMS);
+  if (!ix->impl.dev) return fail(VI_ERR_INVALID_INPUT, "the indexer holds no index (build or load it first)");
+  const vi::SlotFilter *operands[VI_FILTER_MAX_TERMS] = {};
+  for (uint32_t i = 0; i < n_terms; ++i) {
+    const vi_filter_term &t = terms[i];
+    if (t.negate > 1) return fail(VI_ERR_INVALID_INPUT, "term %u: negate %u (0 or 1)", i, t.negate);
+    switch (t.kind) {
+      case VI_TERM_TIMESTAMPS:
+      case VI_TERM_ID_RANGE:
+        if (t.lo > t.hi) return fail(VI_ERR_INVALID_INPUT, "term %u: lo > hi", i);
+        break;
+      case VI_TERM_IDS:
+      case VI_TERM_IDS_DEVICE:
+      case VI_TERM_MASK:
+      case VI_TERM_MASK_DEVICE:
+        if (t.n && !t.data) return fail(VI_ERR_INVALID_INPUT, "term %u: null data with n = %llu", i, (unsigned long long)t.n);
+        break;
+      case VI_TERM_FILTER:
+        if (!t.filter) return fail(VI_ERR_INVALID_INPUT, "term %u: null filter", i);
+        VI_TRY(filter_common(ix, t.filter, &operands[i]));
+        if (t.filter == reuse)
+          return fail(VI_ERR_INVALID_INPUT, "term %u: the filter to overwrite is an operand of the expression", i);
+        break;
+      default:
+        return fail(VI_ERR_INVALID_INPUT, "term %u: kind %u (vi_term_kind: 0 to 6)", i, t.kind);
+    }
+  }
+  const vi::SlotFilter *checked = nullptr;
+  VI_TRY(filter_common(ix, reuse, &checked));
+  std::unique_ptr<vi_filter> fresh;
+  if (!reuse) fresh = std::make_unique<vi_filter>();
+  vi_filter *f = reuse ? reuse : fresh.get();
+  VI_TRY(vi::slot_filter_compose(*ix->impl.dev, (int)join == VI_JOIN_OR, terms, n_terms, operands, &f->impl));
+  fresh.release();
+  *out = f;
+  return VI_OK;
+  });
+}
+
+static vi_filter_term filter_term(const vi_filter *f, uint32_t negate) {
+  vi_filter_term t{};
+  t.kind = VI_TERM_FILTER; t.negate = negate; t.filter = f;
+  return t;
+}
+
+vi_status vi_filter_union(const vi_indexer *ix, const vi_filter *a, const vi_filter *b, vi_filter **out) {
+  const vi_filter_term t[2] = {filter_term(a, 0), filter_term(b, 0)};
+  return vi_indexer_filter_compose(ix, VI_JOIN_OR, t, 2, nullptr, out);
+}
+
+vi_status vi_filter_complement(const vi_indexer *ix, const vi_filter *a, vi_filter **out) {
+  const vi_filter_term t = filter_term(a, 1);
+  return vi_indexer_filter_compose(ix, VI_JOIN_AND, &t, 1, nullptr, out);
+}
+
+vi_status vi_indexer_filter_id_range(const vi_indexer *ix, uint64_t id_min, uint64_t id_max, vi_filter **out) {
+  vi_filter_term t{};
+  t.kind = VI_TERM_ID_RANGE; t.lo = id_min; t.hi = id_max;
+  return vi_indexer_filter_compose(ix, VI_JOIN_AND, &t, 1, nullptr, out);
+}
+
+static vi_status filter_mask_common(const vi_indexer *ix, const uint8_t *mask, uint64_t n, bool on_device, vi_filter **out) {
+  vi_filter_term t{};
+  t.kind = on_device ? VI_TERM_MASK_DEVICE : VI_TERM_MASK; t.data = mask; t.n = n;
+  return vi_indexer_filter_compose(ix, VI_JOIN_AND, &t, 1, nullptr, out);
+}
+
+vi_status vi_indexer_filter_mask(const vi_indexer *ix, const uint8_t *mask, uint64_t n, vi_filter **out) {
+  return filter_mask_common(ix, mask, n, false, out);
+}
+
+vi_status vi_indexer_filter_mask_device(const vi_indexer *ix, const uint8_t *mask_dev, uint64_t n, vi_filter **out) {
+  return filter_mask_common(ix, mask_dev, n, true, out);
+}
+
 uint64_t vi_filter_num_allowed(const vi_filter *f) { return f ? f->impl.num_allowed : 0; }
 
 void vi_filter_free(vi_filter *f) { delete f; }

@@ -54,15 +54,16 @@ VI_LAYOUT_HD inline uint32_t list_of_block(const uint32_t *first, uint32_t nlist
 struct ResidentLists { const uint32_t *first_block, *list_len; uint32_t nlists; };  // (a list not resident here: length 0)
 constexpr uint32_t kListSplit = 8;  // workgroups sharing the blocks of one list (long lists carry most of an index)
 inline dim3 slot_walk_grid(uint32_t nlists) { return dim3(nlists, kListSplit); }
-// One wave per 64-vector block, four waves per workgroup, lane = vector of the block: body(block, lane, resident) per wave
-// and block, `block` counted over the whole index, resident = the lane's position is below the list length.
+// One wave per 64-vector block, four waves per workgroup, lane = vector of the block: body(block, lane, resident, list,
+// b) per wave and block, `block` counted over the whole index, resident = the lane's position is below the list length,
+// b = the block's index within `list` (so the lane's position in its list is 64 b + lane; both are wave-uniform).
 template <class Body>
 __device__ __forceinline__ void for_each_resident_block(const ResidentLists &L, Body body) {
   const uint32_t l = blockIdx.x, lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
   if (l >= L.nlists) return;
   const uint32_t len = L.list_len[l], fb = L.first_block[l], nblk = (len + 63u) / 64u;
   for (uint32_t b = blockIdx.y * 4u + wave; b < nblk; b += gridDim.y * 4u)  // (wave-uniform)
-    body(fb + b, lane, b * 64u + lane < len);
+    body(fb + b, lane, b * 64u + lane < len, l, b);
 }
 #endif
 

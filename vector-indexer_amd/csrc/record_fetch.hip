@@ -32,7 +32,7 @@ struct MatchArgs {
 // The walk of list_layout.hpp, masked by the list length (a pad slot's id word is never read).  A requested id's slot leaves
 // the lowest slot number and one count on its entry; lists lie in list order, so that is the first record in list order.
 __global__ void __launch_bounds__(256) fetch_match_kernel(MatchArgs a) {
-  for_each_resident_block(a.lists, [&](uint32_t block, uint32_t lane, bool resident) {
+  for_each_resident_block(a.lists, [&](uint32_t block, uint32_t lane, bool resident, uint32_t, uint32_t) {
     if (!resident) return;
     const uint32_t slot = block * 64u + lane;
     const uint64_t e = id_table_find(a.t, a.ext_ids[slot]);
@@ -226,8 +226,13 @@ struct Staged {
   }
 };
 
-// the host copy of the layout and the prefix of the lengths, made by the first export of an index under a lock of its own
-vi_status ensure_layout(const DeviceIndex &ix, hipStream_t st) {
+bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+}  // namespace
+
+// the host copy of the layout and the prefix of the lengths, made by the first export (or mask filter) of an index under a
+// lock of its own
+vi_status ensure_fetch_layout(const DeviceIndex &ix, hipStream_t st) {
   FetchState &f = ix.fetch;
   std::lock_guard<std::mutex> lock(f.layout_mu);
   if (f.layout_ready) return VI_OK;
@@ -249,10 +254,6 @@ vi_status ensure_layout(const DeviceIndex &ix, hipStream_t st) {
   f.layout_ready = true;
   return VI_OK;
 }
-
-bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
-}  // namespace
 
 vi_status fetch_records_by_id(const DeviceIndex &ix, const uint64_t *ids, uint64_t n, bool on_device, uint32_t *count,
                               float *values, uint64_t *timestamps, uint64_t *where) {
@@ -339,7 +340,7 @@ vi_status export_records(const DeviceIndex &ix, uint64_t first, uint64_t count, 
   hipStream_t st = c.stream;
   const bool timing = ix.timing != 0;
   const uint32_t dim = ix.dim;
-  VI_TRY(ensure_layout(ix, st));
+  VI_TRY(ensure_fetch_layout(ix, st));
   const FetchState &f = ix.fetch;  // (the layout is immutable once ready)
   // the blocks of the first and the last record of the range: every block between them belongs to a list with records
   auto block_of = [&](uint64_t ord) {

@@ -21,4 +21,10 @@ vi_status fetch_records_by_id(const DeviceIndex &ix, const uint64_t *ids, uint64
 vi_status export_records(const DeviceIndex &ix, uint64_t first, uint64_t count, bool on_device, uint64_t *ext_ids,
                          float *values, uint64_t *timestamps, uint64_t *where);
 
+// Makes ix.fetch's layout (device_index.hpp: FetchState) if no call has yet: the host copies of first block and length
+// and the exclusive prefix of the lengths — the list-order ordinal of every list's first record — on the host and the
+// device.  Synchronises st on the first call of an index, does nothing afterwards.  The one prefix of an index: exports
+// and mask filters (slot_filter.hip) read ix.fetch.prefix.
+vi_status ensure_fetch_layout(const DeviceIndex &ix, hipStream_t st);
+
 }  // namespace vi

@@ -13,6 +13,8 @@ bindings/python/python/vector_indexer_py/__init__.py):
     VectorIndex.remove_ids(ids) / .retain(filter) -> int    extension: remove records from it (by id / all a filter excludes)
     VectorIndex.upsert(xb, ext_ids, timestamps=None) -> int extension: replace the records that carry ext_ids, in one rewrite
     VectorIndex.get(ids) / .export(first, count)            extension: read records back, by id / a range in list order
+    VectorIndex.filter_timestamps / _ids / _id_range / _mask / _compose(terms)   extension: filters for `filter=`; of two
+                                                            filters a & b, a | b, a - b and ~a are filters too
     merge_range_results(device, parts) -> RangeResult       extension: the radius results of the ranks of a partitioned
                                                             index merged on the device into the unpartitioned result
 
@@ -30,7 +32,7 @@ import numpy as np
 from . import _native
 from ._native import (ViError, lib, VI_ASSIGN_EXACT, VI_ASSIGN_REFERENCE, VI_ORDER_LANES, VI_ORDER_SCALAR)
 
-__all__ = ["build", "load", "suggest_nlist", "VectorIndex", "TimestampFilter", "IdFilter", "FilterIntersection", "AnyFilter", "RangeResult", "merge_range_results", "merge_range_results_device", "ViError", "kmeans_mini_batch", "kmeans_parallel",
+__all__ = ["build", "load", "suggest_nlist", "VectorIndex", "TimestampFilter", "IdFilter", "FilterIntersection", "ComposedFilter", "Term", "AnyFilter", "RangeResult", "merge_range_results", "merge_range_results_device", "ViError", "kmeans_mini_batch", "kmeans_parallel",
            "assign", "l2sq_pairs", "VI_ASSIGN_EXACT", "VI_ASSIGN_REFERENCE", "VI_ORDER_LANES", "VI_ORDER_SCALAR"]
 
 
@@ -39,9 +41,81 @@ def suggest_nlist(n: int) -> int:
     return int(lib().vi_calculate_num_clusters(int(n)))
 
 
+class Term:
+    """One term of VectorIndex.filter_compose: Term.timestamps(lo, hi), .id_range(lo, hi), .ids(ids), .ids_device(ptr, n),
+    .mask(a), .mask_device(ptr, n), .filter(f); `~term` is the term negated.  Ids are kept as a flat uint64 array, a mask
+    as a flat uint8 array (bool or uint8 in, non-zero admits); a term keeps what it points at alive."""
+
+    __slots__ = ("kind", "negate", "lo", "hi", "data", "ptr", "n", "flt")
+
+    def __init__(self, kind, negate=False, lo=0, hi=0, data=None, ptr=0, n=0, flt=None):
+        self.kind, self.negate, self.lo, self.hi = int(kind), bool(negate), int(lo), int(hi)
+        self.data, self.ptr, self.n, self.flt = data, int(ptr or 0), int(n), flt
+
+    def __invert__(self):
+        return Term(self.kind, not self.negate, self.lo, self.hi, self.data, self.ptr, self.n, self.flt)
+
+    @classmethod
+    def timestamps(cls, lo: int, hi: int):
+        return cls(_native.VI_TERM_TIMESTAMPS, lo=lo, hi=hi)
+
+    @classmethod
+    def id_range(cls, lo: int, hi: int):
+        return cls(_native.VI_TERM_ID_RANGE, lo=lo, hi=hi)
+
+    @classmethod
+    def ids(cls, ids):
+        a = _native.id_array(ids)
+        return cls(_native.VI_TERM_IDS, data=a, n=a.size)
+
+    @classmethod
+    def ids_device(cls, ids_ptr: int, n: int):
+        return cls(_native.VI_TERM_IDS_DEVICE, ptr=ids_ptr, n=n)
+
+    @classmethod
+    def mask(cls, mask):
+        a = _native.mask_array(mask)
+        return cls(_native.VI_TERM_MASK, data=a, n=a.size)
+
+    @classmethod
+    def mask_device(cls, mask_ptr: int, n: int):
+        return cls(_native.VI_TERM_MASK_DEVICE, ptr=mask_ptr, n=n)
+
+    @classmethod
+    def filter(cls, f):
+        if not isinstance(f, _Filter):
+            raise TypeError("Term.filter takes a filter of the index")
+        return cls(_native.VI_TERM_FILTER, flt=f)
+
+    def _native_term(self) -> "_native.FilterTerm":
+        t = _native.FilterTerm()
+        t.kind, t.negate, t.lo, t.hi, t.n = self.kind, int(self.negate), self.lo, self.hi, self.n
+        if self.data is not None:
+            t.data = self.data.ctypes.data if self.data.size else None
+        elif self.ptr:
+            t.data = self.ptr
+        if self.flt is not None:
+            t.filter = self.flt._h
+        return t
+
+
+def _compose(index, terms, any=False, reuse=None):
+    """vi_indexer_filter_compose over Term objects -> the native handle (reuse's own when reuse is given)"""
+    terms = list(terms)
+    if not all(isinstance(t, Term) for t in terms):
+        raise TypeError("filter_compose takes Term objects")
+    arr = (_native.FilterTerm * max(len(terms), 1))(*[t._native_term() for t in terms])
+    h = C.c_void_p()
+    _native.check(lib().vi_indexer_filter_compose(index._h, _native.VI_JOIN_OR if any else _native.VI_JOIN_AND, arr, len(terms),
+                                                  reuse._h if reuse is not None else None, C.byref(h)))
+    return h
+
+
 class _Filter:
-    """A subset of the resident vectors of one VectorIndex.  Immutable; pass it as `filter=` to that index's searches.
-    Keeps its index alive and frees itself.  `a & b` of two filters of one index: the vectors both admit."""
+    """A subset of the resident vectors of one VectorIndex.  Immutable (but for VectorIndex.filter_compose(reuse=));
+    pass it as `filter=` to that index's searches.  Keeps its index alive and frees itself.  Of two filters of one index:
+    `a & b` the vectors both admit, `a | b` those either admits, `a - b` those a admits and b does not; `~a` the resident
+    vectors a does not admit.  Each is a filter of its own, made by one call."""
 
     def __init__(self, index, handle):
         self._index = index  # (the native filter must be freed before its indexer)
@@ -66,6 +140,23 @@ class _Filter:
         h = C.c_void_p()
         _native.check(lib().vi_filter_intersect(self._index._h, self._h, other._h, C.byref(h)))
         return FilterIntersection(self._index, h, (self, other))
+
+    def __or__(self, other):
+        if not isinstance(other, _Filter):
+            return NotImplemented
+        h = C.c_void_p()
+        _native.check(lib().vi_filter_union(self._index._h, self._h, other._h, C.byref(h)))
+        return ComposedFilter(self._index, h, (self, other))
+
+    def __sub__(self, other):
+        if not isinstance(other, _Filter):
+            return NotImplemented
+        return ComposedFilter(self._index, _compose(self._index, [Term.filter(self), ~Term.filter(other)]), (self, other))
+
+    def __invert__(self):
+        h = C.c_void_p()
+        _native.check(lib().vi_filter_complement(self._index._h, self._h, C.byref(h)))
+        return ComposedFilter(self._index, h, (self,))
 
 
 class TimestampFilter(_Filter):
@@ -93,7 +184,16 @@ class FilterIntersection(_Filter):
         self._indexes = tuple(o._index for o in operands)
 
 
-AnyFilter = Union[TimestampFilter, IdFilter, FilterIntersection]
+class ComposedFilter(_Filter):
+    """A union, a complement, a difference, an id range, a mask or a whole expression (VectorIndex.filter_compose): a filter
+    of its own (operands, id sets and masks may go away); keeps the index of its operands alive."""
+
+    def __init__(self, index, handle, operands=()):
+        super().__init__(index, handle)
+        self._indexes = tuple(o._index for o in operands)
+
+
+AnyFilter = Union[TimestampFilter, IdFilter, FilterIntersection, ComposedFilter]
 
 
 class RangeResult:
@@ -232,6 +332,40 @@ class VectorIndex:
                                                          _native.VI_IDS_DENY if exclude else _native.VI_IDS_ALLOW,
                                                          C.byref(h)))
         return IdFilter(self, h, n, exclude)
+
+    def filter_id_range(self, lo: int, hi: int) -> ComposedFilter:
+        """extension: the records whose external id lies in [lo, hi], both inclusive (Faiss's IDSelectorRange)"""
+        h = C.c_void_p()
+        _native.check(lib().vi_indexer_filter_id_range(self._h, int(lo), int(hi), C.byref(h)))
+        return ComposedFilter(self, h)
+
+    def filter_mask(self, mask) -> ComposedFilter:
+        """extension: the records whose entry of `mask` is non-zero: a bool or uint8 array of num_vectors entries in LIST
+        ORDER — entry i belongs to the record export() returns as row i, so an attribute kept beside an export filters
+        directly.  On a rank of a partitioned index: the rank's own list order (a mask is per rank)."""
+        a = _native.mask_array(mask)
+        h = C.c_void_p()
+        _native.check(lib().vi_indexer_filter_mask(self._h, _native.ptr(a) if a.size else None, a.size, C.byref(h)))
+        return ComposedFilter(self, h)
+
+    def filter_mask_device(self, mask_ptr: int, n: int) -> ComposedFilter:
+        """... for n mask bytes in device memory, read in place"""
+        h = C.c_void_p()
+        _native.check(lib().vi_indexer_filter_mask_device(self._h, C.c_void_p(mask_ptr) if mask_ptr else None, int(n),
+                                                          C.byref(h)))
+        return ComposedFilter(self, h)
+
+    def filter_compose(self, terms, any: bool = False, reuse: Optional[AnyFilter] = None) -> AnyFilter:
+        """extension: ONE filter from the AND (any=False) or the OR (any=True) of 1 to 8 Term objects, `~term` negated, in
+        one launch: Term.timestamps / .id_range / .ids / .ids_device / .mask / .mask_device / .filter (which nests).
+        reuse=f: f, a filter of this index that is no operand of the expression, is overwritten in place and returned —
+        nothing is allocated for it, and f.num_allowed reflects the new content; no search may be using f meanwhile."""
+        terms = list(terms)
+        h = _compose(self, terms, any, reuse)
+        operands = tuple(t.flt for t in terms if isinstance(t, Term) and t.flt is not None)
+        if reuse is not None:
+            return reuse   # (its handle is h; the operands are filters of reuse's own index)
+        return ComposedFilter(self, h, operands)
 
     def search_sync(self, xq, k: int, n_probe: int, include_vectors: bool = False, filter: Optional[AnyFilter] = None):
         xq = np.asarray(xq)

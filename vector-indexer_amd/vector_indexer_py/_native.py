@@ -7,6 +7,9 @@ VI_OK, VI_ERR_INVALID_INPUT, VI_ERR_NOT_FOUND, VI_ERR_INVALID_DATA, VI_ERR_OTHER
 VI_ORDER_SCALAR, VI_ORDER_LANES = 0, 1
 VI_ASSIGN_REFERENCE, VI_ASSIGN_EXACT = 0, 1
 VI_IDS_ALLOW, VI_IDS_DENY = 0, 1
+VI_FILTER_MAX_TERMS = 8
+VI_TERM_TIMESTAMPS, VI_TERM_ID_RANGE, VI_TERM_IDS, VI_TERM_IDS_DEVICE, VI_TERM_MASK, VI_TERM_MASK_DEVICE, VI_TERM_FILTER = range(7)
+VI_JOIN_AND, VI_JOIN_OR = 0, 1
 
 _STATUS_NAME = {1: "InvalidInput", 2: "NotFound", 3: "InvalidData", 4: "Other", 5: "Io", 6: "Panic", 7: "Device"}
 
@@ -69,6 +72,11 @@ class FetchStats(C.Structure):
                 ("ms_table", f32), ("ms_match", f32), ("ms_gather", f32)]
 
 
+class FilterTerm(C.Structure):
+    """vi_filter_term: one term of vi_indexer_filter_compose"""
+    _fields_ = [("kind", u32), ("negate", u32), ("lo", u64), ("hi", u64), ("data", vp), ("n", u64), ("filter", vp)]
+
+
 WHERE_NONE = (1 << 64) - 1   # VI_WHERE_NONE
 
 
@@ -124,6 +132,12 @@ SIGNATURES = {
     "vi_indexer_filter_ids": (C.c_int, [vp, vp, u64, C.c_int, C.POINTER(vp)]),
     "vi_indexer_filter_ids_device": (C.c_int, [vp, vp, u64, C.c_int, C.POINTER(vp)]),
     "vi_filter_intersect": (C.c_int, [vp, vp, vp, C.POINTER(vp)]),
+    "vi_indexer_filter_compose": (C.c_int, [vp, C.c_int, C.POINTER(FilterTerm), u32, vp, C.POINTER(vp)]),
+    "vi_filter_union": (C.c_int, [vp, vp, vp, C.POINTER(vp)]),
+    "vi_filter_complement": (C.c_int, [vp, vp, C.POINTER(vp)]),
+    "vi_indexer_filter_id_range": (C.c_int, [vp, u64, u64, C.POINTER(vp)]),
+    "vi_indexer_filter_mask": (C.c_int, [vp, vp, u64, C.POINTER(vp)]),
+    "vi_indexer_filter_mask_device": (C.c_int, [vp, vp, u64, C.POINTER(vp)]),
     "vi_filter_num_allowed": (u64, [vp]),
     "vi_filter_free": (None, [vp]),
     "vi_indexer_search_filtered": (C.c_int, [vp, vp, vp, u64, u32, u64, u64, vp, vp, vp, vp, C.POINTER(u64)]),
@@ -203,6 +217,15 @@ def id_array(ids):
     if ids.dtype.kind == "i" and (ids < 0).any():
         raise ValueError("ids must be non-negative (external ids are u64)")
     return np.ascontiguousarray(ids.reshape(-1), dtype=np.uint64)
+
+
+def mask_array(mask):
+    """a bool or uint8 array-like with one entry per record -> flat contiguous uint8 (non-zero admits)"""
+    import numpy as np
+    a = np.asarray(mask)
+    if a.dtype != np.bool_ and a.dtype != np.uint8:
+        raise TypeError("a mask is a bool or uint8 array")
+    return np.ascontiguousarray(a.reshape(-1)).view(np.uint8)
 
 
 def check(status, prefix=""):

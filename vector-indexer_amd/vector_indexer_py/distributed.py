@@ -9,7 +9,8 @@ protocol tests) and merged on (dist, tie), which reproduces the single-GPU stabl
 A radius search returns ragged rows, so its exchange is two all-gathers: every rank's lims (nq + 1 u64: fixed size, and
 they tell every rank every total), then one byte buffer per rank padded to the largest total (range_part_layout).  The
 merge by the same key runs on the device, parallel over entries (vi_range_merge_device).  A filter belongs to one handle:
-every rank makes its own from the same predicate and passes it as `filter=`.
+every rank makes its own from the same predicate and passes it as `filter=`.  A mask (VectorIndex.filter_mask, Term.mask)
+is per rank: its bytes follow the rank's own list order, so every rank builds it from its own export().
 
 The reference has no distributed mode (its "two-level sharding" only groups files,
 src/ivf_index.rs:104-164); this is the MI355X-native extension BASELINE.json's north_star asks for.

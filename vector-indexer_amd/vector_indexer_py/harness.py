@@ -138,26 +138,29 @@ class FaissStyleAdapter:
     def nprobe(self, value: int):
         self._nprobe = int(value)
 
-    def _id_filter(self, allowed_ids, excluded_ids):
-        """what Faiss passes as SearchParameters(sel=IDSelectorBatch / IDSelectorNot); None when neither is given"""
-        if allowed_ids is not None and excluded_ids is not None:
-            raise ValueError("give allowed_ids or excluded_ids, not both")
+    def _id_filter(self, allowed_ids, excluded_ids, filter=None):
+        """what Faiss passes as SearchParameters(sel=IDSelectorBatch / IDSelectorNot), or sel= any selector as `filter`, a
+        filter of the wrapped index (ranges, masks, unions, ...); None when none is given"""
+        if sum(x is not None for x in (allowed_ids, excluded_ids, filter)) > 1:
+            raise ValueError("give one of allowed_ids, excluded_ids and filter, not several")
+        if filter is not None:
+            return filter
         if allowed_ids is not None:
             return self._idx.filter_ids(allowed_ids)
         if excluded_ids is not None:
             return self._idx.filter_ids(excluded_ids, exclude=True)
         return None
 
-    def search(self, xq: np.ndarray, k: int, allowed_ids=None, excluded_ids=None):
-        flt = self._id_filter(allowed_ids, excluded_ids)
+    def search(self, xq: np.ndarray, k: int, allowed_ids=None, excluded_ids=None, filter=None):
+        flt = self._id_filter(allowed_ids, excluded_ids, filter)
         if flt is None:
             return self._idx.search_sync(np.ascontiguousarray(xq, dtype=np.float32), k, self._nprobe)
         return self._idx.search_sync(np.ascontiguousarray(xq, dtype=np.float32), k, self._nprobe, filter=flt)
 
-    def range_search(self, x: np.ndarray, thresh: float, allowed_ids=None, excluded_ids=None):
+    def range_search(self, x: np.ndarray, thresh: float, allowed_ids=None, excluded_ids=None, filter=None):
         """Faiss's Index.range_search: (lims, D, I) — query i owns D / I[lims[i]:lims[i + 1]], squared L2 <= thresh, among
         the nprobe probed lists"""
-        flt = self._id_filter(allowed_ids, excluded_ids)
+        flt = self._id_filter(allowed_ids, excluded_ids, filter)
         if flt is None:
             return self._idx.range_search_sync(np.ascontiguousarray(x, dtype=np.float32), float(thresh), self._nprobe)
         return self._idx.range_search_sync(np.ascontiguousarray(x, dtype=np.float32), float(thresh), self._nprobe, filter=flt)
