@@ -559,6 +559,46 @@ vi_status vi_indexer_export_records(const vi_indexer *ix, uint64_t first, uint64
 vi_status vi_indexer_export_records_device(const vi_indexer *ix, uint64_t first, uint64_t count, uint64_t *ext_ids_dev,
                                            float *values_dev, uint64_t *timestamps_dev, uint64_t *where_dev);
 
+/* ---- extension: search by stored record ("what is similar to the record I already hold?") --------------------------
+ * The query of a row is the stored f32 bits of a resident record r; the row is the reference's candidate sequence for
+ * that query (probed lists in shard visiting order, probe rank, list position), less what the filter does not admit,
+ * less — with exclude_self != 0 — the ONE candidate that is r itself (the same list and position: a record with the
+ * same external id, or with the same bits under another id, stays), stably sorted, take(k).  Coarse step, distances,
+ * tie keys, padding (+inf / -1 / tie UINT64_MAX / zero vectors) and counts are exactly those of
+ * vi_indexer_search_filtered* with a deny of that one slot; exclude_self == 0 gives bit for bit what vi_indexer_search*
+ * returns for the stored bits as the query.  If r's own list is not among the probed ones nothing is deleted.
+ *   by ids:    an id names the first record in list order that carries it (the record vi_indexer_get_records returns);
+ *              found[i] = resident records carrying it (the get's count_out).  An absent id is no error: its row is all
+ *              padding, counts[i] = 0, found[i] = 0.  Ids may repeat, in any order; any u64 is an id.
+ *   knn_graph: rows = records [first, first + count) of LIST ORDER (row j is the record vi_indexer_export_records returns
+ *              as row j); first + count > vi_indexer_num_vectors is VI_ERR_INVALID_INPUT.  The range is processed in
+ *              chunks of VI_GRAPH_CHUNK rows (environment, default 65536) through one search context.
+ * k and n_probe are clamped to max_k / max_n_probe first; the row stride is the clamped k (*k_out).  The one extra
+ * candidate exclusion needs internally is not subject to max_k.  COST: an excluding call searches k + 1 wide, so k = 64
+ * (VALU engine) and k = 128 (MFMA engine) fall to the engine that sorts every candidate; results are the same bits.
+ * f == NULL: no filter; a row exists for every named record whether or not the filter admits that record.  D / I /
+ * tie / found of the *_device entries are device pointers; tie and found may be NULL, as V, counts, found, k_out of the
+ * host entries.  nq == 0 / count == 0: VI_OK, nothing touched.  Partitioned handles (world_size > 1) are
+ * VI_ERR_INVALID_INPUT.  Threads: the contract of a search.  vi_indexer_last_stats afterwards reads as after the
+ * underlying search (of the last chunk), k as the caller's clamped k. */
+/* queries named by external id */
+vi_status vi_indexer_search_by_ids(const vi_indexer *ix, const vi_filter *f, const uint64_t *ext_ids, uint64_t nq,
+                                   uint64_t k, uint64_t n_probe, uint32_t exclude_self, float *D, int64_t *I, float *V,
+                                   uint64_t *counts, uint32_t *found, uint64_t *k_out);
+vi_status vi_indexer_search_by_ids_device(const vi_indexer *ix, const vi_filter *f, const uint64_t *ext_ids_dev, uint64_t nq,
+                                          uint64_t k, uint64_t n_probe, uint32_t exclude_self, float *D_dev, int64_t *I_dev,
+                                          uint64_t *tie_dev, uint32_t *found_dev);
+/* rows = records [first, first + count) of LIST ORDER (row j is the record vi_indexer_export_records returns as row j) */
+vi_status vi_indexer_knn_graph(const vi_indexer *ix, const vi_filter *f, uint64_t first, uint64_t count, uint64_t k,
+                               uint64_t n_probe, uint32_t exclude_self, float *D, int64_t *I, uint64_t *counts, uint64_t *k_out);
+vi_status vi_indexer_knn_graph_device(const vi_indexer *ix, const vi_filter *f, uint64_t first, uint64_t count, uint64_t k,
+                                      uint64_t n_probe, uint32_t exclude_self, float *D_dev, int64_t *I_dev, uint64_t *tie_dev);
+/* Of the calling thread's last of the four, summed over its chunks, taken only while the environment variable
+ * VI_SIMILAR_TIMING is set (and not "0"); zeros otherwise.  ms_resolve / ms_search: host clock around the gather of the
+ * queries and around the search; ms_drop: HIP events around self_drop_kernel.  Reported with or without the variable:
+ * drop_bytes, the bytes that kernel moved, and chunk_rows, the rows per chunk used.  Any pointer may be NULL. */
+vi_status vi_similar_last_times(float *ms_resolve, float *ms_search, float *ms_drop, uint64_t *drop_bytes, uint64_t *chunk_rows);
+
 /* ---- extension: radius (range) search -----------------------------------------------------------------------------
  * Every candidate of the probed lists whose squared distance is at most radius2.  The result of a query is the
  * reference's candidate sequence (probed lists in shard visiting order, then probe rank, then list position) after the

@@ -967,6 +967,93 @@ vi_status vi_indexer_search_probed_device(const vi_indexer *ix, const float *que
                                                   I_dev, tie_dev);
 }
 
+// ---- search by stored record (similar_search.hip) ----
+// The checks common to the four entries, all before any device work; on VI_OK *k and *n_probe are clamped and *flt is set.
+static vi_status similar_common(const vi_indexer *ix, const vi_filter *f, uint64_t nq, bool null_ids, bool null_rows, uint64_t *k,
+                                uint64_t *n_probe, const vi::SlotFilter **flt) {
+  VI_TRY(search_common(ix, k, n_probe));
+  if (*k == 0 || *n_probe == 0) return fail(VI_ERR_INVALID_INPUT, "k and n_probe must be greater than 0");
+  if (nq > (1ull << 40)) return fail(VI_ERR_INVALID_INPUT, "%llu rows are too many for one call", (unsigned long long)nq);
+  if (nq && null_ids) return fail(VI_ERR_INVALID_INPUT, "null id array with nq = %llu", (unsigned long long)nq);
+  if (nq && null_rows) return fail(VI_ERR_INVALID_INPUT, "null pointer: D and I are required");
+  if (!ix->impl.dev) return fail(VI_ERR_INVALID_INPUT, "the indexer holds no index (build or load it first)");
+  if (ix->impl.cfg.world_size > 1 || ix->impl.dev->stripe_world > 1)
+    return fail(VI_ERR_INVALID_INPUT,
+                "search by stored record needs the whole index on one handle; on a partitioned handle call "
+                "vi_indexer_get_records_device on every rank, take the record with the lowest `where`, and search its vector "
+                "with vi_indexer_probe_device / vi_indexer_search_probed_device (the record itself is then not excluded)");
+  return filter_common(ix, f, flt);
+}
+
+static vi_status search_by_ids_common(const vi_indexer *ix, const vi_filter *f, const uint64_t *ids, uint64_t nq, uint64_t k,
+                                      uint64_t n_probe, uint32_t exclude_self, bool on_device, float *D, int64_t *I, uint64_t *tie,
+                                      float *V, uint64_t *counts, uint32_t *found, uint64_t *k_out) {
+  return vi::guarded([&]() -> vi_status {
+  const vi::SlotFilter *flt = nullptr;
+  VI_TRY(similar_common(ix, f, nq, !ids, !D || !I, &k, &n_probe, &flt));
+  if (nq == 0) return VI_OK;  // nothing is read or written
+  if (k_out) *k_out = k;
+  vi::SimilarIO io;
+  io.ids = ids; io.on_device = on_device; io.nq = nq; io.k = k; io.n_probe = n_probe; io.exclude_self = exclude_self != 0;
+  io.filter = flt; io.D = D; io.I = I; io.tie = tie; io.V = V; io.counts = counts; io.found = found;
+  return vi::device_index_search_similar(*ix->impl.dev, io);
+  });
+}
+
+vi_status vi_indexer_search_by_ids(const vi_indexer *ix, const vi_filter *f, const uint64_t *ext_ids, uint64_t nq,
+                                   uint64_t k, uint64_t n_probe, uint32_t exclude_self, float *D, int64_t *I, float *V,
+                                   uint64_t *counts, uint32_t *found, uint64_t *k_out) {
+  return search_by_ids_common(ix, f, ext_ids, nq, k, n_probe, exclude_self, false, D, I, nullptr, V, counts, found, k_out);
+}
+
+vi_status vi_indexer_search_by_ids_device(const vi_indexer *ix, const vi_filter *f, const uint64_t *ext_ids_dev, uint64_t nq,
+                                          uint64_t k, uint64_t n_probe, uint32_t exclude_self, float *D_dev, int64_t *I_dev,
+                                          uint64_t *tie_dev, uint32_t *found_dev) {
+  return search_by_ids_common(ix, f, ext_ids_dev, nq, k, n_probe, exclude_self, true, D_dev, I_dev, tie_dev, nullptr, nullptr,
+                              found_dev, nullptr);
+}
+
+static vi_status knn_graph_common(const vi_indexer *ix, const vi_filter *f, uint64_t first, uint64_t count, uint64_t k,
+                                  uint64_t n_probe, uint32_t exclude_self, bool on_device, float *D, int64_t *I, uint64_t *tie,
+                                  uint64_t *counts, uint64_t *k_out) {
+  return vi::guarded([&]() -> vi_status {
+  const vi::SlotFilter *flt = nullptr;
+  VI_TRY(similar_common(ix, f, count, false, !D || !I, &k, &n_probe, &flt));
+  const uint64_t nvec = ix->impl.dev->nvec_resident;
+  if (first > nvec || count > nvec - first)
+    return fail(VI_ERR_INVALID_INPUT, "records [%llu, %llu + %llu) of %llu resident records", (unsigned long long)first,
+                (unsigned long long)first, (unsigned long long)count, (unsigned long long)nvec);
+  if (count == 0) return VI_OK;  // nothing is read or written
+  if (k_out) *k_out = k;
+  vi::SimilarIO io;
+  io.first = first; io.on_device = on_device; io.nq = count; io.k = k; io.n_probe = n_probe; io.exclude_self = exclude_self != 0;
+  io.filter = flt; io.D = D; io.I = I; io.tie = tie; io.counts = counts;
+  return vi::device_index_search_similar(*ix->impl.dev, io);
+  });
+}
+
+vi_status vi_indexer_knn_graph(const vi_indexer *ix, const vi_filter *f, uint64_t first, uint64_t count, uint64_t k,
+                               uint64_t n_probe, uint32_t exclude_self, float *D, int64_t *I, uint64_t *counts, uint64_t *k_out) {
+  return knn_graph_common(ix, f, first, count, k, n_probe, exclude_self, false, D, I, nullptr, counts, k_out);
+}
+
+vi_status vi_indexer_knn_graph_device(const vi_indexer *ix, const vi_filter *f, uint64_t first, uint64_t count, uint64_t k,
+                                      uint64_t n_probe, uint32_t exclude_self, float *D_dev, int64_t *I_dev, uint64_t *tie_dev) {
+  return knn_graph_common(ix, f, first, count, k, n_probe, exclude_self, true, D_dev, I_dev, tie_dev, nullptr, nullptr);
+}
+
+vi_status vi_similar_last_times(float *ms_resolve, float *ms_search, float *ms_drop, uint64_t *drop_bytes, uint64_t *chunk_rows) {
+  return vi::guarded([&]() -> vi_status {
+  const vi::SimilarTimes t = vi::similar_last_times();
+  if (ms_resolve) *ms_resolve = t.ms_resolve;
+  if (ms_search) *ms_search = t.ms_search;
+  if (ms_drop) *ms_drop = t.ms_drop;
+  if (drop_bytes) *drop_bytes = t.drop_bytes;
+  if (chunk_rows) *chunk_rows = t.chunk_rows;
+  return VI_OK;
+  });
+}
+
 vi_status vi_indexer_filter_timestamps(const vi_indexer *ix, uint64_t ts_min, uint64_t ts_max, vi_filter **out) {
   return vi::guarded([&]() -> vi_status {
   if (!ix || !out) return fail(VI_ERR_INVALID_INPUT, "null pointer");

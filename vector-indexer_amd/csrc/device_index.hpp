@@ -89,6 +89,12 @@ struct SearchWorkspace {
   DevBuf<uint64_t> total_allowed;           // generic engine with a filter: candidates per query that received a key
   DevBuf<uint32_t> gprobe, off_by_g, off_by_rank;
   DevBuf<uint32_t> range_bound;             // radius search: per query an upper bound of its hits (+ one flag word)
+  // search by stored record (similar_search.hip), per chunk of rows: the slot of each row's record and the number of
+  // records carrying its id; the k-wide rows of a host caller (its k + 1-wide search rows are D / I / tie / slots above)
+  DevBuf<uint32_t> self_slot, self_found;
+  DevBuf<float> sim_D;
+  DevBuf<int64_t> sim_I;
+  DevBuf<uint64_t> sim_slots;
 };
 
 // ---- reading records back (record_fetch.hip) ----
@@ -236,6 +242,7 @@ struct SearchIO {
   float *D = nullptr;
   int64_t *I = nullptr;
   uint64_t *tie = nullptr;
+  uint64_t *slots = nullptr;       // device only, optional: the global slot of every result (~0 on padding)
   float *V = nullptr;              // host only
   uint64_t *counts = nullptr;      // host only
   // multi-GPU: the coarse step of a query slice can run on another rank (device pointers, [nq][n_probe_eff])
@@ -244,6 +251,32 @@ struct SearchIO {
   const SlotFilter *filter = nullptr;  // restrict the candidates to the filter's slots (the coarse step never sees it)
 };
 vi_status device_index_search(const DeviceIndex &ix, const SearchIO &io);
+
+// ---- search by stored record (similar_search.hip): the rows' queries are records of the index itself ----
+// Row i is the top-k of the stored f32 bits of a record: by id — the first record in list order carrying ids[i], the
+// one a get reports — or by range — record first + i of list order.  exclude_self deletes that one record (its slot, not
+// its id, not its bits) from the row's candidates.  The contract is vi_indexer_search_by_ids / vi_indexer_knn_graph in
+// include/vi_amd.h; arguments are checked by the caller (api.cpp): nq > 0, k > 0, n_probe > 0, an unpartitioned index.
+struct SimilarIO {
+  const uint64_t *ids = nullptr;   // by id: nq ids (host, or device with on_device); null: by range
+  uint64_t first = 0;              // by range: rows are records [first, first + nq) of list order
+  bool on_device = false;          // ids and every output are device pointers
+  uint64_t nq = 0, k = 0, n_probe = 0;
+  bool exclude_self = true;
+  const SlotFilter *filter = nullptr;
+  float *D = nullptr;              // nq x k
+  int64_t *I = nullptr;
+  uint64_t *tie = nullptr;         // device only, optional
+  float *V = nullptr;              // host only, optional: nq x k x dim
+  uint64_t *counts = nullptr;      // host only, optional
+  uint32_t *found = nullptr;       // by id, optional: records carrying each id
+};
+vi_status device_index_search_similar(const DeviceIndex &ix, const SimilarIO &io);
+// this thread's last device_index_search_similar under VI_SIMILAR_TIMING (set, not '0'), summed over its chunks: host
+// clock around the resolve + gather of the queries and around the search, HIP events around self_drop_kernel; the bytes
+// that kernel moved and the rows per chunk used.  Zeros otherwise.
+struct SimilarTimes { float ms_resolve = 0, ms_search = 0, ms_drop = 0; uint64_t drop_bytes = 0, chunk_rows = 0; };
+SimilarTimes similar_last_times();
 
 // Result of a radius search (device_index_range_search): CSR like Faiss's RangeSearchResult — query q owns entries
 // [lims[q], lims[q + 1]) of D / I / tie / slots, sorted as the reference's stable candidate sort leaves them.  Owns its

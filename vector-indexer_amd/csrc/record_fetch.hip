@@ -57,6 +57,7 @@ struct ResolveArgs {
   uint32_t *out_count;         // any of the four may be null
   float *out_values;
   uint64_t *out_ts, *out_where;
+  uint32_t *out_slot;          // internal (resolve_records_by_id): the slot `where` names, kNoSlot for an absent id; or null
   unsigned long long *found;   // requests that found a record
   bool vec_store;              // dim % 4 == 0 and out_values 16-byte aligned
 };
@@ -72,6 +73,7 @@ __device__ __forceinline__ uint32_t resolve_row(const ResolveArgs &a, uint64_t i
 __device__ __forceinline__ void write_row_scalars(const ResolveArgs &a, uint64_t i, uint32_t cnt, uint32_t slot) {
   if (a.out_count) a.out_count[i] = cnt;
   if (a.out_ts) a.out_ts[i] = cnt && a.timestamps ? a.timestamps[slot] : 0ull;
+  if (a.out_slot) a.out_slot[i] = slot;
   if (a.out_where) {
     uint64_t w = kWhereNone;
     if (cnt) {
@@ -151,6 +153,7 @@ struct ExportArgs {
   uint64_t *out_ids;       // any of the four may be null
   float *out_values;
   uint64_t *out_ts, *out_where;
+  uint32_t *out_slot;      // internal (resolve_records_by_range): the slot of every row; or null
 };
 
 // One wave (one workgroup) per resident block that intersects [first, first + count).  The wave finds its list and the
@@ -174,6 +177,7 @@ __global__ void __launch_bounds__(64) export_blocks_kernel(ExportArgs a) {
   if (valid) {
     const uint64_t slot = (uint64_t)b * 64u + lane, j = (uint64_t)(j0 + lane);
     if (a.out_ids) a.out_ids[j] = a.ext_ids[slot];
+    if (a.out_slot) a.out_slot[j] = (uint32_t)slot;
     if (a.out_ts) a.out_ts[j] = a.timestamps ? a.timestamps[slot] : 0ull;
     if (a.out_where) a.out_where[j] = ((uint64_t)l << 32) | full_position((uint64_t)p0 + lane, a.world, a.rank);
   }
@@ -255,13 +259,17 @@ vi_status ensure_fetch_layout(const DeviceIndex &ix, hipStream_t st) {
   return VI_OK;
 }
 
-vi_status fetch_records_by_id(const DeviceIndex &ix, const uint64_t *ids, uint64_t n, bool on_device, uint32_t *count,
-                              float *values, uint64_t *timestamps, uint64_t *where) {
+namespace {
+
+// A get.  ids_on_device / on_device: where the ids and where the four public outputs are.  slot_dev (device, or null) and
+// publish == false are the internal form: the slot of every request, and the handle's fetch stats left as they are.
+vi_status fetch_by_id(const DeviceIndex &ix, const uint64_t *ids, uint64_t n, bool ids_on_device, bool on_device, uint32_t *count,
+                      float *values, uint64_t *timestamps, uint64_t *where, uint32_t *slot_dev, bool publish) {
   if (!ix.ext_ids.p) return fail(VI_ERR_INVALID_INPUT, "this index keeps no external ids");
   VI_HIP(hipSetDevice(ix.device));
   vi_fetch_stats s{};
   bool done = false;  // the call succeeded: its stats become the handle's
-  ContextLease lease(ix.fetch.pool, make_context<FetchContext>, [&] { if (done) ix.fetch.last = s; });
+  ContextLease lease(ix.fetch.pool, make_context<FetchContext>, [&] { if (done && publish) ix.fetch.last = s; });
   if (!lease.ctx) return VI_ERR_DEVICE;  // (the message is make_context's)
   FetchContext &c = *lease.ctx;
   hipStream_t st = c.stream;
@@ -277,8 +285,8 @@ vi_status fetch_records_by_id(const DeviceIndex &ix, const uint64_t *ids, uint64
   VI_TRY(out.stage(where, c.out_where, n));
   // ---- the table of the requested ids (two more flag words: `found`), timed from behind the upload of host ids ----
   IdTable t;
-  VI_TRY(id_set_build(c.ids, ids, n, on_device, 2, st, &t, timing ? c.ev[0] : nullptr));
-  if (!on_device) ids = c.ids.upload.p;
+  VI_TRY(id_set_build(c.ids, ids, n, ids_on_device, 2, st, &t, timing ? c.ev[0] : nullptr));
+  if (!ids_on_device) ids = c.ids.upload.p;
   VI_HIP(hipMemsetAsync(c.first_slot.p, 0xff, (capacity + 1) * sizeof(uint32_t), st));  // kNoSlot
   VI_HIP(hipMemsetAsync(c.count.p, 0, (capacity + 1) * sizeof(uint32_t), st));
   if (timing) VI_HIP(hipEventRecord(c.ev[1], st));
@@ -295,7 +303,7 @@ vi_status fetch_records_by_id(const DeviceIndex &ix, const uint64_t *ids, uint64
   r.blocks = reinterpret_cast<const float4 *>(ix.lists.blocks.p); r.dq = ix.dq; r.dim = dim;
   r.first_block = ix.list_first_block.p; r.nlists = (uint32_t)ix.nlists; r.timestamps = ix.timestamps.p;
   r.world = ix.stripe_world; r.rank = ix.stripe_rank;
-  r.out_count = count; r.out_values = values; r.out_ts = timestamps; r.out_where = where;
+  r.out_count = count; r.out_values = values; r.out_ts = timestamps; r.out_where = where; r.out_slot = slot_dev;
   r.found = reinterpret_cast<unsigned long long *>(c.ids.flags.p + 2);
   r.vec_store = dim % 4 == 0 && aligned16(values);
   if (values) {
@@ -328,13 +336,14 @@ vi_status fetch_records_by_id(const DeviceIndex &ix, const uint64_t *ids, uint64
   return VI_OK;
 }
 
-vi_status export_records(const DeviceIndex &ix, uint64_t first, uint64_t count, bool on_device, uint64_t *ext_ids,
-                         float *values, uint64_t *timestamps, uint64_t *where) {
+// An export; slot_dev and publish as in fetch_by_id.
+vi_status export_range(const DeviceIndex &ix, uint64_t first, uint64_t count, bool on_device, uint64_t *ext_ids, float *values,
+                       uint64_t *timestamps, uint64_t *where, uint32_t *slot_dev, bool publish) {
   if (!ix.ext_ids.p) return fail(VI_ERR_INVALID_INPUT, "this index keeps no external ids");
   VI_HIP(hipSetDevice(ix.device));
   vi_fetch_stats s{};
   bool done = false;  // the call succeeded: its stats become the handle's
-  ContextLease lease(ix.fetch.pool, make_context<FetchContext>, [&] { if (done) ix.fetch.last = s; });
+  ContextLease lease(ix.fetch.pool, make_context<FetchContext>, [&] { if (done && publish) ix.fetch.last = s; });
   if (!lease.ctx) return VI_ERR_DEVICE;  // (the message is make_context's)
   FetchContext &c = *lease.ctx;
   hipStream_t st = c.stream;
@@ -361,7 +370,7 @@ vi_status export_records(const DeviceIndex &ix, uint64_t first, uint64_t count, 
   a.ext_ids = ix.ext_ids.p; a.timestamps = ix.timestamps.p;
   a.block_lo = (uint32_t)block_lo; a.first = first; a.count = count;
   a.world = ix.stripe_world; a.rank = ix.stripe_rank;
-  a.out_ids = ext_ids; a.out_values = values; a.out_ts = timestamps; a.out_where = where;
+  a.out_ids = ext_ids; a.out_values = values; a.out_ts = timestamps; a.out_where = where; a.out_slot = slot_dev;
   if (timing) VI_HIP(hipEventRecord(c.ev[0], st));
   if (dim % 4 == 0 && aligned16(values))
     hipLaunchKernelGGL(export_blocks_kernel<true>, dim3((uint32_t)nblk), dim3(64), 0, st, a);
@@ -382,6 +391,27 @@ vi_status export_records(const DeviceIndex &ix, uint64_t first, uint64_t count, 
   }
   done = true;
   return VI_OK;
+}
+
+}  // namespace
+
+vi_status fetch_records_by_id(const DeviceIndex &ix, const uint64_t *ids, uint64_t n, bool on_device, uint32_t *count,
+                              float *values, uint64_t *timestamps, uint64_t *where) {
+  return fetch_by_id(ix, ids, n, on_device, on_device, count, values, timestamps, where, nullptr, true);
+}
+
+vi_status export_records(const DeviceIndex &ix, uint64_t first, uint64_t count, bool on_device, uint64_t *ext_ids,
+                         float *values, uint64_t *timestamps, uint64_t *where) {
+  return export_range(ix, first, count, on_device, ext_ids, values, timestamps, where, nullptr, true);
+}
+
+vi_status resolve_records_by_id(const DeviceIndex &ix, const uint64_t *ids, uint64_t n, bool ids_on_device, uint32_t *count_dev,
+                                float *values_dev, uint32_t *slot_dev) {
+  return fetch_by_id(ix, ids, n, ids_on_device, true, count_dev, values_dev, nullptr, nullptr, slot_dev, false);
+}
+
+vi_status resolve_records_by_range(const DeviceIndex &ix, uint64_t first, uint64_t count, float *values_dev, uint32_t *slot_dev) {
+  return export_range(ix, first, count, true, nullptr, values_dev, nullptr, nullptr, slot_dev, false);
 }
 
 }  // namespace vi

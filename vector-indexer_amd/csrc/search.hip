@@ -52,18 +52,6 @@ __global__ void gather_vectors_kernel(const float *blocks, uint32_t dq, uint32_t
   }
 }
 
-// body(ctx) with a context of the index's pool held for its duration; the release publishes the context's stats as the
-// handle's, under the pool's lock, however body ends
-template <class Body>
-vi_status with_search_context(const DeviceIndex &ix, Body body) {
-  VI_HIP(hipSetDevice(ix.device));
-  SearchContext *held = nullptr;  // (set before anything can release it)
-  ContextLease lease(ix.search_contexts, make_context<SearchContext>, [&] { ix.last_stats = held->stats; });
-  if (!lease.ctx) return VI_ERR_DEVICE;  // (the message is make_context's)
-  held = lease.ctx;
-  return body(*held);
-}
-
 // What both entries open a batch with: the checks on the arguments (the filter's index; nq x `width` result entries indexed
 // in 32 bits), n_probe clamped to the lists, the context's stats reset, the knobs read — once per call: they may change.
 vi_status open_batch(SearchBatch &b, uint64_t nq, uint64_t k, uint64_t n_probe, uint64_t width) {
@@ -106,6 +94,15 @@ vi_status close_batch(SearchBatch &b, uint64_t *tie, uint64_t n) {
   return VI_OK;
 }
 
+}  // namespace
+
+vi_status launch_gather_vectors(const DeviceIndex &ix, const uint64_t *slots, uint64_t nres, float *V, hipStream_t st) {
+  if (nres == 0) return VI_OK;
+  hipLaunchKernelGGL(gather_vectors_kernel, dim3((uint32_t)nres), dim3(64), 0, st, ix.lists.blocks.p, ix.dq, ix.dim, slots, nres, V);
+  VI_HIP(hipGetLastError());
+  return VI_OK;
+}
+
 // ---- top-k search (fast engines: n_probe_eff <= 64 and k <= 64, the MFMA engine k <= 128) ----
 vi_status topk_search(const DeviceIndex &ix, SearchContext &ctx, const SearchIO &io) {
   SearchWorkspace &ws = ctx.ws;
@@ -130,6 +127,7 @@ vi_status topk_search(const DeviceIndex &ix, SearchContext &ctx, const SearchIO 
   VI_TRY(ws.counts.reserve(nq));
   out.counts = ws.counts.p;
   if (io.V) { VI_TRY(ws.slots.reserve(nq * k)); out.slots = ws.slots.p; }
+  else if (io.on_device) out.slots = io.slots;
 
   if (P == 0 || ix.nlists == 0) {  // empty index: every query has zero results
     std::vector<float> hD(nq * k, INFINITY);
@@ -180,6 +178,8 @@ vi_status topk_search(const DeviceIndex &ix, SearchContext &ctx, const SearchIO 
   }
   return close_batch(b, out.tie, nq * k);  // (host outputs carry no tie keys)
 }
+
+namespace {
 
 // a result buffer grown to `cap` entries with its first `used` kept
 template <typename T>

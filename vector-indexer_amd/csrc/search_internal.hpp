@@ -1,6 +1,6 @@
 // search_internal.hpp — what the search engines' and the index builders' translation units (search.hip, search_kernels.hip,
 // generic_search.hip, filter_search.hip, grouping.hip, select.hip, range_select.hip, rank_images.hip, device_index.hip,
-// list_build.hip, list_update.hip, kmeans.hip) call in each other and share: declared once, here.  A search is one
+// list_build.hip, list_update.hip, kmeans.hip, similar_search.hip) call in each other and share: declared once, here.  A search is one
 // SearchBatch, built by the dispatcher (search.hip) and handed to the engine it chose; the engines hand it on to their
 // stages.  (The probe grouping is called through a header of its own, grouping.hpp; filter_search.hip launches its rank
 // and select phases through rank_stream.hpp and select.hpp.)
@@ -101,6 +101,23 @@ struct SearchBatch {
 };
 // device buffers of a top-k search's results: nq x k each; tie, slots and counts (nq) may be null
 struct SelectOutputs { float *D; int64_t *I; uint64_t *tie, *slots; uint32_t *counts; };
+
+// ---- search.hip: the dispatcher, for the callers that bring their own context (similar_search.hip) ----
+// body(ctx) with a context of the index's pool held for its duration; the release publishes the context's stats as the
+// handle's, under the pool's lock, however body ends
+template <class Body>
+vi_status with_search_context(const DeviceIndex &ix, Body body) {
+  VI_HIP(hipSetDevice(ix.device));
+  SearchContext *held = nullptr;  // (set before anything can release it)
+  ContextLease lease(ix.search_contexts, make_context<SearchContext>, [&] { ix.last_stats = held->stats; });
+  if (!lease.ctx) return VI_ERR_DEVICE;  // (the message is make_context's)
+  held = lease.ctx;
+  return body(*held);
+}
+// one top-k search in a context the caller holds: what device_index_search runs; synchronised on return
+vi_status topk_search(const DeviceIndex &ix, SearchContext &ctx, const SearchIO &io);
+// V[r] (row-major, dim floats) = the stored vector of slots[r], zeros for ~0; queued on st
+vi_status launch_gather_vectors(const DeviceIndex &ix, const uint64_t *slots, uint64_t nres, float *V, hipStream_t st);
 
 // ---- search.hip: a radius search's result as the engines fill it, chunk of queries after chunk ----
 // range_result_begin sizes lims; range_result_place reads the hit counts of queries [q0, q0 + m) back (it synchronises),

@@ -563,6 +563,80 @@ class VectorIndex:
                                                                for p in (ids_ptr, values_ptr, ts_ptr, where_ptr)]),
                       prefix="Failed to export records: ")
 
+    def search_by_ids(self, ids, k: int, n_probe: int, exclude_self: bool = True, include_vectors: bool = False,
+                      filter: Optional[AnyFilter] = None):
+        """extension: "what is similar to the record I hold?" -> (D f32[n, k'], I i64[n, k'][, V f32[n, k', dim]], found
+        u32[n]), k' = k clamped to max_k.  Row i is the top-k of the stored vector of the first record in list order that
+        carries ids[i] (the record get() describes), that ONE record deleted from its candidates if exclude_self — records
+        with the same id or the same bits stay.  found[i]: resident records carrying ids[i]; 0: an absent id, a row of
+        padding (inf / -1 / zero vectors), no error.  Ids may repeat.  An excluding call searches k + 1 wide: k = 64 and
+        k = 128 are served by a slower engine (same bits).  Unpartitioned handles only."""
+        a = _native.id_array(ids)
+        n, k = a.size, int(k)
+        D = np.full((n, max(k, 0)), np.inf, dtype=np.float32)
+        I = np.full((n, max(k, 0)), -1, dtype=np.int64)
+        V = np.zeros((n, max(k, 0), self._dimension), dtype=np.float32) if include_vectors else None
+        found = np.zeros(n, dtype=np.uint32)
+        kout = C.c_uint64(k)
+        _native.check(lib().vi_indexer_search_by_ids(self._h, _filter_handle(filter), _native.ptr(a) if n else None, n, k,
+                                                     int(n_probe), 1 if exclude_self else 0, _native.ptr(D), _native.ptr(I),
+                                                     _native.ptr(V), None, _native.ptr(found), C.byref(kout)),
+                      prefix="Failed to search by ids: ")
+        kk = int(kout.value)
+        if kk != k:  # k was clamped to max_k: the rows are kk wide
+            D = D.reshape(-1)[: n * kk].reshape(n, kk).copy()
+            I = I.reshape(-1)[: n * kk].reshape(n, kk).copy()
+            if V is not None:
+                V = V.reshape(-1)[: n * kk * self._dimension].reshape(n, kk, self._dimension).copy()
+        return (D, I, V, found) if include_vectors else (D, I, found)
+
+    def search_by_ids_device(self, ids_ptr: int, nq: int, k: int, n_probe: int, D_ptr: int, I_ptr: int, tie_ptr: int = 0,
+                             found_ptr: int = 0, exclude_self: bool = True, filter: Optional[AnyFilter] = None):
+        """... for nq u64 ids in device memory, into device memory: D f32 / I i64 / tie u64 [nq, k'], found u32[nq]; a
+        pointer of 0 skips tie / found"""
+        _native.check(lib().vi_indexer_search_by_ids_device(self._h, _filter_handle(filter), C.c_void_p(ids_ptr) if ids_ptr else None,
+                                                            int(nq), int(k), int(n_probe), 1 if exclude_self else 0,
+                                                            C.c_void_p(D_ptr) if D_ptr else None, C.c_void_p(I_ptr) if I_ptr else None,
+                                                            C.c_void_p(tie_ptr) if tie_ptr else None,
+                                                            C.c_void_p(found_ptr) if found_ptr else None),
+                      prefix="Failed to search by ids: ")
+
+    def knn_graph(self, k: int, n_probe: int, first: int = 0, count: Optional[int] = None, exclude_self: bool = True,
+                  filter: Optional[AnyFilter] = None):
+        """extension: the k-NN graph of records [first, first + count) of the list order (count None: to the end) -> (D
+        f32[count, k'], I i64[count, k']); row j belongs to the record export() returns as row j, and is what
+        search_by_ids gives for it.  Processed in chunks of VI_GRAPH_CHUNK rows (environment; default 65536)."""
+        first, k = int(first), int(k)
+        count = max(self.num_vectors - first, 0) if count is None else int(count)
+        D = np.full((count, max(k, 0)), np.inf, dtype=np.float32)
+        I = np.full((count, max(k, 0)), -1, dtype=np.int64)
+        kout = C.c_uint64(k)
+        _native.check(lib().vi_indexer_knn_graph(self._h, _filter_handle(filter), first, count, k, int(n_probe),
+                                                 1 if exclude_self else 0, _native.ptr(D), _native.ptr(I), None, C.byref(kout)),
+                      prefix="Failed to build the k-NN graph: ")
+        kk = int(kout.value)
+        if kk != k:
+            D = D.reshape(-1)[: count * kk].reshape(count, kk).copy()
+            I = I.reshape(-1)[: count * kk].reshape(count, kk).copy()
+        return D, I
+
+    def knn_graph_device(self, first: int, count: int, k: int, n_probe: int, D_ptr: int, I_ptr: int, tie_ptr: int = 0,
+                         exclude_self: bool = True, filter: Optional[AnyFilter] = None):
+        """... into device memory: D f32 / I i64 / tie u64 [count, k']; a tie pointer of 0 skips it"""
+        _native.check(lib().vi_indexer_knn_graph_device(self._h, _filter_handle(filter), int(first), int(count), int(k),
+                                                        int(n_probe), 1 if exclude_self else 0,
+                                                        C.c_void_p(D_ptr) if D_ptr else None, C.c_void_p(I_ptr) if I_ptr else None,
+                                                        C.c_void_p(tie_ptr) if tie_ptr else None),
+                      prefix="Failed to build the k-NN graph: ")
+
+    def similar_times(self) -> dict:
+        """this thread's last search_by_ids / knn_graph (any form) under VI_SIMILAR_TIMING: host ms around the gather of
+        the queries and the search, HIP-event ms and bytes of self_drop_kernel, rows per chunk; zeros otherwise"""
+        r, s, d = C.c_float(0), C.c_float(0), C.c_float(0)
+        b, c = C.c_uint64(0), C.c_uint64(0)
+        _native.check(lib().vi_similar_last_times(C.byref(r), C.byref(s), C.byref(d), C.byref(b), C.byref(c)))
+        return {"ms_resolve": r.value, "ms_search": s.value, "ms_drop": d.value, "drop_bytes": int(b.value), "chunk_rows": int(c.value)}
+
     def fetch_stats(self) -> dict:
         """figures of the most recent get() / export() (either form); the ms_* only under enable_timing()"""
         st = _native.FetchStats()

@@ -177,6 +177,11 @@ SIGNATURES = {
     "vi_indexer_export_records": (C.c_int, [vp, u64, u64, vp, vp, vp, vp]),
     "vi_indexer_export_records_device": (C.c_int, [vp, u64, u64, vp, vp, vp, vp]),
     "vi_indexer_last_fetch_stats": (C.c_int, [vp, C.POINTER(FetchStats)]),
+    "vi_indexer_search_by_ids": (C.c_int, [vp, vp, vp, u64, u64, u64, u32, vp, vp, vp, vp, vp, C.POINTER(u64)]),
+    "vi_indexer_search_by_ids_device": (C.c_int, [vp, vp, vp, u64, u64, u64, u32, vp, vp, vp, vp]),
+    "vi_indexer_knn_graph": (C.c_int, [vp, vp, u64, u64, u64, u64, u32, vp, vp, vp, C.POINTER(u64)]),
+    "vi_indexer_knn_graph_device": (C.c_int, [vp, vp, u64, u64, u64, u64, u32, vp, vp, vp]),
+    "vi_similar_last_times": (C.c_int, [C.POINTER(f32), C.POINTER(f32), C.POINTER(f32), C.POINTER(u64), C.POINTER(u64)]),
 }
 
 _lib = None

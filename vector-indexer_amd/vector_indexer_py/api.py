@@ -11,6 +11,7 @@
     .remove_records(external_ids) -> int                                          extension: remove from a built index
     .upsert_records(records) -> int                                               extension: replace by external id
     .get_records(external_ids) -> [VectorRecord or None]                          extension: read back by external id
+    .search_similar(external_id, k, n_probe, ...) -> [SearchResult] or None       extension: neighbours of a stored record
     SearchRequest.with_timestamp_range / .with_allowed_ids / .with_excluded_ids   extension: filtered search
 
 Errors are ViError (a RuntimeError) whose .kind is the io::ErrorKind name the reference returns.
@@ -307,6 +308,35 @@ class VectorIndexer:
         finally:
             lib().vi_range_result_free(h)
         return [SearchResult(int(I[j]), float(D[j]), V[j].tolist() if V is not None else None) for j in range(n)]
+
+    def search_similar(self, external_id: int, k: Optional[int] = None, n_probe: Optional[int] = None,
+                       include_vectors: bool = False, exclude_self: bool = True,
+                       timestamp_range: Optional[Tuple[int, int]] = None, allowed_ids=None,
+                       excluded_ids=None) -> Optional[List[SearchResult]]:
+        """extension: the neighbours of the stored record that carries external_id (the first in list order where several
+        do: the record get_records returns), nearest first; exclude_self drops that one record — not other records with
+        its id or its vector — from its own result.  None for an id nothing carries.  k / n_probe None: the config's
+        defaults.  The filters restrict the neighbours, not the record asked about."""
+        if allowed_ids is not None and excluded_ids is not None:
+            raise ValueError("give allowed_ids or excluded_ids, not both")
+        selector = (IdSelector.of(allowed_ids, False) if allowed_ids is not None
+                    else IdSelector.of(excluded_ids, True) if excluded_ids is not None else None)
+        ids = _native.id_array([external_id])
+        k = max(int(self._cfg.default_k if k is None else k), 0)
+        p = self._cfg.default_n_probe if n_probe is None else int(n_probe)
+        kcap = max(min(k, self._cfg.max_k), 1)
+        D = np.full((1, kcap), np.inf, dtype=np.float32)
+        I = np.full((1, kcap), -1, dtype=np.int64)
+        V = np.zeros((1, kcap, self._cfg.dimension), dtype=np.float32) if include_vectors else None
+        cnt, found = np.zeros(1, dtype=np.uint64), np.zeros(1, dtype=np.uint32)
+        kout = C.c_uint64(0)
+        _native.check(lib().vi_indexer_search_by_ids(self._h, self._filter(timestamp_range, selector), _native.ptr(ids), 1, k, p,
+                                                     1 if exclude_self else 0, _native.ptr(D), _native.ptr(I), _native.ptr(V),
+                                                     _native.ptr(cnt), _native.ptr(found), C.byref(kout)))
+        if not found[0]:
+            return None
+        return [SearchResult(int(I[0, j]), float(D[0, j]), V[0, j].tolist() if V is not None else None)
+                for j in range(int(cnt[0]))]
 
     def search_request(self, query) -> SearchRequest:
         return SearchRequest(list(query), False, self._cfg.default_k, self._cfg.default_n_probe)
