@@ -593,7 +593,7 @@ vi_status vi_indexer_knn_graph(const vi_indexer *ix, const vi_filter *f, uint64_
                                uint64_t n_probe, uint32_t exclude_self, float *D, int64_t *I, uint64_t *counts, uint64_t *k_out);
 vi_status vi_indexer_knn_graph_device(const vi_indexer *ix, const vi_filter *f, uint64_t first, uint64_t count, uint64_t k,
                                       uint64_t n_probe, uint32_t exclude_self, float *D_dev, int64_t *I_dev, uint64_t *tie_dev);
-/* Of the calling thread's last of the four, summed over its chunks, taken only while the environment variable
+/* Of the calling thread's last of the four (or of the three radius forms below), summed over its chunks, taken only while the environment variable
  * VI_SIMILAR_TIMING is set (and not "0"); zeros otherwise.  ms_resolve / ms_search: host clock around the gather of the
  * queries and around the search; ms_drop: HIP events around self_drop_kernel.  Reported with or without the variable:
  * drop_bytes, the bytes that kernel moved, and chunk_rows, the rows per chunk used.  Any pointer may be NULL. */
@@ -633,6 +633,41 @@ vi_status vi_range_result_device(const vi_range_result *r, const uint64_t **lims
 vi_status vi_range_result_copy_device(const vi_range_result *r, uint64_t *lims_dev, float *D_dev, int64_t *I_dev,
                                       uint64_t *tie_dev);
 void vi_range_result_free(vi_range_result *r); /* NULL ok */
+
+/* ---- extension: radius search by stored record ("which records are within eps of the one I hold?") ------------------
+ * The row of a stored record r is the reference's candidate sequence for the query "r's stored f32 bits" (probed lists in
+ * shard visiting order, probe rank, list position), less what the filter does not admit, less — with exclude_self != 0 —
+ * the ONE candidate that is r itself (the same list and position, i.e. the same slot: a record with the same external
+ * id, or with the same bits under another id, stays), stably sorted, take_while(d <= radius2) in f32, inclusive, on the
+ * reference's scalar-order sum.  exclude_self == 0 gives bit for bit what vi_indexer_range_search_device returns for the
+ * stored bits as queries: lims, D, I and tie.  If r's own list is not among the probed ones nothing is deleted.  A row
+ * exists for every named record whether or not the filter admits that record (f == NULL: no filter).
+ *   by ids:       an id names the first record in list order that carries it (the record vi_indexer_get_records returns);
+ *                 found[i] = resident records carrying it (the get's count_out).  An absent id is no error: its row is
+ *                 empty (lims[i + 1] == lims[i]) and found[i] = 0.  Ids may repeat, in any order; any u64 is an id.
+ *                 ext_ids_dev / found_dev of the *_device entry are device pointers; found / found_dev may be NULL.
+ *   radius_graph: rows = records [first, first + count) of LIST ORDER (row j is the record vi_indexer_export_records
+ *                 returns as row j); first + count > vi_indexer_num_vectors is VI_ERR_INVALID_INPUT.  One entry point:
+ *                 the result lives on the device either way.
+ * radius2 NaN: VI_ERR_INVALID_INPUT; negative: VI_OK, nq empty rows, found still filled; +inf: everything probed less
+ * what is deleted; radius2 = 0 with exclusion: exactly the OTHER records whose distance bits are 0.  n_probe is clamped
+ * to max_n_probe; 0 is VI_ERR_INVALID_INPUT.  Partitioned handles (world_size > 1) are VI_ERR_INVALID_INPUT.  nq == 0 /
+ * count == 0: what vi_indexer_range_search gives for nq == 0, a result of no rows.  The rows are processed in chunks of
+ * VI_GRAPH_CHUNK (environment, default 65536) through one search context; the result is allocated at its true total
+ * and at least doubles when a further chunk outgrows it.  The call is all or nothing: on any error — a result larger
+ * than device memory is VI_ERR_DEVICE — *out stays NULL, found is not written, and the handle stays usable.
+ * The result is an ordinary vi_range_result of the index: vi_range_result_total / _copy (V included) / _device /
+ * _copy_device / _free and vi_range_merge_device take it unchanged.  Threads: the contract of a search.
+ * vi_indexer_last_stats afterwards reads as after a radius search (of the last chunk), k = 0.  vi_similar_last_times
+ * reports these calls too: ms_drop / drop_bytes then cover range_find_kernel and range_move_kernel. */
+vi_status vi_indexer_range_search_by_ids(const vi_indexer *ix, const vi_filter *f, const uint64_t *ext_ids, uint64_t nq,
+                                         float radius2, uint64_t n_probe, uint32_t exclude_self, uint32_t *found,
+                                         vi_range_result **out);
+vi_status vi_indexer_range_search_by_ids_device(const vi_indexer *ix, const vi_filter *f, const uint64_t *ext_ids_dev, uint64_t nq,
+                                                float radius2, uint64_t n_probe, uint32_t exclude_self, uint32_t *found_dev,
+                                                vi_range_result **out);
+vi_status vi_indexer_radius_graph(const vi_indexer *ix, const vi_filter *f, uint64_t first, uint64_t count, float radius2,
+                                  uint64_t n_probe, uint32_t exclude_self, vi_range_result **out);
 
 /* Merge `parts` per-rank partial results (each nq x k, device pointers laid out
  * [part][nq][k]) into the global top-k with the reference's stable order. */

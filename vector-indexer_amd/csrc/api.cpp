@@ -1240,6 +1240,76 @@ vi_status vi_indexer_range_search_device(const vi_indexer *ix, const vi_filter *
   });
 }
 
+// ---- radius search by stored record (similar_search.hip) ----
+// The checks common to the three entries, all before any device work; on VI_OK *out is NULL, *n_probe clamped, *flt set.
+static vi_status range_similar_common(const vi_indexer *ix, const vi_filter *f, uint64_t nq, bool null_ids, float radius2,
+                                      uint64_t *n_probe, vi_range_result **out, const vi::SlotFilter **flt) {
+  if (!out) return fail(VI_ERR_INVALID_INPUT, "null pointer: out is required");
+  *out = nullptr;
+  uint64_t k = 1;
+  VI_TRY(search_common(ix, &k, n_probe));
+  if (*n_probe == 0) return fail(VI_ERR_INVALID_INPUT, "n_probe must be greater than 0");
+  if (std::isnan(radius2)) return fail(VI_ERR_INVALID_INPUT, "radius2 is NaN");
+  if (nq > (1ull << 40)) return fail(VI_ERR_INVALID_INPUT, "%llu rows are too many for one call", (unsigned long long)nq);
+  if (nq && null_ids) return fail(VI_ERR_INVALID_INPUT, "null id array with nq = %llu", (unsigned long long)nq);
+  if (!ix->impl.dev) return fail(VI_ERR_INVALID_INPUT, "the indexer holds no index (build or load it first)");
+  if (ix->impl.cfg.world_size > 1 || ix->impl.dev->stripe_world > 1)
+    return fail(VI_ERR_INVALID_INPUT,
+                "radius search by stored record needs the whole index on one handle; on a partitioned handle call "
+                "vi_indexer_get_records_device on every rank, take the record with the lowest `where`, search its vector "
+                "with vi_indexer_range_search_device on every rank and merge with vi_range_merge_device (the record itself "
+                "is then not excluded)");
+  return filter_common(ix, f, flt);
+}
+
+static vi_status range_similar_run(const vi_indexer *ix, const vi::RangeSimilarIO &io, vi_range_result **out) {
+  auto r = std::make_unique<vi_range_result>();
+  VI_TRY(vi::device_index_range_similar(*ix->impl.dev, io, &r->impl));  // (all or nothing: a failed call leaves no result)
+  *out = r.release();
+  return VI_OK;
+}
+
+static vi_status range_by_ids_common(const vi_indexer *ix, const vi_filter *f, const uint64_t *ids, uint64_t nq, float radius2,
+                                     uint64_t n_probe, uint32_t exclude_self, bool on_device, uint32_t *found,
+                                     vi_range_result **out) {
+  return vi::guarded([&]() -> vi_status {
+  const vi::SlotFilter *flt = nullptr;
+  VI_TRY(range_similar_common(ix, f, nq, !ids, radius2, &n_probe, out, &flt));
+  vi::RangeSimilarIO io;
+  io.ids = ids; io.on_device = on_device; io.nq = nq; io.n_probe = n_probe; io.radius2 = radius2;
+  io.exclude_self = exclude_self != 0; io.filter = flt; io.found = found;
+  return range_similar_run(ix, io, out);
+  });
+}
+
+vi_status vi_indexer_range_search_by_ids(const vi_indexer *ix, const vi_filter *f, const uint64_t *ext_ids, uint64_t nq,
+                                         float radius2, uint64_t n_probe, uint32_t exclude_self, uint32_t *found,
+                                         vi_range_result **out) {
+  return range_by_ids_common(ix, f, ext_ids, nq, radius2, n_probe, exclude_self, false, found, out);
+}
+
+vi_status vi_indexer_range_search_by_ids_device(const vi_indexer *ix, const vi_filter *f, const uint64_t *ext_ids_dev, uint64_t nq,
+                                                float radius2, uint64_t n_probe, uint32_t exclude_self, uint32_t *found_dev,
+                                                vi_range_result **out) {
+  return range_by_ids_common(ix, f, ext_ids_dev, nq, radius2, n_probe, exclude_self, true, found_dev, out);
+}
+
+vi_status vi_indexer_radius_graph(const vi_indexer *ix, const vi_filter *f, uint64_t first, uint64_t count, float radius2,
+                                  uint64_t n_probe, uint32_t exclude_self, vi_range_result **out) {
+  return vi::guarded([&]() -> vi_status {
+  const vi::SlotFilter *flt = nullptr;
+  VI_TRY(range_similar_common(ix, f, count, false, radius2, &n_probe, out, &flt));
+  const uint64_t nvec = ix->impl.dev->nvec_resident;
+  if (first > nvec || count > nvec - first)
+    return fail(VI_ERR_INVALID_INPUT, "records [%llu, %llu + %llu) of %llu resident records", (unsigned long long)first,
+                (unsigned long long)first, (unsigned long long)count, (unsigned long long)nvec);
+  vi::RangeSimilarIO io;
+  io.first = first; io.nq = count; io.n_probe = n_probe; io.radius2 = radius2; io.exclude_self = exclude_self != 0;
+  io.filter = flt;
+  return range_similar_run(ix, io, out);
+  });
+}
+
 uint64_t vi_range_result_total(const vi_range_result *r) { return r ? r->impl.total : 0; }
 
 vi_status vi_range_result_copy(const vi_range_result *r, uint64_t *lims, float *D, int64_t *I, float *V) {

@@ -38,6 +38,24 @@ struct BlockSet {               // a set of lists stored as lane-interleaved blo
   uint64_t nblocks = 0;
 };
 
+struct DeviceIndex;
+
+// Result of a radius search (device_index_range_search): CSR like Faiss's RangeSearchResult — query q owns entries
+// [lims[q], lims[q + 1]) of D / I / tie / slots, sorted as the reference's stable candidate sort leaves them.  Owns its
+// device buffers; outlives later searches of its index, not the index.
+struct RangeResult {
+  const DeviceIndex *ix = nullptr;  // the index searched (vi_range_result_copy gathers stored vectors from it); null: a
+                                    // merged result (range_merge_device), which belongs to no index and has no slots
+  int device = 0;                   // where the buffers live
+  uint64_t nq = 0, total = 0;
+  std::vector<uint64_t> h_lims;     // host copy of lims: nq + 1
+  DevBuf<uint64_t> lims;            // nq + 1
+  DevBuf<float> D;                  // `total` entries each, in buffers of `cap`
+  DevBuf<int64_t> I;
+  DevBuf<uint64_t> tie, slots;      // tie key (candidate-order rank << 32 | list position); global slot of the stored vector
+  uint64_t cap = 0;
+};
+
 struct SearchWorkspace {
   DevBuf<float> q;              // queries on device (nq x dim) when the caller passed host memory
   DevBuf<float> crun_dist;      // coarse partial runs [nq][S][P]
@@ -95,6 +113,11 @@ struct SearchWorkspace {
   DevBuf<float> sim_D;
   DevBuf<int64_t> sim_I;
   DevBuf<uint64_t> sim_slots;
+  // its radius form: the chunk's search result before the drop (kept: range_result_place reuses its capacity from chunk
+  // to chunk and call to call) and the output length of every row; range_find_kernel leaves in self_slot the position
+  // of each row's own entry
+  RangeResult sim_range;
+  DevBuf<uint32_t> sim_len;
 };
 
 // ---- reading records back (record_fetch.hip) ----
@@ -274,25 +297,11 @@ struct SimilarIO {
 vi_status device_index_search_similar(const DeviceIndex &ix, const SimilarIO &io);
 // this thread's last device_index_search_similar under VI_SIMILAR_TIMING (set, not '0'), summed over its chunks: host
 // clock around the resolve + gather of the queries and around the search, HIP events around self_drop_kernel; the bytes
-// that kernel moved and the rows per chunk used.  Zeros otherwise.
+// that kernel moved and the rows per chunk used.  Zeros otherwise.  device_index_range_similar reports the same way:
+// ms_drop / drop_bytes then cover range_find_kernel and range_move_kernel.
 struct SimilarTimes { float ms_resolve = 0, ms_search = 0, ms_drop = 0; uint64_t drop_bytes = 0, chunk_rows = 0; };
 SimilarTimes similar_last_times();
 
-// Result of a radius search (device_index_range_search): CSR like Faiss's RangeSearchResult — query q owns entries
-// [lims[q], lims[q + 1]) of D / I / tie / slots, sorted as the reference's stable candidate sort leaves them.  Owns its
-// device buffers; outlives later searches of its index, not the index.
-struct RangeResult {
-  const DeviceIndex *ix = nullptr;  // the index searched (vi_range_result_copy gathers stored vectors from it); null: a
-                                    // merged result (range_merge_device), which belongs to no index and has no slots
-  int device = 0;                   // where the buffers live
-  uint64_t nq = 0, total = 0;
-  std::vector<uint64_t> h_lims;     // host copy of lims: nq + 1
-  DevBuf<uint64_t> lims;            // nq + 1
-  DevBuf<float> D;                  // `total` entries each, in buffers of `cap`
-  DevBuf<int64_t> I;
-  DevBuf<uint64_t> tie, slots;      // tie key (candidate-order rank << 32 | list position); global slot of the stored vector
-  uint64_t cap = 0;
-};
 struct RangeIO {
   const float *queries = nullptr;  // host or device (on_device)
   bool on_device = false;
@@ -304,6 +313,23 @@ struct RangeIO {
 vi_status device_index_range_search(const DeviceIndex &ix, const RangeIO &io, RangeResult *out);
 // host copies of a result: lims (nq + 1), D, I (total each), V (optional, total x dim: the stored vectors)
 vi_status range_result_copy(const RangeResult &r, uint64_t *lims, float *D, int64_t *I, float *V);
+
+// ---- radius search by stored record (similar_search.hip): SimilarIO's rows, a RangeResult for the answer ----
+// Row i is the radius search of the stored f32 bits of a record, named as SimilarIO names it; exclude_self deletes that
+// one record (its slot) from the row, an absent id has an empty row.  The contract is vi_indexer_range_search_by_ids /
+// vi_indexer_radius_graph in include/vi_amd.h; arguments are checked by the caller (api.cpp): n_probe > 0, radius2 no
+// NaN, an unpartitioned index.  All or nothing: `found` is written once every chunk has succeeded.
+struct RangeSimilarIO {
+  const uint64_t *ids = nullptr;   // by id: nq ids (host, or device with on_device); null: by range
+  uint64_t first = 0;              // by range: rows are records [first, first + nq) of list order
+  bool on_device = false;          // ids and found are device pointers
+  uint64_t nq = 0, n_probe = 0;
+  float radius2 = 0.0f;
+  bool exclude_self = true;
+  const SlotFilter *filter = nullptr;
+  uint32_t *found = nullptr;       // by id, optional: records carrying each id
+};
+vi_status device_index_range_similar(const DeviceIndex &ix, const RangeSimilarIO &io, RangeResult *out);
 
 // The search engines' environment options, read once per search by read_engine_knobs (search.hip) into the call's SearchBatch.
 // A '0' as the first character turns an on-by-default option off.  (The MFMA engine's variables keep its first name, VI_FILTER.)

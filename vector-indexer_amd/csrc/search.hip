@@ -193,6 +193,8 @@ vi_status grow_keeping(DevBuf<T> &b, uint64_t used, uint64_t cap, hipStream_t st
   return VI_OK;
 }
 
+}  // namespace
+
 // ---- radius search ----
 vi_status radius_search(const DeviceIndex &ix, SearchContext &ctx, const RangeIO &io, RangeResult *out) {
   SearchBatch b{ix, ctx, io.filter, nullptr, nullptr};
@@ -208,8 +210,6 @@ vi_status radius_search(const DeviceIndex &ix, SearchContext &ctx, const RangeIO
   else VI_TRY(device_index_range_generic(b, io.radius2, out));
   return close_batch(b, out->tie.p, out->total);
 }
-
-}  // namespace
 
 EngineKnobs read_engine_knobs() {
   auto on = [](const char *name) { const char *e = getenv(name); return !(e && *e == '0'); };

@@ -116,6 +116,8 @@ vi_status with_search_context(const DeviceIndex &ix, Body body) {
 }
 // one top-k search in a context the caller holds: what device_index_search runs; synchronised on return
 vi_status topk_search(const DeviceIndex &ix, SearchContext &ctx, const SearchIO &io);
+// one radius search in a context the caller holds: what device_index_range_search runs; synchronised on return
+vi_status radius_search(const DeviceIndex &ix, SearchContext &ctx, const RangeIO &io, RangeResult *out);
 // V[r] (row-major, dim floats) = the stored vector of slots[r], zeros for ~0; queued on st
 vi_status launch_gather_vectors(const DeviceIndex &ix, const uint64_t *slots, uint64_t nres, float *V, hipStream_t st);
 

@@ -22,6 +22,14 @@
 // inside the dispatcher's 2^31 - 1 entries) in ascending order through the one context, whose workspace is reused.  Rows
 // of a range are in list order, so the queries of a chunk probe the same few lists and the grouping's (list, query
 // group) items stay dense.
+//
+// The radius form (vi_indexer_range_search_by_ids / vi_indexer_radius_graph) runs the same three steps with ragged rows:
+// the chunk is searched by radius_search (search.hip) into a RangeResult of the context (ws.sim_range),
+// range_find_kernel finds each row's own entry and writes the row's output length, range_result_place — the call the
+// radius engines extend a result with, chunk of queries after chunk — extends the caller's result by those lengths, and
+// range_move_kernel writes the entries behind the earlier chunks', one per row left out (self_drop.hpp: why that is
+// exact).  Beside the search's workspace a chunk of C rows holds 4 C D bytes of queries, 28 bytes per hit of the
+// intermediate result and 12 bytes per row.
 #include <hip/hip_runtime.h>
 
 #include <sys/time.h>
@@ -227,9 +235,183 @@ vi_status similar_in_context(const DeviceIndex &ix, SearchContext &ctx, const Si
   return VI_OK;
 }
 
+// ---- the radius form: a chunk's CSR result -> the caller's CSR result, one entry per row deleted ----
+struct RangeFindArgs {
+  const uint64_t *in_lims;   // [m + 1] the chunk's search result
+  const uint64_t *in_slots;
+  uint32_t *self_pos;        // [m] in: the slot of the row's record; out: the position of its entry in the row, or kSelfDropNoMatch
+  const uint32_t *found;     // [m] records carrying the row's id; null: every row has its record (a range)
+  uint32_t *len;             // [m] out: entries of the output row
+  uint32_t m, exclude;
+};
+
+// One wave per row, four rows per workgroup.  The row's slots are searched 64 at a time by ballot (slots are unique: at
+// most one lane answers, and the search ends there); without exclusion nothing is read but the row's bounds.
+__global__ void __launch_bounds__(256) range_find_kernel(RangeFindArgs a) {
+  const uint32_t row = blockIdx.x * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
+  if (row >= a.m) return;  // (wave-uniform)
+  const bool absent = a.found && self_drop_row_absent(a.found[row]);
+  const uint64_t in0 = a.in_lims[row];
+  const uint32_t len = (uint32_t)(a.in_lims[row + 1] - in0);  // (a chunk holds fewer than 2^31 entries)
+  uint32_t s = kSelfDropNoMatch;
+  if (a.exclude && !absent) {
+    const uint64_t self = a.self_pos[row];
+    for (uint32_t j0 = 0; j0 < len && s == kSelfDropNoMatch; j0 += 64u) {
+      const uint32_t j = j0 + lane;
+      const uint64_t hit = __ballot(j < len && a.in_slots[in0 + j] == self);
+      if (hit) s = j0 + (uint32_t)__ffsll((unsigned long long)hit) - 1u;
+    }
+  }
+  if (lane == 0) {
+    a.self_pos[row] = s;
+    a.len[row] = range_drop_len(len, s != kSelfDropNoMatch, absent);
+  }
+}
+
+struct RangeMoveArgs {
+  const uint64_t *in_lims;    // [m + 1]
+  const uint64_t *out_lims;   // [m + 1] the caller's lims from this chunk's first row on
+  const uint32_t *self_pos;   // [m] as range_find_kernel left it
+  const float *D_in;
+  const int64_t *I_in;
+  const uint64_t *tie_in, *slots_in;
+  float *D;
+  int64_t *I;
+  uint64_t *tie, *slots;
+  uint32_t m;
+};
+
+// One wave per row again; lanes stride the row, so every access is a coalesced 4- or 8-byte one.  The row of an absent
+// id has length 0 and moves nothing.
+__global__ void __launch_bounds__(256) range_move_kernel(RangeMoveArgs a) {
+  const uint32_t row = blockIdx.x * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
+  if (row >= a.m) return;  // (wave-uniform)
+  const uint64_t out0 = a.out_lims[row];
+  const uint32_t n = (uint32_t)(a.out_lims[row + 1] - out0);
+  if (n == 0) return;
+  const uint64_t in0 = a.in_lims[row];
+  const uint32_t s = a.self_pos[row];
+  for (uint32_t j = lane; j < n; j += 64u) {
+    const uint64_t src = range_drop_src(in0, j, s);  // (< in_lims[row + 1]: n is the row's length less the match)
+    a.D[out0 + j] = a.D_in[src];
+    a.I[out0 + j] = a.I_in[src];
+    a.tie[out0 + j] = a.tie_in[src];
+    a.slots[out0 + j] = a.slots_in[src];
+  }
+}
+
+struct EventPairs {  // HIP events around the two kernels, only under VI_SIMILAR_TIMING
+  hipEvent_t ev[4] = {};
+  ~EventPairs() {
+    for (auto &e : ev)
+      if (e) (void)hipEventDestroy(e);
+  }
+};
+
+vi_status range_similar_in_context(const DeviceIndex &ix, SearchContext &ctx, const RangeSimilarIO &io, RangeResult *out) {
+  SearchWorkspace &ws = ctx.ws;
+  hipStream_t st = ctx.stream;
+  const uint64_t dim = ix.dim;
+  const uint64_t C = chunk_rows(64);
+  const char *tenv = getenv("VI_SIMILAR_TIMING");
+  const bool timing = tenv && *tenv && *tenv != '0';
+  SimilarTimes tm{};
+  tm.chunk_rows = C;
+  EventPairs ep;
+  if (timing)
+    for (auto &e : ep.ev) VI_HIP(hipEventCreate(&e));
+  RangeIO rio;
+  rio.on_device = true; rio.n_probe = io.n_probe; rio.radius2 = io.radius2; rio.filter = io.filter;
+  if (io.nq == 0) {  // an empty result, made as a radius search of no query makes it
+    VI_TRY(radius_search(ix, ctx, rio, out));
+    VI_HIP(hipStreamSynchronize(st));
+    g_last_times = tm;
+    return VI_OK;
+  }
+  // found is the caller's only once every chunk has succeeded: until then it is kept here
+  const bool want_found = io.found && io.ids;
+  std::vector<uint32_t> h_found;
+  DevBuf<uint32_t> d_found;
+  if (want_found && !io.on_device) h_found.resize(io.nq);
+  if (want_found && io.on_device && io.nq > C) VI_TRY(d_found.reserve(io.nq));
+
+  RangeResult &in = ws.sim_range;
+  VI_TRY(range_result_begin(ix, io.nq, out));
+  for (uint64_t q0 = 0; q0 < io.nq; q0 += C) {
+    const uint64_t m = std::min(C, io.nq - q0);
+    // ---- (1) the chunk's queries: stored rows -> ws.q, their slots, the records carrying each id ----
+    const double t0 = timing ? now_ms() : 0.0;
+    VI_TRY(ws.q.reserve(m * dim));
+    VI_TRY(ws.self_slot.reserve(m));
+    VI_TRY(ws.sim_len.reserve(m));
+    if (io.ids) {
+      VI_TRY(ws.self_found.reserve(m));
+      VI_TRY(resolve_records_by_id(ix, io.ids + q0, m, io.on_device, ws.self_found.p, ws.q.p, ws.self_slot.p));
+    } else {
+      VI_TRY(resolve_records_by_range(ix, io.first + q0, m, ws.q.p, ws.self_slot.p));
+    }
+    const uint32_t *found = io.ids ? ws.self_found.p : nullptr;
+    VI_HIP(hipSetDevice(ix.device));
+    const double t1 = timing ? now_ms() : 0.0;
+    // ---- (2) the radius search of the chunk, into the context's own result ----
+    rio.queries = ws.q.p; rio.nq = m;
+    VI_TRY(radius_search(ix, ctx, rio, &in));  // (synchronised)
+    const double t2 = timing ? now_ms() : 0.0;
+    // ---- (3) every row's own entry and its output length ----
+    const dim3 grid((uint32_t)((m + 3) / 4)), block(256);
+    RangeFindArgs fa{in.lims.p, in.slots.p, ws.self_slot.p, found, ws.sim_len.p, (uint32_t)m, io.exclude_self ? 1u : 0u};
+    if (timing) VI_HIP(hipEventRecord(ep.ev[0], st));
+    hipLaunchKernelGGL(range_find_kernel, grid, block, 0, st, fa);
+    VI_HIP(hipGetLastError());
+    if (timing) VI_HIP(hipEventRecord(ep.ev[1], st));
+    // ---- (4) the caller's result extended by the chunk's rows ----
+    VI_TRY(range_result_place(out, q0, m, ws.sim_len.p, st));
+    // ---- (5) the entries ----
+    const uint64_t moved = out->h_lims[q0 + m] - out->h_lims[q0];
+    if (timing) VI_HIP(hipEventRecord(ep.ev[2], st));
+    if (moved) {
+      RangeMoveArgs ma{in.lims.p, out->lims.p + q0, ws.self_slot.p, in.D.p, in.I.p, in.tie.p, in.slots.p,
+                       out->D.p, out->I.p, out->tie.p, out->slots.p, (uint32_t)m};
+      hipLaunchKernelGGL(range_move_kernel, grid, block, 0, st, ma);
+      VI_HIP(hipGetLastError());
+    }
+    if (timing) VI_HIP(hipEventRecord(ep.ev[3], st));
+    // find: a row's bounds, slot, count, position and length, and (at most) its slots; move: bounds and position, 28
+    // bytes per entry in and out
+    tm.drop_bytes += m * 32 + (io.exclude_self ? in.total * 8 : 0) + m * 36 + moved * 56;
+    if (want_found) {
+      if (!io.on_device) VI_HIP(hipMemcpyAsync(h_found.data() + q0, found, m * 4, hipMemcpyDeviceToHost, st));
+      else if (d_found.p) VI_HIP(hipMemcpyAsync(d_found.p + q0, found, m * 4, hipMemcpyDeviceToDevice, st));
+    }
+    VI_HIP(hipStreamSynchronize(st));  // (the next chunk's resolve writes ws.q and ws.self_slot from a stream of its own)
+    if (timing) {
+      tm.ms_resolve += (float)(t1 - t0);
+      tm.ms_search += (float)(t2 - t1);
+      tm.ms_drop += elapsed_ms(ep.ev[0], ep.ev[1]) + elapsed_ms(ep.ev[2], ep.ev[3]);
+    }
+  }
+  if (want_found) {
+    if (!io.on_device) std::copy(h_found.begin(), h_found.end(), io.found);
+    else {
+      VI_HIP(hipMemcpyAsync(io.found, d_found.p ? d_found.p : ws.self_found.p, io.nq * 4, hipMemcpyDeviceToDevice, st));
+      VI_HIP(hipStreamSynchronize(st));
+    }
+  }
+  g_last_times = tm;
+  return VI_OK;
+}
+
 }  // namespace
 
 SimilarTimes similar_last_times() { return g_last_times; }
+
+vi_status device_index_range_similar(const DeviceIndex &ix, const RangeSimilarIO &io, RangeResult *out) {
+  g_last_times = SimilarTimes{};
+  if (!ix.ext_ids.p) return fail(VI_ERR_INVALID_INPUT, "this index keeps no external ids");
+  const vi_status s = with_search_context(ix, [&](SearchContext &ctx) { return range_similar_in_context(ix, ctx, io, out); });
+  if (s != VI_OK) (void)hipGetLastError();  // (a failed allocation is this call's failure, not the next call's)
+  return s;
+}
 
 vi_status device_index_search_similar(const DeviceIndex &ix, const SimilarIO &io) {
   g_last_times = SimilarTimes{};

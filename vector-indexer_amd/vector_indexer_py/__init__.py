@@ -629,9 +629,56 @@ class VectorIndex:
                                                         C.c_void_p(tie_ptr) if tie_ptr else None),
                       prefix="Failed to build the k-NN graph: ")
 
+    def range_search_by_ids(self, ids, radius2: float, n_probe: int, exclude_self: bool = True, include_vectors: bool = False,
+                            filter: Optional[AnyFilter] = None):
+        """extension: "which records are within radius2 of the record I hold?" -> (lims u64[n + 1], D f32[total], I
+        i64[total][, V f32[total, dim]], found u32[n]); row i owns [lims[i], lims[i + 1]) and is the radius search of the
+        stored vector of the first record in list order that carries ids[i], that ONE record deleted if exclude_self —
+        records with the same id or the same bits stay.  found[i]: resident records carrying ids[i]; 0: an absent id, an
+        empty row, no error.  Ids may repeat.  Unpartitioned handles only."""
+        a = _native.id_array(ids)
+        n = a.size
+        found = np.zeros(n, dtype=np.uint32)
+        h = C.c_void_p()
+        _native.check(lib().vi_indexer_range_search_by_ids(self._h, _filter_handle(filter), _native.ptr(a) if n else None, n,
+                                                           float(radius2), int(n_probe), 1 if exclude_self else 0,
+                                                           _native.ptr(found), C.byref(h)),
+                      prefix="Failed to range-search by ids: ")
+        res = RangeResult(self, h, n)
+        try:
+            return (*res.copy(include_vectors), found)
+        finally:
+            res.free()
+
+    def range_search_by_ids_device(self, ids_ptr: int, nq: int, radius2: float, n_probe: int, exclude_self: bool = True,
+                                   found_ptr: int = 0, filter: Optional[AnyFilter] = None) -> RangeResult:
+        """... for nq u64 ids in device memory; the result stays there (RangeResult), found u32[nq] is written to
+        found_ptr (0 skips it)"""
+        h = C.c_void_p()
+        _native.check(lib().vi_indexer_range_search_by_ids_device(self._h, _filter_handle(filter),
+                                                                  C.c_void_p(ids_ptr) if ids_ptr else None, int(nq), float(radius2),
+                                                                  int(n_probe), 1 if exclude_self else 0,
+                                                                  C.c_void_p(found_ptr) if found_ptr else None, C.byref(h)),
+                      prefix="Failed to range-search by ids: ")
+        return RangeResult(self, h, nq)
+
+    def radius_graph(self, radius2: float, n_probe: int, first: int = 0, count: Optional[int] = None, exclude_self: bool = True,
+                     filter: Optional[AnyFilter] = None) -> RangeResult:
+        """extension: the radius graph of records [first, first + count) of the list order (count None: to the end), left on
+        the device (RangeResult); row j belongs to the record export() returns as row j, and is what range_search_by_ids
+        gives for it.  Processed in chunks of VI_GRAPH_CHUNK rows (environment; default 65536)."""
+        first = int(first)
+        count = max(self.num_vectors - first, 0) if count is None else int(count)
+        h = C.c_void_p()
+        _native.check(lib().vi_indexer_radius_graph(self._h, _filter_handle(filter), first, count, float(radius2), int(n_probe),
+                                                    1 if exclude_self else 0, C.byref(h)),
+                      prefix="Failed to build the radius graph: ")
+        return RangeResult(self, h, count)
+
     def similar_times(self) -> dict:
-        """this thread's last search_by_ids / knn_graph (any form) under VI_SIMILAR_TIMING: host ms around the gather of
-        the queries and the search, HIP-event ms and bytes of self_drop_kernel, rows per chunk; zeros otherwise"""
+        """this thread's last search_by_ids / knn_graph / range_search_by_ids / radius_graph (any form) under
+        VI_SIMILAR_TIMING: host ms around the gather of the queries and the search, HIP-event ms and bytes of the drop
+        kernels (self_drop_kernel; range_find_kernel + range_move_kernel), rows per chunk; zeros otherwise"""
         r, s, d = C.c_float(0), C.c_float(0), C.c_float(0)
         b, c = C.c_uint64(0), C.c_uint64(0)
         _native.check(lib().vi_similar_last_times(C.byref(r), C.byref(s), C.byref(d), C.byref(b), C.byref(c)))

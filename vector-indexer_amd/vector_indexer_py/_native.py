@@ -182,6 +182,9 @@ SIGNATURES = {
     "vi_indexer_knn_graph": (C.c_int, [vp, vp, u64, u64, u64, u64, u32, vp, vp, vp, C.POINTER(u64)]),
     "vi_indexer_knn_graph_device": (C.c_int, [vp, vp, u64, u64, u64, u64, u32, vp, vp, vp]),
     "vi_similar_last_times": (C.c_int, [C.POINTER(f32), C.POINTER(f32), C.POINTER(f32), C.POINTER(u64), C.POINTER(u64)]),
+    "vi_indexer_range_search_by_ids": (C.c_int, [vp, vp, vp, u64, f32, u64, u32, vp, C.POINTER(vp)]),
+    "vi_indexer_range_search_by_ids_device": (C.c_int, [vp, vp, vp, u64, f32, u64, u32, vp, C.POINTER(vp)]),
+    "vi_indexer_radius_graph": (C.c_int, [vp, vp, u64, u64, f32, u64, u32, C.POINTER(vp)]),
 }
 
 _lib = None

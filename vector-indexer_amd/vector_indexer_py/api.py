@@ -12,6 +12,7 @@
     .upsert_records(records) -> int                                               extension: replace by external id
     .get_records(external_ids) -> [VectorRecord or None]                          extension: read back by external id
     .search_similar(external_id, k, n_probe, ...) -> [SearchResult] or None       extension: neighbours of a stored record
+    .range_search_similar(external_id, radius2, ...) -> [SearchResult] or None    extension: ... within a radius of it
     SearchRequest.with_timestamp_range / .with_allowed_ids / .with_excluded_ids   extension: filtered search
 
 Errors are ViError (a RuntimeError) whose .kind is the io::ErrorKind name the reference returns.
@@ -337,6 +338,30 @@ class VectorIndexer:
             return None
         return [SearchResult(int(I[0, j]), float(D[0, j]), V[0, j].tolist() if V is not None else None)
                 for j in range(int(cnt[0]))]
+
+    def range_search_similar(self, external_id: int, radius2: float, n_probe: Optional[int] = None,
+                             include_vectors: bool = False, exclude_self: bool = True) -> Optional[List[SearchResult]]:
+        """extension: every record of the probed lists within squared distance radius2 of the stored record that carries
+        external_id (the first in list order where several do), nearest first; exclude_self drops that one record — not
+        other records with its id or its vector — from its own result.  None for an id nothing carries.  n_probe None:
+        the config's default_n_probe."""
+        ids = _native.id_array([external_id])
+        p = self._cfg.default_n_probe if n_probe is None else int(n_probe)
+        found = np.zeros(1, dtype=np.uint32)
+        h = C.c_void_p()
+        _native.check(lib().vi_indexer_range_search_by_ids(self._h, None, _native.ptr(ids), 1, float(radius2), p,
+                                                           1 if exclude_self else 0, _native.ptr(found), C.byref(h)))
+        try:
+            n = int(lib().vi_range_result_total(h))
+            lims = np.zeros(2, dtype=np.uint64)
+            D, I = np.zeros(n, dtype=np.float32), np.zeros(n, dtype=np.int64)
+            V = np.zeros((n, self._cfg.dimension), dtype=np.float32) if include_vectors else None
+            _native.check(lib().vi_range_result_copy(h, _native.ptr(lims), _native.ptr(D), _native.ptr(I), _native.ptr(V)))
+        finally:
+            lib().vi_range_result_free(h)
+        if not found[0]:
+            return None
+        return [SearchResult(int(I[j]), float(D[j]), V[j].tolist() if V is not None else None) for j in range(n)]
 
     def search_request(self, query) -> SearchRequest:
         return SearchRequest(list(query), False, self._cfg.default_k, self._cfg.default_n_probe)
