@@ -669,6 +669,65 @@ vi_status vi_indexer_range_search_by_ids_device(const vi_indexer *ix, const vi_f
 vi_status vi_indexer_radius_graph(const vi_indexer *ix, const vi_filter *f, uint64_t first, uint64_t count, float radius2,
                                   uint64_t n_probe, uint32_t exclude_self, vi_range_result **out);
 
+/* ---- extension: clustering the stored records by radius ("which records are copies of each other, which form groups?") --
+ * Connected components and DBSCAN labels of the index's own radius graph, without the graph ever leaving the device or
+ * being held whole: one label and one degree per record.  labels and degree have N = vi_indexer_num_vectors(ix) entries
+ * in LIST ORDER: entry j belongs to the record vi_indexer_export_records returns as row j.  The results are exact.
+ *   Participants: the resident records f admits (f == NULL: all of them).
+ *   Row R(j) of participant j: row j of vi_indexer_radius_graph(ix, f, 0, N, radius2, n_probe, exclude_self = 1), read as
+ *              a set of records (slots) — the reference's candidate sequence for j's stored bits, less what the filter
+ *              does not admit, less j's own slot, cut at d <= radius2 in f32, inclusive.  Rows of non-participants are
+ *              ignored, and no non-participant is a hit: the filter deletes them.
+ *   degree[j]  = |R(j)| for a participant, 0 otherwise.
+ *   Adjacent:  a ~ b iff b is in R(a) or a is in R(b).  The probed lists make rows one-directional in places (a record
+ *              whose own list is not probed is one example); the union closes that.
+ *   Core:      a participant with degree + 1 >= min_pts.  min_pts 0 or 1: every participant.
+ *   Clusters:  the connected components of the core records under ~ restricted to core-core pairs.  The label of a core
+ *              record is the list-order ordinal of the lowest-ordinal record of its component, so labels[j] == j exactly
+ *              for the representatives.
+ *   Border:    a non-core participant adjacent to at least one core record; its label is the label of its adjacent core
+ *              record with the lowest list-order ordinal (classic DBSCAN leaves this to the visiting order; here it is fixed).
+ *   Noise:     every other participant.  Noise and every non-participant get VI_LABEL_NOISE.
+ *   *n_clusters_out = the number of distinct labels >= 0.  It is a host pointer in both forms.
+ * min_pts <= 1 is plain connected components, and radius2 = 0 then gives the groups of exact copies; min_pts >= 2 is
+ * DBSCAN over the index's own approximate neighbourhoods.  labels == 0 .. N-1 elementwise is a vi_indexer_filter_mask;
+ * vi_indexer_retain of it removes every duplicate but one.
+ *   - n_probe is clamped to max_n_probe; 0 is VI_ERR_INVALID_INPUT.  radius2 NaN: VI_ERR_INVALID_INPUT; negative: VI_OK
+ *     with no edges (min_pts <= 1: every participant its own cluster; otherwise all noise); +inf: everything probed is adjacent.
+ *   - any output may be NULL; all three NULL is VI_ERR_INVALID_INPUT
+ *   - VI_ERR_INVALID_INPUT before any device work, the outputs untouched: a null ix, a handle with no index, a filter of
+ *     another handle or of a replaced index, a partitioned handle (world_size > 1)
+ *   - all or nothing: on any later failure the outputs are not written and the handle stays usable; host outputs are
+ *     staged on the device until every chunk has succeeded
+ *   - threads: the contract of a search — the call is const on the handle, holds one search context for the whole call,
+ *     and must not overlap an update.  Labels refer to the list order at call time: an update invalidates them.
+ *   - the rows run in chunks of VI_GRAPH_CHUNK (environment, default 65536) as the graph calls do; no chunk's result
+ *     outlives its chunk.  Beside one chunk's result the call holds 12 bytes and one bit per slot, freed on return.
+ * Cost: every pass searches all N rows.  min_pts <= 1: one pass over the radius graph.  min_pts >= 2 with labels or
+ * n_clusters_out asked for: two passes, degrees first and links second (whether a hit is core is not known until its own
+ * row has been searched).  Only degree_out asked for: one pass.  The edges of the first pass are not kept to save the
+ * second, and the rows of a selective filter are not compacted: all N rows are searched and the rows of non-participants
+ * are skipped in the link step. */
+#define VI_LABEL_NOISE (-1)
+vi_status vi_indexer_cluster_radius(const vi_indexer *ix, const vi_filter *f, float radius2, uint64_t n_probe,
+                                    uint32_t min_pts, int64_t *labels_out, uint32_t *degree_out, uint64_t *n_clusters_out);
+vi_status vi_indexer_cluster_radius_device(const vi_indexer *ix, const vi_filter *f, float radius2, uint64_t n_probe,
+                                           uint32_t min_pts, int64_t *labels_dev, uint32_t *degree_dev, uint64_t *n_clusters_out);
+/* Of the calling thread's last vi_indexer_cluster_radius (either form); zeros after a failed one.  rows: N; hits: the sum
+ * of the degrees; passes: 1 or 2 as above; n_core + n_border + n_noise = the participants; chunk_rows: rows per chunk
+ * used; link_bytes: bytes the degree / link kernels read of the chunks' results, all passes.  With only degree_out asked
+ * for nothing is clustered: n_core, n_border, n_noise and n_clusters are 0.  The ms_* are taken only while the
+ * environment variable VI_SIMILAR_TIMING is set (and not "0"), summed over chunks and passes: host clock around the
+ * gather of the queries (ms_resolve) and the radius search (ms_search), HIP events around cluster_degree_kernel /
+ * cluster_link_kernel (ms_link) and cluster_label_kernel (ms_label). */
+typedef struct vi_cluster_stats {
+  uint64_t rows, hits, passes;
+  uint64_t n_core, n_border, n_noise, n_clusters;
+  uint64_t chunk_rows, link_bytes;
+  float ms_resolve, ms_search, ms_link, ms_label;
+} vi_cluster_stats;
+vi_status vi_cluster_last_stats(vi_cluster_stats *out);
+
 /* Merge `parts` per-rank partial results (each nq x k, device pointers laid out
  * [part][nq][k]) into the global top-k with the reference's stable order. */
 vi_status vi_merge_partials_device(int32_t device, uint64_t nq, uint64_t k, uint32_t parts,

@@ -1310,6 +1310,48 @@ vi_status vi_indexer_radius_graph(const vi_indexer *ix, const vi_filter *f, uint
   });
 }
 
+// ---- clustering the stored records by radius (cluster_radius.hip) ----
+static vi_status cluster_radius_common(const vi_indexer *ix, const vi_filter *f, float radius2, uint64_t n_probe, uint32_t min_pts,
+                                       bool on_device, int64_t *labels, uint32_t *degree, uint64_t *n_clusters) {
+  return vi::guarded([&]() -> vi_status {
+  uint64_t k = 1;
+  VI_TRY(search_common(ix, &k, &n_probe));
+  if (n_probe == 0) return fail(VI_ERR_INVALID_INPUT, "n_probe must be greater than 0");
+  if (std::isnan(radius2)) return fail(VI_ERR_INVALID_INPUT, "radius2 is NaN");
+  if (!labels && !degree && !n_clusters)
+    return fail(VI_ERR_INVALID_INPUT, "null pointer: one of labels, degree and n_clusters_out is required");
+  if (!ix->impl.dev) return fail(VI_ERR_INVALID_INPUT, "the indexer holds no index (build or load it first)");
+  if (ix->impl.cfg.world_size > 1 || ix->impl.dev->stripe_world > 1)
+    return fail(VI_ERR_INVALID_INPUT,
+                "clustering by radius needs the whole index on one handle: a partitioned handle (world_size > 1) holds "
+                "only its part of every neighbourhood");
+  const vi::SlotFilter *flt = nullptr;
+  VI_TRY(filter_common(ix, f, &flt));
+  vi::ClusterIO io;
+  io.on_device = on_device; io.n_probe = n_probe; io.radius2 = radius2; io.min_pts = min_pts; io.filter = flt;
+  io.labels = labels; io.degree = degree; io.n_clusters = n_clusters;
+  return vi::device_index_cluster_radius(*ix->impl.dev, io);
+  });
+}
+
+vi_status vi_indexer_cluster_radius(const vi_indexer *ix, const vi_filter *f, float radius2, uint64_t n_probe,
+                                    uint32_t min_pts, int64_t *labels_out, uint32_t *degree_out, uint64_t *n_clusters_out) {
+  return cluster_radius_common(ix, f, radius2, n_probe, min_pts, false, labels_out, degree_out, n_clusters_out);
+}
+
+vi_status vi_indexer_cluster_radius_device(const vi_indexer *ix, const vi_filter *f, float radius2, uint64_t n_probe,
+                                           uint32_t min_pts, int64_t *labels_dev, uint32_t *degree_dev, uint64_t *n_clusters_out) {
+  return cluster_radius_common(ix, f, radius2, n_probe, min_pts, true, labels_dev, degree_dev, n_clusters_out);
+}
+
+vi_status vi_cluster_last_stats(vi_cluster_stats *out) {
+  return vi::guarded([&]() -> vi_status {
+  if (!out) return fail(VI_ERR_INVALID_INPUT, "null pointer");
+  *out = vi::cluster_last_stats();
+  return VI_OK;
+  });
+}
+
 uint64_t vi_range_result_total(const vi_range_result *r) { return r ? r->impl.total : 0; }
 
 vi_status vi_range_result_copy(const vi_range_result *r, uint64_t *lims, float *D, int64_t *I, float *V) {

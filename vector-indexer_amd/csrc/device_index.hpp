@@ -331,6 +331,23 @@ struct RangeSimilarIO {
 };
 vi_status device_index_range_similar(const DeviceIndex &ix, const RangeSimilarIO &io, RangeResult *out);
 
+// ---- clustering the stored records by radius (cluster_radius.hip): the radius graph consumed chunk by chunk ----
+// One label and one degree per resident record, in list order.  The contract is vi_indexer_cluster_radius in
+// include/vi_amd.h; arguments are checked by the caller (api.cpp): n_probe > 0, radius2 no NaN, an output wanted, an
+// unpartitioned index.  All or nothing: the outputs are written once every chunk of every pass has succeeded.
+struct ClusterIO {
+  bool on_device = false;          // labels and degree are device pointers (n_clusters is a host pointer either way)
+  uint64_t n_probe = 0;
+  float radius2 = 0.0f;
+  uint32_t min_pts = 1;
+  const SlotFilter *filter = nullptr;
+  int64_t *labels = nullptr;       // [nvec_resident], optional
+  uint32_t *degree = nullptr;      // [nvec_resident], optional
+  uint64_t *n_clusters = nullptr;  // host, optional
+};
+vi_status device_index_cluster_radius(const DeviceIndex &ix, const ClusterIO &io);
+vi_cluster_stats cluster_last_stats();  // of this thread's last device_index_cluster_radius; zeros after a failed one
+
 // The search engines' environment options, read once per search by read_engine_knobs (search.hip) into the call's SearchBatch.
 // A '0' as the first character turns an on-by-default option off.  (The MFMA engine's variables keep its first name, VI_FILTER.)
 struct EngineKnobs {

@@ -118,6 +118,9 @@ vi_status with_search_context(const DeviceIndex &ix, Body body) {
 vi_status topk_search(const DeviceIndex &ix, SearchContext &ctx, const SearchIO &io);
 // one radius search in a context the caller holds: what device_index_range_search runs; synchronised on return
 vi_status radius_search(const DeviceIndex &ix, SearchContext &ctx, const RangeIO &io, RangeResult *out);
+// rows per chunk of the calls that walk the stored records through one context (similar_search.hip, cluster_radius.hip):
+// VI_GRAPH_CHUNK or 65 536, inside [1, what the dispatcher takes at rows `width` entries wide]
+uint64_t graph_chunk_rows(uint64_t width);
 // V[r] (row-major, dim floats) = the stored vector of slots[r], zeros for ~0; queued on st
 vi_status launch_gather_vectors(const DeviceIndex &ix, const uint64_t *slots, uint64_t nres, float *V, hipStream_t st);
 

@@ -123,14 +123,6 @@ double now_ms() {
 
 thread_local SimilarTimes g_last_times{};
 
-// rows per chunk: VI_GRAPH_CHUNK or the default, inside [1, what the dispatcher takes at this width]
-uint64_t chunk_rows(uint64_t width) {
-  const char *e = getenv("VI_GRAPH_CHUNK");
-  uint64_t c = (e && *e) ? strtoull(e, nullptr, 10) : kGraphChunkDefault;
-  const uint64_t most = kBatchEntries / std::max<uint64_t>(width, 64);
-  return std::min(std::max<uint64_t>(c, 1), most);
-}
-
 struct DropTimer {  // HIP events around self_drop_kernel, only under VI_SIMILAR_TIMING
   hipEvent_t a = nullptr, b = nullptr;
   ~DropTimer() {
@@ -143,7 +135,7 @@ vi_status similar_in_context(const DeviceIndex &ix, SearchContext &ctx, const Si
   SearchWorkspace &ws = ctx.ws;
   hipStream_t st = ctx.stream;
   const uint64_t k = io.k, kk = k + (io.exclude_self ? 1 : 0), dim = ix.dim;
-  const uint64_t C = chunk_rows(kk);
+  const uint64_t C = graph_chunk_rows(kk);
   const char *tenv = getenv("VI_SIMILAR_TIMING");
   const bool timing = tenv && *tenv && *tenv != '0';
   SimilarTimes tm{};
@@ -312,7 +304,7 @@ vi_status range_similar_in_context(const DeviceIndex &ix, SearchContext &ctx, co
   SearchWorkspace &ws = ctx.ws;
   hipStream_t st = ctx.stream;
   const uint64_t dim = ix.dim;
-  const uint64_t C = chunk_rows(64);
+  const uint64_t C = graph_chunk_rows(64);
   const char *tenv = getenv("VI_SIMILAR_TIMING");
   const bool timing = tenv && *tenv && *tenv != '0';
   SimilarTimes tm{};
@@ -402,6 +394,14 @@ vi_status range_similar_in_context(const DeviceIndex &ix, SearchContext &ctx, co
 }
 
 }  // namespace
+
+// rows per chunk: VI_GRAPH_CHUNK or the default, inside [1, what the dispatcher takes at this width]
+uint64_t graph_chunk_rows(uint64_t width) {
+  const char *e = getenv("VI_GRAPH_CHUNK");
+  uint64_t c = (e && *e) ? strtoull(e, nullptr, 10) : kGraphChunkDefault;
+  const uint64_t most = kBatchEntries / std::max<uint64_t>(width, 64);
+  return std::min(std::max<uint64_t>(c, 1), most);
+}
 
 SimilarTimes similar_last_times() { return g_last_times; }
 

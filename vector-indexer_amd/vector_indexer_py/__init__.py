@@ -675,6 +675,42 @@ class VectorIndex:
                       prefix="Failed to build the radius graph: ")
         return RangeResult(self, h, count)
 
+    def cluster_radius(self, radius2: float, n_probe: int, min_pts: int = 1, filter: Optional[AnyFilter] = None,
+                       with_degree: bool = False):
+        """extension: cluster the stored records by radius -> labels i64[n] (or (labels, degree u32[n])) in LIST ORDER:
+        entry j belongs to the record export() returns as row j.  min_pts <= 1: the connected components of the radius
+        graph (radius2 = 0: the groups of exact copies); min_pts >= 2: DBSCAN over it.  A label is the list-order ordinal
+        of its cluster's first record, so `labels == np.arange(n)` marks one representative per cluster — a filter_mask
+        whose retain() removes every duplicate but one; -1: noise, or a record the filter does not admit.  degree: other
+        records within the radius.  The graph is consumed on the device chunk by chunk and never held whole.
+        cluster_stats()["n_clusters"] has the number of clusters.  Unpartitioned handles only."""
+        n = self.num_vectors
+        labels = np.full(n, -1, dtype=np.int64)
+        degree = np.zeros(n, dtype=np.uint32) if with_degree else None
+        nc = C.c_uint64(0)
+        _native.check(lib().vi_indexer_cluster_radius(self._h, _filter_handle(filter), float(radius2), int(n_probe), int(min_pts),
+                                                      _native.ptr(labels), _native.ptr(degree), C.byref(nc)),
+                      prefix="Failed to cluster by radius: ")
+        return (labels, degree) if with_degree else labels
+
+    def cluster_radius_device(self, labels_ptr: int, degree_ptr: int = 0, radius2: float = 0.0, n_probe: int = 1, min_pts: int = 1,
+                              filter: Optional[AnyFilter] = None) -> int:
+        """... into device memory: labels i64[num_vectors] / degree u32[num_vectors]; a pointer of 0 skips that output.
+        Returns the number of clusters."""
+        nc = C.c_uint64(0)
+        _native.check(lib().vi_indexer_cluster_radius_device(self._h, _filter_handle(filter), float(radius2), int(n_probe),
+                                                             int(min_pts), C.c_void_p(labels_ptr) if labels_ptr else None,
+                                                             C.c_void_p(degree_ptr) if degree_ptr else None, C.byref(nc)),
+                      prefix="Failed to cluster by radius: ")
+        return int(nc.value)
+
+    def cluster_stats(self) -> dict:
+        """this thread's last cluster_radius (either form): rows, hits (the sum of the degrees), passes over the graph,
+        n_core / n_border / n_noise / n_clusters, chunk_rows, link_bytes; the ms_* only under VI_SIMILAR_TIMING"""
+        st = _native.ClusterStats()
+        _native.check(lib().vi_cluster_last_stats(C.byref(st)))
+        return {f: getattr(st, f) for f, _ in st._fields_}
+
     def similar_times(self) -> dict:
         """this thread's last search_by_ids / knn_graph / range_search_by_ids / radius_graph (any form) under
         VI_SIMILAR_TIMING: host ms around the gather of the queries and the search, HIP-event ms and bytes of the drop

@@ -72,6 +72,13 @@ class FetchStats(C.Structure):
                 ("ms_table", f32), ("ms_match", f32), ("ms_gather", f32)]
 
 
+class ClusterStats(C.Structure):
+    """vi_cluster_stats"""
+    _fields_ = [("rows", u64), ("hits", u64), ("passes", u64), ("n_core", u64), ("n_border", u64), ("n_noise", u64),
+                ("n_clusters", u64), ("chunk_rows", u64), ("link_bytes", u64), ("ms_resolve", f32), ("ms_search", f32),
+                ("ms_link", f32), ("ms_label", f32)]
+
+
 class FilterTerm(C.Structure):
     """vi_filter_term: one term of vi_indexer_filter_compose"""
     _fields_ = [("kind", u32), ("negate", u32), ("lo", u64), ("hi", u64), ("data", vp), ("n", u64), ("filter", vp)]
@@ -185,6 +192,9 @@ SIGNATURES = {
     "vi_indexer_range_search_by_ids": (C.c_int, [vp, vp, vp, u64, f32, u64, u32, vp, C.POINTER(vp)]),
     "vi_indexer_range_search_by_ids_device": (C.c_int, [vp, vp, vp, u64, f32, u64, u32, vp, C.POINTER(vp)]),
     "vi_indexer_radius_graph": (C.c_int, [vp, vp, u64, u64, f32, u64, u32, C.POINTER(vp)]),
+    "vi_indexer_cluster_radius": (C.c_int, [vp, vp, f32, u64, u32, vp, vp, C.POINTER(u64)]),
+    "vi_indexer_cluster_radius_device": (C.c_int, [vp, vp, f32, u64, u32, vp, vp, C.POINTER(u64)]),
+    "vi_cluster_last_stats": (C.c_int, [C.POINTER(ClusterStats)]),
 }
 
 _lib = None

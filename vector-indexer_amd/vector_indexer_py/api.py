@@ -13,6 +13,7 @@
     .get_records(external_ids) -> [VectorRecord or None]                          extension: read back by external id
     .search_similar(external_id, k, n_probe, ...) -> [SearchResult] or None       extension: neighbours of a stored record
     .range_search_similar(external_id, radius2, ...) -> [SearchResult] or None    extension: ... within a radius of it
+    .duplicate_groups(radius2=0.0, n_probe, min_size=2) -> [[external_id]]        extension: groups of (near-)copies
     SearchRequest.with_timestamp_range / .with_allowed_ids / .with_excluded_ids   extension: filtered search
 
 Errors are ViError (a RuntimeError) whose .kind is the io::ErrorKind name the reference returns.
@@ -362,6 +363,21 @@ class VectorIndexer:
         if not found[0]:
             return None
         return [SearchResult(int(I[j]), float(D[j]), V[j].tolist() if V is not None else None) for j in range(n)]
+
+    def duplicate_groups(self, radius2: float = 0.0, n_probe: Optional[int] = None, min_size: int = 2) -> List[List[int]]:
+        """extension: the clusters of stored records chained by squared distance <= radius2 (0.0: exact copies) that have
+        at least min_size members, as lists of external ids — members in list order, groups ordered by their first
+        member.  The connected components of the index's radius graph over the probed lists, made on the GPU; only one
+        label per record comes back.  n_probe None: the config's default_n_probe."""
+        p = self._cfg.default_n_probe if n_probe is None else int(n_probe)
+        n = int(lib().vi_indexer_num_vectors(self._h))
+        labels, ids = np.full(n, -1, dtype=np.int64), np.zeros(n, dtype=np.uint64)
+        _native.check(lib().vi_indexer_cluster_radius(self._h, None, float(radius2), p, 1, _native.ptr(labels), None, None))
+        if n:
+            _native.check(lib().vi_indexer_export_records(self._h, 0, n, _native.ptr(ids), None, None, None))
+        order = np.argsort(labels, kind="stable")          # by representative, list order inside a group
+        reps, start, size = np.unique(labels[order], return_index=True, return_counts=True)
+        return [[int(e) for e in ids[order[s:s + c]]] for r, s, c in zip(reps, start, size) if r >= 0 and c >= max(int(min_size), 1)]
 
     def search_request(self, query) -> SearchRequest:
         return SearchRequest(list(query), False, self._cfg.default_k, self._cfg.default_n_probe)
