@@ -242,6 +242,30 @@ def test_chunks_give_identical_arrays(plant, chunk, monkeypatch):
         assert (a // C_ != b // C_).any()        # an edge whose two records are searched in different chunks
 
 
+def test_timing_report_counts_the_consumer_kernels_bytes(plant, monkeypatch):
+    """link_bytes is what cluster_degree_kernel / cluster_link_kernel read and write per pass: 32 bytes per row (its
+    bounds, slot, allow word and degree) and the 8-byte slot of every searched entry — the entries of the radius graph
+    with the record itself kept.  It is counted with or without VI_SIMILAR_TIMING; the four spans only with it."""
+    case = plant
+    g = case.gpu.radius_graph(EPS2, 8, exclude_self=False)
+    T = g.total
+    g.free()
+    monkeypatch.setenv("VI_GRAPH_CHUNK", "4")
+    monkeypatch.setenv("VI_SIMILAR_TIMING", "1")
+    for min_pts, passes in ((1, 1), (2, 2)):
+        case.gpu.cluster_radius(EPS2, 8, min_pts)
+        st = case.gpu.cluster_stats()
+        print("cluster_stats", min_pts, T, st)
+        assert st["passes"] == passes and st["chunk_rows"] == 4, st
+        assert st["link_bytes"] == passes * (case.n * 32 + T * 8), (st, T)
+        assert st["ms_resolve"] > 0 and st["ms_search"] > 0 and st["ms_link"] > 0 and st["ms_label"] > 0, st
+    monkeypatch.delenv("VI_SIMILAR_TIMING")
+    case.gpu.cluster_radius(EPS2, 8, 1)
+    st = case.gpu.cluster_stats()
+    assert st["link_bytes"] == case.n * 32 + T * 8, (st, T)
+    assert st["ms_resolve"] == st["ms_search"] == st["ms_link"] == st["ms_label"] == 0.0, st
+
+
 # ---- 4. composition: the reference applied to the library's own radius graph ----
 @pytest.mark.parametrize("name", ["plant", "plant104", "valu", "bytes8"])
 def test_labels_are_the_reference_applied_to_the_librarys_own_radius_graph(name, request):

@@ -378,6 +378,33 @@ def test_absent_and_repeated_ids(base, hip, monkeypatch):
     assert np.array_equal(lims, le)
 
 
+def test_timing_report_counts_the_drop_kernels_bytes(base, monkeypatch):
+    """VI_SIMILAR_TIMING: drop_bytes is what range_find_kernel and range_move_kernel read and write — 68 bytes per row
+    (its bounds in both results, its slot, count, position and length), the 8-byte slot of every searched entry where the
+    row's own is looked for, and 28 bytes in and 28 out per entry moved; the three spans are measured.  The searched
+    entries are the result of the non-excluding call (every id is present).  Without the variable the spans are 0; the
+    bytes are counted all the same."""
+    fx, n = base, 30
+    ids = fx.ext[fx.rows[:n]]
+    r = float(radii_of(fx)[0]["r10"])
+    monkeypatch.setenv("VI_GRAPH_CHUNK", "4")
+    monkeypatch.setenv("VI_SIMILAR_TIMING", "1")
+    total, tm = {}, {}
+    for exclude in (True, False):
+        lims, _, _, found = fx.gpu.range_search_by_ids(ids, r, 8, exclude_self=exclude)
+        total[exclude], tm[exclude] = int(lims[-1]), fx.gpu.similar_times()
+        print("similar_times", exclude, total[exclude], tm[exclude])
+        assert (found == 1).all() and total[exclude] == int(expected(fx, 8, r, exclude)[0][n])
+        assert tm[exclude]["chunk_rows"] == 4, tm
+        assert tm[exclude]["ms_resolve"] > 0 and tm[exclude]["ms_search"] > 0 and tm[exclude]["ms_drop"] > 0, tm
+    assert tm[True]["drop_bytes"] == n * 68 + total[False] * 8 + total[True] * 56, (tm, total)
+    assert tm[False]["drop_bytes"] == n * 68 + total[False] * 56, (tm, total)
+    monkeypatch.delenv("VI_SIMILAR_TIMING")
+    fx.gpu.range_search_by_ids(ids, r, 8)
+    assert fx.gpu.similar_times() == {"ms_resolve": 0.0, "ms_search": 0.0, "ms_drop": 0.0, "drop_bytes": tm[True]["drop_bytes"],
+                                      "chunk_rows": 4}
+
+
 # ---- 6. with a filter ----
 def test_with_a_filter(base):
     fx, ids = base, base.ext[base.rows]

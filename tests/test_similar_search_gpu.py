@@ -295,34 +295,67 @@ def test_duplicate_ids_and_copied_vectors(dups):
 
 
 # ---- absent and repeated ids ----
-def test_absent_and_repeated_ids(base, hip):
+def test_absent_and_repeated_ids(base, hip, monkeypatch):
     present = base.ext[base.rows[:20]]
     absent = u64([U64_MAX, U64_MAX - 1, (1 << 50) + 12345, 5])
     assert not np.isin(absent, base.ext).any()
-    ids = np.concatenate([present[:7], absent[:2], np.full(5, present[3], dtype=np.uint64), absent[2:], present[7:]])
+    # absent at the first row, in the middle, as a whole chunk of 4 (rows 12..15 at VI_GRAPH_CHUNK 4) and at the last row
+    ids = np.concatenate([absent[:1], present[:6], absent[1:2], np.full(4, present[3], dtype=np.uint64), np.tile(absent[2:3], 4),
+                          present[6:], absent[3:4]])
+    assert np.isin(ids[12:16], absent).all()
     is_absent = np.isin(ids, absent)
-    for exclude in (True, False):
-        for k, p in [(10, 8), (64, 8), (200, 8)]:
-            D, I, counts, found, _, V = raw_by_ids(base.gpu, ids, k, p, exclude, want_v=True)      # VI_OK
-            assert (found == np.where(is_absent, 0, 1)).all() and (counts[is_absent] == 0).all()
-            assert np.isposinf(D[is_absent]).all() and (I[is_absent] == -1).all() and (V[is_absent] == 0).all()
-            De, Ie, ce = base.expected(k, p, exclude)
-            pos = {int(e): i for i, e in enumerate(base.ext[base.rows])}
-            sel = np.array([pos[int(e)] for e in ids[~is_absent]])
-            assert_rows((D[~is_absent], I[~is_absent], counts[~is_absent]), (De[sel], Ie[sel], ce[sel]), f"mixed k {k}")
-            rep = np.nonzero(ids == present[3])[0]
-            assert rep.size == 6 and all(np.array_equal(I[rep[0]], I[r]) and np.array_equal(bits(D[rep[0]]), bits(D[r]))
-                                         and np.array_equal(V[rep[0]], V[r]) for r in rep)
-            # the vectors are the stored vectors of the hits
-            hit = I[~is_absent] >= 0
-            assert np.array_equal(V[~is_absent][hit], base.X[base.rows_of(I[~is_absent][hit])])
-            Dd, Id, Td, Fd = device_by_ids(hip, base.gpu, ids, k, p, exclude)
-            assert np.array_equal(Id, I) and np.array_equal(bits(Dd), bits(D)) and np.array_equal(Fd, found)
-            assert (Td[is_absent] == U64_MAX).all() and (Td[Id == -1] == U64_MAX).all() and (Td[Id >= 0] != U64_MAX).all()
-        D, I, counts, found, _ = raw_by_ids(base.gpu, absent, 10, 8, exclude)   # only absent ids: VI_OK
-        assert np.isposinf(D).all() and (I == -1).all() and (counts == 0).all() and (found == 0).all()
+    pos = {int(e): i for i, e in enumerate(base.ext[base.rows])}
+    sel = np.array([pos[int(e)] for e in ids[~is_absent]])
+    for chunk in ("4", None):
+        if chunk is None:
+            monkeypatch.delenv("VI_GRAPH_CHUNK", raising=False)
+        else:
+            monkeypatch.setenv("VI_GRAPH_CHUNK", chunk)
+        for exclude in (True, False):
+            # (k = 64: k + 1 crosses the engine boundary of the excluding call)
+            for k, p in [(10, 8), (64, 8)] + ([(200, 8)] if chunk is None else []):
+                D, I, counts, found, _, V = raw_by_ids(base.gpu, ids, k, p, exclude, want_v=True)      # VI_OK
+                assert base.gpu.similar_times()["chunk_rows"] == int(chunk or 65536)     # the knob reached the call
+                assert (found == np.where(is_absent, 0, 1)).all() and (counts[is_absent] == 0).all()
+                assert np.isposinf(D[is_absent]).all() and (I[is_absent] == -1).all() and (V[is_absent] == 0).all()
+                De, Ie, ce = base.expected(k, p, exclude)
+                assert_rows((D[~is_absent], I[~is_absent], counts[~is_absent]), (De[sel], Ie[sel], ce[sel]),
+                            f"mixed chunk {chunk} k {k} exclude {exclude}")
+                rep = np.nonzero(ids == present[3])[0]
+                assert rep.size == 5 and all(np.array_equal(I[rep[0]], I[r]) and np.array_equal(bits(D[rep[0]]), bits(D[r]))
+                                             and np.array_equal(V[rep[0]], V[r]) for r in rep)
+                # the vectors are the stored vectors of the hits
+                hit = I[~is_absent] >= 0
+                assert np.array_equal(V[~is_absent][hit], base.X[base.rows_of(I[~is_absent][hit])])
+                Dd, Id, Td, Fd = device_by_ids(hip, base.gpu, ids, k, p, exclude)
+                assert np.array_equal(Id, I) and np.array_equal(bits(Dd), bits(D)) and np.array_equal(Fd, found)
+                assert (Td[is_absent] == U64_MAX).all() and (Td[Id == -1] == U64_MAX).all() and (Td[Id >= 0] != U64_MAX).all()
+            D, I, counts, found, _ = raw_by_ids(base.gpu, absent, 10, 8, exclude)   # only absent ids: VI_OK
+            assert np.isposinf(D).all() and (I == -1).all() and (counts == 0).all() and (found == 0).all()
     D, I, found = base.gpu.search_by_ids(np.zeros(0, dtype=np.uint64), 10, 8)
     assert D.shape == (0, 10) and found.size == 0
+
+
+# ---- the timing report ----
+def test_timing_report_counts_the_drop_kernels_bytes(base, monkeypatch):
+    """VI_SIMILAR_TIMING: drop_bytes is what self_drop_kernel reads and writes per row — D, I and slots of k + 1 entries
+    (20 bytes each), D and I of the k output entries (12 bytes each, 20 with the slots a gather of V needs) and the row's
+    count, slot and found words (16 bytes, the count read and written); the three spans are measured.  Without the
+    variable the spans are 0; the bytes are counted all the same."""
+    n, k = 30, 10
+    ids = base.ext[base.rows[:n]]
+    monkeypatch.setenv("VI_GRAPH_CHUNK", "4")
+    monkeypatch.setenv("VI_SIMILAR_TIMING", "1")
+    for want_v, out_entry in ((False, 12), (True, 20)):
+        raw_by_ids(base.gpu, ids, k, 8, True, want_v=want_v)
+        tm = base.gpu.similar_times()
+        print("similar_times", want_v, tm)
+        assert tm["chunk_rows"] == 4 and tm["drop_bytes"] == n * ((k + 1) * 20 + k * out_entry + 16), tm
+        assert tm["ms_resolve"] > 0 and tm["ms_search"] > 0 and tm["ms_drop"] > 0, tm
+    monkeypatch.delenv("VI_SIMILAR_TIMING")
+    raw_by_ids(base.gpu, ids, k, 8, True)
+    assert base.gpu.similar_times() == {"ms_resolve": 0.0, "ms_search": 0.0, "ms_drop": 0.0,
+                                        "drop_bytes": n * ((k + 1) * 20 + k * 12 + 16), "chunk_rows": 4}
 
 
 # ---- with a filter ----

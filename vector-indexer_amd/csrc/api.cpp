@@ -6,6 +6,7 @@
 
 #include <cmath>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <memory>
 #include <new>
@@ -66,12 +67,6 @@ static vi_status attach_device(Indexer *ix) {
                            dev.get()));
   ix->dev = std::move(dev);
   return VI_OK;
-}
-
-static double now_ms() {
-  struct timeval tv;
-  gettimeofday(&tv, nullptr);
-  return tv.tv_sec * 1e3 + tv.tv_usec * 1e-3;
 }
 
 // IvfIndex::fit_with_paths (src/ivf_index.rs:58-177) + save_to (:274-294).  The points go to the GPU once and stay:
@@ -811,15 +806,20 @@ vi_status vi_indexer_get_records_device(const vi_indexer *ix, const uint64_t *ex
   return get_records_common(ix, ext_ids_dev, n, true, count_dev, values_dev, timestamps_dev, where_dev);
 }
 
+// records [first, first + count) of the list order exist: what every entry that takes such a range checks
+static vi_status record_range_check(uint64_t first, uint64_t count, uint64_t nvec) {
+  if (first > nvec || count > nvec - first)
+    return fail(VI_ERR_INVALID_INPUT, "records [%llu, %llu + %llu) of %llu resident records", (unsigned long long)first,
+                (unsigned long long)first, (unsigned long long)count, (unsigned long long)nvec);
+  return VI_OK;
+}
+
 static vi_status export_records_common(const vi_indexer *ix, uint64_t first, uint64_t count, bool on_device, uint64_t *ext_ids,
                                        float *values, uint64_t *timestamps, uint64_t *where) {
   return vi::guarded([&]() -> vi_status {
   if (!ix) return fail(VI_ERR_INVALID_INPUT, "null indexer");
   if (!ix->impl.dev) return fail(VI_ERR_INVALID_INPUT, "the indexer holds no index (build or load it first)");
-  const uint64_t nvec = ix->impl.dev->nvec_resident;
-  if (first > nvec || count > nvec - first)
-    return fail(VI_ERR_INVALID_INPUT, "records [%llu, %llu + %llu) of %llu resident records", (unsigned long long)first,
-                (unsigned long long)first, (unsigned long long)count, (unsigned long long)nvec);
+  VI_TRY(record_range_check(first, count, ix->impl.dev->nvec_resident));
   if (count == 0) return VI_OK;
   return vi::export_records(*ix->impl.dev, first, count, on_device, ext_ids, values, timestamps, where);
   });
@@ -967,22 +967,35 @@ vi_status vi_indexer_search_probed_device(const vi_indexer *ix, const float *que
                                                   I_dev, tie_dev);
 }
 
-// ---- search by stored record (similar_search.hip) ----
-// The checks common to the four entries, all before any device work; on VI_OK *k and *n_probe are clamped and *flt is set.
-static vi_status similar_common(const vi_indexer *ix, const vi_filter *f, uint64_t nq, bool null_ids, bool null_rows, uint64_t *k,
-                                uint64_t *n_probe, const vi::SlotFilter **flt) {
-  VI_TRY(search_common(ix, k, n_probe));
-  if (*k == 0 || *n_probe == 0) return fail(VI_ERR_INVALID_INPUT, "k and n_probe must be greater than 0");
+// ---- the entries whose queries are stored records (similar_search.hip, cluster_radius.hip) ----
+// The checks they share, all before any device work; on VI_OK *n_probe is clamped and *flt is set.  radius2: 0 where the
+// entry has none.  own: the entry's own argument error, or null; it is reported where the entry always reported it,
+// behind the row checks.  advice: what the entry tells the caller of a partitioned handle to do instead.
+static vi_status stored_record_common(const vi_indexer *ix, const vi_filter *f, uint64_t nq, bool null_ids, uint64_t *n_probe,
+                                      float radius2, const char *own, const char *advice, const vi::SlotFilter **flt) {
+  uint64_t k = 1;
+  VI_TRY(search_common(ix, &k, n_probe));
+  if (*n_probe == 0) return fail(VI_ERR_INVALID_INPUT, "n_probe must be greater than 0");
+  if (std::isnan(radius2)) return fail(VI_ERR_INVALID_INPUT, "radius2 is NaN");
   if (nq > (1ull << 40)) return fail(VI_ERR_INVALID_INPUT, "%llu rows are too many for one call", (unsigned long long)nq);
   if (nq && null_ids) return fail(VI_ERR_INVALID_INPUT, "null id array with nq = %llu", (unsigned long long)nq);
-  if (nq && null_rows) return fail(VI_ERR_INVALID_INPUT, "null pointer: D and I are required");
+  if (own) return fail(VI_ERR_INVALID_INPUT, "%s", own);
   if (!ix->impl.dev) return fail(VI_ERR_INVALID_INPUT, "the indexer holds no index (build or load it first)");
-  if (ix->impl.cfg.world_size > 1 || ix->impl.dev->stripe_world > 1)
-    return fail(VI_ERR_INVALID_INPUT,
-                "search by stored record needs the whole index on one handle; on a partitioned handle call "
-                "vi_indexer_get_records_device on every rank, take the record with the lowest `where`, and search its vector "
-                "with vi_indexer_probe_device / vi_indexer_search_probed_device (the record itself is then not excluded)");
+  if (ix->impl.cfg.world_size > 1 || ix->impl.dev->stripe_world > 1) return fail(VI_ERR_INVALID_INPUT, "%s", advice);
   return filter_common(ix, f, flt);
+}
+
+// search by stored record: the four entries; on VI_OK *k is clamped as well
+static vi_status similar_common(const vi_indexer *ix, const vi_filter *f, uint64_t nq, bool null_ids, bool null_rows, uint64_t *k,
+                                uint64_t *n_probe, const vi::SlotFilter **flt) {
+  VI_TRY(search_common(ix, k, n_probe));  // (the clamps; the shared checks find them made)
+  if (*k == 0 || *n_probe == 0) return fail(VI_ERR_INVALID_INPUT, "k and n_probe must be greater than 0");
+  return stored_record_common(
+      ix, f, nq, null_ids, n_probe, 0.0f, nq && null_rows ? "null pointer: D and I are required" : nullptr,
+      "search by stored record needs the whole index on one handle; on a partitioned handle call "
+      "vi_indexer_get_records_device on every rank, take the record with the lowest `where`, and search its vector "
+      "with vi_indexer_probe_device / vi_indexer_search_probed_device (the record itself is then not excluded)",
+      flt);
 }
 
 static vi_status search_by_ids_common(const vi_indexer *ix, const vi_filter *f, const uint64_t *ids, uint64_t nq, uint64_t k,
@@ -994,7 +1007,7 @@ static vi_status search_by_ids_common(const vi_indexer *ix, const vi_filter *f, 
   if (nq == 0) return VI_OK;  // nothing is read or written
   if (k_out) *k_out = k;
   vi::SimilarIO io;
-  io.ids = ids; io.on_device = on_device; io.nq = nq; io.k = k; io.n_probe = n_probe; io.exclude_self = exclude_self != 0;
+  io.rows.ids = ids; io.rows.on_device = on_device; io.rows.nq = nq; io.k = k; io.n_probe = n_probe; io.exclude_self = exclude_self != 0;
   io.filter = flt; io.D = D; io.I = I; io.tie = tie; io.V = V; io.counts = counts; io.found = found;
   return vi::device_index_search_similar(*ix->impl.dev, io);
   });
@@ -1019,14 +1032,11 @@ static vi_status knn_graph_common(const vi_indexer *ix, const vi_filter *f, uint
   return vi::guarded([&]() -> vi_status {
   const vi::SlotFilter *flt = nullptr;
   VI_TRY(similar_common(ix, f, count, false, !D || !I, &k, &n_probe, &flt));
-  const uint64_t nvec = ix->impl.dev->nvec_resident;
-  if (first > nvec || count > nvec - first)
-    return fail(VI_ERR_INVALID_INPUT, "records [%llu, %llu + %llu) of %llu resident records", (unsigned long long)first,
-                (unsigned long long)first, (unsigned long long)count, (unsigned long long)nvec);
+  VI_TRY(record_range_check(first, count, ix->impl.dev->nvec_resident));
   if (count == 0) return VI_OK;  // nothing is read or written
   if (k_out) *k_out = k;
   vi::SimilarIO io;
-  io.first = first; io.on_device = on_device; io.nq = count; io.k = k; io.n_probe = n_probe; io.exclude_self = exclude_self != 0;
+  io.rows.first = first; io.rows.on_device = on_device; io.rows.nq = count; io.k = k; io.n_probe = n_probe; io.exclude_self = exclude_self != 0;
   io.filter = flt; io.D = D; io.I = I; io.tie = tie; io.counts = counts;
   return vi::device_index_search_similar(*ix->impl.dev, io);
   });
@@ -1206,9 +1216,10 @@ static vi_status range_common(const vi_indexer *ix, const vi_filter *f, const fl
   return VI_OK;
 }
 
-static vi_status range_run(const vi_indexer *ix, const vi::RangeIO &io, vi_range_result **out) {
+// *out = the result run(&result) fills, or nothing: a failed call leaves no result
+static vi_status range_run(vi_range_result **out, const std::function<vi_status(vi::RangeResult *)> &run) {
   auto r = std::make_unique<vi_range_result>();
-  VI_TRY(vi::device_index_range_search(*ix->impl.dev, io, &r->impl));  // (all or nothing: a failed search leaves no result)
+  VI_TRY(run(&r->impl));
   *out = r.release();
   return VI_OK;
 }
@@ -1225,7 +1236,7 @@ vi_status vi_indexer_range_search(const vi_indexer *ix, const vi_filter *f, cons
     if (!std::isfinite(queries[i])) return fail(VI_ERR_PANIC, "non-finite query value at flat index %llu", (unsigned long long)i);
   vi::RangeIO io;
   io.queries = queries; io.nq = nq; io.n_probe = n_probe; io.radius2 = radius2; io.filter = flt;
-  return range_run(ix, io, out);
+  return range_run(out, [&](vi::RangeResult *r) { return vi::device_index_range_search(*ix->impl.dev, io, r); });
   });
 }
 
@@ -1236,37 +1247,23 @@ vi_status vi_indexer_range_search_device(const vi_indexer *ix, const vi_filter *
   VI_TRY(range_common(ix, f, queries_dev, nq, radius2, &n_probe, out, &flt));
   vi::RangeIO io;
   io.queries = queries_dev; io.on_device = true; io.nq = nq; io.n_probe = n_probe; io.radius2 = radius2; io.filter = flt;
-  return range_run(ix, io, out);
+  return range_run(out, [&](vi::RangeResult *r) { return vi::device_index_range_search(*ix->impl.dev, io, r); });
   });
 }
 
 // ---- radius search by stored record (similar_search.hip) ----
-// The checks common to the three entries, all before any device work; on VI_OK *out is NULL, *n_probe clamped, *flt set.
+// The checks of the three entries, all before any device work; on VI_OK *out is NULL, *n_probe clamped, *flt set.
 static vi_status range_similar_common(const vi_indexer *ix, const vi_filter *f, uint64_t nq, bool null_ids, float radius2,
                                       uint64_t *n_probe, vi_range_result **out, const vi::SlotFilter **flt) {
   if (!out) return fail(VI_ERR_INVALID_INPUT, "null pointer: out is required");
   *out = nullptr;
-  uint64_t k = 1;
-  VI_TRY(search_common(ix, &k, n_probe));
-  if (*n_probe == 0) return fail(VI_ERR_INVALID_INPUT, "n_probe must be greater than 0");
-  if (std::isnan(radius2)) return fail(VI_ERR_INVALID_INPUT, "radius2 is NaN");
-  if (nq > (1ull << 40)) return fail(VI_ERR_INVALID_INPUT, "%llu rows are too many for one call", (unsigned long long)nq);
-  if (nq && null_ids) return fail(VI_ERR_INVALID_INPUT, "null id array with nq = %llu", (unsigned long long)nq);
-  if (!ix->impl.dev) return fail(VI_ERR_INVALID_INPUT, "the indexer holds no index (build or load it first)");
-  if (ix->impl.cfg.world_size > 1 || ix->impl.dev->stripe_world > 1)
-    return fail(VI_ERR_INVALID_INPUT,
-                "radius search by stored record needs the whole index on one handle; on a partitioned handle call "
-                "vi_indexer_get_records_device on every rank, take the record with the lowest `where`, search its vector "
-                "with vi_indexer_range_search_device on every rank and merge with vi_range_merge_device (the record itself "
-                "is then not excluded)");
-  return filter_common(ix, f, flt);
-}
-
-static vi_status range_similar_run(const vi_indexer *ix, const vi::RangeSimilarIO &io, vi_range_result **out) {
-  auto r = std::make_unique<vi_range_result>();
-  VI_TRY(vi::device_index_range_similar(*ix->impl.dev, io, &r->impl));  // (all or nothing: a failed call leaves no result)
-  *out = r.release();
-  return VI_OK;
+  return stored_record_common(
+      ix, f, nq, null_ids, n_probe, radius2, nullptr,
+      "radius search by stored record needs the whole index on one handle; on a partitioned handle call "
+      "vi_indexer_get_records_device on every rank, take the record with the lowest `where`, search its vector "
+      "with vi_indexer_range_search_device on every rank and merge with vi_range_merge_device (the record itself "
+      "is then not excluded)",
+      flt);
 }
 
 static vi_status range_by_ids_common(const vi_indexer *ix, const vi_filter *f, const uint64_t *ids, uint64_t nq, float radius2,
@@ -1276,9 +1273,9 @@ static vi_status range_by_ids_common(const vi_indexer *ix, const vi_filter *f, c
   const vi::SlotFilter *flt = nullptr;
   VI_TRY(range_similar_common(ix, f, nq, !ids, radius2, &n_probe, out, &flt));
   vi::RangeSimilarIO io;
-  io.ids = ids; io.on_device = on_device; io.nq = nq; io.n_probe = n_probe; io.radius2 = radius2;
+  io.rows.ids = ids; io.rows.on_device = on_device; io.rows.nq = nq; io.n_probe = n_probe; io.radius2 = radius2;
   io.exclude_self = exclude_self != 0; io.filter = flt; io.found = found;
-  return range_similar_run(ix, io, out);
+  return range_run(out, [&](vi::RangeResult *r) { return vi::device_index_range_similar(*ix->impl.dev, io, r); });
   });
 }
 
@@ -1299,14 +1296,11 @@ vi_status vi_indexer_radius_graph(const vi_indexer *ix, const vi_filter *f, uint
   return vi::guarded([&]() -> vi_status {
   const vi::SlotFilter *flt = nullptr;
   VI_TRY(range_similar_common(ix, f, count, false, radius2, &n_probe, out, &flt));
-  const uint64_t nvec = ix->impl.dev->nvec_resident;
-  if (first > nvec || count > nvec - first)
-    return fail(VI_ERR_INVALID_INPUT, "records [%llu, %llu + %llu) of %llu resident records", (unsigned long long)first,
-                (unsigned long long)first, (unsigned long long)count, (unsigned long long)nvec);
+  VI_TRY(record_range_check(first, count, ix->impl.dev->nvec_resident));
   vi::RangeSimilarIO io;
-  io.first = first; io.nq = count; io.n_probe = n_probe; io.radius2 = radius2; io.exclude_self = exclude_self != 0;
+  io.rows.first = first; io.rows.nq = count; io.n_probe = n_probe; io.radius2 = radius2; io.exclude_self = exclude_self != 0;
   io.filter = flt;
-  return range_similar_run(ix, io, out);
+  return range_run(out, [&](vi::RangeResult *r) { return vi::device_index_range_similar(*ix->impl.dev, io, r); });
   });
 }
 
@@ -1314,19 +1308,13 @@ vi_status vi_indexer_radius_graph(const vi_indexer *ix, const vi_filter *f, uint
 static vi_status cluster_radius_common(const vi_indexer *ix, const vi_filter *f, float radius2, uint64_t n_probe, uint32_t min_pts,
                                        bool on_device, int64_t *labels, uint32_t *degree, uint64_t *n_clusters) {
   return vi::guarded([&]() -> vi_status {
-  uint64_t k = 1;
-  VI_TRY(search_common(ix, &k, &n_probe));
-  if (n_probe == 0) return fail(VI_ERR_INVALID_INPUT, "n_probe must be greater than 0");
-  if (std::isnan(radius2)) return fail(VI_ERR_INVALID_INPUT, "radius2 is NaN");
-  if (!labels && !degree && !n_clusters)
-    return fail(VI_ERR_INVALID_INPUT, "null pointer: one of labels, degree and n_clusters_out is required");
-  if (!ix->impl.dev) return fail(VI_ERR_INVALID_INPUT, "the indexer holds no index (build or load it first)");
-  if (ix->impl.cfg.world_size > 1 || ix->impl.dev->stripe_world > 1)
-    return fail(VI_ERR_INVALID_INPUT,
-                "clustering by radius needs the whole index on one handle: a partitioned handle (world_size > 1) holds "
-                "only its part of every neighbourhood");
   const vi::SlotFilter *flt = nullptr;
-  VI_TRY(filter_common(ix, f, &flt));
+  VI_TRY(stored_record_common(
+      ix, f, 0, false, &n_probe, radius2,
+      !labels && !degree && !n_clusters ? "null pointer: one of labels, degree and n_clusters_out is required" : nullptr,
+      "clustering by radius needs the whole index on one handle: a partitioned handle (world_size > 1) holds "
+      "only its part of every neighbourhood",
+      &flt));
   vi::ClusterIO io;
   io.on_device = on_device; io.n_probe = n_probe; io.radius2 = radius2; io.min_pts = min_pts; io.filter = flt;
   io.labels = labels; io.degree = degree; io.n_clusters = n_clusters;

@@ -2,10 +2,10 @@
 // DBSCAN labels of the index's own radius graph, one label per record in list order.
 //
 // The radius graph of an index is large (28 bytes per hit) and only the input of the job; the answer is 8 bytes per
-// record.  So the graph is never kept: the chunk loop of the radius graph call (similar_search.hip) — resolve a chunk of
-// rows into the search context's query buffer, radius_search them into ws.sim_range — is run here with a consumer in
-// place of find / place / move.  The consumer reads the slots of a chunk's hits and nothing else, and the chunk's result
-// is overwritten by the next chunk's.  Beside one chunk's result the call holds 12 bytes and one bit per slot.
+// record.  So the graph is never kept: every pass walks rows [0, N) as the radius graph call does (StoredRowsWalk,
+// search_internal.hpp) and radius_searches a chunk into ws.sim_range, with a consumer in place of find / place / move.
+// The consumer reads the slots of a chunk's hits and nothing else, and the chunk's result is overwritten by the next
+// chunk's.  Beside one chunk's result the call holds 12 bytes and one bit per slot.
 //
 // Passes over the graph (every pass searches every row again):
 //   min_pts <= 1              one: every participant is core, cluster_link_kernel unites as it counts the degrees
@@ -21,7 +21,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cstdlib>
 #include <vector>
 
@@ -148,39 +147,25 @@ __global__ void __launch_bounds__(256) cluster_label_kernel(LabelArgs a) {
   });
 }
 
-double now_ms() {
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-
 thread_local vi_cluster_stats g_last_stats{};
-
-struct Events {  // HIP events around the consumer kernels, only under VI_SIMILAR_TIMING
-  hipEvent_t ev[4] = {};
-  ~Events() {
-    for (auto &e : ev)
-      if (e) (void)hipEventDestroy(e);
-  }
-};
 
 vi_status cluster_in_context(const DeviceIndex &ix, SearchContext &ctx, const ClusterIO &io) {
   SearchWorkspace &ws = ctx.ws;
   hipStream_t st = ctx.stream;
-  const uint64_t N = ix.nvec_resident, dim = ix.dim, nblocks = ix.lists.nblocks, nslots = nblocks * 64;
-  const uint64_t C = graph_chunk_rows(64);
-  const char *tenv = getenv("VI_SIMILAR_TIMING");
-  const bool timing = tenv && *tenv && *tenv != '0';
+  const uint64_t N = ix.nvec_resident, nblocks = ix.lists.nblocks, nslots = nblocks * 64;
+  StoredRowsWalk walk(64);
   const bool link = io.labels || io.n_clusters;
   const bool two = link && io.min_pts >= 2;
   vi_cluster_stats cs{};
-  cs.rows = N; cs.chunk_rows = C; cs.passes = two ? 2 : 1;
+  cs.rows = N; cs.chunk_rows = walk.chunk_rows; cs.passes = two ? 2 : 1;
   if (N == 0 || nblocks == 0) {  // nothing is resident: no label to write
     if (io.n_clusters) *io.n_clusters = 0;
     g_last_stats = cs;
     return VI_OK;
   }
-  Events ep;
-  if (timing)
-    for (auto &e : ep.ev) VI_HIP(hipEventCreate(&e));
+  enum { kSpanLink, kSpanLabel };  // around the degree / link kernel of a chunk; around the label kernel
+  EventSpans<2> spans;
+  VI_TRY(spans.create(walk.timing));
   VI_TRY(ensure_fetch_layout(ix, st));
   VI_HIP(hipSetDevice(ix.device));
 
@@ -201,7 +186,6 @@ vi_status cluster_in_context(const DeviceIndex &ix, SearchContext &ctx, const Cl
     if (io.labels) { VI_TRY(labels_stage.reserve(N)); labels = labels_stage.p; }
     if (io.degree) { VI_TRY(degree_stage.reserve(N)); degree_out = degree_stage.p; }
   }
-  cs.link_bytes = 0;
   const ResidentLists L{ix.list_first_block.p, ix.list_len.p, (uint32_t)ix.nlists};
   const uint64_t *allow = io.filter ? io.filter->allow.p : nullptr;
   hipLaunchKernelGGL(cluster_init_kernel, dim3(ceil_div_u32(nslots, 256)), dim3(256), 0, st, parent.p, border.p, degree.p, (uint32_t)nslots);
@@ -212,51 +196,43 @@ vi_status cluster_in_context(const DeviceIndex &ix, SearchContext &ctx, const Cl
   RangeIO rio;
   rio.on_device = true; rio.n_probe = io.n_probe; rio.radius2 = io.radius2; rio.filter = io.filter;
   RangeResult &in = ws.sim_range;
+  StoredRows all;  // every resident record, in list order
+  all.nq = N;
   for (uint32_t pass = 0; pass < cs.passes; ++pass) {
     const bool linking = link && pass + 1 == cs.passes;
     if (linking) {  // the core bits: from the degrees of the pass before, or (min_pts <= 1) every participant
       hipLaunchKernelGGL(cluster_core_kernel, slot_walk_grid((uint32_t)ix.nlists), dim3(256), 0, st, L, allow, degree.p, io.min_pts, core.p);
       VI_HIP(hipGetLastError());
     }
-    for (uint64_t q0 = 0; q0 < N; q0 += C) {
-      const uint64_t m = std::min(C, N - q0);
-      // ---- (1) the chunk's queries: stored rows -> ws.q, and their slots ----
-      const double t0 = timing ? now_ms() : 0.0;
-      VI_TRY(ws.q.reserve(m * dim));
-      VI_TRY(ws.self_slot.reserve(m));
-      VI_TRY(resolve_records_by_range(ix, q0, m, ws.q.p, ws.self_slot.p));
-      VI_HIP(hipSetDevice(ix.device));
-      const double t1 = timing ? now_ms() : 0.0;
-      // ---- (2) the radius search of the chunk, into the context's own result ----
-      rio.queries = ws.q.p; rio.nq = m;
+    const auto body = [&](const RowChunk &c) -> vi_status {
+      // ---- the radius search of the chunk, into the context's own result ----
+      rio.queries = ws.q.p; rio.nq = c.m;
       VI_TRY(radius_search(ix, ctx, rio, &in));  // (synchronised)
-      const double t2 = timing ? now_ms() : 0.0;
-      // ---- (3) the chunk's entries are consumed; nothing of them is kept ----
+      c.mark_searched();
+      // ---- the chunk's entries are consumed; nothing of them is kept ----
       // a pass that links in one go counts the degrees as well; the link pass of two leaves them as the first made them
       LinkArgs la{in.lims.p, in.slots.p, ws.self_slot.p, allow, core.p, parent.p, border.p,
-                  linking && two ? nullptr : degree.p, (uint32_t)m, (uint32_t)nslots};
-      const dim3 grid((uint32_t)((m + 3) / 4)), block(256);
-      if (timing) VI_HIP(hipEventRecord(ep.ev[0], st));
+                  linking && two ? nullptr : degree.p, (uint32_t)c.m, (uint32_t)nslots};
+      const dim3 grid((uint32_t)((c.m + 3) / 4)), block(256);
+      VI_TRY(spans.begin(kSpanLink, st));
       if (linking) hipLaunchKernelGGL(cluster_link_kernel, grid, block, 0, st, la);
       else hipLaunchKernelGGL(cluster_degree_kernel, grid, block, 0, st, la);
       VI_HIP(hipGetLastError());
-      if (timing) VI_HIP(hipEventRecord(ep.ev[1], st));
+      VI_TRY(spans.end(kSpanLink, st));
       // a row's bounds, slot and allow word, its degree, and the slot of every entry (parent / border / core words: by need)
-      cs.link_bytes += m * 32 + in.total * 8;
-      VI_HIP(hipStreamSynchronize(st));  // (the next chunk's resolve writes ws.q and ws.self_slot from a stream of its own)
-      if (timing) {
-        cs.ms_resolve += (float)(t1 - t0);
-        cs.ms_search += (float)(t2 - t1);
-        cs.ms_link += elapsed_ms(ep.ev[0], ep.ev[1]);
-      }
-    }
+      cs.link_bytes += c.m * 32 + in.total * 8;
+      return VI_OK;
+    };
+    const auto landed = [&](const RowChunk &) -> vi_status { cs.ms_link += spans.ms(kSpanLink); return VI_OK; };
+    VI_TRY(walk.run(ix, ctx, all, body, landed));
   }
+  cs.ms_resolve = walk.ms_resolve; cs.ms_search = walk.ms_search;
   // ---- labels, degrees and counts, in a launch of its own ----
   LabelArgs ga{L, ix.fetch.prefix.p, core.p, parent.p, border.p, degree.p, labels, degree_out, count.p, link ? 1u : 0u};
-  if (timing) VI_HIP(hipEventRecord(ep.ev[2], st));
+  VI_TRY(spans.begin(kSpanLabel, st));
   hipLaunchKernelGGL(cluster_label_kernel, slot_walk_grid((uint32_t)ix.nlists), dim3(256), 0, st, ga);
   VI_HIP(hipGetLastError());
-  if (timing) VI_HIP(hipEventRecord(ep.ev[3], st));
+  VI_TRY(spans.end(kSpanLabel, st));
   unsigned long long h_count[kCounters] = {};
   VI_HIP(hipMemcpyAsync(h_count, count.p, sizeof(h_count), hipMemcpyDeviceToHost, st));
   VI_HIP(hipStreamSynchronize(st));
@@ -265,7 +241,7 @@ vi_status cluster_in_context(const DeviceIndex &ix, SearchContext &ctx, const Cl
     if (io.degree) VI_HIP(hipMemcpyAsync(io.degree, degree_out, N * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     VI_HIP(hipStreamSynchronize(st));
   }
-  if (timing) cs.ms_label = elapsed_ms(ep.ev[2], ep.ev[3]);
+  cs.ms_label = spans.ms(kSpanLabel);
   const uint64_t participants = io.filter ? io.filter->num_allowed : N;
   cs.hits = h_count[kCountHits];
   if (link) {
@@ -284,11 +260,7 @@ vi_status cluster_in_context(const DeviceIndex &ix, SearchContext &ctx, const Cl
 vi_cluster_stats cluster_last_stats() { return g_last_stats; }
 
 vi_status device_index_cluster_radius(const DeviceIndex &ix, const ClusterIO &io) {
-  g_last_stats = vi_cluster_stats{};
-  if (!ix.ext_ids.p) return fail(VI_ERR_INVALID_INPUT, "this index keeps no external ids");
-  const vi_status s = with_search_context(ix, [&](SearchContext &ctx) { return cluster_in_context(ix, ctx, io); });
-  if (s != VI_OK) (void)hipGetLastError();  // (a failed allocation is this call's failure, not the next call's)
-  return s;
+  return stored_record_call(ix, g_last_stats, [&](SearchContext &ctx) { return cluster_in_context(ix, ctx, io); });
 }
 
 }  // namespace vi

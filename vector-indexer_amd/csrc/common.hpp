@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <chrono>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
@@ -106,6 +107,36 @@ inline float elapsed_ms(hipEvent_t a, hipEvent_t b) {
   (void)hipEventElapsedTime(&ms, a, b);
   return ms;
 }
+
+// the host clock of every ms_* figure that is no HIP-event time
+inline double now_ms() {
+  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+
+// N spans of a stream, each between two HIP events of its own.  The events exist only once create(true) has made them:
+// without them begin / end record nothing and ms is 0.  ms(i) is read once the stream has passed end(i).
+template <int N>
+struct EventSpans {
+  hipEvent_t ev[2 * N] = {};
+  ~EventSpans() {
+    for (auto &e : ev)
+      if (e) (void)hipEventDestroy(e);
+  }
+  vi_status create(bool timing) {
+    if (timing)
+      for (auto &e : ev) VI_HIP(hipEventCreate(&e));
+    return VI_OK;
+  }
+  vi_status begin(int i, hipStream_t st) { return record(2 * i, st); }
+  vi_status end(int i, hipStream_t st) { return record(2 * i + 1, st); }
+  float ms(int i) const { return ev[2 * i + 1] ? elapsed_ms(ev[2 * i], ev[2 * i + 1]) : 0.0f; }
+
+ private:
+  vi_status record(int e, hipStream_t st) {
+    if (ev[e]) VI_HIP(hipEventRecord(ev[e], st));
+    return VI_OK;
+  }
+};
 
 inline uint32_t ceil_div_u32(uint64_t a, uint64_t b) { return (uint32_t)((a + b - 1) / b); }
 

@@ -107,9 +107,11 @@ struct SearchWorkspace {
   DevBuf<uint64_t> total_allowed;           // generic engine with a filter: candidates per query that received a key
   DevBuf<uint32_t> gprobe, off_by_g, off_by_rank;
   DevBuf<uint32_t> range_bound;             // radius search: per query an upper bound of its hits (+ one flag word)
-  // search by stored record (similar_search.hip), per chunk of rows: the slot of each row's record and the number of
-  // records carrying its id; the k-wide rows of a host caller (its k + 1-wide search rows are D / I / tie / slots above)
+  // the walk over stored records (similar_search.hip: StoredRowsWalk), per chunk of rows: their vectors in q above, the
+  // slot of each row's record and the number of records carrying its id — reserved and filled by the walk, read by the
+  // chunk bodies of its three callers
   DevBuf<uint32_t> self_slot, self_found;
+  // search by stored record: the k-wide rows of a host caller (its k + 1-wide search rows are D / I / tie / slots above)
   DevBuf<float> sim_D;
   DevBuf<int64_t> sim_I;
   DevBuf<uint64_t> sim_slots;
@@ -275,16 +277,23 @@ struct SearchIO {
 };
 vi_status device_index_search(const DeviceIndex &ix, const SearchIO &io);
 
-// ---- search by stored record (similar_search.hip): the rows' queries are records of the index itself ----
-// Row i is the top-k of the stored f32 bits of a record: by id — the first record in list order carrying ids[i], the
-// one a get reports — or by range — record first + i of list order.  exclude_self deletes that one record (its slot, not
-// its id, not its bits) from the row's candidates.  The contract is vi_indexer_search_by_ids / vi_indexer_knn_graph in
-// include/vi_amd.h; arguments are checked by the caller (api.cpp): nq > 0, k > 0, n_probe > 0, an unpartitioned index.
-struct SimilarIO {
+// ---- the calls whose queries are records of the index itself (similar_search.hip, cluster_radius.hip) ----
+// The rows of such a call.  Row i is the stored f32 bits of a record: by id — the first record in list order carrying
+// ids[i], the one a get reports — or by range — record first + i of list order.
+struct StoredRows {
   const uint64_t *ids = nullptr;   // by id: nq ids (host, or device with on_device); null: by range
   uint64_t first = 0;              // by range: rows are records [first, first + nq) of list order
-  bool on_device = false;          // ids and every output are device pointers
-  uint64_t nq = 0, k = 0, n_probe = 0;
+  uint64_t nq = 0;
+  bool on_device = false;          // ids and the call's outputs (SimilarIO: every output; RangeSimilarIO: found) are device pointers
+};
+
+// ---- search by stored record (similar_search.hip) ----
+// Row i is the top-k of the record rows names.  exclude_self deletes that one record (its slot, not its id, not its
+// bits) from the row's candidates.  The contract is vi_indexer_search_by_ids / vi_indexer_knn_graph in
+// include/vi_amd.h; arguments are checked by the caller (api.cpp): nq > 0, k > 0, n_probe > 0, an unpartitioned index.
+struct SimilarIO {
+  StoredRows rows;
+  uint64_t k = 0, n_probe = 0;
   bool exclude_self = true;
   const SlotFilter *filter = nullptr;
   float *D = nullptr;              // nq x k
@@ -295,10 +304,10 @@ struct SimilarIO {
   uint32_t *found = nullptr;       // by id, optional: records carrying each id
 };
 vi_status device_index_search_similar(const DeviceIndex &ix, const SimilarIO &io);
-// this thread's last device_index_search_similar under VI_SIMILAR_TIMING (set, not '0'), summed over its chunks: host
-// clock around the resolve + gather of the queries and around the search, HIP events around self_drop_kernel; the bytes
-// that kernel moved and the rows per chunk used.  Zeros otherwise.  device_index_range_similar reports the same way:
-// ms_drop / drop_bytes then cover range_find_kernel and range_move_kernel.
+// this thread's last device_index_search_similar, summed over its chunks: the rows per chunk used and the bytes
+// self_drop_kernel moved; under VI_SIMILAR_TIMING (set, not '0') the host clock around the resolve + gather of the
+// queries and around the search and HIP events around self_drop_kernel, else zeros.  device_index_range_similar reports
+// the same way: ms_drop / drop_bytes then cover range_find_kernel and range_move_kernel.
 struct SimilarTimes { float ms_resolve = 0, ms_search = 0, ms_drop = 0; uint64_t drop_bytes = 0, chunk_rows = 0; };
 SimilarTimes similar_last_times();
 
@@ -315,15 +324,13 @@ vi_status device_index_range_search(const DeviceIndex &ix, const RangeIO &io, Ra
 vi_status range_result_copy(const RangeResult &r, uint64_t *lims, float *D, int64_t *I, float *V);
 
 // ---- radius search by stored record (similar_search.hip): SimilarIO's rows, a RangeResult for the answer ----
-// Row i is the radius search of the stored f32 bits of a record, named as SimilarIO names it; exclude_self deletes that
-// one record (its slot) from the row, an absent id has an empty row.  The contract is vi_indexer_range_search_by_ids /
-// vi_indexer_radius_graph in include/vi_amd.h; arguments are checked by the caller (api.cpp): n_probe > 0, radius2 no
-// NaN, an unpartitioned index.  All or nothing: `found` is written once every chunk has succeeded.
+// Row i is the radius search of the record rows names; exclude_self deletes that one record (its slot) from the row, an
+// absent id has an empty row.  The contract is vi_indexer_range_search_by_ids / vi_indexer_radius_graph in
+// include/vi_amd.h; arguments are checked by the caller (api.cpp): n_probe > 0, radius2 no NaN, an unpartitioned index.
+// All or nothing: `found` is written once every chunk has succeeded.
 struct RangeSimilarIO {
-  const uint64_t *ids = nullptr;   // by id: nq ids (host, or device with on_device); null: by range
-  uint64_t first = 0;              // by range: rows are records [first, first + nq) of list order
-  bool on_device = false;          // ids and found are device pointers
-  uint64_t nq = 0, n_probe = 0;
+  StoredRows rows;
+  uint64_t n_probe = 0;
   float radius2 = 0.0f;
   bool exclude_self = true;
   const SlotFilter *filter = nullptr;

@@ -1,6 +1,6 @@
 // search_internal.hpp — what the search engines' and the index builders' translation units (search.hip, search_kernels.hip,
 // generic_search.hip, filter_search.hip, grouping.hip, select.hip, range_select.hip, rank_images.hip, device_index.hip,
-// list_build.hip, list_update.hip, kmeans.hip, similar_search.hip) call in each other and share: declared once, here.  A search is one
+// list_build.hip, list_update.hip, kmeans.hip, similar_search.hip, cluster_radius.hip) call in each other and share: declared once, here.  A search is one
 // SearchBatch, built by the dispatcher (search.hip) and handed to the engine it chose; the engines hand it on to their
 // stages.  (The probe grouping is called through a header of its own, grouping.hpp; filter_search.hip launches its rank
 // and select phases through rank_stream.hpp and select.hpp.)
@@ -8,6 +8,7 @@
 #include <algorithm>
 #include <array>
 #include <cstdint>
+#include <functional>
 
 #include "device_index.hpp"
 #include "list_layout.hpp"
@@ -118,9 +119,6 @@ vi_status with_search_context(const DeviceIndex &ix, Body body) {
 vi_status topk_search(const DeviceIndex &ix, SearchContext &ctx, const SearchIO &io);
 // one radius search in a context the caller holds: what device_index_range_search runs; synchronised on return
 vi_status radius_search(const DeviceIndex &ix, SearchContext &ctx, const RangeIO &io, RangeResult *out);
-// rows per chunk of the calls that walk the stored records through one context (similar_search.hip, cluster_radius.hip):
-// VI_GRAPH_CHUNK or 65 536, inside [1, what the dispatcher takes at rows `width` entries wide]
-uint64_t graph_chunk_rows(uint64_t width);
 // V[r] (row-major, dim floats) = the stored vector of slots[r], zeros for ~0; queued on st
 vi_status launch_gather_vectors(const DeviceIndex &ix, const uint64_t *slots, uint64_t nres, float *V, hipStream_t st);
 
@@ -129,6 +127,38 @@ vi_status launch_gather_vectors(const DeviceIndex &ix, const uint64_t *slots, ui
 // extends lims by them on the host and the device and grows D / I / tie / slots to hold them, keeping what earlier chunks wrote
 vi_status range_result_begin(const DeviceIndex &ix, uint64_t nq, RangeResult *res);
 vi_status range_result_place(RangeResult *res, uint64_t q0, uint64_t m, const uint32_t *counts_dev, hipStream_t st);
+
+// ---- similar_search.hip: the walk over stored records, for the three calls whose queries are records ----
+// One chunk as its body sees it: rows [q0, q0 + m) are resolved — their vectors in ws.q, their slots in ws.self_slot —
+// and `found` (device, [m]) counts the records carrying each row's id; null for a range.
+struct RowChunk {
+  uint64_t q0, m;
+  const uint32_t *found;
+  void mark_searched() const { if (searched_ms) *searched_ms = now_ms(); }  // the body's search ends here (ms_search)
+  double *searched_ms;  // the walk's; null without timing
+};
+// Rows chunk_rows at a time (VI_GRAPH_CHUNK or 65 536, inside [1, what the dispatcher takes at rows `width` entries
+// wide]) in ascending order through one search context.  run() resolves a chunk, hands it to `body` — its search, its
+// consumer kernels and its copies, queued on ctx.stream — synchronises that stream and calls `landed` (optional), where
+// the caller reads what its copies and events brought back.  timing: VI_SIMILAR_TIMING is set, not '0'.
+using ChunkBody = std::function<vi_status(const RowChunk &)>;
+struct StoredRowsWalk {
+  explicit StoredRowsWalk(uint64_t width);
+  const uint64_t chunk_rows;
+  const bool timing;
+  float ms_resolve = 0, ms_search = 0;  // over every run() of this walk
+  vi_status run(const DeviceIndex &ix, SearchContext &ctx, const StoredRows &rows, const ChunkBody &body, const ChunkBody &landed = nullptr);
+};
+// What the three device_index_* entries of these calls are: `last` (the thread's report of the call) reset, an index
+// without external ids rejected, body(ctx) under with_search_context, and no HIP error left behind by a failure.
+template <class Report, class Body>
+vi_status stored_record_call(const DeviceIndex &ix, Report &last, Body body) {
+  last = Report{};
+  if (!ix.ext_ids.p) return fail(VI_ERR_INVALID_INPUT, "this index keeps no external ids");
+  const vi_status s = with_search_context(ix, body);
+  if (s != VI_OK) (void)hipGetLastError();  // (a failed allocation is this call's failure, not the next call's)
+  return s;
+}
 
 // ---- search_kernels.hip: the exact-order VALU engine ----
 vi_status stage_coarse(SearchBatch &b);                   // ws.probes / gorder and the per-list histogram (ws.cnt)

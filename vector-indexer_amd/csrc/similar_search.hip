@@ -14,14 +14,9 @@
 // every candidate.  Every engine returns the reference's bits; only the time differs.  The one extra candidate is
 // internal: max_k clamps the caller's k, not k + 1.
 //
-// Contexts: the call holds ONE search context for all its chunks and, inside it, one fetch context per chunk for the
-// duration of the resolve — always in that order, search then fetch, and never two of a pool.  A get or an export holds
-// a fetch context alone and waits for nothing else, so the order cannot close a cycle.
-//
-// Chunks: rows are processed C at a time (default 65 536, VI_GRAPH_CHUNK, clamped so that C * max(k + 1, 64) stays
-// inside the dispatcher's 2^31 - 1 entries) in ascending order through the one context, whose workspace is reused.  Rows
-// of a range are in list order, so the queries of a chunk probe the same few lists and the grouping's (list, query
-// group) items stay dense.
+// The rows come chunk by chunk from the walk over stored records (StoredRowsWalk, defined at the end of this file and
+// declared in search_internal.hpp; DESIGN.md "The walk over stored records": the chunk size, the order of the two
+// contexts, the synchronise between chunks, the timing).  cluster_radius.hip is its third caller.
 //
 // The radius form (vi_indexer_range_search_by_ids / vi_indexer_radius_graph) runs the same three steps with ragged rows:
 // the chunk is searched by radius_search (search.hip) into a RangeResult of the context (ws.sim_range),
@@ -31,8 +26,6 @@
 // exact).  Beside the search's workspace a chunk of C rows holds 4 C D bytes of queries, 28 bytes per hit of the
 // intermediate result and 12 bytes per row.
 #include <hip/hip_runtime.h>
-
-#include <sys/time.h>
 
 #include <algorithm>
 #include <cstdlib>
@@ -63,23 +56,27 @@ struct DropArgs {
   uint32_t m, k;
 };
 
-// One wave per row, four rows per workgroup; lanes stride the row, so every access is a coalesced 4- or 8-byte one.  The
-// position s of the row's own entry: a ballot over 64 entries at a time (slots are unique: at most one lane answers).
+// The position of the one entry of slots[in0, in0 + len) that holds `self`, or kSelfDropNoMatch: a ballot over 64 entries
+// at a time (slots are unique: at most one lane answers, and the search ends there).  A whole wave calls it with the same
+// in0, len and self, so the loop bound is wave-uniform and the ballot sees all 64 lanes.
+__device__ __forceinline__ uint32_t find_self_entry(const uint64_t *slots, uint64_t in0, uint32_t len, uint64_t self, uint32_t lane) {
+  uint32_t s = kSelfDropNoMatch;
+  for (uint32_t j0 = 0; j0 < len && s == kSelfDropNoMatch; j0 += 64u) {
+    const uint32_t j = j0 + lane;
+    const uint64_t hit = __ballot(j < len && slots[in0 + j] == self);
+    if (hit) s = j0 + (uint32_t)__ffsll((unsigned long long)hit) - 1u;
+  }
+  return s;
+}
+
+// One wave per row, four rows per workgroup; lanes stride the row, so every access is a coalesced 4- or 8-byte one.
 __global__ void __launch_bounds__(256) self_drop_kernel(DropArgs a) {
   const uint32_t row = blockIdx.x * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
   if (row >= a.m) return;  // (wave-uniform)
   const uint32_t k = a.k, kin = k + 1u;
   const uint64_t in0 = (uint64_t)row * kin, out0 = (uint64_t)row * k;
   const bool absent = a.found && self_drop_row_absent(a.found[row]);
-  uint32_t s = kSelfDropNoMatch;
-  if (!absent) {
-    const uint64_t self = a.self_slot[row];
-    for (uint32_t j0 = 0; j0 < kin && s == kSelfDropNoMatch; j0 += 64u) {
-      const uint32_t j = j0 + lane;
-      const uint64_t hit = __ballot(j < kin && a.slots_in[in0 + j] == self);
-      if (hit) s = j0 + (uint32_t)__ffsll((unsigned long long)hit) - 1u;
-    }
-  }
+  const uint32_t s = absent ? kSelfDropNoMatch : find_self_entry(a.slots_in, in0, kin, a.self_slot[row], lane);
   const uint32_t n_in = absent ? 0u : a.counts[row];
   for (uint32_t j = lane; j < k; j += 64u) {
     float d = INFINITY;
@@ -115,57 +112,34 @@ __global__ void __launch_bounds__(256) absent_pad_kernel(const uint32_t *found, 
   if (lane == 0) counts[row] = 0u;
 }
 
-double now_ms() {
-  struct timeval tv;
-  gettimeofday(&tv, nullptr);
-  return tv.tv_sec * 1e3 + tv.tv_usec * 1e-3;
-}
-
 thread_local SimilarTimes g_last_times{};
 
-struct DropTimer {  // HIP events around self_drop_kernel, only under VI_SIMILAR_TIMING
-  hipEvent_t a = nullptr, b = nullptr;
-  ~DropTimer() {
-    if (a) (void)hipEventDestroy(a);
-    if (b) (void)hipEventDestroy(b);
-  }
-};
+// the thread's report of a call that went through: the walk's figures beside the caller's ms_drop and drop_bytes
+void report_times(SimilarTimes tm, const StoredRowsWalk &walk) {
+  tm.ms_resolve = walk.ms_resolve; tm.ms_search = walk.ms_search; tm.chunk_rows = walk.chunk_rows;
+  g_last_times = tm;
+}
 
 vi_status similar_in_context(const DeviceIndex &ix, SearchContext &ctx, const SimilarIO &io) {
   SearchWorkspace &ws = ctx.ws;
   hipStream_t st = ctx.stream;
+  const bool on_device = io.rows.on_device;
   const uint64_t k = io.k, kk = k + (io.exclude_self ? 1 : 0), dim = ix.dim;
-  const uint64_t C = graph_chunk_rows(kk);
-  const char *tenv = getenv("VI_SIMILAR_TIMING");
-  const bool timing = tenv && *tenv && *tenv != '0';
+  StoredRowsWalk walk(kk);
+  EventSpans<1> drop;  // around self_drop_kernel
+  VI_TRY(drop.create(walk.timing));
   SimilarTimes tm{};
-  tm.chunk_rows = C;
-  DropTimer dt;
-  if (timing) { VI_HIP(hipEventCreate(&dt.a)); VI_HIP(hipEventCreate(&dt.b)); }
   const bool want_slots = io.V != nullptr;        // of the caller's rows
-  const bool want_tie = io.on_device && io.tie;
+  const bool want_tie = on_device && io.tie;
   std::vector<uint32_t> h32;
 
-  for (uint64_t q0 = 0; q0 < io.nq; q0 += C) {
-    const uint64_t m = std::min(C, io.nq - q0);
-    // ---- (1) the chunk's queries: stored rows -> ws.q, their slots, the records carrying each id ----
-    const double t0 = timing ? now_ms() : 0.0;
-    VI_TRY(ws.q.reserve(m * dim));
-    VI_TRY(ws.self_slot.reserve(m));
-    if (io.ids) {
-      VI_TRY(ws.self_found.reserve(m));
-      VI_TRY(resolve_records_by_id(ix, io.ids + q0, m, io.on_device, ws.self_found.p, ws.q.p, ws.self_slot.p));
-    } else {
-      VI_TRY(resolve_records_by_range(ix, io.first + q0, m, ws.q.p, ws.self_slot.p));
-    }
-    const uint32_t *found = io.ids ? ws.self_found.p : nullptr;
-    VI_HIP(hipSetDevice(ix.device));
-    const double t1 = timing ? now_ms() : 0.0;
-    // ---- (2) the search: k + 1 wide into the workspace when the record itself goes, else into the caller's rows ----
+  const auto body = [&](const RowChunk &c) -> vi_status {
+    const uint64_t q0 = c.q0, m = c.m;
+    // ---- the search: k + 1 wide into the workspace when the record itself goes, else into the caller's rows ----
     float *D = io.D + q0 * k;  // the caller's rows of this chunk, on the device
     int64_t *I = io.I + q0 * k;
     uint64_t *tie = want_tie ? io.tie + q0 * k : nullptr, *slots = nullptr;
-    if (!io.on_device) {
+    if (!on_device) {
       VI_TRY(ws.sim_D.reserve(m * k));
       VI_TRY(ws.sim_I.reserve(m * k));
       D = ws.sim_D.p; I = ws.sim_I.p;
@@ -184,26 +158,26 @@ vi_status similar_in_context(const DeviceIndex &ix, SearchContext &ctx, const Si
     }
     VI_TRY(topk_search(ix, ctx, sio));  // (synchronised; ws.counts holds the rows' counts)
     ctx.stats.k = k;                    // the caller's k, not k + 1
-    const double t2 = timing ? now_ms() : 0.0;
-    // ---- (3) the caller's rows ----
+    c.mark_searched();
+    // ---- the caller's rows ----
     const dim3 grid((uint32_t)((m + 3) / 4)), block(256);
     if (io.exclude_self) {
-      DropArgs a{ws.D.p, ws.I.p, sio.tie, ws.slots.p, ws.counts.p, ws.self_slot.p, found, D, I, tie, slots, (uint32_t)m, (uint32_t)k};
-      if (timing) VI_HIP(hipEventRecord(dt.a, st));
+      DropArgs a{ws.D.p, ws.I.p, sio.tie, ws.slots.p, ws.counts.p, ws.self_slot.p, c.found, D, I, tie, slots, (uint32_t)m, (uint32_t)k};
+      VI_TRY(drop.begin(0, st));
       hipLaunchKernelGGL(self_drop_kernel, grid, block, 0, st, a);
       VI_HIP(hipGetLastError());
-      if (timing) VI_HIP(hipEventRecord(dt.b, st));
+      VI_TRY(drop.end(0, st));
       // read: D, I, slots (and tie) of k + 1 entries, the three words per row; written: the caller's k entries
       tm.drop_bytes += m * (kk * (20 + (want_tie ? 8 : 0)) + k * (12 + (want_tie ? 8 : 0) + (want_slots ? 8 : 0)) + 16);
-    } else if (found) {
-      hipLaunchKernelGGL(absent_pad_kernel, grid, block, 0, st, found, D, I, tie, slots, ws.counts.p, (uint32_t)m, (uint32_t)k);
+    } else if (c.found) {
+      hipLaunchKernelGGL(absent_pad_kernel, grid, block, 0, st, c.found, D, I, tie, slots, ws.counts.p, (uint32_t)m, (uint32_t)k);
       VI_HIP(hipGetLastError());
     }
-    if (io.found && io.on_device) VI_HIP(hipMemcpyAsync(io.found + q0, found, m * 4, hipMemcpyDeviceToDevice, st));
-    if (!io.on_device) {
+    if (io.found && on_device) VI_HIP(hipMemcpyAsync(io.found + q0, c.found, m * 4, hipMemcpyDeviceToDevice, st));
+    if (!on_device) {
       VI_HIP(hipMemcpyAsync(io.D + q0 * k, D, m * k * sizeof(float), hipMemcpyDeviceToHost, st));
       VI_HIP(hipMemcpyAsync(io.I + q0 * k, I, m * k * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-      if (io.found) VI_HIP(hipMemcpyAsync(io.found + q0, found, m * 4, hipMemcpyDeviceToHost, st));
+      if (io.found) VI_HIP(hipMemcpyAsync(io.found + q0, c.found, m * 4, hipMemcpyDeviceToHost, st));
       if (io.V) {
         VI_TRY(ws.V.reserve(m * k * dim));
         VI_TRY(launch_gather_vectors(ix, slots, m * k, ws.V.p, st));
@@ -214,16 +188,16 @@ vi_status similar_in_context(const DeviceIndex &ix, SearchContext &ctx, const Si
         VI_HIP(hipMemcpyAsync(h32.data(), ws.counts.p, m * 4, hipMemcpyDeviceToHost, st));
       }
     }
-    VI_HIP(hipStreamSynchronize(st));  // (the next chunk's resolve writes ws.q and ws.self_slot from a stream of its own)
-    if (!io.on_device && io.counts)
-      for (uint64_t i = 0; i < m; ++i) io.counts[q0 + i] = h32[i];
-    if (timing) {
-      tm.ms_resolve += (float)(t1 - t0);
-      tm.ms_search += (float)(t2 - t1);
-      if (io.exclude_self) tm.ms_drop += elapsed_ms(dt.a, dt.b);
-    }
-  }
-  g_last_times = tm;
+    return VI_OK;
+  };
+  const auto landed = [&](const RowChunk &c) -> vi_status {
+    if (!on_device && io.counts)
+      for (uint64_t i = 0; i < c.m; ++i) io.counts[c.q0 + i] = h32[i];
+    if (io.exclude_self) tm.ms_drop += drop.ms(0);
+    return VI_OK;
+  };
+  VI_TRY(walk.run(ix, ctx, io.rows, body, landed));
+  report_times(tm, walk);
   return VI_OK;
 }
 
@@ -237,23 +211,14 @@ struct RangeFindArgs {
   uint32_t m, exclude;
 };
 
-// One wave per row, four rows per workgroup.  The row's slots are searched 64 at a time by ballot (slots are unique: at
-// most one lane answers, and the search ends there); without exclusion nothing is read but the row's bounds.
+// One wave per row, four rows per workgroup.  Without exclusion nothing is read but the row's bounds.
 __global__ void __launch_bounds__(256) range_find_kernel(RangeFindArgs a) {
   const uint32_t row = blockIdx.x * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
   if (row >= a.m) return;  // (wave-uniform)
   const bool absent = a.found && self_drop_row_absent(a.found[row]);
   const uint64_t in0 = a.in_lims[row];
   const uint32_t len = (uint32_t)(a.in_lims[row + 1] - in0);  // (a chunk holds fewer than 2^31 entries)
-  uint32_t s = kSelfDropNoMatch;
-  if (a.exclude && !absent) {
-    const uint64_t self = a.self_pos[row];
-    for (uint32_t j0 = 0; j0 < len && s == kSelfDropNoMatch; j0 += 64u) {
-      const uint32_t j = j0 + lane;
-      const uint64_t hit = __ballot(j < len && a.in_slots[in0 + j] == self);
-      if (hit) s = j0 + (uint32_t)__ffsll((unsigned long long)hit) - 1u;
-    }
-  }
+  const uint32_t s = a.exclude && !absent ? find_self_entry(a.in_slots, in0, len, a.self_pos[row], lane) : kSelfDropNoMatch;
   if (lane == 0) {
     a.self_pos[row] = s;
     a.len[row] = range_drop_len(len, s != kSelfDropNoMatch, absent);
@@ -292,108 +257,78 @@ __global__ void __launch_bounds__(256) range_move_kernel(RangeMoveArgs a) {
   }
 }
 
-struct EventPairs {  // HIP events around the two kernels, only under VI_SIMILAR_TIMING
-  hipEvent_t ev[4] = {};
-  ~EventPairs() {
-    for (auto &e : ev)
-      if (e) (void)hipEventDestroy(e);
-  }
-};
-
 vi_status range_similar_in_context(const DeviceIndex &ix, SearchContext &ctx, const RangeSimilarIO &io, RangeResult *out) {
   SearchWorkspace &ws = ctx.ws;
   hipStream_t st = ctx.stream;
-  const uint64_t dim = ix.dim;
-  const uint64_t C = graph_chunk_rows(64);
-  const char *tenv = getenv("VI_SIMILAR_TIMING");
-  const bool timing = tenv && *tenv && *tenv != '0';
+  const StoredRows &rows = io.rows;
+  StoredRowsWalk walk(64);
+  EventSpans<2> drop;  // around range_find_kernel and around range_move_kernel: not range_result_place between them
+  VI_TRY(drop.create(walk.timing));
   SimilarTimes tm{};
-  tm.chunk_rows = C;
-  EventPairs ep;
-  if (timing)
-    for (auto &e : ep.ev) VI_HIP(hipEventCreate(&e));
   RangeIO rio;
   rio.on_device = true; rio.n_probe = io.n_probe; rio.radius2 = io.radius2; rio.filter = io.filter;
-  if (io.nq == 0) {  // an empty result, made as a radius search of no query makes it
+  if (rows.nq == 0) {  // an empty result, made as a radius search of no query makes it
     VI_TRY(radius_search(ix, ctx, rio, out));
     VI_HIP(hipStreamSynchronize(st));
-    g_last_times = tm;
+    report_times(tm, walk);
     return VI_OK;
   }
   // found is the caller's only once every chunk has succeeded: until then it is kept here
-  const bool want_found = io.found && io.ids;
+  const bool want_found = io.found && rows.ids;
   std::vector<uint32_t> h_found;
   DevBuf<uint32_t> d_found;
-  if (want_found && !io.on_device) h_found.resize(io.nq);
-  if (want_found && io.on_device && io.nq > C) VI_TRY(d_found.reserve(io.nq));
+  if (want_found && !rows.on_device) h_found.resize(rows.nq);
+  if (want_found && rows.on_device && rows.nq > walk.chunk_rows) VI_TRY(d_found.reserve(rows.nq));
 
   RangeResult &in = ws.sim_range;
-  VI_TRY(range_result_begin(ix, io.nq, out));
-  for (uint64_t q0 = 0; q0 < io.nq; q0 += C) {
-    const uint64_t m = std::min(C, io.nq - q0);
-    // ---- (1) the chunk's queries: stored rows -> ws.q, their slots, the records carrying each id ----
-    const double t0 = timing ? now_ms() : 0.0;
-    VI_TRY(ws.q.reserve(m * dim));
-    VI_TRY(ws.self_slot.reserve(m));
+  VI_TRY(range_result_begin(ix, rows.nq, out));
+  const auto body = [&](const RowChunk &c) -> vi_status {
+    const uint64_t q0 = c.q0, m = c.m;
+    // ---- the radius search of the chunk, into the context's own result ----
     VI_TRY(ws.sim_len.reserve(m));
-    if (io.ids) {
-      VI_TRY(ws.self_found.reserve(m));
-      VI_TRY(resolve_records_by_id(ix, io.ids + q0, m, io.on_device, ws.self_found.p, ws.q.p, ws.self_slot.p));
-    } else {
-      VI_TRY(resolve_records_by_range(ix, io.first + q0, m, ws.q.p, ws.self_slot.p));
-    }
-    const uint32_t *found = io.ids ? ws.self_found.p : nullptr;
-    VI_HIP(hipSetDevice(ix.device));
-    const double t1 = timing ? now_ms() : 0.0;
-    // ---- (2) the radius search of the chunk, into the context's own result ----
     rio.queries = ws.q.p; rio.nq = m;
     VI_TRY(radius_search(ix, ctx, rio, &in));  // (synchronised)
-    const double t2 = timing ? now_ms() : 0.0;
-    // ---- (3) every row's own entry and its output length ----
+    c.mark_searched();
+    // ---- every row's own entry and its output length ----
     const dim3 grid((uint32_t)((m + 3) / 4)), block(256);
-    RangeFindArgs fa{in.lims.p, in.slots.p, ws.self_slot.p, found, ws.sim_len.p, (uint32_t)m, io.exclude_self ? 1u : 0u};
-    if (timing) VI_HIP(hipEventRecord(ep.ev[0], st));
+    RangeFindArgs fa{in.lims.p, in.slots.p, ws.self_slot.p, c.found, ws.sim_len.p, (uint32_t)m, io.exclude_self ? 1u : 0u};
+    VI_TRY(drop.begin(0, st));
     hipLaunchKernelGGL(range_find_kernel, grid, block, 0, st, fa);
     VI_HIP(hipGetLastError());
-    if (timing) VI_HIP(hipEventRecord(ep.ev[1], st));
-    // ---- (4) the caller's result extended by the chunk's rows ----
+    VI_TRY(drop.end(0, st));
+    // ---- the caller's result extended by the chunk's rows ----
     VI_TRY(range_result_place(out, q0, m, ws.sim_len.p, st));
-    // ---- (5) the entries ----
+    // ---- the entries ----
     const uint64_t moved = out->h_lims[q0 + m] - out->h_lims[q0];
-    if (timing) VI_HIP(hipEventRecord(ep.ev[2], st));
+    VI_TRY(drop.begin(1, st));
     if (moved) {
       RangeMoveArgs ma{in.lims.p, out->lims.p + q0, ws.self_slot.p, in.D.p, in.I.p, in.tie.p, in.slots.p,
                        out->D.p, out->I.p, out->tie.p, out->slots.p, (uint32_t)m};
       hipLaunchKernelGGL(range_move_kernel, grid, block, 0, st, ma);
       VI_HIP(hipGetLastError());
     }
-    if (timing) VI_HIP(hipEventRecord(ep.ev[3], st));
+    VI_TRY(drop.end(1, st));
     // find: a row's bounds, slot, count, position and length, and (at most) its slots; move: bounds and position, 28
     // bytes per entry in and out
     tm.drop_bytes += m * 32 + (io.exclude_self ? in.total * 8 : 0) + m * 36 + moved * 56;
     if (want_found) {
-      if (!io.on_device) VI_HIP(hipMemcpyAsync(h_found.data() + q0, found, m * 4, hipMemcpyDeviceToHost, st));
-      else if (d_found.p) VI_HIP(hipMemcpyAsync(d_found.p + q0, found, m * 4, hipMemcpyDeviceToDevice, st));
+      if (!rows.on_device) VI_HIP(hipMemcpyAsync(h_found.data() + q0, c.found, m * 4, hipMemcpyDeviceToHost, st));
+      else if (d_found.p) VI_HIP(hipMemcpyAsync(d_found.p + q0, c.found, m * 4, hipMemcpyDeviceToDevice, st));
     }
-    VI_HIP(hipStreamSynchronize(st));  // (the next chunk's resolve writes ws.q and ws.self_slot from a stream of its own)
-    if (timing) {
-      tm.ms_resolve += (float)(t1 - t0);
-      tm.ms_search += (float)(t2 - t1);
-      tm.ms_drop += elapsed_ms(ep.ev[0], ep.ev[1]) + elapsed_ms(ep.ev[2], ep.ev[3]);
-    }
-  }
+    return VI_OK;
+  };
+  const auto landed = [&](const RowChunk &) -> vi_status { tm.ms_drop += drop.ms(0) + drop.ms(1); return VI_OK; };
+  VI_TRY(walk.run(ix, ctx, rows, body, landed));
   if (want_found) {
-    if (!io.on_device) std::copy(h_found.begin(), h_found.end(), io.found);
+    if (!rows.on_device) std::copy(h_found.begin(), h_found.end(), io.found);
     else {
-      VI_HIP(hipMemcpyAsync(io.found, d_found.p ? d_found.p : ws.self_found.p, io.nq * 4, hipMemcpyDeviceToDevice, st));
+      VI_HIP(hipMemcpyAsync(io.found, d_found.p ? d_found.p : ws.self_found.p, rows.nq * 4, hipMemcpyDeviceToDevice, st));
       VI_HIP(hipStreamSynchronize(st));
     }
   }
-  g_last_times = tm;
+  report_times(tm, walk);
   return VI_OK;
 }
-
-}  // namespace
 
 // rows per chunk: VI_GRAPH_CHUNK or the default, inside [1, what the dispatcher takes at this width]
 uint64_t graph_chunk_rows(uint64_t width) {
@@ -403,20 +338,51 @@ uint64_t graph_chunk_rows(uint64_t width) {
   return std::min(std::max<uint64_t>(c, 1), most);
 }
 
+bool similar_timing() {
+  const char *e = getenv("VI_SIMILAR_TIMING");
+  return e && *e && *e != '0';
+}
+
+}  // namespace
+
+StoredRowsWalk::StoredRowsWalk(uint64_t width) : chunk_rows(graph_chunk_rows(width)), timing(similar_timing()) {}
+
+vi_status StoredRowsWalk::run(const DeviceIndex &ix, SearchContext &ctx, const StoredRows &rows, const ChunkBody &body,
+                              const ChunkBody &landed) {
+  SearchWorkspace &ws = ctx.ws;
+  for (uint64_t q0 = 0; q0 < rows.nq; q0 += chunk_rows) {
+    const uint64_t m = std::min(chunk_rows, rows.nq - q0);
+    // the chunk's queries: stored rows -> ws.q, their slots, the records carrying each id
+    const double t0 = timing ? now_ms() : 0.0;
+    VI_TRY(ws.q.reserve(m * ix.dim));
+    VI_TRY(ws.self_slot.reserve(m));
+    if (rows.ids) {
+      VI_TRY(ws.self_found.reserve(m));
+      VI_TRY(resolve_records_by_id(ix, rows.ids + q0, m, rows.on_device, ws.self_found.p, ws.q.p, ws.self_slot.p));
+    } else {
+      VI_TRY(resolve_records_by_range(ix, rows.first + q0, m, ws.q.p, ws.self_slot.p));
+    }
+    VI_HIP(hipSetDevice(ix.device));
+    double t1 = timing ? now_ms() : 0.0, t2 = t1;
+    const RowChunk chunk{q0, m, rows.ids ? ws.self_found.p : nullptr, timing ? &t2 : nullptr};
+    VI_TRY(body(chunk));
+    // the next chunk's resolve writes ws.q and ws.self_slot from a stream of its own: this chunk's readers end first
+    VI_HIP(hipStreamSynchronize(ctx.stream));
+    ms_resolve += (float)(t1 - t0);
+    ms_search += (float)(t2 - t1);
+    if (landed) VI_TRY(landed(chunk));
+  }
+  return VI_OK;
+}
+
 SimilarTimes similar_last_times() { return g_last_times; }
 
 vi_status device_index_range_similar(const DeviceIndex &ix, const RangeSimilarIO &io, RangeResult *out) {
-  g_last_times = SimilarTimes{};
-  if (!ix.ext_ids.p) return fail(VI_ERR_INVALID_INPUT, "this index keeps no external ids");
-  const vi_status s = with_search_context(ix, [&](SearchContext &ctx) { return range_similar_in_context(ix, ctx, io, out); });
-  if (s != VI_OK) (void)hipGetLastError();  // (a failed allocation is this call's failure, not the next call's)
-  return s;
+  return stored_record_call(ix, g_last_times, [&](SearchContext &ctx) { return range_similar_in_context(ix, ctx, io, out); });
 }
 
 vi_status device_index_search_similar(const DeviceIndex &ix, const SimilarIO &io) {
-  g_last_times = SimilarTimes{};
-  if (!ix.ext_ids.p) return fail(VI_ERR_INVALID_INPUT, "this index keeps no external ids");
-  return with_search_context(ix, [&](SearchContext &ctx) { return similar_in_context(ix, ctx, io); });
+  return stored_record_call(ix, g_last_times, [&](SearchContext &ctx) { return similar_in_context(ix, ctx, io); });
 }
 
 }  // namespace vi
