@@ -585,9 +585,7 @@ __global__ void __launch_bounds__(256) cand_exact_kernel(const float *X, uint32_
     if (keep) s_keep[grp][kept + (uint32_t)__popc(bits & ((1u << l) - 1u))] = e;
     kept += (uint32_t)__popc(bits);
   }
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  wave_lds_sync();
   float best = INFINITY;
   uint32_t bc = 0xFFFFFFFFu;
   uint32_t tmax = kept;  // (the wave's eight points go round together)

@@ -1,5 +1,5 @@
 // device_math.hpp — exact-order squared-L2 device functions (must be compiled with
-// -ffp-contract=off; a fused multiply-add changes the rounding of acc + t*t).
+// -ffp-contract=off; a fused multiply-add changes the rounding of acc + t*t), and the wave's LDS fence.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -8,6 +8,13 @@
 #include "../../include/vi_reduce_order.h"
 
 namespace vi {
+
+// what one lane wrote to the wave's LDS, visible to the others
+__device__ __forceinline__ void wave_lds_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
 
 __device__ __forceinline__ void sq_add(float &acc, float q, float x) {
   const float t = q - x;

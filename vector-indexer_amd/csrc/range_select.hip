@@ -5,10 +5,12 @@
 // threshold is known before anything is read: a vector with reference distance d <= radius2 has, in the frame its records
 // live in (||q||^2 = qn there), a rank value
 //     m <= thr = (radius2 - qn) + w + 2E + 3 gamma (radius2 + E),      w = (D/64 + 9) u' (|radius2| + qn)
-// E and gamma as in select.hip (*); w covers the f32 rounding of the subtraction and of qn's own sum.  So one pass over
-// the records is enough: the groups whose smallest minimum is at or below thr, their pair records, and of those every
-// sub-block whose minimum is at or below thr — re-evaluated as a whole in the reference's exact order, as the top-k
-// select does it, four sub-blocks per wave instruction.  What comes out depends on exact distances only.
+// = rank_threshold((radius2 - qn) + w): E, gamma and the formula (*) are the top-k select's, formed once in
+// select_device.hpp (query_frame, rank_threshold); w covers the f32 rounding of the subtraction and of qn's own sum.  So
+// one pass over the records is enough: the groups whose smallest minimum is at or below thr, their pair records, and of
+// those every sub-block whose minimum is at or below thr — re-evaluated as a whole in the reference's exact order, four
+// sub-blocks per wave instruction: the top-k select's stage 2, on the same record walk (GroupRecords,
+// scan_pair_records, push_sub / drain_pick).  What comes out depends on exact distances only.
 //
 // Sizing, with nothing evaluated twice: the same pass WITHOUT the evaluations (range_select_kernel<false>) counts the
 // sub-blocks per query; 16 x that bounds the query's hits and sizes its row of the key scratch.  The pass with the
@@ -27,8 +29,6 @@
 
 namespace vi {
 
-vi_status sort_rows_u64(uint64_t *keys, uint64_t nrows, uint32_t logL, hipStream_t st);  // generic_search.hip
-
 namespace {
 
 constexpr uint64_t kMaxRangeKeys = 1ull << 27;  // keys in flight per chunk of queries (1 GiB): the generic engine's budget
@@ -36,10 +36,9 @@ constexpr uint32_t kMinRowLog = 11;             // rows of at least 2048 keys (s
 
 struct RangeArgs {
   SelectCommon c;
-  uint32_t q0, m, P, segb0;  // queries [q0, q0 + m) of the batch
+  uint32_t q0, m, P;  // queries [q0, q0 + m) of the batch
   float radius2;
-  const uint32_t *qoff, *qtot, *rel, *pair_pos, *tile_start;
-  const uint32_t *probes, *gorder, *first_block, *list_len;
+  ListProbes lp;
   uint32_t *bound;    // EMIT false: [nq] 16 x (sub-blocks at or below the threshold)
   uint64_t *keys;     // EMIT true: row (q - q0) of 2^logL keys, preset to ~0
   uint32_t logL;
@@ -75,76 +74,20 @@ __global__ void __launch_bounds__(256, 4) range_select_kernel(RangeArgs a) {
   if (blockIdx.x * 4 + wave >= a.m) return;
   const uint32_t q = a.q0 + blockIdx.x * 4 + wave;
   const SelectCommon &c = a.c;
-  uint32_t *pick = s_pick[wave], *lcache = s_lcache[wave], *qbytes = s_qbytes[wave];
-  float4 *tcache = s_tcache[wave];
+  uint32_t *pick = s_pick[wave], *qbytes = s_qbytes[wave];
   float *qlds = s_qrows + (size_t)wave * c.dim;
-  ProbeRegs pr{0u, 0u, 0u, 0u, 0u, 1u, kNoPos};
-  if ((uint32_t)lane < a.P) {
-    const size_t s = (size_t)q * a.P + lane;
-    const uint32_t mylist = a.probes[s];
-    pr.g = a.gorder[s];
-    pr.rel = a.rel[s];
-    if (mylist != kNoPos) {
-      pr.len = a.list_len[mylist];
-      pr.fb = a.first_block[mylist];
-      const uint32_t pp = a.pair_pos[s];  // where the pair sits among the pairs of its list
-      const uint32_t nseg = list_segments(pr.len, a.segb0, &pr.segb);
-      pr.ng = 2u * nseg;
-      pr.boff = (a.tile_start[mylist] + (pp / c.gq) * nseg * seg_records(pr.segb)) * (2u * c.gq) + (pp % c.gq);
-    }
-  }
-  const size_t gbase = a.qoff[q];
-  const uint32_t G = a.qtot[q];
+  const ProbeRegs pr = load_probe_regs(a.lp, c.gq, q, a.P, lane);
+  const GroupRecords gr{c, a.lp.qoff[q], a.lp.qtot[q], s_tcache[wave], s_lcache[wave]};
   const uint64_t below = (1ull << lane) - 1ull;
-  auto lds_sync = [&]() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  };
-  // ---- the query row, its norm in the records' frame and the margin E: as select_body forms them ----
-  float qn = 0.0f, qres = 0.0f;
-  bool q_bytes = c.u8_nat != nullptr && c.dim <= 256u;  // -> the query is integer-valued in 0..255
-  for (uint32_t e = lane; e < c.dim; e += kWave) {
-    const float v = c.Q[(size_t)q * c.dim + e];
-    if (EMIT) qlds[e] = v;
-    const float vc = c.mu ? v - c.mu[e] : v;
-    qn += vc * vc;
-    const float im = -2.0f * vc, ir = im - __uint_as_float(bf16_rn(im) << 16);
-    qres += ir * ir;
-    q_bytes = q_bytes && v >= 0.0f && v <= 255.0f && v == floorf(v);
-  }
-  q_bytes = __ballot(!q_bytes) == 0ull;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) { qn += __shfl_xor(qn, o); qres += __shfl_xor(qres, o); }
-  uint32_t qn_int = 0u;
-  if (EMIT && q_bytes) {  // the query as bytes, zero padded to whole 16-byte pieces (exact_pair_u8_int), and |q|^2 as an integer
-    const uint32_t nw = ((c.dim + 15u) >> 4) * 4u;
-    for (uint32_t w = lane; w < nw; w += kWave) {
-      uint32_t word = 0u;
-#pragma unroll
-      for (uint32_t b = 0; b < 4; ++b) {
-        const uint32_t e = 4u * w + b;
-        const uint32_t v = e < c.dim ? (uint32_t)c.Q[(size_t)q * c.dim + e] : 0u;
-        word |= v << (8u * b);
-        qn_int += v * v;
-      }
-      qbytes[w] = word;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) qn_int += (uint32_t)__shfl_xor((int)qn_int, o);
-  }
-  float E = c.e_scale * (qn * (1.0f + c.gamma) + 2.0f * c.xmax2) + c.e_abs;
-  if (c.trunc) E += 1.02f * (2.0f * sqrtf(qn) * c.rho_max * (1.0f + 0.00391f) + (c.trunc == 2u ? sqrtf(qres) * c.vmax : 0.0f));
-  // ---- the threshold: known before any record is read.  A query norm the rank arithmetic may have overflowed on, or a
-  //      radius beyond the point where the bound means anything: no bound, everything probed is re-evaluated ----
+  const QueryFrame f = query_frame<EMIT>(c, q, lane, qlds, qbytes);
+  // ---- the threshold: known before any record is read.  A radius beyond the point where the bound means anything (or,
+  //      in rank_threshold, a distrusted query): no bound, everything probed is re-evaluated ----
   float thr = INFINITY;
-  if (qn < 1.0e30f && a.radius2 < 1.0e37f) {
-    const float w = ((float)(c.dim >> 6) + 9.0f) * 6.1e-8f * (fabsf(a.radius2) + qn);  // 6.1e-8 > u' = 1.01 * 2^-24
-    const float mk = (a.radius2 - qn) + w;
-    const float scale = fmaxf(mk + qn, 0.0f) + E;
-    thr = mk + (2.0f * E + 3.0f * c.gamma * scale) * 1.001f + 1e-30f;
+  if (a.radius2 < 1.0e37f) {
+    const float w = ((float)(c.dim >> 6) + 9.0f) * 6.1e-8f * (fabsf(a.radius2) + f.qn);  // 6.1e-8 > u' = 1.01 * 2^-24
+    thr = rank_threshold(c, f, (a.radius2 - f.qn) + w);
   }
-  const uint32_t form = c.u8_nat ? (q_bytes ? 3u : 2u) : (c.hi_nat ? 1u : 0u);
+  const uint32_t form = c.u8_nat ? (f.q_bytes ? 3u : 2u) : (c.hi_nat ? 1u : 0u);
   const uint4 *xbase = c.u8_nat ? c.u8_nat : (c.hi_nat ? c.hi_nat : (const uint4 *)c.blocks);
   const uint32_t xmult = c.u8_nat ? c.dq / 4u : (c.hi_nat ? c.dq / 2u : c.dq);  // 16-byte pieces per vector
   uint64_t *row = EMIT ? a.keys + ((size_t)(q - a.q0) << a.logL) : nullptr;
@@ -159,7 +102,7 @@ __global__ void __launch_bounds__(256, 4) range_select_kernel(RangeArgs a) {
     const uint32_t p = live ? pos : 0u;
     if constexpr (FILT) live = live && ((c.allow[fb + p / kWave] >> (p % kWave)) & 1ull) != 0ull;
     n_exact += (uint32_t)__popcll(__ballot(live));
-    const float d = exact_dist_fn(form, qlds, qbytes, qn_int, xbase + ((size_t)(fb + p / kWave) * xmult) * kWave + (p % kWave), c.dim, live);
+    const float d = exact_dist_fn(form, qlds, qbytes, f.qn_int, xbase + ((size_t)(fb + p / kWave) * xmult) * kWave + (p % kWave), c.dim, live);
     const bool hit = live && d <= a.radius2;
     const uint64_t m = __ballot(hit);
     if (hit) {
@@ -168,113 +111,24 @@ __global__ void __launch_bounds__(256, 4) range_select_kernel(RangeArgs a) {
     }
     cursor += (uint32_t)__popcll(m);
   };
-  // sub-blocks waiting in `pick`: four per round, 16 lanes (= the 16 rows of the sub-block) each
-  auto drain_pick = [&]() {
-    while (npick > 0) {
-      const uint32_t cnt = npick >= 4u ? 4u : npick;
-      npick -= cnt;
-      const uint32_t rq = (uint32_t)lane >> 4;
-      const bool live = rq < cnt;
-      const uint32_t ck = live ? pick[npick + rq] : 0u;
-      const uint32_t r = ck >> (kSubBits + 1), sub = (ck >> 1) & ((1u << kSubBits) - 1u), hh = ck & 1u;
-      exact_emit(live, r, (sub >> 1) * kWave + subblock_vector((uint32_t)lane & 15u, sub & 1u, hh, c.image_order != 0u));
-    }
-  };
-  auto push_sub = [&](bool want, uint32_t r, uint32_t sub, uint32_t hh) {  // every lane calls
-    const uint64_t m = __ballot(want);
-    if (!m) return;
-    const uint32_t cnt = (uint32_t)__popcll(m);
-    n_sub += cnt;
-    if constexpr (EMIT) {
-      if (npick + cnt > kPickCap) drain_pick();
-      if (want) pick[npick + (uint32_t)__popcll(m & below)] = (r << (kSubBits + 1)) | (sub << 1) | hh;
-      npick += cnt;
-      lds_sync();
-    }
-  };
-  // The pair records of the groups flagged `want`, four groups per round (16 lanes x one pair record = the 64 sub-block
-  // minima of a 32-block segment half): every sub-block whose minimum is at or below thr is queued (select_body's
-  // scan_groups in its mode 1)
-  auto scan_groups = [&](bool want, uint32_t r, uint32_t seg, uint32_t hh) {
-    uint64_t m = __ballot(want);
-    const uint32_t slot = (uint32_t)lane >> 4, pi = (uint32_t)lane & 15u;
-    while (m) {
-      int src = 0;
-      uint32_t taken = 0;
-#pragma unroll
-      for (uint32_t i = 0; i < 4; ++i)
-        if (m) {
-          const int b = __builtin_ctzll(m);
-          m &= m - 1ull;
-          if (slot == i) src = b;
-          ++taken;
-        }
-      const bool mine = slot < taken;
-      n_scanned += taken;
-      const uint32_t rr = (uint32_t)__shfl((int)r, src), sg = (uint32_t)__shfl((int)seg, src);
-      const uint32_t h2 = (uint32_t)__shfl((int)hh, src);
-      const uint32_t segb = (uint32_t)__shfl((int)pr.segb, (int)rr), ln = (uint32_t)__shfl((int)pr.len, (int)rr);
-      const uint32_t boff = (uint32_t)__shfl((int)pr.boff, (int)rr);
-      const uint32_t nblk = (ln + kWave - 1) / kWave;
-      const uint32_t bs = sg * segb, be = min(nblk, bs + segb);
-      const uint32_t ntile = be > bs ? 2u * (be - bs) : 0u;
-      const uint32_t npairs = !mine ? 0u : (c.wave_order ? 4u * ((ntile + 15u) / 16u) : (ntile + 3u) / 4u);
-      uint32_t mx = npairs;  // wave maximum: segments of very long lists hold more than 16 records
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) mx = max(mx, (uint32_t)__shfl_xor((int)mx, o));
-      for (uint32_t p0 = 0; p0 < mx; p0 += 16u) {
-        const uint32_t p = p0 + pi;
-        const bool live = p < npairs;
-        float4 B = make_float4(INFINITY, INFINITY, INFINITY, INFINITY);
-        if (live) B = c.brec[(size_t)boff + 2u * c.gq * (sg * seg_records(segb) + p) + c.gq * h2];
-        const float bv[4] = {B.x, B.y, B.z, B.w};
-#pragma unroll
-        for (uint32_t j = 0; j < 4; ++j) {
-          const uint32_t tl = c.wave_order ? 16u * (p >> 2) + 4u * j + (p & 3u) : 4u * p + j;  // tile of the segment
-          const bool ok = live && tl < ntile;  // (a record's unused components, and records no wave wrote, are not read as values)
-          push_sub(ok && !(bv[j] > thr), rr, 2u * bs + tl, h2);  // (!(v > thr): a NaN minimum is expanded, never skipped)
-        }
-      }
-    }
-  };
-  // ---- the first 256 group records go to LDS in one round of loads (select_body's stage 0) ----
-  {
-    float4 t4[kCacheG / kWave];
-    uint32_t l4[kCacheG / kWave];
-#pragma unroll
-    for (uint32_t ch = 0; ch < kCacheG / kWave; ++ch) {
-      const uint32_t gidx = ch * kWave + lane;
-      t4[ch] = make_float4(INFINITY, INFINITY, INFINITY, INFINITY);
-      l4[ch] = 0u;
-      if (gidx < G) {
-        t4[ch] = c.gval[gbase + gidx];
-        l4[ch] = c.gmeta[gbase + gidx];  // probe rank | segment << 6 | lane half << 13
-      }
-    }
-#pragma unroll
-    for (uint32_t ch = 0; ch < kCacheG / kWave; ++ch) {
-      const uint32_t gidx = ch * kWave + lane;
-      if (ch * kWave < G) {
-        tcache[gidx] = t4[ch];
-        lcache[gidx] = l4[ch];
-      }
-    }
-    lds_sync();
-  }
-  // ---- every sub-block whose minimum is at or below thr sits in a group whose smallest minimum is (select_body's stage 2) ----
-  for (uint32_t gb = 0; gb < G; gb += kWave) {
+  auto drain = [&]() { drain_pick(c, pick, npick, lane, exact_emit); };
+  gr.fill(lane);
+  // ---- every sub-block whose minimum is at or below thr sits in a group whose smallest minimum is: those groups' pair
+  //      records, and of those every sub-block at or below thr — queued for its exact distances, or counted ----
+  for (uint32_t gb = 0; gb < gr.G; gb += kWave) {
     const uint32_t gidx = gb + lane;
-    const bool live = gidx < G;
-    float4 T = make_float4(INFINITY, INFINITY, INFINITY, INFINITY);
-    uint32_t L = 0u;
-    if (live) {
-      T = gidx < kCacheG ? tcache[gidx] : c.gval[gbase + gidx];
-      L = gidx < kCacheG ? lcache[gidx] : c.gmeta[gbase + gidx];
-    }
-    scan_groups(live && !(T.x > thr), L & 63u, (L >> 6) & 127u, L >> 13);
+    const bool live = gidx < gr.G;
+    uint32_t r, seg, hh;
+    gr.group_place(gidx, live, r, seg, hh);
+    scan_pair_records(c, pr, lane, live && !(gr.group_values(gidx, live).x > thr), r, seg, hh, n_scanned,
+                      [&](bool ok, float v, uint32_t, uint32_t rr, uint32_t sub, uint32_t h2) {
+                        const bool want = ok && !(v > thr);  // (!(v > thr): a NaN minimum is expanded, never skipped)
+                        if constexpr (EMIT) push_sub(pick, npick, n_sub, lane, want, rr, sub, h2, drain);
+                        else n_sub += (uint32_t)__popcll(__ballot(want));
+                      });
   }
   if constexpr (EMIT) {
-    drain_pick();
+    drain();
     if (lane == 0) {
       a.counts[q] = min(cursor, cap);
       if (cursor > cap) atomicOr(a.overflow, 1u);
@@ -310,9 +164,7 @@ __global__ void __launch_bounds__(256) range_output_kernel(RangeOutArgs a) {
     const uint32_t l = a.probes[(size_t)q * a.P + lane], g = a.gorder[(size_t)q * a.P + lane];
     if (l != kNoPos && g < kWave) s_fb[wave][g] = a.first_block[l];
   }
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  wave_lds_sync();
   const uint64_t *row = a.keys + ((size_t)(q - a.q0) << a.logL);
   const uint64_t at = a.lims[q];
   const uint32_t n = a.counts[q];
@@ -337,8 +189,7 @@ vi_status launch_range_select(SearchBatch &b, float radius2, const SelectFrame &
   hipStream_t st = b.st();
   VI_TRY(ws.range_bound.reserve(nq + 1));  // (the last word: the overflow flag)
   VI_TRY(ws.counts.reserve(nq));
-  RangeArgs a{list_select_common(b, f), 0u, (uint32_t)nq, b.P, kn.segb0, radius2, ws.qoff.p, ws.qtot.p, ws.pair_rel.p, ws.pair_pos.p,
-              ws.tile_start.p, ws.probes.p, ws.gorder.p, ix.list_first_block.p, ix.list_len.p, ws.range_bound.p, nullptr, 0u, ws.counts.p,
+  RangeArgs a{list_select_common(b, f), 0u, (uint32_t)nq, b.P, radius2, list_probes(b), ws.range_bound.p, nullptr, 0u, ws.counts.p,
               ws.range_bound.p + nq};
   if (b.flt) a.c.allow = b.flt->allow.p;
   unsigned long long *dbg = a.c.dbg;

@@ -176,6 +176,7 @@ bool coarse_on_matrix_cores(const DeviceIndex &ix, const EngineKnobs &kn, uint64
 vi_status device_index_search_generic(SearchBatch &b, uint64_t k, const SelectOutputs &out);
 vi_status device_index_range_generic(SearchBatch &b, float radius2, RangeResult *res);
 vi_status generic_probe_export(SearchBatch &b);
+vi_status sort_rows_u64(uint64_t *keys, uint64_t nrows, uint32_t logL, hipStream_t st);  // rows of 2^logL keys, each sorted ascending
 
 // ---- rank_images.hip ----
 // everything the MFMA engine ranks an index from, derived from its f32 blocks: norms, bf16 / int8 images, the centre, the

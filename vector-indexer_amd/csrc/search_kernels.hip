@@ -181,9 +181,7 @@ __global__ void __launch_bounds__(kBlockThreads) scan_kernel(ScanArgs a) {
       const bool live = j < (int)nqi;
       for (uint32_t e = lane; e < dpad; e += kWave) lqf[j * dpad + e] = (live && e < a.dim) ? src[e] : 0.0f;
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
   }
 
   WaveTopK sel[QG];

@@ -160,59 +160,12 @@ __device__ __forceinline__ void select_body(const SelectCommon &c, uint32_t q, s
                                             const ProbeRegs &pr, uint32_t K, int lane, uint32_t *pick, float4 *tcache,
                                             uint32_t *lcache, float *qlds, Top &sel, uint32_t *qbytes = nullptr) {
   const uint64_t below = (1ull << lane) - 1ull;
-  auto lds_sync = [&]() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  };
-  float qn = 0.0f, qres = 0.0f;
-  bool q_bytes = c.u8_nat != nullptr && qbytes != nullptr && c.dim <= 256u;  // -> the query is integer-valued in 0..255
-  for (uint32_t e = lane; e < c.dim; e += kWave) {  // the query row: into LDS for the exact evaluations, and its norm
-    const float v = c.Q[(size_t)q * c.dim + e];
-    qlds[e] = v;
-    const float vc = c.mu ? v - c.mu[e] : v;  // the margins live where the rank values do
-    qn += vc * vc;
-    const float im = -2.0f * vc, ir = im - __uint_as_float(bf16_rn(im) << 16);  // what the hi plane of the query image leaves out
-    qres += ir * ir;
-    q_bytes = q_bytes && v >= 0.0f && v <= 255.0f && v == floorf(v);
-  }
-  q_bytes = __ballot(!q_bytes) == 0ull;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) { qn += __shfl_xor(qn, o); qres += __shfl_xor(qres, o); }
-  uint32_t qn_int = 0u;
-  if (q_bytes) {  // the query as bytes, zero padded to whole 16-byte pieces (exact_pair_u8_int), and |q|^2 as an integer
-    const uint32_t nw = ((c.dim + 15u) >> 4) * 4u;
-    for (uint32_t w = lane; w < nw; w += kWave) {
-      uint32_t word = 0u;
-#pragma unroll
-      for (uint32_t b = 0; b < 4; ++b) {
-        const uint32_t e = 4u * w + b;
-        const uint32_t v = e < c.dim ? (uint32_t)c.Q[(size_t)q * c.dim + e] : 0u;
-        word |= v << (8u * b);
-        qn_int += v * v;
-      }
-      qbytes[w] = word;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) qn_int += (uint32_t)__shfl_xor((int)qn_int, o);
-  }
-  float E = c.e_scale * (qn * (1.0f + c.gamma) + 2.0f * c.xmax2) + c.e_abs;
-  // hi planes of real-valued lists: the image (-2q) . v is ranked as (-2q) . hi(v) [trunc 1] or hi(-2q) . hi(v) [trunc 2];
-  // |(-2q) . (v - hi v)| <= 2 |q| rho_max, and |(-2q - hi(-2q)) . v| <= |query residual| max|v|  (|hi(-2q)| <= 2 |q| (1 + 2^-8))
-  if (c.trunc) E += 1.02f * (2.0f * sqrtf(qn) * c.rho_max * (1.0f + 0.00391f) + (c.trunc == 2u ? sqrtf(qres) * c.vmax : 0.0f));
-  // a query so large that the rank arithmetic may have overflowed (inf - inf = NaN, and NaN fails every guard
-  // below): trust no rank value, re-evaluate everything the query probes
-  const bool distrust = !(qn < 1.0e30f);
-  auto threshold_of = [&](float mk) {  // (*) ; anything non-finite or huge means "no bound"
-    if (distrust || !(mk < 1.0e37f)) return INFINITY;
-    const float scale = fmaxf(mk + qn, 0.0f) + E;
-    return mk + (2.0f * E + 3.0f * c.gamma * scale) * 1.001f + 1e-30f;
-  };
+  const QueryFrame f = query_frame<true>(c, q, lane, qlds, qbytes);
   uint32_t npick = 0, n_exact = 0, n_scanned = 0, n_full = 0, n_sub = 0;
   Top s1;
   float thr = INFINITY;
   sel.init();
-  const float *qrow = qlds;  // (visible to the wave after the lds_sync of stage 0)
+  const float *qrow = qlds;  // (visible to the wave after the wave_lds_sync of stage 0)
   auto exact_offer = [&](bool live, uint32_t r, uint32_t pos) {  // one (probe rank, position) per lane
     const uint32_t fb = (uint32_t)__shfl((int)pr.fb, (int)r);
     const uint32_t g = (uint32_t)__shfl((int)pr.g, (int)r);
@@ -223,8 +176,8 @@ __device__ __forceinline__ void select_body(const SelectCommon &c, uint32_t q, s
       live = live && ((c.allow[fb + p / kWave] >> (p % kWave)) & 1ull) != 0ull;
     }
     n_exact += (uint32_t)__popcll(__ballot(live));
-    if (c.u8_nat && q_bytes)
-      sel = exact_batch_u8_int_fn(sel, qbytes, qn_int, c.u8_nat + ((size_t)(fb + (live ? pos : 0u) / kWave) * (c.dq / 4)) * kWave + (pos % kWave),
+    if (c.u8_nat && f.q_bytes)
+      sel = exact_batch_u8_int_fn(sel, qbytes, f.qn_int, c.u8_nat + ((size_t)(fb + (live ? pos : 0u) / kWave) * (c.dq / 4)) * kWave + (pos % kWave),
                                   c.dim, live, (g << kPosBits) | pos, (int)K);
     else if (c.u8_nat)
       sel = exact_batch_u8_fn(sel, qrow, c.u8_nat + ((size_t)(fb + (live ? pos : 0u) / kWave) * (c.dq / 4)) * kWave + (pos % kWave), c.dim,
@@ -236,75 +189,14 @@ __device__ __forceinline__ void select_body(const SelectCommon &c, uint32_t q, s
       sel = exact_batch_fn(sel, qrow, c.blocks + ((size_t)(fb + (live ? pos : 0u) / kWave) * c.dq) * kWave + (pos % kWave),
                            c.dim, live, (g << kPosBits) | pos, (int)K);
   };
-  // sub-blocks waiting in `pick`: four per round, 16 lanes (= the 16 rows of the sub-block) each
-  auto drain_pick = [&]() {
-    while (npick > 0) {
-      const uint32_t cnt = npick >= 4u ? 4u : npick;
-      npick -= cnt;
-      const uint32_t rq = (uint32_t)lane >> 4;
-      const bool live = rq < cnt;
-      const uint32_t ck = live ? pick[npick + rq] : 0u;
-      const uint32_t r = ck >> (kSubBits + 1), sub = (ck >> 1) & ((1u << kSubBits) - 1u), hh = ck & 1u;
-      exact_offer(live, r, (sub >> 1) * kWave + subblock_vector((uint32_t)lane & 15u, sub & 1u, hh, c.image_order != 0u));
-    }
-  };
-  auto push_sub = [&](bool want, uint32_t r, uint32_t sub, uint32_t hh) {  // every lane calls
-    const uint64_t m = __ballot(want);
-    if (!m) return;
-    const uint32_t cnt = (uint32_t)__popcll(m);
-    n_sub += cnt;
-    if (npick + cnt > kPickCap) drain_pick();
-    if (want) pick[npick + (uint32_t)__popcll(m & below)] = (r << (kSubBits + 1)) | (sub << 1) | hh;
-    npick += cnt;
-    lds_sync();
-  };
-  // The pair records of the groups flagged `want`, four groups per round (16 lanes x one pair record = the 64
-  // sub-block minima of a 32-block segment half).  mode 0: the minima go to the running top-K of rank values (s1);
+  auto drain = [&]() { drain_pick(c, pick, npick, lane, exact_offer); };
+  // The pair records of the groups flagged `want`.  mode 0: the minima go to the running top-K of rank values (s1);
   // mode 1: every sub-block whose minimum is at or below thr is queued for exact evaluation.
   auto scan_groups = [&](bool want, uint32_t r, uint32_t seg, uint32_t hh, int mode) {
-    uint64_t m = __ballot(want);
-    const uint32_t slot = (uint32_t)lane >> 4, pi = (uint32_t)lane & 15u;
-    while (m) {
-      int src = 0;
-      uint32_t taken = 0;
-#pragma unroll
-      for (uint32_t i = 0; i < 4; ++i)
-        if (m) {
-          const int b = __builtin_ctzll(m);
-          m &= m - 1ull;
-          if (slot == i) src = b;
-          ++taken;
-        }
-      const bool mine = slot < taken;
-      n_scanned += taken;
-      const uint32_t rr = (uint32_t)__shfl((int)r, src), sg = (uint32_t)__shfl((int)seg, src);
-      const uint32_t h2 = (uint32_t)__shfl((int)hh, src);
-      const uint32_t segb = (uint32_t)__shfl((int)pr.segb, (int)rr), ln = (uint32_t)__shfl((int)pr.len, (int)rr);
-      const uint32_t boff = (uint32_t)__shfl((int)pr.boff, (int)rr);
-      const uint32_t nblk = (ln + kWave - 1) / kWave;
-      const uint32_t bs = sg * segb, be = min(nblk, bs + segb);
-      // records of the segment: pair order (record p = blocks 2p, 2p + 1; component j = sub-block 4p + j), or the streaming
-      // kernel's wave order (record p, component j = 32-vector tile 16 (p >> 2) + 4 j + (p & 3))
-      const uint32_t ntile = be > bs ? 2u * (be - bs) : 0u;
-      const uint32_t npairs = !mine ? 0u : (c.wave_order ? 4u * ((ntile + 15u) / 16u) : (ntile + 3u) / 4u);
-      uint32_t mx = npairs;  // wave maximum: segments of very long lists hold more than 16 records
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) mx = max(mx, (uint32_t)__shfl_xor((int)mx, o));
-      for (uint32_t p0 = 0; p0 < mx; p0 += 16u) {
-        const uint32_t p = p0 + pi;
-        const bool live = p < npairs;
-        float4 B = make_float4(INFINITY, INFINITY, INFINITY, INFINITY);
-        if (live) B = c.brec[(size_t)boff + 2u * c.gq * (sg * seg_records(segb) + p) + c.gq * h2];
-        const float bv[4] = {B.x, B.y, B.z, B.w};
-#pragma unroll
-        for (uint32_t j = 0; j < 4; ++j) {
-          const uint32_t tl = c.wave_order ? 16u * (p >> 2) + 4u * j + (p & 3u) : 4u * p + j;  // tile of the segment
-          const bool ok = live && tl < ntile;  // (a record's unused components, and records no wave wrote, are not read as values)
-          if (mode == 0) s1 = offer_bulk_fn(s1, ok ? bv[j] : INFINITY, ok ? j : kNoPos, (int)K);
-          else push_sub(ok && !(bv[j] > thr), rr, 2u * bs + tl, h2);  // (!(v > thr): a NaN minimum is expanded, never skipped)
-        }
-      }
-    }
+    scan_pair_records(c, pr, lane, want, r, seg, hh, n_scanned, [&](bool ok, float v, uint32_t j, uint32_t rr, uint32_t sub, uint32_t h2) {
+      if (mode == 0) s1 = offer_bulk_fn(s1, ok ? v : INFINITY, ok ? j : kNoPos, (int)K);
+      else push_sub(pick, npick, n_sub, lane, ok && !(v > thr), rr, sub, h2, drain);  // (!(v > thr): a NaN minimum is expanded, never skipped)
+    });
   };
 
   // (diagnostic, VI_FILTER_STATS: s_memtime ticks per stage, summed over the queries into the stage clocks of ws.stats, kStatClocks)
@@ -316,43 +208,9 @@ __device__ __forceinline__ void select_body(const SelectCommon &c, uint32_t q, s
       tk = now;
     }
   };
-  // ---- stage 0: the first 256 group records go to LDS in one round of loads (the passes below would
-  //      otherwise each pay the global-memory latency per 64 groups) ----
-  {
-    float4 t4[kCacheG / kWave];
-#pragma unroll
-    for (uint32_t ch = 0; ch < kCacheG / kWave; ++ch) {
-      const uint32_t gidx = ch * kWave + lane;
-      t4[ch] = make_float4(INFINITY, INFINITY, INFINITY, INFINITY);
-      if (gidx < G) t4[ch] = c.gval[gbase + gidx];
-    }
-    uint32_t l4[kCacheG / kWave];
-#pragma unroll
-    for (uint32_t ch = 0; ch < kCacheG / kWave; ++ch) {
-      const uint32_t gidx = ch * kWave + lane;
-      l4[ch] = 0u;
-      if (gidx < G) l4[ch] = c.gmeta[gbase + gidx];  // probe rank | segment << 6 | lane half << 13
-    }
-#pragma unroll
-    for (uint32_t ch = 0; ch < kCacheG / kWave; ++ch) {
-      const uint32_t gidx = ch * kWave + lane;
-      if (ch * kWave < G) {
-        tcache[gidx] = t4[ch];
-        lcache[gidx] = l4[ch];
-      }
-    }
-    lds_sync();
-  }
-  auto group_values = [&](uint32_t gidx, bool live) {
-    float4 T = make_float4(INFINITY, INFINITY, INFINITY, INFINITY);
-    if (live) T = gidx < kCacheG ? tcache[gidx] : c.gval[gbase + gidx];
-    return T;
-  };
-  auto group_place = [&](uint32_t gidx, bool live, uint32_t &r, uint32_t &seg, uint32_t &hh) {
-    uint32_t L = 0u;
-    if (live) L = gidx < kCacheG ? lcache[gidx] : c.gmeta[gbase + gidx];
-    r = L & 63u; seg = (L >> 6) & 127u; hh = L >> 13;
-  };
+  // ---- stage 0: the first 256 group records go to LDS ----
+  const GroupRecords gr{c, gbase, G, tcache, lcache};
+  gr.fill(lane);
   lap(0);
   // ---- stage 1a: threshold (*) from the K-th smallest value of the group records (key = 4*group + slot);
   //      the groups' smallest values first: they shut the door on most of the others ----
@@ -368,7 +226,7 @@ __device__ __forceinline__ void select_body(const SelectCommon &c, uint32_t q, s
       float lm = INFINITY;
       for (uint32_t gb = 0; gb < G; gb += kWave) {
         const uint32_t gidx = gb + lane;
-        lm = fminf(lm, group_values(gidx, gidx < G).x);
+        lm = fminf(lm, gr.group_values(gidx, gidx < G).x);
       }
       uint64_t kk = pack_key(lm, (uint32_t)lane);
       wave_sort_u64(kk, lane);
@@ -380,7 +238,7 @@ __device__ __forceinline__ void select_body(const SelectCommon &c, uint32_t q, s
       for (uint32_t gb = 0; gb < G && !overflow; gb += kWave) {
         const uint32_t gidx = gb + lane;
         const bool live = gidx < G;
-        const float4 T = group_values(gidx, live);
+        const float4 T = gr.group_values(gidx, live);
         const float tv[4] = {T.x, T.y, T.z, T.w};
 #pragma unroll
         for (uint32_t j = 0; j < 4; ++j) {
@@ -397,7 +255,7 @@ __device__ __forceinline__ void select_body(const SelectCommon &c, uint32_t q, s
           ncand += cnt;
         }
       }
-      lds_sync();
+      wave_lds_sync();
     }
     if (!overflow) {
       for (uint32_t c0 = 0; c0 < ncand; c0 += kWave) {
@@ -405,27 +263,27 @@ __device__ __forceinline__ void select_body(const SelectCommon &c, uint32_t q, s
         const float v = live ? __uint_as_float(pick[2u * (c0 + lane)]) : INFINITY;
         s1 = offer_bulk_fn(s1, v, live ? pick[2u * (c0 + lane) + 1u] : kNoPos, (int)K);
       }
-      lds_sync();  // (pick is reused by the stages below)
+      wave_lds_sync();  // (pick is reused by the stages below)
     } else {
       s1.init();
       for (uint32_t gb = 0; gb < G; gb += kWave) {
         const uint32_t gidx = gb + lane;
         const bool live = gidx < G;
-        s1 = offer_bulk_fn(s1, group_values(gidx, live).x, live ? 4u * gidx : kNoPos, (int)K);
+        s1 = offer_bulk_fn(s1, gr.group_values(gidx, live).x, live ? 4u * gidx : kNoPos, (int)K);
       }
       for (uint32_t gb = 0; gb < G; gb += kWave) {
         const uint32_t gidx = gb + lane;
         const bool live = gidx < G;
-        const float4 T = group_values(gidx, live);
+        const float4 T = gr.group_values(gidx, live);
         s1 = offer_bulk_fn(s1, T.y, live ? 4u * gidx + 1u : kNoPos, (int)K);
         s1 = offer_bulk_fn(s1, T.z, live ? 4u * gidx + 2u : kNoPos, (int)K);
         s1 = offer_bulk_fn(s1, T.w, live ? 4u * gidx + 3u : kNoPos, (int)K);
       }
     }
-    thr = threshold_of(s1.kth((int)K));
+    thr = rank_threshold(c, f, s1.kth((int)K));
     for (uint32_t gb = 0; gb < G; gb += kWave) {  // is any group's 4th value at or below it?
       const uint32_t gidx = gb + lane;
-      const float4 T = group_values(gidx, gidx < G);
+      const float4 T = gr.group_values(gidx, gidx < G);
       any_full = any_full || __ballot(gidx < G && T.w <= thr) != 0ull;  // (distrust: thr = inf, stage 1b is moot)
     }
   }
@@ -434,14 +292,14 @@ __device__ __forceinline__ void select_body(const SelectCommon &c, uint32_t q, s
   //      loose; the pair records of those groups list every sub-block minimum.  Their values REPLACE the
   //      group's own (which are among them, so they must not be counted twice): drop the group's entries from
   //      the running top-K, then offer its pair records ----
-  if (any_full && !distrust && !(c.xmode & 4u)) {
+  if (any_full && !f.distrust && !(c.xmode & 4u)) {
     {
       bool keep[2] = {false, false};
 #pragma unroll
       for (int e = 0; e < Top::kEntries; ++e) {
         const uint32_t key = s1.ent_p(e);
         const bool mine = key != kNoPos && (uint32_t)(64 * e + lane) < K;  // entries beyond the K-th are not needed
-        keep[e] = mine && !(group_values(mine ? (key >> 2) : 0u, true).w <= thr);
+        keep[e] = mine && !(gr.group_values(mine ? (key >> 2) : 0u, true).w <= thr);
       }
       s1.rebuild(keep[0], keep[1], (int)K);  // the survivors close ranks
     }
@@ -449,10 +307,10 @@ __device__ __forceinline__ void select_body(const SelectCommon &c, uint32_t q, s
       const uint32_t gidx = gb + lane;
       const bool live = gidx < G;
       uint32_t r, seg, hh;
-      group_place(gidx, live, r, seg, hh);
-      scan_groups(live && group_values(gidx, live).w <= thr, r, seg, hh, 0);
+      gr.group_place(gidx, live, r, seg, hh);
+      scan_groups(live && gr.group_values(gidx, live).w <= thr, r, seg, hh, 0);
     }
-    thr = fminf(thr, threshold_of(s1.kth((int)K)));
+    thr = fminf(thr, rank_threshold(c, f, s1.kth((int)K)));
   }
   lap(2);
   // ---- stage 2: exact re-evaluation of every sub-block whose minimum is at or below thr; such a sub-block sits in a
@@ -461,13 +319,13 @@ __device__ __forceinline__ void select_body(const SelectCommon &c, uint32_t q, s
     const uint32_t gidx = gb + lane;
     const bool live = gidx < G;
     uint32_t r, seg, hh;
-    group_place(gidx, live, r, seg, hh);
-    const float4 T = group_values(gidx, live);
+    gr.group_place(gidx, live, r, seg, hh);
+    const float4 T = gr.group_values(gidx, live);
     n_full += (uint32_t)__popcll(__ballot(live && T.w <= thr));
     scan_groups(live && !(T.x > thr) && !(c.xmode & 2u), r, seg, hh, 1);
   }
   lap(3);
-  drain_pick();
+  drain();
   lap(4);
   if (c.dbg && lane == 0 && (q & c.dbg_mask) == 0u) {
 #pragma unroll
@@ -482,9 +340,8 @@ __device__ __forceinline__ void select_body(const SelectCommon &c, uint32_t q, s
 
 struct SelectArgs {
   SelectCommon c;
-  uint32_t nq, P, k, segb0;
-  const uint32_t *qoff, *qtot, *rel, *pair_pos, *tile_start;
-  const uint32_t *probes, *gorder, *first_block, *list_len;
+  uint32_t nq, P, k;
+  ListProbes lp;
   const uint64_t *ext_ids;
   float *D;
   int64_t *I;
@@ -502,24 +359,10 @@ __global__ void __launch_bounds__(256, 4) select_kernel(SelectArgs a) {
   const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
   const uint32_t q = blockIdx.x * 4 + wave;
   if (q >= a.nq) return;
-  ProbeRegs pr{0u, 0u, 0u, 0u, 0u, 1u, kNoPos};
-  uint32_t mylist = kNoPos;
-  if ((uint32_t)lane < a.P) {
-    const size_t s = (size_t)q * a.P + lane;
-    mylist = a.probes[s];
-    pr.g = a.gorder[s];
-    pr.rel = a.rel[s];
-    if (mylist != kNoPos) {
-      pr.len = a.list_len[mylist];
-      pr.fb = a.first_block[mylist];
-      const uint32_t pp = a.pair_pos[s];  // where the pair sits among the pairs of its list
-      const uint32_t nseg = list_segments(pr.len, a.segb0, &pr.segb);
-      pr.ng = 2u * nseg;
-      pr.boff = (a.tile_start[mylist] + (pp / a.c.gq) * nseg * seg_records(pr.segb)) * (2u * a.c.gq) + (pp % a.c.gq);
-    }
-  }
+  uint32_t mylist;
+  const ProbeRegs pr = load_probe_regs(a.lp, a.c.gq, q, a.P, lane, &mylist);
   Top sel;
-  select_body<Top, FILT>(a.c, q, a.qoff[q], a.qtot[q], a.P, pr, a.k, lane, s_pick[wave], s_tcache[wave],
+  select_body<Top, FILT>(a.c, q, a.lp.qoff[q], a.lp.qtot[q], a.P, pr, a.k, lane, s_pick[wave], s_tcache[wave],
                    s_lcache[wave], s_qrows + (size_t)wave * a.c.dim, sel, s_qbytes[wave]);
   // entry e of lane i holds result 64e + i: map the candidate-order rank g back to the probe rank r
   uint32_t found = 0;
@@ -633,11 +476,6 @@ __global__ void __launch_bounds__(256) coarse_select_direct_kernel(CoarseSelectA
   uint32_t *pick = s_pick[wave];
   float *qlds = s_q[wave];
   const uint64_t below = (1ull << lane) - 1ull;
-  auto lds_sync = [&]() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  };
   // (diagnostic, VI_FILTER_STATS=2: s_memtime ticks per stage, summed over the queries into the stage clocks of ws.stats, kStatClocks)
   unsigned long long tk = c.dbg ? __builtin_amdgcn_s_memtime() : 0ull, tks[6] = {0, 0, 0, 0, 0, 0};
   auto lap = [&](int i) {
@@ -647,19 +485,9 @@ __global__ void __launch_bounds__(256) coarse_select_direct_kernel(CoarseSelectA
       tk = now;
     }
   };
-  float qn = 0.0f;
-  for (uint32_t e = lane; e < c.dim; e += kWave) {
-    const float v = c.Q[(size_t)q * c.dim + e];
-    qlds[e] = v;
-    const float vc = c.mu ? v - c.mu[e] : v;
-    qn += vc * vc;
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) qn += __shfl_xor(qn, o);
-  lds_sync();
+  const QueryFrame f = query_frame<true>(c, q, lane, qlds, nullptr);
+  wave_lds_sync();
   lap(0);
-  const float E = c.e_scale * (qn * (1.0f + c.gamma) + 2.0f * c.xmax2);
-  const bool distrust = !(qn < 1.0e30f);  // see select_body
   const uint32_t K = a.P, nblk = (a.nlists + kWave - 1) / kWave, nrec = 4u * nblk;  // records: (block, tile, lane half)
   constexpr uint32_t kPer = kDirectBlocks * 4 / kWave;  // records per lane
   // (min of sub-block 0 with its row, its second min, the same of sub-block 1)
@@ -686,14 +514,7 @@ __global__ void __launch_bounds__(256) coarse_select_direct_kernel(CoarseSelectA
   FastTopK s1;
   s1.init();
   s1 = offer_bulk_fn(s1, lm, (uint32_t)lane, (int)K);
-  float thr = INFINITY;
-  {
-    const float mk = s1.kth((int)K);
-    if (!distrust && mk < 1.0e37f) {
-      const float scale = fmaxf(mk + qn, 0.0f) + E;
-      thr = mk + (2.0f * E + 3.0f * c.gamma * scale) * 1.001f + 1e-30f;
-    }
-  }
+  const float thr = rank_threshold(c, f, s1.kth((int)K));
   lap(1);
   FastTopK sel;
   sel.init();
@@ -741,7 +562,7 @@ __global__ void __launch_bounds__(256) coarse_select_direct_kernel(CoarseSelectA
         for (uint32_t s2 = 0; s2 < 2; ++s2) {
           const uint32_t sb = 2u * i + s2;
           const bool cand = rec < nrec && !(rb1[i][s2] > thr);
-          const bool all8 = cand && (!(rb2[i][s2] > thr) || distrust);
+          const bool all8 = cand && (!(rb2[i][s2] > thr) || f.distrust);
           const uint64_t k = all8 ? 2u : (cand ? 1u : 0u);
           cls |= k << (2u * sb);
           const uint64_t row = __float_as_uint(rb1[i][s2]) & 7u;
@@ -776,7 +597,7 @@ __global__ void __launch_bounds__(256) coarse_select_direct_kernel(CoarseSelectA
       }
       npick = total;
       listed = true;
-      lds_sync();
+      wave_lds_sync();
       if (c.dbg) {
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) n_whole += (uint32_t)__shfl_xor((int)n_whole, o);
@@ -792,7 +613,7 @@ __global__ void __launch_bounds__(256) coarse_select_direct_kernel(CoarseSelectA
 #pragma nounroll  // (a cold path: unrolled, its inlined exact rounds would double the kernel's code)
       for (uint32_t s2 = 0; s2 < 2; ++s2) {
         const bool cand = rec < nrec && !(b1[s2] > thr);
-        const bool all8 = cand && (!(b2[s2] > thr) || distrust);
+        const bool all8 = cand && (!(b2[s2] > thr) || f.distrust);
         const bool one = cand && !all8;
         uint64_t m = __ballot(one);
         if (m) {
@@ -800,7 +621,7 @@ __global__ void __launch_bounds__(256) coarse_select_direct_kernel(CoarseSelectA
           if (npick + cnt > kPickCap) drain_singles();
           if (one) pick[npick + (uint32_t)__popcll(m & below)] = sub_row(rec, s2, __float_as_uint(b1[s2]) & 7u);
           npick += cnt;
-          lds_sync();
+          wave_lds_sync();
         }
         m = __ballot(all8);
         if (m) {  // all 8 rows of the sub-block: into the same list (they used to wait for rounds of their own — a second exact
@@ -819,7 +640,7 @@ __global__ void __launch_bounds__(256) coarse_select_direct_kernel(CoarseSelectA
             }
             npick += cnt;
             n_whole += cnt >> 3;
-            lds_sync();
+            wave_lds_sync();
           }
         }
       }
@@ -842,11 +663,9 @@ __global__ void __launch_bounds__(256) coarse_select_direct_kernel(CoarseSelectA
 
 vi_status launch_list_select(SearchBatch &b, uint64_t k, const SelectFrame &f, const SelectOutputs &out) {
   const DeviceIndex &ix = b.ix;
-  SearchWorkspace &ws = b.ws();
   hipStream_t st = b.st();
-  SelectArgs a{list_select_common(b, f),
-               (uint32_t)b.nq, b.P, (uint32_t)k, b.kn.segb0, ws.qoff.p, ws.qtot.p, ws.pair_rel.p, ws.pair_pos.p, ws.tile_start.p, ws.probes.p,
-               ws.gorder.p, ix.list_first_block.p, ix.list_len.p, ix.ext_ids.p, out.D, out.I, out.tie, out.slots, out.counts};
+  SelectArgs a{list_select_common(b, f), (uint32_t)b.nq, b.P, (uint32_t)k, list_probes(b), ix.ext_ids.p, out.D, out.I, out.tie, out.slots,
+               out.counts};
   const size_t qsm = 4ull * ix.dim * sizeof(float);
   const dim3 grid((uint32_t)((b.nq + 3) / 4));
   if (b.flt) {  // an instantiation of its own: the unfiltered one keeps its registers and its four workgroups per CU

@@ -1,6 +1,10 @@
 // select_device.hpp — what the select kernels of the MFMA engine share (select.hip: top-k; range_select.hip: radius):
-// the frame the rank records live in (SelectCommon), a query's probes in registers, the exact reference distance of one
-// (query row, stored vector) pair per lane in its four forms, and where a sub-block's rows sit in their block.
+// the frame the rank records live in (SelectCommon), the exact reference distance of one (query row, stored vector) pair
+// per lane in its four forms, where a sub-block's rows sit in their block, and — once, for every select — the soundness
+// core of DESIGN §2b: the query in that frame with its error bound (QueryFrame, query_frame), the threshold (*) built
+// from it (rank_threshold), a query's probes in registers (ListProbes, load_probe_regs) and the walk over its records
+// (GroupRecords, scan_pair_records, the pick queue: push_sub / drain_pick).  All inlined: the callers keep the counters
+// and what is done with a value; the noinline exact-evaluation pieces stay with their kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -226,6 +230,235 @@ __device__ __forceinline__ uint32_t subblock_vector(uint32_t e, uint32_t t, uint
 constexpr uint32_t kPickCap = 256;     // sub-blocks waiting for their 16 exact distances (per wave)
 constexpr uint32_t kSubBits = 21;      // request key = (probe rank << 22) | (sub-block of the list << 1) | lane half
 constexpr uint32_t kCacheG = 256;      // group records (values + probe/segment/half) kept in LDS per wave
+
+// ---- the query in the frame its rank records live in ----
+struct QueryFrame {
+  float qn;         // ||q'||^2, q' = q - mu where the images are centred: the margins live where the rank values do
+  float E;          // |recorded rank value - true one| <= E for every vector the query probes
+  uint32_t qn_int;  // q_bytes: ||q||^2 as an integer
+  bool q_bytes;     // 8-bit lists, D <= 256 and the query integer-valued in 0..255: exact_pair_u8_int applies
+  bool distrust;    // a query so large that the rank arithmetic may have overflowed (inf - inf = NaN, and NaN fails every
+                    // guard of the selects): trust no rank value, re-evaluate everything the query probes
+};
+
+// One wave: the frame of query q.  STAGE: the row goes to qlds for the exact evaluations (visible to the wave after the
+// next wave_lds_sync) and, under q_bytes, its byte form to qbytes (null: the caller has no use for it)
+template <bool STAGE>
+__device__ __forceinline__ QueryFrame query_frame(const SelectCommon &c, uint32_t q, int lane, float *qlds, uint32_t *qbytes) {
+  QueryFrame f;
+  float qn = 0.0f, qres = 0.0f;
+  bool q_bytes = c.u8_nat != nullptr && qbytes != nullptr && c.dim <= 256u;
+  for (uint32_t e = lane; e < c.dim; e += kWave) {
+    const float v = c.Q[(size_t)q * c.dim + e];
+    if (STAGE) qlds[e] = v;
+    const float vc = c.mu ? v - c.mu[e] : v;
+    qn += vc * vc;
+    const float im = -2.0f * vc, ir = im - __uint_as_float(bf16_rn(im) << 16);  // what the hi plane of the query image leaves out
+    qres += ir * ir;
+    q_bytes = q_bytes && v >= 0.0f && v <= 255.0f && v == floorf(v);
+  }
+  f.q_bytes = __ballot(!q_bytes) == 0ull;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) { qn += __shfl_xor(qn, o); qres += __shfl_xor(qres, o); }
+  f.qn = qn;
+  f.qn_int = 0u;
+  if (STAGE && f.q_bytes) {  // the query as bytes, zero padded to whole 16-byte pieces (exact_pair_u8_int), and |q|^2 as an integer
+    const uint32_t nw = ((c.dim + 15u) >> 4) * 4u;
+    for (uint32_t w = lane; w < nw; w += kWave) {
+      uint32_t word = 0u;
+#pragma unroll
+      for (uint32_t b = 0; b < 4; ++b) {
+        const uint32_t e = 4u * w + b;
+        const uint32_t v = e < c.dim ? (uint32_t)c.Q[(size_t)q * c.dim + e] : 0u;
+        word |= v << (8u * b);
+        f.qn_int += v * v;
+      }
+      qbytes[w] = word;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) f.qn_int += (uint32_t)__shfl_xor((int)f.qn_int, o);
+  }
+  f.E = c.e_scale * (qn * (1.0f + c.gamma) + 2.0f * c.xmax2) + c.e_abs;
+  // hi planes of real-valued lists: the image (-2q) . v is ranked as (-2q) . hi(v) [trunc 1] or hi(-2q) . hi(v) [trunc 2];
+  // |(-2q) . (v - hi v)| <= 2 |q| rho_max, and |(-2q - hi(-2q)) . v| <= |query residual| max|v|  (|hi(-2q)| <= 2 |q| (1 + 2^-8))
+  if (c.trunc) f.E += 1.02f * (2.0f * sqrtf(qn) * c.rho_max * (1.0f + 0.00391f) + (c.trunc == 2u ? sqrtf(qres) * c.vmax : 0.0f));
+  f.distrust = !(qn < 1.0e30f);
+  return f;
+}
+
+// (*) of select.hip: with mk an upper bound, in the query's frame, of the rank values wanted, every vector wanted has a
+// recorded value at or below this.  Anything non-finite or huge, or a distrusted query, means "no bound"
+__device__ __forceinline__ float rank_threshold(const SelectCommon &c, const QueryFrame &f, float mk) {
+  if (f.distrust || !(mk < 1.0e37f)) return INFINITY;
+  const float scale = fmaxf(mk + f.qn, 0.0f) + f.E;
+  return mk + (2.0f * f.E + 3.0f * c.gamma * scale) * 1.001f + 1e-30f;
+}
+
+// ---- a query's probes, as the grouping left them (both list selects) ----
+struct ListProbes {
+  const uint32_t *qoff, *qtot, *rel, *pair_pos, *tile_start;
+  const uint32_t *probes, *gorder, *first_block, *list_len;
+  uint32_t segb0;
+};
+
+inline ListProbes list_probes(const SearchBatch &b) {
+  const SearchWorkspace &ws = b.ws();
+  return ListProbes{ws.qoff.p, ws.qtot.p, ws.pair_rel.p, ws.pair_pos.p, ws.tile_start.p, ws.probes.p, ws.gorder.p,
+                    b.ix.list_first_block.p, b.ix.list_len.p, b.kn.segb0};
+}
+
+// lane r < P: probe r of query q (its list to *mylist, kNoPos for none)
+__device__ __forceinline__ ProbeRegs load_probe_regs(const ListProbes &lp, uint32_t gq, uint32_t q, uint32_t P, int lane,
+                                                     uint32_t *mylist = nullptr) {
+  ProbeRegs pr{0u, 0u, 0u, 0u, 0u, 1u, kNoPos};
+  uint32_t list = kNoPos;
+  if ((uint32_t)lane < P) {
+    const size_t s = (size_t)q * P + lane;
+    list = lp.probes[s];
+    pr.g = lp.gorder[s];
+    pr.rel = lp.rel[s];
+    if (list != kNoPos) {
+      pr.len = lp.list_len[list];
+      pr.fb = lp.first_block[list];
+      const uint32_t pp = lp.pair_pos[s];  // where the pair sits among the pairs of its list
+      const uint32_t nseg = list_segments(pr.len, lp.segb0, &pr.segb);
+      pr.ng = 2u * nseg;
+      pr.boff = (lp.tile_start[list] + (pp / gq) * nseg * seg_records(pr.segb)) * (2u * gq) + (pp % gq);
+    }
+  }
+  if (mylist) *mylist = list;
+  return pr;
+}
+
+// ---- the record walk of one wave: the query's G group records at gbase, the pair records of the groups it flags, and
+//      the sub-blocks those flag for their 16 exact distances ----
+// The first kCacheG group records in LDS, read in one round of loads (the passes over them would otherwise each pay the
+// global-memory latency per 64 groups); the rest are read where they lie.  The cache is read with its address space spelled
+// out: through the generic pointers a wave keeps both 64-bit addresses live across the whole walk, where the kernels
+// have no registers to spare (resource table)
+struct GroupRecords {
+  const SelectCommon &c;
+  size_t gbase;
+  uint32_t G;
+  float4 *tcache;
+  uint32_t *lcache;
+
+  __device__ __forceinline__ void fill(int lane) const {
+    float4 t4[kCacheG / kWave];
+#pragma unroll
+    for (uint32_t ch = 0; ch < kCacheG / kWave; ++ch) {
+      const uint32_t gidx = ch * kWave + lane;
+      t4[ch] = make_float4(INFINITY, INFINITY, INFINITY, INFINITY);
+      if (gidx < G) t4[ch] = c.gval[gbase + gidx];
+    }
+    uint32_t l4[kCacheG / kWave];
+#pragma unroll
+    for (uint32_t ch = 0; ch < kCacheG / kWave; ++ch) {
+      const uint32_t gidx = ch * kWave + lane;
+      l4[ch] = 0u;
+      if (gidx < G) l4[ch] = c.gmeta[gbase + gidx];  // probe rank | segment << 6 | lane half << 13
+    }
+#pragma unroll
+    for (uint32_t ch = 0; ch < kCacheG / kWave; ++ch) {
+      const uint32_t gidx = ch * kWave + lane;
+      if (ch * kWave < G) {
+        tcache[gidx] = t4[ch];
+        lcache[gidx] = l4[ch];
+      }
+    }
+    wave_lds_sync();
+  }
+  __device__ __forceinline__ float4 group_values(uint32_t gidx, bool live) const {
+    float4 T = make_float4(INFINITY, INFINITY, INFINITY, INFINITY);
+    if (live) T = gidx < kCacheG ? lds_f4((const float *)(tcache + gidx)) : c.gval[gbase + gidx];
+    return T;
+  }
+  __device__ __forceinline__ void group_place(uint32_t gidx, bool live, uint32_t &r, uint32_t &seg, uint32_t &hh) const {
+    uint32_t L = 0u;
+    if (live) L = gidx < kCacheG ? *(const VI_AS_LDS uint32_t *)(lcache + gidx) : c.gmeta[gbase + gidx];
+    r = L & 63u; seg = (L >> 6) & 127u; hh = L >> 13;
+  }
+};
+
+// The pair records of the groups flagged `want` (probe rank r, segment seg, lane half hh: group_place), four groups per
+// round (16 lanes x one pair record = the 64 sub-block minima of a 32-block segment half).  Every lane calls;
+// visit(ok, value, j, probe rank, sub-block of the list, lane half) sees component j of every record, ok false where
+// there is no value
+template <class Visit>
+__device__ __forceinline__ void scan_pair_records(const SelectCommon &c, const ProbeRegs &pr, int lane, bool want, uint32_t r, uint32_t seg,
+                                                  uint32_t hh, uint32_t &n_scanned, Visit visit) {
+  uint64_t m = __ballot(want);
+  const uint32_t slot = (uint32_t)lane >> 4, pi = (uint32_t)lane & 15u;
+  while (m) {
+    int src = 0;
+    uint32_t taken = 0;
+#pragma unroll
+    for (uint32_t i = 0; i < 4; ++i)
+      if (m) {
+        const int b = __builtin_ctzll(m);
+        m &= m - 1ull;
+        if (slot == i) src = b;
+        ++taken;
+      }
+    const bool mine = slot < taken;
+    n_scanned += taken;
+    const uint32_t rr = (uint32_t)__shfl((int)r, src), sg = (uint32_t)__shfl((int)seg, src);
+    const uint32_t h2 = (uint32_t)__shfl((int)hh, src);
+    const uint32_t segb = (uint32_t)__shfl((int)pr.segb, (int)rr), ln = (uint32_t)__shfl((int)pr.len, (int)rr);
+    const uint32_t boff = (uint32_t)__shfl((int)pr.boff, (int)rr);
+    const uint32_t nblk = (ln + kWave - 1) / kWave;
+    const uint32_t bs = sg * segb, be = min(nblk, bs + segb);
+    // records of the segment: pair order (record p = blocks 2p, 2p + 1; component j = sub-block 4p + j), or the streaming
+    // kernel's wave order (record p, component j = 32-vector tile 16 (p >> 2) + 4 j + (p & 3))
+    const uint32_t ntile = be > bs ? 2u * (be - bs) : 0u;
+    const uint32_t npairs = !mine ? 0u : (c.wave_order ? 4u * ((ntile + 15u) / 16u) : (ntile + 3u) / 4u);
+    uint32_t mx = npairs;  // wave maximum: segments of very long lists hold more than 16 records
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) mx = max(mx, (uint32_t)__shfl_xor((int)mx, o));
+    for (uint32_t p0 = 0; p0 < mx; p0 += 16u) {
+      const uint32_t p = p0 + pi;
+      const bool live = p < npairs;
+      float4 B = make_float4(INFINITY, INFINITY, INFINITY, INFINITY);
+      if (live) B = c.brec[(size_t)boff + 2u * c.gq * (sg * seg_records(segb) + p) + c.gq * h2];
+      const float bv[4] = {B.x, B.y, B.z, B.w};
+#pragma unroll
+      for (uint32_t j = 0; j < 4; ++j) {
+        const uint32_t tl = c.wave_order ? 16u * (p >> 2) + 4u * j + (p & 3u) : 4u * p + j;  // tile of the segment
+        const bool ok = live && tl < ntile;  // (a record's unused components, and records no wave wrote, are not read as values)
+        visit(ok, bv[j], j, rr, 2u * bs + tl, h2);
+      }
+    }
+  }
+}
+
+// sub-blocks waiting in `pick`: four per round, 16 lanes (= the 16 rows of the sub-block) each;
+// exact(live, probe rank, position) takes one (query, stored vector) pair per lane
+template <class Exact>
+__device__ __forceinline__ void drain_pick(const SelectCommon &c, const uint32_t *pick, uint32_t &npick, int lane, Exact exact) {
+  while (npick > 0) {
+    const uint32_t cnt = npick >= 4u ? 4u : npick;
+    npick -= cnt;
+    const uint32_t rq = (uint32_t)lane >> 4;
+    const bool live = rq < cnt;
+    const uint32_t ck = live ? pick[npick + rq] : 0u;
+    const uint32_t r = ck >> (kSubBits + 1), sub = (ck >> 1) & ((1u << kSubBits) - 1u), hh = ck & 1u;
+    exact(live, r, (sub >> 1) * kWave + subblock_vector((uint32_t)lane & 15u, sub & 1u, hh, c.image_order != 0u));
+  }
+}
+
+// every lane calls; the lanes that `want` queue their sub-block, after drain() has made room where the queue is full
+template <class Drain>
+__device__ __forceinline__ void push_sub(uint32_t *pick, uint32_t &npick, uint32_t &n_sub, int lane, bool want, uint32_t r, uint32_t sub,
+                                         uint32_t hh, Drain drain) {
+  const uint64_t m = __ballot(want);
+  if (!m) return;
+  const uint32_t cnt = (uint32_t)__popcll(m);
+  n_sub += cnt;
+  if (npick + cnt > kPickCap) drain();
+  if (want) pick[npick + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = (r << (kSubBits + 1)) | (sub << 1) | hh;
+  npick += cnt;
+  wave_lds_sync();
+}
 
 // the frame of a list or table ranked with the batch's arithmetic (b.kn), records in b's workspace; the launchers adjust it per phase
 inline SelectCommon select_common(const SearchBatch &b, const float4 *blocks, float xmax2, uint32_t gq, bool wave_order = false, int trunc = 0) {
