@@ -1,4 +1,4 @@
-"""Build-time gate for the hand-placed waits of the double-buffered rank kernels (filter_search.hip, NBUF == 2).
+"""Build-time gate for the hand-placed waits of the double-buffered rank kernels (rank_block.hip, NBUF == 2).
 
 Their block loop issues the next tile's LDS-DMA as inline asm and ends with a counted `s_waitcnt vmcnt(1)` that is only
 correct if the wave's ONE younger vector-memory operation is its pair-record store.  A register spill (scratch traffic),
@@ -13,7 +13,7 @@ import subprocess
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "vector-indexer_amd", "csrc", "filter_search.hip")
+SRC = os.path.join(ROOT, "vector-indexer_amd", "csrc", "rank_block.hip")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 
@@ -21,7 +21,7 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 def asm(tmp_path_factory):
     if not os.path.exists(HIPCC):
         pytest.skip("hipcc not installed")
-    out = str(tmp_path_factory.mktemp("isa") / "filter_search.s")
+    out = str(tmp_path_factory.mktemp("isa") / "rank_block.s")
     flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-fno-slp-vectorize"]
     subprocess.check_call([HIPCC, *flags, "--cuda-device-only", "-S", "-o", out, SRC], stderr=subprocess.DEVNULL)
     return open(out).read()
@@ -30,7 +30,7 @@ def asm(tmp_path_factory):
 def kernels(asm_text):
     """name -> (body text, metadata dict) of every filter_kernel instantiation"""
     out = {}
-    for m in re.finditer(r"^(_ZN2vi12_GLOBAL__N_113filter_kernelILi(\d+)ELi(\d)ELb([01])ELi(\d)ELi(\d+)EEEvNS0_10FilterArgsE):[^\n]*\n(.*?)\n\s*s_endpgm",
+    for m in re.finditer(r"^(_ZN2vi12_GLOBAL__N_113filter_kernelILi(\d+)ELi(\d)ELb([01])ELi(\d)ELi(\d+)EEEvNS_13RankBlockArgsE):[^\n]*\n(.*?)\n\s*s_endpgm",
                          asm_text, re.S | re.M):
         name, ng, nbuf, table, rank, gq, body = m.groups()
         meta = re.search(r"\.amdhsa_kernel " + re.escape(name) + r"\n(.*?)\.end_amdhsa_kernel", asm_text, re.S).group(1)

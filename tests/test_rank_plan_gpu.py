@@ -1,4 +1,4 @@
-"""Which rank kernel a search takes (filter_search.hip: the rank plan), pinned route by route: for every way through the
+"""Which rank kernel a search takes (mfma_search.hip: the rank plan), pinned route by route: for every way through the
 plan the triple (rank_mode, group_queries, rank_int8) of `last_stats()` is the one listed here, and the result is the
 oracle's, ids and distance bits.  Three small indexes, built once: 8-bit descriptors (hi planes only, streaming kernel,
 int8 products for integer batches), real-valued lists (bf16 x 3 or, asked for, their hi planes; about the origin or about
@@ -14,7 +14,7 @@ import vector_indexer_py as vip
 pytestmark = pytest.mark.gpu
 
 KNOBS = ("VI_FILTER", "VI_FILTER_BF16", "VI_FILTER_HI_ONLY", "VI_FILTER_GQ", "VI_RANK_STREAM", "VI_STREAM_GQ", "VI_RANK_I8",
-         "VI_RANK_APPROX", "VI_CENTER", "VI_FORCE_GENERIC")
+         "VI_RANK_APPROX", "VI_CENTER", "VI_FORCE_GENERIC", "VI_STREAM_PROF")
 K, N_PROBE = 10, 8
 
 
@@ -113,6 +113,17 @@ def test_groups_of_256_from_the_second_integer_batch(bytes_index, monkeypatch):
     st = bytes_index.search("integer")
     print("plan", "VI_STREAM_GQ=256", triple(st))
     assert triple(st) == (3, 256, 1), st
+
+
+def test_streaming_kernel_profile_is_printed_and_the_search_unchanged(bytes_index, monkeypatch, capfd):
+    """VI_STREAM_PROF=1: the streaming bf16 kernel counts into its profile block and the pipeline prints it behind the
+    kernel (rank_stream.hip: print_rank_stream_profile); route and result stay what they are without it"""
+    monkeypatch.setenv("VI_STREAM_PROF", "1")
+    st = bytes_index.search("non-integer")
+    err = capfd.readouterr().err
+    print("plan", "VI_STREAM_PROF=1", triple(st))
+    assert triple(st) == (3, 128, 0), st
+    assert any(line.startswith("rank_stream wave-0 ticks") for line in err.splitlines()), err
 
 
 @pytest.mark.parametrize("centre,approx,mode", [("0", "0", 2), ("0", "1", 4), ("1", "0", 5), ("1", "2", 6)])

@@ -226,7 +226,7 @@ def test_generic_path_equals_fast_path(tmp_path, monkeypatch):
                                             (30000, 20, 1100, "gauss"),       # D % 16 != 0: the coarse select reads a table row per lane
                                             (36000, 48, 1100, "clustered")])  # ... and fetches them by the whole wave (3 chunks)
 def test_mfma_filter_path_parity(n, d, nlist, kind, tmp_path, monkeypatch):
-    """VI_FILTER=1 forces the f32-MFMA rank + exact re-evaluation pipeline (filter_search.hip).  Its result must
+    """VI_FILTER=1 forces the f32-MFMA rank + exact re-evaluation pipeline (mfma_search.hip).  Its result must
     be the oracle's, bit for bit, including ties, lists shorter than k and masses of duplicates (whole-group
     re-evaluation).  nlist >= 1024 with >= 256 queries also runs the coarse quantizer on the matrix cores."""
     rng = np.random.default_rng(n + d)

@@ -83,7 +83,7 @@ struct SearchWorkspace {
   DevBuf<uint32_t> counts;      // [nq]
   DevBuf<uint64_t> stats;       // device-side counters (layout: StatWord, search_internal.hpp)
   DevBuf<float> V;
-  // MFMA engine (filter_search.hip)
+  // MFMA engine (mfma_search.hip)
   DevBuf<uint32_t> c_seg, c_item, c_pairs;  // the coarse table grouped as one list ...
   uint64_t c_nq = 0;                        // ... for this batch size
   DevBuf<uint32_t> pair_rel, qtot, qoff;    // group-record offsets: per (query, probe), per query, scan over queries
@@ -99,7 +99,7 @@ struct SearchWorkspace {
   DevBuf<uint32_t> qimg8;                   // int8 image of the batch (q - 127), when the lists have one (split_queries_kernel)
   DevBuf<float> brec;                       // pair records: the 4 sub-block minima of two blocks per (record tile, lane half, query of the group)
   struct GqHint { uint64_t nq; uint32_t P, gq; };
-  std::vector<GqHint> gq_hint;              // queries per rank work item measured to suit a batch shape (filter_search.hip)
+  std::vector<GqHint> gq_hint;              // queries per rank work item measured to suit a batch shape (mfma_search.hip)
   uint64_t *hstats_pinned = nullptr;        // page-locked landing buffer of the grouping's counts (kStatGroupingLanding words)
   bool stats_zeroed = false;                // the batch flags of ws.stats start at zero (StatWord, search_internal.hpp)
   bool queries_hi_only = false;             // the previous batch's -2 q were all bf16-exact (no lo plane)
@@ -179,7 +179,7 @@ struct DeviceIndex {
   float i8_xmax2 = 0.0f;
   bool lists_lo_zero = false, cent_lo_zero = false;  // every stored value is bf16-exact (lo planes all zero)
   // sampled means over the stored vectors: ||v - centroid of its list||^2 and ||v||^2 (what the ranking arithmetic of
-  // real-valued lists is chosen by: filter_search.hip, rank_approx_mode)
+  // real-valued lists is chosen by: mfma_search.hip, rank_approx_mode)
   float mean_spread = 0.0f, mean_norm2 = 0.0f;
   float rho2_max = 0.0f;  // max |x - hi(x)|^2 over the stored vectors (x = v - mu when centred): the hi-plane ranking's margin
   // Real-valued lists far from the origin (SIFT-like values with noise, embeddings with a common offset): the bf16 images

@@ -1,4 +1,4 @@
-// rank_images.hip — index-load time: everything the MFMA engine (filter_search.hip, rank_stream.hip) ranks an index
+// rank_images.hip — index-load time: everything the MFMA engine (rank_block.hip, rank_stream.hip) ranks an index
 // from, derived once from its f32 blocks by prepare_rank_images: squared norms and their maxima, the bf16 hi/lo images
 // (about the mean of the stored vectors where that pays), the hi planes' residual, the row-major coarse table, the
 // sampled list spread, and the u8 / int8 / hi-natural copies of bf16-exact lists.
@@ -561,7 +561,7 @@ vi_status prepare_rank_images(DeviceIndex *ix) {
   DevBuf<uint32_t> word;  // the device word the steps' maxima and flags come back through
   VI_TRY(word.reserve(1));
   VI_TRY(slot_norms(ix, word.p));
-  if ((ix->dim & 3) == 0 && ix->dim <= kMaxFilterDim) {  // (otherwise the MFMA engine never runs: no images)
+  if ((ix->dim & 3) == 0 && ix->dim <= kMaxMfmaDim) {  // (otherwise the MFMA engine never runs: no images)
     VI_TRY(bf16_images(ix, word.p));
     VI_TRY(centre_images(ix, vi_center));
     VI_TRY(hi_plane_residual(ix, word.p));

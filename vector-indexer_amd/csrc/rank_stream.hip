@@ -2,7 +2,7 @@
 //
 // Replaces the workings of ivf_index.rs:205-262 (the per-list distance loop of `search_with_paths`) for a whole batch;
 // what it produces — sub-block minima of a rank value in pair records and the four smallest of a segment in group
-// records — is what filter_search.hip's select turns into the exact top-k.
+// records — is what the select (select.hip) turns into the exact top-k.
 //
 // Work item = one list segment x up to 128 queries that probe it (item_desc_kernel), one workgroup of 4 waves.
 //
@@ -35,6 +35,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <vector>
 
 #include "common.hpp"
 #include "mfma_bf16.hpp"
@@ -597,7 +598,7 @@ vi_status launch_nc(const RankStreamArgs &a, uint32_t nitems, int rank_mode, boo
   // (bf16 x 3 — RANK 1 — compiles but needs two tiles of hi + lo planes in registers: it spills; the pipeline keeps the
   // block-synchronous kernel for it and does not instantiate it here)
   if (rank_mode != 2) return fail(VI_ERR_OTHER, "the streaming rank kernel is built for bf16-exact lists only");
-  if (gq == 256) {  // groups of 256 are formed for batches of bf16-exact queries only (filter_search.hip)
+  if (gq == 256) {  // groups of 256 are formed for batches of bf16-exact queries only (mfma_search.hip: plan_rank)
     if (!qlo) return launch_one<Bf16Form<2, false>, NC, 8>(rank_stream_kernel<NC, 2, false, 8>, a, nitems, st);
     return launch_one<Bf16Form<2, true>, NC, 8>(rank_stream_kernel<NC, 2, true, 8>, a, nitems, st);
   }
@@ -636,6 +637,38 @@ vi_status launch_rank_stream_i8(const RankStreamI8Args &a, uint32_t nc32, uint32
     case 4: return launch_nc_i8<4>(a, nitems, gq, st);
     default: return fail(VI_ERR_OTHER, "unsupported dimension for the int8 rank kernel");
   }
+}
+
+// the counter block as rank_stream_body leaves it: totals h[0..18], then {start, end, items, multiply ticks} per workgroup
+vi_status print_rank_stream_profile(const uint64_t *prof_dev, const char *dump_path, hipStream_t st) {
+  constexpr int kTotals = 32, kWorkgroups = (kRankStreamProfWords - kTotals) / 4;
+  uint64_t h[24];
+  VI_HIP(hipMemcpyAsync(h, prof_dev, sizeof(h), hipMemcpyDeviceToHost, st));
+  VI_HIP(hipStreamSynchronize(st));
+  fprintf(stderr, "rank_stream wave-0 ticks (100 MHz) summed over workgroups: multiply %llu (of which waiting for tiles %llu) "
+          "end-of-item wait %llu gather %llu merge %llu | items %llu steps %llu | loop total %llu\n",
+          (unsigned long long)h[0], (unsigned long long)h[6], (unsigned long long)h[1], (unsigned long long)h[2],
+          (unsigned long long)h[3], (unsigned long long)h[4], (unsigned long long)h[5], (unsigned long long)h[7]);
+  if (dump_path) {
+    std::vector<uint64_t> w(4 * kWorkgroups);
+    VI_HIP(hipMemcpy(w.data(), prof_dev + kTotals, w.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    if (FILE *f = fopen(dump_path, "w")) {
+      uint64_t base = ~0ull;
+      for (int i = 0; i < kWorkgroups; ++i) if (w[4 * i + 1]) base = std::min(base, w[4 * i]);
+      for (int i = 0; i < kWorkgroups; ++i)  // workgroup, start, end (10 ns ticks after the first start), items
+        if (w[4 * i + 1]) fprintf(f, "%d %llu %llu %llu\n", i, (unsigned long long)(w[4 * i] - base), (unsigned long long)(w[4 * i + 1] - base),
+                                  (unsigned long long)w[4 * i + 2]);
+      fclose(f);
+    }
+  }
+  fprintf(stderr, "   loops entered over %llu ticks, last exit %llu ticks after the first entry\n", (unsigned long long)(h[17] - h[16]),
+          (unsigned long long)(h[18] - h[16]));
+  fprintf(stderr, "   longest workgroup loop %llu ticks, workgroups with items %llu, most items in one %llu\n", (unsigned long long)h[13],
+          (unsigned long long)h[14], (unsigned long long)h[15]);
+  fprintf(stderr, "   after B1: T+idx %llu, DMA issue %llu, vmcnt(0) %llu, B2 %llu | after B2: merge+stores %llu, idx read %llu, load_item %llu\n",
+          (unsigned long long)h[8], (unsigned long long)h[9], (unsigned long long)h[10], (unsigned long long)h[2],
+          (unsigned long long)h[11], (unsigned long long)h[12], (unsigned long long)h[3]);
+  return VI_OK;
 }
 
 }  // namespace vi

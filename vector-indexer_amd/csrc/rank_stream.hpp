@@ -1,4 +1,4 @@
-// rank_stream.hpp — the streaming list-rank kernel (rank_stream.hip) as filter_search.hip's pipeline launches it.
+// rank_stream.hpp — the streaming list-rank kernel (rank_stream.hip) as mfma_search.hip's pipeline launches it.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -19,16 +19,22 @@ struct RankStreamArgs {
   uint32_t *queue;       // work counter, zero at launch
   float4 *gval;         // group records (their place words are written by group_place_kernel)
   float4 *brec;         // pair records, wave order (scan.hpp: seg_records)
-  unsigned long long *prof;  // diagnostic: 8 counters of phase clocks (rank_stream.hip), or null
+  unsigned long long *prof;  // diagnostic: the counter block of phase clocks below (kRankStreamProfWords), or null
   uint32_t xmode;       // ablation knob (VI_FILTER_XMODE): 1 tiles not re-read, 2 no ranking epilogue, 8 no record store
 };
+// 64-bit words of the counter block `prof` points at: 32 of totals (zero at launch, word 16 all ones: a minimum), then
+// 4 per workgroup
+constexpr uint32_t kRankStreamProfWords = 32 + 4 * 1024;
+// (VI_STREAM_PROF) the block's phase clocks to stderr, read back behind the kernel on st: synchronises.  dump_path (or
+// null: VI_STREAM_PROF_DUMP): a file for the per-workgroup clocks
+vi_status print_rank_stream_profile(const uint64_t *prof_dev, const char *dump_path, hipStream_t st);
 
 // rank_mode 1: bf16 x 3; 2: the stored vectors are bf16-exact (hi planes only); qlo: the batch's queries have a lo plane
 // gq: queries per work item the grouping formed, 128 or 256
 vi_status launch_rank_stream(const RankStreamArgs &a, uint32_t nc, uint32_t nitems, int rank_mode, bool qlo, uint32_t gq, hipStream_t st);
 
 // 8-bit descriptors (every stored value an integer in 0..255) against queries of integers in 0..254: the same work items
-// ranked with exact int8 products, in the frame shifted by 127 (rank_images.hip: i8_image_kernel; filter_search.hip: split_queries_kernel).
+// ranked with exact int8 products, in the frame shifted by 127 (rank_images.hip: i8_image_kernel; mfma_search.hip: split_queries_kernel).
 // Rank value of (q, v): 2 r with r = h(v) - q'.v', q' = q - 127, v' = v - 127, h(v) = ceil(|v'|^2 / 2) — an integer with
 // |v'|^2 - 2 q'.v' <= 2 r <= |v'|^2 - 2 q'.v' + 1, stored as a float (exact below 2^24).
 struct RankStreamI8Args {

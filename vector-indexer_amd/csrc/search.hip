@@ -1,6 +1,6 @@
 // search.hip — the dispatcher: the two public entries (device_index_search, device_index_range_search) and what is common
 // to the three engines behind them.  An entry leases a SearchContext of the handle, opens a SearchBatch on it (checks, the
-// clamp of n_probe, the stats reset, the knobs, the queries on the device), picks the engine — MFMA (filter_search.hip),
+// clamp of n_probe, the stats reset, the knobs, the queries on the device), picks the engine — MFMA (mfma_search.hip),
 // exact-order VALU (search_kernels.hip) or generic (generic_search.hip) — hands it the batch and closes it (stripe ties,
 // the one synchronisation, phase times).  Also here: the RangeResult assembly the radius engines fill chunk by chunk.
 #include <hip/hip_runtime.h>

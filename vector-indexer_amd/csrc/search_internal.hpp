@@ -1,9 +1,9 @@
 // search_internal.hpp — what the search engines' and the index builders' translation units (search.hip, search_kernels.hip,
-// generic_search.hip, filter_search.hip, grouping.hip, select.hip, range_select.hip, rank_images.hip, device_index.hip,
+// generic_search.hip, mfma_search.hip, grouping.hip, select.hip, range_select.hip, rank_images.hip, device_index.hip,
 // list_build.hip, list_update.hip, kmeans.hip, similar_search.hip, cluster_radius.hip) call in each other and share: declared once, here.  A search is one
 // SearchBatch, built by the dispatcher (search.hip) and handed to the engine it chose; the engines hand it on to their
-// stages.  (The probe grouping is called through a header of its own, grouping.hpp; filter_search.hip launches its rank
-// and select phases through rank_stream.hpp and select.hpp.)
+// stages.  (The probe grouping is called through a header of its own, grouping.hpp; mfma_search.hip launches its rank
+// and select phases through rank_block.hpp, rank_stream.hpp and select.hpp.)
 #pragma once
 #include <algorithm>
 #include <array>
@@ -15,7 +15,7 @@
 
 namespace vi {
 
-constexpr uint32_t kMaxFilterDim = 1536;  // the MFMA engine's dimension limit (rank_wide_kernel above 128)
+constexpr uint32_t kMaxMfmaDim = 1536;  // the MFMA engine's dimension limit (rank_wide_kernel above 128)
 constexpr uint32_t kNarrowDim = 128;     // up to here the queries of a work item stay in registers (filter_kernel)
 
 // ---- SearchWorkspace::stats: the engines' block of 64-bit device counters, by word ----
@@ -165,7 +165,7 @@ vi_status stage_coarse(SearchBatch &b);                   // ws.probes / gorder 
 vi_status adopt_probes(SearchBatch &b, bool histogram);   // ... from b.probes_in / order_in, validated
 vi_status search_valu_pipeline(SearchBatch &b, uint64_t k, const SelectOutputs &out);
 
-// ---- filter_search.hip: the MFMA engine ----
+// ---- mfma_search.hip: the MFMA engine ----
 vi_status search_mfma_pipeline(SearchBatch &b, uint64_t k, const SelectOutputs &out);
 vi_status range_mfma_pipeline(SearchBatch &b, float radius2, RangeResult *res);
 vi_status coarse_only_mfma(SearchBatch &b);

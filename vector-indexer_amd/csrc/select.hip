@@ -1,4 +1,4 @@
-// select.hip — the select phase of the MFMA engine: from the records the rank kernels leave (filter_search.hip,
+// select.hip — the select phase of the MFMA engine: from the records the rank kernels leave (rank_block.hip,
 // rank_stream.hip) to the exact top-k, for the lists (select_kernel) and for the coarse table (coarse_select_kernel,
 // coarse_select_direct_kernel).  Only the records are shared with the rank kernels; what a record holds and where it
 // sits is described there and in scan.hpp.

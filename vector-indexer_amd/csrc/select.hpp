@@ -1,4 +1,4 @@
-// select.hpp — the select phase of the MFMA engine (select.hip, range_select.hip) as filter_search.hip's pipelines launch it
+// select.hpp — the select phase of the MFMA engine (select.hip, range_select.hip) as mfma_search.hip's pipelines launch it
 // on their SearchBatch (search_internal.hpp), and the constants both sides must agree on.
 #pragma once
 #include <hip/hip_runtime.h>
