@@ -728,6 +728,65 @@ typedef struct vi_cluster_stats {
 } vi_cluster_stats;
 vi_status vi_cluster_last_stats(vi_cluster_stats *out);
 
+/* ---- extension: adaptive probing — per-query probe counts by distance ratio, code budget or list ---------------------
+ * Every search entry above takes one n_probe for the whole batch.  Here n_probe is the UPPER bound and a rule decides,
+ * per query, how many of its probes are searched: a prefix of its probe row.  For a row with `found` real probes in
+ * coarse order, their exact coarse distances d_r (euclidean_distance_squared of the query and the centroid, the bits
+ * the coarse step sorts by) and the full lengths of their lists, the number of probes kept is
+ *
+ *     p_q = clamp(min(p_ratio, p_codes, p_explicit),  lo = min(max(min_probe, 1), found),  hi = found)
+ *
+ *   p_ratio    = #{ r < found : d_r <= t },  t = fl32(ratio2 * d_0): one rounded f32 multiply, compared in f32.
+ *                ratio2 == 0: off.  d_0 == 0 keeps exactly the centroids at distance bits 0.
+ *   p_codes    = the smallest p >= 1 whose first p lists hold >= max_codes vectors together — the list that crosses the
+ *                budget is still searched (Faiss's IndexIVF.max_codes) — or `found` if they never do.  max_codes == 0: off.
+ *   p_explicit = n_probe_q[q].  NULL: off.
+ *
+ * Exactness is the library's: the pruned search of query q is, bit for bit, the search of q alone with n_probe = p_q —
+ * ids, distance bits, counts, padding and tie keys.  (The reference sorts centroids by (distance, index), so a prefix of
+ * a probe row is the probe row of a smaller n_probe, and its shard visiting order restricted to a prefix is the prefix's
+ * own: the candidate-order ranks of the kept probes are the old ranks closed up.)  A zero-initialised rule prunes
+ * nothing, and pruning is idempotent: a row that already carries markers is pruned over its real probes.
+ *
+ *   vi_indexer_prune_probes_device   in place, between vi_indexer_probe_device and vi_indexer_search_probed_device (the
+ *                                    multi-GPU seam): probes r >= p_q of a row and their order words become the marker
+ *                                    0xFFFFFFFF, the orders of the kept probes are closed up.  queries_dev: the nq
+ *                                    queries the rows belong to; rows as vi_indexer_search_probed_device takes them
+ *                                    (anything else is VI_ERR_INVALID_INPUT); n_kept_dev (optional, nq u32): p_q.
+ *   vi_indexer_search_adaptive       one call: the coarse step ONCE, the prune, the list phase over the pruned rows, all
+ *   vi_indexer_search_adaptive_device  on the device.  Outputs as vi_indexer_search_filtered / _filtered_device, plus
+ *                                    n_probed (optional, nq u32: p_q).  f == NULL: no filter.
+ *   - n_probe is clamped to max_n_probe and k to max_k, as always (k_out); a zero rule returns bit for bit what
+ *     vi_indexer_search_filtered* returns: D, I, tie, counts and V
+ *   - VI_ERR_INVALID_INPUT before any device work, outputs untouched: a null ix or rule; a handle with no index; ratio2
+ *     NaN, infinite, negative or in (0, 1); n_probe == 0 or k == 0; a query_dim mismatch; a foreign or stale filter;
+ *     max_codes != 0 on a partitioned handle (its lists hold resident lengths only).  The ratio and the explicit rule
+ *     work on partitioned handles: the coarse table is replicated, every rank prunes alike
+ *   - vi_indexer_last_stats afterwards reads as after the underlying search; its scanned_vectors is where the saving shows
+ *   - threads: the contract of a search
+ *   - n_probe_q: host memory for vi_indexer_search_adaptive, device memory for the two _device entries
+ * Out of scope: radius search, the calls whose queries are stored records, and clustering take no rule.
+ * vi_prune_last_stats: of the calling thread's last call of the three — the real probes its rows held, the probes kept,
+ * and, only while the environment variable VI_PRUNE_TIMING is set (and not "0"), the HIP-event time of
+ * probe_prune_kernel (zero otherwise).  Zeros after a call that failed or pruned nothing (nq == 0, an empty index: its
+ * n_probed is all zero).  Any of the three pointers may be NULL, not all. */
+typedef struct vi_probe_rule {
+  uint32_t min_probe;        /* 0 => 1 */
+  float    ratio2;           /* 0 = off; else finite and >= 1 */
+  uint64_t max_codes;        /* 0 = off */
+  const uint32_t *n_probe_q; /* NULL = off; nq entries, host memory for the host entry, device for _device */
+} vi_probe_rule;
+vi_status vi_indexer_prune_probes_device(const vi_indexer *ix, const float *queries_dev, uint64_t nq, uint64_t n_probe_eff,
+                                         uint32_t *probes_dev, uint32_t *order_dev, const vi_probe_rule *rule,
+                                         uint32_t *n_kept_dev);
+vi_status vi_indexer_search_adaptive(const vi_indexer *ix, const vi_filter *f, const vi_probe_rule *rule, const float *queries,
+                                     uint64_t nq, uint32_t query_dim, uint64_t k, uint64_t n_probe, float *D, int64_t *I,
+                                     float *V, uint64_t *counts, uint32_t *n_probed, uint64_t *k_out);
+vi_status vi_indexer_search_adaptive_device(const vi_indexer *ix, const vi_filter *f, const vi_probe_rule *rule,
+                                            const float *queries_dev, uint64_t nq, uint64_t k, uint64_t n_probe,
+                                            float *D_dev, int64_t *I_dev, uint64_t *tie_dev, uint32_t *n_probed_dev);
+vi_status vi_prune_last_stats(uint64_t *probes_in, uint64_t *probes_kept, float *ms_prune);
+
 /* Merge `parts` per-rank partial results (each nq x k, device pointers laid out
  * [part][nq][k]) into the global top-k with the reference's stable order. */
 vi_status vi_merge_partials_device(int32_t device, uint64_t nq, uint64_t k, uint32_t parts,

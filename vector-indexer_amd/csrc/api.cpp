@@ -16,6 +16,7 @@
 #include "device_index.hpp"
 #include "kmeans.hpp"
 #include "list_layout.hpp"
+#include "probe_rules.hpp"
 #include "record_fetch.hpp"
 #include "rng.hpp"
 #include "shards.hpp"
@@ -965,6 +966,95 @@ vi_status vi_indexer_search_probed_device(const vi_indexer *ix, const float *que
                                           uint64_t *tie_dev) {
   return vi_indexer_search_probed_filtered_device(ix, nullptr, queries_dev, nq, k, n_probe_eff, probes_dev, order_dev, D_dev,
                                                   I_dev, tie_dev);
+}
+
+// ---- adaptive probing (probe_prune.hip) ----
+// The checks the three entries share, all before any device work; on VI_OK *k and *n_probe are clamped, *flt is set and
+// *pr carries the rule.
+// query_dim: of the entry that takes one, else null.
+static vi_status adaptive_common(const vi_indexer *ix, const vi_filter *f, const vi_probe_rule *rule, const uint32_t *query_dim,
+                                 uint64_t *k, uint64_t *n_probe, const vi::SlotFilter **flt, vi::ProbePrune *pr) {
+  vi::prune_reset_stats();  // (vi_prune_last_stats reads zeros after a call that failed or pruned nothing)
+  VI_TRY(search_common(ix, k, n_probe));
+  if (!rule) return fail(VI_ERR_INVALID_INPUT, "null probe rule");
+  if (!vi::probe_ratio_legal(rule->ratio2)) return fail(VI_ERR_INVALID_INPUT, "ratio2 must be 0 (off) or finite and >= 1");
+  if (*k == 0 || *n_probe == 0) return fail(VI_ERR_INVALID_INPUT, "k and n_probe must be greater than 0");
+  if (query_dim && *query_dim != ix->impl.cfg.dimension)
+    return fail(VI_ERR_INVALID_INPUT, "query dimension mismatch: expected %u, got %u", ix->impl.cfg.dimension, *query_dim);
+  if (rule->max_codes != 0 && (ix->impl.cfg.world_size > 1 || (ix->impl.dev && ix->impl.dev->stripe_world > 1)))
+    return fail(VI_ERR_INVALID_INPUT, "max_codes needs the whole index on one handle: a partitioned handle knows the resident "
+                "lengths of its lists only (the ratio and the per-query counts work on every rank)");
+  VI_TRY(filter_common(ix, f, flt));
+  if (!ix->impl.dev) return fail(VI_ERR_INVALID_INPUT, "the indexer holds no index (build or load it first)");
+  pr->min_probe = rule->min_probe; pr->ratio2 = rule->ratio2; pr->max_codes = rule->max_codes; pr->n_probe_q = rule->n_probe_q;
+  return VI_OK;
+}
+
+vi_status vi_indexer_prune_probes_device(const vi_indexer *ix, const float *queries_dev, uint64_t nq, uint64_t n_probe_eff,
+                                         uint32_t *probes_dev, uint32_t *order_dev, const vi_probe_rule *rule,
+                                         uint32_t *n_kept_dev) {
+  return vi::guarded([&]() -> vi_status {
+  uint64_t k = 1, n_probe = n_probe_eff;
+  const vi::SlotFilter *flt = nullptr;
+  vi::ProbePrune pr;
+  VI_TRY(adaptive_common(ix, nullptr, rule, nullptr, &k, &n_probe, &flt, &pr));
+  if (n_probe_eff != std::min<uint64_t>(n_probe, ix->impl.meta.k()))
+    return fail(VI_ERR_INVALID_INPUT, "n_probe_eff does not match this index (use the value vi_indexer_probe_device returned)");
+  if (nq == 0) return VI_OK;
+  if (!queries_dev || !probes_dev || !order_dev) return fail(VI_ERR_INVALID_INPUT, "null pointer");
+  pr.n_kept = n_kept_dev;
+  return vi::device_index_prune_probes(*ix->impl.dev, queries_dev, nq, (uint32_t)n_probe_eff, probes_dev, order_dev, pr);
+  });
+}
+
+vi_status vi_indexer_search_adaptive(const vi_indexer *ix, const vi_filter *f, const vi_probe_rule *rule, const float *queries,
+                                     uint64_t nq, uint32_t query_dim, uint64_t k, uint64_t n_probe, float *D, int64_t *I,
+                                     float *V, uint64_t *counts, uint32_t *n_probed, uint64_t *k_out) {
+  return vi::guarded([&]() -> vi_status {
+  const vi::SlotFilter *flt = nullptr;
+  vi::ProbePrune pr;
+  VI_TRY(adaptive_common(ix, f, rule, &query_dim, &k, &n_probe, &flt, &pr));
+  if (k_out) *k_out = k;
+  if (nq == 0) return VI_OK;
+  if (!queries || !D || !I) return fail(VI_ERR_INVALID_INPUT, "null pointer");
+  for (uint64_t i = 0; i < nq * (uint64_t)query_dim; ++i)  // (as vi_indexer_search_filtered)
+    if (!std::isfinite(queries[i])) return fail(VI_ERR_PANIC, "non-finite query value at flat index %llu", (unsigned long long)i);
+  pr.n_kept = n_probed;
+  vi::SearchIO io;
+  io.queries = queries; io.nq = nq; io.k = k; io.n_probe = n_probe;
+  io.D = D; io.I = I; io.V = V; io.counts = counts;
+  io.filter = flt; io.prune = &pr;
+  return vi::device_index_search(*ix->impl.dev, io);
+  });
+}
+
+vi_status vi_indexer_search_adaptive_device(const vi_indexer *ix, const vi_filter *f, const vi_probe_rule *rule,
+                                            const float *queries_dev, uint64_t nq, uint64_t k, uint64_t n_probe,
+                                            float *D_dev, int64_t *I_dev, uint64_t *tie_dev, uint32_t *n_probed_dev) {
+  return vi::guarded([&]() -> vi_status {
+  const vi::SlotFilter *flt = nullptr;
+  vi::ProbePrune pr;
+  VI_TRY(adaptive_common(ix, f, rule, nullptr, &k, &n_probe, &flt, &pr));
+  if (nq == 0) return VI_OK;
+  if (!queries_dev || !D_dev || !I_dev) return fail(VI_ERR_INVALID_INPUT, "null pointer");
+  pr.n_kept = n_probed_dev;
+  vi::SearchIO io;
+  io.queries = queries_dev; io.on_device = true; io.nq = nq; io.k = k; io.n_probe = n_probe;
+  io.D = D_dev; io.I = I_dev; io.tie = tie_dev;
+  io.filter = flt; io.prune = &pr;
+  return vi::device_index_search(*ix->impl.dev, io);
+  });
+}
+
+vi_status vi_prune_last_stats(uint64_t *probes_in, uint64_t *probes_kept, float *ms_prune) {
+  return vi::guarded([&]() -> vi_status {
+  if (!probes_in && !probes_kept && !ms_prune) return fail(VI_ERR_INVALID_INPUT, "null pointer: no output asked for");
+  const vi::PruneStats s = vi::prune_last_stats();
+  if (probes_in) *probes_in = s.probes_in;
+  if (probes_kept) *probes_kept = s.probes_kept;
+  if (ms_prune) *ms_prune = s.ms_prune;
+  return VI_OK;
+  });
 }
 
 // ---- the entries whose queries are stored records (similar_search.hip, cluster_radius.hip) ----

@@ -63,6 +63,12 @@ struct SearchWorkspace {
   DevBuf<uint32_t> probes;      // [nq][P] list ids in probe-rank order
   DevBuf<uint32_t> gorder;      // [nq][P] candidate-order rank of each probe (shard visiting order)
   DevBuf<uint32_t> probe_flag;  // validation result of caller-supplied probe lists
+  // adaptive probing (probe_prune.hip): real and kept probes per query [2][nq], their two sums and the page-locked words
+  // the sums land in; a host caller's per-query counts in, kept counts out
+  DevBuf<uint32_t> prune_counts;
+  DevBuf<uint64_t> prune_totals;
+  uint64_t *prune_pinned = nullptr;
+  DevBuf<uint32_t> prune_limit, prune_kept;
   DevBuf<uint32_t> cnt;         // [nlists] (#queries probing list) ; cursor = second half
   DevBuf<uint32_t> list_tot;    // [nlists] queries probing each list
   DevBuf<uint32_t> seg_start;   // [nlists+1]
@@ -201,7 +207,10 @@ struct DeviceIndex {
   struct SearchContext : StreamEvents<6> {
     SearchWorkspace ws;
     vi_search_stats stats{};
-    ~SearchContext() { if (ws.hstats_pinned) (void)hipHostFree(ws.hstats_pinned); }
+    ~SearchContext() {
+      if (ws.hstats_pinned) (void)hipHostFree(ws.hstats_pinned);
+      if (ws.prune_pinned) (void)hipHostFree(ws.prune_pinned);
+    }
   };
   mutable ContextPool<SearchContext, 4> search_contexts;
   mutable vi_search_stats last_stats{};  // of the most recent search that finished on this handle (under the pool's lock)
@@ -260,6 +269,27 @@ vi_status device_index_update(const DeviceIndex &old, const SlotFilter *keep, co
                               const uint64_t *row_ext_dev, const uint64_t *row_ts_dev, const std::vector<uint32_t> &old_len_host,
                               DeviceIndex *out, float *ms_kernel, uint64_t *kernel_bytes);
 
+// ---- adaptive probing (probe_prune.hip, probe_rules.hpp): per-query probe counts between coarse step and list phase ----
+// A search's rule (vi_probe_rule) and where the number of probes each query kept goes.  The two arrays are host memory on
+// a search with host queries, device memory otherwise.
+struct ProbePrune {
+  uint32_t min_probe = 0;
+  float ratio2 = 0.0f;
+  uint64_t max_codes = 0;
+  const uint32_t *n_probe_q = nullptr;  // nq counts, optional
+  uint32_t *n_kept = nullptr;           // nq, optional
+};
+// probe rows [nq][P] of a coarse step (device), pruned in place over the queries they belong to; the rows are validated as
+// a list phase validates them.  Synchronised on return.
+vi_status device_index_prune_probes(const DeviceIndex &ix, const float *queries_dev, uint64_t nq, uint32_t P, uint32_t *probes_dev,
+                                    uint32_t *order_dev, const ProbePrune &rule);
+// of this thread's last pruning call (device_index_prune_probes, or a search with SearchIO::prune): real probes in, probes
+// kept, and under VI_PRUNE_TIMING (set, not '0') the HIP-event time of probe_prune_kernel; zeros after a call that failed
+// or pruned nothing (no query, an empty index): the entries of the C ABI reset them first (prune_reset_stats)
+struct PruneStats { uint64_t probes_in = 0, probes_kept = 0; float ms_prune = 0.0f; };
+PruneStats prune_last_stats();
+void prune_reset_stats();
+
 struct SearchIO {
   const float *queries = nullptr;  // host or device (queries_on_device)
   bool on_device = false;          // queries and D/I/tie are device pointers
@@ -274,6 +304,7 @@ struct SearchIO {
   const uint32_t *probes_in = nullptr, *order_in = nullptr;  // skip the coarse step, use these probe lists
   uint32_t *probes_out = nullptr, *order_out = nullptr;      // coarse step only: probe lists + candidate-order ranks
   const SlotFilter *filter = nullptr;  // restrict the candidates to the filter's slots (the coarse step never sees it)
+  const ProbePrune *prune = nullptr;   // adaptive probing: the rows of this search's own coarse step pruned before its list phase
 };
 vi_status device_index_search(const DeviceIndex &ix, const SearchIO &io);
 

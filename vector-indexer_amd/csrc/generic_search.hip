@@ -349,6 +349,10 @@ vi_status generic_prepare(SearchBatch &b, std::vector<uint64_t> &h_total) {
   } else {
     VI_TRY(generic_coarse(b));
     VI_TRY(generic_candidate_order(b, false));
+    if (b.prune) {  // adaptive probing: the rows shortened, then placed by their closed-up order as a caller's rows are
+      VI_TRY(prune_staged_probes(b, false));
+      VI_TRY(generic_candidate_order(b, true));
+    }
   }
   h_total.resize(nq);
   VI_HIP(hipMemcpyAsync(h_total.data(), ws.total.p, nq * 8, hipMemcpyDeviceToHost, b.st()));

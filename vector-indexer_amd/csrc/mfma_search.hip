@@ -364,11 +364,11 @@ vi_status coarse_phase(SearchBatch &b) {
   } else {
     VI_TRY(build_query_image(b));
   }
-  if (coarse_mfma) {
-    VI_TRY(stage_coarse_mfma(b, histogram_cleared));
-  } else {
-    if (b.probes_in) VI_TRY(adopt_probes(b, true));
-    else VI_TRY(stage_coarse(b));
+  if (coarse_mfma) VI_TRY(stage_coarse_mfma(b, histogram_cleared));
+  else if (b.probes_in) VI_TRY(adopt_probes(b, true));
+  else VI_TRY(stage_coarse(b));
+  VI_TRY(prune_staged_probes(b, true));  // (adaptive probing: shorter rows, their histogram, no pair ranks)
+  if (!coarse_mfma || b.prune) {  // (the coarse select on the matrix cores leaves the record offsets of its own rows)
     hipLaunchKernelGGL(pair_groups_kernel, dim3((uint32_t)((b.nq + 255) / 256)), dim3(256), 0, b.st(), ws.probes.p,
                        b.ix.list_len.p, (uint32_t)b.nq, b.P, b.kn.segb0, ws.pair_rel.p, ws.qtot.p);
   }

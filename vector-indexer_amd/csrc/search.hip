@@ -141,6 +141,10 @@ vi_status topk_search(const DeviceIndex &ix, SearchContext &ctx, const SearchIO 
       if (io.counts) std::memset(io.counts, 0, nq * 8);
       if (io.V) std::memset(io.V, 0, nq * k * dim * 4);
     }
+    if (io.prune && io.prune->n_kept) {  // adaptive probing: no query probed anything
+      if (io.on_device) VI_HIP(hipMemset(io.prune->n_kept, 0, nq * sizeof(uint32_t)));
+      else std::memset(io.prune->n_kept, 0, nq * sizeof(uint32_t));
+    }
     return VI_OK;
   }
 
@@ -154,6 +158,11 @@ vi_status topk_search(const DeviceIndex &ix, SearchContext &ctx, const SearchIO 
     return VI_OK;
   }
   b.timing = generic ? 0 : ix.timing;
+  PruneRun prune;  // adaptive probing: the engine prunes the rows of its coarse step before its list phase
+  if (io.prune && !io.probes_in) {
+    VI_TRY(prune_begin(prune, io.prune, !io.on_device));
+    b.prune = &prune;
+  }
   if (generic) VI_TRY(device_index_search_generic(b, k, out));  // (k > 128 or n_probe > 64, with the caller's probe lists too)
   else if (mfma_ok) VI_TRY(search_mfma_pipeline(b, k, out));
   else VI_TRY(search_valu_pipeline(b, k, out));
@@ -176,7 +185,9 @@ vi_status topk_search(const DeviceIndex &ix, SearchContext &ctx, const SearchIO 
       for (uint64_t i = 0; i < nq; ++i) io.counts[i] = c32[i];
     }
   }
-  return close_batch(b, out.tie, nq * k);  // (host outputs carry no tie keys)
+  VI_TRY(close_batch(b, out.tie, nq * k));  // (host outputs carry no tie keys)
+  if (b.prune) prune_finish(prune);
+  return VI_OK;
 }
 
 namespace {

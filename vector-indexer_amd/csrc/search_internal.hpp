@@ -1,6 +1,6 @@
 // search_internal.hpp — what the search engines' and the index builders' translation units (search.hip, search_kernels.hip,
 // generic_search.hip, mfma_search.hip, grouping.hip, select.hip, range_select.hip, rank_images.hip, device_index.hip,
-// list_build.hip, list_update.hip, kmeans.hip, similar_search.hip, cluster_radius.hip) call in each other and share: declared once, here.  A search is one
+// list_build.hip, list_update.hip, kmeans.hip, similar_search.hip, cluster_radius.hip, probe_prune.hip) call in each other and share: declared once, here.  A search is one
 // SearchBatch, built by the dispatcher (search.hip) and handed to the engine it chose; the engines hand it on to their
 // stages.  (The probe grouping is called through a header of its own, grouping.hpp; mfma_search.hip launches its rank
 // and select phases through rank_block.hpp, rank_stream.hpp and select.hpp.)
@@ -83,6 +83,15 @@ vi_status upload(DevBuf<T> &buf, const T *host, size_t n, hipStream_t st) {
 
 // ---- one search: what every stage of it works from ----
 using SearchContext = DeviceIndex::SearchContext;
+// one pruning call as it runs (probe_prune.hip): its rule, the kernel's two sums on their way back, its clock
+struct PruneRun {
+  const ProbePrune *rule = nullptr;
+  bool host = false;        // the rule's arrays are host memory
+  hipStream_t pending = nullptr;  // the stream whose copies into this object (and the rule's host array) are not known to have landed
+  const uint64_t *totals = nullptr;  // the workspace's landing words: sum of real probes, sum of probes kept
+  EventSpans<1> span;       // around probe_prune_kernel, under VI_PRUNE_TIMING
+  ~PruneRun() { if (pending) (void)hipStreamSynchronize(pending); }  // (a call that failed behind the kernel: nothing lands later)
+};
 struct SearchBatch {
   const DeviceIndex &ix;
   SearchContext &ctx;      // leased for this call: workspace, stats, events and THE stream of this search
@@ -97,6 +106,7 @@ struct SearchBatch {
   // counts of ws.stats; (MFMA engine) the event in front of the rank kernel is recorded; the grouping's scatter left the
   // streaming rank kernel's work items behind (item_push_kernel)
   bool pair_rank_valid = false, group_counts_cleared = false, rank_clock_started = false, items_pushed = false;
+  PruneRun *prune = nullptr;  // adaptive probing: every engine prunes the rows of its coarse step (prune_staged_probes), or null
   SearchWorkspace &ws() const { return ctx.ws; }
   hipStream_t st() const { return ctx.stream; }
 };
@@ -163,6 +173,9 @@ vi_status stored_record_call(const DeviceIndex &ix, Report &last, Body body) {
 // ---- search_kernels.hip: the exact-order VALU engine ----
 vi_status stage_coarse(SearchBatch &b);                   // ws.probes / gorder and the per-list histogram (ws.cnt)
 vi_status adopt_probes(SearchBatch &b, bool histogram);   // ... from b.probes_in / order_in, validated
+// what adopt_probes validates: rows [nq][P] of a caller (device) by validate_probes_kernel; synchronises st
+vi_status validate_probe_rows(const DeviceIndex &ix, SearchWorkspace &ws, const uint32_t *probes, const uint32_t *order, uint64_t nq,
+                              uint32_t P, hipStream_t st);
 vi_status search_valu_pipeline(SearchBatch &b, uint64_t k, const SelectOutputs &out);
 
 // ---- mfma_search.hip: the MFMA engine ----
@@ -177,6 +190,15 @@ vi_status device_index_search_generic(SearchBatch &b, uint64_t k, const SelectOu
 vi_status device_index_range_generic(SearchBatch &b, float radius2, RangeResult *res);
 vi_status generic_probe_export(SearchBatch &b);
 vi_status sort_rows_u64(uint64_t *keys, uint64_t nrows, uint32_t logL, hipStream_t st);  // rows of 2^logL keys, each sorted ascending
+
+// ---- probe_prune.hip: adaptive probing ----
+// A search with a rule: prune_begin opens the run (this thread's PruneStats reset, the clock made), every engine calls
+// prune_staged_probes behind its coarse step — ws.probes / ws.gorder pruned in place, the coarse step's per-list
+// histogram counted again from the shortened rows if asked, the coarse select's pair ranks dropped; a batch without a
+// run: nothing — and prune_finish, once the search's stream is synchronised, publishes the thread's PruneStats.
+vi_status prune_begin(PruneRun &run, const ProbePrune *rule, bool host);
+vi_status prune_staged_probes(SearchBatch &b, bool histogram);
+void prune_finish(PruneRun &run);
 
 // ---- rank_images.hip ----
 // everything the MFMA engine ranks an index from, derived from its f32 blocks: norms, bf16 / int8 images, the centre, the

@@ -598,26 +598,33 @@ vi_status stage_coarse(SearchBatch &b) {
 vi_status adopt_probes(SearchBatch &b, bool histogram) {
   const DeviceIndex &ix = b.ix;
   SearchWorkspace &ws = b.ws();
-  const uint64_t nq = b.nq, nlists = ix.nlists;
+  const uint64_t nq = b.nq;
   const uint32_t P = b.P, *probes_in = b.probes_in, *order_in = b.order_in;
   hipStream_t st = b.st();
   VI_TRY(ws.probes.reserve(nq * P));
   VI_TRY(ws.gorder.reserve(nq * P));
+  VI_HIP(hipMemcpyAsync(ws.probes.p, probes_in, nq * P * 4, hipMemcpyDeviceToDevice, st));
+  VI_HIP(hipMemcpyAsync(ws.gorder.p, order_in, nq * P * 4, hipMemcpyDeviceToDevice, st));
+  VI_TRY(validate_probe_rows(ix, ws, probes_in, order_in, nq, P, st));
+  if (histogram) VI_TRY(launch_probe_histogram(ix, ws, ws.probes.p, (uint32_t)(nq * P), P, st));
+  return VI_OK;
+}
+
+vi_status validate_probe_rows(const DeviceIndex &ix, SearchWorkspace &ws, const uint32_t *probes, const uint32_t *order, uint64_t nq,
+                              uint32_t P, hipStream_t st) {
+  const uint64_t nlists = ix.nlists;
   VI_TRY(ws.probe_flag.reserve(1));
   VI_HIP(hipMemsetAsync(ws.probe_flag.p, 0, 4, st));
-  hipLaunchKernelGGL(validate_probes_kernel, dim3((uint32_t)nq), dim3(64), ((P + 31u) / 32u) * 4u, st, probes_in, order_in, P,
+  hipLaunchKernelGGL(validate_probes_kernel, dim3((uint32_t)nq), dim3(64), ((P + 31u) / 32u) * 4u, st, probes, order, P,
                      (uint32_t)nlists, ws.probe_flag.p);
   VI_HIP(hipGetLastError());
   uint32_t bad = 0;
   VI_HIP(hipMemcpyAsync(&bad, ws.probe_flag.p, 4, hipMemcpyDeviceToHost, st));
-  VI_HIP(hipMemcpyAsync(ws.probes.p, probes_in, nq * P * 4, hipMemcpyDeviceToDevice, st));
-  VI_HIP(hipMemcpyAsync(ws.gorder.p, order_in, nq * P * 4, hipMemcpyDeviceToDevice, st));
   VI_HIP(hipStreamSynchronize(st));
   if (bad)
     return fail(VI_ERR_INVALID_INPUT, "probe lists out of range: every probe must be < %llu (or the empty marker 0xFFFFFFFF "
                 "after the last real probe of a row), and the orders of a row's real probes must be distinct and below "
                 "its number of real probes", (unsigned long long)nlists);
-  if (histogram) VI_TRY(launch_probe_histogram(ix, ws, ws.probes.p, (uint32_t)(nq * P), P, st));
   return VI_OK;
 }
 
@@ -640,6 +647,7 @@ vi_status search_valu_pipeline(SearchBatch &b, uint64_t k, const SelectOutputs &
   if (timing) VI_HIP(hipEventRecord(ctx.ev[0], st));
   if (b.probes_in) VI_TRY(adopt_probes(b, true));
   else VI_TRY(stage_coarse(b));
+  VI_TRY(prune_staged_probes(b, true));
   if (timing) VI_HIP(hipEventRecord(ctx.ev[1], st));
   // ---- 3. group (query,probe) pairs by list ----
   const double avg_q_per_list = (double)nq * P / (double)std::max<uint64_t>(1, nlists);

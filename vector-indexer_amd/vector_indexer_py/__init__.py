@@ -15,6 +15,8 @@ bindings/python/python/vector_indexer_py/__init__.py):
     VectorIndex.get(ids) / .export(first, count)            extension: read records back, by id / a range in list order
     VectorIndex.filter_timestamps / _ids / _id_range / _mask / _compose(terms)   extension: filters for `filter=`; of two
                                                             filters a & b, a | b, a - b and ~a are filters too
+    VectorIndex.search_adaptive_sync(xq, k, n_probe, rule)  extension: n_probe as an upper bound, a ProbeRule deciding each
+                                                            query's own probe count (distance ratio, code budget, per query)
     merge_range_results(device, parts) -> RangeResult       extension: the radius results of the ranks of a partitioned
                                                             index merged on the device into the unpartitioned result
 
@@ -32,7 +34,7 @@ import numpy as np
 from . import _native
 from ._native import (ViError, lib, VI_ASSIGN_EXACT, VI_ASSIGN_REFERENCE, VI_ORDER_LANES, VI_ORDER_SCALAR)
 
-__all__ = ["build", "load", "suggest_nlist", "VectorIndex", "TimestampFilter", "IdFilter", "FilterIntersection", "ComposedFilter", "Term", "AnyFilter", "RangeResult", "merge_range_results", "merge_range_results_device", "ViError", "kmeans_mini_batch", "kmeans_parallel",
+__all__ = ["build", "load", "suggest_nlist", "VectorIndex", "ProbeRule", "TimestampFilter", "IdFilter", "FilterIntersection", "ComposedFilter", "Term", "AnyFilter", "RangeResult", "merge_range_results", "merge_range_results_device", "ViError", "kmeans_mini_batch", "kmeans_parallel",
            "assign", "l2sq_pairs", "VI_ASSIGN_EXACT", "VI_ASSIGN_REFERENCE", "VI_ORDER_LANES", "VI_ORDER_SCALAR"]
 
 
@@ -268,6 +270,38 @@ def merge_range_results(device: int, parts) -> RangeResult:
 
 def _filter_handle(f):
     return f._h if f is not None else None
+
+
+class ProbeRule:
+    """extension: adaptive probing — how many of its n_probe probes each query of a search keeps (vi_probe_rule).  The
+    probes kept are a prefix of the query's probe row: those whose centroid distance is <= ratio2 * the nearest one's
+    (squared distances, f32; 0.0: off), no more than it takes for their lists to hold max_codes vectors (the list that
+    crosses the budget included: Faiss's max_codes; 0: off), no more than n_probe_q[q] (None: off), never fewer than
+    min_probe.  The result of a query is exactly the search of that query alone with its own probe count.  n_probe_q: an
+    integer array-like with one entry per query for the host calls, a device address (int) of nq u32 for the device
+    calls.  ProbeRule() prunes nothing."""
+
+    __slots__ = ("min_probe", "ratio2", "max_codes", "n_probe_q")
+
+    def __init__(self, min_probe: int = 1, ratio2: float = 0.0, max_codes: int = 0, n_probe_q=None):
+        self.min_probe, self.ratio2, self.max_codes, self.n_probe_q = int(min_probe), float(ratio2), int(max_codes), n_probe_q
+
+    def _native_rule(self, nq: int, device: bool):
+        """(vi_probe_rule, what it points at)"""
+        r = _native.ProbeRuleC()
+        r.min_probe, r.ratio2, r.max_codes = self.min_probe, self.ratio2, self.max_codes
+        keep = None
+        if self.n_probe_q is not None:
+            if device:
+                if not isinstance(self.n_probe_q, (int, np.integer)):
+                    raise TypeError("a device call takes n_probe_q as a device address")
+                r.n_probe_q = int(self.n_probe_q)
+            else:
+                keep = np.ascontiguousarray(np.asarray(self.n_probe_q).reshape(-1), dtype=np.uint32)
+                if keep.size != nq:
+                    raise RuntimeError("n_probe_q must have one entry per query")
+                r.n_probe_q = keep.ctypes.data if keep.size else None
+        return r, keep
 
 
 class VectorIndex:
@@ -754,6 +788,71 @@ class VectorIndex:
                                                                      C.c_void_p(order_ptr), C.c_void_p(D_ptr),
                                                                      C.c_void_p(I_ptr),
                                                                      C.c_void_p(tie_ptr) if tie_ptr else None))
+
+
+    # ---- adaptive probing (vi_probe_rule) ----
+    def search_adaptive_sync(self, xq, k: int, n_probe: int, rule: ProbeRule, filter: Optional[AnyFilter] = None,
+                             include_vectors: bool = False, return_probed: bool = False):
+        """extension: search_sync with n_probe as the upper bound and `rule` deciding each query's own probe count ->
+        (D, I[, V][, n_probed u32[nq]]).  One coarse step, the prune and the list phase, all on the device; the rows of a
+        query are what search_sync gives for it alone at n_probe = n_probed[q].  ProbeRule(): search_sync itself."""
+        if not isinstance(rule, ProbeRule):
+            raise TypeError("rule must be a ProbeRule")
+        xq = np.asarray(xq)
+        if xq.ndim != 2:
+            raise RuntimeError("Query array must be 2-dimensional")
+        if xq.shape[1] != self._dimension:
+            raise RuntimeError(f"Query dimension {xq.shape[1]} doesn't match index dimension {self._dimension}")
+        xq = np.ascontiguousarray(xq, dtype=np.float32)
+        nq, k = xq.shape[0], int(k)
+        D = np.full((nq, max(k, 0)), np.inf, dtype=np.float32)
+        I = np.full((nq, max(k, 0)), -1, dtype=np.int64)
+        V = np.zeros((nq, max(k, 0), self._dimension), dtype=np.float32) if include_vectors else None
+        probed = np.zeros(nq, dtype=np.uint32)
+        r, keep = rule._native_rule(nq, device=False)
+        kout = C.c_uint64(k)
+        _native.check(lib().vi_indexer_search_adaptive(self._h, _filter_handle(filter), C.byref(r), _native.ptr(xq), nq, xq.shape[1],
+                                                       k, int(n_probe), _native.ptr(D), _native.ptr(I), _native.ptr(V), None,
+                                                       _native.ptr(probed), C.byref(kout)))
+        del keep
+        kk = int(kout.value)
+        if kk != k:  # k was clamped to max_k: results occupy the first kk columns
+            D2 = np.full((nq, k), np.inf, dtype=np.float32)
+            I2 = np.full((nq, k), -1, dtype=np.int64)
+            D2[:, :kk] = D.reshape(-1)[: nq * kk].reshape(nq, kk)
+            I2[:, :kk] = I.reshape(-1)[: nq * kk].reshape(nq, kk)
+            D, I = D2, I2
+            if V is not None:
+                V2 = np.zeros((nq, k, self._dimension), dtype=np.float32)
+                V2[:, :kk] = V.reshape(-1)[: nq * kk * self._dimension].reshape(nq, kk, self._dimension)
+                V = V2
+        return (D, I) + ((V,) if include_vectors else ()) + ((probed,) if return_probed else ())
+
+    def search_adaptive_device(self, xq_ptr: int, nq: int, k: int, n_probe: int, rule: ProbeRule, D_ptr: int, I_ptr: int,
+                               tie_ptr: int = 0, n_probed_ptr: int = 0, filter: Optional[AnyFilter] = None):
+        """... for nq queries in device memory, into device memory as search_device; n_probed u32[nq] is written to
+        n_probed_ptr (0 skips it); rule.n_probe_q is a device address"""
+        r, _ = rule._native_rule(nq, device=True)
+        _native.check(lib().vi_indexer_search_adaptive_device(self._h, _filter_handle(filter), C.byref(r), C.c_void_p(xq_ptr),
+                                                              int(nq), int(k), int(n_probe), C.c_void_p(D_ptr), C.c_void_p(I_ptr),
+                                                              C.c_void_p(tie_ptr) if tie_ptr else None,
+                                                              C.c_void_p(n_probed_ptr) if n_probed_ptr else None))
+
+    def prune_probes_device(self, xq_ptr: int, nq: int, n_probe_eff: int, probes_ptr: int, order_ptr: int, rule: ProbeRule,
+                            n_kept_ptr: int = 0):
+        """the prune alone, in place on the rows probe_device left (of the same nq queries), before search_probed_device:
+        the multi-GPU seam.  Probes past a query's count and their orders become 0xFFFFFFFF, the kept orders close up."""
+        r, _ = rule._native_rule(nq, device=True)
+        _native.check(lib().vi_indexer_prune_probes_device(self._h, C.c_void_p(xq_ptr), int(nq), int(n_probe_eff),
+                                                           C.c_void_p(probes_ptr), C.c_void_p(order_ptr), C.byref(r),
+                                                           C.c_void_p(n_kept_ptr) if n_kept_ptr else None))
+
+    def prune_stats(self) -> dict:
+        """this thread's last search_adaptive_* / prune_probes_device: real probes in, probes kept, and under
+        VI_PRUNE_TIMING the HIP-event ms of the prune kernel (0.0 otherwise)"""
+        a, b, ms = C.c_uint64(0), C.c_uint64(0), C.c_float(0)
+        _native.check(lib().vi_prune_last_stats(C.byref(a), C.byref(b), C.byref(ms)))
+        return {"probes_in": int(a.value), "probes_kept": int(b.value), "ms_prune": float(ms.value)}
 
 
 def _config(dimension, index_dir, shards_dir, **ext):

@@ -79,6 +79,11 @@ class ClusterStats(C.Structure):
                 ("ms_link", f32), ("ms_label", f32)]
 
 
+class ProbeRuleC(C.Structure):
+    """vi_probe_rule"""
+    _fields_ = [("min_probe", u32), ("ratio2", f32), ("max_codes", u64), ("n_probe_q", vp)]
+
+
 class FilterTerm(C.Structure):
     """vi_filter_term: one term of vi_indexer_filter_compose"""
     _fields_ = [("kind", u32), ("negate", u32), ("lo", u64), ("hi", u64), ("data", vp), ("n", u64), ("filter", vp)]
@@ -195,6 +200,11 @@ SIGNATURES = {
     "vi_indexer_cluster_radius": (C.c_int, [vp, vp, f32, u64, u32, vp, vp, C.POINTER(u64)]),
     "vi_indexer_cluster_radius_device": (C.c_int, [vp, vp, f32, u64, u32, vp, vp, C.POINTER(u64)]),
     "vi_cluster_last_stats": (C.c_int, [C.POINTER(ClusterStats)]),
+    "vi_indexer_prune_probes_device": (C.c_int, [vp, vp, u64, u64, vp, vp, C.POINTER(ProbeRuleC), vp]),
+    "vi_indexer_search_adaptive": (C.c_int, [vp, vp, C.POINTER(ProbeRuleC), vp, u64, u32, u64, u64, vp, vp, vp, vp, vp,
+                                             C.POINTER(u64)]),
+    "vi_indexer_search_adaptive_device": (C.c_int, [vp, vp, C.POINTER(ProbeRuleC), vp, u64, u64, u64, vp, vp, vp, vp]),
+    "vi_prune_last_stats": (C.c_int, [C.POINTER(u64), C.POINTER(u64), C.POINTER(f32)]),
 }
 
 _lib = None

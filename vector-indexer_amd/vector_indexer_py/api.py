@@ -15,6 +15,7 @@
     .range_search_similar(external_id, radius2, ...) -> [SearchResult] or None    extension: ... within a radius of it
     .duplicate_groups(radius2=0.0, n_probe, min_size=2) -> [[external_id]]        extension: groups of (near-)copies
     SearchRequest.with_timestamp_range / .with_allowed_ids / .with_excluded_ids   extension: filtered search
+    SearchRequest.with_probe_ratio(ratio2, min_probe=1) / .with_max_codes(n)      extension: adaptive probing
 
 Errors are ViError (a RuntimeError) whose .kind is the io::ErrorKind name the reference returns.
 """
@@ -94,6 +95,17 @@ class SearchRequest:
     timestamp_range: Optional[Tuple[int, int]] = None
     # extension: only records whose external id is in a set / is not in a set (None: all); with timestamp_range: both
     id_selector: Optional[IdSelector] = None
+    # extension: adaptive probing — n_probe is the upper bound; the probes whose centroid distance exceeds probe_ratio2 x
+    # the nearest one's are dropped (0.0: off), and probing stops once the probed lists hold max_codes vectors (0: off)
+    probe_ratio2: float = 0.0
+    min_probe: int = 1
+    max_codes: int = 0
+
+    def with_probe_ratio(self, ratio2, min_probe=1):
+        return replace(self, probe_ratio2=float(ratio2), min_probe=int(min_probe))
+
+    def with_max_codes(self, n):
+        return replace(self, max_codes=int(n))
 
     def with_k(self, k):
         return replace(self, k=k)
@@ -281,9 +293,16 @@ class VectorIndexer:
         V = np.zeros((1, max(kcap, 1), self._cfg.dimension), dtype=np.float32) if req.include_vectors else None
         cnt = np.zeros(1, dtype=np.uint64)
         kout = C.c_uint64(0)
-        _native.check(lib().vi_indexer_search_filtered(self._h, self._filter(req.timestamp_range, req.id_selector), _native.ptr(q), 1,
-                                                       q.shape[1], k, int(req.n_probe), _native.ptr(D), _native.ptr(I),
-                                                       _native.ptr(V), _native.ptr(cnt), C.byref(kout)))
+        flt = self._filter(req.timestamp_range, req.id_selector)
+        if req.probe_ratio2 != 0.0 or req.max_codes != 0:  # adaptive probing
+            rule = _native.ProbeRuleC(int(req.min_probe), float(req.probe_ratio2), int(req.max_codes), None)
+            _native.check(lib().vi_indexer_search_adaptive(self._h, flt, C.byref(rule), _native.ptr(q), 1, q.shape[1], k,
+                                                           int(req.n_probe), _native.ptr(D), _native.ptr(I), _native.ptr(V),
+                                                           _native.ptr(cnt), None, C.byref(kout)))
+        else:
+            _native.check(lib().vi_indexer_search_filtered(self._h, flt, _native.ptr(q), 1,
+                                                           q.shape[1], k, int(req.n_probe), _native.ptr(D), _native.ptr(I),
+                                                           _native.ptr(V), _native.ptr(cnt), C.byref(kout)))
         return [SearchResult(int(I[0, j]), float(D[0, j]), V[0, j].tolist() if V is not None else None)
                 for j in range(int(cnt[0]))]
 

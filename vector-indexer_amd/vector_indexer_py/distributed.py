@@ -108,11 +108,18 @@ class ShardedSearcher:
         self._dist.all_gather_into_tensor(packed, mine, group=self._group)
         return self.merge_range(lims_all, packed.view(self.world, mine.numel()), cap)
 
-    def search(self, xq, k, n_probe, filter=None):
+    def search(self, xq, k, n_probe, filter=None, rule=None):
         """filter: this rank's own filter object (every rank makes its own from the same predicate); it reaches
-        local_search as the keyword `filter`, and only when given"""
+        local_search as the keyword `filter`, and only when given.  rule: a ProbeRule (ratio2 / n_probe_q; the same on
+        every rank) — adaptive probing; it reaches local_search as the keyword `rule`, and only when given: the coarse
+        step, the prune of its rows, then the list phase of this rank over the pruned rows"""
         import torch
-        D, I, T = self._local_search(xq, k, n_probe) if filter is None else self._local_search(xq, k, n_probe, filter=filter)
+        kw = {}
+        if filter is not None:
+            kw["filter"] = filter
+        if rule is not None:
+            kw["rule"] = rule
+        D, I, T = self._local_search(xq, k, n_probe, **kw)
         if self.world == 1:
             return D, I
         nq, k = D.shape
@@ -134,12 +141,41 @@ def gpu_searcher(index, device_index: int, group=None) -> ShardedSearcher:
 
     dev = torch.device("cuda", device_index)
 
-    def local_search(xq, k, n_probe, filter=None):
+    def gathered_probes(xq, n_probe):
+        """the coarse step split over the ranks by query and all-gathered (the table is replicated: every rank computes
+        the same rows), or run whole on this rank where the batch does not divide -> (probes, order, n_probe_eff)"""
+        import torch.distributed as dist
+        nq, dim = xq.shape
+        world = dist.get_world_size(group) if dist.is_initialized() else 1
+        p_eff = min(int(n_probe), index.num_centroids)
+        probes = torch.empty((nq, p_eff), dtype=torch.int32, device=dev)  # u32 bit patterns
+        order = torch.empty((nq, p_eff), dtype=torch.int32, device=dev)
+        torch.cuda.synchronize(dev)  # (xq may come from torch's stream)
+        if world == 1 or nq % world:
+            index.probe_device(xq.data_ptr(), nq, n_probe, probes.data_ptr(), order.data_ptr())
+            return probes, order, p_eff
+        per, r = nq // world, dist.get_rank(group)
+        mine_p = torch.empty((per, p_eff), dtype=torch.int32, device=dev)
+        mine_o = torch.empty((per, p_eff), dtype=torch.int32, device=dev)
+        index.probe_device(xq.data_ptr() + r * per * dim * 4, per, n_probe, mine_p.data_ptr(), mine_o.data_ptr())
+        dist.all_gather_into_tensor(probes, mine_p, group=group)
+        dist.all_gather_into_tensor(order, mine_o, group=group)
+        torch.cuda.synchronize(dev)
+        return probes, order, p_eff
+
+    def local_search(xq, k, n_probe, filter=None, rule=None):
         nq = xq.shape[0]
         D = torch.empty((nq, k), dtype=torch.float32, device=dev)
         I = torch.empty((nq, k), dtype=torch.int64, device=dev)
         T = torch.empty((nq, k), dtype=torch.int64, device=dev)  # u64 bit pattern
-        index.search_device(xq.data_ptr(), nq, k, n_probe, D.data_ptr(), I.data_ptr(), T.data_ptr(), filter=filter)
+        if rule is None:
+            index.search_device(xq.data_ptr(), nq, k, n_probe, D.data_ptr(), I.data_ptr(), T.data_ptr(), filter=filter)
+            return D, I, T
+        # adaptive probing: the prune between the gathered probe step and this rank's list phase
+        probes, order, p_eff = gathered_probes(xq, n_probe)
+        index.prune_probes_device(xq.data_ptr(), nq, p_eff, probes.data_ptr(), order.data_ptr(), rule)
+        index.search_probed_device(xq.data_ptr(), nq, k, p_eff, probes.data_ptr(), order.data_ptr(), D.data_ptr(), I.data_ptr(),
+                                   T.data_ptr(), filter=filter)
         return D, I, T
 
     def to_tensors(res):

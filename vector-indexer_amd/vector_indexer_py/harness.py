@@ -120,11 +120,14 @@ def synthetic_dataset(n: int, d: int, nq: int, k: int, seed: int = 42) -> Tuple[
 class FaissStyleAdapter:
     """the Faiss-looking face of an index: .d, .nprobe (settable), .search(xq, k) -> (D, I), .range_search(x, thresh),
     .add(x), .add_with_ids(x, ids), .remove_ids(ids) -> int, .update_vectors(ids, x) -> int, .reconstruct(id),
-    .reconstruct_batch(ids), .ntotal
+    .reconstruct_batch(ids), .ntotal, .max_codes / .probe_ratio2 (settable: adaptive probing)
     (vector_indexer_adapter.py:75-140; the reference hops through an asyncio thread, the search here is synchronous)"""
 
     def __init__(self, vector_index, k: int = 100):
         self._idx, self._k, self._nprobe = vector_index, k, 1
+        # adaptive probing, read by search: Faiss's IndexIVF.max_codes (0: off), and the squared-distance ratio beyond
+        # which a probe is dropped (0.0: off); nprobe is then the upper bound of every query's own probe count
+        self.max_codes, self.probe_ratio2 = 0, 0.0
 
     @property
     def d(self) -> int:
@@ -153,6 +156,10 @@ class FaissStyleAdapter:
 
     def search(self, xq: np.ndarray, k: int, allowed_ids=None, excluded_ids=None, filter=None):
         flt = self._id_filter(allowed_ids, excluded_ids, filter)
+        if self.max_codes or self.probe_ratio2:
+            from . import ProbeRule
+            rule = ProbeRule(ratio2=float(self.probe_ratio2), max_codes=int(self.max_codes))
+            return self._idx.search_adaptive_sync(np.ascontiguousarray(xq, dtype=np.float32), k, self._nprobe, rule, filter=flt)
         if flt is None:
             return self._idx.search_sync(np.ascontiguousarray(xq, dtype=np.float32), k, self._nprobe)
         return self._idx.search_sync(np.ascontiguousarray(xq, dtype=np.float32), k, self._nprobe, filter=flt)
