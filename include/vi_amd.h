@@ -522,6 +522,73 @@ vi_status vi_shard_upsert_to(const char *shards_dir, uint64_t shard_id, uint64_t
                              const uint64_t *ids, const uint64_t *ext_ids, const uint64_t *timestamps, const float *vecs,
                              uint64_t *removed_out);
 
+/* ---- extension (the reference never retrains, api.rs:101-237): refine a built or loaded index — recentre the lists and
+ * re-home the records, on the GPU; Lloyd iterations warm-started from the table the index has ----
+ * The index holds n records in list order (the order vi_indexer_export_records returns): record i is row X[i] in list
+ * lab[i]; the table C has k lists, the empty ones included.  ONE ITERATION:
+ *   1. centres.  For each list l with at least one record, C'[l] is what the reference's update_centroids_parallel
+ *      (kmeans.rs:674-719) gives for cluster l of (X, lab): per column one sequential f32 chain from +0.0 over the list's
+ *      records in list order, then that function's division by the count.  A list WITHOUT a record keeps C[l] bit for
+ *      bit.  (A deliberate deviation: the reference writes zeros there, and a zero centroid would attract records.)
+ *   2. labels.  lab'[i] is the list the reference's search would probe first for X[i] on the table C': the coarse step of
+ *      ivf_index.rs:205-220 at n_probe = 1, scalar summation order, the lowest list index among equal distances — the
+ *      rule of vi_indexer_add_records, so afterwards every record sits where an add would put it.
+ *   3. lists.  List l holds the records with lab' == l in ascending order of their position before the iteration (stable).
+ *      List ids, centroids_to_shard and the number of lists do not change; a list may end empty and stays as an entry
+ *      with no records (num_vectors == 0, still in the coarse table, still probed), as after vi_indexer_remove_ids.
+ * `iters` iterations run one after another; the call stops early after an iteration that moved no record and whose C'
+ * equals its C bit for bit (every further iteration would be the identity), which shows in iterations_run alone.
+ *   - *moved_out (optional): records whose list after the call differs from their list before it (0 on an error)
+ *   - iters == 0: VI_OK and nothing at all changes — no file is touched, the resident index stays, old filters stay valid
+ *   - files afterwards: index.bin holds the new table; every shard file that holds a list equals, byte for byte, the
+ *     reference's writer over the new lists: lists keep their file order, external ids and stored timestamps are carried
+ *     verbatim, and VectorMeta.id is renumbered to the record's position in the NEW list order, 0..n-1 (so refine(3)
+ *     equals three refine(1), and the repeated internal ids earlier updates may have left are gone; a later add continues
+ *     from n).  Shard files without a list are left alone.
+ *   - crash behaviour: every file is written under a temporary name first (shard_<id>.bin.tmp, index.bin.tmp); a failure
+ *     before the first rename removes them and leaves files and handle unchanged.  Then the renames: shards first,
+ *     index.bin last, then the resident index is swapped.  A crash between the first and the last rename leaves a
+ *     directory that mixes old and new files — the limit vi_indexer_upsert_records has.
+ *   - resident index: a replaced index: every vi_filter made before a call that ran an iteration is
+ *     VI_ERR_INVALID_INPUT afterwards (free it), vi_range_results must be freed or copied before the call, and the call
+ *     must not overlap searches on the handle; this is not enforced (the rules of vi_indexer_add_records)
+ *   - errors, all VI_ERR_INVALID_INPUT before any file or device change: a null ix, a handle with no index, a partitioned
+ *     handle (world_size > 1), an index without a record.  A shard file whose lists are no longer the resident ones:
+ *     VI_ERR_INVALID_DATA.
+ * Device memory: the old and the new resident index coexist until the swap, beside 32 bytes per record of labels and
+ * orders, the grouping's scratch, one chunk of stored rows and two tables; no N x D row-major copy is made anywhere. */
+vi_status vi_indexer_refine(vi_indexer *ix, uint64_t iters, uint64_t *moved_out);
+/* the most recent vi_indexer_refine on this handle with iters > 0 (wall-clock ms unless said otherwise) */
+typedef struct vi_refine_stats {
+  uint64_t iterations_run;   /* iterations run, the one that found the fixed point included */
+  uint64_t moved;            /* records whose list changed over the call */
+  uint64_t lists_emptied;    /* lists that held records before the call and hold none after it */
+  uint64_t shards_rewritten; /* shard files rewritten, each once */
+  uint64_t bytes_written;    /* bytes of those files and of index.bin */
+  uint64_t means_bytes;      /* bytes list_means_kernel read and wrote, summed over the iterations ... */
+  uint64_t rehome_bytes;     /* ... and rehome_blocks_kernel */
+  float ms_total;
+  float ms_means;            /* the centres of every iteration: list_means_kernel, the table read back and compared */
+  float ms_label;            /* the labels of every iteration: coarse table, walk over the stored rows, grouping */
+  float ms_rehome;           /* the new layout, rehome_blocks_kernel, the new coarse table */
+  float ms_images;           /* norms and ranking images of the new index */
+  float ms_files;            /* new files written and renamed */
+  float ms_means_kernel;     /* HIP-event time of list_means_kernel alone, summed over the iterations (part of ms_means) */
+  float ms_rehome_kernel;    /* HIP-event time of rehome_blocks_kernel alone (part of ms_rehome) */
+} vi_refine_stats;
+vi_status vi_indexer_last_refine_stats(const vi_indexer *ix, vi_refine_stats *out);
+/* the balance of the resident lists, from their lengths (on a rank of a partitioned index: the rank's part of every list):
+ * when imbalance grows after many adds, a refine is due */
+typedef struct vi_list_stats {
+  uint64_t lists;            /* entries of the coarse table */
+  uint64_t empty_lists;      /* ... without a record */
+  uint64_t min_len, max_len; /* shortest (the empty ones count) and longest list */
+  double mean_len;
+  double imbalance;          /* Faiss's imbalance factor, lists * sum(len^2) / sum(len)^2: 1 = equal lengths, lists = one
+                                list holds everything; 0 for an index without a record */
+} vi_list_stats;
+vi_status vi_indexer_list_stats(const vi_indexer *ix, vi_list_stats *out);
+
 /* ---- extension (the reference reads a stored vector only through include_vectors, api.rs:213-217): read records back from
  * a built or loaded index: by external id, or a range of all of them in list order ----
  * LIST ORDER: the resident records ordered by list index ascending (the row of vi_indexer_centroids = the centroid_id of

@@ -18,6 +18,7 @@
 #include "list_layout.hpp"
 #include "probe_rules.hpp"
 #include "record_fetch.hpp"
+#include "refine_rules.hpp"
 #include "rng.hpp"
 #include "shards.hpp"
 #include "slot_filter.hpp"
@@ -39,6 +40,7 @@ struct Indexer {
   vi_add_stats add_stats{};             // ... and of the last vi_indexer_add_records that added something
   vi_remove_stats remove_stats{};       // ... and of the last vi_indexer_retain / vi_indexer_remove_ids that removed something
   vi_upsert_stats upsert_stats{};       // ... and of the last vi_indexer_upsert_records with n > 0
+  vi_refine_stats refine_stats{};       // ... and of the last vi_indexer_refine with iters > 0
 };
 
 // No C++ exception may unwind through the C ABI into a Rust / ctypes caller (std::vector growth, std::string, a
@@ -418,6 +420,81 @@ static vi_status upsert_records(Indexer *ix, const uint64_t *ext_ids, const floa
   return VI_OK;
 }
 
+// vi_indexer_refine behind its argument checks (iters > 0).  The order of events of update_records with every list
+// touched: the new resident index first (device_index_refine: it decides what the files hold), every shard file that
+// holds a list and index.bin written from it under temporary names, the renames — shards, then index.bin — the swap.
+// Everything before the renames fails without a trace.
+static vi_status refine_records(Indexer *ix, uint64_t iters, uint64_t *moved_out) {
+  const double t0 = now_ms();
+  const DeviceIndex &old = *ix->dev;
+  const uint32_t dim = ix->cfg.dimension;
+  const uint64_t nlists = old.nlists;
+  if (ix->meta.k() != nlists || ix->meta.centroids.size() != nlists * dim)
+    return fail(VI_ERR_OTHER, "refine: the table of the handle does not match its index");
+  VI_HIP(hipSetDevice(old.device));
+  auto dev = std::make_unique<DeviceIndex>();
+  RefineResult rr;
+  VI_TRY(device_index_refine(old, ix->meta.centroids.data(), iters, dev.get(), &rr));
+  const double t1 = now_ms();
+
+  // ---- files: every shard that holds a list, its lists in the order the file has them; then index.bin ----
+  IndexMeta meta = ix->meta;
+  meta.centroids = rr.table;
+  ShardRewriteSet files(ix->shards_dir);
+  IndexMetaRewrite index_file;
+  {
+    const auto lists_of_shard = touched_lists_by_shard(ix->meta, nlists, [](uint64_t) { return true; });
+    ShardExportWs ws;
+    DevBuf<uint64_t> id0;
+    std::vector<uint64_t> cids;
+    std::vector<float> cvec;
+    for (const auto &kv : lists_of_shard) {
+      const uint64_t s = kv.first;
+      cids.clear(); cvec.clear();
+      {
+        ShardFile f;  // (closed again before its successor is written)
+        VI_TRY(files.open(s, dim, &f));
+        for (const uint32_t l : kv.second) {  // every resident list of the shard is in the file, at its resident length
+          const ShardListView *lv;
+          VI_TRY(files.find(f, s, l, rr.old_len[l], &lv));
+        }
+        if (f.num_lists() != kv.second.size())
+          return fail(VI_ERR_INVALID_DATA, "shard %llu holds %u lists, the index %zu of it", (unsigned long long)s, f.num_lists(),
+                      kv.second.size());
+        for (uint32_t i = 0; i < f.num_lists(); ++i) {
+          const uint64_t l = f.list(i).centroid_id;
+          if (l >= nlists || ix->meta.c2s[l] != s)
+            return fail(VI_ERR_INVALID_DATA, "shard %llu holds a list the index keeps elsewhere", (unsigned long long)s);
+          cids.push_back(l);
+          cvec.insert(cvec.end(), &meta.centroids[l * dim], &meta.centroids[l * dim] + dim);
+        }
+      }
+      uint64_t bytes = 0;
+      VI_TRY(shard_export_blocks(*dev, files.temporary(s), s, cids, cvec.data(), ws, id0, &bytes));
+      files.add(s, bytes);
+    }
+    VI_TRY(index_meta_replace(meta, ix->index_dir, &index_file));
+  }
+
+  // ---- renames (shards, then index.bin), then the swap ----
+  VI_TRY(files.commit());
+  VI_TRY(index_file.commit());
+  ix->dev = std::move(dev);
+  ix->meta.centroids.swap(meta.centroids);
+  const double t2 = now_ms();
+  vi_refine_stats rs{};
+  rs.iterations_run = rr.iterations_run; rs.moved = rr.moved; rs.lists_emptied = rr.lists_emptied;
+  rs.shards_rewritten = files.files(); rs.bytes_written = files.bytes() + index_file.bytes();
+  rs.means_bytes = rr.means_bytes; rs.rehome_bytes = rr.rehome_bytes;
+  rs.ms_total = (float)(t2 - t0);
+  rs.ms_means = rr.ms_means; rs.ms_label = rr.ms_label; rs.ms_rehome = rr.ms_rehome; rs.ms_images = rr.ms_images;
+  rs.ms_files = (float)(t2 - t1);
+  rs.ms_means_kernel = rr.ms_means_kernel; rs.ms_rehome_kernel = rr.ms_rehome_kernel;
+  ix->refine_stats = rs;
+  if (moved_out) *moved_out = rr.moved;
+  return VI_OK;
+}
+
 }  // namespace vi
 
 using vi::fail;
@@ -770,6 +847,50 @@ vi_status vi_indexer_upsert_records(vi_indexer *ix, const uint64_t *ext_ids, con
     return fail(VI_ERR_INVALID_INPUT, "records are upserted through an unpartitioned handle (world_size <= 1); ranks reload from its files");
   if (ix->impl.dev->nlists == 0) return fail(VI_ERR_INVALID_INPUT, "the index has no list to add to");
   return vi::upsert_records(&ix->impl, ext_ids, values, timestamps, n, replaced_out);
+  });
+}
+
+vi_status vi_indexer_refine(vi_indexer *ix, uint64_t iters, uint64_t *moved_out) {
+  return vi::guarded([&]() -> vi_status {
+  if (moved_out) *moved_out = 0;
+  if (!ix) return fail(VI_ERR_INVALID_INPUT, "null indexer");
+  if (!ix->impl.dev) return fail(VI_ERR_INVALID_INPUT, "the indexer holds no index (build or load it first)");
+  if (ix->impl.cfg.world_size > 1 || ix->impl.dev->stripe_world > 1)
+    return fail(VI_ERR_INVALID_INPUT, "an index is refined through an unpartitioned handle (world_size <= 1); ranks reload from its files");
+  if (ix->impl.dev->nlists == 0 || ix->impl.dev->nvec_resident == 0)
+    return fail(VI_ERR_INVALID_INPUT, "the index holds no record to refine by");
+  if (iters == 0) return VI_OK;  // nothing changes: no file, no index, no filter
+  return vi::refine_records(&ix->impl, iters, moved_out);
+  });
+}
+
+vi_status vi_indexer_last_refine_stats(const vi_indexer *ix, vi_refine_stats *out) {
+  if (!ix || !out) return fail(VI_ERR_INVALID_INPUT, "null pointer");
+  *out = ix->impl.refine_stats;
+  return VI_OK;
+}
+
+vi_status vi_indexer_list_stats(const vi_indexer *ix, vi_list_stats *out) {
+  return vi::guarded([&]() -> vi_status {
+  if (!ix || !out) return fail(VI_ERR_INVALID_INPUT, "null pointer");
+  *out = vi_list_stats{};
+  if (!ix->impl.dev) return fail(VI_ERR_INVALID_INPUT, "the indexer holds no index (build or load it first)");
+  std::vector<uint32_t> len;
+  VI_HIP(hipSetDevice(ix->impl.dev->device));
+  VI_TRY(vi::read_list_lengths(*ix->impl.dev, &len));
+  out->lists = len.size();
+  if (len.empty()) return VI_OK;
+  uint64_t total = 0;
+  out->min_len = len[0];
+  for (const uint32_t v : len) {
+    out->empty_lists += v == 0;
+    out->min_len = std::min<uint64_t>(out->min_len, v);
+    out->max_len = std::max<uint64_t>(out->max_len, v);
+    total += v;
+  }
+  out->mean_len = (double)total / (double)len.size();
+  out->imbalance = vi::refine_imbalance(len.data(), len.size());
+  return VI_OK;
   });
 }
 

@@ -220,7 +220,7 @@ struct DeviceIndex {
   ~DeviceIndex();
 };
 
-// ---- the four routes to a resident index ----
+// ---- the five routes to a resident index ----
 // Each lays its lists out by list_layout.hpp, reserves and uploads through alloc_list_storage, builds (or copies) the
 // coarse table and ends with prepare_rank_images (search_internal.hpp, device_index.hip); what differs is where the list
 // blocks come from:
@@ -268,6 +268,25 @@ vi_status device_index_update(const DeviceIndex &old, const SlotFilter *keep, co
                               const uint32_t *order_dev, const uint32_t *seg_dev, const std::vector<uint64_t> &seg_host,
                               const uint64_t *row_ext_dev, const uint64_t *row_ts_dev, const std::vector<uint32_t> &old_len_host,
                               DeviceIndex *out, float *ms_kernel, uint64_t *kernel_bytes);
+//   device_index_refine      (list_refine.hip)   the blocks of an older index, every record re-homed to the list of its
+//                                                nearest centre after `iters` Lloyd iterations warm-started from the
+//                                                old table: vi_indexer_refine (api.cpp: refine_records)
+// What a refine hands back beside the index: the new table (nlists x dim, host), the lengths before and after, the counts
+// of the contract (include/vi_amd.h: vi_refine_stats), the host clock of the phases and the HIP-event time and bytes of
+// list_means_kernel (summed over the iterations) and rehome_blocks_kernel.
+struct RefineResult {
+  std::vector<float> table;
+  std::vector<uint32_t> old_len, new_len;
+  uint64_t iterations_run = 0, moved = 0, lists_emptied = 0, means_bytes = 0, rehome_bytes = 0;
+  float ms_means = 0, ms_label = 0, ms_rehome = 0, ms_images = 0, ms_means_kernel = 0, ms_rehome_kernel = 0;
+};
+// `out` = a fresh index holding the records of `old` (unpartitioned, at least one record; only read) in the lists that
+// `iters` >= 1 iterations leave them in; table_host: old's coarse table, nlists x dim.  One iteration: every list with a
+// record gets the mean of its records as its centre (one sequential f32 chain per column in list order, then one divide;
+// an empty list keeps its centroid bits), every record the label of the first probe of the coarse step on the new table,
+// every list the records of its label in their previous order.  Stops early after an iteration that moved nothing and
+// changed no word of the table.  The old blocks are read until the end and never written; complete on return.
+vi_status device_index_refine(const DeviceIndex &old, const float *table_host, uint64_t iters, DeviceIndex *out, RefineResult *res);
 
 // ---- adaptive probing (probe_prune.hip, probe_rules.hpp): per-query probe counts between coarse step and list phase ----
 // A search's rule (vi_probe_rule) and where the number of probes each query kept goes.  The two arrays are host memory on
@@ -440,6 +459,11 @@ vi_status shard_export_device(const std::string &shards_dir, uint64_t shard_id, 
                               const float *cvecs_host, const std::vector<uint64_t> &src_off, const std::vector<uint32_t> &len,
                               const float *X_dev, const uint32_t *order_dev, const uint64_t *ext_dev, const uint64_t *ts_dev,
                               uint64_t now, ShardExportWs &ws, hipStream_t st);
+// the same from the blocks of a resident index (list_refine.hip): the lists cids in file order with the records, external
+// ids and timestamps the index holds, VectorMeta.id = the record's list-order ordinal, written to `path`; id0_buf: one
+// more staging array, reused from shard to shard
+vi_status shard_export_blocks(const DeviceIndex &ix, const std::string &path, uint64_t shard_id, const std::vector<uint64_t> &cids,
+                              const float *cvecs_host, ShardExportWs &ws, DevBuf<uint64_t> &id0_buf, uint64_t *bytes_out);
 
 // ---- appending records to a resident index (list_update.hip; device_index_update is declared with the routes above) ----
 // labels_dev[i] (device, n u32) = the list the reference's coarse step probes first for row i of rows_dev (device, n x dim):

@@ -400,6 +400,10 @@ vi_status slurp(const std::string &path, std::vector<uint8_t> *out, vi_status no
 
 vi_status index_meta_save(const IndexMeta &m, const std::string &index_dir) {
   VI_TRY(make_dirs(index_dir));
+  return index_meta_write(m, index_dir + "/index.bin", nullptr);
+}
+
+vi_status index_meta_write(const IndexMeta &m, const std::string &path, uint64_t *bytes_out) {
   std::vector<uint8_t> b;
   const uint64_t k = m.k(), d = m.dimension;
   b.reserve(k * (d * 4 + 12) + 64);
@@ -412,12 +416,39 @@ vi_status index_meta_save(const IndexMeta &m, const std::string &index_dir) {
   b.push_back(1); put_varint(b, k); put_varint(b, k);
   for (uint64_t c = 0; c < k; ++c) put_varint(b, m.c2s[c]);
   put_varint(b, d);
-  const std::string path = index_dir + "/index.bin";
   FILE *f = fopen(path.c_str(), "wb");
   if (!f) return fail(VI_ERR_IO, "File::create(%s): %s", path.c_str(), strerror(errno));
   const bool ok = fwrite(b.data(), 1, b.size(), f) == b.size();
   if (fclose(f) != 0 || !ok) return fail(VI_ERR_IO, "write(%s) failed", path.c_str());
+  if (bytes_out) *bytes_out = b.size();
   return VI_OK;
+}
+
+vi_status index_meta_replace(const IndexMeta &m, const std::string &index_dir, IndexMetaRewrite *rw) {
+  rw->tmp_ = index_dir + "/index.bin.tmp";
+  rw->final_ = index_dir + "/index.bin";
+  const vi_status s = index_meta_write(m, rw->tmp_, &rw->bytes_);
+  if (s != VI_OK) {
+    ::remove(rw->tmp_.c_str());
+    rw->tmp_.clear();
+  }
+  return s;
+}
+
+vi_status IndexMetaRewrite::commit() {
+  if (tmp_.empty()) return fail(VI_ERR_OTHER, "index.bin: nothing was written");
+  if (::rename(tmp_.c_str(), final_.c_str()) != 0) {
+    const int e = errno;
+    ::remove(tmp_.c_str());
+    tmp_.clear();
+    return fail(VI_ERR_IO, "rename(%s): %s", final_.c_str(), strerror(e));
+  }
+  tmp_.clear();
+  return VI_OK;
+}
+
+IndexMetaRewrite::~IndexMetaRewrite() {
+  if (!tmp_.empty()) ::remove(tmp_.c_str());
 }
 
 vi_status index_meta_load(const std::string &index_dir, IndexMeta *out) {

@@ -145,6 +145,25 @@ struct IndexMeta {
 };
 vi_status index_meta_save(const IndexMeta &m, const std::string &index_dir);
 vi_status index_meta_load(const std::string &index_dir, IndexMeta *out);
+// the same bytes to any path (bytes_out, optional: how many)
+vi_status index_meta_write(const IndexMeta &m, const std::string &path, uint64_t *bytes_out);
+// index.bin rewritten as the shard files of a ShardRewriteSet are: written to index.bin.tmp beside it (index_meta_replace),
+// renamed over it by commit(); what is written and not renamed when the object goes away is unlinked.  Host only.
+class IndexMetaRewrite {
+ public:
+  IndexMetaRewrite() = default;
+  ~IndexMetaRewrite();
+  IndexMetaRewrite(const IndexMetaRewrite &) = delete;
+  IndexMetaRewrite &operator=(const IndexMetaRewrite &) = delete;
+  vi_status commit();
+  uint64_t bytes() const { return bytes_; }
+
+ private:
+  friend vi_status index_meta_replace(const IndexMeta &m, const std::string &index_dir, IndexMetaRewrite *rw);
+  std::string tmp_, final_;
+  uint64_t bytes_ = 0;
+};
+vi_status index_meta_replace(const IndexMeta &m, const std::string &index_dir, IndexMetaRewrite *rw);
 
 // batched vector file of read_vectors_from_file (src/utils.rs:82-107): concatenated
 // bincode Vec<(u64, Vec<f32>, u64)> batches.  Decoding stops silently at the first

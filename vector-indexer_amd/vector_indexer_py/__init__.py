@@ -12,6 +12,7 @@ bindings/python/python/vector_indexer_py/__init__.py):
     VectorIndex.add(xb, ext_ids=None, timestamps=None)      extension: append records to a built or loaded index
     VectorIndex.remove_ids(ids) / .retain(filter) -> int    extension: remove records from it (by id / all a filter excludes)
     VectorIndex.upsert(xb, ext_ids, timestamps=None) -> int extension: replace the records that carry ext_ids, in one rewrite
+    VectorIndex.refine(iters=1) -> int / .list_stats()      extension: recentre the lists and re-home the records / list balance
     VectorIndex.get(ids) / .export(first, count)            extension: read records back, by id / a range in list order
     VectorIndex.filter_timestamps / _ids / _id_range / _mask / _compose(terms)   extension: filters for `filter=`; of two
                                                             filters a & b, a | b, a - b and ~a are filters too
@@ -552,6 +553,31 @@ class VectorIndex:
         """phases of the most recent upsert() of at least one row"""
         st = _native.UpsertStats()
         _native.check(lib().vi_indexer_last_upsert_stats(self._h, C.byref(st)))
+        return {f: getattr(st, f) for f, _ in st._fields_}
+
+    def refine(self, iters: int = 1) -> int:
+        """extension: `iters` Lloyd iterations warm-started from the table the index has, on the GPU: every list with a
+        record gets the mean of its records as its centroid (an empty list keeps its own), every record goes to the list
+        of its now-nearest centroid (the rule of add()), in its previous order -> records whose list changed.  Stops early
+        at a fixed point.  index.bin and every shard file with a list are rewritten once (internal ids become the new list
+        order, 0..n-1), the resident index is swapped once; iters == 0 changes nothing.  Unpartitioned indexes only.
+        Filters made before a call that ran an iteration are rejected afterwards; RangeResults must be copied or freed
+        before it; the call must not overlap searches of this index."""
+        moved = C.c_uint64(0)
+        _native.check(lib().vi_indexer_refine(self._h, int(iters), C.byref(moved)), prefix="Failed to refine the index: ")
+        return int(moved.value)
+
+    def refine_stats(self) -> dict:
+        """counts and phases of the most recent refine() with iters > 0"""
+        st = _native.RefineStats()
+        _native.check(lib().vi_indexer_last_refine_stats(self._h, C.byref(st)))
+        return {f: getattr(st, f) for f, _ in st._fields_}
+
+    def list_stats(self) -> dict:
+        """the balance of the resident lists: lists, empty_lists, min_len, max_len, mean_len and Faiss's imbalance factor
+        (1 = equal lengths); on a rank of a partitioned index, of the rank's part"""
+        st = _native.ListStats()
+        _native.check(lib().vi_indexer_list_stats(self._h, C.byref(st)))
         return {f: getattr(st, f) for f, _ in st._fields_}
 
     def get(self, ids, *, vectors: bool = True):

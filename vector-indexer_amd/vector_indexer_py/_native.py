@@ -67,6 +67,20 @@ class UpsertStats(C.Structure):
                 ("ms_kernel", f32), ("kernel_bytes", u64)]
 
 
+class RefineStats(C.Structure):
+    """vi_refine_stats"""
+    _fields_ = [("iterations_run", u64), ("moved", u64), ("lists_emptied", u64), ("shards_rewritten", u64),
+                ("bytes_written", u64), ("means_bytes", u64), ("rehome_bytes", u64), ("ms_total", f32), ("ms_means", f32),
+                ("ms_label", f32), ("ms_rehome", f32), ("ms_images", f32), ("ms_files", f32), ("ms_means_kernel", f32),
+                ("ms_rehome_kernel", f32)]
+
+
+class ListStats(C.Structure):
+    """vi_list_stats"""
+    _fields_ = [("lists", u64), ("empty_lists", u64), ("min_len", u64), ("max_len", u64), ("mean_len", C.c_double),
+                ("imbalance", C.c_double)]
+
+
 class FetchStats(C.Structure):
     _fields_ = [("n", u64), ("n_found", u64), ("slots_scanned", u64), ("bytes_moved", u64), ("ms_total", f32),
                 ("ms_table", f32), ("ms_match", f32), ("ms_gather", f32)]
@@ -184,6 +198,9 @@ SIGNATURES = {
     "vi_indexer_upsert_records": (C.c_int, [vp, vp, vp, vp, u64, C.POINTER(u64)]),
     "vi_shard_upsert_to": (C.c_int, [C.c_char_p, u64, u64, vp, vp, vp, vp, vp, C.POINTER(u64)]),
     "vi_indexer_last_upsert_stats": (C.c_int, [vp, C.POINTER(UpsertStats)]),
+    "vi_indexer_refine": (C.c_int, [vp, u64, C.POINTER(u64)]),
+    "vi_indexer_last_refine_stats": (C.c_int, [vp, C.POINTER(RefineStats)]),
+    "vi_indexer_list_stats": (C.c_int, [vp, C.POINTER(ListStats)]),
     "vi_indexer_get_records": (C.c_int, [vp, vp, u64, vp, vp, vp, vp]),
     "vi_indexer_get_records_device": (C.c_int, [vp, vp, u64, vp, vp, vp, vp]),
     "vi_indexer_export_records": (C.c_int, [vp, u64, u64, vp, vp, vp, vp]),

@@ -10,6 +10,7 @@
     .add_records(records)                                                         extension: append to a built index
     .remove_records(external_ids) -> int                                          extension: remove from a built index
     .upsert_records(records) -> int                                               extension: replace by external id
+    .refine_lists(iters=1) -> int                                                 extension: recentre lists, re-home records
     .get_records(external_ids) -> [VectorRecord or None]                          extension: read back by external id
     .search_similar(external_id, k, n_probe, ...) -> [SearchResult] or None       extension: neighbours of a stored record
     .range_search_similar(external_id, radius2, ...) -> [SearchResult] or None    extension: ... within a radius of it
@@ -267,6 +268,16 @@ class VectorIndexer:
         _native.check(lib().vi_indexer_upsert_records(self._h, _native.ptr(ext), _native.ptr(vals), _native.ptr(ts), n,
                                                       C.byref(replaced)))
         return int(replaced.value)
+
+    def refine_lists(self, iters: int = 1) -> int:
+        """extension: recentre the lists of the built or loaded index on the records they hold and re-home every record
+        to its nearest centroid, `iters` times (files and resident index, one rewrite) -> records whose list changed.
+        iters == 0 changes nothing."""
+        moved = C.c_uint64(0)
+        if int(iters) > 0:
+            self._drop_filters()  # (cached filters describe the index this call replaces)
+        _native.check(lib().vi_indexer_refine(self._h, int(iters), C.byref(moved)))
+        return int(moved.value)
 
     def get_records(self, external_ids) -> List[Optional[VectorRecord]]:
         """extension: the stored record of every id, in request order: its vector and timestamp as they are stored (of the

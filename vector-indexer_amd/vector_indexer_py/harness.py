@@ -189,6 +189,10 @@ class FaissStyleAdapter:
         replaced.  Unlike Faiss, an id the index does not hold is added"""
         return self._idx.upsert(np.ascontiguousarray(x, dtype=np.float32), ids)
 
+    def imbalance_factor(self) -> float:
+        """Faiss's invlists.imbalance_factor(): nlist * sum(len^2) / sum(len)^2 over the inverted lists, 1 = balanced"""
+        return float(self._idx.list_stats()["imbalance"])
+
     def reconstruct_batch(self, ids) -> np.ndarray:
         """Faiss's Index.reconstruct_batch: the stored vectors of ids, one row each; an id the index does not hold raises
         KeyError naming it"""
