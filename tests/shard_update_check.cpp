@@ -239,6 +239,76 @@ static void check_rewrite_set(const std::string &work) {
   }
 }
 
+// index.bin as the last pair of a set behind two shard pairs (a refine): `old_meta` is in place (blocked: a non-empty
+// directory instead), `new_meta` is written beside it and registered
+static void check_index_pair(const std::string &work) {
+  IndexMeta old_meta, new_meta;
+  old_meta.dimension = new_meta.dimension = 2;
+  old_meta.centroids = {1.0f, 2.0f, 3.0f, 4.0f};
+  new_meta.centroids = {1.5f, 2.5f, 3.5f, 4.5f};
+  old_meta.c2s = new_meta.c2s = {0, 1};
+  const auto stage_index = [&](const std::string &dir, bool blocked, ShardRewriteSet *set) {
+    stage(dir, -1, set);
+    if (blocked) {
+      CHECK(make_dirs(dir + "/index.bin") == VI_OK, "%s", last_error_ref().c_str());
+      spill(dir + "/index.bin/in_the_way", "x");
+    } else {
+      CHECK(index_meta_save(old_meta, dir) == VI_OK, "%s", last_error_ref().c_str());
+    }
+    CHECK(index_meta_replace(new_meta, dir, set) == VI_OK, "%s", last_error_ref().c_str());
+  };
+  const auto no_temporaries = [](const std::string &dir) {
+    return !exists(dir + "/shard_0.bin.tmp") && !exists(dir + "/shard_1.bin.tmp") && !exists(dir + "/index.bin.tmp");
+  };
+  const auto table_in_place = [](const std::string &dir) {
+    IndexMeta m;
+    return index_meta_load(dir, &m) == VI_OK ? m.centroids : std::vector<float>();
+  };
+  {  // committed: shards in registered order, then index.bin
+    const std::string dir = work + "/index_committed";
+    ShardRewriteSet set(dir);
+    stage_index(dir, false, &set);
+    const uint64_t index_bytes = slurp(dir + "/index.bin.tmp").size();
+    CHECK(set.files() == 2 && index_bytes > 0 && set.bytes() == 8 + index_bytes, "index committed: %llu files, %llu bytes",
+          (unsigned long long)set.files(), (unsigned long long)set.bytes());
+    CHECK(table_in_place(dir) == old_meta.centroids, "index committed: index.bin changed before the commit");
+    CHECK(set.commit() == VI_OK, "index committed: %s", last_error_ref().c_str());
+    CHECK(no_temporaries(dir), "index committed: a temporary is left");
+    CHECK(text(dir + "/shard_0.bin") == "new0" && text(dir + "/shard_1.bin") == "new1", "index committed: a shard file was not replaced");
+    CHECK(table_in_place(dir) == new_meta.centroids, "index committed: index.bin was not replaced");
+  }
+  {  // the rename of index.bin fails: it comes last, both shard files are in place by then and the message says so
+    const std::string dir = work + "/index_rename_fails";
+    ShardRewriteSet set(dir);
+    stage_index(dir, true, &set);
+    CHECK(set.commit() == VI_ERR_IO, "index rename fails: status");
+    CHECK(ends_with(last_error_ref(), kInPlace) && last_error_ref().find("rename(" + dir + "/index.bin.tmp): ") == 0,
+          "index rename fails: text '%s'", last_error_ref().c_str());
+    CHECK(text(dir + "/shard_0.bin") == "new0" && text(dir + "/shard_1.bin") == "new1", "index rename fails: a shard file was not replaced");
+    CHECK(no_temporaries(dir) && exists(dir + "/index.bin/in_the_way"), "index rename fails: a temporary is left");
+  }
+  {  // a shard rename in front of it fails: index.bin is not reached
+    const std::string dir = work + "/index_not_reached";
+    ShardRewriteSet set(dir);
+    stage(dir, 1, &set);
+    CHECK(index_meta_save(old_meta, dir) == VI_OK && index_meta_replace(new_meta, dir, &set) == VI_OK, "%s", last_error_ref().c_str());
+    CHECK(set.commit() == VI_ERR_IO, "index not reached: status");
+    CHECK(text(dir + "/shard_0.bin") == "new0" && table_in_place(dir) == old_meta.centroids, "index not reached: order of the renames");
+    CHECK(no_temporaries(dir), "index not reached: a temporary is left");
+  }
+  {  // destroyed without commit
+    const std::string dir = work + "/index_dropped";
+    {
+      ShardRewriteSet set(dir);
+      stage_index(dir, false, &set);
+      CHECK(exists(dir + "/index.bin.tmp"), "index dropped: staged");
+    }
+    CHECK(no_temporaries(dir), "index dropped: a temporary is left");
+    CHECK(text(dir + "/shard_0.bin") == "old0" && text(dir + "/shard_1.bin") == "old1" && table_in_place(dir) == old_meta.centroids,
+          "index dropped: a final file changed");
+  }
+}
+
 int main(int argc, char **argv) {
   if (argc < 2) {
     std::printf("usage: shard_update_check <scratch directory>\n");
@@ -250,6 +320,7 @@ int main(int argc, char **argv) {
     check_round_trip(work, dim);
   }
   check_rewrite_set(work);
+  check_index_pair(work);
   if (failures) std::printf("%d checks failed\n", failures);
   return failures ? 1 : 0;
 }

@@ -223,15 +223,17 @@ struct DeviceIndex {
 // ---- the five routes to a resident index ----
 // Each lays its lists out by list_layout.hpp, reserves and uploads through alloc_list_storage, builds (or copies) the
 // coarse table and ends with prepare_rank_images (search_internal.hpp, device_index.hip); what differs is where the list
-// blocks come from:
+// blocks come from.  The last two start from an older index and share their frame and the vocabulary of their block
+// kernels (list_blocks.hpp: refuse_update, begin_update, launch_block_kernel, copy_old_block, fill_block_column).  Who calls which, and
+// in what order with the files, is index_lifecycle.cpp:
 //   device_index_load        (device_index.hip)  records of the shard files, in stripes or by shard placement: a load, and
-//                                                the build of a rank of a multi-GPU run (api.cpp: attach_device)
+//                                                the build of a rank of a multi-GPU run (index_lifecycle.cpp: attach_device)
 //   device_index_from_rows   (device_index.hip)  rows of a device matrix, grouped on the host: the two-level hierarchy of
 //                                                the k-means assignment (kmeans.hip)
-//   device_index_from_order  (list_build.hip)    rows of a device matrix, grouped on the device: a single-GPU build (api.cpp)
+//   device_index_from_order  (list_build.hip)    rows of a device matrix, grouped on the device: a single-GPU build (index_lifecycle.cpp: fit_and_save)
 //   device_index_update      (list_update.hip)   the blocks of an older index, less the records a filter excludes and / or
 //                                                with new rows behind them: vi_indexer_add_records, vi_indexer_retain /
-//                                                vi_indexer_remove_ids, vi_indexer_upsert_records (api.cpp: update_records)
+//                                                vi_indexer_remove_ids, vi_indexer_upsert_records (index_lifecycle.cpp: update_records)
 //
 // Upload: centroid table + this rank's part of the lists, repacked on the GPU.  placement 0: a stripe of every list
 // (block b on rank b % world); 1: the whole lists of the shard files dealt to this rank (greedy by bytes).
@@ -270,7 +272,7 @@ vi_status device_index_update(const DeviceIndex &old, const SlotFilter *keep, co
                               DeviceIndex *out, float *ms_kernel, uint64_t *kernel_bytes);
 //   device_index_refine      (list_refine.hip)   the blocks of an older index, every record re-homed to the list of its
 //                                                nearest centre after `iters` Lloyd iterations warm-started from the
-//                                                old table: vi_indexer_refine (api.cpp: refine_records)
+//                                                old table: vi_indexer_refine (index_lifecycle.cpp: refine_records)
 // What a refine hands back beside the index: the new table (nlists x dim, host), the lengths before and after, the counts
 // of the contract (include/vi_amd.h: vi_refine_stats), the host clock of the phases and the HIP-event time and bytes of
 // list_means_kernel (summed over the iterations) and rehome_blocks_kernel.
@@ -439,36 +441,40 @@ struct EngineKnobs {
 };
 EngineKnobs read_engine_knobs();
 
-// ---- GPU list build (list_build.hip; device_index_from_order is declared with the routes above) ----
+// ---- grouping ids by list on the GPU (list_build.hip; device_index_from_order is declared with the routes above) ----
 // ids 0..n-1 grouped by label, ascending id inside a label (stable radix sort): order (device, n u32), seg (device,
 // k+1 u32 offsets into order) and the offsets on the host if off_host is given.  Complete on return.  scratch_keep
 // (optional): the sort's scratch (3 n + 256 n / 4096 words) in a buffer of the caller's, kept from call to call.
 vi_status group_ids_by_label_device(const uint32_t *labels_dev, uint64_t n, uint64_t k, DevBuf<uint32_t> &order,
                                     DevBuf<uint32_t> &seg, std::vector<uint64_t> *off_host, hipStream_t st,
                                     DevBuf<uint32_t> *scratch_keep = nullptr);
-struct ShardExportWs {  // staging of shard_export_device, reused from shard to shard
+// ---- shard files from records in HBM (shard_export.hip) ----
+struct ShardExportWs {  // staging of an export, reused from shard to shard
   DevBuf<uint8_t> image;
-  DevBuf<uint64_t> d_src, d_dst;
-  DevBuf<uint32_t> d_len, d_first;
+  DevBuf<uint64_t> d_src, d_id0, d_dst;
+  DevBuf<uint32_t> d_first;
   uint8_t *host = nullptr;  // pinned
   uint64_t host_cap = 0;
   ~ShardExportWs();
 };
-// shard_<id>.bin from device-resident points, byte-identical to shard_save_to (shards.cpp)
+// shard_<id>.bin from device-resident points, byte-identical to shard_save_to (shards.cpp): list i of the shard is rows
+// order_dev[src_off[i] .. + len[i]) of X_dev, VectorMeta.id the row; written under its final name
 vi_status shard_export_device(const std::string &shards_dir, uint64_t shard_id, uint32_t dim, const std::vector<uint64_t> &cids,
                               const float *cvecs_host, const std::vector<uint64_t> &src_off, const std::vector<uint32_t> &len,
                               const float *X_dev, const uint32_t *order_dev, const uint64_t *ext_dev, const uint64_t *ts_dev,
                               uint64_t now, ShardExportWs &ws, hipStream_t st);
-// the same from the blocks of a resident index (list_refine.hip): the lists cids in file order with the records, external
-// ids and timestamps the index holds, VectorMeta.id = the record's list-order ordinal, written to `path`; id0_buf: one
-// more staging array, reused from shard to shard
+// the same from the blocks of a resident index: the lists cids in file order with the records, external ids and
+// timestamps the index holds, VectorMeta.id = the record's list-order ordinal, written to `path`
 vi_status shard_export_blocks(const DeviceIndex &ix, const std::string &path, uint64_t shard_id, const std::vector<uint64_t> &cids,
-                              const float *cvecs_host, ShardExportWs &ws, DevBuf<uint64_t> &id0_buf, uint64_t *bytes_out);
+                              const float *cvecs_host, ShardExportWs &ws, uint64_t *bytes_out);
 
 // ---- appending records to a resident index (list_update.hip; device_index_update is declared with the routes above) ----
 // labels_dev[i] (device, n u32) = the list the reference's coarse step probes first for row i of rows_dev (device, n x dim):
 // the index's own coarse step with n_probe = 1, in chunks
 vi_status device_index_label_rows(const DeviceIndex &ix, const float *rows_dev, uint64_t n, uint32_t *labels_dev);
+// one chunk of it, and of a refine's labelling (list_refine.hip), as one search: m rows, k 1, n_probe 1, probes_out =
+// labels_dev; order_scratch: m words of the caller's, written and not read
+vi_status device_index_label_chunk(const DeviceIndex &ix, const float *rows_dev, uint64_t m, uint32_t *labels_dev, uint32_t *order_scratch);
 
 vi_status merge_partials_packed_device(int device, uint64_t nq, uint64_t k, uint32_t parts, const void *packed,
                                        float *D_out, int64_t *I_out);

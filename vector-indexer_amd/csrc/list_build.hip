@@ -12,19 +12,15 @@
 //        nothing is re-read from the shard files the build has just written.  Layout, storage and coarse table are the
 //        steps every index route shares (list_layout.hpp, device_index.hip); slot_rows_kernel and
 //        slot_timestamps_kernel are this route's own
-//     -> shard files: one kernel per shard lays the records (24 B meta + D f32 + pad) out in file order in a staging
-//        image, one copy to pinned host memory, one write(2).
+// The shard files are written from the same device copy, one kernel per shard (shard_export.hip).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstdio>
-#include <cstring>
 #include <vector>
 
 #include "device_index.hpp"
 #include "scan.hpp"
 #include "search_internal.hpp"
-#include "shards.hpp"
 
 namespace vi {
 namespace {
@@ -164,7 +160,7 @@ __global__ void slot_rows_kernel(const uint32_t *order, const uint64_t *src_off,
   for (uint32_t j = threadIdx.x; j < padded; j += blockDim.x) dst[j] = j < len ? order[so + j] : kNoPos;
 }
 
-// the timestamp every slot's record carries in the shard files (export_records_kernel: 0 or no array => now); pad slots 0
+// the timestamp every slot's record carries in the shard files (shard_export.hip, RowSource: 0 or no array => now); pad slots 0
 __global__ void slot_timestamps_kernel(const uint32_t *row_of_slot, const uint64_t *timestamps, uint64_t now, uint64_t nslots,
                                        uint64_t *out) {
   const uint64_t s = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -176,51 +172,6 @@ __global__ void slot_timestamps_kernel(const uint32_t *row_of_slot, const uint64
     if (ts == 0) ts = now;
   }
   out[s] = ts;
-}
-
-// records of one shard in file order.  One wave per record: 32-bit words of {id, external_id, timestamp, D x f32, pad}
-struct ExportArgs {
-  const float *X;
-  const uint32_t *order;         // ids grouped by list
-  const uint64_t *ext_ids;       // per point, or null: the id itself (bindings/python/src/lib.rs:236-243)
-  const uint64_t *timestamps;    // per point (0 => now), or null: now (vector_store.rs:36-40)
-  uint64_t now;
-  const uint64_t *rec_src;       // per list of the shard: offset into order
-  const uint64_t *rec_dst;       // per list: byte offset of its first record inside the staging image
-  const uint32_t *rec_len;       // per list
-  const uint32_t *rec_first;     // per list: index of its first record among the shard's records (exclusive scan of rec_len)
-  uint32_t nlists, dim, stride;  // stride = bytes per record
-  uint64_t nrec;                 // records of the shard
-  uint8_t *image;
-};
-
-__global__ void __launch_bounds__(256) export_records_kernel(ExportArgs a) {
-  const int lane = threadIdx.x & 63;
-  const uint64_t rec = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (rec >= a.nrec) return;
-  uint32_t lo = 0, hi = a.nlists;  // largest l with rec_first[l] <= rec (lists of the shard are non-empty)
-  while (hi - lo > 1) {
-    const uint32_t mid = (lo + hi) >> 1;
-    if (a.rec_first[mid] <= rec) lo = mid; else hi = mid;
-  }
-  const uint32_t j = (uint32_t)(rec - a.rec_first[lo]);
-  const uint32_t id = a.order[a.rec_src[lo] + j];
-  uint32_t *dst = reinterpret_cast<uint32_t *>(a.image + a.rec_dst[lo] + (uint64_t)j * a.stride);
-  const uint64_t ext = a.ext_ids ? a.ext_ids[id] : (uint64_t)id;
-  uint64_t ts = a.timestamps ? a.timestamps[id] : 0ull;
-  if (ts == 0) ts = a.now;
-  const uint32_t *src = reinterpret_cast<const uint32_t *>(a.X + (size_t)id * a.dim);
-  const uint32_t words = a.stride / 4;
-  for (uint32_t w = lane; w < words; w += kWave) {
-    uint32_t v = 0;
-    if (w == 0) v = id;                     // internal id = position (vector_store.rs:33), high word 0
-    else if (w == 2) v = (uint32_t)ext;
-    else if (w == 3) v = (uint32_t)(ext >> 32);
-    else if (w == 4) v = (uint32_t)ts;
-    else if (w == 5) v = (uint32_t)(ts >> 32);
-    else if (w >= 6 && w < 6 + a.dim) v = src[w - 6];
-    dst[w] = v;
-  }
 }
 
 }  // namespace
@@ -314,59 +265,6 @@ vi_status device_index_from_order(int device, uint32_t dim, const float *table_h
     VI_HIP(hipStreamSynchronize(st));
   }
   return prepare_rank_images(ix);
-}
-
-// One shard file from device-resident points, the frame by the routines shard_save_to uses (shards.cpp: byte-identical):
-// lists = the shard's lists in file order, each (centroid id, centroid vector (host), offset into order_dev, length).
-vi_status shard_export_device(const std::string &shards_dir, uint64_t shard_id, uint32_t dim, const std::vector<uint64_t> &cids,
-                              const float *cvecs_host, const std::vector<uint64_t> &src_off, const std::vector<uint32_t> &len,
-                              const float *X_dev, const uint32_t *order_dev, const uint64_t *ext_dev, const uint64_t *ts_dev,
-                              uint64_t now, ShardExportWs &ws, hipStream_t st) {
-  VI_TRY(make_dirs(shards_dir));
-  const std::string path = shard_file_path(shards_dir, shard_id);
-  ::remove(path.c_str());  // shards.rs:73
-  const uint32_t nl = (uint32_t)cids.size();
-  const ShardPlan pl(dim, std::vector<uint64_t>(len.begin(), len.end()));
-  const uint64_t data_off = pl.data_off, total = pl.total;
-  uint64_t nrec = 0;
-  for (uint32_t i = 0; i < nl; ++i) nrec += len[i];
-  if (nrec >= 0xFFFFFFFFull) return fail(VI_ERR_OTHER, "shard with more than 2^32 records");
-  // staging image on the device (records only; header, index and centroid vectors are patched in on the host)
-  VI_TRY(ws.image.reserve(total + 16));
-  if (ws.host_cap < total) {
-    if (ws.host) (void)hipHostFree(ws.host);
-    ws.host = nullptr;
-    ws.host_cap = 0;
-    VI_HIP(hipHostMalloc((void **)&ws.host, total + 16));
-    ws.host_cap = total;
-  }
-  // only lists with records take part in the kernel's search table
-  std::vector<uint64_t> k_src, k_dst;
-  std::vector<uint32_t> k_len, k_first;
-  for (uint32_t i = 0, first = 0; i < nl; ++i) {
-    if (len[i]) { k_src.push_back(src_off[i]); k_dst.push_back(pl.records(i)); k_len.push_back(len[i]); k_first.push_back(first); }
-    first += len[i];
-  }
-  if (nrec) {
-    VI_TRY(upload(ws.d_src, k_src.data(), k_src.size(), st));
-    VI_TRY(upload(ws.d_dst, k_dst.data(), k_dst.size(), st));
-    VI_TRY(upload(ws.d_len, k_len.data(), k_len.size(), st));
-    VI_TRY(upload(ws.d_first, k_first.data(), k_first.size(), st));
-    ExportArgs a{X_dev, order_dev, ext_dev, ts_dev, now, ws.d_src.p, ws.d_dst.p, ws.d_len.p, ws.d_first.p,
-                 (uint32_t)k_src.size(), dim, (uint32_t)pl.stride, nrec, ws.image.p};
-    hipLaunchKernelGGL(export_records_kernel, dim3((uint32_t)((nrec + 3) / 4)), dim3(256), 0, st, a);
-    VI_HIP(hipGetLastError());
-    VI_HIP(hipMemcpyAsync(ws.host + data_off, ws.image.p + data_off, total - data_off, hipMemcpyDeviceToHost, st));
-    VI_HIP(hipStreamSynchronize(st));  // (k_* are read by the copies above)
-  }
-  std::vector<const void *> cvecs(nl);
-  for (uint32_t i = 0; i < nl; ++i) cvecs[i] = cvecs_host + (uint64_t)i * dim;
-  shard_frame_write(ws.host, pl, shard_id, cids.data(), cvecs.data());
-  return shard_image_write(path, ws.host, total, false);
-}
-
-ShardExportWs::~ShardExportWs() {
-  if (host) (void)hipHostFree(host);
 }
 
 }  // namespace vi

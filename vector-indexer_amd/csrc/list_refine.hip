@@ -15,13 +15,16 @@
 //   labels   a coarse-only index of the new table (device_index_from_rows, whose one list holds one row of the table, so
 //            that every launch of prepare_rank_images has work) and the walk over stored records (StoredRowsWalk):
 //            chunks of stored rows of the OLD index, in ordinal order, through that index's coarse step at n_probe 1 —
-//            the labeller of an add (device_index_label_rows).  The search kernels are the ones every search runs.
+//            the labeller of an add, chunk for chunk (device_index_label_chunk).  The search kernels are the ones every
+//            search runs.
 //   lists    relabel_kernel brings the labels into position order and counts the moved records; the stable grouping of
 //            positions by label (group_ids_by_label_device) gives the next order; compose_kernel maps it back to old
 //            ordinals.
 // After the last iteration, once: the new layout from the new lengths (lay_out_from_old), rehome_blocks_kernel — one wave
-// per NEW block, lane = new position, source = the old slot of ordinal cur[seg[l] + p] — the new table
-// (coarse_table_from_rows) and prepare_rank_images, the load's own code.
+// per NEW block, lane = new position, source = the old slot of ordinal cur[seg[l] + p]; what it shares with an update's
+// block kernel is list_blocks.hpp, as are the frame it starts in (refuse_update, begin_update) and its launch — the new table
+// (coarse_table_from_rows) and prepare_rank_images, the load's own code.  The shard files of the new index are written by
+// shard_export.hip.
 //
 // Device memory beside the old and the new index: eight u32 words per record (the old and the new labels by ordinal, the
 // new labels by position, cur and cur_lab twice each, the grouping's output) plus the grouping's scratch, one chunk of
@@ -29,20 +32,18 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstring>
 #include <vector>
 
 #include "device_index.hpp"
+#include "list_blocks.hpp"
 #include "record_fetch.hpp"
 #include "refine_rules.hpp"
 #include "search_internal.hpp"
-#include "shards.hpp"
 
 namespace vi {
 namespace {
 
 constexpr int kWave = 64;
-constexpr int kRehomeWaves = 4;                       // new blocks per workgroup of rehome_blocks_kernel
 constexpr uint32_t kMeanCols = 64;                    // columns of one list_means_kernel wave: lane = column on the way out
 constexpr uint32_t kMeanQuads = kMeanCols / 4;
 constexpr uint32_t kMeanStride = kMeanCols + 4;       // dwords; the pad keeps 16-byte alignment and spreads the rows over the banks
@@ -127,9 +128,7 @@ __global__ void __launch_bounds__(256) compose_kernel(const uint32_t *order, con
 }
 
 struct RehomeArgs {
-  // the old index
-  const float4 *old_blocks;
-  const uint64_t *old_ext, *old_ts;
+  OldBlocks old;                           // the old index
   const uint32_t *old_first;               // per list
   const uint64_t *old_prefix;              // per list
   uint32_t nlists, dq;
@@ -139,18 +138,16 @@ struct RehomeArgs {
   const uint32_t *new_first, *new_len;     // per list
   const uint32_t *block_list;              // per new block: its list
   uint64_t nblocks;
-  float4 *blocks;
-  uint64_t *ext, *ts;
+  NewBlocks out;
 };
 
 // One wave per NEW block, lane = new position.  Vector, external id and timestamp of position p of list l come from the
-// old slot of ordinal cur[seg[l] + p]; a pad lane gets what every upload leaves there: a zero vector, id ~0, timestamp 0.
-// Every word of the new blocks / ext / ts is written exactly once.  A block whose 64 sources are one whole old block in
-// order — every block of a list nothing joined and nothing left, but its last — is a straight copy of it: four 1 KiB rows
-// in flight, as update_blocks_kernel copies (list_update.hip: copy_old_block).
-__global__ void __launch_bounds__(kRehomeWaves * kWave) rehome_blocks_kernel(RehomeArgs a) {
+// old slot of ordinal cur[seg[l] + p]; the rest is list_blocks.hpp: a pad lane's values, the fill of the lane's column,
+// and the straight copy of a block whose 64 sources are one whole old block in order — every block of a list nothing
+// joined and nothing left, but its last.
+__global__ void __launch_bounds__(kBlockWaves * kWave) rehome_blocks_kernel(RehomeArgs a) {
   const uint32_t lane = threadIdx.x & (kWave - 1);
-  const uint64_t b = (uint64_t)blockIdx.x * kRehomeWaves + (threadIdx.x >> 6);
+  const uint64_t b = (uint64_t)blockIdx.x * kBlockWaves + (threadIdx.x >> 6);
   if (b >= a.nblocks) return;
   const uint32_t l = a.block_list[b];
   const uint32_t p = (uint32_t)(b - a.new_first[l]) * kWave + lane;
@@ -158,99 +155,19 @@ __global__ void __launch_bounds__(kRehomeWaves * kWave) rehome_blocks_kernel(Reh
   uint64_t src_slot = 0;
   if (valid) src_slot = refine_slot_of_ordinal(a.old_prefix, a.old_first, a.nlists, a.cur[a.seg[l] + p]);
   const uint32_t dq = a.dq;
-  float4 *dst = a.blocks + (b * dq) * kWave + lane;
-  const uint64_t slot = b * kWave + lane;
   const uint64_t slot0 = __shfl(src_slot, 0, kWave);
   if (__all(valid && src_slot == slot0 + lane) && (slot0 & 63u) == 0) {  // (wave-uniform) one whole old block, in order
-    const float4 *src = a.old_blocks + ((slot0 >> 6) * dq) * kWave + lane;
-    for (uint32_t qd = 0; qd < dq; qd += 4) {  // (dq is a multiple of 4: layout_dq)
-      const float4 t0 = src[(size_t)(qd + 0) * kWave], t1 = src[(size_t)(qd + 1) * kWave];
-      const float4 t2 = src[(size_t)(qd + 2) * kWave], t3 = src[(size_t)(qd + 3) * kWave];
-      dst[(size_t)(qd + 0) * kWave] = t0;
-      dst[(size_t)(qd + 1) * kWave] = t1;
-      dst[(size_t)(qd + 2) * kWave] = t2;
-      dst[(size_t)(qd + 3) * kWave] = t3;
-    }
-    a.ext[slot] = a.old_ext[slot0 + lane];
-    a.ts[slot] = a.old_ts[slot0 + lane];
+    copy_old_block(a.old, a.out, dq, slot0 >> 6, b, lane);
     return;
   }
-  const float4 *src = a.old_blocks + ((src_slot >> 6) * dq) * kWave + (src_slot & 63u);  // (read only where valid)
-  for (uint32_t qd = 0; qd < dq; qd += 4) {
-    float4 t0 = make_float4(0.f, 0.f, 0.f, 0.f), t1 = t0, t2 = t0, t3 = t0;
-    if (valid) {
-      t0 = src[(size_t)(qd + 0) * kWave];
-      t1 = src[(size_t)(qd + 1) * kWave];
-      t2 = src[(size_t)(qd + 2) * kWave];
-      t3 = src[(size_t)(qd + 3) * kWave];
-    }
-    dst[(size_t)(qd + 0) * kWave] = t0;
-    dst[(size_t)(qd + 1) * kWave] = t1;
-    dst[(size_t)(qd + 2) * kWave] = t2;
-    dst[(size_t)(qd + 3) * kWave] = t3;
-  }
-  a.ext[slot] = valid ? a.old_ext[src_slot] : ~0ull;
-  a.ts[slot] = valid ? a.old_ts[src_slot] : 0ull;
+  const float4 *src = a.old.blocks + ((src_slot >> 6) * dq) * kWave + (src_slot & 63u);  // (read only where valid)
+  fill_block_column(a.out.blocks + (b * dq) * kWave + lane, dq, [&](uint32_t qd, float4 (&t)[4]) {
+    if (valid) load_block_quads(src, qd, t);
+  });
+  const uint64_t slot = b * kWave + lane;
+  a.out.ext[slot] = valid ? a.old.ext[src_slot] : kPadExtId;
+  a.out.ts[slot] = valid ? a.old.ts[src_slot] : kPadTimestamp;
 }
-
-// records of one shard in file order, read from the blocks of a resident index.  One wave per record: 32-bit words of
-// {id, external_id, timestamp, D x f32, pad} (list_build.hip: export_records_kernel reads a row-major matrix instead).
-// VectorMeta.id is the record's list-order ordinal.
-struct BlockExportArgs {
-  const float *blocks;           // the index's blocks as floats
-  const uint64_t *ext_ids, *timestamps;
-  const uint64_t *rec_slot0;     // per list of the shard with records: slot of its first record
-  const uint64_t *rec_id0;       // per list: ordinal of its first record
-  const uint64_t *rec_dst;       // per list: byte offset of its first record inside the staging image
-  const uint32_t *rec_first;     // per list: index of its first record among the shard's records
-  uint32_t nlists, dim, dq, stride;
-  uint64_t nrec;
-  uint8_t *image;
-};
-
-__global__ void __launch_bounds__(256) export_block_records_kernel(BlockExportArgs a) {
-  const int lane = threadIdx.x & 63;
-  const uint64_t rec = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (rec >= a.nrec) return;
-  uint32_t lo = 0, hi = a.nlists;  // largest l with rec_first[l] <= rec (only lists with records take part)
-  while (hi - lo > 1) {
-    const uint32_t mid = (lo + hi) >> 1;
-    if (a.rec_first[mid] <= rec) lo = mid; else hi = mid;
-  }
-  const uint64_t j = rec - a.rec_first[lo];
-  const uint64_t slot = a.rec_slot0[lo] + j, id = a.rec_id0[lo] + j;
-  uint32_t *dst = reinterpret_cast<uint32_t *>(a.image + a.rec_dst[lo] + j * a.stride);
-  const uint64_t ext = a.ext_ids[slot], ts = a.timestamps[slot];
-  const uint32_t *src = reinterpret_cast<const uint32_t *>(a.blocks) + ((slot >> 6) * a.dq) * (kWave * 4) + (slot & 63u) * 4;
-  const uint32_t words = a.stride / 4;
-  for (uint32_t w = lane; w < words; w += kWave) {
-    uint32_t v = 0;
-    if (w == 0) v = (uint32_t)id;
-    else if (w == 1) v = (uint32_t)(id >> 32);
-    else if (w == 2) v = (uint32_t)ext;
-    else if (w == 3) v = (uint32_t)(ext >> 32);
-    else if (w == 4) v = (uint32_t)ts;
-    else if (w == 5) v = (uint32_t)(ts >> 32);
-    else if (w >= 6 && w < 6 + a.dim) {
-      const uint32_t e = w - 6;
-      v = src[(size_t)(e >> 2) * (kWave * 4) + (e & 3u)];
-    }
-    dst[w] = v;
-  }
-}
-
-struct EventPair {
-  hipEvent_t a = nullptr, b = nullptr;
-  vi_status create() {
-    VI_HIP(hipEventCreate(&a));
-    VI_HIP(hipEventCreate(&b));
-    return VI_OK;
-  }
-  ~EventPair() {
-    if (a) (void)hipEventDestroy(a);
-    if (b) (void)hipEventDestroy(b);
-  }
-};
 
 inline dim3 grid_1d(uint64_t n) { return dim3((uint32_t)((n + 255) / 256)); }
 
@@ -260,12 +177,9 @@ vi_status device_index_refine(const DeviceIndex &old, const float *table_host, u
   *res = RefineResult{};
   const uint64_t nlists = old.nlists, n = old.nvec_resident;
   const uint32_t dim = old.dim, dq = old.dq;
-  if (old.stripe_world > 1) return fail(VI_ERR_INVALID_INPUT, "a partitioned index is not refined");
-  if (!old.timestamps.p || !old.ext_ids.p) return fail(VI_ERR_INVALID_INPUT, "the index keeps no ids or timestamps");
+  VI_TRY(refuse_update(old, "a partitioned index is not refined"));
   if (iters == 0 || n == 0 || nlists == 0) return fail(VI_ERR_OTHER, "refine: nothing to do");
-  VI_TRY(init_device_index(ix, old.device, dim, nlists));
-  ix->order = old.order;
-  ix->timing = old.timing;
+  VI_TRY(begin_update(old, ix));
   hipStream_t st = ix->stream;
   VI_TRY(ensure_fetch_layout(old, st));
   const FetchState &lay = old.fetch;
@@ -289,8 +203,8 @@ vi_status device_index_refine(const DeviceIndex &old, const float *table_host, u
   VI_HIP(hipMemcpyAsync(cur_lab[0].p, lab0.p, n * 4, hipMemcpyDeviceToDevice, st));
   VI_HIP(hipStreamSynchronize(st));
 
-  EventPair ev;
-  VI_TRY(ev.create());
+  EventSpans<1> ev;  // list_means_kernel
+  VI_TRY(ev.create(true));
   std::vector<float> h_table(table_host, table_host + nlists * dim), h_new(nlists * dim);
   std::vector<uint64_t> seg_host;
   const uint32_t *cur_p = nullptr;  // identity before the first iteration
@@ -302,13 +216,13 @@ vi_status device_index_refine(const DeviceIndex &old, const float *table_host, u
     {
       MeansArgs a{(const float4 *)old.lists.blocks.p, dq, dim, (uint32_t)nlists, old.list_first_block.p, old.list_len.p, lay.prefix.p,
                   cur_p, seg.p, table[tc].p, table[tc ^ 1].p};
-      VI_HIP(hipEventRecord(ev.a, st));
+      VI_TRY(ev.begin(0, st));
       hipLaunchKernelGGL(list_means_kernel, dim3((uint32_t)nlists, (dim + kMeanCols - 1) / kMeanCols), dim3(kWave), 0, st, a);
       VI_HIP(hipGetLastError());
-      VI_HIP(hipEventRecord(ev.b, st));
+      VI_TRY(ev.end(0, st));
       VI_HIP(hipMemcpyAsync(h_new.data(), table[tc ^ 1].p, nlists * dim * sizeof(float), hipMemcpyDeviceToHost, st));
       VI_HIP(hipStreamSynchronize(st));
-      res->ms_means_kernel += elapsed_ms(ev.a, ev.b);
+      res->ms_means_kernel += ev.ms(0);
       // read: every record's values (and its ordinal on the gather path) and the old table; written: the new table
       res->means_bytes += n * (uint64_t)dim * 4 + (cur_p ? n * 4 : 0) + 2 * nlists * (uint64_t)dim * 4;
     }
@@ -327,15 +241,7 @@ vi_status device_index_refine(const DeviceIndex &old, const float *table_host, u
         StoredRowsWalk walk(64);
         VI_TRY(order_scratch.reserve(std::min(n, walk.chunk_rows)));
         return walk.run(old, ctx, all_rows, [&](const RowChunk &c) -> vi_status {
-          SearchIO io;
-          io.queries = ctx.ws.q.p;
-          io.on_device = true;
-          io.nq = c.m;
-          io.k = 1;
-          io.n_probe = 1;
-          io.probes_out = lab_ord.p + c.q0;
-          io.order_out = order_scratch.p;
-          return device_index_search(coarse, io);
+          return device_index_label_chunk(coarse, ctx.ws.q.p, c.m, lab_ord.p + c.q0, order_scratch.p);
         });
       });
       if (s != VI_OK) { (void)hipGetLastError(); return s; }
@@ -384,18 +290,10 @@ vi_status device_index_refine(const DeviceIndex &old, const float *table_host, u
   if (ix->nvec_resident != n) return fail(VI_ERR_OTHER, "refine: the new layout does not hold every record");
   const uint64_t total_blocks = ix->lists.nblocks;
   {
-    RehomeArgs a{(const float4 *)old.lists.blocks.p, old.ext_ids.p, old.timestamps.p, old.list_first_block.p, lay.prefix.p, (uint32_t)nlists,
-                 dq, cur_p, seg.p, ix->list_first_block.p, ix->list_len.p, block_list.p, total_blocks, (float4 *)ix->lists.blocks.p,
-                 ix->ext_ids.p, ix->timestamps.p};
-    VI_HIP(hipEventRecord(ev.a, st));
-    hipLaunchKernelGGL(rehome_blocks_kernel, dim3((uint32_t)((total_blocks + kRehomeWaves - 1) / kRehomeWaves)), dim3(kRehomeWaves * kWave),
-                       0, st, a);
-    VI_HIP(hipGetLastError());
-    VI_HIP(hipEventRecord(ev.b, st));
-    VI_HIP(hipStreamSynchronize(st));
-    res->ms_rehome_kernel = elapsed_ms(ev.a, ev.b);
-    // read + written: every new block once each way (blocks, ids, timestamps), less what pad lanes do not read; the order
-    res->rehome_bytes = 2 * total_blocks * ((uint64_t)dq * kWave * 16 + kWave * 16) + n * 4;
+    const RehomeArgs a{old_blocks_of(old), old.list_first_block.p, lay.prefix.p, (uint32_t)nlists, dq, cur_p, seg.p,
+                       ix->list_first_block.p, ix->list_len.p, block_list.p, total_blocks, new_blocks_of(ix)};
+    VI_TRY(launch_block_kernel(rehome_blocks_kernel, a, total_blocks, st, &res->ms_rehome_kernel));
+    res->rehome_bytes = block_bytes_moved(total_blocks, dq) + n * 4;  // (... and the order)
   }
   VI_TRY(coarse_table_from_rows(ix, table[tc].p));
   const double t3 = now_ms();
@@ -404,64 +302,6 @@ vi_status device_index_refine(const DeviceIndex &old, const float *table_host, u
   res->ms_images = (float)(now_ms() - t3);
   res->table.swap(h_table);
   return VI_OK;
-}
-
-// One shard file from the blocks of a resident index, the frame by the routines shard_save_to uses (shards.cpp:
-// byte-identical): cids = the shard's lists in file order, their centroid vectors cvecs_host (cids.size() x dim).  The
-// file goes to `path` (a temporary name of the caller's); a file left short by a failed write is removed.
-vi_status shard_export_blocks(const DeviceIndex &ix, const std::string &path, uint64_t shard_id, const std::vector<uint64_t> &cids,
-                              const float *cvecs_host, ShardExportWs &ws, DevBuf<uint64_t> &id0_buf, uint64_t *bytes_out) {
-  hipStream_t st = ix.stream;
-  VI_HIP(hipSetDevice(ix.device));
-  VI_TRY(ensure_fetch_layout(ix, st));
-  const FetchState &lay = ix.fetch;
-  const uint32_t nl = (uint32_t)cids.size(), dim = ix.dim;
-  std::vector<uint64_t> counts(nl);
-  uint64_t nrec = 0;
-  for (uint32_t i = 0; i < nl; ++i) {
-    if (cids[i] >= ix.nlists) return fail(VI_ERR_INVALID_DATA, "shard %llu names a list the index does not hold", (unsigned long long)shard_id);
-    counts[i] = lay.h_len[cids[i]];
-    nrec += counts[i];
-  }
-  if (nrec >= 0xFFFFFFFFull) return fail(VI_ERR_OTHER, "shard with more than 2^32 records");
-  const ShardPlan pl(dim, counts);
-  const uint64_t data_off = pl.data_off, total = pl.total;
-  VI_TRY(ws.image.reserve(total + 16));
-  if (ws.host_cap < total) {
-    if (ws.host) (void)hipHostFree(ws.host);
-    ws.host = nullptr;
-    ws.host_cap = 0;
-    VI_HIP(hipHostMalloc((void **)&ws.host, total + 16));
-    ws.host_cap = total;
-  }
-  std::vector<uint64_t> k_slot0, k_id0, k_dst;
-  std::vector<uint32_t> k_first;
-  for (uint32_t i = 0, first = 0; i < nl; ++i) {
-    if (counts[i]) {
-      k_slot0.push_back(refine_slot(lay.h_first[cids[i]], 0));
-      k_id0.push_back(lay.h_prefix[cids[i]]);
-      k_dst.push_back(pl.records(i));
-      k_first.push_back(first);
-    }
-    first += (uint32_t)counts[i];
-  }
-  if (nrec) {
-    VI_TRY(upload(ws.d_src, k_slot0.data(), k_slot0.size(), st));
-    VI_TRY(upload(id0_buf, k_id0.data(), k_id0.size(), st));
-    VI_TRY(upload(ws.d_dst, k_dst.data(), k_dst.size(), st));
-    VI_TRY(upload(ws.d_first, k_first.data(), k_first.size(), st));
-    BlockExportArgs a{ix.lists.blocks.p, ix.ext_ids.p, ix.timestamps.p, ws.d_src.p, id0_buf.p, ws.d_dst.p, ws.d_first.p,
-                      (uint32_t)k_slot0.size(), dim, ix.dq, (uint32_t)pl.stride, nrec, ws.image.p};
-    hipLaunchKernelGGL(export_block_records_kernel, dim3((uint32_t)((nrec + 3) / 4)), dim3(256), 0, st, a);
-    VI_HIP(hipGetLastError());
-    VI_HIP(hipMemcpyAsync(ws.host + data_off, ws.image.p + data_off, total - data_off, hipMemcpyDeviceToHost, st));
-    VI_HIP(hipStreamSynchronize(st));  // (k_* are read by the copies above)
-  }
-  std::vector<const void *> cvecs(nl);
-  for (uint32_t i = 0; i < nl; ++i) cvecs[i] = cvecs_host + (uint64_t)i * dim;
-  shard_frame_write(ws.host, pl, shard_id, cids.data(), cvecs.data());
-  if (bytes_out) *bytes_out = total;
-  return shard_image_write(path, ws.host, total, true);
 }
 
 }  // namespace vi

@@ -2,16 +2,17 @@
 // vi_indexer_upsert_records: a new DeviceIndex from the blocks of the old one, without re-reading a shard file.  One
 // route, device_index_update, with two optional halves — what goes (a keep filter) and what joins (rows):
 //
-//   begin_update: the refusals, a fresh index on the old one's device
+//   refuse_update, begin_update (list_blocks.hpp; defined here): the refusals, a fresh index on the old one's device
 //     -> the records every list keeps: with a filter, kept_count_kernel and one read-back; without, the old lengths the
 //        caller read (nothing is launched)
 //     -> on the host: new length = kept + rows received, the new layout from the new lengths, and the list of every new
 //        block (lay_out_from_old)
 //     -> one wave per NEW block, lane = vector (update_blocks_kernel).  A block whose 64 positions are the records of one
-//        old block is a straight copy of it (copy_old_block).  Pad lanes get what every index upload leaves there: zero
-//        vectors, external id ~0, timestamp 0.  Every word of the new blocks / ext_ids / timestamps is written exactly once.
-//     -> finish_update: the launch between two events, then prepare_rank_images: norms, images and the rank mode's
-//        statistics, by the code a load runs.
+//        old block is a straight copy of it.  Pad lanes get what every index upload leaves there: zero vectors, external
+//        id ~0, timestamp 0.  Every word of the new blocks / ext_ids / timestamps is written exactly once.  The copy, the
+//        fill of a lane's column and the pad values are list_blocks.hpp's, shared with a refine's rehome_blocks_kernel.
+//     -> finish_update: the launch between two events (launch_block_kernel), then prepare_rank_images: norms, images and
+//        the rank mode's statistics, by the code a load runs.
 //
 // What goes.  keep.allow holds one bit per old slot, pad slots 0.  kept_count_kernel, one wave per list: lanes stride over
 // the list's old blocks; the popcount of each block's allow word, scanned across the wave with a carry from stride to
@@ -22,7 +23,7 @@
 // and allow, block_prefix and kept are never read.
 //
 // What joins.  The new rows (device, row-major, uploaded once) get their label from the coarse step of the old index with
-// n_probe = 1 (device_index_label_rows: device_index_search with probes_out, in chunks) — the first probe of the
+// n_probe = 1 (device_index_label_rows: device_index_label_chunk, a search with probes_out, chunk by chunk) — the first probe of the
 // reference's coarse step (ivf_index.rs:205-220), whatever engine ranks it — and are grouped by label, ascending call
 // index inside a label (group_ids_by_label_device).  Position kept[l] <= p < new_len[l] reads its row from the row-major
 // upload (as repack_rows_kernel reads it).  No rows: new_len == kept everywhere, no lane is new, and rows, order, seg,
@@ -37,6 +38,7 @@
 #include <vector>
 
 #include "device_index.hpp"
+#include "list_blocks.hpp"
 #include "search_internal.hpp"
 #include "slot_filter.hpp"
 
@@ -44,7 +46,6 @@ namespace vi {
 namespace {
 
 constexpr int kWave = 64;
-constexpr int kUpdateWaves = 4;            // waves per workgroup: new blocks of update_blocks_kernel, lists of kept_count_kernel
 constexpr uint64_t kLabelChunk = 65536;    // rows per coarse step
 
 struct CountArgs {
@@ -55,9 +56,9 @@ struct CountArgs {
   uint32_t *kept;                          // per list
 };
 
-__global__ void __launch_bounds__(kUpdateWaves * kWave) kept_count_kernel(CountArgs a) {
+__global__ void __launch_bounds__(kBlockWaves * kWave) kept_count_kernel(CountArgs a) {
   const uint32_t lane = threadIdx.x & (kWave - 1);
-  const uint32_t l = blockIdx.x * kUpdateWaves + (threadIdx.x >> 6);
+  const uint32_t l = blockIdx.x * kBlockWaves + (threadIdx.x >> 6);
   if (l >= a.nlists) return;
   const uint32_t first = a.old_first[l], nblk = (a.old_len[l] + kWave - 1) / kWave;
   uint32_t carry = 0;
@@ -77,9 +78,7 @@ __global__ void __launch_bounds__(kUpdateWaves * kWave) kept_count_kernel(CountA
 }
 
 struct UpdateArgs {
-  // the old index
-  const float4 *old_blocks;
-  const uint64_t *old_ext, *old_ts;
+  OldBlocks old;                           // the old index
   const uint32_t *old_first, *old_len;     // per list
   // what is kept of it.  allow == nullptr: everything, and none of the three is read
   const uint64_t *allow;                   // per old block
@@ -95,24 +94,8 @@ struct UpdateArgs {
   const uint64_t *row_ext, *row_ts;        // per row, resolved on the host
   const uint32_t *order, *seg;
   uint32_t dim, dq;
-  float4 *blocks;
-  uint64_t *ext, *ts;
+  NewBlocks out;
 };
-
-// A new block that is one old block, vectors, ids and timestamps: four 1 KiB rows in flight.  src / dst: the lane's column
-// of the old / new block, old_slot / slot: its slot there.
-__device__ __forceinline__ void copy_old_block(const UpdateArgs &a, const float4 *src, float4 *dst, uint64_t old_slot, uint64_t slot) {
-  for (uint32_t qd = 0; qd < a.dq; qd += 4) {  // (dq is a multiple of 4: layout_dq)
-    const float4 t0 = src[(size_t)(qd + 0) * kWave], t1 = src[(size_t)(qd + 1) * kWave];
-    const float4 t2 = src[(size_t)(qd + 2) * kWave], t3 = src[(size_t)(qd + 3) * kWave];
-    dst[(size_t)(qd + 0) * kWave] = t0;
-    dst[(size_t)(qd + 1) * kWave] = t1;
-    dst[(size_t)(qd + 2) * kWave] = t2;
-    dst[(size_t)(qd + 3) * kWave] = t3;
-  }
-  a.ext[slot] = a.old_ext[old_slot];
-  a.ts[slot] = a.old_ts[old_slot];
-}
 
 // the r-th (from 0) set bit of w, which has more than r set bits: halve the word, step into the half that holds it
 __device__ __forceinline__ uint32_t nth_set_bit(uint64_t w, uint32_t r) {
@@ -142,21 +125,19 @@ __device__ __forceinline__ float4 row_quad(const float *v, uint32_t qd, uint32_t
 // kRows: there may be rows (else kept == new_len and rows / order / seg / row_ext / row_ts are not read).  One body, the
 // three instantiations finish_update chooses from: the two tests cost the remove route 1 % as kernel arguments (r14).
 template <bool kDrops, bool kRows>
-__global__ void __launch_bounds__(kUpdateWaves * kWave) update_blocks_kernel(UpdateArgs a) {
+__global__ void __launch_bounds__(kBlockWaves * kWave) update_blocks_kernel(UpdateArgs a) {
   const uint32_t lane = threadIdx.x & (kWave - 1);
-  const uint64_t b = (uint64_t)blockIdx.x * kUpdateWaves + (threadIdx.x >> 6);
+  const uint64_t b = (uint64_t)blockIdx.x * kBlockWaves + (threadIdx.x >> 6);
   if (b >= a.nblocks) return;
   const uint32_t l = a.block_list[b];
   const uint32_t j = (uint32_t)(b - a.new_first[l]);           // block of the list
   const uint32_t old_len = a.old_len[l], new_len = a.new_len[l], old_first = a.old_first[l];
   const uint32_t kept = !kDrops ? old_len : !kRows ? new_len : a.kept[l];
   const uint32_t dq = a.dq;
-  float4 *dst = a.blocks + (b * dq) * kWave + lane;
-  const uint64_t slot = b * kWave + lane;
   const bool lost_nothing = kept == old_len;                   // (wave-uniform) kept positions are the old ones
   // a straight copy needs both: a list that loses one record and receives one keeps its length and moves every position
   if (lost_nothing && j * kWave + (kWave - 1) < old_len) {     // ... and all 64 are old records
-    copy_old_block(a, a.old_blocks + ((uint64_t)(old_first + j) * dq) * kWave + lane, dst, (uint64_t)(old_first + j) * kWave + lane, slot);
+    copy_old_block(a.old, a.out, dq, old_first + j, b, lane);
     return;
   }
   const uint32_t p = j * kWave + lane;                         // position inside the new list (new_len < 2^32 - 64)
@@ -177,106 +158,83 @@ __global__ void __launch_bounds__(kUpdateWaves * kWave) update_blocks_kernel(Upd
     sb = lo;
     sl = is_old ? nth_set_bit(a.allow[old_first + sb], ps - a.block_prefix[old_first + sb]) : 0u;
   }
-  const float4 *src = a.old_blocks + ((uint64_t)(old_first + sb) * dq) * kWave + sl;  // (read only where is_old)
+  const float4 *src = a.old.blocks + ((uint64_t)(old_first + sb) * dq) * kWave + sl;  // (read only where is_old)
   const uint64_t old_slot = (uint64_t)(old_first + sb) * kWave + sl;
   uint32_t row = 0;
   if (is_new) row = a.order[a.seg[l] + (p - kept)];
   const float *v = a.rows + (size_t)row * a.dim;               // (read only where is_new)
-  for (uint32_t qd = 0; qd < dq; qd += 4) {  // four rows in flight (dq is a multiple of 4: layout_dq)
-    float4 t0 = make_float4(0.f, 0.f, 0.f, 0.f), t1 = t0, t2 = t0, t3 = t0;
+  fill_block_column(a.out.blocks + (b * dq) * kWave + lane, dq, [&](uint32_t qd, float4 (&t)[4]) {
     if (is_old) {
-      t0 = src[(size_t)(qd + 0) * kWave];
-      t1 = src[(size_t)(qd + 1) * kWave];
-      t2 = src[(size_t)(qd + 2) * kWave];
-      t3 = src[(size_t)(qd + 3) * kWave];
+      load_block_quads(src, qd, t);
     } else if (is_new) {
-      t0 = row_quad(v, qd + 0, a.dim);
-      t1 = row_quad(v, qd + 1, a.dim);
-      t2 = row_quad(v, qd + 2, a.dim);
-      t3 = row_quad(v, qd + 3, a.dim);
+#pragma unroll
+      for (uint32_t i = 0; i < 4; ++i) t[i] = row_quad(v, qd + i, a.dim);
     }
-    dst[(size_t)(qd + 0) * kWave] = t0;
-    dst[(size_t)(qd + 1) * kWave] = t1;
-    dst[(size_t)(qd + 2) * kWave] = t2;
-    dst[(size_t)(qd + 3) * kWave] = t3;
-  }
-  a.ext[slot] = is_old ? a.old_ext[old_slot] : is_new ? a.row_ext[row] : ~0ull;
-  a.ts[slot] = is_old ? a.old_ts[old_slot] : is_new ? a.row_ts[row] : 0ull;
+  });
+  const uint64_t slot = b * kWave + lane;
+  a.out.ext[slot] = is_old ? a.old.ext[old_slot] : is_new ? a.row_ext[row] : kPadExtId;
+  a.out.ts[slot] = is_old ? a.old.ts[old_slot] : is_new ? a.row_ts[row] : kPadTimestamp;
 }
 
-struct EventPair {
-  hipEvent_t a = nullptr, b = nullptr;
-  ~EventPair() {
-    if (a) (void)hipEventDestroy(a);
-    if (b) (void)hipEventDestroy(b);
-  }
-};
-
-// What an update begins with: the refusals (`refusal`: the call's own words for a partitioned index), a fresh index on
-// old's device with old's summation order and timing, the two out-values at zero.
-vi_status begin_update(const DeviceIndex &old, const char *refusal, DeviceIndex *ix, float *ms_kernel, uint64_t *kernel_bytes) {
-  if (old.stripe_world > 1) return fail(VI_ERR_INVALID_INPUT, "%s", refusal);
-  if (!old.timestamps.p || !old.ext_ids.p) return fail(VI_ERR_INVALID_INPUT, "the index keeps no ids or timestamps");
-  VI_TRY(init_device_index(ix, old.device, old.dim, old.nlists));
-  ix->order = old.order;
-  ix->timing = old.timing;
-  if (ms_kernel) *ms_kernel = 0.0f;
-  if (kernel_bytes) *kernel_bytes = 0;
-  return VI_OK;
-}
-
-// ... and ends with, once lay_out_from_old has run: the old index, the new layout and the new storage filled in, the block
-// kernel timed between two events (one wave per new block), prepare_rank_images.
+// ... and an update ends with, once lay_out_from_old has run: the old index, the new layout and the new storage filled
+// in, the block kernel timed between two events (one wave per new block), prepare_rank_images.
 vi_status finish_update(const DeviceIndex &old, DeviceIndex *ix, const DevBuf<uint32_t> &block_list, UpdateArgs a, float *ms_kernel,
                         uint64_t *kernel_bytes) {
-  hipStream_t st = ix->stream;
   const uint64_t total_blocks = ix->lists.nblocks;
   if (total_blocks) {
-    a.old_blocks = (const float4 *)old.lists.blocks.p;
-    a.old_ext = old.ext_ids.p; a.old_ts = old.timestamps.p;
+    a.old = old_blocks_of(old);
     a.old_first = old.list_first_block.p; a.old_len = old.list_len.p;
     a.new_first = ix->list_first_block.p; a.new_len = ix->list_len.p;
     a.block_list = block_list.p; a.nblocks = total_blocks;
     a.dim = ix->dim; a.dq = ix->dq;
-    a.blocks = (float4 *)ix->lists.blocks.p; a.ext = ix->ext_ids.p; a.ts = ix->timestamps.p;
-    EventPair ev;
-    VI_HIP(hipEventCreate(&ev.a));
-    VI_HIP(hipEventCreate(&ev.b));
-    VI_HIP(hipEventRecord(ev.a, st));
+    a.out = new_blocks_of(ix);
     // (rows without a filter, a filter without rows, both; neither — nothing changes — runs as the first: no lane is new)
     void (*kernel)(UpdateArgs) = !a.allow ? update_blocks_kernel<false, true> : !a.rows ? update_blocks_kernel<true, false>
                                                                                          : update_blocks_kernel<true, true>;
-    hipLaunchKernelGGL(kernel, dim3((uint32_t)((total_blocks + kUpdateWaves - 1) / kUpdateWaves)), dim3(kUpdateWaves * kWave), 0, st, a);
-    VI_HIP(hipGetLastError());
-    VI_HIP(hipEventRecord(ev.b, st));
-    VI_HIP(hipStreamSynchronize(st));  // (the block list and the caller's scratch are freed on return)
-    if (ms_kernel) (void)hipEventElapsedTime(ms_kernel, ev.a, ev.b);
-    // read + written: every new block once each way (blocks, ids, timestamps), less what pad and new lanes do not read
-    if (kernel_bytes) *kernel_bytes = 2 * total_blocks * ((uint64_t)ix->dq * kWave * 16 + kWave * 16);
+    VI_TRY(launch_block_kernel(kernel, a, total_blocks, ix->stream, ms_kernel));  // (the block list and the caller's scratch are freed on return)
+    if (kernel_bytes) *kernel_bytes = block_bytes_moved(total_blocks, ix->dq);
   }
   return prepare_rank_images(ix);
 }
 
 }  // namespace
 
+vi_status refuse_update(const DeviceIndex &old, const char *refusal) {
+  if (old.stripe_world > 1) return fail(VI_ERR_INVALID_INPUT, "%s", refusal);
+  if (!old.timestamps.p || !old.ext_ids.p) return fail(VI_ERR_INVALID_INPUT, "the index keeps no ids or timestamps");
+  return VI_OK;
+}
+
+vi_status begin_update(const DeviceIndex &old, DeviceIndex *ix) {
+  VI_TRY(init_device_index(ix, old.device, old.dim, old.nlists));
+  ix->order = old.order;
+  ix->timing = old.timing;
+  return VI_OK;
+}
+
+// One chunk of a labelling: labels_dev[i] = the first probe of ix's coarse step for row i of the m rows at rows_dev.
+// order_scratch: m words (the coarse step writes the candidate-order ranks too: all zero at one probe).
+vi_status device_index_label_chunk(const DeviceIndex &ix, const float *rows_dev, uint64_t m, uint32_t *labels_dev, uint32_t *order_scratch) {
+  SearchIO io;
+  io.queries = rows_dev;
+  io.on_device = true;
+  io.nq = m;
+  io.k = 1;
+  io.n_probe = 1;
+  io.probes_out = labels_dev;
+  io.order_out = order_scratch;
+  return device_index_search(ix, io);
+}
+
 // labels_dev[i] = the list the reference's coarse step probes first for row i: the old index's own coarse step, n_probe 1
 vi_status device_index_label_rows(const DeviceIndex &ix, const float *rows_dev, uint64_t n, uint32_t *labels_dev) {
   if (n == 0) return VI_OK;
   if (ix.nlists == 0) return fail(VI_ERR_INVALID_INPUT, "the index has no list to add to");
   VI_HIP(hipSetDevice(ix.device));
-  DevBuf<uint32_t> order_scratch;  // (the coarse step writes the candidate-order ranks too: all zero at one probe)
+  DevBuf<uint32_t> order_scratch;
   VI_TRY(order_scratch.reserve(std::min(n, kLabelChunk)));
-  for (uint64_t at = 0; at < n; at += kLabelChunk) {
-    SearchIO io;
-    io.queries = rows_dev + at * ix.dim;
-    io.on_device = true;
-    io.nq = std::min(kLabelChunk, n - at);
-    io.k = 1;
-    io.n_probe = 1;
-    io.probes_out = labels_dev + at;
-    io.order_out = order_scratch.p;
-    VI_TRY(device_index_search(ix, io));
-  }
+  for (uint64_t at = 0; at < n; at += kLabelChunk)
+    VI_TRY(device_index_label_chunk(ix, rows_dev + at * ix.dim, std::min(kLabelChunk, n - at), labels_dev + at, order_scratch.p));
   return VI_OK;
 }
 
@@ -288,8 +246,11 @@ vi_status device_index_update(const DeviceIndex &old, const SlotFilter *keep, co
                               const uint64_t *row_ext_dev, const uint64_t *row_ts_dev, const std::vector<uint32_t> &old_len_host,
                               DeviceIndex *ix, float *ms_kernel, uint64_t *kernel_bytes) {
   const uint64_t nlists = old.nlists;
-  VI_TRY(begin_update(old, !keep ? "a partitioned index takes no records" : n == 0 ? "a partitioned index gives no records up"
-                                 : "a partitioned index takes no records and gives none up", ix, ms_kernel, kernel_bytes));
+  VI_TRY(refuse_update(old, !keep ? "a partitioned index takes no records" : n == 0 ? "a partitioned index gives no records up"
+                                  : "a partitioned index takes no records and gives none up"));
+  VI_TRY(begin_update(old, ix));
+  if (ms_kernel) *ms_kernel = 0.0f;
+  if (kernel_bytes) *kernel_bytes = 0;
   if (keep && keep->owner_serial != old.serial) return fail(VI_ERR_INVALID_INPUT, "the filter was made from another index");
   if (n && (seg_host.size() != nlists + 1 || seg_host[nlists] != n)) return fail(VI_ERR_OTHER, "update: grouping does not match the index");
   if (!keep && old_len_host.size() != nlists) return fail(VI_ERR_OTHER, "update: the list lengths do not match the index");
@@ -304,8 +265,8 @@ vi_status device_index_update(const DeviceIndex &old, const SlotFilter *keep, co
     if (nlists) {
       hipStream_t st = ix->stream;
       CountArgs c{keep->allow.p, old.list_first_block.p, old.list_len.p, (uint32_t)nlists, block_prefix.p, d_kept.p};
-      hipLaunchKernelGGL(kept_count_kernel, dim3((uint32_t)((nlists + kUpdateWaves - 1) / kUpdateWaves)),
-                         dim3(kUpdateWaves * kWave), 0, st, c);
+      hipLaunchKernelGGL(kept_count_kernel, dim3((uint32_t)((nlists + kBlockWaves - 1) / kBlockWaves)),
+                         dim3(kBlockWaves * kWave), 0, st, c);
       VI_HIP(hipGetLastError());
       VI_HIP(hipMemcpyAsync(counted.data(), d_kept.p, nlists * 4, hipMemcpyDeviceToHost, st));
       VI_HIP(hipStreamSynchronize(st));

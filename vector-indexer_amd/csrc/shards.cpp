@@ -333,7 +333,12 @@ vi_status ShardRewriteSet::find(const ShardFile &f, uint64_t s, uint32_t l, uint
 }
 
 void ShardRewriteSet::add(uint64_t s, uint64_t bytes) {
-  pairs_.emplace_back(temporary(s), shard_file_path(dir_, s));
+  add_pair(temporary(s), shard_file_path(dir_, s), bytes);
+  ++shard_files_;
+}
+
+void ShardRewriteSet::add_pair(std::string temporary, std::string final_path, uint64_t bytes) {
+  pairs_.emplace_back(std::move(temporary), std::move(final_path));
   bytes_ += bytes;
 }
 
@@ -424,31 +429,13 @@ vi_status index_meta_write(const IndexMeta &m, const std::string &path, uint64_t
   return VI_OK;
 }
 
-vi_status index_meta_replace(const IndexMeta &m, const std::string &index_dir, IndexMetaRewrite *rw) {
-  rw->tmp_ = index_dir + "/index.bin.tmp";
-  rw->final_ = index_dir + "/index.bin";
-  const vi_status s = index_meta_write(m, rw->tmp_, &rw->bytes_);
-  if (s != VI_OK) {
-    ::remove(rw->tmp_.c_str());
-    rw->tmp_.clear();
-  }
+vi_status index_meta_replace(const IndexMeta &m, const std::string &index_dir, ShardRewriteSet *set) {
+  const std::string path = index_dir + "/index.bin", tmp = path + ".tmp";
+  uint64_t bytes = 0;
+  const vi_status s = index_meta_write(m, tmp, &bytes);
+  if (s != VI_OK) ::remove(tmp.c_str());
+  else set->add_pair(tmp, path, bytes);
   return s;
-}
-
-vi_status IndexMetaRewrite::commit() {
-  if (tmp_.empty()) return fail(VI_ERR_OTHER, "index.bin: nothing was written");
-  if (::rename(tmp_.c_str(), final_.c_str()) != 0) {
-    const int e = errno;
-    ::remove(tmp_.c_str());
-    tmp_.clear();
-    return fail(VI_ERR_IO, "rename(%s): %s", final_.c_str(), strerror(e));
-  }
-  tmp_.clear();
-  return VI_OK;
-}
-
-IndexMetaRewrite::~IndexMetaRewrite() {
-  if (!tmp_.empty()) ::remove(tmp_.c_str());
 }
 
 vi_status index_meta_load(const std::string &index_dir, IndexMeta *out) {

@@ -85,7 +85,7 @@ vi_status shard_save_to(const std::string &shards_dir, uint64_t shard_id, uint32
 // The file is written to out_path — byte-identical to shard_save_to of the resulting lists: lists keep their file order,
 // centroid vectors and kept records are copied verbatim, in runs (VectorMeta.id included), a list that keeps nothing and
 // receives nothing stays as an entry with num_vectors == 0 — and f's own file is left alone: the caller renames out_path
-// over it when every file of its batch is complete (api.cpp: update_records).  bytes_out / removed_out / lists_out
+// over it when every file of its batch is complete (index_lifecycle.cpp: update_records).  bytes_out / removed_out / lists_out
 // (optional): size of the file written, records removed, lists that lost or received a record.
 vi_status shard_update_write(const ShardFile &f, uint64_t shard_id, const std::vector<const uint64_t *> &keep, uint64_t n_add,
                              const uint64_t *centroid_ids, const uint64_t *ids, const uint64_t *ext_ids,
@@ -105,9 +105,10 @@ vi_status shard_upsert_to(const std::string &shards_dir, uint64_t shard_id, uint
                           const uint64_t *ids, const uint64_t *ext_ids, const uint64_t *timestamps, const float *vecs,
                           uint64_t *removed_out);
 
-// The shard files one call rewrites: every file is written beside the old one under a temporary name and registered;
-// commit() renames them over the old files in the order registered.  Whatever is registered and not renamed when the set
-// goes away is unlinked: a call can fail anywhere before commit() without a trace.  Host only.
+// The files one call rewrites: every file is written beside the old one under a temporary name and registered; commit()
+// renames them over the old files in the order registered.  Whatever is registered and not renamed when the set goes
+// away is unlinked: a call can fail anywhere before commit() without a trace.  The shard files of a call, and behind
+// them its index.bin if the call changes the table (index_meta_replace).  Host only.
 class ShardRewriteSet {
  public:
   explicit ShardRewriteSet(std::string shards_dir) : dir_(std::move(shards_dir)) {}
@@ -121,18 +122,20 @@ class ShardRewriteSet {
   vi_status find(const ShardFile &f, uint64_t s, uint32_t l, uint32_t len, const ShardListView **out) const;
   std::string temporary(uint64_t s) const { return shard_file_path(dir_, s) + ".tmp"; }
   void add(uint64_t s, uint64_t bytes);  // temporary(s) is written, `bytes` long
+  // any other pair: `temporary` is written, `bytes` long, and becomes `final_path` (counted by bytes(), not by files())
+  void add_pair(std::string temporary, std::string final_path, uint64_t bytes);
   // Renames in order.  The first failure unlinks the temporaries not yet renamed: VI_ERR_IO (the files renamed before it
   // stay in place, and the message says so).  Close every ShardFile of the set's files first.
   vi_status commit();
-  uint64_t files() const { return pairs_.size(); }
-  uint64_t bytes() const { return bytes_; }
+  uint64_t files() const { return shard_files_; }  // shard files registered
+  uint64_t bytes() const { return bytes_; }        // of every pair
 
  private:
   void drop();
   std::string dir_;
   std::vector<std::pair<std::string, std::string>> pairs_;  // (temporary, final)
   size_t done_ = 0;                                         // pairs renamed or unlinked
-  uint64_t bytes_ = 0;
+  uint64_t shard_files_ = 0, bytes_ = 0;
 };
 
 // index/index.bin: IvfIndex{centroids, centroids_to_shard, dimension} through bincode 2
@@ -147,23 +150,9 @@ vi_status index_meta_save(const IndexMeta &m, const std::string &index_dir);
 vi_status index_meta_load(const std::string &index_dir, IndexMeta *out);
 // the same bytes to any path (bytes_out, optional: how many)
 vi_status index_meta_write(const IndexMeta &m, const std::string &path, uint64_t *bytes_out);
-// index.bin rewritten as the shard files of a ShardRewriteSet are: written to index.bin.tmp beside it (index_meta_replace),
-// renamed over it by commit(); what is written and not renamed when the object goes away is unlinked.  Host only.
-class IndexMetaRewrite {
- public:
-  IndexMetaRewrite() = default;
-  ~IndexMetaRewrite();
-  IndexMetaRewrite(const IndexMetaRewrite &) = delete;
-  IndexMetaRewrite &operator=(const IndexMetaRewrite &) = delete;
-  vi_status commit();
-  uint64_t bytes() const { return bytes_; }
-
- private:
-  friend vi_status index_meta_replace(const IndexMeta &m, const std::string &index_dir, IndexMetaRewrite *rw);
-  std::string tmp_, final_;
-  uint64_t bytes_ = 0;
-};
-vi_status index_meta_replace(const IndexMeta &m, const std::string &index_dir, IndexMetaRewrite *rw);
+// index.bin as one more file of a rewrite set: written to index.bin.tmp beside it and registered as the set's last pair
+// so far (a temporary left short by a failed write is removed, nothing is registered)
+vi_status index_meta_replace(const IndexMeta &m, const std::string &index_dir, ShardRewriteSet *set);
 
 // batched vector file of read_vectors_from_file (src/utils.rs:82-107): concatenated
 // bincode Vec<(u64, Vec<f32>, u64)> batches.  Decoding stops silently at the first
