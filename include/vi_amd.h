@@ -577,6 +577,63 @@ typedef struct vi_refine_stats {
   float ms_rehome_kernel;    /* HIP-event time of rehome_blocks_kernel alone (part of ms_rehome) */
 } vi_refine_stats;
 vi_status vi_indexer_last_refine_stats(const vi_indexer *ix, vi_refine_stats *out);
+
+/* ---- extension: rebalance a built or loaded index — a refine whose first iterations split overfull lists into the empty
+ * ones (the cure Faiss's k-means applies to an empty cluster).  A refine is warm-started, so it never moves a centroid
+ * across the data: a list many adds piled into stays one list, a list vi_indexer_remove_ids emptied stays empty.  Here an
+ * empty (or nearly empty) list takes over one half of an overfull one.  The number of lists, the list ids and
+ * centroids_to_shard do not change ----
+ * The call runs rule->iters iterations of vi_indexer_refine's contract; each of the first rule->split_rounds of them is
+ * that contract's steps 1, 1b, 2, 3 over the records in the current list order (1, 2 and 3 verbatim):
+ *  1b. PLAN, from the list lengths len[] at the start of the iteration, mean = n / lists in double:
+ *        donors     the lists with len >= 2 and (double)len > split_factor * mean, by (len descending, index ascending)
+ *        receivers  the lists with len <= receiver_max_len, by (len ascending, index ascending); a list that qualifies
+ *                   as both is a donor only
+ *        pair i = (donor i, receiver i) for i < min(#donors, #receivers, max_splits or no cap)
+ *      SPLIT of pair (d, r) over the members x_0 .. x_{m-1} of d in list order, c = C'[d] from step 1.  Every distance is
+ *      the reference's euclidean_distance_squared scalar chain (utils.rs:28-30): an unfused (a - b) * (a - b) accumulated
+ *      in column order, the arithmetic of the coarse step.
+ *        seeds   a = the position with the largest d(x_i, c), b = the position with the largest d(x_i, x_a), each the
+ *                lowest position among equals.  d(x_b, x_a) == 0 (all members equal): the pair is SKIPPED — both
+ *                centroids stay as step 1 left them.  Otherwise ca = x_a, cb = x_b.
+ *        inner iteration, at most split_iters times: side_i = 1 if d(x_i, cb) < d(x_i, ca), else 0 (a tie goes to side
+ *                0).  Either side empty: stop, keep ca and cb.  Otherwise ca' / cb' = the centre of the side-0 / side-1
+ *                members: step 1's chain per column over THAT side's members in list order, then its one divide.  Stop
+ *                after an inner iteration that left every bit of ca and cb unchanged.
+ *        result  C'[d] = ca, C'[r] = cb.  A receiver that still holds records loses them to step 2 like any other record;
+ *                the split itself touches no record.
+ * Step 2 labels against the table after 1b, and the fixed-point test compares THAT table with the iteration's input
+ * table: an iteration whose plan is empty or wholly skipped is a plain refine iteration and may end the call early.
+ *   - split_rounds == 0: the call IS vi_indexer_refine(iters), file for file
+ *   - files, crash behaviour, resident index and filters, device memory: as vi_indexer_refine (beside its memory: one
+ *     byte per member of the donors, two centres and a few words per pair)
+ *   - errors, all VI_ERR_INVALID_INPUT before any file or device change: a null rule, iters == 0, split_rounds > iters, a
+ *     split_factor that is not finite or below 1, split_iters outside 1..64, a non-zero reserved0, and everything
+ *     vi_indexer_refine refuses (a null ix, no index, a partitioned handle, no record) */
+typedef struct vi_rebalance_rule {
+  uint64_t iters;            /* iterations of vi_indexer_refine's contract, >= 1 */
+  uint64_t split_rounds;     /* the first split_rounds iterations carry a split step; <= iters; 0: the call IS vi_indexer_refine(iters) */
+  double   split_factor;     /* a donor is longer than split_factor * (n / lists); finite, >= 1.0 */
+  uint64_t receiver_max_len; /* a receiver holds at most this many records; 0 = empty lists only */
+  uint64_t max_splits;       /* pairs per round at most; 0 = no cap */
+  uint32_t split_iters;      /* inner two-means iterations of a split, 1..64 */
+  uint32_t reserved0;
+} vi_rebalance_rule;
+void vi_rebalance_rule_init(vi_rebalance_rule *r);   /* 1, 1, 2.0, 0, 0, 4 */
+vi_status vi_indexer_rebalance(vi_indexer *ix, const vi_rebalance_rule *rule, uint64_t *moved_out);
+/* the most recent vi_indexer_rebalance on this handle that ran: the fields of vi_refine_stats, then the split steps */
+typedef struct vi_rebalance_stats {
+  uint64_t iterations_run, moved, lists_emptied, shards_rewritten, bytes_written, means_bytes, rehome_bytes;
+  float ms_total, ms_means, ms_label, ms_rehome, ms_images, ms_files, ms_means_kernel, ms_rehome_kernel;
+  uint64_t pairs_planned;    /* pairs of every round's plan */
+  uint64_t splits_done;      /* ... whose two centres went into the table */
+  uint64_t splits_skipped;   /* ... whose members were all equal */
+  uint64_t inner_iterations; /* inner iterations, summed over the pairs */
+  uint64_t split_bytes;      /* bytes the three split kernels read and wrote */
+  float ms_split;            /* plans and splits of every round, the table written back (wall clock; in none of the phases above) */
+  float ms_split_kernels;    /* HIP-event time of the split kernels alone (part of ms_split) */
+} vi_rebalance_stats;
+vi_status vi_indexer_last_rebalance_stats(const vi_indexer *ix, vi_rebalance_stats *out);
 /* the balance of the resident lists, from their lengths (on a rank of a partitioned index: the rank's part of every list):
  * when imbalance grows after many adds, a refine is due */
 typedef struct vi_list_stats {

@@ -410,6 +410,46 @@ vi_status vi_indexer_refine(vi_indexer *ix, uint64_t iters, uint64_t *moved_out)
   });
 }
 
+void vi_rebalance_rule_init(vi_rebalance_rule *r) {
+  if (!r) return;
+  *r = vi_rebalance_rule{};
+  r->iters = 1;
+  r->split_rounds = 1;
+  r->split_factor = 2.0;
+  r->split_iters = 4;
+}
+
+vi_status vi_indexer_rebalance(vi_indexer *ix, const vi_rebalance_rule *rule, uint64_t *moved_out) {
+  return vi::guarded([&]() -> vi_status {
+  if (moved_out) *moved_out = 0;
+  if (!ix) return fail(VI_ERR_INVALID_INPUT, "null indexer");
+  if (!rule) return fail(VI_ERR_INVALID_INPUT, "null rule");
+  if (rule->iters == 0) return fail(VI_ERR_INVALID_INPUT, "a rebalance runs at least one iteration");
+  if (rule->split_rounds > rule->iters) return fail(VI_ERR_INVALID_INPUT, "split_rounds exceeds iters");
+  if (!std::isfinite(rule->split_factor) || rule->split_factor < 1.0) return fail(VI_ERR_INVALID_INPUT, "split_factor must be finite and at least 1");
+  if (rule->split_iters < 1 || rule->split_iters > 64) return fail(VI_ERR_INVALID_INPUT, "split_iters must lie in 1..64");
+  if (rule->reserved0 != 0) return fail(VI_ERR_INVALID_INPUT, "reserved0 must be 0");
+  if (!ix->impl.dev) return fail(VI_ERR_INVALID_INPUT, "the indexer holds no index (build or load it first)");
+  if (ix->impl.cfg.world_size > 1 || ix->impl.dev->stripe_world > 1)
+    return fail(VI_ERR_INVALID_INPUT, "an index is rebalanced through an unpartitioned handle (world_size <= 1); ranks reload from its files");
+  if (ix->impl.dev->nlists == 0 || ix->impl.dev->nvec_resident == 0)
+    return fail(VI_ERR_INVALID_INPUT, "the index holds no record to rebalance by");
+  vi::SplitRule sr;
+  sr.split_rounds = rule->split_rounds;
+  sr.split_factor = rule->split_factor;
+  sr.receiver_max_len = rule->receiver_max_len;
+  sr.max_splits = rule->max_splits;
+  sr.split_iters = rule->split_iters;
+  return vi::refine_records(&ix->impl, rule->iters, moved_out, &sr);
+  });
+}
+
+vi_status vi_indexer_last_rebalance_stats(const vi_indexer *ix, vi_rebalance_stats *out) {
+  if (!ix || !out) return fail(VI_ERR_INVALID_INPUT, "null pointer");
+  *out = ix->impl.rebalance_stats;
+  return VI_OK;
+}
+
 vi_status vi_indexer_last_refine_stats(const vi_indexer *ix, vi_refine_stats *out) {
   if (!ix || !out) return fail(VI_ERR_INVALID_INPUT, "null pointer");
   *out = ix->impl.refine_stats;

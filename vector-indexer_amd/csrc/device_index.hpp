@@ -23,6 +23,7 @@
 
 #include "common.hpp"
 #include "context_pool.hpp"
+#include "rebalance_rules.hpp"
 #include "shards.hpp"
 
 namespace vi {
@@ -282,13 +283,43 @@ struct RefineResult {
   uint64_t iterations_run = 0, moved = 0, lists_emptied = 0, means_bytes = 0, rehome_bytes = 0;
   float ms_means = 0, ms_label = 0, ms_rehome = 0, ms_images = 0, ms_means_kernel = 0, ms_rehome_kernel = 0;
 };
+// The members of the lists of a resident index as a refine's kernels take them: list l's own records in their own order
+// (cur == nullptr; seg is not read), or the list-order ordinals cur[seg[l] .. seg[l + 1]) (refine_rules.hpp).
+struct ListMembers {
+  const float4 *blocks;
+  uint32_t dq, dim, nlists;
+  const uint32_t *first_block, *old_len;   // per list
+  const uint64_t *prefix;                  // per list: ordinal of its first record
+  const uint32_t *cur, *seg;
+};
+// The split step a rebalance adds to the first split_rounds iterations of a refine (include/vi_amd.h: vi_rebalance_rule),
+// and what it counts: the fields of vi_rebalance_stats, ms_kernels in HIP-event time, ms in wall time.
+struct SplitRule {
+  uint64_t split_rounds = 0;
+  double split_factor = 2.0;
+  uint64_t receiver_max_len = 0, max_splits = 0;
+  uint32_t split_iters = 4;
+};
+struct SplitStats {
+  uint64_t pairs_planned = 0, splits_done = 0, splits_skipped = 0, inner_iterations = 0, split_bytes = 0;
+  float ms = 0, ms_kernels = 0;
+};
 // `out` = a fresh index holding the records of `old` (unpartitioned, at least one record; only read) in the lists that
 // `iters` >= 1 iterations leave them in; table_host: old's coarse table, nlists x dim.  One iteration: every list with a
 // record gets the mean of its records as its centre (one sequential f32 chain per column in list order, then one divide;
 // an empty list keeps its centroid bits), every record the label of the first probe of the coarse step on the new table,
 // every list the records of its label in their previous order.  Stops early after an iteration that moved nothing and
 // changed no word of the table.  The old blocks are read until the end and never written; complete on return.
-vi_status device_index_refine(const DeviceIndex &old, const float *table_host, uint64_t iters, DeviceIndex *out, RefineResult *res);
+// rule (optional; with it, split: what the split steps counted): the first rule->split_rounds iterations carry the split
+// step of a rebalance between centres and labels.  Without it no launch and no byte differs from a plain refine.
+vi_status device_index_refine(const DeviceIndex &old, const float *table_host, uint64_t iters, DeviceIndex *out, RefineResult *res,
+                              const SplitRule *rule = nullptr, SplitStats *split = nullptr);
+//   device_split_lists       (list_split.hip)    the split step of vi_indexer_rebalance for the pairs of one iteration:
+//                                                table_host (nlists x dim, the centres of step 1) gets ca in the donor's
+//                                                row and cb in the receiver's row of every pair that was not skipped.
+//                                                len_host: the lengths the plan was made from.  Synchronises `st`.
+vi_status device_split_lists(const ListMembers &m, const std::vector<RebalancePair> &pairs, const uint64_t *len_host, uint32_t split_iters,
+                             float *table_host, hipStream_t st, SplitStats *stats);
 
 // ---- adaptive probing (probe_prune.hip, probe_rules.hpp): per-query probe counts between coarse step and list phase ----
 // A search's rule (vi_probe_rule) and where the number of probes each query kept goes.  The two arrays are host memory on

@@ -412,7 +412,8 @@ vi_status upsert_records(Indexer *ix, const uint64_t *ext_ids, const float *X, c
 
 // ---- refine: every list touched, the new resident index first (device_index_refine: it decides what the files hold),
 // then every shard file that holds a list, and index.bin behind them, written from it ----
-vi_status refine_records(Indexer *ix, uint64_t iters, uint64_t *moved_out) {
+// rule (a rebalance): the split steps of the first iterations, and the counts go to rebalance_stats instead
+vi_status refine_records(Indexer *ix, uint64_t iters, uint64_t *moved_out, const SplitRule *rule) {
   const double t0 = now_ms();
   const DeviceIndex &old = *ix->dev;
   const uint32_t dim = ix->cfg.dimension;
@@ -422,7 +423,8 @@ vi_status refine_records(Indexer *ix, uint64_t iters, uint64_t *moved_out) {
   VI_HIP(hipSetDevice(old.device));
   auto dev = std::make_unique<DeviceIndex>();
   RefineResult rr;
-  VI_TRY(device_index_refine(old, ix->meta.centroids.data(), iters, dev.get(), &rr));
+  SplitStats ss;
+  VI_TRY(device_index_refine(old, ix->meta.centroids.data(), iters, dev.get(), &rr, rule, rule ? &ss : nullptr));
   const double t1 = now_ms();
 
   // ---- files: every shard that holds a list, its lists in the order the file has them; then index.bin ----
@@ -463,7 +465,21 @@ vi_status refine_records(Indexer *ix, uint64_t iters, uint64_t *moved_out) {
   rs.ms_means = rr.ms_means; rs.ms_label = rr.ms_label; rs.ms_rehome = rr.ms_rehome; rs.ms_images = rr.ms_images;
   rs.ms_files = (float)(t2 - t1);
   rs.ms_means_kernel = rr.ms_means_kernel; rs.ms_rehome_kernel = rr.ms_rehome_kernel;
-  ix->refine_stats = rs;
+  if (rule) {
+    vi_rebalance_stats bs{};
+    bs.iterations_run = rs.iterations_run; bs.moved = rs.moved; bs.lists_emptied = rs.lists_emptied;
+    bs.shards_rewritten = rs.shards_rewritten; bs.bytes_written = rs.bytes_written;
+    bs.means_bytes = rs.means_bytes; bs.rehome_bytes = rs.rehome_bytes;
+    bs.ms_total = rs.ms_total; bs.ms_means = rs.ms_means; bs.ms_label = rs.ms_label; bs.ms_rehome = rs.ms_rehome;
+    bs.ms_images = rs.ms_images; bs.ms_files = rs.ms_files;
+    bs.ms_means_kernel = rs.ms_means_kernel; bs.ms_rehome_kernel = rs.ms_rehome_kernel;
+    bs.pairs_planned = ss.pairs_planned; bs.splits_done = ss.splits_done; bs.splits_skipped = ss.splits_skipped;
+    bs.inner_iterations = ss.inner_iterations; bs.split_bytes = ss.split_bytes;
+    bs.ms_split = ss.ms; bs.ms_split_kernels = ss.ms_kernels;
+    ix->rebalance_stats = bs;
+  } else {
+    ix->refine_stats = rs;
+  }
   if (moved_out) *moved_out = rr.moved;
   return VI_OK;
 }

@@ -18,6 +18,7 @@ struct Indexer {
   vi_remove_stats remove_stats{};       // ... and of the last vi_indexer_retain / vi_indexer_remove_ids that removed something
   vi_upsert_stats upsert_stats{};       // ... and of the last vi_indexer_upsert_records with n > 0
   vi_refine_stats refine_stats{};       // ... and of the last vi_indexer_refine with iters > 0
+  vi_rebalance_stats rebalance_stats{}; // ... and of the last vi_indexer_rebalance
 };
 
 // the resident index of this rank from the handle's files (a load; the build of a rank of a multi-GPU run)
@@ -33,6 +34,6 @@ vi_status add_records(Indexer *ix, const uint64_t *ext_ids, const float *X, cons
 vi_status retain_records(Indexer *ix, const SlotFilter &keep, uint64_t *removed_out);
 vi_status upsert_records(Indexer *ix, const uint64_t *ext_ids, const float *X, const uint64_t *timestamps, uint64_t n,
                          uint64_t *replaced_out);
-vi_status refine_records(Indexer *ix, uint64_t iters, uint64_t *moved_out);
+vi_status refine_records(Indexer *ix, uint64_t iters, uint64_t *moved_out, const SplitRule *rule = nullptr);
 
 }  // namespace vi

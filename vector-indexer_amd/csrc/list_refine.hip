@@ -12,6 +12,9 @@
 //            then one divide (refine_rules.hpp) — update_centroids_parallel's order (src/kmeans.rs:690-703).  A list
 //            without a member keeps its centroid bits (the reference writes zeros there; a zero centroid would attract
 //            records, so this is a deliberate deviation).
+//   split    only with a rule (vi_indexer_rebalance), in its first split_rounds iterations: the plan over the lengths the
+//            iteration starts with (rebalance_rules.hpp), the pairs' two-means over the old blocks (list_split.hip), the
+//            two centres of every split pair into C' — the table the labels are made against and the fixed-point test sees
 //   labels   a coarse-only index of the new table (device_index_from_rows, whose one list holds one row of the table, so
 //            that every launch of prepare_rank_images has work) and the walk over stored records (StoredRowsWalk):
 //            chunks of stored rows of the OLD index, in ordinal order, through that index's coarse step at n_probe 1 —
@@ -173,8 +176,11 @@ inline dim3 grid_1d(uint64_t n) { return dim3((uint32_t)((n + 255) / 256)); }
 
 }  // namespace
 
-vi_status device_index_refine(const DeviceIndex &old, const float *table_host, uint64_t iters, DeviceIndex *ix, RefineResult *res) {
+vi_status device_index_refine(const DeviceIndex &old, const float *table_host, uint64_t iters, DeviceIndex *ix, RefineResult *res,
+                              const SplitRule *rule, SplitStats *split) {
   *res = RefineResult{};
+  if (rule && !split) return fail(VI_ERR_OTHER, "refine: a split rule without a place for its counts");
+  if (split) *split = SplitStats{};
   const uint64_t nlists = old.nlists, n = old.nvec_resident;
   const uint32_t dim = old.dim, dq = old.dq;
   VI_TRY(refuse_update(old, "a partitioned index is not refined"));
@@ -226,9 +232,27 @@ vi_status device_index_refine(const DeviceIndex &old, const float *table_host, u
       // read: every record's values (and its ordinal on the gather path) and the old table; written: the new table
       res->means_bytes += n * (uint64_t)dim * 4 + (cur_p ? n * 4 : 0) + 2 * nlists * (uint64_t)dim * 4;
     }
-    const uint64_t changed = refine_changed_words((const uint32_t *)h_table.data(), (const uint32_t *)h_new.data(), nlists * dim);
-    const double t1 = now_ms();
+    uint64_t changed = refine_changed_words((const uint32_t *)h_table.data(), (const uint32_t *)h_new.data(), nlists * dim);
+    double t1 = now_ms();
     res->ms_means += (float)(t1 - t0);
+    if (rule && it < rule->split_rounds) {
+      // ---- split (a rebalance): the plan from the lengths this iteration starts with, the pairs' centres into C' ----
+      std::vector<uint64_t> len(nlists);
+      for (uint64_t l = 0; l < nlists; ++l) len[l] = cur_p ? seg_host[l + 1] - seg_host[l] : (uint64_t)lay.h_len[l];
+      const std::vector<RebalancePair> pairs = rebalance_plan(len.data(), nlists, rule->split_factor, rule->receiver_max_len, rule->max_splits);
+      if (!pairs.empty()) {
+        const ListMembers members{(const float4 *)old.lists.blocks.p, dq, dim, (uint32_t)nlists, old.list_first_block.p, old.list_len.p,
+                                  lay.prefix.p, cur_p, seg.p};
+        VI_TRY(device_split_lists(members, pairs, len.data(), rule->split_iters, h_new.data(), st, split));
+        // the table the labels are made against, and the one the fixed-point test sees
+        VI_HIP(hipMemcpyAsync(table[tc ^ 1].p, h_new.data(), nlists * dim * sizeof(float), hipMemcpyHostToDevice, st));
+        VI_HIP(hipStreamSynchronize(st));
+        changed = refine_changed_words((const uint32_t *)h_table.data(), (const uint32_t *)h_new.data(), nlists * dim);
+      }
+      const double ts = now_ms();
+      split->ms += (float)(ts - t1);
+      t1 = ts;
+    }
     // ---- labels: the coarse step of C' over every stored row, in ordinal order ----
     {
       DeviceIndex coarse;  // the table, and one list that holds its first row

@@ -13,6 +13,8 @@ bindings/python/python/vector_indexer_py/__init__.py):
     VectorIndex.remove_ids(ids) / .retain(filter) -> int    extension: remove records from it (by id / all a filter excludes)
     VectorIndex.upsert(xb, ext_ids, timestamps=None) -> int extension: replace the records that carry ext_ids, in one rewrite
     VectorIndex.refine(iters=1) -> int / .list_stats()      extension: recentre the lists and re-home the records / list balance
+    VectorIndex.rebalance(rule=None, **fields) -> int       extension: a refine whose first iterations split overfull lists
+                                                            into the empty ones (RebalanceRule)
     VectorIndex.get(ids) / .export(first, count)            extension: read records back, by id / a range in list order
     VectorIndex.filter_timestamps / _ids / _id_range / _mask / _compose(terms)   extension: filters for `filter=`; of two
                                                             filters a & b, a | b, a - b and ~a are filters too
@@ -35,7 +37,7 @@ import numpy as np
 from . import _native
 from ._native import (ViError, lib, VI_ASSIGN_EXACT, VI_ASSIGN_REFERENCE, VI_ORDER_LANES, VI_ORDER_SCALAR)
 
-__all__ = ["build", "load", "suggest_nlist", "VectorIndex", "ProbeRule", "TimestampFilter", "IdFilter", "FilterIntersection", "ComposedFilter", "Term", "AnyFilter", "RangeResult", "merge_range_results", "merge_range_results_device", "ViError", "kmeans_mini_batch", "kmeans_parallel",
+__all__ = ["build", "load", "suggest_nlist", "VectorIndex", "ProbeRule", "RebalanceRule", "TimestampFilter", "IdFilter", "FilterIntersection", "ComposedFilter", "Term", "AnyFilter", "RangeResult", "merge_range_results", "merge_range_results_device", "ViError", "kmeans_mini_batch", "kmeans_parallel",
            "assign", "l2sq_pairs", "VI_ASSIGN_EXACT", "VI_ASSIGN_REFERENCE", "VI_ORDER_LANES", "VI_ORDER_SCALAR"]
 
 
@@ -305,6 +307,28 @@ class ProbeRule:
         return r, keep
 
 
+class RebalanceRule:
+    """extension: the rule of VectorIndex.rebalance (vi_rebalance_rule): `iters` iterations of refine()'s contract, the
+    first `split_rounds` of which split overfull lists: a list longer than split_factor * (n / lists) gives one half of
+    its records (two-means from its two farthest members, at most split_iters inner iterations) to a list that holds at
+    most receiver_max_len records (0: empty lists only), longest donor to shortest receiver, at most max_splits pairs a
+    round (0: no cap).  split_rounds == 0: refine(iters) itself."""
+
+    __slots__ = ("iters", "split_rounds", "split_factor", "receiver_max_len", "max_splits", "split_iters")
+
+    def __init__(self, iters: int = 1, split_rounds: int = 1, split_factor: float = 2.0, receiver_max_len: int = 0,
+                 max_splits: int = 0, split_iters: int = 4):
+        self.iters, self.split_rounds, self.split_factor = int(iters), int(split_rounds), float(split_factor)
+        self.receiver_max_len, self.max_splits, self.split_iters = int(receiver_max_len), int(max_splits), int(split_iters)
+
+    def _native_rule(self):
+        r = _native.RebalanceRuleC()
+        lib().vi_rebalance_rule_init(C.byref(r))
+        for f in self.__slots__:
+            setattr(r, f, getattr(self, f))
+        return r
+
+
 class VectorIndex:
     """Index handle (PyVectorIndex + the async wrapper of the reference)."""
 
@@ -571,6 +595,29 @@ class VectorIndex:
         """counts and phases of the most recent refine() with iters > 0"""
         st = _native.RefineStats()
         _native.check(lib().vi_indexer_last_refine_stats(self._h, C.byref(st)))
+        return {f: getattr(st, f) for f, _ in st._fields_}
+
+    def rebalance(self, rule: Optional[RebalanceRule] = None, **fields) -> int:
+        """extension: refine() with a split step in its first iterations (RebalanceRule; `fields` are its fields, given
+        instead of a rule): an overfull list gives one half of its records to an empty one, which a warm-started refine
+        never does -> records whose list changed.  The number of lists, the list ids and the shard of every list stay.
+        Files, resident index, filters and overlap with searches: as refine()."""
+        if rule is None:
+            rule = RebalanceRule(**fields)
+        elif fields:
+            raise TypeError("give a rule or its fields, not both")
+        if not isinstance(rule, RebalanceRule):
+            raise TypeError("rule must be a RebalanceRule")
+        moved = C.c_uint64(0)
+        r = rule._native_rule()
+        _native.check(lib().vi_indexer_rebalance(self._h, C.byref(r), C.byref(moved)), prefix="Failed to rebalance the index: ")
+        return int(moved.value)
+
+    def rebalance_stats(self) -> dict:
+        """counts and phases of the most recent rebalance(): the fields of refine_stats(), then pairs_planned, splits_done,
+        splits_skipped, inner_iterations, split_bytes, ms_split and ms_split_kernels"""
+        st = _native.RebalanceStats()
+        _native.check(lib().vi_indexer_last_rebalance_stats(self._h, C.byref(st)))
         return {f: getattr(st, f) for f, _ in st._fields_}
 
     def list_stats(self) -> dict:

@@ -75,6 +75,19 @@ class RefineStats(C.Structure):
                 ("ms_rehome_kernel", f32)]
 
 
+class RebalanceRuleC(C.Structure):
+    """vi_rebalance_rule"""
+    _fields_ = [("iters", u64), ("split_rounds", u64), ("split_factor", C.c_double), ("receiver_max_len", u64),
+                ("max_splits", u64), ("split_iters", u32), ("reserved0", u32)]
+
+
+class RebalanceStats(C.Structure):
+    """vi_rebalance_stats: the fields of vi_refine_stats, then the split steps"""
+    _fields_ = RefineStats._fields_ + [("pairs_planned", u64), ("splits_done", u64), ("splits_skipped", u64),
+                                       ("inner_iterations", u64), ("split_bytes", u64), ("ms_split", f32),
+                                       ("ms_split_kernels", f32)]
+
+
 class ListStats(C.Structure):
     """vi_list_stats"""
     _fields_ = [("lists", u64), ("empty_lists", u64), ("min_len", u64), ("max_len", u64), ("mean_len", C.c_double),
@@ -200,6 +213,9 @@ SIGNATURES = {
     "vi_indexer_last_upsert_stats": (C.c_int, [vp, C.POINTER(UpsertStats)]),
     "vi_indexer_refine": (C.c_int, [vp, u64, C.POINTER(u64)]),
     "vi_indexer_last_refine_stats": (C.c_int, [vp, C.POINTER(RefineStats)]),
+    "vi_rebalance_rule_init": (None, [C.POINTER(RebalanceRuleC)]),
+    "vi_indexer_rebalance": (C.c_int, [vp, C.POINTER(RebalanceRuleC), C.POINTER(u64)]),
+    "vi_indexer_last_rebalance_stats": (C.c_int, [vp, C.POINTER(RebalanceStats)]),
     "vi_indexer_list_stats": (C.c_int, [vp, C.POINTER(ListStats)]),
     "vi_indexer_get_records": (C.c_int, [vp, vp, u64, vp, vp, vp, vp]),
     "vi_indexer_get_records_device": (C.c_int, [vp, vp, u64, vp, vp, vp, vp]),

@@ -11,6 +11,7 @@
     .remove_records(external_ids) -> int                                          extension: remove from a built index
     .upsert_records(records) -> int                                               extension: replace by external id
     .refine_lists(iters=1) -> int                                                 extension: recentre lists, re-home records
+    .rebalance_lists(rule=None, **fields) -> int                                  extension: ... and split overfull lists into empty ones
     .get_records(external_ids) -> [VectorRecord or None]                          extension: read back by external id
     .search_similar(external_id, k, n_probe, ...) -> [SearchResult] or None       extension: neighbours of a stored record
     .range_search_similar(external_id, radius2, ...) -> [SearchResult] or None    extension: ... within a radius of it
@@ -277,6 +278,20 @@ class VectorIndexer:
         if int(iters) > 0:
             self._drop_filters()  # (cached filters describe the index this call replaces)
         _native.check(lib().vi_indexer_refine(self._h, int(iters), C.byref(moved)))
+        return int(moved.value)
+
+    def rebalance_lists(self, rule=None, **fields) -> int:
+        """extension: refine_lists whose first iterations split overfull lists into the empty ones (a RebalanceRule of
+        vector_indexer_py, or its fields) -> records whose list changed"""
+        from . import RebalanceRule
+        if rule is None:
+            rule = RebalanceRule(**fields)
+        elif fields:
+            raise TypeError("give a rule or its fields, not both")
+        moved = C.c_uint64(0)
+        r = rule._native_rule()
+        self._drop_filters()  # (cached filters describe the index this call replaces)
+        _native.check(lib().vi_indexer_rebalance(self._h, C.byref(r), C.byref(moved)))
         return int(moved.value)
 
     def get_records(self, external_ids) -> List[Optional[VectorRecord]]:

@@ -193,6 +193,15 @@ class FaissStyleAdapter:
         """Faiss's invlists.imbalance_factor(): nlist * sum(len^2) / sum(len)^2 over the inverted lists, 1 = balanced"""
         return float(self._idx.list_stats()["imbalance"])
 
+    def rebalance(self, rule=None, **fields) -> dict:
+        """not Faiss's: VectorIndex.rebalance, reported the way a harness wants it -> {"moved", "imbalance_before",
+        "imbalance_after", "empty_before", "empty_after"}"""
+        before = self._idx.list_stats()
+        moved = self._idx.rebalance(rule, **fields)
+        after = self._idx.list_stats()
+        return {"moved": moved, "imbalance_before": float(before["imbalance"]), "imbalance_after": float(after["imbalance"]),
+                "empty_before": int(before["empty_lists"]), "empty_after": int(after["empty_lists"])}
+
     def reconstruct_batch(self, ids) -> np.ndarray:
         """Faiss's Index.reconstruct_batch: the stored vectors of ids, one row each; an id the index does not hold raises
         KeyError naming it"""
