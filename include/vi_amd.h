@@ -852,6 +852,64 @@ typedef struct vi_cluster_stats {
 } vi_cluster_stats;
 vi_status vi_cluster_last_stats(vi_cluster_stats *out);
 
+/* ---- extension: exact (flat) k-NN — the k nearest records of the whole index, one dense sweep on the matrix cores ------
+ * Every search entry above answers "the k nearest among the lists I probed".  This one answers "the k nearest records,
+ * full stop": for each query the k smallest keys (distance, ordinal) over EVERY resident record (with a filter: every
+ * record the filter admits).
+ *   distance: the reference's f32 squared L2 in scalar order (euclidean_distance_squared, VI_ORDER_SCALAR) — the bits
+ *             every search returns
+ *   ordinal:  the record's list-order ordinal, the row vi_indexer_export_records gives it
+ *   ties:     equal distances go to the LOWER ORDINAL.  This is a rule of this call's own: the tie order of a probed
+ *             search depends on shard visiting order and probe rank, which mean nothing without probing.  On data
+ *             without equal distances among a query's nearest k + 1, ids and distance bits equal those of
+ *             vi_indexer_search at n_probe = the number of lists.
+ * D is nq x k f32, I nq x k external ids, ord (optional) nq x k ordinals, counts (optional) nq result counts; rows with
+ * fewer than k admitted records are padded as a search pads them (+inf / -1; UINT64_MAX in ord).
+ *
+ * How: an ordinary search at opts->seed_probe gives every query a bound (the distance of its k-th hit); one kernel then
+ * multiplies the bf16 ranking images of ALL blocks with ALL queries on the matrix cores and keeps only the records whose
+ * rank value can lie under the bound (the margins of a search's selects); those are evaluated exactly, collected under
+ * the bound, sorted, cut at k.  No result depends on a rank value.  A query that cannot be bounded (fewer than k
+ * admitted hits in the seed, non-finite magnitude) or collects more than opts->cand_cap candidates (massive ties) is
+ * answered by sorting the exact key of every admitted record: slow and always right, so the call never fails on its data.
+ *   - opts (NULL: the defaults) never changes a result.  seed_probe: n_probe of the seeding search, 0 = 16, clamped to
+ *     max_n_probe.  cand_cap: candidates a query may collect, 0 = max(8 k, 1024); values below k are raised to k, values
+ *     above 8192 lowered to it.
+ *   - limits, all VI_ERR_INVALID_INPUT with a message and before any device work: k == 0 or k > 128 (k is NOT clamped to
+ *     max_k: the result is exact or an error); query_dim != dimension; a NULL queries, D or I with nq > 0; a handle
+ *     without an index; a partitioned handle (world_size > 1); a filter of another handle; an index whose distances are
+ *     not VI_ORDER_SCALAR, whose dimension is no multiple of 4 or exceeds 1536, which holds 2^26 slots or more, or whose
+ *     largest squared norm is not below 1e30 (the preconditions of the matrix-core engine).  Nothing falls to a slower path.
+ *   - a non-finite query value: VI_ERR_PANIC from the host entry, as vi_indexer_search; the device entry does not read the
+ *     queries on the host and answers such a query through the sort-everything path.
+ *   - nq == 0: VI_OK, nothing written.  An empty index: every row padded, counts 0.
+ *   - threads: the contract of a search — const on the handle, one search context held for the whole call, must not
+ *     overlap an update.  Ordinals refer to the list order at call time. */
+typedef struct vi_exact_opts {
+  uint64_t seed_probe;
+  uint64_t cand_cap;
+} vi_exact_opts;
+void vi_exact_opts_init(vi_exact_opts *opts);
+vi_status vi_indexer_search_exact(const vi_indexer *ix, const vi_filter *f, const vi_exact_opts *opts, const float *queries,
+                                  uint64_t nq, uint32_t query_dim, uint64_t k, float *D, int64_t *I, uint64_t *ord,
+                                  uint64_t *counts);
+vi_status vi_indexer_search_exact_device(const vi_indexer *ix, const vi_filter *f, const vi_exact_opts *opts,
+                                         const float *queries_dev, uint64_t nq, uint64_t k, float *D_dev, int64_t *I_dev,
+                                         uint64_t *ord_dev, uint64_t *counts_dev);
+/* Of the calling thread's last vi_indexer_search_exact (either form); zeros after a failed one.  seed_probe / cand_cap:
+ * the values used.  query_tile x block_splits: the sweep's grid (queries per workgroup; workgroups sharing the blocks).
+ * survivors: (query, record) pairs the sweep evaluated exactly; candidates: those it kept under the bound;
+ * overflow_rows: queries answered by the sort-everything path.  The ms_* are taken only while the environment variable
+ * VI_EXACT_TIMING is set (and not "0"), which adds a synchronisation per phase: host clock around the seeding search,
+ * the sweep (bounds, query images and flat_sweep_kernel) and the finish (sort, ids, overflow rows, copies). */
+typedef struct vi_exact_stats {
+  uint64_t nq, k, seed_probe, cand_cap;
+  uint64_t query_tile, block_splits;
+  uint64_t survivors, candidates, overflow_rows;
+  float ms_seed, ms_sweep, ms_finish, ms_total;
+} vi_exact_stats;
+vi_status vi_exact_last_stats(vi_exact_stats *out);
+
 /* ---- extension: adaptive probing — per-query probe counts by distance ratio, code budget or list ---------------------
  * Every search entry above takes one n_probe for the whole batch.  Here n_probe is the UPPER bound and a rule decides,
  * per query, how many of its probes are searched: a prefix of its probe row.  For a row with `found` real probes in

@@ -10,6 +10,7 @@
 #include <string>
 
 #include "device_index.hpp"
+#include "flat_search.hpp"
 #include "index_lifecycle.hpp"
 #include "kmeans.hpp"
 #include "probe_rules.hpp"
@@ -1133,6 +1134,62 @@ vi_status vi_cluster_last_stats(vi_cluster_stats *out) {
   return vi::guarded([&]() -> vi_status {
   if (!out) return fail(VI_ERR_INVALID_INPUT, "null pointer");
   *out = vi::cluster_last_stats();
+  return VI_OK;
+  });
+}
+
+// ---- exact (flat) k-NN over every resident record (flat_search.hip) ----
+void vi_exact_opts_init(vi_exact_opts *opts) {
+  if (opts) *opts = vi_exact_opts{0, 0};
+}
+
+static vi_status search_exact_common(const vi_indexer *ix, const vi_filter *f, const vi_exact_opts *opts, const float *queries,
+                                     uint64_t nq, const uint32_t *query_dim, uint64_t k, bool on_device, float *D, int64_t *I,
+                                     uint64_t *ord, uint64_t *counts) {
+  return vi::guarded([&]() -> vi_status {
+  if (!ix) return fail(VI_ERR_INVALID_INPUT, "null indexer");
+  if (k == 0 || k > vi::kExactMaxK)  // (not clamped to max_k: the answer is exact or an error)
+    return fail(VI_ERR_INVALID_INPUT, "k must be in 1..%llu for an exact search, not %llu", (unsigned long long)vi::kExactMaxK,
+                (unsigned long long)k);
+  if (query_dim && *query_dim != ix->impl.cfg.dimension)
+    return fail(VI_ERR_INVALID_INPUT, "query dimension mismatch: expected %u, got %u", ix->impl.cfg.dimension, *query_dim);
+  if (nq && (!queries || !D || !I)) return fail(VI_ERR_INVALID_INPUT, "null pointer: queries, D and I are required");
+  if (!ix->impl.dev) return fail(VI_ERR_INVALID_INPUT, "the indexer holds no index (build or load it first)");
+  if (ix->impl.cfg.world_size > 1 || ix->impl.dev->stripe_world > 1)
+    return fail(VI_ERR_INVALID_INPUT, "exact search needs the whole index on one handle: a partitioned handle (world_size > 1) "
+                                      "holds only its part of the records");
+  const vi::SlotFilter *flt = nullptr;
+  VI_TRY(filter_common(ix, f, &flt));
+  if (nq == 0) return VI_OK;
+  if (!on_device)  // NaN/Inf in a query makes partial_cmp().unwrap() panic in the reference (ivf_index.rs:215)
+    for (uint64_t i = 0; i < nq * (uint64_t)ix->impl.cfg.dimension; ++i)
+      if (!std::isfinite(queries[i])) return fail(VI_ERR_PANIC, "non-finite query value at flat index %llu", (unsigned long long)i);
+  vi::ExactIO io;
+  io.queries = queries; io.on_device = on_device; io.nq = nq; io.k = k; io.filter = flt;
+  uint64_t one = 1, seed = opts ? opts->seed_probe : 0;
+  if (seed) VI_TRY(search_common(ix, &one, &seed));  // (the clamp to max_n_probe)
+  io.seed_probe = seed; io.cand_cap = opts ? opts->cand_cap : 0;
+  io.D = D; io.I = I; io.ord = ord; io.counts = counts;
+  return vi::device_index_search_exact(*ix->impl.dev, io);
+  });
+}
+
+vi_status vi_indexer_search_exact(const vi_indexer *ix, const vi_filter *f, const vi_exact_opts *opts, const float *queries,
+                                  uint64_t nq, uint32_t query_dim, uint64_t k, float *D, int64_t *I, uint64_t *ord,
+                                  uint64_t *counts) {
+  return search_exact_common(ix, f, opts, queries, nq, &query_dim, k, false, D, I, ord, counts);
+}
+
+vi_status vi_indexer_search_exact_device(const vi_indexer *ix, const vi_filter *f, const vi_exact_opts *opts,
+                                         const float *queries_dev, uint64_t nq, uint64_t k, float *D_dev, int64_t *I_dev,
+                                         uint64_t *ord_dev, uint64_t *counts_dev) {
+  return search_exact_common(ix, f, opts, queries_dev, nq, nullptr, k, true, D_dev, I_dev, ord_dev, counts_dev);
+}
+
+vi_status vi_exact_last_stats(vi_exact_stats *out) {
+  return vi::guarded([&]() -> vi_status {
+  if (!out) return fail(VI_ERR_INVALID_INPUT, "null pointer");
+  *out = vi::exact_last_stats();
   return VI_OK;
   });
 }

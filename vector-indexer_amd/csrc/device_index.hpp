@@ -127,6 +127,16 @@ struct SearchWorkspace {
   // of each row's own entry
   RangeResult sim_range;
   DevBuf<uint32_t> sim_len;
+  // exact search (flat_search.hip): the seeding search's rows; per query its rank threshold, bound key, candidate count
+  // and overflow flag; the candidates [nq][cap]; the batch's image; per block the ordinal of its first record and its
+  // records; the overflow rows and their keys; a host caller's outputs; the sweep's counters
+  struct FlatBuffers {
+    DevBuf<float> seed_D, thr, D;
+    DevBuf<int64_t> seed_I, I;
+    DevBuf<uint64_t> bound, cand, keys, ord, counts;
+    DevBuf<uint32_t> cnt, ovf, qimg, block_ord, block_cnt, rows;
+    DevBuf<unsigned long long> counters;
+  } flat;
 };
 
 // ---- reading records back (record_fetch.hip) ----

@@ -818,6 +818,56 @@ class VectorIndex:
         _native.check(lib().vi_cluster_last_stats(C.byref(st)))
         return {f: getattr(st, f) for f, _ in st._fields_}
 
+    @staticmethod
+    def _exact_opts(opts):
+        """None, a dict or keyword-like mapping with seed_probe / cand_cap -> vi_exact_opts (or None: the defaults)"""
+        if opts is None:
+            return None
+        unknown = set(opts) - {"seed_probe", "cand_cap"}
+        if unknown:
+            raise TypeError(f"unknown exact-search options: {sorted(unknown)}")
+        o = _native.ExactOpts()
+        lib().vi_exact_opts_init(C.byref(o))
+        o.seed_probe, o.cand_cap = int(opts.get("seed_probe", 0)), int(opts.get("cand_cap", 0))
+        return C.byref(o)
+
+    def search_exact_sync(self, xq, k: int, filter: Optional[AnyFilter] = None, opts=None, with_ordinals: bool = False):
+        """extension: the k nearest records of the WHOLE index (of the records `filter` admits), one dense sweep on the
+        matrix cores -> (D f32[nq, k], I i64[nq, k][, ord u64[nq, k]]): the reference's distance bits, ties to the lower
+        list-order ordinal (the row export() gives the record), +inf / -1 / 2^64-1 padding.  k in 1..128.  opts: a dict
+        with seed_probe and / or cand_cap, which never change a result.  Unpartitioned handles only."""
+        xq = np.asarray(xq)
+        if xq.ndim != 2:
+            raise RuntimeError("Query array must be 2-dimensional")
+        if xq.shape[1] != self._dimension:
+            raise RuntimeError(f"Query dimension {xq.shape[1]} doesn't match index dimension {self._dimension}")
+        xq = np.ascontiguousarray(xq, dtype=np.float32)
+        nq, k = xq.shape[0], int(k)
+        D = np.full((nq, max(k, 0)), np.inf, dtype=np.float32)
+        I = np.full((nq, max(k, 0)), -1, dtype=np.int64)
+        ord_ = np.full((nq, max(k, 0)), (1 << 64) - 1, dtype=np.uint64) if with_ordinals else None
+        _native.check(lib().vi_indexer_search_exact(self._h, _filter_handle(filter), self._exact_opts(opts), _native.ptr(xq), nq,
+                                                    xq.shape[1], k, _native.ptr(D), _native.ptr(I), _native.ptr(ord_), None),
+                      prefix="Failed to search exactly: ")
+        return (D, I, ord_) if with_ordinals else (D, I)
+
+    def search_exact_device(self, xq_ptr: int, nq: int, k: int, D_ptr: int, I_ptr: int, ord_ptr: int = 0, counts_ptr: int = 0,
+                            filter: Optional[AnyFilter] = None, opts=None):
+        """... for nq queries in device memory, into device memory: D f32[nq, k], I i64[nq, k], optionally ord u64[nq, k]
+        and counts u64[nq] (a pointer of 0 skips that output)"""
+        _native.check(lib().vi_indexer_search_exact_device(self._h, _filter_handle(filter), self._exact_opts(opts), C.c_void_p(xq_ptr),
+                                                           int(nq), int(k), C.c_void_p(D_ptr), C.c_void_p(I_ptr),
+                                                           C.c_void_p(ord_ptr) if ord_ptr else None,
+                                                           C.c_void_p(counts_ptr) if counts_ptr else None),
+                      prefix="Failed to search exactly: ")
+
+    def exact_stats(self) -> dict:
+        """this thread's last search_exact_sync / search_exact_device: the options used, the sweep's grid, survivors
+        (pairs evaluated exactly), candidates (kept under the bound), overflow_rows; the ms_* only under VI_EXACT_TIMING"""
+        st = _native.ExactStats()
+        _native.check(lib().vi_exact_last_stats(C.byref(st)))
+        return {f: getattr(st, f) for f, _ in st._fields_}
+
     def similar_times(self) -> dict:
         """this thread's last search_by_ids / knn_graph / range_search_by_ids / radius_graph (any form) under
         VI_SIMILAR_TIMING: host ms around the gather of the queries and the search, HIP-event ms and bytes of the drop

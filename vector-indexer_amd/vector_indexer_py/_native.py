@@ -106,6 +106,18 @@ class ClusterStats(C.Structure):
                 ("ms_link", f32), ("ms_label", f32)]
 
 
+class ExactOpts(C.Structure):
+    """vi_exact_opts"""
+    _fields_ = [("seed_probe", u64), ("cand_cap", u64)]
+
+
+class ExactStats(C.Structure):
+    """vi_exact_stats"""
+    _fields_ = [("nq", u64), ("k", u64), ("seed_probe", u64), ("cand_cap", u64), ("query_tile", u64), ("block_splits", u64),
+                ("survivors", u64), ("candidates", u64), ("overflow_rows", u64), ("ms_seed", f32), ("ms_sweep", f32),
+                ("ms_finish", f32), ("ms_total", f32)]
+
+
 class ProbeRuleC(C.Structure):
     """vi_probe_rule"""
     _fields_ = [("min_probe", u32), ("ratio2", f32), ("max_codes", u64), ("n_probe_q", vp)]
@@ -238,6 +250,10 @@ SIGNATURES = {
                                              C.POINTER(u64)]),
     "vi_indexer_search_adaptive_device": (C.c_int, [vp, vp, C.POINTER(ProbeRuleC), vp, u64, u64, u64, vp, vp, vp, vp]),
     "vi_prune_last_stats": (C.c_int, [C.POINTER(u64), C.POINTER(u64), C.POINTER(f32)]),
+    "vi_exact_opts_init": (None, [C.POINTER(ExactOpts)]),
+    "vi_indexer_search_exact": (C.c_int, [vp, vp, C.POINTER(ExactOpts), vp, u64, u32, u64, vp, vp, vp, vp]),
+    "vi_indexer_search_exact_device": (C.c_int, [vp, vp, C.POINTER(ExactOpts), vp, u64, u64, vp, vp, vp, vp]),
+    "vi_exact_last_stats": (C.c_int, [C.POINTER(ExactStats)]),
 }
 
 _lib = None

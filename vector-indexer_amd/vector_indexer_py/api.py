@@ -16,6 +16,8 @@
     .search_similar(external_id, k, n_probe, ...) -> [SearchResult] or None       extension: neighbours of a stored record
     .range_search_similar(external_id, radius2, ...) -> [SearchResult] or None    extension: ... within a radius of it
     .duplicate_groups(radius2=0.0, n_probe, min_size=2) -> [[external_id]]        extension: groups of (near-)copies
+    .search_exact(req) -> [SearchResult]                                          extension: the k nearest of the whole index
+    .recall_of(queries, k, n_probe, ...) -> (recall_1nn, recall_intersection)     extension: recall against search_exact
     SearchRequest.with_timestamp_range / .with_allowed_ids / .with_excluded_ids   extension: filtered search
     SearchRequest.with_probe_ratio(ratio2, min_probe=1) / .with_max_codes(n)      extension: adaptive probing
 
@@ -133,6 +135,17 @@ class SearchResult:
     external_id: int
     distance: float
     vector: Optional[List[float]] = field(default=None)
+
+
+def recalls(I: np.ndarray, exact: np.ndarray) -> Tuple[float, float]:
+    """(1-NN-in-top-k recall, intersection recall) of result ids I against the exact ids, both nq x k; -1 is padding"""
+    if I.shape[0] == 0:
+        return 1.0, 1.0
+    real = exact >= 0
+    r1 = float(((I == exact[:, :1]) & real[:, :1]).any(axis=1).mean())
+    hit = ((I[:, :, None] == exact[:, None, :]) & real[:, None, :]).any(axis=2).sum(axis=1)
+    inter = float((hit / np.maximum(real.sum(axis=1), 1)).mean())
+    return r1, inter
 
 
 class VectorIndexer:
@@ -423,6 +436,44 @@ class VectorIndexer:
         order = np.argsort(labels, kind="stable")          # by representative, list order inside a group
         reps, start, size = np.unique(labels[order], return_index=True, return_counts=True)
         return [[int(e) for e in ids[order[s:s + c]]] for r, s, c in zip(reps, start, size) if r >= 0 and c >= max(int(min_size), 1)]
+
+    def search_exact(self, req: SearchRequest) -> List[SearchResult]:
+        """extension: the k nearest records of the WHOLE index to req.query (of the records req's filters admit), nearest
+        first, equal distances by list order; req.n_probe and the adaptive fields are not read.  k in 1..128."""
+        q = np.ascontiguousarray(np.asarray(req.query, dtype=np.float32).reshape(1, -1))
+        k = int(req.k)
+        D = np.full((1, max(k, 1)), np.inf, dtype=np.float32)
+        I = np.full((1, max(k, 1)), -1, dtype=np.int64)
+        cnt = np.zeros(1, dtype=np.uint64)
+        _native.check(lib().vi_indexer_search_exact(self._h, self._filter(req.timestamp_range, req.id_selector), None, _native.ptr(q),
+                                                    1, q.shape[1], k, _native.ptr(D), _native.ptr(I), None, _native.ptr(cnt)))
+        V = None
+        if req.include_vectors and cnt[0]:
+            V = {r.external_id: r.values for r in self.get_records(I[0, :int(cnt[0])]) if r is not None}
+        return [SearchResult(int(I[0, j]), float(D[0, j]), V.get(int(I[0, j])) if V is not None else None)
+                for j in range(int(cnt[0]))]
+
+    def recall_of(self, queries, k: int, n_probe: Optional[int] = None, rule=None, filter=None) -> Tuple[float, float]:
+        """extension: what a search at n_probe (None: the config's default; with `rule`, a ProbeRule of vector_indexer_py:
+        adaptive probing) recalls on these queries, measured against search_exact with the same filter (a native filter
+        handle as _filter returns, or None) -> (share of queries whose exact nearest neighbour is among their k results,
+        mean share of the exact k found): the two figures the benchmark reports"""
+        Q = np.ascontiguousarray(np.asarray(queries, dtype=np.float32).reshape(-1, self._cfg.dimension))
+        nq, k = Q.shape[0], int(k)
+        p = self._cfg.default_n_probe if n_probe is None else int(n_probe)
+        D, I = np.full((nq, k), np.inf, dtype=np.float32), np.full((nq, k), -1, dtype=np.int64)
+        Dx, Ix = D.copy(), I.copy()
+        kout = C.c_uint64(0)
+        if rule is not None:
+            r, _keep = rule._native_rule(nq, False)
+            _native.check(lib().vi_indexer_search_adaptive(self._h, filter, C.byref(r), _native.ptr(Q), nq, Q.shape[1], k, p,
+                                                           _native.ptr(D), _native.ptr(I), None, None, None, C.byref(kout)))
+        else:
+            _native.check(lib().vi_indexer_search_filtered(self._h, filter, _native.ptr(Q), nq, Q.shape[1], k, p, _native.ptr(D),
+                                                           _native.ptr(I), None, None, C.byref(kout)))
+        _native.check(lib().vi_indexer_search_exact(self._h, filter, None, _native.ptr(Q), nq, Q.shape[1], k, _native.ptr(Dx),
+                                                    _native.ptr(Ix), None, None))
+        return recalls(I, Ix)
 
     def search_request(self, query) -> SearchRequest:
         return SearchRequest(list(query), False, self._cfg.default_k, self._cfg.default_n_probe)
