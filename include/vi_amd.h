@@ -910,6 +910,63 @@ typedef struct vi_exact_stats {
 } vi_exact_stats;
 vi_status vi_exact_last_stats(vi_exact_stats *out);
 
+/* ---- extension: exact (flat) radius search — every record of the whole index within a distance, one dense sweep to CSR --
+ * The radius entries above answer "within radius2 among the lists I probed".  This one answers "within radius2, full
+ * stop": per query EVERY resident record (with a filter: every record the filter admits) whose distance d <= radius2.
+ *   distance: the reference's f32 squared L2 in scalar order, the bits every search returns; the comparison is an f32
+ *             compare, so d == radius2 is inside
+ *   order:    rows are sorted by (distance bits, list-order ordinal): the rule of vi_indexer_search_exact
+ *   result:   an ordinary vi_range_result of the index — vi_range_result_total / _copy (V included) / _device /
+ *             _copy_device / _free work on it unchanged.  tie carries the record's list-order ordinal, the row
+ *             vi_indexer_export_records gives it — NOT a probed search's tie key, so these results are not meant for
+ *             vi_range_merge_device.
+ *   radius2:  negative: VI_OK, nq empty rows, no sweep; NaN: VI_ERR_INVALID_INPUT; +inf: every admitted record
+ *   opts (NULL: the defaults):
+ *     radii    optional, nq floats — host memory for the host entry, device memory for the device entry.  When set, query
+ *              q uses radii[q] and the scalar radius2 is ignored (it may be anything).  A NaN or negative entry gives
+ *              that query an empty row; a device array is not read back to validate it.
+ *     pool_cap capacity, in hits, of the pool the sweep appends to; 0 = max(2^22, 256 per query).  It never changes a result: a sweep
+ *              that finds more hits than the pool holds counts them all, the pool grows to the count and the sweep
+ *              runs once more.
+ * How: one wave per query forms the rank threshold of the radius in the query's frame (the radius select's own formula)
+ * and the query's bf16 image; one kernel multiplies the bf16 ranking images of ALL blocks with ALL queries on the matrix
+ * cores, evaluates every record whose rank value can lie under the threshold in the reference's chain and appends those
+ * with d <= radius2 to a pool; the pool is scattered into CSR rows, every row sorted, ids and slots resolved.  No result
+ * depends on a rank value, on the order hits arrive in or on the second sweep.  A query whose magnitude the rank
+ * arithmetic cannot be trusted with, or a radius of 1e37 or more, evaluates every admitted record.
+ *   - limits, all VI_ERR_INVALID_INPUT with a message and before any device work: those of vi_indexer_search_exact — a
+ *     handle without an index, a partitioned handle (world_size > 1), a filter of another handle, query_dim != dimension,
+ *     a NULL queries with nq > 0, a NULL out, an index whose distances are not VI_ORDER_SCALAR, whose dimension is no
+ *     multiple of 4 or exceeds 1536, which holds 2^26 slots or more, or whose largest squared norm is not below 1e30.
+ *     Nothing falls to a slower path.
+ *   - a non-finite query value: VI_ERR_PANIC from the host entry, as vi_indexer_search
+ *   - nq == 0: VI_OK, a result of no rows.  An empty index: nq empty rows.
+ *   - all or nothing: when scratch or result memory cannot be had the call fails with VI_ERR_DEVICE and *out stays NULL
+ *   - queries are processed in chunks of 65536; threads: the contract of a search — const on the handle, one search
+ *     context held for the whole call, must not overlap an update.  Ordinals refer to the list order at call time. */
+typedef struct vi_exact_range_opts {
+  const float *radii;
+  uint64_t pool_cap;
+} vi_exact_range_opts;
+void vi_exact_range_opts_init(vi_exact_range_opts *opts);
+vi_status vi_indexer_range_search_exact(const vi_indexer *ix, const vi_filter *f, const vi_exact_range_opts *opts,
+                                        const float *queries, uint64_t nq, uint32_t query_dim, float radius2,
+                                        vi_range_result **out);
+vi_status vi_indexer_range_search_exact_device(const vi_indexer *ix, const vi_filter *f, const vi_exact_range_opts *opts,
+                                               const float *queries_dev, uint64_t nq, float radius2, vi_range_result **out);
+/* Of the calling thread's last vi_indexer_range_search_exact (either form); zeros after a failed one.  query_tile x
+ * block_splits: the sweep's grid; chunks: query chunks processed.  survivors: (query, record) pairs evaluated exactly,
+ * all sweeps; hits: entries of the result; sweeps: the most sweeps a chunk ran — 0 (nothing to sweep), 1 or 2;
+ * pool_cap: the largest pool used, in hits.  The ms_* are taken only while the environment variable VI_EXACT_TIMING is
+ * set (and not "0"), which adds a synchronisation per phase: host clock around thresholds + images, the sweep(s), the
+ * sizing + scatter into rows, the sort and the output kernel, summed over the chunks. */
+typedef struct vi_exact_range_stats {
+  uint64_t nq, query_tile, block_splits, chunks;
+  uint64_t survivors, hits, sweeps, pool_cap;
+  float ms_prepare, ms_sweep, ms_place, ms_sort, ms_output, ms_total;
+} vi_exact_range_stats;
+vi_status vi_exact_range_last_stats(vi_exact_range_stats *out);
+
 /* ---- extension: adaptive probing — per-query probe counts by distance ratio, code budget or list ---------------------
  * Every search entry above takes one n_probe for the whole batch.  Here n_probe is the UPPER bound and a rule decides,
  * per query, how many of its probes are searched: a prefix of its probe row.  For a row with `found` real probes in

@@ -10,6 +10,7 @@
 #include <string>
 
 #include "device_index.hpp"
+#include "flat_range.hpp"
 #include "flat_search.hpp"
 #include "index_lifecycle.hpp"
 #include "kmeans.hpp"
@@ -1190,6 +1191,56 @@ vi_status vi_exact_last_stats(vi_exact_stats *out) {
   return vi::guarded([&]() -> vi_status {
   if (!out) return fail(VI_ERR_INVALID_INPUT, "null pointer");
   *out = vi::exact_last_stats();
+  return VI_OK;
+  });
+}
+
+// ---- exact (flat) radius search over every resident record (flat_range.hip) ----
+void vi_exact_range_opts_init(vi_exact_range_opts *opts) {
+  if (opts) *opts = vi_exact_range_opts{nullptr, 0};
+}
+
+static vi_status range_exact_common(const vi_indexer *ix, const vi_filter *f, const vi_exact_range_opts *opts, const float *queries,
+                                    uint64_t nq, const uint32_t *query_dim, float radius2, bool on_device, vi_range_result **out) {
+  return vi::guarded([&]() -> vi_status {
+  if (!out) return fail(VI_ERR_INVALID_INPUT, "null pointer: out is required");
+  *out = nullptr;
+  if (!ix) return fail(VI_ERR_INVALID_INPUT, "null indexer");
+  const float *radii = opts ? opts->radii : nullptr;
+  if (!radii && std::isnan(radius2)) return fail(VI_ERR_INVALID_INPUT, "radius2 is NaN");
+  if (query_dim && *query_dim != ix->impl.cfg.dimension)
+    return fail(VI_ERR_INVALID_INPUT, "query dimension mismatch: expected %u, got %u", ix->impl.cfg.dimension, *query_dim);
+  if (nq && !queries) return fail(VI_ERR_INVALID_INPUT, "null pointer: queries are required");
+  if (!ix->impl.dev) return fail(VI_ERR_INVALID_INPUT, "the indexer holds no index (build or load it first)");
+  if (ix->impl.cfg.world_size > 1 || ix->impl.dev->stripe_world > 1)
+    return fail(VI_ERR_INVALID_INPUT, "exact radius search needs the whole index on one handle: a partitioned handle (world_size > 1) "
+                                      "holds only its part of the records");
+  const vi::SlotFilter *flt = nullptr;
+  VI_TRY(filter_common(ix, f, &flt));
+  if (!on_device)  // NaN/Inf in a query makes partial_cmp().unwrap() panic in the reference (ivf_index.rs:215)
+    for (uint64_t i = 0; i < nq * (uint64_t)ix->impl.cfg.dimension; ++i)
+      if (!std::isfinite(queries[i])) return fail(VI_ERR_PANIC, "non-finite query value at flat index %llu", (unsigned long long)i);
+  vi::ExactRangeIO io;
+  io.queries = queries; io.on_device = on_device; io.nq = nq; io.radius2 = radius2; io.radii = radii;
+  io.pool_cap = opts ? opts->pool_cap : 0; io.filter = flt;
+  return range_run(out, [&](vi::RangeResult *r) { return vi::device_index_range_exact(*ix->impl.dev, io, r); });
+  });
+}
+
+vi_status vi_indexer_range_search_exact(const vi_indexer *ix, const vi_filter *f, const vi_exact_range_opts *opts, const float *queries,
+                                        uint64_t nq, uint32_t query_dim, float radius2, vi_range_result **out) {
+  return range_exact_common(ix, f, opts, queries, nq, &query_dim, radius2, false, out);
+}
+
+vi_status vi_indexer_range_search_exact_device(const vi_indexer *ix, const vi_filter *f, const vi_exact_range_opts *opts,
+                                               const float *queries_dev, uint64_t nq, float radius2, vi_range_result **out) {
+  return range_exact_common(ix, f, opts, queries_dev, nq, nullptr, radius2, true, out);
+}
+
+vi_status vi_exact_range_last_stats(vi_exact_range_stats *out) {
+  return vi::guarded([&]() -> vi_status {
+  if (!out) return fail(VI_ERR_INVALID_INPUT, "null pointer");
+  *out = vi::exact_range_last_stats();
   return VI_OK;
   });
 }

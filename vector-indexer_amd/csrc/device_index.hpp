@@ -137,6 +137,16 @@ struct SearchWorkspace {
     DevBuf<uint32_t> cnt, ovf, qimg, block_ord, block_cnt, rows;
     DevBuf<unsigned long long> counters;
   } flat;
+  // exact radius search (flat_range.hip), per chunk of queries: rank threshold, radius, hit count and row cursor of every
+  // query; the chunk's image; a host caller's radii; per block the ordinal of its first record and its records; the hit
+  // pool (key, query); the rows before and after their sort; the queries whose rows are too long for the LDS sort and
+  // the padded scratch those are sorted on; the cursor and the survivor count
+  struct FlatRangeBuffers {
+    DevBuf<float> thr, rad, radii;
+    DevBuf<uint32_t> cnt, fill, qimg, block_ord, block_cnt, pool_q, longq;
+    DevBuf<uint64_t> pool_key, rows, pad;
+    DevBuf<unsigned long long> counters;
+  } flat_range;
 };
 
 // ---- reading records back (record_fetch.hip) ----

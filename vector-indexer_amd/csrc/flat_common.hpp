@@ -1,0 +1,71 @@
+// flat_common.hpp — the device pieces the two flat (exact, whole-index) calls share: flat_search.hip (k-NN)
+// and flat_range.hip (radius).  Each translation unit compiles its own copy (unnamed namespace): the reference
+// chain of one pair, the bf16 image of one query, the per-block ordinals and the way back from an ordinal to its block.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "device_math.hpp"
+#include "list_layout.hpp"
+#include "mfma_bf16.hpp"
+#include "select_device.hpp"
+
+namespace vi {
+namespace {
+
+// the reference's sum (src/utils.rs:28-30) of one (query row, stored vector) pair: one sequential f32 chain, no fused
+// multiply-add (the file is compiled with -ffp-contract=off), written without packed instructions
+__device__ __forceinline__ float exact_scalar(const float *qrow, const float4 *xv, uint32_t dim) {
+  float acc = 0.0f;
+  for (uint32_t qd = 0; qd < (dim >> 2); ++qd) {
+    const float4 x = xv[(size_t)qd * kWave];
+    const float4 q = *reinterpret_cast<const float4 *>(qrow + 4 * qd);
+    sq_add(acc, q.x, x.x); sq_add(acc, q.y, x.y); sq_add(acc, q.z, x.z); sq_add(acc, q.w, x.w);
+  }
+  return acc;
+}
+
+// ---- per block: the list-order ordinal of its first record and the records it holds (1..64) ----
+__global__ void flat_blocks_kernel(const uint32_t *first_block, const uint32_t *list_len, const uint64_t *prefix, uint32_t nlists,
+                                   uint32_t nblocks, uint32_t *block_ord, uint32_t *block_cnt) {
+  const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= nblocks) return;
+  const uint32_t l = list_of_block(first_block, nlists, b);
+  const uint32_t pos0 = (b - first_block[l]) * 64u, len = list_len[l];
+  block_ord[b] = (uint32_t)prefix[l] + pos0;
+  block_cnt[b] = len > pos0 ? min(64u, len - pos0) : 0u;
+}
+
+// one wave: query q of the frame c -> its bf16 image of nc chunks,
+// qimg[query][plane hi / lo][chunk][half] x 16 B of -2 (q - mu): the layout every rank kernel reads
+__device__ __forceinline__ void split_query_image(const SelectCommon &c, uint32_t q, uint32_t nc, int lane, uint4 *qimg) {
+  const float *row = c.Q + (size_t)q * c.dim;
+  for (uint32_t p = lane; p < 2u * nc; p += kWave) {  // piece (chunk ch, half h): dimensions 16 ch + 8 h ..
+    const uint32_t ch = p >> 1, h = p & 1u, e = 16u * ch + 8u * h;
+    float4 v0 = make_float4(0.f, 0.f, 0.f, 0.f), v1 = v0;
+    if (e < c.dim) v0 = *reinterpret_cast<const float4 *>(row + e);  // dim % 4 == 0
+    if (e + 4 < c.dim) v1 = *reinterpret_cast<const float4 *>(row + e + 4);
+    if (c.mu) {
+      if (e < c.dim) { const float4 m = *reinterpret_cast<const float4 *>(c.mu + e); v0.x -= m.x; v0.y -= m.y; v0.z -= m.z; v0.w -= m.w; }
+      if (e + 4 < c.dim) { const float4 m = *reinterpret_cast<const float4 *>(c.mu + e + 4); v1.x -= m.x; v1.y -= m.y; v1.z -= m.z; v1.w -= m.w; }
+    }
+    uint4 hi, lo;
+    split8(v0, v1, -2.0f, hi, lo);
+    qimg[(size_t)q * 4 * nc + 2 * ch + h] = hi;
+    qimg[(size_t)q * 4 * nc + 2 * nc + 2 * ch + h] = lo;
+  }
+}
+
+// the block of a list-order ordinal: block_ord[b] <= ordinal < block_ord[b + 1] (every block holds a record)
+__device__ __forceinline__ uint32_t block_of_ordinal(const uint32_t *block_ord, uint32_t nblocks, uint32_t ordinal) {
+  uint32_t lo = 0, hi = nblocks;
+  while (hi - lo > 1) {
+    const uint32_t mid = lo + (hi - lo) / 2;
+    if (block_ord[mid] <= ordinal) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+
+}  // namespace
+}  // namespace vi

@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "device_index.hpp"
+#include "flat_common.hpp"
 #include "flat_search.hpp"
 #include "mfma_bf16.hpp"
 #include "record_fetch.hpp"
@@ -43,29 +44,6 @@ constexpr uint64_t kNoKey = ~0ull;
 constexpr uint64_t kOverflowKeys = 1ull << 25;  // keys of one chunk of overflow rows (256 MB)
 
 enum { kCountSurvivors = 0, kCountCandidates = 1, kCounters = 2 };
-
-// the reference's sum (src/utils.rs:28-30) of one (query row, stored vector) pair: one sequential f32 chain, no fused
-// multiply-add (the file is compiled with -ffp-contract=off), written without packed instructions
-__device__ __forceinline__ float exact_scalar(const float *qrow, const float4 *xv, uint32_t dim) {
-  float acc = 0.0f;
-  for (uint32_t qd = 0; qd < (dim >> 2); ++qd) {
-    const float4 x = xv[(size_t)qd * kWave];
-    const float4 q = *reinterpret_cast<const float4 *>(qrow + 4 * qd);
-    sq_add(acc, q.x, x.x); sq_add(acc, q.y, x.y); sq_add(acc, q.z, x.z); sq_add(acc, q.w, x.w);
-  }
-  return acc;
-}
-
-// ---- per block: the list-order ordinal of its first record and the records it holds (1..64) ----
-__global__ void flat_blocks_kernel(const uint32_t *first_block, const uint32_t *list_len, const uint64_t *prefix, uint32_t nlists,
-                                   uint32_t nblocks, uint32_t *block_ord, uint32_t *block_cnt) {
-  const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b >= nblocks) return;
-  const uint32_t l = list_of_block(first_block, nlists, b);
-  const uint32_t pos0 = (b - first_block[l]) * 64u, len = list_len[l];
-  block_ord[b] = (uint32_t)prefix[l] + pos0;
-  block_cnt[b] = len > pos0 ? min(64u, len - pos0) : 0u;
-}
 
 __global__ void flat_clear_kernel(uint32_t *cnt, uint32_t *ovf, uint32_t nq) {
   const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
@@ -106,21 +84,7 @@ __global__ void __launch_bounds__(256) flat_prepare_kernel(PrepareArgs a) {
     a.cnt[q] = 0u;
     a.ovf[q] = ok ? 0u : 1u;
   }
-  const float *row = a.c.Q + (size_t)q * a.c.dim;
-  for (uint32_t p = lane; p < 2u * a.nc; p += kWave) {  // piece (chunk c, half h): dimensions 16 c + 8 h ..
-    const uint32_t c = p >> 1, h = p & 1u, e = 16u * c + 8u * h;
-    float4 v0 = make_float4(0.f, 0.f, 0.f, 0.f), v1 = v0;
-    if (e < a.c.dim) v0 = *reinterpret_cast<const float4 *>(row + e);  // dim % 4 == 0
-    if (e + 4 < a.c.dim) v1 = *reinterpret_cast<const float4 *>(row + e + 4);
-    if (a.c.mu) {
-      if (e < a.c.dim) { const float4 m = *reinterpret_cast<const float4 *>(a.c.mu + e); v0.x -= m.x; v0.y -= m.y; v0.z -= m.z; v0.w -= m.w; }
-      if (e + 4 < a.c.dim) { const float4 m = *reinterpret_cast<const float4 *>(a.c.mu + e + 4); v1.x -= m.x; v1.y -= m.y; v1.z -= m.z; v1.w -= m.w; }
-    }
-    uint4 hi, lo;
-    split8(v0, v1, -2.0f, hi, lo);
-    a.qimg[(size_t)q * 4 * a.nc + 2 * c + h] = hi;
-    a.qimg[(size_t)q * 4 * a.nc + 2 * a.nc + 2 * c + h] = lo;
-  }
+  split_query_image(a.c, q, a.nc, lane, a.qimg);
 }
 
 // ---- step 2: the sweep ----
@@ -300,11 +264,7 @@ __device__ __forceinline__ void emit_row(const OutArgs &o, uint32_t q, const uin
     }
     ++found;
     const uint32_t ordinal = (uint32_t)key;
-    uint32_t lo = 0, hi = o.nblocks;  // block_ord[lo] <= ordinal < block_ord[hi]: every block holds a record
-    while (hi - lo > 1) {
-      const uint32_t mid = lo + (hi - lo) / 2;
-      if (o.block_ord[mid] <= ordinal) lo = mid; else hi = mid;
-    }
+    const uint32_t lo = block_of_ordinal(o.block_ord, o.nblocks, ordinal);
     o.D[at] = __uint_as_float((uint32_t)(key >> 32));
     o.I[at] = (int64_t)o.ext_ids[(size_t)lo * kWave + (ordinal - o.block_ord[lo])];
     if (o.ord) o.ord[at] = ordinal;

@@ -868,6 +868,65 @@ class VectorIndex:
         _native.check(lib().vi_exact_last_stats(C.byref(st)))
         return {f: getattr(st, f) for f, _ in st._fields_}
 
+    @staticmethod
+    def _exact_range_opts(opts, radii_ptr):
+        """None or a dict with pool_cap, and the address of the per-query radii (or None) -> vi_exact_range_opts or None"""
+        unknown = set(opts or ()) - {"pool_cap"}
+        if unknown:
+            raise TypeError(f"unknown exact-range options: {sorted(unknown)}")
+        if not opts and radii_ptr is None:
+            return None
+        o = _native.ExactRangeOpts()
+        lib().vi_exact_range_opts_init(C.byref(o))
+        o.radii, o.pool_cap = radii_ptr, int((opts or {}).get("pool_cap", 0))
+        return C.byref(o)
+
+    def range_search_exact_sync(self, xq, radius2: float, filter: Optional[AnyFilter] = None, radii=None, opts=None,
+                                include_vectors: bool = False):
+        """extension: EVERY record of the whole index (of the records `filter` admits) with squared distance <= radius2,
+        one dense sweep on the matrix cores -> (lims u64[nq + 1], D f32[total], I i64[total][, V f32[total, dim]]); query
+        q owns [lims[q], lims[q + 1]), sorted by (distance bits, list-order ordinal).  radii: one radius per query
+        instead of radius2 (NaN or negative: an empty row).  opts: a dict with pool_cap, which never changes a result.
+        Unpartitioned handles only."""
+        xq = np.asarray(xq)
+        if xq.ndim != 2:
+            raise RuntimeError("Query array must be 2-dimensional")
+        if xq.shape[1] != self._dimension:
+            raise RuntimeError(f"Query dimension {xq.shape[1]} doesn't match index dimension {self._dimension}")
+        xq = np.ascontiguousarray(xq, dtype=np.float32)
+        if radii is not None:
+            radii = np.ascontiguousarray(radii, dtype=np.float32).reshape(-1)
+            if radii.size != xq.shape[0]:
+                raise RuntimeError(f"{radii.size} radii for {xq.shape[0]} queries")
+        h = C.c_void_p()
+        _native.check(lib().vi_indexer_range_search_exact(self._h, _filter_handle(filter),
+                                                          self._exact_range_opts(opts, _native.ptr(radii)), _native.ptr(xq),
+                                                          xq.shape[0], xq.shape[1], float(radius2), C.byref(h)),
+                      prefix="Failed to range-search exactly: ")
+        res = RangeResult(self, h, xq.shape[0])
+        try:
+            return res.copy(include_vectors)
+        finally:
+            res.free()
+
+    def range_search_exact_device(self, xq_ptr: int, nq: int, radius2: float, filter: Optional[AnyFilter] = None,
+                                  radii_ptr: int = 0, opts=None) -> RangeResult:
+        """... for nq queries (and, with radii_ptr, nq f32 radii) in device memory; the result stays there (RangeResult),
+        its tie array holding every hit's list-order ordinal — the row export() gives the record"""
+        h = C.c_void_p()
+        _native.check(lib().vi_indexer_range_search_exact_device(self._h, _filter_handle(filter),
+                                                                 self._exact_range_opts(opts, C.c_void_p(radii_ptr) if radii_ptr else None),
+                                                                 C.c_void_p(xq_ptr), int(nq), float(radius2), C.byref(h)),
+                      prefix="Failed to range-search exactly: ")
+        return RangeResult(self, h, nq)
+
+    def exact_range_stats(self) -> dict:
+        """this thread's last range_search_exact_sync / range_search_exact_device: the sweep's grid, query chunks,
+        survivors (pairs evaluated exactly), hits, sweeps (0, 1 or 2), pool_cap; the ms_* only under VI_EXACT_TIMING"""
+        st = _native.ExactRangeStats()
+        _native.check(lib().vi_exact_range_last_stats(C.byref(st)))
+        return {f: getattr(st, f) for f, _ in st._fields_}
+
     def similar_times(self) -> dict:
         """this thread's last search_by_ids / knn_graph / range_search_by_ids / radius_graph (any form) under
         VI_SIMILAR_TIMING: host ms around the gather of the queries and the search, HIP-event ms and bytes of the drop

@@ -118,6 +118,18 @@ class ExactStats(C.Structure):
                 ("ms_finish", f32), ("ms_total", f32)]
 
 
+class ExactRangeOpts(C.Structure):
+    """vi_exact_range_opts"""
+    _fields_ = [("radii", vp), ("pool_cap", u64)]
+
+
+class ExactRangeStats(C.Structure):
+    """vi_exact_range_stats"""
+    _fields_ = [("nq", u64), ("query_tile", u64), ("block_splits", u64), ("chunks", u64), ("survivors", u64), ("hits", u64),
+                ("sweeps", u64), ("pool_cap", u64), ("ms_prepare", f32), ("ms_sweep", f32), ("ms_place", f32), ("ms_sort", f32),
+                ("ms_output", f32), ("ms_total", f32)]
+
+
 class ProbeRuleC(C.Structure):
     """vi_probe_rule"""
     _fields_ = [("min_probe", u32), ("ratio2", f32), ("max_codes", u64), ("n_probe_q", vp)]
@@ -254,6 +266,10 @@ SIGNATURES = {
     "vi_indexer_search_exact": (C.c_int, [vp, vp, C.POINTER(ExactOpts), vp, u64, u32, u64, vp, vp, vp, vp]),
     "vi_indexer_search_exact_device": (C.c_int, [vp, vp, C.POINTER(ExactOpts), vp, u64, u64, vp, vp, vp, vp]),
     "vi_exact_last_stats": (C.c_int, [C.POINTER(ExactStats)]),
+    "vi_exact_range_opts_init": (None, [C.POINTER(ExactRangeOpts)]),
+    "vi_indexer_range_search_exact": (C.c_int, [vp, vp, C.POINTER(ExactRangeOpts), vp, u64, u32, f32, C.POINTER(vp)]),
+    "vi_indexer_range_search_exact_device": (C.c_int, [vp, vp, C.POINTER(ExactRangeOpts), vp, u64, f32, C.POINTER(vp)]),
+    "vi_exact_range_last_stats": (C.c_int, [C.POINTER(ExactRangeStats)]),
 }
 
 _lib = None

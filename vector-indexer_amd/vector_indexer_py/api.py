@@ -18,6 +18,8 @@
     .duplicate_groups(radius2=0.0, n_probe, min_size=2) -> [[external_id]]        extension: groups of (near-)copies
     .search_exact(req) -> [SearchResult]                                          extension: the k nearest of the whole index
     .recall_of(queries, k, n_probe, ...) -> (recall_1nn, recall_intersection)     extension: recall against search_exact
+    .range_search_exact(query, radius2, ...) -> [SearchResult]                    extension: everything within a radius, whole index
+    .range_recall_of(queries, radius2, n_probe) -> float                          extension: radius recall against range_search_exact
     SearchRequest.with_timestamp_range / .with_allowed_ids / .with_excluded_ids   extension: filtered search
     SearchRequest.with_probe_ratio(ratio2, min_probe=1) / .with_max_codes(n)      extension: adaptive probing
 
@@ -474,6 +476,47 @@ class VectorIndexer:
         _native.check(lib().vi_indexer_search_exact(self._h, filter, None, _native.ptr(Q), nq, Q.shape[1], k, _native.ptr(Dx),
                                                     _native.ptr(Ix), None, None))
         return recalls(I, Ix)
+
+    def range_search_exact(self, query, radius2: float, include_vectors: bool = False,
+                           timestamp_range: Optional[Tuple[int, int]] = None, allowed_ids=None,
+                           excluded_ids=None) -> List[SearchResult]:
+        """extension: every record of the WHOLE index within squared distance radius2 of the query (of the records the
+        filters admit), nearest first, equal distances by list order: range_search without probing"""
+        if allowed_ids is not None and excluded_ids is not None:
+            raise ValueError("give allowed_ids or excluded_ids, not both")
+        selector = (IdSelector.of(allowed_ids, False) if allowed_ids is not None
+                    else IdSelector.of(excluded_ids, True) if excluded_ids is not None else None)
+        q = np.ascontiguousarray(np.asarray(query, dtype=np.float32).reshape(1, -1))
+        h = C.c_void_p()
+        _native.check(lib().vi_indexer_range_search_exact(self._h, self._filter(timestamp_range, selector), None, _native.ptr(q), 1,
+                                                          q.shape[1], float(radius2), C.byref(h)))
+        try:
+            n = int(lib().vi_range_result_total(h))
+            lims = np.zeros(2, dtype=np.uint64)
+            D, I = np.zeros(n, dtype=np.float32), np.zeros(n, dtype=np.int64)
+            V = np.zeros((n, self._cfg.dimension), dtype=np.float32) if include_vectors else None
+            _native.check(lib().vi_range_result_copy(h, _native.ptr(lims), _native.ptr(D), _native.ptr(I), _native.ptr(V)))
+        finally:
+            lib().vi_range_result_free(h)
+        return [SearchResult(int(I[j]), float(D[j]), V[j].tolist() if V is not None else None) for j in range(n)]
+
+    def range_recall_of(self, queries, radius2: float, n_probe: Optional[int] = None) -> float:
+        """extension: what a radius search at n_probe (None: the config's default) recalls on these queries: its hits over
+        the hits of range_search_exact, summed over the queries (1.0 where the exact search finds nothing).  Every probed
+        hit is an exact hit, so the counts alone say it."""
+        Q = np.ascontiguousarray(np.asarray(queries, dtype=np.float32).reshape(-1, self._cfg.dimension))
+        p = self._cfg.default_n_probe if n_probe is None else int(n_probe)
+        L, totals = lib(), []
+        for probed in (True, False):
+            h = C.c_void_p()
+            if probed:
+                _native.check(L.vi_indexer_range_search(self._h, None, _native.ptr(Q), Q.shape[0], Q.shape[1], float(radius2), p, C.byref(h)))
+            else:
+                _native.check(L.vi_indexer_range_search_exact(self._h, None, None, _native.ptr(Q), Q.shape[0], Q.shape[1],
+                                                              float(radius2), C.byref(h)))
+            totals.append(int(L.vi_range_result_total(h)))
+            L.vi_range_result_free(h)
+        return totals[0] / totals[1] if totals[1] else 1.0
 
     def search_request(self, query) -> SearchRequest:
         return SearchRequest(list(query), False, self._cfg.default_k, self._cfg.default_n_probe)

@@ -178,6 +178,12 @@ class FaissStyleAdapter:
             return self._idx.range_search_sync(np.ascontiguousarray(x, dtype=np.float32), float(thresh), self._nprobe)
         return self._idx.range_search_sync(np.ascontiguousarray(x, dtype=np.float32), float(thresh), self._nprobe, filter=flt)
 
+    def exact_range_search(self, x: np.ndarray, thresh: float, allowed_ids=None, excluded_ids=None, filter=None):
+        """what a Faiss IndexFlatL2 over the same records answers to range_search: (lims, D, I) of every record with squared
+        L2 <= thresh, whatever nprobe says; rows sorted by distance"""
+        flt = self._id_filter(allowed_ids, excluded_ids, filter)
+        return self._idx.range_search_exact_sync(np.ascontiguousarray(x, dtype=np.float32), float(thresh), filter=flt)
+
     def add(self, x: np.ndarray):
         """Faiss's Index.add: the rows of x join the index with ids ntotal, ntotal + 1, ..."""
         self._idx.add(np.ascontiguousarray(x, dtype=np.float32))
