@@ -967,6 +967,69 @@ typedef struct vi_exact_range_stats {
 } vi_exact_range_stats;
 vi_status vi_exact_range_last_stats(vi_exact_range_stats *out);
 
+/* ---- extension: exact radius graph and clustering — a symmetric self-join of the stored records on the matrix cores ----
+ * vi_indexer_radius_graph and vi_indexer_cluster_radius answer over the PROBED lists.  These answer over the whole index:
+ * every pair of stored records whose distance d <= radius2, each unordered pair visited once by a triangular sweep.
+ * Everything is in LIST ORDER: row j is the record vi_indexer_export_records returns as row j, N = vi_indexer_num_vectors.
+ *   distance: the reference's f32 squared L2 in scalar order of the two records' stored bits; d(u, v) and d(v, u) are the
+ *             same bits.  The comparison is an f32 compare, so d == radius2 is inside.
+ *   participants: the resident records; with a filter, the admitted ones.
+ *
+ * vi_indexer_cluster_radius_exact / _device: vi_indexer_cluster_radius with R(j) redefined — R(j) is every participant
+ * other than j's own slot whose distance to j's stored bits is <= radius2, over the whole index.  degree, adjacency, the
+ * core rule, the border rule, noise, labels as list-order ordinals of the cluster's first record, *n_clusters_out and NULL
+ * outputs all follow the text of vi_indexer_cluster_radius word for word; the adjacency is now symmetric by construction
+ * and the labels are those of the exact graph.  There is no n_probe.  The graph is never held: a pair is consumed where
+ * the sweep finds it.  min_pts <= 1: one sweep that links (and counts the degrees); min_pts >= 2 with labels or
+ * n_clusters_out asked for: a sweep for the degrees, the core bits, a sweep that links; only degree_out: one sweep.
+ * Beside the sweep's workspace the call holds 12 bytes and one bit per slot, freed on return.
+ *   - radius2 NaN: VI_ERR_INVALID_INPUT; negative: VI_OK, no pair, no sweep (min_pts <= 1: every participant its own
+ *     cluster; otherwise all noise); +inf: every two participants are adjacent
+ *   - all three outputs NULL: VI_ERR_INVALID_INPUT.  All or nothing, as vi_indexer_cluster_radius.
+ *
+ * vi_indexer_radius_graph_exact: the whole graph, rows 0..N, as an ordinary vi_range_result of the index (on the device;
+ * vi_range_result_total / _copy (V included) / _device / _copy_device / _free work on it unchanged).  Each row is ordered
+ * by (distance bits, list-order ordinal) and tie is the ordinal: exactly what vi_indexer_range_search_exact returns for
+ * the exported rows as queries.  exclude_self = 1 removes the row's own SLOT from its row — not its id, not every copy of
+ * its vector.  A record that is not admitted has an empty row and is in no row.
+ *   - radius2 negative: VI_OK, N empty rows, no sweep; NaN: VI_ERR_INVALID_INPUT; +inf: every admitted pair
+ *   - opts (NULL: the default) holds pool_cap only, the capacity in entries of the pool the sweep appends to, 0 =
+ *     max(2^22, 256 N).  It never changes a result: a sweep that finds more entries than the pool holds counts them all,
+ *     the pool grows to the count and the sweep runs once more.
+ *   - all or nothing: on any error *out stays NULL
+ *
+ * Limits of all three, VI_ERR_INVALID_INPUT with a message and before any device work: a null ix, a handle without an
+ * index, a partitioned handle (world_size > 1), a filter of another handle, an index without external ids, an index
+ * whose distances are not VI_ORDER_SCALAR, whose dimension is no multiple of 4 or exceeds 1536, which holds 2^26 slots or
+ * more, or whose largest squared norm is not below 1e30.  Nothing falls to a slower path.
+ * The rows run in chunks of VI_GRAPH_CHUNK (environment, default 65536) as the graph calls do; no result depends on it.
+ * Threads: the contract of a search — const on the handle, one search context held for the whole call, must not overlap
+ * an update.  Ordinals and labels refer to the list order at call time. */
+typedef struct vi_exact_join_opts {
+  uint64_t pool_cap;
+} vi_exact_join_opts;
+vi_status vi_indexer_cluster_radius_exact(const vi_indexer *ix, const vi_filter *f, float radius2, uint32_t min_pts,
+                                          int64_t *labels_out, uint32_t *degree_out, uint64_t *n_clusters_out);
+vi_status vi_indexer_cluster_radius_exact_device(const vi_indexer *ix, const vi_filter *f, float radius2, uint32_t min_pts,
+                                                 int64_t *labels_dev, uint32_t *degree_dev, uint64_t *n_clusters_out);
+vi_status vi_indexer_radius_graph_exact(const vi_indexer *ix, const vi_filter *f, float radius2, uint32_t exclude_self,
+                                        const vi_exact_join_opts *opts, vi_range_result **out);
+/* Of the calling thread's last vi_indexer_cluster_radius_exact (either form) or vi_indexer_radius_graph_exact; zeros
+ * after a failed one.  rows: N; tiles x segments: the largest grid a sweep launched (row tiles of 128 rows, segments of
+ * consecutive blocks); sweeps: sweeps over all rows — 0 (nothing to sweep), 1, or 2 (degrees then links; a pool that
+ * was too small); survivors: (row, record) pairs evaluated exactly, all sweeps; pairs: unordered pairs within the
+ * radius, as the last sweep counted them (the self entries of a graph that keeps them are not pairs); hits: directed
+ * entries — the result's total for the graph, the sum of the degrees for the clustering; pool_cap: the pool used, in
+ * entries (0 for the clustering); chunk_rows: rows per chunk.  The ms_* are taken only while the environment variable
+ * VI_EXACT_TIMING is set (and not "0"), which adds a synchronisation per phase: host clock around the gather of a chunk's
+ * rows, thresholds + images, the sweep kernel, and everything after the last sweep, summed over chunks and sweeps. */
+typedef struct vi_exact_join_stats {
+  uint64_t rows, tiles, segments, sweeps;
+  uint64_t survivors, pairs, hits, pool_cap, chunk_rows;
+  float ms_resolve, ms_prepare, ms_sweep, ms_finish;
+} vi_exact_join_stats;
+vi_status vi_exact_join_last_stats(vi_exact_join_stats *out);
+
 /* ---- extension: adaptive probing — per-query probe counts by distance ratio, code budget or list ---------------------
  * Every search entry above takes one n_probe for the whole batch.  Here n_probe is the UPPER bound and a rule decides,
  * per query, how many of its probes are searched: a prefix of its probe row.  For a row with `found` real probes in

@@ -10,6 +10,7 @@
 #include <string>
 
 #include "device_index.hpp"
+#include "flat_join.hpp"
 #include "flat_range.hpp"
 #include "flat_search.hpp"
 #include "index_lifecycle.hpp"
@@ -1241,6 +1242,60 @@ vi_status vi_exact_range_last_stats(vi_exact_range_stats *out) {
   return vi::guarded([&]() -> vi_status {
   if (!out) return fail(VI_ERR_INVALID_INPUT, "null pointer");
   *out = vi::exact_range_last_stats();
+  return VI_OK;
+  });
+}
+
+// ---- exact radius graph and clustering: the self-join of the stored records (flat_join.hip) ----
+static vi_status exact_join_common(const vi_indexer *ix, const vi_filter *f, float radius2, const char *own, const vi::SlotFilter **flt) {
+  if (!ix) return fail(VI_ERR_INVALID_INPUT, "null indexer");
+  if (std::isnan(radius2)) return fail(VI_ERR_INVALID_INPUT, "radius2 is NaN");
+  if (own) return fail(VI_ERR_INVALID_INPUT, "%s", own);
+  if (!ix->impl.dev) return fail(VI_ERR_INVALID_INPUT, "the indexer holds no index (build or load it first)");
+  if (ix->impl.cfg.world_size > 1 || ix->impl.dev->stripe_world > 1)
+    return fail(VI_ERR_INVALID_INPUT, "the exact radius join needs the whole index on one handle: a partitioned handle (world_size > 1) "
+                                      "holds only its part of every neighbourhood");
+  return filter_common(ix, f, flt);
+}
+
+static vi_status cluster_exact_common(const vi_indexer *ix, const vi_filter *f, float radius2, uint32_t min_pts, bool on_device,
+                                      int64_t *labels, uint32_t *degree, uint64_t *n_clusters) {
+  return vi::guarded([&]() -> vi_status {
+  vi::ExactJoinIO io;
+  VI_TRY(exact_join_common(ix, f, radius2,
+                           !labels && !degree && !n_clusters ? "null pointer: one of labels, degree and n_clusters_out is required" : nullptr,
+                           &io.filter));
+  io.radius2 = radius2; io.on_device = on_device; io.min_pts = min_pts; io.labels = labels; io.degree = degree; io.n_clusters = n_clusters;
+  return vi::device_index_cluster_exact(*ix->impl.dev, io);
+  });
+}
+
+vi_status vi_indexer_cluster_radius_exact(const vi_indexer *ix, const vi_filter *f, float radius2, uint32_t min_pts,
+                                          int64_t *labels_out, uint32_t *degree_out, uint64_t *n_clusters_out) {
+  return cluster_exact_common(ix, f, radius2, min_pts, false, labels_out, degree_out, n_clusters_out);
+}
+
+vi_status vi_indexer_cluster_radius_exact_device(const vi_indexer *ix, const vi_filter *f, float radius2, uint32_t min_pts,
+                                                 int64_t *labels_dev, uint32_t *degree_dev, uint64_t *n_clusters_out) {
+  return cluster_exact_common(ix, f, radius2, min_pts, true, labels_dev, degree_dev, n_clusters_out);
+}
+
+vi_status vi_indexer_radius_graph_exact(const vi_indexer *ix, const vi_filter *f, float radius2, uint32_t exclude_self,
+                                        const vi_exact_join_opts *opts, vi_range_result **out) {
+  return vi::guarded([&]() -> vi_status {
+  if (!out) return fail(VI_ERR_INVALID_INPUT, "null pointer: out is required");
+  *out = nullptr;
+  vi::ExactJoinIO io;
+  VI_TRY(exact_join_common(ix, f, radius2, nullptr, &io.filter));
+  io.radius2 = radius2; io.exclude_self = exclude_self != 0; io.pool_cap = opts ? opts->pool_cap : 0;
+  return range_run(out, [&](vi::RangeResult *r) { return vi::device_index_graph_exact(*ix->impl.dev, io, r); });
+  });
+}
+
+vi_status vi_exact_join_last_stats(vi_exact_join_stats *out) {
+  return vi::guarded([&]() -> vi_status {
+  if (!out) return fail(VI_ERR_INVALID_INPUT, "null pointer");
+  *out = vi::exact_join_last_stats();
   return VI_OK;
   });
 }

@@ -1,6 +1,7 @@
-// flat_common.hpp — the device pieces the two flat (exact, whole-index) calls share: flat_search.hip (k-NN)
-// and flat_range.hip (radius).  Each translation unit compiles its own copy (unnamed namespace): the reference
-// chain of one pair, the bf16 image of one query, the per-block ordinals and the way back from an ordinal to its block.
+// flat_common.hpp — the device pieces the flat (exact, whole-index) calls share: flat_search.hip (k-NN),
+// flat_range.hip (radius) and flat_join.hip (the radius self-join).  Each translation unit compiles
+// its own copy (unnamed namespace): the reference chain of one pair, the rank threshold of a radius, the bf16 image of one
+// query, the per-block ordinals and the way back from an ordinal to its block.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -24,6 +25,19 @@ __device__ __forceinline__ float exact_scalar(const float *qrow, const float4 *x
     sq_add(acc, q.x, x.x); sq_add(acc, q.y, x.y); sq_add(acc, q.z, x.z); sq_add(acc, q.w, x.w);
   }
   return acc;
+}
+
+// The rank threshold of radius r >= 0 for the query of frame f: a record with reference distance <= r has a true rank
+// value <= r - qn up to the rounding of the reference's own sum (w, as the radius select forms it); rank_threshold adds the
+// rank arithmetic's margins.  A radius beyond the point where the bound means anything, or a distrusted query: no bound,
+// every admitted record is evaluated
+__device__ __forceinline__ float radius_rank_threshold(const SelectCommon &c, const QueryFrame &f, float r) {
+  float thr = INFINITY;
+  if (r < 1.0e37f) {
+    const float w = ((float)(c.dim >> 6) + 9.0f) * 6.1e-8f * (fabsf(r) + f.qn);
+    thr = rank_threshold(c, f, (r - f.qn) + w);
+  }
+  return thr;
 }
 
 // ---- per block: the list-order ordinal of its first record and the records it holds (1..64) ----

@@ -13,7 +13,7 @@
 //               pool's capacity nothing is written and everything is still counted.
 //   3. size     the host reads the cursor: a pool that was too small grows to the count and the sweep runs once more.
 //               range_result_place sizes lims and the result from the per-query counts.
-//   4. place    flat_range_place_kernel scatters the pool into the rows; flat_range_sort_kernel sorts every row of up to
+//   4. place    (flat_rows.hpp) flat_range_place_kernel scatters the pool into the rows; flat_range_sort_kernel sorts every row of up to
 //               8192 keys in LDS, longer rows go through sort_rows_u64 on padded scratch; flat_range_output_kernel writes
 //               D / I / tie (the ordinal) / slot.
 // Neither the order hits arrive in nor the second sweep shows in a result; no result depends on a rank value.
@@ -27,6 +27,7 @@
 #include "device_index.hpp"
 #include "flat_common.hpp"
 #include "flat_range.hpp"
+#include "flat_rows.hpp"
 #include "mfma_bf16.hpp"
 #include "record_fetch.hpp"
 #include "search_internal.hpp"
@@ -40,8 +41,6 @@ constexpr uint32_t kTileQ = 128;       // queries per workgroup: four waves of o
 constexpr uint32_t kMaxChunks = 8;     // D <= 128: chunks of 16 dimensions whose B fragments a wave keeps in registers
 constexpr uint32_t kStreamChunks = 2;  // D > 128: chunks per K step (both operands stream through LDS)
 constexpr uint32_t kQueueLen = 1024;   // survivors of one wave and accumulator tile: 32 queries x 32 vectors, never more
-constexpr uint64_t kNoKey = ~0ull;
-constexpr uint64_t kPadKeys = 1ull << 25;  // keys of one batch of long rows on their padded scratch (256 MB)
 
 enum { kCursor = 0, kSurvivors = 1, kCounters = 2 };
 
@@ -65,14 +64,7 @@ __global__ void __launch_bounds__(256) flat_range_prepare_kernel(RangePrepareArg
   const QueryFrame f = query_frame<false>(a.c, q, lane, nullptr, nullptr);
   const float r = a.radii ? a.radii[q] : a.radius2;
   const bool empty = !(r >= 0.0f);  // negative or NaN: no squared distance is within it
-  // a record with reference distance <= r has a true rank value <= r - qn up to the rounding of the reference's own sum
-  // (w, as the radius select forms it); rank_threshold adds the rank arithmetic's margins.  A radius beyond the point where
-  // the bound means anything, or a distrusted query: no bound, every admitted record is evaluated
-  float thr = INFINITY;
-  if (r < 1.0e37f) {
-    const float w = ((float)(a.c.dim >> 6) + 9.0f) * 6.1e-8f * (fabsf(r) + f.qn);
-    thr = rank_threshold(a.c, f, (r - f.qn) + w);
-  }
+  const float thr = radius_rank_threshold(a.c, f, r);
   if (lane == 0) {
     a.thr[q] = empty ? -INFINITY : thr;
     a.rad[q] = empty ? -1.0f : r;
@@ -309,76 +301,6 @@ __global__ void __launch_bounds__(256, 2) flat_range_sweep_kernel(RangeSweepArgs
   if (lane == 0 && nsurv) atomicAdd(a.counters + kSurvivors, (unsigned long long)nsurv);
 }
 
-// ---- step 4: pool -> rows -> the result ----
-// entry i of the pool to the next free place of its query's row; lims: the chunk's (global) row offsets, lims[0] = base
-__global__ void __launch_bounds__(256) flat_range_place_kernel(const uint64_t *pool_key, const uint32_t *pool_q, uint64_t n,
-                                                               const uint64_t *lims, uint32_t *fill, uint64_t *rows) {
-  const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
-  if (i >= n) return;
-  const uint32_t q = pool_q[i];
-  rows[(lims[q] - lims[0]) + atomicAdd(fill + q, 1u)] = pool_key[i];
-}
-
-// one wave per query: a row of 2 .. kRangeSortLds keys sorted in LDS (a bitonic network over the next power of two)
-__global__ void __launch_bounds__(64) flat_range_sort_kernel(const uint64_t *lims, uint64_t *rows) {
-  extern __shared__ __attribute__((aligned(16))) uint64_t s_keys[];
-  const int lane = threadIdx.x;
-  const uint64_t at = lims[blockIdx.x] - lims[0], n64 = lims[blockIdx.x + 1] - lims[blockIdx.x];
-  if (n64 < 2 || n64 > kRangeSortLds) return;
-  const uint32_t n = (uint32_t)n64;
-  uint32_t P = kWave;
-  while (P < n) P <<= 1;
-  for (uint32_t i = lane; i < P; i += kWave) s_keys[i] = i < n ? rows[at + i] : kNoKey;
-  wave_lds_sync();
-  for (uint32_t k2 = 2; k2 <= P; k2 <<= 1)
-    for (uint32_t j2 = k2 >> 1; j2 > 0; j2 >>= 1) {
-      for (uint32_t t = lane; t < P / 2; t += kWave) {
-        const uint32_t i = ((t & ~(j2 - 1u)) << 1) | (t & (j2 - 1u));
-        const uint64_t x = s_keys[i], y = s_keys[i + j2];
-        if ((x > y) == ((i & k2) == 0u)) { s_keys[i] = y; s_keys[i + j2] = x; }
-      }
-      wave_lds_sync();
-    }
-  for (uint32_t i = lane; i < n; i += kWave) rows[at + i] = s_keys[i];
-}
-
-// the rows of queries long[blockIdx.y] to (BACK false) or from (BACK true) rows of 2^logL keys padded with kNoKey
-template <bool BACK>
-__global__ void __launch_bounds__(256) flat_range_pad_kernel(const uint64_t *lims, const uint32_t *longq, uint32_t logL, uint64_t *rows,
-                                                             uint64_t *pad) {
-  const uint32_t q = longq[blockIdx.y];
-  const uint64_t at = lims[q] - lims[0], n = lims[q + 1] - lims[q];
-  uint64_t *row = pad + ((size_t)blockIdx.y << logL);
-  for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < (1ull << logL); i += (uint64_t)gridDim.x * 256u) {
-    if (BACK) { if (i < n) rows[at + i] = row[i]; }
-    else row[i] = i < n ? rows[at + i] : kNoKey;
-  }
-}
-
-struct RangeOutArgs {
-  const uint64_t *rows;
-  uint64_t n;
-  const uint32_t *block_ord;
-  const uint64_t *ext_ids;
-  uint32_t nblocks;
-  float *D;       // the chunk's first entry of the result
-  int64_t *I;
-  uint64_t *tie, *slots;
-};
-
-// sorted key i of the chunk -> entry i: the distance, the external id, the ordinal and the slot of the record
-__global__ void __launch_bounds__(256) flat_range_output_kernel(RangeOutArgs o) {
-  const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
-  if (i >= o.n) return;
-  const uint64_t key = o.rows[i];
-  const uint32_t ordinal = (uint32_t)key, b = block_of_ordinal(o.block_ord, o.nblocks, ordinal);
-  const uint64_t slot = (uint64_t)b * kWave + (ordinal - o.block_ord[b]);
-  o.D[i] = __uint_as_float((uint32_t)(key >> 32));
-  o.I[i] = (int64_t)o.ext_ids[slot];
-  o.tie[i] = ordinal;
-  o.slots[i] = slot;
-}
-
 thread_local vi_exact_range_stats g_last_stats{};
 
 vi_status range_exact_in_context(const DeviceIndex &ix, SearchContext &ctx, const ExactRangeIO &io, RangeResult *out) {
@@ -437,9 +359,7 @@ vi_status range_exact_in_context(const DeviceIndex &ix, SearchContext &ctx, cons
   const void *fn = resident ? (const void *)flat_range_sweep_kernel<true> : (const void *)flat_range_sweep_kernel<false>;
   if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
     return fail(VI_ERR_DEVICE, "cannot reserve %d bytes of LDS for the exact radius search's sweep", lds);
-  if (hipFuncSetAttribute((const void *)flat_range_sort_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                          (int)(kRangeSortLds * sizeof(uint64_t))) != hipSuccess)
-    return fail(VI_ERR_DEVICE, "cannot reserve LDS for the exact radius search's sort");
+  VI_TRY(reserve_csr_sort_lds());
 
   for (uint64_t q0 = 0; q0 < nq; q0 += kRangeQueryChunk) {
     const uint64_t m = std::min<uint64_t>(kRangeQueryChunk, nq - q0);
@@ -503,37 +423,7 @@ vi_status range_exact_in_context(const DeviceIndex &ix, SearchContext &ctx, cons
                        (const uint32_t *)fr.pool_q.p, total, lims, fr.fill.p, fr.rows.p);
     VI_HIP(hipGetLastError());
     VI_TRY(lap(es.ms_place));
-    uint64_t longest = 0, lds_row = 0;  // the longest row, and the longest the LDS sort takes
-    std::vector<uint32_t> longq;
-    for (uint64_t q = 0; q < m; ++q) {
-      const uint64_t n = out->h_lims[q0 + q + 1] - out->h_lims[q0 + q];
-      longest = std::max(longest, n);
-      if (n > kRangeSortLds) longq.push_back((uint32_t)q);
-      else lds_row = std::max(lds_row, n);
-    }
-    if (lds_row >= 2) {
-      uint64_t p2 = kWave;
-      while (p2 < lds_row) p2 <<= 1;
-      hipLaunchKernelGGL(flat_range_sort_kernel, dim3((uint32_t)m), dim3(64), p2 * sizeof(uint64_t), st, lims, fr.rows.p);
-      VI_HIP(hipGetLastError());
-    }
-    if (!longq.empty()) {
-      uint32_t logL = 14;
-      while ((1ull << logL) < longest) ++logL;
-      const uint64_t per = std::max<uint64_t>(1, kPadKeys >> logL);
-      VI_TRY(upload(fr.longq, longq.data(), longq.size(), st));
-      VI_TRY(fr.pad.reserve(std::min<uint64_t>(per, longq.size()) << logL));
-      const uint32_t gx = (uint32_t)std::min<uint64_t>((1ull << logL) / 256u, 1024u);
-      for (uint64_t r0 = 0; r0 < longq.size(); r0 += per) {
-        const uint32_t nr = (uint32_t)std::min<uint64_t>(per, longq.size() - r0);
-        hipLaunchKernelGGL(flat_range_pad_kernel<false>, dim3(gx, nr), dim3(256), 0, st, lims, fr.longq.p + r0, logL, fr.rows.p, fr.pad.p);
-        VI_HIP(hipGetLastError());
-        VI_TRY(sort_rows_u64(fr.pad.p, nr, logL, st));
-        hipLaunchKernelGGL(flat_range_pad_kernel<true>, dim3(gx, nr), dim3(256), 0, st, lims, fr.longq.p + r0, logL, fr.rows.p, fr.pad.p);
-        VI_HIP(hipGetLastError());
-      }
-      VI_HIP(hipStreamSynchronize(st));  // (`longq` is read by its upload until here)
-    }
+    VI_TRY(sort_csr_rows(lims, out->h_lims.data() + q0, m, fr.rows.p, fr.longq, fr.pad, st));
     VI_TRY(lap(es.ms_sort));
     RangeOutArgs o{fr.rows.p, total, fr.block_ord.p, ix.ext_ids.p, nblocks, out->D.p + base, out->I.p + base, out->tie.p + base,
                    out->slots.p + base};

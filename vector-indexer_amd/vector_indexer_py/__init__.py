@@ -927,6 +927,55 @@ class VectorIndex:
         _native.check(lib().vi_exact_range_last_stats(C.byref(st)))
         return {f: getattr(st, f) for f, _ in st._fields_}
 
+    def cluster_radius_exact(self, radius2: float, min_pts: int = 1, filter: Optional[AnyFilter] = None, with_degree: bool = False):
+        """extension: cluster_radius over the EXACT radius graph of the whole index — no n_probe: every pair of records
+        (of the records `filter` admits) within squared distance radius2 is an edge, each pair visited once by a
+        triangular sweep on the matrix cores -> labels i64[n] (or (labels, degree u32[n])) in LIST ORDER, by the rules of
+        cluster_radius.  The graph is never held.  exact_join_stats() has the sweep's figures.  Unpartitioned handles only."""
+        n = self.num_vectors
+        labels = np.full(n, -1, dtype=np.int64)
+        degree = np.zeros(n, dtype=np.uint32) if with_degree else None
+        nc = C.c_uint64(0)
+        _native.check(lib().vi_indexer_cluster_radius_exact(self._h, _filter_handle(filter), float(radius2), int(min_pts),
+                                                            _native.ptr(labels), _native.ptr(degree), C.byref(nc)),
+                      prefix="Failed to cluster exactly by radius: ")
+        return (labels, degree) if with_degree else labels
+
+    def cluster_radius_exact_device(self, labels_ptr: int, degree_ptr: int = 0, radius2: float = 0.0, min_pts: int = 1,
+                                    filter: Optional[AnyFilter] = None) -> int:
+        """... into device memory: labels i64[num_vectors] / degree u32[num_vectors]; a pointer of 0 skips that output.
+        Returns the number of clusters."""
+        nc = C.c_uint64(0)
+        _native.check(lib().vi_indexer_cluster_radius_exact_device(self._h, _filter_handle(filter), float(radius2), int(min_pts),
+                                                                   C.c_void_p(labels_ptr) if labels_ptr else None,
+                                                                   C.c_void_p(degree_ptr) if degree_ptr else None, C.byref(nc)),
+                      prefix="Failed to cluster exactly by radius: ")
+        return int(nc.value)
+
+    def radius_graph_exact(self, radius2: float, exclude_self: bool = True, filter: Optional[AnyFilter] = None, opts=None) -> RangeResult:
+        """extension: the EXACT radius graph of all stored records, left on the device (RangeResult): row j belongs to
+        the record export() returns as row j and holds every record (that `filter` admits) within squared distance
+        radius2, sorted by (distance bits, list-order ordinal), tie = the ordinal — what range_search_exact gives for the
+        exported rows as queries, at half the matrix work.  exclude_self drops the row's own slot.  opts: a dict with
+        pool_cap, which never changes a result.  Unpartitioned handles only."""
+        unknown = set(opts or ()) - {"pool_cap"}
+        if unknown:
+            raise TypeError(f"unknown exact-join options: {sorted(unknown)}")
+        o = _native.ExactJoinOpts(int((opts or {}).get("pool_cap", 0)))
+        h = C.c_void_p()
+        _native.check(lib().vi_indexer_radius_graph_exact(self._h, _filter_handle(filter), float(radius2), 1 if exclude_self else 0,
+                                                          C.byref(o), C.byref(h)),
+                      prefix="Failed to build the exact radius graph: ")
+        return RangeResult(self, h, self.num_vectors)
+
+    def exact_join_stats(self) -> dict:
+        """this thread's last cluster_radius_exact (either form) / radius_graph_exact: rows, the largest grid (tiles x
+        segments), sweeps over all rows, survivors (pairs evaluated exactly), pairs (unordered, within the radius), hits
+        (directed entries), pool_cap, chunk_rows; the ms_* only under VI_EXACT_TIMING"""
+        st = _native.ExactJoinStats()
+        _native.check(lib().vi_exact_join_last_stats(C.byref(st)))
+        return {f: getattr(st, f) for f, _ in st._fields_}
+
     def similar_times(self) -> dict:
         """this thread's last search_by_ids / knn_graph / range_search_by_ids / radius_graph (any form) under
         VI_SIMILAR_TIMING: host ms around the gather of the queries and the search, HIP-event ms and bytes of the drop

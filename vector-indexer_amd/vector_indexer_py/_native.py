@@ -130,6 +130,18 @@ class ExactRangeStats(C.Structure):
                 ("ms_output", f32), ("ms_total", f32)]
 
 
+class ExactJoinOpts(C.Structure):
+    """vi_exact_join_opts"""
+    _fields_ = [("pool_cap", u64)]
+
+
+class ExactJoinStats(C.Structure):
+    """vi_exact_join_stats"""
+    _fields_ = [("rows", u64), ("tiles", u64), ("segments", u64), ("sweeps", u64), ("survivors", u64), ("pairs", u64),
+                ("hits", u64), ("pool_cap", u64), ("chunk_rows", u64), ("ms_resolve", f32), ("ms_prepare", f32),
+                ("ms_sweep", f32), ("ms_finish", f32)]
+
+
 class ProbeRuleC(C.Structure):
     """vi_probe_rule"""
     _fields_ = [("min_probe", u32), ("ratio2", f32), ("max_codes", u64), ("n_probe_q", vp)]
@@ -270,6 +282,10 @@ SIGNATURES = {
     "vi_indexer_range_search_exact": (C.c_int, [vp, vp, C.POINTER(ExactRangeOpts), vp, u64, u32, f32, C.POINTER(vp)]),
     "vi_indexer_range_search_exact_device": (C.c_int, [vp, vp, C.POINTER(ExactRangeOpts), vp, u64, f32, C.POINTER(vp)]),
     "vi_exact_range_last_stats": (C.c_int, [C.POINTER(ExactRangeStats)]),
+    "vi_indexer_cluster_radius_exact": (C.c_int, [vp, vp, f32, u32, vp, vp, C.POINTER(u64)]),
+    "vi_indexer_cluster_radius_exact_device": (C.c_int, [vp, vp, f32, u32, vp, vp, C.POINTER(u64)]),
+    "vi_indexer_radius_graph_exact": (C.c_int, [vp, vp, f32, u32, C.POINTER(ExactJoinOpts), C.POINTER(vp)]),
+    "vi_exact_join_last_stats": (C.c_int, [C.POINTER(ExactJoinStats)]),
 }
 
 _lib = None

@@ -424,15 +424,20 @@ class VectorIndexer:
             return None
         return [SearchResult(int(I[j]), float(D[j]), V[j].tolist() if V is not None else None) for j in range(n)]
 
-    def duplicate_groups(self, radius2: float = 0.0, n_probe: Optional[int] = None, min_size: int = 2) -> List[List[int]]:
+    def duplicate_groups(self, radius2: float = 0.0, n_probe: Optional[int] = None, min_size: int = 2,
+                         exact: bool = False) -> List[List[int]]:
         """extension: the clusters of stored records chained by squared distance <= radius2 (0.0: exact copies) that have
         at least min_size members, as lists of external ids — members in list order, groups ordered by their first
         member.  The connected components of the index's radius graph over the probed lists, made on the GPU; only one
-        label per record comes back.  n_probe None: the config's default_n_probe."""
+        label per record comes back.  n_probe None: the config's default_n_probe.  exact: the components of the EXACT
+        radius graph of the whole index instead (vi_indexer_cluster_radius_exact); n_probe is then not read."""
         p = self._cfg.default_n_probe if n_probe is None else int(n_probe)
         n = int(lib().vi_indexer_num_vectors(self._h))
         labels, ids = np.full(n, -1, dtype=np.int64), np.zeros(n, dtype=np.uint64)
-        _native.check(lib().vi_indexer_cluster_radius(self._h, None, float(radius2), p, 1, _native.ptr(labels), None, None))
+        if exact:
+            _native.check(lib().vi_indexer_cluster_radius_exact(self._h, None, float(radius2), 1, _native.ptr(labels), None, None))
+        else:
+            _native.check(lib().vi_indexer_cluster_radius(self._h, None, float(radius2), p, 1, _native.ptr(labels), None, None))
         if n:
             _native.check(lib().vi_indexer_export_records(self._h, 0, n, _native.ptr(ids), None, None, None))
         order = np.argsort(labels, kind="stable")          # by representative, list order inside a group
