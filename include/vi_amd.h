@@ -1030,6 +1030,62 @@ typedef struct vi_exact_join_stats {
 } vi_exact_join_stats;
 vi_status vi_exact_join_last_stats(vi_exact_join_stats *out);
 
+/* ---- extension: exact k-NN graph of the stored records — a bounded triangular self-join on the matrix cores ------------
+ * vi_indexer_knn_graph answers over the PROBED lists.  This answers over the whole index: rows 0..N in LIST ORDER, N =
+ * vi_indexer_num_vectors, row j belonging to the record vi_indexer_export_records returns as row j.  Row u holds the k
+ * smallest keys (distance bits, list-order ordinal) over the participants: every resident record, with a filter every
+ * admitted one.
+ *   distance: the reference's f32 squared L2 in scalar order of the two records' stored bits; equal distances go to the
+ *             LOWER ORDINAL (the rule of vi_indexer_search_exact)
+ *   k:        1..128, NOT clamped to max_k
+ *   exclude_self = 1: the row's own SLOT is no candidate — its id and the copies of its vector still are.
+ *   exclude_self = 0: the own slot is one entry at distance 0.
+ *   D is N x k f32, I N x k external ids, ord (optional) N x k ordinals, counts (optional) N entry counts; short rows are
+ *   padded as vi_indexer_search_exact pads them (+inf / -1 / UINT64_MAX).  A record the filter does not admit has an
+ *   all-padding row with count 0 and is in no row (the rule of vi_indexer_radius_graph_exact).
+ * The result is, bit for bit, what vi_indexer_search_exact returns for the exported rows as queries, minus the own slot
+ * when excluded — at half the matrix work, every unordered pair being visited once.
+ *
+ * How: a search at opts->seed_probe over every chunk of rows gives each record a bound B (the distance of its k-th hit,
+ * +inf where the seed found fewer than k: an unbounded row).  One triangular sweep (the blocking of
+ * vi_indexer_radius_graph_exact) then meets the pair (u, v) once, in u's frame, and evaluates it in the reference's chain
+ * whenever its rank value can lie under u's threshold of B_u OR under u's threshold of B_v; the entry (row u: v) is kept
+ * if d <= B_u and the entry (row v: u) if d <= B_v, in a pool; the rows are sorted and cut at k.  No result depends on a
+ * rank value, on the bounds beyond their being upper bounds, or on the order entries arrive in.
+ *   - opts (NULL: the defaults) never changes a result.  seed_probe: n_probe of the seeding search, 0 = 16, clamped to
+ *     max_n_probe.  pool_cap: capacity in entries of the pool, 0 = max(2^22, (2 k + 16) N); a sweep that finds more
+ *     entries than the pool holds counts them all, the pool grows to the count and the sweep runs once more.
+ *   - limits, all VI_ERR_INVALID_INPUT with a message and before any device work: those of
+ *     vi_indexer_radius_graph_exact — a null ix, a handle without an index, a partitioned handle (world_size > 1), a
+ *     filter of another handle, an index without external ids, an index whose distances are not VI_ORDER_SCALAR, whose
+ *     dimension is no multiple of 4 or exceeds 1536, which holds 2^26 slots or more, or whose largest squared norm is not
+ *     below 1e30 — and k == 0, k > 128, a NULL D or I.  Nothing falls to a slower path.
+ *   - an empty index: VI_OK, nothing written
+ *   - all or nothing: the outputs of the host entry are written once everything has succeeded
+ * The rows run in chunks of VI_GRAPH_CHUNK (environment, default 65536); no result depends on it.  Threads: the contract
+ * of a search — const on the handle, one search context held for the whole call, must not overlap an update. */
+typedef struct vi_exact_knn_opts { uint64_t seed_probe; uint64_t pool_cap; } vi_exact_knn_opts;
+void vi_exact_knn_opts_init(vi_exact_knn_opts *opts);
+vi_status vi_indexer_knn_graph_exact(const vi_indexer *ix, const vi_filter *f, const vi_exact_knn_opts *opts, uint64_t k,
+                                     uint32_t exclude_self, float *D, int64_t *I, uint64_t *ord, uint64_t *counts);
+vi_status vi_indexer_knn_graph_exact_device(const vi_indexer *ix, const vi_filter *f, const vi_exact_knn_opts *opts, uint64_t k,
+                                            uint32_t exclude_self, float *D_dev, int64_t *I_dev, uint64_t *ord_dev,
+                                            uint64_t *counts_dev);
+/* Of the calling thread's last vi_indexer_knn_graph_exact (either form); zeros after a failed one.  rows: N; k and
+ * seed_probe: the values used; tiles x segments: the largest grid a sweep launched; sweeps: 0 (an empty index), 1, or 2 (a
+ * pool that was too small); survivors: (row, record) pairs the compare let through, all sweeps; candidates: entries of
+ * the pool as the last sweep counted them; unbounded_rows: admitted rows whose seed found fewer than k; pool_cap: the
+ * pool used, in entries; chunk_rows: rows per chunk.  The ms_* are taken only while the environment variable
+ * VI_EXACT_TIMING is set (and not "0"), which adds a synchronisation per phase: host clock around pass 1 (gathers, seeding
+ * searches, bounds), the gather of a chunk's rows with its thresholds and images, the sweep kernel, and everything after
+ * the last sweep, summed over chunks and sweeps. */
+typedef struct vi_exact_knn_stats {
+  uint64_t rows, k, seed_probe, tiles, segments, sweeps;
+  uint64_t survivors, candidates, unbounded_rows, pool_cap, chunk_rows;
+  float ms_seed, ms_prepare, ms_sweep, ms_finish;
+} vi_exact_knn_stats;
+vi_status vi_exact_knn_last_stats(vi_exact_knn_stats *out);
+
 /* ---- extension: adaptive probing — per-query probe counts by distance ratio, code budget or list ---------------------
  * Every search entry above takes one n_probe for the whole batch.  Here n_probe is the UPPER bound and a rule decides,
  * per query, how many of its probes are searched: a prefix of its probe row.  For a row with `found` real probes in

@@ -11,6 +11,7 @@
 
 #include "device_index.hpp"
 #include "flat_join.hpp"
+#include "flat_knn.hpp"
 #include "flat_range.hpp"
 #include "flat_search.hpp"
 #include "index_lifecycle.hpp"
@@ -1296,6 +1297,52 @@ vi_status vi_exact_join_last_stats(vi_exact_join_stats *out) {
   return vi::guarded([&]() -> vi_status {
   if (!out) return fail(VI_ERR_INVALID_INPUT, "null pointer");
   *out = vi::exact_join_last_stats();
+  return VI_OK;
+  });
+}
+
+// ---- exact k-NN graph of the stored records: a bounded triangular self-join (flat_knn.hip) ----
+void vi_exact_knn_opts_init(vi_exact_knn_opts *opts) {
+  if (opts) *opts = vi_exact_knn_opts{0, 0};
+}
+
+static vi_status knn_graph_exact_common(const vi_indexer *ix, const vi_filter *f, const vi_exact_knn_opts *opts, uint64_t k,
+                                        uint32_t exclude_self, bool on_device, float *D, int64_t *I, uint64_t *ord, uint64_t *counts) {
+  return vi::guarded([&]() -> vi_status {
+  if (!ix) return fail(VI_ERR_INVALID_INPUT, "null indexer");
+  if (k == 0 || k > vi::kExactMaxK)  // (not clamped to max_k: the answer is exact or an error)
+    return fail(VI_ERR_INVALID_INPUT, "k must be in 1..%llu for an exact k-NN graph, not %llu", (unsigned long long)vi::kExactMaxK,
+                (unsigned long long)k);
+  if (!D || !I) return fail(VI_ERR_INVALID_INPUT, "null pointer: D and I are required");
+  if (!ix->impl.dev) return fail(VI_ERR_INVALID_INPUT, "the indexer holds no index (build or load it first)");
+  if (ix->impl.cfg.world_size > 1 || ix->impl.dev->stripe_world > 1)
+    return fail(VI_ERR_INVALID_INPUT, "the exact k-NN graph needs the whole index on one handle: a partitioned handle (world_size > 1) "
+                                      "holds only its part of every neighbourhood");
+  vi::ExactKnnIO io;
+  VI_TRY(filter_common(ix, f, &io.filter));
+  uint64_t one = 1, seed = opts ? opts->seed_probe : 0;
+  if (seed) VI_TRY(search_common(ix, &one, &seed));  // (the clamp to max_n_probe)
+  io.k = k; io.exclude_self = exclude_self != 0; io.seed_probe = seed; io.pool_cap = opts ? opts->pool_cap : 0;
+  io.on_device = on_device; io.D = D; io.I = I; io.ord = ord; io.counts = counts;
+  return vi::device_index_knn_graph_exact(*ix->impl.dev, io);
+  });
+}
+
+vi_status vi_indexer_knn_graph_exact(const vi_indexer *ix, const vi_filter *f, const vi_exact_knn_opts *opts, uint64_t k,
+                                     uint32_t exclude_self, float *D, int64_t *I, uint64_t *ord, uint64_t *counts) {
+  return knn_graph_exact_common(ix, f, opts, k, exclude_self, false, D, I, ord, counts);
+}
+
+vi_status vi_indexer_knn_graph_exact_device(const vi_indexer *ix, const vi_filter *f, const vi_exact_knn_opts *opts, uint64_t k,
+                                            uint32_t exclude_self, float *D_dev, int64_t *I_dev, uint64_t *ord_dev,
+                                            uint64_t *counts_dev) {
+  return knn_graph_exact_common(ix, f, opts, k, exclude_self, true, D_dev, I_dev, ord_dev, counts_dev);
+}
+
+vi_status vi_exact_knn_last_stats(vi_exact_knn_stats *out) {
+  return vi::guarded([&]() -> vi_status {
+  if (!out) return fail(VI_ERR_INVALID_INPUT, "null pointer");
+  *out = vi::exact_knn_last_stats();
   return VI_OK;
   });
 }

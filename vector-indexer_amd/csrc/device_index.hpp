@@ -141,7 +141,7 @@ struct SearchWorkspace {
   // query; the chunk's image; a host caller's radii; per block the ordinal of its first record and its records; the hit
   // pool (key, query); the rows before and after their sort; the queries whose rows are too long for the LDS sort and
   // the padded scratch those are sorted on; the cursor and the survivor count.  The exact radius join (flat_join.hip)
-  // uses the same buffers, rows in place of queries: cnt / fill then span all N rows
+  // and the exact k-NN graph (flat_knn.hip) use the same buffers, rows in place of queries: cnt / fill then span all N rows
   struct FlatRangeBuffers {
     DevBuf<float> thr, rad, radii;
     DevBuf<uint32_t> cnt, fill, qimg, block_ord, block_cnt, pool_q, longq;

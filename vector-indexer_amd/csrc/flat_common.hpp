@@ -1,5 +1,6 @@
 // flat_common.hpp — the device pieces the flat (exact, whole-index) calls share: flat_search.hip (k-NN),
-// flat_range.hip (radius) and flat_join.hip (the radius self-join).  Each translation unit compiles
+// flat_range.hip (radius), flat_join.hip (the radius self-join) and flat_knn.hip (the k-NN
+// self-join).  Each translation unit compiles
 // its own copy (unnamed namespace): the reference chain of one pair, the rank threshold of a radius, the bf16 image of one
 // query, the per-block ordinals and the way back from an ordinal to its block.
 #pragma once

@@ -1,5 +1,6 @@
 // flat_rows.hpp — from a pool of hits to sorted CSR rows: the last step of the exact radius search (flat_range.hip,
-// DESIGN §4s) and of the exact radius graph (flat_join.hip).  A pool entry is (key = distance bits << 32 |
+// DESIGN §4s), of the exact radius graph (flat_join.hip) and, up to the sort, of the exact k-NN graph
+// (flat_knn.hip).  A pool entry is (key = distance bits << 32 |
 // ordinal, row); flat_range_place_kernel scatters the pool into the rows, flat_range_sort_kernel sorts every row of up to
 // kRangeSortLds keys in LDS, longer rows go through sort_rows_u64 on padded scratch (sort_csr_rows), and
 // flat_range_output_kernel writes D / I / tie (the ordinal) / slot.  Each translation unit compiles its own copy.

@@ -35,9 +35,9 @@ from typing import Optional, Tuple, Union
 import numpy as np
 
 from . import _native
-from ._native import (ViError, lib, VI_ASSIGN_EXACT, VI_ASSIGN_REFERENCE, VI_ORDER_LANES, VI_ORDER_SCALAR)
+from ._native import (ExactKnnOpts, ViError, lib, VI_ASSIGN_EXACT, VI_ASSIGN_REFERENCE, VI_ORDER_LANES, VI_ORDER_SCALAR)
 
-__all__ = ["build", "load", "suggest_nlist", "VectorIndex", "ProbeRule", "RebalanceRule", "TimestampFilter", "IdFilter", "FilterIntersection", "ComposedFilter", "Term", "AnyFilter", "RangeResult", "merge_range_results", "merge_range_results_device", "ViError", "kmeans_mini_batch", "kmeans_parallel",
+__all__ = ["build", "load", "suggest_nlist", "VectorIndex", "ProbeRule", "RebalanceRule", "TimestampFilter", "IdFilter", "FilterIntersection", "ComposedFilter", "Term", "AnyFilter", "RangeResult", "merge_range_results", "merge_range_results_device", "ViError", "ExactKnnOpts", "kmeans_mini_batch", "kmeans_parallel",
            "assign", "l2sq_pairs", "VI_ASSIGN_EXACT", "VI_ASSIGN_REFERENCE", "VI_ORDER_LANES", "VI_ORDER_SCALAR"]
 
 
@@ -974,6 +974,57 @@ class VectorIndex:
         (directed entries), pool_cap, chunk_rows; the ms_* only under VI_EXACT_TIMING"""
         st = _native.ExactJoinStats()
         _native.check(lib().vi_exact_join_last_stats(C.byref(st)))
+        return {f: getattr(st, f) for f, _ in st._fields_}
+
+    @staticmethod
+    def _exact_knn_opts(opts):
+        """None, an ExactKnnOpts or a dict with seed_probe / pool_cap -> vi_exact_knn_opts (or None: the defaults)"""
+        if opts is None or isinstance(opts, ExactKnnOpts):
+            return opts if opts is None else C.byref(opts)
+        unknown = set(opts) - {"seed_probe", "pool_cap"}
+        if unknown:
+            raise TypeError(f"unknown exact-knn options: {sorted(unknown)}")
+        o = ExactKnnOpts()
+        lib().vi_exact_knn_opts_init(C.byref(o))
+        o.seed_probe, o.pool_cap = int(opts.get("seed_probe", 0)), int(opts.get("pool_cap", 0))
+        return C.byref(o)
+
+    def knn_graph_exact(self, k: int, exclude_self: bool = True, filter: Optional[AnyFilter] = None, opts=None,
+                        with_ord: bool = False):
+        """extension: the EXACT k-NN graph of all stored records -> (D f32[n, k], I i64[n, k][, ord u64[n, k]], counts
+        u64[n]): row j belongs to the record export() returns as row j and holds the k nearest records of the WHOLE index
+        (of the records `filter` admits), the reference's distance bits, ties to the lower list-order ordinal, +inf / -1 /
+        2^64-1 padding — what search_exact_sync gives for the exported rows, every pair visited once by a triangular
+        sweep on the matrix cores.  exclude_self drops the row's own slot.  k in 1..128.  opts: an ExactKnnOpts or a dict
+        with seed_probe and / or pool_cap, which never change a result.  Unpartitioned handles only."""
+        n, k = self.num_vectors, int(k)
+        D = np.full((n, max(k, 0)), np.inf, dtype=np.float32)
+        I = np.full((n, max(k, 0)), -1, dtype=np.int64)
+        ord_ = np.full((n, max(k, 0)), (1 << 64) - 1, dtype=np.uint64) if with_ord else None
+        counts = np.zeros(n, dtype=np.uint64)
+        _native.check(lib().vi_indexer_knn_graph_exact(self._h, _filter_handle(filter), self._exact_knn_opts(opts), k,
+                                                       1 if exclude_self else 0, _native.ptr(D), _native.ptr(I), _native.ptr(ord_),
+                                                       _native.ptr(counts)),
+                      prefix="Failed to build the exact k-NN graph: ")
+        return (D, I, ord_, counts) if with_ord else (D, I, counts)
+
+    def knn_graph_exact_device(self, k: int, D_ptr: int, I_ptr: int, ord_ptr: int = 0, counts_ptr: int = 0,
+                               exclude_self: bool = True, filter: Optional[AnyFilter] = None, opts=None):
+        """... into device memory: D f32 / I i64 / ord u64 [num_vectors, k], counts u64[num_vectors]; a pointer of 0 skips
+        ord / counts"""
+        _native.check(lib().vi_indexer_knn_graph_exact_device(self._h, _filter_handle(filter), self._exact_knn_opts(opts), int(k),
+                                                              1 if exclude_self else 0, C.c_void_p(D_ptr) if D_ptr else None,
+                                                              C.c_void_p(I_ptr) if I_ptr else None,
+                                                              C.c_void_p(ord_ptr) if ord_ptr else None,
+                                                              C.c_void_p(counts_ptr) if counts_ptr else None),
+                      prefix="Failed to build the exact k-NN graph: ")
+
+    def exact_knn_stats(self) -> dict:
+        """this thread's last knn_graph_exact (either form): rows, k, seed_probe, the largest grid (tiles x segments),
+        sweeps, survivors (pairs the compare let through), candidates (pool entries), unbounded_rows, pool_cap,
+        chunk_rows; the ms_* only under VI_EXACT_TIMING"""
+        st = _native.ExactKnnStats()
+        _native.check(lib().vi_exact_knn_last_stats(C.byref(st)))
         return {f: getattr(st, f) for f, _ in st._fields_}
 
     def similar_times(self) -> dict:

@@ -142,6 +142,18 @@ class ExactJoinStats(C.Structure):
                 ("ms_sweep", f32), ("ms_finish", f32)]
 
 
+class ExactKnnOpts(C.Structure):
+    """vi_exact_knn_opts"""
+    _fields_ = [("seed_probe", u64), ("pool_cap", u64)]
+
+
+class ExactKnnStats(C.Structure):
+    """vi_exact_knn_stats"""
+    _fields_ = [("rows", u64), ("k", u64), ("seed_probe", u64), ("tiles", u64), ("segments", u64), ("sweeps", u64),
+                ("survivors", u64), ("candidates", u64), ("unbounded_rows", u64), ("pool_cap", u64), ("chunk_rows", u64),
+                ("ms_seed", f32), ("ms_prepare", f32), ("ms_sweep", f32), ("ms_finish", f32)]
+
+
 class ProbeRuleC(C.Structure):
     """vi_probe_rule"""
     _fields_ = [("min_probe", u32), ("ratio2", f32), ("max_codes", u64), ("n_probe_q", vp)]
@@ -286,6 +298,10 @@ SIGNATURES = {
     "vi_indexer_cluster_radius_exact_device": (C.c_int, [vp, vp, f32, u32, vp, vp, C.POINTER(u64)]),
     "vi_indexer_radius_graph_exact": (C.c_int, [vp, vp, f32, u32, C.POINTER(ExactJoinOpts), C.POINTER(vp)]),
     "vi_exact_join_last_stats": (C.c_int, [C.POINTER(ExactJoinStats)]),
+    "vi_exact_knn_opts_init": (None, [C.POINTER(ExactKnnOpts)]),
+    "vi_indexer_knn_graph_exact": (C.c_int, [vp, vp, C.POINTER(ExactKnnOpts), u64, u32, vp, vp, vp, vp]),
+    "vi_indexer_knn_graph_exact_device": (C.c_int, [vp, vp, C.POINTER(ExactKnnOpts), u64, u32, vp, vp, vp, vp]),
+    "vi_exact_knn_last_stats": (C.c_int, [C.POINTER(ExactKnnStats)]),
 }
 
 _lib = None

@@ -20,6 +20,7 @@
     .recall_of(queries, k, n_probe, ...) -> (recall_1nn, recall_intersection)     extension: recall against search_exact
     .range_search_exact(query, radius2, ...) -> [SearchResult]                    extension: everything within a radius, whole index
     .range_recall_of(queries, radius2, n_probe) -> float                          extension: radius recall against range_search_exact
+    .knn_graph_recall(k, n_probe) -> float                                        extension: recall of the k-NN graph against the exact one
     SearchRequest.with_timestamp_range / .with_allowed_ids / .with_excluded_ids   extension: filtered search
     SearchRequest.with_probe_ratio(ratio2, min_probe=1) / .with_max_codes(n)      extension: adaptive probing
 
@@ -522,6 +523,27 @@ class VectorIndexer:
             totals.append(int(L.vi_range_result_total(h)))
             L.vi_range_result_free(h)
         return totals[0] / totals[1] if totals[1] else 1.0
+
+    def knn_graph_recall(self, k: int, n_probe: Optional[int] = None) -> float:
+        """extension: what the k-NN graph of the stored records at n_probe (None: the config's default) recalls: the share
+        of its entries, own slot excluded, that are in the rows of the exact graph (vi_indexer_knn_graph_exact), by
+        external id; 1.0 for an index without records."""
+        L, n, k = lib(), int(lib().vi_indexer_num_vectors(self._h)), int(k)
+        p = self._cfg.default_n_probe if n_probe is None else int(n_probe)
+        if n == 0:
+            return 1.0
+        Dp, Ip = np.empty((n, k), dtype=np.float32), np.full((n, k), -1, dtype=np.int64)
+        De, Ie = np.empty((n, k), dtype=np.float32), np.full((n, k), -1, dtype=np.int64)
+        kout = C.c_uint64(k)
+        _native.check(L.vi_indexer_knn_graph(self._h, None, 0, n, k, p, 1, _native.ptr(Dp), _native.ptr(Ip), None, C.byref(kout)))
+        Ip = Ip.reshape(-1)[: n * int(kout.value)].reshape(n, int(kout.value))
+        _native.check(L.vi_indexer_knn_graph_exact(self._h, None, None, k, 1, _native.ptr(De), _native.ptr(Ie), None, None))
+        found = entries = 0
+        for r0 in range(0, n, 65536):
+            a, e = Ip[r0:r0 + 65536], Ie[r0:r0 + 65536]
+            found += int(((a[:, :, None] == e[:, None, :]).any(axis=2) & (a >= 0)).sum())
+            entries += int((a >= 0).sum())
+        return found / entries if entries else 1.0
 
     def search_request(self, query) -> SearchRequest:
         return SearchRequest(list(query), False, self._cfg.default_k, self._cfg.default_n_probe)
