@@ -910,6 +910,48 @@ typedef struct vi_exact_stats {
 } vi_exact_stats;
 vi_status vi_exact_last_stats(vi_exact_stats *out);
 
+/* ---- extension: exact (flat) inner-product k-NN — the k records of the whole index with the largest q.v ---------------
+ * Every entry above scores by squared L2.  For vectors that are not normalised (recommender factors, raw embeddings) the
+ * order by inner product is another order; this call answers it: for each query the k (1..128) records with the LARGEST
+ * score over EVERY resident record (with a filter: every record the filter admits).
+ *   score:    the f32 chain  s = 0.0f; for i in 0..dimension: s = s + q[i] * v[i]  over the stored f32 values, i
+ *             ascending, the multiply and the add rounded separately (no fused multiply-add).  This chain never yields
+ *             -0.0, so equal scores have equal bits.
+ *   order:    larger score first in an f32 compare; equal scores go to the LOWER list-order ORDINAL (the row
+ *             vi_indexer_export_records gives the record): the tie rule of vi_indexer_search_exact.
+ * S is nq x k f32, descending; I nq x k external ids; ord (optional) nq x k ordinals; counts (optional) nq result counts,
+ * each skipped when NULL.  Rows with fewer than k admitted records are padded with -inf / -1 / UINT64_MAX.
+ *
+ * How: the unchanged L2 search at opts->seed_probe finds k distinct admitted records per query; the smallest of their
+ * chain scores, t_q, is a lower bound of the query's true k-th largest score whatever the seed found.  One kernel then
+ * multiplies the bf16 ranking images of ALL blocks with the images of -2 q on the matrix cores, accumulators started at
+ * zero, and keeps the records whose value can lie at or under thr_q = -2 t_q + 2 q.mu + margins (mu: the centre of the
+ * images, 0 where the index is not centred; the margins cover the chain's rounding, q.mu and the bf16 x 3 arithmetic);
+ * those are evaluated in the chain, kept if s >= t_q, sorted, cut at k.  No result depends on a rank value.  A query that
+ * cannot be bounded (fewer than k admitted hits in the seed, squared norm of 1e30 or more, a non-finite threshold) or
+ * collects more than opts->cand_cap candidates (massive ties, an all-zero query) is answered by sorting the key of every
+ * admitted record: slow and always right, so the call never fails on its data.
+ *   - opts (NULL: the defaults) is vi_exact_opts as vi_indexer_search_exact reads it and never changes a result.
+ *   - limits and errors: those of vi_indexer_search_exact, all VI_ERR_INVALID_INPUT with a message and before any device
+ *     work — k == 0 or k > 128, query_dim != dimension, a NULL queries, S or I with nq > 0, a handle without an index, a
+ *     partitioned handle, a filter of another handle, an index whose distances are not VI_ORDER_SCALAR, whose dimension
+ *     is no multiple of 4 or exceeds 1536, which holds 2^26 slots or more, or whose largest squared norm is not below
+ *     1e30.  Nothing falls to a slower path.  A non-finite query value: VI_ERR_PANIC from the host entry; the device
+ *     entry does not read the queries on the host and answers such a query through the sort-everything path.
+ *   - nq == 0: VI_OK, nothing written.  An empty index: every row padded, counts 0.
+ *   - threads: the contract of a search — const on the handle, one search context held for the whole call, must not
+ *     overlap an update.  Ordinals refer to the list order at call time. */
+vi_status vi_indexer_search_exact_ip(const vi_indexer *ix, const vi_filter *f, const vi_exact_opts *opts, const float *queries,
+                                     uint64_t nq, uint32_t query_dim, uint64_t k, float *S, int64_t *I, uint64_t *ord,
+                                     uint64_t *counts);
+vi_status vi_indexer_search_exact_ip_device(const vi_indexer *ix, const vi_filter *f, const vi_exact_opts *opts,
+                                            const float *queries_dev, uint64_t nq, uint64_t k, float *S_dev, int64_t *I_dev,
+                                            uint64_t *ord_dev, uint64_t *counts_dev);
+/* Of the calling thread's last vi_indexer_search_exact_ip (either form); zeros after a failed one.  The fields are those
+ * of vi_exact_last_stats: survivors are the (query, record) pairs the sweep evaluated in the chain, candidates those with
+ * s >= t_q, overflow_rows the queries answered by the sort-everything path; the ms_* only under VI_EXACT_TIMING. */
+vi_status vi_exact_ip_last_stats(vi_exact_stats *out);
+
 /* ---- extension: exact (flat) radius search — every record of the whole index within a distance, one dense sweep to CSR --
  * The radius entries above answer "within radius2 among the lists I probed".  This one answers "within radius2, full
  * stop": per query EVERY resident record (with a filter: every record the filter admits) whose distance d <= radius2.

@@ -13,6 +13,7 @@
 #include "flat_join.hpp"
 #include "flat_knn.hpp"
 #include "flat_range.hpp"
+#include "flat_ip.hpp"
 #include "flat_search.hpp"
 #include "index_lifecycle.hpp"
 #include "kmeans.hpp"
@@ -1148,7 +1149,7 @@ void vi_exact_opts_init(vi_exact_opts *opts) {
 
 static vi_status search_exact_common(const vi_indexer *ix, const vi_filter *f, const vi_exact_opts *opts, const float *queries,
                                      uint64_t nq, const uint32_t *query_dim, uint64_t k, bool on_device, float *D, int64_t *I,
-                                     uint64_t *ord, uint64_t *counts) {
+                                     uint64_t *ord, uint64_t *counts, bool inner_product = false) {
   return vi::guarded([&]() -> vi_status {
   if (!ix) return fail(VI_ERR_INVALID_INPUT, "null indexer");
   if (k == 0 || k > vi::kExactMaxK)  // (not clamped to max_k: the answer is exact or an error)
@@ -1173,7 +1174,7 @@ static vi_status search_exact_common(const vi_indexer *ix, const vi_filter *f, c
   if (seed) VI_TRY(search_common(ix, &one, &seed));  // (the clamp to max_n_probe)
   io.seed_probe = seed; io.cand_cap = opts ? opts->cand_cap : 0;
   io.D = D; io.I = I; io.ord = ord; io.counts = counts;
-  return vi::device_index_search_exact(*ix->impl.dev, io);
+  return inner_product ? vi::device_index_search_exact_ip(*ix->impl.dev, io) : vi::device_index_search_exact(*ix->impl.dev, io);
   });
 }
 
@@ -1193,6 +1194,27 @@ vi_status vi_exact_last_stats(vi_exact_stats *out) {
   return vi::guarded([&]() -> vi_status {
   if (!out) return fail(VI_ERR_INVALID_INPUT, "null pointer");
   *out = vi::exact_last_stats();
+  return VI_OK;
+  });
+}
+
+// ---- exact (flat) inner-product k-NN over every resident record (flat_ip.hip): the arguments of the exact search ----
+vi_status vi_indexer_search_exact_ip(const vi_indexer *ix, const vi_filter *f, const vi_exact_opts *opts, const float *queries,
+                                     uint64_t nq, uint32_t query_dim, uint64_t k, float *S, int64_t *I, uint64_t *ord,
+                                     uint64_t *counts) {
+  return search_exact_common(ix, f, opts, queries, nq, &query_dim, k, false, S, I, ord, counts, true);
+}
+
+vi_status vi_indexer_search_exact_ip_device(const vi_indexer *ix, const vi_filter *f, const vi_exact_opts *opts,
+                                            const float *queries_dev, uint64_t nq, uint64_t k, float *S_dev, int64_t *I_dev,
+                                            uint64_t *ord_dev, uint64_t *counts_dev) {
+  return search_exact_common(ix, f, opts, queries_dev, nq, nullptr, k, true, S_dev, I_dev, ord_dev, counts_dev, true);
+}
+
+vi_status vi_exact_ip_last_stats(vi_exact_stats *out) {
+  return vi::guarded([&]() -> vi_status {
+  if (!out) return fail(VI_ERR_INVALID_INPUT, "null pointer");
+  *out = vi::exact_ip_last_stats();
   return VI_OK;
   });
 }

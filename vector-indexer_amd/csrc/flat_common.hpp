@@ -1,6 +1,6 @@
 // flat_common.hpp — the device pieces the flat (exact, whole-index) calls share: flat_search.hip (k-NN),
-// flat_range.hip (radius), flat_join.hip (the radius self-join) and flat_knn.hip (the k-NN
-// self-join).  Each translation unit compiles
+// flat_range.hip (radius), flat_join.hip (the radius self-join), flat_knn.hip (the k-NN
+// self-join) and flat_ip.hip (inner-product k-NN).  Each translation unit compiles
 // its own copy (unnamed namespace): the reference chain of one pair, the rank threshold of a radius, the bf16 image of one
 // query, the per-block ordinals and the way back from an ordinal to its block.
 #pragma once
@@ -24,6 +24,19 @@ __device__ __forceinline__ float exact_scalar(const float *qrow, const float4 *x
     const float4 x = xv[(size_t)qd * kWave];
     const float4 q = *reinterpret_cast<const float4 *>(qrow + 4 * qd);
     sq_add(acc, q.x, x.x); sq_add(acc, q.y, x.y); sq_add(acc, q.z, x.z); sq_add(acc, q.w, x.w);
+  }
+  return acc;
+}
+
+// the inner product of one (query row, stored vector) pair as the exact inner-product search defines it (flat_ip.hip,
+// DESIGN §4v): s = 0; s = s + q[i] * v[i] for i ascending, multiply and add rounded separately (no fused multiply-add).
+// The chain starts at +0 and x + (-x) rounds to +0, so it never yields -0
+__device__ __forceinline__ float ip_scalar(const float *qrow, const float4 *xv, uint32_t dim) {
+  float acc = 0.0f;
+  for (uint32_t qd = 0; qd < (dim >> 2); ++qd) {
+    const float4 x = xv[(size_t)qd * kWave];
+    const float4 q = *reinterpret_cast<const float4 *>(qrow + 4 * qd);
+    acc = acc + q.x * x.x; acc = acc + q.y * x.y; acc = acc + q.z * x.z; acc = acc + q.w * x.w;
   }
   return acc;
 }

@@ -868,6 +868,44 @@ class VectorIndex:
         _native.check(lib().vi_exact_last_stats(C.byref(st)))
         return {f: getattr(st, f) for f, _ in st._fields_}
 
+    def search_exact_ip_sync(self, xq, k: int, filter: Optional[AnyFilter] = None, opts=None, with_ordinals: bool = False):
+        """extension: the k records of the WHOLE index (of the records `filter` admits) with the largest inner product
+        q.v, one dense sweep on the matrix cores -> (S f32[nq, k] descending, I i64[nq, k][, ord u64[nq, k]]).  The score
+        is the sequential f32 chain s = s + q[i] * v[i] (no fused multiply-add); equal scores go to the lower list-order
+        ordinal (the row export() gives the record); -inf / -1 / 2^64-1 padding.  k in 1..128.  opts: a dict with
+        seed_probe and / or cand_cap, which never change a result.  Unpartitioned handles only."""
+        xq = np.asarray(xq)
+        if xq.ndim != 2:
+            raise RuntimeError("Query array must be 2-dimensional")
+        if xq.shape[1] != self._dimension:
+            raise RuntimeError(f"Query dimension {xq.shape[1]} doesn't match index dimension {self._dimension}")
+        xq = np.ascontiguousarray(xq, dtype=np.float32)
+        nq, k = xq.shape[0], int(k)
+        S = np.full((nq, max(k, 0)), -np.inf, dtype=np.float32)
+        I = np.full((nq, max(k, 0)), -1, dtype=np.int64)
+        ord_ = np.full((nq, max(k, 0)), (1 << 64) - 1, dtype=np.uint64) if with_ordinals else None
+        _native.check(lib().vi_indexer_search_exact_ip(self._h, _filter_handle(filter), self._exact_opts(opts), _native.ptr(xq), nq,
+                                                       xq.shape[1], k, _native.ptr(S), _native.ptr(I), _native.ptr(ord_), None),
+                      prefix="Failed to search exactly by inner product: ")
+        return (S, I, ord_) if with_ordinals else (S, I)
+
+    def search_exact_ip_device(self, xq_ptr: int, nq: int, k: int, S_ptr: int, I_ptr: int, ord_ptr: int = 0, counts_ptr: int = 0,
+                               filter: Optional[AnyFilter] = None, opts=None):
+        """... for nq queries in device memory, into device memory: S f32[nq, k], I i64[nq, k], optionally ord u64[nq, k]
+        and counts u64[nq] (a pointer of 0 skips that output)"""
+        _native.check(lib().vi_indexer_search_exact_ip_device(self._h, _filter_handle(filter), self._exact_opts(opts),
+                                                              C.c_void_p(xq_ptr), int(nq), int(k), C.c_void_p(S_ptr), C.c_void_p(I_ptr),
+                                                              C.c_void_p(ord_ptr) if ord_ptr else None,
+                                                              C.c_void_p(counts_ptr) if counts_ptr else None),
+                      prefix="Failed to search exactly by inner product: ")
+
+    def exact_ip_stats(self) -> dict:
+        """this thread's last search_exact_ip_sync / search_exact_ip_device: the fields of exact_stats — survivors (pairs
+        evaluated in the chain), candidates (those reaching the seed's score), overflow_rows; ms_* under VI_EXACT_TIMING"""
+        st = _native.ExactStats()
+        _native.check(lib().vi_exact_ip_last_stats(C.byref(st)))
+        return {f: getattr(st, f) for f, _ in st._fields_}
+
     @staticmethod
     def _exact_range_opts(opts, radii_ptr):
         """None or a dict with pool_cap, and the address of the per-query radii (or None) -> vi_exact_range_opts or None"""

@@ -290,6 +290,9 @@ SIGNATURES = {
     "vi_indexer_search_exact": (C.c_int, [vp, vp, C.POINTER(ExactOpts), vp, u64, u32, u64, vp, vp, vp, vp]),
     "vi_indexer_search_exact_device": (C.c_int, [vp, vp, C.POINTER(ExactOpts), vp, u64, u64, vp, vp, vp, vp]),
     "vi_exact_last_stats": (C.c_int, [C.POINTER(ExactStats)]),
+    "vi_indexer_search_exact_ip": (C.c_int, [vp, vp, C.POINTER(ExactOpts), vp, u64, u32, u64, vp, vp, vp, vp]),
+    "vi_indexer_search_exact_ip_device": (C.c_int, [vp, vp, C.POINTER(ExactOpts), vp, u64, u64, vp, vp, vp, vp]),
+    "vi_exact_ip_last_stats": (C.c_int, [C.POINTER(ExactStats)]),
     "vi_exact_range_opts_init": (None, [C.POINTER(ExactRangeOpts)]),
     "vi_indexer_range_search_exact": (C.c_int, [vp, vp, C.POINTER(ExactRangeOpts), vp, u64, u32, f32, C.POINTER(vp)]),
     "vi_indexer_range_search_exact_device": (C.c_int, [vp, vp, C.POINTER(ExactRangeOpts), vp, u64, f32, C.POINTER(vp)]),

@@ -17,6 +17,7 @@
     .range_search_similar(external_id, radius2, ...) -> [SearchResult] or None    extension: ... within a radius of it
     .duplicate_groups(radius2=0.0, n_probe, min_size=2) -> [[external_id]]        extension: groups of (near-)copies
     .search_exact(req) -> [SearchResult]                                          extension: the k nearest of the whole index
+    .search_exact_ip(req) -> [SearchResult]                                       extension: the k largest inner products, whole index
     .recall_of(queries, k, n_probe, ...) -> (recall_1nn, recall_intersection)     extension: recall against search_exact
     .range_search_exact(query, radius2, ...) -> [SearchResult]                    extension: everything within a radius, whole index
     .range_recall_of(queries, radius2, n_probe) -> float                          extension: radius recall against range_search_exact
@@ -459,6 +460,23 @@ class VectorIndexer:
         if req.include_vectors and cnt[0]:
             V = {r.external_id: r.values for r in self.get_records(I[0, :int(cnt[0])]) if r is not None}
         return [SearchResult(int(I[0, j]), float(D[0, j]), V.get(int(I[0, j])) if V is not None else None)
+                for j in range(int(cnt[0]))]
+
+    def search_exact_ip(self, req: SearchRequest) -> List[SearchResult]:
+        """extension: the k records of the WHOLE index with the largest inner product with req.query (of the records req's
+        filters admit), largest first, equal scores by list order; SearchResult.distance carries the score.  req.n_probe
+        and the adaptive fields are not read.  k in 1..128."""
+        q = np.ascontiguousarray(np.asarray(req.query, dtype=np.float32).reshape(1, -1))
+        k = int(req.k)
+        S = np.full((1, max(k, 1)), -np.inf, dtype=np.float32)
+        I = np.full((1, max(k, 1)), -1, dtype=np.int64)
+        cnt = np.zeros(1, dtype=np.uint64)
+        _native.check(lib().vi_indexer_search_exact_ip(self._h, self._filter(req.timestamp_range, req.id_selector), None, _native.ptr(q),
+                                                       1, q.shape[1], k, _native.ptr(S), _native.ptr(I), None, _native.ptr(cnt)))
+        V = None
+        if req.include_vectors and cnt[0]:
+            V = {r.external_id: r.values for r in self.get_records(I[0, :int(cnt[0])]) if r is not None}
+        return [SearchResult(int(I[0, j]), float(S[0, j]), V.get(int(I[0, j])) if V is not None else None)
                 for j in range(int(cnt[0]))]
 
     def recall_of(self, queries, k: int, n_probe: Optional[int] = None, rule=None, filter=None) -> Tuple[float, float]:

@@ -170,6 +170,12 @@ class FaissStyleAdapter:
         flt = self._id_filter(allowed_ids, excluded_ids, filter)
         return self._idx.search_exact_sync(np.ascontiguousarray(xq, dtype=np.float32), k, filter=flt)
 
+    def exact_ip_search(self, xq: np.ndarray, k: int, allowed_ids=None, excluded_ids=None, filter=None):
+        """what a Faiss IndexFlatIP over the same records answers: (S, I) of the k records with the largest inner
+        product, largest first, whatever nprobe says (k <= 128)"""
+        flt = self._id_filter(allowed_ids, excluded_ids, filter)
+        return self._idx.search_exact_ip_sync(np.ascontiguousarray(xq, dtype=np.float32), k, filter=flt)
+
     def range_search(self, x: np.ndarray, thresh: float, allowed_ids=None, excluded_ids=None, filter=None):
         """Faiss's Index.range_search: (lims, D, I) — query i owns D / I[lims[i]:lims[i + 1]], squared L2 <= thresh, among
         the nprobe probed lists"""
