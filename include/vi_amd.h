@@ -1009,6 +1009,61 @@ typedef struct vi_exact_range_stats {
 } vi_exact_range_stats;
 vi_status vi_exact_range_last_stats(vi_exact_range_stats *out);
 
+/* ---- extension: exact (flat) inner-product threshold search — every record of the whole index whose score reaches a value -
+ * vi_indexer_search_exact_ip answers "the k largest q.v" and needs a bound from an L2 seed.  This one answers "every record
+ * whose q.v reaches min_score": the threshold is known before a record is read, so there is no seeding search, no
+ * cand_cap and no sort-everything path, and the cost does not depend on how the L2 and inner-product orders relate.
+ * Per query: EVERY resident record (with a filter: every record the filter admits) whose score s >= min_score.
+ *   score:    the chain of vi_indexer_search_exact_ip — s = 0.0f; s = s + q[i] * v[i], i ascending, the multiply and the
+ *             add rounded separately.  The comparison is an f32 compare, so s == min_score is inside (Faiss'
+ *             IndexFlatIP.range_search keeps s > thresh, strictly: pass nextafter(thresh, +inf) for that rule).
+ *   NaN score: the device entry can produce one from non-finite queries; it fails >= and is never a hit.
+ *   order:    rows are sorted by score descending, equal scores to the LOWER list-order ordinal: the rule of
+ *             vi_indexer_search_exact_ip
+ *   result:   an ordinary vi_range_result of the index — vi_range_result_total / _copy (V included) / _device /
+ *             _copy_device / _free work on it unchanged.  D carries the scores; tie carries the record's list-order
+ *             ordinal, the row vi_indexer_export_records gives it, so these results are not meant for
+ *             vi_range_merge_device.
+ *   min_score: NaN: VI_ERR_INVALID_INPUT; -inf: every admitted record; any other value, +inf included, is compared as it is
+ *   opts (NULL: the defaults):
+ *     min_scores optional, nq floats — host memory for the host entry, device memory for the device entry.  When set,
+ *              query q uses min_scores[q] and the scalar min_score is ignored (it may be anything).  A NaN entry gives
+ *              that query an empty row; a device array is not read back to validate it.
+ *     pool_cap capacity, in hits, of the pool the sweep appends to; 0 = max(2^22, 256 per query).  It never changes a result: a sweep
+ *              that finds more hits than the pool holds counts them all, the pool grows to the count and the sweep
+ *              runs once more.
+ * How: one wave per query forms thr_q = -2 min_score + 2 q.mu + margins (the threshold of vi_indexer_search_exact_ip with
+ * t_q = min_score) and the bf16 image of -2 q; one kernel multiplies the bf16 ranking images of ALL blocks with ALL
+ * queries on the matrix cores, accumulators started at zero, evaluates every record whose value can lie at or under thr_q
+ * in the chain and appends those with s >= min_score to a pool; the pool is scattered into CSR rows, every row sorted,
+ * scores, ids and slots resolved.  No result depends on a rank value, on the order hits arrive in or on the second sweep.
+ * A query whose magnitude the rank arithmetic cannot be trusted with (squared norm of 1e30 or more), a threshold of
+ * magnitude 1e37 or more (-inf among them) or a rank threshold that is not finite evaluates every admitted record.
+ *   - limits, errors and edge cases are those of vi_indexer_range_search_exact: VI_ERR_INVALID_INPUT with a message and
+ *     before any device work for a handle without an index, a partitioned handle (world_size > 1), a filter of another
+ *     handle, query_dim != dimension, a NULL queries with nq > 0, a NULL out, an index whose distances are not
+ *     VI_ORDER_SCALAR, whose dimension is no multiple of 4 or exceeds 1536, which holds 2^26 slots or more, or whose
+ *     largest squared norm is not below 1e30.  Nothing falls to a slower path.
+ *   - a non-finite query value: VI_ERR_PANIC from the host entry, as vi_indexer_search
+ *   - nq == 0: VI_OK, a result of no rows.  An empty index: nq empty rows.
+ *   - all or nothing: when scratch or result memory cannot be had the call fails with VI_ERR_DEVICE and *out stays NULL
+ *   - queries are processed in chunks of 65536; threads: the contract of a search — const on the handle, one search
+ *     context held for the whole call, must not overlap an update.  Ordinals refer to the list order at call time. */
+typedef struct vi_exact_ip_range_opts {
+  const float *min_scores;
+  uint64_t pool_cap;
+} vi_exact_ip_range_opts;
+void vi_exact_ip_range_opts_init(vi_exact_ip_range_opts *opts);
+vi_status vi_indexer_range_search_exact_ip(const vi_indexer *ix, const vi_filter *f, const vi_exact_ip_range_opts *opts,
+                                           const float *queries, uint64_t nq, uint32_t query_dim, float min_score,
+                                           vi_range_result **out);
+vi_status vi_indexer_range_search_exact_ip_device(const vi_indexer *ix, const vi_filter *f, const vi_exact_ip_range_opts *opts,
+                                                  const float *queries_dev, uint64_t nq, float min_score, vi_range_result **out);
+/* Of the calling thread's last vi_indexer_range_search_exact_ip (either form); zeros after a failed one.  The fields are
+ * those of vi_exact_range_last_stats: survivors are the (query, record) pairs evaluated in the chain, hits the entries of
+ * the result; the ms_* only under VI_EXACT_TIMING. */
+vi_status vi_exact_ip_range_last_stats(vi_exact_range_stats *out);
+
 /* ---- extension: exact radius graph and clustering — a symmetric self-join of the stored records on the matrix cores ----
  * vi_indexer_radius_graph and vi_indexer_cluster_radius answer over the PROBED lists.  These answer over the whole index:
  * every pair of stored records whose distance d <= radius2, each unordered pair visited once by a triangular sweep.

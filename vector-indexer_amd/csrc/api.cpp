@@ -14,6 +14,7 @@
 #include "flat_knn.hpp"
 #include "flat_range.hpp"
 #include "flat_ip.hpp"
+#include "flat_ip_range.hpp"
 #include "flat_search.hpp"
 #include "index_lifecycle.hpp"
 #include "kmeans.hpp"
@@ -1265,6 +1266,57 @@ vi_status vi_exact_range_last_stats(vi_exact_range_stats *out) {
   return vi::guarded([&]() -> vi_status {
   if (!out) return fail(VI_ERR_INVALID_INPUT, "null pointer");
   *out = vi::exact_range_last_stats();
+  return VI_OK;
+  });
+}
+
+// ---- exact (flat) inner-product threshold search over every resident record (flat_ip_range.hip) ----
+void vi_exact_ip_range_opts_init(vi_exact_ip_range_opts *opts) {
+  if (opts) *opts = vi_exact_ip_range_opts{nullptr, 0};
+}
+
+static vi_status ip_range_common(const vi_indexer *ix, const vi_filter *f, const vi_exact_ip_range_opts *opts, const float *queries,
+                                 uint64_t nq, const uint32_t *query_dim, float min_score, bool on_device, vi_range_result **out) {
+  return vi::guarded([&]() -> vi_status {
+  if (!out) return fail(VI_ERR_INVALID_INPUT, "null pointer: out is required");
+  *out = nullptr;
+  if (!ix) return fail(VI_ERR_INVALID_INPUT, "null indexer");
+  const float *min_scores = opts ? opts->min_scores : nullptr;
+  if (!min_scores && std::isnan(min_score)) return fail(VI_ERR_INVALID_INPUT, "min_score is NaN");
+  if (query_dim && *query_dim != ix->impl.cfg.dimension)
+    return fail(VI_ERR_INVALID_INPUT, "query dimension mismatch: expected %u, got %u", ix->impl.cfg.dimension, *query_dim);
+  if (nq && !queries) return fail(VI_ERR_INVALID_INPUT, "null pointer: queries are required");
+  if (!ix->impl.dev) return fail(VI_ERR_INVALID_INPUT, "the indexer holds no index (build or load it first)");
+  if (ix->impl.cfg.world_size > 1 || ix->impl.dev->stripe_world > 1)
+    return fail(VI_ERR_INVALID_INPUT, "exact inner-product threshold search needs the whole index on one handle: a partitioned handle "
+                                      "(world_size > 1) holds only its part of the records");
+  const vi::SlotFilter *flt = nullptr;
+  VI_TRY(filter_common(ix, f, &flt));
+  if (!on_device)  // NaN/Inf in a query makes partial_cmp().unwrap() panic in the reference (ivf_index.rs:215)
+    for (uint64_t i = 0; i < nq * (uint64_t)ix->impl.cfg.dimension; ++i)
+      if (!std::isfinite(queries[i])) return fail(VI_ERR_PANIC, "non-finite query value at flat index %llu", (unsigned long long)i);
+  vi::ExactIpRangeIO io;
+  io.queries = queries; io.on_device = on_device; io.nq = nq; io.min_score = min_score; io.min_scores = min_scores;
+  io.pool_cap = opts ? opts->pool_cap : 0; io.filter = flt;
+  return range_run(out, [&](vi::RangeResult *r) { return vi::device_index_range_exact_ip(*ix->impl.dev, io, r); });
+  });
+}
+
+vi_status vi_indexer_range_search_exact_ip(const vi_indexer *ix, const vi_filter *f, const vi_exact_ip_range_opts *opts,
+                                           const float *queries, uint64_t nq, uint32_t query_dim, float min_score,
+                                           vi_range_result **out) {
+  return ip_range_common(ix, f, opts, queries, nq, &query_dim, min_score, false, out);
+}
+
+vi_status vi_indexer_range_search_exact_ip_device(const vi_indexer *ix, const vi_filter *f, const vi_exact_ip_range_opts *opts,
+                                                  const float *queries_dev, uint64_t nq, float min_score, vi_range_result **out) {
+  return ip_range_common(ix, f, opts, queries_dev, nq, nullptr, min_score, true, out);
+}
+
+vi_status vi_exact_ip_range_last_stats(vi_exact_range_stats *out) {
+  return vi::guarded([&]() -> vi_status {
+  if (!out) return fail(VI_ERR_INVALID_INPUT, "null pointer");
+  *out = vi::exact_ip_range_last_stats();
   return VI_OK;
   });
 }

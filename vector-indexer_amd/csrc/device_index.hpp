@@ -141,13 +141,15 @@ struct SearchWorkspace {
   // query; the chunk's image; a host caller's radii; per block the ordinal of its first record and its records; the hit
   // pool (key, query); the rows before and after their sort; the queries whose rows are too long for the LDS sort and
   // the padded scratch those are sorted on; the cursor and the survivor count.  The exact radius join (flat_join.hip)
-  // and the exact k-NN graph (flat_knn.hip) use the same buffers, rows in place of queries: cnt / fill then span all N rows
+  // and the exact k-NN graph (flat_knn.hip) use the same buffers, rows in place of queries: cnt / fill then span all N rows.
+  // The exact inner-product threshold search (flat_ip_range.hip) has a set of its own beside them: rad holds the scores
+  // t_q, radii a host caller's min_scores, the pool's keys are ip_key
   struct FlatRangeBuffers {
     DevBuf<float> thr, rad, radii;
     DevBuf<uint32_t> cnt, fill, qimg, block_ord, block_cnt, pool_q, longq;
     DevBuf<uint64_t> pool_key, rows, pad;
     DevBuf<unsigned long long> counters;
-  } flat_range;
+  } flat_range, flat_ip_range;
 };
 
 // ---- reading records back (record_fetch.hip) ----

@@ -1,8 +1,9 @@
 // flat_common.hpp — the device pieces the flat (exact, whole-index) calls share: flat_search.hip (k-NN),
 // flat_range.hip (radius), flat_join.hip (the radius self-join), flat_knn.hip (the k-NN
-// self-join) and flat_ip.hip (inner-product k-NN).  Each translation unit compiles
-// its own copy (unnamed namespace): the reference chain of one pair, the rank threshold of a radius, the bf16 image of one
-// query, the per-block ordinals and the way back from an ordinal to its block.
+// self-join), flat_ip.hip (inner-product k-NN) and flat_ip_range.hip (inner-product threshold
+// search).  Each translation unit compiles
+// its own copy (unnamed namespace): the reference chain of one pair, the rank threshold of a radius and of a score, the
+// inner-product result key, the bf16 image of one query, the per-block ordinals and the way back from an ordinal to its block.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -52,6 +53,49 @@ __device__ __forceinline__ float radius_rank_threshold(const SelectCommon &c, co
     thr = rank_threshold(c, f, (r - f.qn) + w);
   }
   return thr;
+}
+
+// ---- inner product (flat_ip.hip, flat_ip_range.hip) ----
+// A result key: the score's bits mapped so that unsigned order is DESCENDING score order, above the record's list-order
+// ordinal: an ascending u64 sort is "score descending, ordinal ascending".  The map flips the sign bit of a non-negative
+// score and every bit of a negative one (ascending order), then complements.  ip_scalar never yields -0, so equal scores
+// have equal bits; no finite or infinite score maps to all ones, which stays "no record".
+__device__ __forceinline__ uint64_t ip_key(float s, uint32_t ordinal) {
+  const uint32_t b = __float_as_uint(s), up = (b & 0x80000000u) ? ~b : b ^ 0x80000000u;
+  return ((uint64_t)~up << 32) | ordinal;
+}
+__device__ __forceinline__ float ip_key_score(uint64_t key) {
+  const uint32_t up = ~(uint32_t)(key >> 32);
+  return __uint_as_float((up & 0x80000000u) ? up ^ 0x80000000u : ~up);
+}
+
+// one wave: q.mu and sum |q_i mu_i| of the query row against the centre of the block images (both 0 where c.mu is null)
+__device__ __forceinline__ void ip_centre_terms(const SelectCommon &c, const float *row, int lane, float &qm, float &am) {
+  qm = 0.0f; am = 0.0f;
+  if (c.mu)
+    for (uint32_t e = lane; e < c.dim; e += kWave) {
+      const float t = row[e] * c.mu[e];
+      qm += t; am += fabsf(t);
+    }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) { qm += __shfl_xor(qm, o); am += __shfl_xor(am, o); }
+}
+
+// The rank threshold of score t: thr = -2 t + 2 q.mu + margins, rounded outwards.  A record is wanted if its
+// chain score s~ >= t.  f: the frame of the query with mu = nullptr (the UNCENTRED ||q||^2 and budget E); c: the frame of
+// the block images (gamma, mu); qm, am: ip_centre_terms; vmax_raw: max ||v|| over the stored vectors, uncentred, rounded up.
+//   |s~ - q.v| <= gamma sum |q_i v_i| <= gamma ||q|| max ||v||  (gamma = (D+2)u' >= the chain's (D+1)u'), so a wanted
+//   record has -2 q.v <= -2 t + 2 gamma ||q|| max ||v||; the true swept value is p = -2 q.v' = -2 q.v + 2 q.mu;
+//   qm is q.mu within gamma sum |q_i mu_i| (am, itself within a factor 1 + gamma); the swept value is p within
+//   E = e_scale (||q||^2 (1 + gamma) + 2 max ||v'||^2): §2b's bf16 x 3 budget for an accumulator that starts at zero,
+//   the rounding of v - mu included;
+//   forming -2 t + 2 qm and adding the margin rounds three times at magnitudes <= 2 |t| + 2 |qm| + margin.
+// The caller decides what a non-finite or huge value means (no bound).
+__device__ __forceinline__ float ip_rank_threshold(const SelectCommon &c, const QueryFrame &f, float qm, float am, float vmax_raw, float t) {
+  const float qnorm = sqrtf(f.qn * (1.0f + c.gamma)) * 1.0001f;
+  const float mk = -2.0f * t + 2.0f * qm, mag = 2.0f * fabsf(t) + 2.0f * fabsf(qm);
+  const float margin = f.E + 2.0f * c.gamma * qnorm * vmax_raw + 2.02f * c.gamma * am + c.gamma * mag;
+  return mk + margin * 1.001f + 1e-30f;
 }
 
 // ---- per block: the list-order ordinal of its first record and the records it holds (1..64) ----

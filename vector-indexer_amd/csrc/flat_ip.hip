@@ -52,19 +52,6 @@ constexpr uint64_t kOverflowKeys = 1ull << 25;  // keys of one chunk of overflow
 
 enum { kCountSurvivors = 0, kCountCandidates = 1, kCounters = 2 };
 
-// A result key: the score's bits mapped so that unsigned order is DESCENDING score order, above the record's list-order
-// ordinal: an ascending u64 sort is "score descending, ordinal ascending".  The map flips the sign bit of a non-negative
-// score and every bit of a negative one (ascending order), then complements.  ip_scalar never yields -0, so equal scores
-// have equal bits; no finite or infinite score maps to all ones, which stays "no record".
-__device__ __forceinline__ uint64_t ip_key(float s, uint32_t ordinal) {
-  const uint32_t b = __float_as_uint(s), up = (b & 0x80000000u) ? ~b : b ^ 0x80000000u;
-  return ((uint64_t)~up << 32) | ordinal;
-}
-__device__ __forceinline__ float ip_key_score(uint64_t key) {
-  const uint32_t up = ~(uint32_t)(key >> 32);
-  return __uint_as_float((up & 0x80000000u) ? up ^ 0x80000000u : ~up);
-}
-
 __global__ void flat_ip_clear_kernel(uint32_t *cnt, uint32_t *ovf, uint32_t nq, unsigned long long *counters) {
   const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
   if (q < kCounters) counters[q] = 0ull;
@@ -92,12 +79,8 @@ __global__ void __launch_bounds__(256) flat_ip_prepare_kernel(IpPrepareArgs a) {
   c0.mu = nullptr;
   const QueryFrame f = query_frame<false>(c0, q, lane, nullptr, nullptr);
   const float *row = a.c.Q + (size_t)q * a.c.dim;
-  float qm = 0.0f, am = 0.0f;  // q.mu and sum |q_i mu_i|
-  if (a.c.mu)
-    for (uint32_t e = lane; e < a.c.dim; e += kWave) {
-      const float t = row[e] * a.c.mu[e];
-      qm += t; am += fabsf(t);
-    }
+  float qm, am;  // q.mu and sum |q_i mu_i|
+  ip_centre_terms(a.c, row, lane, qm, am);
   float t = INFINITY;  // the smallest chain score among the seed's hits
   bool missing = false;
   for (uint32_t i = lane; i < a.k; i += kWave) {
@@ -106,19 +89,9 @@ __global__ void __launch_bounds__(256) flat_ip_prepare_kernel(IpPrepareArgs a) {
     t = fminf(t, ip_scalar(row, a.c.blocks + (size_t)(slot >> 6) * a.c.dq * kWave + (slot & 63ull), a.c.dim));
   }
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) { qm += __shfl_xor(qm, o); am += __shfl_xor(am, o); t = fminf(t, __shfl_xor(t, o)); }
+  for (int o = 32; o > 0; o >>= 1) t = fminf(t, __shfl_xor(t, o));
   const bool bounded = !f.distrust && __ballot(missing) == 0ull && fabsf(t) < 1.0e37f;
-  // thr_q = -2 t_q + 2 q.mu + margins, rounded outwards.  A record is wanted if its chain score s~ >= t_q.
-  //   |s~ - q.v| <= gamma sum |q_i v_i| <= gamma ||q|| max ||v||  (gamma = (D+2)u' >= the chain's (D+1)u'), so a wanted
-  //   record has -2 q.v <= -2 t_q + 2 gamma ||q|| max ||v||; the true swept value is p = -2 q.v' = -2 q.v + 2 q.mu;
-  //   qm is q.mu within gamma sum |q_i mu_i| (am, itself within a factor 1 + gamma); the swept value is p within
-  //   E = e_scale (||q||^2 (1 + gamma) + 2 max ||v'||^2): §2b's bf16 x 3 budget for an accumulator that starts at zero,
-  //   the rounding of v - mu included, with the UNCENTRED ||q||^2 (f.qn, f.E of the frame without mu);
-  //   forming -2 t_q + 2 qm and adding the margin rounds three times at magnitudes <= 2 |t_q| + 2 |qm| + margin.
-  const float qnorm = sqrtf(f.qn * (1.0f + a.c.gamma)) * 1.0001f;
-  const float mk = -2.0f * t + 2.0f * qm, mag = 2.0f * fabsf(t) + 2.0f * fabsf(qm);
-  const float margin = f.E + 2.0f * a.c.gamma * qnorm * a.vmax_raw + 2.02f * a.c.gamma * am + a.c.gamma * mag;
-  const float thr = mk + margin * 1.001f + 1e-30f;
+  const float thr = ip_rank_threshold(a.c, f, qm, am, a.vmax_raw, t);  // (flat_common.hpp)
   if (lane == 0) {
     const bool ok = bounded && fabsf(thr) < 1.0e37f;  // (a NaN or huge threshold: no bound)
     a.thr[q] = ok ? thr : -INFINITY;

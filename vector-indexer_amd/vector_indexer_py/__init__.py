@@ -965,6 +965,63 @@ class VectorIndex:
         _native.check(lib().vi_exact_range_last_stats(C.byref(st)))
         return {f: getattr(st, f) for f, _ in st._fields_}
 
+    @staticmethod
+    def _exact_ip_range_opts(opts, min_scores_ptr):
+        """None or a dict with pool_cap, and the address of the per-query thresholds (or None) -> vi_exact_ip_range_opts or None"""
+        unknown = set(opts or ()) - {"pool_cap"}
+        if unknown:
+            raise TypeError(f"unknown exact-ip-range options: {sorted(unknown)}")
+        if not opts and min_scores_ptr is None:
+            return None
+        o = _native.ExactIpRangeOpts()
+        lib().vi_exact_ip_range_opts_init(C.byref(o))
+        o.min_scores, o.pool_cap = min_scores_ptr, int((opts or {}).get("pool_cap", 0))
+        return C.byref(o)
+
+    def range_search_exact_ip_sync(self, xq, min_score: float, filter: Optional[AnyFilter] = None, min_scores=None, opts=None):
+        """extension: EVERY record of the whole index (of the records `filter` admits) whose inner product q.v reaches
+        min_score (s >= min_score), one dense sweep on the matrix cores -> (lims u64[nq + 1], S f32[total], I i64[total]);
+        query q owns [lims[q], lims[q + 1]), sorted by score descending, equal scores to the lower list-order ordinal.
+        The score is the chain of search_exact_ip_sync.  min_scores: one threshold per query instead of min_score (NaN:
+        an empty row).  opts: a dict with pool_cap, which never changes a result.  Unpartitioned handles only."""
+        xq = np.asarray(xq)
+        if xq.ndim != 2:
+            raise RuntimeError("Query array must be 2-dimensional")
+        if xq.shape[1] != self._dimension:
+            raise RuntimeError(f"Query dimension {xq.shape[1]} doesn't match index dimension {self._dimension}")
+        xq = np.ascontiguousarray(xq, dtype=np.float32)
+        if min_scores is not None:
+            min_scores = np.ascontiguousarray(min_scores, dtype=np.float32).reshape(-1)
+            if min_scores.size != xq.shape[0]:
+                raise RuntimeError(f"{min_scores.size} min_scores for {xq.shape[0]} queries")
+        h = C.c_void_p()
+        _native.check(lib().vi_indexer_range_search_exact_ip(self._h, _filter_handle(filter),
+                                                             self._exact_ip_range_opts(opts, _native.ptr(min_scores)), _native.ptr(xq),
+                                                             xq.shape[0], xq.shape[1], float(min_score), C.byref(h)),
+                      prefix="Failed to range-search exactly by inner product: ")
+        res = RangeResult(self, h, xq.shape[0])
+        try:
+            return res.copy()
+        finally:
+            res.free()
+
+    def range_search_exact_ip_device(self, xq_ptr: int, nq: int, min_score: float, filter: Optional[AnyFilter] = None,
+                                     min_scores_ptr: int = 0, opts=None) -> RangeResult:
+        """... for nq queries (and, with min_scores_ptr, nq f32 thresholds) in device memory; the result stays there
+        (RangeResult): D holds the scores, tie every hit's list-order ordinal — the row export() gives the record"""
+        h = C.c_void_p()
+        _native.check(lib().vi_indexer_range_search_exact_ip_device(
+            self._h, _filter_handle(filter), self._exact_ip_range_opts(opts, C.c_void_p(min_scores_ptr) if min_scores_ptr else None),
+            C.c_void_p(xq_ptr), int(nq), float(min_score), C.byref(h)), prefix="Failed to range-search exactly by inner product: ")
+        return RangeResult(self, h, nq)
+
+    def exact_ip_range_stats(self) -> dict:
+        """this thread's last range_search_exact_ip_sync / range_search_exact_ip_device: the fields of exact_range_stats —
+        survivors (pairs evaluated in the chain), hits, sweeps (0, 1 or 2), pool_cap; the ms_* only under VI_EXACT_TIMING"""
+        st = _native.ExactRangeStats()
+        _native.check(lib().vi_exact_ip_range_last_stats(C.byref(st)))
+        return {f: getattr(st, f) for f, _ in st._fields_}
+
     def cluster_radius_exact(self, radius2: float, min_pts: int = 1, filter: Optional[AnyFilter] = None, with_degree: bool = False):
         """extension: cluster_radius over the EXACT radius graph of the whole index — no n_probe: every pair of records
         (of the records `filter` admits) within squared distance radius2 is an edge, each pair visited once by a

@@ -123,6 +123,11 @@ class ExactRangeOpts(C.Structure):
     _fields_ = [("radii", vp), ("pool_cap", u64)]
 
 
+class ExactIpRangeOpts(C.Structure):
+    """vi_exact_ip_range_opts"""
+    _fields_ = [("min_scores", vp), ("pool_cap", u64)]
+
+
 class ExactRangeStats(C.Structure):
     """vi_exact_range_stats"""
     _fields_ = [("nq", u64), ("query_tile", u64), ("block_splits", u64), ("chunks", u64), ("survivors", u64), ("hits", u64),
@@ -297,6 +302,10 @@ SIGNATURES = {
     "vi_indexer_range_search_exact": (C.c_int, [vp, vp, C.POINTER(ExactRangeOpts), vp, u64, u32, f32, C.POINTER(vp)]),
     "vi_indexer_range_search_exact_device": (C.c_int, [vp, vp, C.POINTER(ExactRangeOpts), vp, u64, f32, C.POINTER(vp)]),
     "vi_exact_range_last_stats": (C.c_int, [C.POINTER(ExactRangeStats)]),
+    "vi_exact_ip_range_opts_init": (None, [C.POINTER(ExactIpRangeOpts)]),
+    "vi_indexer_range_search_exact_ip": (C.c_int, [vp, vp, C.POINTER(ExactIpRangeOpts), vp, u64, u32, f32, C.POINTER(vp)]),
+    "vi_indexer_range_search_exact_ip_device": (C.c_int, [vp, vp, C.POINTER(ExactIpRangeOpts), vp, u64, f32, C.POINTER(vp)]),
+    "vi_exact_ip_range_last_stats": (C.c_int, [C.POINTER(ExactRangeStats)]),
     "vi_indexer_cluster_radius_exact": (C.c_int, [vp, vp, f32, u32, vp, vp, C.POINTER(u64)]),
     "vi_indexer_cluster_radius_exact_device": (C.c_int, [vp, vp, f32, u32, vp, vp, C.POINTER(u64)]),
     "vi_indexer_radius_graph_exact": (C.c_int, [vp, vp, f32, u32, C.POINTER(ExactJoinOpts), C.POINTER(vp)]),

@@ -20,6 +20,7 @@
     .search_exact_ip(req) -> [SearchResult]                                       extension: the k largest inner products, whole index
     .recall_of(queries, k, n_probe, ...) -> (recall_1nn, recall_intersection)     extension: recall against search_exact
     .range_search_exact(query, radius2, ...) -> [SearchResult]                    extension: everything within a radius, whole index
+    .range_search_exact_ip(query, min_score, ...) -> [SearchResult]               extension: every inner product >= min_score, whole index
     .range_recall_of(queries, radius2, n_probe) -> float                          extension: radius recall against range_search_exact
     .knn_graph_recall(k, n_probe) -> float                                        extension: recall of the k-NN graph against the exact one
     SearchRequest.with_timestamp_range / .with_allowed_ids / .with_excluded_ids   extension: filtered search
@@ -523,6 +524,29 @@ class VectorIndexer:
         finally:
             lib().vi_range_result_free(h)
         return [SearchResult(int(I[j]), float(D[j]), V[j].tolist() if V is not None else None) for j in range(n)]
+
+    def range_search_exact_ip(self, query, min_score: float, include_vectors: bool = False,
+                              timestamp_range: Optional[Tuple[int, int]] = None, allowed_ids=None,
+                              excluded_ids=None) -> List[SearchResult]:
+        """extension: every record of the WHOLE index whose inner product with the query reaches min_score (of the records
+        the filters admit), largest first, equal scores by list order; SearchResult.distance carries the score"""
+        if allowed_ids is not None and excluded_ids is not None:
+            raise ValueError("give allowed_ids or excluded_ids, not both")
+        selector = (IdSelector.of(allowed_ids, False) if allowed_ids is not None
+                    else IdSelector.of(excluded_ids, True) if excluded_ids is not None else None)
+        q = np.ascontiguousarray(np.asarray(query, dtype=np.float32).reshape(1, -1))
+        h = C.c_void_p()
+        _native.check(lib().vi_indexer_range_search_exact_ip(self._h, self._filter(timestamp_range, selector), None, _native.ptr(q), 1,
+                                                             q.shape[1], float(min_score), C.byref(h)))
+        try:
+            n = int(lib().vi_range_result_total(h))
+            lims = np.zeros(2, dtype=np.uint64)
+            S, I = np.zeros(n, dtype=np.float32), np.zeros(n, dtype=np.int64)
+            V = np.zeros((n, self._cfg.dimension), dtype=np.float32) if include_vectors else None
+            _native.check(lib().vi_range_result_copy(h, _native.ptr(lims), _native.ptr(S), _native.ptr(I), _native.ptr(V)))
+        finally:
+            lib().vi_range_result_free(h)
+        return [SearchResult(int(I[j]), float(S[j]), V[j].tolist() if V is not None else None) for j in range(n)]
 
     def range_recall_of(self, queries, radius2: float, n_probe: Optional[int] = None) -> float:
         """extension: what a radius search at n_probe (None: the config's default) recalls on these queries: its hits over

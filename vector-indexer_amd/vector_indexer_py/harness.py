@@ -190,6 +190,13 @@ class FaissStyleAdapter:
         flt = self._id_filter(allowed_ids, excluded_ids, filter)
         return self._idx.range_search_exact_sync(np.ascontiguousarray(x, dtype=np.float32), float(thresh), filter=flt)
 
+    def exact_ip_range_search(self, x: np.ndarray, thresh: float, allowed_ids=None, excluded_ids=None, filter=None):
+        """what a Faiss IndexFlatIP over the same records answers to range_search, with the threshold itself inside:
+        (lims, S, I) of every record with inner product >= thresh (Faiss keeps > thresh), whatever nprobe says; rows
+        sorted by score, largest first"""
+        flt = self._id_filter(allowed_ids, excluded_ids, filter)
+        return self._idx.range_search_exact_ip_sync(np.ascontiguousarray(x, dtype=np.float32), float(thresh), filter=flt)
+
     def add(self, x: np.ndarray):
         """Faiss's Index.add: the rows of x join the index with ids ntotal, ntotal + 1, ..."""
         self._idx.add(np.ascontiguousarray(x, dtype=np.float32))
