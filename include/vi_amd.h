@@ -923,7 +923,14 @@ vi_status vi_exact_last_stats(vi_exact_stats *out);
  * each skipped when NULL.  Rows with fewer than k admitted records are padded with -inf / -1 / UINT64_MAX.
  *
  * How: the unchanged L2 search at opts->seed_probe finds k distinct admitted records per query; the smallest of their
- * chain scores, t_q, is a lower bound of the query's true k-th largest score whatever the seed found.  One kernel then
+ * chain scores, t_q, is a lower bound of the query's true k-th largest score whatever the seed found.  A ladder of
+ * sampled sweeps then raises it: with r the largest power of two <= cand_cap / (2 k), clamped to [2, 4], the level of
+ * stride s multiplies the bf16 hi planes of the blocks (64 slots) whose index is 0 mod s with the hi plane of -2 q,
+ * compares without margins, evaluates the survivors in the chain and collects the scores >= t_q; the k-th largest of
+ * them, the smallest chain score of k distinct admitted records again, becomes t_q where it is larger.  Strides are
+ * r^m, ..., r^2, r, coarsest first, m the smallest with ceil(blocks / r^m) * 64 <= cand_cap or one block left (at most 8 levels; none for
+ * an index of at most cand_cap slots); a query with fewer than k seed hits can gain its bound there.  The environment
+ * variable VI_EXACT_IP_LADDER=0 skips the ladder; it never changes a result.  One kernel then
  * multiplies the bf16 ranking images of ALL blocks with the images of -2 q on the matrix cores, accumulators started at
  * zero, and keeps the records whose value can lie at or under thr_q = -2 t_q + 2 q.mu + margins (mu: the centre of the
  * images, 0 where the index is not centred; the margins cover the chain's rounding, q.mu and the bf16 x 3 arithmetic);
@@ -951,6 +958,21 @@ vi_status vi_indexer_search_exact_ip_device(const vi_indexer *ix, const vi_filte
  * of vi_exact_last_stats: survivors are the (query, record) pairs the sweep evaluated in the chain, candidates those with
  * s >= t_q, overflow_rows the queries answered by the sort-everything path; the ms_* only under VI_EXACT_TIMING. */
 vi_status vi_exact_ip_last_stats(vi_exact_stats *out);
+/* The ladder of the calling thread's last vi_indexer_search_exact_ip (either form); zeros after a failed one, and with
+ * VI_EXACT_IP_LADDER=0.  levels, ratio (r) and strides[0 .. levels), coarsest first: the schedule above.  Per level:
+ * level_survivors, the (query, record) pairs it evaluated in the chain, and level_candidates, those with s >= t_q.
+ * rows_tightened: queries whose t_q some level raised above the L2 seed's; rows_level_overflow: (query, level) pairs
+ * that met more than cand_cap such scores (the first cand_cap are kept: still distinct admitted records, so the bound
+ * they give is sound).  vi_exact_stats keeps its meaning: survivors, candidates and overflow_rows describe the final
+ * sweep only.  ms_ladder: host clock around the levels, only under VI_EXACT_TIMING, and then no part of ms_sweep. */
+typedef struct vi_exact_ip_seed_stats {
+  uint64_t levels, ratio;
+  uint64_t strides[8];
+  uint64_t level_survivors[8], level_candidates[8];
+  uint64_t rows_tightened, rows_level_overflow;
+  float ms_ladder;
+} vi_exact_ip_seed_stats;
+vi_status vi_exact_ip_seed_last_stats(vi_exact_ip_seed_stats *out);
 
 /* ---- extension: exact (flat) radius search — every record of the whole index within a distance, one dense sweep to CSR --
  * The radius entries above answer "within radius2 among the lists I probed".  This one answers "within radius2, full

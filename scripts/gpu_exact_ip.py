@@ -9,6 +9,10 @@ it) and on a norm-spread copy of it (every row scaled by a factor drawn from {0.
   * the only route before: a torch fp32 matmul + topk over the exported rows, in chunks of 131 072 rows;
   * search_exact_device (the L2 sweep of the parent) on the same handle;
   * the rows whose ids differ from the matmul's (near-ties of the matmul form), and the sweep's rate against the bf16 peak.
+With --ladder it measures the score-seeded ladder instead and writes profiles/r36_exact_ip_seed.json: on both
+data sets the call with VI_EXACT_IP_LADDER=0 (the path before the ladder) and =1 in one process, the matmul route, the
+phases (seed / ladder / sweep / finish), the schedule, per-level survivors and candidates per query against k r, the level
+overflows, the final sweep's counts and overflow rows; k = 1 and 128 on the bench data as secondary points.
 Needs an MI355X; nothing here falls back to the CPU."""
 import argparse
 import json
@@ -91,6 +95,44 @@ def measure(vip, torch, bench, xb, xq, args, dev):
     return res
 
 
+def measure_ladder(vip, torch, xb, xq, args, dev, ks):
+    sync = lambda: torch.cuda.synchronize(dev)  # noqa: E731
+    nq, res = xq.shape[0], {}
+    with tempfile.TemporaryDirectory() as work:
+        index = vip.build(xb.cpu().numpy(), work, nlist=args.nlist, now_secs=1_700_000_000)
+        n = index.num_vectors
+        rows = torch.empty((n, args.d), dtype=torch.float32, device=dev)
+        ids = torch.empty(n, dtype=torch.int64, device=dev)
+        index.export_device(0, n, ids.data_ptr(), rows.data_ptr())
+        for k in ks:
+            S = {m: torch.empty((nq, k), dtype=torch.float32, device=dev) for m in "01"}
+            I = {m: torch.empty((nq, k), dtype=torch.int64, device=dev) for m in "01"}
+            point = {}
+            for mode in "01":
+                os.environ["VI_EXACT_IP_LADDER"] = mode
+                ip = lambda: index.search_exact_ip_device(xq.data_ptr(), nq, k, S[mode].data_ptr(), I[mode].data_ptr())  # noqa: E731
+                ip()
+                r = {"ms": timed(ip, sync, args.repeats)}
+                os.environ["VI_EXACT_TIMING"] = "1"
+                ip()
+                del os.environ["VI_EXACT_TIMING"]
+                st, ss = index.exact_ip_stats(), index.exact_ip_seed_stats()
+                r["phases"] = {"ms_seed": st["ms_seed"], "ms_ladder": ss["ms_ladder"], "ms_sweep": st["ms_sweep"], "ms_finish": st["ms_finish"]}
+                r["final_sweep"] = {"survivors_per_query": st["survivors"] / nq, "candidates_per_query": st["candidates"] / nq,
+                                    "overflow_rows": st["overflow_rows"]}
+                r["ladder"] = {"levels": ss["levels"], "ratio": ss["ratio"], "strides": ss["strides"], "k_r_estimate": k * ss["ratio"],
+                               "level_survivors_per_query": [v / nq for v in ss["level_survivors"]],
+                               "level_candidates_per_query": [v / nq for v in ss["level_candidates"]],
+                               "rows_tightened": ss["rows_tightened"], "rows_level_overflow": ss["rows_level_overflow"]}
+                point["ladder_" + mode] = r
+            del os.environ["VI_EXACT_IP_LADDER"]
+            point["equal"] = bool((I["0"] == I["1"]).all().item() and (S["0"].view(torch.int32) == S["1"].view(torch.int32)).all().item())
+            matmul_topk(rows, ids, xq, k)
+            point["matmul_topk_ms"] = timed(lambda: matmul_topk(rows, ids, xq, k), sync, args.repeats)
+            res["k_%d" % k] = point
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=1_000_000)
@@ -99,8 +141,10 @@ def main():
     ap.add_argument("--nq", type=int, default=10_000)
     ap.add_argument("--k", type=int, default=10)
     ap.add_argument("--repeats", type=int, default=5)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r34_exact_ip.json"))
+    ap.add_argument("--ladder", action="store_true", help="measure the score-seeded ladder (profiles/r36_exact_ip_seed.json)")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    args.out = args.out or os.path.join(ROOT, "profiles", "r36_exact_ip_seed.json" if args.ladder else "r34_exact_ip.json")
 
     import torch
     if not torch.cuda.is_available():
@@ -111,11 +155,15 @@ def main():
     xb, xq = bench.make_dataset(args.n, args.d, args.nq, 1234, dev)
     res = {"shape": {"n": args.n, "d": args.d, "nlist": args.nlist, "nq": args.nq, "k": args.k, "repeats": args.repeats},
            "device": torch.cuda.get_device_name(0)}
-    res["bench_data"] = measure(vip, torch, bench, xb, xq, args, dev)
     g = torch.Generator(device=dev)
     g.manual_seed(99)
     factor = torch.tensor([0.25, 1.0, 4.0], device=dev)[torch.randint(0, 3, (args.n, 1), generator=g, device=dev)]
-    res["norm_spread"] = measure(vip, torch, bench, (xb * factor).contiguous(), xq, args, dev)
+    if args.ladder:
+        res["bench_data"] = measure_ladder(vip, torch, xb, xq, args, dev, [args.k, 1, 128])
+        res["norm_spread"] = measure_ladder(vip, torch, (xb * factor).contiguous(), xq, args, dev, [args.k])
+    else:
+        res["bench_data"] = measure(vip, torch, bench, xb, xq, args, dev)
+        res["norm_spread"] = measure(vip, torch, bench, (xb * factor).contiguous(), xq, args, dev)
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
     with open(args.out, "w") as f:
         json.dump(res, f, indent=1)

@@ -1220,6 +1220,14 @@ vi_status vi_exact_ip_last_stats(vi_exact_stats *out) {
   });
 }
 
+vi_status vi_exact_ip_seed_last_stats(vi_exact_ip_seed_stats *out) {
+  return vi::guarded([&]() -> vi_status {
+  if (!out) return fail(VI_ERR_INVALID_INPUT, "null pointer");
+  *out = vi::exact_ip_seed_last_stats();
+  return VI_OK;
+  });
+}
+
 // ---- exact (flat) radius search over every resident record (flat_range.hip) ----
 void vi_exact_range_opts_init(vi_exact_range_opts *opts) {
   if (opts) *opts = vi_exact_range_opts{nullptr, 0};

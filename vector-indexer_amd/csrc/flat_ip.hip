@@ -11,6 +11,9 @@
 //               records, so the k-th largest score of the index is >= t_q whatever the seed found — the rank threshold
 //               thr_q (below) and the bf16 hi / lo image of -2 q.  A query whose seed holds fewer than k records, or whose
 //               magnitude the rank arithmetic cannot be trusted with, is flagged for step 4 and skipped by the sweep.
+//   1b. ladder  ip_seed_ladder (flat_ip_seed.hip): hi-plane sweeps over nested samples of the blocks raise
+//               t_q to the k-th largest chain score each sample holds and re-form thr_q; a query with fewer than k seed
+//               hits may gain its bound there.  VI_EXACT_IP_LADDER=0 skips it; no result depends on it.
 //   2. sweep    flat_ip_sweep_kernel: the blocking of the radius sweep (§4s) — 256 threads own 128 queries and a strided
 //               share of all blocks, a wave owns one 32-column tile, B fragments (hi and lo) in registers for the whole
 //               sweep at D <= 128, block images by LDS-DMA into two buffers, bf16 x 3 on v_mfma_f32_32x32x16_bf16 — with
@@ -34,6 +37,7 @@
 #include "device_index.hpp"
 #include "flat_common.hpp"
 #include "flat_ip.hpp"
+#include "flat_ip_seed.hpp"
 #include "mfma_bf16.hpp"
 #include "record_fetch.hpp"
 #include "search_internal.hpp"
@@ -51,10 +55,11 @@ constexpr uint64_t kNoKey = ~0ull;
 constexpr uint64_t kOverflowKeys = 1ull << 25;  // keys of one chunk of overflow rows (256 MB)
 
 enum { kCountSurvivors = 0, kCountCandidates = 1, kCounters = 2 };
+constexpr uint32_t kAllCounters = kCounters + kIpSeedCounters;  // the final sweep's, then the ladder's (flat_ip_seed.hpp)
 
 __global__ void flat_ip_clear_kernel(uint32_t *cnt, uint32_t *ovf, uint32_t nq, unsigned long long *counters) {
   const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
-  if (q < kCounters) counters[q] = 0ull;
+  if (q < kAllCounters) counters[q] = 0ull;
   if (q < nq) { cnt[q] = 0u; ovf[q] = 0u; }
 }
 
@@ -64,7 +69,7 @@ struct IpPrepareArgs {
   const uint64_t *seed_slots; // [nq][k] global slots of the seed's hits, all ones where it found none
   float vmax_raw;             // max ||v|| over the stored vectors, uncentred (rounded up): the chain's own rounding
   uint32_t nq, k, nc;
-  float *thr, *tq;
+  IpQueryTerms t;             // the bound, both thresholds and the frame terms the ladder re-forms them from
   uint32_t *cnt, *ovf;
   uint4 *qimg;  // [query][plane hi / lo][chunk][half] x 16 B of -2 q: the layout of split_query_image, not centred
   unsigned long long *counters;
@@ -73,7 +78,7 @@ struct IpPrepareArgs {
 __global__ void __launch_bounds__(256) flat_ip_prepare_kernel(IpPrepareArgs a) {
   const int lane = threadIdx.x & (kWave - 1);
   const uint32_t q = blockIdx.x * 4u + (threadIdx.x >> 6);
-  if (blockIdx.x == 0 && threadIdx.x < kCounters) a.counters[threadIdx.x] = 0ull;
+  if (blockIdx.x == 0 && threadIdx.x < kAllCounters) a.counters[threadIdx.x] = 0ull;
   if (q >= a.nq) return;
   SelectCommon c0 = a.c;  // the query as it is: ||q||^2, its image and the budget E all live in the uncentred frame
   c0.mu = nullptr;
@@ -94,8 +99,12 @@ __global__ void __launch_bounds__(256) flat_ip_prepare_kernel(IpPrepareArgs a) {
   const float thr = ip_rank_threshold(a.c, f, qm, am, a.vmax_raw, t);  // (flat_common.hpp)
   if (lane == 0) {
     const bool ok = bounded && fabsf(thr) < 1.0e37f;  // (a NaN or huge threshold: no bound)
-    a.thr[q] = ok ? thr : -INFINITY;
-    a.tq[q] = ok ? t : -INFINITY;
+    a.t.thr[q] = ok ? thr : -INFINITY;
+    a.t.tq[q] = a.t.t0[q] = ok ? t : -INFINITY;
+    // the sampled levels compare without margins; a query without a bound admits everything there and may gain one,
+    // unless its magnitude is distrusted
+    a.t.sthr[q] = f.distrust ? -INFINITY : (ok ? -2.0f * t + 2.0f * qm : INFINITY);
+    a.t.qn[q] = f.qn; a.t.E[q] = f.E; a.t.qm[q] = qm; a.t.am[q] = am;
     a.cnt[q] = 0u;
     a.ovf[q] = ok ? 0u : 1u;
   }
@@ -363,6 +372,7 @@ __global__ void __launch_bounds__(64) flat_ip_take_kernel(IpOutArgs o, const uin
 }
 
 thread_local vi_exact_stats g_last_stats{};
+thread_local vi_exact_ip_seed_stats g_last_seed_stats{};
 
 vi_status exact_ip_in_context(const DeviceIndex &ix, SearchContext &ctx, const ExactIO &io) {
   SearchWorkspace &ws = ctx.ws;
@@ -372,7 +382,10 @@ vi_status exact_ip_in_context(const DeviceIndex &ix, SearchContext &ctx, const E
   const uint32_t dim = ix.dim, nc = ix.dq / 4, nblocks = (uint32_t)ix.lists.nblocks;
   const char *te = getenv("VI_EXACT_TIMING");
   const bool timing = te && *te != '0';
+  const char *le = getenv("VI_EXACT_IP_LADDER");
+  const bool ladder = !(le && *le == '0');
   vi_exact_stats es{};
+  vi_exact_ip_seed_stats ss{};
   es.nq = nq; es.k = k; es.query_tile = kTileQ;
   es.cand_cap = exact_cand_cap(io.cand_cap, k);
   es.seed_probe = std::min<uint64_t>(io.seed_probe ? io.seed_probe : kExactSeedProbe, std::max<uint64_t>(1, ix.nlists));
@@ -399,8 +412,8 @@ vi_status exact_ip_in_context(const DeviceIndex &ix, SearchContext &ctx, const E
   VI_TRY(fw.cnt.reserve(nq));
   VI_TRY(fw.ovf.reserve(nq));
   VI_TRY(fw.cand.reserve(nq * cap));
-  VI_TRY(fw.counters.reserve(kCounters));
-  const dim3 per_query((uint32_t)((std::max<uint64_t>(nq, kCounters) + 255) / 256)), per_wave((uint32_t)((nq + 3) / 4));
+  VI_TRY(fw.counters.reserve(kAllCounters));
+  const dim3 per_query((uint32_t)((std::max<uint64_t>(nq, kAllCounters) + 255) / 256)), per_wave((uint32_t)((nq + 3) / 4));
   std::vector<uint32_t> h_ovf(nq, 0u);
 
   const bool empty = ix.nlists == 0 || ix.nvec_resident == 0 || nblocks == 0;
@@ -424,7 +437,7 @@ vi_status exact_ip_in_context(const DeviceIndex &ix, SearchContext &ctx, const E
     VI_TRY(ensure_fetch_layout(ix, st));
     VI_TRY(fw.block_ord.reserve(nblocks));
     VI_TRY(fw.block_cnt.reserve(nblocks));
-    VI_TRY(fw.thr.reserve(2 * nq));  // the thresholds, the scores t_q behind them
+    VI_TRY(fw.thr.reserve(IpQueryTerms::kArrays * nq));  // the thresholds, the scores t_q and the frame terms behind them
     VI_TRY(fw.qimg.reserve(nq * nc * 16));
     hipLaunchKernelGGL(flat_blocks_kernel, dim3((nblocks + 255) / 256), dim3(256), 0, st, ix.list_first_block.p, ix.list_len.p,
                        ix.fetch.prefix.p, (uint32_t)ix.nlists, nblocks, fw.block_ord.p, fw.block_cnt.p);
@@ -435,20 +448,35 @@ vi_status exact_ip_in_context(const DeviceIndex &ix, SearchContext &ctx, const E
     b.kn.rank_bf16 = true; b.kn.stats = false;
     b.Qd = Qd; b.nq = nq;
     const SelectCommon c = select_common(b, (const float4 *)ix.lists.blocks.p, ix.centered ? ix.xmax2_c : ix.xmax2, kTileQ);
-    float *tq = fw.thr.p + nq;
-    IpPrepareArgs pa{c, ws.slots.p, (float)(std::sqrt((double)ix.xmax2) * 1.0001), (uint32_t)nq, (uint32_t)k, nc,
-                     fw.thr.p, tq, fw.cnt.p, fw.ovf.p, (uint4 *)fw.qimg.p, fw.counters.p};
+    const IpQueryTerms terms = IpQueryTerms::at(fw.thr.p, nq);
+    const float *tq = terms.tq;
+    const float vmax_raw = (float)(std::sqrt((double)ix.xmax2) * 1.0001);
+    IpPrepareArgs pa{c, ws.slots.p, vmax_raw, (uint32_t)nq, (uint32_t)k, nc, terms, fw.cnt.p, fw.ovf.p, (uint4 *)fw.qimg.p, fw.counters.p};
     hipLaunchKernelGGL(flat_ip_prepare_kernel, per_wave, dim3(256), 0, st, pa);
     VI_HIP(hipGetLastError());
 
     int cus = 0;
     VI_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ix.device));
+    const uint64_t *allow = io.filter ? io.filter->allow.p : nullptr;
+
+    // ---- 1b. the ladder: sampled hi-plane sweeps raise t_q before the sweep that has to be sound ----
+    if (ladder) {
+      const IpSeedSchedule sched = ip_seed_schedule(nblocks, cap, k);
+      ss.levels = sched.levels; ss.ratio = sched.ratio;
+      for (uint32_t l = 0; l < sched.levels; ++l) ss.strides[l] = sched.strides[l];
+      double tl = 0.0;
+      if (timing) { VI_HIP(hipStreamSynchronize(st)); tl = now_ms(); }
+      IpLadderArgs la{c, vmax_raw, (const uint4 *)ix.lists_bf16.p, (const uint4 *)fw.qimg.p, fw.block_cnt.p, allow, terms, fw.cnt.p,
+                      fw.ovf.p, (uint32_t *)fw.cand.p, fw.counters.p + kCounters, (uint32_t)nq, (uint32_t)k, nc, nblocks, cap, cus};
+      VI_TRY(ip_seed_ladder(la, sched, st));
+      if (timing) { VI_HIP(hipStreamSynchronize(st)); ss.ms_ladder = (float)(now_ms() - tl); }
+    }
     const uint32_t ntiles = (uint32_t)((nq + kTileQ - 1) / kTileQ);
     // two workgroups per CU at a time: two rounds of them, so that the tail of the grid is short
     const uint32_t nsplit = std::min<uint32_t>(nblocks, std::max<uint32_t>(1u, (4u * (uint32_t)std::max(cus, 1) + ntiles - 1) / ntiles));
     es.block_splits = nsplit;
     IpSweepArgs sa{(const uint4 *)ix.lists_bf16.p, (const uint4 *)fw.qimg.p, (const float4 *)ix.lists.blocks.p, Qd,
-                   fw.block_ord.p, fw.block_cnt.p, io.filter ? io.filter->allow.p : nullptr, fw.thr.p, tq, fw.cnt.p, fw.ovf.p,
+                   fw.block_ord.p, fw.block_cnt.p, allow, terms.thr, tq, fw.cnt.p, fw.ovf.p,
                    fw.cand.p, fw.counters.p, (uint32_t)nq, dim, ix.dq, nc, nblocks, nsplit, cap, ix.lists_lo_zero ? 0u : 1u};
     const bool resident = dim <= kNarrowDim;
     const int lds = (int)(ip_lds_words(resident, nc) * 16u);
@@ -460,7 +488,7 @@ vi_status exact_ip_in_context(const DeviceIndex &ix, SearchContext &ctx, const E
     VI_HIP(hipGetLastError());
     if (timing) {
       VI_HIP(hipStreamSynchronize(st));
-      es.ms_sweep = (float)(now_ms() - t1);
+      es.ms_sweep = (float)(now_ms() - t1) - ss.ms_ladder;
     }
     t2 = now_ms();
 
@@ -497,7 +525,7 @@ vi_status exact_ip_in_context(const DeviceIndex &ix, SearchContext &ctx, const E
     return fail(VI_ERR_DEVICE, "cannot reserve %d bytes of LDS for the exact inner-product search's sort", lds_finish);
   hipLaunchKernelGGL(flat_ip_finish_kernel, dim3((uint32_t)nq), dim3(64), lds_finish, st, o, (const uint64_t *)fw.cand.p, fw.cnt.p, fw.ovf.p, cap, fw.counters.p);
   VI_HIP(hipGetLastError());
-  unsigned long long h_count[kCounters] = {};
+  unsigned long long h_count[kAllCounters] = {};
   VI_HIP(hipMemcpyAsync(h_count, fw.counters.p, sizeof(h_count), hipMemcpyDeviceToHost, st));
   if (!io.on_device) {
     VI_HIP(hipMemcpyAsync(io.D, o.S, nq * k * sizeof(float), hipMemcpyDeviceToHost, st));
@@ -508,19 +536,28 @@ vi_status exact_ip_in_context(const DeviceIndex &ix, SearchContext &ctx, const E
   VI_HIP(hipStreamSynchronize(st));
   es.survivors = h_count[kCountSurvivors];
   es.candidates = h_count[kCountCandidates];
+  for (uint32_t l = 0; l < ss.levels; ++l) {
+    ss.level_survivors[l] = h_count[kCounters + kSeedCountSurvivors + l];
+    ss.level_candidates[l] = h_count[kCounters + kSeedCountCandidates + l];
+  }
+  ss.rows_tightened = h_count[kCounters + kSeedCountTightened];
+  ss.rows_level_overflow = h_count[kCounters + kSeedCountLevelOverflow];
   const double t3 = now_ms();
   es.ms_finish = timing ? (float)(t3 - t2) : 0.0f;
   es.ms_total = timing ? (float)(t3 - t0) : 0.0f;
   g_last_stats = es;
+  g_last_seed_stats = ss;
   return VI_OK;
 }
 
 }  // namespace
 
 vi_exact_stats exact_ip_last_stats() { return g_last_stats; }
+vi_exact_ip_seed_stats exact_ip_seed_last_stats() { return g_last_seed_stats; }
 
 vi_status device_index_search_exact_ip(const DeviceIndex &ix, const ExactIO &io) {
   g_last_stats = vi_exact_stats{};
+  g_last_seed_stats = vi_exact_ip_seed_stats{};
   if (io.nq == 0) return VI_OK;
   // the limits of the exact L2 search (§4r): VI_ERR_INVALID_INPUT before any device work, never a slower path
   if (ix.stripe_world > 1) return fail(VI_ERR_INVALID_INPUT, "exact inner-product search needs the whole index on one handle");

@@ -11,5 +11,6 @@ namespace vi {
 
 vi_status device_index_search_exact_ip(const DeviceIndex &ix, const ExactIO &io);
 vi_exact_stats exact_ip_last_stats();  // of this thread's last device_index_search_exact_ip; zeros after a failed one
+vi_exact_ip_seed_stats exact_ip_seed_last_stats();  // ... and of its ladder (flat_ip_seed.hip); zeros after a failed one
 
 }  // namespace vi

@@ -906,6 +906,17 @@ class VectorIndex:
         _native.check(lib().vi_exact_ip_last_stats(C.byref(st)))
         return {f: getattr(st, f) for f, _ in st._fields_}
 
+    def exact_ip_seed_stats(self) -> dict:
+        """the ladder of this thread's last search_exact_ip_sync / search_exact_ip_device: levels, ratio, and per level
+        (coarsest first, lists of length levels) strides, level_survivors, level_candidates; rows_tightened,
+        rows_level_overflow; ms_ladder under VI_EXACT_TIMING.  levels is 0 with VI_EXACT_IP_LADDER=0"""
+        st = _native.ExactIpSeedStats()
+        _native.check(lib().vi_exact_ip_seed_last_stats(C.byref(st)))
+        out = {f: getattr(st, f) for f, _ in st._fields_}
+        for f in ("strides", "level_survivors", "level_candidates"):
+            out[f] = list(out[f])[:st.levels]
+        return out
+
     @staticmethod
     def _exact_range_opts(opts, radii_ptr):
         """None or a dict with pool_cap, and the address of the per-query radii (or None) -> vi_exact_range_opts or None"""

@@ -118,6 +118,12 @@ class ExactStats(C.Structure):
                 ("ms_finish", f32), ("ms_total", f32)]
 
 
+class ExactIpSeedStats(C.Structure):
+    """vi_exact_ip_seed_stats"""
+    _fields_ = [("levels", u64), ("ratio", u64), ("strides", u64 * 8), ("level_survivors", u64 * 8), ("level_candidates", u64 * 8),
+                ("rows_tightened", u64), ("rows_level_overflow", u64), ("ms_ladder", f32)]
+
+
 class ExactRangeOpts(C.Structure):
     """vi_exact_range_opts"""
     _fields_ = [("radii", vp), ("pool_cap", u64)]
@@ -298,6 +304,7 @@ SIGNATURES = {
     "vi_indexer_search_exact_ip": (C.c_int, [vp, vp, C.POINTER(ExactOpts), vp, u64, u32, u64, vp, vp, vp, vp]),
     "vi_indexer_search_exact_ip_device": (C.c_int, [vp, vp, C.POINTER(ExactOpts), vp, u64, u64, vp, vp, vp, vp]),
     "vi_exact_ip_last_stats": (C.c_int, [C.POINTER(ExactStats)]),
+    "vi_exact_ip_seed_last_stats": (C.c_int, [C.POINTER(ExactIpSeedStats)]),
     "vi_exact_range_opts_init": (None, [C.POINTER(ExactRangeOpts)]),
     "vi_indexer_range_search_exact": (C.c_int, [vp, vp, C.POINTER(ExactRangeOpts), vp, u64, u32, f32, C.POINTER(vp)]),
     "vi_indexer_range_search_exact_device": (C.c_int, [vp, vp, C.POINTER(ExactRangeOpts), vp, u64, f32, C.POINTER(vp)]),
