@@ -898,6 +898,10 @@ vi_status vi_indexer_search_exact_device(const vi_indexer *ix, const vi_filter *
                                          uint64_t *ord_dev, uint64_t *counts_dev);
 /* Of the calling thread's last vi_indexer_search_exact (either form); zeros after a failed one.  seed_probe / cand_cap:
  * the values used.  query_tile x block_splits: the sweep's grid (queries per workgroup; workgroups sharing the blocks).
+ * The environment variable VI_EXACT_BLOCK_SPLITS=n (n >= 1, read on every call; unset, empty, 0 or no number: no cap)
+ * lowers block_splits to min(automatic choice, n) in vi_indexer_search_exact, vi_indexer_range_search_exact,
+ * vi_indexer_search_exact_ip (its ladder's levels too) and vi_indexer_range_search_exact_ip: a tuning and test knob —
+ * fewer splits make a workgroup walk more blocks — that never changes a result.
  * survivors: (query, record) pairs the sweep evaluated exactly; candidates: those it kept under the bound;
  * overflow_rows: queries answered by the sort-everything path.  The ms_* are taken only while the environment variable
  * VI_EXACT_TIMING is set (and not "0"), which adds a synchronisation per phase: host clock around the seeding search,

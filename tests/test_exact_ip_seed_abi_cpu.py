@@ -3,6 +3,7 @@ libvi_amd.so with the prototype and the struct include/vi_amd.h documents, refus
 thread that has searched nothing.  (Loading the library needs no GPU.)"""
 import ctypes as C
 import os
+import threading
 
 import vector_indexer_py as vip
 from vector_indexer_py import _native as N
@@ -23,6 +24,9 @@ def test_the_symbol_resolves_and_the_header_declares_it_verbatim():
     assert C.sizeof(N.ExactIpSeedStats) == 8 * (2 + 3 * 8 + 2) + 8      # (the float, padded to the struct's alignment)
     assert C.sizeof(N.ExactOpts) == 16                                   # (vi_exact_opts did not grow)
     assert L.vi_exact_ip_seed_last_stats(None) == N.VI_ERR_INVALID_INPUT and b"null pointer" in L.vi_last_error()
-    st = N.ExactIpSeedStats(levels=7)
-    assert L.vi_exact_ip_seed_last_stats(C.byref(st)) == N.VI_OK and st.levels == 0 and st.ms_ladder == 0.0
+    st, rc = N.ExactIpSeedStats(levels=7), []
+    fresh = threading.Thread(target=lambda: rc.append(L.vi_exact_ip_seed_last_stats(C.byref(st))))
+    fresh.start()      # (the stats are per thread, and this one may have searched in an earlier GPU test of the run)
+    fresh.join()
+    assert rc == [N.VI_OK] and st.levels == 0 and st.ms_ladder == 0.0
     assert callable(vip.VectorIndex.exact_ip_seed_stats)

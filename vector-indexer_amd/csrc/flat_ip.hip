@@ -473,7 +473,7 @@ vi_status exact_ip_in_context(const DeviceIndex &ix, SearchContext &ctx, const E
     }
     const uint32_t ntiles = (uint32_t)((nq + kTileQ - 1) / kTileQ);
     // two workgroups per CU at a time: two rounds of them, so that the tail of the grid is short
-    const uint32_t nsplit = std::min<uint32_t>(nblocks, std::max<uint32_t>(1u, (4u * (uint32_t)std::max(cus, 1) + ntiles - 1) / ntiles));
+    const uint32_t nsplit = exact_block_splits(4u, cus, ntiles, nblocks);
     es.block_splits = nsplit;
     IpSweepArgs sa{(const uint4 *)ix.lists_bf16.p, (const uint4 *)fw.qimg.p, (const float4 *)ix.lists.blocks.p, Qd,
                    fw.block_ord.p, fw.block_cnt.p, allow, terms.thr, tq, fw.cnt.p, fw.ovf.p,

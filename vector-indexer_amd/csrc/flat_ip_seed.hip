@@ -41,6 +41,7 @@
 #include "device_index.hpp"
 #include "flat_common.hpp"
 #include "flat_ip_seed.hpp"
+#include "flat_search.hpp"
 #include "mfma_bf16.hpp"
 #include "wave_sort.hpp"
 
@@ -302,7 +303,7 @@ vi_status ip_seed_ladder(const IpLadderArgs &a, const IpSeedSchedule &s, hipStre
   for (uint32_t l = 0; l < s.levels; ++l) {
     const uint32_t stride = s.strides[l], nsample = (a.nblocks + stride - 1) / stride;
     // three workgroups per CU at a time (144 VGPRs): two rounds of them where the sample has the blocks for it
-    const uint32_t nsplit = std::min<uint32_t>(nsample, std::max<uint32_t>(1u, (6u * (uint32_t)std::max(a.cus, 1) + ntiles - 1) / ntiles));
+    const uint32_t nsplit = exact_block_splits(6u, a.cus, ntiles, nsample);
     IpSeedArgs sa{a.img, a.qimg, a.c.blocks, a.c.Q, a.block_cnt, a.allow, a.t.sthr, a.t.tq, a.cnt, a.keys,
                   a.counters + kSeedCountSurvivors + l, a.nq, a.c.dim, a.c.dq, a.nc, nsample, stride, nsplit, a.cap};
     if (resident) hipLaunchKernelGGL(flat_ip_seed_kernel<true>, dim3(ntiles, nsplit), dim3(256), lds, st, sa);

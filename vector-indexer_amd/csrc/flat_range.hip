@@ -28,6 +28,7 @@
 #include "flat_common.hpp"
 #include "flat_range.hpp"
 #include "flat_rows.hpp"
+#include "flat_search.hpp"
 #include "mfma_bf16.hpp"
 #include "record_fetch.hpp"
 #include "search_internal.hpp"
@@ -386,7 +387,7 @@ vi_status range_exact_in_context(const DeviceIndex &ix, SearchContext &ctx, cons
     uint64_t cap = exact_range_pool_cap(io.pool_cap, m);
     const uint32_t ntiles = (uint32_t)((m + kTileQ - 1) / kTileQ);
     // two workgroups per CU at a time: two rounds of them, so that the tail of the grid is short
-    const uint32_t nsplit = std::min<uint32_t>(nblocks, std::max<uint32_t>(1u, (4u * (uint32_t)std::max(cus, 1) + ntiles - 1) / ntiles));
+    const uint32_t nsplit = exact_block_splits(4u, cus, ntiles, nblocks);
     es.block_splits = nsplit;
     unsigned long long h_count[kCounters] = {};
     for (uint32_t sweep = 1; sweep <= 2; ++sweep) {

@@ -397,7 +397,7 @@ vi_status exact_in_context(const DeviceIndex &ix, SearchContext &ctx, const Exac
     VI_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ix.device));
     const uint32_t ntiles = (uint32_t)((nq + kTileQ - 1) / kTileQ);
     // one workgroup per CU at a time (LDS): two rounds of them, so that the tail of the grid is short
-    const uint32_t nsplit = std::min<uint32_t>(nblocks, std::max<uint32_t>(1u, (2u * (uint32_t)std::max(cus, 1) + ntiles - 1) / ntiles));
+    const uint32_t nsplit = exact_block_splits(2u, cus, ntiles, nblocks);
     es.block_splits = nsplit;
     SweepArgs sa{(const uint4 *)ix.lists_bf16.p, io.filter ? io.filter->xnorm_img.p : ix.xnorm_img.p, (const uint4 *)fw.qimg.p,
                  (const float4 *)ix.lists.blocks.p, Qd, fw.block_ord.p, fw.block_cnt.p, io.filter ? io.filter->allow.p : nullptr,

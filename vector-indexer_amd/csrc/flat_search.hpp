@@ -4,6 +4,7 @@
 // here, before any device work.
 #pragma once
 #include <cstdint>
+#include <cstdlib>
 
 #include "common.hpp"
 
@@ -23,6 +24,21 @@ inline uint64_t exact_key(uint32_t dist_bits, uint32_t ordinal) { return ((uint6
 inline uint64_t exact_cand_cap(uint64_t asked, uint64_t k) {
   const uint64_t cap = asked ? (asked < k ? k : asked) : (8 * k < 1024 ? 1024 : 8 * k);
   return cap < kExactMaxCap ? cap : kExactMaxCap;
+}
+// workgroups that share one query tile's `nwork` blocks in a query-side sweep (the grid's y): `rounds` workgroups per CU
+// over the tiles, each walking the blocks split, split + nsplit, ...  VI_EXACT_BLOCK_SPLITS=n (n >= 1, read on every
+// call) caps the count — a tuning and test knob: fewer splits are longer walks.  Unset, empty, 0 or no number: no cap.
+// No result depends on it.
+inline uint32_t exact_block_splits(uint32_t rounds, int cus, uint32_t ntiles, uint32_t nwork) {
+  const uint32_t fill = (rounds * (uint32_t)(cus > 1 ? cus : 1) + ntiles - 1) / ntiles;
+  uint32_t nsplit = nwork < fill ? nwork : fill;  // (fill >= 1)
+  if (const char *e = getenv("VI_EXACT_BLOCK_SPLITS")) {
+    uint64_t n = 0;
+    const char *p = e;
+    for (; *p >= '0' && *p <= '9'; ++p) n = n < (1ull << 32) ? n * 10 + (uint64_t)(*p - '0') : n;
+    if (p != e && *p == '\0' && n >= 1 && n < nsplit) nsplit = (uint32_t)n;
+  }
+  return nsplit;
 }
 
 struct ExactIO {
